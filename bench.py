@@ -8,7 +8,9 @@ processes its own shard of the batch -- the path has no data-path collective -- 
 communication is the final gather of the stixel outputs to rank 0 over RCCL, inside the timed
 region.  Rank 0 prints ONE JSON line.
 
-    python bench.py [--gpus N --steps K --warmup W] [--batch B] [--preset drn_d_22_unary]
+    python bench.py [--gpus N --steps K --warmup W] [--batch B] [--preset drn_d_22_unary] [--dump-outputs DIR]
+
+The timed region is exactly K steps after W untimed ones; ms_per_step is its wall time / K.
 
 stdout carries ONE compact JSON line (< 4 KB: compact_line()); the complete object (per-kernel times,
 timed blocks, every oracle check, the --full sweeps) goes to bench_full.json next to this file (and
@@ -91,9 +93,12 @@ def parse():
     ap.add_argument("--no-variants", action="store_true",
                     help="(kept for old command lines: the sweeps only run with --full) also skips the "
                          "pruning-off / floor-family figures of the default run")
-    ap.add_argument("--min-seconds", type=float, default=1.0,
-                    help="repeat the timed K-step block until this much time has been measured; "
-                         "the MEDIAN block is reported")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the timed K-step block until this much time has been measured and report the "
+                         "MEDIAN block (default 0: one block, i.e. exactly --steps timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the Section arrays of the last timed step as float32 .npy files into DIR "
+                         "(at most 64 MB: a fixed, seeded sample of the batch's images when the batch is larger)")
     return ap.parse_args()
 
 
@@ -772,6 +777,41 @@ def measure_variants(args, wl, dev, local_rank):
 COMPACT_LIMIT = 4096   # bytes of the stdout line (the driver keeps a bounded tail of stdout)
 
 
+DUMP_LIMIT = 64 << 20          # bytes of all --dump-outputs files together
+
+
+def dump_outputs(wl, d_sections, out_dir):
+    """--dump-outputs DIR: the Section arrays a caller of the timed path receives, from its last timed step, as
+    float32 .npy files (one per Section field, [images][columns][max_sections]; every int32 field is exact in
+    float32).  Entries behind a column's terminator (type -1) are unspecified by the format and written as 0.
+    When the batch does not fit into DUMP_LIMIT, a fixed sample of its images (numpy seed 0) is written;
+    images.npy holds their indices in the batch, stixels_per_column.npy each column's number of sections."""
+    from instance_stixels_amd.config import SECTION_DTYPE
+    B, C, S = wl.B, wl.C, wl.S
+    names = SECTION_DTYPE.names
+    per_image = C * S * len(names) * 4 + C * 4 + 8
+    k = min(B, (DUMP_LIMIT - 4096 * (len(names) + 2)) // per_image)
+    if k < 1:
+        raise SystemExit(f"bench.py --dump-outputs: one image's output is larger than {DUMP_LIMIT} bytes")
+    images = np.arange(B) if k == B else np.sort(np.random.default_rng(0).choice(B, k, replace=False))
+    idx = wl.torch.tensor(images, dtype=wl.torch.int64, device=d_sections.device)
+    rec = d_sections[idx].cpu().numpy().view(SECTION_DTYPE).reshape(k, C, S)
+    term = rec["type"] == -1
+    n = np.where(term.any(-1), np.argmax(term, -1), S - 1)
+    valid = np.arange(S) <= n[..., None]
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {f"sections_{f}": np.where(valid, rec[f].astype(np.float32), np.float32(0)) for f in names}
+    arrays["stixels_per_column"] = n.astype(np.float32)
+    arrays["images"] = images.astype(np.float64)
+    total = 0
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, np.ascontiguousarray(a))
+        total += os.path.getsize(path)
+    assert total <= DUMP_LIMIT, total
+    return {"dir": out_dir, "files": sorted(arrays), "images": [int(i) for i in images], "bytes": total}
+
+
 def _r(x, nd=3):
     return round(x, nd) if isinstance(x, float) else x
 
@@ -981,9 +1021,9 @@ def main():
             d = float(t.item())
         return d
 
-    # the K-step block is repeated until --min-seconds have been measured (every rank sees the
-    # same max-reduced times, so all ranks stop together) and the MEDIAN block is reported: a
-    # 0.1 s measurement is over before a power / utilisation sampler sees the GPU busy
+    # one K-step block by default; with --min-seconds S the block is repeated until S seconds have been
+    # measured (every rank sees the same max-reduced times, so all ranks stop together) and the MEDIAN
+    # block is reported
     blocks = []
     while not blocks or (sum(blocks) < args.min_seconds and len(blocks) < 200):
         blocks.append(timed_block())
@@ -993,6 +1033,8 @@ def main():
     kt = {k: float(np.mean([b[k] for b in kt_blocks])) for k in kt_blocks[0]}
     repaired = core.lut_fused_repairs() - repairs0
     timed_out = wl.d_sections if pipe is None else pipe.last_local()
+    # (before anything else runs on these buffers; N > 1: rank 0's own shard)
+    dumped = dump_outputs(wl, timed_out, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
     gather_stats = pipe.stats() if pipe is not None else None
 
     # N > 1 (or --force-dist): what every rank measured by itself, and the same K steps WITHOUT the
@@ -1232,6 +1274,8 @@ def main():
                                       "single_frame_ms": _r(o.get("single_frame", {}).get("ms_per_frame"), 4)}
         if cpu is not None:
             out["cpu_baseline"] = cpu
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         out["distinct_frames"] = wl.distinct
         out["verify_all_ok"] = bool(VERIFIED) and all(ok for _, ok in VERIFIED)
         out["verified"] = [{"what": w, "ok": ok} for w, ok in VERIFIED]

@@ -119,3 +119,52 @@ def test_gpus_n_launcher_command_is_torch_distributed_run():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert '"-m", "torch.distributed.run", "--nnodes=1"' in src and '"--master-addr", "127.0.0.1"' in src
     assert "os.exec" not in src            # a child process, never a re-exec
+
+
+def _fake_workload(B, C, S, seed=5):
+    """What dump_outputs reads of a bench Workload, on the CPU: a [B][C][S] Section batch with a terminator in
+    every column and garbage behind it (the format leaves those entries unspecified)."""
+    import types
+    import numpy as np
+    import torch
+    from instance_stixels_amd.config import SECTION_DTYPE
+    rng = np.random.default_rng(seed)
+    rec = np.zeros((B, C, S), SECTION_DTYPE)
+    for f in SECTION_DTYPE.names:
+        rec[f] = rng.integers(0, 1000, rec.shape) if rec[f].dtype == np.int32 else rng.random(rec.shape)
+    n = rng.integers(0, S, (B, C))
+    rec["type"][np.arange(S) == n[..., None]] = -1
+    rec["type"][np.arange(S) < n[..., None]] = rng.integers(0, 3, (B, C, S))[np.arange(S) < n[..., None]]
+    d = torch.from_numpy(rec.view(np.int32).reshape(B, C, S, 8).copy())
+    return types.SimpleNamespace(B=B, C=C, S=S, torch=torch), d, rec, n
+
+
+def test_dump_outputs_writes_the_sections_as_float32_up_to_each_terminator(tmp_path):
+    import numpy as np
+    wl, d, rec, n = _fake_workload(3, 5, 7)
+    info = bench.dump_outputs(wl, d, str(tmp_path))
+    assert info["images"] == [0, 1, 2] and info["bytes"] <= bench.DUMP_LIMIT
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(f + ".npy" for f in info["files"])
+    np.testing.assert_array_equal(np.load(tmp_path / "stixels_per_column.npy"), n)
+    valid = np.arange(7) <= n[..., None]
+    for f in rec.dtype.names:
+        a = np.load(tmp_path / f"sections_{f}.npy")
+        assert a.dtype == np.float32 and a.shape == (3, 5, 7)
+        np.testing.assert_array_equal(a[valid], rec[f][valid].astype(np.float32))
+        assert not a[~valid].any()
+
+
+def test_dump_outputs_of_a_large_batch_is_a_fixed_sample_under_the_limit(tmp_path):
+    """Per image 256 columns x 200 sections (the bench's 1024x2048 frames): 64 images are 100 MB, more than the
+    limit; the sample of images is the same in every run."""
+    import numpy as np
+    wl, d, rec, n = _fake_workload(64, 256, 200)
+    a = bench.dump_outputs(wl, d, str(tmp_path / "a"))
+    b = bench.dump_outputs(wl, d, str(tmp_path / "b"))
+    assert a["images"] == b["images"] and 1 <= len(a["images"]) < 64 and a["bytes"] <= bench.DUMP_LIMIT
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) == a["bytes"]
+    k = np.asarray(a["images"])
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "images.npy"), k)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "sections_vB.npy")[:, :, 0], rec["vB"][k, :, 0])
+    for f in a["files"]:
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f"{f}.npy"), np.load(tmp_path / "b" / f"{f}.npy"))

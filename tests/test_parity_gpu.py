@@ -1064,6 +1064,49 @@ def test_bench_default_run_prints_one_compact_line(tmp_path):
     assert full["verify"]["ok"] and full["timed_blocks"]["count"] >= 1 and full["prune"]["evaluated_frac"] < 0.5
 
 
+def test_bench_steps_and_dump_outputs(tmp_path):
+    """bench.py --steps K times exactly K steps (one block, ms_per_step = its time / K) and --dump-outputs DIR writes
+    what the last timed step computed: every Section of every image equals the oracle's on the same seeded frames."""
+    import json
+    import subprocess
+    import sys
+    from instance_stixels_amd import make_config, synthetic
+    from instance_stixels_amd.config import SECTION_DTYPE
+    from oracle import oracle
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                          "--batch", "3", "--rows", "256", "--cols", "512", "--max-dis", "64", "--preset",
+                          "drn_d_38_pairwise", "--no-variants", "--no-cpu-baseline", "--no-single", "--no-d2h",
+                          "--no-prune-stats", "--dump-outputs", str(dump), "--out", str(tmp_path / "bench_full.json")],
+                         capture_output=True, text=True, timeout=600, cwd=root,
+                         env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
+    assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-1500:]
+    d = json.loads(out.stdout.strip().splitlines()[-1])
+    full = json.load(open(tmp_path / "bench_full.json"))
+    assert d["steps"] == 4 and full["timed_blocks"]["count"] == 1 and full["timed_blocks"]["steps_per_block"] == 4
+    assert d["ms_per_step"] == pytest.approx(full["timed_blocks"]["seconds"][0] / 4 * 1e3, rel=1e-2, abs=1e-2)
+    assert full["dump_outputs"]["images"] == [0, 1, 2] and full["dump_outputs"]["bytes"] <= 64 << 20
+    cfg = make_config("drn_d_38_pairwise", 256, 512, 64)
+    params, lut, odr = oracle.host_initialize(cfg)
+    n = np.load(dump / "stixels_per_column.npy")
+    assert n.shape == (3, cfg.realcols)
+    dumped = {name: np.load(dump / f"sections_{name}.npy") for name in SECTION_DTYPE.names}
+    for i in range(3):
+        f = synthetic.make_frame(cfg, seed=17 + i, family="scene")
+        gf, ng, ig, vh = oracle.host_ground(cfg, f.vhor_image, f.camera_tilt, f.camera_height, f.alpha_ground)
+        ref = oracle.compute(params, lut, odr, oracle.join_columns(cfg, f.disparity), f.segmentation, gf, ng, ig, vh,
+                             cfg.pairwise, want_tables=False)["sections"]
+        for c in range(cfg.realcols):
+            k = helpers.n_sections(ref[c])
+            assert n[i, c] == k
+            for name in SECTION_DTYPE.names:
+                got = dumped[name][i, c]
+                assert got.dtype == np.float32
+                np.testing.assert_array_equal(got[:k + 1], ref[c][:k + 1][name].astype(np.float32))
+                assert not got[k + 1:].any()
+
+
 def test_capi_rccl_gather_one_rank():
     """The C-ABI gather for C++ callers (is_comm_*, is_gather_sections, Stixels::ComputeBatchGather) in a FRESH
     child process on a one-rank RCCL communicator: ncclGather of the sizes and counts, the grouped
