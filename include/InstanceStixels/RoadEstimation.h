@@ -13,6 +13,7 @@
 
 #include <vector>
 
+#include "Stixels.hpp"
 #include "configuration.h"
 #include "util.h"
 
@@ -46,6 +47,26 @@ public:
     int GetDevice() const { return m_device; }
     int GetActiveDevice() const { return m_ctx_device; }
 
+    /* Batched road estimation (an addition): the result of Compute(d_disparity + i * rows * cols) for every frame
+     * i of d_disparity [n_images][rows][cols] (device, on the object's device), bit for bit, written as the
+     * road parameters of Stixels::ComputeBatch:
+     *   out[i] = {(int)ceil(horizon point), pitch, camera height, slope} and ok[i] = 1 where Compute would
+     *   return true; out[i] = {0, 0, 0, 0} and ok[i] = 0 where it would return false.
+     * The histogram and the Hough transform of the whole batch run on the device (is_road_vdisparity_batch,
+     * is_road_hough_batch), the lines come back in one copy, and the line choice of Compute runs on the host.
+     * A frame whose candidate buffer overflowed, or whose first max_lines lines hold no acceptable one while it
+     * has more, is finished with HoughLines on its binary image (GetBatchFallbacks()).  `stream`: a hipStream_t
+     * of the object's device, or null for the object's own stream; the call returns after it synchronised
+     * once.  Device scratch for n_images frames is allocated on first need and released by Finish().  The
+     * single-frame getters (GetPitch() ...) are left as they are. */
+    void ComputeBatch(const pixel_t* d_disparity, int n_images, Stixels::RoadParameters* out, uint8_t* ok,
+                      void* stream = nullptr);
+    /* Lines returned per frame (default 256) and local maxima kept per frame (default 4096, at most
+     * IS_ROAD_MAX_CANDIDATES) by the device Hough transform of ComputeBatch. */
+    void SetBatchLimits(int max_lines, int max_candidates);
+    /* Frames of the last ComputeBatch that were finished with the host Hough transform. */
+    int GetBatchFallbacks() const { return m_batch_fallbacks; }
+
     /* additions for tests */
     const std::vector<uint8_t>& GetBinaryVDisparity() const { return m_vDisp; }
     /* Standard Hough transform of a rows x cols 8-bit image; returns (rho, theta) pairs sorted
@@ -59,6 +80,9 @@ private:
                                  float& slope) const;
     bool ComputeHough(float& rho, float& theta, float& horizonPoint, float& pitch,
                       float& cameraHeight, float& slope);
+    /* the line choice of ComputeHough over lines[0 .. n) */
+    bool ChooseLine(const std::pair<float, float>* lines, size_t n, Stixels::RoadParameters& out) const;
+    void FreeBatch();
 
     bool m_is_initialized = false;
     int m_device = -1;      /* requested (SetDevice) */
@@ -69,6 +93,15 @@ private:
     int* d_maximum = nullptr;
     uint8_t* d_vDispBinary = nullptr;
     std::vector<uint8_t> m_vDisp;
+    /* ComputeBatch */
+    is_road_ctx* m_batch_ctx = nullptr; /* scratch for m_batch_cap frames */
+    int m_batch_cap = 0;
+    int m_batch_lines = 256, m_batch_candidates = 4096;
+    int m_batch_out_lines = 0;          /* max_lines the output blocks below were sized for */
+    char* d_batch_out = nullptr;        /* [cap][lines][2] float lines, [cap] totals, [cap] overflow flags */
+    char* h_batch_out = nullptr;        /* pinned twin of d_batch_out */
+    int m_batch_fallbacks = 0;
+    std::vector<uint8_t> m_batch_binary;
 
     int m_HoughAccumThr = 25;
     float m_binThr = 0.2f, m_maxPitch = 0, m_minPitch = 0;

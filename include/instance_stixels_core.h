@@ -242,6 +242,55 @@ int is_flip_and_pad(const float* d_cnn_out, int32_t* d_segmentation, int n_image
 int is_road_vdisparity(const float* d_disparity, int rows, int cols, int max_dis, float threshold,
                        int* d_vdisp, int* d_maximum, uint8_t* d_binary, void* stream);
 
+/* ---- batched road estimation: is_road_vdisparity + RoadEstimation::HoughLines for n frames ----------------
+ * Every launch covers the whole batch (the number of launches does not depend on n), and every result is
+ * bitwise the one of the single-frame path: the histogram, maximum and binary image of is_road_vdisparity, and
+ * the lines of RoadEstimation::HoughLines (rho = 1, theta = (float)pi / 180; sin / cos tables computed on the
+ * host exactly as HoughLines computes them and uploaded once).  Nothing here falls back to the CPU.
+ * A context owns the Hough tables and the scratch of up to max_batch frames of one shape.  Its calls are
+ * stream-ordered like those of is_ctx: is_road_hough_batch reads what the last is_road_vdisparity_batch on
+ * the same context left, so both go to one stream (or are ordered by the caller). */
+typedef struct is_road_ctx is_road_ctx;
+
+/* Largest max_candidates of is_road_hough_batch. */
+#define IS_ROAD_MAX_CANDIDATES 8192
+
+/* rows in [1, 32767], cols >= 1, max_dis in [1, 16384], max_batch >= 1; device: a HIP device index, or -1 for
+ * the calling thread's current device.  Every later call on the context runs on that device and puts the
+ * caller's current device back. */
+int is_road_ctx_create(is_road_ctx** ctx, int rows, int cols, int max_dis, int max_batch, int device);
+int is_road_ctx_destroy(is_road_ctx* ctx);
+int is_road_ctx_device(const is_road_ctx* ctx);
+/* The context's binary images, [max_batch][rows][max_dis] uint8 on its device: what the last
+ * is_road_vdisparity_batch wrote for frame i starts at i * rows * max_dis. */
+const uint8_t* is_road_ctx_binary(const is_road_ctx* ctx);
+
+/* v-disparity of n_images frames (1 <= n_images <= max_batch) on `stream`:
+ *   d_disparity  [n_images][rows][cols] float, device (pixels equal to 0 are skipped; bins outside
+ *                [0, max_dis) are ignored)
+ *   threshold    binarisation: count > maximum * threshold ? 255 : 0 (fp32, as is_road_vdisparity)
+ *   d_vdisp      optional (may be null), device [n_images][rows][max_dis] int: the histograms
+ *   d_maximum    optional, device [n_images] int: the maximum of each histogram
+ *   d_binary     optional, device [n_images][rows][max_dis] uint8: the binary images
+ * The context keeps the binary images and the list of non-zero pixels of each frame for is_road_hough_batch;
+ * the optional outputs are copies of its scratch. */
+int is_road_vdisparity_batch(is_road_ctx* ctx, const float* d_disparity, int n_images, float threshold,
+                             int* d_vdisp, int* d_maximum, uint8_t* d_binary, void* stream);
+
+/* Standard Hough transform of the binary images of the last is_road_vdisparity_batch (n_images no more than
+ * that call's) on `stream`: accumulator threshold `threshold` (votes > threshold), 4-neighbour local maxima
+ * with HoughLines' comparisons, lines sorted by votes descending, then accumulator index ascending.
+ *   max_lines       >= 1: lines written per frame
+ *   max_candidates  [1, IS_ROAD_MAX_CANDIDATES]: local maxima kept per frame for the sort
+ *   d_lines         device [n_images][max_lines][2] float: (rho, theta) of the first min(max_lines, total)
+ *                   lines, as HoughLines returns them; the rest is left as it was
+ *   d_votes         optional (may be null), device [n_images][max_lines] int: the votes of those lines
+ *   d_total         device [n_images] int: the number of local maxima of the frame (HoughLines' line count)
+ *   d_overflow      device [n_images] int: 1 if total > max_candidates -- then the lines are NOT those of
+ *                   HoughLines (the sort saw only some of the maxima), else 0 */
+int is_road_hough_batch(is_road_ctx* ctx, int n_images, int threshold, int max_lines, int max_candidates,
+                        float* d_lines, int* d_votes, int* d_total, int* d_overflow, void* stream);
+
 /* Thin wrappers over the HIP runtime so that the plain-C++ host class needs no HIP headers
  * (the reference's callers are all .cu files; ours may be plain C++). */
 int is_device_malloc(void** ptr, size_t bytes);

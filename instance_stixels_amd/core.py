@@ -28,6 +28,8 @@ EXPORTS = [
     "is_lut_fused_repairs",
     "is_comm_unique_id", "is_comm_init_rank", "is_comm_destroy", "is_comm_rank", "is_gather_i32",
     "is_gather_sections",
+    "is_road_ctx_create", "is_road_ctx_destroy", "is_road_ctx_device", "is_road_ctx_binary",
+    "is_road_vdisparity_batch", "is_road_hough_batch",
 ]
 
 
@@ -77,6 +79,13 @@ def lib():
                                              ctypes.POINTER(cf)]
         L.is_flip_and_pad.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp]
         L.is_road_vdisparity.argtypes = [vp, ci, ci, ci, cf, vp, vp, vp, vp]
+        L.is_road_ctx_create.argtypes = [ctypes.POINTER(vp), ci, ci, ci, ci, ci]
+        L.is_road_ctx_destroy.argtypes = [vp]
+        L.is_road_ctx_device.argtypes = [vp]
+        L.is_road_ctx_binary.argtypes = [vp]
+        L.is_road_ctx_binary.restype = vp
+        L.is_road_vdisparity_batch.argtypes = [vp, vp, ci, cf, vp, vp, vp, vp]
+        L.is_road_hough_batch.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]
         L.is_cluster_instances.argtypes = [vp, ctypes.POINTER(InstanceBuffers), vp]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]

@@ -54,6 +54,13 @@ hipError_t isk_launch_pack(const is_section*, int, int, int32_t*, int32_t*, is_s
 hipError_t isk_launch_unpack(const int32_t*, int32_t*, const is_section*, int, int, is_section*, hipStream_t);
 hipError_t isk_launch_flip_and_pad(const float*, int32_t*, int, int, int, int, int, hipStream_t);
 hipError_t isk_launch_vdisparity(const float*, int*, int*, uint8_t*, int, int, int, float, hipStream_t);
+int isk_road_sort_max(void);
+int isk_road_counters(void);
+hipError_t isk_set_lds_road_hough(int);
+hipError_t isk_launch_road_vdisparity(const float*, int*, uint8_t*, int*, int*, int, int, int, int, float,
+                                      hipStream_t);
+hipError_t isk_launch_road_hough(const int*, const int*, int*, const float*, int2*, float*, int*, int*, int*, int,
+                                 int, int, int, int, int, int, int, float, float, hipStream_t);
 }
 
 #define IS_FLT_HUGE 1e30f
@@ -551,6 +558,135 @@ int is_road_vdisparity(const float* d_disparity, int rows, int cols, int max_dis
     if (rows < 1 || cols < 1 || max_dis < 1 || max_dis > 16384) return fail_arg("bad shape");
     HIP_TRY(isk_launch_vdisparity(d_disparity, d_vdisp, d_maximum, d_binary, rows, cols, max_dis,
                                   threshold, (hipStream_t)stream));
+    return IS_OK;
+}
+
+/* ---- batched road estimation (is_k_road.hip) ---- */
+struct is_road_ctx {
+    int device, rows, cols, max_dis, max_batch;
+    int numangle, numrho, band; /* Hough accumulator (numangle + 2) x (numrho + 2); angles per workgroup */
+    float rho, theta;
+    int last_n;                 /* frames of the last is_road_vdisparity_batch (0: none yet) */
+    float* d_tab;               /* [2][numangle]: tabSin, tabCos of HoughLines */
+    int* d_vdisp;               /* [max_batch][rows][max_dis] */
+    uint8_t* d_binary;          /* [max_batch][rows][max_dis] */
+    int* d_counters;            /* [max_batch][isk_road_counters()]: maximum, non-zero pixels */
+    int* d_points;              /* [max_batch][rows * max_dis]: (i << 16) | j of the non-zero pixels */
+    int* d_ncand;               /* [max_batch] */
+    int2* d_cand;               /* [max_batch][IS_ROAD_MAX_CANDIDATES]: (accumulator index, votes) */
+};
+
+static void road_ctx_free(is_road_ctx* c) {
+    (void)hipFree(c->d_tab); (void)hipFree(c->d_vdisp); (void)hipFree(c->d_binary);
+    (void)hipFree(c->d_counters); (void)hipFree(c->d_points); (void)hipFree(c->d_ncand);
+    (void)hipFree(c->d_cand);
+    free(c);
+}
+
+int is_road_ctx_create(is_road_ctx** out, int rows, int cols, int max_dis, int max_batch, int device) {
+    if (!out) return fail_arg("null pointer");
+    *out = nullptr;
+    if (rows < 1 || rows > 32767 || cols < 1 || max_dis < 1 || max_dis > 16384)
+        return fail_arg("bad shape (rows in [1, 32767], cols >= 1, max_dis in [1, 16384])");
+    if (max_batch < 1 || max_batch > 65535) return fail_arg("max_batch outside [1, 65535]");
+    if (isk_road_sort_max() != IS_ROAD_MAX_CANDIDATES) return fail_arg("is_k_road.hip and the header disagree");
+    if (device < 0) HIP_TRY(hipGetDevice(&device));
+    DeviceScope dev_scope(device);
+    if (dev_scope.err != hipSuccess) return fail_hip(dev_scope.err, "hipSetDevice(device)", __FILE__, __LINE__);
+    /* RoadEstimation::HoughLines(image, rows, max_dis, 1.0f, kPi / 180, threshold), expression for expression */
+    const float kPi = 3.1415926535897932384626433832795f;
+    const float rho = 1.0f, theta = kPi / 180;
+    const int width = max_dis, height = rows;
+    const float irho = 1 / rho;
+    const double min_theta = 0, max_theta = 3.1415926535897932384626433832795;
+    const int numangle = (int)lrint((max_theta - min_theta) / theta);
+    const int numrho = (int)lrint(((width + height) * 2 + 1) / rho);
+    float* tab = (float*)malloc(sizeof(float) * 2 * numangle);
+    if (!tab) return IS_ENOMEM;
+    float ang = (float)min_theta;
+    for (int n = 0; n < numangle; ang += theta, n++) {
+        tab[n] = (float)(sin((double)ang) * irho);
+        tab[numangle + n] = (float)(cos((double)ang) * irho);
+    }
+    /* angles per workgroup: as many accumulator rows (plus the two halo rows) as 160 KiB of LDS hold */
+    const size_t row_bytes = sizeof(int) * (size_t)(numrho + 2);
+    int band = (int)(160 * 1024 / row_bytes) - 2;
+    if (band > numangle) band = numangle;
+    if (band < 1) { free(tab); return fail_arg("Hough accumulator rows do not fit the LDS (rows + max_dis too large)"); }
+    const hipError_t e = isk_set_lds_road_hough((int)(row_bytes * (band + 2)));
+    if (e != hipSuccess) { free(tab); return fail_hip(e, "isk_set_lds_road_hough", __FILE__, __LINE__); }
+
+    is_road_ctx* c = (is_road_ctx*)calloc(1, sizeof(is_road_ctx));
+    if (!c) { free(tab); return IS_ENOMEM; }
+    c->device = device; c->rows = rows; c->cols = cols; c->max_dis = max_dis; c->max_batch = max_batch;
+    c->numangle = numangle; c->numrho = numrho; c->band = band; c->rho = rho; c->theta = theta;
+    const size_t cells = (size_t)rows * max_dis;
+    const size_t B = (size_t)max_batch;
+    bool ok = hipMalloc((void**)&c->d_tab, sizeof(float) * 2 * numangle) == hipSuccess &&
+              hipMalloc((void**)&c->d_vdisp, sizeof(int) * B * cells) == hipSuccess &&
+              hipMalloc((void**)&c->d_binary, B * cells) == hipSuccess &&
+              hipMalloc((void**)&c->d_counters, sizeof(int) * B * isk_road_counters()) == hipSuccess &&
+              hipMalloc((void**)&c->d_points, sizeof(int) * B * cells) == hipSuccess &&
+              hipMalloc((void**)&c->d_ncand, sizeof(int) * B) == hipSuccess &&
+              hipMalloc((void**)&c->d_cand, sizeof(int2) * B * IS_ROAD_MAX_CANDIDATES) == hipSuccess;
+    if (ok) ok = hipMemcpy(c->d_tab, tab, sizeof(float) * 2 * numangle, hipMemcpyHostToDevice) == hipSuccess;
+    free(tab);
+    if (!ok) {
+        (void)hipGetLastError();
+        road_ctx_free(c);
+        snprintf(g_err, sizeof(g_err), "is_road_ctx_create: device allocation of %zu frames failed", B);
+        return IS_ENOMEM;
+    }
+    *out = c;
+    return IS_OK;
+}
+
+int is_road_ctx_destroy(is_road_ctx* c) {
+    if (!c) return IS_OK;
+    ON_CTX_DEVICE(c);
+    HIP_TRY(hipDeviceSynchronize());
+    road_ctx_free(c);
+    return IS_OK;
+}
+
+int is_road_ctx_device(const is_road_ctx* c) { return c ? c->device : -1; }
+const uint8_t* is_road_ctx_binary(const is_road_ctx* c) { return c ? c->d_binary : nullptr; }
+
+int is_road_vdisparity_batch(is_road_ctx* c, const float* d_disparity, int n_images, float threshold,
+                             int* d_vdisp, int* d_maximum, uint8_t* d_binary, void* stream) {
+    if (!c || !d_disparity) return fail_arg("null pointer");
+    if (n_images < 1 || n_images > c->max_batch) return fail_arg("n_images outside [1, max_batch]");
+    ON_CTX_DEVICE(c);
+    const hipStream_t s = (hipStream_t)stream;
+    const int nc = isk_road_counters();
+    const size_t cells = (size_t)c->rows * c->max_dis;
+    HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(int) * nc * n_images, s));
+    HIP_TRY(isk_launch_road_vdisparity(d_disparity, c->d_vdisp, c->d_binary, c->d_counters, c->d_points, n_images,
+                                       c->rows, c->cols, c->max_dis, threshold, s));
+    if (d_vdisp)
+        HIP_TRY(hipMemcpyAsync(d_vdisp, c->d_vdisp, sizeof(int) * cells * n_images, hipMemcpyDeviceToDevice, s));
+    if (d_maximum) /* entry 0 of each frame's counters */
+        HIP_TRY(hipMemcpy2DAsync(d_maximum, sizeof(int), c->d_counters, sizeof(int) * nc, sizeof(int), n_images,
+                                 hipMemcpyDeviceToDevice, s));
+    if (d_binary) HIP_TRY(hipMemcpyAsync(d_binary, c->d_binary, cells * n_images, hipMemcpyDeviceToDevice, s));
+    c->last_n = n_images;
+    return IS_OK;
+}
+
+int is_road_hough_batch(is_road_ctx* c, int n_images, int threshold, int max_lines, int max_candidates,
+                        float* d_lines, int* d_votes, int* d_total, int* d_overflow, void* stream) {
+    if (!c || !d_lines || !d_total || !d_overflow) return fail_arg("null pointer");
+    if (n_images < 1 || n_images > c->last_n)
+        return fail_arg("n_images outside [1, frames of the last is_road_vdisparity_batch]");
+    if (max_lines < 1) return fail_arg("max_lines < 1");
+    if (max_candidates < 1 || max_candidates > IS_ROAD_MAX_CANDIDATES)
+        return fail_arg("max_candidates outside [1, IS_ROAD_MAX_CANDIDATES]");
+    ON_CTX_DEVICE(c);
+    const hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(c->d_ncand, 0, sizeof(int) * n_images, s));
+    HIP_TRY(isk_launch_road_hough(c->d_points, c->d_counters, c->d_ncand, c->d_tab, c->d_cand, d_lines, d_votes,
+                                  d_total, d_overflow, n_images, c->rows * c->max_dis, c->numangle, c->numrho,
+                                  c->band, threshold, max_candidates, max_lines, c->rho, c->theta, s));
     return IS_OK;
 }
 

@@ -1,0 +1,211 @@
+/*
+ * is_k_road.hip -- batched road estimation (f3 for n frames): v-disparity histogram, binarisation +
+ * compaction, the standard Hough transform and its per-frame sort, every launch covering the whole batch.
+ * Results are those of RoadEstimation::Compute frame by frame (is_k_frontend.hip k_vdisp_* for the
+ * histogram, RoadEstimation::HoughLines for the transform), bit for bit.  See is_road_* in
+ * instance_stixels_core.h.
+ */
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+/* Per-frame counters of the batch scratch: [frame][IS_ROAD_CNT] ints. */
+#define IS_ROAD_CNT 2
+#define IS_ROAD_CNT_MAX 0    /* maximum of the histogram */
+#define IS_ROAD_CNT_POINTS 1 /* non-zero pixels of the binary image (entries of the point list) */
+#define IS_ROAD_SORT_MAX 8192 /* largest candidate capacity the one-workgroup sort handles (64 KiB of keys) */
+
+/* Histogram of one (row, frame): the scheme of k_vdisp_histogram with a frame index. */
+__global__ __launch_bounds__(256) void k_road_histogram(const float* __restrict__ disparity,
+                                                        int* __restrict__ vdisp, int* __restrict__ counters,
+                                                        int rows, int cols, int max_dis) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int* bins = (int*)smem; /* [max_dis] */
+    const int row = blockIdx.x, f = blockIdx.y;
+    for (int i = threadIdx.x; i < max_dis; i += blockDim.x) bins[i] = 0;
+    __syncthreads();
+    const float* src = disparity + ((size_t)f * rows + row) * cols;
+    for (int j = threadIdx.x; j < cols; j += blockDim.x) {
+        const float d = src[j];
+        if (d != 0) {
+            const int col = (int)d;
+            if (col >= 0 && col < max_dis) atomicAdd(&bins[col], 1);
+        }
+    }
+    __syncthreads();
+    int m = 0;
+    int* dst = vdisp + ((size_t)f * rows + row) * max_dis;
+    for (int i = threadIdx.x; i < max_dis; i += blockDim.x) {
+        const int v = bins[i];
+        dst[i] = v;
+        m = max(m, v);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o, 64));
+    if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(&counters[f * IS_ROAD_CNT + IS_ROAD_CNT_MAX], m);
+}
+
+/* Binarisation (the comparison of k_vdisp_binarize) and compaction of the non-zero pixels of each frame
+ * into points[f][k] = (i << 16) | j.  One atomic per wave: the ballot's popcount reserves the wave's slots. */
+__global__ __launch_bounds__(256) void k_road_binarize(const int* __restrict__ vdisp, uint8_t* __restrict__ binary,
+                                                       int* __restrict__ counters, int* __restrict__ points,
+                                                       float threshold, int rows, int max_dis) {
+    const int f = blockIdx.y;
+    const int n = rows * max_dis;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t off = (size_t)f * n;
+    bool on = false;
+    if (idx < n) {
+        const float p = (float)vdisp[off + idx];
+        on = p > counters[f * IS_ROAD_CNT + IS_ROAD_CNT_MAX] * threshold;
+        binary[off + idx] = on ? 255 : 0;
+    }
+    const uint64_t mask = __ballot(on);
+    if (mask == 0) return;
+    const int lane = threadIdx.x & 63;
+    const int leader = __ffsll((unsigned long long)mask) - 1;
+    int base = 0;
+    if (lane == leader) base = atomicAdd(&counters[f * IS_ROAD_CNT + IS_ROAD_CNT_POINTS], __popcll(mask));
+    base = __shfl(base, leader, 64);
+    if (on) {
+        const int k = base + __popcll(mask & ((1ull << lane) - 1));
+        points[off + k] = ((idx / max_dis) << 16) | (idx % max_dis); /* k < n: one slot per pixel */
+    }
+}
+
+/* Hough vote + local maxima of one (band of angles, frame).  The band's accumulator rows and one halo row on
+ * each side live in LDS: lds[k][numrho + 2] holds accumulator row n0 + k (angle n0 + k - 1), k = 0 .. band + 1.
+ * Rows of angles outside [0, numangle) are the accumulator's zero padding; so are the columns 0 and
+ * numrho + 1.  Votes: r = rint(j*tabCos[a] + i*tabSin[a]) in fp32 without contraction, as HoughLines. */
+__global__ __launch_bounds__(256) void k_road_hough(const int* __restrict__ points,
+                                                    const int* __restrict__ counters,
+                                                    const float* __restrict__ tab, /* [sin | cos][numangle] */
+                                                    int2* __restrict__ cand, int* __restrict__ ncand,
+                                                    int n_cells, int numangle, int numrho, int band,
+                                                    int threshold, int cap) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int* acc = (int*)smem;
+    const int f = blockIdx.y;
+    const int n0 = blockIdx.x * band; /* first angle of the band */
+    const int stride = numrho + 2;
+    const int lrows = band + 2;
+    for (int k = threadIdx.x; k < lrows * stride; k += blockDim.x) acc[k] = 0;
+    __syncthreads();
+    const int a_lo = max(n0 - 1, 0), a_hi = min(n0 + band + 1, numangle); /* angles voted here */
+    const int npts = counters[f * IS_ROAD_CNT + IS_ROAD_CNT_POINTS];
+    const int* pts = points + (size_t)f * n_cells;
+    const float* tabSin = tab;
+    const float* tabCos = tab + numangle;
+    const int roff = (numrho - 1) / 2;
+    for (int p = threadIdx.x; p < npts; p += blockDim.x) {
+        const int v = pts[p];
+        const float fi = (float)(v >> 16), fj = (float)(v & 0xffff);
+        for (int a = a_lo; a < a_hi; a++) {
+            const float x = fj * tabCos[a];
+            const float y = fi * tabSin[a];
+            const int r = (int)rintf(x + y) + roff;
+            if (r >= 0 && r < numrho) atomicAdd(&acc[(a - n0 + 1) * stride + r + 1], 1);
+        }
+    }
+    __syncthreads();
+    const int nb = min(band, numangle - n0); /* real angles of the band */
+    for (int t = threadIdx.x; t < nb * numrho; t += blockDim.x) {
+        const int k = t / numrho + 1, r = t % numrho;
+        const int lb = k * stride + r + 1;
+        const int v = acc[lb];
+        if (v > threshold && v > acc[lb - 1] && v >= acc[lb + 1] && v > acc[lb - stride] &&
+            v >= acc[lb + stride]) {
+            const int slot = atomicAdd(&ncand[f], 1); /* local maxima found (may exceed cap) */
+            if (slot < cap) cand[(size_t)f * cap + slot] = make_int2((n0 + k) * stride + r + 1, v);
+        }
+    }
+}
+
+/* Sort of one frame's candidates (votes descending, accumulator index ascending: unique keys, so the order
+ * of arrival does not matter) by a bitonic sort of 64-bit keys in LDS, then the first max_lines lines as
+ * HoughLines writes them. */
+__global__ __launch_bounds__(256) void k_road_sort(const int2* __restrict__ cand, const int* __restrict__ ncand,
+                                                   float* __restrict__ lines, int* __restrict__ votes,
+                                                   int* __restrict__ total, int* __restrict__ overflow,
+                                                   int cap, int max_lines, int numrho, float rho, float theta) {
+    __shared__ unsigned long long keys[IS_ROAD_SORT_MAX];
+    const int f = blockIdx.x;
+    const int found = ncand[f];
+    const int m = min(found, cap);
+    int P = 1;
+    while (P < m) P <<= 1;
+    for (int t = threadIdx.x; t < P; t += blockDim.x) {
+        unsigned long long k = ~0ull;
+        if (t < m) {
+            const int2 c = cand[(size_t)f * cap + t];
+            k = ((unsigned long long)(unsigned)(0x7fffffff - c.y) << 32) | (unsigned)c.x;
+        }
+        keys[t] = k;
+    }
+    __syncthreads();
+    for (int size = 2; size <= P; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = threadIdx.x; t < P; t += blockDim.x) {
+                const int u = t ^ stride;
+                if (u > t) {
+                    const unsigned long long a = keys[t], b = keys[u];
+                    const bool up = (t & size) == 0;
+                    if ((a > b) == up) { keys[t] = b; keys[u] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    const double scale = 1. / (numrho + 2);
+    const int nl = min(m, max_lines);
+    for (int t = threadIdx.x; t < nl; t += blockDim.x) {
+        const unsigned long long k = keys[t];
+        const int idx = (int)(k & 0xffffffffu);
+        const int n = (int)floor(idx * scale) - 1;
+        const int r = idx - (n + 1) * (numrho + 2) - 1;
+        float* l = lines + ((size_t)f * max_lines + t) * 2;
+        l[0] = (r - (numrho - 1) * 0.5f) * rho;
+        l[1] = 0.0f + n * theta;
+        if (votes) votes[(size_t)f * max_lines + t] = 0x7fffffff - (int)(k >> 32);
+    }
+    if (threadIdx.x == 0) {
+        total[f] = found;
+        overflow[f] = found > cap ? 1 : 0;
+    }
+}
+
+extern "C" {
+
+int isk_road_sort_max(void) { return IS_ROAD_SORT_MAX; }
+int isk_road_counters(void) { return IS_ROAD_CNT; }
+
+hipError_t isk_set_lds_road_hough(int bytes) {
+    return hipFuncSetAttribute((const void*)k_road_hough, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+
+/* counters [n][IS_ROAD_CNT] must be zero on entry (the caller clears them in one memset) */
+hipError_t isk_launch_road_vdisparity(const float* disparity, int* vdisp, uint8_t* binary, int* counters,
+                                      int* points, int n_images, int rows, int cols, int max_dis,
+                                      float threshold, hipStream_t stream) {
+    hipLaunchKernelGGL(k_road_histogram, dim3(rows, n_images), dim3(256), sizeof(int) * max_dis, stream,
+                       disparity, vdisp, counters, rows, cols, max_dis);
+    const int n = rows * max_dis;
+    hipLaunchKernelGGL(k_road_binarize, dim3((n + 255) / 256, n_images), dim3(256), 0, stream, vdisp, binary,
+                       counters, points, threshold, rows, max_dis);
+    return hipGetLastError();
+}
+
+/* ncand [n] must be zero on entry */
+hipError_t isk_launch_road_hough(const int* points, const int* counters, int* ncand, const float* tab, int2* cand,
+                                 float* lines, int* votes, int* total, int* overflow, int n_images, int n_cells, int numangle,
+                                 int numrho, int band, int threshold, int cap, int max_lines, float rho,
+                                 float theta, hipStream_t stream) {
+    const int nbands = (numangle + band - 1) / band;
+    const size_t lds = sizeof(int) * (size_t)(band + 2) * (numrho + 2);
+    hipLaunchKernelGGL(k_road_hough, dim3(nbands, n_images), dim3(256), lds, stream, points, counters, tab, cand,
+                       ncand, n_cells, numangle, numrho, band, threshold, cap);
+    hipLaunchKernelGGL(k_road_sort, dim3(n_images), dim3(256), 0, stream, cand, ncand, lines, votes, total,
+                       overflow, cap, max_lines, numrho, rho, theta);
+    return hipGetLastError();
+}
+
+} /* extern "C" */

@@ -28,8 +28,12 @@ EXPORTS = [
     "ish_set_device", "ish_compute_batch", "ish_time_compute_batch", "ish_compute_batch_gather",
     "ire_create", "ire_destroy", "ire_initialize", "ire_finish", "ire_compute", "ire_get_binary",
     "ire_hough_lines", "ire_set_device", "ire_active_device", "ire_compute_device",
-    "ish_get_input_disparity_on_device",
+    "ish_get_input_disparity_on_device", "ire_compute_batch", "ire_set_batch_limits", "ire_batch_fallbacks",
 ]
+
+# Stixels::RoadParameters, what RoadEstimation::ComputeBatch writes per frame
+ROAD_PARAMETERS_DTYPE = np.dtype([("vhor", np.int32), ("camera_tilt", np.float32),
+                                  ("camera_height", np.float32), ("alpha_ground", np.float32)])
 
 
 class _IshConfig(ctypes.Structure):
@@ -96,6 +100,9 @@ def lib():
         L.ire_active_device.argtypes = [vp]
         L.ire_compute_device.argtypes = [vp, vp, vp]
         L.ish_get_input_disparity_on_device.argtypes = [vp]
+        L.ire_compute_batch.argtypes = [vp, vp, ci, vp, vp, vp]
+        L.ire_set_batch_limits.argtypes = [vp, ci, ci]
+        L.ire_batch_fallbacks.argtypes = [vp]
         L.ish_get_input_disparity_on_device.restype = vp
         _LIB = L
     return _LIB
@@ -364,6 +371,34 @@ class RoadEstimation:
         self.pitch, self.camera_height, self.slope = float(out[0]), float(out[1]), float(out[2])
         self.horizon_point = int(out[3])
         return bool(rc)
+
+    def ComputeBatch(self, d_ptr, n, stream=0):
+        """RoadEstimation::ComputeBatch on d_ptr [n][rows][cols] f32 (device pointer as int, on the object's
+        device).  Returns (road, ok): road is n tuples (vhor_image, camera_tilt, camera_height, alpha_ground)
+        for Stixels.ComputeBatch, ok n bools (False: no road line, the tuple is zeros)."""
+        out = np.zeros(n, ROAD_PARAMETERS_DTYPE)
+        ok = np.zeros(n, np.uint8)
+        rc = lib().ire_compute_batch(self._h, ctypes.c_void_p(int(d_ptr)), int(n), out.ctypes.data,
+                                     ok.ctypes.data, ctypes.c_void_p(int(stream)))
+        if rc == -1:
+            raise ValueError(lib().ish_last_error().decode())
+        if rc < 0:
+            raise RuntimeError(lib().ish_last_error().decode())
+        road = [(int(r["vhor"]), float(r["camera_tilt"]), float(r["camera_height"]), float(r["alpha_ground"]))
+                for r in out]
+        return road, [bool(x) for x in ok]
+
+    def SetBatchLimits(self, max_lines, max_candidates):
+        """Lines per frame and local maxima kept per frame by the device Hough transform of ComputeBatch."""
+        if lib().ire_set_batch_limits(self._h, int(max_lines), int(max_candidates)) < 0:
+            raise ValueError(lib().ish_last_error().decode())
+
+    def GetBatchFallbacks(self):
+        """Frames of the last ComputeBatch finished with the host Hough transform."""
+        n = int(lib().ire_batch_fallbacks(self._h))
+        if n < 0:
+            raise ValueError("RoadEstimation is closed")
+        return n
 
     def GetBinaryVDisparity(self):
         out = np.zeros(self._shape, np.uint8)

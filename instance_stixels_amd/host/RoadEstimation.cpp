@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <stdexcept>
 
 static const float kPi = 3.1415926535897932384626433832795f; /* CV_PI as float */
 
@@ -64,7 +65,96 @@ void RoadEstimation::Finish() { /* RE.cu:84-92 */
     IS_CHECK_RETURN(is_device_free(d_maximum));
     IS_CHECK_RETURN(is_device_free(d_vDispBinary));
     d_vDisp = nullptr; d_disparity = nullptr; d_maximum = nullptr; d_vDispBinary = nullptr;
+    FreeBatch();
     m_is_initialized = false;
+}
+
+void RoadEstimation::FreeBatch() { /* (under the caller's device guard) */
+    IS_CHECK_RETURN(is_road_ctx_destroy(m_batch_ctx)); /* synchronises the device */
+    IS_CHECK_RETURN(is_device_free(d_batch_out));
+    IS_CHECK_RETURN(is_host_free(h_batch_out));
+    m_batch_ctx = nullptr; d_batch_out = nullptr; h_batch_out = nullptr;
+    m_batch_cap = 0;
+    m_batch_out_lines = 0;
+}
+
+void RoadEstimation::SetBatchLimits(int max_lines, int max_candidates) {
+    if (max_lines < 1) throw std::invalid_argument("max_lines must be at least 1");
+    if (max_candidates < 1 || max_candidates > IS_ROAD_MAX_CANDIDATES)
+        throw std::invalid_argument("max_candidates outside [1, IS_ROAD_MAX_CANDIDATES]");
+    m_batch_lines = max_lines;
+    m_batch_candidates = max_candidates;
+}
+
+void RoadEstimation::ComputeBatch(const pixel_t* d_im, int n_images, Stixels::RoadParameters* out, uint8_t* ok,
+                                  void* stream) {
+    if (!m_is_initialized) throw std::invalid_argument("RoadEstimation::ComputeBatch before Initialize()");
+    if (n_images < 1 || !d_im || !out || !ok) throw std::invalid_argument("ComputeBatch: empty batch or null pointer");
+    const DeviceGuard guard(m_ctx_device);
+    void* s = stream ? stream : m_stream;
+    const int L = m_batch_lines;
+    /* out block, in the order that lets ONE copy fetch n frames: [cap] totals, [cap] overflow flags,
+     * [cap][L][2] lines */
+    if (n_images > m_batch_cap || L != m_batch_out_lines) {
+        const int cap = std::max(n_images, m_batch_cap);
+        FreeBatch();
+        IS_CHECK_RETURN(is_road_ctx_create(&m_batch_ctx, m_rows, m_cols, m_max_dis, cap, m_ctx_device));
+        const size_t bytes = sizeof(int) * 2 * (size_t)cap + sizeof(float) * 2 * (size_t)cap * L;
+        IS_CHECK_RETURN(is_device_malloc((void**)&d_batch_out, bytes));
+        IS_CHECK_RETURN(is_host_malloc((void**)&h_batch_out, bytes));
+        m_batch_cap = cap;
+        m_batch_out_lines = L;
+    }
+    const int cap = m_batch_cap;
+    int* d_total = (int*)d_batch_out;
+    int* d_overflow = d_total + cap;
+    float* d_lines = (float*)(d_overflow + cap);
+    IS_CHECK_RETURN(is_road_vdisparity_batch(m_batch_ctx, d_im, n_images, m_binThr, nullptr, nullptr, nullptr, s));
+    IS_CHECK_RETURN(is_road_hough_batch(m_batch_ctx, n_images, m_HoughAccumThr, L, m_batch_candidates, d_lines,
+                                        nullptr, d_total, d_overflow, s));
+    const size_t bytes = sizeof(int) * 2 * (size_t)cap + sizeof(float) * 2 * (size_t)n_images * L;
+    IS_CHECK_RETURN(is_memcpy_d2h(h_batch_out, d_batch_out, bytes, s));
+    IS_CHECK_RETURN(is_stream_synchronize(s));
+
+    const int* total = (const int*)h_batch_out;
+    const int* overflow = total + cap;
+    const float* h_lines = (const float*)(overflow + cap);
+    const size_t cells = (size_t)m_rows * m_max_dis;
+    std::vector<std::pair<float, float>> lines;
+    m_batch_fallbacks = 0;
+    for (int i = 0; i < n_images; i++) {
+        const int nl = std::min(total[i], L);
+        lines.resize(nl);
+        for (int k = 0; k < nl; k++)
+            lines[k] = std::make_pair(h_lines[((size_t)i * L + k) * 2], h_lines[((size_t)i * L + k) * 2 + 1]);
+        bool found = !overflow[i] && ChooseLine(lines.data(), lines.size(), out[i]);
+        if (!found && (overflow[i] || total[i] > L)) { /* the lines the device kept do not decide it */
+            m_batch_binary.resize(cells);
+            IS_CHECK_RETURN(is_memcpy_d2h(m_batch_binary.data(), is_road_ctx_binary(m_batch_ctx) + i * cells,
+                                          cells, s));
+            IS_CHECK_RETURN(is_stream_synchronize(s));
+            lines = HoughLines(m_batch_binary.data(), m_rows, m_max_dis, 1.0f, kPi / 180, m_HoughAccumThr);
+            found = ChooseLine(lines.data(), lines.size(), out[i]);
+            m_batch_fallbacks++;
+        }
+        ok[i] = found ? 1 : 0;
+        if (!found) out[i] = Stixels::RoadParameters{0, 0.0f, 0.0f, 0.0f};
+    }
+}
+
+bool RoadEstimation::ChooseLine(const std::pair<float, float>* lines, size_t n,
+                                Stixels::RoadParameters& out) const { /* ComputeHough's loop */
+    float rho, theta, horizonPoint, pitch, cameraHeight, slope;
+    for (size_t k = 0; k < n; k++) {
+        rho = std::abs(lines[k].first);
+        theta = lines[k].second;
+        ComputeCameraProperties(m_rows, rho, theta, horizonPoint, pitch, cameraHeight, slope);
+        if (pitch >= m_minPitch && pitch <= m_maxPitch) {
+            out = Stixels::RoadParameters{(int)ceil(horizonPoint), pitch, cameraHeight, slope};
+            return true;
+        }
+    }
+    return false;
 }
 
 bool RoadEstimation::Compute(const std::vector<pixel_t>& im) { /* RE.cu:94-102 */

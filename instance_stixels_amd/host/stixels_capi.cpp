@@ -351,6 +351,20 @@ int ire_compute_device(void* h, float* d_image, float* out4) {
     });
     return rc ? rc : ok;
 }
+/* ComputeBatch(d_disparity [n][rows][cols], n): out [n] Stixels::RoadParameters (int vhor, float tilt,
+ * float height, float alpha: 16 bytes each), ok [n] uint8; stream: a hipStream_t or null (the object's own).
+ * Returns the number of frames finished with the host Hough transform (GetBatchFallbacks()). */
+static_assert(sizeof(Stixels::RoadParameters) == 16, "ire_compute_batch writes 16-byte records");
+int ire_compute_batch(void* h, const float* d_disparity, int n, void* out, uint8_t* ok, void* stream) {
+    const int rc = guard([&] {
+        ((RoadEstimation*)h)->ComputeBatch(d_disparity, n, (Stixels::RoadParameters*)out, ok, stream);
+    });
+    return rc ? rc : ((RoadEstimation*)h)->GetBatchFallbacks();
+}
+int ire_set_batch_limits(void* h, int max_lines, int max_candidates) {
+    return guard([&] { ((RoadEstimation*)h)->SetBatchLimits(max_lines, max_candidates); });
+}
+int ire_batch_fallbacks(void* h) { return h ? ((RoadEstimation*)h)->GetBatchFallbacks() : -1; }
 void* ish_get_input_disparity_on_device(void* h) {
     return (void*)((Stixels*)h)->GetInputDisparityImageOnDevice();
 }
