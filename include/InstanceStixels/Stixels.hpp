@@ -110,6 +110,30 @@ public:
                             const int32_t* d_segmentation, const RoadParameters* road, void* comm, int dst,
                             const int* images_per_rank, const RoadParameters* road_all,
                             std::vector<StixelsData>& out, void* stream = nullptr);
+    /* f5 (an addition): the Sections of frames 0 .. n_images-1 of the LAST Compute() or ComputeBatch() -- both
+     * leave them in d_stixels, their cluster labels in d_instance_labels -- rendered to dense per-pixel result
+     * maps and scored against ground truth on the device, as is_render_sections of instance_stixels_core.h
+     * defines every field (all device pointers on the object's device; NULL = skipped). */
+    struct RenderTargets {
+        uint8_t* label = nullptr;           /* [n][rows][cols] labelIds (class_to_label of the section class) */
+        float* disparity = nullptr;         /* [n][rows][cols] section disparity */
+        int32_t* instance = nullptr;        /* [n][rows][cols] class*1000 + cluster label; needs instances */
+        const uint8_t* gt_label = nullptr;  /* [n][rows][cols], with confusion */
+        int n_labels = 34;
+        unsigned long long* confusion = nullptr; /* [n_labels][n_labels], added to */
+        const float* gt_disparity = nullptr;     /* [n][rows][cols]: the deviation of RenderResult */
+        const uint8_t* class_to_label = nullptr; /* host [n_classes]; NULL: Cityscapes trainId -> labelId */
+        int n_classes = 0;
+    };
+    struct RenderResult {
+        double disp_abs_sum;   /* sum of |stixel - gt| over pixels where both are non-zero (0 without gt) */
+        int64_t disp_count;
+        int32_t stixel_count;  /* sections in front of the terminators */
+    };
+    /* Queues the render on `stream` (null: the object's own), then ONE small copy and a synchronisation for the
+     * per-frame results.  Throws std::invalid_argument before any compute, when n_images exceeds the last call's
+     * batch, or when an instance image is asked of a call that ran without instances. */
+    std::vector<RenderResult> RenderBatch(int n_images, const RenderTargets& targets, void* stream = nullptr);
     /* Introspection for tests / bench. */
     const StixelParameters& GetParameters() const { return m_params; }
     const std::vector<float>& GetObjectCostLUT() const { return m_obj_cost_lut; }
@@ -180,6 +204,14 @@ private:
     int32_t* h_all_counts = nullptr; /* ComputeBatchGather on dst: the per-column counts of all ranks (pinned) */
     size_t m_h_all_counts_cap = 0;
     int32_t* h_instance_packed = nullptr;
+    /* RenderBatch: what the last Compute() / ComputeBatch() left in d_stixels (0 frames: nothing renderable --
+     * before any compute, and after ComputeBatchGather, which reuses d_stixels for its shard) and whether its
+     * cluster labels are there; the per-section label map and the per-frame results (allocated on first use) */
+    int m_render_images = 0;
+    bool m_render_instances = false;
+    int32_t* d_section_instance = nullptr; /* [max_batch][realcols][max_sections] */
+    char* d_render_results = nullptr;      /* [max_batch] double | [max_batch] int64 | [max_batch] int32 */
+    char* h_render_results = nullptr;
     /* every device operation of the object runs on this stream (an ordinary stream: it still
      * synchronises with work the caller queued on the legacy NULL stream, like the reference's
      * default-stream code; on the NULL stream itself the auxiliary streams of the core never

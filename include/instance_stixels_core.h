@@ -291,6 +291,70 @@ int is_road_vdisparity_batch(is_road_ctx* ctx, const float* d_disparity, int n_i
 int is_road_hough_batch(is_road_ctx* ctx, int n_images, int threshold, int max_lines, int max_candidates,
                         float* d_lines, int* d_votes, int* d_total, int* d_overflow, void* stream);
 
+/* ---- f5: stixels to dense result maps, scored against ground truth on the device ----------------------------
+ * The reference evaluates stixels through per-pixel images drawn on the host
+ * (tools/visualization/clustering_visualization.py draw_stixels :164-413, draw_instance_masks :118-142) and
+ * scores those (cityscapesscripts for the labelIds, tools/evaluation/disparity.py for the disparity).  Geometry
+ * of that tooling: the stixel width is w = cols / realcols (integer division, :186 -- not column_step);
+ * section (c, i) covers x in [c*w, c*w + w-1] and y in [rows-1-vT, rows-1-vB] (:214-217), inclusive.  Pixels
+ * no section covers (x >= realcols*w, rows after an early terminator) are 0 in every image (:1166-1176).
+ * Well-formed sections (what is_compute leaves) partition each column; hand-built ones that overlap (the
+ * highest section index wins), have vB > vT or leave [0, rows-1] are clipped to the frame and never written
+ * outside it. */
+
+/* Largest n_labels of the confusion matrix, largest n_classes of a caller's class -> label table. */
+#define IS_RENDER_MAX_LABELS 64
+#define IS_RENDER_MAX_CLASSES 256
+
+/* Zero-initialise (memset / `= {}`) before setting fields, as is_instance_buffers.  Every output is optional
+ * (NULL: skipped, costs nothing); all device arrays are on the current device.
+ *   d_sections          [n_images][realcols][max_sections] is_section, terminator type == -1 (16-byte aligned)
+ *   d_section_instance  optional [n_images][realcols][max_sections] int32: the cluster label of every section,
+ *                       -1 = none (is_section_instance_labels); NULL: no section is an instance
+ *   rows, cols          the image (cols >= realcols); max_sections in [1, 32767]
+ *   h_class_to_label    host [n_classes] (n_classes in [1, IS_RENDER_MAX_CLASSES]): semantic class -> label
+ *                       value; NULL: Cityscapes trainId -> labelId (:396-402, trainId2label[c].id), n_classes
+ *                       ignored.  A class outside the table gives 0.
+ *   d_label             [n_images][rows][cols] uint8: the label of the covering section
+ *   d_disparity         [n_images][rows][cols] float: its disparity, bit for bit, every section type (:403-409)
+ *   d_instance          [n_images][rows][cols] int32: semantic_class*1000 + l for a section with cluster label
+ *                       0 <= l < 1000 (read_stixel_file :108-114), else 0; the mask of instance k in
+ *                       draw_instance_masks is exactly instance == k
+ *   d_gt_label, d_confusion   both or neither: gt [n_images][rows][cols] uint8; confusion [n_labels][n_labels]
+ *                       uint64 (n_labels in [1, IS_RENDER_MAX_LABELS]), ADDED to: conf[gt][pred] += 1 for every
+ *                       pixel with gt < n_labels and pred < n_labels, pred = the label image's value (0 where no
+ *                       section covers), summed over the batch
+ *   d_gt_disparity, d_disp_abs_sum, d_disp_count   all or none: gt [n_images][rows][cols] float; per frame the
+ *                       sum of fabsf(stixel - gt) (each term fp32, accumulated in fp64, the same bits on every
+ *                       run) and the count over pixels with stixel != 0 and gt != 0 (disparity.py:56-62)
+ *   d_stixel_count      [n_images] int32: sections in front of the terminators (run_cityscapes.py:611) */
+typedef struct is_render_args {
+    const is_section* d_sections;
+    const int32_t* d_section_instance;
+    int n_images, realcols, max_sections, rows, cols;
+    const uint8_t* h_class_to_label;
+    int n_classes;
+    uint8_t* d_label;
+    float* d_disparity;
+    int32_t* d_instance;
+    const uint8_t* d_gt_label;
+    int n_labels;
+    unsigned long long* d_confusion;
+    const float* d_gt_disparity;
+    double* d_disp_abs_sum;
+    int64_t* d_disp_count;
+    int32_t* d_stixel_count;
+} is_render_args;
+
+/* The per-candidate cluster labels of an is_compute call with instances (d_indices, d_labels,
+ * d_instances_per_class of per_image[0 .. n_images-1]) as a per-section map: d_section_instance
+ * [n_images][realcols][max_sections] int32, -1 where a section is no candidate.  On `stream`. */
+int is_section_instance_labels(const is_instance_buffers* per_image, int n_images, int realcols, int max_sections,
+                               int32_t* d_section_instance, void* stream);
+/* Renders and scores n_images frames on `stream`, asynchronously (two launches, plus one for the label map of
+ * the caller's instances above). */
+int is_render_sections(const is_render_args* args, void* stream);
+
 /* Thin wrappers over the HIP runtime so that the plain-C++ host class needs no HIP headers
  * (the reference's callers are all .cu files; ours may be plain C++). */
 int is_device_malloc(void** ptr, size_t bytes);

@@ -30,13 +30,26 @@ EXPORTS = [
     "is_gather_sections",
     "is_road_ctx_create", "is_road_ctx_destroy", "is_road_ctx_device", "is_road_ctx_binary",
     "is_road_vdisparity_batch", "is_road_hough_batch",
+    "is_section_instance_labels", "is_render_sections",
 ]
+RENDER_MAX_LABELS = 64    # IS_RENDER_MAX_LABELS
+RENDER_MAX_CLASSES = 256  # IS_RENDER_MAX_CLASSES
 
 
 class InstanceBuffers(ctypes.Structure):
     _fields_ = [("d_centerofmass", ctypes.c_void_p), ("d_indices", ctypes.c_void_p),
                 ("d_core_candidates", ctypes.c_void_p), ("d_instances_per_class", ctypes.c_void_p),
                 ("d_labels", ctypes.c_void_p), ("d_packed", ctypes.c_void_p)]
+
+
+class RenderArgs(ctypes.Structure):
+    """is_render_args: zero-initialised by ctypes; device pointers as ints."""
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    _fields_ = [("d_sections", vp), ("d_section_instance", vp), ("n_images", ci), ("realcols", ci),
+                ("max_sections", ci), ("rows", ci), ("cols", ci), ("h_class_to_label", vp), ("n_classes", ci),
+                ("d_label", vp), ("d_disparity", vp), ("d_instance", vp), ("d_gt_label", vp), ("n_labels", ci),
+                ("d_confusion", vp), ("d_gt_disparity", vp), ("d_disp_abs_sum", vp), ("d_disp_count", vp),
+                ("d_stixel_count", vp)]
 
 
 class CoreError(RuntimeError):
@@ -87,6 +100,8 @@ def lib():
         L.is_road_vdisparity_batch.argtypes = [vp, vp, ci, cf, vp, vp, vp, vp]
         L.is_road_hough_batch.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]
         L.is_cluster_instances.argtypes = [vp, ctypes.POINTER(InstanceBuffers), vp]
+        L.is_section_instance_labels.argtypes = [ctypes.POINTER(InstanceBuffers), ci, ci, ci, vp, vp]
+        L.is_render_sections.argtypes = [ctypes.POINTER(RenderArgs), vp]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
         L.is_get_device.argtypes = [ctypes.POINTER(ci)]
@@ -347,6 +362,18 @@ def pack_sections_ptr(d_sections, n_columns, max_sections, d_counts, d_offsets, 
 def unpack_sections_ptr(d_counts, d_offsets, d_packed, n_columns, max_sections, d_sections, stream=0):
     _check(lib().is_unpack_sections(d_counts, d_offsets, d_packed, int(n_columns), int(max_sections),
                                     d_sections, stream), "is_unpack_sections")
+
+
+def render_sections_ptr(stream=0, class_to_label=None, **fields):
+    """is_render_sections on raw device pointers (ints): fields are those of RenderArgs (d_sections, n_images,
+    realcols, max_sections, rows, cols, d_label, ...); class_to_label: a host sequence of label values, None for
+    Cityscapes trainId -> labelId.  Asynchronous on `stream`."""
+    a = RenderArgs(**fields)
+    table = None
+    if class_to_label is not None:
+        table = np.ascontiguousarray(class_to_label, np.uint8)
+        a.h_class_to_label, a.n_classes = table.ctypes.data, table.size
+    _check(lib().is_render_sections(ctypes.byref(a), ctypes.c_void_p(int(stream))), "is_render_sections")
 
 
 def flip_and_pad(cnn_out, rows_power2_segmentation, device=0):

@@ -59,6 +59,9 @@ int isk_road_counters(void);
 hipError_t isk_set_lds_road_hough(int);
 hipError_t isk_launch_road_vdisparity(const float*, int*, uint8_t*, int*, int*, int, int, int, int, float,
                                       hipStream_t);
+int isk_render_scatter_images(void);
+hipError_t isk_launch_section_instance(const is_instance_buffers*, int, int, int, int, int32_t*, hipStream_t);
+hipError_t isk_launch_render(const is_render_args*, const uint8_t*, int, hipStream_t);
 hipError_t isk_launch_road_hough(const int*, const int*, int*, const float*, int2*, float*, int*, int*, int*, int,
                                  int, int, int, int, int, int, int, float, float, hipStream_t);
 }
@@ -687,6 +690,49 @@ int is_road_hough_batch(is_road_ctx* c, int n_images, int threshold, int max_lin
     HIP_TRY(isk_launch_road_hough(c->d_points, c->d_counters, c->d_ncand, c->d_tab, c->d_cand, d_lines, d_votes,
                                   d_total, d_overflow, n_images, c->rows * c->max_dis, c->numangle, c->numrho,
                                   c->band, threshold, max_candidates, max_lines, c->rho, c->theta, s));
+    return IS_OK;
+}
+
+/* ---- f5: render + score (is_k_render.hip) ---- */
+int is_section_instance_labels(const is_instance_buffers* per_image, int n_images, int realcols, int max_sections,
+                               int32_t* d_section_instance, void* stream) {
+    if (!per_image || !d_section_instance) return fail_arg("null pointer");
+    if (n_images < 1 || realcols < 1 || max_sections < 1) return fail_arg("empty shape");
+    for (int i = 0; i < n_images; i++)
+        if (!per_image[i].d_indices || !per_image[i].d_labels || !per_image[i].d_instances_per_class)
+            return fail_arg("d_indices, d_labels and d_instances_per_class are required for every image");
+    const hipStream_t s = (hipStream_t)stream;
+    const size_t cs = (size_t)realcols * max_sections;
+    HIP_TRY(hipMemsetAsync(d_section_instance, 0xff, sizeof(int32_t) * cs * n_images, s));
+    const int chunk = isk_render_scatter_images();
+    for (int i = 0; i < n_images; i += chunk)
+        HIP_TRY(isk_launch_section_instance(per_image + i, n_images - i < chunk ? n_images - i : chunk, i, realcols,
+                                            max_sections, d_section_instance, s));
+    return IS_OK;
+}
+
+int is_render_sections(const is_render_args* a, void* stream) {
+    if (!a || !a->d_sections) return fail_arg("null sections");
+    if (a->n_images < 1 || a->realcols < 1 || a->rows < 1 || a->cols < a->realcols)
+        return fail_arg("bad shape (n_images >= 1, realcols >= 1, rows >= 1, cols >= realcols)");
+    if (a->max_sections < 1 || a->max_sections > 32767) return fail_arg("max_sections outside [1, 32767]");
+    if ((a->realcols + 64) / 64 > 65535 || (size_t)a->n_images * ((a->rows + 127) / 128) > 0x7fffffff)
+        return fail_arg("batch too large for one launch");
+    if ((uintptr_t)a->d_sections & 15) return fail_arg("d_sections must be 16-byte aligned");
+    if (!a->d_confusion != !a->d_gt_label) return fail_arg("d_confusion and d_gt_label go together");
+    if (a->d_confusion && (a->n_labels < 1 || a->n_labels > IS_RENDER_MAX_LABELS))
+        return fail_arg("n_labels outside [1, IS_RENDER_MAX_LABELS]");
+    if (!a->d_disp_abs_sum != !a->d_disp_count || !a->d_disp_abs_sum != !a->d_gt_disparity)
+        return fail_arg("d_gt_disparity, d_disp_abs_sum and d_disp_count go together");
+    if (a->h_class_to_label && (a->n_classes < 1 || a->n_classes > IS_RENDER_MAX_CLASSES))
+        return fail_arg("n_classes outside [1, IS_RENDER_MAX_CLASSES]");
+    /* Cityscapes trainId -> labelId (cityscapesscripts' labels.py, trainId2label[c].id) */
+    static const uint8_t kCityscapes[19] = {7, 8, 11, 12, 13, 17, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 31, 32, 33};
+    uint8_t table[IS_RENDER_MAX_CLASSES] = {0};
+    const uint8_t* src = a->h_class_to_label ? a->h_class_to_label : kCityscapes;
+    const int n_classes = a->h_class_to_label ? a->n_classes : 19;
+    memcpy(table, src, n_classes);
+    HIP_TRY(isk_launch_render(a, table, n_classes, (hipStream_t)stream));
     return IS_OK;
 }
 

@@ -29,6 +29,7 @@ EXPORTS = [
     "ire_create", "ire_destroy", "ire_initialize", "ire_finish", "ire_compute", "ire_get_binary",
     "ire_hough_lines", "ire_set_device", "ire_active_device", "ire_compute_device",
     "ish_get_input_disparity_on_device", "ire_compute_batch", "ire_set_batch_limits", "ire_batch_fallbacks",
+    "ish_render_batch",
 ]
 
 # Stixels::RoadParameters, what RoadEstimation::ComputeBatch writes per frame
@@ -103,6 +104,7 @@ def lib():
         L.ire_compute_batch.argtypes = [vp, vp, ci, vp, vp, vp]
         L.ire_set_batch_limits.argtypes = [vp, ci, ci]
         L.ire_batch_fallbacks.argtypes = [vp]
+        L.ish_render_batch.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp]
         L.ish_get_input_disparity_on_device.restype = vp
         _LIB = L
     return _LIB
@@ -273,6 +275,27 @@ class Stixels:
                                                  int(n_iter), int(bool(with_instances)),
                                                  ctypes.byref(t)), "time_compute_batch")
         return t.value
+
+    def RenderBatch(self, n, label=None, disparity=None, instance=None, gt_label=None, n_labels=34,
+                    confusion=None, gt_disparity=None, stream=0, class_to_label=None):
+        """Stixels::RenderBatch: frames 0 .. n-1 of the last Compute() / ComputeBatch() to dense per-pixel maps
+        and scores on the device (device pointers as ints, None = skipped; see is_render_sections):
+        label [n][rows][cols] u8 labelIds, disparity f32, instance i32; gt_label u8 with confusion
+        [n_labels][n_labels] u64 (added to); gt_disparity f32 for the deviation.  class_to_label: host table of
+        label values per semantic class (None: Cityscapes trainId -> labelId).
+        Returns (disp_abs_sum [n] f64, disp_count [n] i64, stixel_count [n] i32) as numpy arrays."""
+        n = int(n)
+        sums = np.zeros(max(n, 0), np.float64)
+        counts = np.zeros(max(n, 0), np.int64)
+        stixels = np.zeros(max(n, 0), np.int32)
+        table = None if class_to_label is None else np.ascontiguousarray(class_to_label, np.uint8)
+        p = lambda x: None if x is None else ctypes.c_void_p(int(x))  # noqa: E731
+        self._check(lib().ish_render_batch(
+            self._h, n, p(label), p(disparity), p(instance), p(gt_label), int(n_labels), p(confusion),
+            p(gt_disparity), None if table is None else table.ctypes.data, 0 if table is None else table.size,
+            sums.ctypes.data, counts.ctypes.data, stixels.ctypes.data, ctypes.c_void_p(int(stream))),
+            "RenderBatch")
+        return sums, counts, stixels
 
     def GetInstanceStixels(self):
         cap = self.GetRealCols() * self.GetMaxSections()

@@ -15,6 +15,7 @@
 #include <fstream>
 #include <iostream>
 #include <stdexcept>
+#include <string>
 
 #include "DeviceGuard.h"
 
@@ -375,6 +376,12 @@ void Stixels::Finish() { /* Stixels.cu:250-283 */
     IS_CHECK_RETURN(is_device_free(d_all_counts));
     IS_CHECK_RETURN(is_device_free(d_all_packed));
     IS_CHECK_RETURN(is_device_free(d_all_sections));
+    IS_CHECK_RETURN(is_device_free(d_section_instance));
+    IS_CHECK_RETURN(is_device_free(d_render_results));
+    if (h_render_results) IS_CHECK_RETURN(is_host_free(h_render_results));
+    d_section_instance = nullptr; d_render_results = nullptr; h_render_results = nullptr;
+    m_render_images = 0;
+    m_render_instances = false;
     d_pack_counts = d_pack_offsets = d_all_counts = nullptr;
     d_pack_sections = d_all_packed = d_all_sections = nullptr;
     m_all_columns_cap = m_all_packed_cap = 0;
@@ -466,6 +473,8 @@ float Stixels::Compute(const bool pairwise, StixelsData& stixels_data,
                                g.normalization.data(), g.inv_sigma2.data(), &m_vhor,
                                pairwise ? 1 : 0, 1, d_stixels, &ib, nullptr, nullptr,
                                m_stream)); /* :535-590 */
+    m_render_images = 1;
+    m_render_instances = true;
     /* results into pinned memory, ONE copy and ONE synchronisation (:600, :629-633): the header
      * row(s) with the per-class counts and the first m_head_sections sections of every column (a
      * column rarely has more: 10-40 on road scenes) */
@@ -548,6 +557,8 @@ void Stixels::ComputeBatch(bool pairwise, int n_images, const pixel_t* d_big,
     IS_CHECK_RETURN(is_compute(m_ctx, d_disparity, d_seg, gf.data(), ng.data(), ig.data(),
                                vh.data(), pairwise ? 1 : 0, n_images, d_stixels,
                                instance_stixels ? ibs.data() : nullptr, nullptr, nullptr, stream));
+    m_render_images = n_images;
+    m_render_instances = instance_stixels != nullptr;
     /* Results to the host COMPACTED and through pinned memory: a column uses 10-60 of its 200 slots, and the
      * reference's fixed-stride copy (Stixels.cu:629-633: one frame) would move 1.6 MB per frame into pageable
      * vectors.  is_pack_sections leaves per-column offsets + the used sections; two pinned copies (the offsets, then
@@ -610,6 +621,71 @@ void Stixels::ComputeBatch(bool pairwise, int n_images, const pixel_t* d_big,
     m_labels_on_host = false;
 }
 
+std::vector<Stixels::RenderResult> Stixels::RenderBatch(int n_images, const RenderTargets& t, void* stream) {
+    if (m_render_images == 0)
+        throw std::invalid_argument("RenderBatch renders the Sections of the last Compute() or ComputeBatch(): "
+                                    "there are none.");
+    if (n_images < 1 || n_images > m_render_images)
+        throw std::invalid_argument("RenderBatch: n_images outside [1, frames of the last compute call].");
+    if (t.instance != nullptr && !m_render_instances)
+        throw std::invalid_argument("RenderBatch: an instance image needs a compute call with instances.");
+    const DeviceGuard guard(m_ctx_device);
+    if (stream == nullptr) stream = m_stream;
+    const size_t B = (size_t)m_max_batch;
+    const size_t res_bytes = B * (sizeof(double) + sizeof(int64_t) + sizeof(int32_t));
+    if (d_render_results == nullptr) {
+        IS_CHECK_RETURN(is_device_malloc((void**)&d_render_results, res_bytes));
+        IS_CHECK_RETURN(is_host_malloc((void**)&h_render_results, res_bytes));
+    }
+    double* d_sum = (double*)d_render_results;
+    int64_t* d_cnt = (int64_t*)(d_render_results + B * sizeof(double));
+    int32_t* d_nst = (int32_t*)(d_render_results + B * (sizeof(double) + sizeof(int64_t)));
+    is_render_args a = {};
+    a.d_sections = d_stixels;
+    a.n_images = n_images;
+    a.realcols = m_realcols;
+    a.max_sections = m_max_sections;
+    a.rows = m_rows;
+    a.cols = m_cols;
+    a.h_class_to_label = t.class_to_label;
+    a.n_classes = t.n_classes;
+    a.d_label = t.label;
+    a.d_disparity = t.disparity;
+    a.d_instance = t.instance;
+    a.d_gt_label = t.gt_label;
+    a.n_labels = t.n_labels;
+    a.d_confusion = t.confusion;
+    if (t.gt_disparity) {
+        a.d_gt_disparity = t.gt_disparity;
+        a.d_disp_abs_sum = d_sum;
+        a.d_disp_count = d_cnt;
+    } else {
+        IS_CHECK_RETURN(is_memset(d_sum, 0, B * (sizeof(double) + sizeof(int64_t)), stream));
+    }
+    a.d_stixel_count = d_nst;
+    if (t.instance) { /* the cluster labels of every frame as a per-section map */
+        if (d_section_instance == nullptr)
+            IS_CHECK_RETURN(is_device_malloc((void**)&d_section_instance,
+                                             B * m_realcols * m_max_sections * sizeof(int32_t)));
+        std::vector<is_instance_buffers> ibs;
+        for (int i = 0; i < n_images; i++) ibs.push_back(InstanceBuffers(i));
+        IS_CHECK_RETURN(is_section_instance_labels(ibs.data(), n_images, m_realcols, m_max_sections,
+                                                   d_section_instance, stream));
+        a.d_section_instance = d_section_instance;
+    }
+    const int rc = is_render_sections(&a, stream);
+    if (rc == IS_EINVAL) throw std::invalid_argument(std::string("RenderBatch: ") + is_last_error());
+    IS_CHECK_RETURN(rc);
+    IS_CHECK_RETURN(is_memcpy_d2h(h_render_results, d_render_results, res_bytes, stream));
+    IS_CHECK_RETURN(is_stream_synchronize(stream));
+    const double* h_sum = (const double*)h_render_results;
+    const int64_t* h_cnt = (const int64_t*)(h_render_results + B * sizeof(double));
+    const int32_t* h_nst = (const int32_t*)(h_render_results + B * (sizeof(double) + sizeof(int64_t)));
+    std::vector<RenderResult> out(n_images);
+    for (int i = 0; i < n_images; i++) out[i] = RenderResult{h_sum[i], h_cnt[i], h_nst[i]};
+    return out;
+}
+
 /* the packed payload of a batch (ComputeBatch, ComputeBatchGather): allocated on first use, released by Finish */
 void Stixels::EnsurePackBuffers() {
     if (d_pack_counts != nullptr) return;
@@ -657,6 +733,7 @@ void Stixels::ComputeBatchGather(bool pairwise, int n_images, const pixel_t* d_b
     IS_CHECK_RETURN(is_join_columns(m_ctx, d_big, m_cols, m_median_join ? 1 : 0, d_disparity, n_images, stream));
     IS_CHECK_RETURN(is_compute(m_ctx, d_disparity, d_seg, gf.data(), ng.data(), ig.data(), vh.data(),
                                pairwise ? 1 : 0, n_images, d_stixels, nullptr, nullptr, nullptr, stream));
+    m_render_images = 0; /* (d_stixels now holds this rank's shard; RenderBatch renders Compute / ComputeBatch) */
 
     /* ---- pack: per-column counts + the used sections (10-40 of the 200 slots of a column) */
     EnsurePackBuffers();

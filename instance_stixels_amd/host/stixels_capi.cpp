@@ -264,6 +264,27 @@ int ish_time_compute_batch(void* h, int pairwise, int n_images, const float* d_b
     });
 }
 
+/* RenderBatch(): frames 0 .. n-1 of the last Compute() / ComputeBatch() to dense maps + scores (every device
+ * pointer optional; class_to_label: host [n_classes] or null for Cityscapes).  disp_abs_sum / disp_count /
+ * stixel_count: host [n] each. */
+int ish_render_batch(void* h, int n, uint8_t* label, float* disparity, int32_t* instance, const uint8_t* gt_label,
+                     int n_labels, unsigned long long* confusion, const float* gt_disparity,
+                     const uint8_t* class_to_label, int n_classes, double* disp_abs_sum, int64_t* disp_count,
+                     int32_t* stixel_count, void* stream) {
+    return guard([&] {
+        Stixels::RenderTargets t;
+        t.label = label; t.disparity = disparity; t.instance = instance;
+        t.gt_label = gt_label; t.n_labels = n_labels; t.confusion = confusion; t.gt_disparity = gt_disparity;
+        t.class_to_label = class_to_label; t.n_classes = n_classes;
+        const std::vector<Stixels::RenderResult> r = ((Stixels*)h)->RenderBatch(n, t, stream);
+        for (int i = 0; i < n; i++) {
+            disp_abs_sum[i] = r[i].disp_abs_sum;
+            disp_count[i] = r[i].disp_count;
+            stixel_count[i] = r[i].stixel_count;
+        }
+    });
+}
+
 int ish_set_device(void* h, int device) {
     return guard([&] { ((Stixels*)h)->SetDevice(device); });
 }
