@@ -24,7 +24,7 @@ size_t isk_pairwise_lds_bytes(const DevParams* P, int nwaves);
 hipError_t isk_launch_join(const float*, float*, int, int, int, int, int, int, float, int, hipStream_t);
 hipError_t isk_launch_prepare(const DevParams*, int, const float*, const int32_t*, const float*,
                               const int*, const float*, RowRec*, float*, int*, float*, PruneRec*, int*,
-                              hipStream_t, hipStream_t, hipEvent_t, hipEvent_t);
+                              hipStream_t);
 struct StepRec;
 hipError_t isk_launch_priors(const DevParams*, const float*, PriorRec*, int, hipStream_t);
 hipError_t isk_launch_dp_unary(const DevParams*, int, int, const RowRec*, const float*, const float*,
@@ -44,7 +44,6 @@ hipError_t isk_set_lds_unary(const DevParams*);
 hipError_t isk_set_lds_pairwise(const DevParams*, int);
 hipError_t isk_set_lds_backtrace(const DevParams*);
 int isk_debug_occupancy(const DevParams*, int);
-int isk_unary_uses_carry(const DevParams*, int);
 int isk_unary_uses_fused_lut(const DevParams*, int);
 hipError_t isk_launch_cluster(int, float, int, int, const is_instance_buffers*,
                               const is_instance_buffers*, int32_t*, hipStream_t);
@@ -90,19 +89,6 @@ extern "C" int isk_fail(int code, const char* msg) {
     } while (0)
 
 #define IS_STAGE_SLOTS 4 /* pinned staging ring of the per-frame ground model */
-#define IS_GRAPH_MAX_IMAGES 8 /* calls of up to that many images are replayed as hipGraphs */
-#define IS_GRAPH_ENTRIES 4    /* distinct argument sets remembered per context */
-struct is_graph_entry {
-    bool valid;
-    const void *joined, *seg, *sections, *ct, *it;
-    int pairwise, n_images, n_inst;
-    int win_tiles; /* the windowed / classic tile split of the captured launches (a function of the call's horizons) */
-    is_instance_buffers inst[IS_GRAPH_MAX_IMAGES];
-    int slot; /* the pinned staging slot baked into the copy nodes */
-    hipGraphExec_t exec;
-    unsigned long long last_use;
-};
-
 
 struct is_ctx {
     is_stixel_params params;
@@ -134,19 +120,14 @@ struct is_ctx {
     hipEvent_t staging_free[IS_STAGE_SLOTS]; /* recorded after the H2D copies of the slot's call */
     bool staging_pending[IS_STAGE_SLOTS];
     int stage_next;
-    hipStream_t aux_stream;  /* = aux_streams[0]: second stream of the prepare kernels */
     hipStream_t aux_streams[IS_AUX_STREAMS]; /* column groups of the pairwise DP in flight */
-    hipEvent_t ev_fork, ev_join;
+    hipEvent_t ev_fork;
     hipEvent_t ev_joins[IS_AUX_STREAMS];
     int32_t* d_cluster_scratch; /* [max_batch][8][2][C*S] work arrays of k_cluster_instances */
     is_instance_buffers* d_inst_tbl; /* [max_batch] device copy of the caller's per-image arrays */
     int* d_inst_cnt;            /* [max_batch*C][8] instance candidates per column and class */
     unsigned long long* d_counters; /* [IS_CNT_N] evaluation counters (is_set_eval_counters) */
     bool counting;
-    /* hipGraph replay of small calls (see is_compute) */
-    bool graphs;
-    unsigned long long graph_clock;
-    struct is_graph_entry* graph_cache; /* [IS_GRAPH_ENTRIES] */
     /* scratch */
     RowRec* d_recs;          /* [max_batch*C][H+1] */
     float* d_lutT;           /* [max_batch*C][H+1][D] */
@@ -284,9 +265,6 @@ static int ctx_init(is_ctx* c, const is_stixel_params* p, const float* obj_cost_
     c->params = *p;
     c->device = device;
     c->max_batch = max_batch;
-    c->graphs = getenv("IS_GRAPH") != nullptr; /* opt-in: measured slower than eager launches (see is_compute) */
-    c->graph_cache = (is_graph_entry*)calloc(IS_GRAPH_ENTRIES, sizeof(is_graph_entry));
-    if (!c->graph_cache) return IS_ENOMEM;
 
     DevParams& d = c->dp;
     d.H = p->rows; d.C = p->cols; d.D = p->max_dis; d.P2 = P2; d.P2S = P2S;
@@ -318,16 +296,10 @@ static int ctx_init(is_ctx* c, const is_stixel_params* p, const float* obj_cost_
     const bool debug = getenv("IS_DEBUG") != nullptr;
     {
         auto knob = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : -1; };
-        d.knob_ring_kernel = getenv("IS_NO_RING_KERNEL") ? 0 : -1;
-        d.knob_prepare_overlap = knob("IS_PREPARE_OVERLAP");
-        d.knob_p2_lds_floor = knob("IS_P2_LDS");
         d.knob_pw_groups = knob("IS_PW_GROUPS");
         d.knob_p2_split = knob("IS_P2_SPLIT");
         d.knob_p2x = knob("IS_P2X");
-        d.knob_unary_diag = knob("IS_UNARY_DIAG") == 1; /* (experiment: off unless asked for) */
         d.knob_win_tiles = knob("IS_P1_WIN_TILES");
-        d.knob_pw_waves = knob("IS_PW_WAVES");
-        d.knob_lut_carry = knob("IS_LUT_CARRY"); /* carry-only lutT (is_device.h): opt-in */
         d.knob_lut_fused = knob("IS_LUT_FUSED"); /* the LUT units inside the unary DP launch (is_k_unary_fast.hip, LUTF) */
     }
     {
@@ -356,8 +328,6 @@ static int ctx_init(is_ctx* c, const is_stixel_params* p, const float* obj_cost_
     /* waves per DP workgroup: the LUT tile is 64*(D+1) floats; keep >= 16 waves per CU */
     c->nwaves_unary = IS_UNARY_WAVES;
     c->nwaves_pairwise = IS_UNARY_WAVES;
-    if (d.knob_pw_waves >= 1 && d.knob_pw_waves <= IS_UNARY_WAVES) c->nwaves_pairwise = d.knob_pw_waves;
-    else d.knob_pw_waves = -1;
     if (sizeof(int) * (6 * (size_t)d.H + 3 * (size_t)d.S + 4) > 160 * 1024 ||
         isk_unary_lds_bytes(&d) > 160 * 1024 || isk_pairwise_lds_bytes(&d, c->nwaves_pairwise) > 160 * 1024 ||
         isk_prepare_lds_bytes(&d) > 160 * 1024 || isk_phase2_lds_bytes(&d) > 64 * 1024 ||
@@ -426,9 +396,7 @@ static int ctx_init(is_ctx* c, const is_stixel_params* p, const float* obj_cost_
         HIP_TRY(hipStreamCreateWithFlags(&c->aux_streams[i], hipStreamNonBlocking));
         HIP_TRY(hipEventCreateWithFlags(&c->ev_joins[i], hipEventDisableTiming));
     }
-    c->aux_stream = c->aux_streams[0];
     HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
     for (int i = 0; i < 4; i++) HIP_TRY(hipEventCreate(&c->ev[i]));
 
     {
@@ -471,11 +439,6 @@ int is_ctx_destroy(is_ctx* c) {
     if (!c) return IS_OK;
     DeviceScope scope(c->device);
     (void)hipDeviceSynchronize();
-    if (c->graph_cache) {
-        for (int i = 0; i < IS_GRAPH_ENTRIES; i++)
-            if (c->graph_cache[i].valid) (void)hipGraphExecDestroy(c->graph_cache[i].exec);
-        free(c->graph_cache);
-    }
     (void)hipFree(c->d_obj_cost_lut); (void)hipFree(c->d_odr); (void)hipFree(c->d_rcp); (void)hipFree(c->d_col_flags); (void)hipFree(c->d_prune); (void)hipFree(c->d_n_generic); (void)hipFree(c->d_stage);
     (void)hipFree(c->d_recs); (void)hipFree(c->d_lutT); (void)hipFree(c->d_priors); (void)hipFree(c->d_steps); (void)hipFree(c->d_part_cost); (void)hipFree(c->d_part_idx); (void)hipFree(c->d_sv); (void)hipFree(c->d_blksum); (void)hipFree(c->d_t8row); (void)hipFree(c->dp.win_lo); (void)hipFree(c->dp.lut_ready); (void)hipFree(c->dp.lutf_bad);
     if (c->h_lutf_repairs) (void)hipHostFree(c->h_lutf_repairs);
@@ -490,7 +453,6 @@ int is_ctx_destroy(is_ctx* c) {
         if (c->ev_joins[i]) (void)hipEventDestroy(c->ev_joins[i]);
     }
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     for (int i = 0; i < 4; i++)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     free(c);
@@ -820,7 +782,7 @@ int is_get_kernel_times_ms(is_ctx* c, float* prepare_ms, float* dp_ms, float* ba
  * horizon mixes sky (d ~ 0) with objects of any disparity -- measured: 3.6 % of the steps of tile 7 read
  * outside the window, 22-35 % of tiles 12-13, and a step with a lane outside pays a memory round trip.
  * The split decides launch geometry only (workgroup shapes, which kernel instantiation a tile runs), never
- * results; a hipGraph replays the split it was captured with, so it is part of the graph cache's key. */
+ * results. */
 static int call_win_tiles(const DevParams& P, const int* h_vhor, int n_images, int pairwise) {
     int vmin = P.H;
     for (int i = 0; i < n_images; i++) vmin = h_vhor[i] < vmin ? h_vhor[i] : vmin;
@@ -834,16 +796,14 @@ static int call_win_tiles(const DevParams& P, const int* h_vhor, int n_images, i
     return w;
 }
 
-/* Everything is_compute queues on `stream` behind the host-side staging of slot `slot`.
- * `capturing`: the calls are being recorded into a hipGraph -- no timing events, no staging
- * event (the caller records it behind the graph launch). */
+/* Everything is_compute queues on `stream` behind the host-side staging of slot `slot`. */
 static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_seg, int pairwise, int n_images,
                            is_section* d_sections, const is_instance_buffers* instances, float* d_cost_table,
-                           int32_t* d_index_table, hipStream_t stream, int slot, bool capturing) {
+                           int32_t* d_index_table, hipStream_t stream, int slot) {
     const DevParams& P = c->dp;
     const size_t H = P.H;
     const int ncols = n_images * P.C;
-    const bool timing = c->timing && !capturing;
+    const bool timing = c->timing;
     const bool one_copy = n_images == c->max_batch;
     if (one_copy) {
         HIP_TRY(hipMemcpyAsync(c->d_stage, c->h_stage[slot], c->stage_bytes, hipMemcpyHostToDevice, stream));
@@ -864,15 +824,14 @@ static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_se
     if (want_inst && !one_copy) /* the per-image output pointers travel through the pinned staging slot of this call */
         HIP_TRY(hipMemcpyAsync(c->d_inst_tbl, c->h_inst_pinned[slot], sizeof(is_instance_buffers) * n_images,
                                hipMemcpyHostToDevice, stream));
-    if (!capturing) HIP_TRY(hipEventRecord(c->staging_free[slot], stream));
+    HIP_TRY(hipEventRecord(c->staging_free[slot], stream));
 
     float* ct = d_cost_table ? d_cost_table : c->d_cost_table;
     int32_t* it = d_index_table ? d_index_table : c->d_index_table;
 
     DevParams Pw = P; /* (+ this call's windowed / classic tile split and the form of lutT) */
     Pw.win_tiles = call_win_tiles(P, c->h_vhor_pinned[slot], n_images, pairwise);
-    Pw.lut_carry = (!pairwise && isk_unary_uses_carry(&Pw, ncols)) ? 1 : 0;
-    Pw.lut_fused = (!pairwise && !capturing) ? isk_unary_uses_fused_lut(&Pw, ncols) : 0;
+    Pw.lut_fused = !pairwise ? isk_unary_uses_fused_lut(&Pw, ncols) : 0;
     /* a hand-over of this context has been distrusted before (another dispatcher, a partition mode, a CU mask): the
      * fused launch stays off unless IS_LUT_FUSED asks for it by value -- a repaired call costs 2.8 x an ordinary one */
     if (Pw.lut_fused && (P.knob_lut_fused < 0 || P.knob_lut_fused == 3) && c->h_lutf_repairs && *(volatile int*)c->h_lutf_repairs > 0) Pw.lut_fused = 0;
@@ -880,7 +839,7 @@ static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_se
     /* (d_n_generic is zero here: cleared at creation and by k_backtrace at the end of every call) */
     HIP_TRY(isk_launch_prepare(&Pw, ncols, d_joined, d_seg, c->d_ground, c->d_vhor,
                                c->d_obj_cost_lut, c->d_recs, c->d_lutT, c->d_col_flags, c->d_sv,
-                               c->d_prune, c->d_n_generic, stream, c->aux_stream, c->ev_fork, c->ev_join));
+                               c->d_prune, c->d_n_generic, stream));
     if (pairwise) HIP_TRY(isk_launch_priors(&P, c->d_ground, c->d_priors, n_images, stream));
     if (timing) HIP_TRY(hipEventRecord(c->ev[1], stream));
     if (pairwise)
@@ -913,28 +872,6 @@ static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_se
     return IS_OK;
 }
 
-/* ---- hipGraph replay of small calls (opt-in: IS_GRAPH=1) ----------------------------------------
- * A single frame is ~15 queue operations (copies, a memset, 6-38 kernels) of a few microseconds
- * each.  The whole sequence of a call only depends on the pointers and sizes the caller passes, so
- * calls of up to IS_GRAPH_MAX_IMAGES images can be captured once per distinct argument set and
- * replayed with one hipGraphLaunch; the per-frame host data (ground model, horizon) still travels
- * through the pinned staging slot the graph's copy nodes read.  MEASURED (round 3, ROCm 7.2, one
- * 1024x2048 frame through Stixels::Compute): 0.455 ms replayed against 0.400 ms launched eagerly
- * (pairwise 1.92 vs 1.91 ms) -- the gaps between dependent dispatches are the GPU's, not the
- * host's, and a replay adds its own launch cost; so the path is off unless IS_GRAPH is set
- * (bit-exact on the whole GPU suite).  Needs a real stream: the legacy NULL stream cannot be captured.
- * A cached graph owns ONE pinned staging slot (its copy nodes read it): every replay waits on the host
- * for the previous replay's staging event before it refills the slot, i.e. replays of one graph
- * serialise on that copy. */
-static bool graph_matches(const is_graph_entry& e, const float* d_joined, const int32_t* d_seg, int pairwise,
-                          int n_images, const is_section* d_sections, const is_instance_buffers* instances,
-                          const float* ct, const int32_t* it, int win_tiles) {
-    if (!e.valid || e.win_tiles != win_tiles || e.joined != d_joined || e.seg != d_seg || e.sections != d_sections || e.ct != ct ||
-        e.it != it || e.pairwise != pairwise || e.n_images != n_images || e.n_inst != (instances ? n_images : 0))
-        return false;
-    return !instances || memcmp(e.inst, instances, sizeof(is_instance_buffers) * n_images) == 0;
-}
-
 int is_compute(is_ctx* c, const float* d_joined, const int32_t* d_seg, const float* h_gf,
                const float* h_ng, const float* h_is2, const int* h_vhor, int pairwise, int n_images,
                is_section* d_sections, const is_instance_buffers* instances, float* d_cost_table,
@@ -953,26 +890,10 @@ int is_compute(is_ctx* c, const float* d_joined, const int32_t* d_seg, const flo
     hipStream_t stream = (hipStream_t)stream_;
     const size_t H = c->dp.H;
 
-    /* a cached graph of exactly this call?  (its staging slot is part of the graph) */
-    const bool graph_ok = c->graphs && stream != nullptr && n_images <= IS_GRAPH_MAX_IMAGES && !c->timing &&
-                          !c->counting;
-    is_graph_entry* ge = nullptr;
-    const int win_tiles = call_win_tiles(c->dp, h_vhor, n_images, pairwise);
-    if (graph_ok)
-        for (int i = 0; i < IS_GRAPH_ENTRIES; i++)
-            if (graph_matches(c->graph_cache[i], d_joined, d_seg, pairwise, n_images, d_sections, instances,
-                              d_cost_table, d_index_table, win_tiles))
-                ge = &c->graph_cache[i];
-
     /* stage the per-frame ground model (the reference does 3 blocking cudaMemcpy per frame,
      * Stixels.cu:479-493): pinned + async here, through a ring of slots each guarded by an event */
-    int slot;
-    if (ge) {
-        slot = ge->slot;
-    } else {
-        slot = c->stage_next;
-        c->stage_next = (slot + 1) % IS_STAGE_SLOTS;
-    }
+    const int slot = c->stage_next;
+    c->stage_next = (slot + 1) % IS_STAGE_SLOTS;
     if (c->staging_pending[slot]) HIP_TRY(hipEventSynchronize(c->staging_free[slot]));
     for (int i = 0; i < n_images; i++) {
         float* dst = c->h_ground_pinned[slot] + (size_t)i * 3 * H;
@@ -986,54 +907,9 @@ int is_compute(is_ctx* c, const float* d_joined, const int32_t* d_seg, const flo
     if (instances) memcpy(c->h_inst_pinned[slot], instances, sizeof(is_instance_buffers) * n_images);
     else memset(c->h_inst_pinned[slot], 0, sizeof(is_instance_buffers) * n_images);
 
-    if (graph_ok && !ge) { /* first call with these arguments: record it */
-        is_graph_entry* victim = &c->graph_cache[0];
-        for (int i = 1; i < IS_GRAPH_ENTRIES; i++)
-            if (!c->graph_cache[i].valid || (victim->valid && c->graph_cache[i].last_use < victim->last_use))
-                victim = &c->graph_cache[i];
-        if (victim->valid) {
-            (void)hipGraphExecDestroy(victim->exec);
-            victim->valid = false;
-        }
-        hipGraph_t graph = nullptr;
-        hipError_t e = hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed);
-        if (e == hipSuccess) {
-            const int rc = compute_enqueue(c, d_joined, d_seg, pairwise, n_images, d_sections, instances,
-                                           d_cost_table, d_index_table, stream, slot, true);
-            e = hipStreamEndCapture(stream, &graph);
-            if (rc == IS_OK && e == hipSuccess && graph) {
-                hipGraphExec_t exec = nullptr;
-                e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-                if (e == hipSuccess) {
-                    victim->valid = true;
-                    victim->joined = d_joined; victim->seg = d_seg; victim->sections = d_sections;
-                    victim->ct = d_cost_table; victim->it = d_index_table;
-                    victim->pairwise = pairwise; victim->n_images = n_images;
-                    victim->win_tiles = win_tiles;
-                    victim->n_inst = instances ? n_images : 0;
-                    if (instances) memcpy(victim->inst, instances, sizeof(is_instance_buffers) * n_images);
-                    victim->slot = slot;
-                    victim->exec = exec;
-                    ge = victim;
-                }
-            }
-            if (graph) (void)hipGraphDestroy(graph);
-        }
-        if (!ge) { /* capture is not available here: never try again on this context */
-            (void)hipGetLastError();
-            c->graphs = false;
-        }
-    }
-    if (ge) {
-        ge->last_use = ++c->graph_clock;
-        HIP_TRY(hipGraphLaunch(ge->exec, stream));
-        HIP_TRY(hipEventRecord(c->staging_free[slot], stream));
-        c->staging_pending[slot] = true;
-        return IS_OK;
-    }
     c->staging_pending[slot] = true;
     const int rc = compute_enqueue(c, d_joined, d_seg, pairwise, n_images, d_sections, instances, d_cost_table,
-                                   d_index_table, stream, slot, false);
+                                   d_index_table, stream, slot);
     /* Invariant the early-outs of k_dp_unary / k_pw_phase2_generic rely on: d_n_generic is zero
      * between calls (k_prepare counts the generic columns of a call, block 0 of k_backtrace clears
      * the counter at its end).  A call that failed half way may have counted without clearing. */

@@ -173,15 +173,10 @@ struct DevParams {
     float gamma2;
     /* host-side launch knobs: the IS_* environment variables, read ONCE in is_ctx_create (never
      * per call); -1 = automatic.  The kernels ignore them. */
-    int knob_ring_kernel;     /* IS_NO_RING_KERNEL=1 -> 0: unary FAST columns through k_dp_unary */
-    int knob_prepare_overlap; /* IS_PREPARE_OVERLAP: 0 = two prepare launches in order, 1 = on two streams, 2 / unset = one fused launch */
-    int knob_p2_lds_floor;    /* IS_P2_LDS: floor on phase 2's LDS allocation (occupancy throttle) */
     int knob_pw_groups;       /* IS_PW_GROUPS: column groups (streams) of the pairwise DP */
     int knob_p2_split;        /* IS_P2_SPLIT: 1 = k_pw_phase2s, 0 = k_pw_phase2 */
     int knob_p2x;             /* IS_P2X=0: large batches walk phase 2 with k_pw_phase2 (one column per wave) */
     int knob_win_tiles;       /* IS_P1_WIN_TILES: number of phase-1 tiles that stage an fn window (-1: those below the horizon) */
-    int knob_pw_waves;        /* IS_PW_WAVES: waves per phase-1 workgroup for every tile (-1: 8, windowed tiles IS_P1_WIN_WAVES) */
-    int knob_unary_diag;      /* IS_UNARY_DIAG=1: the diagonal blocks of the unary DP in k_dp_unary_diag (two columns per wave) */
     /* fn windows of the DP kernels (IS_P1_WIN): [n_columns][ntiles] first lutT column of the window a
      * (column, tile) stages in LDS; written by the prepare kernel, device memory of the context */
     int* win_lo;
@@ -205,10 +200,6 @@ struct DevParams {
                          * 3 = (tests) the default policy (-1) with the wrong id of 2: the first large call is repaired, and the
                          * context then keeps the table in the prepare launch (DevParams::lutf_repairs) */
     int lut_fused;      /* set per call: 0, 1, or 2 (the test mode) */
-    int knob_lut_carry; /* IS_LUT_CARRY=1: carry rows only wherever the DP can rebuild the rest (unary calls whose every
-                         * tile runs the windowed ring kernel); default: lutT is materialised (measured faster) */
-    int lut_carry;      /* set per call: k_object_lut stores only the rows 32 k of lutT (the carries of its 32-row
-                         * blocks, 1/32 of the table); the DP rebuilds the rows it reads (is_k_unary_fast.hip, GEN) */
 };
 
 /* fn windows (k_dp_unary_fast, k_pw_phase1).  A (column, tile) workgroup keeps lutT[vT + 1][*] of its 64 rows in

@@ -2449,11 +2449,8 @@ static size_t p1_lds_bytes(const DevParams* P, int nwaves, bool windowed) {
 }
 size_t isk_pairwise_lds_bytes(const DevParams* P, int nwaves) { return p1_lds_bytes(P, nwaves, false); }
 size_t isk_phase2_lds_bytes(const DevParams* P) {
-    size_t need = sizeof(double) * 2 * IS_LOG_TABLE_SIZE +
-                  sizeof(float) * (P->D + (IS_TILE + 1) + (size_t)ISP2_ROWS * ISP2_WS) + 16;
-    /* IS_P2_LDS: a floor on the allocation = an occupancy throttle for experiments */
-    const size_t floor_bytes = P->knob_p2_lds_floor > 0 ? (size_t)P->knob_p2_lds_floor : 0;
-    return need > floor_bytes ? need : floor_bytes;
+    return sizeof(double) * 2 * IS_LOG_TABLE_SIZE +
+           sizeof(float) * (P->D + (IS_TILE + 1) + (size_t)ISP2_ROWS * ISP2_WS) + 16;
 }
 
 size_t isk_phase2x_lds_bytes(const DevParams* P) {
@@ -2483,8 +2480,7 @@ hipError_t isk_launch_dp_pairwise(const DevParams* P, int ncols, int nwaves, con
                                   hipEvent_t ev_fork, hipEvent_t* ev_join) {
     /* windowed tiles (P->win_tiles): IS_P1_WIN_WAVES waves per workgroup -- the smaller LDS footprint lets a CU
      * hold more, smaller workgroups (measured at D = 64: 4 waves x 4 workgroups beat 8 x 3 on every tile) */
-    int nwaves_win = IS_P1_WIN_WAVES < nwaves ? IS_P1_WIN_WAVES : nwaves;
-    if (P->knob_pw_waves > 0) nwaves_win = nwaves; /* (experiments: one wave count for all tiles) */
+    const int nwaves_win = IS_P1_WIN_WAVES < nwaves ? IS_P1_WIN_WAVES : nwaves;
     const size_t lds2 = isk_phase2_lds_bytes(P);
     /* Columns are independent: with enough of them the batch is cut into groups whose
      * phase-1 / phase-2 chains (2 x ntiles dependent launches each) run on their own streams, so

@@ -728,7 +728,7 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prepare_columns(
  * transposed cost table and every store of a lutT row is one fully coalesced 256-byte access. */
 #define LUT_BLOCK 32
 /* The table is 8.6 GB for a batch of 64 (1024 x 2048 x 128): its stores ARE the kernel.  Measured (batch 64,
- * k_object_lut alone, tools/abl_prep.sh): 1.78 ms = 4.8 TB/s with plain stores; the same instruction stream
+ * the LUT units as a kernel of their own, tools/abl_prep.sh): 1.78 ms = 4.8 TB/s with plain stores; the same instruction stream
  * with the stores wrapped into 8 rows per column (absorbed by the L2, PREP_ABL_WRAP) 0.48 ms; non-temporal
  * stores (full 256-byte rows that nothing reads before the whole table is written: no reason to keep them in
  * the L2 / MALL) 1.59 ms = 5.4 TB/s.  Storing fewer fn per row only pays in whole 128-byte lines
@@ -736,11 +736,6 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prepare_columns(
 #ifndef PREP_LUT_NT
 #define PREP_LUT_NT 1
 #endif
-/* carry_only (DevParams::lut_carry): only the rows 32 k -- the carries the 32-row blocks are chained through,
- * StixelsKernels.cu:268-272 -- are stored: 1/32 of the bytes.  The windowed unary ring kernel rebuilds the rows
- * it reads from them (the same network on the same values: bit-identical), generic columns get their whole table
- * from k_object_lut_generic afterwards. */
-template <bool CARRY_ONLY>
 __device__ __forceinline__ void object_lut_body(const DevParams& P, const int colg, const int fn_block,
                                                 const int lane, const float* __restrict__ joined,
                                                 const float* __restrict__ cost_T /*[dis][fn]*/,
@@ -802,9 +797,7 @@ __device__ __forceinline__ void object_lut_body(const DevParams& P, const int co
 #pragma unroll
             for (int l = LUT_BLOCK - 1; l >= j; l--) c[l] += c[l - j];
         }
-        if (CARRY_ONLY) {
-            if (fn_ok && i + LUT_BLOCK <= H) __builtin_nontemporal_store(c[LUT_BLOCK - 1], &lcol[(size_t)(i + LUT_BLOCK) * D + fn]);
-        } else if (full) {
+        if (full) {
 #pragma unroll
 #ifdef PREP_ABL_WRAP /* ablation: the same stores into 8 rows per column (absorbed by the L2): what do the HBM bytes cost */
             for (int l = 0; l < LUT_BLOCK; l++) lcol[(size_t)((i + l + 1) & 7) * D + fnc] = c[l];
@@ -829,13 +822,6 @@ __device__ __forceinline__ void object_lut_body(const DevParams& P, const int co
     if (i < H) block(i, false);
 }
 
-__global__ __launch_bounds__(64) void k_object_lut(const DevParams P,
-                                                   const float* __restrict__ joined,
-                                                   const float* __restrict__ cost_T,
-                                                   float* __restrict__ lutT) {
-    object_lut_body<false>(P, (int)blockIdx.x, (int)blockIdx.y, (int)threadIdx.x, joined, cost_T, lutT);
-}
-
 /* Behind a fused LUT + DP launch (k_dp_unary_fast, LUTF) whose workgroups could not trust the hand-over: the complete
  * table again, by the ordinary units.  Leaves at once while the word is 0 -- the normal case. */
 __global__ __launch_bounds__(64) void k_object_lut_repair(const DevParams P, int ncols, const float* __restrict__ joined,
@@ -845,27 +831,12 @@ __global__ __launch_bounds__(64) void k_object_lut_repair(const DevParams P, int
     const int fn_blocks = (P.D + 63) / 64;
     for (int u = (int)blockIdx.x; u < ncols * fn_blocks; u += (int)gridDim.x) {
         const int colg = u / fn_blocks;
-        object_lut_body<false>(P, colg, u - colg * fn_blocks, (int)threadIdx.x, joined, cost_T, lutT);
-    }
-}
-
-/* After a carry-only prepare: the complete table of the GENERIC columns (k_dp_unary reads it as it is).  A small
- * grid that leaves at once when the prepare kernel counted no generic column -- the normal case. */
-__global__ __launch_bounds__(64) void k_object_lut_generic(const DevParams P, int ncols, const float* __restrict__ joined,
-                                                           const float* __restrict__ cost_T, float* __restrict__ lutT,
-                                                           const int* __restrict__ col_flags,
-                                                           const int* __restrict__ n_generic) {
-    if (__builtin_amdgcn_readfirstlane(*n_generic) == 0) return;
-    const int fn_blocks = (P.D + 63) / 64;
-    for (int u = (int)blockIdx.x; u < ncols * fn_blocks; u += (int)gridDim.x) {
-        const int colg = u / fn_blocks;
-        if (__builtin_amdgcn_readfirstlane(col_flags[colg]) == 0) continue;
-        object_lut_body<false>(P, colg, u - colg * fn_blocks, (int)threadIdx.x, joined, cost_T, lutT);
+        object_lut_body(P, colg, u - colg * fn_blocks, (int)threadIdx.x, joined, cost_T, lutT);
     }
 }
 
 /* Both preparation kernels in ONE launch: a 256-thread workgroup is either one column of
- * k_prepare_columns (blocks 0 .. ncols - 1) or four (column, 64 fn) units of k_object_lut (the
+ * k_prepare_columns (blocks 0 .. ncols - 1) or four (column, 64 fn) units of object_lut_body (the
  * blocks after them).  A frame or a few: neither kernel fills the chip and both are latency chains
  * (59 + 45 us one after the other, 51 us together; on two streams they did not overlap in
  * practice).  A batch of 64: the LUT blocks start while the last column blocks drain, 2.85 instead
@@ -915,12 +886,8 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prepare_fused(
     if (is_lut) {
         const int fn_blocks = (P.D + 63) / 64;
         const int unit = lut_b * (PREP_THREADS / 64) + (int)(threadIdx.x >> 6);
-        if (unit < ncols * fn_blocks) {
-            if (P.lut_carry)
-                object_lut_body<true>(P, unit / fn_blocks, unit % fn_blocks, (int)(threadIdx.x & 63), joined, cost_T, lutT);
-            else
-                object_lut_body<false>(P, unit / fn_blocks, unit % fn_blocks, (int)(threadIdx.x & 63), joined, cost_T, lutT);
-        }
+        if (unit < ncols * fn_blocks)
+            object_lut_body(P, unit / fn_blocks, unit % fn_blocks, (int)(threadIdx.x & 63), joined, cost_T, lutT);
     } else {
         prepare_columns_body(P, col_b, smem, joined, seg, ground, vhor_arr, recs,
                              col_flags, sv_arr, prune, n_generic);
@@ -978,47 +945,17 @@ hipError_t isk_launch_prepare(const DevParams* P, int ncols, const float* joined
                               const int32_t* seg, const float* ground, const int* vhor,
                               const float* cost_T, RowRec* recs, float* lutT,
                               int* col_flags, float* sv_arr, PruneRec* prune, int* n_generic,
-                              hipStream_t stream,
-                              hipStream_t aux, hipEvent_t ev_fork, hipEvent_t ev_join) {
-    /* The two prepare kernels are independent: one launch with workgroups of both kinds
-     * (k_prepare_fused) by default.  IS_PREPARE_OVERLAP = 0: two launches in order on one stream,
-     * 1: two launches on two streams (did not overlap in practice), 2: the default. */
-    const bool side_by_side = aux != nullptr && P->knob_prepare_overlap == 1;
-    hipError_t e;
+                              hipStream_t stream) {
     if (P->lut_fused) { /* the LUT units run inside the unary DP launch (k_dp_unary_fast, LUTF): records only here */
         hipLaunchKernelGGL(k_prepare_columns, dim3(ncols), dim3(PREP_THREADS), isk_prepare_lds_bytes(P), stream, *P,
                            joined, seg, ground, vhor, recs, col_flags, sv_arr, prune, n_generic);
         return hipGetLastError();
     }
-    const bool fused = P->knob_prepare_overlap == 2 || P->knob_prepare_overlap < 0;
-    if (fused) {
-        const int units = ncols * ((P->D + 63) / 64);
-        const int n_lut = (units + PREP_THREADS / 64 - 1) / (PREP_THREADS / 64);
-        hipLaunchKernelGGL(k_prepare_fused, dim3(ncols + n_lut), dim3(PREP_THREADS),
-                           isk_prepare_lds_bytes(P), stream, *P, ncols, n_lut, joined, seg, ground, vhor,
-                           cost_T, recs, lutT, col_flags, sv_arr, prune, n_generic);
-        if (P->lut_carry) {
-            const int g = units < 2048 ? units : 2048;
-            hipLaunchKernelGGL(k_object_lut_generic, dim3(g), dim3(64), 0, stream, *P, ncols, joined, cost_T, lutT,
-                               col_flags, n_generic);
-        }
-        return hipGetLastError();
-    }
-    hipStream_t lut_stream = stream;
-    if (side_by_side) {
-        if ((e = hipEventRecord(ev_fork, stream)) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(aux, ev_fork, 0)) != hipSuccess) return e;
-        lut_stream = aux;
-    }
-    hipLaunchKernelGGL(k_object_lut, dim3(ncols, (P->D + 63) / 64), dim3(64), 0, lut_stream, *P,
-                       joined, cost_T, lutT);
-    hipLaunchKernelGGL(k_prepare_columns, dim3(ncols), dim3(PREP_THREADS),
-                       isk_prepare_lds_bytes(P), stream, *P, joined, seg, ground, vhor, recs,
-                       col_flags, sv_arr, prune, n_generic);
-    if (side_by_side) {
-        if ((e = hipEventRecord(ev_join, aux)) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(stream, ev_join, 0)) != hipSuccess) return e;
-    }
+    /* the two prepare kernels are independent: one launch with workgroups of both kinds (k_prepare_fused) */
+    const int units = ncols * ((P->D + 63) / 64);
+    const int n_lut = (units + PREP_THREADS / 64 - 1) / (PREP_THREADS / 64);
+    hipLaunchKernelGGL(k_prepare_fused, dim3(ncols + n_lut), dim3(PREP_THREADS), isk_prepare_lds_bytes(P), stream, *P,
+                       ncols, n_lut, joined, seg, ground, vhor, cost_T, recs, lutT, col_flags, sv_arr, prune, n_generic);
     return hipGetLastError();
 }
 

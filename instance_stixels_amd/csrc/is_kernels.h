@@ -9,7 +9,8 @@
  *                       k_flip_and_pad, k_vdisp_*  
  *   is_k_prepare.hip    k_prepare_columns   A4-A6 StixelsKernels.cu:371-469 and
  *                                           StixelsKernels.h:73-103: per-row boundary records
- *                       k_object_lut        A4   StixelsKernels.cu:236-296, 959-978
+ *                       k_prepare_fused     A4   StixelsKernels.cu:236-296, 959-978: the records + the
+ *                                           object LUT (object_lut_body) in one launch
  *                       k_prior_tables      A9   StixelsKernels.cu:88-199 (DP-state independent)
  *   is_k_unary.hip      k_dp_unary          A7-A9 StixelsKernels.cu:477-839, PAIRWISE=false:
  *                                           independent (column, tile pair) work items, one lane

@@ -13,8 +13,10 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-CASES = [("is_k_unary_fast", "k_dp_unary_fastILb%dELi%dELb%dE" % (inv, nvr, pre), 2)
-         for inv in (0, 1) for nvr in (2, 4) for pre in (0, 1)] + \
+# k_dp_unary_fast<HAS_INVALID, NVR, WIN, LUTF, REPAIR>: a pattern names the first kernel it prefixes, WIN = 0 the
+# classic-tile launch, WIN = 1 the plain windowed one (emitted before its LUTF and REPAIR forms)
+CASES = [("is_k_unary_fast", "k_dp_unary_fastILb%dELi%dELb%dE" % (inv, nvr, win), 2)
+         for inv in (0, 1) for nvr in (2, 4) for win in (0, 1)] + \
         [("is_k_pairwise", "k_pw_phase1ILb0ELi2", 4), ("is_k_pairwise", "k_pw_phase1ILb0ELi0", 4),
          ("is_k_pairwise", "k_pw_phase1ILb1ELi2", 0), ("is_k_pairwise", "k_pw_phase1ILb1ELi0", 0)]
 

@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage (GPU box): ENVS="IS_LUT_CARRY=0 IS_LUT_CARRY=1" tools/ab_env.sh [bench args]: kernel times + images/s of the product
+# usage (GPU box): ENVS="IS_LUT_FUSED=0 IS_LUT_FUSED=1" tools/ab_env.sh [bench args]: kernel times + images/s of the product
 # library under each environment setting (the IS_* knobs are read when a context is created), same box, same run
 set -u
 export TMPDIR=/tmp
