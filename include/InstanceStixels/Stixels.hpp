@@ -134,6 +134,16 @@ public:
      * per-frame results.  Throws std::invalid_argument before any compute, when n_images exceeds the last call's
      * batch, or when an instance image is asked of a call that ran without instances. */
     std::vector<RenderResult> RenderBatch(int n_images, const RenderTargets& targets, void* stream = nullptr);
+    /* f6 (an addition): per frame 0 .. n_images-1 of the LAST Compute() or ComputeBatch(), the sparse joint
+     * histogram of its instance image (RenderTargets::instance, never rendered) and d_gt_instance [n][rows][cols]
+     * int32 Cityscapes instanceIds, as is_instance_overlap defines it: {pred, gt, count} ascending by (pred, gt),
+     * every table complete (a frame that overflows the initial capacity is repeated alone with a larger one, up to
+     * rows*cols).  One packed copy of the used records.  Throws std::invalid_argument before any compute under
+     * RenderBatch's rules, and when the last call ran without instances. */
+    std::vector<std::vector<is_overlap_record>> InstanceOverlapBatch(int n_images, const int32_t* d_gt_instance,
+                                                                     void* stream = nullptr);
+    /* Records per frame of InstanceOverlapBatch's first pass (default 4096; [1, IS_OVERLAP_MAX_CAPACITY]). */
+    void SetInstanceOverlapCapacity(int records);
     /* Introspection for tests / bench. */
     const StixelParameters& GetParameters() const { return m_params; }
     const std::vector<float>& GetObjectCostLUT() const { return m_obj_cost_lut; }
@@ -212,6 +222,15 @@ private:
     int32_t* d_section_instance = nullptr; /* [max_batch][realcols][max_sections] */
     char* d_render_results = nullptr;      /* [max_batch] double | [max_batch] int64 | [max_batch] int32 */
     char* h_render_results = nullptr;
+    /* InstanceOverlapBatch: [max_batch][capacity] records, then n_records | overflow per frame, the packed records
+     * (device and pinned host, allocated on first use, grown with the capacity) */
+    int m_overlap_capacity = 4096;
+    size_t m_overlap_cap_alloc = 0;
+    is_overlap_record* d_overlap_records = nullptr;
+    is_overlap_record* d_overlap_packed = nullptr;
+    int32_t* d_overlap_header = nullptr;   /* [max_batch] n_records | [max_batch] overflow */
+    int32_t* h_overlap_header = nullptr;
+    is_overlap_record* h_overlap_packed = nullptr;
     /* every device operation of the object runs on this stream (an ordinary stream: it still
      * synchronises with work the caller queued on the legacy NULL stream, like the reference's
      * default-stream code; on the NULL stream itself the auxiliary streams of the core never

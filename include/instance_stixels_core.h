@@ -355,6 +355,53 @@ int is_section_instance_labels(const is_instance_buffers* per_image, int n_image
  * the caller's instances above). */
 int is_render_sections(const is_render_args* args, void* stream);
 
+/* ---- f6: the instance image against ground-truth instanceIds, as a sparse joint histogram per frame ----------
+ * The reference scores instances with cityscapesscripts' evalInstanceLevelSemanticLabeling, which reads one mask
+ * per predicted instance (draw_instance_masks) and the *_gtFine_instanceIds.png files.  Every quantity of that
+ * evaluation (areas, intersections, void and group overlaps) is a sum over the joint histogram
+ *     H_f(p, g) = #{ pixels x : P_f(x) == p and G_f(x) == g },   over every pixel, p = 0 included,
+ * where P_f is the instance image that is_render_sections draws -- class*1000 + l, else 0, with the same geometry
+ * and clipping, built from the Sections and never read from a rendered image -- and G_f the caller's instanceIds.  The table of a
+ * frame holds the non-zero entries, ascending by pred then gt (both as signed int32), and sums to rows*cols. */
+typedef struct is_overlap_record {
+    int32_t pred;
+    int32_t gt;
+    int64_t count;
+} is_overlap_record;
+
+/* Largest capacity and frame (rows * cols) of is_instance_overlap. */
+#define IS_OVERLAP_MAX_CAPACITY (1 << 28)
+
+/* Zero-initialise before setting fields.  All device arrays are on the current device.
+ *   d_sections, d_section_instance, n_images, realcols, max_sections, rows, cols   as in is_render_args; the map
+ *                       may be NULL, then P_f is 0 everywhere; rows * cols <= IS_OVERLAP_MAX_CAPACITY
+ *   d_gt_instance       [n_images][rows][cols] int32 Cityscapes instanceIds (labelId*1000 + k, or a labelId);
+ *                       any value is accepted
+ *   capacity            records per frame, in [1, IS_OVERLAP_MAX_CAPACITY]; rows * cols always suffices
+ *   d_records           [n_images][capacity] records, 8-byte aligned: frame f's table in its first
+ *                       n_records[f] entries; the rest is left as it was
+ *   d_n_records         [n_images] int32
+ *   d_overflow          [n_images] int32: 1 where the frame has more than `capacity` distinct pairs; its
+ *                       n_records is then 0 and its records unspecified (never written outside its row) */
+typedef struct is_instance_overlap_args {
+    const is_section* d_sections;
+    const int32_t* d_section_instance;
+    int n_images, realcols, max_sections, rows, cols;
+    const int32_t* d_gt_instance;
+    int capacity;
+    is_overlap_record* d_records;
+    int32_t* d_n_records;
+    int32_t* d_overflow;
+} is_instance_overlap_args;
+
+/* The tables of n_images frames on `stream`, asynchronously (a temporary per-frame hash of 2 x capacity slots,
+ * rounded up to a power of two, from the stream-ordered allocator). */
+int is_instance_overlap(const is_instance_overlap_args* args, void* stream);
+/* The records of is_instance_overlap's output packed back to back in frame order, frame f's n_records[f] first
+ * entries of d_records [n_images][capacity] -> d_packed [sum of n_records].  On `stream`. */
+int is_pack_overlap_records(const is_overlap_record* d_records, const int32_t* d_n_records, int n_images,
+                            int capacity, is_overlap_record* d_packed, void* stream);
+
 /* Thin wrappers over the HIP runtime so that the plain-C++ host class needs no HIP headers
  * (the reference's callers are all .cu files; ours may be plain C++). */
 int is_device_malloc(void** ptr, size_t bytes);

@@ -31,9 +31,13 @@ EXPORTS = [
     "is_road_ctx_create", "is_road_ctx_destroy", "is_road_ctx_device", "is_road_ctx_binary",
     "is_road_vdisparity_batch", "is_road_hough_batch",
     "is_section_instance_labels", "is_render_sections",
+    "is_instance_overlap", "is_pack_overlap_records",
 ]
 RENDER_MAX_LABELS = 64    # IS_RENDER_MAX_LABELS
 RENDER_MAX_CLASSES = 256  # IS_RENDER_MAX_CLASSES
+OVERLAP_MAX_CAPACITY = 1 << 28  # IS_OVERLAP_MAX_CAPACITY
+# is_overlap_record: one entry of a frame's joint histogram of instance image and gt instanceIds
+OVERLAP_DTYPE = np.dtype([("pred", np.int32), ("gt", np.int32), ("count", np.int64)])
 
 
 class InstanceBuffers(ctypes.Structure):
@@ -50,6 +54,14 @@ class RenderArgs(ctypes.Structure):
                 ("d_label", vp), ("d_disparity", vp), ("d_instance", vp), ("d_gt_label", vp), ("n_labels", ci),
                 ("d_confusion", vp), ("d_gt_disparity", vp), ("d_disp_abs_sum", vp), ("d_disp_count", vp),
                 ("d_stixel_count", vp)]
+
+
+class InstanceOverlapArgs(ctypes.Structure):
+    """is_instance_overlap_args: zero-initialised by ctypes; device pointers as ints."""
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    _fields_ = [("d_sections", vp), ("d_section_instance", vp), ("n_images", ci), ("realcols", ci),
+                ("max_sections", ci), ("rows", ci), ("cols", ci), ("d_gt_instance", vp), ("capacity", ci),
+                ("d_records", vp), ("d_n_records", vp), ("d_overflow", vp)]
 
 
 class CoreError(RuntimeError):
@@ -102,6 +114,8 @@ def lib():
         L.is_cluster_instances.argtypes = [vp, ctypes.POINTER(InstanceBuffers), vp]
         L.is_section_instance_labels.argtypes = [ctypes.POINTER(InstanceBuffers), ci, ci, ci, vp, vp]
         L.is_render_sections.argtypes = [ctypes.POINTER(RenderArgs), vp]
+        L.is_instance_overlap.argtypes = [ctypes.POINTER(InstanceOverlapArgs), vp]
+        L.is_pack_overlap_records.argtypes = [vp, vp, ci, ci, vp, vp]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
         L.is_get_device.argtypes = [ctypes.POINTER(ci)]
@@ -374,6 +388,13 @@ def render_sections_ptr(stream=0, class_to_label=None, **fields):
         table = np.ascontiguousarray(class_to_label, np.uint8)
         a.h_class_to_label, a.n_classes = table.ctypes.data, table.size
     _check(lib().is_render_sections(ctypes.byref(a), ctypes.c_void_p(int(stream))), "is_render_sections")
+
+
+def instance_overlap_ptr(stream=0, **fields):
+    """is_instance_overlap on raw device pointers (ints): fields are those of InstanceOverlapArgs.  Asynchronous
+    on `stream`."""
+    a = InstanceOverlapArgs(**fields)
+    _check(lib().is_instance_overlap(ctypes.byref(a), ctypes.c_void_p(int(stream))), "is_instance_overlap")
 
 
 def flip_and_pad(cnn_out, rows_power2_segmentation, device=0):

@@ -61,6 +61,8 @@ hipError_t isk_launch_road_vdisparity(const float*, int*, uint8_t*, int*, int*, 
 int isk_render_scatter_images(void);
 hipError_t isk_launch_section_instance(const is_instance_buffers*, int, int, int, int, int32_t*, hipStream_t);
 hipError_t isk_launch_render(const is_render_args*, const uint8_t*, int, hipStream_t);
+hipError_t isk_launch_instance_overlap(const is_instance_overlap_args*, hipStream_t);
+hipError_t isk_launch_pack_overlap(const is_overlap_record*, const int32_t*, int, int, is_overlap_record*, hipStream_t);
 hipError_t isk_launch_road_hough(const int*, const int*, int*, const float*, int2*, float*, int*, int*, int*, int,
                                  int, int, int, int, int, int, int, float, float, hipStream_t);
 }
@@ -695,6 +697,37 @@ int is_render_sections(const is_render_args* a, void* stream) {
     const int n_classes = a->h_class_to_label ? a->n_classes : 19;
     memcpy(table, src, n_classes);
     HIP_TRY(isk_launch_render(a, table, n_classes, (hipStream_t)stream));
+    return IS_OK;
+}
+
+/* ---- f6: instance overlap tables (is_k_instance_eval.hip) ---- */
+int is_instance_overlap(const is_instance_overlap_args* a, void* stream) {
+    if (!a || !a->d_sections || !a->d_gt_instance) return fail_arg("null sections or gt");
+    if (!a->d_records || !a->d_n_records || !a->d_overflow) return fail_arg("null output");
+    if (a->n_images < 1 || a->realcols < 1 || a->rows < 1 || a->cols < a->realcols)
+        return fail_arg("bad shape (n_images >= 1, realcols >= 1, rows >= 1, cols >= realcols)");
+    if ((long long)a->rows * a->cols > IS_OVERLAP_MAX_CAPACITY) return fail_arg("frame larger than IS_OVERLAP_MAX_CAPACITY pixels");
+    if (a->max_sections < 1 || a->max_sections > 32767) return fail_arg("max_sections outside [1, 32767]");
+    if (a->capacity < 1 || a->capacity > IS_OVERLAP_MAX_CAPACITY) return fail_arg("capacity outside [1, IS_OVERLAP_MAX_CAPACITY]");
+    if (a->n_images > 65535 || (a->realcols + 64) / 64 > 65535 || (size_t)a->n_images * ((a->rows + 127) / 128) > 0x7fffffff)
+        return fail_arg("batch too large for one launch");
+    if ((uintptr_t)a->d_sections & 15) return fail_arg("d_sections must be 16-byte aligned");
+    if (((uintptr_t)a->d_gt_instance | (uintptr_t)a->d_section_instance | (uintptr_t)a->d_n_records |
+         (uintptr_t)a->d_overflow) & 3)
+        return fail_arg("d_gt_instance, d_section_instance, d_n_records and d_overflow must be 4-byte aligned");
+    if ((uintptr_t)a->d_records & 7) return fail_arg("d_records must be 8-byte aligned");
+    HIP_TRY(isk_launch_instance_overlap(a, (hipStream_t)stream));
+    return IS_OK;
+}
+
+int is_pack_overlap_records(const is_overlap_record* d_records, const int32_t* d_n_records, int n_images,
+                            int capacity, is_overlap_record* d_packed, void* stream) {
+    if (!d_records || !d_n_records || !d_packed) return fail_arg("null pointer");
+    if (n_images < 1 || n_images > 65535 || capacity < 1 || capacity > IS_OVERLAP_MAX_CAPACITY)
+        return fail_arg("n_images outside [1, 65535] or capacity outside [1, IS_OVERLAP_MAX_CAPACITY]");
+    if (((uintptr_t)d_records | (uintptr_t)d_packed) & 7) return fail_arg("records must be 8-byte aligned");
+    if ((uintptr_t)d_n_records & 3) return fail_arg("d_n_records must be 4-byte aligned");
+    HIP_TRY(isk_launch_pack_overlap(d_records, d_n_records, n_images, capacity, d_packed, (hipStream_t)stream));
     return IS_OK;
 }
 

@@ -30,6 +30,7 @@ EXPORTS = [
     "ire_hough_lines", "ire_set_device", "ire_active_device", "ire_compute_device",
     "ish_get_input_disparity_on_device", "ire_compute_batch", "ire_set_batch_limits", "ire_batch_fallbacks",
     "ish_render_batch",
+    "ish_instance_overlap_batch", "ish_instance_overlap_records", "ish_set_instance_overlap_capacity",
 ]
 
 # Stixels::RoadParameters, what RoadEstimation::ComputeBatch writes per frame
@@ -105,6 +106,9 @@ def lib():
         L.ire_set_batch_limits.argtypes = [vp, ci, ci]
         L.ire_batch_fallbacks.argtypes = [vp]
         L.ish_render_batch.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp]
+        L.ish_instance_overlap_batch.argtypes = [vp, ci, vp, vp, vp]
+        L.ish_instance_overlap_records.argtypes = [vp, vp, ctypes.c_int64]
+        L.ish_set_instance_overlap_capacity.argtypes = [vp, ci]
         L.ish_get_input_disparity_on_device.restype = vp
         _LIB = L
     return _LIB
@@ -296,6 +300,25 @@ class Stixels:
             sums.ctypes.data, counts.ctypes.data, stixels.ctypes.data, ctypes.c_void_p(int(stream))),
             "RenderBatch")
         return sums, counts, stixels
+
+    def InstanceOverlapBatch(self, n, d_gt, stream=0):
+        """Stixels::InstanceOverlapBatch: per frame 0 .. n-1 of the last Compute() / ComputeBatch(), the sparse joint
+        histogram of its instance image and the ground-truth instanceIds d_gt (device int32 [n][rows][cols], an
+        int pointer): a numpy array of core.OVERLAP_DTYPE (pred, gt, count), ascending by (pred, gt), summing to
+        rows*cols.  Returns a list of n such arrays."""
+        n = int(n)
+        counts = np.zeros(max(n, 0), np.int64)
+        self._check(lib().ish_instance_overlap_batch(self._h, n, ctypes.c_void_p(int(d_gt)) if d_gt else None,
+                                                     counts.ctypes.data, ctypes.c_void_p(int(stream))),
+                    "InstanceOverlapBatch")
+        flat = np.zeros(int(counts.sum()), _core.OVERLAP_DTYPE)
+        self._check(lib().ish_instance_overlap_records(self._h, flat.ctypes.data if flat.size else None,
+                                                       flat.size), "InstanceOverlapBatch")
+        return np.split(flat, np.cumsum(counts)[:-1]) if n > 0 else []
+
+    def SetInstanceOverlapCapacity(self, records):
+        """Records per frame of InstanceOverlapBatch's first pass (frames beyond it are repeated with more)."""
+        self._check(lib().ish_set_instance_overlap_capacity(self._h, int(records)), "SetInstanceOverlapCapacity")
 
     def GetInstanceStixels(self):
         cap = self.GetRealCols() * self.GetMaxSections()

@@ -380,6 +380,14 @@ void Stixels::Finish() { /* Stixels.cu:250-283 */
     IS_CHECK_RETURN(is_device_free(d_render_results));
     if (h_render_results) IS_CHECK_RETURN(is_host_free(h_render_results));
     d_section_instance = nullptr; d_render_results = nullptr; h_render_results = nullptr;
+    IS_CHECK_RETURN(is_device_free(d_overlap_records));
+    IS_CHECK_RETURN(is_device_free(d_overlap_packed));
+    IS_CHECK_RETURN(is_device_free(d_overlap_header));
+    if (h_overlap_header) IS_CHECK_RETURN(is_host_free(h_overlap_header));
+    if (h_overlap_packed) IS_CHECK_RETURN(is_host_free(h_overlap_packed));
+    d_overlap_records = d_overlap_packed = nullptr; d_overlap_header = nullptr;
+    h_overlap_header = nullptr; h_overlap_packed = nullptr;
+    m_overlap_cap_alloc = 0;
     m_render_images = 0;
     m_render_instances = false;
     d_pack_counts = d_pack_offsets = d_all_counts = nullptr;
@@ -683,6 +691,118 @@ std::vector<Stixels::RenderResult> Stixels::RenderBatch(int n_images, const Rend
     const int32_t* h_nst = (const int32_t*)(h_render_results + B * (sizeof(double) + sizeof(int64_t)));
     std::vector<RenderResult> out(n_images);
     for (int i = 0; i < n_images; i++) out[i] = RenderResult{h_sum[i], h_cnt[i], h_nst[i]};
+    return out;
+}
+
+void Stixels::SetInstanceOverlapCapacity(int records) {
+    if (records < 1 || records > IS_OVERLAP_MAX_CAPACITY)
+        throw std::invalid_argument("SetInstanceOverlapCapacity: records outside [1, IS_OVERLAP_MAX_CAPACITY].");
+    m_overlap_capacity = records;
+}
+
+std::vector<std::vector<is_overlap_record>> Stixels::InstanceOverlapBatch(int n_images, const int32_t* d_gt,
+                                                                          void* stream) {
+    if (m_render_images == 0)
+        throw std::invalid_argument("InstanceOverlapBatch scores the Sections of the last Compute() or ComputeBatch(): "
+                                    "there are none.");
+    if (n_images < 1 || n_images > m_render_images)
+        throw std::invalid_argument("InstanceOverlapBatch: n_images outside [1, frames of the last compute call].");
+    if (!m_render_instances)
+        throw std::invalid_argument("InstanceOverlapBatch: needs a compute call with instances.");
+    if (d_gt == nullptr) throw std::invalid_argument("InstanceOverlapBatch: null d_gt_instance.");
+    const DeviceGuard guard(m_ctx_device);
+    if (stream == nullptr) stream = m_stream;
+    const size_t B = (size_t)m_max_batch;
+    const size_t cs = (size_t)m_realcols * m_max_sections;
+    const size_t cap = (size_t)m_overlap_capacity;
+    if (d_section_instance == nullptr)
+        IS_CHECK_RETURN(is_device_malloc((void**)&d_section_instance, B * cs * sizeof(int32_t)));
+    if (d_overlap_header == nullptr) {
+        IS_CHECK_RETURN(is_device_malloc((void**)&d_overlap_header, 2 * B * sizeof(int32_t)));
+        IS_CHECK_RETURN(is_host_malloc((void**)&h_overlap_header, 2 * B * sizeof(int32_t)));
+    }
+    if (m_overlap_cap_alloc < cap) {
+        IS_CHECK_RETURN(is_device_free(d_overlap_records));
+        IS_CHECK_RETURN(is_device_free(d_overlap_packed));
+        if (h_overlap_packed) IS_CHECK_RETURN(is_host_free(h_overlap_packed));
+        d_overlap_records = d_overlap_packed = h_overlap_packed = nullptr;
+        m_overlap_cap_alloc = 0;
+        IS_CHECK_RETURN(is_device_malloc((void**)&d_overlap_records, B * cap * sizeof(is_overlap_record)));
+        IS_CHECK_RETURN(is_device_malloc((void**)&d_overlap_packed, B * cap * sizeof(is_overlap_record)));
+        IS_CHECK_RETURN(is_host_malloc((void**)&h_overlap_packed, B * cap * sizeof(is_overlap_record)));
+        m_overlap_cap_alloc = cap;
+    }
+    std::vector<is_instance_buffers> ibs;
+    for (int i = 0; i < n_images; i++) ibs.push_back(InstanceBuffers(i));
+    IS_CHECK_RETURN(is_section_instance_labels(ibs.data(), n_images, m_realcols, m_max_sections, d_section_instance,
+                                               stream));
+    const size_t frame_px = (size_t)m_rows * m_cols;
+    auto args = [&](int first, int n, int capacity, is_overlap_record* rec, int32_t* hdr) {
+        is_instance_overlap_args a = {};
+        a.d_sections = d_stixels + first * cs;
+        a.d_section_instance = d_section_instance + first * cs;
+        a.n_images = n;
+        a.realcols = m_realcols;
+        a.max_sections = m_max_sections;
+        a.rows = m_rows;
+        a.cols = m_cols;
+        a.d_gt_instance = d_gt + first * frame_px;
+        a.capacity = capacity;
+        a.d_records = rec;
+        a.d_n_records = hdr;
+        a.d_overflow = hdr + n;
+        return a;
+    };
+    /* the batch: tables, packed on the device; the per-frame counts first, then the used records */
+    const is_instance_overlap_args a = args(0, n_images, (int)cap, d_overlap_records, d_overlap_header);
+    const int rc = is_instance_overlap(&a, stream);
+    if (rc == IS_EINVAL) throw std::invalid_argument(std::string("InstanceOverlapBatch: ") + is_last_error());
+    IS_CHECK_RETURN(rc);
+    IS_CHECK_RETURN(is_pack_overlap_records(d_overlap_records, d_overlap_header, n_images, (int)cap,
+                                            d_overlap_packed, stream));
+    IS_CHECK_RETURN(is_memcpy_d2h(h_overlap_header, d_overlap_header, 2 * n_images * sizeof(int32_t), stream));
+    IS_CHECK_RETURN(is_stream_synchronize(stream));
+    size_t total = 0;
+    for (int i = 0; i < n_images; i++) total += (size_t)h_overlap_header[i];
+    if (total)
+        IS_CHECK_RETURN(is_memcpy_d2h(h_overlap_packed, d_overlap_packed, total * sizeof(is_overlap_record), stream));
+    IS_CHECK_RETURN(is_stream_synchronize(stream));
+    std::vector<std::vector<is_overlap_record>> out(n_images);
+    std::vector<int> retry;
+    size_t off = 0;
+    for (int i = 0; i < n_images; i++) {
+        const int m = h_overlap_header[i];
+        if (h_overlap_header[n_images + i]) retry.push_back(i);
+        out[i].assign(h_overlap_packed + off, h_overlap_packed + off + m);
+        off += (size_t)m;
+    }
+    /* frames with more distinct pairs than the capacity: alone, with 8x the table until it fits (rows*cols always
+     * does: a frame has no more pairs than pixels) */
+    for (const int f : retry) {
+        size_t c = cap;
+        for (;;) {
+            c = std::min(c * 8, frame_px);
+            is_overlap_record* d_rec = nullptr;
+            int32_t* d_hdr = nullptr;
+            IS_CHECK_RETURN(is_device_malloc((void**)&d_rec, c * sizeof(is_overlap_record)));
+            IS_CHECK_RETURN(is_device_malloc((void**)&d_hdr, 2 * sizeof(int32_t)));
+            const is_instance_overlap_args r = args(f, 1, (int)c, d_rec, d_hdr);
+            int32_t hdr[2] = {0, 0};
+            int err = is_instance_overlap(&r, stream);
+            if (err == IS_OK) err = is_memcpy_d2h(hdr, d_hdr, sizeof(hdr), stream);
+            if (err == IS_OK) err = is_stream_synchronize(stream);
+            if (err == IS_OK && !hdr[1]) {
+                out[f].resize((size_t)hdr[0]);
+                if (hdr[0]) err = is_memcpy_d2h(out[f].data(), d_rec, (size_t)hdr[0] * sizeof(is_overlap_record), stream);
+                if (err == IS_OK) err = is_stream_synchronize(stream);
+            }
+            IS_CHECK_RETURN(is_device_free(d_rec));
+            IS_CHECK_RETURN(is_device_free(d_hdr));
+            IS_CHECK_RETURN(err);
+            if (!hdr[1]) break;
+            if (c >= frame_px) throw std::runtime_error("InstanceOverlapBatch: a table of rows*cols records overflowed.");
+        }
+    }
     return out;
 }
 

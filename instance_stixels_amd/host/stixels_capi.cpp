@@ -285,6 +285,39 @@ int ish_render_batch(void* h, int n, uint8_t* label, float* disparity, int32_t* 
     });
 }
 
+/* InstanceOverlapBatch(): the tables of frames 0 .. n-1 of the last Compute() / ComputeBatch() against
+ * d_gt_instance.  n_records: host [n].  The records stay with the calling thread until ish_instance_overlap_records
+ * copies them out (all frames back to back, in frame order) -- the caller sizes that buffer from n_records. */
+namespace {
+thread_local std::vector<is_overlap_record> g_overlap;
+thread_local void* g_overlap_owner = nullptr;
+}
+int ish_instance_overlap_batch(void* h, int n, const int32_t* d_gt_instance, int64_t* n_records, void* stream) {
+    return guard([&] {
+        g_overlap.clear();
+        g_overlap_owner = nullptr;
+        const std::vector<std::vector<is_overlap_record>> t = ((Stixels*)h)->InstanceOverlapBatch(n, d_gt_instance,
+                                                                                                  stream);
+        for (int i = 0; i < n; i++) {
+            n_records[i] = (int64_t)t[i].size();
+            g_overlap.insert(g_overlap.end(), t[i].begin(), t[i].end());
+        }
+        g_overlap_owner = h;
+    });
+}
+int ish_instance_overlap_records(void* h, is_overlap_record* out, int64_t cap) {
+    return guard([&] {
+        if (h != g_overlap_owner || (int64_t)g_overlap.size() > cap)
+            throw std::invalid_argument("ish_instance_overlap_records: no tables of this object, or cap too small.");
+        std::memcpy(out, g_overlap.data(), g_overlap.size() * sizeof(is_overlap_record));
+        g_overlap.clear();
+        g_overlap_owner = nullptr;
+    });
+}
+int ish_set_instance_overlap_capacity(void* h, int records) {
+    return guard([&] { ((Stixels*)h)->SetInstanceOverlapCapacity(records); });
+}
+
 int ish_set_device(void* h, int device) {
     return guard([&] { ((Stixels*)h)->SetDevice(device); });
 }
