@@ -21,15 +21,6 @@
 #ifndef IS_UNARY_OCC
 #define IS_UNARY_OCC IS_UNARY_WAVES /* waves per SIMD the unary DP is compiled for (VGPR budget 512/OCC) */
 #endif
-#ifndef IS_CMPX_UPDATE
-#define IS_CMPX_UPDATE 1 /* running minima of the unary DP through v_cmpx + moves (take_if_less) */
-#endif
-#ifndef IS_PRUNE
-#define IS_PRUNE 1 /* exact branch-and-bound on vB in FAST columns (descending vB, early exit) */
-#endif
-#ifndef IS_SKIP_GROUND_ABOVE_HORIZON
-#define IS_SKIP_GROUND_ABOVE_HORIZON 1 /* tiles above the horizon: ground candidates cost +inf, skip them */
-#endif
 #define IS_TILE 64
 /* Rows per BOUND BLOCK of the pairwise branch-and-bound (lemmas L6 / L7): the running
  * minima q of the StepRecs restart, the pre-pass of phase 1 evaluates a block top, and phase 2 leaves
@@ -222,9 +213,6 @@ struct DevParams {
  * contiguous window of round 4 --, a tile above the horizon that holds sky (d ~ 0) AND an object one half per
  * cluster (k_prepare picks whichever of the three forms holds most of the tile's rows).  Staged column c (0 ..
  * IS_P1_WIN - 1) is lutT column IS_WIN_COL(w, c); IS_WIN_FIND(w, fn) is the staged column of fn, or negative. */
-#ifndef IS_WIN_SPLIT
-#define IS_WIN_SPLIT 1 /* 0: contiguous fn windows only (round 4) */
-#endif
 #define IS_WIN_HALF (IS_P1_WIN / 2)
 #define IS_WIN_A(w) ((int)((unsigned)(w) & 0xFFFFu))
 #define IS_WIN_B(w) ((int)((unsigned)(w) >> 16))

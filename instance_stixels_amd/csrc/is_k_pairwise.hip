@@ -372,16 +372,13 @@ __device__ __forceinline__ void l8_group_min_store(const DevParams& P, float T8,
         if ((lane & ((1 << (LOG - 3)) - 1)) == 0) dst[bq * 8 + base] = v[0];
     }
 }
-/* ---- the same minima on the DPP / permlane path (IS_L78_DPP, groups of 32 lanes) --------------------
+/* ---- the same minima on the DPP / permlane path (groups of 32 lanes) ------------------------------
  * __shfl_xor is a ds_bpermute (LDS crossbar, an address VGPR, an lgkmcnt wait) and __builtin_fminf
  * re-quiets a value that went through a bitcast (v_max x, x): 3 instructions and a round trip per
  * exchange.  Here an exchange is v_permlane16_swap (distance 16: the rows of TWO values swapped by one
  * instruction, so that one minimum reduces both -- each lands in its own row parity) or a v_mov_b32_dpp
  * (row_ror / quad_perm, bank-masked where the two halves of a pair go different ways) + a bare v_min_f32.
  * The results are the minima of the same numbers: bit-identical to the shuffle version. */
-#ifndef IS_L78_DPP
-#define IS_L78_DPP 1
-#endif
 template <int CTRL, int BANK = 0xf>
 __device__ __forceinline__ float dpp_mov(float old, float src) {
     return __uint_as_float(__builtin_amdgcn_update_dpp(__float_as_uint(old), __float_as_uint(src), CTRL, 0xf, BANK, false));
@@ -473,7 +470,7 @@ __device__ __forceinline__ void l78_block_summaries(const DevParams& P, const Ro
     const float T8 = t8col[vBc];
     const RowRec* rec = rcol + vBc;
     float* const slot = bsum_col + (size_t)(((tile_lo >> 6) * IS_QPT) + (row >> IS_QB_LOG) + 1) * IS_L7_F;
-    if (IS_L78_DPP && LOG == 5) {
+    if (LOG == 5) {
         l78_store32(P, T, T8, rec, vB - 1 < vhor, ok, slot, (int)(threadIdx.x & 63));
         return;
     }
@@ -504,9 +501,6 @@ __device__ __forceinline__ void l8_store_never(float* dst, bool writer) {
  * its 64 rows are never visited.  In a homogeneous road or sky stretch -- where the sticky bounds
  * never close, every split being a near-optimal candidate -- exactly the block with the stretch's
  * first row survives (tools/l7_study.py). */
-#ifndef IS_P1_L7
-#define IS_P1_L7 1
-#endif
 #define IS_P1_L7_WORDS 136 /* LDS words of the exchange: [2][64] threshold keys + 2 x 64-bit masks, padded */
 /* LDS words per bound block of a phase-1 launch: 64 object bounds (one per lane) + its 24-float summary + the
  * 8 instance-prefix dwords of the record at its top row */
@@ -572,7 +566,7 @@ template <bool SKY, bool ALL_LANES = false, bool NOGROUND = false, bool DESC = f
 __device__ __forceinline__ void pairwise_step(const DevParams& P, const StepVals st, int vB,
                                               bool live, float od, const SegTerms& t, PairBest& b) {
     /* ALL_LANES (phase 1): every lane with vT < H is live and rows vT >= H are never stored */
-    constexpr bool CMPX = IS_CMPX_UPDATE && ALL_LANES;
+    constexpr bool CMPX = ALL_LANES;
     static_assert(!DESC || CMPX, "descending walks are whole-wave steps");
     if (SKY) { /* :729-775 */
         const float cost = P.dw * t.sd + st.pwmp + P.sw * t.seg_s;
@@ -638,9 +632,6 @@ __device__ __forceinline__ void pairwise_step(const DevParams& P, const StepVals
 #ifndef IS_P1_WIN_WAVES
 #define IS_P1_WIN_WAVES 4
 #endif
-#ifndef IS_P2_GATHER_MASKED
-#define IS_P2_GATHER_MASKED 1
-#endif
 #ifndef IS_P1_TOUCH_AHEAD
 #define IS_P1_TOUCH_AHEAD 2
 #endif
@@ -684,42 +675,8 @@ __device__ __forceinline__ void touch_round(const RowRec* rcol, const StepRec* s
  * per step, and frees 32 SGPRs (the kernel had 72 SGPR spills).  The StepRec stays in SGPRs and is
  * double buffered (16 + 16), loaded one step ahead.  `asm volatile`: a DPP read of a lane that
  * EXEC has switched off returns 0, so these instructions must never sink into divergent code. */
-#ifndef IS_P1_DPP
-#define IS_P1_DPP 1
-#endif
-#ifndef IS_P1_DPP_INV
-#define IS_P1_DPP_INV 1 /* the DPP / scalar-operand step also with an invalid-disparity value (mean_valid_fast) */
-#endif
-#ifndef IS_P1_TILE0_DIRECT
-#define IS_P1_TILE0_DIRECT 1
-#endif
-#ifndef IS_P1_SREC_LATE
-#define IS_P1_SREC_LATE 1 /* StepRec of the next step: loaded at the end of the step, pinned (= waited for) at its use */
-#endif
 #ifndef IS_P1_SREC
 #define IS_P1_SREC 1 /* class-prefix half of the vB record as scalar operands (see eval_segment_mix) */
-#endif
-#ifdef IS_ABL_P1PHASES
-/* debug build only: s_memtime cycles of wave 0 of every phase-1 workgroup in prologue / walk /
- * waiting for the other waves / merge, plus the number of full and ground-sky rounds of wave 0 */
-__device__ unsigned long long g_p1phase[16 * 8]; /* [min(tile, 15)][counter] */
-#define ISP1_MARK(k)                                                              \
-    do {                                                                          \
-        const unsigned long long now__ = __builtin_readcyclecounter();            \
-        if (threadIdx.x == 0) atomicAdd(&g_p1phase[min(tile, 15) * 8 + (k)], now__ - t_p1); \
-        t_p1 = now__;                                                             \
-    } while (0)
-#define ISP1_COUNT(k) do { if (threadIdx.x == 0) atomicAdd(&g_p1phase[min(tile, 15) * 8 + (k)], 1ull); } while (0)
-extern "C" void isk_debug_p1phases(unsigned long long* out, int reset) {
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_p1phase), sizeof(g_p1phase));
-    if (reset) {
-        unsigned long long z[16 * 8] = {0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_p1phase), z, sizeof(z));
-    }
-}
-#else
-#define ISP1_MARK(k)
-#define ISP1_COUNT(k)
 #endif
 
 template <bool FAST, bool HAS_INVALID, int NR, bool WIN>
@@ -754,18 +711,11 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
     const int nw = nwl * nsplit;
     const int w = split * nwl + wl;
     const int tile_lo = tile * IS_TILE;
-#ifdef IS_ABL_P1HOT /* timing-only ablation for batches whose columns are all EQUAL (tools/p1_hot_probe.py): phase 1 reads the
-                     * tables of column (colg mod 8) -- the same values, from lines that stay in the XCD's L2 -- so that the
-                     * difference to the product build is what phase 1 pays for memory latency and bandwidth */
-    const int colr = colg & 7;
-#else
     const int colr = colg;
-#endif
     const RowRec* rcol = recs + (size_t)colr * (H + 1);
     const float* lcol = lutT + (size_t)colr * (H + 1) * D;
     const StepRec* scol = steps + (size_t)colr * H;
 
-#if IS_P1_TILE0_DIRECT
     /* Tile 0 has ONE candidate per row, the first segment (vB = 0, :481-594), and it belongs to wave 0
      * of split 0: that wave computes it with its operands straight from global memory (1/h, the two
      * lutT values of the lane) and writes the partial minima in the form the merge below would; no
@@ -800,11 +750,7 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
         if (counters != nullptr && lane == 0 && split == 0) atomicAdd(counters + IS_CNT_P1_FULL, 1ull);
         return;
     }
-#endif
 
-#ifdef IS_ABL_P1PHASES
-    unsigned long long t_p1 = __builtin_readcyclecounter();
-#endif
     const int vB_last = min(tile_lo, H - 1);
     const int vT = tile_lo + lane;
     const int vTc = min(vT, H - 1);
@@ -821,7 +767,7 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
     constexpr int PRE_N = 2; /* floats per thread: NLB * 32 <= PRE_N * nthreads at 1024 rows */
     float pre_v[PRE_N];
     const int nthr = (int)blockDim.x;
-    const bool pre_regs = FAST && IS_PRUNE && NLB * IS_P1_SUM_F <= PRE_N * nthr;
+    const bool pre_regs = FAST && NLB * IS_P1_SUM_F <= PRE_N * nthr;
     auto pre_load = [&](int i) -> float { /* entry i of s_sum */
         const int k = i / IS_P1_SUM_F, j = i - k * IS_P1_SUM_F;
         if (j >= IS_L7_F) return ((const float*)(rcol + (size_t)k * IS_QB))[24 + (j - IS_L7_F)];
@@ -844,7 +790,7 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
             const int i = tid + j * nthr;
             if (i < NLB * IS_P1_SUM_F) s_sum[i] = pre_v[j];
         }
-    } else if (FAST && IS_PRUNE) { /* tall frames: a plain loop */
+    } else if (FAST) { /* tall frames: a plain loop */
         for (int i = tid; i < NLB * IS_P1_SUM_F; i += nthr) s_sum[i] = pre_load(i);
     }
     const float* my_tile = s_tile + lane * DP;
@@ -856,7 +802,6 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
     if (tid < 2 * 64) s_thr[tid] = 0xFF800000u;
     if (tid < 4) s_thr[2 * 64 + tid] = 0u;
     __syncthreads();
-    ISP1_MARK(0);
 
     PairBest b;
     b.g = b.o = b.s = IS_INF;
@@ -898,7 +843,7 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
         }
         return vt - vb;
     };
-    if (FAST && IS_PRUNE) {
+    if (FAST) {
         /* FAST columns: vB downwards with the exact branch-and-bound of DESIGN.md "Pruning".  The
          * candidates of a tile fall into BLOCKS: block k >= 1 = the vB values 64 (k-1) + 1 .. 64 k
          * whose StepRecs phase 2 of tile k - 1 built, block 0 = the first segment vB = 0.  A
@@ -935,8 +880,8 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
             cprune_t pq0 = (cprune_t)prec;
             const float pE1o = pq0->E1o;
             const float pE1gs = __builtin_fmaxf(pq0->E1g, pq0->E1s);
-            const bool pnog = IS_SKIP_GROUND_ABOVE_HORIZON && tile_lo >= vhor;
-            l7 = IS_P1_L7 && (pE1gs < IS_INF) && NLB <= 63;
+            const bool pnog = tile_lo >= vhor;
+            l7 = (pE1gs < IS_INF) && NLB <= 63;
             if (l7) {
                 bl7 = l7_lane_bounds(P, my);
                 float thr_g = IS_INF, thr_s = IS_INF;
@@ -1046,13 +991,12 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
                 mask_s = (unsigned long long)__builtin_amdgcn_readfirstlane(s_thr[2 * 64 + 2]) |
                          ((unsigned long long)__builtin_amdgcn_readfirstlane(s_thr[2 * 64 + 3]) << 32);
             }
-            ISP1_MARK(6); /* (debug build: the pre-pass) */
         }
         if (w <= vB_last) {
             cprune_t pq = (cprune_t)prec;
             const float E1o = pq->E1o, E2 = 3.0f * pq->E2; /* see seg_o_lower_bound */
             const float E1gs = __builtin_fmaxf(pq->E1g, pq->E1s);
-            const bool nog = IS_SKIP_GROUND_ABOVE_HORIZON && tile_lo >= vhor;
+            const bool nog = tile_lo >= vhor;
             int vB = vB_last - (vB_last - w) % nw; /* the wave's largest vB */
             LutRow<NRW> next_row;
             load_lut_row<NRW>(next_row, lrsrc, lcol, vB, D, lane4r);
@@ -1072,17 +1016,16 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
              * ic >= -E2 and f_oi >= 0 (`E2` here is 3 E2 of PruneRec: -2 * that = -6 E2) */
             float lbseg = -2.0f * E2;
 #define IS_P1_NEXT_ROW() load_lut_row<NRW>(next_row, lrsrc, lcol, max(vB - nw, 0), D, lane4r)
-            /* (with an invalid-disparity value the step used to keep the scalar-load form: valid-count operands and
-             * an IEEE division per step took the DPP form to 90+ VGPRs.  Round 5: the mean of a FAST column through
-             * mean_valid_fast -- a table read and the exact-division shortcut -- so both run the same step) */
-            constexpr bool USE_DPP = IS_P1_DPP && (!HAS_INVALID || IS_P1_DPP_INV);
+            /* (an invalid-disparity value takes the same step: valid-count operands and an IEEE division per step
+             * took it to 90+ VGPRs; the mean of a FAST column goes through mean_valid_fast -- a table read and the
+             * exact-division shortcut -- since round 5) */
             /* record of vB (c_*), of vB - nw (n_*): vector loads, two steps ahead; StepRec one step
              * ahead in a second set of SGPRs */
             const int l15 = lane & 15;
             float c_r0 = 0.0f, c_r1 = 0.0f, n_r0 = 0.0f, n_r1 = 0.0f;
             StepVals st_next;
             isk_f16v S; /* IS_P1_SREC: the class-prefix half of the record of vB as scalars (eval_segment_mix) */
-            if (USE_DPP) { /* (requesting these before the tile staging of the prologue measured 2.5 % slower) */
+            { /* (requesting these before the tile staging of the prologue measured 2.5 % slower) */
                 const float* q0 = (const float*)(rcol + vB);
                 const float* q1 = (const float*)(rcol + max(vB - nw, 0));
                 if (!IS_P1_SREC) { c_r0 = q0[l15]; n_r0 = q1[l15]; }
@@ -1091,20 +1034,19 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
                 st_next = sload_step(scol + vB);
                 if (IS_P1_SREC) srec_request(S, rcol + vB);
             }
-#define IS_P1_DRAIN() if (USE_DPP && IS_P1_SREC) srec_arrived(S) /* a request is in flight after every step */
+#define IS_P1_DRAIN() if (IS_P1_SREC) srec_arrived(S) /* a request is in flight after every step */
             /* IS_P1_SREC: the StepRec and the scalar half of the record of the next step are requested
              * when the step has read its own for the last time (the bounds): one set of registers
              * each instead of two, and the loads have the first half of the next step to arrive */
 #define IS_P1_REQUEST_NEXT(last_use)                                                               \
-            if (USE_DPP && IS_P1_SREC) {                                                           \
+            if (IS_P1_SREC) {                                                                      \
                 const int vn = max(vB - nw, 0);                                                    \
                 const StepRec* sn = scol + vn;                                                     \
                 asm volatile("" : "+s"(sn) : "s"(__builtin_amdgcn_readfirstlane((int)(last_use))));    \
-                st_next = IS_P1_SREC_LATE ? sload_step_raw(sn) : sload_step(sn);                   \
+                st_next = sload_step_raw(sn); /* pinned (= waited for) at its use */               \
                 srec_request_next(S, rcol + vn);                                                   \
             }
 #define IS_P1_STEP(SKY, NOG)                                                                       \
-            ISP1_COUNT(4);                                                                         \
             const LutRow<NRW> row = next_row;                                                       \
             if (IS_P1_TOUCH_AHEAD > 0)                                                             \
                 touch_step(rcol, scol, max(vB - IS_P1_TOUCH_AHEAD * nw, 0), lane, scr);            \
@@ -1115,39 +1057,30 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
             bool ok_o = false, ok_x = (NOG);                                                       \
             {                                                                                      \
                 n_full++;                                                                          \
+                const float r0 = c_r0, r1 = c_r1;                                                  \
+                StepVals st = st_next;                                                             \
+                c_r0 = n_r0; c_r1 = n_r1;                                                          \
+                {                                                                                  \
+                    const float* q2 = (const float*)(rcol + max(vB - 2 * nw, 0));                  \
+                    if (!IS_P1_SREC) n_r0 = q2[l15];                                               \
+                    n_r1 = q2[16 + l15];                                                           \
+                }                                                                                  \
+                constexpr int WANT = (SKY) ? IS_WANT_SKY : ((NOG) ? 0 : IS_WANT_GROUND);           \
                 SegTerms t;                                                                        \
-                StepVals st;                                                                       \
-                float od;                                                                          \
-                if (USE_DPP) {                                                                     \
-                    const float r0 = c_r0, r1 = c_r1;                                              \
-                    st = st_next;                                                                  \
-                    c_r0 = n_r0; c_r1 = n_r1;                                                      \
-                    {                                                                              \
-                        const float* q2 = (const float*)(rcol + max(vB - 2 * nw, 0));              \
-                        if (!IS_P1_SREC) n_r0 = q2[l15];                                           \
-                        n_r1 = q2[16 + l15];                                                       \
-                    }                                                                              \
-                    constexpr int WANT = (SKY) ? IS_WANT_SKY : ((NOG) ? 0 : IS_WANT_GROUND);       \
-                    if (IS_P1_SREC) {                                                              \
-                        if (IS_P1_SREC_LATE) pin_step(st);                                         \
-                        srec_arrived(S);                                                           \
-                        t = eval_segment_mix<HAS_INVALID, WANT>(my, S, r1, (float)h, s_rcp[h], D, P.iw, s_rcp); \
-                    } else {                                                                       \
-                        t = eval_segment_dpp<HAS_INVALID, WANT>(my, r0, r1, (float)h, s_rcp[h], D, P.iw, s_rcp); \
-                    }                                                                              \
-                    od = od_value(row, t.fni, vB);                                \
-                    if (!IS_P1_SREC) {                                                             \
-                        /* the next StepRec: requested only now -- every LDS wait is an lgkmcnt(0) \
-                         * wait and would wait for this scalar load too (SMEM returns out of order) */ \
-                        const StepRec* sn = scol + max(vB - nw, 0);                                \
-                        asm volatile("" : "+s"(sn) : "v"(od));                                     \
-                        st_next = sload_step(sn);                                                  \
-                    }                                                                              \
+                if (IS_P1_SREC) {                                                                  \
+                    pin_step(st);                                                                  \
+                    srec_arrived(S);                                                               \
+                    t = eval_segment_mix<HAS_INVALID, WANT>(my, S, r1, (float)h, s_rcp[h], D, P.iw, s_rcp); \
                 } else {                                                                           \
-                    const RowRec rb = sload_rec(rcol + vB);                                        \
-                    st = sload_step(scol + vB);                                                    \
-                    t = eval_segment<true, HAS_INVALID>(my, rb, (float)h, s_rcp[h], D, P.iw, s_rcp);      \
-                    od = od_value(row, t.fni, vB);                                \
+                    t = eval_segment_dpp<HAS_INVALID, WANT>(my, r0, r1, (float)h, s_rcp[h], D, P.iw, s_rcp); \
+                }                                                                                  \
+                const float od = od_value(row, t.fni, vB);                                         \
+                if (!IS_P1_SREC) {                                                                 \
+                    /* the next StepRec: requested only now -- every LDS wait is an lgkmcnt(0)     \
+                     * wait and would wait for this scalar load too (SMEM returns out of order) */ \
+                    const StepRec* sn = scol + max(vB - nw, 0);                                    \
+                    asm volatile("" : "+s"(sn) : "v"(od));                                         \
+                    st_next = sload_step(sn);                                                      \
                 }                                                                                  \
                 pairwise_step<SKY, true, NOG, true>(P, st, vB, live, od, t, b);                    \
                 const float lb_o = min_raw((st.q_o - E1o) + P.sw * seg_o_lower_bound(t, E2), lbp[0]); \
@@ -1168,7 +1101,6 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
 #define IS_P1_GS4(SKY, lo, x_dead, x_closed)                                                       \
             {                                                                                      \
                 const int n_here = min(4, (vB - (lo)) / nw + 1);                                   \
-                ISP1_COUNT(5);                                                                     \
                 n_gs += n_here;                                                                    \
                 if (IS_P1_TOUCH_AHEAD > 0) touch_round(rcol, scol, vB - 4 * nw, nw, (lo), lane, scr); \
                 float c_f[4], c_cost[4];                                                           \
@@ -1318,7 +1250,7 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
             b.o = (live && cost < b.o) ? cost : b.o;
             vB += nw;
         }
-        if (IS_SKIP_GROUND_ABOVE_HORIZON && tile_lo >= vhor) {
+        if (tile_lo >= vhor) {
             for (; vB <= min(vhor, vB_last); vB += nw) { /* ground range, ground candidate = +inf */
                 const RowRec rb = sload_rec(rcol + vB);
                 const StepVals st = sload_step(scol + vB);
@@ -1355,9 +1287,7 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
      * Every L2-warming DMA must have landed before this wave can end: its LDS target would
      * otherwise be written after the workgroup's LDS has been handed to another one. */
     wait_vmcnt<0>();
-    ISP1_MARK(1);
     __syncthreads();
-    ISP1_MARK(2);
     float* m_cost = (float*)smem;               /* [nwl][3][64] (aliases the tile) */
     int* m_idx = (int*)(m_cost + nwl * 3 * 64); /* [nwl][3][64] */
     m_cost[(wl * 3 + 0) * 64 + lane] = b.g; m_idx[(wl * 3 + 0) * 64 + lane] = b.ig;
@@ -1381,11 +1311,10 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
         part_cost[o] = c;
         part_idx[o] = ix;
     }
-    ISP1_MARK(3);
 }
 
 #ifndef ISP1_OCC_INV
-#define ISP1_OCC_INV (IS_P1_DPP_INV ? 6 : 8) /* with an invalid-disparity value (8: the scalar-load form of the step, 64 VGPRs) */
+#define ISP1_OCC_INV 6 /* with an invalid-disparity value */
 #endif
 #ifndef ISP1_OCC
 #define ISP1_OCC 6 /* waves per SIMD phase 1 is compiled for: 80 VGPRs, no spills (8: 64 VGPRs + spills) */
@@ -1433,28 +1362,6 @@ __global__ __launch_bounds__(IS_UNARY_WAVES * 64, HAS_INVALID ? ISP1_OCC_INV : (
 #endif
 #define ISP2_WS (ISP2_WMAX + 1) /* row stride: lanes reading one column of 64 rows hit 32 banks */
 #define ISP2_ROWS (IS_TILE + 1)
-
-#ifdef IS_ABL_P2PHASES
-/* debug build only: s_memtime cycles of the sections of a phase-2 step, summed over all waves */
-__device__ unsigned long long g_p2phase[8];
-#define ISP2_MARK_INIT() unsigned long long t_p2 = __builtin_readcyclecounter()
-#define ISP2_MARK(k)                                                              \
-    do {                                                                          \
-        const unsigned long long now__ = __builtin_readcyclecounter();            \
-        acc_p2[k] += now__ - t_p2;                                                \
-        t_p2 = now__;                                                             \
-    } while (0)
-extern "C" void isk_debug_p2phases(unsigned long long* out, int reset) {
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_p2phase), sizeof(g_p2phase));
-    if (reset) {
-        unsigned long long z[8] = {0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_p2phase), z, sizeof(z));
-    }
-}
-#else
-#define ISP2_MARK_INIT()
-#define ISP2_MARK(k)
-#endif
 
 __device__ __forceinline__ float wave_min_f(float x) {
 #pragma unroll
@@ -1571,11 +1478,6 @@ __device__ __forceinline__ void pw_phase2_body(const DevParams& P, char* smem, i
     st.q_o = q_o; st.q_gs = q_gs;
     int ob_cached = -1;
     float S_obc = 0.0f, V_obc = 0.0f;
-#ifdef IS_ABL_P2PHASES
-    unsigned long long acc_p2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-    ISP2_MARK_INIT();
-    ISP2_MARK(0); /* prologue */
     for (int s = 0; s < n_rows; s++) {
         const int r = tile_lo + s; /* row that becomes final in this step */
         PriorVals pv = sload_prior(pcol + min(r + 1, H - 1));
@@ -1584,9 +1486,7 @@ __device__ __forceinline__ void pw_phase2_body(const DevParams& P, char* smem, i
             pv.pc = opaque_s(pv.pc); /* the record and the priors arrive behind one wait */
             const int hc = max(vTc + 1 - r, 1);
             const bool live = (vT < H) && (vT >= r);
-            ISP2_MARK(1); /* scalar loads */
             const SegTerms t = eval_segment<FAST, HAS_INVALID>(my, rb, (float)hc, s_rcp[hc], D, P.iw, s_rcp);
-            ISP2_MARK(2); /* eval_segment */
             const int fo = t.fni - lo;
             const bool inwin = (unsigned)fo < (unsigned)W;
             const int foc = inwin ? fo : 0;
@@ -1594,17 +1494,15 @@ __device__ __forceinline__ void pw_phase2_body(const DevParams& P, char* smem, i
             if (__builtin_amdgcn_ballot_w64(live && !inwin) != 0ull) { /* outside the window: rare */
                 /* (only the lanes outside fetch: with every lane gathering, a step of this kind pulled up to
                  * 128 lines -- 16 KB -- for the few values it needed) */
-                if (IS_P2_GATHER_MASKED ? (live && !inwin) : true) {
+                if (live && !inwin) {
                     const float og = my_row[(unsigned)t.fni] - (lcol + (size_t)r * D)[(unsigned)t.fni];
                     od = inwin ? od : og;
                 }
             }
-            ISP2_MARK(3); /* LUT values */
             if (r - 1 < vhor)
                 pairwise_step<false>(P, st, r, live, od, t, b);
             else
                 pairwise_step<true>(P, st, r, live, od, t, b);
-            ISP2_MARK(4); /* pairwise_step */
         }
         /* lane s holds the final values of row r: broadcast, derive the StepRec of vB = r+1.
          * (Also for the last row of the image, whose StepRec nobody reads: an unconditional
@@ -1634,10 +1532,8 @@ __device__ __forceinline__ void pw_phase2_body(const DevParams& P, char* smem, i
                 typedef const __attribute__((address_space(4))) float* cflt_t;
                 rcp_h = *(cflt_t)(rcp + min(max(r + 1 - ob, 1), H));
             }
-            ISP2_MARK(5); /* broadcasts */
             st = make_step<HAS_INVALID>(P, S_r1, V_r1, S_ob, V_ob, s_odr, s_invc, s_logc, &pv, vhor, r,
                                         cG, cO, cS, ob, rcp_h);
-            ISP2_MARK(6); /* make_step */
             /* fminf skips NaN fields: a candidate that selects one costs NaN and never wins */
             const float m8 = min_raw(min3_raw(st.p1_hi, st.p1_lo, st.p1_mid),
                                      min3_raw(min3_raw(st.p2_hi, st.p2_lo, st.p2_mid), st.p3_yes, st.p3_no));
@@ -1650,13 +1546,8 @@ __device__ __forceinline__ void pw_phase2_body(const DevParams& P, char* smem, i
                 store_step(scol + r + 1, st);
                 t8row[(size_t)colg * H + r + 1] = pwm8; /* (lemma L8: the row's own transition bound) */
             }
-            ISP2_MARK(7); /* running minima + store */
         }
     }
-#ifdef IS_ABL_P2PHASES
-    if (lane == 0)
-        for (int k = 0; k < 8; k++) atomicAdd(&g_p2phase[k], acc_p2[k]);
-#endif
     if (vT < H) {
         const size_t o = ((size_t)colg * H + vT) * 3;
         cost_table[o + 0] = b.g; cost_table[o + 1] = b.o; cost_table[o + 2] = b.s;
@@ -1887,7 +1778,7 @@ __device__ __forceinline__ void pw_phase2x_body(const DevParams& P, char* smem, 
         const int foc = inwin ? fo : 0;
         float od = my_win[foc] - my_winbase[(r - tile_lo) * ISP2X_WS + foc];
         if (__builtin_amdgcn_ballot_w64(live && !inwin) != 0ull) { /* outside the window: rare */
-            if (IS_P2_GATHER_MASKED ? (live && !inwin) : true) { /* (only the lanes outside fetch, see pw_phase2_body) */
+            if (live && !inwin) { /* (only the lanes outside fetch, see pw_phase2_body) */
                 const float og = (lcol + (size_t)(vTc + 1) * D)[(unsigned)t.fni] - (lcol + (size_t)r * D)[(unsigned)t.fni];
                 od = inwin ? od : og;
             }
@@ -2253,7 +2144,7 @@ __device__ __forceinline__ void pw_phase2s_body(const DevParams& P, char* smem, 
         /* S (and V) prefix at the START row of this lane's best object candidate, carried beside b.io: the row that
          * becomes final hands it to make_step through one v_readlane.  (Until round 6 the chain fetched it with a scalar
          * load from global memory whenever the start lay below the tile -- a round trip of its own on every such row:
-         * "broadcasts" 330 of the 2030 clocks a row costs, tools/experiments/p2s_phase_probe.py.) */
+         * "broadcasts" 330 of the 2030 clocks a row costs.) */
         float So, Vo = 0.0f;
         {
             const int ob0 = max(b.io, 0) / 3;
@@ -2267,11 +2158,6 @@ __device__ __forceinline__ void pw_phase2s_body(const DevParams& P, char* smem, 
         st.p2_hi = st.p2_lo = st.p2_mid = st.p3_yes = st.p3_no = 0.0f;
         float q_o = IS_INF, q_gs = IS_INF; /* (per tile, see pw_phase2_body) */
         st.q_o = q_o; st.q_gs = q_gs;
-#ifdef IS_ABL_P2PHASES /* (debug build: the chain wave's sections, tools/experiments/p2s_phase_probe.py) */
-        unsigned long long acc_p2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-        ISP2_MARK_INIT();
-        ISP2_MARK(0); /* prologue */
         for (int s = 0; s < n_rows; s++) {
             const int r = tile_lo + s;
             PriorVals pv;
@@ -2290,16 +2176,11 @@ __device__ __forceinline__ void pw_phase2s_body(const DevParams& P, char* smem, 
                 float fn = vs[8 * lane + 4];
                 isp2s_f4 p0 = v4[128], p1 = v4[129];
                 if (__builtin_amdgcn_readfirstlane(seen) < s) {
-#ifdef IS_ABL_P2PHASES
-                    acc_p2[3] += 1ull + (unsigned long long)isp2s_wait_ge(s_seq + q, s); /* (section 3: a count) */
-#else
                     isp2s_wait_ge(s_seq + q, s);
-#endif
                     lv = v4[2 * lane];
                     fn = vs[8 * lane + 4];
                     p0 = v4[128]; p1 = v4[129];
                 }
-                ISP2_MARK(1); /* slot flag + data */
                 const float a_gs = lv.x, b_gs = lv.y, a_o = lv.z, b_o = lv.w;
                 pv.pc = p0.x; pv.g_from = p0.y; pv.s_from_g = p0.z; pv.o_from_s = p0.w;
                 pv.og_hi = p1.x; pv.og_lo = p1.y; pv.og_mid = p1.z; pv.g_prev = p1.w;
@@ -2307,7 +2188,6 @@ __device__ __forceinline__ void pw_phase2s_body(const DevParams& P, char* smem, 
                  * execute in order) */
                 ISP2S_FENCE_RELEASE();
                 if (lane == 0) *s_cons = s;
-                ISP2_MARK(2); /* slot reads */
                 if (r - 1 < vhor)
                     pairwise_step_pre<false>(P, st, r, a_gs, b_gs, a_o, b_o, fn, b);
                 else
@@ -2317,7 +2197,6 @@ __device__ __forceinline__ void pw_phase2s_body(const DevParams& P, char* smem, 
                     So = up ? S_vb : So;
                     if (HAS_INVALID) Vo = up ? V_vb : Vo;
                 }
-                ISP2_MARK(4); /* pairwise_step */
             } else {
                 pv = sload_prior(pcol + min(r + 1, H - 1));
             }
@@ -2328,13 +2207,11 @@ __device__ __forceinline__ void pw_phase2s_body(const DevParams& P, char* smem, 
                 const float S_ob = readlane_f(So, s);
                 const float V_ob = HAS_INVALID ? readlane_f(Vo, s) : 0.0f;
                 S_vb = S_r1; V_vb = V_r1; /* prefix index r + 1 = the start row of the next step's candidates */
-                ISP2_MARK(5); /* broadcasts */
                 /* (measured here in round 6, neither kept: the exact-division shortcut for chains of up to 64 rows with
                  * its reciprocal out of a register through v_readlane -- make_step 844 -> 994 clocks, both divisions stay
                  * in the code --, and object_disparity_range[k] out of registers instead of LDS -- no measurable change) */
                 st = make_step<HAS_INVALID>(P, S_r1, V_r1, S_ob, V_ob, s_odr, s_invc, s_logc, &pv, vhor, r,
                                             cG, cO, cS, ob);
-                ISP2_MARK(6); /* make_step */
                 const float m8 = min_raw(min3_raw(st.p1_hi, st.p1_lo, st.p1_mid),
                                          min3_raw(min3_raw(st.p2_hi, st.p2_lo, st.p2_mid), st.p3_yes, st.p3_no));
                 if ((s & (IS_QB - 1)) == 0) q_o = q_gs = IS_INF; /* vB = r + 1 starts a bound block */
@@ -2346,13 +2223,8 @@ __device__ __forceinline__ void pw_phase2s_body(const DevParams& P, char* smem, 
                     store_step(scol + r + 1, st);
                     t8row[(size_t)colg * H + r + 1] = pwm8;
                 }
-                ISP2_MARK(7); /* running minima + store */
             }
         }
-#ifdef IS_ABL_P2PHASES
-        if (lane == 0)
-            for (int k = 0; k < 8; k++) atomicAdd(&g_p2phase[k], acc_p2[k]);
-#endif
         if (vT < H) {
             const size_t o = ((size_t)colg * H + vT) * 3;
             cost_table[o + 0] = b.g; cost_table[o + 1] = b.o; cost_table[o + 2] = b.s;
@@ -2389,7 +2261,7 @@ __device__ __forceinline__ void pw_phase2s_body(const DevParams& P, char* smem, 
             if (__builtin_amdgcn_ballot_w64(live && !inwin) != 0ull) { /* outside the window: rare */
                 /* (only the lanes outside fetch: with every lane gathering, a step of this kind pulled up to
                  * 128 lines -- 16 KB -- for the few values it needed) */
-                if (IS_P2_GATHER_MASKED ? (live && !inwin) : true) {
+                if (live && !inwin) {
                     const float og = my_row[(unsigned)t.fni] - (lcol + (size_t)r * D)[(unsigned)t.fni];
                     od = inwin ? od : og;
                 }
@@ -2505,9 +2377,6 @@ hipError_t isk_launch_dp_pairwise(const DevParams* P, int ncols, int nwaves, con
 /* the vB-side lutT row in registers (LutRow<2>, D <= 128): slower than the per-lane gather while
  * phase 1 was issue-bound (41.4 vs 38.0 ms per 64 frames, round 1), faster now that the pruned
  * phase 1 is latency-bound (30.4 vs 31.2 ms): no memory access on the chain mean -> fn -> value */
-#ifndef IS_PW_PHASE1_ROW_REGS
-#define IS_PW_PHASE1_ROW_REGS 1
-#endif
 #define IS_LAUNCH_P1(INV, c0, c1, st)                                                              \
     do {                                                                                           \
         if (win_t)                                                                                 \
@@ -2515,7 +2384,7 @@ hipError_t isk_launch_dp_pairwise(const DevParams* P, int ncols, int nwaves, con
                                dim3(nw_t * 64), lds1_t, st, *P, c0, c1, tile, nsplit, recs, lutT,  \
                                steps, rcp, vhor, col_flags, prune, part_cost, part_idx, counters, \
                                joined, cost_T, blksum);                                            \
-        else if (IS_PW_PHASE1_ROW_REGS && P->D <= 128)                                             \
+        else if (P->D <= 128)                                                                      \
             hipLaunchKernelGGL((k_pw_phase1<INV, 2>), dim3(((c1) - (c0)) * nsplit),                \
                                dim3(nw_t * 64), lds1_t, st, *P, c0, c1, tile, nsplit, recs, lutT,  \
                                steps, rcp, vhor, col_flags, prune, part_cost, part_idx, counters, \

@@ -6,14 +6,8 @@
 /* A4-A6  per-column preparation                                                           */
 /* ====================================================================================== */
 #define PREP_THREADS 256
-#ifndef PREP_STORE_LATE
-#define PREP_STORE_LATE 1
-#endif
-#ifndef PREP_CLASS_BY_WAVE
-#define PREP_CLASS_BY_WAVE 1 /* measured: column blocks 1.04 -> 0.95 ms, fused launch 2.56 -> 2.48 ms per batch of 64 */
-#endif
 #ifndef PREP_EPI_ROWS
-#define PREP_EPI_ROWS 256 /* rows per block of the record epilogue (0 = piece by piece) */
+#define PREP_EPI_ROWS 256 /* rows per block of the record epilogue */
 #endif
 
 /* LDS stride of a segmentation channel: H/8 + 1 prefix entries, rounded up to 16 bytes */
@@ -112,19 +106,8 @@ __device__ __forceinline__ int32_t full_prefix(const int32_t* ps, int v) {
     return r;
 }
 
-#ifndef PREP_REC_NT
-#define PREP_REC_NT 0
-#endif
 /* one 16-byte piece of a record */
-__device__ __forceinline__ void prep_store16(int4* dst, int4 x) {
-#if PREP_REC_NT
-    typedef int v4i __attribute__((ext_vector_type(4)));
-    v4i y = {x.x, x.y, x.z, x.w};
-    __builtin_nontemporal_store(y, reinterpret_cast<v4i*>(dst));
-#else
-    *dst = x;
-#endif
-}
+__device__ __forceinline__ void prep_store16(int4* dst, int4 x) { *dst = x; }
 __device__ __forceinline__ void store_instance_prefix(RowRec* o, int slow, int64_t mx, int64_t my,
                                                       int64_t mx2, int64_t my2) {
     /* dwords 24..31 of the record as two 16-byte stores */
@@ -252,7 +235,7 @@ __device__ __forceinline__ void prepare_columns_body(
             const int n_b = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ok && IS_WIN_FIND(w_b, fl) >= 0));
             const int n_s = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ok && IS_WIN_FIND(w_s, fl) >= 0));
             int w_best = n_b > n_a ? w_b : w_a;
-            if (IS_WIN_SPLIT && n_s > max(n_a, n_b)) w_best = w_s;
+            if (n_s > max(n_a, n_b)) w_best = w_s;
             if (lane == 0) P.win_lo[(size_t)colg * P.ntiles + t] = w_best;
         }
     }
@@ -325,7 +308,7 @@ __device__ __forceinline__ void prepare_columns_body(
     int64_t base_mx2 = block_excl_scan_i64(sum_mx2, s_wave);
     int64_t base_my2 = block_excl_scan_i64(sum_my2, s_wave);
     /* the owner of rows [r_lo, r_lo+R) writes the exclusive prefix at those indices; the owner
-     * of row H-1 also writes index H (the total).  PREP_STORE_LATE: every piece of a 128-byte record
+     * of row H-1 also writes index H (the total).  Every piece of a 128-byte record
      * (instance prefixes, class chunks, the four fp32 prefixes) is stored at the END of the kernel,
      * back to back, so that the pieces of a line meet in the L2 instead of reaching the memory as
      * eight partial writes spread over the workgroup's life. */
@@ -336,9 +319,7 @@ __device__ __forceinline__ void prepare_columns_body(
     auto instance_rows = [&](bool store, auto dst_row) {
         int64_t bx = base_mx, by = base_my, bx2 = base_mx2, by2 = base_my2;
         for (int r = r_lo; r < r_lo + R && r < H; r++) {
-#ifndef PREP_ABL_NOSTORE_INST
             if (store) store_instance_prefix(dst_row(r), slow, bx, by, bx2, by2);
-#endif
             const double fx = ((double)(P.column_step * col) + 0.5 * ((double)P.column_step - 1.0)) +
                               (double)offx_raw(r >> 3) + 0.5;
             const int64_t mx = (int64_t)fx;
@@ -354,24 +335,12 @@ __device__ __forceinline__ void prepare_columns_body(
             s_tot[0] = (float)((double)bx2 + (double)by2); /* column totals (PruneRec.E2) */
         }
     };
-#ifndef PREP_REC_NT
-#define PREP_REC_NT 0
-#endif
-#ifdef PREP_ABL_RECWRAP /* ablation: the same record stores into 8 rows per column (absorbed by the L2) */
-#define PREP_RROW(v) ((v) & 7)
-#else
-#define PREP_RROW(v) (v)
-#endif
-    auto rec_row = [&](int r) -> RowRec* { return rcol + PREP_RROW(r); };
-    if (PREP_STORE_LATE) {
-        /* (the records are stored in the epilogue; here only the column totals are needed, and the owner of row
-         * H - 1 has them: its exclusive prefix + its own rows -- the integers instance_rows would end with) */
-        if (r_lo <= H - 1 && H - 1 < r_lo + R)
-            s_tot[0] = (float)((double)(int64_t)((uint64_t)base_mx2 + (uint64_t)sum_mx2) +
-                               (double)(int64_t)((uint64_t)base_my2 + (uint64_t)sum_my2));
-    } else {
-        instance_rows(true, rec_row);
-    }
+    auto rec_row = [&](int r) -> RowRec* { return rcol + r; };
+    /* (the records are stored in the epilogue; here only the column totals are needed, and the owner of row
+     * H - 1 has them: its exclusive prefix + its own rows -- the integers instance_rows will end with) */
+    if (r_lo <= H - 1 && H - 1 < r_lo + R)
+        s_tot[0] = (float)((double)(int64_t)((uint64_t)base_mx2 + (uint64_t)sum_mx2) +
+                           (double)(int64_t)((uint64_t)base_my2 + (uint64_t)sum_my2));
     __syncthreads();
 
     /* ---- square the offset channels in place (StixelsKernels.cu:411-416), then exclusive
@@ -478,21 +447,18 @@ __device__ __forceinline__ void prepare_columns_body(
         for (int it = tid; it < NB * 5; it += PREP_THREADS) {
             const int kb = it / 5, q = it - kb * 5;
             class_item(kb, q, [&](int v, int qq, int4 x) {
-#ifndef PREP_ABL_NOSTORE_CLASS
-                prep_store16(reinterpret_cast<int4*>(rcol + PREP_RROW(v)) + qq, x);
-#endif
+                prep_store16(reinterpret_cast<int4*>(rcol + v) + qq, x);
             });
         }
     }
     };
-    if (!PREP_STORE_LATE) class_chunks();
 
     /* ---- fp32 prefixes with the reference's block-scan association (:452-461).  A thread keeps
      * the four prefixes of its rows (v = tid + k * PREP_THREADS) and writes dwords 20..23 of the
      * record {G, K, S, V} as ONE 16-byte store per row at the end. */
     constexpr int MAXR = 9; /* rows per thread held in registers: H + 1 <= 9 * 256 */
     const bool regs = (H + 1) <= MAXR * PREP_THREADS;
-    const bool epi = PREP_EPI_ROWS > 0 && PREP_STORE_LATE && regs && R > 0 && (PREP_EPI_ROWS % (R > 0 ? R : 1)) == 0;
+    const bool epi = regs && R > 0 && (PREP_EPI_ROWS % (R > 0 ? R : 1)) == 0;
     float pS[MAXR], pV[MAXR], pG[MAXR], pK[MAXR];
 #pragma unroll
     for (int k = 0; k < MAXR; k++) pS[k] = pV[k] = pG[k] = pK[k] = 0.0f;
@@ -614,9 +580,7 @@ __device__ __forceinline__ void prepare_columns_body(
             const int v = tid + k * PREP_THREADS;
             if (v <= H) {
                 pK[k] = prefix_at(v);
-#ifndef PREP_ABL_NOSTORE_F4
-                if (!epi) prep_store16(reinterpret_cast<int4*>(rcol + PREP_RROW(v)) + 5, make_int4(__float_as_int(pG[k]), __float_as_int(pK[k]), __float_as_int(pS[k]), __float_as_int(pV[k])));
-#endif
+                if (!epi) prep_store16(reinterpret_cast<int4*>(rcol + v) + 5, make_int4(__float_as_int(pG[k]), __float_as_int(pK[k]), __float_as_int(pS[k]), __float_as_int(pV[k])));
             }
         }
     } else {
@@ -627,12 +591,12 @@ __device__ __forceinline__ void prepare_columns_body(
      * 64: the 34 extra barriers cost more than the partial lines do; the kernel is bound by its LDS /
      * VALU work, not by its 2.15 GB of stores) */
     if (epi) {
-        /* PREP_EPI_ROWS: the epilogue walks the column in blocks of rows and every producer stores its
+        /* The epilogue walks the column in blocks of rows and every producer stores its
          * pieces of the block's records before anyone goes on to the next block -- no barrier, the waves
          * only have to stay roughly together: the partial lines a workgroup has in flight are
          * PREP_EPI_ROWS x 128 bytes instead of the whole column's 131 KB (x 128 workgroups per XCD: 16.8 MB
          * against 4 MB of L2 -- lines left the L2 before their last piece arrived). */
-        constexpr int ER = PREP_EPI_ROWS > 0 ? PREP_EPI_ROWS : PREP_THREADS;
+        constexpr int ER = PREP_EPI_ROWS;
         constexpr int M = ER >= PREP_THREADS ? ER / PREP_THREADS : 1; /* register slots per block */
         constexpr int SUBS = ER >= PREP_THREADS ? 1 : PREP_THREADS / ER; /* blocks per register slot */
         static_assert(ER % 8 == 0 && (ER >= PREP_THREADS ? ER % PREP_THREADS == 0 : PREP_THREADS % ER == 0),
@@ -648,58 +612,38 @@ __device__ __forceinline__ void prepare_columns_body(
                         if (k < MAXR) {
                             const int v = k * PREP_THREADS + tid;
                             if ((SUBS == 1 || tid / ER == sub) && v <= H)
-                                prep_store16(reinterpret_cast<int4*>(rcol + PREP_RROW(v)) + 5,
+                                prep_store16(reinterpret_cast<int4*>(rcol + v) + 5,
                                              make_int4(__float_as_int(pG[k]), __float_as_int(pK[k]),
                                                        __float_as_int(pS[k]), __float_as_int(pV[k])));
                         }
                     }
-#ifdef PREP_ABL_WAVEROWS /* timing-only: every wave stores ALL pieces of its own 64 rows (instance pieces: dummies) */
-                    {
-                        const int v = kk * M * PREP_THREADS + tid;
-                        if (v <= H) {
-                            prep_store16(reinterpret_cast<int4*>(rcol + v) + 6, make_int4(v, tid, 0, 0));
-                            prep_store16(reinterpret_cast<int4*>(rcol + v) + 7, make_int4(v, tid, 1, 0));
-                        }
-                        const int ln = tid & 63, wv = tid >> 6;
-                        if (ln < 40) {
-                            const int kbl = ln / 5, q = ln - kbl * 5, kb = ((row0 + 64 * wv) >> 3) + kbl;
-                            if (kb * 8 <= H)
-                                class_item(kb, q, [&](int vv, int qq, int4 x) {
-                                    prep_store16(reinterpret_cast<int4*>(rcol + PREP_RROW(vv)) + qq, x);
-                                });
-                        }
-                    }
-                    if (false)
-#elif PREP_CLASS_BY_WAVE
                     /* the class chunks of a wave's OWN 64 rows (the rows whose {G, K, S, V} it has just stored):
-                     * lanes 0..39 = 8 blocks x 5 chunks */
+                     * lanes 0..39 = 8 blocks x 5 chunks.  Measured against the block-strided loop below: column
+                     * blocks 1.04 -> 0.95 ms, fused launch 2.56 -> 2.48 ms per batch of 64 */
                     if (ER == PREP_THREADS) {
                         const int ln = tid & 63, wv = tid >> 6;
                         if (ln < 40) {
                             const int kbl = ln / 5, q = ln - kbl * 5, kb = ((row0 + 64 * wv) >> 3) + kbl;
                             if (kb * 8 <= H)
                                 class_item(kb, q, [&](int vv, int qq, int4 x) {
-                                    prep_store16(reinterpret_cast<int4*>(rcol + PREP_RROW(vv)) + qq, x);
+                                    prep_store16(reinterpret_cast<int4*>(rcol + vv) + qq, x);
                                 });
                         }
                     } else
-#endif
                     for (int it = tid; it < (ER / 8) * 5; it += PREP_THREADS) { /* class chunks: 1/8-resolution blocks x 5 */
                         const int kbl = it / 5, q = it - kbl * 5, kb = (row0 >> 3) + kbl;
                         if (kb * 8 <= H)
                             class_item(kb, q, [&](int v, int qq, int4 x) {
-                                prep_store16(reinterpret_cast<int4*>(rcol + PREP_RROW(v)) + qq, x);
+                                prep_store16(reinterpret_cast<int4*>(rcol + v) + qq, x);
                             });
                     }
-#ifndef PREP_ABL_WAVEROWS
                     if (r_lo >= row0 && r_lo < row0 + ER) instance_rows(true, rec_row);
-#endif
                 }
             }
         }
         /* (row H when it starts a block of its own -- H a multiple of PREP_EPI_ROWS: its class chunk and
          * {G, K, S, V} went out with that block above, its instance piece with row H - 1's owner) */
-    } else if (PREP_STORE_LATE) {
+    } else {
         class_chunks();
         instance_rows(true, rec_row);
     }
@@ -728,27 +672,19 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prepare_columns(
  * transposed cost table and every store of a lutT row is one fully coalesced 256-byte access. */
 #define LUT_BLOCK 32
 /* The table is 8.6 GB for a batch of 64 (1024 x 2048 x 128): its stores ARE the kernel.  Measured (batch 64,
- * the LUT units as a kernel of their own, tools/abl_prep.sh): 1.78 ms = 4.8 TB/s with plain stores; the same instruction stream
- * with the stores wrapped into 8 rows per column (absorbed by the L2, PREP_ABL_WRAP) 0.48 ms; non-temporal
- * stores (full 256-byte rows that nothing reads before the whole table is written: no reason to keep them in
- * the L2 / MALL) 1.59 ms = 5.4 TB/s.  Storing fewer fn per row only pays in whole 128-byte lines
- * (PREP_ABL_FNMAX=105: 2.37 ms, partial lines are read-modify-write). */
-#ifndef PREP_LUT_NT
-#define PREP_LUT_NT 1
-#endif
+ * the LUT units as a kernel of their own): 1.78 ms = 4.8 TB/s with plain stores; the same instruction stream
+ * with the stores wrapped into 8 rows per column (absorbed by the L2) 0.48 ms; non-temporal stores (full
+ * 256-byte rows that nothing reads before the whole table is written: no reason to keep them in the L2 /
+ * MALL) 1.59 ms = 5.4 TB/s.  Storing fewer fn per row only pays in whole 128-byte lines (105 of 128 fn:
+ * 2.37 ms, partial lines are read-modify-write). */
 __device__ __forceinline__ void object_lut_body(const DevParams& P, const int colg, const int fn_block,
                                                 const int lane, const float* __restrict__ joined,
                                                 const float* __restrict__ cost_T /*[dis][fn]*/,
                                                 float* __restrict__ lutT) {
     const int H = P.H, D = P.D;
     const int fn = fn_block * 64 + lane;
-#ifdef PREP_ABL_FNMAX /* ablation: how much of the LUT blocks' time is their store bytes */
-    const bool fn_ok = fn < PREP_ABL_FNMAX;
-    const int fnc = fn_ok ? fn : PREP_ABL_FNMAX - 1;
-#else
     const bool fn_ok = fn < D;
     const int fnc = fn_ok ? fn : D - 1;
-#endif
     const float* dcol = joined + (size_t)colg * H;
     float* lcol = lutT + (size_t)colg * (H + 1) * D;
     if (fn_ok) lcol[fn] = 0.0f; /* arr[0] = 0, :283-285 */
@@ -799,13 +735,7 @@ __device__ __forceinline__ void object_lut_body(const DevParams& P, const int co
         }
         if (full) {
 #pragma unroll
-#ifdef PREP_ABL_WRAP /* ablation: the same stores into 8 rows per column (absorbed by the L2): what do the HBM bytes cost */
-            for (int l = 0; l < LUT_BLOCK; l++) lcol[(size_t)((i + l + 1) & 7) * D + fnc] = c[l];
-#elif PREP_LUT_NT
-            for (int l = 0; l < LUT_BLOCK; l++) __builtin_nontemporal_store(c[l], &lcol[(size_t)(i + l + 1) * D + fnc]);
-#else
-            for (int l = 0; l < LUT_BLOCK; l++) lcol[(size_t)(i + l + 1) * D + fnc] = c[l]; /* :266 */
-#endif
+            for (int l = 0; l < LUT_BLOCK; l++) __builtin_nontemporal_store(c[l], &lcol[(size_t)(i + l + 1) * D + fnc]); /* :266 */
         } else if (fn_ok) {
 #pragma unroll
             for (int l = 0; l < LUT_BLOCK; l++)
@@ -845,12 +775,6 @@ __global__ __launch_bounds__(64) void k_object_lut_repair(const DevParams P, int
  * 0.325 ms) -- side by side they take the memory system from each other.  (Until the LUT loop
  * stored unconditionally its body took 166 VGPRs under this kernel's launch bounds and the fused
  * launch cost a large batch the occupancy both bodies live on: 8.2 ms.) */
-#ifndef IS_FUSED_LUT_FIRST
-#define IS_FUSED_LUT_FIRST 0
-#endif
-#ifndef IS_FUSED_INTERLEAVE
-#define IS_FUSED_INTERLEAVE 0
-#endif
 __global__ __launch_bounds__(PREP_THREADS) void k_prepare_fused(
     const DevParams P, int ncols, int n_lut, const float* __restrict__ joined, const int32_t* __restrict__ seg,
     const float* __restrict__ ground, const int* __restrict__ vhor_arr, const float* __restrict__ cost_T,
@@ -858,31 +782,8 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prepare_fused(
     float* __restrict__ sv_arr, PruneRec* __restrict__ prune, int* __restrict__ n_generic) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int b = (int)blockIdx.x;
-    bool is_lut;
-    int lut_b, col_b;
-#if IS_FUSED_INTERLEAVE
-    /* block order: IS_FUSED_INTERLEAVE column blocks, one LUT block, ... while both kinds last */
-    {
-        constexpr int G = IS_FUSED_INTERLEAVE + 1;
-        const int groups = min(ncols / IS_FUSED_INTERLEAVE, n_lut); /* full groups */
-        if (b < groups * G) {
-            const int g = b / G, r = b - g * G;
-            is_lut = r == IS_FUSED_INTERLEAVE;
-            lut_b = g;
-            col_b = g * IS_FUSED_INTERLEAVE + r;
-        } else { /* the rest of the longer kind */
-            const int rest = b - groups * G;
-            const int cols_left = ncols - groups * IS_FUSED_INTERLEAVE;
-            is_lut = rest >= cols_left;
-            col_b = groups * IS_FUSED_INTERLEAVE + rest;
-            lut_b = groups + (rest - cols_left);
-        }
-    }
-#else
-    is_lut = IS_FUSED_LUT_FIRST ? b < n_lut : b >= ncols;
-    lut_b = IS_FUSED_LUT_FIRST ? b : b - ncols;
-    col_b = IS_FUSED_LUT_FIRST ? b - n_lut : b;
-#endif
+    const bool is_lut = b >= ncols; /* the LUT blocks follow the column blocks */
+    const int lut_b = b - ncols, col_b = b;
     if (is_lut) {
         const int fn_blocks = (P.D + 63) / 64;
         const int unit = lut_b * (PREP_THREADS / 64) + (int)(threadIdx.x >> 6);
@@ -926,11 +827,7 @@ extern "C" {
 
 size_t isk_prepare_lds_bytes(const DevParams* P) {
     return sizeof(float) * (size_t)prep_scan_leaves(P->H, P->P2) * 3 +
-           sizeof(int32_t) * (size_t)P->CH * prep_seg_stride(P->H) + 192
-#ifdef PREP_LDS_PAD /* occupancy experiments */
-           + PREP_LDS_PAD
-#endif
-        ;
+           sizeof(int32_t) * (size_t)P->CH * prep_seg_stride(P->H) + 192;
 }
 
 hipError_t isk_launch_lut_repair(const DevParams* P, int ncols, const float* joined, const float* cost_T, float* lutT,

@@ -37,7 +37,7 @@ __device__ __forceinline__ void unary_step(const DevParams& P, const RowRec& my,
     /* cost = dw*data + pw*(1/h) + sw*seg, left to right (:716-719, 762-765, 820-823) */
     const float cost_o = P.dw * od + pwih + P.sw * t.seg_o;
     /* full steps: every lane with vT < H is live, and rows vT >= H are never stored */
-    constexpr bool ALL_LANES = IS_CMPX_UPDATE && FAST && !DIAG && !FIRST;
+    constexpr bool ALL_LANES = FAST && !DIAG && !FIRST;
     if (ALL_LANES) {
         take_if_less(b.o, b.vo, cost_o, vB);
     } else {
@@ -117,7 +117,7 @@ __device__ __forceinline__ void unary_loop(const DevParams& P, const RowRec& my,
                                                                   vTc, vhor, 0, 0.0f, row_ok, b);
         vB += nw;
     }
-    if (IS_SKIP_GROUND_ABOVE_HORIZON && tile_lo >= vhor) /* whole tile at / above the horizon */
+    if (tile_lo >= vhor) /* whole tile at / above the horizon */
         vB = unary_range<FAST, HAS_INVALID, false, false, NR, true>(
             P, my, rcol, lcol, my_tile, s_rcp, vT, vTc, vhor, vB, nw, min(min(vhor, tile_lo), vB_end),
             row_ok, lane4, lrsrc, next_row, b);
@@ -165,7 +165,7 @@ __device__ __forceinline__ SegTerms unary_step_desc(const DevParams& P, const Ro
     const float od = my_tile[t.fni] - pick_lut<NR>(lrow, t.fni);
     const float pwih = P.pw * r;
     const float cost_o = P.dw * od + pwih + P.sw * t.seg_o;
-    constexpr bool ALL_LANES = IS_CMPX_UPDATE && !DIAG && !FIRST;
+    constexpr bool ALL_LANES = !DIAG && !FIRST;
     if (ALL_LANES) {
         take_if_le(b.o, b.vo, cost_o, vB);
     } else {
@@ -235,7 +235,7 @@ __device__ __forceinline__ int unary_range_desc(const DevParams& P, const RowRec
         const SegTerms t = unary_step_desc<HAS_INVALID, SKY, DIAG, false, NR, NOGROUND>(
             P, my, cur, row, my_tile, s_rcp, vT, vTc, vhor, vB, hf, row_ok, b);
         hf += nwf;
-        if (PRUNE && IS_PRUNE && nothing_below_can_win<SKY, NOGROUND>(P, pv, t, b)) return IS_WAVE_DONE;
+        if (PRUNE && nothing_below_can_win<SKY, NOGROUND>(P, pv, t, b)) return IS_WAVE_DONE;
     }
     return vB;
 }
@@ -260,7 +260,7 @@ __device__ __forceinline__ void unary_loop_desc(const DevParams& P, const RowRec
     }
     LutRow<NR> next_row;
     load_lut_row<NR>(next_row, lrsrc, lcol, vB, P.D, lane4);
-    const bool nog = IS_SKIP_GROUND_ABOVE_HORIZON && tile_lo >= vhor;
+    const bool nog = tile_lo >= vhor;
 #define IS_RANGE(SKY, DIAG, PRUNE, NOG, lower)                                                     \
     vB = unary_range_desc<HAS_INVALID, SKY, DIAG, PRUNE, NR, NOG>(P, my, rcol, lcol, my_tile, s_rcp,   \
                                                                   vT, vTc, vhor, vB, nw, lower, row_ok, \
@@ -287,27 +287,6 @@ __device__ __forceinline__ void unary_loop_desc(const DevParams& P, const RowRec
                                                                         vTc, vhor, 0, 0.0f, row_ok, b);
     }
 }
-
-#ifdef IS_ABL_PHASES
-/* debug build only: cycles (s_memtime) spent by wave 0 of every workgroup pass in staging / loop /
- * wait-for-other-waves / merge+store, summed over the launch */
-__device__ unsigned long long g_phase[8];
-#define IS_PHASE_MARK(k)                                                                  \
-    do {                                                                                  \
-        const unsigned long long now__ = __builtin_readcyclecounter();                    \
-        if (threadIdx.x == 0) atomicAdd(&g_phase[k], now__ - t_phase);                    \
-        t_phase = now__;                                                                  \
-    } while (0)
-extern "C" void isk_debug_phases_old(unsigned long long* out, int reset) {
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase), sizeof(g_phase));
-    if (reset) {
-        unsigned long long z[8] = {0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_phase), z, sizeof(z));
-    }
-}
-#else
-#define IS_PHASE_MARK(k)
-#endif
 
 /* FASTCOLS: the launch handles only the columns of that encoding (col_flags), workgroups of the
  * other kind leave at once.  Two lean kernels instead of one that carries both loop nests: no
@@ -371,9 +350,6 @@ __global__ __launch_bounds__(IS_UNARY_WAVES * 64, IS_UNARY_OCC) void k_dp_unary(
     const int tile_lo = tile * IS_TILE;
     if (!first) __syncthreads(); /* the merge area of the previous tile aliases the LUT tile */
     first = false;
-#ifdef IS_ABL_PHASES
-    unsigned long long t_phase = __builtin_readcyclecounter();
-#endif
 
     stage_lut_tile<false>(s_tile, lcol, tile_lo, H, D, tid, (int)blockDim.x);
 
@@ -381,7 +357,6 @@ __global__ __launch_bounds__(IS_UNARY_WAVES * 64, IS_UNARY_OCC) void k_dp_unary(
     const int vTc = min(vT, H - 1);
     const RowRec my = load_rec(rcol + vTc + 1);
     __syncthreads();
-    IS_PHASE_MARK(0);
 
     UnaryBest b;
     b.g = b.o = b.s = IS_INF;
@@ -389,20 +364,16 @@ __global__ __launch_bounds__(IS_UNARY_WAVES * 64, IS_UNARY_OCC) void k_dp_unary(
     b.vo = 0; /* index_table[vT*3+OBJECT] = OBJECT at vB = 0, :592 */
     const float* my_tile = s_tile + lane * DP;
     const int vB_end = min(tile_lo + IS_TILE - 1, H - 1);
-#ifndef IS_ABL_NOLOOP
     if (FASTCOLS)
         unary_loop_desc<HAS_INVALID, NR>(P, my, rcol, lcol, my_tile, s_rcp, vT, vTc, vhor, w, nw, tile_lo,
                                          vB_end, lane * 4, lrsrc, prune + colg, b);
     else
         unary_loop<false, HAS_INVALID, NR>(P, my, rcol, lcol, my_tile, s_rcp, vT, vTc, vhor, w, nw, tile_lo,
                                            vB_end, lane * 4, lrsrc, b);
-#endif
-    IS_PHASE_MARK(1);
 
     /* merge the waves' partial minima: min cost, ties -> smallest vB (= first strict minimum
      * of the reference's ascending-vB loop) */
     __syncthreads();
-    IS_PHASE_MARK(2);
     float* m_cost = s_tile;                        /* [nw][3][64] (aliases the LUT tile) */
     int* m_vb = (int*)(m_cost + nw * 3 * 64);      /* [nw][3][64] */
     m_cost[(w * 3 + 0) * 64 + lane] = b.g; m_vb[(w * 3 + 0) * 64 + lane] = b.vg;
@@ -436,7 +407,6 @@ __global__ __launch_bounds__(IS_UNARY_WAVES * 64, IS_UNARY_OCC) void k_dp_unary(
         cd[0] = m_cost[0 * 64 + lane]; cd[1] = m_cost[1 * 64 + lane]; cd[2] = m_cost[2 * 64 + lane];
         id[0] = m_vb[0 * 64 + lane]; id[1] = m_vb[1 * 64 + lane]; id[2] = m_vb[2 * 64 + lane];
     }
-    IS_PHASE_MARK(3);
     } /* pass */
     } /* pair */
     } /* item */

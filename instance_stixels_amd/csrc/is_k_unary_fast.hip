@@ -41,12 +41,6 @@
 #ifndef ISF_WAVES
 #define ISF_WAVES 8
 #endif
-#ifndef ISF_DPP
-#define ISF_DPP 1 /* the record of vB as two dwords per lane + DPP operands instead of 32 VGPRs */
-#endif
-#ifndef ISF_GS_STEPS
-#define ISF_GS_STEPS 1 /* ground / sky-only steps once the object bound holds for the wave */
-#endif
 #ifndef ISF_OCC_INV
 #define ISF_OCC_INV 6 /* with an invalid-disparity value (round 5: the mean through mean_valid_fast; 5 while it was an IEEE division; 7 until round 5: at 72 VGPRs these instantiations spill 2-6 registers; measured again with the 22.8 KB workgroups that LDS admits seven of: 6 | 7 waves per SIMD 10 600 | 10 220 frames/s at invalid_disparity = 0, 15 550 | 15 130 on the 784x1792 crop) */
 #endif
@@ -92,7 +86,7 @@ __device__ __forceinline__ SegTerms fast_step(const DevParams& P, const RowRec& 
     const bool live = DIAG ? ((h > 0) && row_ok) : row_ok;
     const int hc = DIAG ? max(h, 1) : h;
     const float r = s_rcp[hc]; /* RN(1/h) = (float)(1./h) = inverse_height, :485, :608 */
-#if ISF_DPP
+    /* the record of vB as two dwords per lane + DPP operands instead of 32 VGPRs */
     const int l15 = threadIdx.x & 15;
     /* FIRST (vB = 0): ground + object; otherwise the sky OR the ground candidate, or neither */
     constexpr int WANT = SKY ? IS_WANT_SKY : (NOGROUND ? 0 : IS_WANT_GROUND);
@@ -101,10 +95,6 @@ __device__ __forceinline__ SegTerms fast_step(const DevParams& P, const RowRec& 
 #else
     const SegTerms t = eval_segment_dpp<HAS_INVALID, WANT>(my, srec[l15], srec[16 + l15], (float)hc, r, P.D,
                                                            P.iw, s_rcp);
-#endif
-#else
-    const RowRec rb = lds_rec(srec);
-    const SegTerms t = eval_segment<true, HAS_INVALID>(my, rb, (float)hc, r, P.D, P.iw, s_rcp);
 #endif
     float vtv, vbv;
     if (WIN) {
@@ -130,7 +120,7 @@ __device__ __forceinline__ SegTerms fast_step(const DevParams& P, const RowRec& 
     const float pwih = P.pw * r;
     /* cost = dw*data + pw*(1/h) + sw*seg, left to right (:716-719, 762-765, 820-823) */
     const float cost_o = P.dw * od + pwih + P.sw * t.seg_o;
-    constexpr bool ALL_LANES = IS_CMPX_UPDATE && !DIAG && !FIRST;
+    constexpr bool ALL_LANES = !DIAG && !FIRST;
     if (ALL_LANES) {
         take_if_le(b.o, b.vo, cost_o, vB);
     } else {
@@ -251,27 +241,6 @@ __device__ __forceinline__ bool gs_walk(const DevParams& P, const PruneValsF& pv
     return false;
 }
 
-#ifdef IS_ABL_PHASES
-__device__ unsigned long long g_fphase[8];
-#define ISF_MARK_INIT() unsigned long long t_phase = __builtin_readcyclecounter()
-#define ISF_MARK(k)                                                                       \
-    do {                                                                                  \
-        const unsigned long long now__ = __builtin_readcyclecounter();                    \
-        if (threadIdx.x == 0) atomicAdd(&g_fphase[k], now__ - t_phase);                   \
-        t_phase = now__;                                                                  \
-    } while (0)
-extern "C" void isk_debug_phases(unsigned long long* out, int reset) {
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fphase), sizeof(g_fphase));
-    if (reset) {
-        unsigned long long z[8] = {0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_fphase), z, sizeof(z));
-    }
-}
-#else
-#define ISF_MARK_INIT()
-#define ISF_MARK(k)
-#endif
-
 /* LDS-DMA of the lutT row and the record of vB into one ring slot: NVR + 1 VMEM instructions,
  * always issued (a uniform count for wait_vmcnt), no registers, no waiting. */
 template <int NVR>
@@ -330,9 +299,6 @@ __device__ __forceinline__ void ring_prefetch_win(const WinLane& wl, int vB, flo
  * `<=` update of a descending walk are fast_step's.  The tile that contains the horizon keeps the uniform steps (its
  * vB change from ground to sky candidates on the way).  Afterwards every lane holds its own row again and the wave
  * goes on below the tile. */
-#ifndef ISF_QDIAG
-#define ISF_QDIAG 1
-#endif
 /* Every record of the tile is staged in LDS (s_nat): the record of vB = tile_lo + a IS the record of row a - 1, so the
  * vB operands, the first record of every lane and the records the quarters 0 and 1 come back to are all LDS reads --
  * nothing in the diagonal phase waits for memory: 3.67 against 4.00 ms per 64 frames for staging only the rows
@@ -537,12 +503,8 @@ __device__ __forceinline__ void lut_unit_fused(const DevParams& P, const int col
         }
         float* dst = lcol + (size_t)(i + 1) * D + fnc;
         if (full) {
-#ifdef ISF_ABL_LUTF_NOSTORE /* timing-only ablation: one row per block is stored (the network stays alive) */
-            __builtin_nontemporal_store(c[LB - 1], dst + (size_t)(LB - 1) * D);
-#else
 #pragma unroll
             for (int l = 0; l < LB; l++) __builtin_nontemporal_store(c[l], dst + (size_t)l * D);
-#endif
         } else if (fn_ok) {
 #pragma unroll
             for (int l = 0; l < LB; l++)
@@ -550,12 +512,10 @@ __device__ __forceinline__ void lut_unit_fused(const DevParams& P, const int col
         }
         add = c[LB - 1]; /* :268-272 */
     };
-#ifndef ISF_ABL_LUTF_EMPTY /* timing-only ablation: the units do nothing (the table of an earlier IS_LUT_FUSED=0 call is still there) */
     int i = 0;
 #pragma unroll 1
     for (; i + LB <= H; i += LB) block(i, true);
     if (i < H) block(i, false);
-#endif
     /* The unit's rows are visible before its count is: the stores have been acknowledged by the L2 (vmcnt(0)) that
      * the column's DP workgroups read through -- LUT block and DP workgroups of a column share their XCD (block ID mod
      * 8: OBSERVED placement, not a contract, so the unit publishes its XCC id and a reader that does not share it sets
@@ -680,18 +640,13 @@ next_item: /* (REPAIR: the next (column, tile) item of this workgroup) */
     const bool row_ok = vT < H;
     const int vB_end = min(tile_lo + IS_TILE - 1, H - 1);
     float* my_ring = s_ring + (size_t)w * K * SLOT;
-    ISF_MARK_INIT();
 
     /* ---- prologue: the wave's first K slots are requested first, then the tile's lutT rows,
      * the 1/h table and this lane's record.  The wave's steps: vB_top, vB_top - 8, ... >= 0
      * (H >= 8 = the number of waves, so vB_top >= 0). */
     /* QDIAG: the diagonal block in quarters (diag_quarters), the walk then starts below the tile */
-    const bool qd = ISF_QDIAG && WIN && nwv == 4 && (tile_lo >= vhor || tile_lo + IS_TILE - 1 <= vhor);
-#ifdef ISF_ABL_NODIAG /* timing-only ablation (wrong results): the walk without its diagonal block */
-    const int vB_top = tile_lo - w;
-#else
+    const bool qd = WIN && nwv == 4 && (tile_lo >= vhor || tile_lo + IS_TILE - 1 <= vhor);
     const int vB_top = (qd ? tile_lo : vB_end) - w; /* (qd: may be negative = no step for this wave) */
-#endif
     const WinLane wlane = win_lane(lcol, rcol, D, win_lo, lane);
 #pragma unroll
     for (int i = 0; i < K; i++)
@@ -700,7 +655,6 @@ next_item: /* (REPAIR: the next (column, tile) item of this workgroup) */
         if (WIN) ring_prefetch_win(wlane, vq, my_ring + i * SLOT);
         else ring_prefetch<NVR>(lcol, rcol, vq, D, my_ring + i * SLOT, my_ring + i * SLOT + ROWF, lane);
     }
-    ISF_MARK(4); /* (debug build: ring requests issued) */
     /* (qd: diag_quarters loads the record of the row this lane's quarter works for first -- requested here, in front
      * of the tile staging, it costs the kernel 43 spilled VGPRs --; the quarters 0 and 1 take their own rows'
      * records out of s_nat when they come back to them) */
@@ -719,7 +673,6 @@ next_item: /* (REPAIR: the next (column, tile) item of this workgroup) */
             *reinterpret_cast<float4*>(s_nat + row * ISF_NAT_STRIDE + 4 * ch) = x[k];
         }
     }
-    ISF_MARK(5); /* (debug build: record requested) */
     if (WIN) stage_window_and_rcp(s_tile, s_rcp, lcol, rcp, tile_lo, H, D, win_lo, tid, (int)blockDim.x);
     else stage_tile_and_rcp(s_tile, s_rcp, lcol, rcp, tile_lo, H, D, tid, (int)blockDim.x);
     int n_winmiss = 0;
@@ -728,7 +681,6 @@ next_item: /* (REPAIR: the next (column, tile) item of this workgroup) */
     fwin.gcol = lcol;
     fwin.misses = &n_winmiss;
     fwin.vT1 = min(vT + 1, H);
-    ISF_MARK(6); /* (debug build: tile + 1/h table staged; mark 0 then = the barrier) */
 
     PruneValsF pv;
     {
@@ -742,14 +694,12 @@ next_item: /* (REPAIR: the next (column, tile) item of this workgroup) */
     b.vg = b.vs = -1;
     b.vo = 0; /* index_table[vT*3+OBJECT] = OBJECT at vB = 0, :592 */
     const float* my_tile = s_tile + lane * DP;
-    const bool nog = IS_SKIP_GROUND_ABOVE_HORIZON && tile_lo >= vhor;
+    const bool nog = tile_lo >= vhor;
     __syncthreads(); /* the tile and the 1/h table: the only data the waves share */
-    ISF_MARK(0);
     if (WIN && qd) {
         if (tile_lo >= vhor) diag_quarters<HAS_INVALID, true>(P, my, b, lcol, s_tile, s_rcp, s_nat, tile_lo, w, win_lo, n_winmiss);
         else diag_quarters<HAS_INVALID, false>(P, my, b, lcol, s_tile, s_rcp, s_nat, tile_lo, w, win_lo, n_winmiss);
     }
-    ISF_MARK(7); /* (debug build: the diagonal quarters) */
     pv.gdead = pv.dead | __builtin_amdgcn_ballot_w64(my.G == IS_INF);
 
     /* ---- the wave's walk, vB downwards; slot i % K holds step i */
@@ -772,7 +722,7 @@ next_item: /* (REPAIR: the next (column, tile) item of this workgroup) */
         const bool diag = vB > tile_lo;
         bool done = false;
         int ok = 0;
-        if (ISF_GS_STEPS && o_closed && vB != 0) { /* (closed in a full step: the diagonal is over) */
+        if (o_closed && vB != 0) { /* (closed in a full step: the diagonal is over) */
             vB_gs = vB; /* the rest of the walk holds ground / sky candidates only: gs_walk, behind the loop */
             break;
         } else {
@@ -791,7 +741,7 @@ next_item: /* (REPAIR: the next (column, tile) item of this workgroup) */
             } else {
                 const SegTerms t = fast_step<HAS_INVALID, true, false, false, false, WIN>(
                     P, my, rb, lrow, my_tile, s_rcp, vT, vTc, vhor, vB, row_ok, b, S, fwin);
-                if (IS_PRUNE) ok = fast_bounds<true, false>(P, pv, t, b);
+                ok = fast_bounds<true, false>(P, pv, t, b);
             }
         } else { /* ground + object (:687) */
             if (diag) {
@@ -800,11 +750,11 @@ next_item: /* (REPAIR: the next (column, tile) item of this workgroup) */
             } else if (nog) {
                 const SegTerms t = fast_step<HAS_INVALID, false, false, false, true, WIN>(
                     P, my, rb, lrow, my_tile, s_rcp, vT, vTc, vhor, vB, row_ok, b, S, fwin);
-                if (IS_PRUNE) ok = fast_bounds<false, true>(P, pv, t, b);
+                ok = fast_bounds<false, true>(P, pv, t, b);
             } else {
                 const SegTerms t = fast_step<HAS_INVALID, false, false, false, false, WIN>(
                     P, my, rb, lrow, my_tile, s_rcp, vT, vTc, vhor, vB, row_ok, b, S, fwin);
-                if (IS_PRUNE) ok = fast_bounds<false, false>(P, pv, t, b);
+                ok = fast_bounds<false, false>(P, pv, t, b);
             }
         }
         done = ok == 3;
@@ -837,7 +787,6 @@ next_item: /* (REPAIR: the next (column, tile) item of this workgroup) */
         if (v > vhor) (void)gs_walk<true>(P, pv, my, rcol, s_rcp, vTc, v, max(vhor + 1, 1), nwv, b, n_gs, true);
         else if (!nog) (void)gs_walk<false>(P, pv, my, rcol, s_rcp, vTc, v, 0, nwv, b, n_gs, vT <= vhor);
     }
-    ISF_MARK(1);
     if (counters != nullptr && lane == 0) {
         atomicAdd(counters + IS_CNT_UNARY_FULL, (unsigned long long)n_full);
         atomicAdd(counters + IS_CNT_UNARY_GS, (unsigned long long)n_gs);
@@ -850,7 +799,6 @@ next_item: /* (REPAIR: the next (column, tile) item of this workgroup) */
      * has to wait for them until the very end: the drain hides behind the barrier and the merge
      * (it used to sit in front of them: an HBM latency per workgroup). */
     __syncthreads();
-    ISF_MARK(2);
     float* m_cost = s_tile;                              /* [8][3][64] */
     int* m_vb = (int*)(m_cost + nwv * 3 * 64);           /* [8][3][64] */
     float* f_cost = m_cost + 2 * nwv * 3 * 64;           /* [3][64] final values */
@@ -884,7 +832,6 @@ next_item: /* (REPAIR: the next (column, tile) item of this workgroup) */
         id[0] = f_vb[0 * 64 + lane]; id[1] = f_vb[1 * 64 + lane]; id[2] = f_vb[2 * 64 + lane];
     }
     wait_vmcnt<0>(); /* no LDS-DMA may land after the workgroup has gone (its LDS is reassigned) */
-    ISF_MARK(3);
     }
 item_done:
     if (REPAIR) {
@@ -911,7 +858,7 @@ static size_t isf_lds_bytes(const DevParams* P, int nvr, int nwaves, bool window
     const size_t rcp = ((size_t)P->H + 1 + 3) & ~(size_t)3;
     size_t tile = ((size_t)IS_TILE * DP + 3) & ~(size_t)3;
     size_t ring = (size_t)nwaves * ISF_RING * ((windowed ? (size_t)IS_P1_WIN : 64 * (size_t)nvr) + ISF_REC_F);
-    if (windowed && ISF_QDIAG) ring += ISF_NAT_F; /* the records of the rows 0 .. 31 (diag_quarters) */
+    if (windowed) ring += ISF_NAT_F; /* the records of the rows 0 .. 31 (diag_quarters) */
     const size_t merge = (size_t)nwaves * 3 * 64 * 2 + 2 * 3 * 64; /* lives in the tile's space */
     if (tile < merge) tile = merge;
     return sizeof(float) * (rcp + tile + ring) + 16;

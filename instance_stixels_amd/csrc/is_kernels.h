@@ -283,9 +283,6 @@ __device__ __forceinline__ void stage_rcp(float* s_rcp, const float* __restrict_
     }
 }
 
-#ifndef IS_STAGE_SPREAD
-#define IS_STAGE_SPREAD 1
-#endif
 /* The tile and the 1/h table behind ONE memory round trip: staged one after the other, the
  * second one's loads are only issued after the first one's vmcnt(0) wait (measured in the unary
  * ring kernel: 19 % + 15 % of a workgroup's life for the two).  Common shapes (16-byte path of
@@ -307,17 +304,12 @@ __device__ __forceinline__ void stage_tile_and_rcp(float* s_tile, float* s_rcp,
     float4 x[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) rc[k] = rcp[min(tid + k * nthreads, H)];
-#if IS_STAGE_SPREAD
     /* D = 128, 512 threads: a group of 8 lanes takes one 128-byte line, a wave 8 ROWS x 8 chunks, its four
      * loads the four quarters of those rows: the dword stores below then hit banks (row + 4 chunk + j)
      * mod 32 -- 8 rows x 8 chunks spread over all of them -- instead of one row's 32 chunks at a stride
      * of four dwords (4-way conflicts on every staging store) */
     const bool spread = quads == 32 && nthreads == 8 * IS_TILE;
     const int sr = (tid >> 6) * 8 + ((tid & 63) >> 3), sq = tid & 7;
-#else
-    const bool spread = false;
-    const int sr = 0, sq = 0;
-#endif
     const int r0 = tid / quads, f0 = (tid - r0 * quads) * 4;
     const int dr = nthreads / quads;
 #pragma unroll
@@ -618,9 +610,6 @@ __device__ __forceinline__ SegTerms eval_segment_dpp(const RowRec& my, float R0,
  * ahead and srec_arrived() before the step (one s_load_dwordx16 from the record's line in global
  * memory -- the ring's LDS-DMA has brought that line into the L2 steps before). */
 typedef float isk_f16v __attribute__((ext_vector_type(16)));
-#ifndef IS_MIX_PK
-#define IS_MIX_PK 1 /* the sixteen scalar-operand subtractions as eight v_pk_add_f32 (neg modifiers): -1.5 % */
-#endif
 __device__ __forceinline__ void srec_request(isk_f16v& S, const RowRec* grec) {
     asm volatile("s_load_dwordx16 %0, %1, 0x0" : "=s"(S) : "s"(grec));
 }
@@ -638,7 +627,7 @@ __device__ __forceinline__ SegTerms eval_segment_mix(const RowRec& my, const isk
     SegTerms t;
     const float nic = iw * (float)dpp_sub_i_first<3>(my.Fnic, R1);
     float f_g = 0.0f;
-#if IS_MIX_PK
+    /* the sixteen scalar-operand subtractions as eight v_pk_add_f32 (neg modifiers): -1.5 % */
     typedef float f2 __attribute__((ext_vector_type(2)));
 #define IS_PK_SUB(a0, a1, k) (f2{a0, a1} - f2{S[k], S[(k) + 1]})
     if (WANT & IS_WANT_GROUND) {
@@ -660,15 +649,6 @@ __device__ __forceinline__ SegTerms eval_segment_mix(const RowRec& my, const isk
         f_oi = __builtin_fminf(__builtin_fminf(f_oi, e2.x), e2.y);
     }
 #undef IS_PK_SUB
-#else
-    if (WANT & IS_WANT_GROUND) f_g = __builtin_fminf(my.Fg0 - S[0], my.Fg1 - S[1]);
-    float f_on = my.Fon[0] - S[2];
-#pragma unroll
-    for (int c = 1; c < IS_N_ON; c++) f_on = __builtin_fminf(f_on, my.Fon[c] - S[2 + c]);
-    float f_oi = my.Foi[0] - S[10];
-#pragma unroll
-    for (int c = 1; c < 6; c++) f_oi = __builtin_fminf(f_oi, my.Foi[c] - S[10 + c]);
-#endif
     {
         const float a6 = dpp_sub<0>(my.Foi[6], R1), a7 = dpp_sub<1>(my.Foi[7], R1);
         f_oi = min3_raw(f_oi, a6, a7);
@@ -751,14 +731,6 @@ __device__ __forceinline__ unsigned lds_addr(const float* p) {
     return __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(isf_lds_t)p);
 }
 
-__device__ __forceinline__ RowRec lds_rec(const float* p) {
-    RowRec r;
-    const float4* s = reinterpret_cast<const float4*>(p);
-    float4* d = reinterpret_cast<float4*>(&r);
-#pragma unroll
-    for (int i = 0; i < 8; i++) d[i] = s[i];
-    return r;
-}
 
 
 #endif /* IS_KERNELS_H_ */
