@@ -447,6 +447,12 @@ int is_debug_lut_fused_state(is_ctx* ctx, int* repaired);
  * to 1 or 2).  Synchronises the device. */
 int is_lut_fused_repairs(is_ctx* ctx, int* calls_repaired);
 
+/* Which unary DP the last unary is_compute call of this context ran: *path = 1 when it computed only the table rows
+ * the back-trace visits (k_unary_path; IS_UNARY_PATH), 0 when it ran the tile path (every row),
+ * -1 before the first unary call.  *repaired = the number of calls of this context whose path walk distrusted
+ * itself and whose repair launches redid the call on the tile path.  Synchronises the device. */
+int is_debug_unary_path(is_ctx* ctx, int* path, int* repaired);
+
 /* Test hook: the bound-block summaries the pairwise DP of the last is_compute call left for one stixel
  * column (lemmas L7 / L8): h_out[n_blocks][24], returns n_blocks through *n_blocks. */
 int is_debug_read_block_summaries(is_ctx* ctx, int column, float* h_out, int cap_floats, int* n_blocks);

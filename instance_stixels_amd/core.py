@@ -25,7 +25,7 @@ EXPORTS = [
     "is_ctx_device", "is_set_eval_counters", "is_get_eval_counters",
     "is_pack_sections", "is_unpack_sections", "is_stream_create", "is_stream_destroy",
     "is_debug_read_object_lut", "is_debug_read_block_summaries", "is_debug_lut_fused_state",
-    "is_lut_fused_repairs",
+    "is_lut_fused_repairs", "is_debug_unary_path",
     "is_comm_unique_id", "is_comm_init_rank", "is_comm_destroy", "is_comm_rank", "is_gather_i32",
     "is_gather_sections",
     "is_road_ctx_create", "is_road_ctx_destroy", "is_road_ctx_device", "is_road_ctx_binary",
@@ -136,6 +136,7 @@ def lib():
         L.is_debug_read_object_lut.argtypes = [vp, ci, vp]
         L.is_debug_lut_fused_state.argtypes = [vp, ctypes.POINTER(ci)]
         L.is_lut_fused_repairs.argtypes = [vp, ctypes.POINTER(ci)]
+        L.is_debug_unary_path.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]
         try:   # (an experiment library built from an older tree may lack the newest test hook)
             L.is_debug_read_block_summaries.argtypes = [vp, ci, vp, ci, ctypes.POINTER(ci)]
         except AttributeError:
@@ -207,6 +208,14 @@ class Core:
         out = ctypes.c_int(-1)
         _check(lib().is_debug_lut_fused_state(self._ctx, ctypes.byref(out)), "is_debug_lut_fused_state")
         return int(out.value)
+
+    def unary_path(self):
+        """(path, repaired): path = 1 when the last unary call computed only the rows the back-trace visits
+        (k_unary_path), 0 for the tile path, -1 before any unary call; repaired = calls of this context whose
+        path walk was distrusted and redone on the tile path (test hook, see instance_stixels_core.h)."""
+        path, rep = ctypes.c_int(-1), ctypes.c_int(-1)
+        _check(lib().is_debug_unary_path(self._ctx, ctypes.byref(path), ctypes.byref(rep)), "is_debug_unary_path")
+        return int(path.value), int(rep.value)
 
     def lut_fused_repairs(self):
         """Calls of this context whose fused LUT hand-over was distrusted and repaired (sticky count)."""

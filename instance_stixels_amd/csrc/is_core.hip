@@ -36,7 +36,9 @@ hipError_t isk_launch_dp_pairwise(const DevParams*, int, int, const RowRec*, con
                                   float*, int32_t*, unsigned long long*, const float*, const int*, float*, float*,
                                   hipStream_t, hipStream_t*, int, hipEvent_t, hipEvent_t*);
 hipError_t isk_launch_backtrace(const DevParams*, int, int, const RowRec*, const float*,
-                                const int32_t*, const int*, is_section*, int*, int*, hipStream_t);
+                                const int32_t*, const int*, is_section*, int*, int*, int*, hipStream_t);
+hipError_t isk_launch_dp_unary_path(const DevParams*, int, int, const RowRec*, const float*, const float*, const int*,
+                                    const int*, const PruneRec*, float*, int32_t*, const int*, int*, int, hipStream_t);
 hipError_t isk_launch_compact(const DevParams*, int, const is_section*, const int*,
                               const is_instance_buffers*, hipStream_t);
 hipError_t isk_set_lds_prepare(const DevParams*);
@@ -105,6 +107,8 @@ struct is_ctx {
     int* d_col_flags;        /* [max_batch*C] 0 = FAST column, see RowRec */
     PruneRec* d_prune;       /* [max_batch*C] branch-and-bound slacks of the column */
     int* d_n_generic;        /* [1] generic-encoding columns of the current call */
+    int* d_path_bad;         /* [2] k_unary_path's distrust word of the current call, calls repaired (k_backtrace) */
+    int last_unary_path = -1; /* the unary DP of the last unary call: 1 = k_unary_path, 0 = tile path */
     /* per-call device inputs */
     /* one block [ground: max_batch x 3 x H floats][instance table: max_batch][vhor: max_batch ints], on
      * the device and in every pinned staging slot: a full batch (the host class's single frame
@@ -303,6 +307,8 @@ static int ctx_init(is_ctx* c, const is_stixel_params* p, const float* obj_cost_
         d.knob_p2x = knob("IS_P2X");
         d.knob_win_tiles = knob("IS_P1_WIN_TILES");
         d.knob_lut_fused = knob("IS_LUT_FUSED"); /* the LUT units inside the unary DP launch (is_k_unary_fast.hip, LUTF) */
+        d.knob_unary_path = knob("IS_UNARY_PATH"); /* the unary DP of the visited rows only (is_device.h) */
+        c->last_unary_path = -1;
     }
     {
         /* branch-and-bound constants (PruneRec, is_device.h).  gamma_d bounds the relative error of
@@ -351,6 +357,8 @@ static int ctx_init(is_ctx* c, const is_stixel_params* p, const float* obj_cost_
     ALLOC(c->d_prune, sizeof(PruneRec) * B * C);
     ALLOC(c->d_n_generic, sizeof(int));
     HIP_TRY(hipMemset(c->d_n_generic, 0, sizeof(int))); /* later calls: k_backtrace clears it */
+    ALLOC(c->d_path_bad, 2 * sizeof(int));
+    HIP_TRY(hipMemset(c->d_path_bad, 0, 2 * sizeof(int))); /* [0]: k_backtrace clears it */
     c->stage_off_inst = sizeof(float) * B * 3 * H; /* (H is a multiple of 8: 8-byte aligned) */
     c->stage_off_vhor = c->stage_off_inst + sizeof(is_instance_buffers) * B;
     c->stage_bytes = c->stage_off_vhor + sizeof(int) * B;
@@ -442,7 +450,7 @@ int is_ctx_destroy(is_ctx* c) {
     DeviceScope scope(c->device);
     (void)hipDeviceSynchronize();
     (void)hipFree(c->d_obj_cost_lut); (void)hipFree(c->d_odr); (void)hipFree(c->d_rcp); (void)hipFree(c->d_col_flags); (void)hipFree(c->d_prune); (void)hipFree(c->d_n_generic); (void)hipFree(c->d_stage);
-    (void)hipFree(c->d_recs); (void)hipFree(c->d_lutT); (void)hipFree(c->d_priors); (void)hipFree(c->d_steps); (void)hipFree(c->d_part_cost); (void)hipFree(c->d_part_idx); (void)hipFree(c->d_sv); (void)hipFree(c->d_blksum); (void)hipFree(c->d_t8row); (void)hipFree(c->dp.win_lo); (void)hipFree(c->dp.lut_ready); (void)hipFree(c->dp.lutf_bad);
+    (void)hipFree(c->d_recs); (void)hipFree(c->d_lutT); (void)hipFree(c->d_priors); (void)hipFree(c->d_steps); (void)hipFree(c->d_part_cost); (void)hipFree(c->d_part_idx); (void)hipFree(c->d_sv); (void)hipFree(c->d_blksum); (void)hipFree(c->d_t8row); (void)hipFree(c->dp.win_lo); (void)hipFree(c->dp.lut_ready); (void)hipFree(c->dp.lutf_bad); (void)hipFree(c->d_path_bad);
     if (c->h_lutf_repairs) (void)hipHostFree(c->h_lutf_repairs);
     (void)hipFree(c->d_cost_table); (void)hipFree(c->d_index_table); (void)hipFree(c->d_cluster_scratch);
     (void)hipFree(c->d_inst_cnt); (void)hipFree(c->d_counters);
@@ -777,6 +785,17 @@ int is_lut_fused_repairs(is_ctx* c, int* calls_repaired) {
     return IS_OK;
 }
 
+int is_debug_unary_path(is_ctx* c, int* path, int* repaired) {
+    if (!c || !path || !repaired) return fail_arg("null pointer");
+    ON_CTX_DEVICE(c);
+    HIP_TRY(hipDeviceSynchronize());
+    int w[2] = {0, 0};
+    HIP_TRY(hipMemcpy(w, c->d_path_bad, sizeof(w), hipMemcpyDeviceToHost));
+    *path = c->last_unary_path;
+    *repaired = w[1];
+    return IS_OK;
+}
+
 int is_debug_read_block_summaries(is_ctx* c, int column, float* h_out, int cap_floats, int* n_blocks) {
     if (!c || !h_out || !n_blocks) return fail_arg("null pointer");
     if (column < 0 || column >= c->max_batch * c->dp.C) return fail_arg("column outside the context's scratch");
@@ -868,6 +887,18 @@ static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_se
     /* a hand-over of this context has been distrusted before (another dispatcher, a partition mode, a CU mask): the
      * fused launch stays off unless IS_LUT_FUSED asks for it by value -- a repaired call costs 2.8 x an ordinary one */
     if (Pw.lut_fused && (P.knob_lut_fused < 0 || P.knob_lut_fused == 3) && c->h_lutf_repairs && *(volatile int*)c->h_lutf_repairs > 0) Pw.lut_fused = 0;
+    /* the unary DP of the visited rows only (k_unary_path; rules: is_device.h, IS_UNARY_PATH_MIN_COLS) */
+    bool path = false;
+    if (!pairwise && !c->counting && P.knob_unary_path != 0) {
+        const bool tables = d_cost_table != nullptr || d_index_table != nullptr;
+        if (P.knob_unary_path >= 2)
+            path = true;
+        else
+            path = !tables && P.knob_lut_fused != 2 && P.knob_lut_fused != 3 && P.sigma_od < IS_FLT_HUGE &&
+                   (P.knob_unary_path == 1 || ncols >= IS_UNARY_PATH_MIN_COLS);
+    }
+    if (path) Pw.lut_fused = 0; /* the walk reads the complete object table of the prepare launch */
+    if (!pairwise) c->last_unary_path = path ? 1 : 0;
     if (timing) HIP_TRY(hipEventRecord(c->ev[0], stream));
     /* (d_n_generic is zero here: cleared at creation and by k_backtrace at the end of every call) */
     HIP_TRY(isk_launch_prepare(&Pw, ncols, d_joined, d_seg, c->d_ground, c->d_vhor,
@@ -882,6 +913,10 @@ static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_se
                                        c->d_part_idx, ct, it, c->counting ? c->d_counters : nullptr,
                                        c->d_obj_cost_lut, c->d_n_generic, c->d_blksum, c->d_t8row, stream, c->aux_streams,
                                        IS_AUX_STREAMS, c->ev_fork, c->ev_joins));
+    else if (path)
+        HIP_TRY(isk_launch_dp_unary_path(&Pw, ncols, c->nwaves_unary, c->d_recs, c->d_lutT, c->d_rcp, c->d_vhor,
+                                         c->d_col_flags, c->d_prune, ct, it, c->d_n_generic, c->d_path_bad,
+                                         P.knob_unary_path == 3 ? 1 : 0, stream));
     else
         HIP_TRY(isk_launch_dp_unary(&Pw, ncols, c->nwaves_unary, c->d_recs, c->d_lutT, c->d_rcp,
                                     c->d_vhor, c->d_col_flags, c->d_prune, ct, it, c->d_n_generic,
@@ -889,7 +924,8 @@ static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_se
                                     stream));
     if (timing) HIP_TRY(hipEventRecord(c->ev[2], stream));
     HIP_TRY(isk_launch_backtrace(&P, ncols, pairwise ? 1 : 0, c->d_recs, ct, it, c->d_col_flags,
-                                 d_sections, want_inst ? c->d_inst_cnt : nullptr, c->d_n_generic, stream));
+                                 d_sections, want_inst ? c->d_inst_cnt : nullptr, c->d_n_generic, c->d_path_bad,
+                                 stream));
     if (want_inst) {
         /* the instance candidates (StixelsKernels.cu:926-942) and their clustering
          * (Stixels::ClusterInstances, Stixels.cu:613) of the WHOLE batch: two launches */
@@ -946,6 +982,9 @@ int is_compute(is_ctx* c, const float* d_joined, const int32_t* d_seg, const flo
     /* Invariant the early-outs of k_dp_unary / k_pw_phase2_generic rely on: d_n_generic is zero
      * between calls (k_prepare counts the generic columns of a call, block 0 of k_backtrace clears
      * the counter at its end).  A call that failed half way may have counted without clearing. */
-    if (rc != IS_OK) (void)hipMemsetAsync(c->d_n_generic, 0, sizeof(int), stream);
+    if (rc != IS_OK) {
+        (void)hipMemsetAsync(c->d_n_generic, 0, sizeof(int), stream);
+        (void)hipMemsetAsync(c->d_path_bad, 0, sizeof(int), stream);
+    }
     return rc;
 }

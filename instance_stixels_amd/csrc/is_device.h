@@ -191,7 +191,24 @@ struct DevParams {
                          * 3 = (tests) the default policy (-1) with the wrong id of 2: the first large call is repaired, and the
                          * context then keeps the table in the prepare launch (DevParams::lutf_repairs) */
     int lut_fused;      /* set per call: 0, 1, or 2 (the test mode) */
+    int knob_unary_path; /* IS_UNARY_PATH, see IS_UNARY_PATH_MIN_COLS */
 };
+
+/* The unary DP along the back-trace's path (k_unary_path, is_k_unary_path.hip): a unary call computes only the
+ * table rows k_backtrace visits instead of every row, and repair launches redo the call on the tile path when a
+ * walk meets what it cannot vouch for.  IS_UNARY_PATH (read once in is_ctx_create):
+ *   -1 / unset  automatic: unary calls that request no tables (d_cost_table / d_index_table null), with the
+ *               evaluation counters off (they instrument the tile kernels), IS_LUT_FUSED not 2 / 3 (those test the
+ *               fused hand-over), pruning on (IS_NO_PRUNE unset, finite weights and object costs: an unpruned
+ *               walk is slower than the tile path, measured 2345 against 3040 frames/s) and at least
+ *               IS_UNARY_PATH_MIN_COLS columns;
+ *    0          never;
+ *    1          the same rules at any number of columns;
+ *    2          (tests) also when tables are requested: only the visited rows of the caller's tables are written;
+ *    3          (tests) as 2, and every call distrusts itself: the repair launches run. */
+#ifndef IS_UNARY_PATH_MIN_COLS
+#define IS_UNARY_PATH_MIN_COLS 2048
+#endif
 
 /* fn windows (k_dp_unary_fast, k_pw_phase1).  A (column, tile) workgroup keeps lutT[vT + 1][*] of its 64 rows in
  * LDS: D + 1 floats per row, 33 KB at D = 128 -- which is what limited a CU to three workgroups.  A lane only

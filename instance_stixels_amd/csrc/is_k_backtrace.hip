@@ -86,7 +86,8 @@ __global__ __launch_bounds__(64) void k_backtrace(const DevParams P, int ncols, 
                                                   const int* __restrict__ col_flags,
                                                   is_section* __restrict__ sections,
                                                   int* __restrict__ inst_cnt /* [ncols][8] or null */,
-                                                  int* __restrict__ n_generic /* reset for the next call */) {
+                                                  int* __restrict__ n_generic /* reset for the next call */,
+                                                  int* __restrict__ path_bad /* [2] or null, see below */) {
     static_assert(!(STAGE && TWO), "the staged variant is for small calls: one column per wave");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x;
@@ -100,6 +101,12 @@ __global__ __launch_bounds__(64) void k_backtrace(const DevParams P, int ncols, 
      * this call have read it: they precede this launch in stream order) goes back to zero here --
      * a memset node per call costs a single frame ten microseconds of queue time */
     if (blockIdx.x == 0 && lane == 0) *n_generic = 0;
+    /* likewise the distrust word of k_unary_path (its repair launches precede this one): a call it was set in
+     * counts in path_bad[1] (is_debug_unary_path) */
+    if (path_bad && blockIdx.x == 0 && lane == 0 && path_bad[0] != 0) {
+        path_bad[1] += 1;
+        path_bad[0] = 0;
+    }
     const int H = P.H, S = P.S;
     int* s_cut = (int*)smem + half * (3 * S + 8); /* [S][3]: vT, vB, type */
     int* s_n = s_cut + 3 * S;                     /* [1] */
@@ -286,18 +293,18 @@ extern "C" {
 hipError_t isk_launch_backtrace(const DevParams* P, int ncols, int pairwise, const RowRec* recs,
                                 const float* cost_table, const int32_t* index_table,
                                 const int* col_flags, is_section* sections, int* inst_cnt,
-                                int* n_generic, hipStream_t stream) {
+                                int* n_generic, int* path_bad, hipStream_t stream) {
     const size_t lds = sizeof(int) * (3 * (size_t)P->S + 8);
     const size_t lds_staged = lds + sizeof(int) * 6 * (size_t)P->H;
     if (ncols <= IS_BACKTRACE_STAGE_MAX_COLS && lds_staged <= 64 * 1024)
         hipLaunchKernelGGL(k_backtrace<true>, dim3(ncols), dim3(64), lds_staged, stream, *P, ncols, pairwise,
-                           recs, cost_table, index_table, col_flags, sections, inst_cnt, n_generic);
+                           recs, cost_table, index_table, col_flags, sections, inst_cnt, n_generic, path_bad);
     else if (ncols >= IS_BACKTRACE_TWO_MIN_COLS)
         hipLaunchKernelGGL((k_backtrace<false, true>), dim3((ncols + 1) / 2), dim3(64), 2 * lds, stream, *P, ncols,
-                           pairwise, recs, cost_table, index_table, col_flags, sections, inst_cnt, n_generic);
+                           pairwise, recs, cost_table, index_table, col_flags, sections, inst_cnt, n_generic, path_bad);
     else
         hipLaunchKernelGGL(k_backtrace<false>, dim3(ncols), dim3(64), lds, stream, *P, ncols, pairwise, recs,
-                           cost_table, index_table, col_flags, sections, inst_cnt, n_generic);
+                           cost_table, index_table, col_flags, sections, inst_cnt, n_generic, path_bad);
     return hipGetLastError();
 }
 

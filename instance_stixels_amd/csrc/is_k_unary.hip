@@ -291,7 +291,9 @@ __device__ __forceinline__ void unary_loop_desc(const DevParams& P, const RowRec
 /* FASTCOLS: the launch handles only the columns of that encoding (col_flags), workgroups of the
  * other kind leave at once.  Two lean kernels instead of one that carries both loop nests: no
  * register spills, and the generic launch costs ~nothing when every column is FAST. */
-template <bool HAS_INVALID, int NR, bool FASTCOLS>
+/* GATED (FASTCOLS only): the repair launch behind k_unary_path (is_k_unary_path.hip), which leaves at once while
+ * the word `n_generic` points to -- the path's distrust word then -- is 0, like the generic launch. */
+template <bool HAS_INVALID, int NR, bool FASTCOLS, bool GATED = false>
 __global__ __launch_bounds__(IS_UNARY_WAVES * 64, IS_UNARY_OCC) void k_dp_unary(const DevParams P, int ncols,
                                                   const RowRec* __restrict__ recs,
                                                   const float* __restrict__ lutT,
@@ -318,7 +320,7 @@ __global__ __launch_bounds__(IS_UNARY_WAVES * 64, IS_UNARY_OCC) void k_dp_unary(
      * and leaves at once when the batch has no generic column (k_prepare_columns counts them):
      * a full grid of workgroups that each only read their column's flag cost 0.13 ms per 64
      * frames in dispatch alone. */
-    if (!FASTCOLS && __builtin_amdgcn_readfirstlane(*n_generic) == 0) return;
+    if ((!FASTCOLS || GATED) && __builtin_amdgcn_readfirstlane(*n_generic) == 0) return;
     const int n_items = ((ncols + nxcd - 1) / nxcd) * nxcd * wg_per_col;
     for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
     __syncthreads(); /* the previous item's merge area aliases this item's LUT tile */
@@ -412,6 +414,9 @@ __global__ __launch_bounds__(IS_UNARY_WAVES * 64, IS_UNARY_OCC) void k_dp_unary(
     } /* item */
 }
 
+extern "C" hipError_t isk_launch_unary_path(const DevParams*, int, const RowRec*, const float*, const float*,
+                                            const int*, const int*, const PruneRec*, float*, int32_t*, int*, int,
+                                            hipStream_t);
 extern "C" hipError_t isk_launch_dp_unary_fast(const DevParams*, int, const RowRec*, const float*,
                                                const float*, const int*, const int*, const PruneRec*,
                                                float*, int32_t*, unsigned long long*, const float*,
@@ -473,6 +478,39 @@ hipError_t isk_launch_dp_unary(const DevParams* P, int ncols, int nwaves, const 
     return hipGetLastError();
 }
 
+/* The unary DP of a call that takes the path walk (is_k_unary_path.hip): the visited rows of the FAST columns, then
+ * the generic columns in full (leaves at once when the call has none), then the repair: the tile-path DP of every
+ * FAST column again, leaving at once while k_unary_path has not set *bad.  lutT is complete (the prepare launch). */
+hipError_t isk_launch_dp_unary_path(const DevParams* P, int ncols, int nwaves, const RowRec* recs, const float* lutT,
+                                    const float* rcp, const int* vhor, const int* col_flags, const PruneRec* prune,
+                                    float* cost_table, int32_t* index_table, const int* n_generic, int* bad,
+                                    int force_bad, hipStream_t stream) {
+    const hipError_t e = isk_launch_unary_path(P, ncols, recs, lutT, rcp, vhor, col_flags, prune, cost_table,
+                                               index_table, bad, force_bad, stream);
+    if (e != hipSuccess) return e;
+    const int npairs = (P->ntiles + 1) / 2;
+    const unsigned items = (unsigned)((ncols + 7) / 8) * 8u * (unsigned)npairs;
+    const dim3 grid_generic(items < 16384u ? items : 16384u);
+    const dim3 grid_repair(items < 2048u ? items : 2048u); /* (walks the items: a safety net, not a fast path) */
+    const size_t lds = isk_unary_lds_bytes(P);
+#define IS_LAUNCH_UNARY_PATH(INV, NR)                                                              \
+    do {                                                                                           \
+        hipLaunchKernelGGL((k_dp_unary<INV, NR, false>), grid_generic, dim3(nwaves * 64), lds,     \
+                           stream, *P, ncols, recs, lutT, rcp, vhor, col_flags, prune, cost_table, \
+                           index_table, n_generic, 1);                                             \
+        hipLaunchKernelGGL((k_dp_unary<INV, NR, true, true>), grid_repair, dim3(nwaves * 64), lds, \
+                           stream, *P, ncols, recs, lutT, rcp, vhor, col_flags, prune, cost_table, \
+                           index_table, bad, 1);                                                   \
+    } while (0)
+    if (P->D <= 128) {
+        if (P->invalid >= 0) IS_LAUNCH_UNARY_PATH(true, 2); else IS_LAUNCH_UNARY_PATH(false, 2);
+    } else {
+        if (P->invalid >= 0) IS_LAUNCH_UNARY_PATH(true, 0); else IS_LAUNCH_UNARY_PATH(false, 0);
+    }
+#undef IS_LAUNCH_UNARY_PATH
+    return hipGetLastError();
+}
+
 int isk_debug_occupancy(const DevParams* P, int nwaves) {
     int nb = -1;
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_dp_unary<false, 2, true>,
@@ -492,6 +530,13 @@ hipError_t isk_set_lds_unary(const DevParams* P) {
     IS_SET_UNARY_LDS(true, 0, true); IS_SET_UNARY_LDS(true, 0, false);
     IS_SET_UNARY_LDS(false, 0, true); IS_SET_UNARY_LDS(false, 0, false);
 #undef IS_SET_UNARY_LDS
+#define IS_SET_UNARY_LDS_GATED(INV, NR)                                                           \
+    e = hipFuncSetAttribute((const void*)k_dp_unary<INV, NR, true, true>,                         \
+                            hipFuncAttributeMaxDynamicSharedMemorySize, b);                       \
+    if (e != hipSuccess) return e
+    IS_SET_UNARY_LDS_GATED(true, 2); IS_SET_UNARY_LDS_GATED(false, 2);
+    IS_SET_UNARY_LDS_GATED(true, 0); IS_SET_UNARY_LDS_GATED(false, 0);
+#undef IS_SET_UNARY_LDS_GATED
     return isk_set_lds_unary_fast(P);
 }
 

@@ -1,0 +1,206 @@
+/* is_k_unary_path.hip -- the unary DP along the back-trace's own path.  See is_kernels.h. */
+#include "is_kernels.h"
+
+/* ====================================================================================== */
+/* Unary DP of the visited rows only: one wave per column                                  */
+/* ====================================================================================== */
+/* In unary mode the predecessor cost is never added, so row vT of the tables (min / arg-min over vB of one
+ * segment's cost, per type) depends on no other row, and k_backtrace reads only the rows on its path: row
+ * H - 1, then row vB - 1 of every Section it emits.  This kernel walks that path itself: it computes a row
+ * completely, picks the type with k_backtrace's rules, takes vB from the index of that type and goes on at
+ * vT = vB - 1.  It writes the three (cost, index) pairs of every visited row at their usual addresses and
+ * leaves every other row alone; the unchanged k_backtrace behind it then reads exactly those rows.
+ *
+ * A row: the lanes are 64 consecutive candidates vB = 64 s + 1 + lane, walked downwards in s, then the first
+ * segment vB = 0 in lane 0.  Each candidate is the tile path's evaluation (eval_segment with my = record vT + 1,
+ * rb = record vB, the cost assembly of unary_step) with the per-lane cases of the tile kernels: SKY when
+ * vB - 1 >= vhor, otherwise GROUND; FIRST (vB = 0): ground only when vT <= vhor.  A lane's candidates descend,
+ * so it keeps the LAST of equal costs (<=, take_if_le's rule); the lanes merge with the tile path's merge
+ * (min cost, ties -> smallest vB, +inf -> the initial index).  NaN candidates never pass <=.
+ *
+ * Pruning (lemma L5): the class-group minima f_* of the LONGEST segment of a step (lane 0,
+ * vB = 64 s + 1) bound the cost of every candidate vB' <= vB of the row, per type.  A type whose bound exceeds
+ * the row's best so far (some lane's best < lb) closes for the rest of the row; the row ends when every type
+ * that can still receive candidates is closed.  A column whose E1o is +inf (IS_NO_PRUNE, non-finite
+ * weights) is walked in full.
+ *
+ * What the kernel cannot reproduce it does not try to: a chosen index outside [0, vT] (every candidate of
+ * the type +inf or NaN) sets *bad, and the repair launches behind this one redo the whole call on the tile
+ * path.  Generic-encoding columns (col_flags != 0) are left to k_dp_unary<.., false>, as on the tile path. */
+struct PathBest {
+    float c[3];
+    int v[3];
+};
+
+/* the merge of the tile kernels (k_dp_unary, k_dp_unary_fast): min cost, ties -> the smallest recorded vB */
+__device__ __forceinline__ void path_take(float& c, int& v, float c2, int v2) {
+    const bool take = (c2 < c) || (c2 == c && v2 >= 0 && (v < 0 || v2 < v));
+    c = take ? c2 : c;
+    v = take ? v2 : v;
+}
+
+template <bool HAS_INVALID>
+__device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* __restrict__ rcol,
+                                             const float* __restrict__ lcol, const float* __restrict__ rcp,
+                                             const PruneRec& pr, int vT, int vhor, int lane) {
+    const int D = P.D;
+    const RowRec my = load_rec(rcol + vT + 1); /* (in VGPRs: the scalar form spills SGPRs) */
+    const float* __restrict__ lrowT = lcol + (size_t)(vT + 1) * D;
+    float bg = IS_INF, bo = IS_INF, bs = IS_INF;
+    int vg = -1, vo = -1, vs = -1;
+    const bool prune_on = pr.E1o < IS_INF;
+    bool open_o = true, open_s = true;
+    /* ground data cost +inf from this row on (at / above the horizon): no ground candidate can win */
+    bool open_g = !(my.G == IS_INF);
+    for (int s = (vT - 1) >> 6; s >= 0; s--) { /* (vT = 0: no candidate vB >= 1) */
+        const int vB = 64 * s + 1 + lane;
+        const bool live = vB <= vT;
+        const int vBc = live ? vB : vT;
+        const RowRec rb = load_rec(rcol + vBc);
+        const int h = vT + 1 - vBc;
+        const float r = rcp[h]; /* RN(1/h) */
+        const SegTerms t = eval_segment<true, HAS_INVALID>(my, rb, (float)h, r, D, P.iw, rcp);
+        const float pwih = P.pw * r;
+        /* cost = dw*data + pw*(1/h) + sw*seg, left to right (unary_step) */
+        if (open_o) {
+            const float od = lrowT[t.fni] - lcol[(size_t)vBc * D + t.fni];
+            const float cost_o = P.dw * od + pwih + P.sw * t.seg_o;
+            if (live && cost_o <= bo) { bo = cost_o; vo = vB; }
+        }
+        if (vB - 1 >= vhor) {
+            const float cost_s = P.dw * t.sd + pwih + P.sw * t.seg_s;
+            if (open_s && live && cost_s <= bs) { bs = cost_s; vs = vB; }
+        } else {
+            const float cost_g = P.dw * t.gd + pwih + P.sw * t.seg_g;
+            if (open_g && live && cost_g <= bg) { bg = cost_g; vg = vB; }
+        }
+        if (prune_on) {
+            /* the longest segment of the step: lane 0 (vB = 64 s + 1 <= vT) */
+            const float f_on = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.f_on)));
+            const float f_oi = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.f_oi)));
+            const float f_sky = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.f_sky)));
+            const float f_g = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.f_g)));
+            const float lb_o = P.sw * __builtin_fminf(f_on, f_oi - pr.E2) - pr.E1o;
+            const float lb_s = P.sw * f_sky - pr.E1s;
+            const float lb_g = P.sw * f_g - pr.E1g;
+            /* lb > (the row's best) <=> some lane's best is below lb (a best is never NaN) */
+            if (__builtin_amdgcn_ballot_w64(lb_o > bo) != 0ull) open_o = false;
+            if (__builtin_amdgcn_ballot_w64(lb_s > bs) != 0ull) open_s = false;
+            if (__builtin_amdgcn_ballot_w64(lb_g > bg) != 0ull) open_g = false;
+            /* candidates left: vB' <= 64 s; sky ones need vB' - 1 >= vhor */
+            const bool sky_left = 64 * s - 1 >= vhor;
+            if (!open_o && !open_g && (!open_s || !sky_left)) break;
+        }
+        if (s == 0) { /* first segment vB = 0 (:481-594): ground + object, lane 0 */
+            if (open_o || open_g) {
+                const RowRec rb0 = load_rec(rcol);
+                const int h0 = vT + 1;
+                const float r0 = rcp[h0];
+                const SegTerms t0 = eval_segment<true, HAS_INVALID>(my, rb0, (float)h0, r0, D, P.iw, rcp);
+                const float pwih0 = P.pw * r0;
+                if (open_o) {
+                    const float od = lrowT[t0.fni] - lcol[t0.fni];
+                    const float cost_o = P.dw * od + pwih0 + P.sw * t0.seg_o;
+                    if (lane == 0 && cost_o <= bo) { bo = cost_o; vo = 0; }
+                }
+                if (open_g) {
+                    const float cost_g = P.dw * t0.gd + pwih0 + P.sw * t0.seg_g;
+                    if (lane == 0 && vT <= vhor && cost_g <= bg) { bg = cost_g; vg = 0; }
+                }
+            }
+        }
+    }
+    if (vT == 0) { /* the first segment is the only candidate */
+        const RowRec rb0 = load_rec(rcol);
+        const float r0 = rcp[1];
+        const SegTerms t0 = eval_segment<true, HAS_INVALID>(my, rb0, 1.0f, r0, D, P.iw, rcp);
+        const float pwih0 = P.pw * r0;
+        const float od = lrowT[t0.fni] - lcol[t0.fni];
+        const float cost_o = P.dw * od + pwih0 + P.sw * t0.seg_o;
+        if (lane == 0 && cost_o <= bo) { bo = cost_o; vo = 0; }
+        const float cost_g = P.dw * t0.gd + pwih0 + P.sw * t0.seg_g;
+        if (open_g && lane == 0 && vT <= vhor && cost_g <= bg) { bg = cost_g; vg = 0; }
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        path_take(bg, vg, __shfl_xor(bg, m), __shfl_xor(vg, m));
+        path_take(bo, vo, __shfl_xor(bo, m), __shfl_xor(vo, m));
+        path_take(bs, vs, __shfl_xor(bs, m), __shfl_xor(vs, m));
+    }
+    PathBest b;
+    b.c[IS_GROUND] = bg; b.c[IS_OBJECT] = bo; b.c[IS_SKY] = bs;
+    /* a type without a finite candidate keeps the initial index (:592 for the object type) */
+    b.v[IS_GROUND] = (bg < IS_INF) ? vg : -1;
+    b.v[IS_OBJECT] = (bo < IS_INF) ? vo : 0;
+    b.v[IS_SKY] = (bs < IS_INF) ? vs : -1;
+    return b;
+}
+
+template <bool HAS_INVALID>
+__global__ __launch_bounds__(64) void k_unary_path(const DevParams P, int ncols, const RowRec* __restrict__ recs,
+                                                   const float* __restrict__ lutT, const float* __restrict__ rcp,
+                                                   const int* __restrict__ vhor_arr, const int* __restrict__ col_flags,
+                                                   const PruneRec* __restrict__ prune, float* __restrict__ cost_table,
+                                                   int32_t* __restrict__ index_table, int* __restrict__ bad,
+                                                   int force_bad) {
+    const int colg = (int)blockIdx.x, lane = (int)threadIdx.x;
+    if (force_bad && colg == 0 && lane == 0) /* (IS_UNARY_PATH=3, tests: distrust every call) */
+        __hip_atomic_fetch_or(bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (colg >= ncols) return;
+    if (__builtin_amdgcn_readfirstlane(col_flags[colg]) != 0) return; /* generic encoding: k_dp_unary */
+    const int H = P.H, S = P.S;
+    const int vhor = __builtin_amdgcn_readfirstlane(vhor_arr[colg / P.C]);
+    const RowRec* rcol = recs + (size_t)colg * (H + 1);
+    const float* lcol = lutT + (size_t)colg * (H + 1) * P.D;
+    float* ct = cost_table + (size_t)colg * H * 3;
+    int32_t* it = index_table + (size_t)colg * H * 3;
+    PruneRec pr;
+    {
+        cprune_t q = (cprune_t)(prune + colg);
+        pr.E1o = q->E1o; pr.E1g = q->E1g; pr.E1s = q->E1s; pr.E2 = q->E2;
+    }
+    /* k_backtrace's walk (is_k_backtrace.hip): the type of the last row, then per Section the arg-min of row
+     * vB - 1 with its tie rules; at most S - 1 Sections, and the row vB - 1 of the last one is still read */
+    int vT = H - 1, n = 0, type = IS_OBJECT;
+    bool last = false;
+    for (;;) {
+        const PathBest b = path_row<HAS_INVALID>(P, rcol, lcol, rcp, pr, vT, vhor, lane);
+        if (lane == 0) {
+            ct[vT * 3 + 0] = b.c[0]; ct[vT * 3 + 1] = b.c[1]; ct[vT * 3 + 2] = b.c[2];
+            it[vT * 3 + 0] = b.v[0]; it[vT * 3 + 1] = b.v[1]; it[vT * 3 + 2] = b.v[2];
+        }
+        if (last) break;
+        const float cG = b.c[IS_GROUND], cO = b.c[IS_OBJECT], cS = b.c[IS_SKY];
+        int t = IS_OBJECT;
+        if (cG < cO) t = IS_GROUND;
+        if ((n == 0 || type == IS_OBJECT) && cS < __builtin_fminf(cG, cO)) t = IS_SKY;
+        type = t;
+        const int raw = type == IS_GROUND ? b.v[IS_GROUND] : (type == IS_OBJECT ? b.v[IS_OBJECT] : b.v[IS_SKY]);
+        const int vB = __builtin_amdgcn_readfirstlane(raw);
+        if (vB < 0 || vB > vT) { /* the back-trace would leave the rows this walk can vouch for */
+            if (lane == 0) __hip_atomic_fetch_or(bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            break;
+        }
+        n++;
+        if (vB == 0) break;
+        vT = vB - 1;
+        last = n >= S - 1;
+    }
+}
+
+extern "C" {
+
+hipError_t isk_launch_unary_path(const DevParams* P, int ncols, const RowRec* recs, const float* lutT,
+                                 const float* rcp, const int* vhor, const int* col_flags, const PruneRec* prune,
+                                 float* cost_table, int32_t* index_table, int* bad, int force_bad,
+                                 hipStream_t stream) {
+    if (P->invalid >= 0)
+        hipLaunchKernelGGL(k_unary_path<true>, dim3(ncols), dim3(64), 0, stream, *P, ncols, recs, lutT, rcp, vhor,
+                           col_flags, prune, cost_table, index_table, bad, force_bad);
+    else
+        hipLaunchKernelGGL(k_unary_path<false>, dim3(ncols), dim3(64), 0, stream, *P, ncols, recs, lutT, rcp, vhor,
+                           col_flags, prune, cost_table, index_table, bad, force_bad);
+    return hipGetLastError();
+}
+
+} /* extern "C" */
