@@ -15,59 +15,8 @@
 
 #include "instance_stixels_core.h"
 #include "is_device.h"
+#include "is_launch.h"
 #include "is_numerics.h"
-
-extern "C" {
-size_t isk_prepare_lds_bytes(const DevParams* P);
-size_t isk_unary_lds_bytes(const DevParams* P);
-size_t isk_pairwise_lds_bytes(const DevParams* P, int nwaves);
-hipError_t isk_launch_join(const float*, float*, int, int, int, int, int, int, float, int, hipStream_t);
-hipError_t isk_launch_prepare(const DevParams*, int, const float*, const int32_t*, const float*,
-                              const int*, const float*, RowRec*, float*, int*, float*, PruneRec*, int*,
-                              hipStream_t);
-struct StepRec;
-hipError_t isk_launch_priors(const DevParams*, const float*, PriorRec*, int, hipStream_t);
-hipError_t isk_launch_dp_unary(const DevParams*, int, int, const RowRec*, const float*, const float*,
-                               const int*, const int*, const PruneRec*, float*, int32_t*, const int*,
-                               unsigned long long*, const float*, const float*, hipStream_t);
-hipError_t isk_launch_dp_pairwise(const DevParams*, int, int, const RowRec*, const float*,
-                                  const float*, const PriorRec*, const float*, const float*, const float*,
-                                  const int*, const int*, const PruneRec*, StepRec*, float*, int*,
-                                  float*, int32_t*, unsigned long long*, const float*, const int*, float*, float*,
-                                  hipStream_t, hipStream_t*, int, hipEvent_t, hipEvent_t*);
-hipError_t isk_launch_backtrace(const DevParams*, int, int, const RowRec*, const float*,
-                                const int32_t*, const int*, is_section*, int*, int*, int*, hipStream_t);
-hipError_t isk_launch_dp_unary_path(const DevParams*, int, int, const RowRec*, const float*, const float*, const int*,
-                                    const int*, const PruneRec*, float*, int32_t*, const int*, int*, int, hipStream_t);
-hipError_t isk_launch_compact(const DevParams*, int, const is_section*, const int*,
-                              const is_instance_buffers*, hipStream_t);
-hipError_t isk_set_lds_prepare(const DevParams*);
-hipError_t isk_set_lds_unary(const DevParams*);
-hipError_t isk_set_lds_pairwise(const DevParams*, int);
-hipError_t isk_set_lds_backtrace(const DevParams*);
-int isk_debug_occupancy(const DevParams*, int);
-int isk_unary_uses_fused_lut(const DevParams*, int);
-hipError_t isk_launch_cluster(int, float, int, int, const is_instance_buffers*,
-                              const is_instance_buffers*, int32_t*, hipStream_t);
-size_t isk_phase2_lds_bytes(const DevParams* P);
-size_t isk_phase2s_lds_bytes(const DevParams* P);
-hipError_t isk_launch_pack(const is_section*, int, int, int32_t*, int32_t*, is_section*, hipStream_t);
-hipError_t isk_launch_unpack(const int32_t*, int32_t*, const is_section*, int, int, is_section*, hipStream_t);
-hipError_t isk_launch_flip_and_pad(const float*, int32_t*, int, int, int, int, int, hipStream_t);
-hipError_t isk_launch_vdisparity(const float*, int*, int*, uint8_t*, int, int, int, float, hipStream_t);
-int isk_road_sort_max(void);
-int isk_road_counters(void);
-hipError_t isk_set_lds_road_hough(int);
-hipError_t isk_launch_road_vdisparity(const float*, int*, uint8_t*, int*, int*, int, int, int, int, float,
-                                      hipStream_t);
-int isk_render_scatter_images(void);
-hipError_t isk_launch_section_instance(const is_instance_buffers*, int, int, int, int, int32_t*, hipStream_t);
-hipError_t isk_launch_render(const is_render_args*, const uint8_t*, int, hipStream_t);
-hipError_t isk_launch_instance_overlap(const is_instance_overlap_args*, hipStream_t);
-hipError_t isk_launch_pack_overlap(const is_overlap_record*, const int32_t*, int, int, is_overlap_record*, hipStream_t);
-hipError_t isk_launch_road_hough(const int*, const int*, int*, const float*, int2*, float*, int*, int*, int*, int,
-                                 int, int, int, int, int, int, int, float, float, hipStream_t);
-}
 
 #define IS_FLT_HUGE 1e30f
 static thread_local char g_err[512] = "";
@@ -94,9 +43,24 @@ extern "C" int isk_fail(int code, const char* msg) {
 
 #define IS_STAGE_SLOTS 4 /* pinned staging ring of the per-frame ground model */
 
+/* The IS_* launch knobs (experiments, A/B runs, tests): environment variables read ONCE in is_ctx_create, never per
+ * call; -1 = automatic.  Only plan_call reads them. */
+struct Knobs {
+    int pw_groups;   /* IS_PW_GROUPS: column groups (streams) of the pairwise DP */
+    int p2_split;    /* IS_P2_SPLIT: 1 = k_pw_phase2s, 0 = k_pw_phase2 */
+    int p2x;         /* IS_P2X=0: large batches walk phase 2 with k_pw_phase2 (one column per wave) */
+    int win_tiles;   /* IS_P1_WIN_TILES: number of DP tiles that stage an fn window at any call size */
+    int lut_fused;   /* IS_LUT_FUSED: -1 / 1 = the LUT units run inside the unary DP launch where they can, 0 = never,
+                      * 2 = (tests) fused with a WRONG XCC id published: every workgroup distrusts, the repair launches
+                      * run, 3 = (tests) the default policy (-1) with the wrong id of 2: the first large call is
+                      * repaired, and the context then keeps the table in the prepare launch (DevParams::lutf_repairs) */
+    int unary_path;  /* IS_UNARY_PATH, see plan_call */
+};
+
 struct is_ctx {
     is_stixel_params params;
     DevParams dp;
+    Knobs knobs;
     int device;
     int max_batch;
     int nwaves_unary, nwaves_pairwise;
@@ -108,7 +72,7 @@ struct is_ctx {
     PruneRec* d_prune;       /* [max_batch*C] branch-and-bound slacks of the column */
     int* d_n_generic;        /* [1] generic-encoding columns of the current call */
     int* d_path_bad;         /* [2] k_unary_path's distrust word of the current call, calls repaired (k_backtrace) */
-    int last_unary_path = -1; /* the unary DP of the last unary call: 1 = k_unary_path, 0 = tile path */
+    int last_unary_path = -1; /* the unary DP of the last unary call: 1 = k_unary_path, 0 = tile path (CallPlan::unary_walk) */
     /* per-call device inputs */
     /* one block [ground: max_batch x 3 x H floats][instance table: max_batch][vhor: max_batch ints], on
      * the device and in every pinned staging slot: a full batch (the host class's single frame
@@ -302,12 +266,14 @@ static int ctx_init(is_ctx* c, const is_stixel_params* p, const float* obj_cost_
     const bool debug = getenv("IS_DEBUG") != nullptr;
     {
         auto knob = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : -1; };
-        d.knob_pw_groups = knob("IS_PW_GROUPS");
-        d.knob_p2_split = knob("IS_P2_SPLIT");
-        d.knob_p2x = knob("IS_P2X");
-        d.knob_win_tiles = knob("IS_P1_WIN_TILES");
-        d.knob_lut_fused = knob("IS_LUT_FUSED"); /* the LUT units inside the unary DP launch (is_k_unary_fast.hip, LUTF) */
-        d.knob_unary_path = knob("IS_UNARY_PATH"); /* the unary DP of the visited rows only (is_device.h) */
+        Knobs& k = c->knobs;
+        k.pw_groups = knob("IS_PW_GROUPS");
+        k.p2_split = knob("IS_P2_SPLIT");
+        k.p2x = knob("IS_P2X");
+        k.win_tiles = knob("IS_P1_WIN_TILES");
+        k.lut_fused = knob("IS_LUT_FUSED"); /* the LUT units inside the unary DP launch (is_k_unary_fast.hip, LUTF) */
+        k.unary_path = knob("IS_UNARY_PATH"); /* the unary DP of the visited rows only (k_unary_path) */
+        d.lutf_wrong_xcc = k.lut_fused >= 2 ? 1 : 0;
         c->last_unary_path = -1;
     }
     {
@@ -829,23 +795,95 @@ int is_get_kernel_times_ms(is_ctx* c, float* prepare_ms, float* dp_ms, float* ba
     return IS_OK;
 }
 
-/* fn windows of the DP kernels (is_device.h, IS_P1_WIN) for the tiles that start below the horizon of every image
- * of the call: ground and what stands on it span few disparities within 64 rows, while a tile above the
- * horizon mixes sky (d ~ 0) with objects of any disparity -- measured: 3.6 % of the steps of tile 7 read
- * outside the window, 22-35 % of tiles 12-13, and a step with a lane outside pays a memory round trip.
- * The split decides launch geometry only (workgroup shapes, which kernel instantiation a tile runs), never
- * results. */
-static int call_win_tiles(const DevParams& P, const int* h_vhor, int n_images, int pairwise) {
-    int vmin = P.H;
-    for (int i = 0; i < n_images; i++) vmin = h_vhor[i] < vmin ? h_vhor[i] : vmin;
-    int w = (IS_P1_WINDOWED(P.D) && P.win_lo != nullptr && vmin > 0) ? (vmin + IS_TILE - 1) / IS_TILE : 0;
-    /* the unary kernel windows EVERY tile: a lane outside costs it an L2 gather (2.8 % of its steps on the
-     * synthetic scene), not the HBM round trip on a latency-bound chain it costs phase 1 -- measured at
-     * batch 64: 9 windowed tiles 7450, all 16: 7760 frames/s (pairwise 3780 / 3810, but its unpruned
-     * floor 1720 / 1630) */
-    if (!pairwise && IS_P1_WINDOWED(P.D) && P.win_lo != nullptr) w = P.ntiles;
-    if (P.knob_win_tiles >= 0) w = P.knob_win_tiles; /* (experiments, tests) */
-    return w;
+/* Every launch decision of one DP call (CallPlan, is_launch.h); the launchers launch what it says.  The choices decide
+ * launch geometry and kernel instantiations only, never results. */
+static CallPlan plan_call(const is_ctx* c, int n_images, int pairwise, const int* h_vhor, bool tables_requested) {
+    const DevParams& P = c->dp;
+    const Knobs& k = c->knobs;
+    const int ncols = n_images * P.C;
+    CallPlan p = {};
+    p.ncols = ncols, p.pairwise = pairwise, p.nwaves = pairwise ? c->nwaves_pairwise : c->nwaves_unary;
+
+    /* fn windows (is_device.h, IS_P1_WIN).  Pairwise phase 1: the tiles that start below the horizon of every image of
+     * the call -- ground and what stands on it span few disparities within 64 rows, while a tile above the horizon
+     * mixes sky (d ~ 0) with objects of any disparity: measured, 3.6 % of the steps of tile 7 read outside the window,
+     * 22-35 % of tiles 12-13, and a step with a lane outside pays a memory round trip on a latency-bound chain.  The
+     * unary kernel windows EVERY tile: a lane outside costs it an L2 gather (2.8 % of its steps on the synthetic
+     * scene) -- measured at batch 64: 9 windowed tiles 7450, all 16: 7760 frames/s (pairwise 3780 / 3810, but its
+     * unpruned floor 1720 / 1630).  IS_P1_WIN_TILES forces the window for that many tiles at any call size: tests. */
+    if (IS_P1_WINDOWED(P.D) && (k.win_tiles >= 0 || ncols >= (pairwise ? IS_P1_WIN_MIN_COLS : ISF_WIN_MIN_COLS))) {
+        int w = k.win_tiles >= 0 ? k.win_tiles : P.ntiles, vmin = P.H;
+        if (k.win_tiles < 0 && pairwise) {
+            for (int i = 0; i < n_images; i++) vmin = h_vhor[i] < vmin ? h_vhor[i] : vmin;
+            w = vmin > 0 ? (vmin + IS_TILE - 1) / IS_TILE : 0;
+        }
+        p.win_tiles = w < P.ntiles ? w : P.ntiles;
+    }
+
+    if (!pairwise) {
+        /* The unary DP along the back-trace's path (k_unary_path, is_k_unary_path.hip): the call computes only the table
+         * rows k_backtrace visits instead of every row, and repair launches redo the call on the tile path when a walk
+         * meets what it cannot vouch for.  IS_UNARY_PATH:
+         *   -1 / unset  automatic: unary calls that request no tables (d_cost_table / d_index_table null), with the
+         *               evaluation counters off (they instrument the tile kernels), IS_LUT_FUSED not 2 / 3 (those test
+         *               the fused hand-over), pruning on (IS_NO_PRUNE unset, finite weights and object costs: an
+         *               unpruned walk is slower than the tile path, measured 2345 against 3040 frames/s) and at least
+         *               IS_UNARY_PATH_MIN_COLS columns;
+         *    0          never;
+         *    1          the same rules at any number of columns;
+         *    2          (tests) also when tables are requested: only the visited rows of the caller's tables are written;
+         *    3          (tests) as 2, and every call distrusts itself: the repair launches run. */
+        if (!c->counting && k.unary_path != 0)
+            p.unary_walk = k.unary_path >= 2 ||
+                           (!tables_requested && k.lut_fused != 2 && k.lut_fused != 3 && P.sigma_od < IS_FLT_HUGE &&
+                            (k.unary_path == 1 || ncols >= IS_UNARY_PATH_MIN_COLS));
+        p.unary_force_bad = p.unary_walk && k.unary_path == 3;
+        /* the tile path: FAST columns through the chunk-staged kernel of is_k_unary_fast.hip whenever the shape allows
+         * it, then k_dp_unary takes only the generic columns (measured on MI355X, batch 64: 8.7 ms against 9.3 ms of
+         * the tile-pair kernel, and no scratch) */
+        p.unary_nvr = p.unary_walk ? 0 : isk_unary_fast_chunk_rows(&P);
+        /* LUTF: the LUT units run inside the unary DP launch -- every tile windowed in ONE launch of 4-wave workgroups,
+         * 1, 2 or 4 units per column (a LUT block is four waves).  By itself only where it pays (ISF_LUTF_MIN_COLS; D =
+         * 256, four units per column, 32 frames of 1024x4096: 3940 | 4040 frames/s fused | prepare launch);
+         * IS_LUT_FUSED=1 / 2: at any size.  A hand-over of this context that has been distrusted before (another
+         * dispatcher, a partition mode, a CU mask) keeps it off unless IS_LUT_FUSED asks for it by value: a repaired
+         * call costs 2.8 x an ordinary one. */
+        const int fnb = (P.D + 63) / 64;
+        const bool by_itself = k.lut_fused < 0 || k.lut_fused == 3; /* (3, tests: the default policy, wrong XCC id) */
+        const bool repaired_before = c->h_lutf_repairs && *(volatile int*)c->h_lutf_repairs > 0;
+        p.lut_fused = p.unary_nvr != 0 && k.lut_fused != 0 && ISF_WIN_WAVES == 4 && (fnb == 1 || fnb == 2 || fnb == 4) &&
+                      p.win_tiles == P.ntiles &&
+                      !(by_itself && (ncols < ISF_LUTF_MIN_COLS || fnb > 2 || repaired_before));
+    }
+    /* the walk reads the complete object table of the prepare launch */
+    p.prepare_lut = !p.lut_fused;
+
+    if (pairwise) {
+        /* few columns: two workgroups per (column, tile) in phase 1 */
+        p.nsplit = ncols <= IS_PW_SPLIT_MAX_COLS ? 2 : 1;
+        /* Columns are independent: with enough of them the batch is cut into groups whose phase-1 / phase-2 chains
+         * (2 x ntiles dependent launches each) run on streams of their own, so that the tails and the latency-bound
+         * serial phase 2 of one group share the CUs with the other groups' launches */
+        static_assert(IS_PAIRWISE_MAX_GROUPS <= IS_AUX_STREAMS + 1, "a column group needs a stream of the context");
+        p.groups = ncols / IS_PAIRWISE_SPLIT_MIN_COLS;
+        p.groups = p.groups < 1 ? 1 : p.groups > IS_PAIRWISE_MAX_GROUPS ? IS_PAIRWISE_MAX_GROUPS : p.groups;
+        if (k.pw_groups >= 1 && k.pw_groups <= IS_AUX_STREAMS + 1) p.groups = k.pw_groups;
+        /* phase 2: four waves per column while the columns are too few to fill the chip (IS_P2_SPLIT_MAX_COLS);
+         * large batches two columns per wave (k_pw_phase2x), which needs an even number of columns per image (a pair
+         * never straddles two images); IS_P2X=0 selects k_pw_phase2 */
+        bool split2 = ncols <= IS_P2_SPLIT_MAX_COLS;
+        if (k.p2_split >= 0) split2 = k.p2_split != 0;
+        p.phase2 = split2 ? IS_P2_SPLIT
+                   : (P.C % 2) == 0 && k.p2x != 0 && isk_phase2x_lds_bytes(&P) <= 64 * 1024 ? IS_P2_TWO : IS_P2_ONE;
+    }
+
+    if (ncols <= IS_BACKTRACE_STAGE_MAX_COLS && isk_backtrace_lds_bytes(&P, IS_BT_STAGED) <= 64 * 1024)
+        p.backtrace = IS_BT_STAGED;
+    else if (ncols >= IS_BACKTRACE_TWO_MIN_COLS && isk_backtrace_lds_bytes(&P, IS_BT_TWO) <= 160 * 1024)
+        p.backtrace = IS_BT_TWO;
+    else
+        p.backtrace = IS_BT_PLAIN;
+    return p;
 }
 
 /* Everything is_compute queues on `stream` behind the host-side staging of slot `slot`. */
@@ -854,7 +892,6 @@ static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_se
                            int32_t* d_index_table, hipStream_t stream, int slot) {
     const DevParams& P = c->dp;
     const size_t H = P.H;
-    const int ncols = n_images * P.C;
     const bool timing = c->timing;
     const bool one_copy = n_images == c->max_batch;
     if (one_copy) {
@@ -878,54 +915,31 @@ static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_se
                                hipMemcpyHostToDevice, stream));
     HIP_TRY(hipEventRecord(c->staging_free[slot], stream));
 
-    float* ct = d_cost_table ? d_cost_table : c->d_cost_table;
-    int32_t* it = d_index_table ? d_index_table : c->d_index_table;
+    const CallPlan plan = plan_call(c, n_images, pairwise, c->h_vhor_pinned[slot],
+                                    d_cost_table != nullptr || d_index_table != nullptr);
+    if (!pairwise) c->last_unary_path = plan.unary_walk;
+    CallBuffers b;
+    b.joined = d_joined; b.seg = d_seg; b.ground = c->d_ground; b.vhor = c->d_vhor;
+    b.cost_T = c->d_obj_cost_lut; b.odr = c->d_odr; b.rcp = c->d_rcp;
+    b.recs = c->d_recs; b.lutT = c->d_lutT; b.col_flags = c->d_col_flags; b.sv = c->d_sv; b.prune = c->d_prune;
+    b.n_generic = c->d_n_generic; b.path_bad = c->d_path_bad; b.priors = c->d_priors; b.steps = c->d_steps;
+    b.part_cost = c->d_part_cost; b.part_idx = c->d_part_idx; b.blksum = c->d_blksum; b.t8row = c->d_t8row;
+    b.cost_table = d_cost_table ? d_cost_table : c->d_cost_table;
+    b.index_table = d_index_table ? d_index_table : c->d_index_table;
+    b.counters = c->counting ? c->d_counters : nullptr;
+    b.inst_cnt = want_inst ? c->d_inst_cnt : nullptr;
 
-    DevParams Pw = P; /* (+ this call's windowed / classic tile split and the form of lutT) */
-    Pw.win_tiles = call_win_tiles(P, c->h_vhor_pinned[slot], n_images, pairwise);
-    Pw.lut_fused = !pairwise ? isk_unary_uses_fused_lut(&Pw, ncols) : 0;
-    /* a hand-over of this context has been distrusted before (another dispatcher, a partition mode, a CU mask): the
-     * fused launch stays off unless IS_LUT_FUSED asks for it by value -- a repaired call costs 2.8 x an ordinary one */
-    if (Pw.lut_fused && (P.knob_lut_fused < 0 || P.knob_lut_fused == 3) && c->h_lutf_repairs && *(volatile int*)c->h_lutf_repairs > 0) Pw.lut_fused = 0;
-    /* the unary DP of the visited rows only (k_unary_path; rules: is_device.h, IS_UNARY_PATH_MIN_COLS) */
-    bool path = false;
-    if (!pairwise && !c->counting && P.knob_unary_path != 0) {
-        const bool tables = d_cost_table != nullptr || d_index_table != nullptr;
-        if (P.knob_unary_path >= 2)
-            path = true;
-        else
-            path = !tables && P.knob_lut_fused != 2 && P.knob_lut_fused != 3 && P.sigma_od < IS_FLT_HUGE &&
-                   (P.knob_unary_path == 1 || ncols >= IS_UNARY_PATH_MIN_COLS);
-    }
-    if (path) Pw.lut_fused = 0; /* the walk reads the complete object table of the prepare launch */
-    if (!pairwise) c->last_unary_path = path ? 1 : 0;
     if (timing) HIP_TRY(hipEventRecord(c->ev[0], stream));
     /* (d_n_generic is zero here: cleared at creation and by k_backtrace at the end of every call) */
-    HIP_TRY(isk_launch_prepare(&Pw, ncols, d_joined, d_seg, c->d_ground, c->d_vhor,
-                               c->d_obj_cost_lut, c->d_recs, c->d_lutT, c->d_col_flags, c->d_sv,
-                               c->d_prune, c->d_n_generic, stream));
+    HIP_TRY(isk_launch_prepare(&P, &plan, &b, stream));
     if (pairwise) HIP_TRY(isk_launch_priors(&P, c->d_ground, c->d_priors, n_images, stream));
     if (timing) HIP_TRY(hipEventRecord(c->ev[1], stream));
     if (pairwise)
-        HIP_TRY(isk_launch_dp_pairwise(&Pw, ncols, c->nwaves_pairwise, c->d_recs, c->d_lutT,
-                                       d_joined, c->d_priors, c->d_odr, c->d_rcp, c->d_sv, c->d_vhor,
-                                       c->d_col_flags, c->d_prune, c->d_steps, c->d_part_cost,
-                                       c->d_part_idx, ct, it, c->counting ? c->d_counters : nullptr,
-                                       c->d_obj_cost_lut, c->d_n_generic, c->d_blksum, c->d_t8row, stream, c->aux_streams,
-                                       IS_AUX_STREAMS, c->ev_fork, c->ev_joins));
-    else if (path)
-        HIP_TRY(isk_launch_dp_unary_path(&Pw, ncols, c->nwaves_unary, c->d_recs, c->d_lutT, c->d_rcp, c->d_vhor,
-                                         c->d_col_flags, c->d_prune, ct, it, c->d_n_generic, c->d_path_bad,
-                                         P.knob_unary_path == 3 ? 1 : 0, stream));
+        HIP_TRY(isk_launch_dp_pairwise(&P, &plan, &b, stream, c->aux_streams, c->ev_fork, c->ev_joins));
     else
-        HIP_TRY(isk_launch_dp_unary(&Pw, ncols, c->nwaves_unary, c->d_recs, c->d_lutT, c->d_rcp,
-                                    c->d_vhor, c->d_col_flags, c->d_prune, ct, it, c->d_n_generic,
-                                    c->counting ? c->d_counters : nullptr, d_joined, c->d_obj_cost_lut,
-                                    stream));
+        HIP_TRY(isk_launch_dp_unary(&P, &plan, &b, stream));
     if (timing) HIP_TRY(hipEventRecord(c->ev[2], stream));
-    HIP_TRY(isk_launch_backtrace(&P, ncols, pairwise ? 1 : 0, c->d_recs, ct, it, c->d_col_flags,
-                                 d_sections, want_inst ? c->d_inst_cnt : nullptr, c->d_n_generic, c->d_path_bad,
-                                 stream));
+    HIP_TRY(isk_launch_backtrace(&P, &plan, &b, d_sections, stream));
     if (want_inst) {
         /* the instance candidates (StixelsKernels.cu:926-942) and their clustering
          * (Stixels::ClusterInstances, Stixels.cu:613) of the WHOLE batch: two launches */

@@ -35,13 +35,6 @@
 #define IS_QPT (IS_TILE / IS_QB) /* bound blocks per tile */
 #define IS_PW_MAX_SPLIT 4            /* phase-1 workgroups per (column, tile) at small batches */
 #define IS_PW_SPLIT_TARGET_WGS 1024 /* partial-minima slots reserved for the split phase 1 */
-#ifndef IS_PW_SPLIT_MAX_COLS
-#define IS_PW_SPLIT_MAX_COLS 512     /* up to that many columns: two phase-1 workgroups per (column, tile) */
-#endif
-#define IS_PAIRWISE_SPLIT_MIN_COLS 1024 /* columns per group before the pairwise DP uses one more stream */
-#define IS_PAIRWISE_MAX_GROUPS 3       /* column groups (streams of the context) of the pairwise DP; IS_PW_GROUPS overrides.  The latency-bound phase 2 of one group runs beside the launches of the others.  Round 5, frames/s with 1 / 2 / 3 / 4 groups: batch 64 4116 / 4283 / 4333 / 4227, batch 32 3776 / 3909 / 4009 / 3992, batch 16 2937 / 3120 / 3147 / 3219 (profiles/r05_ab_groups.log).  Beside a PIPELINED RCCL gather of the previous step's output (bench.py --gpus N, parallel.py) the groups cost 5 % instead (round 4: 3680 against 3860): such callers create their context with IS_PW_GROUPS=1, as bench.py does */
-#define IS_P2_SPLIT_MAX_COLS 2048     /* up to eight 2048-px frames: phase 2 of the pairwise DP as chain + evaluator wave per column */
-#define IS_BACKTRACE_STAGE_MAX_COLS 2048 /* up to eight 2048-px frames: the back-trace chases in LDS */
 #define IS_AUX_STREAMS 7               /* auxiliary streams a context owns */
 #define IS_N_ON 8           /* non-instance object classes 2..9   (Cityscapes.h:69) */
 #define IS_N_OI 8           /* instance object classes     11..18 (Cityscapes.h:75) */
@@ -162,19 +155,11 @@ struct DevParams {
      * 2 * gamma_d, the relative error bound of the tree-summed prefixes */
     float sigma_od;
     float gamma2;
-    /* host-side launch knobs: the IS_* environment variables, read ONCE in is_ctx_create (never
-     * per call); -1 = automatic.  The kernels ignore them. */
-    int knob_pw_groups;       /* IS_PW_GROUPS: column groups (streams) of the pairwise DP */
-    int knob_p2_split;        /* IS_P2_SPLIT: 1 = k_pw_phase2s, 0 = k_pw_phase2 */
-    int knob_p2x;             /* IS_P2X=0: large batches walk phase 2 with k_pw_phase2 (one column per wave) */
-    int knob_win_tiles;       /* IS_P1_WIN_TILES: number of phase-1 tiles that stage an fn window (-1: those below the horizon) */
     /* fn windows of the DP kernels (IS_P1_WIN): [n_columns][ntiles] first lutT column of the window a
      * (column, tile) stages in LDS; written by the prepare kernel, device memory of the context */
     int* win_lo;
-    int win_tiles; /* the tiles 0 .. win_tiles - 1 of this call stage a window (set per call: unary every tile,
-                    * pairwise phase 1 the tiles that start below every horizon of the batch) */
     /* LUT units INSIDE the unary DP launch (is_k_unary_fast.hip, LUTF): device counters [columns] of finished
-     * (column, 64 fn) units, zeroed by k_prepare_columns; lut_fused is set per call */
+     * (column, 64 fn) units, zeroed by k_prepare_columns */
     int* lut_ready;
     /* ... and one word per context that a DP workgroup sets when it cannot trust what it waited for: its column's units
      * ran on another XCD than itself (the hand-over goes through the XCD's L2: the units publish their XCC id with
@@ -186,29 +171,9 @@ struct DevParams {
      * call: after the first repair the fused launch is off for the rest of the context's life unless IS_LUT_FUSED asks
      * for it by value.  is_lut_fused_repairs() returns it. */
     int* lutf_repairs;
-    int knob_lut_fused; /* IS_LUT_FUSED: -1 / 1 = the LUT units run inside the unary DP launch where they can, 0 = never,
-                         * 2 = (tests) fused with a WRONG XCC id published: every workgroup distrusts, the repair launches run,
-                         * 3 = (tests) the default policy (-1) with the wrong id of 2: the first large call is repaired, and the
-                         * context then keeps the table in the prepare launch (DevParams::lutf_repairs) */
-    int lut_fused;      /* set per call: 0, 1, or 2 (the test mode) */
-    int knob_unary_path; /* IS_UNARY_PATH, see IS_UNARY_PATH_MIN_COLS */
+    int lutf_wrong_xcc; /* (tests, IS_LUT_FUSED=2 / 3) the fused LUT units publish a WRONG XCC id: every workgroup of a
+                         * fused launch distrusts its hand-over and the repair launches run */
 };
-
-/* The unary DP along the back-trace's path (k_unary_path, is_k_unary_path.hip): a unary call computes only the
- * table rows k_backtrace visits instead of every row, and repair launches redo the call on the tile path when a
- * walk meets what it cannot vouch for.  IS_UNARY_PATH (read once in is_ctx_create):
- *   -1 / unset  automatic: unary calls that request no tables (d_cost_table / d_index_table null), with the
- *               evaluation counters off (they instrument the tile kernels), IS_LUT_FUSED not 2 / 3 (those test the
- *               fused hand-over), pruning on (IS_NO_PRUNE unset, finite weights and object costs: an unpruned
- *               walk is slower than the tile path, measured 2345 against 3040 frames/s) and at least
- *               IS_UNARY_PATH_MIN_COLS columns;
- *    0          never;
- *    1          the same rules at any number of columns;
- *    2          (tests) also when tables are requested: only the visited rows of the caller's tables are written;
- *    3          (tests) as 2, and every call distrusts itself: the repair launches run. */
-#ifndef IS_UNARY_PATH_MIN_COLS
-#define IS_UNARY_PATH_MIN_COLS 2048
-#endif
 
 /* fn windows (k_dp_unary_fast, k_pw_phase1).  A (column, tile) workgroup keeps lutT[vT + 1][*] of its 64 rows in
  * LDS: D + 1 floats per row, 33 KB at D = 128 -- which is what limited a CU to three workgroups.  A lane only

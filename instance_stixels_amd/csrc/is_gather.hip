@@ -40,8 +40,7 @@ typedef int ncclDataType_t;
 static const ncclResult_t ncclSuccess = 0;
 static const ncclDataType_t ncclInt32 = 2;
 #include "instance_stixels_core.h"
-
-extern "C" int isk_fail(int code, const char* msg);
+#include "is_launch.h"
 
 namespace {
 

@@ -287,24 +287,26 @@ __global__ __launch_bounds__(ISC_THREADS) void k_compact_instances(
 
 extern "C" {
 
-#ifndef IS_BACKTRACE_TWO_MIN_COLS
-#define IS_BACKTRACE_TWO_MIN_COLS 8192 /* more one-column waves than the chip holds at once */
-#endif
-hipError_t isk_launch_backtrace(const DevParams* P, int ncols, int pairwise, const RowRec* recs,
-                                const float* cost_table, const int32_t* index_table,
-                                const int* col_flags, is_section* sections, int* inst_cnt,
-                                int* n_generic, int* path_bad, hipStream_t stream) {
+/* dynamic LDS of each form (IS_BT_*, plan_call): the launch and its attribute */
+size_t isk_backtrace_lds_bytes(const DevParams* P, int form) {
     const size_t lds = sizeof(int) * (3 * (size_t)P->S + 8);
-    const size_t lds_staged = lds + sizeof(int) * 6 * (size_t)P->H;
-    if (ncols <= IS_BACKTRACE_STAGE_MAX_COLS && lds_staged <= 64 * 1024)
-        hipLaunchKernelGGL(k_backtrace<true>, dim3(ncols), dim3(64), lds_staged, stream, *P, ncols, pairwise,
-                           recs, cost_table, index_table, col_flags, sections, inst_cnt, n_generic, path_bad);
-    else if (ncols >= IS_BACKTRACE_TWO_MIN_COLS)
-        hipLaunchKernelGGL((k_backtrace<false, true>), dim3((ncols + 1) / 2), dim3(64), 2 * lds, stream, *P, ncols,
-                           pairwise, recs, cost_table, index_table, col_flags, sections, inst_cnt, n_generic, path_bad);
+    return form == IS_BT_STAGED ? lds + sizeof(int) * 6 * (size_t)P->H : form == IS_BT_TWO ? 2 * lds : lds;
+}
+
+hipError_t isk_launch_backtrace(const DevParams* P, const CallPlan* plan, const CallBuffers* b, is_section* sections,
+                                hipStream_t stream) {
+    const int ncols = plan->ncols;
+    const size_t lds = isk_backtrace_lds_bytes(P, plan->backtrace);
+#define IS_BT_ARGS                                                                                                 \
+    *P, ncols, plan->pairwise, b->recs, b->cost_table, b->index_table, b->col_flags, sections, b->inst_cnt,        \
+        b->n_generic, b->path_bad
+    if (plan->backtrace == IS_BT_STAGED)
+        hipLaunchKernelGGL(k_backtrace<true>, dim3(ncols), dim3(64), lds, stream, IS_BT_ARGS);
+    else if (plan->backtrace == IS_BT_TWO)
+        hipLaunchKernelGGL((k_backtrace<false, true>), dim3((ncols + 1) / 2), dim3(64), lds, stream, IS_BT_ARGS);
     else
-        hipLaunchKernelGGL(k_backtrace<false>, dim3(ncols), dim3(64), lds, stream, *P, ncols, pairwise, recs,
-                           cost_table, index_table, col_flags, sections, inst_cnt, n_generic, path_bad);
+        hipLaunchKernelGGL(k_backtrace<false>, dim3(ncols), dim3(64), lds, stream, IS_BT_ARGS);
+#undef IS_BT_ARGS
     return hipGetLastError();
 }
 
@@ -321,13 +323,14 @@ hipError_t isk_launch_compact(const DevParams* P, int n_images, const is_section
     return hipGetLastError();
 }
 
+/* every form plan_call can select: the plain one, the staged one up to 64 KiB, the two-column one up to 160 KiB */
 hipError_t isk_set_lds_backtrace(const DevParams* P) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_backtrace<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)(sizeof(int) * (3 * (size_t)P->S + 8)));
-    if (e != hipSuccess) return e;
-    if (sizeof(int) * (3 * (size_t)P->S + 8 + 6 * (size_t)P->H) <= 64 * 1024) {
-        e = hipFuncSetAttribute((const void*)k_backtrace<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(sizeof(int) * (3 * (size_t)P->S + 8 + 6 * (size_t)P->H)));
+    const void* kernel[3] = {(const void*)k_backtrace<false>, (const void*)k_backtrace<true>,
+                             (const void*)k_backtrace<false, true>}; /* [IS_BT_*] */
+    const size_t cap[3] = {160 * 1024, 64 * 1024, 160 * 1024};
+    for (int form = 0; form < 3; form++) {
+        const size_t bytes = isk_backtrace_lds_bytes(P, form);
+        const hipError_t e = bytes <= cap[form] ? hipFuncSetAttribute(kernel[form], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipSuccess;
         if (e != hipSuccess) return e;
     }
     /* more than ~2000 stixel columns: the per-column offsets exceed the 64 KiB default */

@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "instance_stixels_core.h"
+#include "is_launch.h"
 
 #define IS_IOV_RCH 32          /* image rows per lane */
 #define IS_IOV_WAVES 4         /* waves per workgroup: 128 rows x 64 stixel columns */

@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "instance_stixels_core.h"
+#include "is_launch.h"
 
 #define PK_SCAN_THREADS 1024
 

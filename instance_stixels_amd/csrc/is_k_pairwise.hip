@@ -626,9 +626,6 @@ __device__ __forceinline__ void pairwise_step(const DevParams& P, const StepVals
  * instruction (two lanes, no VGPR, destination a scratch word nobody reads), issued just before
  * the step's own row prefetch so that it never lengthens a vmcnt wait; when the scalar loads come
  * they hit the L2. */
-#ifndef IS_P1_WIN_MIN_COLS
-#define IS_P1_WIN_MIN_COLS 4096
-#endif
 #ifndef IS_P1_WIN_WAVES
 #define IS_P1_WIN_WAVES 4
 #endif
@@ -696,7 +693,7 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
     const int H = P.H, D = P.D;
     /* the vT-side tile: all D lutT columns of the 64 rows, or the fn window [win_lo, win_lo + IS_P1_WIN) of
      * wide tables (is_device.h) */
-    constexpr bool windowed = WIN; /* (the launch picks the instantiation: tile < P.win_tiles) */
+    constexpr bool windowed = WIN; /* (the launch picks the instantiation: tile < CallPlan::win_tiles) */
     const int win_w = windowed ? IS_P1_WIN : D;
     const int DP = win_w + 1;
     float* s_tile = (float*)smem;             /* [64][win_w + 1] */
@@ -2341,91 +2338,50 @@ size_t isk_phase2s_lds_bytes(const DevParams* P) {
            sizeof(int) * (ISP2S_SLOTS + 1 + 2 * ISP2S_WAVES) + 32;
 }
 
-hipError_t isk_launch_dp_pairwise(const DevParams* P, int ncols, int nwaves, const RowRec* recs,
-                                  const float* lutT, const float* joined, const PriorRec* priors, const float* odr,
-                                  const float* rcp, const float* sv_arr, const int* vhor,
-                                  const int* col_flags, const PruneRec* prune, StepRec* steps,
-                                  float* part_cost, int* part_idx, float* cost_table,
-                                  int32_t* index_table, unsigned long long* counters,
-                                  const float* cost_T, const int* n_generic, float* blksum, float* t8row,
-                                  hipStream_t stream, hipStream_t* aux, int n_aux,
-                                  hipEvent_t ev_fork, hipEvent_t* ev_join) {
-    /* windowed tiles (P->win_tiles): IS_P1_WIN_WAVES waves per workgroup -- the smaller LDS footprint lets a CU
+/* The phase-1 / phase-2 launch pairs of every tile, per column group (plan->groups, the first on `stream`, the others on
+ * aux[0 ..]: forked from `stream` and joined back to it). */
+hipError_t isk_launch_dp_pairwise(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream,
+                                  const hipStream_t* aux, hipEvent_t ev_fork, const hipEvent_t* ev_join) {
+    const int ncols = plan->ncols, nwaves = plan->nwaves, nsplit = plan->nsplit, groups = plan->groups;
+    /* windowed tiles (plan->win_tiles): IS_P1_WIN_WAVES waves per workgroup -- the smaller LDS footprint lets a CU
      * hold more, smaller workgroups (measured at D = 64: 4 waves x 4 workgroups beat 8 x 3 on every tile) */
     const int nwaves_win = IS_P1_WIN_WAVES < nwaves ? IS_P1_WIN_WAVES : nwaves;
     const size_t lds2 = isk_phase2_lds_bytes(P);
-    /* Columns are independent: with enough of them the batch is cut into groups whose
-     * phase-1 / phase-2 chains (2 x ntiles dependent launches each) run on their own streams, so
-     * that the tails and the latency-bound serial phase 2 of one group share the CUs with the
-     * other groups' launches. */
-    /* few columns: two workgroups per (column, tile) in phase 1 */
-    /* (measured on MI355X, frames/s of one / two 256-column frames per call: 1 workgroup per
-     * (column, tile) 540 / 903, 2: 587 / 931, 3: 584 / -, 4: 561 / -) */
-    static_assert(2 * IS_PW_SPLIT_MAX_COLS <= IS_PW_SPLIT_TARGET_WGS,
-                  "the context reserves IS_PW_SPLIT_TARGET_WGS partial-minima slots for the split phase 1");
-    int nsplit = ncols <= IS_PW_SPLIT_MAX_COLS ? 2 : 1;
-    if (nsplit > IS_PW_MAX_SPLIT) nsplit = IS_PW_MAX_SPLIT;
-    int groups = ncols / IS_PAIRWISE_SPLIT_MIN_COLS;
-    groups = groups < 1 ? 1 : groups;
-    /* measured on MI355X at batch 64 after the pruning of phase 1: 1 group 29.8 ms, 2 groups 30.2,
-     * 4 groups 30.1, 8 groups 30.6 per step -- launches of different streams barely overlap, so the
-     * default is one group; IS_PW_GROUPS overrides */
-    if (groups > IS_PAIRWISE_MAX_GROUPS) groups = IS_PAIRWISE_MAX_GROUPS;
-    if (groups > n_aux + 1) groups = n_aux + 1;
-    if (P->knob_pw_groups >= 1 && P->knob_pw_groups <= n_aux + 1) groups = P->knob_pw_groups;
+    const size_t lds2s = isk_phase2s_lds_bytes(P);
+    const size_t lds2x = isk_phase2x_lds_bytes(P);
     hipError_t e;
+#define IS_P2_ARGS                                                                                                  \
+    c0, c1, tile, nsplit, b->recs, b->lutT, b->joined, b->priors, b->odr, b->rcp, b->sv, b->vhor, b->col_flags,     \
+        b->part_cost, b->part_idx, b->steps, b->cost_table, b->index_table
 /* the vB-side lutT row in registers (LutRow<2>, D <= 128): slower than the per-lane gather while
  * phase 1 was issue-bound (41.4 vs 38.0 ms per 64 frames, round 1), faster now that the pruned
- * phase 1 is latency-bound (30.4 vs 31.2 ms): no memory access on the chain mean -> fn -> value */
-#define IS_LAUNCH_P1(INV, c0, c1, st)                                                              \
-    do {                                                                                           \
-        if (win_t)                                                                                 \
-            hipLaunchKernelGGL((k_pw_phase1<INV, 2, true>), dim3(((c1) - (c0)) * nsplit),          \
-                               dim3(nw_t * 64), lds1_t, st, *P, c0, c1, tile, nsplit, recs, lutT,  \
-                               steps, rcp, vhor, col_flags, prune, part_cost, part_idx, counters, \
-                               joined, cost_T, blksum);                                            \
-        else if (P->D <= 128)                                                                      \
-            hipLaunchKernelGGL((k_pw_phase1<INV, 2>), dim3(((c1) - (c0)) * nsplit),                \
-                               dim3(nw_t * 64), lds1_t, st, *P, c0, c1, tile, nsplit, recs, lutT,  \
-                               steps, rcp, vhor, col_flags, prune, part_cost, part_idx, counters, \
-                               joined, cost_T, blksum);                                            \
-        else                                                                                       \
-            hipLaunchKernelGGL((k_pw_phase1<INV, 0>), dim3(((c1) - (c0)) * nsplit),                \
-                               dim3(nw_t * 64), lds1_t, st, *P, c0, c1, tile, nsplit, recs, lutT,  \
-                               steps, rcp, vhor, col_flags, prune, part_cost, part_idx, counters,  \
-                               joined, cost_T, blksum);                                            \
+ * phase 1 is latency-bound (30.4 vs 31.2 ms): no memory access on the chain mean -> fn -> value.
+ * (any D: the windowed instantiation keeps 64 columns of a vB row in one register per lane) */
+#define IS_LAUNCH_P1(KERNEL)                                                                                        \
+    hipLaunchKernelGGL(KERNEL, dim3((c1 - c0) * nsplit), dim3(nw_t * 64), lds1_t, st, *P, c0, c1, tile, nsplit,     \
+                       b->recs, b->lutT, b->steps, b->rcp, b->vhor, b->col_flags, b->prune, b->part_cost,           \
+                       b->part_idx, b->counters, b->joined, b->cost_T, b->blksum)
+#define IS_LAUNCH_TILE(INV)                                                                                         \
+    do {                                                                                                            \
+        if (win_t)                                                                                                  \
+            IS_LAUNCH_P1((k_pw_phase1<INV, 2, true>));                                                              \
+        else if (P->D <= 128)                                                                                       \
+            IS_LAUNCH_P1((k_pw_phase1<INV, 2>));                                                                    \
+        else                                                                                                        \
+            IS_LAUNCH_P1((k_pw_phase1<INV, 0>));                                                                    \
+        if (plan->phase2 == IS_P2_SPLIT) {                                                                          \
+            hipLaunchKernelGGL(k_pw_phase2s<INV>, dim3(c1 - c0), dim3(ISP2S_WAVES * 64), lds2s, st, *P, IS_P2_ARGS, \
+                               b->blksum, b->t8row);                                                                \
+        } else if (plan->phase2 == IS_P2_TWO) {                                                                     \
+            hipLaunchKernelGGL(k_pw_phase2x<INV>, dim3((c1 - c0 + 1) / 2), dim3(64), lds2x, st, *P, IS_P2_ARGS,     \
+                               b->blksum, b->t8row);                                                                \
+            hipLaunchKernelGGL(k_pw_phase2_generic<INV>, dim3(min(c1 - c0, 512)), dim3(64), lds2, st, *P,           \
+                               IS_P2_ARGS, b->n_generic, b->blksum, b->t8row);                                      \
+        } else {                                                                                                    \
+            hipLaunchKernelGGL(k_pw_phase2<INV>, dim3(c1 - c0), dim3(64), lds2, st, *P, IS_P2_ARGS, b->blksum,      \
+                               b->t8row);                                                                           \
+        }                                                                                                           \
     } while (0)
-#define IS_LAUNCH_P2(INV, c0, c1, st)                                                              \
-    hipLaunchKernelGGL(k_pw_phase2<INV>, dim3((c1) - (c0)), dim3(64), lds2, st, *P, c0, c1, tile,  \
-                       nsplit, recs, lutT, joined, priors, odr, rcp, sv_arr, vhor, col_flags,      \
-                       part_cost,                                                                  \
-                       part_idx, steps, cost_table, index_table, blksum, t8row)
-#define IS_LAUNCH_P2X(INV, c0, c1, st)                                                             \
-    do {                                                                                           \
-        hipLaunchKernelGGL(k_pw_phase2x<INV>, dim3(((c1) - (c0) + 1) / 2), dim3(64), lds2x, st, *P, c0, \
-                           c1, tile, nsplit, recs, lutT, joined, priors, odr, rcp, sv_arr, vhor,   \
-                           col_flags, part_cost, part_idx, steps, cost_table, index_table, blksum, t8row); \
-        hipLaunchKernelGGL(k_pw_phase2_generic<INV>, dim3(min((c1) - (c0), 512)), dim3(64), lds2, st, \
-                           *P, c0, c1, tile, nsplit, recs, lutT, joined, priors, odr, rcp, sv_arr, \
-                           vhor, col_flags, part_cost, part_idx, steps, cost_table, index_table,   \
-                           n_generic, blksum, t8row);                                                     \
-    } while (0)
-#define IS_LAUNCH_P2S(INV, c0, c1, st)                                                             \
-    hipLaunchKernelGGL(k_pw_phase2s<INV>, dim3((c1) - (c0)), dim3(ISP2S_WAVES * 64), lds2s, st, *P, \
-                       c0, c1, tile, nsplit, recs, lutT, joined, priors, odr, rcp, sv_arr, vhor,   \
-                       col_flags, part_cost, part_idx, steps, cost_table, index_table, blksum, t8row)
-    const bool inv = P->invalid >= 0;
-    /* phase 2 split over four waves per column (k_pw_phase2s) while the columns are too few to fill
-     * the chip with one wave each: it shortens the serial chain of a column (one frame: 82 -> 74 us
-     * per tile) but spends four wave slots per column, which costs throughput at large batches
-     * (batch 64: 32.7 vs 25.4 ms per step).  IS_P2_SPLIT=0/1 overrides. */
-    bool split2 = ncols <= IS_P2_SPLIT_MAX_COLS;
-    if (P->knob_p2_split >= 0) split2 = P->knob_p2_split != 0;
-    const size_t lds2s = isk_phase2s_lds_bytes(P);
-    /* large batches: two columns per wave in phase 2 (k_pw_phase2x); needs an even number of
-     * columns per image (a pair never straddles two images); IS_P2X=0 selects k_pw_phase2 */
-    const size_t lds2x = isk_phase2x_lds_bytes(P);
-    const bool two_col = !split2 && (P->C % 2) == 0 && P->knob_p2x != 0 && lds2x <= 64 * 1024;
     if (groups > 1) {
         if ((e = hipEventRecord(ev_fork, stream)) != hipSuccess) return e;
         for (int g = 1; g < groups; g++)
@@ -2433,14 +2389,7 @@ hipError_t isk_launch_dp_pairwise(const DevParams* P, int ncols, int nwaves, con
     }
     for (int tile = 0; tile < P->ntiles; tile++) {
         /* (the block bounds of tile t need t + 1 of the ntiles + 1 entries lds1 has room for) */
-        /* (large batches only: a call of a few frames does not fill the chip, there the eight waves per
-         * column are the parallelism: one frame 1.57 ms classic, 1.63 ms windowed; frames/s at batch 4 / 8 /
-         * 16 / 32: 1461 / 2068 / 2795 / 3178 classic, 1424 / 2010 / 2798 / 3269 windowed.  IS_P1_WIN_TILES
-         * forces the window for that many tiles at any batch: tests) */
-        /* (any D: the windowed instantiation keeps 64 columns of a vB row in one register per lane) */
-        const bool win_t = IS_P1_WINDOWED(P->D) &&
-                           P->win_lo != nullptr && tile < P->win_tiles &&
-                           (P->knob_win_tiles >= 0 || ncols >= IS_P1_WIN_MIN_COLS);
+        const bool win_t = tile < plan->win_tiles;
         const int nw_t = win_t ? nwaves_win : nwaves;
         const size_t lds1_t = p1_lds_bytes(P, nw_t, win_t) -
                               sizeof(float) * IS_P1_BLK_WORDS * (size_t)IS_QPT * (size_t)(P->ntiles - tile);
@@ -2448,20 +2397,12 @@ hipError_t isk_launch_dp_pairwise(const DevParams* P, int ncols, int nwaves, con
             const int c0 = (int)((long long)ncols * g / groups) & ~1; /* (even: column pairs) */
             const int c1 = g + 1 == groups ? ncols : ((int)((long long)ncols * (g + 1) / groups) & ~1);
             hipStream_t st = g == 0 ? stream : aux[g - 1];
-            if (inv) IS_LAUNCH_P1(true, c0, c1, st); else IS_LAUNCH_P1(false, c0, c1, st);
-            if (split2) {
-                if (inv) IS_LAUNCH_P2S(true, c0, c1, st); else IS_LAUNCH_P2S(false, c0, c1, st);
-            } else if (two_col) {
-                if (inv) IS_LAUNCH_P2X(true, c0, c1, st); else IS_LAUNCH_P2X(false, c0, c1, st);
-            } else {
-                if (inv) IS_LAUNCH_P2(true, c0, c1, st); else IS_LAUNCH_P2(false, c0, c1, st);
-            }
+            if (P->invalid >= 0) IS_LAUNCH_TILE(true); else IS_LAUNCH_TILE(false);
         }
     }
+#undef IS_LAUNCH_TILE
 #undef IS_LAUNCH_P1
-#undef IS_LAUNCH_P2
-#undef IS_LAUNCH_P2S
-#undef IS_LAUNCH_P2X
+#undef IS_P2_ARGS
     for (int g = 1; g < groups; g++) {
         if ((e = hipEventRecord(ev_join[g - 1], aux[g - 1])) != hipSuccess) return e;
         if ((e = hipStreamWaitEvent(stream, ev_join[g - 1], 0)) != hipSuccess) return e;
@@ -2469,20 +2410,14 @@ hipError_t isk_launch_dp_pairwise(const DevParams* P, int ncols, int nwaves, con
     return hipGetLastError();
 }
 
-hipError_t isk_set_lds_pairwise(const DevParams* P, int nwaves_pair) {
-    hipError_t e;
-    const int c = (int)isk_pairwise_lds_bytes(P, nwaves_pair);
-    e = hipFuncSetAttribute((const void*)k_pw_phase1<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, c);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute((const void*)k_pw_phase1<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, c);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute((const void*)k_pw_phase1<true, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, c);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute((const void*)k_pw_phase1<false, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, c);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute((const void*)k_pw_phase1<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, c);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute((const void*)k_pw_phase1<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, c);
+hipError_t isk_set_lds_pairwise(const DevParams* P, int nwaves) {
+    const int c = (int)isk_pairwise_lds_bytes(P, nwaves); /* (the windowed instantiations need less) */
+    hipError_t e = hipSuccess;
+#define IS_SET_P1_LDS(...) \
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_pw_phase1<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, c)
+    IS_SET_P1_LDS(true, 2); IS_SET_P1_LDS(false, 2); IS_SET_P1_LDS(true, 2, true); IS_SET_P1_LDS(false, 2, true);
+    IS_SET_P1_LDS(true, 0); IS_SET_P1_LDS(false, 0);
+#undef IS_SET_P1_LDS
     return e;
 }
 

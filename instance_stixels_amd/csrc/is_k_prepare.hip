@@ -838,21 +838,19 @@ hipError_t isk_launch_lut_repair(const DevParams* P, int ncols, const float* joi
     return hipGetLastError();
 }
 
-hipError_t isk_launch_prepare(const DevParams* P, int ncols, const float* joined,
-                              const int32_t* seg, const float* ground, const int* vhor,
-                              const float* cost_T, RowRec* recs, float* lutT,
-                              int* col_flags, float* sv_arr, PruneRec* prune, int* n_generic,
-                              hipStream_t stream) {
-    if (P->lut_fused) { /* the LUT units run inside the unary DP launch (k_dp_unary_fast, LUTF): records only here */
+hipError_t isk_launch_prepare(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream) {
+    const int ncols = plan->ncols;
+    if (!plan->prepare_lut) { /* the LUT units run inside the unary DP launch (k_dp_unary_fast, LUTF): records only here */
         hipLaunchKernelGGL(k_prepare_columns, dim3(ncols), dim3(PREP_THREADS), isk_prepare_lds_bytes(P), stream, *P,
-                           joined, seg, ground, vhor, recs, col_flags, sv_arr, prune, n_generic);
+                           b->joined, b->seg, b->ground, b->vhor, b->recs, b->col_flags, b->sv, b->prune, b->n_generic);
         return hipGetLastError();
     }
     /* the two prepare kernels are independent: one launch with workgroups of both kinds (k_prepare_fused) */
     const int units = ncols * ((P->D + 63) / 64);
     const int n_lut = (units + PREP_THREADS / 64 - 1) / (PREP_THREADS / 64);
     hipLaunchKernelGGL(k_prepare_fused, dim3(ncols + n_lut), dim3(PREP_THREADS), isk_prepare_lds_bytes(P), stream, *P,
-                       ncols, n_lut, joined, seg, ground, vhor, cost_T, recs, lutT, col_flags, sv_arr, prune, n_generic);
+                       ncols, n_lut, b->joined, b->seg, b->ground, b->vhor, b->cost_T, b->recs, b->lutT, b->col_flags,
+                       b->sv, b->prune, b->n_generic);
     return hipGetLastError();
 }
 

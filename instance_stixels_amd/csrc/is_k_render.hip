@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "instance_stixels_core.h"
+#include "is_launch.h"
 
 #define IS_RENDER_RCH 32    /* image rows per lane */
 #define IS_RENDER_WAVES 4   /* waves per workgroup, stacked vertically: 128 rows x 64 stixel columns */

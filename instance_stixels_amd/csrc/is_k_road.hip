@@ -9,6 +9,8 @@
 
 #include <stdint.h>
 
+#include "is_launch.h"
+
 /* Per-frame counters of the batch scratch: [frame][IS_ROAD_CNT] ints. */
 #define IS_ROAD_CNT 2
 #define IS_ROAD_CNT_MAX 0    /* maximum of the histogram */

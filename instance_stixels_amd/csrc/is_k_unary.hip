@@ -414,14 +414,6 @@ __global__ __launch_bounds__(IS_UNARY_WAVES * 64, IS_UNARY_OCC) void k_dp_unary(
     } /* item */
 }
 
-extern "C" hipError_t isk_launch_unary_path(const DevParams*, int, const RowRec*, const float*, const float*,
-                                            const int*, const int*, const PruneRec*, float*, int32_t*, int*, int,
-                                            hipStream_t);
-extern "C" hipError_t isk_launch_dp_unary_fast(const DevParams*, int, const RowRec*, const float*,
-                                               const float*, const int*, const int*, const PruneRec*,
-                                               float*, int32_t*, unsigned long long*, const float*,
-                                               const float*, hipStream_t);
-
 extern "C" {
 
 size_t isk_unary_lds_bytes(const DevParams* P) {
@@ -431,43 +423,45 @@ size_t isk_unary_lds_bytes(const DevParams* P) {
     return rcp + (tile > merge ? tile : merge) + 16;
 }
 
-hipError_t isk_launch_dp_unary(const DevParams* P, int ncols, int nwaves, const RowRec* recs,
-                               const float* lutT, const float* rcp, const int* vhor,
-                               const int* col_flags, const PruneRec* prune, float* cost_table,
-                               int32_t* index_table, const int* n_generic,
-                               unsigned long long* counters, const float* joined, const float* cost_T,
-                               hipStream_t stream) {
-    /* FAST columns: the chunk-staged kernel of is_k_unary_fast.hip whenever the shape allows it;
-     * then only the generic columns are left for this file's kernel */
-    /* (measured on MI355X, batch 64: 8.7 ms against 9.3 ms of the tile-pair kernel below, and no
-     * scratch) */
-    const bool fast_kernel = isk_unary_fast_chunk_rows(P) > 0;
-    if (fast_kernel) {
-        const hipError_t e = isk_launch_dp_unary_fast(P, ncols, recs, lutT, rcp, vhor, col_flags, prune,
-                                                      cost_table, index_table, counters, joined, cost_T,
-                                                      stream);
-        if (e != hipSuccess) return e;
-    }
-    const int groups = (ncols + 7) / 8;
+/* The unary DP of a call, as plan_call decided:
+ *  - the walk (is_k_unary_path.hip): the visited rows of the FAST columns, then the generic columns in full (leaves at
+ *    once when the call has none), then the repair: the tile-path DP of every FAST column again, leaving at once
+ *    while k_unary_path has not set path_bad.  lutT is complete (the prepare launch);
+ *  - the tile path: the FAST columns through k_dp_unary_fast (plan->unary_nvr) or the kernel of this file, then the
+ *    generic columns. */
+hipError_t isk_launch_dp_unary(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream) {
+    const int ncols = plan->ncols;
+    hipError_t e = hipSuccess;
+    if (plan->unary_walk)
+        e = isk_launch_unary_path(P, plan, b, stream);
+    else if (plan->unary_nvr)
+        e = isk_launch_dp_unary_fast(P, plan, b, stream);
+    if (e != hipSuccess) return e;
+    const bool tiles = !plan->unary_walk && !plan->unary_nvr;
     /* one tile pair (big, small) per workgroup: equal-length workgroups pack best; measured on
      * MI355X at batch 32: 1 pair 9.98 ms, 2 pairs 10.10 ms, 4 pairs 10.55 ms, single tiles 11.1 ms */
     const int npairs = (P->ntiles + 1) / 2;
     const int pairs_per_wg = 1;
-    const int wg_per_col = (npairs + pairs_per_wg - 1) / pairs_per_wg;
-    const dim3 grid(groups * 8 * wg_per_col);
-    const dim3 grid_generic(grid.x < 16384u ? grid.x : 16384u); /* walks the items, see the kernel */
+    const unsigned items = (unsigned)((ncols + 7) / 8) * 8u * (unsigned)npairs;
+    const dim3 grid_generic(items < 16384u ? items : 16384u); /* walks the items, see the kernel */
+    const dim3 grid_repair(items < 2048u ? items : 2048u);    /* (walks the items: a safety net, not a fast path) */
+    const dim3 block(plan->nwaves * 64);
     const size_t lds = isk_unary_lds_bytes(P);
     /* D <= 128: the vB-side lutT row travels in two registers per lane (LutRow<2>); wider
      * tables gather per lane */
-#define IS_LAUNCH_UNARY(INV, NR)                                                                   \
-    do {                                                                                           \
-        if (!fast_kernel)                                                                          \
-            hipLaunchKernelGGL((k_dp_unary<INV, NR, true>), grid, dim3(nwaves * 64), lds, stream,  \
-                               *P, ncols, recs, lutT, rcp, vhor, col_flags, prune, cost_table,     \
-                               index_table, n_generic, pairs_per_wg);                              \
-        hipLaunchKernelGGL((k_dp_unary<INV, NR, false>), grid_generic, dim3(nwaves * 64), lds,     \
-                           stream, *P, ncols, recs, lutT, rcp, vhor, col_flags, prune, cost_table, \
-                           index_table, n_generic, pairs_per_wg);                                  \
+#define IS_LAUNCH_UNARY(INV, NR)                                                                           \
+    do {                                                                                                   \
+        if (tiles)                                                                                         \
+            hipLaunchKernelGGL((k_dp_unary<INV, NR, true>), dim3(items), block, lds, stream, *P, ncols, b->recs,  \
+                               b->lutT, b->rcp, b->vhor, b->col_flags, b->prune, b->cost_table,            \
+                               b->index_table, b->n_generic, pairs_per_wg);                                \
+        hipLaunchKernelGGL((k_dp_unary<INV, NR, false>), grid_generic, block, lds, stream, *P, ncols,      \
+                           b->recs, b->lutT, b->rcp, b->vhor, b->col_flags, b->prune, b->cost_table,       \
+                           b->index_table, b->n_generic, pairs_per_wg);                                    \
+        if (plan->unary_walk)                                                                              \
+            hipLaunchKernelGGL((k_dp_unary<INV, NR, true, true>), grid_repair, block, lds, stream, *P,     \
+                               ncols, b->recs, b->lutT, b->rcp, b->vhor, b->col_flags, b->prune,           \
+                               b->cost_table, b->index_table, b->path_bad, pairs_per_wg);                  \
     } while (0)
     if (P->D <= 128) {
         if (P->invalid >= 0) IS_LAUNCH_UNARY(true, 2); else IS_LAUNCH_UNARY(false, 2);
@@ -475,39 +469,6 @@ hipError_t isk_launch_dp_unary(const DevParams* P, int ncols, int nwaves, const 
         if (P->invalid >= 0) IS_LAUNCH_UNARY(true, 0); else IS_LAUNCH_UNARY(false, 0);
     }
 #undef IS_LAUNCH_UNARY
-    return hipGetLastError();
-}
-
-/* The unary DP of a call that takes the path walk (is_k_unary_path.hip): the visited rows of the FAST columns, then
- * the generic columns in full (leaves at once when the call has none), then the repair: the tile-path DP of every
- * FAST column again, leaving at once while k_unary_path has not set *bad.  lutT is complete (the prepare launch). */
-hipError_t isk_launch_dp_unary_path(const DevParams* P, int ncols, int nwaves, const RowRec* recs, const float* lutT,
-                                    const float* rcp, const int* vhor, const int* col_flags, const PruneRec* prune,
-                                    float* cost_table, int32_t* index_table, const int* n_generic, int* bad,
-                                    int force_bad, hipStream_t stream) {
-    const hipError_t e = isk_launch_unary_path(P, ncols, recs, lutT, rcp, vhor, col_flags, prune, cost_table,
-                                               index_table, bad, force_bad, stream);
-    if (e != hipSuccess) return e;
-    const int npairs = (P->ntiles + 1) / 2;
-    const unsigned items = (unsigned)((ncols + 7) / 8) * 8u * (unsigned)npairs;
-    const dim3 grid_generic(items < 16384u ? items : 16384u);
-    const dim3 grid_repair(items < 2048u ? items : 2048u); /* (walks the items: a safety net, not a fast path) */
-    const size_t lds = isk_unary_lds_bytes(P);
-#define IS_LAUNCH_UNARY_PATH(INV, NR)                                                              \
-    do {                                                                                           \
-        hipLaunchKernelGGL((k_dp_unary<INV, NR, false>), grid_generic, dim3(nwaves * 64), lds,     \
-                           stream, *P, ncols, recs, lutT, rcp, vhor, col_flags, prune, cost_table, \
-                           index_table, n_generic, 1);                                             \
-        hipLaunchKernelGGL((k_dp_unary<INV, NR, true, true>), grid_repair, dim3(nwaves * 64), lds, \
-                           stream, *P, ncols, recs, lutT, rcp, vhor, col_flags, prune, cost_table, \
-                           index_table, bad, 1);                                                   \
-    } while (0)
-    if (P->D <= 128) {
-        if (P->invalid >= 0) IS_LAUNCH_UNARY_PATH(true, 2); else IS_LAUNCH_UNARY_PATH(false, 2);
-    } else {
-        if (P->invalid >= 0) IS_LAUNCH_UNARY_PATH(true, 0); else IS_LAUNCH_UNARY_PATH(false, 0);
-    }
-#undef IS_LAUNCH_UNARY_PATH
     return hipGetLastError();
 }
 
@@ -519,25 +480,16 @@ int isk_debug_occupancy(const DevParams* P, int nwaves) {
 }
 
 hipError_t isk_set_lds_unary(const DevParams* P) {
-    hipError_t e;
     const int b = (int)isk_unary_lds_bytes(P);
-#define IS_SET_UNARY_LDS(INV, NR, FC)                                                             \
-    e = hipFuncSetAttribute((const void*)k_dp_unary<INV, NR, FC>,                                 \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, b);                       \
-    if (e != hipSuccess) return e
-    IS_SET_UNARY_LDS(true, 2, true); IS_SET_UNARY_LDS(true, 2, false);
-    IS_SET_UNARY_LDS(false, 2, true); IS_SET_UNARY_LDS(false, 2, false);
-    IS_SET_UNARY_LDS(true, 0, true); IS_SET_UNARY_LDS(true, 0, false);
-    IS_SET_UNARY_LDS(false, 0, true); IS_SET_UNARY_LDS(false, 0, false);
+    hipError_t e = hipSuccess;
+#define IS_SET_UNARY_LDS(...) \
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_dp_unary<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, b)
+    IS_SET_UNARY_LDS(true, 2, true); IS_SET_UNARY_LDS(true, 2, false); IS_SET_UNARY_LDS(true, 2, true, true);
+    IS_SET_UNARY_LDS(false, 2, true); IS_SET_UNARY_LDS(false, 2, false); IS_SET_UNARY_LDS(false, 2, true, true);
+    IS_SET_UNARY_LDS(true, 0, true); IS_SET_UNARY_LDS(true, 0, false); IS_SET_UNARY_LDS(true, 0, true, true);
+    IS_SET_UNARY_LDS(false, 0, true); IS_SET_UNARY_LDS(false, 0, false); IS_SET_UNARY_LDS(false, 0, true, true);
 #undef IS_SET_UNARY_LDS
-#define IS_SET_UNARY_LDS_GATED(INV, NR)                                                           \
-    e = hipFuncSetAttribute((const void*)k_dp_unary<INV, NR, true, true>,                         \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, b);                       \
-    if (e != hipSuccess) return e
-    IS_SET_UNARY_LDS_GATED(true, 2); IS_SET_UNARY_LDS_GATED(false, 2);
-    IS_SET_UNARY_LDS_GATED(true, 0); IS_SET_UNARY_LDS_GATED(false, 0);
-#undef IS_SET_UNARY_LDS_GATED
-    return isk_set_lds_unary_fast(P);
+    return e != hipSuccess ? e : isk_set_lds_unary_fast(P);
 }
 
 } /* extern "C" */

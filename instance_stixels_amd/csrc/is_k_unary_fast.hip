@@ -51,13 +51,7 @@
 #define ISF_SREC 1 /* the class-prefix half of the vB record as scalar operands (eval_segment_mix) */
 #endif
 #define ISF_THREADS (ISF_WAVES * 64)
-#ifndef ISF_WIN_WAVES
-#define ISF_WIN_WAVES 4 /* waves per workgroup of the windowed tiles */
-#endif
 static_assert(ISF_WIN_WAVES >= 3 && ISF_WIN_WAVES <= ISF_WAVES, "the merge runs on 3 x 64 threads (one wave per type)");
-#ifndef ISF_WIN_MIN_COLS
-#define ISF_WIN_MIN_COLS 0 /* columns per call from which the windowed launch is used.  Round 4: 2048 (frames/s windowed | classic at batch 2: 6470 | 6050, 4: 6090 | 6350, 8: 6890 | 6680, 16: 7480 | 7010, 32: 7860 | 7200); with the diagonal blocks in quarters (round 5) the windowed launch wins at every size: batch 1: 6290 | 5220, 2: 8180 | 6140, 4: 7110 | 6380, 8: 9190 | 9070 */
-#endif
 
 struct UnaryBestF {
     float g, o, s;
@@ -459,9 +453,6 @@ __device__ __forceinline__ void diag_quarters(const DevParams& P, RowRec& my, Un
 #ifndef ISF_OCC_LUTF_INV
 #define ISF_OCC_LUTF_INV 6 /* with an invalid-disparity value: 80 VGPRs; at 7: 6 spilled VGPRs (see ISF_OCC_INV) */
 #endif
-#ifndef ISF_LUTF_MIN_COLS
-#define ISF_LUTF_MIN_COLS 2048 /* columns per call from which the LUT units run inside the DP launch by default */
-#endif
 #ifndef ISF_LUTF_POLL_MAX
 #define ISF_LUTF_POLL_MAX (1 << 14) /* polls of a DP workgroup for its column's units before it distrusts the hand-over */
 #endif
@@ -523,9 +514,9 @@ __device__ __forceinline__ void lut_unit_fused(const DevParams& P, const int col
      * gfx950, an agent-scope acquire an invalidation: at one per unit / workgroup the launch took 10.6 ms.) */
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    /* count + 256 x the XCC id of this unit (lut_fused == 2, tests: a wrong one): the readers check that they share it */
+    /* count + 256 x the XCC id of this unit (lutf_wrong_xcc, tests: a wrong one): the readers check that they share it */
     if (lane == 0)
-        __hip_atomic_fetch_add(ready + colg, 1 + (((xcc_id() + (P.lut_fused == 2 ? 1 : 0)) & 15) << 8), __ATOMIC_RELAXED,
+        __hip_atomic_fetch_add(ready + colg, 1 + (((xcc_id() + (P.lutf_wrong_xcc ? 1 : 0)) & 15) << 8), __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -843,9 +834,6 @@ item_done:
 
 extern "C" {
 
-hipError_t isk_launch_lut_repair(const DevParams* P, int ncols, const float* joined, const float* cost_T, float* lutT,
-                                 hipStream_t stream); /* is_k_prepare.hip */
-
 /* NVR = 64-lane loads per lutT row; 0 = the shape cannot use this kernel */
 static int isf_nvr(const DevParams* P) {
     if (P->D <= 128) return 2;
@@ -881,94 +869,55 @@ hipError_t isk_set_lds_unary_fast(const DevParams* P) {
     if (w > bb) bb = w;
     const int b = (int)bb;
     hipError_t e = hipSuccess;
-#define ISF_SET(INV, NVR)                                                                         \
-    if (e == hipSuccess)                                                                          \
-    e = hipFuncSetAttribute((const void*)k_dp_unary_fast<INV, NVR>,                               \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, b);                       \
-    if (e == hipSuccess)                                                                          \
-    e = hipFuncSetAttribute((const void*)k_dp_unary_fast<INV, NVR, true>,                         \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, b);                       \
-    /* (the LUTF and REPAIR forms of the windowed launch: same LDS layout, bounded by b) */        \
-    if (e == hipSuccess)                                                                          \
-    e = hipFuncSetAttribute((const void*)k_dp_unary_fast<INV, NVR, true, true>,                   \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, b);                       \
-    if (e == hipSuccess)                                                                          \
-    e = hipFuncSetAttribute((const void*)k_dp_unary_fast<INV, NVR, true, false, true>,            \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, b)
-    if (nvr == 2) { ISF_SET(true, 2); ISF_SET(false, 2); } else { ISF_SET(true, 4); ISF_SET(false, 4); }
+    /* (the LUTF and REPAIR forms of the windowed launch: same LDS layout, bounded by b) */
+#define ISF_SET(...) \
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_dp_unary_fast<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, b)
+#define ISF_SET_ALL(INV, NVR) ISF_SET(INV, NVR); ISF_SET(INV, NVR, true); ISF_SET(INV, NVR, true, true); ISF_SET(INV, NVR, true, false, true)
+    if (nvr == 2) { ISF_SET_ALL(true, 2); ISF_SET_ALL(false, 2); } else { ISF_SET_ALL(true, 4); ISF_SET_ALL(false, 4); }
+#undef ISF_SET_ALL
 #undef ISF_SET
     return e;
 }
 
-/* 1 when this call's LUT units run inside the DP launch (LUTF): every tile windowed in ONE launch of 4-wave
- * workgroups, 1, 2 or 4 units per column (a LUT block is four waves). */
-int isk_unary_uses_fused_lut(const DevParams* P, int ncols) {
-    const int fnb = (P->D + 63) / 64;
-    if (P->knob_lut_fused == 0 || P->lut_ready == nullptr || P->lutf_bad == nullptr || ISF_WIN_WAVES != 4 ||
-        (fnb != 1 && fnb != 2 && fnb != 4))
-        return 0;
-    if (isk_unary_fast_chunk_rows(P) == 0) return 0;
-    if (!IS_P1_WINDOWED(P->D) || P->win_lo == nullptr) return 0;
-    if (!(P->knob_win_tiles >= 0 || ncols >= ISF_WIN_MIN_COLS)) return 0;
-    if (P->win_tiles < P->ntiles) return 0;
-    /* by itself only where it pays (frames/s fused | prepare launch at 1 / 4 / 8 / 12 / 16 / 64 frames per call: 4730 |
-     * 6240, 7070 | 7100, 9300 | 9060, 9930 | 9440, 9610 | 9100, 11 030 | 10 160); IS_LUT_FUSED=1 / 2: at any size */
-    const bool by_itself = P->knob_lut_fused < 0 || P->knob_lut_fused == 3; /* (3, tests: the default policy with a wrong XCC id published) */
-    if (by_itself && (ncols < ISF_LUTF_MIN_COLS || fnb > 2)) return 0; /* (D = 256, four units per column, 32 frames of 1024x4096: 3940 | 4040) */
-    return P->knob_lut_fused >= 2 ? 2 : 1;
-}
-
-/* FAST columns of the batch; the caller runs k_dp_unary<.., false> for the generic ones. */
-hipError_t isk_launch_dp_unary_fast(const DevParams* P, int ncols, const RowRec* recs,
-                                    const float* lutT, const float* rcp, const int* vhor,
-                                    const int* col_flags, const PruneRec* prune, float* cost_table,
-                                    int32_t* index_table, unsigned long long* counters,
-                                    const float* joined, const float* cost_T, hipStream_t stream) {
-    const int nvr = isk_unary_fast_chunk_rows(P);
+/* FAST columns of the batch; the caller runs k_dp_unary<.., false> for the generic ones.  The tiles 0 .. wt - 1
+ * (plan->win_tiles) stage an fn window of IS_P1_WIN lutT columns instead of all D and run as ISF_WIN_WAVES-wave
+ * workgroups in a launch of their own: 20 instead of 52 KB of LDS per workgroup, seven 4-wave workgroups per CU instead
+ * of three 8-wave ones.  The tiles do not depend on each other: the taller (classic) ones go first.  With
+ * plan->lut_fused (every tile windowed) the LUT units run inside the windowed launch, followed by the repair launches. */
+hipError_t isk_launch_dp_unary_fast(const DevParams* P, const CallPlan* plan, const CallBuffers* b,
+                                    hipStream_t stream) {
+    const int ncols = plan->ncols, nvr = plan->unary_nvr, wt = plan->win_tiles;
     const int groups = (ncols + 7) / 8;
-    /* The tiles 0 .. wt - 1 (P->win_tiles: those that start below every horizon of the batch) stage an fn window of
-     * IS_P1_WIN lutT columns instead of all D and run as ISF_WIN_WAVES-wave workgroups in a launch of their own:
-     * 20 instead of 52 KB of LDS per workgroup, seven 4-wave workgroups per CU instead of three 8-wave ones.  The
-     * tiles do not depend on each other: the taller (classic) ones go first. */
-    int wt = 0;
-    if (IS_P1_WINDOWED(P->D) && P->win_lo != nullptr && (P->knob_win_tiles >= 0 || ncols >= ISF_WIN_MIN_COLS))
-        wt = P->win_tiles < P->ntiles ? P->win_tiles : P->ntiles;
     const int nw_win = ISF_WIN_WAVES;
     const size_t lds = isk_unary_fast_lds_bytes(P, nvr);
     /* LUTF: 8 LUT blocks + cpb 8 ntiles DP blocks per super-group of cpb = 4 / fn_blocks column groups */
     unsigned fused_grid = 0;
-    if (P->lut_fused) {
-        if (wt < P->ntiles) return hipErrorInvalidValue;
+    if (plan->lut_fused) {
         const int fnb = (P->D + 63) / 64, cpb = 4 / fnb;
         const int nSG = (groups + cpb - 1) / cpb;
         fused_grid = (unsigned)nSG * (8u + (unsigned)(cpb * 8 * P->ntiles));
     }
     const size_t lds_win = isf_lds_bytes(P, nvr, nw_win, true);
-#define ISF_LAUNCH(INV, NVR)                                                                      \
-    do {                                                                                          \
-        if (wt < P->ntiles)                                                                       \
-            hipLaunchKernelGGL((k_dp_unary_fast<INV, NVR>), dim3(groups * 8 * (P->ntiles - wt)),  \
-                               dim3(ISF_THREADS), lds, stream, *P,                                 \
-                               ncols, recs, lutT, rcp, vhor, col_flags, prune, cost_table, index_table, \
-                               counters, joined, cost_T, wt, P->ntiles - wt, nullptr);            \
-        if (wt > 0 && P->lut_fused) {                                                             \
-            hipLaunchKernelGGL((k_dp_unary_fast<INV, NVR, true, true>), dim3(fused_grid),         \
-                               dim3(nw_win * 64), lds_win, stream, *P,                             \
-                               ncols, recs, lutT, rcp, vhor, col_flags, prune, cost_table, index_table, \
-                               counters, joined, cost_T, 0, wt, nullptr);                         \
-            /* the repair launches: they leave at once unless a workgroup above set lutf_bad */      \
-            const hipError_t er = isk_launch_lut_repair(P, ncols, joined, cost_T, const_cast<float*>(lutT), stream); \
-            if (er != hipSuccess) return er;                                                      \
-            hipLaunchKernelGGL((k_dp_unary_fast<INV, NVR, true, false, true>),                    \
-                               dim3(groups * 8 * wt < 1536 ? groups * 8 * wt : 1536),              \
-                               dim3(nw_win * 64), lds_win, stream, *P,                             \
-                               ncols, recs, lutT, rcp, vhor, col_flags, prune, cost_table, index_table, \
-                               nullptr, joined, cost_T, 0, wt, P->lutf_bad);                      \
-        } else if (wt > 0)                                                                        \
-            hipLaunchKernelGGL((k_dp_unary_fast<INV, NVR, true>), dim3(groups * 8 * wt),          \
-                               dim3(nw_win * 64), lds_win, stream, *P,                             \
-                               ncols, recs, lutT, rcp, vhor, col_flags, prune, cost_table, index_table, \
-                               counters, joined, cost_T, 0, wt, nullptr);                         \
+#define ISF_ARGS(COUNTERS) \
+    ncols, b->recs, b->lutT, b->rcp, b->vhor, b->col_flags, b->prune, b->cost_table, b->index_table, COUNTERS, b->joined, \
+        b->cost_T
+#define ISF_LAUNCH(INV, NVR)                                                                                         \
+    do {                                                                                                             \
+        if (wt < P->ntiles)                                                                                          \
+            hipLaunchKernelGGL((k_dp_unary_fast<INV, NVR>), dim3(groups * 8 * (P->ntiles - wt)), dim3(ISF_THREADS),  \
+                               lds, stream, *P, ISF_ARGS(b->counters), wt, P->ntiles - wt, nullptr);                 \
+        if (wt > 0 && plan->lut_fused) {                                                                             \
+            hipLaunchKernelGGL((k_dp_unary_fast<INV, NVR, true, true>), dim3(fused_grid), dim3(nw_win * 64),         \
+                               lds_win, stream, *P, ISF_ARGS(b->counters), 0, wt, nullptr);                          \
+            /* the repair launches: they leave at once unless a workgroup above set lutf_bad */                      \
+            const hipError_t er = isk_launch_lut_repair(P, ncols, b->joined, b->cost_T, b->lutT, stream);            \
+            if (er != hipSuccess) return er;                                                                         \
+            hipLaunchKernelGGL((k_dp_unary_fast<INV, NVR, true, false, true>),                                       \
+                               dim3(groups * 8 * wt < 1536 ? groups * 8 * wt : 1536), dim3(nw_win * 64), lds_win,    \
+                               stream, *P, ISF_ARGS(nullptr), 0, wt, P->lutf_bad);                                   \
+        } else if (wt > 0)                                                                                           \
+            hipLaunchKernelGGL((k_dp_unary_fast<INV, NVR, true>), dim3(groups * 8 * wt), dim3(nw_win * 64), lds_win, \
+                               stream, *P, ISF_ARGS(b->counters), 0, wt, nullptr);                                   \
     } while (0)
     if (P->invalid >= 0) {
         if (nvr == 2) ISF_LAUNCH(true, 2); else ISF_LAUNCH(true, 4);
@@ -976,6 +925,7 @@ hipError_t isk_launch_dp_unary_fast(const DevParams* P, int ncols, const RowRec*
         if (nvr == 2) ISF_LAUNCH(false, 2); else ISF_LAUNCH(false, 4);
     }
 #undef ISF_LAUNCH
+#undef ISF_ARGS
     return hipGetLastError();
 }
 

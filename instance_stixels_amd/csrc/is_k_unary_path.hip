@@ -190,16 +190,13 @@ __global__ __launch_bounds__(64) void k_unary_path(const DevParams P, int ncols,
 
 extern "C" {
 
-hipError_t isk_launch_unary_path(const DevParams* P, int ncols, const RowRec* recs, const float* lutT,
-                                 const float* rcp, const int* vhor, const int* col_flags, const PruneRec* prune,
-                                 float* cost_table, int32_t* index_table, int* bad, int force_bad,
-                                 hipStream_t stream) {
-    if (P->invalid >= 0)
-        hipLaunchKernelGGL(k_unary_path<true>, dim3(ncols), dim3(64), 0, stream, *P, ncols, recs, lutT, rcp, vhor,
-                           col_flags, prune, cost_table, index_table, bad, force_bad);
-    else
-        hipLaunchKernelGGL(k_unary_path<false>, dim3(ncols), dim3(64), 0, stream, *P, ncols, recs, lutT, rcp, vhor,
-                           col_flags, prune, cost_table, index_table, bad, force_bad);
+hipError_t isk_launch_unary_path(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream) {
+#define IS_LAUNCH_PATH(INV)                                                                                        \
+    hipLaunchKernelGGL(k_unary_path<INV>, dim3(plan->ncols), dim3(64), 0, stream, *P, plan->ncols, b->recs, b->lutT, \
+                       b->rcp, b->vhor, b->col_flags, b->prune, b->cost_table, b->index_table, b->path_bad,         \
+                       plan->unary_force_bad)
+    if (P->invalid >= 0) IS_LAUNCH_PATH(true); else IS_LAUNCH_PATH(false);
+#undef IS_LAUNCH_PATH
     return hipGetLastError();
 }
 

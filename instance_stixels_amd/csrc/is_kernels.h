@@ -35,23 +35,13 @@
 
 #include "instance_stixels_core.h"
 #include "is_device.h"
+#include "is_launch.h"
 #include "is_numerics.h"
 
 #define IS_INF (__builtin_inff())
 
 typedef const __attribute__((address_space(4))) RowRec* crec_t;     /* scalar-load view */
 typedef const __attribute__((address_space(4))) PriorRec* cprior_t;
-
-/* workgroup LDS sizes (defined next to the kernels that use them) */
-extern "C" {
-size_t isk_prepare_lds_bytes(const DevParams* P);
-size_t isk_unary_lds_bytes(const DevParams* P);
-size_t isk_pairwise_lds_bytes(const DevParams* P, int nwaves);
-size_t isk_phase2_lds_bytes(const DevParams* P);
-size_t isk_unary_fast_lds_bytes(const DevParams* P, int chunk_rows);
-int isk_unary_fast_chunk_rows(const DevParams* P);
-hipError_t isk_set_lds_unary_fast(const DevParams* P);
-}
 
 /* ====================================================================================== */
 /* Segment evaluation shared by both DP kernels                                            */

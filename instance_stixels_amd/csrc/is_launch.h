@@ -1,0 +1,190 @@
+/*
+ * is_launch.h -- the internal launch interface of the gfx950 column-DP core: every isk_* function, declared once and
+ * included by every file that defines or calls one (a drifted definition does not compile).  None is public ABI.
+ * plan_call (is_core.hip) makes every launch decision of a DP call; the DP launchers launch what its CallPlan says.
+ */
+#ifndef IS_LAUNCH_H_
+#define IS_LAUNCH_H_
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "instance_stixels_core.h"
+#include "is_device.h"
+
+/* ---- size thresholds of plan_call (columns of the call = n_images * realcols); -D overrides ---- */
+#ifndef IS_UNARY_PATH_MIN_COLS
+#define IS_UNARY_PATH_MIN_COLS 2048 /* the unary DP of the visited rows only (k_unary_path), see IS_UNARY_PATH in plan_call */
+#endif
+#ifndef ISF_WIN_MIN_COLS
+#define ISF_WIN_MIN_COLS 0 /* columns per call from which the unary DP stages fn windows.  Round 4: 2048 (frames/s windowed | classic at batch 2: 6470 | 6050, 4: 6090 | 6350, 8: 6890 | 6680, 16: 7480 | 7010, 32: 7860 | 7200); with the diagonal blocks in quarters (round 5) the windowed launch wins at every size: batch 1: 6290 | 5220, 2: 8180 | 6140, 4: 7110 | 6380, 8: 9190 | 9070 */
+#endif
+#ifndef ISF_WIN_WAVES
+#define ISF_WIN_WAVES 4 /* waves per workgroup of the windowed unary tiles (the fused LUT units need 4: a LUT block) */
+#endif
+#ifndef ISF_LUTF_MIN_COLS
+#define ISF_LUTF_MIN_COLS 2048 /* columns per call from which the LUT units run inside the unary DP launch by default (frames/s fused | prepare launch at 1 / 4 / 8 / 12 / 16 / 64 frames per call: 4730 | 6240, 7070 | 7100, 9300 | 9060, 9930 | 9440, 9610 | 9100, 11 030 | 10 160) */
+#endif
+#ifndef IS_P1_WIN_MIN_COLS
+#define IS_P1_WIN_MIN_COLS 4096 /* columns per call from which pairwise phase 1 stages fn windows: a call of a few frames does not fill the chip, there the eight waves per column are the parallelism (one frame 1.57 ms classic, 1.63 ms windowed; frames/s at batch 4 / 8 / 16 / 32: 1461 / 2068 / 2795 / 3178 classic, 1424 / 2010 / 2798 / 3269 windowed) */
+#endif
+#ifndef IS_PW_SPLIT_MAX_COLS
+#define IS_PW_SPLIT_MAX_COLS 512 /* up to that many columns: two phase-1 workgroups per (column, tile) (measured on MI355X, frames/s of one / two 256-column frames per call: 1 workgroup per (column, tile) 540 / 903, 2: 587 / 931, 3: 584 / -, 4: 561 / -) */
+#endif
+static_assert(2 * IS_PW_SPLIT_MAX_COLS <= IS_PW_SPLIT_TARGET_WGS && IS_PW_MAX_SPLIT >= 2,
+              "the context reserves IS_PW_SPLIT_TARGET_WGS partial-minima slots for the split phase 1");
+#define IS_PAIRWISE_SPLIT_MIN_COLS 1024 /* columns per group before the pairwise DP uses one more stream */
+#define IS_PAIRWISE_MAX_GROUPS 3       /* column groups (streams of the context) of the pairwise DP; IS_PW_GROUPS overrides.  The latency-bound phase 2 of one group runs beside the launches of the others.  Round 5, frames/s with 1 / 2 / 3 / 4 groups: batch 64 4116 / 4283 / 4333 / 4227, batch 32 3776 / 3909 / 4009 / 3992, batch 16 2937 / 3120 / 3147 / 3219 (profiles/r05_ab_groups.log).  Beside a PIPELINED RCCL gather of the previous step's output (bench.py --gpus N, parallel.py) the groups cost 5 % instead (round 4: 3680 against 3860): such callers create their context with IS_PW_GROUPS=1, as bench.py does */
+#define IS_P2_SPLIT_MAX_COLS 2048     /* up to eight 2048-px frames: phase 2 of the pairwise DP as chain + evaluator waves per column (k_pw_phase2s): it shortens the serial chain of a column (one frame: 82 -> 74 us per tile) but spends four wave slots per column, which costs throughput at large batches (batch 64: 32.7 vs 25.4 ms per step).  IS_P2_SPLIT=0/1 overrides. */
+#define IS_BACKTRACE_STAGE_MAX_COLS 2048 /* up to eight 2048-px frames: the back-trace chases in LDS */
+#ifndef IS_BACKTRACE_TWO_MIN_COLS
+#define IS_BACKTRACE_TWO_MIN_COLS 8192 /* two columns per wave: more one-column waves than the chip holds at once */
+#endif
+
+/* ---- one DP call ---- */
+
+enum { IS_P2_ONE = 0, IS_P2_SPLIT = 1, IS_P2_TWO = 2 };       /* k_pw_phase2 | k_pw_phase2s | k_pw_phase2x + generic */
+enum { IS_BT_PLAIN = 0, IS_BT_STAGED = 1, IS_BT_TWO = 2 };    /* k_backtrace<false> | <true> | <false, true> */
+
+/* Every launch decision of one is_compute call (plan_call, is_core.hip). */
+struct CallPlan {
+    int ncols;         /* columns of the call */
+    int pairwise;
+    int nwaves;        /* waves per DP workgroup of the classic tiles */
+    int win_tiles;     /* the DP tiles 0 .. win_tiles - 1 stage an fn window (IS_P1_WIN); <= ntiles */
+    /* unary */
+    int unary_walk;    /* 1: k_unary_path + the generic columns + the repair launch; 0: the tile path */
+    int unary_force_bad; /* (tests, IS_UNARY_PATH=3) every walk distrusts itself: the repair launch runs */
+    int unary_nvr;     /* tile path: k_dp_unary_fast<., NVR> for the FAST columns; 0 = k_dp_unary for every column */
+    int lut_fused;     /* 1: the LUT units run inside the unary DP launch (LUTF) */
+    /* prepare */
+    int prepare_lut;   /* 1: k_prepare_fused (records + object LUT); 0: k_prepare_columns (records only) */
+    /* pairwise */
+    int groups;        /* column groups, one stream each */
+    int nsplit;        /* phase-1 workgroups per (column, tile) */
+    int phase2;        /* IS_P2_* */
+    /* back-trace */
+    int backtrace;     /* IS_BT_* */
+};
+
+struct StepRec;
+
+/* The device buffers of one DP call: the context's scratch and the caller's tables. */
+struct CallBuffers {
+    const float* joined;
+    const int32_t* seg;
+    const float* ground;
+    const int* vhor;
+    const float* cost_T;
+    const float* odr;
+    const float* rcp;
+    RowRec* recs;
+    float* lutT;
+    int* col_flags;
+    float* sv;
+    PruneRec* prune;
+    int* n_generic;
+    int* path_bad;
+    PriorRec* priors;
+    StepRec* steps;
+    float* part_cost;
+    int* part_idx;
+    float* blksum;
+    float* t8row;
+    float* cost_table;
+    int32_t* index_table;
+    unsigned long long* counters; /* null unless the evaluation counters are on */
+    int* inst_cnt;             /* null unless instance outputs are requested */
+};
+
+extern "C" {
+
+/* is_core.hip */
+int isk_fail(int code, const char* msg);
+
+/* is_k_prepare.hip */
+size_t isk_prepare_lds_bytes(const DevParams* P);
+hipError_t isk_set_lds_prepare(const DevParams* P);
+hipError_t isk_launch_prepare(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream);
+hipError_t isk_launch_priors(const DevParams* P, const float* ground, PriorRec* priors, int n_images,
+                             hipStream_t stream);
+hipError_t isk_launch_lut_repair(const DevParams* P, int ncols, const float* joined, const float* cost_T, float* lutT,
+                                 hipStream_t stream);
+
+/* is_k_unary.hip */
+size_t isk_unary_lds_bytes(const DevParams* P);
+hipError_t isk_set_lds_unary(const DevParams* P);
+hipError_t isk_launch_dp_unary(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream);
+int isk_debug_occupancy(const DevParams* P, int nwaves);
+
+/* is_k_unary_fast.hip */
+size_t isk_unary_fast_lds_bytes(const DevParams* P, int nvr);
+int isk_unary_fast_chunk_rows(const DevParams* P);
+hipError_t isk_set_lds_unary_fast(const DevParams* P);
+hipError_t isk_launch_dp_unary_fast(const DevParams* P, const CallPlan* plan, const CallBuffers* b,
+                                    hipStream_t stream);
+
+/* is_k_unary_path.hip */
+hipError_t isk_launch_unary_path(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream);
+
+/* is_k_pairwise.hip */
+size_t isk_pairwise_lds_bytes(const DevParams* P, int nwaves);
+size_t isk_phase2_lds_bytes(const DevParams* P);
+size_t isk_phase2x_lds_bytes(const DevParams* P);
+size_t isk_phase2s_lds_bytes(const DevParams* P);
+hipError_t isk_set_lds_pairwise(const DevParams* P, int nwaves);
+hipError_t isk_launch_dp_pairwise(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream,
+                                  const hipStream_t* aux, hipEvent_t ev_fork, const hipEvent_t* ev_join);
+
+/* is_k_backtrace.hip */
+size_t isk_backtrace_lds_bytes(const DevParams* P, int form);
+hipError_t isk_set_lds_backtrace(const DevParams* P);
+hipError_t isk_launch_backtrace(const DevParams* P, const CallPlan* plan, const CallBuffers* b, is_section* sections,
+                                hipStream_t stream);
+hipError_t isk_launch_compact(const DevParams* P, int n_images, const is_section* sections, const int* inst_cnt,
+                              const is_instance_buffers* d_tbl, hipStream_t stream);
+
+/* is_k_cluster.hip */
+hipError_t isk_launch_cluster(int n_slots, float eps, int min_pts, int n_images, const is_instance_buffers* d_tbl,
+                              const is_instance_buffers* one, int32_t* scratch, hipStream_t stream);
+
+/* is_k_frontend.hip */
+hipError_t isk_launch_join(const float* big, float* joined, int H, int W, int C, int step, int margin, int median,
+                           float invalid, int n_images, hipStream_t stream);
+hipError_t isk_launch_flip_and_pad(const float* in, int32_t* out, int n, int CH, int Hs, int Ws, int P2S,
+                                   hipStream_t stream);
+hipError_t isk_launch_vdisparity(const float* disparity, int* vdisp, int* maximum, uint8_t* binary, int rows,
+                                 int cols, int max_dis, float threshold, hipStream_t stream);
+
+/* is_k_pack.hip */
+hipError_t isk_launch_pack(const is_section* sections, int n_columns, int S, int32_t* counts, int32_t* offsets,
+                           is_section* packed, hipStream_t stream);
+hipError_t isk_launch_unpack(const int32_t* counts, int32_t* offsets, const is_section* packed, int n_columns, int S,
+                             is_section* sections, hipStream_t stream);
+
+/* is_k_road.hip */
+int isk_road_sort_max(void);
+int isk_road_counters(void);
+hipError_t isk_set_lds_road_hough(int bytes);
+hipError_t isk_launch_road_vdisparity(const float* disparity, int* vdisp, uint8_t* binary, int* counters, int* points,
+                                      int n_images, int rows, int cols, int max_dis, float threshold,
+                                      hipStream_t stream);
+hipError_t isk_launch_road_hough(const int* points, const int* counters, int* ncand, const float* tab, int2* cand,
+                                 float* lines, int* votes, int* total, int* overflow, int n_images, int n_cells,
+                                 int numangle, int numrho, int band, int threshold, int cap, int max_lines, float rho,
+                                 float theta, hipStream_t stream);
+
+/* is_k_render.hip */
+int isk_render_scatter_images(void);
+hipError_t isk_launch_section_instance(const is_instance_buffers* per_image, int n_images, int first_image,
+                                       int realcols, int max_sections, int32_t* out, hipStream_t stream);
+hipError_t isk_launch_render(const is_render_args* r, const uint8_t* table, int n_classes, hipStream_t stream);
+
+/* is_k_instance_eval.hip */
+hipError_t isk_launch_instance_overlap(const is_instance_overlap_args* r, hipStream_t stream);
+hipError_t isk_launch_pack_overlap(const is_overlap_record* records, const int32_t* n_records, int n_images,
+                                   int capacity, is_overlap_record* packed, hipStream_t stream);
+
+} /* extern "C" */
+
+#endif /* IS_LAUNCH_H_ */
