@@ -88,18 +88,18 @@ private:
     int m_device = -1;      /* requested (SetDevice) */
     int m_ctx_device = -1;  /* where the buffers of the last Initialize() live */
     void* m_stream = nullptr;
-    pixel_t* d_disparity = nullptr;
-    int* d_vDisp = nullptr;
-    int* d_maximum = nullptr;
-    uint8_t* d_vDispBinary = nullptr;
+    DeviceArray<pixel_t> d_disparity;
+    DeviceArray<int> d_vDisp;
+    DeviceArray<int> d_maximum;
+    DeviceArray<uint8_t> d_vDispBinary;
     std::vector<uint8_t> m_vDisp;
     /* ComputeBatch */
     is_road_ctx* m_batch_ctx = nullptr; /* scratch for m_batch_cap frames */
     int m_batch_cap = 0;
     int m_batch_lines = 256, m_batch_candidates = 4096;
     int m_batch_out_lines = 0;          /* max_lines the output blocks below were sized for */
-    char* d_batch_out = nullptr;        /* [cap][lines][2] float lines, [cap] totals, [cap] overflow flags */
-    char* h_batch_out = nullptr;        /* pinned twin of d_batch_out */
+    DeviceArray<char> d_batch_out;      /* [cap] totals, [cap] overflow flags, [cap][lines][2] float lines */
+    PinnedArray<char> h_batch_out;      /* pinned twin of d_batch_out */
     int m_batch_fallbacks = 0;
     std::vector<uint8_t> m_batch_binary;
 

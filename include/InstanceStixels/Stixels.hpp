@@ -165,7 +165,13 @@ private:
     float ComputeObjectDisparityRange(const float previous_mean) const;
     float FastLog(float v) const;
     void FillHeader(StixelsData& d, float alpha_ground, int vhor_lib) const;
-    void EnsurePackBuffers();
+    /* the ground models of frames 0 .. n_images-1 end to end ([n][rows] each) and their library-convention vhor */
+    void BatchGround(int n_images, const RoadParameters* road, GroundModel& batch, std::vector<int>& vhor) const;
+    /* packed Sections (counts[frame * realcols + column] per column, in order) into the fixed-stride sections of
+     * the frames in `out`, each column closed by a terminator */
+    void ScatterSections(const int32_t* counts, const Section* packed, size_t total,
+                         std::vector<StixelsData>& out) const;
+    void ReservePackBuffers();
     is_instance_buffers InstanceBuffers(int image = 0) const;
     GroundModel m_ground; /* per-frame ground model, storage reused between frames */
     /* the road parameters m_ground was computed for: a frame with the same parameters (a fixed
@@ -176,61 +182,57 @@ private:
 
     /* device (owned between Initialize and Finish, Stixels.cu:53-74, 136-163) */
     is_ctx* m_ctx = nullptr;
-    pixel_t* d_disparity = nullptr;
-    pixel_t* d_disparity_big = nullptr;
-    int32_t* d_segmentation = nullptr;
-    Section* d_stixels = nullptr;
-    float* d_instance_centerofmass = nullptr;
-    int32_t* d_instance_indices = nullptr;
-    uint8_t* d_instance_core_candidates = nullptr;
-    int32_t* d_instances_per_class = nullptr;
+    DeviceArray<pixel_t> d_disparity;
+    DeviceArray<pixel_t> d_disparity_big;
+    DeviceArray<int32_t> d_segmentation;
+    DeviceArray<float> d_instance_centerofmass;
+    DeviceArray<int32_t> d_instance_indices;
+    DeviceArray<uint8_t> d_instance_core_candidates;
     /* (every instance array: one slice per frame of the batch) */
-    int32_t* d_instance_labels = nullptr;  /* the reference's d_instance_labels, Stixels.cu:66-68 */
-    int32_t* d_instance_packed = nullptr;  /* [1 + 3*classes*realcols*max_sections], see is_instance_buffers */
+    DeviceArray<int32_t> d_instance_labels;  /* the reference's d_instance_labels, Stixels.cu:66-68 */
+    DeviceArray<int32_t> d_instance_packed;  /* [1 + 3*classes*realcols*max_sections], see is_instance_buffers */
     /* pinned host mirrors: Compute() ends with ONE stream synchronisation */
-    Section* h_stixels = nullptr;
+    PinnedArray<Section> h_stixels;
     /* One device block: header rows (the per-class candidate counts, d_instances_per_class) in
-     * front of the sections (d_stixels).  Compute() fetches the header and the first
-     * m_head_sections sections of every column with ONE pitched copy into h_stixels_head; a column
-     * without a terminator among them (rare) makes it fetch the complete array. */
-    Section* d_stixels_block = nullptr;
-    Section* h_stixels_head = nullptr;
+     * front of the sections (d_stixels), both aliases into it set by InitializeBatch.  Compute()
+     * fetches the header and the first m_head_sections sections of every column with ONE pitched
+     * copy into h_stixels_head; a column without a terminator among them (rare) makes it fetch the
+     * complete array. */
+    DeviceArray<Section> d_stixels_block;
+    Section* d_stixels = nullptr;
+    int32_t* d_instances_per_class = nullptr;
+    PinnedArray<Section> h_stixels_head;
     int m_header_rows = 0;
     int m_head_sections = 0;
-    int32_t* h_instance_head = nullptr;    /* [max_batch][8 per-class counts] */
+    PinnedArray<int32_t> h_instance_head;    /* [max_batch][8 per-class counts] */
     /* ComputeBatchGather: the packed payload of this rank and, on the destination, the landing buffers
      * (allocated on first use, grown on demand, released by Finish) */
-    int32_t* d_pack_counts = nullptr;
-    int32_t* d_pack_offsets = nullptr;
-    Section* d_pack_sections = nullptr;
-    int32_t* d_all_counts = nullptr;
-    Section* d_all_packed = nullptr;
-    Section* d_all_sections = nullptr;
-    size_t m_all_columns_cap = 0, m_all_packed_cap = 0;
+    DeviceArray<int32_t> d_pack_counts;
+    DeviceArray<int32_t> d_pack_offsets;
+    DeviceArray<Section> d_pack_sections;
+    DeviceArray<int32_t> d_all_counts;
+    DeviceArray<Section> d_all_packed;
     /* ComputeBatch: the same packed payload copied to the host in two pinned pieces (offsets, used sections) */
-    int32_t* h_pack_offsets = nullptr;
-    Section* h_pack_sections = nullptr;
-    size_t m_h_pack_cap = 0; /* sections h_pack_sections holds */
-    int32_t* h_all_counts = nullptr; /* ComputeBatchGather on dst: the per-column counts of all ranks (pinned) */
-    size_t m_h_all_counts_cap = 0;
-    int32_t* h_instance_packed = nullptr;
+    PinnedArray<int32_t> h_pack_offsets;
+    PinnedArray<Section> h_pack_sections;
+    PinnedArray<int32_t> h_all_counts; /* ComputeBatchGather on dst: the per-column counts of all ranks */
+    PinnedArray<int32_t> h_instance_packed;
     /* RenderBatch: what the last Compute() / ComputeBatch() left in d_stixels (0 frames: nothing renderable --
      * before any compute, and after ComputeBatchGather, which reuses d_stixels for its shard) and whether its
      * cluster labels are there; the per-section label map and the per-frame results (allocated on first use) */
     int m_render_images = 0;
     bool m_render_instances = false;
-    int32_t* d_section_instance = nullptr; /* [max_batch][realcols][max_sections] */
-    char* d_render_results = nullptr;      /* [max_batch] double | [max_batch] int64 | [max_batch] int32 */
-    char* h_render_results = nullptr;
+    DeviceArray<int32_t> d_section_instance; /* [max_batch][realcols][max_sections] */
+    DeviceArray<char> d_render_results;      /* [max_batch] double | [max_batch] int64 | [max_batch] int32 */
+    PinnedArray<char> h_render_results;
     /* InstanceOverlapBatch: [max_batch][capacity] records, then n_records | overflow per frame, the packed records
      * (device and pinned host, allocated on first use, grown with the capacity) */
     int m_overlap_capacity = 4096;
-    size_t m_overlap_cap_alloc = 0;
-    is_overlap_record* d_overlap_records = nullptr;
-    is_overlap_record* d_overlap_packed = nullptr;
-    int32_t* d_overlap_header = nullptr;   /* [max_batch] n_records | [max_batch] overflow */
-    int32_t* h_overlap_header = nullptr;
-    is_overlap_record* h_overlap_packed = nullptr;
+    DeviceArray<is_overlap_record> d_overlap_records;
+    DeviceArray<is_overlap_record> d_overlap_packed;
+    DeviceArray<int32_t> d_overlap_header;   /* [max_batch] n_records | [max_batch] overflow */
+    PinnedArray<int32_t> h_overlap_header;
+    PinnedArray<is_overlap_record> h_overlap_packed;
     /* every device operation of the object runs on this stream (an ordinary stream: it still
      * synchronises with work the caller queued on the legacy NULL stream, like the reference's
      * default-stream code; on the NULL stream itself the auxiliary streams of the core never

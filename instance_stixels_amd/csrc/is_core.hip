@@ -57,7 +57,21 @@ struct Knobs {
     int unary_path;  /* IS_UNARY_PATH, see plan_call */
 };
 
+/* Every device block of a context, recorded by alloc(): the context's destroy frees the record, so a buffer added
+ * later cannot be left out of it.  (Zero-initialised by the context's calloc.) */
+struct OwnedBlocks {
+    void* ptr[32];
+    int n;
+    template <typename T> hipError_t alloc(T** p, size_t bytes) {
+        const hipError_t e = n < 32 ? hipMalloc((void**)p, bytes) : hipErrorInvalidValue; /* (full: enlarge ptr) */
+        if (e == hipSuccess) ptr[n++] = *p;
+        return e;
+    }
+    void free_all() { while (n > 0) (void)hipFree(ptr[--n]); }
+};
+
 struct is_ctx {
+    OwnedBlocks owned;       /* every device block below (ALLOC in ctx_init) */
     is_stixel_params params;
     DevParams dp;
     Knobs knobs;
@@ -313,7 +327,7 @@ static int ctx_init(is_ctx* c, const is_stixel_params* p, const float* obj_cost_
     size_t total = 0;
 #define ALLOC(ptr, bytes)                                     \
     do {                                                      \
-        HIP_TRY(hipMalloc((void**)&(ptr), (bytes)));          \
+        HIP_TRY(c->owned.alloc(&(ptr), (bytes)));             \
         total += (bytes);                                     \
     } while (0)
     ALLOC(c->d_obj_cost_lut, sizeof(float) * D * D);
@@ -415,11 +429,8 @@ int is_ctx_destroy(is_ctx* c) {
     if (!c) return IS_OK;
     DeviceScope scope(c->device);
     (void)hipDeviceSynchronize();
-    (void)hipFree(c->d_obj_cost_lut); (void)hipFree(c->d_odr); (void)hipFree(c->d_rcp); (void)hipFree(c->d_col_flags); (void)hipFree(c->d_prune); (void)hipFree(c->d_n_generic); (void)hipFree(c->d_stage);
-    (void)hipFree(c->d_recs); (void)hipFree(c->d_lutT); (void)hipFree(c->d_priors); (void)hipFree(c->d_steps); (void)hipFree(c->d_part_cost); (void)hipFree(c->d_part_idx); (void)hipFree(c->d_sv); (void)hipFree(c->d_blksum); (void)hipFree(c->d_t8row); (void)hipFree(c->dp.win_lo); (void)hipFree(c->dp.lut_ready); (void)hipFree(c->dp.lutf_bad); (void)hipFree(c->d_path_bad);
+    c->owned.free_all();
     if (c->h_lutf_repairs) (void)hipHostFree(c->h_lutf_repairs);
-    (void)hipFree(c->d_cost_table); (void)hipFree(c->d_index_table); (void)hipFree(c->d_cluster_scratch);
-    (void)hipFree(c->d_inst_cnt); (void)hipFree(c->d_counters);
     for (int i = 0; i < IS_STAGE_SLOTS; i++) {
         if (c->h_stage[i]) (void)hipHostFree(c->h_stage[i]);
         if (c->staging_free[i]) (void)hipEventDestroy(c->staging_free[i]);
@@ -504,6 +515,7 @@ int is_road_vdisparity(const float* d_disparity, int rows, int cols, int max_dis
 
 /* ---- batched road estimation (is_k_road.hip) ---- */
 struct is_road_ctx {
+    OwnedBlocks owned;          /* every device block below */
     int device, rows, cols, max_dis, max_batch;
     int numangle, numrho, band; /* Hough accumulator (numangle + 2) x (numrho + 2); angles per workgroup */
     float rho, theta;
@@ -518,9 +530,7 @@ struct is_road_ctx {
 };
 
 static void road_ctx_free(is_road_ctx* c) {
-    (void)hipFree(c->d_tab); (void)hipFree(c->d_vdisp); (void)hipFree(c->d_binary);
-    (void)hipFree(c->d_counters); (void)hipFree(c->d_points); (void)hipFree(c->d_ncand);
-    (void)hipFree(c->d_cand);
+    c->owned.free_all();
     free(c);
 }
 
@@ -563,16 +573,18 @@ int is_road_ctx_create(is_road_ctx** out, int rows, int cols, int max_dis, int m
     c->numangle = numangle; c->numrho = numrho; c->band = band; c->rho = rho; c->theta = theta;
     const size_t cells = (size_t)rows * max_dis;
     const size_t B = (size_t)max_batch;
-    bool ok = hipMalloc((void**)&c->d_tab, sizeof(float) * 2 * numangle) == hipSuccess &&
-              hipMalloc((void**)&c->d_vdisp, sizeof(int) * B * cells) == hipSuccess &&
-              hipMalloc((void**)&c->d_binary, B * cells) == hipSuccess &&
-              hipMalloc((void**)&c->d_counters, sizeof(int) * B * isk_road_counters()) == hipSuccess &&
-              hipMalloc((void**)&c->d_points, sizeof(int) * B * cells) == hipSuccess &&
-              hipMalloc((void**)&c->d_ncand, sizeof(int) * B) == hipSuccess &&
-              hipMalloc((void**)&c->d_cand, sizeof(int2) * B * IS_ROAD_MAX_CANDIDATES) == hipSuccess;
-    if (ok) ok = hipMemcpy(c->d_tab, tab, sizeof(float) * 2 * numangle, hipMemcpyHostToDevice) == hipSuccess;
+    hipError_t err = hipSuccess; /* (the first failure stops the allocations) */
+    auto alloc = [&](auto** p, size_t bytes) { if (err == hipSuccess) err = c->owned.alloc(p, bytes); };
+    alloc(&c->d_tab, sizeof(float) * 2 * numangle);
+    alloc(&c->d_vdisp, sizeof(int) * B * cells);
+    alloc(&c->d_binary, B * cells);
+    alloc(&c->d_counters, sizeof(int) * B * isk_road_counters());
+    alloc(&c->d_points, sizeof(int) * B * cells);
+    alloc(&c->d_ncand, sizeof(int) * B);
+    alloc(&c->d_cand, sizeof(int2) * B * IS_ROAD_MAX_CANDIDATES);
+    if (err == hipSuccess) err = hipMemcpy(c->d_tab, tab, sizeof(float) * 2 * numangle, hipMemcpyHostToDevice);
     free(tab);
-    if (!ok) {
+    if (err != hipSuccess) {
         (void)hipGetLastError();
         road_ctx_free(c);
         snprintf(g_err, sizeof(g_err), "is_road_ctx_create: device allocation of %zu frames failed", B);

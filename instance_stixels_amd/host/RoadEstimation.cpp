@@ -46,10 +46,10 @@ void RoadEstimation::Initialize(const float camera_center_y, const float baselin
     m_ctx_device = device;
     const DeviceGuard guard(device);
     IS_CHECK_RETURN(is_stream_create(&m_stream, 1));
-    IS_CHECK_RETURN(is_device_malloc((void**)&d_disparity, (size_t)m_cols * m_rows * sizeof(float)));
-    IS_CHECK_RETURN(is_device_malloc((void**)&d_vDisp, (size_t)m_max_dis * m_rows * sizeof(int)));
-    IS_CHECK_RETURN(is_device_malloc((void**)&d_maximum, sizeof(int)));
-    IS_CHECK_RETURN(is_device_malloc((void**)&d_vDispBinary, (size_t)m_max_dis * m_rows));
+    d_disparity.reserve((size_t)m_cols * m_rows);
+    d_vDisp.reserve((size_t)m_max_dis * m_rows);
+    d_maximum.reserve(1);
+    d_vDispBinary.reserve((size_t)m_max_dis * m_rows);
     m_is_initialized = true;
 }
 
@@ -60,22 +60,20 @@ void RoadEstimation::Finish() { /* RE.cu:84-92 */
         IS_CHECK_RETURN(is_stream_destroy(m_stream));
         m_stream = nullptr;
     }
-    IS_CHECK_RETURN(is_device_free(d_vDisp));
-    IS_CHECK_RETURN(is_device_free(d_disparity));
-    IS_CHECK_RETURN(is_device_free(d_maximum));
-    IS_CHECK_RETURN(is_device_free(d_vDispBinary));
-    d_vDisp = nullptr; d_disparity = nullptr; d_maximum = nullptr; d_vDispBinary = nullptr;
+    d_vDisp.release();
+    d_disparity.release();
+    d_maximum.release();
+    d_vDispBinary.release();
     FreeBatch();
     m_is_initialized = false;
 }
 
 void RoadEstimation::FreeBatch() { /* (under the caller's device guard) */
     IS_CHECK_RETURN(is_road_ctx_destroy(m_batch_ctx)); /* synchronises the device */
-    IS_CHECK_RETURN(is_device_free(d_batch_out));
-    IS_CHECK_RETURN(is_host_free(h_batch_out));
-    m_batch_ctx = nullptr; d_batch_out = nullptr; h_batch_out = nullptr;
-    m_batch_cap = 0;
-    m_batch_out_lines = 0;
+    d_batch_out.release();
+    h_batch_out.release();
+    m_batch_ctx = nullptr;
+    m_batch_cap = m_batch_out_lines = 0;
 }
 
 void RoadEstimation::SetBatchLimits(int max_lines, int max_candidates) {
@@ -100,23 +98,23 @@ void RoadEstimation::ComputeBatch(const pixel_t* d_im, int n_images, Stixels::Ro
         FreeBatch();
         IS_CHECK_RETURN(is_road_ctx_create(&m_batch_ctx, m_rows, m_cols, m_max_dis, cap, m_ctx_device));
         const size_t bytes = sizeof(int) * 2 * (size_t)cap + sizeof(float) * 2 * (size_t)cap * L;
-        IS_CHECK_RETURN(is_device_malloc((void**)&d_batch_out, bytes));
-        IS_CHECK_RETURN(is_host_malloc((void**)&h_batch_out, bytes));
+        d_batch_out.reserve(bytes);
+        h_batch_out.reserve(bytes);
         m_batch_cap = cap;
         m_batch_out_lines = L;
     }
     const int cap = m_batch_cap;
-    int* d_total = (int*)d_batch_out;
+    int* d_total = (int*)d_batch_out.get();
     int* d_overflow = d_total + cap;
     float* d_lines = (float*)(d_overflow + cap);
     IS_CHECK_RETURN(is_road_vdisparity_batch(m_batch_ctx, d_im, n_images, m_binThr, nullptr, nullptr, nullptr, s));
     IS_CHECK_RETURN(is_road_hough_batch(m_batch_ctx, n_images, m_HoughAccumThr, L, m_batch_candidates, d_lines,
                                         nullptr, d_total, d_overflow, s));
     const size_t bytes = sizeof(int) * 2 * (size_t)cap + sizeof(float) * 2 * (size_t)n_images * L;
-    IS_CHECK_RETURN(is_memcpy_d2h(h_batch_out, d_batch_out, bytes, s));
+    IS_CHECK_RETURN(is_memcpy_d2h(h_batch_out.get(), d_batch_out.get(), bytes, s));
     IS_CHECK_RETURN(is_stream_synchronize(s));
 
-    const int* total = (const int*)h_batch_out;
+    const int* total = (const int*)h_batch_out.get();
     const int* overflow = total + cap;
     const float* h_lines = (const float*)(overflow + cap);
     const size_t cells = (size_t)m_rows * m_max_dis;
@@ -160,16 +158,16 @@ bool RoadEstimation::ChooseLine(const std::pair<float, float>* lines, size_t n,
 bool RoadEstimation::Compute(const std::vector<pixel_t>& im) { /* RE.cu:94-102 */
     {
         const DeviceGuard guard(m_ctx_device);
-        IS_CHECK_RETURN(is_memcpy_h2d(d_disparity, im.data(), im.size() * sizeof(pixel_t), m_stream));
+        IS_CHECK_RETURN(is_memcpy_h2d(d_disparity.get(), im.data(), im.size() * sizeof(pixel_t), m_stream));
         IS_CHECK_RETURN(is_stream_synchronize(m_stream)); /* the caller's vector may be a temporary */
     }
-    return Compute(d_disparity);
+    return Compute(d_disparity.get());
 }
 
 bool RoadEstimation::Compute(pixel_t* d_im) { /* RE.cu:104-138 */
     const DeviceGuard guard(m_ctx_device); /* (d_im lives on the object's device: Stixels::SetDevice(d) + SetDevice(d)) */
-    IS_CHECK_RETURN(is_road_vdisparity(d_im, m_rows, m_cols, m_max_dis, m_binThr, d_vDisp, d_maximum,
-                                       d_vDispBinary, m_stream));
+    IS_CHECK_RETURN(is_road_vdisparity(d_im, m_rows, m_cols, m_max_dis, m_binThr, d_vDisp.get(), d_maximum.get(),
+                                       d_vDispBinary.get(), m_stream));
     float rho, theta, horizonPoint, pitch, cameraHeight, slope;
     bool ok = false;
     if (ComputeHough(rho, theta, horizonPoint, pitch, cameraHeight, slope)) {
@@ -235,7 +233,7 @@ std::vector<std::pair<float, float>> RoadEstimation::HoughLines(const uint8_t* i
 bool RoadEstimation::ComputeHough(float& rho, float& theta, float& horizonPoint, float& pitch,
                                   float& cameraHeight, float& slope) { /* RE.cu:140-176 */
     /* (called from Compute, under its device guard) */
-    IS_CHECK_RETURN(is_memcpy_d2h(m_vDisp.data(), d_vDispBinary, (size_t)m_max_dis * m_rows, m_stream));
+    IS_CHECK_RETURN(is_memcpy_d2h(m_vDisp.data(), d_vDispBinary.get(), (size_t)m_max_dis * m_rows, m_stream));
     IS_CHECK_RETURN(is_stream_synchronize(m_stream));
     const auto lines = HoughLines(m_vDisp.data(), m_rows, m_max_dis, 1.0f, kPi / 180, m_HoughAccumThr);
     for (const auto& l : lines) {

@@ -330,88 +330,45 @@ void Stixels::InitializeBatch(int max_batch) { /* Stixels.cu:43-248 */
     const size_t row_bytes = (size_t)m_max_sections * sizeof(Section);
     m_header_rows = (int)((B * m_instance_classes * sizeof(int32_t) + row_bytes - 1) / row_bytes);
     m_head_sections = m_max_sections < 64 ? m_max_sections : 64;
-    IS_CHECK_RETURN(is_device_malloc((void**)&d_stixels_block,
-                                     ((size_t)m_header_rows + B * m_realcols) * row_bytes));
-    d_stixels = d_stixels_block + (size_t)m_header_rows * m_max_sections;
-    d_instances_per_class = reinterpret_cast<int32_t*>(d_stixels_block);
-    IS_CHECK_RETURN(is_device_malloc((void**)&d_instance_centerofmass,
-                                     B * inst_n * 2 * sizeof(float)));
-    IS_CHECK_RETURN(is_device_malloc((void**)&d_instance_indices,
-                                     B * inst_n * 2 * sizeof(int32_t)));
-    IS_CHECK_RETURN(is_device_malloc((void**)&d_instance_core_candidates, B * inst_n));
-    IS_CHECK_RETURN(is_device_malloc(
-        (void**)&d_segmentation,
-        (size_t)rows_power2_segmentation * m_realcols * m_segmentation_channels * sizeof(int32_t)));
-    IS_CHECK_RETURN(is_device_malloc((void**)&d_disparity_big,
-                                     (size_t)m_rows * m_cols * sizeof(float)));
-    IS_CHECK_RETURN(is_device_malloc((void**)&d_disparity,
-                                     B * m_rows * m_realcols * sizeof(float)));
-    IS_CHECK_RETURN(is_device_malloc((void**)&d_instance_labels, B * inst_n * sizeof(int32_t)));
-    IS_CHECK_RETURN(is_device_malloc((void**)&d_instance_packed, B * (1 + 3 * inst_n) * sizeof(int32_t)));
-    IS_CHECK_RETURN(is_host_malloc((void**)&h_stixels,
-                                   (size_t)m_realcols * m_max_sections * sizeof(Section)));
-    IS_CHECK_RETURN(is_host_malloc((void**)&h_stixels_head,
-                                   ((size_t)m_header_rows + m_realcols) * m_head_sections * sizeof(Section)));
-    IS_CHECK_RETURN(is_host_malloc((void**)&h_instance_head, B * 16 * sizeof(int32_t)));
-    IS_CHECK_RETURN(is_host_malloc((void**)&h_instance_packed, (1 + 3 * inst_n) * sizeof(int32_t)));
-    h_instance_packed[0] = 0;
+    d_stixels_block.reserve(((size_t)m_header_rows + B * m_realcols) * m_max_sections);
+    d_stixels = d_stixels_block.get() + (size_t)m_header_rows * m_max_sections;
+    d_instances_per_class = reinterpret_cast<int32_t*>(d_stixels_block.get());
+    d_instance_centerofmass.reserve(B * inst_n * 2);
+    d_instance_indices.reserve(B * inst_n * 2);
+    d_instance_core_candidates.reserve(B * inst_n);
+    d_segmentation.reserve((size_t)rows_power2_segmentation * m_realcols * m_segmentation_channels);
+    d_disparity_big.reserve((size_t)m_rows * m_cols);
+    d_disparity.reserve(B * m_rows * m_realcols);
+    d_instance_labels.reserve(B * inst_n);
+    d_instance_packed.reserve(B * (1 + 3 * inst_n));
+    h_stixels.reserve((size_t)m_realcols * m_max_sections);
+    h_stixels_head.reserve(((size_t)m_header_rows + m_realcols) * m_head_sections);
+    h_instance_head.reserve(B * 16);
+    h_instance_packed.reserve(1 + 3 * inst_n);
+    h_instance_packed.get()[0] = 0;
     m_ground_valid = false; /* (the ground model depends on the configuration just applied) */
     m_is_initialized = true;
 }
 
 void Stixels::Finish() { /* Stixels.cu:250-283 */
     const DeviceGuard guard(m_ctx_device);
-    IS_CHECK_RETURN(is_device_free(d_segmentation));
-    IS_CHECK_RETURN(is_device_free(d_disparity_big));
-    IS_CHECK_RETURN(is_device_free(d_disparity));
-    IS_CHECK_RETURN(is_device_free(d_stixels_block));
-    IS_CHECK_RETURN(is_device_free(d_instance_centerofmass));
-    IS_CHECK_RETURN(is_device_free(d_instance_indices));
-    IS_CHECK_RETURN(is_device_free(d_instance_core_candidates));
-    IS_CHECK_RETURN(is_device_free(d_instance_labels));
-    IS_CHECK_RETURN(is_device_free(d_instance_packed));
-    IS_CHECK_RETURN(is_device_free(d_pack_counts));
-    IS_CHECK_RETURN(is_device_free(d_pack_offsets));
-    IS_CHECK_RETURN(is_device_free(d_pack_sections));
-    IS_CHECK_RETURN(is_device_free(d_all_counts));
-    IS_CHECK_RETURN(is_device_free(d_all_packed));
-    IS_CHECK_RETURN(is_device_free(d_all_sections));
-    IS_CHECK_RETURN(is_device_free(d_section_instance));
-    IS_CHECK_RETURN(is_device_free(d_render_results));
-    if (h_render_results) IS_CHECK_RETURN(is_host_free(h_render_results));
-    d_section_instance = nullptr; d_render_results = nullptr; h_render_results = nullptr;
-    IS_CHECK_RETURN(is_device_free(d_overlap_records));
-    IS_CHECK_RETURN(is_device_free(d_overlap_packed));
-    IS_CHECK_RETURN(is_device_free(d_overlap_header));
-    if (h_overlap_header) IS_CHECK_RETURN(is_host_free(h_overlap_header));
-    if (h_overlap_packed) IS_CHECK_RETURN(is_host_free(h_overlap_packed));
-    d_overlap_records = d_overlap_packed = nullptr; d_overlap_header = nullptr;
-    h_overlap_header = nullptr; h_overlap_packed = nullptr;
-    m_overlap_cap_alloc = 0;
+    d_disparity.release(); d_disparity_big.release(); d_segmentation.release();
+    d_stixels_block.release(); h_stixels.release(); h_stixels_head.release();
+    d_stixels = nullptr; d_instances_per_class = nullptr; /* (aliases into d_stixels_block) */
+    d_instance_centerofmass.release(); d_instance_indices.release(); d_instance_core_candidates.release();
+    d_instance_labels.release(); d_instance_packed.release(); h_instance_head.release(); h_instance_packed.release();
+    d_pack_counts.release(); d_pack_offsets.release(); d_pack_sections.release();
+    h_pack_offsets.release(); h_pack_sections.release();
+    d_all_counts.release(); d_all_packed.release(); h_all_counts.release();
+    d_section_instance.release(); d_render_results.release(); h_render_results.release();
+    d_overlap_records.release(); d_overlap_packed.release(); h_overlap_packed.release();
+    d_overlap_header.release(); h_overlap_header.release();
     m_render_images = 0;
     m_render_instances = false;
-    d_pack_counts = d_pack_offsets = d_all_counts = nullptr;
-    d_pack_sections = d_all_packed = d_all_sections = nullptr;
-    m_all_columns_cap = m_all_packed_cap = 0;
-    if (h_pack_offsets) IS_CHECK_RETURN(is_host_free(h_pack_offsets));
-    if (h_pack_sections) IS_CHECK_RETURN(is_host_free(h_pack_sections));
-    if (h_all_counts) IS_CHECK_RETURN(is_host_free(h_all_counts));
-    h_pack_offsets = nullptr; h_pack_sections = nullptr; h_all_counts = nullptr;
-    m_h_pack_cap = m_h_all_counts_cap = 0;
-    IS_CHECK_RETURN(is_host_free(h_stixels));
-    IS_CHECK_RETURN(is_host_free(h_stixels_head));
-    h_stixels_head = nullptr; d_stixels_block = nullptr;
-    IS_CHECK_RETURN(is_host_free(h_instance_head));
-    IS_CHECK_RETURN(is_host_free(h_instance_packed));
-    d_instance_labels = nullptr; d_instance_packed = nullptr;
-    h_stixels = nullptr; h_instance_head = nullptr; h_instance_packed = nullptr;
     IS_CHECK_RETURN(is_ctx_destroy(m_ctx));
     m_ctx = nullptr;
     IS_CHECK_RETURN(is_stream_destroy(m_stream));
     m_stream = nullptr;
-    d_segmentation = nullptr; d_disparity_big = nullptr; d_disparity = nullptr;
-    d_stixels = nullptr; d_instance_centerofmass = nullptr; d_instance_indices = nullptr;
-    d_instance_core_candidates = nullptr; d_instances_per_class = nullptr;
     m_log_lut.clear(); m_obj_cost_lut.clear(); m_object_disparity_range.clear();
     m_normalization_object.clear(); m_inv_sigma2_object.clear();
     m_is_initialized = false;
@@ -422,7 +379,7 @@ void Stixels::Finish() { /* Stixels.cu:250-283 */
 
 void Stixels::SetSegmentation(const std::vector<int32_t>& segmentation) { /* :340-346 */
     const DeviceGuard guard(m_ctx_device);
-    IS_CHECK_RETURN(is_memcpy_h2d(d_segmentation, segmentation.data(),
+    IS_CHECK_RETURN(is_memcpy_h2d(d_segmentation.get(), segmentation.data(),
                                   sizeof(int32_t) * segmentation.size(), m_stream));
     IS_CHECK_RETURN(is_stream_synchronize(m_stream));
 }
@@ -431,12 +388,12 @@ void Stixels::SetDisparityImage(const std::vector<pixel_t>& disp_im) { /* :348-3
     const DeviceGuard guard(m_ctx_device);
     /* the reference queues a cudaMemcpyAsync from the caller's pageable vector; the copy is
      * finished here before returning, so the vector may be a temporary */
-    IS_CHECK_RETURN(is_memcpy_h2d(d_disparity_big, disp_im.data(),
+    IS_CHECK_RETURN(is_memcpy_h2d(d_disparity_big.get(), disp_im.data(),
                                   sizeof(pixel_t) * disp_im.size(), m_stream));
     IS_CHECK_RETURN(is_stream_synchronize(m_stream));
 }
 
-pixel_t* Stixels::GetInputDisparityImageOnDevice() { return d_disparity_big; } /* :357-359 */
+pixel_t* Stixels::GetInputDisparityImageOnDevice() { return d_disparity_big.get(); } /* :357-359 */
 int Stixels::GetRealCols() { return m_realcols; }
 int Stixels::GetMaxSections() { return m_max_sections; }
 
@@ -457,12 +414,12 @@ void Stixels::FillHeader(StixelsData& d, float alpha_ground, int vhor_lib) const
 
 float Stixels::Compute(const bool pairwise, StixelsData& stixels_data,
                        int32_t* d_segmentation_local) { /* Stixels.cu:449-637 */
-    if (d_segmentation_local == nullptr) d_segmentation_local = d_segmentation;
+    if (d_segmentation_local == nullptr) d_segmentation_local = d_segmentation.get();
     const DeviceGuard guard(m_ctx_device);
 
     /* JoinColumns does not need the ground model: it runs while the host computes it */
-    IS_CHECK_RETURN(is_join_columns(m_ctx, d_disparity_big, m_cols, m_median_join ? 1 : 0,
-                                    d_disparity, 1, m_stream)); /* :509-511 */
+    IS_CHECK_RETURN(is_join_columns(m_ctx, d_disparity_big.get(), m_cols, m_median_join ? 1 : 0,
+                                    d_disparity.get(), 1, m_stream)); /* :509-511 */
     GroundModel& g = m_ground;
     const float key[12] = {(float)m_vhor, m_camera_tilt, m_camera_height, m_alpha_ground, m_focal, m_baseline,
                            m_pout, m_sigma_camera_height, m_sigma_camera_tilt, m_sigma_disparity_ground,
@@ -477,7 +434,7 @@ float Stixels::Compute(const bool pairwise, StixelsData& stixels_data,
     /* the DP, the instance candidates and their clustering (ClusterInstances, :613) are queued
      * back to back on the device; nothing returns to the host in between */
     const is_instance_buffers ib = InstanceBuffers(0);
-    IS_CHECK_RETURN(is_compute(m_ctx, d_disparity, d_segmentation_local, g.function.data(),
+    IS_CHECK_RETURN(is_compute(m_ctx, d_disparity.get(), d_segmentation_local, g.function.data(),
                                g.normalization.data(), g.inv_sigma2.data(), &m_vhor,
                                pairwise ? 1 : 0, 1, d_stixels, &ib, nullptr, nullptr,
                                m_stream)); /* :535-590 */
@@ -488,11 +445,11 @@ float Stixels::Compute(const bool pairwise, StixelsData& stixels_data,
      * column rarely has more: 10-40 on road scenes) */
     const int K = m_head_sections;
     const size_t row_bytes = (size_t)m_max_sections * sizeof(Section);
-    IS_CHECK_RETURN(is_memcpy2d_d2h(h_stixels_head, (size_t)K * sizeof(Section), d_stixels_block, row_bytes,
+    IS_CHECK_RETURN(is_memcpy2d_d2h(h_stixels_head.get(), (size_t)K * sizeof(Section), d_stixels_block.get(), row_bytes,
                                     (size_t)K * sizeof(Section), (size_t)m_header_rows + m_realcols,
                                     m_stream));
     IS_CHECK_RETURN(is_stream_synchronize(m_stream));
-    const int32_t* head = reinterpret_cast<const int32_t*>(h_stixels_head);
+    const int32_t* head = reinterpret_cast<const int32_t*>(h_stixels_head.get());
     for (int k = 0; k < m_instance_classes; k++) m_instances_per_class[k] = head[k];
     m_labels_on_host = false;
 
@@ -500,7 +457,7 @@ float Stixels::Compute(const bool pairwise, StixelsData& stixels_data,
     /* sections of every column up to and including its terminator; what lies behind a
      * terminator is unspecified (in the reference: whatever the device buffer held) */
     Section* out = stixels_data.sections.data();
-    const Section* cols = h_stixels_head + (size_t)m_header_rows * K;
+    const Section* cols = h_stixels_head.get() + (size_t)m_header_rows * K;
     bool complete = true;
     for (int c = 0; c < m_realcols && complete; c++) {
         const Section* src = cols + (size_t)c * K;
@@ -512,10 +469,10 @@ float Stixels::Compute(const bool pairwise, StixelsData& stixels_data,
     }
     if (!complete) { /* a column with more than K sections: fetch everything */
         const size_t n_sec = (size_t)m_realcols * m_max_sections;
-        IS_CHECK_RETURN(is_memcpy_d2h(h_stixels, d_stixels, n_sec * sizeof(Section), m_stream));
+        IS_CHECK_RETURN(is_memcpy_d2h(h_stixels.get(), d_stixels, n_sec * sizeof(Section), m_stream));
         IS_CHECK_RETURN(is_stream_synchronize(m_stream));
         for (int c = 0; c < m_realcols; c++) {
-            const Section* src = h_stixels + (size_t)c * m_max_sections;
+            const Section* src = h_stixels.get() + (size_t)c * m_max_sections;
             int n = 0;
             while (n < m_max_sections - 1 && src[n].type != -1) n++;
             std::memcpy(out + (size_t)c * m_max_sections, src, (size_t)(n + 1) * sizeof(Section));
@@ -528,13 +485,63 @@ is_instance_buffers Stixels::InstanceBuffers(int image) const {
     const size_t inst_n = (size_t)m_instance_classes * m_realcols * m_max_sections;
     const size_t i = (size_t)image;
     is_instance_buffers ib = {}; /* (zero-initialised: fields added by later versions stay NULL) */
-    ib.d_centerofmass = d_instance_centerofmass + i * inst_n * 2;
-    ib.d_indices = d_instance_indices + i * inst_n * 2;
-    ib.d_core_candidates = d_instance_core_candidates + i * inst_n;
+    ib.d_centerofmass = d_instance_centerofmass.get() + i * inst_n * 2;
+    ib.d_indices = d_instance_indices.get() + i * inst_n * 2;
+    ib.d_core_candidates = d_instance_core_candidates.get() + i * inst_n;
     ib.d_instances_per_class = d_instances_per_class + i * m_instance_classes;
-    ib.d_labels = d_instance_labels + i * inst_n;
-    ib.d_packed = d_instance_packed + i * (1 + 3 * inst_n);
+    ib.d_labels = d_instance_labels.get() + i * inst_n;
+    ib.d_packed = d_instance_packed.get() + i * (1 + 3 * inst_n);
     return ib;
+}
+
+/* the ground model of every frame of a batch on the host (the DP reads it from the core's staging block) */
+void Stixels::BatchGround(int n_images, const RoadParameters* road, GroundModel& batch,
+                          std::vector<int>& vhor) const {
+    const size_t H = (size_t)m_rows;
+    batch.function.resize(n_images * H);
+    batch.normalization.resize(n_images * H);
+    batch.inv_sigma2.resize(n_images * H);
+    vhor.resize(n_images);
+    GroundModel g;
+    for (int i = 0; i < n_images; i++) {
+        vhor[i] = m_rows - road[i].vhor - 1;
+        PrecomputeGround(vhor[i], road[i].camera_tilt, road[i].camera_height, road[i].alpha_ground, g);
+        std::copy(g.function.begin(), g.function.end(), batch.function.begin() + i * H);
+        std::copy(g.normalization.begin(), g.normalization.end(), batch.normalization.begin() + i * H);
+        std::copy(g.inv_sigma2.begin(), g.inv_sigma2.end(), batch.inv_sigma2.begin() + i * H);
+    }
+}
+
+/* The host half of ComputeBatch / ComputeBatchGather: back to the fixed-stride layout incl. each column's
+ * terminator -- what lies behind a terminator is unspecified, as in Compute().  A count is clamped to the
+ * sections a column can hold before its terminator. */
+void Stixels::ScatterSections(const int32_t* counts, const Section* packed, size_t total,
+                              std::vector<StixelsData>& out) const {
+    Section term;
+    std::memset(&term, 0, sizeof(term));
+    term.type = -1; /* StixelsKernels.cu:952-954 */
+    size_t o = 0;
+    for (size_t i = 0; i < out.size(); i++) {
+        Section* dst = out[i].sections.data();
+        for (int c = 0; c < m_realcols; c++) {
+            int32_t n = counts[i * m_realcols + c];
+            n = n < 0 ? 0 : (n > m_max_sections - 1 ? m_max_sections - 1 : n);
+            if (o + (size_t)n > total) throw std::runtime_error("Stixels: the column counts exceed the packed sections.");
+            if (n > 0) std::memcpy(dst + (size_t)c * m_max_sections, packed + o, (size_t)n * sizeof(Section));
+            dst[(size_t)c * m_max_sections + n] = term;
+            o += (size_t)n;
+        }
+    }
+}
+
+/* the packed payload of a batch (ComputeBatch, ComputeBatchGather): allocated on first use, released by Finish */
+void Stixels::ReservePackBuffers() {
+    const size_t cols = (size_t)m_max_batch * m_realcols;
+    d_pack_counts.reserve(cols);
+    d_pack_offsets.reserve(cols + 1);
+    d_pack_sections.reserve(cols * (m_max_sections - 1));
+    h_pack_offsets.reserve(cols + 1);
+    h_pack_sections.reserve(cols * 64); /* (grown to what a batch needs by its caller) */
 }
 
 void Stixels::ComputeBatch(bool pairwise, int n_images, const pixel_t* d_big,
@@ -545,76 +552,55 @@ void Stixels::ComputeBatch(bool pairwise, int n_images, const pixel_t* d_big,
         throw std::invalid_argument("n_images outside [1, max_batch] of InitializeBatch().");
     const DeviceGuard guard(m_ctx_device);
     if (stream == nullptr) stream = m_stream;
-    std::vector<float> gf((size_t)n_images * m_rows), ng(gf.size()), ig(gf.size());
-    std::vector<int> vh(n_images);
-    for (int i = 0; i < n_images; i++) {
-        GroundModel g;
-        vh[i] = m_rows - road[i].vhor - 1;
-        PrecomputeGround(vh[i], road[i].camera_tilt, road[i].camera_height, road[i].alpha_ground,
-                         g);
-        std::copy(g.function.begin(), g.function.end(), gf.begin() + (size_t)i * m_rows);
-        std::copy(g.normalization.begin(), g.normalization.end(), ng.begin() + (size_t)i * m_rows);
-        std::copy(g.inv_sigma2.begin(), g.inv_sigma2.end(), ig.begin() + (size_t)i * m_rows);
-    }
-    IS_CHECK_RETURN(is_join_columns(m_ctx, d_big, m_cols, m_median_join ? 1 : 0, d_disparity,
+    GroundModel g;
+    std::vector<int> vh;
+    BatchGround(n_images, road, g, vh);
+    IS_CHECK_RETURN(is_join_columns(m_ctx, d_big, m_cols, m_median_join ? 1 : 0, d_disparity.get(),
                                     n_images, stream));
     /* instance candidates + clustering of every frame: two more launches for the whole batch */
     std::vector<is_instance_buffers> ibs;
     if (instance_stixels)
         for (int i = 0; i < n_images; i++) ibs.push_back(InstanceBuffers(i));
-    IS_CHECK_RETURN(is_compute(m_ctx, d_disparity, d_seg, gf.data(), ng.data(), ig.data(),
-                               vh.data(), pairwise ? 1 : 0, n_images, d_stixels,
+    IS_CHECK_RETURN(is_compute(m_ctx, d_disparity.get(), d_seg, g.function.data(), g.normalization.data(),
+                               g.inv_sigma2.data(), vh.data(), pairwise ? 1 : 0, n_images, d_stixels,
                                instance_stixels ? ibs.data() : nullptr, nullptr, nullptr, stream));
     m_render_images = n_images;
     m_render_instances = instance_stixels != nullptr;
     /* Results to the host COMPACTED and through pinned memory: a column uses 10-60 of its 200 slots, and the
      * reference's fixed-stride copy (Stixels.cu:629-633: one frame) would move 1.6 MB per frame into pageable
      * vectors.  is_pack_sections leaves per-column offsets + the used sections; two pinned copies (the offsets, then
-     * exactly the used sections) and a scatter on the host restore the fixed-stride layout incl. each column's
-     * terminator -- what lies behind a terminator is unspecified, as in Compute(). */
+     * exactly the used sections) and a scatter on the host restore the fixed-stride layout. */
     const size_t ncols = (size_t)n_images * m_realcols;
-    EnsurePackBuffers();
-    IS_CHECK_RETURN(is_pack_sections((const is_section*)d_stixels, (int)ncols, m_max_sections, d_pack_counts,
-                                     d_pack_offsets, (is_section*)d_pack_sections, stream));
-    IS_CHECK_RETURN(is_memcpy_d2h(h_pack_offsets, d_pack_offsets, (ncols + 1) * sizeof(int32_t), stream));
+    ReservePackBuffers();
+    IS_CHECK_RETURN(is_pack_sections((const is_section*)d_stixels, (int)ncols, m_max_sections, d_pack_counts.get(),
+                                     d_pack_offsets.get(), (is_section*)d_pack_sections.get(), stream));
+    const int32_t* offsets = h_pack_offsets.get();
+    IS_CHECK_RETURN(is_memcpy_d2h(h_pack_offsets.get(), d_pack_offsets.get(), (ncols + 1) * sizeof(int32_t), stream));
     if (instance_stixels) /* the per-class counts of all frames: one small copy */
-        IS_CHECK_RETURN(is_memcpy_d2h(h_instance_head, d_instances_per_class,
+        IS_CHECK_RETURN(is_memcpy_d2h(h_instance_head.get(), d_instances_per_class,
                                       (size_t)n_images * m_instance_classes * sizeof(int32_t), stream));
     IS_CHECK_RETURN(is_stream_synchronize(stream));
-    const size_t total = (size_t)h_pack_offsets[ncols];
-    if (total > m_h_pack_cap) { /* (first call: 64 per column; grown to what a batch needs) */
-        if (h_pack_sections) IS_CHECK_RETURN(is_host_free(h_pack_sections));
-        h_pack_sections = nullptr;
-        m_h_pack_cap = total + total / 4 + 1024;
-        IS_CHECK_RETURN(is_host_malloc((void**)&h_pack_sections, m_h_pack_cap * sizeof(Section)));
-    }
+    const size_t total = (size_t)offsets[ncols];
+    if (total > h_pack_sections.capacity()) h_pack_sections.reserve(total + total / 4 + 1024);
     if (total > 0)
-        IS_CHECK_RETURN(is_memcpy_d2h(h_pack_sections, d_pack_sections, total * sizeof(Section), stream));
+        IS_CHECK_RETURN(is_memcpy_d2h(h_pack_sections.get(), d_pack_sections.get(), total * sizeof(Section), stream));
     out.resize(n_images);
     for (int i = 0; i < n_images; i++) FillHeader(out[i], road[i].alpha_ground, vh[i]); /* (beside the copy) */
+    std::vector<int32_t> counts(ncols);
+    for (size_t col = 0; col < ncols; col++) counts[col] = offsets[col + 1] - offsets[col];
     IS_CHECK_RETURN(is_stream_synchronize(stream));
-    Section term;
-    std::memset(&term, 0, sizeof(term));
-    term.type = -1; /* StixelsKernels.cu:952-954 */
-    for (int i = 0; i < n_images; i++) {
-        Section* dst = out[i].sections.data();
-        for (int c = 0; c < m_realcols; c++) {
-            const size_t col = (size_t)i * m_realcols + c;
-            const size_t o = (size_t)h_pack_offsets[col], n = (size_t)h_pack_offsets[col + 1] - o;
-            if (n > 0) std::memcpy(dst + (size_t)c * m_max_sections, h_pack_sections + o, n * sizeof(Section));
-            dst[(size_t)c * m_max_sections + n] = term;
-        }
-    }
+    ScatterSections(counts.data(), h_pack_sections.get(), total, out);
     if (!instance_stixels) return;
     /* (column, section, label) triples of every frame, sized by the counts just read */
+    const int32_t* head = h_instance_head.get();
     const size_t inst_n = (size_t)m_instance_classes * m_realcols * m_max_sections;
     std::vector<int> totals(n_images, 0);
     std::vector<std::vector<int32_t>> triples(n_images);
     for (int i = 0; i < n_images; i++) {
-        for (int k = 0; k < m_instance_classes; k++) totals[i] += h_instance_head[i * m_instance_classes + k];
+        for (int k = 0; k < m_instance_classes; k++) totals[i] += head[i * m_instance_classes + k];
         triples[i].resize(3 * (size_t)totals[i] + 1);
         if (totals[i] > 0)
-            IS_CHECK_RETURN(is_memcpy_d2h(triples[i].data(), d_instance_packed + (size_t)i * (1 + 3 * inst_n),
+            IS_CHECK_RETURN(is_memcpy_d2h(triples[i].data(), d_instance_packed.get() + (size_t)i * (1 + 3 * inst_n),
                                           (1 + 3 * (size_t)totals[i]) * sizeof(int32_t), stream));
     }
     IS_CHECK_RETURN(is_stream_synchronize(stream));
@@ -625,7 +611,7 @@ void Stixels::ComputeBatch(bool pairwise, int n_images, const pixel_t* d_big,
             (*instance_stixels)[i][std::make_pair(t[3 * j], t[3 * j + 1])] = t[3 * j + 2];
     }
     /* a following GetInstanceStixels() returns the mapping of frame 0 (slice 0 of the arrays) */
-    for (int k = 0; k < m_instance_classes; k++) m_instances_per_class[k] = h_instance_head[k];
+    for (int k = 0; k < m_instance_classes; k++) m_instances_per_class[k] = head[k];
     m_labels_on_host = false;
 }
 
@@ -641,13 +627,11 @@ std::vector<Stixels::RenderResult> Stixels::RenderBatch(int n_images, const Rend
     if (stream == nullptr) stream = m_stream;
     const size_t B = (size_t)m_max_batch;
     const size_t res_bytes = B * (sizeof(double) + sizeof(int64_t) + sizeof(int32_t));
-    if (d_render_results == nullptr) {
-        IS_CHECK_RETURN(is_device_malloc((void**)&d_render_results, res_bytes));
-        IS_CHECK_RETURN(is_host_malloc((void**)&h_render_results, res_bytes));
-    }
-    double* d_sum = (double*)d_render_results;
-    int64_t* d_cnt = (int64_t*)(d_render_results + B * sizeof(double));
-    int32_t* d_nst = (int32_t*)(d_render_results + B * (sizeof(double) + sizeof(int64_t)));
+    d_render_results.reserve(res_bytes);
+    h_render_results.reserve(res_bytes);
+    double* d_sum = (double*)d_render_results.get();
+    int64_t* d_cnt = (int64_t*)(d_render_results.get() + B * sizeof(double));
+    int32_t* d_nst = (int32_t*)(d_render_results.get() + B * (sizeof(double) + sizeof(int64_t)));
     is_render_args a = {};
     a.d_sections = d_stixels;
     a.n_images = n_images;
@@ -672,23 +656,21 @@ std::vector<Stixels::RenderResult> Stixels::RenderBatch(int n_images, const Rend
     }
     a.d_stixel_count = d_nst;
     if (t.instance) { /* the cluster labels of every frame as a per-section map */
-        if (d_section_instance == nullptr)
-            IS_CHECK_RETURN(is_device_malloc((void**)&d_section_instance,
-                                             B * m_realcols * m_max_sections * sizeof(int32_t)));
+        d_section_instance.reserve(B * m_realcols * m_max_sections);
         std::vector<is_instance_buffers> ibs;
         for (int i = 0; i < n_images; i++) ibs.push_back(InstanceBuffers(i));
         IS_CHECK_RETURN(is_section_instance_labels(ibs.data(), n_images, m_realcols, m_max_sections,
-                                                   d_section_instance, stream));
-        a.d_section_instance = d_section_instance;
+                                                   d_section_instance.get(), stream));
+        a.d_section_instance = d_section_instance.get();
     }
     const int rc = is_render_sections(&a, stream);
     if (rc == IS_EINVAL) throw std::invalid_argument(std::string("RenderBatch: ") + is_last_error());
     IS_CHECK_RETURN(rc);
-    IS_CHECK_RETURN(is_memcpy_d2h(h_render_results, d_render_results, res_bytes, stream));
+    IS_CHECK_RETURN(is_memcpy_d2h(h_render_results.get(), d_render_results.get(), res_bytes, stream));
     IS_CHECK_RETURN(is_stream_synchronize(stream));
-    const double* h_sum = (const double*)h_render_results;
-    const int64_t* h_cnt = (const int64_t*)(h_render_results + B * sizeof(double));
-    const int32_t* h_nst = (const int32_t*)(h_render_results + B * (sizeof(double) + sizeof(int64_t)));
+    const double* h_sum = (const double*)h_render_results.get();
+    const int64_t* h_cnt = (const int64_t*)(h_render_results.get() + B * sizeof(double));
+    const int32_t* h_nst = (const int32_t*)(h_render_results.get() + B * (sizeof(double) + sizeof(int64_t)));
     std::vector<RenderResult> out(n_images);
     for (int i = 0; i < n_images; i++) out[i] = RenderResult{h_sum[i], h_cnt[i], h_nst[i]};
     return out;
@@ -715,32 +697,21 @@ std::vector<std::vector<is_overlap_record>> Stixels::InstanceOverlapBatch(int n_
     const size_t B = (size_t)m_max_batch;
     const size_t cs = (size_t)m_realcols * m_max_sections;
     const size_t cap = (size_t)m_overlap_capacity;
-    if (d_section_instance == nullptr)
-        IS_CHECK_RETURN(is_device_malloc((void**)&d_section_instance, B * cs * sizeof(int32_t)));
-    if (d_overlap_header == nullptr) {
-        IS_CHECK_RETURN(is_device_malloc((void**)&d_overlap_header, 2 * B * sizeof(int32_t)));
-        IS_CHECK_RETURN(is_host_malloc((void**)&h_overlap_header, 2 * B * sizeof(int32_t)));
-    }
-    if (m_overlap_cap_alloc < cap) {
-        IS_CHECK_RETURN(is_device_free(d_overlap_records));
-        IS_CHECK_RETURN(is_device_free(d_overlap_packed));
-        if (h_overlap_packed) IS_CHECK_RETURN(is_host_free(h_overlap_packed));
-        d_overlap_records = d_overlap_packed = h_overlap_packed = nullptr;
-        m_overlap_cap_alloc = 0;
-        IS_CHECK_RETURN(is_device_malloc((void**)&d_overlap_records, B * cap * sizeof(is_overlap_record)));
-        IS_CHECK_RETURN(is_device_malloc((void**)&d_overlap_packed, B * cap * sizeof(is_overlap_record)));
-        IS_CHECK_RETURN(is_host_malloc((void**)&h_overlap_packed, B * cap * sizeof(is_overlap_record)));
-        m_overlap_cap_alloc = cap;
-    }
+    d_section_instance.reserve(B * cs);
+    d_overlap_header.reserve(2 * B);
+    h_overlap_header.reserve(2 * B);
+    d_overlap_records.reserve(B * cap);
+    d_overlap_packed.reserve(B * cap);
+    h_overlap_packed.reserve(B * cap);
     std::vector<is_instance_buffers> ibs;
     for (int i = 0; i < n_images; i++) ibs.push_back(InstanceBuffers(i));
-    IS_CHECK_RETURN(is_section_instance_labels(ibs.data(), n_images, m_realcols, m_max_sections, d_section_instance,
-                                               stream));
+    IS_CHECK_RETURN(is_section_instance_labels(ibs.data(), n_images, m_realcols, m_max_sections,
+                                               d_section_instance.get(), stream));
     const size_t frame_px = (size_t)m_rows * m_cols;
     auto args = [&](int first, int n, int capacity, is_overlap_record* rec, int32_t* hdr) {
         is_instance_overlap_args a = {};
         a.d_sections = d_stixels + first * cs;
-        a.d_section_instance = d_section_instance + first * cs;
+        a.d_section_instance = d_section_instance.get() + first * cs;
         a.n_images = n;
         a.realcols = m_realcols;
         a.max_sections = m_max_sections;
@@ -754,26 +725,30 @@ std::vector<std::vector<is_overlap_record>> Stixels::InstanceOverlapBatch(int n_
         return a;
     };
     /* the batch: tables, packed on the device; the per-frame counts first, then the used records */
-    const is_instance_overlap_args a = args(0, n_images, (int)cap, d_overlap_records, d_overlap_header);
+    const int32_t* header = h_overlap_header.get();
+    const is_instance_overlap_args a = args(0, n_images, (int)cap, d_overlap_records.get(), d_overlap_header.get());
     const int rc = is_instance_overlap(&a, stream);
     if (rc == IS_EINVAL) throw std::invalid_argument(std::string("InstanceOverlapBatch: ") + is_last_error());
     IS_CHECK_RETURN(rc);
-    IS_CHECK_RETURN(is_pack_overlap_records(d_overlap_records, d_overlap_header, n_images, (int)cap,
-                                            d_overlap_packed, stream));
-    IS_CHECK_RETURN(is_memcpy_d2h(h_overlap_header, d_overlap_header, 2 * n_images * sizeof(int32_t), stream));
+    IS_CHECK_RETURN(is_pack_overlap_records(d_overlap_records.get(), d_overlap_header.get(), n_images, (int)cap,
+                                            d_overlap_packed.get(), stream));
+    IS_CHECK_RETURN(is_memcpy_d2h(h_overlap_header.get(), d_overlap_header.get(), 2 * n_images * sizeof(int32_t),
+                                  stream));
     IS_CHECK_RETURN(is_stream_synchronize(stream));
     size_t total = 0;
-    for (int i = 0; i < n_images; i++) total += (size_t)h_overlap_header[i];
+    for (int i = 0; i < n_images; i++) total += (size_t)header[i];
     if (total)
-        IS_CHECK_RETURN(is_memcpy_d2h(h_overlap_packed, d_overlap_packed, total * sizeof(is_overlap_record), stream));
+        IS_CHECK_RETURN(is_memcpy_d2h(h_overlap_packed.get(), d_overlap_packed.get(),
+                                      total * sizeof(is_overlap_record), stream));
     IS_CHECK_RETURN(is_stream_synchronize(stream));
     std::vector<std::vector<is_overlap_record>> out(n_images);
     std::vector<int> retry;
+    const is_overlap_record* packed = h_overlap_packed.get();
     size_t off = 0;
     for (int i = 0; i < n_images; i++) {
-        const int m = h_overlap_header[i];
-        if (h_overlap_header[n_images + i]) retry.push_back(i);
-        out[i].assign(h_overlap_packed + off, h_overlap_packed + off + m);
+        const int m = header[i];
+        if (header[n_images + i]) retry.push_back(i);
+        out[i].assign(packed + off, packed + off + m);
         off += (size_t)m;
     }
     /* frames with more distinct pairs than the capacity: alone, with 8x the table until it fits (rows*cols always
@@ -782,41 +757,30 @@ std::vector<std::vector<is_overlap_record>> Stixels::InstanceOverlapBatch(int n_
         size_t c = cap;
         for (;;) {
             c = std::min(c * 8, frame_px);
-            is_overlap_record* d_rec = nullptr;
-            int32_t* d_hdr = nullptr;
-            IS_CHECK_RETURN(is_device_malloc((void**)&d_rec, c * sizeof(is_overlap_record)));
-            IS_CHECK_RETURN(is_device_malloc((void**)&d_hdr, 2 * sizeof(int32_t)));
-            const is_instance_overlap_args r = args(f, 1, (int)c, d_rec, d_hdr);
+            struct Table { /* this attempt's table, freed on every way out of the attempt */
+                DeviceArray<is_overlap_record> rec;
+                DeviceArray<int32_t> hdr;
+                ~Table() { rec.release(); hdr.release(); }
+            } t;
+            t.rec.reserve(c);
+            t.hdr.reserve(2);
+            const is_instance_overlap_args r = args(f, 1, (int)c, t.rec.get(), t.hdr.get());
             int32_t hdr[2] = {0, 0};
-            int err = is_instance_overlap(&r, stream);
-            if (err == IS_OK) err = is_memcpy_d2h(hdr, d_hdr, sizeof(hdr), stream);
-            if (err == IS_OK) err = is_stream_synchronize(stream);
-            if (err == IS_OK && !hdr[1]) {
+            IS_CHECK_RETURN(is_instance_overlap(&r, stream));
+            IS_CHECK_RETURN(is_memcpy_d2h(hdr, t.hdr.get(), sizeof(hdr), stream));
+            IS_CHECK_RETURN(is_stream_synchronize(stream));
+            if (!hdr[1]) {
                 out[f].resize((size_t)hdr[0]);
-                if (hdr[0]) err = is_memcpy_d2h(out[f].data(), d_rec, (size_t)hdr[0] * sizeof(is_overlap_record), stream);
-                if (err == IS_OK) err = is_stream_synchronize(stream);
+                if (hdr[0])
+                    IS_CHECK_RETURN(is_memcpy_d2h(out[f].data(), t.rec.get(), (size_t)hdr[0] * sizeof(is_overlap_record),
+                                                  stream));
+                IS_CHECK_RETURN(is_stream_synchronize(stream));
+                break;
             }
-            IS_CHECK_RETURN(is_device_free(d_rec));
-            IS_CHECK_RETURN(is_device_free(d_hdr));
-            IS_CHECK_RETURN(err);
-            if (!hdr[1]) break;
             if (c >= frame_px) throw std::runtime_error("InstanceOverlapBatch: a table of rows*cols records overflowed.");
         }
     }
     return out;
-}
-
-/* the packed payload of a batch (ComputeBatch, ComputeBatchGather): allocated on first use, released by Finish */
-void Stixels::EnsurePackBuffers() {
-    if (d_pack_counts != nullptr) return;
-    const size_t cols = (size_t)m_max_batch * m_realcols;
-    IS_CHECK_RETURN(is_device_malloc((void**)&d_pack_counts, cols * sizeof(int32_t)));
-    IS_CHECK_RETURN(is_device_malloc((void**)&d_pack_offsets, (cols + 1) * sizeof(int32_t)));
-    IS_CHECK_RETURN(is_device_malloc((void**)&d_pack_sections, cols * (m_max_sections - 1) * sizeof(Section)));
-    IS_CHECK_RETURN(is_host_malloc((void**)&h_pack_offsets, (cols + 1) * sizeof(int32_t)));
-    if (h_pack_sections != nullptr) return; /* (ComputeBatchGather on dst may have made it already) */
-    m_h_pack_cap = cols * 64;
-    IS_CHECK_RETURN(is_host_malloc((void**)&h_pack_sections, m_h_pack_cap * sizeof(Section)));
 }
 
 /* The shard of this rank, then the compacted gather of every rank's Sections on `dst` (the
@@ -836,33 +800,28 @@ void Stixels::ComputeBatchGather(bool pairwise, int n_images, const pixel_t* d_b
         throw std::invalid_argument("images_per_rank[rank] differs from n_images.");
     if (rank == dst && road_all == nullptr)
         throw std::invalid_argument("the destination rank needs road_all (the headers of every frame).");
-    const size_t per = (size_t)m_realcols * m_max_sections;
     const int my_cols = n_images * m_realcols;
 
     /* ---- this rank's shard: ground model on the host, JoinColumns + DP + back-trace on the device */
-    std::vector<float> gf((size_t)n_images * m_rows), ng(gf.size()), ig(gf.size());
-    std::vector<int> vh(n_images);
-    for (int i = 0; i < n_images; i++) {
-        GroundModel g;
-        vh[i] = m_rows - road[i].vhor - 1;
-        PrecomputeGround(vh[i], road[i].camera_tilt, road[i].camera_height, road[i].alpha_ground, g);
-        std::copy(g.function.begin(), g.function.end(), gf.begin() + (size_t)i * m_rows);
-        std::copy(g.normalization.begin(), g.normalization.end(), ng.begin() + (size_t)i * m_rows);
-        std::copy(g.inv_sigma2.begin(), g.inv_sigma2.end(), ig.begin() + (size_t)i * m_rows);
-    }
-    IS_CHECK_RETURN(is_join_columns(m_ctx, d_big, m_cols, m_median_join ? 1 : 0, d_disparity, n_images, stream));
-    IS_CHECK_RETURN(is_compute(m_ctx, d_disparity, d_seg, gf.data(), ng.data(), ig.data(), vh.data(),
-                               pairwise ? 1 : 0, n_images, d_stixels, nullptr, nullptr, nullptr, stream));
+    GroundModel g;
+    std::vector<int> vh;
+    BatchGround(n_images, road, g, vh);
+    IS_CHECK_RETURN(is_join_columns(m_ctx, d_big, m_cols, m_median_join ? 1 : 0, d_disparity.get(), n_images,
+                                    stream));
+    IS_CHECK_RETURN(is_compute(m_ctx, d_disparity.get(), d_seg, g.function.data(), g.normalization.data(),
+                               g.inv_sigma2.data(), vh.data(), pairwise ? 1 : 0, n_images, d_stixels, nullptr,
+                               nullptr, nullptr, stream));
     m_render_images = 0; /* (d_stixels now holds this rank's shard; RenderBatch renders Compute / ComputeBatch) */
 
     /* ---- pack: per-column counts + the used sections (10-40 of the 200 slots of a column) */
-    EnsurePackBuffers();
-    IS_CHECK_RETURN(is_pack_sections((const is_section*)d_stixels, my_cols, m_max_sections, d_pack_counts,
-                                     d_pack_offsets, (is_section*)d_pack_sections, stream));
+    ReservePackBuffers();
+    IS_CHECK_RETURN(is_pack_sections((const is_section*)d_stixels, my_cols, m_max_sections, d_pack_counts.get(),
+                                     d_pack_offsets.get(), (is_section*)d_pack_sections.get(), stream));
 
     /* ---- gather on dst.  Landing buffers: counts for every column, sections for 64 per column at first
      * (synthetic and real scenes use 10-60); when a batch needs more, EVERY rank sees IS_ENOMEM from the
-     * gather (dst's go-ahead), dst grows to the worst case and all ranks repeat the call */
+     * gather (dst's go-ahead), dst grows to the worst case and all ranks repeat the call.  A landing buffer
+     * is replaced only after the stream has finished with the old one. */
     std::vector<int32_t> columns(nranks);
     size_t all_cols = 0;
     int all_images = 0;
@@ -872,25 +831,22 @@ void Stixels::ComputeBatchGather(bool pairwise, int n_images, const pixel_t* d_b
         all_images += images_per_rank[r];
     }
     std::vector<int64_t> totals(nranks, 0);
-    if (rank == dst && (m_all_columns_cap < all_cols || d_all_counts == nullptr)) {
+    if (rank == dst && d_all_counts.capacity() < (all_cols + 1) * 2) {
         IS_CHECK_RETURN(is_stream_synchronize(stream));
-        IS_CHECK_RETURN(is_device_free(d_all_counts));
-        IS_CHECK_RETURN(is_device_malloc((void**)&d_all_counts, (all_cols + 1) * sizeof(int32_t) * 2));
-        m_all_columns_cap = all_cols;
+        d_all_counts.reserve((all_cols + 1) * 2);
     }
     for (int attempt = 0;; attempt++) {
         if (rank == dst) {
             const size_t want = attempt == 0 ? all_cols * 64 : all_cols * (size_t)(m_max_sections - 1);
-            if (m_all_packed_cap < want) {
+            if (d_all_packed.capacity() < want) {
                 IS_CHECK_RETURN(is_stream_synchronize(stream));
-                IS_CHECK_RETURN(is_device_free(d_all_packed));
-                IS_CHECK_RETURN(is_device_malloc((void**)&d_all_packed, want * sizeof(Section)));
-                m_all_packed_cap = want;
+                d_all_packed.reserve(want);
             }
         }
-        const int rc = is_gather_sections(comm, dst, columns.data(), d_pack_counts, d_pack_offsets,
-                                          (const is_section*)d_pack_sections, d_all_counts,
-                                          (is_section*)d_all_packed, m_all_packed_cap, totals.data(), stream);
+        const int rc = is_gather_sections(comm, dst, columns.data(), d_pack_counts.get(), d_pack_offsets.get(),
+                                          (const is_section*)d_pack_sections.get(), d_all_counts.get(),
+                                          (is_section*)d_all_packed.get(), d_all_packed.capacity(), totals.data(),
+                                          stream);
         if (rc == IS_ENOMEM && attempt == 0) continue; /* (every rank takes this branch together) */
         IS_CHECK_RETURN(rc);
         break;
@@ -901,45 +857,19 @@ void Stixels::ComputeBatchGather(bool pairwise, int n_images, const pixel_t* d_b
         return;
     }
     /* ---- dst: the packed payload of all ranks to the host through pinned memory (per-column counts + exactly the used
-     * sections), then back to fixed-stride Section arrays with each column's terminator on the host -- like
-     * ComputeBatch; is_unpack_sections is the device-side form of the same scatter for callers that keep the result
-     * on the GPU */
+     * sections), then back to fixed-stride Section arrays on the host -- like ComputeBatch; is_unpack_sections is the
+     * device-side form of the same scatter for callers that keep the result on the GPU */
     size_t total = 0;
     for (int r = 0; r < nranks; r++) total += (size_t)totals[r];
-    if (m_h_all_counts_cap < all_cols) {
-        if (h_all_counts) IS_CHECK_RETURN(is_host_free(h_all_counts));
-        h_all_counts = nullptr;
-        IS_CHECK_RETURN(is_host_malloc((void**)&h_all_counts, all_cols * sizeof(int32_t)));
-        m_h_all_counts_cap = all_cols;
-    }
-    if (total > m_h_pack_cap) {
-        if (h_pack_sections) IS_CHECK_RETURN(is_host_free(h_pack_sections));
-        h_pack_sections = nullptr;
-        m_h_pack_cap = total + total / 4 + 1024;
-        IS_CHECK_RETURN(is_host_malloc((void**)&h_pack_sections, m_h_pack_cap * sizeof(Section)));
-    }
-    IS_CHECK_RETURN(is_memcpy_d2h(h_all_counts, d_all_counts, all_cols * sizeof(int32_t), stream));
+    h_all_counts.reserve(all_cols);
+    if (total > h_pack_sections.capacity()) h_pack_sections.reserve(total + total / 4 + 1024);
+    IS_CHECK_RETURN(is_memcpy_d2h(h_all_counts.get(), d_all_counts.get(), all_cols * sizeof(int32_t), stream));
     if (total > 0)
-        IS_CHECK_RETURN(is_memcpy_d2h(h_pack_sections, d_all_packed, total * sizeof(Section), stream));
+        IS_CHECK_RETURN(is_memcpy_d2h(h_pack_sections.get(), d_all_packed.get(), total * sizeof(Section), stream));
     out.resize(all_images);
     for (int i = 0; i < all_images; i++) FillHeader(out[i], road_all[i].alpha_ground, m_rows - road_all[i].vhor - 1);
     IS_CHECK_RETURN(is_stream_synchronize(stream));
-    Section term;
-    std::memset(&term, 0, sizeof(term));
-    term.type = -1; /* StixelsKernels.cu:952-954 */
-    size_t o = 0;
-    for (int i = 0; i < all_images; i++) {
-        Section* dst_sec = out[i].sections.data();
-        for (int c = 0; c < m_realcols; c++) {
-            int32_t n = h_all_counts[(size_t)i * m_realcols + c];
-            n = n < 0 ? 0 : (n > m_max_sections - 1 ? m_max_sections - 1 : n);
-            if (o + (size_t)n > total) throw std::runtime_error("ComputeBatchGather: the gathered counts exceed the gathered sections.");
-            if (n > 0) std::memcpy(dst_sec + (size_t)c * m_max_sections, h_pack_sections + o, (size_t)n * sizeof(Section));
-            dst_sec[(size_t)c * m_max_sections + n] = term;
-            o += (size_t)n;
-        }
-    }
-    (void)per;
+    ScatterSections(h_all_counts.get(), h_pack_sections.get(), total, out);
 }
 
 /* ---------------------------------------------------------------- instances */
@@ -966,17 +896,17 @@ std::map<std::pair<int, int>, int> Stixels::GetInstanceStixels() { /* Stixels.cu
         int total = 0;
         for (int k = 0; k < m_instance_classes; k++) total += m_instances_per_class[k];
         if (total > 0) {
-            IS_CHECK_RETURN(is_memcpy_d2h(h_instance_packed, d_instance_packed,
+            IS_CHECK_RETURN(is_memcpy_d2h(h_instance_packed.get(), d_instance_packed.get(),
                                           (1 + 3 * (size_t)total) * sizeof(int32_t), m_stream));
             IS_CHECK_RETURN(is_stream_synchronize(m_stream));
         } else {
-            h_instance_packed[0] = 0;
+            h_instance_packed.get()[0] = 0;
         }
         m_labels_on_host = true;
     }
     std::map<std::pair<int, int>, int> mapping;
-    const int total = h_instance_packed[0];
-    const int32_t* t = h_instance_packed + 1;
+    const int total = h_instance_packed.get()[0];
+    const int32_t* t = h_instance_packed.get() + 1;
     for (int i = 0; i < total; i++)
         mapping[std::make_pair(t[3 * i], t[3 * i + 1])] = t[3 * i + 2];
     return mapping;

@@ -9,7 +9,8 @@ import instance_eval_reference as ir
 import render_reference as rr
 from instance_stixels_amd import core, evaluation, host, synthetic
 from instance_stixels_amd.config import SECTION_DTYPE
-from test_render_gpu import PRESETS, SHAPES, Out, _dev, _setup, _torch
+from test_render_gpu import PRESETS, SHAPES, Out, _dev, _full, _setup, _torch
+from test_road_batch_gpu import _batch, _init
 
 pytestmark = pytest.mark.gpu
 
@@ -129,6 +130,55 @@ def test_overlap_streams_canaries_determinism_overflow_and_refusals():
     with pytest.raises(ValueError, match="instances"):
         st.InstanceOverlapBatch(2, d_gt.data_ptr())
     st.close()
+
+
+def test_finish_then_initialize_again_matches_a_fresh_object():
+    """Finish() releases every buffer the calls grew; InitializeBatch with another batch size on the same object then
+    gives what a fresh object gives, bit for bit: ComputeBatch with instances, RenderBatch, InstanceOverlapBatch
+    through its overflow retries, and RoadEstimation::ComputeBatch."""
+    rows, cols, D, n = 256, 512, 64, 4
+    st, case, (big, seg, road), _, _ = _setup("drn_d_38_pairwise", rows, cols, D, n, {}, seed=rows + n)
+    cfg = case["cfg"]
+    rng = np.random.default_rng(12)
+    gt = rng.integers(0, 40, (n, rows, cols)).astype(np.uint8)
+    gd = rng.uniform(0, 50, (n, rows, cols)).astype(np.float32)
+    d_gi = _dev(rng.integers(0, 6, (n, rows, cols)).astype(np.int32))
+
+    def run(obj, m):
+        data, maps = obj.ComputeBatch(cfg.pairwise, big.data_ptr(), seg.data_ptr(), road[:m], with_instances=True)
+        assert any(maps), "no instances: the case does not exercise the instance buffers"
+        rendered = _full(obj, m, (m, rows, cols), gt[:m], gd[:m])
+        obj.SetInstanceOverlapCapacity(3)  # every frame overflows it: the retries with larger tables run
+        tables = obj.InstanceOverlapBatch(m, d_gi.data_ptr())
+        assert all(len(t) > 3 for t in tables)
+        return ([d.sections.tobytes() for d in data], maps, [np.asarray(x).tobytes() for x in rendered],
+                [t.tobytes() for t in tables])
+
+    for m in (n, 2, 3):  # the same object: Initialize(n) by _setup, then Finish -> Initialize(m)
+        if m != n:
+            st.Finish()
+            st.Initialize(max_batch=m)
+        fresh = host.Stixels()
+        fresh.SetConfig(cfg)
+        fresh.Initialize(max_batch=m)
+        assert run(st, m) == run(fresh, m), m
+        fresh.close()
+    st.close()
+
+    disp, cases = _batch(rows, cols, D, n, seed=13)
+    d = _torch()[0].from_numpy(disp).to(_torch()[1])
+    re_ = host.RoadEstimation()
+    _init(re_, cases[0]["cfg"], rows, cols, D)
+    for m in (n, 2):
+        if m != n:
+            re_.Finish()
+            _init(re_, cases[0]["cfg"], rows, cols, D)
+        fresh = host.RoadEstimation()
+        _init(fresh, cases[0]["cfg"], rows, cols, D)
+        got, want = re_.ComputeBatch(d.data_ptr(), m), fresh.ComputeBatch(d.data_ptr(), m)
+        assert got == want and any(got[1]), m
+        fresh.close()
+    re_.close()
 
 
 def _c_abi(secs_dev, map_dev, n, realcols, S, rows, cols, d_gt, cap, offset=0):
