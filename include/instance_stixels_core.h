@@ -429,7 +429,10 @@ int is_device_synchronize(void);
 /* Test hook (A4, ComputeObjectLUT): copies the object data-cost prefix table of ONE stixel column
  * (0 <= column < n_images * realcols) as the last is_compute call on this context left it into
  * host memory, h_out[(rows + 1) * max_dis] = lutT[v][fn] -- the transpose of the reference's
- * d_object_lut[fn][v] (Stixels.cu:159-160, StixelsKernels.cu:959-978).  Synchronises the device. */
+ * d_object_lut[fn][v] (Stixels.cu:159-160, StixelsKernels.cu:959-978).  Synchronises the device.  After a unary call
+ * that took the visited-rows walk (is_debug_unary_path: path 1) the buffer holds NO complete table: that call stores
+ * only the table's block carries elsewhere and rebuilds the entries it reads; only the generic-encoding columns, and
+ * every column of a repaired call, are complete. */
 int is_debug_read_object_lut(is_ctx* ctx, int column, float* h_out);
 
 /* Test hook: did the last unary is_compute call on this context run its repair launches?  A unary call whose every

@@ -80,6 +80,7 @@ struct is_ctx {
     int nwaves_unary, nwaves_pairwise;
     /* frame-independent device tables */
     float* d_obj_cost_lut;   /* [D dis][D fn], transposed w.r.t. Stixels.cu:122-129 */
+    float* d_obj_cost_fn;    /* [D fn][D dis], as Stixels.cu:122-129: a walk lane's gather stays in one fn row */
     float* d_odr;            /* [D]     object_disparity_range */
     float* d_rcp;            /* [H+1]   RN(1/h) = (float)(1./h), the reference's inverse_height */
     int* d_col_flags;        /* [max_batch*C] 0 = FAST column, see RowRec */
@@ -115,6 +116,7 @@ struct is_ctx {
     /* scratch */
     RowRec* d_recs;          /* [max_batch*C][H+1] */
     float* d_lutT;           /* [max_batch*C][H+1][D] */
+    float* d_lutC;           /* [max_batch*C][ceil(H/32)][D] the LUT's block carries of a walk call (CallPlan::lut_carry) */
     int* h_lutf_repairs = nullptr; /* pinned + mapped: calls whose fused LUT hand-over was repaired (DevParams::lutf_repairs) */
     PriorRec* d_priors;      /* [max_batch][H] */
     StepRec* d_steps;        /* [max_batch*C][H]   per-vB transition records of the pairwise DP (64 B) */
@@ -331,6 +333,7 @@ static int ctx_init(is_ctx* c, const is_stixel_params* p, const float* obj_cost_
         total += (bytes);                                     \
     } while (0)
     ALLOC(c->d_obj_cost_lut, sizeof(float) * D * D);
+    ALLOC(c->d_obj_cost_fn, sizeof(float) * D * D);
     ALLOC(c->d_odr, sizeof(float) * D);
     ALLOC(c->d_rcp, sizeof(float) * (H + 1));
     ALLOC(c->d_col_flags, sizeof(int) * B * C);
@@ -348,6 +351,7 @@ static int ctx_init(is_ctx* c, const is_stixel_params* p, const float* obj_cost_
     c->d_vhor = (int*)(c->d_stage + c->stage_off_vhor);
     ALLOC(c->d_recs, sizeof(RowRec) * B * C * (H + 1));
     ALLOC(c->d_lutT, sizeof(float) * B * C * (H + 1) * D);
+    ALLOC(c->d_lutC, sizeof(float) * B * C * isk_lut_carry_rows((int)H) * D);
     ALLOC(c->d_priors, sizeof(PriorRec) * B * H);
     ALLOC(c->d_steps, (size_t)64 * B * C * H);
     /* phase 1 may use up to IS_PW_MAX_SPLIT workgroups per column while columns are few */
@@ -398,6 +402,7 @@ static int ctx_init(is_ctx* c, const is_stixel_params* p, const float* obj_cost_
         free(t);
         HIP_TRY(e);
     }
+    HIP_TRY(hipMemcpy(c->d_obj_cost_fn, obj_cost_lut, sizeof(float) * D * D, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->d_odr, obj_disparity_range, sizeof(float) * D, hipMemcpyHostToDevice));
     {
         /* inverse_height = (float)(1./(vT+1-vB)) (StixelsKernels.cu:485, 608) doubles as the
@@ -867,8 +872,10 @@ static CallPlan plan_call(const is_ctx* c, int n_images, int pairwise, const int
                       p.win_tiles == P.ntiles &&
                       !(by_itself && (ncols < ISF_LUTF_MIN_COLS || fnb > 2 || repaired_before));
     }
-    /* the walk reads the complete object table of the prepare launch */
     p.prepare_lut = !p.lut_fused;
+    /* the walk rebuilds the table entries it reads from the block carries (k_unary_path); the launches behind it that
+     * read the complete table build it first for the columns they take (isk_launch_dp_unary) */
+    p.lut_carry = p.unary_walk;
 
     if (pairwise) {
         /* few columns: two workgroups per (column, tile) in phase 1 */
@@ -932,8 +939,8 @@ static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_se
     if (!pairwise) c->last_unary_path = plan.unary_walk;
     CallBuffers b;
     b.joined = d_joined; b.seg = d_seg; b.ground = c->d_ground; b.vhor = c->d_vhor;
-    b.cost_T = c->d_obj_cost_lut; b.odr = c->d_odr; b.rcp = c->d_rcp;
-    b.recs = c->d_recs; b.lutT = c->d_lutT; b.col_flags = c->d_col_flags; b.sv = c->d_sv; b.prune = c->d_prune;
+    b.cost_T = c->d_obj_cost_lut; b.cost_F = c->d_obj_cost_fn; b.odr = c->d_odr; b.rcp = c->d_rcp;
+    b.recs = c->d_recs; b.lutT = c->d_lutT; b.lutC = c->d_lutC; b.col_flags = c->d_col_flags; b.sv = c->d_sv; b.prune = c->d_prune;
     b.n_generic = c->d_n_generic; b.path_bad = c->d_path_bad; b.priors = c->d_priors; b.steps = c->d_steps;
     b.part_cost = c->d_part_cost; b.part_idx = c->d_part_idx; b.blksum = c->d_blksum; b.t8row = c->d_t8row;
     b.cost_table = d_cost_table ? d_cost_table : c->d_cost_table;

@@ -677,17 +677,23 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prepare_columns(
  * 256-byte rows that nothing reads before the whole table is written: no reason to keep them in the L2 /
  * MALL) 1.59 ms = 5.4 TB/s.  Storing fewer fn per row only pays in whole 128-byte lines (105 of 128 fn:
  * 2.37 ms, partial lines are read-modify-write). */
+/*
+ * CARRY (the prepare launch of a walk call, k_unary_path): only the carries, lutC[k][fn] = lutT[32 k][fn] for the
+ * ceil(H / 32) blocks k of the column (lutC[0] = 0), as whole non-temporal rows of the compact [ceil(H/32)][D]
+ * buffer `out` (isk_lut_carry_rows).  Only c[31] of a block is stored, so the compiler keeps the lane-31 path of the
+ * network: the same additions on the same values as the full table's.  The walk rebuilds the entries it reads. */
+template <bool CARRY>
 __device__ __forceinline__ void object_lut_body(const DevParams& P, const int colg, const int fn_block,
                                                 const int lane, const float* __restrict__ joined,
                                                 const float* __restrict__ cost_T /*[dis][fn]*/,
-                                                float* __restrict__ lutT) {
+                                                float* __restrict__ out) {
     const int H = P.H, D = P.D;
     const int fn = fn_block * 64 + lane;
     const bool fn_ok = fn < D;
     const int fnc = fn_ok ? fn : D - 1;
     const float* dcol = joined + (size_t)colg * H;
-    float* lcol = lutT + (size_t)colg * (H + 1) * D;
-    if (fn_ok) lcol[fn] = 0.0f; /* arr[0] = 0, :283-285 */
+    float* lcol = out + (size_t)colg * (CARRY ? isk_lut_carry_rows(H) : H + 1) * D;
+    if (fn_ok) lcol[fn] = 0.0f; /* arr[0] = 0, :283-285 (CARRY: the carry of block 0) */
     float add = 0.0f;
     /* the per-row costs of the NEXT block are fetched before this block's 32 row stores are issued:
      * a wave's memory operations retire in order, so loads queued behind the stores would wait
@@ -696,13 +702,9 @@ __device__ __forceinline__ void object_lut_body(const DevParams& P, const int co
     /* (int)d of a block's 32 rows: one coalesced load, requested a block before its costs are (a
      * wave that is alone on its SIMD -- a single frame -- otherwise waits for two dependent memory
      * round trips per block: the disparities, then the table entries they select) */
-    auto fetch_d = [&](int i) -> float {
-        const int rl = i + (lane & (LUT_BLOCK - 1));
-        return (rl < H) ? dcol[rl] : 0.0f; /* rows beyond the image use dis = 0, :244-247 */
-    };
+    auto fetch_d = [&](int i) -> float { return lut_row_d(dcol, i + (lane & (LUT_BLOCK - 1)), H); };
     auto fetch = [&](float d_l, float (&c)[LUT_BLOCK]) {
-        int dis_l = (int)d_l;
-        dis_l = min(max(dis_l, 0), D - 1); /* memory safety outside the input domain (Q8) */
+        const int dis_l = lut_bin(d_l, D);
 #pragma unroll
         for (int l = 0; l < LUT_BLOCK; l++) { /* wave-uniform broadcasts */
             const int dis = __builtin_amdgcn_readlane(dis_l, l);
@@ -733,7 +735,9 @@ __device__ __forceinline__ void object_lut_body(const DevParams& P, const int co
 #pragma unroll
             for (int l = LUT_BLOCK - 1; l >= j; l--) c[l] += c[l - j];
         }
-        if (full) {
+        if (CARRY) {
+            if (i + LUT_BLOCK < H) __builtin_nontemporal_store(c[LUT_BLOCK - 1], &lcol[(size_t)(i / LUT_BLOCK + 1) * D + fnc]);
+        } else if (full) {
 #pragma unroll
             for (int l = 0; l < LUT_BLOCK; l++) __builtin_nontemporal_store(c[l], &lcol[(size_t)(i + l + 1) * D + fnc]); /* :266 */
         } else if (fn_ok) {
@@ -761,7 +765,23 @@ __global__ __launch_bounds__(64) void k_object_lut_repair(const DevParams P, int
     const int fn_blocks = (P.D + 63) / 64;
     for (int u = (int)blockIdx.x; u < ncols * fn_blocks; u += (int)gridDim.x) {
         const int colg = u / fn_blocks;
-        object_lut_body(P, colg, u - colg * fn_blocks, (int)threadIdx.x, joined, cost_T, lutT);
+        object_lut_body<false>(P, colg, u - colg * fn_blocks, (int)threadIdx.x, joined, cost_T, lutT);
+    }
+}
+
+/* In front of the tile launches that read the table in a walk call (k_dp_unary<.., false> for the generic-encoding
+ * columns, which the walk leaves alone): the complete table of exactly those columns.  Leaves at once while the call
+ * has none (*n_generic == 0, the normal case). */
+__global__ __launch_bounds__(64) void k_object_lut_generic(const DevParams P, int ncols, const float* __restrict__ joined,
+                                                           const float* __restrict__ cost_T, float* __restrict__ lutT,
+                                                           const int* __restrict__ col_flags,
+                                                           const int* __restrict__ n_generic) {
+    if (__builtin_amdgcn_readfirstlane(*n_generic) == 0) return;
+    const int fn_blocks = (P.D + 63) / 64;
+    for (int u = (int)blockIdx.x; u < ncols * fn_blocks; u += (int)gridDim.x) {
+        const int colg = u / fn_blocks;
+        if (__builtin_amdgcn_readfirstlane(col_flags[colg]) == 0) continue;
+        object_lut_body<false>(P, colg, u - colg * fn_blocks, (int)threadIdx.x, joined, cost_T, lutT);
     }
 }
 
@@ -775,10 +795,11 @@ __global__ __launch_bounds__(64) void k_object_lut_repair(const DevParams P, int
  * 0.325 ms) -- side by side they take the memory system from each other.  (Until the LUT loop
  * stored unconditionally its body took 166 VGPRs under this kernel's launch bounds and the fused
  * launch cost a large batch the occupancy both bodies live on: 8.2 ms.) */
+template <bool CARRY> /* lut: lutT, or CARRY: the walk's carry rows lutC (object_lut_body) */
 __global__ __launch_bounds__(PREP_THREADS) void k_prepare_fused(
     const DevParams P, int ncols, int n_lut, const float* __restrict__ joined, const int32_t* __restrict__ seg,
     const float* __restrict__ ground, const int* __restrict__ vhor_arr, const float* __restrict__ cost_T,
-    RowRec* __restrict__ recs, float* __restrict__ lutT, int* __restrict__ col_flags,
+    RowRec* __restrict__ recs, float* __restrict__ lut, int* __restrict__ col_flags,
     float* __restrict__ sv_arr, PruneRec* __restrict__ prune, int* __restrict__ n_generic) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int b = (int)blockIdx.x;
@@ -788,7 +809,7 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prepare_fused(
         const int fn_blocks = (P.D + 63) / 64;
         const int unit = lut_b * (PREP_THREADS / 64) + (int)(threadIdx.x >> 6);
         if (unit < ncols * fn_blocks)
-            object_lut_body(P, unit / fn_blocks, unit % fn_blocks, (int)(threadIdx.x & 63), joined, cost_T, lutT);
+            object_lut_body<CARRY>(P, unit / fn_blocks, unit % fn_blocks, (int)(threadIdx.x & 63), joined, cost_T, lut);
     } else {
         prepare_columns_body(P, col_b, smem, joined, seg, ground, vhor_arr, recs,
                              col_flags, sv_arr, prune, n_generic);
@@ -831,10 +852,17 @@ size_t isk_prepare_lds_bytes(const DevParams* P) {
 }
 
 hipError_t isk_launch_lut_repair(const DevParams* P, int ncols, const float* joined, const float* cost_T, float* lutT,
-                                 hipStream_t stream) {
+                                 const int* run_if, hipStream_t stream) {
     const int units = ncols * ((P->D + 63) / 64);
     hipLaunchKernelGGL(k_object_lut_repair, dim3(units < 8192 ? units : 8192), dim3(64), 0, stream, *P, ncols, joined,
-                       cost_T, lutT, P->lutf_bad);
+                       cost_T, lutT, run_if);
+    return hipGetLastError();
+}
+
+hipError_t isk_launch_lut_generic(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream) {
+    const int units = plan->ncols * ((P->D + 63) / 64);
+    hipLaunchKernelGGL(k_object_lut_generic, dim3(units < 2048 ? units : 2048), dim3(64), 0, stream, *P, plan->ncols,
+                       b->joined, b->cost_T, b->lutT, b->col_flags, b->n_generic);
     return hipGetLastError();
 }
 
@@ -848,9 +876,12 @@ hipError_t isk_launch_prepare(const DevParams* P, const CallPlan* plan, const Ca
     /* the two prepare kernels are independent: one launch with workgroups of both kinds (k_prepare_fused) */
     const int units = ncols * ((P->D + 63) / 64);
     const int n_lut = (units + PREP_THREADS / 64 - 1) / (PREP_THREADS / 64);
-    hipLaunchKernelGGL(k_prepare_fused, dim3(ncols + n_lut), dim3(PREP_THREADS), isk_prepare_lds_bytes(P), stream, *P,
-                       ncols, n_lut, b->joined, b->seg, b->ground, b->vhor, b->cost_T, b->recs, b->lutT, b->col_flags,
-                       b->sv, b->prune, b->n_generic);
+#define IS_LAUNCH_PREPARE(CARRY, LUT)                                                                                 \
+    hipLaunchKernelGGL(k_prepare_fused<CARRY>, dim3(ncols + n_lut), dim3(PREP_THREADS), isk_prepare_lds_bytes(P), stream, \
+                       *P, ncols, n_lut, b->joined, b->seg, b->ground, b->vhor, b->cost_T, b->recs, LUT, b->col_flags,  \
+                       b->sv, b->prune, b->n_generic)
+    if (plan->lut_carry) IS_LAUNCH_PREPARE(true, b->lutC); else IS_LAUNCH_PREPARE(false, b->lutT);
+#undef IS_LAUNCH_PREPARE
     return hipGetLastError();
 }
 
@@ -866,7 +897,10 @@ hipError_t isk_set_lds_prepare(const DevParams* P) {
     hipError_t e = hipFuncSetAttribute((const void*)k_prepare_columns, hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)isk_prepare_lds_bytes(P));
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute((const void*)k_prepare_fused, hipFuncAttributeMaxDynamicSharedMemorySize,
+    e = hipFuncSetAttribute((const void*)k_prepare_fused<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)isk_prepare_lds_bytes(P));
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute((const void*)k_prepare_fused<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)isk_prepare_lds_bytes(P));
 }
 

@@ -426,7 +426,9 @@ size_t isk_unary_lds_bytes(const DevParams* P) {
 /* The unary DP of a call, as plan_call decided:
  *  - the walk (is_k_unary_path.hip): the visited rows of the FAST columns, then the generic columns in full (leaves at
  *    once when the call has none), then the repair: the tile-path DP of every FAST column again, leaving at once
- *    while k_unary_path has not set path_bad.  lutT is complete (the prepare launch);
+ *    while k_unary_path has not set path_bad.  The prepare launch stored only the LUT's block carries (lutC), so each
+ *    of the two is preceded by a gated launch that builds the complete lutT of the columns it takes
+ *    (k_object_lut_generic: the generic columns; k_object_lut_repair on path_bad: every column);
  *  - the tile path: the FAST columns through k_dp_unary_fast (plan->unary_nvr) or the kernel of this file, then the
  *    generic columns. */
 hipError_t isk_launch_dp_unary(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream) {
@@ -455,13 +457,19 @@ hipError_t isk_launch_dp_unary(const DevParams* P, const CallPlan* plan, const C
             hipLaunchKernelGGL((k_dp_unary<INV, NR, true>), dim3(items), block, lds, stream, *P, ncols, b->recs,  \
                                b->lutT, b->rcp, b->vhor, b->col_flags, b->prune, b->cost_table,            \
                                b->index_table, b->n_generic, pairs_per_wg);                                \
+        if (plan->lut_carry && (e = isk_launch_lut_generic(P, plan, b, stream)) != hipSuccess) return e;  \
         hipLaunchKernelGGL((k_dp_unary<INV, NR, false>), grid_generic, block, lds, stream, *P, ncols,      \
                            b->recs, b->lutT, b->rcp, b->vhor, b->col_flags, b->prune, b->cost_table,       \
                            b->index_table, b->n_generic, pairs_per_wg);                                    \
-        if (plan->unary_walk)                                                                              \
+        if (plan->unary_walk) {                                                                            \
+            if (plan->lut_carry &&                                                                         \
+                (e = isk_launch_lut_repair(P, ncols, b->joined, b->cost_T, b->lutT, b->path_bad, stream)) != \
+                    hipSuccess)                                                                            \
+                return e;                                                                                  \
             hipLaunchKernelGGL((k_dp_unary<INV, NR, true, true>), grid_repair, block, lds, stream, *P,     \
                                ncols, b->recs, b->lutT, b->rcp, b->vhor, b->col_flags, b->prune,           \
                                b->cost_table, b->index_table, b->path_bad, pairs_per_wg);                  \
+        }                                                                                                  \
     } while (0)
     if (P->D <= 128) {
         if (P->invalid >= 0) IS_LAUNCH_UNARY(true, 2); else IS_LAUNCH_UNARY(false, 2);

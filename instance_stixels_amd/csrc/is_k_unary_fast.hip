@@ -910,7 +910,7 @@ hipError_t isk_launch_dp_unary_fast(const DevParams* P, const CallPlan* plan, co
             hipLaunchKernelGGL((k_dp_unary_fast<INV, NVR, true, true>), dim3(fused_grid), dim3(nw_win * 64),         \
                                lds_win, stream, *P, ISF_ARGS(b->counters), 0, wt, nullptr);                          \
             /* the repair launches: they leave at once unless a workgroup above set lutf_bad */                      \
-            const hipError_t er = isk_launch_lut_repair(P, ncols, b->joined, b->cost_T, b->lutT, stream);            \
+            const hipError_t er = isk_launch_lut_repair(P, ncols, b->joined, b->cost_T, b->lutT, P->lutf_bad, stream); \
             if (er != hipSuccess) return er;                                                                         \
             hipLaunchKernelGGL((k_dp_unary_fast<INV, NVR, true, false, true>),                                       \
                                dim3(groups * 8 * wt < 1536 ? groups * 8 * wt : 1536), dim3(nw_win * 64), lds_win,    \

@@ -24,9 +24,76 @@
  * that can still receive candidates is closed.  A column whose E1o is +inf (IS_NO_PRUNE, non-finite
  * weights) is walked in full.
  *
+ * The object table: the prepare launch of a walk call stores only its block carries lutC[k][fn] =
+ * lutT[32 k][fn] (CallPlan::lut_carry).  The lanes of a step are exactly LUT blocks 2 s and 2 s + 1 (lane l: candidate
+ * vB = 64 s + 1 + l, entry lutT[64 s + l + 1] = output l & 31 of block 2 s + l / 32), so the wave rebuilds the entries
+ * of a step with the reference's own 32-lane network, lanes = rows, once per distinct fn of the step (lut_network).
+ * The vT side, lutT[vT + 1][fn], is output vT & 31 of block vT / 32: picked from the first step's networks when that
+ * block is among them, otherwise built two fn at a time (lut_row_entry), and kept per row in an LDS cache.
+ *
  * What the kernel cannot reproduce it does not try to: a chosen index outside [0, vT] (every candidate of
  * the type +inf or NaN) sets *bad, and the repair launches behind this one redo the whole call on the tile
  * path.  Generic-encoding columns (col_flags != 0) are left to k_dp_unary<.., false>, as on the tile path. */
+/* One column's object table as the walk reads it: the carries, the disparities, the fn-major cost table and the
+ * LDS cache of row vT + 1 (s_tag[fn] = the row whose entry s_val[fn] holds) */
+struct LutCol {
+    const float* __restrict__ dcol;  /* [H] joined disparities */
+    const float* __restrict__ ccol;  /* [nb][D] lutC: lutT[32 k] */
+    const float* __restrict__ costF; /* [fn][dis] */
+    int* s_tag;
+    float* s_val;
+    int H, D, nb;
+};
+
+__device__ __forceinline__ float read_lane(float v, int l) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+
+/* Half h of the wave (lanes 32 h .. 32 h + 31) runs LUT block blk of fn (both per half): lane 32 h + p returns
+ * lutT[32 blk + p + 1][fn].  object_lut_body's network with lanes = rows -- the reference's own layout
+ * (StixelsKernels.cu:249-266): c = obj_cost_lut[fn][dis of row 32 blk + p], lane 0 of the half first adds the carry
+ * (c[0] += add, block 0 included), then c[p] += c[p - j] for j = 1, 2, 4, 8, 16 within the half.  The same
+ * additions on the same values: the same bits. */
+__device__ __forceinline__ float lut_network(const LutCol& L, int dis, int fn, int blk, int lane) {
+    const int p = lane & 31;
+    float c = L.costF[(size_t)fn * L.D + dis];
+    if (p == 0) c += L.ccol[(size_t)blk * L.D + fn];
+#pragma unroll
+    for (int j = 1; j < 32; j <<= 1) {
+        const float t = __shfl_up(c, j, 32);
+        if (p >= j) c += t;
+    }
+    return c;
+}
+
+/* lutT[vT + 1][fni] for the lanes in `need` (others: 0).  Cache misses are built two fn per pass, one per half,
+ * with the network of block vT / 32; disT: the bin of row 32 (vT / 32) + (lane & 31). */
+__device__ __forceinline__ float lut_row_entry(const LutCol& L, int disT, int vT, int fni, bool need, int lane) {
+    const int tag = vT + 1, kT = vT >> 5, pT = vT & 31;
+    __syncthreads(); /* (one wave) the cache writes above before its reads */
+    float v = 0.0f;
+    bool miss = false;
+    if (need) {
+        miss = L.s_tag[fni] != tag;
+        v = L.s_val[fni];
+    }
+    uint64_t m = __builtin_amdgcn_ballot_w64(miss);
+    while (m != 0ull) {
+        const int fa = __builtin_amdgcn_readlane(fni, __builtin_ctzll(m));
+        m &= ~__builtin_amdgcn_ballot_w64(fni == fa);
+        const int fb = m != 0ull ? __builtin_amdgcn_readlane(fni, __builtin_ctzll(m)) : fa;
+        m &= ~__builtin_amdgcn_ballot_w64(fni == fb);
+        const float out = lut_network(L, disT, lane < 32 ? fa : fb, kT, lane);
+        const float va = read_lane(out, pT), vb = read_lane(out, 32 + pT);
+        v = fni == fa ? va : (fni == fb ? vb : v);
+        if (lane == 0) {
+            L.s_tag[fa] = tag; L.s_val[fa] = va;
+            L.s_tag[fb] = tag; L.s_val[fb] = vb;
+        }
+    }
+    return v;
+}
+
 struct PathBest {
     float c[3];
     int v[3];
@@ -40,12 +107,13 @@ __device__ __forceinline__ void path_take(float& c, int& v, float c2, int v2) {
 }
 
 template <bool HAS_INVALID>
-__device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* __restrict__ rcol,
-                                             const float* __restrict__ lcol, const float* __restrict__ rcp,
-                                             const PruneRec& pr, int vT, int vhor, int lane) {
+__device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* __restrict__ rcol, const LutCol& L,
+                                             const float* __restrict__ rcp, const PruneRec& pr, int vT, int vhor,
+                                             int lane) {
     const int D = P.D;
     const RowRec my = load_rec(rcol + vT + 1); /* (in VGPRs: the scalar form spills SGPRs) */
-    const float* __restrict__ lrowT = lcol + (size_t)(vT + 1) * D;
+    const int disT = lut_bin(lut_row_d(L.dcol, (vT & ~31) + (lane & 31), L.H), D);
+    const int s_first = (vT - 1) >> 6;
     float bg = IS_INF, bo = IS_INF, bs = IS_INF;
     int vg = -1, vo = -1, vs = -1;
     const bool prune_on = pr.E1o < IS_INF;
@@ -57,13 +125,31 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
         const bool live = vB <= vT;
         const int vBc = live ? vB : vT;
         const RowRec rb = load_rec(rcol + vBc);
+        const int disS = lut_bin(lut_row_d(L.dcol, 64 * s + lane, L.H), D); /* rows of the step's two LUT blocks */
         const int h = vT + 1 - vBc;
         const float r = rcp[h]; /* RN(1/h) */
         const SegTerms t = eval_segment<true, HAS_INVALID>(my, rb, (float)h, r, D, P.iw, rcp);
         const float pwih = P.pw * r;
         /* cost = dw*data + pw*(1/h) + sw*seg, left to right (unary_step) */
         if (open_o) {
-            const float od = lrowT[t.fni] - lcol[(size_t)vBc * D + t.fni];
+            /* lutT[vB][fni]: one network pass per distinct fn of the live lanes; the first step of the row also
+             * leaves lutT[vT + 1][fn] (lane vT - 64 s) in the row cache */
+            const int blk = min(2 * s + (lane >> 5), L.nb - 1); /* (clamped: rows >= H only feed dead lanes) */
+            const int lT = vT - 64 * s;
+            const bool keep_row = s == s_first && lT < 64;
+            float ent = 0.0f;
+            uint64_t m = __builtin_amdgcn_ballot_w64(live);
+            while (m != 0ull) {
+                const int fn = __builtin_amdgcn_readlane(t.fni, __builtin_ctzll(m));
+                m &= ~__builtin_amdgcn_ballot_w64(t.fni == fn);
+                const float out = lut_network(L, disS, fn, blk, lane);
+                ent = t.fni == fn ? out : ent;
+                if (keep_row) {
+                    const float v = read_lane(out, lT);
+                    if (lane == 0) { L.s_tag[fn] = vT + 1; L.s_val[fn] = v; }
+                }
+            }
+            const float od = lut_row_entry(L, disT, vT, t.fni, live, lane) - ent;
             const float cost_o = P.dw * od + pwih + P.sw * t.seg_o;
             if (live && cost_o <= bo) { bo = cost_o; vo = vB; }
         }
@@ -99,7 +185,7 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
                 const SegTerms t0 = eval_segment<true, HAS_INVALID>(my, rb0, (float)h0, r0, D, P.iw, rcp);
                 const float pwih0 = P.pw * r0;
                 if (open_o) {
-                    const float od = lrowT[t0.fni] - lcol[t0.fni];
+                    const float od = lut_row_entry(L, disT, vT, t0.fni, lane == 0, lane) - 0.0f; /* lutT[0] = 0 */
                     const float cost_o = P.dw * od + pwih0 + P.sw * t0.seg_o;
                     if (lane == 0 && cost_o <= bo) { bo = cost_o; vo = 0; }
                 }
@@ -115,7 +201,7 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
         const float r0 = rcp[1];
         const SegTerms t0 = eval_segment<true, HAS_INVALID>(my, rb0, 1.0f, r0, D, P.iw, rcp);
         const float pwih0 = P.pw * r0;
-        const float od = lrowT[t0.fni] - lcol[t0.fni];
+        const float od = lut_row_entry(L, disT, vT, t0.fni, lane == 0, lane) - 0.0f; /* lutT[0] = 0 */
         const float cost_o = P.dw * od + pwih0 + P.sw * t0.seg_o;
         if (lane == 0 && cost_o <= bo) { bo = cost_o; vo = 0; }
         const float cost_g = P.dw * t0.gd + pwih0 + P.sw * t0.seg_g;
@@ -138,7 +224,8 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
 
 template <bool HAS_INVALID>
 __global__ __launch_bounds__(64) void k_unary_path(const DevParams P, int ncols, const RowRec* __restrict__ recs,
-                                                   const float* __restrict__ lutT, const float* __restrict__ rcp,
+                                                   const float* __restrict__ joined, const float* __restrict__ lutC,
+                                                   const float* __restrict__ cost_F, const float* __restrict__ rcp,
                                                    const int* __restrict__ vhor_arr, const int* __restrict__ col_flags,
                                                    const PruneRec* __restrict__ prune, float* __restrict__ cost_table,
                                                    int32_t* __restrict__ index_table, int* __restrict__ bad,
@@ -151,7 +238,15 @@ __global__ __launch_bounds__(64) void k_unary_path(const DevParams P, int ncols,
     const int H = P.H, S = P.S;
     const int vhor = __builtin_amdgcn_readfirstlane(vhor_arr[colg / P.C]);
     const RowRec* rcol = recs + (size_t)colg * (H + 1);
-    const float* lcol = lutT + (size_t)colg * (H + 1) * P.D;
+    extern __shared__ int s_lut_row[]; /* [2][D]: the row cache of lut_row_entry */
+    LutCol L;
+    L.H = H; L.D = P.D; L.nb = isk_lut_carry_rows(H);
+    L.dcol = joined + (size_t)colg * H;
+    L.ccol = lutC + (size_t)colg * L.nb * P.D;
+    L.costF = cost_F;
+    L.s_tag = s_lut_row;
+    L.s_val = (float*)(s_lut_row + P.D);
+    for (int i = lane; i < P.D; i += 64) L.s_tag[i] = -1;
     float* ct = cost_table + (size_t)colg * H * 3;
     int32_t* it = index_table + (size_t)colg * H * 3;
     PruneRec pr;
@@ -164,7 +259,7 @@ __global__ __launch_bounds__(64) void k_unary_path(const DevParams P, int ncols,
     int vT = H - 1, n = 0, type = IS_OBJECT;
     bool last = false;
     for (;;) {
-        const PathBest b = path_row<HAS_INVALID>(P, rcol, lcol, rcp, pr, vT, vhor, lane);
+        const PathBest b = path_row<HAS_INVALID>(P, rcol, L, rcp, pr, vT, vhor, lane);
         if (lane == 0) {
             ct[vT * 3 + 0] = b.c[0]; ct[vT * 3 + 1] = b.c[1]; ct[vT * 3 + 2] = b.c[2];
             it[vT * 3 + 0] = b.v[0]; it[vT * 3 + 1] = b.v[1]; it[vT * 3 + 2] = b.v[2];
@@ -192,9 +287,9 @@ extern "C" {
 
 hipError_t isk_launch_unary_path(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream) {
 #define IS_LAUNCH_PATH(INV)                                                                                        \
-    hipLaunchKernelGGL(k_unary_path<INV>, dim3(plan->ncols), dim3(64), 0, stream, *P, plan->ncols, b->recs, b->lutT, \
-                       b->rcp, b->vhor, b->col_flags, b->prune, b->cost_table, b->index_table, b->path_bad,         \
-                       plan->unary_force_bad)
+    hipLaunchKernelGGL(k_unary_path<INV>, dim3(plan->ncols), dim3(64), sizeof(float) * 2 * P->D, stream, *P,       \
+                       plan->ncols, b->recs, b->joined, b->lutC, b->cost_F, b->rcp, b->vhor, b->col_flags, b->prune, \
+                       b->cost_table, b->index_table, b->path_bad, plan->unary_force_bad)
     if (P->invalid >= 0) IS_LAUNCH_PATH(true); else IS_LAUNCH_PATH(false);
 #undef IS_LAUNCH_PATH
     return hipGetLastError();

@@ -201,6 +201,15 @@ __device__ __forceinline__ RowRec load_rec(const RowRec* p) {
     return r;
 }
 
+/* The object table's disparity of row `row` of a joined column and its cost bin (ComputeObjectLUT,
+ * StixelsKernels.cu:244-247): rows beyond the image use 0; the bin is (int)d clamped to [0, D - 1] (memory safety
+ * outside the input domain, Q8).  The table's builder (object_lut_body) and the walk's rebuild of its entries
+ * (k_unary_path) both go through these two. */
+__device__ __forceinline__ float lut_row_d(const float* __restrict__ dcol, int row, int H) {
+    return (row < H) ? dcol[row] : 0.0f;
+}
+__device__ __forceinline__ int lut_bin(float d, int D) { return min(max((int)d, 0), D - 1); }
+
 
 /* lutT rows tile_lo+1 .. tile_lo+64 of a column into the LDS tile (row stride D+1).  When the
  * workgroup covers whole rows per sweep (nthreads a multiple of D) a thread keeps its column and

@@ -43,6 +43,9 @@ static_assert(2 * IS_PW_SPLIT_MAX_COLS <= IS_PW_SPLIT_TARGET_WGS && IS_PW_MAX_SP
 
 /* ---- one DP call ---- */
 
+/* rows of a column's carry buffer lutC (CallPlan::lut_carry): the carries lutT[32 k] of the ceil(H / 32) LUT blocks */
+__host__ __device__ inline int isk_lut_carry_rows(int H) { return (H + 31) / 32; }
+
 enum { IS_P2_ONE = 0, IS_P2_SPLIT = 1, IS_P2_TWO = 2 };       /* k_pw_phase2 | k_pw_phase2s | k_pw_phase2x + generic */
 enum { IS_BT_PLAIN = 0, IS_BT_STAGED = 1, IS_BT_TWO = 2 };    /* k_backtrace<false> | <true> | <false, true> */
 
@@ -59,6 +62,7 @@ struct CallPlan {
     int lut_fused;     /* 1: the LUT units run inside the unary DP launch (LUTF) */
     /* prepare */
     int prepare_lut;   /* 1: k_prepare_fused (records + object LUT); 0: k_prepare_columns (records only) */
+    int lut_carry;     /* 1 (with unary_walk): the prepare launch stores only the LUT's block carries (lutC) */
     /* pairwise */
     int groups;        /* column groups, one stream each */
     int nsplit;        /* phase-1 workgroups per (column, tile) */
@@ -76,10 +80,12 @@ struct CallBuffers {
     const float* ground;
     const int* vhor;
     const float* cost_T;
+    const float* cost_F;
     const float* odr;
     const float* rcp;
     RowRec* recs;
     float* lutT;
+    float* lutC;
     int* col_flags;
     float* sv;
     PruneRec* prune;
@@ -109,7 +115,8 @@ hipError_t isk_launch_prepare(const DevParams* P, const CallPlan* plan, const Ca
 hipError_t isk_launch_priors(const DevParams* P, const float* ground, PriorRec* priors, int n_images,
                              hipStream_t stream);
 hipError_t isk_launch_lut_repair(const DevParams* P, int ncols, const float* joined, const float* cost_T, float* lutT,
-                                 hipStream_t stream);
+                                 const int* run_if, hipStream_t stream);
+hipError_t isk_launch_lut_generic(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream);
 
 /* is_k_unary.hip */
 size_t isk_unary_lds_bytes(const DevParams* P);
