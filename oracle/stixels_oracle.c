@@ -2,8 +2,7 @@
  * stixels_oracle.c -- CPU restatement of the reference's column-DP hot path.
  *
  * TEST INFRASTRUCTURE ONLY (see stixels_oracle.h for the rules and the parity-pin status:
- * "parity unpinned" beyond the scan / column-join known answers of the reference's own
- * disabled unit tests).
+ * pinned against the reference's own code built for gfx950, tests/test_reference_gpu.py).
  *
  * The restatement follows the reference's SIMT structure literally: every region between
  * two __syncthreads() of the CUDA kernel becomes a loop over the block's threads, every

@@ -5,13 +5,15 @@
  * include, link or call this; only tests/, __graft_entry__.smoke() and bench.py's
  * cpu_baseline leg do.
  *
- * PARITY PIN STATUS: "parity unpinned" beyond the two known-answer patterns that the
- * reference's own (disabled) unit tests hold -- the exclusive-scan identity and the
- * column-join layout (InstanceStixels/tests/generate_testdata.py:51-62), see
- * tests/test_oracle_kat.py.  The reference is CUDA (no nvcc, no NVIDIA GPU in this image) and
- * building it needs stand-ins for CUDA/cuML headers, so it is treated as unbuildable here;
- * its end-to-end regression (tests/run_test.sh) needs Cityscapes + weights.  Every function
- * below therefore cites the reference file:line it restates so it can be audited by reading.
+ * PARITY PIN STATUS: pinned against the reference's own code.  `make -C oracle ref` hipifies
+ * the reference and builds it for gfx950 (oracle/_ref/, oracle/ref_shim.h for the numerics
+ * substitutions: width-32 shuffles, __logf / device logf = is_logf, host logf = libm);
+ * tests/test_reference_gpu.py compares this oracle, the HIP path and the reference bit for bit
+ * (Sections, joined disparity, object LUT, instance candidates, v-disparity), and
+ * tests/golden/reference_hip/ keeps recorded reference outputs that
+ * tests/test_oracle_vs_reference_golden.py checks on the CPU.  Not pinned here: DBSCAN labels
+ * (pinned on the reference's Python) and the Hough step of RoadEstimation.cu.  Every function
+ * below cites the reference file:line it restates so it can be audited by reading.
  */
 #ifndef STIXELS_ORACLE_H_
 #define STIXELS_ORACLE_H_
