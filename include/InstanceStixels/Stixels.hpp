@@ -144,6 +144,39 @@ public:
                                                                      void* stream = nullptr);
     /* Records per frame of InstanceOverlapBatch's first pass (default 4096; [1, IS_OVERLAP_MAX_CAPACITY]). */
     void SetInstanceOverlapCapacity(int records);
+    /* f7 (an addition): the 3-D stixel world of frames 0 .. n_images-1 of the LAST Compute() or ComputeBatch() --
+     * per stixel one is_world_stixel (instance_stixels_core.h): its Section fields, its column and index, the
+     * cluster label GetInstanceStixels() gives it (-1: none; every id is -1 after a call without instances) and the
+     * twelve floats Get3DVertices() gives it, for the road parameters of that call.  Frame f's records are
+     * stixels[frame_offsets[f] .. frame_offsets[f + 1]), in (column, section) order.  Built on the device and
+     * brought to the host compacted: the frame totals, then exactly the used records, through pinned memory.
+     * Throws std::invalid_argument before any compute under RenderBatch's rules, and "Camera parameters are not
+     * set." under Get3DVertices' condition.  (A column WITHOUT a terminator, which no compute call leaves, gives
+     * max_sections - 1 records, as is_pack_sections packs it, where Get3DVertices walks all max_sections slots.) */
+    struct World {
+        std::vector<int32_t> frame_offsets; /* [n_images + 1] */
+        std::vector<is_world_stixel> stixels;
+    };
+    /* By value: every call allocates the result anew.  At batch 64 of 1024x2048 that is ~89 MB of fresh pages per
+     * call, and this form then measured SLOWER than the host composition it replaces: a
+     * caller that runs batch after batch uses one of the two forms below. */
+    World WorldBatch(int n_images, void* stream = nullptr);
+    /* The same into a caller's World, whose vectors keep their capacity from call to call: one copy out of the
+     * pinned buffer into warm pages per batch. */
+    void WorldBatch(int n_images, World& world, void* stream = nullptr);
+    /* The same without that copy: the records where the device-to-host copy left them, in the object's pinned
+     * buffer, readable until the next WorldBatch*() or Finish() of this object (what ish_world_batch and the
+     * Python binding read, straight into the caller's array).  frame_offsets: [n_images + 1]. */
+    const is_world_stixel* WorldBatchView(int n_images, std::vector<int32_t>& frame_offsets, void* stream = nullptr);
+    /* n records from a view into the caller's array: the copy of WorldBatch(n, world), split over up to 8 host
+     * threads from 8 MB on (one thread copies a 64-frame batch in ~3.4 ms, longer than the device takes to build
+     * and deliver it). */
+    static void CopyWorldRecords(is_world_stixel* dst, const is_world_stixel* src, size_t n);
+    /* Records per frame the device buffer of WorldBatch's first pass holds.  Without it (and again after
+     * SetWorldCapacity(0)) the buffer has the exact size where the last call was a ComputeBatch (which has counted
+     * its sections; then the totals and the records travel behind ONE synchronisation) and 4096 records per frame
+     * after a Compute().  A batch that needs more is repeated with its true total: the result is always complete. */
+    void SetWorldCapacity(int records_per_frame);
     /* Introspection for tests / bench. */
     const StixelParameters& GetParameters() const { return m_params; }
     const std::vector<float>& GetObjectCostLUT() const { return m_obj_cost_lut; }
@@ -233,6 +266,19 @@ private:
     DeviceArray<int32_t> d_overlap_header;   /* [max_batch] n_records | [max_batch] overflow */
     PinnedArray<int32_t> h_overlap_header;
     PinnedArray<is_overlap_record> h_overlap_packed;
+    /* WorldBatch: the road parameters of the last compute call (library-convention vhor) and, after a
+     * ComputeBatch, the section totals in front of every frame ([n + 1], else empty); the per-column counts and
+     * offsets, the frame totals and the records (device and pinned host, allocated on first use, grown on demand) */
+    std::vector<float> m_world_alpha;
+    std::vector<int> m_world_vhor;
+    std::vector<int32_t> m_world_known_offsets;
+    int m_world_capacity = 0; /* records per frame of SetWorldCapacity; 0: not set */
+    DeviceArray<int32_t> d_world_counts;   /* [max_batch * realcols] */
+    DeviceArray<int32_t> d_world_offsets;  /* [max_batch * realcols + 1] */
+    DeviceArray<int32_t> d_world_totals;   /* [max_batch] */
+    DeviceArray<is_world_stixel> d_world;
+    PinnedArray<int32_t> h_world_totals;
+    PinnedArray<is_world_stixel> h_world;
     /* every device operation of the object runs on this stream (an ordinary stream: it still
      * synchronises with work the caller queued on the legacy NULL stream, like the reference's
      * default-stream code; on the NULL stream itself the auxiliary streams of the core never

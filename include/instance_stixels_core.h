@@ -402,6 +402,60 @@ int is_instance_overlap(const is_instance_overlap_args* args, void* stream);
 int is_pack_overlap_records(const is_overlap_record* d_records, const int32_t* d_n_records, int n_images,
                             int capacity, is_overlap_record* d_packed, void* stream);
 
+/* ---- f7: the 3-D stixel world of a batch, one record per stixel (is_k_world.hip) ------------------------------
+ * What the reference's live path hands on per frame (apps/stixels_node.cu:74-208: Compute -> GetInstanceStixels ->
+ * Get3DVertices -> populateStixelsArray): the fields of its InstanceStixel message plus what SaveStixels writes, for
+ * every section in front of a column's terminator, in (image, column, section) order.  96 bytes = six 16-byte
+ * chunks; the device writes a record as 16-byte stores, so d_world must be 16-byte aligned (the struct itself has
+ * the natural alignment of its 4-byte fields; hipMalloc, pinned and numpy allocations all qualify). */
+typedef struct is_world_stixel {
+    int32_t column, section;   /* stixel column of its frame; index inside the column */
+    int32_t type, vB, vT, semantic_class;
+    int32_t instance_id;       /* the d_section_instance value, -1 = none (also with a NULL map) */
+    float disparity, cost, instance_meanx, instance_meany;
+    float vertices[12];        /* Get3DVertices order: TL, TR, BR, BL, each (x, y, z) */
+    int32_t reserved;          /* 0 */
+} is_world_stixel;
+#ifdef __cplusplus
+static_assert(sizeof(is_world_stixel) == 96, "is_world_stixel is six 16-byte chunks");
+#else
+_Static_assert(sizeof(is_world_stixel) == 96, "is_world_stixel is six 16-byte chunks");
+#endif
+
+/* Zero-initialise before setting fields.  All device arrays are on the current device.
+ *   d_sections, d_section_instance, n_images, realcols, max_sections   as in is_render_args, with max_sections in
+ *                       [2, 32767] and n_images * realcols * max_sections < 2^31; the map may be NULL
+ *   rows, column_step   of the frame (Get3DVertices: x = column * column_step, y from rows)
+ *   focal, baseline, camera_center_x, camera_center_y   the camera of SetCameraParameters
+ *   h_alpha_ground, h_vhor   host [n_images]: the road of every frame, vhor in the library's convention
+ *                       (StixelsData::vhor); read before the call returns
+ *   capacity            records d_world holds (>= 0; d_world may be NULL when it is 0)
+ *   d_counts            [n_columns] (n_columns = n_images * realcols), d_offsets [n_columns + 1]: exactly what
+ *                       is_pack_sections writes there -- d_offsets[n_columns] is the TRUE total of the batch
+ *   d_frame_totals      [n_images] records of every frame
+ *   d_world             record r of the batch at index r for r < capacity; nothing is written at or beyond
+ *                       `capacity`, the caller sees the overflow in the total and repeats
+ * The records are those of the sections is_pack_sections packs.  vertices: the fp32 expressions of
+ * Stixels::Get3DVertices (reference Stixels.cu:683-742) in its operand order: sky keeps depth 0, a zero
+ * disparity (an object's, or ground at vhor) gives the host's +-inf, and NaN where the host has NaN. */
+typedef struct is_world_args {
+    const is_section* d_sections;
+    const int32_t* d_section_instance;
+    int n_images, realcols, max_sections, rows, column_step;
+    float focal, baseline, camera_center_x, camera_center_y;
+    const float* h_alpha_ground;
+    const int* h_vhor;
+    int capacity;
+    int32_t* d_counts;
+    int32_t* d_offsets;
+    int32_t* d_frame_totals;
+    is_world_stixel* d_world;
+} is_world_args;
+
+/* The world of n_images frames on `stream`, asynchronously: no host synchronisation, no allocation (two launches
+ * for the counts and offsets, one per 64 frames for the records). */
+int is_stixel_world(const is_world_args* args, void* stream);
+
 /* Thin wrappers over the HIP runtime so that the plain-C++ host class needs no HIP headers
  * (the reference's callers are all .cu files; ours may be plain C++). */
 int is_device_malloc(void** ptr, size_t bytes);

@@ -32,6 +32,7 @@ EXPORTS = [
     "is_road_vdisparity_batch", "is_road_hough_batch",
     "is_section_instance_labels", "is_render_sections",
     "is_instance_overlap", "is_pack_overlap_records",
+    "is_stixel_world",
 ]
 RENDER_MAX_LABELS = 64    # IS_RENDER_MAX_LABELS
 RENDER_MAX_CLASSES = 256  # IS_RENDER_MAX_CLASSES
@@ -62,6 +63,34 @@ class InstanceOverlapArgs(ctypes.Structure):
     _fields_ = [("d_sections", vp), ("d_section_instance", vp), ("n_images", ci), ("realcols", ci),
                 ("max_sections", ci), ("rows", ci), ("cols", ci), ("d_gt_instance", vp), ("capacity", ci),
                 ("d_records", vp), ("d_n_records", vp), ("d_overflow", vp)]
+
+
+# is_world_stixel: one stixel of the 3-D world of a frame (is_stixel_world, Stixels::WorldBatch), 96 bytes
+WORLD_DTYPE = np.dtype([
+    ("column", np.int32), ("section", np.int32), ("type", np.int32), ("vB", np.int32), ("vT", np.int32),
+    ("semantic_class", np.int32), ("instance_id", np.int32), ("disparity", np.float32), ("cost", np.float32),
+    ("instance_meanx", np.float32), ("instance_meany", np.float32), ("vertices", np.float32, (12,)),
+    ("reserved", np.int32),
+])
+assert WORLD_DTYPE.itemsize == 96
+
+
+class WorldStixel(ctypes.Structure):
+    """is_world_stixel, for the layout checks of the tests."""
+    _fields_ = [("column", ctypes.c_int32), ("section", ctypes.c_int32), ("type", ctypes.c_int32),
+                ("vB", ctypes.c_int32), ("vT", ctypes.c_int32), ("semantic_class", ctypes.c_int32),
+                ("instance_id", ctypes.c_int32), ("disparity", ctypes.c_float), ("cost", ctypes.c_float),
+                ("instance_meanx", ctypes.c_float), ("instance_meany", ctypes.c_float),
+                ("vertices", ctypes.c_float * 12), ("reserved", ctypes.c_int32)]
+
+
+class WorldArgs(ctypes.Structure):
+    """is_world_args: zero-initialised by ctypes; device pointers as ints, h_* host pointers."""
+    vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    _fields_ = [("d_sections", vp), ("d_section_instance", vp), ("n_images", ci), ("realcols", ci),
+                ("max_sections", ci), ("rows", ci), ("column_step", ci), ("focal", cf), ("baseline", cf),
+                ("camera_center_x", cf), ("camera_center_y", cf), ("h_alpha_ground", vp), ("h_vhor", vp),
+                ("capacity", ci), ("d_counts", vp), ("d_offsets", vp), ("d_frame_totals", vp), ("d_world", vp)]
 
 
 class CoreError(RuntimeError):
@@ -116,6 +145,7 @@ def lib():
         L.is_render_sections.argtypes = [ctypes.POINTER(RenderArgs), vp]
         L.is_instance_overlap.argtypes = [ctypes.POINTER(InstanceOverlapArgs), vp]
         L.is_pack_overlap_records.argtypes = [vp, vp, ci, ci, vp, vp]
+        L.is_stixel_world.argtypes = [ctypes.POINTER(WorldArgs), vp]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
         L.is_get_device.argtypes = [ctypes.POINTER(ci)]
@@ -404,6 +434,16 @@ def instance_overlap_ptr(stream=0, **fields):
     on `stream`."""
     a = InstanceOverlapArgs(**fields)
     _check(lib().is_instance_overlap(ctypes.byref(a), ctypes.c_void_p(int(stream))), "is_instance_overlap")
+
+
+def stixel_world_ptr(alpha_ground, vhor, stream=0, **fields):
+    """is_stixel_world on raw device pointers (ints): fields are those of WorldArgs; alpha_ground / vhor: the road
+    of every frame (host sequences, library-convention vhor).  Asynchronous on `stream`."""
+    a = WorldArgs(**fields)
+    alpha = np.ascontiguousarray(alpha_ground, np.float32)
+    vh = np.ascontiguousarray(vhor, np.int32)
+    a.h_alpha_ground, a.h_vhor = alpha.ctypes.data, vh.ctypes.data
+    _check(lib().is_stixel_world(ctypes.byref(a), ctypes.c_void_p(int(stream))), "is_stixel_world")
 
 
 def flip_and_pad(cnn_out, rows_power2_segmentation, device=0):

@@ -722,6 +722,26 @@ int is_pack_overlap_records(const is_overlap_record* d_records, const int32_t* d
     return IS_OK;
 }
 
+/* ---- f7: the stixel world (is_k_world.hip) ---- */
+int is_stixel_world(const is_world_args* a, void* stream) {
+    if (!a) return fail_arg("null args");
+    if (a->n_images < 1 || a->realcols < 1 || a->rows < 1 || a->column_step < 1)
+        return fail_arg("bad shape (n_images >= 1, realcols >= 1, rows >= 1, column_step >= 1)");
+    if (a->max_sections < 2 || a->max_sections > 32767) return fail_arg("max_sections outside [2, 32767]");
+    if ((long long)a->n_images * a->realcols * a->max_sections > 0x7fffffffLL)
+        return fail_arg("n_images * realcols * max_sections does not fit 31 bits");
+    if (a->capacity < 0) return fail_arg("negative capacity");
+    if (!a->d_sections || !a->d_counts || !a->d_offsets || !a->d_frame_totals) return fail_arg("null sections or output");
+    if (!a->h_alpha_ground || !a->h_vhor) return fail_arg("null road parameters");
+    if (a->capacity > 0 && !a->d_world) return fail_arg("null d_world with a capacity");
+    if (((uintptr_t)a->d_sections | (uintptr_t)a->d_world) & 15) return fail_arg("d_sections and d_world must be 16-byte aligned");
+    if (((uintptr_t)a->d_section_instance | (uintptr_t)a->d_counts | (uintptr_t)a->d_offsets |
+         (uintptr_t)a->d_frame_totals) & 3)
+        return fail_arg("d_section_instance, d_counts, d_offsets and d_frame_totals must be 4-byte aligned");
+    HIP_TRY(isk_launch_world(a, (hipStream_t)stream));
+    return IS_OK;
+}
+
 static_assert(IS_CNT_N == IS_EVAL_COUNTERS, "is_device.h and instance_stixels_core.h disagree on the counter array");
 
 int is_set_eval_counters(is_ctx* c, int enabled) {

@@ -91,11 +91,20 @@ __global__ __launch_bounds__(256) void k_unpack_sections(const int32_t* __restri
 
 extern "C" {
 
+/* counts [n_columns] and offsets [n_columns + 1] of the columns' used sections (also for is_k_world.hip) */
+hipError_t isk_launch_count_sections(const is_section* sections, int n_columns, int S, int32_t* counts,
+                                     int32_t* offsets, hipStream_t stream) {
+    hipLaunchKernelGGL(k_count_sections, dim3((n_columns + 3) / 4), dim3(256), 0, stream, sections, n_columns, S,
+                       counts);
+    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(PK_SCAN_THREADS), 0, stream, counts, n_columns, offsets);
+    return hipGetLastError();
+}
+
 hipError_t isk_launch_pack(const is_section* sections, int n_columns, int S, int32_t* counts,
                            int32_t* offsets, is_section* packed, hipStream_t stream) {
     const dim3 grid((n_columns + 3) / 4);
-    hipLaunchKernelGGL(k_count_sections, grid, dim3(256), 0, stream, sections, n_columns, S, counts);
-    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(PK_SCAN_THREADS), 0, stream, counts, n_columns, offsets);
+    const hipError_t e = isk_launch_count_sections(sections, n_columns, S, counts, offsets, stream);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_scatter_sections, grid, dim3(256), 0, stream, sections, n_columns, S, counts,
                        offsets, packed);
     return hipGetLastError();

@@ -164,6 +164,8 @@ hipError_t isk_launch_vdisparity(const float* disparity, int* vdisp, int* maximu
                                  int cols, int max_dis, float threshold, hipStream_t stream);
 
 /* is_k_pack.hip */
+hipError_t isk_launch_count_sections(const is_section* sections, int n_columns, int S, int32_t* counts,
+                                     int32_t* offsets, hipStream_t stream);
 hipError_t isk_launch_pack(const is_section* sections, int n_columns, int S, int32_t* counts, int32_t* offsets,
                            is_section* packed, hipStream_t stream);
 hipError_t isk_launch_unpack(const int32_t* counts, int32_t* offsets, const is_section* packed, int n_columns, int S,
@@ -191,6 +193,9 @@ hipError_t isk_launch_render(const is_render_args* r, const uint8_t* table, int 
 hipError_t isk_launch_instance_overlap(const is_instance_overlap_args* r, hipStream_t stream);
 hipError_t isk_launch_pack_overlap(const is_overlap_record* records, const int32_t* n_records, int n_images,
                                    int capacity, is_overlap_record* packed, hipStream_t stream);
+
+/* is_k_world.hip */
+hipError_t isk_launch_world(const is_world_args* w, hipStream_t stream);
 
 } /* extern "C" */
 

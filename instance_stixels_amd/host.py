@@ -31,7 +31,9 @@ EXPORTS = [
     "ish_get_input_disparity_on_device", "ire_compute_batch", "ire_set_batch_limits", "ire_batch_fallbacks",
     "ish_render_batch",
     "ish_instance_overlap_batch", "ish_instance_overlap_records", "ish_set_instance_overlap_capacity",
+    "ish_world_batch", "ish_world_records", "ish_set_world_capacity",
 ]
+WORLD_DTYPE = _core.WORLD_DTYPE  # is_world_stixel, the records of Stixels.WorldBatch
 
 # Stixels::RoadParameters, what RoadEstimation::ComputeBatch writes per frame
 ROAD_PARAMETERS_DTYPE = np.dtype([("vhor", np.int32), ("camera_tilt", np.float32),
@@ -109,6 +111,9 @@ def lib():
         L.ish_instance_overlap_batch.argtypes = [vp, ci, vp, vp, vp]
         L.ish_instance_overlap_records.argtypes = [vp, vp, ctypes.c_int64]
         L.ish_set_instance_overlap_capacity.argtypes = [vp, ci]
+        L.ish_world_batch.argtypes = [vp, ci, vp, vp]
+        L.ish_world_records.argtypes = [vp, vp, ctypes.c_int64]
+        L.ish_set_world_capacity.argtypes = [vp, ci]
         L.ish_get_input_disparity_on_device.restype = vp
         _LIB = L
     return _LIB
@@ -319,6 +324,30 @@ class Stixels:
     def SetInstanceOverlapCapacity(self, records):
         """Records per frame of InstanceOverlapBatch's first pass (frames beyond it are repeated with more)."""
         self._check(lib().ish_set_instance_overlap_capacity(self._h, int(records)), "SetInstanceOverlapCapacity")
+
+    def WorldBatch(self, n, stream=0, out=None):
+        """Stixels::WorldBatch: the 3-D stixel world of frames 0 .. n-1 of the last Compute() / ComputeBatch(),
+        built on the device: (frame_offsets [n+1] int32, records) with records a numpy array of WORLD_DTYPE
+        (is_world_stixel) in (frame, column, section) order; frame f is records[frame_offsets[f]:frame_offsets[f+1]].
+        The records are copied ONCE on the host, out of the object's pinned buffer.  out: a C-contiguous WORLD_DTYPE
+        array the caller keeps from batch to batch; where it holds the batch, records is a view of its head and no
+        memory is allocated (a fresh array of a 64-frame batch at 1024x2048 is ~89 MB of new pages per call, which
+        costs more than the copy itself)."""
+        n = int(n)
+        offsets = np.zeros(max(n, 0) + 1, np.int32)
+        self._check(lib().ish_world_batch(self._h, n, offsets.ctypes.data, ctypes.c_void_p(int(stream))),
+                    "WorldBatch")
+        total = int(offsets[-1])
+        if out is not None and (out.dtype != WORLD_DTYPE or out.ndim != 1 or not out.flags.c_contiguous):
+            raise ValueError("WorldBatch: out must be a C-contiguous 1-D array of WORLD_DTYPE")
+        records = out[:total] if out is not None and out.size >= total else np.empty(total, WORLD_DTYPE)
+        self._check(lib().ish_world_records(self._h, records.ctypes.data if total else None, total), "WorldBatch")
+        return offsets, records
+
+    def SetWorldCapacity(self, records_per_frame):
+        """Records per frame of WorldBatch's first pass (a batch beyond it is repeated with its true total);
+        0: back to the default, the exact size after a ComputeBatch and 4096 per frame after a Compute()."""
+        self._check(lib().ish_set_world_capacity(self._h, int(records_per_frame)), "SetWorldCapacity")
 
     def GetInstanceStixels(self):
         cap = self.GetRealCols() * self.GetMaxSections()

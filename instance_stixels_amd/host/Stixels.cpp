@@ -16,6 +16,7 @@
 #include <iostream>
 #include <stdexcept>
 #include <string>
+#include <thread>
 
 #include "DeviceGuard.h"
 
@@ -363,6 +364,9 @@ void Stixels::Finish() { /* Stixels.cu:250-283 */
     d_section_instance.release(); d_render_results.release(); h_render_results.release();
     d_overlap_records.release(); d_overlap_packed.release(); h_overlap_packed.release();
     d_overlap_header.release(); h_overlap_header.release();
+    d_world_counts.release(); d_world_offsets.release(); d_world_totals.release(); d_world.release();
+    h_world_totals.release(); h_world.release();
+    m_world_known_offsets.clear();
     m_render_images = 0;
     m_render_instances = false;
     IS_CHECK_RETURN(is_ctx_destroy(m_ctx));
@@ -440,6 +444,9 @@ float Stixels::Compute(const bool pairwise, StixelsData& stixels_data,
                                m_stream)); /* :535-590 */
     m_render_images = 1;
     m_render_instances = true;
+    m_world_alpha.assign(1, m_alpha_ground);
+    m_world_vhor.assign(1, m_vhor);
+    m_world_known_offsets.clear();
     /* results into pinned memory, ONE copy and ONE synchronisation (:600, :629-633): the header
      * row(s) with the per-class counts and the first m_head_sections sections of every column (a
      * column rarely has more: 10-40 on road scenes) */
@@ -566,6 +573,10 @@ void Stixels::ComputeBatch(bool pairwise, int n_images, const pixel_t* d_big,
                                instance_stixels ? ibs.data() : nullptr, nullptr, nullptr, stream));
     m_render_images = n_images;
     m_render_instances = instance_stixels != nullptr;
+    m_world_alpha.resize(n_images);
+    for (int i = 0; i < n_images; i++) m_world_alpha[i] = road[i].alpha_ground;
+    m_world_vhor = vh;
+    m_world_known_offsets.clear();
     /* Results to the host COMPACTED and through pinned memory: a column uses 10-60 of its 200 slots, and the
      * reference's fixed-stride copy (Stixels.cu:629-633: one frame) would move 1.6 MB per frame into pageable
      * vectors.  is_pack_sections leaves per-column offsets + the used sections; two pinned copies (the offsets, then
@@ -581,6 +592,8 @@ void Stixels::ComputeBatch(bool pairwise, int n_images, const pixel_t* d_big,
                                       (size_t)n_images * m_instance_classes * sizeof(int32_t), stream));
     IS_CHECK_RETURN(is_stream_synchronize(stream));
     const size_t total = (size_t)offsets[ncols];
+    m_world_known_offsets.resize(n_images + 1);
+    for (int i = 0; i <= n_images; i++) m_world_known_offsets[i] = offsets[(size_t)i * m_realcols];
     if (total > h_pack_sections.capacity()) h_pack_sections.reserve(total + total / 4 + 1024);
     if (total > 0)
         IS_CHECK_RETURN(is_memcpy_d2h(h_pack_sections.get(), d_pack_sections.get(), total * sizeof(Section), stream));
@@ -781,6 +794,118 @@ std::vector<std::vector<is_overlap_record>> Stixels::InstanceOverlapBatch(int n_
         }
     }
     return out;
+}
+
+void Stixels::SetWorldCapacity(int records_per_frame) {
+    if (records_per_frame < 0 || records_per_frame > m_realcols * (m_max_sections - 1))
+        throw std::invalid_argument("SetWorldCapacity: records_per_frame outside [0, realcols * (max_sections - 1)].");
+    m_world_capacity = records_per_frame;
+}
+
+Stixels::World Stixels::WorldBatch(int n_images, void* stream) {
+    World w;
+    WorldBatch(n_images, w, stream);
+    return w;
+}
+
+void Stixels::WorldBatch(int n_images, World& w, void* stream) {
+    const is_world_stixel* records = WorldBatchView(n_images, w.frame_offsets, stream);
+    w.stixels.resize((size_t)w.frame_offsets[n_images]);
+    CopyWorldRecords(w.stixels.data(), records, w.stixels.size());
+}
+
+void Stixels::CopyWorldRecords(is_world_stixel* dst, const is_world_stixel* src, size_t n) {
+    const size_t per_thread = ((size_t)1 << 20) / sizeof(is_world_stixel) * 8; /* 8 MB of records */
+    const size_t parts = std::min<size_t>(8, n / per_thread);
+    if (parts < 2) {
+        if (n) std::memcpy(dst, src, n * sizeof(is_world_stixel));
+        return;
+    }
+    std::vector<std::thread> pool;
+    for (size_t t = 0; t < parts; t++) {
+        const size_t lo = n * t / parts, hi = n * (t + 1) / parts;
+        pool.emplace_back([=] { std::memcpy(dst + lo, src + lo, (hi - lo) * sizeof(is_world_stixel)); });
+    }
+    for (auto& t : pool) t.join();
+}
+
+const is_world_stixel* Stixels::WorldBatchView(int n_images, std::vector<int32_t>& frame_offsets, void* stream) {
+    if (m_render_images == 0)
+        throw std::invalid_argument("WorldBatch exports the Sections of the last Compute() or ComputeBatch(): "
+                                    "there are none.");
+    if (n_images < 1 || n_images > m_render_images)
+        throw std::invalid_argument("WorldBatch: n_images outside [1, frames of the last compute call].");
+    if (m_camera_center_x == -1 || m_camera_center_y == -1)
+        throw std::invalid_argument("Camera parameters are not set.");
+    const DeviceGuard guard(m_ctx_device);
+    if (stream == nullptr) stream = m_stream;
+    const size_t B = (size_t)m_max_batch;
+    const size_t frame_max = (size_t)m_realcols * (m_max_sections - 1);
+    d_world_counts.reserve(B * m_realcols);
+    d_world_offsets.reserve(B * m_realcols + 1);
+    d_world_totals.reserve(B);
+    h_world_totals.reserve(B);
+    /* the first pass: the exact size where the last call counted its sections, else a capacity per frame */
+    const bool known = m_world_capacity == 0 && !m_world_known_offsets.empty();
+    size_t cap = known ? (size_t)m_world_known_offsets[n_images]
+                       : std::min((size_t)(m_world_capacity ? m_world_capacity : 4096), frame_max) * n_images;
+    is_world_args a = {};
+    a.d_sections = (const is_section*)d_stixels;
+    if (m_render_instances) { /* the cluster labels of every frame as a per-section map */
+        d_section_instance.reserve(B * m_realcols * m_max_sections);
+        std::vector<is_instance_buffers> ibs;
+        for (int i = 0; i < n_images; i++) ibs.push_back(InstanceBuffers(i));
+        IS_CHECK_RETURN(is_section_instance_labels(ibs.data(), n_images, m_realcols, m_max_sections,
+                                                   d_section_instance.get(), stream));
+        a.d_section_instance = d_section_instance.get();
+    }
+    a.n_images = n_images;
+    a.realcols = m_realcols;
+    a.max_sections = m_max_sections;
+    a.rows = m_rows;
+    a.column_step = m_column_step;
+    a.focal = m_focal;
+    a.baseline = m_baseline;
+    a.camera_center_x = m_camera_center_x;
+    a.camera_center_y = m_camera_center_y;
+    a.h_alpha_ground = m_world_alpha.data();
+    a.h_vhor = m_world_vhor.data();
+    a.d_counts = d_world_counts.get();
+    a.d_offsets = d_world_offsets.get();
+    a.d_frame_totals = d_world_totals.get();
+    const int32_t* totals = h_world_totals.get();
+    size_t total = 0;
+    for (int pass = 0;; pass++) {
+        d_world.reserve(cap);
+        a.capacity = (int)cap;
+        a.d_world = d_world.get();
+        const int rc = is_stixel_world(&a, stream);
+        if (rc == IS_EINVAL) throw std::invalid_argument(std::string("WorldBatch: ") + is_last_error());
+        IS_CHECK_RETURN(rc);
+        IS_CHECK_RETURN(is_memcpy_d2h(h_world_totals.get(), d_world_totals.get(), n_images * sizeof(int32_t), stream));
+        if (known && pass == 0 && cap > 0) { /* the records ride behind the totals: one synchronisation */
+            h_world.reserve(cap);
+            IS_CHECK_RETURN(is_memcpy_d2h(h_world.get(), d_world.get(), cap * sizeof(is_world_stixel), stream));
+        }
+        IS_CHECK_RETURN(is_stream_synchronize(stream));
+        total = 0;
+        for (int i = 0; i < n_images; i++) total += (size_t)totals[i];
+        if (total <= cap) {
+            if (!(known && pass == 0) && total > 0) {
+                h_world.reserve(total + total / 4);
+                IS_CHECK_RETURN(is_memcpy_d2h(h_world.get(), d_world.get(), total * sizeof(is_world_stixel), stream));
+                IS_CHECK_RETURN(is_stream_synchronize(stream));
+            }
+            break;
+        }
+        if (pass > 0 || total > frame_max * n_images)
+            throw std::runtime_error("WorldBatch: the batch holds more records than its columns can.");
+        cap = total; /* overflow: again, with the true total */
+    }
+    frame_offsets.resize(n_images + 1);
+    frame_offsets[0] = 0;
+    for (int i = 0; i < n_images; i++) frame_offsets[i + 1] = frame_offsets[i] + totals[i];
+    return h_world.get();
 }
 
 /* The shard of this rank, then the compacted gather of every rank's Sections on `dst` (the

@@ -318,6 +318,38 @@ int ish_set_instance_overlap_capacity(void* h, int records) {
     return guard([&] { ((Stixels*)h)->SetInstanceOverlapCapacity(records); });
 }
 
+/* WorldBatch(): the records of frames 0 .. n-1 of the last Compute() / ComputeBatch().  frame_offsets: host
+ * [n + 1].  The records stay in the object's pinned buffer (Stixels::WorldBatchView) until ish_world_records copies
+ * them into the caller's array (cap in records, sized from frame_offsets[n]; an array the caller keeps from batch to
+ * batch costs no fresh pages): ONE copy on the host.  Both calls from the same thread, nothing of this object in
+ * between. */
+namespace {
+thread_local const is_world_stixel* g_world = nullptr;
+thread_local int64_t g_world_n = 0;
+thread_local void* g_world_owner = nullptr;
+}
+int ish_world_batch(void* h, int n, int32_t* frame_offsets, void* stream) {
+    return guard([&] {
+        g_world_owner = nullptr;
+        std::vector<int32_t> offsets;
+        g_world = ((Stixels*)h)->WorldBatchView(n, offsets, stream);
+        std::memcpy(frame_offsets, offsets.data(), offsets.size() * sizeof(int32_t));
+        g_world_n = offsets[n];
+        g_world_owner = h;
+    });
+}
+int ish_world_records(void* h, is_world_stixel* out, int64_t cap) {
+    return guard([&] {
+        if (h != g_world_owner || g_world_n > cap)
+            throw std::invalid_argument("ish_world_records: no records of this object, or cap too small.");
+        Stixels::CopyWorldRecords(out, g_world, (size_t)g_world_n);
+        g_world_owner = nullptr;
+    });
+}
+int ish_set_world_capacity(void* h, int records_per_frame) {
+    return guard([&] { ((Stixels*)h)->SetWorldCapacity(records_per_frame); });
+}
+
 int ish_set_device(void* h, int device) {
     return guard([&] { ((Stixels*)h)->SetDevice(device); });
 }
