@@ -86,7 +86,7 @@ struct is_ctx {
     int* d_col_flags;        /* [max_batch*C] 0 = FAST column, see RowRec */
     PruneRec* d_prune;       /* [max_batch*C] branch-and-bound slacks of the column */
     int* d_n_generic;        /* [1] generic-encoding columns of the current call */
-    int* d_path_bad;         /* [2] k_unary_path's distrust word of the current call, calls repaired (k_backtrace) */
+    int* d_path_bad;         /* [2] k_unary_path's distrust word of the current call (cleared by the next prepare launch), calls repaired (k_backtrace) */
     int last_unary_path = -1; /* the unary DP of the last unary call: 1 = k_unary_path, 0 = tile path (CallPlan::unary_walk) */
     /* per-call device inputs */
     /* one block [ground: max_batch x 3 x H floats][instance table: max_batch][vhor: max_batch ints], on
@@ -422,6 +422,7 @@ static int ctx_init(is_ctx* c, const is_stixel_params* p, const float* obj_cost_
     }
     HIP_TRY(isk_set_lds_prepare(&d));
     HIP_TRY(isk_set_lds_unary(&d));
+    HIP_TRY(isk_set_lds_unary_path(&d));
     HIP_TRY(isk_set_lds_pairwise(&d, c->nwaves_pairwise));
     HIP_TRY(isk_set_lds_backtrace(&d));
     if (debug)
@@ -834,7 +835,8 @@ int is_get_kernel_times_ms(is_ctx* c, float* prepare_ms, float* dp_ms, float* ba
 
 /* Every launch decision of one DP call (CallPlan, is_launch.h); the launchers launch what it says.  The choices decide
  * launch geometry and kernel instantiations only, never results. */
-static CallPlan plan_call(const is_ctx* c, int n_images, int pairwise, const int* h_vhor, bool tables_requested) {
+static CallPlan plan_call(const is_ctx* c, int n_images, int pairwise, const int* h_vhor, bool tables_requested,
+                          bool want_inst) {
     const DevParams& P = c->dp;
     const Knobs& k = c->knobs;
     const int ncols = n_images * P.C;
@@ -875,6 +877,10 @@ static CallPlan plan_call(const is_ctx* c, int n_images, int pairwise, const int
                            (!tables_requested && k.lut_fused != 2 && k.lut_fused != 3 && P.sigma_od < IS_FLT_HUGE &&
                             (k.unary_path == 1 || ncols >= IS_UNARY_PATH_MIN_COLS));
         p.unary_force_bad = p.unary_walk && k.unary_path == 3;
+        /* the walk knows (vT, vB, type, cost) of every Section when it hops: it writes them, and k_backtrace takes
+         * only what the walk left (generic columns, a distrusted call).  Instance outputs need k_backtrace's
+         * candidate counts of every column: such calls keep the ungated launch. */
+        p.walk_sections = p.unary_walk && !want_inst;
         /* the tile path: FAST columns through the chunk-staged kernel of is_k_unary_fast.hip whenever the shape allows
          * it, then k_dp_unary takes only the generic columns (measured on MI355X, batch 64: 8.7 ms against 9.3 ms of
          * the tile-pair kernel, and no scratch) */
@@ -955,7 +961,7 @@ static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_se
     HIP_TRY(hipEventRecord(c->staging_free[slot], stream));
 
     const CallPlan plan = plan_call(c, n_images, pairwise, c->h_vhor_pinned[slot],
-                                    d_cost_table != nullptr || d_index_table != nullptr);
+                                    d_cost_table != nullptr || d_index_table != nullptr, want_inst);
     if (!pairwise) c->last_unary_path = plan.unary_walk;
     CallBuffers b;
     b.joined = d_joined; b.seg = d_seg; b.ground = c->d_ground; b.vhor = c->d_vhor;
@@ -965,11 +971,13 @@ static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_se
     b.part_cost = c->d_part_cost; b.part_idx = c->d_part_idx; b.blksum = c->d_blksum; b.t8row = c->d_t8row;
     b.cost_table = d_cost_table ? d_cost_table : c->d_cost_table;
     b.index_table = d_index_table ? d_index_table : c->d_index_table;
+    b.sections = d_sections;
     b.counters = c->counting ? c->d_counters : nullptr;
     b.inst_cnt = want_inst ? c->d_inst_cnt : nullptr;
 
     if (timing) HIP_TRY(hipEventRecord(c->ev[0], stream));
-    /* (d_n_generic is zero here: cleared at creation and by k_backtrace at the end of every call) */
+    /* (d_n_generic is zero here: cleared at creation and by k_backtrace at the end of every call; the prepare launch
+     * clears d_path_bad[0], the distrust word of the last walk) */
     HIP_TRY(isk_launch_prepare(&P, &plan, &b, stream));
     if (pairwise) HIP_TRY(isk_launch_priors(&P, c->d_ground, c->d_priors, n_images, stream));
     if (timing) HIP_TRY(hipEventRecord(c->ev[1], stream));
@@ -978,7 +986,7 @@ static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_se
     else
         HIP_TRY(isk_launch_dp_unary(&P, &plan, &b, stream));
     if (timing) HIP_TRY(hipEventRecord(c->ev[2], stream));
-    HIP_TRY(isk_launch_backtrace(&P, &plan, &b, d_sections, stream));
+    HIP_TRY(isk_launch_backtrace(&P, &plan, &b, stream));
     if (want_inst) {
         /* the instance candidates (StixelsKernels.cu:926-942) and their clustering
          * (Stixels::ClusterInstances, Stixels.cu:613) of the WHOLE batch: two launches */

@@ -5,68 +5,6 @@
 /* ====================================================================================== */
 /* A10  back-tracing, one wavefront per column                                             */
 /* ====================================================================================== */
-/* Everything of one Section that depends only on (vT, vB, type): StixelsKernels.cu:868-944. */
-__device__ __forceinline__ is_section make_section(const DevParams& P, const RowRec* rcol, bool wide,
-                                                   int vT, int vB, int type, float cost) {
-    const RowRec a = load_rec(rcol + vT + 1);
-    const RowRec bq = load_rec(rcol + vB);
-    const RowRecWide& aw = reinterpret_cast<const RowRecWide&>(a);
-    const RowRecWide& bw = reinterpret_cast<const RowRecWide&>(bq);
-    is_section sec;
-    sec.vT = vT;
-    sec.type = type;
-    sec.vB = vB;
-    { /* ComputeMean, :47-60 */
-        const float sd = a.S - bq.S;
-        if (P.invalid >= 0) {
-            const float valid_dif = a.V - bq.V;
-            sec.disparity = (valid_dif == 0) ? 0 : sd / valid_dif;
-        } else {
-            sec.disparity = sd / (float)(vT + 1 - vB);
-        }
-    }
-    sec.cost = __builtin_fminf(cost, 1e4f);
-    const int hgt = vT + 1 - vB;
-    const float meanx = wide ? (float)(aw.MX - bw.MX) : (a.MX - bq.MX);
-    const float meany = wide ? (float)(aw.MY - bw.MY) : (a.MY - bq.MY);
-    sec.instance_meanx = meanx / (float)hgt;
-    sec.instance_meany = meany / (float)hgt;
-    if (sec.type == IS_GROUND) { /* GetGroundSegmentationClass, Cityscapes.h:52-59 */
-        const float cost_road = wide ? (float)(aw.Fg0 - bw.Fg0) : (a.Fg0 - bq.Fg0);
-        const float cost_sidewalk = wide ? (float)(aw.Fg1 - bw.Fg1) : (a.Fg1 - bq.Fg1);
-        sec.semantic_class = (cost_road < cost_sidewalk) ? 0 : 1;
-    } else if (sec.type == IS_SKY || sec.disparity < 1.0f) { /* :894-902 */
-        sec.type = IS_SKY;
-        sec.semantic_class = 10;
-    } else { /* GetObjectSegmentationClass, Cityscapes.h:85-111 */
-        const float meanx2 = wide ? (float)(aw.MX2 - bw.MX2)
-                                  : ((a.MX2h - bq.MX2h) + (a.MX2l - bq.MX2l));
-        const float meany2 = wide ? (float)(aw.MY2 - bw.MY2)
-                                  : ((a.MY2h - bq.MY2h) + (a.MY2l - bq.MY2l));
-        const float height = (float)hgt;
-        const float ic = P.iw * (meanx2 - meanx * meanx / height + meany2 - meany * meany / height);
-        const float nic = P.iw * (float)(a.Fnic - bq.Fnic);
-        float min_cost = IS_INF;
-        int min_class = 2;
-#pragma unroll
-        for (int c = 0; c < IS_N_ON; c++) {
-            float cs = 0.0f;
-            cs += nic;
-            cs += wide ? (float)(aw.Fon[c] - bw.Fon[c]) : (a.Fon[c] - bq.Fon[c]);
-            if (min_cost > cs) { min_cost = cs; min_class = 2 + c; }
-        }
-#pragma unroll
-        for (int c = 0; c < IS_N_OI; c++) {
-            float cs = 0.0f;
-            cs += ic;
-            cs += wide ? (float)(aw.Foi[c] - bw.Foi[c]) : (a.Foi[c] - bq.Foi[c]);
-            if (min_cost > cs) { min_cost = cs; min_class = 11 + c; }
-        }
-        sec.semantic_class = min_class;
-    }
-    return sec;
-}
-
 /* One wavefront per column.  The reference lets thread 0 do everything serially
  * (StixelsKernels.cu:843-955); only the index chase is inherently serial, so: lane 0 walks the
  * chain and records the cuts, then the lanes build the Sections in parallel (one per lane).  The
@@ -87,7 +25,8 @@ __global__ __launch_bounds__(64) void k_backtrace(const DevParams P, int ncols, 
                                                   is_section* __restrict__ sections,
                                                   int* __restrict__ inst_cnt /* [ncols][8] or null */,
                                                   int* __restrict__ n_generic /* reset for the next call */,
-                                                  int* __restrict__ path_bad /* [2] or null, see below */) {
+                                                  int* __restrict__ path_bad /* [2] or null, see below */,
+                                                  int gated /* CallPlan::walk_sections */) {
     static_assert(!(STAGE && TWO), "the staged variant is for small calls: one column per wave");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x;
@@ -97,6 +36,12 @@ __global__ __launch_bounds__(64) void k_backtrace(const DevParams P, int ncols, 
     if ((TWO ? (int)blockIdx.x * 2 : (int)blockIdx.x) >= ncols) return;
     const bool valid = colq < ncols;           /* (TWO, odd column count: the last wave's second half idles) */
     const int colg = valid ? colq : ncols - 1;
+    /* gated (the walk has written the Sections of the columns it took): only generic-encoding columns, or every
+     * column of a call whose walk distrusted itself (the repair launches precede this one).  Every wave reads
+     * path_bad[0], so this launch does not clear it: the next call's prepare launch does. */
+    const bool wide = col_flags[colg] != 0; /* generic record encoding, see RowRec */
+    const bool need = valid && (!gated || wide || path_bad[0] != 0);
+    const bool wave_needed = __builtin_amdgcn_ballot_w64(need) != 0ull;
     /* the count of generic-encoding columns (k_prepare_columns adds to it, the generic DP kernels of
      * this call have read it: they precede this launch in stream order) goes back to zero here --
      * a memset node per call costs a single frame ten microseconds of queue time */
@@ -105,12 +50,12 @@ __global__ __launch_bounds__(64) void k_backtrace(const DevParams P, int ncols, 
      * counts in path_bad[1] (is_debug_unary_path) */
     if (path_bad && blockIdx.x == 0 && lane == 0 && path_bad[0] != 0) {
         path_bad[1] += 1;
-        path_bad[0] = 0;
+        if (!gated) path_bad[0] = 0;
     }
+    if (!wave_needed) return;
     const int H = P.H, S = P.S;
     int* s_cut = (int*)smem + half * (3 * S + 8); /* [S][3]: vT, vB, type */
     int* s_n = s_cut + 3 * S;                     /* [1] */
-    const bool wide = col_flags[colg] != 0; /* generic record encoding, see RowRec */
     const RowRec* rcol = recs + (size_t)colg * (H + 1);
     const float* ct = cost_table + (size_t)colg * H * 3;
     const int32_t* it = index_table + (size_t)colg * H * 3;
@@ -128,7 +73,8 @@ __global__ __launch_bounds__(64) void k_backtrace(const DevParams P, int ncols, 
         s_cost = l_cost;
         s_idx = l_idx;
     }
-    if (li == 0) {
+    if (li == 0 && !need) *s_n = 0; /* (TWO: the other half's column is wanted) */
+    if (li == 0 && need) {
         int vT = H - 1;
         const float last_ground = s_cost[vT * 3 + IS_GROUND];
         const float last_object = s_cost[vT * 3 + IS_OBJECT];
@@ -187,7 +133,7 @@ __global__ __launch_bounds__(64) void k_backtrace(const DevParams P, int ncols, 
             const int vT = s_cut[i * 3 + 0], vB = s_cut[i * 3 + 1], type = s_cut[i * 3 + 2];
             sec = make_section(P, rcol, wide, vT, vB, type, s_cost[vT * 3 + type]);
         }
-        if (i <= n && valid) out[i] = sec;
+        if (i <= n && need) out[i] = sec;
         if (inst_cnt) { /* candidates per instance class, :926-942 (the scatter: k_compact_instances) */
             const bool cand = i < n && sec.type == IS_OBJECT && sec.semantic_class >= IS_FIRST_INSTANCE_CLASS;
             const int k = sec.semantic_class - IS_FIRST_INSTANCE_CLASS;
@@ -198,7 +144,7 @@ __global__ __launch_bounds__(64) void k_backtrace(const DevParams P, int ncols, 
             }
         }
     }
-    if (inst_cnt && li < IS_INSTANCE_CLASSES && valid) inst_cnt[(size_t)colg * IS_INSTANCE_CLASSES + li] = my_cnt;
+    if (inst_cnt && li < IS_INSTANCE_CLASSES && need) inst_cnt[(size_t)colg * IS_INSTANCE_CLASSES + li] = my_cnt;
 }
 
 /* ====================================================================================== */
@@ -293,13 +239,12 @@ size_t isk_backtrace_lds_bytes(const DevParams* P, int form) {
     return form == IS_BT_STAGED ? lds + sizeof(int) * 6 * (size_t)P->H : form == IS_BT_TWO ? 2 * lds : lds;
 }
 
-hipError_t isk_launch_backtrace(const DevParams* P, const CallPlan* plan, const CallBuffers* b, is_section* sections,
-                                hipStream_t stream) {
+hipError_t isk_launch_backtrace(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream) {
     const int ncols = plan->ncols;
     const size_t lds = isk_backtrace_lds_bytes(P, plan->backtrace);
 #define IS_BT_ARGS                                                                                                 \
-    *P, ncols, plan->pairwise, b->recs, b->cost_table, b->index_table, b->col_flags, sections, b->inst_cnt,        \
-        b->n_generic, b->path_bad
+    *P, ncols, plan->pairwise, b->recs, b->cost_table, b->index_table, b->col_flags, b->sections, b->inst_cnt,     \
+        b->n_generic, b->path_bad, plan->walk_sections
     if (plan->backtrace == IS_BT_STAGED)
         hipLaunchKernelGGL(k_backtrace<true>, dim3(ncols), dim3(64), lds, stream, IS_BT_ARGS);
     else if (plan->backtrace == IS_BT_TWO)

@@ -133,8 +133,12 @@ __device__ __forceinline__ void prepare_columns_body(
     const DevParams& P, const int colg, char* smem, const float* __restrict__ joined,
     const int32_t* __restrict__ seg, const float* __restrict__ ground /*[img][3][H]*/,
     const int* __restrict__ vhor_arr, RowRec* __restrict__ recs, int* __restrict__ col_flags,
-    float* __restrict__ sv_arr, PruneRec* __restrict__ prune, int* __restrict__ n_generic) {
+    float* __restrict__ sv_arr /* null: a unary call, nothing reads the copies */, PruneRec* __restrict__ prune,
+    int* __restrict__ n_generic, int* __restrict__ path_bad) {
     const int H = P.H, P2 = P.P2, P2S = P.P2S, CH = P.CH, K = P.K;
+    /* the distrust word of the last call's walk: every wave of a gated k_backtrace reads it, so that launch cannot
+     * clear it; the next call does, in front of its own walk */
+    if (colg == 0 && threadIdx.x == 0) path_bad[0] = 0;
     if (P.lut_ready != nullptr && threadIdx.x == 0) {
         P.lut_ready[colg] = 0; /* (the fused LUT units of the DP launch count up) */
         if (colg == 0 && P.lutf_bad != nullptr) *P.lutf_bad = 0;
@@ -462,7 +466,8 @@ __device__ __forceinline__ void prepare_columns_body(
     float pS[MAXR], pV[MAXR], pG[MAXR], pK[MAXR];
 #pragma unroll
     for (int k = 0; k < MAXR; k++) pS[k] = pV[k] = pG[k] = pK[k] = 0.0f;
-    float* svcol = sv_arr + (size_t)colg * 2 * (H + 1); /* compact copies for the pairwise phase 2 */
+    /* compact copies for the pairwise phase 2 */
+    float* svcol = sv_arr != nullptr ? sv_arr + (size_t)colg * 2 * (H + 1) : nullptr;
     /* S: disparity (valid-masked when invalid >= 0, :382-389) */
     for (int i = tid; i < NP; i += PREP_THREADS) {
         float x = 0.0f;
@@ -483,13 +488,13 @@ __device__ __forceinline__ void prepare_columns_body(
 #pragma unroll
         for (int k = 0; k < MAXR; k++) {
             const int v = tid + k * PREP_THREADS;
-            if (v <= H) { pS[k] = prefix_at(v); svcol[v] = pS[k]; }
+            if (v <= H) { pS[k] = prefix_at(v); if (svcol) svcol[v] = pS[k]; }
         }
     } else {
         for (int v = tid; v <= H; v += PREP_THREADS) {
             const float x = prefix_at(v);
             rcol[v].S = x;
-            svcol[v] = x;
+            if (svcol) svcol[v] = x;
         }
     }
     __syncthreads();
@@ -503,20 +508,20 @@ __device__ __forceinline__ void prepare_columns_body(
 #pragma unroll
             for (int k = 0; k < MAXR; k++) {
                 const int v = tid + k * PREP_THREADS;
-                if (v <= H) { pV[k] = prefix_at(v); svcol[H + 1 + v] = pV[k]; }
+                if (v <= H) { pV[k] = prefix_at(v); if (svcol) svcol[H + 1 + v] = pV[k]; }
             }
         } else {
             for (int v = tid; v <= H; v += PREP_THREADS) {
                 const float x = prefix_at(v);
                 rcol[v].V = x;
-                svcol[H + 1 + v] = x;
+                if (svcol) svcol[H + 1 + v] = x;
             }
         }
         __syncthreads();
     } else {
         for (int v = tid; v <= H; v += PREP_THREADS) {
             if (!regs) rcol[v].V = 0.0f;
-            svcol[H + 1 + v] = 0.0f;
+            if (svcol) svcol[H + 1 + v] = 0.0f;
         }
     }
     /* G: ground data cost, +inf at / above the horizon (:435-446) */
@@ -653,10 +658,10 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prepare_columns(
     const DevParams P, const float* __restrict__ joined, const int32_t* __restrict__ seg,
     const float* __restrict__ ground, const int* __restrict__ vhor_arr, RowRec* __restrict__ recs,
     int* __restrict__ col_flags, float* __restrict__ sv_arr, PruneRec* __restrict__ prune,
-    int* __restrict__ n_generic) {
+    int* __restrict__ n_generic, int* __restrict__ path_bad) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     prepare_columns_body(P, (int)blockIdx.x, smem, joined, seg, ground, vhor_arr, recs, col_flags, sv_arr,
-                         prune, n_generic);
+                         prune, n_generic, path_bad);
 }
 
 /* ====================================================================================== */
@@ -800,7 +805,8 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prepare_fused(
     const DevParams P, int ncols, int n_lut, const float* __restrict__ joined, const int32_t* __restrict__ seg,
     const float* __restrict__ ground, const int* __restrict__ vhor_arr, const float* __restrict__ cost_T,
     RowRec* __restrict__ recs, float* __restrict__ lut, int* __restrict__ col_flags,
-    float* __restrict__ sv_arr, PruneRec* __restrict__ prune, int* __restrict__ n_generic) {
+    float* __restrict__ sv_arr, PruneRec* __restrict__ prune, int* __restrict__ n_generic,
+    int* __restrict__ path_bad) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int b = (int)blockIdx.x;
     const bool is_lut = b >= ncols; /* the LUT blocks follow the column blocks */
@@ -812,7 +818,7 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prepare_fused(
             object_lut_body<CARRY>(P, unit / fn_blocks, unit % fn_blocks, (int)(threadIdx.x & 63), joined, cost_T, lut);
     } else {
         prepare_columns_body(P, col_b, smem, joined, seg, ground, vhor_arr, recs,
-                             col_flags, sv_arr, prune, n_generic);
+                             col_flags, sv_arr, prune, n_generic, path_bad);
     }
 }
 
@@ -868,9 +874,11 @@ hipError_t isk_launch_lut_generic(const DevParams* P, const CallPlan* plan, cons
 
 hipError_t isk_launch_prepare(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream) {
     const int ncols = plan->ncols;
+    float* sv = plan->pairwise ? b->sv : nullptr; /* (only the pairwise phase 2 reads the S / V copies) */
     if (!plan->prepare_lut) { /* the LUT units run inside the unary DP launch (k_dp_unary_fast, LUTF): records only here */
         hipLaunchKernelGGL(k_prepare_columns, dim3(ncols), dim3(PREP_THREADS), isk_prepare_lds_bytes(P), stream, *P,
-                           b->joined, b->seg, b->ground, b->vhor, b->recs, b->col_flags, b->sv, b->prune, b->n_generic);
+                           b->joined, b->seg, b->ground, b->vhor, b->recs, b->col_flags, sv, b->prune, b->n_generic,
+                           b->path_bad);
         return hipGetLastError();
     }
     /* the two prepare kernels are independent: one launch with workgroups of both kinds (k_prepare_fused) */
@@ -879,7 +887,7 @@ hipError_t isk_launch_prepare(const DevParams* P, const CallPlan* plan, const Ca
 #define IS_LAUNCH_PREPARE(CARRY, LUT)                                                                                 \
     hipLaunchKernelGGL(k_prepare_fused<CARRY>, dim3(ncols + n_lut), dim3(PREP_THREADS), isk_prepare_lds_bytes(P), stream, \
                        *P, ncols, n_lut, b->joined, b->seg, b->ground, b->vhor, b->cost_T, b->recs, LUT, b->col_flags,  \
-                       b->sv, b->prune, b->n_generic)
+                       sv, b->prune, b->n_generic, b->path_bad)
     if (plan->lut_carry) IS_LAUNCH_PREPARE(true, b->lutC); else IS_LAUNCH_PREPARE(false, b->lutT);
 #undef IS_LAUNCH_PREPARE
     return hipGetLastError();

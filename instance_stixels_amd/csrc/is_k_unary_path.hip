@@ -31,6 +31,10 @@
  * The vT side, lutT[vT + 1][fn], is output vT & 31 of block vT / 32: picked from the first step's networks when that
  * block is among them, otherwise built two fn at a time (lut_row_entry), and kept per row in an LDS cache.
  *
+ * Sections (CallPlan::walk_sections, a call without instance outputs): lane 0 records (vT, vB, type, cost) of every
+ * hop in LDS; after a chain that succeeded the lanes build the Sections with k_backtrace's make_section and store them
+ * with the terminator, and k_backtrace runs gated (generic columns, every column of a distrusted call).
+ *
  * What the kernel cannot reproduce it does not try to: a chosen index outside [0, vT] (every candidate of
  * the type +inf or NaN) sets *bad, and the repair launches behind this one redo the whole call on the tile
  * path.  Generic-encoding columns (col_flags != 0) are left to k_dp_unary<.., false>, as on the tile path. */
@@ -120,7 +124,11 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
     bool open_o = true, open_s = true;
     /* ground data cost +inf from this row on (at / above the horizon): no ground candidate can win */
     bool open_g = !(my.G == IS_INF);
-    for (int s = (vT - 1) >> 6; s >= 0; s--) { /* (vT = 0: no candidate vB >= 1) */
+    /* Full steps while the object type is open, then ground- / sky-only steps: the close is monotone within a row.
+     * `ended`: the exit test fired, nothing below can win (the first segment included). */
+    bool ended = false;
+    int s = s_first; /* (vT = 0: -1, no candidate vB >= 1) */
+    for (; s >= 0 && open_o; s--) {
         const int vB = 64 * s + 1 + lane;
         const bool live = vB <= vT;
         const int vBc = live ? vB : vT;
@@ -131,7 +139,7 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
         const SegTerms t = eval_segment<true, HAS_INVALID>(my, rb, (float)h, r, D, P.iw, rcp);
         const float pwih = P.pw * r;
         /* cost = dw*data + pw*(1/h) + sw*seg, left to right (unary_step) */
-        if (open_o) {
+        {
             /* lutT[vB][fni]: one network pass per distinct fn of the live lanes; the first step of the row also
              * leaves lutT[vT + 1][fn] (lane vT - 64 s) in the row cache */
             const int blk = min(2 * s + (lane >> 5), L.nb - 1); /* (clamped: rows >= H only feed dead lanes) */
@@ -175,25 +183,58 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
             if (__builtin_amdgcn_ballot_w64(lb_g > bg) != 0ull) open_g = false;
             /* candidates left: vB' <= 64 s; sky ones need vB' - 1 >= vhor */
             const bool sky_left = 64 * s - 1 >= vhor;
-            if (!open_o && !open_g && (!open_s || !sky_left)) break;
+            if (!open_o && !open_g && (!open_s || !sky_left)) { ended = true; break; }
         }
-        if (s == 0) { /* first segment vB = 0 (:481-594): ground + object, lane 0 */
-            if (open_o || open_g) {
-                const RowRec rb0 = load_rec(rcol);
-                const int h0 = vT + 1;
-                const float r0 = rcp[h0];
-                const SegTerms t0 = eval_segment<true, HAS_INVALID>(my, rb0, (float)h0, r0, D, P.iw, rcp);
-                const float pwih0 = P.pw * r0;
-                if (open_o) {
-                    const float od = lut_row_entry(L, disT, vT, t0.fni, lane == 0, lane) - 0.0f; /* lutT[0] = 0 */
-                    const float cost_o = P.dw * od + pwih0 + P.sw * t0.seg_o;
-                    if (lane == 0 && cost_o <= bo) { bo = cost_o; vo = 0; }
-                }
-                if (open_g) {
-                    const float cost_g = P.dw * t0.gd + pwih0 + P.sw * t0.seg_g;
-                    if (lane == 0 && vT <= vhor && cost_g <= bg) { bg = cost_g; vg = 0; }
-                }
+    }
+    /* The object type is closed for the rest of the row: chunks 0 / 4 / 5 of the vB record instead of the whole of
+     * it (chunk 0 only while ground is open), eval_segment's ground and sky terms alone (eval_segment_gs), no table
+     * entries; the same bounds for the types still open, the same exit test. */
+    for (; s >= 0 && !ended; s--) {
+        const int vB = 64 * s + 1 + lane;
+        const bool live = vB <= vT;
+        const int vBc = live ? vB : vT;
+        const int h = vT + 1 - vBc;
+        const float pwih = P.pw * rcp[h];
+        SegTerms t;
+        if (open_g) t = eval_segment_gs<IS_WANT_GROUND | IS_WANT_SKY>(my, load_rec_gs<IS_WANT_GROUND | IS_WANT_SKY>(rcol + vBc), P.iw);
+        else t = eval_segment_gs<IS_WANT_SKY>(my, load_rec_gs<IS_WANT_SKY>(rcol + vBc), P.iw);
+        if (vB - 1 >= vhor) {
+            const float cost_s = P.dw * t.sd + pwih + P.sw * t.seg_s;
+            if (open_s && live && cost_s <= bs) { bs = cost_s; vs = vB; }
+        } else if (open_g) {
+            const float cost_g = P.dw * t.gd + pwih + P.sw * t.seg_g;
+            if (live && cost_g <= bg) { bg = cost_g; vg = vB; }
+        }
+        /* (prune_on holds: only a bound closes the object type) */
+        const float f_sky = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.f_sky)));
+        const float lb_s = P.sw * f_sky - pr.E1s;
+        if (__builtin_amdgcn_ballot_w64(lb_s > bs) != 0ull) open_s = false;
+        if (open_g) {
+            const float f_g = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.f_g)));
+            const float lb_g = P.sw * f_g - pr.E1g;
+            if (__builtin_amdgcn_ballot_w64(lb_g > bg) != 0ull) open_g = false;
+        }
+        const bool sky_left = 64 * s - 1 >= vhor;
+        if (!open_g && (!open_s || !sky_left)) ended = true;
+    }
+    if (vT > 0 && !ended) { /* first segment vB = 0 (:481-594): ground + object, lane 0 */
+        const int h0 = vT + 1;
+        const float r0 = rcp[h0];
+        const float pwih0 = P.pw * r0;
+        if (open_o) {
+            const RowRec rb0 = load_rec(rcol);
+            const SegTerms t0 = eval_segment<true, HAS_INVALID>(my, rb0, (float)h0, r0, D, P.iw, rcp);
+            const float od = lut_row_entry(L, disT, vT, t0.fni, lane == 0, lane) - 0.0f; /* lutT[0] = 0 */
+            const float cost_o = P.dw * od + pwih0 + P.sw * t0.seg_o;
+            if (lane == 0 && cost_o <= bo) { bo = cost_o; vo = 0; }
+            if (open_g) {
+                const float cost_g = P.dw * t0.gd + pwih0 + P.sw * t0.seg_g;
+                if (lane == 0 && vT <= vhor && cost_g <= bg) { bg = cost_g; vg = 0; }
             }
+        } else if (open_g) {
+            const SegTerms t0 = eval_segment_gs<IS_WANT_GROUND>(my, load_rec_gs<IS_WANT_GROUND>(rcol), P.iw);
+            const float cost_g = P.dw * t0.gd + pwih0 + P.sw * t0.seg_g;
+            if (lane == 0 && vT <= vhor && cost_g <= bg) { bg = cost_g; vg = 0; }
         }
     }
     if (vT == 0) { /* the first segment is the only candidate */
@@ -228,8 +269,9 @@ __global__ __launch_bounds__(64) void k_unary_path(const DevParams P, int ncols,
                                                    const float* __restrict__ cost_F, const float* __restrict__ rcp,
                                                    const int* __restrict__ vhor_arr, const int* __restrict__ col_flags,
                                                    const PruneRec* __restrict__ prune, float* __restrict__ cost_table,
-                                                   int32_t* __restrict__ index_table, int* __restrict__ bad,
-                                                   int force_bad) {
+                                                   int32_t* __restrict__ index_table,
+                                                   is_section* __restrict__ sections /* or null */,
+                                                   int* __restrict__ bad, int force_bad) {
     const int colg = (int)blockIdx.x, lane = (int)threadIdx.x;
     if (force_bad && colg == 0 && lane == 0) /* (IS_UNARY_PATH=3, tests: distrust every call) */
         __hip_atomic_fetch_or(bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -238,7 +280,7 @@ __global__ __launch_bounds__(64) void k_unary_path(const DevParams P, int ncols,
     const int H = P.H, S = P.S;
     const int vhor = __builtin_amdgcn_readfirstlane(vhor_arr[colg / P.C]);
     const RowRec* rcol = recs + (size_t)colg * (H + 1);
-    extern __shared__ int s_lut_row[]; /* [2][D]: the row cache of lut_row_entry */
+    extern __shared__ int s_lut_row[]; /* [2][D]: the row cache of lut_row_entry, then [S][4]: the chain's hops */
     LutCol L;
     L.H = H; L.D = P.D; L.nb = isk_lut_carry_rows(H);
     L.dcol = joined + (size_t)colg * H;
@@ -247,6 +289,7 @@ __global__ __launch_bounds__(64) void k_unary_path(const DevParams P, int ncols,
     L.s_tag = s_lut_row;
     L.s_val = (float*)(s_lut_row + P.D);
     for (int i = lane; i < P.D; i += 64) L.s_tag[i] = -1;
+    int* s_cut = s_lut_row + 2 * P.D; /* [S][4]: vT, vB, type, cost bits of every hop (CallPlan::walk_sections) */
     float* ct = cost_table + (size_t)colg * H * 3;
     int32_t* it = index_table + (size_t)colg * H * 3;
     PruneRec pr;
@@ -274,22 +317,51 @@ __global__ __launch_bounds__(64) void k_unary_path(const DevParams P, int ncols,
         const int vB = __builtin_amdgcn_readfirstlane(raw);
         if (vB < 0 || vB > vT) { /* the back-trace would leave the rows this walk can vouch for */
             if (lane == 0) __hip_atomic_fetch_or(bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
+            return; /* no Section of this column is written: the ungated k_backtrace of the repair writes them */
+        }
+        if (sections != nullptr && lane == 0) { /* (n <= S - 2) */
+            const float c = type == IS_GROUND ? cG : (type == IS_OBJECT ? cO : cS);
+            s_cut[4 * n + 0] = vT; s_cut[4 * n + 1] = vB; s_cut[4 * n + 2] = type; s_cut[4 * n + 3] = __float_as_int(c);
         }
         n++;
         if (vB == 0) break;
         vT = vB - 1;
         last = n >= S - 1;
     }
+    if (sections == nullptr) return;
+    /* the chain succeeded: the lanes build its n Sections and the terminator, as k_backtrace's second loop does */
+    __syncthreads(); /* (one wave) lane 0's hops before the lanes read them */
+    is_section* out = sections + (size_t)colg * S;
+    for (int i0 = 0; i0 <= n; i0 += 64) {
+        const int i = i0 + lane;
+        is_section sec;
+        sec.type = -1; sec.vB = 0; sec.vT = 0; sec.disparity = 0.0f; /* terminator, :952-954 */
+        sec.semantic_class = 0; sec.cost = 0.0f; sec.instance_meanx = 0.0f; sec.instance_meany = 0.0f;
+        if (i < n)
+            sec = make_section(P, rcol, false, s_cut[4 * i + 0], s_cut[4 * i + 1], s_cut[4 * i + 2],
+                               __int_as_float(s_cut[4 * i + 3]));
+        if (i <= n) out[i] = sec;
+    }
 }
 
 extern "C" {
 
+/* the row cache [2][D] and the hops [S][4] */
+size_t isk_unary_path_lds_bytes(const DevParams* P) { return sizeof(int) * (2 * (size_t)P->D + 4 * (size_t)P->S); }
+
+hipError_t isk_set_lds_unary_path(const DevParams* P) {
+    const int b = (int)isk_unary_path_lds_bytes(P);
+    hipError_t e = hipFuncSetAttribute((const void*)k_unary_path<false>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute((const void*)k_unary_path<true>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
+}
+
 hipError_t isk_launch_unary_path(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream) {
 #define IS_LAUNCH_PATH(INV)                                                                                        \
-    hipLaunchKernelGGL(k_unary_path<INV>, dim3(plan->ncols), dim3(64), sizeof(float) * 2 * P->D, stream, *P,       \
+    hipLaunchKernelGGL(k_unary_path<INV>, dim3(plan->ncols), dim3(64), isk_unary_path_lds_bytes(P), stream, *P,    \
                        plan->ncols, b->recs, b->joined, b->lutC, b->cost_F, b->rcp, b->vhor, b->col_flags, b->prune, \
-                       b->cost_table, b->index_table, b->path_bad, plan->unary_force_bad)
+                       b->cost_table, b->index_table, plan->walk_sections ? b->sections : nullptr, b->path_bad,    \
+                       plan->unary_force_bad)
     if (P->invalid >= 0) IS_LAUNCH_PATH(true); else IS_LAUNCH_PATH(false);
 #undef IS_LAUNCH_PATH
     return hipGetLastError();

@@ -30,6 +30,7 @@
 #define IS_KERNELS_H_
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -199,6 +200,115 @@ __device__ __forceinline__ RowRec load_rec(const RowRec* p) {
 #pragma unroll
     for (int i = 0; i < 8; i++) d[i] = s[i];
     return r;
+}
+
+/* What a ground / sky candidate needs of the vB record: chunks 0 (Fg0 Fg1), 4 (Fsky Fnic) and 5 (G K) of its eight
+ * 16-byte chunks; chunk 0 only when the ground type is wanted. */
+#define IS_WANT_GROUND 1
+#define IS_WANT_SKY 2
+struct RowRecGS {
+    float Fg0, Fg1, Fsky;
+    int32_t Fnic;
+    float G, K;
+};
+template <int WANT>
+__device__ __forceinline__ RowRecGS load_rec_gs(const RowRec* p) {
+    static_assert(offsetof(RowRec, Fg0) == 0 && offsetof(RowRec, Fsky) == 72 && offsetof(RowRec, Fnic) == 76 &&
+                      offsetof(RowRec, G) == 80 && offsetof(RowRec, K) == 84,
+                  "chunks 0 / 4 / 5");
+    const int4* s = (const int4*)p;
+    const int4 c4 = s[4], c5 = s[5];
+    RowRecGS r;
+    r.Fg0 = r.Fg1 = 0.0f;
+    if (WANT & IS_WANT_GROUND) {
+        const int4 c0 = s[0];
+        r.Fg0 = __int_as_float(c0.x); r.Fg1 = __int_as_float(c0.y);
+    }
+    r.Fsky = __int_as_float(c4.z); r.Fnic = c4.w;
+    r.G = __int_as_float(c5.x); r.K = __int_as_float(c5.y);
+    return r;
+}
+
+/* The ground and sky terms of eval_segment<true, .> alone (seg_g, seg_s, gd, sd, f_g, f_sky; the object fields are
+ * not set): the same expressions on the same operands in the same order, so every cost keeps its bits.  WANT without
+ * IS_WANT_GROUND leaves the ground fields unset too. */
+template <int WANT = IS_WANT_GROUND | IS_WANT_SKY>
+__device__ __forceinline__ SegTerms eval_segment_gs(const RowRec& my, const RowRecGS& rb, float iw) {
+    SegTerms t;
+    const float nic = iw * (float)(my.Fnic - rb.Fnic);
+    if (WANT & IS_WANT_GROUND) {
+        t.f_g = __builtin_fminf(my.Fg0 - rb.Fg0, my.Fg1 - rb.Fg1);
+        t.seg_g = t.f_g + nic;
+        t.gd = my.G - rb.G;
+    }
+    if (WANT & IS_WANT_SKY) {
+        t.f_sky = my.Fsky - rb.Fsky;
+        t.seg_s = t.f_sky + nic;
+        t.sd = my.K - rb.K;
+    }
+    return t;
+}
+
+/* Everything of one Section that depends only on (vT, vB, type): StixelsKernels.cu:868-944. */
+__device__ __forceinline__ is_section make_section(const DevParams& P, const RowRec* rcol, bool wide,
+                                                   int vT, int vB, int type, float cost) {
+    const RowRec a = load_rec(rcol + vT + 1);
+    const RowRec bq = load_rec(rcol + vB);
+    const RowRecWide& aw = reinterpret_cast<const RowRecWide&>(a);
+    const RowRecWide& bw = reinterpret_cast<const RowRecWide&>(bq);
+    is_section sec;
+    sec.vT = vT;
+    sec.type = type;
+    sec.vB = vB;
+    { /* ComputeMean, :47-60 */
+        const float sd = a.S - bq.S;
+        if (P.invalid >= 0) {
+            const float valid_dif = a.V - bq.V;
+            sec.disparity = (valid_dif == 0) ? 0 : sd / valid_dif;
+        } else {
+            sec.disparity = sd / (float)(vT + 1 - vB);
+        }
+    }
+    sec.cost = __builtin_fminf(cost, 1e4f);
+    const int hgt = vT + 1 - vB;
+    const float meanx = wide ? (float)(aw.MX - bw.MX) : (a.MX - bq.MX);
+    const float meany = wide ? (float)(aw.MY - bw.MY) : (a.MY - bq.MY);
+    sec.instance_meanx = meanx / (float)hgt;
+    sec.instance_meany = meany / (float)hgt;
+    if (sec.type == IS_GROUND) { /* GetGroundSegmentationClass, Cityscapes.h:52-59 */
+        const float cost_road = wide ? (float)(aw.Fg0 - bw.Fg0) : (a.Fg0 - bq.Fg0);
+        const float cost_sidewalk = wide ? (float)(aw.Fg1 - bw.Fg1) : (a.Fg1 - bq.Fg1);
+        sec.semantic_class = (cost_road < cost_sidewalk) ? 0 : 1;
+    } else if (sec.type == IS_SKY || sec.disparity < 1.0f) { /* :894-902 */
+        sec.type = IS_SKY;
+        sec.semantic_class = 10;
+    } else { /* GetObjectSegmentationClass, Cityscapes.h:85-111 */
+        const float meanx2 = wide ? (float)(aw.MX2 - bw.MX2)
+                                  : ((a.MX2h - bq.MX2h) + (a.MX2l - bq.MX2l));
+        const float meany2 = wide ? (float)(aw.MY2 - bw.MY2)
+                                  : ((a.MY2h - bq.MY2h) + (a.MY2l - bq.MY2l));
+        const float height = (float)hgt;
+        const float ic = P.iw * (meanx2 - meanx * meanx / height + meany2 - meany * meany / height);
+        const float nic = P.iw * (float)(a.Fnic - bq.Fnic);
+        float min_cost = IS_INF;
+        int min_class = 2;
+#pragma unroll
+        for (int c = 0; c < IS_N_ON; c++) {
+            float cs = 0.0f;
+            cs += nic;
+            cs += wide ? (float)(aw.Fon[c] - bw.Fon[c]) : (a.Fon[c] - bq.Fon[c]);
+            if (min_cost > cs) { min_cost = cs; min_class = 2 + c; }
+        }
+#pragma unroll
+        for (int c = 0; c < IS_N_OI; c++) {
+            float cs = 0.0f;
+            cs += ic;
+            cs += wide ? (float)(aw.Foi[c] - bw.Foi[c]) : (a.Foi[c] - bq.Foi[c]);
+            if (min_cost > cs) { min_cost = cs; min_class = 11 + c; }
+        }
+        sec.semantic_class = min_class;
+    }
+    return sec;
 }
 
 /* The object table's disparity of row `row` of a joined column and its cost bin (ComputeObjectLUT,
@@ -524,8 +634,6 @@ __device__ __forceinline__ float seg_o_lower_bound(const SegTerms& t, float E2x3
 
 /* what a step needs besides the object terms: the ground candidate's, the sky candidate's, both
  * (the first segment of the pairwise model, generic callers) or neither (tiles above the horizon) */
-#define IS_WANT_GROUND 1
-#define IS_WANT_SKY 2
 
 /* eval_segment<true, HAS_INVALID> (is_kernels.h) with the vB record in (R0, R1): identical
  * operations in identical order, only the source of the vB operand differs.  WANT: which of the

@@ -58,6 +58,8 @@ struct CallPlan {
     /* unary */
     int unary_walk;    /* 1: k_unary_path + the generic columns + the repair launch; 0: the tile path */
     int unary_force_bad; /* (tests, IS_UNARY_PATH=3) every walk distrusts itself: the repair launch runs */
+    int walk_sections; /* 1 (a walk call without instance outputs): k_unary_path writes the Sections of the columns it
+                        * takes, and k_backtrace runs gated: only generic columns, every column of a distrusted call */
     int unary_nvr;     /* tile path: k_dp_unary_fast<., NVR> for the FAST columns; 0 = k_dp_unary for every column */
     int lut_fused;     /* 1: the LUT units run inside the unary DP launch (LUTF) */
     /* prepare */
@@ -99,6 +101,7 @@ struct CallBuffers {
     float* t8row;
     float* cost_table;
     int32_t* index_table;
+    is_section* sections;      /* the caller's Section output */
     unsigned long long* counters; /* null unless the evaluation counters are on */
     int* inst_cnt;             /* null unless instance outputs are requested */
 };
@@ -132,6 +135,8 @@ hipError_t isk_launch_dp_unary_fast(const DevParams* P, const CallPlan* plan, co
                                     hipStream_t stream);
 
 /* is_k_unary_path.hip */
+size_t isk_unary_path_lds_bytes(const DevParams* P);
+hipError_t isk_set_lds_unary_path(const DevParams* P);
 hipError_t isk_launch_unary_path(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream);
 
 /* is_k_pairwise.hip */
@@ -146,8 +151,7 @@ hipError_t isk_launch_dp_pairwise(const DevParams* P, const CallPlan* plan, cons
 /* is_k_backtrace.hip */
 size_t isk_backtrace_lds_bytes(const DevParams* P, int form);
 hipError_t isk_set_lds_backtrace(const DevParams* P);
-hipError_t isk_launch_backtrace(const DevParams* P, const CallPlan* plan, const CallBuffers* b, is_section* sections,
-                                hipStream_t stream);
+hipError_t isk_launch_backtrace(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream);
 hipError_t isk_launch_compact(const DevParams* P, int n_images, const is_section* sections, const int* inst_cnt,
                               const is_instance_buffers* d_tbl, hipStream_t stream);
 
