@@ -177,6 +177,24 @@ public:
      * its sections; then the totals and the records travel behind ONE synchronisation) and 4096 records per frame
      * after a Compute().  A batch that needs more is repeated with its true total: the result is always complete. */
     void SetWorldCapacity(int records_per_frame);
+    /* f8 (an addition): the instance id of every stixel of frames 0 .. n_images-1 of the LAST Compute() or
+     * ComputeBatch() by majority vote over d_gt_instance [n][rows][cols] int32 (Cityscapes instanceIds), as
+     * is_assign_instances_gt defines it -- the reference tooling's assign_instances_gt (--use-instancegt), the
+     * upper bound of its instance evaluation.  The vote needs no instance candidates: it works after a compute call
+     * without instance outputs too.  It fills a second per-section map of the object, and from then on RenderBatch,
+     * InstanceOverlapBatch and WorldBatch* take their instance ids from that map (frames the vote did not cover have
+     * none) until the next compute call or UseClusterInstances().  `mapping`, when given, receives per frame
+     * (column, section) -> label of every labelled section, in one packed copy behind one synchronisation.  Throws
+     * std::invalid_argument under RenderBatch's rules (before any compute, n_images beyond the last batch). */
+    void AssignInstancesGTBatch(int n_images, const int32_t* d_gt_instance, void* stream = nullptr,
+                                std::vector<InstanceMapping>* mapping = nullptr);
+    /* Back to the cluster labels of the last compute call. */
+    void UseClusterInstances() { m_gt_instances = false; }
+    /* The vote's parameters (defaults: the reference's): the minimum fraction of the 10 % rule, the labelIds of
+     * classes 11..18 (null: Cityscapes 24, 25, 26, 27, 28, 31, 32, 33), and whether the ground truth is in trainId
+     * form (class*1000 + k, *_instanceTrainIds.png).  Throws std::invalid_argument on a NaN fraction or an id outside
+     * [0, 2147482]. */
+    void SetGTAssignmentParameters(double min_fraction, const int* label_ids8, bool gt_is_train_ids);
     /* Introspection for tests / bench. */
     const StixelParameters& GetParameters() const { return m_params; }
     const std::vector<float>& GetObjectCostLUT() const { return m_obj_cost_lut; }
@@ -206,6 +224,11 @@ private:
                          std::vector<StixelsData>& out) const;
     void ReservePackBuffers();
     is_instance_buffers InstanceBuffers(int image = 0) const;
+    /* The per-section instance map of frames 0 .. n_images-1 for RenderBatch, InstanceOverlapBatch and WorldBatch*:
+     * the ground-truth map while it is active (nothing is launched), else the cluster labels of the last compute call
+     * scattered into d_section_instance on `stream`; null after a call without instances. */
+    const int32_t* SectionInstanceMap(int n_images, void* stream);
+    bool HaveInstances() const { return m_gt_instances || m_render_instances; }
     GroundModel m_ground; /* per-frame ground model, storage reused between frames */
     /* the road parameters m_ground was computed for: a frame with the same parameters (a fixed
      * camera model, a replayed sequence) reuses it -- 1024 rows of erf / sqrt / log on the host
@@ -256,6 +279,15 @@ private:
     int m_render_images = 0;
     bool m_render_instances = false;
     DeviceArray<int32_t> d_section_instance; /* [max_batch][realcols][max_sections] */
+    /* AssignInstancesGTBatch: the ground-truth map of the same shape, whether the consumers read it, and its
+     * parameters; the packed (frame, column, section, label) quads behind their count, device and pinned host */
+    DeviceArray<int32_t> d_section_instance_gt;
+    DeviceArray<int32_t> d_section_instance_gt_packed; /* [4 + 4 * sections of the batch], is_pack_section_labels */
+    bool m_gt_instances = false;
+    double m_gt_min_fraction = 0.1;
+    int m_gt_label_ids[IS_INSTANCE_CLASSES] = {24, 25, 26, 27, 28, 31, 32, 33};
+    bool m_gt_is_train_ids = false;
+    PinnedArray<int32_t> h_section_instance_gt;
     DeviceArray<char> d_render_results;      /* [max_batch] double | [max_batch] int64 | [max_batch] int32 */
     PinnedArray<char> h_render_results;
     /* InstanceOverlapBatch: [max_batch][capacity] records, then n_records | overflow per frame, the packed records

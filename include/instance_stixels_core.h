@@ -456,6 +456,61 @@ typedef struct is_world_args {
  * for the counts and offsets, one per 64 frames for the records). */
 int is_stixel_world(const is_world_args* args, void* stream);
 
+/* ---- f8: instance ids from the ground-truth instance image, by majority vote (is_k_assign_gt.hip) -------------
+ * Replaces the second way the reference's evaluation tooling gives a stixel its instance id: assign_instances_gt
+ * (tools/visualization/clustering_visualization.py:846-891, option --use-instancegt of tools/run_cityscapes.py)
+ * over the per-class masks of load_instance_mask (tools/visualization/cityscapes_instance_loader.py:32-71), the
+ * upper-bound rows of its instance evaluation.  For every section in front of a column's terminator, whatever its
+ * type, with semantic class c and w = cols / realcols (integer division):
+ *   - c outside 11..18: -1.  Class c owns the labelId L = label_ids[c - 11] (c itself with gt_is_train_ids).
+ *   - the rectangle is image rows rows-1-vT .. rows-1-vB, image columns column*w .. column*w + w-1, clipped to the
+ *     frame in 64-bit arithmetic as is_render_sections clips (nothing outside the image is ever read; parity with
+ *     the reference is claimed for sections inside the frame); an empty rectangle gives -1.
+ *   - a pixel v votes for k = v - L*1000 if v > 1000 and L*1000 <= v < (L+1)*1000 (k in 0..999, the group id
+ *     L*1000 is k = 0); every other pixel -- other classes, ids <= 1000, negative or huge values -- votes for
+ *     background.  The most frequent value wins, background competes; ties go to background, then to the smaller
+ *     k (numpy's bincount().argmax()).
+ *   - the winner's pixel count must NOT be < (min_fraction * w) * (vT - vB), evaluated in binary64 in that order
+ *     without contraction -- vT - vB of the section as it stands, not its height, so a one-row stixel always
+ *     passes (the reference's quirk, :881-883).
+ *   - the label is k when a non-background value won and passed, else -1: the consumers turn it into the instance
+ *     image value c*1000 + k exactly as they do with cluster labels.
+ * Slots at and behind the terminator get -1, as is_section_instance_labels leaves them.
+ *
+ * Zero-initialise before setting fields.  All device arrays are on the current device.
+ *   d_sections, n_images, realcols, max_sections, rows, cols   as in is_render_args; rows * (cols / realcols) and
+ *                       n_images * ceil(realcols / 4) must fit 31 bits
+ *   d_gt_instance       [n_images][rows][cols] int32 (4-byte aligned; 16-byte aligned with cols % 8 == 0 and
+ *                       w == 8 takes the vector path); any value is accepted
+ *   min_fraction        0 (the zero-initialised struct) selects the reference's 0.1; a negative value switches the
+ *                       rule off; NaN is refused
+ *   h_label_ids         host [8] labelIds of classes 11..18, each in [0, 2147482]; NULL: Cityscapes
+ *                       {24, 25, 26, 27, 28, 31, 32, 33} (*_instanceIds.png).  Read before the call returns.
+ *   gt_is_train_ids     != 0: the ground truth holds c*1000 + k already (*_instanceTrainIds.png): L = c,
+ *                       h_label_ids is ignored
+ *   d_section_instance  [n_images][realcols][max_sections] int32, every slot written
+ *   d_section_votes     optional, same shape: the winner's pixel count (background's when background won, also
+ *                       when the rule rejected it), 0 where no vote took place */
+typedef struct is_assign_gt_args {
+    const is_section* d_sections;
+    const int32_t* d_gt_instance;
+    int n_images, rows, cols, realcols, max_sections;
+    double min_fraction;
+    const int* h_label_ids;
+    int gt_is_train_ids;
+    int32_t* d_section_instance;
+    int32_t* d_section_votes;
+} is_assign_gt_args;
+
+/* The map of n_images frames on `stream`, asynchronously: one launch, no allocation, copy or synchronisation. */
+int is_assign_instances_gt(const is_assign_gt_args* args, void* stream);
+/* The labelled slots (>= 0) of a per-section map [n_images][realcols][max_sections] for one small copy to the host:
+ * d_packed [4 + 4 * capacity] int32, 16-byte aligned: d_packed[0] = the number of labelled slots (the TRUE number,
+ * also beyond capacity), [1..3] = 0, then one (frame, column, section, label) quad per labelled slot, at most
+ * `capacity` of them, in no particular order.  n_images * realcols * max_sections < 2^31.  On `stream`. */
+int is_pack_section_labels(const int32_t* d_section_instance, int n_images, int realcols, int max_sections,
+                           int capacity, int32_t* d_packed, void* stream);
+
 /* Thin wrappers over the HIP runtime so that the plain-C++ host class needs no HIP headers
  * (the reference's callers are all .cu files; ours may be plain C++). */
 int is_device_malloc(void** ptr, size_t bytes);

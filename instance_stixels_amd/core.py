@@ -33,6 +33,7 @@ EXPORTS = [
     "is_section_instance_labels", "is_render_sections",
     "is_instance_overlap", "is_pack_overlap_records",
     "is_stixel_world",
+    "is_assign_instances_gt", "is_pack_section_labels",
 ]
 RENDER_MAX_LABELS = 64    # IS_RENDER_MAX_LABELS
 RENDER_MAX_CLASSES = 256  # IS_RENDER_MAX_CLASSES
@@ -93,6 +94,14 @@ class WorldArgs(ctypes.Structure):
                 ("capacity", ci), ("d_counts", vp), ("d_offsets", vp), ("d_frame_totals", vp), ("d_world", vp)]
 
 
+class AssignGtArgs(ctypes.Structure):
+    """is_assign_gt_args: zero-initialised by ctypes; device pointers as ints, h_label_ids a host pointer."""
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    _fields_ = [("d_sections", vp), ("d_gt_instance", vp), ("n_images", ci), ("rows", ci), ("cols", ci),
+                ("realcols", ci), ("max_sections", ci), ("min_fraction", ctypes.c_double), ("h_label_ids", vp),
+                ("gt_is_train_ids", ci), ("d_section_instance", vp), ("d_section_votes", vp)]
+
+
 class CoreError(RuntimeError):
     pass
 
@@ -146,6 +155,8 @@ def lib():
         L.is_instance_overlap.argtypes = [ctypes.POINTER(InstanceOverlapArgs), vp]
         L.is_pack_overlap_records.argtypes = [vp, vp, ci, ci, vp, vp]
         L.is_stixel_world.argtypes = [ctypes.POINTER(WorldArgs), vp]
+        L.is_assign_instances_gt.argtypes = [ctypes.POINTER(AssignGtArgs), vp]
+        L.is_pack_section_labels.argtypes = [vp, ci, ci, ci, ci, vp, vp]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
         L.is_get_device.argtypes = [ctypes.POINTER(ci)]
@@ -444,6 +455,28 @@ def stixel_world_ptr(alpha_ground, vhor, stream=0, **fields):
     vh = np.ascontiguousarray(vhor, np.int32)
     a.h_alpha_ground, a.h_vhor = alpha.ctypes.data, vh.ctypes.data
     _check(lib().is_stixel_world(ctypes.byref(a), ctypes.c_void_p(int(stream))), "is_stixel_world")
+
+
+def assign_instances_gt_ptr(stream=0, label_ids=None, **fields):
+    """is_assign_instances_gt on raw device pointers (ints): fields are those of AssignGtArgs (d_sections,
+    d_gt_instance, n_images, rows, cols, realcols, max_sections, min_fraction, gt_is_train_ids, d_section_instance,
+    d_section_votes); label_ids: a host sequence of the eight labelIds of classes 11..18, None for Cityscapes.
+    Asynchronous on `stream`."""
+    a = AssignGtArgs(**fields)
+    ids = None
+    if label_ids is not None:
+        ids = np.ascontiguousarray(label_ids, np.int32)
+        if ids.size != 8:
+            raise ValueError("label_ids must hold 8 ids")
+        a.h_label_ids = ids.ctypes.data
+    _check(lib().is_assign_instances_gt(ctypes.byref(a), ctypes.c_void_p(int(stream))), "is_assign_instances_gt")
+
+
+def pack_section_labels_ptr(d_section_instance, n_images, realcols, max_sections, capacity, d_packed, stream=0):
+    """is_pack_section_labels on raw device pointers (ints)."""
+    _check(lib().is_pack_section_labels(d_section_instance, int(n_images), int(realcols), int(max_sections),
+                                        int(capacity), d_packed, ctypes.c_void_p(int(stream))),
+           "is_pack_section_labels")
 
 
 def flip_and_pad(cnn_out, rows_power2_segmentation, device=0):

@@ -743,6 +743,47 @@ int is_stixel_world(const is_world_args* a, void* stream) {
     return IS_OK;
 }
 
+/* ---- f8: instance ids from the ground truth (is_k_assign_gt.hip) ---- */
+int is_assign_instances_gt(const is_assign_gt_args* a, void* stream) {
+    if (!a || !a->d_sections || !a->d_gt_instance) return fail_arg("null sections or gt");
+    if (!a->d_section_instance) return fail_arg("null d_section_instance");
+    if (a->n_images < 1 || a->realcols < 1 || a->rows < 1 || a->cols < a->realcols)
+        return fail_arg("bad shape (n_images >= 1, realcols >= 1, rows >= 1, cols >= realcols)");
+    if (a->max_sections < 1 || a->max_sections > 32767) return fail_arg("max_sections outside [1, 32767]");
+    if ((long long)a->rows * (a->cols / a->realcols) > 0x7fffffffLL)
+        return fail_arg("rows * (cols / realcols) does not fit 31 bits");
+    if ((long long)a->n_images * ((a->realcols + 3) / 4) > 0x7fffffffLL) return fail_arg("batch too large for one launch");
+    if ((uintptr_t)a->d_sections & 15) return fail_arg("d_sections must be 16-byte aligned");
+    if (((uintptr_t)a->d_gt_instance | (uintptr_t)a->d_section_instance | (uintptr_t)a->d_section_votes) & 3)
+        return fail_arg("d_gt_instance, d_section_instance and d_section_votes must be 4-byte aligned");
+    if (a->min_fraction != a->min_fraction) return fail_arg("min_fraction is NaN");
+    /* Cityscapes labelIds of trainIds 11..18 (cityscapes_instance_loader.py:45) */
+    static const int kCityscapes[IS_INSTANCE_CLASSES] = {24, 25, 26, 27, 28, 31, 32, 33};
+    int ids[IS_INSTANCE_CLASSES];
+    for (int i = 0; i < IS_INSTANCE_CLASSES; i++) {
+        ids[i] = a->gt_is_train_ids ? IS_FIRST_INSTANCE_CLASS + i : a->h_label_ids ? a->h_label_ids[i] : kCityscapes[i];
+        if (ids[i] < 0 || ids[i] > 2147482) return fail_arg("label id outside [0, 2147482]");
+    }
+    is_assign_gt_args r = *a;
+    if (r.min_fraction == 0.0) r.min_fraction = 0.1;
+    HIP_TRY(isk_launch_assign_gt(&r, ids, (hipStream_t)stream));
+    return IS_OK;
+}
+
+int is_pack_section_labels(const int32_t* d_section_instance, int n_images, int realcols, int max_sections,
+                           int capacity, int32_t* d_packed, void* stream) {
+    if (!d_section_instance || !d_packed) return fail_arg("null pointer");
+    if (n_images < 1 || realcols < 1 || max_sections < 1 || capacity < 0) return fail_arg("empty shape or negative capacity");
+    if ((long long)n_images * realcols * max_sections > 0x7fffffffLL)
+        return fail_arg("n_images * realcols * max_sections does not fit 31 bits");
+    if ((uintptr_t)d_section_instance & 3) return fail_arg("d_section_instance must be 4-byte aligned");
+    if ((uintptr_t)d_packed & 15) return fail_arg("d_packed must be 16-byte aligned");
+    const hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(d_packed, 0, 16, s));
+    HIP_TRY(isk_launch_pack_section_labels(d_section_instance, n_images, realcols, max_sections, capacity, d_packed, s));
+    return IS_OK;
+}
+
 static_assert(IS_CNT_N == IS_EVAL_COUNTERS, "is_device.h and instance_stixels_core.h disagree on the counter array");
 
 int is_set_eval_counters(is_ctx* c, int enabled) {

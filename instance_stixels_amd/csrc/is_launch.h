@@ -201,6 +201,11 @@ hipError_t isk_launch_pack_overlap(const is_overlap_record* records, const int32
 /* is_k_world.hip */
 hipError_t isk_launch_world(const is_world_args* w, hipStream_t stream);
 
+/* is_k_assign_gt.hip */
+hipError_t isk_launch_assign_gt(const is_assign_gt_args* r, const int* label_ids, hipStream_t stream);
+hipError_t isk_launch_pack_section_labels(const int32_t* map, int n_images, int realcols, int max_sections,
+                                          int capacity, int32_t* packed, hipStream_t stream);
+
 } /* extern "C" */
 
 #endif /* IS_LAUNCH_H_ */

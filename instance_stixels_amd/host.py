@@ -32,6 +32,7 @@ EXPORTS = [
     "ish_render_batch",
     "ish_instance_overlap_batch", "ish_instance_overlap_records", "ish_set_instance_overlap_capacity",
     "ish_world_batch", "ish_world_records", "ish_set_world_capacity",
+    "ish_assign_instances_gt_batch", "ish_assign_instances_gt_quads", "ish_use_cluster_instances", "ish_set_gt_assignment_parameters",
 ]
 WORLD_DTYPE = _core.WORLD_DTYPE  # is_world_stixel, the records of Stixels.WorldBatch
 
@@ -115,6 +116,10 @@ def lib():
         L.ish_world_records.argtypes = [vp, vp, ctypes.c_int64]
         L.ish_set_world_capacity.argtypes = [vp, ci]
         L.ish_get_input_disparity_on_device.restype = vp
+        L.ish_assign_instances_gt_batch.argtypes = [vp, ci, vp, ctypes.POINTER(ctypes.c_int64), vp]
+        L.ish_assign_instances_gt_quads.argtypes = [vp, vp, ctypes.c_int64]
+        L.ish_use_cluster_instances.argtypes = [vp]
+        L.ish_set_gt_assignment_parameters.argtypes = [vp, ctypes.c_double, vp, ci]
         _LIB = L
     return _LIB
 
@@ -343,6 +348,42 @@ class Stixels:
         records = out[:total] if out is not None and out.size >= total else np.empty(total, WORLD_DTYPE)
         self._check(lib().ish_world_records(self._h, records.ctypes.data if total else None, total), "WorldBatch")
         return offsets, records
+
+    def AssignInstancesGTBatch(self, n, d_gt, stream=0, with_mapping=True):
+        """Stixels::AssignInstancesGTBatch: the instance id of every stixel of frames 0 .. n-1 of the last Compute() /
+        ComputeBatch() by majority vote over the ground-truth instanceIds d_gt (device int32 [n][rows][cols], an int
+        pointer), as the reference tooling's assign_instances_gt.  From then on RenderBatch, InstanceOverlapBatch and
+        WorldBatch take their instance ids from this vote, until the next compute call or UseClusterInstances().
+        Returns per frame {(column, section): label} of every labelled section, or None without with_mapping."""
+        n = int(n)
+        p = ctypes.c_void_p(int(d_gt)) if d_gt else None
+        k = ctypes.c_int64(0)
+        self._check(lib().ish_assign_instances_gt_batch(self._h, n, p, ctypes.byref(k) if with_mapping else None,
+                                                        ctypes.c_void_p(int(stream))), "AssignInstancesGTBatch")
+        if not with_mapping:
+            return None
+        quads = np.empty((k.value, 4), np.int32)
+        self._check(lib().ish_assign_instances_gt_quads(self._h, quads.ctypes.data if k.value else None, k.value),
+                    "AssignInstancesGTBatch")
+        maps = [{} for _ in range(n)]
+        for f, u, v, l in quads.tolist():
+            maps[f][(u, v)] = l
+        return maps
+
+    def UseClusterInstances(self):
+        """Back to the cluster labels of the last compute call for RenderBatch / InstanceOverlapBatch / WorldBatch."""
+        self._check(lib().ish_use_cluster_instances(self._h), "UseClusterInstances")
+
+    def SetGTAssignmentParameters(self, min_fraction=0.1, label_ids=None, gt_is_train_ids=False):
+        """The parameters of AssignInstancesGTBatch: the minimum fraction of the reference's 10 % rule, the labelIds of
+        classes 11..18 (None: Cityscapes 24, 25, 26, 27, 28, 31, 32, 33), and whether the ground truth is in trainId
+        form (class*1000 + k)."""
+        ids = None if label_ids is None else np.ascontiguousarray(label_ids, np.int32)
+        if ids is not None and ids.size != 8:
+            raise ValueError("SetGTAssignmentParameters: label_ids must hold 8 ids")
+        self._check(lib().ish_set_gt_assignment_parameters(self._h, float(min_fraction),
+                                                           None if ids is None else ids.ctypes.data,
+                                                           int(bool(gt_is_train_ids))), "SetGTAssignmentParameters")
 
     def SetWorldCapacity(self, records_per_frame):
         """Records per frame of WorldBatch's first pass (a batch beyond it is repeated with its true total);

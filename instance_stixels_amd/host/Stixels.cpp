@@ -362,6 +362,7 @@ void Stixels::Finish() { /* Stixels.cu:250-283 */
     h_pack_offsets.release(); h_pack_sections.release();
     d_all_counts.release(); d_all_packed.release(); h_all_counts.release();
     d_section_instance.release(); d_render_results.release(); h_render_results.release();
+    d_section_instance_gt.release(); d_section_instance_gt_packed.release(); h_section_instance_gt.release();
     d_overlap_records.release(); d_overlap_packed.release(); h_overlap_packed.release();
     d_overlap_header.release(); h_overlap_header.release();
     d_world_counts.release(); d_world_offsets.release(); d_world_totals.release(); d_world.release();
@@ -369,6 +370,7 @@ void Stixels::Finish() { /* Stixels.cu:250-283 */
     m_world_known_offsets.clear();
     m_render_images = 0;
     m_render_instances = false;
+    m_gt_instances = false;
     IS_CHECK_RETURN(is_ctx_destroy(m_ctx));
     m_ctx = nullptr;
     IS_CHECK_RETURN(is_stream_destroy(m_stream));
@@ -444,6 +446,7 @@ float Stixels::Compute(const bool pairwise, StixelsData& stixels_data,
                                m_stream)); /* :535-590 */
     m_render_images = 1;
     m_render_instances = true;
+    m_gt_instances = false;
     m_world_alpha.assign(1, m_alpha_ground);
     m_world_vhor.assign(1, m_vhor);
     m_world_known_offsets.clear();
@@ -573,6 +576,7 @@ void Stixels::ComputeBatch(bool pairwise, int n_images, const pixel_t* d_big,
                                instance_stixels ? ibs.data() : nullptr, nullptr, nullptr, stream));
     m_render_images = n_images;
     m_render_instances = instance_stixels != nullptr;
+    m_gt_instances = false;
     m_world_alpha.resize(n_images);
     for (int i = 0; i < n_images; i++) m_world_alpha[i] = road[i].alpha_ground;
     m_world_vhor = vh;
@@ -634,7 +638,7 @@ std::vector<Stixels::RenderResult> Stixels::RenderBatch(int n_images, const Rend
                                     "there are none.");
     if (n_images < 1 || n_images > m_render_images)
         throw std::invalid_argument("RenderBatch: n_images outside [1, frames of the last compute call].");
-    if (t.instance != nullptr && !m_render_instances)
+    if (t.instance != nullptr && !HaveInstances())
         throw std::invalid_argument("RenderBatch: an instance image needs a compute call with instances.");
     const DeviceGuard guard(m_ctx_device);
     if (stream == nullptr) stream = m_stream;
@@ -668,14 +672,7 @@ std::vector<Stixels::RenderResult> Stixels::RenderBatch(int n_images, const Rend
         IS_CHECK_RETURN(is_memset(d_sum, 0, B * (sizeof(double) + sizeof(int64_t)), stream));
     }
     a.d_stixel_count = d_nst;
-    if (t.instance) { /* the cluster labels of every frame as a per-section map */
-        d_section_instance.reserve(B * m_realcols * m_max_sections);
-        std::vector<is_instance_buffers> ibs;
-        for (int i = 0; i < n_images; i++) ibs.push_back(InstanceBuffers(i));
-        IS_CHECK_RETURN(is_section_instance_labels(ibs.data(), n_images, m_realcols, m_max_sections,
-                                                   d_section_instance.get(), stream));
-        a.d_section_instance = d_section_instance.get();
-    }
+    if (t.instance) a.d_section_instance = SectionInstanceMap(n_images, stream);
     const int rc = is_render_sections(&a, stream);
     if (rc == IS_EINVAL) throw std::invalid_argument(std::string("RenderBatch: ") + is_last_error());
     IS_CHECK_RETURN(rc);
@@ -687,6 +684,85 @@ std::vector<Stixels::RenderResult> Stixels::RenderBatch(int n_images, const Rend
     std::vector<RenderResult> out(n_images);
     for (int i = 0; i < n_images; i++) out[i] = RenderResult{h_sum[i], h_cnt[i], h_nst[i]};
     return out;
+}
+
+/* The map the three consumers read.  With the ground-truth map active nothing is launched. */
+const int32_t* Stixels::SectionInstanceMap(int n_images, void* stream) {
+    if (m_gt_instances) return d_section_instance_gt.get();
+    if (!m_render_instances) return nullptr;
+    d_section_instance.reserve((size_t)m_max_batch * m_realcols * m_max_sections);
+    std::vector<is_instance_buffers> ibs;
+    for (int i = 0; i < n_images; i++) ibs.push_back(InstanceBuffers(i));
+    IS_CHECK_RETURN(is_section_instance_labels(ibs.data(), n_images, m_realcols, m_max_sections,
+                                               d_section_instance.get(), stream));
+    return d_section_instance.get();
+}
+
+void Stixels::SetGTAssignmentParameters(double min_fraction, const int* label_ids8, bool gt_is_train_ids) {
+    static const int kCityscapes[IS_INSTANCE_CLASSES] = {24, 25, 26, 27, 28, 31, 32, 33};
+    if (min_fraction != min_fraction) throw std::invalid_argument("SetGTAssignmentParameters: min_fraction is NaN.");
+    const int* ids = label_ids8 ? label_ids8 : kCityscapes;
+    for (int i = 0; i < IS_INSTANCE_CLASSES; i++)
+        if (ids[i] < 0 || ids[i] > 2147482)
+            throw std::invalid_argument("SetGTAssignmentParameters: label id outside [0, 2147482].");
+    m_gt_min_fraction = min_fraction;
+    for (int i = 0; i < IS_INSTANCE_CLASSES; i++) m_gt_label_ids[i] = ids[i];
+    m_gt_is_train_ids = gt_is_train_ids;
+}
+
+/* Replaces assign_instances_gt of the reference tooling (clustering_visualization.py:846-891) for a batch. */
+void Stixels::AssignInstancesGTBatch(int n_images, const int32_t* d_gt, void* stream,
+                                     std::vector<InstanceMapping>* mapping) {
+    if (m_render_images == 0)
+        throw std::invalid_argument("AssignInstancesGTBatch labels the Sections of the last Compute() or "
+                                    "ComputeBatch(): there are none.");
+    if (n_images < 1 || n_images > m_render_images)
+        throw std::invalid_argument("AssignInstancesGTBatch: n_images outside [1, frames of the last compute call].");
+    if (d_gt == nullptr) throw std::invalid_argument("AssignInstancesGTBatch: null d_gt_instance.");
+    const DeviceGuard guard(m_ctx_device);
+    if (stream == nullptr) stream = m_stream;
+    const size_t cs = (size_t)m_realcols * m_max_sections;
+    d_section_instance_gt.reserve((size_t)m_max_batch * cs);
+    is_assign_gt_args a = {};
+    a.d_sections = (const is_section*)d_stixels;
+    a.d_gt_instance = d_gt;
+    a.n_images = n_images;
+    a.rows = m_rows;
+    a.cols = m_cols;
+    a.realcols = m_realcols;
+    a.max_sections = m_max_sections;
+    /* (a 0 in the C struct selects its default; a negative fraction rejects exactly what 0 rejects: nothing) */
+    a.min_fraction = m_gt_min_fraction == 0.0 ? -1.0 : m_gt_min_fraction;
+    a.h_label_ids = m_gt_label_ids;
+    a.gt_is_train_ids = m_gt_is_train_ids ? 1 : 0;
+    a.d_section_instance = d_section_instance_gt.get();
+    const int rc = is_assign_instances_gt(&a, stream);
+    if (rc == IS_EINVAL) throw std::invalid_argument(std::string("AssignInstancesGTBatch: ") + is_last_error());
+    IS_CHECK_RETURN(rc);
+    if (n_images < m_render_images) /* the frames the vote did not cover have no instances */
+        IS_CHECK_RETURN(is_memset(d_section_instance_gt.get() + n_images * cs, 0xff,
+                                  (size_t)(m_render_images - n_images) * cs * sizeof(int32_t), stream));
+    m_gt_instances = true;
+    if (!mapping) return;
+    /* the labelled sections as quads behind their count: a label needs a section, so the sections of the batch
+     * (counted by ComputeBatch; every slot in front of a terminator after a Compute()) bound the quads */
+    const size_t cap = !m_world_known_offsets.empty() ? (size_t)m_world_known_offsets[n_images]
+                                                      : (size_t)n_images * m_realcols * (m_max_sections - 1);
+    const size_t words = 4 + 4 * cap;
+    h_section_instance_gt.reserve(words);
+    DeviceArray<int32_t>& d_packed = d_section_instance_gt_packed;
+    d_packed.reserve(words);
+    IS_CHECK_RETURN(is_pack_section_labels(d_section_instance_gt.get(), n_images, m_realcols, m_max_sections, (int)cap,
+                                           d_packed.get(), stream));
+    IS_CHECK_RETURN(is_memcpy_d2h(h_section_instance_gt.get(), d_packed.get(), words * sizeof(int32_t), stream));
+    IS_CHECK_RETURN(is_stream_synchronize(stream));
+    const int32_t* h = h_section_instance_gt.get();
+    if ((size_t)h[0] > cap) throw std::runtime_error("AssignInstancesGTBatch: more labelled sections than sections.");
+    mapping->assign(n_images, InstanceMapping());
+    for (int j = 0; j < h[0]; j++) {
+        const int32_t* q = h + 4 + 4 * (size_t)j;
+        (*mapping)[q[0]][std::make_pair(q[1], q[2])] = q[3];
+    }
 }
 
 void Stixels::SetInstanceOverlapCapacity(int records) {
@@ -702,7 +778,7 @@ std::vector<std::vector<is_overlap_record>> Stixels::InstanceOverlapBatch(int n_
                                     "there are none.");
     if (n_images < 1 || n_images > m_render_images)
         throw std::invalid_argument("InstanceOverlapBatch: n_images outside [1, frames of the last compute call].");
-    if (!m_render_instances)
+    if (!HaveInstances())
         throw std::invalid_argument("InstanceOverlapBatch: needs a compute call with instances.");
     if (d_gt == nullptr) throw std::invalid_argument("InstanceOverlapBatch: null d_gt_instance.");
     const DeviceGuard guard(m_ctx_device);
@@ -710,21 +786,17 @@ std::vector<std::vector<is_overlap_record>> Stixels::InstanceOverlapBatch(int n_
     const size_t B = (size_t)m_max_batch;
     const size_t cs = (size_t)m_realcols * m_max_sections;
     const size_t cap = (size_t)m_overlap_capacity;
-    d_section_instance.reserve(B * cs);
     d_overlap_header.reserve(2 * B);
     h_overlap_header.reserve(2 * B);
     d_overlap_records.reserve(B * cap);
     d_overlap_packed.reserve(B * cap);
     h_overlap_packed.reserve(B * cap);
-    std::vector<is_instance_buffers> ibs;
-    for (int i = 0; i < n_images; i++) ibs.push_back(InstanceBuffers(i));
-    IS_CHECK_RETURN(is_section_instance_labels(ibs.data(), n_images, m_realcols, m_max_sections,
-                                               d_section_instance.get(), stream));
+    const int32_t* const section_instance = SectionInstanceMap(n_images, stream);
     const size_t frame_px = (size_t)m_rows * m_cols;
     auto args = [&](int first, int n, int capacity, is_overlap_record* rec, int32_t* hdr) {
         is_instance_overlap_args a = {};
         a.d_sections = d_stixels + first * cs;
-        a.d_section_instance = d_section_instance.get() + first * cs;
+        a.d_section_instance = section_instance + first * cs;
         a.n_images = n;
         a.realcols = m_realcols;
         a.max_sections = m_max_sections;
@@ -851,14 +923,7 @@ const is_world_stixel* Stixels::WorldBatchView(int n_images, std::vector<int32_t
                        : std::min((size_t)(m_world_capacity ? m_world_capacity : 4096), frame_max) * n_images;
     is_world_args a = {};
     a.d_sections = (const is_section*)d_stixels;
-    if (m_render_instances) { /* the cluster labels of every frame as a per-section map */
-        d_section_instance.reserve(B * m_realcols * m_max_sections);
-        std::vector<is_instance_buffers> ibs;
-        for (int i = 0; i < n_images; i++) ibs.push_back(InstanceBuffers(i));
-        IS_CHECK_RETURN(is_section_instance_labels(ibs.data(), n_images, m_realcols, m_max_sections,
-                                                   d_section_instance.get(), stream));
-        a.d_section_instance = d_section_instance.get();
-    }
+    a.d_section_instance = SectionInstanceMap(n_images, stream);
     a.n_images = n_images;
     a.realcols = m_realcols;
     a.max_sections = m_max_sections;
@@ -937,6 +1002,7 @@ void Stixels::ComputeBatchGather(bool pairwise, int n_images, const pixel_t* d_b
                                g.inv_sigma2.data(), vh.data(), pairwise ? 1 : 0, n_images, d_stixels, nullptr,
                                nullptr, nullptr, stream));
     m_render_images = 0; /* (d_stixels now holds this rank's shard; RenderBatch renders Compute / ComputeBatch) */
+    m_gt_instances = false;
 
     /* ---- pack: per-column counts + the used sections (10-40 of the 200 slots of a column) */
     ReservePackBuffers();

@@ -350,6 +350,47 @@ int ish_set_world_capacity(void* h, int records_per_frame) {
     return guard([&] { ((Stixels*)h)->SetWorldCapacity(records_per_frame); });
 }
 
+/* AssignInstancesGTBatch(): the ground-truth vote over frames 0 .. n-1 of the last Compute() / ComputeBatch(); from
+ * then on RenderBatch / InstanceOverlapBatch / WorldBatch read its map.  n_quads (optional): the number of labelled
+ * sections; their (frame, column, section, label) quads stay with the calling thread until ish_assign_instances_gt_quads
+ * copies them out -- the caller sizes that buffer from *n_quads.  Null: no mapping is fetched, the call is asynchronous. */
+namespace {
+thread_local std::vector<int32_t> g_gt_quads;
+thread_local void* g_gt_owner = nullptr;
+}
+int ish_assign_instances_gt_batch(void* h, int n, const int32_t* d_gt_instance, int64_t* n_quads, void* stream) {
+    return guard([&] {
+        g_gt_quads.clear();
+        g_gt_owner = nullptr;
+        std::vector<Stixels::InstanceMapping> maps;
+        ((Stixels*)h)->AssignInstancesGTBatch(n, d_gt_instance, stream, n_quads ? &maps : nullptr);
+        if (!n_quads) return;
+        for (int i = 0; i < n; i++)
+            for (const auto& kv : maps[i]) {
+                const int32_t q[4] = {i, kv.first.first, kv.first.second, kv.second};
+                g_gt_quads.insert(g_gt_quads.end(), q, q + 4);
+            }
+        *n_quads = (int64_t)(g_gt_quads.size() / 4);
+        g_gt_owner = h;
+    });
+}
+int ish_assign_instances_gt_quads(void* h, int32_t* out, int64_t cap) {
+    return guard([&] {
+        if (h != g_gt_owner || (int64_t)(g_gt_quads.size() / 4) > cap)
+            throw std::invalid_argument("ish_assign_instances_gt_quads: no quads of this object, or cap too small.");
+        if (!g_gt_quads.empty()) std::memcpy(out, g_gt_quads.data(), g_gt_quads.size() * sizeof(int32_t));
+        g_gt_quads.clear();
+        g_gt_owner = nullptr;
+    });
+}
+int ish_use_cluster_instances(void* h) {
+    return guard([&] { ((Stixels*)h)->UseClusterInstances(); });
+}
+/* label_ids8: host [8] or null for Cityscapes */
+int ish_set_gt_assignment_parameters(void* h, double min_fraction, const int* label_ids8, int gt_is_train_ids) {
+    return guard([&] { ((Stixels*)h)->SetGTAssignmentParameters(min_fraction, label_ids8, gt_is_train_ids != 0); });
+}
+
 int ish_set_device(void* h, int device) {
     return guard([&] { ((Stixels*)h)->SetDevice(device); });
 }
