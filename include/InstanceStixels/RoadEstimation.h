@@ -73,15 +73,22 @@ public:
      * by accumulator votes (descending, ties by accumulator index). */
     static std::vector<std::pair<float, float>> HoughLines(const uint8_t* image, int rows, int cols,
                                                            float rho, float theta, int threshold);
+    /* The line choice of Compute / ComputeBatch on a given list, for a camera and a v-disparity image of `rows`
+     * rows, without a device: the index of the first line whose pitch passes the gate (out = its road
+     * parameters), or -1 (out untouched). */
+    static int ChooseLine(float camera_center_y, float baseline, float focal, int rows,
+                          const std::pair<float, float>* lines, size_t n, Stixels::RoadParameters& out);
 
 private:
+    /* the camera and the pitch gate of Initialize (everything the line choice reads) */
+    void SetCamera(float camera_center_y, float baseline, float focal, int rows);
     void ComputeCameraProperties(int vdisp_rows, const float rho, const float theta,
                                  float& horizonPoint, float& pitch, float& cameraHeight,
                                  float& slope) const;
     bool ComputeHough(float& rho, float& theta, float& horizonPoint, float& pitch,
                       float& cameraHeight, float& slope);
-    /* the line choice of ComputeHough over lines[0 .. n) */
-    bool ChooseLine(const std::pair<float, float>* lines, size_t n, Stixels::RoadParameters& out) const;
+    /* the line choice of ComputeHough over lines[0 .. n): the index of the accepted line, or -1 */
+    int ChooseLine(const std::pair<float, float>* lines, size_t n, Stixels::RoadParameters& out) const;
     void FreeBatch();
 
     bool m_is_initialized = false;

@@ -27,7 +27,7 @@ EXPORTS = [
     "ish_get_instance_stixels", "ish_get_3d_vertices", "ish_save_stixels", "ish_time_compute",
     "ish_set_device", "ish_compute_batch", "ish_time_compute_batch", "ish_compute_batch_gather",
     "ire_create", "ire_destroy", "ire_initialize", "ire_finish", "ire_compute", "ire_get_binary",
-    "ire_hough_lines", "ire_set_device", "ire_active_device", "ire_compute_device",
+    "ire_hough_lines", "ire_choose_line", "ire_set_device", "ire_active_device", "ire_compute_device",
     "ish_get_input_disparity_on_device", "ire_compute_batch", "ire_set_batch_limits", "ire_batch_fallbacks",
     "ish_render_batch",
     "ish_instance_overlap_batch", "ish_instance_overlap_records", "ish_set_instance_overlap_capacity",
@@ -101,6 +101,7 @@ def lib():
         L.ire_compute.argtypes = [vp, vp, ctypes.c_size_t, vp]
         L.ire_get_binary.argtypes = [vp, vp, ctypes.c_size_t]
         L.ire_hough_lines.argtypes = [vp, ci, ci, cf, cf, ci, vp, ci]
+        L.ire_choose_line.argtypes = [cf, cf, cf, ci, vp, ci, vp]
         L.ire_set_device.argtypes = [vp, ci]
         L.ire_active_device.argtypes = [vp]
         L.ire_compute_device.argtypes = [vp, vp, vp]
@@ -444,6 +445,19 @@ def hough_lines(image, rho=1.0, theta=float(np.pi / 180), threshold=25, cap=4096
     n = lib().ire_hough_lines(img.ctypes.data, img.shape[0], img.shape[1], rho, theta, threshold,
                               out.ctypes.data, cap)
     return out[:min(n, cap)].copy()
+
+
+def choose_line(lines, camera_center_y, baseline, focal, rows):
+    """RoadEstimation::ChooseLine on lines [n][2] (rho, theta), for a camera and a v-disparity image of `rows`
+    rows; needs no device.  Returns (index, road): the index of the first line whose pitch passes the gate and
+    its (vhor_image, camera_tilt, camera_height, alpha_ground), or (-1, None)."""
+    l = np.ascontiguousarray(lines, np.float32).reshape(-1, 2)
+    out = np.zeros(1, ROAD_PARAMETERS_DTYPE)
+    k = int(lib().ire_choose_line(camera_center_y, baseline, focal, int(rows), l.ctypes.data, len(l), out.ctypes.data))
+    if k < 0:
+        return -1, None
+    r = out[0]
+    return k, (int(r["vhor"]), np.float32(r["camera_tilt"]), np.float32(r["camera_height"]), np.float32(r["alpha_ground"]))
 
 
 class RoadEstimation:

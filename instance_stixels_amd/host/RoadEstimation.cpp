@@ -21,20 +21,15 @@ RoadEstimation::~RoadEstimation() {}
 void RoadEstimation::Initialize(const float camera_center_y, const float baseline,
                                 const float focal, const int rows, const int cols,
                                 const int max_dis, const float road_vdisparity_threshold) {
-    m_cy = camera_center_y; /* RE.cu:37-40 */
-    m_b = baseline;
     /* re-initialisation (a new frame shape or camera, stixels_wrapper.cu:124-152) releases the stream and the
      * buffers of the previous one first -- on THEIR device, which Finish() still knows */
     if (m_is_initialized || m_stream) Finish();
-    m_focal = focal;
+    SetCamera(camera_center_y, baseline, focal, rows);
     m_HoughAccumThr = 25; /* RE.cu:45-57 */
     m_binThr = road_vdisparity_threshold;
-    m_maxPitch = 50 * kPi / 180.0f;
-    m_minPitch = -50 * kPi / 180.0f;
     m_maxCameraHeight = 1.90f;
     m_minCameraHeight = 1.30f;
     m_max_dis = max_dis;
-    m_rows = rows;
     m_cols = cols;
     m_rho = m_theta = 0;
     m_horizonPoint = 0;
@@ -51,6 +46,15 @@ void RoadEstimation::Initialize(const float camera_center_y, const float baselin
     d_maximum.reserve(1);
     d_vDispBinary.reserve((size_t)m_max_dis * m_rows);
     m_is_initialized = true;
+}
+
+void RoadEstimation::SetCamera(float camera_center_y, float baseline, float focal, int rows) {
+    m_cy = camera_center_y; /* RE.cu:37-40 */
+    m_b = baseline;
+    m_focal = focal;
+    m_maxPitch = 50 * kPi / 180.0f; /* RE.cu:47-57 */
+    m_minPitch = -50 * kPi / 180.0f;
+    m_rows = rows;
 }
 
 void RoadEstimation::Finish() { /* RE.cu:84-92 */
@@ -125,14 +129,14 @@ void RoadEstimation::ComputeBatch(const pixel_t* d_im, int n_images, Stixels::Ro
         lines.resize(nl);
         for (int k = 0; k < nl; k++)
             lines[k] = std::make_pair(h_lines[((size_t)i * L + k) * 2], h_lines[((size_t)i * L + k) * 2 + 1]);
-        bool found = !overflow[i] && ChooseLine(lines.data(), lines.size(), out[i]);
+        bool found = !overflow[i] && ChooseLine(lines.data(), lines.size(), out[i]) >= 0;
         if (!found && (overflow[i] || total[i] > L)) { /* the lines the device kept do not decide it */
             m_batch_binary.resize(cells);
             IS_CHECK_RETURN(is_memcpy_d2h(m_batch_binary.data(), is_road_ctx_binary(m_batch_ctx) + i * cells,
                                           cells, s));
             IS_CHECK_RETURN(is_stream_synchronize(s));
             lines = HoughLines(m_batch_binary.data(), m_rows, m_max_dis, 1.0f, kPi / 180, m_HoughAccumThr);
-            found = ChooseLine(lines.data(), lines.size(), out[i]);
+            found = ChooseLine(lines.data(), lines.size(), out[i]) >= 0;
             m_batch_fallbacks++;
         }
         ok[i] = found ? 1 : 0;
@@ -140,8 +144,15 @@ void RoadEstimation::ComputeBatch(const pixel_t* d_im, int n_images, Stixels::Ro
     }
 }
 
-bool RoadEstimation::ChooseLine(const std::pair<float, float>* lines, size_t n,
-                                Stixels::RoadParameters& out) const { /* ComputeHough's loop */
+int RoadEstimation::ChooseLine(float camera_center_y, float baseline, float focal, int rows,
+                               const std::pair<float, float>* lines, size_t n, Stixels::RoadParameters& out) {
+    RoadEstimation re; /* (no device buffers: never initialised) */
+    re.SetCamera(camera_center_y, baseline, focal, rows);
+    return re.ChooseLine(lines, n, out);
+}
+
+int RoadEstimation::ChooseLine(const std::pair<float, float>* lines, size_t n,
+                               Stixels::RoadParameters& out) const { /* ComputeHough's loop */
     float rho, theta, horizonPoint, pitch, cameraHeight, slope;
     for (size_t k = 0; k < n; k++) {
         rho = std::abs(lines[k].first);
@@ -149,10 +160,10 @@ bool RoadEstimation::ChooseLine(const std::pair<float, float>* lines, size_t n,
         ComputeCameraProperties(m_rows, rho, theta, horizonPoint, pitch, cameraHeight, slope);
         if (pitch >= m_minPitch && pitch <= m_maxPitch) {
             out = Stixels::RoadParameters{(int)ceil(horizonPoint), pitch, cameraHeight, slope};
-            return true;
+            return (int)k;
         }
     }
-    return false;
+    return -1;
 }
 
 bool RoadEstimation::Compute(const std::vector<pixel_t>& im) { /* RE.cu:94-102 */

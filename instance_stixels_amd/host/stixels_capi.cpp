@@ -507,5 +507,12 @@ int ire_hough_lines(const uint8_t* image, int rows, int cols, float rho, float t
     for (int i = 0; i < n; i++) { out[2 * i] = lines[i].first; out[2 * i + 1] = lines[i].second; }
     return (int)lines.size();
 }
+/* RoadEstimation::ChooseLine on lines [n][2] (rho, theta), without a device: the index of the accepted line
+ * (out: one Stixels::RoadParameters record) or -1 (out untouched) */
+int ire_choose_line(float cy, float baseline, float focal, int rows, const float* lines, int n, void* out) {
+    std::vector<std::pair<float, float>> l((size_t)std::max(n, 0));
+    for (int i = 0; i < n; i++) l[i] = std::make_pair(lines[2 * i], lines[2 * i + 1]);
+    return RoadEstimation::ChooseLine(cy, baseline, focal, rows, l.data(), l.size(), *(Stixels::RoadParameters*)out);
+}
 
 } /* extern "C" */

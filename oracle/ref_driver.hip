@@ -14,6 +14,10 @@
  *                        instance-candidate arrays the class left on the device.
  *   ref_road_vdisparity  the three kernels of RoadEstimationKernels.cu with the launch geometry
  *                        of RoadEstimation::Compute.
+ *   ref_road_*           the reference's RoadEstimation class itself: Initialize, Compute(host
+ *                        image), the getters, Finish.  Its one call into OpenCV, cv::HoughLines,
+ *                        lands in ref_stubs/opencv2/opencv.hpp, which holds no transform: it
+ *                        records its arguments and returns the lines ref_road_set_lines installed.
  *
  * The reference's device asserts are compiled out (-DNDEBUG, as in its release build), so the
  * host checks below are what keep an input outside the reference's domain from
@@ -21,8 +25,9 @@
  * compares them (class costs, instance offsets); the one value it indexes with is the argmin
  * class of Cityscapes.h's fixed 19-class loops (semantic_class - 11 in [0, 8)).
  *
- * Stixels is opened with `private` read as `public` in this translation unit only, to read the
- * device buffers the class keeps (the layout does not change; the reference is not edited).
+ * Stixels and RoadEstimation are opened with `private` read as `public` in this translation unit
+ * only, to read the device buffers and the shape the classes keep (the layout does not change;
+ * the reference is not edited).
  */
 #include <hip/hip_runtime.h>
 
@@ -39,6 +44,7 @@
 
 #define private public
 #include "Stixels.hpp"
+#include "RoadEstimation.h"
 #undef private
 #include "RoadEstimationKernels.h"
 
@@ -305,6 +311,91 @@ int ref_road_vdisparity(const float* disparity, int rows, int cols, int max_dis,
     for (void* p : {(void*)d_disparity, (void*)d_vdisp, (void*)d_maximum, (void*)d_binary})
         if (p) (void)hipFree(p);
     return rc;
+}
+
+// ---- the reference's RoadEstimation class ------------------------------------------------------
+// One object per handle.  The class neither checks its shape nor the bins it counts into, so
+// initialize and compute check them here, as ref_road_vdisparity does.
+
+int ref_road_create(void** out) {
+    *out = new RoadEstimation();
+    return REF_OK;
+}
+
+int ref_road_finish(void* h) {
+    RoadEstimation* re = static_cast<RoadEstimation*>(h);
+    if (re->IsInitialized()) re->Finish();
+    return REF_OK;
+}
+
+int ref_road_destroy(void* h) {
+    if (!h) return REF_OK;
+    ref_road_finish(h);
+    delete static_cast<RoadEstimation*>(h);
+    return REF_OK;
+}
+
+// Initialize; an initialised object is finished first (the class itself would leak its buffers),
+// which is what the reference's wrapper does before it initialises for another shape.
+int ref_road_initialize(void* h, float camera_center_y, float baseline, float focal, int rows, int cols,
+                        int max_dis, float threshold) {
+    if (rows < 1 || cols < 1 || max_dis < 1) return fail(REF_E_DOMAIN, "empty frame");
+    RoadEstimation* re = static_cast<RoadEstimation*>(h);
+    ref_road_finish(h);
+    re->Initialize(camera_center_y, baseline, focal, rows, cols, max_dis, threshold);
+    return REF_OK;
+}
+
+// The lines the stub's cv::HoughLines returns from now on: lines [n][2] (rho, theta).
+int ref_road_set_lines(const float* lines, int n) {
+    std::vector<cv::Vec2f>& a = cv::hough_lines_stub().answer;
+    a.resize((size_t)(n > 0 ? n : 0));
+    for (int i = 0; i < n; ++i) {
+        a[i][0] = lines[2 * i];
+        a[i][1] = lines[2 * i + 1];
+    }
+    return REF_OK;
+}
+
+// RoadEstimation::Compute(const std::vector<pixel_t>&) on disparity [rows][cols]; *ok: its return value.
+int ref_road_compute(void* h, const float* disparity, size_t n, int* ok) {
+    RoadEstimation* re = static_cast<RoadEstimation*>(h);
+    if (!re->IsInitialized()) return fail(REF_E_DOMAIN, "RoadEstimation is not initialised");
+    if (n != (size_t)re->m_rows * re->m_cols) return fail(REF_E_DOMAIN, "the image is not rows x cols");
+    for (size_t i = 0; i < n; ++i)  // ComputeHistogram indexes with (int) d for every d != 0
+        if (!(disparity[i] >= 0.0f && disparity[i] < (float)re->m_max_dis))
+            return fail(REF_E_DOMAIN, "disparity outside [0, max_dis) at pixel " + std::to_string(i));
+    const bool found = re->Compute(std::vector<pixel_t>(disparity, disparity + n));
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail("reference RoadEstimation::Compute", e);
+    *ok = found ? 1 : 0;
+    return REF_OK;
+}
+
+// out5: pitch, camera height, slope, and the (|rho|, theta) of the line the class accepted last
+int ref_road_get(void* h, int* horizon_point, float* out5) {
+    RoadEstimation* re = static_cast<RoadEstimation*>(h);
+    *horizon_point = re->GetHorizonPoint();
+    out5[0] = re->GetPitch();
+    out5[1] = re->GetCameraHeight();
+    out5[2] = re->GetSlope();
+    out5[3] = re->m_rho;
+    out5[4] = re->m_theta;
+    return REF_OK;
+}
+
+// What the stub's cv::HoughLines saw last.  ints: rows, cols, type, threshold, calls so far;
+// doubles: rho, theta; image (may be null): up to n bytes of its copy of the image.
+int ref_road_hough_call(int* ints, double* doubles, uint8_t* image, size_t n) {
+    const cv::HoughLinesStub& s = cv::hough_lines_stub();
+    ints[0] = s.rows; ints[1] = s.cols; ints[2] = s.type; ints[3] = s.threshold; ints[4] = s.calls;
+    doubles[0] = s.rho; doubles[1] = s.theta;
+    if (image) {
+        if (n != s.image.size()) return fail(REF_E_DOMAIN, "the recorded image has another size");
+        std::memcpy(image, s.image.data(), n);
+    }
+    return REF_OK;
 }
 
 }  // extern "C"

@@ -45,6 +45,14 @@ def lib():
         L.ref_shapes.argtypes = [vp, vp]
         L.ref_stixels_compute.argtypes = [vp, ci, vp, vp, ci, cf, cf, cf, vp, vp, vp, vp, vp, vp, vp, vp]
         L.ref_road_vdisparity.argtypes = [vp, ci, ci, ci, cf, vp, vp, vp]
+        L.ref_road_create.argtypes = [vp]
+        L.ref_road_destroy.argtypes = [vp]
+        L.ref_road_finish.argtypes = [vp]
+        L.ref_road_initialize.argtypes = [vp, cf, cf, cf, ci, ci, ci, cf]
+        L.ref_road_set_lines.argtypes = [vp, ci]
+        L.ref_road_compute.argtypes = [vp, vp, ctypes.c_size_t, vp]
+        L.ref_road_get.argtypes = [vp, vp, vp]
+        L.ref_road_hough_call.argtypes = [vp, vp, vp, ctypes.c_size_t]
         _LIB = L
     return _LIB
 
@@ -136,3 +144,51 @@ def road_vdisparity(disparity, max_dis, threshold):
     _check(lib().ref_road_vdisparity(_p(d), rows, cols, int(max_dis), ctypes.c_float(threshold), _p(vdisp),
                                      _p(binary), _p(m)))
     return vdisp, binary, int(m[0])
+
+
+class RoadEstimation:
+    """The reference's RoadEstimation class.  Its cv::HoughLines is the stub of oracle/ref_stubs/opencv2:
+    no transform, it returns what `set_hough_lines` installed and records its arguments (`hough_call`)."""
+
+    def __init__(self):
+        self._h = ctypes.c_void_p()
+        _check(lib().ref_road_create(ctypes.byref(self._h)))
+
+    def Initialize(self, camera_center_y, baseline, focal, rows, cols, max_dis, road_vdisparity_threshold=0.2):
+        _check(lib().ref_road_initialize(self._h, camera_center_y, baseline, focal, int(rows), int(cols),
+                                         int(max_dis), road_vdisparity_threshold))
+
+    def Compute(self, disparity):
+        d = np.ascontiguousarray(disparity, np.float32)
+        ok = ctypes.c_int(0)
+        _check(lib().ref_road_compute(self._h, _p(d), d.size, ctypes.byref(ok)))
+        hp, out = ctypes.c_int(0), np.zeros(5, np.float32)
+        _check(lib().ref_road_get(self._h, ctypes.byref(hp), _p(out)))
+        self.horizon_point, self.pitch, self.camera_height, self.slope = hp.value, out[0], out[1], out[2]
+        self.accepted_line = out[3:5].copy()       # (|rho|, theta) of the line accepted last
+        return bool(ok.value)
+
+    def Finish(self):
+        _check(lib().ref_road_finish(self._h))
+
+    def close(self):
+        if self._h:
+            _check(lib().ref_road_destroy(self._h))
+            self._h = ctypes.c_void_p()
+
+
+def set_hough_lines(lines):
+    """The (rho, theta) list [n][2] the stub's cv::HoughLines returns from now on."""
+    l = np.ascontiguousarray(lines, np.float32).reshape(-1, 2)
+    _check(lib().ref_road_set_lines(_p(l), len(l)))
+
+
+def hough_call():
+    """What the stub's cv::HoughLines saw last: dict(image uint8 [rows][cols], type, rho, theta (doubles),
+    threshold, calls)."""
+    ints, dbl = np.zeros(5, np.int32), np.zeros(2, np.float64)
+    _check(lib().ref_road_hough_call(_p(ints), _p(dbl), None, 0))
+    image = np.zeros((max(int(ints[0]), 0), max(int(ints[1]), 0)), np.uint8)
+    _check(lib().ref_road_hough_call(_p(ints), _p(dbl), _p(image), image.size))
+    return dict(image=image, type=int(ints[2]), threshold=int(ints[3]), calls=int(ints[4]), rho=float(dbl[0]),
+                theta=float(dbl[1]))

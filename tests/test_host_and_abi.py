@@ -165,6 +165,14 @@ def test_hough_lines_on_synthetic_plane():
     slope = (0 - down) / (rho / np.sin(theta) - last)
     assert abs(slope - alpha) < 0.03
     assert len(host.hough_lines(np.zeros((64, 32), np.uint8))) == 0
+    # the whole list, bit for bit, against the float64 definition (tests/hough_reference.py): the image has a few
+    # votes float64 cannot place, but none of them touches a peak or a peak's neighbour, so the list is determined
+    from hough_reference import Hough
+    h = Hough(img, threshold=25)
+    assert h.determined() and h.n_ambiguous <= 8
+    want = h.lines()[0]
+    assert lines.shape == want.shape and np.array_equal(lines.view(np.int32), want.view(np.int32))
+    h.check_lines(lines)
 
 
 def test_oracle_vdisparity_kernels():

@@ -279,6 +279,165 @@ def test_vdisparity_kernels():
             assert np.array_equal(r_v, v) and np.array_equal(r_b, b) and r_m == m, (i, what)
 
 
+def _road_three_way(ours, ref, frame, D, what):
+    """One frame through our RoadEstimation::Compute and the reference's, the reference's cv::HoughLines answering
+    with OUR host transform of our binary image: the same return value, horizon point and pitch / height / slope
+    bits; the call the reference made: the image equal to our binary v-disparity, rho 1, our theta, threshold 25.
+    Returns (ok, horizon point, pitch, height, slope) or None where the driver refuses the frame."""
+    from hough_reference import THETA
+    from instance_stixels_amd import host
+    from test_road_batch_gpu import HOUGH_THR, _bits, _oracle_safe
+    ok = ours.Compute(frame)
+    binary = ours.GetBinaryVDisparity()
+    lines = host.hough_lines(binary, cap=1 << 20)
+    reference.set_hough_lines(lines)
+    if not _oracle_safe(frame, D):     # the reference does not bounds-check its bins: the driver must refuse
+        with pytest.raises(reference.ReferenceError) as e:
+            ref.Compute(frame)
+        assert e.value.code == reference.REF_E_DOMAIN
+        return None
+    before = reference.hough_call()["calls"]
+    assert ref.Compute(frame) == ok, what
+    call = reference.hough_call()
+    assert call["calls"] == before + 1
+    assert call["image"].shape == binary.shape and np.array_equal(call["image"], binary), what
+    assert call["type"] == 0 and call["rho"] == 1.0 and call["threshold"] == HOUGH_THR
+    assert np.float32(call["theta"]).view(np.int32) == THETA.view(np.int32)      # RoadEstimation.cpp's kPi / 180
+    got = (ours.horizon_point, ours.pitch, ours.camera_height, ours.slope)
+    if ok:
+        assert ours.horizon_point == ref.horizon_point, what
+        assert np.array_equal(_bits(got[1:]), _bits([ref.pitch, ref.camera_height, ref.slope])), what
+    return (ok,) + got
+
+
+@pytest.mark.parametrize("shape", [(256, 512, 64), (1024, 2048, 128)])
+def test_road_estimation_class(shape):
+    """RoadEstimation::Compute and ComputeBatch against the reference's RoadEstimation class (RoadEstimation.cu
+    built as it stands; its cv::HoughLines is the stub of oracle/ref_stubs/opencv2 and returns the lines of our
+    host transform), on the frames of test_road_batch_gpu._batch that lie in the reference's domain."""
+    import torch
+    from instance_stixels_amd import host
+    from test_road_batch_gpu import _batch, _init, _same
+    rows, cols, D = shape
+    n = 8
+    disp, cases = _batch(rows, cols, D, n, seed=rows + D)
+    cfg = cases[0]["cfg"]
+    ours, ref = host.RoadEstimation(), reference.RoadEstimation()
+    try:
+        _init(ours, cfg, rows, cols, D)
+        ref.Initialize(cfg.camera_center_y * rows / 1024, cfg.baseline, cfg.focal, rows, cols, D)
+        single = [_road_three_way(ours, ref, disp[i], D, i) for i in range(n)]
+        keep = [i for i in range(n) if single[i] is not None]
+        assert len(keep) >= 6 and any(single[i][0] for i in keep) and not all(single[i][0] for i in keep)
+        d = torch.from_numpy(disp[keep]).to(torch.device("cuda", 0))
+        road, ok = ours.ComputeBatch(d.data_ptr(), len(keep))
+        _same(road, ok, [single[i] for i in keep])
+    finally:
+        ours.close()
+        ref.close()
+
+
+def test_road_estimation_reinitialize():
+    """Another shape and another camera between frames, on both sides (the reference's caller finishes the object
+    before it initialises it again; the driver does that)."""
+    from instance_stixels_amd import host
+    from test_road_batch_gpu import _batch
+    a = (256, 512, 64, 128.0, 0.209313, 2262.52)
+    b = (128, 256, 32, 70.0, 0.35, 300.0)
+    frames = {s: _batch(s[0], s[1], s[2], 2, seed=5 + s[0])[0] for s in (a, b)}
+    ours, ref = host.RoadEstimation(), reference.RoadEstimation()
+    try:
+        seen = []
+        for k, s in enumerate((a, b, a, b)):
+            rows, cols, D, cy, base, focal = s
+            ours.Initialize(cy, base, focal, rows, cols, D)
+            ref.Initialize(cy, base, focal, rows, cols, D)
+            out = _road_three_way(ours, ref, frames[s][k // 2], D, k)
+            assert out is not None and out[0]
+            seen.append(out)
+        assert seen[0] != seen[1] and seen[2] != seen[3]      # the other camera gives another road
+    finally:
+        ours.close()
+        ref.close()
+
+
+def _edge_lines(camera, rows, D):
+    """Integral (rho, n) pairs that put the pitch just inside and just outside the gate: neighbours in rho at one
+    angle of which RoadEstimation::ChooseLine accepts one and refuses the other.  Returns {sign of the pitch:
+    (accepted line, refused line)}."""
+    from hough_reference import THETA
+    from instance_stixels_amd import host
+    found = {}
+    for n in (1, 2, 3, 5, 10, 30, 60, 90, 120, 150, 170, 177, 178, 179):
+        theta = np.float32(n) * THETA
+        took = [host.choose_line([[rho, theta]], *camera, rows) for rho in range(0, rows + D + 1)]
+        for rho in range(rows + D):
+            if (took[rho][0] >= 0) != (took[rho + 1][0] >= 0):
+                inside, outside = (rho, rho + 1) if took[rho][0] >= 0 else (rho + 1, rho)
+                sign = 1 if took[inside][1][1] > 0 else -1
+                found.setdefault(sign, ([inside, theta], [outside, theta]))
+    return found
+
+
+def test_road_line_choice_on_injected_lists():
+    """ComputeHough's loop and ComputeCameraProperties (RoadEstimation.cu:136-193) against
+    RoadEstimation::ChooseLine on hand-made line lists inside the domain cv::HoughLines can produce: rho integral
+    (numrho is odd at resolution 1) and theta = n * THETA.  Non-integral rho is left out on purpose: the
+    reference takes `abs` of the float rho unqualified, and which overload that names depends on the headers in
+    sight -- the integer one truncates; on integral rho both agree, so only there is the reference's result
+    defined for our purposes."""
+    from hough_reference import THETA
+    from instance_stixels_amd import host
+    from test_road_batch_gpu import _batch, _bits
+    rows, cols, D = 256, 512, 64
+    frame = _batch(rows, cols, D, 1, seed=9)[0][0]
+
+    def t(n):
+        return np.float32(n) * THETA
+
+    cameras = [(128.0, 0.209313, 2262.52), (200.0, 0.3, 100.0)]    # the second: both edges of the gate in reach
+    ref = reference.RoadEstimation()
+    try:
+        for camera in cameras:
+            ref.Initialize(*camera, rows, cols, D)
+            edges = _edge_lines(camera, rows, D)
+            assert 1 in edges and (camera[2] > 1000 or -1 in edges), edges
+            fail = [[37, t(0)], [0, t(0)], edges[1][1]]          # horizon inf, NaN, pitch past +50 degrees
+            assert all(host.choose_line([l], *camera, rows)[0] == -1 for l in fail)
+            lists = {
+                "n = 0, horizon inf": [[37, t(0)]],
+                "n = 0, rho 0, horizon NaN": [[0, t(0)]],
+                "n = 90": [[100, t(90)]],
+                "negative rho": [[-150, t(100)], [150, t(100)]],
+                "negative rho at n = 170": [[-20, t(170)]],
+                "three refused, then one": fail + [[120, t(80)], [100, t(90)]],
+                "none passes": fail,
+                "empty": np.zeros((0, 2), np.float32),
+            }
+            for sign, (inside, outside) in edges.items():
+                lists[f"pitch gate {sign:+d}: outside, inside"] = [outside, inside]
+                lists[f"pitch gate {sign:+d}: outside alone"] = [outside]
+            accepted = 0
+            for what, lines in lists.items():
+                lines = np.asarray(lines, np.float32).reshape(-1, 2)
+                k, road = host.choose_line(lines, *camera, rows)
+                reference.set_hough_lines(lines)
+                assert ref.Compute(frame) == (k >= 0), what
+                if k < 0:
+                    continue
+                accepted += 1
+                want = np.array([abs(lines[k, 0]), lines[k, 1]], np.float32)     # the same accepted index
+                assert np.array_equal(_bits(ref.accepted_line), _bits(want)), what
+                assert not any(abs(l[0]) == want[0] and l[1] == want[1] for l in lines[:k]), what
+                assert road[0] == ref.horizon_point, what
+                assert np.array_equal(_bits(road[1:]), _bits([ref.pitch, ref.camera_height, ref.slope])), what
+            assert accepted >= 5
+            k = host.choose_line(lists["three refused, then one"], *camera, rows)[0]
+            assert k == 3
+    finally:
+        ref.close()
+
+
 def test_driver_refuses_inputs_outside_the_domain():
     """The host checks of ref_driver.hip refuse before any launch: the reference's device
     asserts are compiled out, so nothing else stands between these inputs and a launch."""

@@ -11,7 +11,7 @@ from instance_stixels_amd import core, host
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROAD_CORE = ["is_road_ctx_create", "is_road_ctx_destroy", "is_road_ctx_device", "is_road_ctx_binary",
              "is_road_vdisparity_batch", "is_road_hough_batch"]
-ROAD_HOST = ["ire_compute_batch", "ire_set_batch_limits", "ire_batch_fallbacks"]
+ROAD_HOST = ["ire_compute_batch", "ire_set_batch_limits", "ire_batch_fallbacks", "ire_choose_line"]
 
 
 def test_road_batch_symbols_are_declared_exported_and_bound():

@@ -240,3 +240,76 @@ def test_compute_batch_on_a_set_device_restores_the_current_device():
         assert torch.cuda.current_device() == other
     finally:
         torch.cuda.set_device(0)
+
+
+# Frames of _batch(rows, cols, D, 8, seed=rows + D) whose deciding line stands alone: the first line of the float64
+# reference's list that passes the pitch gate is a certain peak and its lo exceeds hi of every other possible peak
+# that passes the gate (so every list inside the bounds leads to it).  The others are the all-zero frame (1), the
+# sky-only frame (4: one column of pixels, refused by the gate).  STRICT: the frames where that line outvotes every
+# other possible peak, gated or not (in the larger shapes the sky column's line comes first and is refused).
+DECIDED = (0, 2, 3, 5, 6, 7)
+STRICT = {256: (0, 2, 3, 5, 6, 7), 1024: (2,), 2048: ()}
+
+
+@pytest.mark.parametrize("shape", [(256, 512, 64), (1024, 2048, 128), (2048, 4096, 256)])
+def test_device_hough_against_the_float64_reference(shape):
+    """k_road_hough / k_road_sort against tests/hough_reference.py, a witness that shares nothing with the host
+    transform they are otherwise compared with: lines and votes of 8 frames inside the reference's bounds, and
+    the road parameters of the deciding line where the reference says it stands alone."""
+    import torch
+    from hough_reference import Hough
+    rows, cols, D = shape
+    n, max_lines, cap = 8, 4096, 8192
+    disp, cases = _batch(rows, cols, D, n, seed=rows + D)
+    cfg = cases[0]["cfg"]
+    camera = (cfg.camera_center_y * rows / 1024, cfg.baseline, cfg.focal)
+    dev = torch.device("cuda", 0)
+    d = torch.from_numpy(disp).to(dev)
+    bn = torch.full((n, rows, D), 7, dtype=torch.uint8, device=dev)
+    lines = torch.full((n, max_lines, 2), float("nan"), dtype=torch.float32, device=dev)
+    votes = torch.zeros((n, max_lines), dtype=torch.int32, device=dev)
+    total = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    over = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    L = core.lib()
+    ctx = ctypes.c_void_p()
+    assert L.is_road_ctx_create(ctypes.byref(ctx), rows, cols, D, n, -1) == 0, L.is_last_error()
+    try:
+        assert L.is_road_vdisparity_batch(ctx, d.data_ptr(), n, ctypes.c_float(THR), None, None, bn.data_ptr(),
+                                          None) == 0, L.is_last_error()
+        assert L.is_road_hough_batch(ctx, n, HOUGH_THR, max_lines, cap, lines.data_ptr(), votes.data_ptr(),
+                                     total.data_ptr(), over.data_ptr(), None) == 0, L.is_last_error()
+        torch.cuda.synchronize()
+    finally:
+        L.is_road_ctx_destroy(ctx)
+    bn, lines, votes, total, over = (t.cpu().numpy() for t in (bn, lines, votes, total, over))
+    decided, strict = [], []
+    for i in range(n):
+        assert np.array_equal(bn[i], _vdisparity_np(disp[i], D, THR)[1]), i
+        h = Hough(bn[i], threshold=HOUGH_THR)
+        certain, possible = int(h.certain_peaks().sum()), int(h.possible_peaks().sum())
+        print(f"{shape} frame {i}: points {h.n_points} ambiguous {h.n_ambiguous} certain {certain} "
+              f"possible {possible} device {total[i]}")
+        assert possible <= min(max_lines, cap) and not over[i], i
+        assert certain <= total[i] <= possible, i
+        got = lines[i, :total[i]]
+        h.check_lines(got, votes[i, :total[i]])
+        # the line that decides the road
+        want, wn, wr, _ = h.lines()
+        k, road = host.choose_line(want, *camera, rows)
+        if k < 0:
+            assert i not in DECIDED, i
+            continue
+        pn, pr = np.nonzero(h.possible_peaks())
+        gated = np.zeros((h.numangle, h.numrho), bool)
+        for a, c, l in zip(pn, pr, h.line(pn, pr)):
+            gated[a, c] = host.choose_line(l, *camera, rows)[0] == 0
+        if h.dominant(wn[k], wr[k]):
+            strict.append(i)
+        if h.dominant(wn[k], wr[k], among=gated):
+            decided.append(i)
+            k_got, road_got = host.choose_line(got, *camera, rows)
+            assert k_got >= 0 and np.array_equal(_bits(got[k_got]), _bits(want[k])), i
+            assert road_got[0] == road[0] and np.array_equal(_bits(road_got[1:]), _bits(road[1:])), i
+            if i in strict:
+                assert k_got == 0, i
+    assert tuple(decided) == DECIDED and tuple(strict) == STRICT[rows], (decided, strict)
