@@ -99,6 +99,9 @@ int main(int argc, char** argv) {
            vhor_img, road.GetSlope(), alpha);
     printf("%d stixels, %zu instance candidates; it took an average of %.3f milliseconds, %.1f fps\n",
            n_stixels, mapping.size(), total_ms / (frames - 1), 1000.0 * (frames - 1) / total_ms);
+    /* the same frame per instance instead of per stixel, reduced on the device */
+    const Stixels::InstanceObjectsView objects = stixels.InstanceObjectsBatchView(1);
+    printf("%d instance objects with %d contour points\n", objects.n_objects, objects.n_points);
     stixels.Finish();
     road.Finish();
     return 0;

@@ -195,6 +195,34 @@ public:
      * form (class*1000 + k, *_instanceTrainIds.png).  Throws std::invalid_argument on a NaN fraction or an id outside
      * [0, 2147482]. */
     void SetGTAssignmentParameters(double min_fraction, const int* label_ids8, bool gt_is_train_ids);
+    /* f9 (an addition): the per-INSTANCE form of frames 0 .. n_images-1 of the LAST Compute() or ComputeBatch(), as
+     * is_instance_objects (instance_stixels_core.h) defines every field: one is_instance_object per (frame, class,
+     * label) that has a stixel, ascending, and per object one is_contour_point per stixel column it touches -- the
+     * depth-closest stixel of the instance in that column -- at points[first_point .. first_point + n_columns).  The
+     * instance ids are those the three consumers above read: the cluster labels, or the ground-truth vote after
+     * AssignInstancesGTBatch; after a call without instances the batch has no objects.  A few kilobytes per frame
+     * where WorldBatch moves megabytes.  Built on the device; the totals, the per-frame counts and the records reach
+     * pinned memory behind ONE synchronisation (a batch beyond the capacities is repeated once with its true totals,
+     * and the object keeps the larger buffers).  Throws std::invalid_argument under RenderBatch's rules. */
+    struct InstanceObjects {
+        std::vector<int32_t> frame_objects, frame_points; /* [n_images] each */
+        std::vector<is_instance_object> objects;
+        std::vector<is_contour_point> points;
+    };
+    /* The records where the copy left them, in the object's pinned buffer: readable until the next
+     * InstanceObjectsBatch*() or Finish() of this object. */
+    struct InstanceObjectsView {
+        const int32_t* frame_objects; /* [n_images] */
+        const int32_t* frame_points;  /* [n_images] */
+        const is_instance_object* objects;
+        const is_contour_point* points;
+        int32_t n_objects, n_points;
+    };
+    InstanceObjectsView InstanceObjectsBatchView(int n_images, void* stream = nullptr);
+    /* The same copied into a caller's InstanceObjects, whose vectors keep their capacity from call to call. */
+    void InstanceObjectsBatch(int n_images, InstanceObjects& out, void* stream = nullptr);
+    /* Objects per frame the first pass has room for (default 64; [1, 8000]); the points get 8 per object. */
+    void SetInstanceObjectCapacity(int objects_per_frame);
     /* Introspection for tests / bench. */
     const StixelParameters& GetParameters() const { return m_params; }
     const std::vector<float>& GetObjectCostLUT() const { return m_obj_cost_lut; }
@@ -311,6 +339,13 @@ private:
     DeviceArray<is_world_stixel> d_world;
     PinnedArray<int32_t> h_world_totals;
     PinnedArray<is_world_stixel> h_world;
+    /* InstanceObjectsBatch: objects per frame of the first pass; one device block and its pinned mirror, laid out
+     * [2] totals | [max_batch] frame objects | [max_batch] frame points | objects | points (16-byte aligned parts),
+     * so that one copy brings everything; the capacities the block was laid out for */
+    int m_object_capacity = 64;
+    size_t m_objects_cap = 0, m_object_points_cap = 0;
+    DeviceArray<char> d_objects_block;
+    PinnedArray<char> h_objects_block;
     /* every device operation of the object runs on this stream (an ordinary stream: it still
      * synchronises with work the caller queued on the legacy NULL stream, like the reference's
      * default-stream code; on the NULL stream itself the auxiliary streams of the core never

@@ -511,6 +511,95 @@ int is_assign_instances_gt(const is_assign_gt_args* args, void* stream);
 int is_pack_section_labels(const int32_t* d_section_instance, int n_images, int realcols, int max_sections,
                            int capacity, int32_t* d_packed, void* stream);
 
+/* ---- f9: per-instance objects and their contours (is_k_objects.hip) ------------------------------------------------
+ * What the reference's consumers reduce on the host from the per-stixel output: the top-down view
+ * (tools/visualization/clustering_visualization.py:563-792: per instance and column the closest stixel, connected
+ * into a contour, and a mean disparity of the instance) and the per-instance masks (draw_instance_masks :118-142,
+ * the union of the rectangles of all stixels of one instance).  Here as a keyed reduction on the device, per frame
+ * over the key (class, label), with w = cols / realcols (integer division) as in f5 / f6 / f8.
+ *
+ * Members.  A section in front of its column's terminator, whatever its type, is a member of instance (c, l) of its
+ * frame when its semantic_class is c in 11..18 and its d_section_instance value is l with 0 <= l < 1000 -- exactly
+ * the sections f5 / f6 give the instance image value c*1000 + l.  Every other section belongs to no object, and a
+ * NULL map gives zero objects.  (In a column without a terminator, which no compute call leaves, every one of the
+ * max_sections slots counts, as is_render_sections paints them all.)  The image rows of a member are rows-1-vT .. rows-1-vB, clipped to the frame in
+ * 64-bit arithmetic as is_render_sections clips; a member whose clipped rectangle is empty still counts as a stixel
+ * (n_stixels, n_columns, the disparity fields, a contour point), contributes 0 pixels and leaves top / bottom alone.
+ *
+ * One is_instance_object per instance with at least one member, ascending by (frame, class, label):
+ *   n_stixels          its members;  n_columns: the stixel columns that hold one;  col_min, col_max: the first and
+ *                      last of them (image columns col_min*w .. col_max*w + w-1)
+ *   top, bottom        smallest and largest clipped image row, inclusive; top = rows and bottom = -1 when no member
+ *                      has a non-empty rectangle
+ *   pixels             the sum over the members of clipped height * w (int32, wrapping).  For the well-formed columns
+ *                      is_compute leaves this is exactly the area of draw_instance_masks' mask of the instance;
+ *                      hand-built sections that overlap are counted once per SECTION, not once per pixel
+ *   disparity_min/max  over the members whose disparity is not NaN, in the order of the order-preserving integer
+ *                      mapping of fp32 (the fp32 order, with -0 below +0, so the bits do not depend on the order of
+ *                      accumulation); +inf / -inf when every member is NaN
+ *   disparity_q16_sum  the sum over the members of clipped height * llrint((double)d * 65536.0) for d in [0, 32768)
+ *                      (which excludes NaN and the infinities; other d contribute 0), int64, wrapping.  The
+ *                      pixel-weighted mean disparity is sum / (65536.0 * pixels / w)
+ *   first_point        the index of its first contour point in d_points; its points are first_point ..
+ *                      first_point + n_columns - 1
+ * Every field is an integer sum, an integer extreme or an extreme over a total order: the bytes do not depend on the
+ * order in which the device accumulates.
+ *
+ * One is_contour_point per (object, stixel column holding a member), ascending by (object, column): the member of
+ * that column with the LARGEST disparity, i.e. the depth-closest one (z = focal * baseline / d) -- the same integer
+ * order, NaN below everything, ties to the smaller section index.  (The reference's plot picks the closest by
+ * Euclidean distance after a hard-coded Cityscapes filter; a host can recompute the 3-D position of every point from
+ * (column, vB, vT, disparity), see instance_stixels_amd/world.py instance_objects.)  object: the index in d_objects;
+ * section, vB, vT, disparity: of that member, bit for bit; column_pixels: the instance's pixels in that column. */
+typedef struct is_instance_object {
+    int32_t frame, semantic_class, label, n_stixels;
+    int32_t n_columns, first_point, pixels, col_min;
+    int32_t col_max, top, bottom, reserved; /* reserved = 0 */
+    float disparity_min, disparity_max;
+    int64_t disparity_q16_sum;
+} is_instance_object;
+typedef struct is_contour_point {
+    int32_t object, column, section, vB;
+    int32_t vT, column_pixels;
+    float disparity;
+    int32_t reserved; /* 0 */
+} is_contour_point;
+#ifdef __cplusplus
+static_assert(sizeof(is_instance_object) == 64 && sizeof(is_contour_point) == 32, "16-byte chunks");
+#else
+_Static_assert(sizeof(is_instance_object) == 64 && sizeof(is_contour_point) == 32, "16-byte chunks");
+#endif
+
+/* Zero-initialise before setting fields.  All device arrays are on the current device.
+ *   d_sections, d_section_instance, n_images, realcols, max_sections, rows, cols   as in is_render_args; the map
+ *                       holds cluster labels or the ground-truth vote of f8; n_images in [1, 65535], max_sections in
+ *                       [1, 32767] and n_images * realcols * max_sections < 2^31
+ *   object_capacity, point_capacity   records d_objects / d_points hold (>= 0; the array may be NULL when it is 0)
+ *   d_objects, d_points 16-byte aligned (the device writes 16-byte chunks): object r at index r for r <
+ *                       object_capacity, point p at index p for p < point_capacity.  Nothing is written at or beyond
+ *                       a capacity -- the caller sees the overflow in d_totals and repeats, as with is_stixel_world.
+ *                       The two capacities are independent: a point below point_capacity is written even when its
+ *                       object is not
+ *   d_frame_objects, d_frame_points   [n_images] int32: the objects and points of every frame
+ *   d_totals            [2] int32: the TRUE numbers of objects and points of the batch, also beyond the capacities */
+typedef struct is_instance_objects_args {
+    const is_section* d_sections;
+    const int32_t* d_section_instance;
+    int n_images, realcols, max_sections, rows, cols;
+    int object_capacity, point_capacity;
+    is_instance_object* d_objects;
+    is_contour_point* d_points;
+    int32_t* d_frame_objects;
+    int32_t* d_frame_points;
+    int32_t* d_totals;
+} is_instance_objects_args;
+
+/* The objects and contours of n_images frames on `stream`, asynchronously, without a host synchronisation: one memset
+ * and four launches.  The scratch -- per frame 8000 keys x (40 bytes + one bit per stixel column), 33 MB for 64 frames
+ * of 256 columns -- comes from the stream-ordered allocator and goes back to it on `stream`; a NULL map queues three
+ * small memsets only. */
+int is_instance_objects(const is_instance_objects_args* args, void* stream);
+
 /* Thin wrappers over the HIP runtime so that the plain-C++ host class needs no HIP headers
  * (the reference's callers are all .cu files; ours may be plain C++). */
 int is_device_malloc(void** ptr, size_t bytes);

@@ -34,6 +34,7 @@ EXPORTS = [
     "is_instance_overlap", "is_pack_overlap_records",
     "is_stixel_world",
     "is_assign_instances_gt", "is_pack_section_labels",
+    "is_instance_objects",
 ]
 RENDER_MAX_LABELS = 64    # IS_RENDER_MAX_LABELS
 RENDER_MAX_CLASSES = 256  # IS_RENDER_MAX_CLASSES
@@ -102,6 +103,30 @@ class AssignGtArgs(ctypes.Structure):
                 ("gt_is_train_ids", ci), ("d_section_instance", vp), ("d_section_votes", vp)]
 
 
+# is_instance_object: one instance of a frame (is_instance_objects, Stixels::InstanceObjectsBatch), 64 bytes
+OBJECT_DTYPE = np.dtype([
+    ("frame", np.int32), ("semantic_class", np.int32), ("label", np.int32), ("n_stixels", np.int32),
+    ("n_columns", np.int32), ("first_point", np.int32), ("pixels", np.int32), ("col_min", np.int32),
+    ("col_max", np.int32), ("top", np.int32), ("bottom", np.int32), ("reserved", np.int32),
+    ("disparity_min", np.float32), ("disparity_max", np.float32), ("disparity_q16_sum", np.int64),
+])
+# is_contour_point: the depth-closest stixel of an object in one stixel column, 32 bytes
+CONTOUR_DTYPE = np.dtype([
+    ("object", np.int32), ("column", np.int32), ("section", np.int32), ("vB", np.int32),
+    ("vT", np.int32), ("column_pixels", np.int32), ("disparity", np.float32), ("reserved", np.int32),
+])
+assert OBJECT_DTYPE.itemsize == 64 and CONTOUR_DTYPE.itemsize == 32
+
+
+class InstanceObjectsArgs(ctypes.Structure):
+    """is_instance_objects_args: zero-initialised by ctypes; device pointers as ints."""
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    _fields_ = [("d_sections", vp), ("d_section_instance", vp), ("n_images", ci), ("realcols", ci),
+                ("max_sections", ci), ("rows", ci), ("cols", ci), ("object_capacity", ci), ("point_capacity", ci),
+                ("d_objects", vp), ("d_points", vp), ("d_frame_objects", vp), ("d_frame_points", vp),
+                ("d_totals", vp)]
+
+
 class CoreError(RuntimeError):
     pass
 
@@ -157,6 +182,7 @@ def lib():
         L.is_stixel_world.argtypes = [ctypes.POINTER(WorldArgs), vp]
         L.is_assign_instances_gt.argtypes = [ctypes.POINTER(AssignGtArgs), vp]
         L.is_pack_section_labels.argtypes = [vp, ci, ci, ci, ci, vp, vp]
+        L.is_instance_objects.argtypes = [ctypes.POINTER(InstanceObjectsArgs), vp]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
         L.is_get_device.argtypes = [ctypes.POINTER(ci)]
@@ -477,6 +503,13 @@ def pack_section_labels_ptr(d_section_instance, n_images, realcols, max_sections
     _check(lib().is_pack_section_labels(d_section_instance, int(n_images), int(realcols), int(max_sections),
                                         int(capacity), d_packed, ctypes.c_void_p(int(stream))),
            "is_pack_section_labels")
+
+
+def instance_objects_ptr(stream=0, **fields):
+    """is_instance_objects on raw device pointers (ints): fields are those of InstanceObjectsArgs.  Asynchronous on
+    `stream`."""
+    a = InstanceObjectsArgs(**fields)
+    _check(lib().is_instance_objects(ctypes.byref(a), ctypes.c_void_p(int(stream))), "is_instance_objects")
 
 
 def flip_and_pad(cnn_out, rows_power2_segmentation, device=0):

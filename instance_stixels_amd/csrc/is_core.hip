@@ -784,6 +784,29 @@ int is_pack_section_labels(const int32_t* d_section_instance, int n_images, int 
     return IS_OK;
 }
 
+/* ---- f9: per-instance objects and contours (is_k_objects.hip) ---- */
+int is_instance_objects(const is_instance_objects_args* a, void* stream) {
+    if (!a) return fail_arg("null args");
+    if (!a->d_sections) return fail_arg("null sections");
+    if (a->n_images < 1 || a->realcols < 1 || a->rows < 1 || a->cols < a->realcols)
+        return fail_arg("bad shape (n_images >= 1, realcols >= 1, rows >= 1, cols >= realcols)");
+    if (a->n_images > 65535) return fail_arg("n_images outside [1, 65535]");
+    if (a->max_sections < 1 || a->max_sections > 32767) return fail_arg("max_sections outside [1, 32767]");
+    if ((long long)a->n_images * a->realcols * a->max_sections > 0x7fffffffLL)
+        return fail_arg("n_images * realcols * max_sections does not fit 31 bits");
+    if (a->object_capacity < 0 || a->point_capacity < 0) return fail_arg("negative capacity");
+    if (!a->d_frame_objects || !a->d_frame_points || !a->d_totals) return fail_arg("null output");
+    if ((a->object_capacity > 0 && !a->d_objects) || (a->point_capacity > 0 && !a->d_points))
+        return fail_arg("null d_objects or d_points with a capacity");
+    if (((uintptr_t)a->d_sections | (uintptr_t)a->d_objects | (uintptr_t)a->d_points) & 15)
+        return fail_arg("d_sections, d_objects and d_points must be 16-byte aligned");
+    if (((uintptr_t)a->d_section_instance | (uintptr_t)a->d_frame_objects | (uintptr_t)a->d_frame_points |
+         (uintptr_t)a->d_totals) & 3)
+        return fail_arg("d_section_instance, d_frame_objects, d_frame_points and d_totals must be 4-byte aligned");
+    HIP_TRY(isk_launch_instance_objects(a, (hipStream_t)stream));
+    return IS_OK;
+}
+
 static_assert(IS_CNT_N == IS_EVAL_COUNTERS, "is_device.h and instance_stixels_core.h disagree on the counter array");
 
 int is_set_eval_counters(is_ctx* c, int enabled) {

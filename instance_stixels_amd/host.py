@@ -32,9 +32,12 @@ EXPORTS = [
     "ish_render_batch",
     "ish_instance_overlap_batch", "ish_instance_overlap_records", "ish_set_instance_overlap_capacity",
     "ish_world_batch", "ish_world_records", "ish_set_world_capacity",
+    "ish_instance_objects_batch", "ish_instance_objects_records", "ish_set_instance_object_capacity",
     "ish_assign_instances_gt_batch", "ish_assign_instances_gt_quads", "ish_use_cluster_instances", "ish_set_gt_assignment_parameters",
 ]
 WORLD_DTYPE = _core.WORLD_DTYPE  # is_world_stixel, the records of Stixels.WorldBatch
+OBJECT_DTYPE = _core.OBJECT_DTYPE    # is_instance_object, the objects of Stixels.InstanceObjectsBatch
+CONTOUR_DTYPE = _core.CONTOUR_DTYPE  # is_contour_point, its contour points
 
 # Stixels::RoadParameters, what RoadEstimation::ComputeBatch writes per frame
 ROAD_PARAMETERS_DTYPE = np.dtype([("vhor", np.int32), ("camera_tilt", np.float32),
@@ -116,6 +119,9 @@ def lib():
         L.ish_world_batch.argtypes = [vp, ci, vp, vp]
         L.ish_world_records.argtypes = [vp, vp, ctypes.c_int64]
         L.ish_set_world_capacity.argtypes = [vp, ci]
+        L.ish_instance_objects_batch.argtypes = [vp, ci, vp, vp, vp, vp]
+        L.ish_instance_objects_records.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64]
+        L.ish_set_instance_object_capacity.argtypes = [vp, ci]
         L.ish_get_input_disparity_on_device.restype = vp
         L.ish_assign_instances_gt_batch.argtypes = [vp, ci, vp, ctypes.POINTER(ctypes.c_int64), vp]
         L.ish_assign_instances_gt_quads.argtypes = [vp, vp, ctypes.c_int64]
@@ -349,6 +355,31 @@ class Stixels:
         records = out[:total] if out is not None and out.size >= total else np.empty(total, WORLD_DTYPE)
         self._check(lib().ish_world_records(self._h, records.ctypes.data if total else None, total), "WorldBatch")
         return offsets, records
+
+    def InstanceObjectsBatch(self, n, stream=0):
+        """Stixels::InstanceObjectsBatch: the per-instance form of frames 0 .. n-1 of the last Compute() /
+        ComputeBatch(), reduced on the device: (objects, points, frame_objects, frame_points) with objects a numpy
+        array of OBJECT_DTYPE (is_instance_object) ascending by (frame, class, label), points one of CONTOUR_DTYPE
+        (is_contour_point) ascending by (object, column) -- object o owns points[first_point : first_point +
+        n_columns] -- and the objects / points of every frame as int32 [n].  The instance ids are the cluster labels,
+        or the ground-truth vote after AssignInstancesGTBatch.  world.instance_objects turns the two arrays into
+        boxes, mean disparities and 3-D contours."""
+        n = int(n)
+        frame_objects, frame_points = np.zeros(max(n, 0), np.int32), np.zeros(max(n, 0), np.int32)
+        totals = np.zeros(2, np.int32)
+        self._check(lib().ish_instance_objects_batch(self._h, n, frame_objects.ctypes.data, frame_points.ctypes.data,
+                                                     totals.ctypes.data, ctypes.c_void_p(int(stream))),
+                    "InstanceObjectsBatch")
+        objects, points = np.empty(int(totals[0]), OBJECT_DTYPE), np.empty(int(totals[1]), CONTOUR_DTYPE)
+        self._check(lib().ish_instance_objects_records(self._h, objects.ctypes.data, objects.size,
+                                                       points.ctypes.data, points.size), "InstanceObjectsBatch")
+        return objects, points, frame_objects, frame_points
+
+    def SetInstanceObjectCapacity(self, objects_per_frame):
+        """Objects per frame InstanceObjectsBatch's first pass has room for (a batch beyond it is repeated once with
+        its true totals; the object keeps the larger buffers)."""
+        self._check(lib().ish_set_instance_object_capacity(self._h, int(objects_per_frame)),
+                    "SetInstanceObjectCapacity")
 
     def AssignInstancesGTBatch(self, n, d_gt, stream=0, with_mapping=True):
         """Stixels::AssignInstancesGTBatch: the instance id of every stixel of frames 0 .. n-1 of the last Compute() /

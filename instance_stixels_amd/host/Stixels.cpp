@@ -367,6 +367,8 @@ void Stixels::Finish() { /* Stixels.cu:250-283 */
     d_overlap_header.release(); h_overlap_header.release();
     d_world_counts.release(); d_world_offsets.release(); d_world_totals.release(); d_world.release();
     h_world_totals.release(); h_world.release();
+    d_objects_block.release(); h_objects_block.release();
+    m_objects_cap = m_object_points_cap = 0;
     m_world_known_offsets.clear();
     m_render_images = 0;
     m_render_instances = false;
@@ -971,6 +973,94 @@ const is_world_stixel* Stixels::WorldBatchView(int n_images, std::vector<int32_t
     frame_offsets[0] = 0;
     for (int i = 0; i < n_images; i++) frame_offsets[i + 1] = frame_offsets[i] + totals[i];
     return h_world.get();
+}
+
+void Stixels::SetInstanceObjectCapacity(int objects_per_frame) {
+    if (objects_per_frame < 1 || objects_per_frame > IS_INSTANCE_CLASSES * 1000)
+        throw std::invalid_argument("SetInstanceObjectCapacity: objects_per_frame outside [1, 8000].");
+    m_object_capacity = objects_per_frame;
+}
+
+void Stixels::InstanceObjectsBatch(int n_images, InstanceObjects& out, void* stream) {
+    const InstanceObjectsView v = InstanceObjectsBatchView(n_images, stream);
+    out.frame_objects.assign(v.frame_objects, v.frame_objects + n_images);
+    out.frame_points.assign(v.frame_points, v.frame_points + n_images);
+    out.objects.assign(v.objects, v.objects + v.n_objects);
+    out.points.assign(v.points, v.points + v.n_points);
+}
+
+Stixels::InstanceObjectsView Stixels::InstanceObjectsBatchView(int n_images, void* stream) {
+    if (m_render_images == 0)
+        throw std::invalid_argument("InstanceObjectsBatch reduces the Sections of the last Compute() or "
+                                    "ComputeBatch(): there are none.");
+    if (n_images < 1 || n_images > m_render_images)
+        throw std::invalid_argument("InstanceObjectsBatch: n_images outside [1, frames of the last compute call].");
+    const DeviceGuard guard(m_ctx_device);
+    if (stream == nullptr) stream = m_stream;
+    const size_t B = (size_t)m_max_batch;
+    /* [2] totals | [B] frame objects | [B] frame points, padded to 16 bytes | objects | points */
+    const size_t head = (sizeof(int32_t) * (2 + 2 * B) + 15) / 16 * 16;
+    size_t want_objects = std::max(m_objects_cap, (size_t)m_object_capacity * n_images);
+    size_t want_points = std::max(m_object_points_cap, 8 * (size_t)m_object_capacity * n_images);
+    is_instance_objects_args a = {};
+    a.d_sections = (const is_section*)d_stixels;
+    a.d_section_instance = SectionInstanceMap(n_images, stream);
+    a.n_images = n_images;
+    a.realcols = m_realcols;
+    a.max_sections = m_max_sections;
+    a.rows = m_rows;
+    a.cols = m_cols;
+    const int32_t* h = nullptr;
+    for (int pass = 0;; pass++) {
+        if (want_objects > m_objects_cap || want_points > m_object_points_cap || d_objects_block.get() == nullptr) {
+            /* grow: both blocks into locals, the members and the capacities only after both exist */
+            const size_t bytes = head + want_objects * sizeof(is_instance_object) + want_points * sizeof(is_contour_point);
+            DeviceArray<char> d_new;
+            PinnedArray<char> h_new;
+            d_new.reserve(bytes);
+            try {
+                h_new.reserve(bytes);
+            } catch (...) {
+                d_new.release();
+                throw;
+            }
+            d_objects_block = std::move(d_new); /* (a swap: the locals now hold the old blocks) */
+            h_objects_block = std::move(h_new);
+            d_new.release();
+            h_new.release();
+            m_objects_cap = want_objects;
+            m_object_points_cap = want_points;
+        }
+        const size_t used = head + m_objects_cap * sizeof(is_instance_object);
+        char* const d = d_objects_block.get();
+        a.object_capacity = (int)std::min<size_t>(m_objects_cap, 0x7fffffff);
+        a.point_capacity = (int)std::min<size_t>(m_object_points_cap, 0x7fffffff);
+        a.d_totals = (int32_t*)d;
+        a.d_frame_objects = a.d_totals + 2;
+        a.d_frame_points = a.d_frame_objects + B;
+        a.d_objects = (is_instance_object*)(d + head);
+        a.d_points = (is_contour_point*)(d + used);
+        const int rc = is_instance_objects(&a, stream);
+        if (rc == IS_EINVAL) throw std::invalid_argument(std::string("InstanceObjectsBatch: ") + is_last_error());
+        IS_CHECK_RETURN(rc);
+        /* everything behind one synchronisation: the block is small (64 + 8 * 32 bytes per object of capacity) */
+        IS_CHECK_RETURN(is_memcpy_d2h(h_objects_block.get(), d, used + m_object_points_cap * sizeof(is_contour_point),
+                                      stream));
+        IS_CHECK_RETURN(is_stream_synchronize(stream));
+        h = (const int32_t*)h_objects_block.get();
+        if ((size_t)h[0] <= m_objects_cap && (size_t)h[1] <= m_object_points_cap) break;
+        if (pass > 0) throw std::runtime_error("InstanceObjectsBatch: the totals changed between two passes.");
+        want_objects = std::max(m_objects_cap, (size_t)h[0]); /* overflow: again, with the true totals */
+        want_points = std::max(m_object_points_cap, (size_t)h[1]);
+    }
+    InstanceObjectsView v;
+    v.frame_objects = h + 2;
+    v.frame_points = h + 2 + B;
+    v.objects = (const is_instance_object*)(h_objects_block.get() + head);
+    v.points = (const is_contour_point*)(h_objects_block.get() + head + m_objects_cap * sizeof(is_instance_object));
+    v.n_objects = h[0];
+    v.n_points = h[1];
+    return v;
 }
 
 /* The shard of this rank, then the compacted gather of every rank's Sections on `dst` (the

@@ -350,6 +350,43 @@ int ish_set_world_capacity(void* h, int records_per_frame) {
     return guard([&] { ((Stixels*)h)->SetWorldCapacity(records_per_frame); });
 }
 
+/* InstanceObjectsBatch(): the per-instance objects and contour points of frames 0 .. n-1 of the last Compute() /
+ * ComputeBatch().  frame_objects, frame_points: host [n]; totals: host [2] (objects, points).  The records stay in
+ * the object's pinned buffer (Stixels::InstanceObjectsBatchView) until ish_instance_objects_records copies them into
+ * the caller's arrays (capacities in records, sized from totals).  Both calls from the same thread, nothing of this
+ * object in between. */
+namespace {
+thread_local Stixels::InstanceObjectsView g_objects = {};
+thread_local void* g_objects_owner = nullptr;
+}
+int ish_instance_objects_batch(void* h, int n, int32_t* frame_objects, int32_t* frame_points, int32_t* totals,
+                               void* stream) {
+    return guard([&] {
+        g_objects_owner = nullptr;
+        g_objects = ((Stixels*)h)->InstanceObjectsBatchView(n, stream);
+        std::memcpy(frame_objects, g_objects.frame_objects, n * sizeof(int32_t));
+        std::memcpy(frame_points, g_objects.frame_points, n * sizeof(int32_t));
+        totals[0] = g_objects.n_objects;
+        totals[1] = g_objects.n_points;
+        g_objects_owner = h;
+    });
+}
+int ish_instance_objects_records(void* h, is_instance_object* objects, int64_t cap_objects, is_contour_point* points,
+                                 int64_t cap_points) {
+    return guard([&] {
+        if (h != g_objects_owner || g_objects.n_objects > cap_objects || g_objects.n_points > cap_points)
+            throw std::invalid_argument("ish_instance_objects_records: no records of this object, or cap too small.");
+        if (g_objects.n_objects)
+            std::memcpy(objects, g_objects.objects, (size_t)g_objects.n_objects * sizeof(is_instance_object));
+        if (g_objects.n_points)
+            std::memcpy(points, g_objects.points, (size_t)g_objects.n_points * sizeof(is_contour_point));
+        g_objects_owner = nullptr;
+    });
+}
+int ish_set_instance_object_capacity(void* h, int objects_per_frame) {
+    return guard([&] { ((Stixels*)h)->SetInstanceObjectCapacity(objects_per_frame); });
+}
+
 /* AssignInstancesGTBatch(): the ground-truth vote over frames 0 .. n-1 of the last Compute() / ComputeBatch(); from
  * then on RenderBatch / InstanceOverlapBatch / WorldBatch read its map.  n_quads (optional): the number of labelled
  * sections; their (frame, column, section, label) quads stay with the calling thread until ish_assign_instances_gt_quads

@@ -9,7 +9,7 @@ reference's `compute3d`, so that every array has the reference's bits.
 import numpy as np
 
 from .config import GROUND, OBJECT
-from .core import WORLD_DTYPE  # noqa: F401  (the dtype of `records`)
+from .core import CONTOUR_DTYPE, OBJECT_DTYPE, WORLD_DTYPE  # noqa: F401  (the dtypes of the record arrays)
 
 FIRST_INSTANCE_CLASS = 11  # IS_FIRST_INSTANCE_CLASS: an object stixel of class >= 11 is an instance candidate
 
@@ -84,3 +84,55 @@ def pointcloud(records, image_shape, groundplane, camera_parameters, realcols):
             "ground_semantics": records["semantic_class"][gnd].astype(np.int64),
             "object_semantics": records["semantic_class"][obj].astype(np.int64),
             "instances": instance_ids(records[obj])[candidate]}
+
+
+def instance_objects(objects, points, image_shape, realcols, camera_parameters):
+    """The per-instance view of a batch from the two arrays of `host.Stixels.InstanceObjectsBatch`: objects
+    (OBJECT_DTYPE) and points (CONTOUR_DTYPE); image_shape: (rows, cols); realcols: the stixel columns of a frame.
+    Returns a dictionary, one entry per object in the arrays' order:
+      mean_disparity [n] float64: the pixel-weighted mean disparity, disparity_q16_sum / (65536 * pixels / w) with
+                     w = cols // realcols (NaN for an object without pixels);
+      box [n][4] int64: (left, top, right, bottom) in image pixels, inclusive -- col_min * w, top, col_max * w + w - 1,
+                     bottom; an object without pixels has top = rows and bottom = -1;
+      contour_offsets [n + 1]: object o owns contour[contour_offsets[o]:contour_offsets[o + 1]] (its first_point and
+                     n_columns), ascending by stixel column;
+      contour [m][3] float64: per contour point the image point the reference's pointcloud() gives that stixel
+                     (mean x, mean y, disparity); contour3d [m][3]: the same through compute3d, in metres;
+      closest_distance [n] float64: the smallest Euclidean distance sqrt(x^2 + y^2 + z^2) of the object's contour
+                     points, the measure the reference's top-down view ranks stixels by.
+    A contour point is the DEPTH-closest stixel of the object in its column (the largest disparity).  The reference's
+    plot instead takes the Euclidean-closest stixel of the column after dropping stixels more than 3 m off the
+    instance's median depth; a caller that wants that choice applies it to the per-stixel records of WorldBatch --
+    the few contour points here are the cheap form.  Raises ValueError where compute3d raises: a zero disparity
+    among the contour points, or camera_parameters None."""
+    objects, points = np.asarray(objects), np.asarray(points)
+    rows, cols = int(image_shape[0]), int(image_shape[1])
+    if int(realcols) < 1 or (objects.size and int(objects["col_max"].max()) >= int(realcols)):
+        raise ValueError("instance_objects: realcols does not hold the objects' columns")
+    first = objects["first_point"].astype(np.int64)
+    count = objects["n_columns"].astype(np.int64)
+    if objects.size and (first[0] != 0 or np.any(first[1:] != first[:-1] + count[:-1])
+                         or first[-1] + count[-1] != len(points)):
+        raise ValueError("instance_objects: the points are not those of the objects")
+    width = cols // int(realcols)
+    pixels = objects["pixels"].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean_disparity = np.where(pixels > 0, objects["disparity_q16_sum"].astype(np.float64)
+                                  / (65536.0 * pixels / width), np.nan)
+    box = np.stack([objects["col_min"].astype(np.int64) * width, objects["top"].astype(np.int64),
+                    objects["col_max"].astype(np.int64) * width + width - 1, objects["bottom"].astype(np.int64)],
+                   axis=1).reshape(-1, 4)
+    left = points["column"].astype(np.int64) * width
+    right = left + width - 1
+    top = rows - points["vT"].astype(np.int64) - 1
+    bottom = rows - points["vB"].astype(np.int64) - 1
+    contour = np.empty((len(points), 3))
+    contour[:, 0] = 0.5 * (left + right + 1)
+    contour[:, 1] = 0.5 * (top + bottom)
+    contour[:, 2] = points["disparity"]
+    contour3d = compute3d(contour, camera_parameters)
+    distance = np.sqrt((contour3d ** 2).sum(axis=1))
+    offsets = np.concatenate([[0], np.cumsum(count)]).astype(np.int64)
+    closest = np.array([distance[offsets[o]:offsets[o + 1]].min() for o in range(len(objects))], np.float64)
+    return {"mean_disparity": mean_disparity, "box": box, "contour_offsets": offsets, "contour": contour,
+            "contour3d": contour3d, "closest_distance": closest}
