@@ -189,7 +189,9 @@ int is_cluster_instances(is_ctx* ctx, const is_instance_buffers* instances, void
  *   d_offsets   [n_columns + 1]  exclusive prefix of the counts; d_offsets[n_columns] = total
  *   d_packed    [>= total]       the sections in (image, column, section) order
  * is_unpack_sections is the inverse (it recomputes d_offsets from d_counts and writes the
- * terminators); entries behind a terminator are unspecified on both sides. */
+ * terminators); entries behind a terminator are unspecified on both sides.  The d_counts given to
+ * is_unpack_sections must be those is_pack_sections produced (0 <= count < max_sections, d_packed
+ * holding their sum): other counts give offsets outside d_packed. */
 int is_pack_sections(const is_section* d_sections, int n_columns, int max_sections,
                      int32_t* d_counts, int32_t* d_offsets, is_section* d_packed, void* stream);
 int is_unpack_sections(const int32_t* d_counts, int32_t* d_offsets, const is_section* d_packed,

@@ -140,9 +140,13 @@ __global__ __launch_bounds__(256) void k_vdisp_histogram(const float* __restrict
     const float* src = disparity + (size_t)row * cols;
     for (int j = threadIdx.x; j < cols; j += blockDim.x) {
         const float d = src[j];
-        if (d != 0) { /* RoadEstimationKernels.cu:33-37 */
-            const int col = (int)d;
-            if (col >= 0 && col < max_dis) atomicAdd(&bins[col], 1); /* guard: reference is unchecked */
+        if (d != 0) {
+            /* RoadEstimationKernels.cu:33-37: the bin is (int)d, truncation toward zero.  NaN goes to bin 0,
+             * stated here and not left to the conversion: the reference's float -> int of NaN gives 0 on its
+             * GPU, in C++ (int)NaN is undefined.  The bin guard (the reference is unchecked) is the float
+             * range (-1, max_dis), so +-inf and |d| >= 2^31 are never converted and fall in no bin. */
+            if (d != d) atomicAdd(&bins[0], 1);
+            else if (d > -1.0f && d < (float)max_dis) atomicAdd(&bins[(int)d], 1);
         }
     }
     __syncthreads();

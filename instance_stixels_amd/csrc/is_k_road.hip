@@ -29,9 +29,9 @@ __global__ __launch_bounds__(256) void k_road_histogram(const float* __restrict_
     const float* src = disparity + ((size_t)f * rows + row) * cols;
     for (int j = threadIdx.x; j < cols; j += blockDim.x) {
         const float d = src[j];
-        if (d != 0) {
-            const int col = (int)d;
-            if (col >= 0 && col < max_dis) atomicAdd(&bins[col], 1);
+        if (d != 0) { /* RoadEstimationKernels.cu:33-37; NaN -> bin 0 explicitly, as k_vdisp_histogram */
+            if (d != d) atomicAdd(&bins[0], 1);
+            else if (d > -1.0f && d < (float)max_dis) atomicAdd(&bins[(int)d], 1);
         }
     }
     __syncthreads();

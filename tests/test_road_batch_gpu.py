@@ -6,6 +6,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import frontend_reference
 import helpers
 from instance_stixels_amd import core, host
 from oracle import oracle
@@ -61,14 +62,9 @@ def _batch(rows, cols, D, n, seed):
 
 def _vdisparity_np(d, D, thr):
     """numpy twin of is_road_vdisparity for frames with bins outside [0, D) too (the oracle mirrors the
-    reference, which does not check them)."""
-    col = d.astype(np.int32)
-    keep = (d != 0) & (col >= 0) & (col < D)
-    r = np.nonzero(keep)[0]
-    v = np.bincount(r * D + col[keep], minlength=d.shape[0] * D).astype(np.int32).reshape(d.shape[0], D)
-    m = int(v.max())
-    b = np.where(v.astype(np.float32) > np.float32(m) * np.float32(thr), 255, 0).astype(np.uint8)
-    return v, b, m
+    reference, which does not check them): the restatement of tests/frontend_reference.py, whose bins are
+    stated rule by rule (tests/test_vdisparity_edges_gpu.py feeds it NaN, +-inf and values beyond int32)."""
+    return frontend_reference.vdisparity(d, D, thr)
 
 
 def _oracle_safe(d, D):
