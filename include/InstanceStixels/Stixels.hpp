@@ -26,7 +26,87 @@
 
 constexpr float PIFLOAT = 3.1416f;
 
-class Stixels {
+/* Every DeviceArray / PinnedArray of a Stixels object (its private base: the members keep their plain names).
+ * Stixels::Finish() releases them with release_all(), which stands at the end of the declarations; the static_assert
+ * behind the struct counts the members, so an array added here and not released there does not compile. */
+struct StixelsBuffers {
+    DeviceArray<pixel_t> d_disparity;
+    DeviceArray<pixel_t> d_disparity_big;
+    DeviceArray<int32_t> d_segmentation;
+    DeviceArray<float> d_instance_centerofmass;
+    DeviceArray<int32_t> d_instance_indices;
+    DeviceArray<uint8_t> d_instance_core_candidates;
+    /* (every instance array: one slice per frame of the batch) */
+    DeviceArray<int32_t> d_instance_labels;  /* the reference's d_instance_labels, Stixels.cu:66-68 */
+    DeviceArray<int32_t> d_instance_packed;  /* [1 + 3*classes*realcols*max_sections], see is_instance_buffers */
+    /* pinned host mirrors: Compute() ends with ONE stream synchronisation */
+    PinnedArray<Section> h_stixels;
+    /* One device block: header rows (the per-class candidate counts, d_instances_per_class) in
+     * front of the sections (d_stixels), both aliases into it set by InitializeBatch.  Compute()
+     * fetches the header and the first m_head_sections sections of every column with ONE pitched
+     * copy into h_stixels_head; a column without a terminator among them (rare) makes it fetch the
+     * complete array. */
+    DeviceArray<Section> d_stixels_block;
+    PinnedArray<Section> h_stixels_head;
+    PinnedArray<int32_t> h_instance_head;    /* [max_batch][8 per-class counts] */
+    /* ComputeBatchGather: the packed payload of this rank and, on the destination, the landing buffers
+     * (allocated on first use, grown on demand, released by Finish) */
+    DeviceArray<int32_t> d_pack_counts;
+    DeviceArray<int32_t> d_pack_offsets;
+    DeviceArray<Section> d_pack_sections;
+    DeviceArray<int32_t> d_all_counts;
+    DeviceArray<Section> d_all_packed;
+    /* ComputeBatch: the same packed payload copied to the host in two pinned pieces (offsets, used sections) */
+    PinnedArray<int32_t> h_pack_offsets;
+    PinnedArray<Section> h_pack_sections;
+    PinnedArray<int32_t> h_all_counts; /* ComputeBatchGather on dst: the per-column counts of all ranks */
+    PinnedArray<int32_t> h_instance_packed;
+    /* RenderBatch: the per-section label map and the per-frame results (allocated on first use) */
+    DeviceArray<int32_t> d_section_instance; /* [max_batch][realcols][max_sections] */
+    /* AssignInstancesGTBatch: the ground-truth map of the same shape; the packed (frame, column, section, label)
+     * quads behind their count, device and pinned host */
+    DeviceArray<int32_t> d_section_instance_gt;
+    DeviceArray<int32_t> d_section_instance_gt_packed; /* [4 + 4 * sections of the batch], is_pack_section_labels */
+    PinnedArray<int32_t> h_section_instance_gt;
+    DeviceArray<char> d_render_results;      /* [max_batch] double | [max_batch] int64 | [max_batch] int32 */
+    PinnedArray<char> h_render_results;
+    /* InstanceOverlapBatch: [max_batch][capacity] records, then n_records | overflow per frame, the packed records
+     * (device and pinned host, allocated on first use, grown with the capacity) */
+    DeviceArray<is_overlap_record> d_overlap_records;
+    DeviceArray<is_overlap_record> d_overlap_packed;
+    DeviceArray<int32_t> d_overlap_header;   /* [max_batch] n_records | [max_batch] overflow */
+    PinnedArray<int32_t> h_overlap_header;
+    PinnedArray<is_overlap_record> h_overlap_packed;
+    /* WorldBatch: the per-column counts and offsets, the frame totals and the records (device and pinned host,
+     * allocated on first use, grown on demand) */
+    DeviceArray<int32_t> d_world_counts;   /* [max_batch * realcols] */
+    DeviceArray<int32_t> d_world_offsets;  /* [max_batch * realcols + 1] */
+    DeviceArray<int32_t> d_world_totals;   /* [max_batch] */
+    DeviceArray<is_world_stixel> d_world;
+    PinnedArray<int32_t> h_world_totals;
+    PinnedArray<is_world_stixel> h_world;
+    /* InstanceObjectsBatch: one device block and its pinned mirror, laid out
+     * [2] totals | [max_batch] frame objects | [max_batch] frame points | objects | points (16-byte aligned parts),
+     * so that one copy brings everything */
+    DeviceArray<char> d_objects_block;
+    PinnedArray<char> h_objects_block;
+    void release_all() { /* in the order of the declarations */
+        d_disparity.release(); d_disparity_big.release(); d_segmentation.release(); d_instance_centerofmass.release();
+        d_instance_indices.release(); d_instance_core_candidates.release(); d_instance_labels.release();
+        d_instance_packed.release(); h_stixels.release(); d_stixels_block.release(); h_stixels_head.release();
+        h_instance_head.release(); d_pack_counts.release(); d_pack_offsets.release(); d_pack_sections.release();
+        d_all_counts.release(); d_all_packed.release(); h_pack_offsets.release(); h_pack_sections.release();
+        h_all_counts.release(); h_instance_packed.release(); d_section_instance.release();
+        d_section_instance_gt.release(); d_section_instance_gt_packed.release(); h_section_instance_gt.release();
+        d_render_results.release(); h_render_results.release(); d_overlap_records.release();
+        d_overlap_packed.release(); d_overlap_header.release(); h_overlap_header.release(); h_overlap_packed.release();
+        d_world_counts.release(); d_world_offsets.release(); d_world_totals.release(); d_world.release();
+        h_world_totals.release(); h_world.release(); d_objects_block.release(); h_objects_block.release();
+    }
+};
+static_assert(sizeof(StixelsBuffers) == 40 * sizeof(DeviceArray<char>), "release_all() must release every array");
+
+class Stixels : private StixelsBuffers {
 public:
     Stixels();
     ~Stixels();
@@ -189,7 +269,7 @@ public:
     void AssignInstancesGTBatch(int n_images, const int32_t* d_gt_instance, void* stream = nullptr,
                                 std::vector<InstanceMapping>* mapping = nullptr);
     /* Back to the cluster labels of the last compute call. */
-    void UseClusterInstances() { m_gt_instances = false; }
+    void UseClusterInstances() { m_last.gt_instances = false; }
     /* The vote's parameters (defaults: the reference's): the minimum fraction of the 10 % rule, the labelIds of
      * classes 11..18 (null: Cityscapes 24, 25, 26, 27, 28, 31, 32, 33), and whether the ground truth is in trainId
      * form (class*1000 + k, *_instanceTrainIds.png).  Throws std::invalid_argument on a NaN fraction or an id outside
@@ -256,7 +336,30 @@ private:
      * the ground-truth map while it is active (nothing is launched), else the cluster labels of the last compute call
      * scattered into d_section_instance on `stream`; null after a call without instances. */
     const int32_t* SectionInstanceMap(int n_images, void* stream);
-    bool HaveInstances() const { return m_gt_instances || m_render_instances; }
+    bool HaveInstances() const { return m_last.gt_instances || m_last.cluster_instances; }
+    /* What the last compute call left in d_stixels: the one record that RenderBatch, InstanceOverlapBatch, WorldBatch*,
+     * AssignInstancesGTBatch and InstanceObjectsBatch* consume.  Two writers: RememberBatch (Compute, ComputeBatch) and
+     * ForgetBatch (Finish, and ComputeBatchGather, which reuses d_stixels for its shard). */
+    struct LastBatch {
+        int frames = 0;                 /* 0: nothing to consume */
+        bool cluster_instances = false; /* its cluster labels are in d_instance_labels */
+        bool gt_instances = false;      /* the consumers read the ground-truth map (AssignInstancesGTBatch) */
+        std::vector<float> alpha;       /* [frames] road parameters, library-convention vhor */
+        std::vector<int> vhor;
+        std::vector<int32_t> known_offsets; /* after a ComputeBatch: the sections in front of every frame, else empty */
+    } m_last;
+    void RememberBatch(int frames, bool cluster_instances, const float* alpha, const int* vhor);
+    void ForgetBatch();
+    /* How every consumer opens (a new one starts here): std::invalid_argument unless frames 0 .. n_images-1 of m_last
+     * exist; then the caller's scope runs on the object's device, and a null `stream` becomes the object's own. */
+    struct ConsumerScope;
+    ConsumerScope BeginConsumer(const char* name, const char* verb, int n_images, void*& stream);
+    /* what every consumer's args struct says alike: the Sections of frames first .. first + n_images - 1 and their
+     * geometry (n_images, realcols, max_sections, rows, cols; is_world_args has no cols) */
+    template <class Args> void FillGeometry(Args& a, int n_images, int first = 0) const;
+    void FillGeometry(is_world_args& a, int n_images) const;
+    /* the return code of a consumer's core call: IS_EINVAL is the caller's fault ("<name>: <the core's text>") */
+    static void CheckConsumer(const char* name, int rc);
     GroundModel m_ground; /* per-frame ground model, storage reused between frames */
     /* the road parameters m_ground was computed for: a frame with the same parameters (a fixed
      * camera model, a replayed sequence) reuses it -- 1024 rows of erf / sqrt / log on the host
@@ -266,86 +369,19 @@ private:
 
     /* device (owned between Initialize and Finish, Stixels.cu:53-74, 136-163) */
     is_ctx* m_ctx = nullptr;
-    DeviceArray<pixel_t> d_disparity;
-    DeviceArray<pixel_t> d_disparity_big;
-    DeviceArray<int32_t> d_segmentation;
-    DeviceArray<float> d_instance_centerofmass;
-    DeviceArray<int32_t> d_instance_indices;
-    DeviceArray<uint8_t> d_instance_core_candidates;
-    /* (every instance array: one slice per frame of the batch) */
-    DeviceArray<int32_t> d_instance_labels;  /* the reference's d_instance_labels, Stixels.cu:66-68 */
-    DeviceArray<int32_t> d_instance_packed;  /* [1 + 3*classes*realcols*max_sections], see is_instance_buffers */
-    /* pinned host mirrors: Compute() ends with ONE stream synchronisation */
-    PinnedArray<Section> h_stixels;
-    /* One device block: header rows (the per-class candidate counts, d_instances_per_class) in
-     * front of the sections (d_stixels), both aliases into it set by InitializeBatch.  Compute()
-     * fetches the header and the first m_head_sections sections of every column with ONE pitched
-     * copy into h_stixels_head; a column without a terminator among them (rare) makes it fetch the
-     * complete array. */
-    DeviceArray<Section> d_stixels_block;
-    Section* d_stixels = nullptr;
+    Section* d_stixels = nullptr;             /* (aliases into d_stixels_block) */
     int32_t* d_instances_per_class = nullptr;
-    PinnedArray<Section> h_stixels_head;
     int m_header_rows = 0;
     int m_head_sections = 0;
-    PinnedArray<int32_t> h_instance_head;    /* [max_batch][8 per-class counts] */
-    /* ComputeBatchGather: the packed payload of this rank and, on the destination, the landing buffers
-     * (allocated on first use, grown on demand, released by Finish) */
-    DeviceArray<int32_t> d_pack_counts;
-    DeviceArray<int32_t> d_pack_offsets;
-    DeviceArray<Section> d_pack_sections;
-    DeviceArray<int32_t> d_all_counts;
-    DeviceArray<Section> d_all_packed;
-    /* ComputeBatch: the same packed payload copied to the host in two pinned pieces (offsets, used sections) */
-    PinnedArray<int32_t> h_pack_offsets;
-    PinnedArray<Section> h_pack_sections;
-    PinnedArray<int32_t> h_all_counts; /* ComputeBatchGather on dst: the per-column counts of all ranks */
-    PinnedArray<int32_t> h_instance_packed;
-    /* RenderBatch: what the last Compute() / ComputeBatch() left in d_stixels (0 frames: nothing renderable --
-     * before any compute, and after ComputeBatchGather, which reuses d_stixels for its shard) and whether its
-     * cluster labels are there; the per-section label map and the per-frame results (allocated on first use) */
-    int m_render_images = 0;
-    bool m_render_instances = false;
-    DeviceArray<int32_t> d_section_instance; /* [max_batch][realcols][max_sections] */
-    /* AssignInstancesGTBatch: the ground-truth map of the same shape, whether the consumers read it, and its
-     * parameters; the packed (frame, column, section, label) quads behind their count, device and pinned host */
-    DeviceArray<int32_t> d_section_instance_gt;
-    DeviceArray<int32_t> d_section_instance_gt_packed; /* [4 + 4 * sections of the batch], is_pack_section_labels */
-    bool m_gt_instances = false;
+    /* AssignInstancesGTBatch: the parameters of the vote */
     double m_gt_min_fraction = 0.1;
     int m_gt_label_ids[IS_INSTANCE_CLASSES] = {24, 25, 26, 27, 28, 31, 32, 33};
     bool m_gt_is_train_ids = false;
-    PinnedArray<int32_t> h_section_instance_gt;
-    DeviceArray<char> d_render_results;      /* [max_batch] double | [max_batch] int64 | [max_batch] int32 */
-    PinnedArray<char> h_render_results;
-    /* InstanceOverlapBatch: [max_batch][capacity] records, then n_records | overflow per frame, the packed records
-     * (device and pinned host, allocated on first use, grown with the capacity) */
-    int m_overlap_capacity = 4096;
-    DeviceArray<is_overlap_record> d_overlap_records;
-    DeviceArray<is_overlap_record> d_overlap_packed;
-    DeviceArray<int32_t> d_overlap_header;   /* [max_batch] n_records | [max_batch] overflow */
-    PinnedArray<int32_t> h_overlap_header;
-    PinnedArray<is_overlap_record> h_overlap_packed;
-    /* WorldBatch: the road parameters of the last compute call (library-convention vhor) and, after a
-     * ComputeBatch, the section totals in front of every frame ([n + 1], else empty); the per-column counts and
-     * offsets, the frame totals and the records (device and pinned host, allocated on first use, grown on demand) */
-    std::vector<float> m_world_alpha;
-    std::vector<int> m_world_vhor;
-    std::vector<int32_t> m_world_known_offsets;
-    int m_world_capacity = 0; /* records per frame of SetWorldCapacity; 0: not set */
-    DeviceArray<int32_t> d_world_counts;   /* [max_batch * realcols] */
-    DeviceArray<int32_t> d_world_offsets;  /* [max_batch * realcols + 1] */
-    DeviceArray<int32_t> d_world_totals;   /* [max_batch] */
-    DeviceArray<is_world_stixel> d_world;
-    PinnedArray<int32_t> h_world_totals;
-    PinnedArray<is_world_stixel> h_world;
-    /* InstanceObjectsBatch: objects per frame of the first pass; one device block and its pinned mirror, laid out
-     * [2] totals | [max_batch] frame objects | [max_batch] frame points | objects | points (16-byte aligned parts),
-     * so that one copy brings everything; the capacities the block was laid out for */
+    int m_overlap_capacity = 4096; /* records per frame of InstanceOverlapBatch's first pass */
+    int m_world_capacity = 0;      /* records per frame of SetWorldCapacity; 0: not set */
+    /* InstanceObjectsBatch: objects per frame of the first pass, the capacities d_objects_block was laid out for */
     int m_object_capacity = 64;
     size_t m_objects_cap = 0, m_object_points_cap = 0;
-    DeviceArray<char> d_objects_block;
-    PinnedArray<char> h_objects_block;
     /* every device operation of the object runs on this stream (an ordinary stream: it still
      * synchronises with work the caller queued on the legacy NULL stream, like the reference's
      * default-stream code; on the NULL stream itself the auxiliary streams of the core never

@@ -667,14 +667,27 @@ int is_section_instance_labels(const is_instance_buffers* per_image, int n_image
     return IS_OK;
 }
 
+/* ---- f5 .. f9: what the entry points that read a batch's Sections check alike.  Each calls it where its own sequence
+ * of refusals has always had these checks: of two faults at once, the same one still answers. ---- */
+/* The frame geometry (is_world_args has no cols and checks its own): the shape, then the entry point's own limit on
+ * it (`own`: its message where the limit is broken, else NULL), then max_sections.  NULL: sound. */
+template <class A>
+static const char* geometry_fault(const A* a, const char* own = nullptr) {
+    if (a->n_images < 1 || a->realcols < 1 || a->rows < 1 || a->cols < a->realcols)
+        return "bad shape (n_images >= 1, realcols >= 1, rows >= 1, cols >= realcols)";
+    if (own) return own;
+    if (a->max_sections < 1 || a->max_sections > 32767) return "max_sections outside [1, 32767]";
+    return nullptr;
+}
+/* one of the pointers (a NULL passes) is not a multiple of `bytes`, a power of two */
+template <class... P> static bool misaligned(uintptr_t bytes, P... p) { return ((... | (uintptr_t)p) & (bytes - 1)) != 0; }
+
 int is_render_sections(const is_render_args* a, void* stream) {
     if (!a || !a->d_sections) return fail_arg("null sections");
-    if (a->n_images < 1 || a->realcols < 1 || a->rows < 1 || a->cols < a->realcols)
-        return fail_arg("bad shape (n_images >= 1, realcols >= 1, rows >= 1, cols >= realcols)");
-    if (a->max_sections < 1 || a->max_sections > 32767) return fail_arg("max_sections outside [1, 32767]");
+    if (const char* fault = geometry_fault(a)) return fail_arg(fault);
     if ((a->realcols + 64) / 64 > 65535 || (size_t)a->n_images * ((a->rows + 127) / 128) > 0x7fffffff)
         return fail_arg("batch too large for one launch");
-    if ((uintptr_t)a->d_sections & 15) return fail_arg("d_sections must be 16-byte aligned");
+    if (misaligned(16, a->d_sections)) return fail_arg("d_sections must be 16-byte aligned");
     if (!a->d_confusion != !a->d_gt_label) return fail_arg("d_confusion and d_gt_label go together");
     if (a->d_confusion && (a->n_labels < 1 || a->n_labels > IS_RENDER_MAX_LABELS))
         return fail_arg("n_labels outside [1, IS_RENDER_MAX_LABELS]");
@@ -696,18 +709,16 @@ int is_render_sections(const is_render_args* a, void* stream) {
 int is_instance_overlap(const is_instance_overlap_args* a, void* stream) {
     if (!a || !a->d_sections || !a->d_gt_instance) return fail_arg("null sections or gt");
     if (!a->d_records || !a->d_n_records || !a->d_overflow) return fail_arg("null output");
-    if (a->n_images < 1 || a->realcols < 1 || a->rows < 1 || a->cols < a->realcols)
-        return fail_arg("bad shape (n_images >= 1, realcols >= 1, rows >= 1, cols >= realcols)");
-    if ((long long)a->rows * a->cols > IS_OVERLAP_MAX_CAPACITY) return fail_arg("frame larger than IS_OVERLAP_MAX_CAPACITY pixels");
-    if (a->max_sections < 1 || a->max_sections > 32767) return fail_arg("max_sections outside [1, 32767]");
+    const bool large = (long long)a->rows * a->cols > IS_OVERLAP_MAX_CAPACITY;
+    if (const char* fault = geometry_fault(a, large ? "frame larger than IS_OVERLAP_MAX_CAPACITY pixels" : nullptr))
+        return fail_arg(fault);
     if (a->capacity < 1 || a->capacity > IS_OVERLAP_MAX_CAPACITY) return fail_arg("capacity outside [1, IS_OVERLAP_MAX_CAPACITY]");
     if (a->n_images > 65535 || (a->realcols + 64) / 64 > 65535 || (size_t)a->n_images * ((a->rows + 127) / 128) > 0x7fffffff)
         return fail_arg("batch too large for one launch");
-    if ((uintptr_t)a->d_sections & 15) return fail_arg("d_sections must be 16-byte aligned");
-    if (((uintptr_t)a->d_gt_instance | (uintptr_t)a->d_section_instance | (uintptr_t)a->d_n_records |
-         (uintptr_t)a->d_overflow) & 3)
+    if (misaligned(16, a->d_sections)) return fail_arg("d_sections must be 16-byte aligned");
+    if (misaligned(4, a->d_gt_instance, a->d_section_instance, a->d_n_records, a->d_overflow))
         return fail_arg("d_gt_instance, d_section_instance, d_n_records and d_overflow must be 4-byte aligned");
-    if ((uintptr_t)a->d_records & 7) return fail_arg("d_records must be 8-byte aligned");
+    if (misaligned(8, a->d_records)) return fail_arg("d_records must be 8-byte aligned");
     HIP_TRY(isk_launch_instance_overlap(a, (hipStream_t)stream));
     return IS_OK;
 }
@@ -735,9 +746,8 @@ int is_stixel_world(const is_world_args* a, void* stream) {
     if (!a->d_sections || !a->d_counts || !a->d_offsets || !a->d_frame_totals) return fail_arg("null sections or output");
     if (!a->h_alpha_ground || !a->h_vhor) return fail_arg("null road parameters");
     if (a->capacity > 0 && !a->d_world) return fail_arg("null d_world with a capacity");
-    if (((uintptr_t)a->d_sections | (uintptr_t)a->d_world) & 15) return fail_arg("d_sections and d_world must be 16-byte aligned");
-    if (((uintptr_t)a->d_section_instance | (uintptr_t)a->d_counts | (uintptr_t)a->d_offsets |
-         (uintptr_t)a->d_frame_totals) & 3)
+    if (misaligned(16, a->d_sections, a->d_world)) return fail_arg("d_sections and d_world must be 16-byte aligned");
+    if (misaligned(4, a->d_section_instance, a->d_counts, a->d_offsets, a->d_frame_totals))
         return fail_arg("d_section_instance, d_counts, d_offsets and d_frame_totals must be 4-byte aligned");
     HIP_TRY(isk_launch_world(a, (hipStream_t)stream));
     return IS_OK;
@@ -747,14 +757,12 @@ int is_stixel_world(const is_world_args* a, void* stream) {
 int is_assign_instances_gt(const is_assign_gt_args* a, void* stream) {
     if (!a || !a->d_sections || !a->d_gt_instance) return fail_arg("null sections or gt");
     if (!a->d_section_instance) return fail_arg("null d_section_instance");
-    if (a->n_images < 1 || a->realcols < 1 || a->rows < 1 || a->cols < a->realcols)
-        return fail_arg("bad shape (n_images >= 1, realcols >= 1, rows >= 1, cols >= realcols)");
-    if (a->max_sections < 1 || a->max_sections > 32767) return fail_arg("max_sections outside [1, 32767]");
+    if (const char* fault = geometry_fault(a)) return fail_arg(fault);
     if ((long long)a->rows * (a->cols / a->realcols) > 0x7fffffffLL)
         return fail_arg("rows * (cols / realcols) does not fit 31 bits");
     if ((long long)a->n_images * ((a->realcols + 3) / 4) > 0x7fffffffLL) return fail_arg("batch too large for one launch");
-    if ((uintptr_t)a->d_sections & 15) return fail_arg("d_sections must be 16-byte aligned");
-    if (((uintptr_t)a->d_gt_instance | (uintptr_t)a->d_section_instance | (uintptr_t)a->d_section_votes) & 3)
+    if (misaligned(16, a->d_sections)) return fail_arg("d_sections must be 16-byte aligned");
+    if (misaligned(4, a->d_gt_instance, a->d_section_instance, a->d_section_votes))
         return fail_arg("d_gt_instance, d_section_instance and d_section_votes must be 4-byte aligned");
     if (a->min_fraction != a->min_fraction) return fail_arg("min_fraction is NaN");
     /* Cityscapes labelIds of trainIds 11..18 (cityscapes_instance_loader.py:45) */
@@ -788,20 +796,17 @@ int is_pack_section_labels(const int32_t* d_section_instance, int n_images, int 
 int is_instance_objects(const is_instance_objects_args* a, void* stream) {
     if (!a) return fail_arg("null args");
     if (!a->d_sections) return fail_arg("null sections");
-    if (a->n_images < 1 || a->realcols < 1 || a->rows < 1 || a->cols < a->realcols)
-        return fail_arg("bad shape (n_images >= 1, realcols >= 1, rows >= 1, cols >= realcols)");
-    if (a->n_images > 65535) return fail_arg("n_images outside [1, 65535]");
-    if (a->max_sections < 1 || a->max_sections > 32767) return fail_arg("max_sections outside [1, 32767]");
+    if (const char* fault = geometry_fault(a, a->n_images > 65535 ? "n_images outside [1, 65535]" : nullptr))
+        return fail_arg(fault);
     if ((long long)a->n_images * a->realcols * a->max_sections > 0x7fffffffLL)
         return fail_arg("n_images * realcols * max_sections does not fit 31 bits");
     if (a->object_capacity < 0 || a->point_capacity < 0) return fail_arg("negative capacity");
     if (!a->d_frame_objects || !a->d_frame_points || !a->d_totals) return fail_arg("null output");
     if ((a->object_capacity > 0 && !a->d_objects) || (a->point_capacity > 0 && !a->d_points))
         return fail_arg("null d_objects or d_points with a capacity");
-    if (((uintptr_t)a->d_sections | (uintptr_t)a->d_objects | (uintptr_t)a->d_points) & 15)
+    if (misaligned(16, a->d_sections, a->d_objects, a->d_points))
         return fail_arg("d_sections, d_objects and d_points must be 16-byte aligned");
-    if (((uintptr_t)a->d_section_instance | (uintptr_t)a->d_frame_objects | (uintptr_t)a->d_frame_points |
-         (uintptr_t)a->d_totals) & 3)
+    if (misaligned(4, a->d_section_instance, a->d_frame_objects, a->d_frame_points, a->d_totals))
         return fail_arg("d_section_instance, d_frame_objects, d_frame_points and d_totals must be 4-byte aligned");
     HIP_TRY(isk_launch_instance_objects(a, (hipStream_t)stream));
     return IS_OK;

@@ -353,26 +353,10 @@ void Stixels::InitializeBatch(int max_batch) { /* Stixels.cu:43-248 */
 
 void Stixels::Finish() { /* Stixels.cu:250-283 */
     const DeviceGuard guard(m_ctx_device);
-    d_disparity.release(); d_disparity_big.release(); d_segmentation.release();
-    d_stixels_block.release(); h_stixels.release(); h_stixels_head.release();
+    release_all();
     d_stixels = nullptr; d_instances_per_class = nullptr; /* (aliases into d_stixels_block) */
-    d_instance_centerofmass.release(); d_instance_indices.release(); d_instance_core_candidates.release();
-    d_instance_labels.release(); d_instance_packed.release(); h_instance_head.release(); h_instance_packed.release();
-    d_pack_counts.release(); d_pack_offsets.release(); d_pack_sections.release();
-    h_pack_offsets.release(); h_pack_sections.release();
-    d_all_counts.release(); d_all_packed.release(); h_all_counts.release();
-    d_section_instance.release(); d_render_results.release(); h_render_results.release();
-    d_section_instance_gt.release(); d_section_instance_gt_packed.release(); h_section_instance_gt.release();
-    d_overlap_records.release(); d_overlap_packed.release(); h_overlap_packed.release();
-    d_overlap_header.release(); h_overlap_header.release();
-    d_world_counts.release(); d_world_offsets.release(); d_world_totals.release(); d_world.release();
-    h_world_totals.release(); h_world.release();
-    d_objects_block.release(); h_objects_block.release();
     m_objects_cap = m_object_points_cap = 0;
-    m_world_known_offsets.clear();
-    m_render_images = 0;
-    m_render_instances = false;
-    m_gt_instances = false;
+    ForgetBatch();
     IS_CHECK_RETURN(is_ctx_destroy(m_ctx));
     m_ctx = nullptr;
     IS_CHECK_RETURN(is_stream_destroy(m_stream));
@@ -446,12 +430,7 @@ float Stixels::Compute(const bool pairwise, StixelsData& stixels_data,
                                g.normalization.data(), g.inv_sigma2.data(), &m_vhor,
                                pairwise ? 1 : 0, 1, d_stixels, &ib, nullptr, nullptr,
                                m_stream)); /* :535-590 */
-    m_render_images = 1;
-    m_render_instances = true;
-    m_gt_instances = false;
-    m_world_alpha.assign(1, m_alpha_ground);
-    m_world_vhor.assign(1, m_vhor);
-    m_world_known_offsets.clear();
+    RememberBatch(1, true, &m_alpha_ground, &m_vhor);
     /* results into pinned memory, ONE copy and ONE synchronisation (:600, :629-633): the header
      * row(s) with the per-class counts and the first m_head_sections sections of every column (a
      * column rarely has more: 10-40 on road scenes) */
@@ -576,13 +555,9 @@ void Stixels::ComputeBatch(bool pairwise, int n_images, const pixel_t* d_big,
     IS_CHECK_RETURN(is_compute(m_ctx, d_disparity.get(), d_seg, g.function.data(), g.normalization.data(),
                                g.inv_sigma2.data(), vh.data(), pairwise ? 1 : 0, n_images, d_stixels,
                                instance_stixels ? ibs.data() : nullptr, nullptr, nullptr, stream));
-    m_render_images = n_images;
-    m_render_instances = instance_stixels != nullptr;
-    m_gt_instances = false;
-    m_world_alpha.resize(n_images);
-    for (int i = 0; i < n_images; i++) m_world_alpha[i] = road[i].alpha_ground;
-    m_world_vhor = vh;
-    m_world_known_offsets.clear();
+    std::vector<float> alpha(n_images);
+    for (int i = 0; i < n_images; i++) alpha[i] = road[i].alpha_ground;
+    RememberBatch(n_images, instance_stixels != nullptr, alpha.data(), vh.data());
     /* Results to the host COMPACTED and through pinned memory: a column uses 10-60 of its 200 slots, and the
      * reference's fixed-stride copy (Stixels.cu:629-633: one frame) would move 1.6 MB per frame into pageable
      * vectors.  is_pack_sections leaves per-column offsets + the used sections; two pinned copies (the offsets, then
@@ -598,8 +573,8 @@ void Stixels::ComputeBatch(bool pairwise, int n_images, const pixel_t* d_big,
                                       (size_t)n_images * m_instance_classes * sizeof(int32_t), stream));
     IS_CHECK_RETURN(is_stream_synchronize(stream));
     const size_t total = (size_t)offsets[ncols];
-    m_world_known_offsets.resize(n_images + 1);
-    for (int i = 0; i <= n_images; i++) m_world_known_offsets[i] = offsets[(size_t)i * m_realcols];
+    m_last.known_offsets.resize(n_images + 1);
+    for (int i = 0; i <= n_images; i++) m_last.known_offsets[i] = offsets[(size_t)i * m_realcols];
     if (total > h_pack_sections.capacity()) h_pack_sections.reserve(total + total / 4 + 1024);
     if (total > 0)
         IS_CHECK_RETURN(is_memcpy_d2h(h_pack_sections.get(), d_pack_sections.get(), total * sizeof(Section), stream));
@@ -634,16 +609,58 @@ void Stixels::ComputeBatch(bool pairwise, int n_images, const pixel_t* d_big,
     m_labels_on_host = false;
 }
 
+/* ---------------------------------------------------------------- the last batch and its consumers */
+
+void Stixels::RememberBatch(int frames, bool cluster_instances, const float* alpha, const int* vhor) {
+    m_last.frames = frames;
+    m_last.cluster_instances = cluster_instances;
+    m_last.gt_instances = false;
+    m_last.alpha.assign(alpha, alpha + frames);
+    m_last.vhor.assign(vhor, vhor + frames);
+    m_last.known_offsets.clear();
+}
+
+void Stixels::ForgetBatch() { RememberBatch(0, false, nullptr, nullptr); }
+
+struct Stixels::ConsumerScope { DeviceGuard guard; };
+
+Stixels::ConsumerScope Stixels::BeginConsumer(const char* name, const char* verb, int n_images, void*& stream) {
+    if (m_last.frames == 0)
+        throw std::invalid_argument(std::string(name) + " " + verb +
+                                    " the Sections of the last Compute() or ComputeBatch(): there are none.");
+    if (n_images < 1 || n_images > m_last.frames)
+        throw std::invalid_argument(std::string(name) + ": n_images outside [1, frames of the last compute call].");
+    if (stream == nullptr) stream = m_stream;
+    return ConsumerScope{DeviceGuard(m_ctx_device)};
+}
+
+template <class Args>
+void Stixels::FillGeometry(Args& a, int n_images, int first) const {
+    a.d_sections = (const is_section*)d_stixels + (size_t)first * m_realcols * m_max_sections;
+    a.n_images = n_images;
+    a.realcols = m_realcols;
+    a.max_sections = m_max_sections;
+    a.rows = m_rows;
+    a.cols = m_cols;
+}
+
+void Stixels::FillGeometry(is_world_args& a, int n_images) const {
+    a.d_sections = (const is_section*)d_stixels;
+    a.n_images = n_images;
+    a.realcols = m_realcols;
+    a.max_sections = m_max_sections;
+    a.rows = m_rows;
+}
+
+void Stixels::CheckConsumer(const char* name, int rc) {
+    if (rc == IS_EINVAL) throw std::invalid_argument(std::string(name) + ": " + is_last_error());
+    IS_CHECK_RETURN(rc);
+}
+
 std::vector<Stixels::RenderResult> Stixels::RenderBatch(int n_images, const RenderTargets& t, void* stream) {
-    if (m_render_images == 0)
-        throw std::invalid_argument("RenderBatch renders the Sections of the last Compute() or ComputeBatch(): "
-                                    "there are none.");
-    if (n_images < 1 || n_images > m_render_images)
-        throw std::invalid_argument("RenderBatch: n_images outside [1, frames of the last compute call].");
+    const ConsumerScope scope = BeginConsumer("RenderBatch", "renders", n_images, stream);
     if (t.instance != nullptr && !HaveInstances())
         throw std::invalid_argument("RenderBatch: an instance image needs a compute call with instances.");
-    const DeviceGuard guard(m_ctx_device);
-    if (stream == nullptr) stream = m_stream;
     const size_t B = (size_t)m_max_batch;
     const size_t res_bytes = B * (sizeof(double) + sizeof(int64_t) + sizeof(int32_t));
     d_render_results.reserve(res_bytes);
@@ -652,12 +669,7 @@ std::vector<Stixels::RenderResult> Stixels::RenderBatch(int n_images, const Rend
     int64_t* d_cnt = (int64_t*)(d_render_results.get() + B * sizeof(double));
     int32_t* d_nst = (int32_t*)(d_render_results.get() + B * (sizeof(double) + sizeof(int64_t)));
     is_render_args a = {};
-    a.d_sections = d_stixels;
-    a.n_images = n_images;
-    a.realcols = m_realcols;
-    a.max_sections = m_max_sections;
-    a.rows = m_rows;
-    a.cols = m_cols;
+    FillGeometry(a, n_images);
     a.h_class_to_label = t.class_to_label;
     a.n_classes = t.n_classes;
     a.d_label = t.label;
@@ -675,9 +687,7 @@ std::vector<Stixels::RenderResult> Stixels::RenderBatch(int n_images, const Rend
     }
     a.d_stixel_count = d_nst;
     if (t.instance) a.d_section_instance = SectionInstanceMap(n_images, stream);
-    const int rc = is_render_sections(&a, stream);
-    if (rc == IS_EINVAL) throw std::invalid_argument(std::string("RenderBatch: ") + is_last_error());
-    IS_CHECK_RETURN(rc);
+    CheckConsumer("RenderBatch", is_render_sections(&a, stream));
     IS_CHECK_RETURN(is_memcpy_d2h(h_render_results.get(), d_render_results.get(), res_bytes, stream));
     IS_CHECK_RETURN(is_stream_synchronize(stream));
     const double* h_sum = (const double*)h_render_results.get();
@@ -690,8 +700,8 @@ std::vector<Stixels::RenderResult> Stixels::RenderBatch(int n_images, const Rend
 
 /* The map the three consumers read.  With the ground-truth map active nothing is launched. */
 const int32_t* Stixels::SectionInstanceMap(int n_images, void* stream) {
-    if (m_gt_instances) return d_section_instance_gt.get();
-    if (!m_render_instances) return nullptr;
+    if (m_last.gt_instances) return d_section_instance_gt.get();
+    if (!m_last.cluster_instances) return nullptr;
     d_section_instance.reserve((size_t)m_max_batch * m_realcols * m_max_sections);
     std::vector<is_instance_buffers> ibs;
     for (int i = 0; i < n_images; i++) ibs.push_back(InstanceBuffers(i));
@@ -715,41 +725,28 @@ void Stixels::SetGTAssignmentParameters(double min_fraction, const int* label_id
 /* Replaces assign_instances_gt of the reference tooling (clustering_visualization.py:846-891) for a batch. */
 void Stixels::AssignInstancesGTBatch(int n_images, const int32_t* d_gt, void* stream,
                                      std::vector<InstanceMapping>* mapping) {
-    if (m_render_images == 0)
-        throw std::invalid_argument("AssignInstancesGTBatch labels the Sections of the last Compute() or "
-                                    "ComputeBatch(): there are none.");
-    if (n_images < 1 || n_images > m_render_images)
-        throw std::invalid_argument("AssignInstancesGTBatch: n_images outside [1, frames of the last compute call].");
+    const ConsumerScope scope = BeginConsumer("AssignInstancesGTBatch", "labels", n_images, stream);
     if (d_gt == nullptr) throw std::invalid_argument("AssignInstancesGTBatch: null d_gt_instance.");
-    const DeviceGuard guard(m_ctx_device);
-    if (stream == nullptr) stream = m_stream;
     const size_t cs = (size_t)m_realcols * m_max_sections;
     d_section_instance_gt.reserve((size_t)m_max_batch * cs);
     is_assign_gt_args a = {};
-    a.d_sections = (const is_section*)d_stixels;
+    FillGeometry(a, n_images);
     a.d_gt_instance = d_gt;
-    a.n_images = n_images;
-    a.rows = m_rows;
-    a.cols = m_cols;
-    a.realcols = m_realcols;
-    a.max_sections = m_max_sections;
     /* (a 0 in the C struct selects its default; a negative fraction rejects exactly what 0 rejects: nothing) */
     a.min_fraction = m_gt_min_fraction == 0.0 ? -1.0 : m_gt_min_fraction;
     a.h_label_ids = m_gt_label_ids;
     a.gt_is_train_ids = m_gt_is_train_ids ? 1 : 0;
     a.d_section_instance = d_section_instance_gt.get();
-    const int rc = is_assign_instances_gt(&a, stream);
-    if (rc == IS_EINVAL) throw std::invalid_argument(std::string("AssignInstancesGTBatch: ") + is_last_error());
-    IS_CHECK_RETURN(rc);
-    if (n_images < m_render_images) /* the frames the vote did not cover have no instances */
+    CheckConsumer("AssignInstancesGTBatch", is_assign_instances_gt(&a, stream));
+    if (n_images < m_last.frames) /* the frames the vote did not cover have no instances */
         IS_CHECK_RETURN(is_memset(d_section_instance_gt.get() + n_images * cs, 0xff,
-                                  (size_t)(m_render_images - n_images) * cs * sizeof(int32_t), stream));
-    m_gt_instances = true;
+                                  (size_t)(m_last.frames - n_images) * cs * sizeof(int32_t), stream));
+    m_last.gt_instances = true;
     if (!mapping) return;
     /* the labelled sections as quads behind their count: a label needs a section, so the sections of the batch
      * (counted by ComputeBatch; every slot in front of a terminator after a Compute()) bound the quads */
-    const size_t cap = !m_world_known_offsets.empty() ? (size_t)m_world_known_offsets[n_images]
-                                                      : (size_t)n_images * m_realcols * (m_max_sections - 1);
+    const size_t cap = !m_last.known_offsets.empty() ? (size_t)m_last.known_offsets[n_images]
+                                                     : (size_t)n_images * m_realcols * (m_max_sections - 1);
     const size_t words = 4 + 4 * cap;
     h_section_instance_gt.reserve(words);
     DeviceArray<int32_t>& d_packed = d_section_instance_gt_packed;
@@ -775,16 +772,10 @@ void Stixels::SetInstanceOverlapCapacity(int records) {
 
 std::vector<std::vector<is_overlap_record>> Stixels::InstanceOverlapBatch(int n_images, const int32_t* d_gt,
                                                                           void* stream) {
-    if (m_render_images == 0)
-        throw std::invalid_argument("InstanceOverlapBatch scores the Sections of the last Compute() or ComputeBatch(): "
-                                    "there are none.");
-    if (n_images < 1 || n_images > m_render_images)
-        throw std::invalid_argument("InstanceOverlapBatch: n_images outside [1, frames of the last compute call].");
+    const ConsumerScope scope = BeginConsumer("InstanceOverlapBatch", "scores", n_images, stream);
     if (!HaveInstances())
         throw std::invalid_argument("InstanceOverlapBatch: needs a compute call with instances.");
     if (d_gt == nullptr) throw std::invalid_argument("InstanceOverlapBatch: null d_gt_instance.");
-    const DeviceGuard guard(m_ctx_device);
-    if (stream == nullptr) stream = m_stream;
     const size_t B = (size_t)m_max_batch;
     const size_t cs = (size_t)m_realcols * m_max_sections;
     const size_t cap = (size_t)m_overlap_capacity;
@@ -797,13 +788,8 @@ std::vector<std::vector<is_overlap_record>> Stixels::InstanceOverlapBatch(int n_
     const size_t frame_px = (size_t)m_rows * m_cols;
     auto args = [&](int first, int n, int capacity, is_overlap_record* rec, int32_t* hdr) {
         is_instance_overlap_args a = {};
-        a.d_sections = d_stixels + first * cs;
+        FillGeometry(a, n, first);
         a.d_section_instance = section_instance + first * cs;
-        a.n_images = n;
-        a.realcols = m_realcols;
-        a.max_sections = m_max_sections;
-        a.rows = m_rows;
-        a.cols = m_cols;
         a.d_gt_instance = d_gt + first * frame_px;
         a.capacity = capacity;
         a.d_records = rec;
@@ -814,9 +800,7 @@ std::vector<std::vector<is_overlap_record>> Stixels::InstanceOverlapBatch(int n_
     /* the batch: tables, packed on the device; the per-frame counts first, then the used records */
     const int32_t* header = h_overlap_header.get();
     const is_instance_overlap_args a = args(0, n_images, (int)cap, d_overlap_records.get(), d_overlap_header.get());
-    const int rc = is_instance_overlap(&a, stream);
-    if (rc == IS_EINVAL) throw std::invalid_argument(std::string("InstanceOverlapBatch: ") + is_last_error());
-    IS_CHECK_RETURN(rc);
+    CheckConsumer("InstanceOverlapBatch", is_instance_overlap(&a, stream));
     IS_CHECK_RETURN(is_pack_overlap_records(d_overlap_records.get(), d_overlap_header.get(), n_images, (int)cap,
                                             d_overlap_packed.get(), stream));
     IS_CHECK_RETURN(is_memcpy_d2h(h_overlap_header.get(), d_overlap_header.get(), 2 * n_images * sizeof(int32_t),
@@ -904,15 +888,9 @@ void Stixels::CopyWorldRecords(is_world_stixel* dst, const is_world_stixel* src,
 }
 
 const is_world_stixel* Stixels::WorldBatchView(int n_images, std::vector<int32_t>& frame_offsets, void* stream) {
-    if (m_render_images == 0)
-        throw std::invalid_argument("WorldBatch exports the Sections of the last Compute() or ComputeBatch(): "
-                                    "there are none.");
-    if (n_images < 1 || n_images > m_render_images)
-        throw std::invalid_argument("WorldBatch: n_images outside [1, frames of the last compute call].");
+    const ConsumerScope scope = BeginConsumer("WorldBatch", "exports", n_images, stream);
     if (m_camera_center_x == -1 || m_camera_center_y == -1)
         throw std::invalid_argument("Camera parameters are not set.");
-    const DeviceGuard guard(m_ctx_device);
-    if (stream == nullptr) stream = m_stream;
     const size_t B = (size_t)m_max_batch;
     const size_t frame_max = (size_t)m_realcols * (m_max_sections - 1);
     d_world_counts.reserve(B * m_realcols);
@@ -920,23 +898,19 @@ const is_world_stixel* Stixels::WorldBatchView(int n_images, std::vector<int32_t
     d_world_totals.reserve(B);
     h_world_totals.reserve(B);
     /* the first pass: the exact size where the last call counted its sections, else a capacity per frame */
-    const bool known = m_world_capacity == 0 && !m_world_known_offsets.empty();
-    size_t cap = known ? (size_t)m_world_known_offsets[n_images]
+    const bool known = m_world_capacity == 0 && !m_last.known_offsets.empty();
+    size_t cap = known ? (size_t)m_last.known_offsets[n_images]
                        : std::min((size_t)(m_world_capacity ? m_world_capacity : 4096), frame_max) * n_images;
     is_world_args a = {};
-    a.d_sections = (const is_section*)d_stixels;
+    FillGeometry(a, n_images);
     a.d_section_instance = SectionInstanceMap(n_images, stream);
-    a.n_images = n_images;
-    a.realcols = m_realcols;
-    a.max_sections = m_max_sections;
-    a.rows = m_rows;
     a.column_step = m_column_step;
     a.focal = m_focal;
     a.baseline = m_baseline;
     a.camera_center_x = m_camera_center_x;
     a.camera_center_y = m_camera_center_y;
-    a.h_alpha_ground = m_world_alpha.data();
-    a.h_vhor = m_world_vhor.data();
+    a.h_alpha_ground = m_last.alpha.data();
+    a.h_vhor = m_last.vhor.data();
     a.d_counts = d_world_counts.get();
     a.d_offsets = d_world_offsets.get();
     a.d_frame_totals = d_world_totals.get();
@@ -946,9 +920,7 @@ const is_world_stixel* Stixels::WorldBatchView(int n_images, std::vector<int32_t
         d_world.reserve(cap);
         a.capacity = (int)cap;
         a.d_world = d_world.get();
-        const int rc = is_stixel_world(&a, stream);
-        if (rc == IS_EINVAL) throw std::invalid_argument(std::string("WorldBatch: ") + is_last_error());
-        IS_CHECK_RETURN(rc);
+        CheckConsumer("WorldBatch", is_stixel_world(&a, stream));
         IS_CHECK_RETURN(is_memcpy_d2h(h_world_totals.get(), d_world_totals.get(), n_images * sizeof(int32_t), stream));
         if (known && pass == 0 && cap > 0) { /* the records ride behind the totals: one synchronisation */
             h_world.reserve(cap);
@@ -990,26 +962,15 @@ void Stixels::InstanceObjectsBatch(int n_images, InstanceObjects& out, void* str
 }
 
 Stixels::InstanceObjectsView Stixels::InstanceObjectsBatchView(int n_images, void* stream) {
-    if (m_render_images == 0)
-        throw std::invalid_argument("InstanceObjectsBatch reduces the Sections of the last Compute() or "
-                                    "ComputeBatch(): there are none.");
-    if (n_images < 1 || n_images > m_render_images)
-        throw std::invalid_argument("InstanceObjectsBatch: n_images outside [1, frames of the last compute call].");
-    const DeviceGuard guard(m_ctx_device);
-    if (stream == nullptr) stream = m_stream;
+    const ConsumerScope scope = BeginConsumer("InstanceObjectsBatch", "reduces", n_images, stream);
     const size_t B = (size_t)m_max_batch;
     /* [2] totals | [B] frame objects | [B] frame points, padded to 16 bytes | objects | points */
     const size_t head = (sizeof(int32_t) * (2 + 2 * B) + 15) / 16 * 16;
     size_t want_objects = std::max(m_objects_cap, (size_t)m_object_capacity * n_images);
     size_t want_points = std::max(m_object_points_cap, 8 * (size_t)m_object_capacity * n_images);
     is_instance_objects_args a = {};
-    a.d_sections = (const is_section*)d_stixels;
+    FillGeometry(a, n_images);
     a.d_section_instance = SectionInstanceMap(n_images, stream);
-    a.n_images = n_images;
-    a.realcols = m_realcols;
-    a.max_sections = m_max_sections;
-    a.rows = m_rows;
-    a.cols = m_cols;
     const int32_t* h = nullptr;
     for (int pass = 0;; pass++) {
         if (want_objects > m_objects_cap || want_points > m_object_points_cap || d_objects_block.get() == nullptr) {
@@ -1040,9 +1001,7 @@ Stixels::InstanceObjectsView Stixels::InstanceObjectsBatchView(int n_images, voi
         a.d_frame_points = a.d_frame_objects + B;
         a.d_objects = (is_instance_object*)(d + head);
         a.d_points = (is_contour_point*)(d + used);
-        const int rc = is_instance_objects(&a, stream);
-        if (rc == IS_EINVAL) throw std::invalid_argument(std::string("InstanceObjectsBatch: ") + is_last_error());
-        IS_CHECK_RETURN(rc);
+        CheckConsumer("InstanceObjectsBatch", is_instance_objects(&a, stream));
         /* everything behind one synchronisation: the block is small (64 + 8 * 32 bytes per object of capacity) */
         IS_CHECK_RETURN(is_memcpy_d2h(h_objects_block.get(), d, used + m_object_points_cap * sizeof(is_contour_point),
                                       stream));
@@ -1091,8 +1050,7 @@ void Stixels::ComputeBatchGather(bool pairwise, int n_images, const pixel_t* d_b
     IS_CHECK_RETURN(is_compute(m_ctx, d_disparity.get(), d_seg, g.function.data(), g.normalization.data(),
                                g.inv_sigma2.data(), vh.data(), pairwise ? 1 : 0, n_images, d_stixels, nullptr,
                                nullptr, nullptr, stream));
-    m_render_images = 0; /* (d_stixels now holds this rank's shard; RenderBatch renders Compute / ComputeBatch) */
-    m_gt_instances = false;
+    ForgetBatch(); /* (d_stixels now holds this rank's shard; the consumers read Compute / ComputeBatch) */
 
     /* ---- pack: per-column counts + the used sections (10-40 of the 200 slots of a column) */
     ReservePackBuffers();

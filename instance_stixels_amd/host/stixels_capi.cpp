@@ -31,6 +31,33 @@ int guard(F&& f) {
         return -2;
     }
 }
+/* A result that stays with the calling thread between the call that computed it for object `h` and the one call that
+ * copies it out: set for h, taken once by h if it fits the caller's arrays (else refused, and kept), cleared. */
+template <class T>
+struct Pending {
+    T value{};
+    void* owner = nullptr;
+    void clear() { set(nullptr, T()); }
+    void set(void* h, T v) { value = std::move(v), owner = h; }
+    const T& take(void* h, bool fits, const char* refusal) {
+        if (h != owner || !fits) throw std::invalid_argument(refusal);
+        owner = nullptr;
+        return value;
+    }
+};
+struct WorldRecords { const is_world_stixel* records; int64_t n; };
+thread_local Pending<std::vector<is_overlap_record>> g_overlap;
+thread_local Pending<WorldRecords> g_world;
+thread_local Pending<Stixels::InstanceObjectsView> g_objects;
+thread_local Pending<std::vector<int32_t>> g_gt_quads;
+
+/* road [n][4] = (vhor_image, camera_tilt, camera_height, alpha_ground) */
+std::vector<Stixels::RoadParameters> to_road(const float* road, int n) {
+    std::vector<Stixels::RoadParameters> rp(n);
+    for (int i = 0; i < n; i++)
+        rp[i] = Stixels::RoadParameters{(int)road[4 * i], road[4 * i + 1], road[4 * i + 2], road[4 * i + 3]};
+    return rp;
+}
 }  // namespace
 
 extern "C" {
@@ -177,9 +204,7 @@ int ish_compute_batch(void* h, int pairwise, int n_images, const float* d_big, c
                       int* counts, void* stream) {
     return guard([&] {
         Stixels* s = (Stixels*)h;
-        std::vector<Stixels::RoadParameters> rp(n_images);
-        for (int i = 0; i < n_images; i++)
-            rp[i] = Stixels::RoadParameters{(int)road[4 * i], road[4 * i + 1], road[4 * i + 2], road[4 * i + 3]};
+        const std::vector<Stixels::RoadParameters> rp = to_road(road, n_images);
         std::vector<StixelsData> out;
         std::vector<Stixels::InstanceMapping> maps;
         s->ComputeBatch(pairwise != 0, n_images, d_big, d_seg, rp.data(), out, stream,
@@ -211,12 +236,6 @@ int ish_compute_batch_gather(void* h, int pairwise, int n_images, const float* d
                              int* n_out, void* stream) {
     return guard([&] {
         Stixels* s = (Stixels*)h;
-        auto conv = [](const float* r, int n) {
-            std::vector<Stixels::RoadParameters> rp(n);
-            for (int i = 0; i < n; i++)
-                rp[i] = Stixels::RoadParameters{(int)r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]};
-            return rp;
-        };
         if (road_all) { /* dst: the caller sized road_all / sections_all / vhor_all for n_all frames */
             int rank = 0, nranks = 0;
             if (is_comm_rank(comm, &rank, &nranks) != IS_OK)
@@ -226,8 +245,8 @@ int ish_compute_batch_gather(void* h, int pairwise, int n_images, const float* d
             if (sum != (long)n_all)
                 throw std::invalid_argument("ish_compute_batch_gather: n_all differs from the sum of images_per_rank");
         }
-        const std::vector<Stixels::RoadParameters> rp = conv(road, n_images);
-        const std::vector<Stixels::RoadParameters> ra = road_all ? conv(road_all, n_all)
+        const std::vector<Stixels::RoadParameters> rp = to_road(road, n_images);
+        const std::vector<Stixels::RoadParameters> ra = road_all ? to_road(road_all, n_all)
                                                                  : std::vector<Stixels::RoadParameters>();
         std::vector<StixelsData> out;
         s->ComputeBatchGather(pairwise != 0, n_images, d_big, d_seg, rp.data(), comm, dst, images_per_rank,
@@ -247,9 +266,7 @@ int ish_time_compute_batch(void* h, int pairwise, int n_images, const float* d_b
                            const float* road, int n_iter, int with_instances, double* s_per_call) {
     return guard([&] {
         Stixels* s = (Stixels*)h;
-        std::vector<Stixels::RoadParameters> rp(n_images);
-        for (int i = 0; i < n_images; i++)
-            rp[i] = Stixels::RoadParameters{(int)road[4 * i], road[4 * i + 1], road[4 * i + 2], road[4 * i + 3]};
+        const std::vector<Stixels::RoadParameters> rp = to_road(road, n_images);
         std::vector<StixelsData> out;
         std::vector<Stixels::InstanceMapping> maps;
         s->ComputeBatch(pairwise != 0, n_images, d_big, d_seg, rp.data(), out, nullptr,
@@ -288,30 +305,25 @@ int ish_render_batch(void* h, int n, uint8_t* label, float* disparity, int32_t* 
 /* InstanceOverlapBatch(): the tables of frames 0 .. n-1 of the last Compute() / ComputeBatch() against
  * d_gt_instance.  n_records: host [n].  The records stay with the calling thread until ish_instance_overlap_records
  * copies them out (all frames back to back, in frame order) -- the caller sizes that buffer from n_records. */
-namespace {
-thread_local std::vector<is_overlap_record> g_overlap;
-thread_local void* g_overlap_owner = nullptr;
-}
 int ish_instance_overlap_batch(void* h, int n, const int32_t* d_gt_instance, int64_t* n_records, void* stream) {
     return guard([&] {
         g_overlap.clear();
-        g_overlap_owner = nullptr;
         const std::vector<std::vector<is_overlap_record>> t = ((Stixels*)h)->InstanceOverlapBatch(n, d_gt_instance,
                                                                                                   stream);
+        std::vector<is_overlap_record> all;
         for (int i = 0; i < n; i++) {
             n_records[i] = (int64_t)t[i].size();
-            g_overlap.insert(g_overlap.end(), t[i].begin(), t[i].end());
+            all.insert(all.end(), t[i].begin(), t[i].end());
         }
-        g_overlap_owner = h;
+        g_overlap.set(h, std::move(all));
     });
 }
 int ish_instance_overlap_records(void* h, is_overlap_record* out, int64_t cap) {
     return guard([&] {
-        if (h != g_overlap_owner || (int64_t)g_overlap.size() > cap)
-            throw std::invalid_argument("ish_instance_overlap_records: no tables of this object, or cap too small.");
-        std::memcpy(out, g_overlap.data(), g_overlap.size() * sizeof(is_overlap_record));
-        g_overlap.clear();
-        g_overlap_owner = nullptr;
+        const std::vector<is_overlap_record>& t = g_overlap.take(
+            h, (int64_t)g_overlap.value.size() <= cap,
+            "ish_instance_overlap_records: no tables of this object, or cap too small.");
+        std::memcpy(out, t.data(), t.size() * sizeof(is_overlap_record));
     });
 }
 int ish_set_instance_overlap_capacity(void* h, int records) {
@@ -323,27 +335,20 @@ int ish_set_instance_overlap_capacity(void* h, int records) {
  * them into the caller's array (cap in records, sized from frame_offsets[n]; an array the caller keeps from batch to
  * batch costs no fresh pages): ONE copy on the host.  Both calls from the same thread, nothing of this object in
  * between. */
-namespace {
-thread_local const is_world_stixel* g_world = nullptr;
-thread_local int64_t g_world_n = 0;
-thread_local void* g_world_owner = nullptr;
-}
 int ish_world_batch(void* h, int n, int32_t* frame_offsets, void* stream) {
     return guard([&] {
-        g_world_owner = nullptr;
+        g_world.clear();
         std::vector<int32_t> offsets;
-        g_world = ((Stixels*)h)->WorldBatchView(n, offsets, stream);
+        const is_world_stixel* records = ((Stixels*)h)->WorldBatchView(n, offsets, stream);
         std::memcpy(frame_offsets, offsets.data(), offsets.size() * sizeof(int32_t));
-        g_world_n = offsets[n];
-        g_world_owner = h;
+        g_world.set(h, WorldRecords{records, offsets[n]});
     });
 }
 int ish_world_records(void* h, is_world_stixel* out, int64_t cap) {
     return guard([&] {
-        if (h != g_world_owner || g_world_n > cap)
-            throw std::invalid_argument("ish_world_records: no records of this object, or cap too small.");
-        Stixels::CopyWorldRecords(out, g_world, (size_t)g_world_n);
-        g_world_owner = nullptr;
+        const WorldRecords& w = g_world.take(h, g_world.value.n <= cap,
+                                             "ish_world_records: no records of this object, or cap too small.");
+        Stixels::CopyWorldRecords(out, w.records, (size_t)w.n);
     });
 }
 int ish_set_world_capacity(void* h, int records_per_frame) {
@@ -355,32 +360,26 @@ int ish_set_world_capacity(void* h, int records_per_frame) {
  * the object's pinned buffer (Stixels::InstanceObjectsBatchView) until ish_instance_objects_records copies them into
  * the caller's arrays (capacities in records, sized from totals).  Both calls from the same thread, nothing of this
  * object in between. */
-namespace {
-thread_local Stixels::InstanceObjectsView g_objects = {};
-thread_local void* g_objects_owner = nullptr;
-}
 int ish_instance_objects_batch(void* h, int n, int32_t* frame_objects, int32_t* frame_points, int32_t* totals,
                                void* stream) {
     return guard([&] {
-        g_objects_owner = nullptr;
-        g_objects = ((Stixels*)h)->InstanceObjectsBatchView(n, stream);
-        std::memcpy(frame_objects, g_objects.frame_objects, n * sizeof(int32_t));
-        std::memcpy(frame_points, g_objects.frame_points, n * sizeof(int32_t));
-        totals[0] = g_objects.n_objects;
-        totals[1] = g_objects.n_points;
-        g_objects_owner = h;
+        g_objects.clear();
+        const Stixels::InstanceObjectsView v = ((Stixels*)h)->InstanceObjectsBatchView(n, stream);
+        std::memcpy(frame_objects, v.frame_objects, n * sizeof(int32_t));
+        std::memcpy(frame_points, v.frame_points, n * sizeof(int32_t));
+        totals[0] = v.n_objects;
+        totals[1] = v.n_points;
+        g_objects.set(h, v);
     });
 }
 int ish_instance_objects_records(void* h, is_instance_object* objects, int64_t cap_objects, is_contour_point* points,
                                  int64_t cap_points) {
     return guard([&] {
-        if (h != g_objects_owner || g_objects.n_objects > cap_objects || g_objects.n_points > cap_points)
-            throw std::invalid_argument("ish_instance_objects_records: no records of this object, or cap too small.");
-        if (g_objects.n_objects)
-            std::memcpy(objects, g_objects.objects, (size_t)g_objects.n_objects * sizeof(is_instance_object));
-        if (g_objects.n_points)
-            std::memcpy(points, g_objects.points, (size_t)g_objects.n_points * sizeof(is_contour_point));
-        g_objects_owner = nullptr;
+        const Stixels::InstanceObjectsView& v = g_objects.take(
+            h, g_objects.value.n_objects <= cap_objects && g_objects.value.n_points <= cap_points,
+            "ish_instance_objects_records: no records of this object, or cap too small.");
+        if (v.n_objects) std::memcpy(objects, v.objects, (size_t)v.n_objects * sizeof(is_instance_object));
+        if (v.n_points) std::memcpy(points, v.points, (size_t)v.n_points * sizeof(is_contour_point));
     });
 }
 int ish_set_instance_object_capacity(void* h, int objects_per_frame) {
@@ -391,33 +390,28 @@ int ish_set_instance_object_capacity(void* h, int objects_per_frame) {
  * then on RenderBatch / InstanceOverlapBatch / WorldBatch read its map.  n_quads (optional): the number of labelled
  * sections; their (frame, column, section, label) quads stay with the calling thread until ish_assign_instances_gt_quads
  * copies them out -- the caller sizes that buffer from *n_quads.  Null: no mapping is fetched, the call is asynchronous. */
-namespace {
-thread_local std::vector<int32_t> g_gt_quads;
-thread_local void* g_gt_owner = nullptr;
-}
 int ish_assign_instances_gt_batch(void* h, int n, const int32_t* d_gt_instance, int64_t* n_quads, void* stream) {
     return guard([&] {
         g_gt_quads.clear();
-        g_gt_owner = nullptr;
         std::vector<Stixels::InstanceMapping> maps;
         ((Stixels*)h)->AssignInstancesGTBatch(n, d_gt_instance, stream, n_quads ? &maps : nullptr);
         if (!n_quads) return;
+        std::vector<int32_t> quads;
         for (int i = 0; i < n; i++)
             for (const auto& kv : maps[i]) {
                 const int32_t q[4] = {i, kv.first.first, kv.first.second, kv.second};
-                g_gt_quads.insert(g_gt_quads.end(), q, q + 4);
+                quads.insert(quads.end(), q, q + 4);
             }
-        *n_quads = (int64_t)(g_gt_quads.size() / 4);
-        g_gt_owner = h;
+        *n_quads = (int64_t)(quads.size() / 4);
+        g_gt_quads.set(h, std::move(quads));
     });
 }
 int ish_assign_instances_gt_quads(void* h, int32_t* out, int64_t cap) {
     return guard([&] {
-        if (h != g_gt_owner || (int64_t)(g_gt_quads.size() / 4) > cap)
-            throw std::invalid_argument("ish_assign_instances_gt_quads: no quads of this object, or cap too small.");
-        if (!g_gt_quads.empty()) std::memcpy(out, g_gt_quads.data(), g_gt_quads.size() * sizeof(int32_t));
-        g_gt_quads.clear();
-        g_gt_owner = nullptr;
+        const std::vector<int32_t>& q = g_gt_quads.take(
+            h, (int64_t)(g_gt_quads.value.size() / 4) <= cap,
+            "ish_assign_instances_gt_quads: no quads of this object, or cap too small.");
+        if (!q.empty()) std::memcpy(out, q.data(), q.size() * sizeof(int32_t));
     });
 }
 int ish_use_cluster_instances(void* h) {
