@@ -90,6 +90,11 @@ struct StixelsBuffers {
      * so that one copy brings everything */
     DeviceArray<char> d_objects_block;
     PinnedArray<char> h_objects_block;
+    /* SweepBatch: the Sections of [sets][frames] and one block of their instance arrays, frame after frame (per-class
+     * counts | centres | indices | labels | packed triples | core flags, see Stixels::SweepInstanceBuffers); allocated
+     * on first use, grown on demand */
+    DeviceArray<Section> d_sweep_stixels;
+    DeviceArray<char> d_sweep_instances;
     void release_all() { /* in the order of the declarations */
         d_disparity.release(); d_disparity_big.release(); d_segmentation.release(); d_instance_centerofmass.release();
         d_instance_indices.release(); d_instance_core_candidates.release(); d_instance_labels.release();
@@ -102,9 +107,10 @@ struct StixelsBuffers {
         d_overlap_packed.release(); d_overlap_header.release(); h_overlap_header.release(); h_overlap_packed.release();
         d_world_counts.release(); d_world_offsets.release(); d_world_totals.release(); d_world.release();
         h_world_totals.release(); h_world.release(); d_objects_block.release(); h_objects_block.release();
+        d_sweep_stixels.release(); d_sweep_instances.release();
     }
 };
-static_assert(sizeof(StixelsBuffers) == 40 * sizeof(DeviceArray<char>), "release_all() must release every array");
+static_assert(sizeof(StixelsBuffers) == 42 * sizeof(DeviceArray<char>), "release_all() must release every array");
 
 class Stixels : private StixelsBuffers {
 public:
@@ -303,6 +309,44 @@ public:
     void InstanceObjectsBatch(int n_images, InstanceObjects& out, void* stream = nullptr);
     /* Objects per frame the first pass has room for (default 64; [1, 8000]); the points get 8 per object. */
     void SetInstanceObjectCapacity(int objects_per_frame);
+    /* Parameter sweeps (an addition): what the reference's hyper-parameter search (tools/run_cityscapes.py:566-680)
+     * changes between two runs over the same frames -- the four weights in SetWeightParameters' user-facing form (the
+     * class applies its instance / segmentation rule) and the three clustering parameters. */
+    struct SweepSet {
+        float prior_weight, disparity_weight, segmentation_weight, instance_weight;
+        float eps;
+        int min_pts, size_filter;
+    };
+    /* the set as the core takes it: SetWeightParameters' rule for the instance weight */
+    static is_sweep_set CoreSweepSet(const SweepSet& set);
+    /* ComputeBatch for every set of `sets` on the same inputs in one call (is_compute_sweep): the column join and the
+     * ground models run once, the weight-independent half of the DP once, the rest per set.  The results stay on the
+     * device, in arrays the object allocates on first use and grows by the Sections and the instance arrays of
+     * sets x n_images frames (never by DP scratch); nothing is copied to the host.  Afterwards set 0 is "the last batch"
+     * of the consumers (RenderBatch, InstanceOverlapBatch, WorldBatch*, AssignInstancesGTBatch, InstanceObjectsBatch*);
+     * SelectSweepSet chooses another.  The object's own parameters are unchanged.  Throws std::invalid_argument, before
+     * anything is queued, when n_images is outside [1, max_batch] or `sets` is empty. */
+    void SweepBatch(bool pairwise, int n_images, const pixel_t* d_disparity_big, const int32_t* d_segmentation,
+                    const RoadParameters* road, const std::vector<SweepSet>& sets, void* stream = nullptr,
+                    bool with_instances = true);
+    /* Makes set k of the last SweepBatch what the consumers read (no copy).  Throws std::invalid_argument when k is
+     * outside the sets of that call, or when the last compute call was not a sweep (Compute, ComputeBatch,
+     * ComputeBatchGather and Finish end it). */
+    void SelectSweepSet(int k);
+    /* One set of the last SweepBatch to the host, as ComputeBatch delivers a batch (packed on the device, through
+     * pinned memory); `instance_stixels` needs a sweep with instances.  Throws like SelectSweepSet. */
+    void SweepSections(int k, std::vector<StixelsData>& out, std::vector<InstanceMapping>* instance_stixels = nullptr);
+    /* The clustering of the last compute call -- or of the selected set of a sweep -- again with other parameters,
+     * without its DP (is_recluster): the labels (and `instance_stixels`, when given) are afterwards those of a compute
+     * call made with these three parameters, the Sections untouched.  Ends an active ground-truth map, as
+     * UseClusterInstances does.  Throws std::invalid_argument before any compute call and after one without
+     * instances. */
+    void ReclusterBatch(float eps, int min_pts, int size_filter, std::vector<InstanceMapping>* instance_stixels = nullptr,
+                        void* stream = nullptr);
+    /* frames of the last compute call the consumers can read (0: none) */
+    int LastFrames() const { return m_last.frames; }
+    /* sets of the last SweepBatch while it is what the consumers read (0: the last compute call was not a sweep) */
+    int SweepSets() const { return m_sweep.sets; }
     /* Introspection for tests / bench. */
     const StixelParameters& GetParameters() const { return m_params; }
     const std::vector<float>& GetObjectCostLUT() const { return m_obj_cost_lut; }
@@ -331,7 +375,26 @@ private:
     void ScatterSections(const int32_t* counts, const Section* packed, size_t total,
                          std::vector<StixelsData>& out) const;
     void ReservePackBuffers();
-    is_instance_buffers InstanceBuffers(int image = 0) const;
+    is_instance_buffers InstanceBuffers(int image = 0) const;     /* the object's own arrays: what Compute* writes */
+    is_instance_buffers LastInstanceBuffers(int image) const;     /* what the consumers read (a sweep: its selected set) */
+    /* the instance arrays of frame `image` of set `set` inside d_sweep_instances */
+    is_instance_buffers SweepInstanceBuffers(int set, int image) const;
+    size_t SweepInstanceStride() const;
+    /* the Sections the consumers read: d_stixels, or the selected set of a sweep */
+    const Section* LastSections() const;
+    /* the Sections of `n_images` frames at `d_sections` to the host, as ComputeBatch delivers them */
+    void FetchSections(const Section* d_sections, int n_images, const float* alpha, const int* vhor,
+                       std::vector<StixelsData>& out, void* stream);
+    /* the (column, section) -> label mappings of the frames whose instance arrays are ibs[0 .. n) */
+    void FetchInstanceMappings(const std::vector<is_instance_buffers>& ibs, std::vector<InstanceMapping>& out,
+                               void* stream);
+    /* The last SweepBatch while it is what the consumers read (RememberBatch ends it). */
+    struct Sweep {
+        int sets = 0;      /* 0: the last compute call was not a sweep */
+        int frames = 0;    /* frames per set */
+        int selected = 0;
+        bool instances = false;
+    } m_sweep;
     /* The per-section instance map of frames 0 .. n_images-1 for RenderBatch, InstanceOverlapBatch and WorldBatch*:
      * the ground-truth map while it is active (nothing is launched), else the cluster labels of the last compute call
      * scattered into d_section_instance on `stream`; null after a call without instances. */

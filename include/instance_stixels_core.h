@@ -181,6 +181,39 @@ int is_compute(is_ctx* ctx, const float* d_joined, const int32_t* d_segmentation
  * is_compute() runs it by itself for every image whose d_labels is set. */
 int is_cluster_instances(is_ctx* ctx, const is_instance_buffers* instances, void* stream);
 
+/* ---- parameter sweeps: many weight / clustering sets on one resident batch ------------------------------------
+ * The reference's hyper-parameter search (tools/run_cityscapes.py:566-680) re-runs the stixel stage over the same
+ * frames while only the four weights and the three clustering parameters change.  One set of those seven: */
+typedef struct is_sweep_set {
+    float prior_weight, disparity_weight, segmentation_weight, instance_weight; /* as in is_stixel_params:
+                                                    instance_weight already relative to segmentation_weight */
+    float clustering_eps; int clustering_min_pts, clustering_size_filter; int reserved; /* 0 */
+} is_sweep_set;
+
+/* is_compute for n_sets parameter sets on the same inputs in one call.  Slice k of every output ([n_sets][n_images]
+ * ...) holds, byte for byte up to each column's terminator, what is_compute writes on a context created with the same
+ * is_stixel_params except the seven fields of h_sets[k].  The weight-independent work of a call (staging, column
+ * records, object table, pairwise priors) runs once; the DP, the back-trace, the instance candidates and their
+ * clustering run per set.  No cost / index tables.  The context's own parameters are untouched: an is_compute
+ * afterwards gives what it gave before.  Asynchronous and stream-ordered like is_compute; the same constraints, and
+ *   n_sets >= 1, every reserved field 0, n_sets * n_images * realcols * max_sections < 2^31
+ *   d_sections   device, [n_sets][n_images][realcols][max_sections]
+ *   instances    [n_sets][n_images] or NULL */
+int is_compute_sweep(is_ctx* ctx, const float* d_joined, const int32_t* d_segmentation,
+                     const float* h_ground_function, const float* h_normalization_ground,
+                     const float* h_inv_sigma2_ground, const int* h_vhor, int pairwise, int n_images,
+                     const is_sweep_set* h_sets, int n_sets, is_section* d_sections,
+                     const is_instance_buffers* instances, void* stream);
+
+/* The clustering of a compute call again with other parameters, without its DP: the core-candidate flags of every
+ * candidate are derived anew from d_indices -> d_sections ((vT + 1 - vB) >= size_filter), then the batch is clustered
+ * with (eps, min_pts) in one launch.  d_sections and instances [n_images] are those of the compute call (or of one
+ * set of a sweep); d_labels (and d_packed, where given) afterwards equal those of a compute call made with the three
+ * parameters.  Every image needs d_indices, d_centerofmass, d_core_candidates, d_instances_per_class and d_labels
+ * (IS_EINVAL otherwise); n_images <= max_batch. */
+int is_recluster(is_ctx* ctx, const is_section* d_sections, int n_images, float eps, int min_pts, int size_filter,
+                 const is_instance_buffers* instances, void* stream);
+
 /* Compaction of the fixed-stride Section output for the final gather of a multi-GPU batch
  * (the reference copies all max_sections = 200 slots of every column to the host,
  * Stixels.cu:629-633, of which 10-40 are used).  On the current device, on `stream`:
@@ -664,7 +697,9 @@ int is_debug_read_block_summaries(is_ctx* ctx, int column, float* h_out, int cap
 const char* is_last_error(void);
 const char* is_version(void);
 /* Average duration (ms) of the DP kernel launches recorded by the last is_compute call on
- * this context, measured with HIP events on the launch stream; <0 if timing is disabled. */
+ * this context, measured with HIP events on the launch stream; <0 if timing is disabled.  An
+ * is_compute_sweep records none: after one, is_get_kernel_times_ms returns IS_EINVAL ("no call
+ * recorded") until the next is_compute. */
 int is_set_kernel_timing(is_ctx* ctx, int enabled);
 int is_get_kernel_times_ms(is_ctx* ctx, float* prepare_ms, float* dp_ms, float* backtrace_ms);
 size_t is_scratch_bytes(const is_ctx* ctx);

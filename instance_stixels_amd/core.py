@@ -35,6 +35,7 @@ EXPORTS = [
     "is_stixel_world",
     "is_assign_instances_gt", "is_pack_section_labels",
     "is_instance_objects",
+    "is_compute_sweep", "is_recluster",
 ]
 RENDER_MAX_LABELS = 64    # IS_RENDER_MAX_LABELS
 RENDER_MAX_CLASSES = 256  # IS_RENDER_MAX_CLASSES
@@ -47,6 +48,15 @@ class InstanceBuffers(ctypes.Structure):
     _fields_ = [("d_centerofmass", ctypes.c_void_p), ("d_indices", ctypes.c_void_p),
                 ("d_core_candidates", ctypes.c_void_p), ("d_instances_per_class", ctypes.c_void_p),
                 ("d_labels", ctypes.c_void_p), ("d_packed", ctypes.c_void_p)]
+
+
+class SweepSet(ctypes.Structure):
+    """is_sweep_set: the seven parameters one set of a sweep changes (instance_weight relative to
+    segmentation_weight, as in StixelParams); 32 bytes."""
+    _fields_ = [("prior_weight", ctypes.c_float), ("disparity_weight", ctypes.c_float),
+                ("segmentation_weight", ctypes.c_float), ("instance_weight", ctypes.c_float),
+                ("clustering_eps", ctypes.c_float), ("clustering_min_pts", ctypes.c_int),
+                ("clustering_size_filter", ctypes.c_int), ("reserved", ctypes.c_int)]
 
 
 class RenderArgs(ctypes.Structure):
@@ -183,6 +193,8 @@ def lib():
         L.is_assign_instances_gt.argtypes = [ctypes.POINTER(AssignGtArgs), vp]
         L.is_pack_section_labels.argtypes = [vp, ci, ci, ci, ci, vp, vp]
         L.is_instance_objects.argtypes = [ctypes.POINTER(InstanceObjectsArgs), vp]
+        L.is_compute_sweep.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, ci, vp, vp, vp]
+        L.is_recluster.argtypes = [vp, vp, ci, cf, ci, ci, vp, vp]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
         L.is_get_device.argtypes = [ctypes.POINTER(ci)]
@@ -330,6 +342,86 @@ class Core:
         _check(lib().is_compute(self._ctx, d_joined, d_seg, _hp(gf), _hp(ng), _hp(ig), _hp(vh),
                                 int(bool(pairwise)), int(n_images), d_sections, inst,
                                 d_cost_table, d_index_table, stream), "is_compute")
+
+    def compute_sweep_ptr(self, d_joined, d_seg, ground_function, normalization_ground, inv_sigma2_ground, vhor,
+                          pairwise, n_images, sets, d_sections, instances=None, stream=0):
+        """is_compute_sweep on raw device pointers: sets a sequence of SweepSet, instances [n_sets][n_images]
+        InstanceBuffers (flat) or None.  Returns the return code and raises nothing (the tests check IS_EINVAL)."""
+        H = self.params.rows
+        gf = np.ascontiguousarray(ground_function, np.float32).reshape(n_images, H)
+        ng = np.ascontiguousarray(normalization_ground, np.float32).reshape(n_images, H)
+        ig = np.ascontiguousarray(inv_sigma2_ground, np.float32).reshape(n_images, H)
+        vh = np.ascontiguousarray(vhor, np.int32).reshape(n_images)
+        arr_sets = (SweepSet * max(len(sets), 1))(*sets)
+        inst = None
+        if instances is not None:
+            arr = (InstanceBuffers * len(instances))(*instances)
+            inst = ctypes.cast(arr, ctypes.c_void_p)
+        return lib().is_compute_sweep(self._ctx, d_joined, d_seg, _hp(gf), _hp(ng), _hp(ig), _hp(vh),
+                                      int(bool(pairwise)), int(n_images), ctypes.cast(arr_sets, ctypes.c_void_p),
+                                      len(sets), d_sections, inst, stream)
+
+    def recluster_ptr(self, d_sections, n_images, eps, min_pts, size_filter, instances, stream=0):
+        """is_recluster on raw device pointers; returns the return code."""
+        arr = (InstanceBuffers * len(instances))(*instances)
+        return lib().is_recluster(self._ctx, d_sections, int(n_images), float(eps), int(min_pts), int(size_filter),
+                                  ctypes.cast(arr, ctypes.c_void_p), stream)
+
+    def run_sweep(self, sets, joined=None, disparity_big=None, segmentation=None, ground_function=None,
+                  normalization_ground=None, inv_sigma2_ground=None, vhor=None, pairwise=False, median_join=False,
+                  want_instances=True, canary=0):
+        """Runs is_compute_sweep given numpy inputs like run(); every output has a leading [n_sets] axis.  canary > 0:
+        the Section and label arrays are allocated with that many guard elements in front and behind, filled with a
+        pattern, returned as sections_guard / labels_guard (front, back) for the caller to check."""
+        import torch
+        p = self.params
+        C, H, S = p.cols, p.rows, p.max_sections
+        K = len(sets)
+        dev = torch.device("cuda", self.device)
+        seg = torch.from_numpy(np.ascontiguousarray(segmentation, np.int32)).to(dev)
+        n = seg.shape[0]
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if joined is None:
+            big = torch.from_numpy(np.ascontiguousarray(disparity_big, np.float32)).to(dev)
+            d_joined = torch.empty((n, C, H), dtype=torch.float32, device=dev)
+            self.join_columns_ptr(big.data_ptr(), big.shape[2], median_join, d_joined.data_ptr(), n, stream)
+        else:
+            d_joined = torch.from_numpy(np.ascontiguousarray(joined, np.float32)).to(dev)
+        g = int(canary)
+        pat = 0x5A5A5A5A
+        sec_all = torch.full((K * n * C * S * 8 + 2 * g * 8,), pat, dtype=torch.int32, device=dev)
+        sections = sec_all[g * 8: g * 8 + K * n * C * S * 8]
+        inst_t, inst_s, lab_all = None, None, None
+        if want_instances:
+            com = torch.zeros((K, n, INSTANCE_CLASSES, C * S, 2), dtype=torch.float32, device=dev)
+            idx = torch.zeros((K, n, INSTANCE_CLASSES, C * S, 2), dtype=torch.int32, device=dev)
+            core = torch.zeros((K, n, INSTANCE_CLASSES, C * S), dtype=torch.uint8, device=dev)
+            per = torch.zeros((K, n, INSTANCE_CLASSES), dtype=torch.int32, device=dev)
+            lab_all = torch.full((K * n * INSTANCE_CLASSES * C * S + 2 * g,), -9, dtype=torch.int32, device=dev)
+            lab = lab_all[g: g + K * n * INSTANCE_CLASSES * C * S].view(K, n, INSTANCE_CLASSES, C * S)
+            inst_t = (com, idx, core, per, lab)
+            inst_s = [InstanceBuffers(com[k, i].data_ptr(), idx[k, i].data_ptr(), core[k, i].data_ptr(),
+                                      per[k, i].data_ptr(), lab[k, i].data_ptr(), None)
+                      for k in range(K) for i in range(n)]
+        rc = self.compute_sweep_ptr(d_joined.data_ptr(), seg.data_ptr(), ground_function, normalization_ground,
+                                    inv_sigma2_ground, vhor, pairwise, n, sets, sections.data_ptr(), inst_s, stream)
+        _check(rc, "is_compute_sweep")
+        torch.cuda.synchronize(dev)
+        out = dict(joined=d_joined.cpu().numpy(),
+                   sections=sections.cpu().numpy().view(SECTION_DTYPE).reshape(K, n, C, S))
+        if g:
+            a = sec_all.cpu().numpy()
+            out["sections_guard"] = (a[:g * 8].copy(), a[a.size - g * 8:].copy(), np.int32(pat))
+        if want_instances:
+            out["inst_centerofmass"] = inst_t[0].cpu().numpy()
+            out["inst_indices"] = inst_t[1].cpu().numpy()
+            out["inst_core"] = inst_t[2].cpu().numpy()
+            out["inst_per_class"] = inst_t[3].cpu().numpy()
+            out["inst_labels"] = inst_t[4].cpu().numpy()
+            if g:
+                a = lab_all.cpu().numpy()
+                out["labels_guard"] = (a[:g].copy(), a[a.size - g:].copy(), np.int32(-9))
+        return out
 
     # ---- torch-tensor convenience API ----------------------------------------------------
     def run(self, disparity_big=None, joined=None, segmentation=None, ground_function=None,

@@ -128,6 +128,18 @@ struct is_ctx {
     float* d_cost_table;     /* [max_batch*C][H][3] */
     int32_t* d_index_table;  /* [max_batch*C][H][3] */
     size_t scratch_bytes;
+    /* parameter sweeps (is_compute_sweep, is_recluster): the object slack of ctx_init before the weights decide
+     * whether it counts (+inf: a non-finite table or IS_NO_PRUNE), and buffers that grow with the number of sets, owned
+     * apart from `owned` (sweep_reserve replaces them) */
+    float sigma_od_free;
+    PruneRec* d_sweep_prune;            /* [n_sets][columns of the call] the sets' PruneRecs (k_prune_scale) */
+    size_t sweep_prune_cap;             /* records */
+    is_instance_buffers* d_sweep_inst;  /* [n_sets][n_images] device copy of the caller's per-image arrays */
+    is_instance_buffers* h_sweep_inst;  /* pinned staging of the same */
+    size_t sweep_inst_cap;              /* entries */
+    hipEvent_t sweep_inst_free;         /* recorded behind the H2D copy out of h_sweep_inst */
+    bool sweep_inst_pending;
+    int* d_sweep_state;                 /* [0] the generic-column count of the call (k_sweep_state), [1] the constant 1 */
     /* timing */
     bool timing;
     hipEvent_t ev[4];
@@ -246,6 +258,12 @@ int is_ctx_create(const is_stixel_params* p, const float* obj_cost_lut,
     return IS_OK;
 }
 
+/* the branch-and-bound needs non-negative, finite weights (ctx_init; per set of a sweep) */
+static bool weights_allow_pruning(float dw, float pw, float sw, float iw) {
+    return dw >= 0.0f && sw >= 0.0f && iw >= 0.0f && pw >= 0.0f && dw < IS_FLT_HUGE && sw < IS_FLT_HUGE &&
+           iw < IS_FLT_HUGE;
+}
+
 static int ctx_init(is_ctx* c, const is_stixel_params* p, const float* obj_cost_lut,
                     const float* obj_disparity_range, int max_batch, int device, int P2, int P2S) {
     c->params = *p;
@@ -307,12 +325,10 @@ static int ctx_init(is_ctx* c, const is_stixel_params* p, const float* obj_cost_
             if (fabs(v) > max_abs) max_abs = fabs(v);
             if (v < min_v) min_v = v;
         }
-        const bool weights_ok = d.dw >= 0.0f && d.sw >= 0.0f && d.iw >= 0.0f && d.pw >= 0.0f &&
-                                d.dw < IS_FLT_HUGE && d.sw < IS_FLT_HUGE && d.iw < IS_FLT_HUGE;
-        if (finite && weights_ok && !no_prune)
-            d.sigma_od = (float)(((0.0 - min_v) * d.H + 2.0 * gamma * d.H * max_abs) * 1.001);
-        else
-            d.sigma_od = __builtin_inff(); /* pruning off */
+        const bool weights_ok = weights_allow_pruning(d.dw, d.pw, d.sw, d.iw);
+        c->sigma_od_free = finite && !no_prune ? (float)(((0.0 - min_v) * d.H + 2.0 * gamma * d.H * max_abs) * 1.001)
+                                               : __builtin_inff();
+        d.sigma_od = weights_ok ? c->sigma_od_free : __builtin_inff(); /* (+inf: pruning off) */
     }
 
     /* waves per DP workgroup: the LUT tile is 64*(D+1) floats; keep >= 16 waves per CU */
@@ -376,6 +392,11 @@ static int ctx_init(is_ctx* c, const is_stixel_params* p, const float* obj_cost_
     ALLOC(c->d_cluster_scratch, sizeof(int32_t) * B * IS_INSTANCE_CLASSES * 2 * C * (size_t)d.S);
     ALLOC(c->d_inst_cnt, sizeof(int) * B * C * IS_INSTANCE_CLASSES);
     ALLOC(c->d_counters, sizeof(unsigned long long) * IS_CNT_N);
+    ALLOC(c->d_sweep_state, 2 * sizeof(int));
+    {
+        const int init[2] = {0, 1};
+        HIP_TRY(hipMemcpy(c->d_sweep_state, init, sizeof(init), hipMemcpyHostToDevice));
+    }
 #undef ALLOC
     c->scratch_bytes = total;
     for (int i = 0; i < IS_STAGE_SLOTS; i++) {
@@ -391,6 +412,7 @@ static int ctx_init(is_ctx* c, const is_stixel_params* p, const float* obj_cost_
         HIP_TRY(hipEventCreateWithFlags(&c->ev_joins[i], hipEventDisableTiming));
     }
     HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&c->sweep_inst_free, hipEventDisableTiming));
     for (int i = 0; i < 4; i++) HIP_TRY(hipEventCreate(&c->ev[i]));
 
     {
@@ -446,6 +468,10 @@ int is_ctx_destroy(is_ctx* c) {
         if (c->ev_joins[i]) (void)hipEventDestroy(c->ev_joins[i]);
     }
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
+    if (c->sweep_inst_free) (void)hipEventDestroy(c->sweep_inst_free);
+    if (c->d_sweep_prune) (void)hipFree(c->d_sweep_prune);
+    if (c->d_sweep_inst) (void)hipFree(c->d_sweep_inst);
+    if (c->h_sweep_inst) (void)hipHostFree(c->h_sweep_inst);
     for (int i = 0; i < 4; i++)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     free(c);
@@ -904,9 +930,8 @@ int is_get_kernel_times_ms(is_ctx* c, float* prepare_ms, float* dp_ms, float* ba
 
 /* Every launch decision of one DP call (CallPlan, is_launch.h); the launchers launch what it says.  The choices decide
  * launch geometry and kernel instantiations only, never results. */
-static CallPlan plan_call(const is_ctx* c, int n_images, int pairwise, const int* h_vhor, bool tables_requested,
-                          bool want_inst) {
-    const DevParams& P = c->dp;
+static CallPlan plan_call(const is_ctx* c, const DevParams& P, int n_images, int pairwise, const int* h_vhor,
+                          bool tables_requested, bool want_inst) {
     const Knobs& k = c->knobs;
     const int ncols = n_images * P.C;
     CallPlan p = {};
@@ -1000,13 +1025,10 @@ static CallPlan plan_call(const is_ctx* c, int n_images, int pairwise, const int
     return p;
 }
 
-/* Everything is_compute queues on `stream` behind the host-side staging of slot `slot`. */
-static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_seg, int pairwise, int n_images,
-                           is_section* d_sections, const is_instance_buffers* instances, float* d_cost_table,
-                           int32_t* d_index_table, hipStream_t stream, int slot) {
-    const DevParams& P = c->dp;
-    const size_t H = P.H;
-    const bool timing = c->timing;
+/* The H2D copies of a call's staging slot: the ground model and the horizons, with the per-image instance table in
+ * the same copy where the batch is full (`inst_tbl`: a call with fewer frames copies the table by itself). */
+static int enqueue_staging(is_ctx* c, int n_images, bool inst_tbl, hipStream_t stream, int slot) {
+    const size_t H = c->dp.H;
     const bool one_copy = n_images == c->max_batch;
     if (one_copy) {
         HIP_TRY(hipMemcpyAsync(c->d_stage, c->h_stage[slot], c->stage_bytes, hipMemcpyHostToDevice, stream));
@@ -1016,32 +1038,59 @@ static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_se
         HIP_TRY(hipMemcpyAsync(c->d_vhor, c->h_vhor_pinned[slot], sizeof(int) * n_images,
                                hipMemcpyHostToDevice, stream));
     }
-    bool want_inst = false, want_labels = false;
-    if (instances)
-        for (int i = 0; i < n_images; i++) {
-            const is_instance_buffers& ib = instances[i];
-            want_inst = want_inst || ib.d_centerofmass || ib.d_indices || ib.d_core_candidates ||
-                        ib.d_instances_per_class;
-            want_labels = want_labels || ib.d_labels;
-        }
-    if (want_inst && !one_copy) /* the per-image output pointers travel through the pinned staging slot of this call */
+    if (inst_tbl && !one_copy) /* the per-image output pointers travel through the pinned staging slot of this call */
         HIP_TRY(hipMemcpyAsync(c->d_inst_tbl, c->h_inst_pinned[slot], sizeof(is_instance_buffers) * n_images,
                                hipMemcpyHostToDevice, stream));
     HIP_TRY(hipEventRecord(c->staging_free[slot], stream));
+    return IS_OK;
+}
 
-    const CallPlan plan = plan_call(c, n_images, pairwise, c->h_vhor_pinned[slot],
-                                    d_cost_table != nullptr || d_index_table != nullptr, want_inst);
-    if (!pairwise) c->last_unary_path = plan.unary_walk;
+/* which outputs the per-image arrays of a call ask for */
+static void instance_wants(const is_instance_buffers* instances, int n, bool* want_inst, bool* want_labels) {
+    *want_inst = *want_labels = false;
+    if (instances)
+        for (int i = 0; i < n; i++) {
+            const is_instance_buffers& ib = instances[i];
+            *want_inst = *want_inst || ib.d_centerofmass || ib.d_indices || ib.d_core_candidates ||
+                         ib.d_instances_per_class;
+            *want_labels = *want_labels || ib.d_labels;
+        }
+}
+
+/* the context's scratch as the launchers take it (the caller adds its outputs) */
+static CallBuffers call_buffers(const is_ctx* c, const float* d_joined, const int32_t* d_seg) {
     CallBuffers b;
     b.joined = d_joined; b.seg = d_seg; b.ground = c->d_ground; b.vhor = c->d_vhor;
     b.cost_T = c->d_obj_cost_lut; b.cost_F = c->d_obj_cost_fn; b.odr = c->d_odr; b.rcp = c->d_rcp;
     b.recs = c->d_recs; b.lutT = c->d_lutT; b.lutC = c->d_lutC; b.col_flags = c->d_col_flags; b.sv = c->d_sv; b.prune = c->d_prune;
     b.n_generic = c->d_n_generic; b.path_bad = c->d_path_bad; b.priors = c->d_priors; b.steps = c->d_steps;
     b.part_cost = c->d_part_cost; b.part_idx = c->d_part_idx; b.blksum = c->d_blksum; b.t8row = c->d_t8row;
-    b.cost_table = d_cost_table ? d_cost_table : c->d_cost_table;
-    b.index_table = d_index_table ? d_index_table : c->d_index_table;
-    b.sections = d_sections;
+    b.cost_table = c->d_cost_table;
+    b.index_table = c->d_index_table;
+    b.sections = nullptr;
     b.counters = c->counting ? c->d_counters : nullptr;
+    b.inst_cnt = nullptr;
+    return b;
+}
+
+/* Everything is_compute queues on `stream` behind the host-side staging of slot `slot`. */
+static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_seg, int pairwise, int n_images,
+                           is_section* d_sections, const is_instance_buffers* instances, float* d_cost_table,
+                           int32_t* d_index_table, hipStream_t stream, int slot) {
+    const DevParams& P = c->dp;
+    const bool timing = c->timing;
+    bool want_inst = false, want_labels = false;
+    instance_wants(instances, n_images, &want_inst, &want_labels);
+    const int rc_stage = enqueue_staging(c, n_images, want_inst, stream, slot);
+    if (rc_stage != IS_OK) return rc_stage;
+
+    const CallPlan plan = plan_call(c, P, n_images, pairwise, c->h_vhor_pinned[slot],
+                                    d_cost_table != nullptr || d_index_table != nullptr, want_inst);
+    if (!pairwise) c->last_unary_path = plan.unary_walk;
+    CallBuffers b = call_buffers(c, d_joined, d_seg);
+    if (d_cost_table) b.cost_table = d_cost_table;
+    if (d_index_table) b.index_table = d_index_table;
+    b.sections = d_sections;
     b.inst_cnt = want_inst ? c->d_inst_cnt : nullptr;
 
     if (timing) HIP_TRY(hipEventRecord(c->ev[0], stream));
@@ -1071,26 +1120,28 @@ static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_se
     return IS_OK;
 }
 
-int is_compute(is_ctx* c, const float* d_joined, const int32_t* d_seg, const float* h_gf,
-               const float* h_ng, const float* h_is2, const int* h_vhor, int pairwise, int n_images,
-               is_section* d_sections, const is_instance_buffers* instances, float* d_cost_table,
-               int32_t* d_index_table, void* stream_) {
-    if (!c || !d_joined || !d_seg || !h_gf || !h_ng || !h_is2 || !h_vhor || !d_sections)
-        return fail_arg("null pointer");
-    if (n_images < 1 || n_images > c->max_batch) return fail_arg("n_images outside [1, max_batch]");
+/* The argument checks is_compute and is_compute_sweep share (`n_inst` entries of `instances`). */
+static const char* compute_fault(const is_ctx* c, const float* d_joined, const int32_t* d_seg, const float* h_gf,
+                                 const float* h_ng, const float* h_is2, const int* h_vhor, int n_images,
+                                 const is_section* d_sections, const is_instance_buffers* instances, long long n_inst) {
+    if (!c || !d_joined || !d_seg || !h_gf || !h_ng || !h_is2 || !h_vhor || !d_sections) return "null pointer";
+    if (n_images < 1 || n_images > c->max_batch) return "n_images outside [1, max_batch]";
     if ((((uintptr_t)d_joined) | ((uintptr_t)d_seg)) & 15)
-        return fail_arg("d_joined / d_segmentation must be 16-byte aligned (vector loads)");
+        return "d_joined / d_segmentation must be 16-byte aligned (vector loads)";
     if (instances)
-        for (int i = 0; i < n_images; i++)
+        for (long long i = 0; i < n_inst; i++)
             if (instances[i].d_labels && (!instances[i].d_centerofmass || !instances[i].d_core_candidates ||
                                           !instances[i].d_instances_per_class))
-                return fail_arg("d_labels needs d_centerofmass, d_core_candidates and d_instances_per_class");
-    ON_CTX_DEVICE(c);
-    hipStream_t stream = (hipStream_t)stream_;
-    const size_t H = c->dp.H;
+                return "d_labels needs d_centerofmass, d_core_candidates and d_instances_per_class";
+    return nullptr;
+}
 
-    /* stage the per-frame ground model (the reference does 3 blocking cudaMemcpy per frame,
-     * Stixels.cu:479-493): pinned + async here, through a ring of slots each guarded by an event */
+/* The host half of a call: the per-frame ground model (the reference does 3 blocking cudaMemcpy per frame,
+ * Stixels.cu:479-493) and the per-image instance table into the next pinned staging slot: pinned + async, through a
+ * ring of slots each guarded by an event.  `instances`: n_images entries or NULL. */
+static int stage_call(is_ctx* c, const float* h_gf, const float* h_ng, const float* h_is2, const int* h_vhor,
+                      int n_images, const is_instance_buffers* instances, int* out_slot) {
+    const size_t H = c->dp.H;
     const int slot = c->stage_next;
     c->stage_next = (slot + 1) % IS_STAGE_SLOTS;
     if (c->staging_pending[slot]) HIP_TRY(hipEventSynchronize(c->staging_free[slot]));
@@ -1105,16 +1156,221 @@ int is_compute(is_ctx* c, const float* d_joined, const int32_t* d_seg, const flo
      * older call -- possibly freed since -- in d_inst_tbl) */
     if (instances) memcpy(c->h_inst_pinned[slot], instances, sizeof(is_instance_buffers) * n_images);
     else memset(c->h_inst_pinned[slot], 0, sizeof(is_instance_buffers) * n_images);
-
     c->staging_pending[slot] = true;
+    *out_slot = slot;
+    return IS_OK;
+}
+
+/* Invariant the early-outs of k_dp_unary / k_pw_phase2_generic rely on: d_n_generic is zero
+ * between calls (k_prepare counts the generic columns of a call, block 0 of k_backtrace clears
+ * the counter at its end).  A call that failed half way may have counted without clearing. */
+static void clear_call_state(is_ctx* c, hipStream_t stream) {
+    (void)hipMemsetAsync(c->d_n_generic, 0, sizeof(int), stream);
+    (void)hipMemsetAsync(c->d_path_bad, 0, sizeof(int), stream);
+}
+
+int is_compute(is_ctx* c, const float* d_joined, const int32_t* d_seg, const float* h_gf,
+               const float* h_ng, const float* h_is2, const int* h_vhor, int pairwise, int n_images,
+               is_section* d_sections, const is_instance_buffers* instances, float* d_cost_table,
+               int32_t* d_index_table, void* stream_) {
+    if (const char* fault = compute_fault(c, d_joined, d_seg, h_gf, h_ng, h_is2, h_vhor, n_images, d_sections,
+                                          instances, n_images))
+        return fail_arg(fault);
+    ON_CTX_DEVICE(c);
+    hipStream_t stream = (hipStream_t)stream_;
+    int slot = 0;
+    const int rc_stage = stage_call(c, h_gf, h_ng, h_is2, h_vhor, n_images, instances, &slot);
+    if (rc_stage != IS_OK) return rc_stage;
     const int rc = compute_enqueue(c, d_joined, d_seg, pairwise, n_images, d_sections, instances, d_cost_table,
                                    d_index_table, stream, slot);
-    /* Invariant the early-outs of k_dp_unary / k_pw_phase2_generic rely on: d_n_generic is zero
-     * between calls (k_prepare counts the generic columns of a call, block 0 of k_backtrace clears
-     * the counter at its end).  A call that failed half way may have counted without clearing. */
-    if (rc != IS_OK) {
-        (void)hipMemsetAsync(c->d_n_generic, 0, sizeof(int), stream);
-        (void)hipMemsetAsync(c->d_path_bad, 0, sizeof(int), stream);
-    }
+    if (rc != IS_OK) clear_call_state(c, stream);
     return rc;
+}
+
+/* ---- parameter sweeps ---- */
+
+/* The sweep's own buffers for `records` PruneRecs and `entries` instance-table entries: grown into locals, the
+ * context's members replaced after both exist (the old ones only after the device has finished with them). */
+static int sweep_reserve(is_ctx* c, size_t records, size_t entries) {
+    if (records > c->sweep_prune_cap) {
+        PruneRec* p = nullptr;
+        HIP_TRY(hipMalloc((void**)&p, sizeof(PruneRec) * records));
+        HIP_TRY(hipDeviceSynchronize());
+        if (c->d_sweep_prune) (void)hipFree(c->d_sweep_prune);
+        c->d_sweep_prune = p;
+        c->sweep_prune_cap = records;
+    }
+    if (entries > c->sweep_inst_cap) {
+        is_instance_buffers *d = nullptr, *h = nullptr;
+        HIP_TRY(hipMalloc((void**)&d, sizeof(is_instance_buffers) * entries));
+        const hipError_t e = hipHostMalloc((void**)&h, sizeof(is_instance_buffers) * entries);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            return fail_hip(e, "hipHostMalloc(sweep instance table)", __FILE__, __LINE__);
+        }
+        HIP_TRY(hipDeviceSynchronize());
+        if (c->d_sweep_inst) (void)hipFree(c->d_sweep_inst);
+        if (c->h_sweep_inst) (void)hipHostFree(c->h_sweep_inst);
+        c->d_sweep_inst = d;
+        c->h_sweep_inst = h;
+        c->sweep_inst_cap = entries;
+        c->sweep_inst_pending = false;
+    }
+    return IS_OK;
+}
+
+/* `n` entries of the caller's instance table to d_sweep_inst through the pinned copy, on `stream` */
+static int sweep_stage_instances(is_ctx* c, const is_instance_buffers* instances, size_t n, hipStream_t stream) {
+    if (c->sweep_inst_pending) HIP_TRY(hipEventSynchronize(c->sweep_inst_free));
+    memcpy(c->h_sweep_inst, instances, sizeof(is_instance_buffers) * n);
+    HIP_TRY(hipMemcpyAsync(c->d_sweep_inst, c->h_sweep_inst, sizeof(is_instance_buffers) * n, hipMemcpyHostToDevice,
+                           stream));
+    HIP_TRY(hipEventRecord(c->sweep_inst_free, stream));
+    c->sweep_inst_pending = true;
+    return IS_OK;
+}
+
+/* Everything is_compute_sweep queues on `stream`.  Once: the staging copies, the prepare launch, the pairwise priors
+ * (k_prior_tables reads no weight), the sets' PruneRecs.  Per set: what compute_enqueue queues behind its prepare
+ * launch, with a DevParams of the set's own.  The per-call state a single call consumes:
+ *  - d_n_generic: kept behind the prepare launch and put back in front of every set after the first (k_sweep_state);
+ *    k_backtrace of the last set leaves it zero, as the invariant between calls asks;
+ *  - d_path_bad[0]: cleared in front of every set after the first by the same launch;
+ *  - the object table: the carry rows where a set walks, the complete table where a set takes the tile path, both
+ *    where the sets disagree; never the fused LUT + DP launch, whose table would be rebuilt per set;
+ *  - d_inst_cnt, d_cluster_scratch, cost / index scratch, the pairwise scratch: one stream, so the sets follow each
+ *    other through them as consecutive calls do. */
+static int sweep_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_seg, int pairwise, int n_images,
+                         const is_sweep_set* sets, int n_sets, is_section* d_sections,
+                         const is_instance_buffers* instances, hipStream_t stream, int slot) {
+    const int ncols = n_images * c->dp.C;
+    const size_t frame_sections = (size_t)c->dp.C * c->dp.S;
+    c->ev_valid = false; /* (a sweep records no kernel times: is_get_kernel_times_ms refuses until the next is_compute) */
+    const int rc_stage = enqueue_staging(c, n_images, false, stream, slot);
+    if (rc_stage != IS_OK) return rc_stage;
+    if (instances) {
+        const int rc = sweep_stage_instances(c, instances, (size_t)n_sets * n_images, stream);
+        if (rc != IS_OK) return rc;
+    }
+
+    /* the sets' parameter blocks and plans */
+    DevParams* Pk = (DevParams*)malloc(sizeof(DevParams) * n_sets);
+    CallPlan* plans = (CallPlan*)malloc(sizeof(CallPlan) * n_sets);
+    struct Release { void *a, *b; ~Release() { free(a); free(b); } } release{Pk, plans};
+    if (!Pk || !plans) return IS_ENOMEM;
+    bool any_walk = false, any_tile = false;
+    for (int k = 0; k < n_sets; k++) {
+        DevParams& P = Pk[k];
+        P = c->dp;
+        P.dw = sets[k].disparity_weight; P.pw = sets[k].prior_weight; P.sw = sets[k].segmentation_weight;
+        P.iw = sets[k].instance_weight;
+        P.size_filter = sets[k].clustering_size_filter;
+        P.sigma_od = weights_allow_pruning(P.dw, P.pw, P.sw, P.iw) ? c->sigma_od_free : __builtin_inff();
+        bool want_inst = false, want_labels = false;
+        instance_wants(instances ? instances + (size_t)k * n_images : nullptr, n_images, &want_inst, &want_labels);
+        plans[k] = plan_call(c, P, n_images, pairwise, c->h_vhor_pinned[slot], false, want_inst);
+        plans[k].lut_fused = 0;
+        plans[k].prepare_lut = 1;
+        if (!pairwise) (plans[k].unary_walk ? any_walk : any_tile) = true;
+    }
+
+    /* the prepare launch with both PruneRec weights 1 and the weight-free object slack: the records it leaves in
+     * d_prune are the slacks themselves (is_k_sweep.hip) */
+    DevParams P0 = c->dp;
+    P0.dw = 1.0f;
+    P0.iw = 1.0f;
+    P0.sigma_od = c->sigma_od_free;
+    CallPlan prep = plans[0];
+    prep.lut_carry = any_walk ? 1 : 0;
+    CallBuffers b = call_buffers(c, d_joined, d_seg);
+    HIP_TRY(isk_launch_prepare(&P0, &prep, &b, stream));
+    if (any_walk && any_tile) /* the sets disagree: the complete table of every column beside the carry rows */
+        HIP_TRY(isk_launch_lut_repair(&P0, ncols, d_joined, c->d_obj_cost_lut, c->d_lutT, c->d_sweep_state + 1, stream));
+    if (pairwise) HIP_TRY(isk_launch_priors(&P0, c->d_ground, c->d_priors, n_images, stream));
+    for (int k0 = 0; k0 < n_sets; k0 += IS_SWEEP_SCALE_SETS) {
+        const int m = n_sets - k0 < IS_SWEEP_SCALE_SETS ? n_sets - k0 : IS_SWEEP_SCALE_SETS;
+        SweepScale sc = {};
+        for (int k = 0; k < m; k++) {
+            sc.dw[k] = Pk[k0 + k].dw;
+            sc.iw[k] = Pk[k0 + k].iw;
+            sc.sigma_od[k] = Pk[k0 + k].sigma_od;
+        }
+        HIP_TRY(isk_launch_prune_scale(c->d_prune, c->d_sweep_prune + (size_t)k0 * ncols, ncols, m, &sc, stream));
+    }
+    HIP_TRY(isk_launch_sweep_state(c->d_n_generic, c->d_path_bad, c->d_sweep_state, 0, stream));
+
+    for (int k = 0; k < n_sets; k++) {
+        const DevParams& P = Pk[k];
+        const CallPlan& plan = plans[k];
+        const is_instance_buffers* inst_k = instances ? instances + (size_t)k * n_images : nullptr;
+        const is_instance_buffers* d_tbl = instances ? c->d_sweep_inst + (size_t)k * n_images : nullptr;
+        is_section* sections = d_sections + (size_t)k * n_images * frame_sections;
+        bool want_inst = false, want_labels = false;
+        instance_wants(inst_k, n_images, &want_inst, &want_labels);
+        if (k > 0) HIP_TRY(isk_launch_sweep_state(c->d_n_generic, c->d_path_bad, c->d_sweep_state, 1, stream));
+        b.prune = c->d_sweep_prune + (size_t)k * ncols;
+        b.sections = sections;
+        b.inst_cnt = want_inst ? c->d_inst_cnt : nullptr;
+        if (pairwise)
+            HIP_TRY(isk_launch_dp_pairwise(&P, &plan, &b, stream, c->aux_streams, c->ev_fork, c->ev_joins));
+        else
+            HIP_TRY(isk_launch_dp_unary(&P, &plan, &b, stream));
+        HIP_TRY(isk_launch_backtrace(&P, &plan, &b, stream));
+        if (want_inst) {
+            HIP_TRY(isk_launch_compact(&P, n_images, sections, c->d_inst_cnt, d_tbl, stream));
+            if (want_labels)
+                HIP_TRY(isk_launch_cluster(P.C * P.S, sets[k].clustering_eps, sets[k].clustering_min_pts, n_images,
+                                           d_tbl, nullptr, c->d_cluster_scratch, stream));
+        }
+        if (!pairwise) c->last_unary_path = plan.unary_walk;
+    }
+    return IS_OK;
+}
+
+int is_compute_sweep(is_ctx* c, const float* d_joined, const int32_t* d_seg, const float* h_gf, const float* h_ng,
+                     const float* h_is2, const int* h_vhor, int pairwise, int n_images, const is_sweep_set* h_sets,
+                     int n_sets, is_section* d_sections, const is_instance_buffers* instances, void* stream_) {
+    if (!h_sets) return fail_arg("null pointer");
+    if (n_sets < 1) return fail_arg("n_sets < 1");
+    if (const char* fault = compute_fault(c, d_joined, d_seg, h_gf, h_ng, h_is2, h_vhor, n_images, d_sections,
+                                          instances, (long long)n_sets * (n_images > 0 ? n_images : 0)))
+        return fail_arg(fault);
+    if ((long long)n_sets * n_images * c->dp.C * c->dp.S > 0x7fffffffLL)
+        return fail_arg("n_sets * n_images * realcols * max_sections does not fit 31 bits");
+    for (int k = 0; k < n_sets; k++)
+        if (h_sets[k].reserved != 0) return fail_arg("is_sweep_set.reserved must be 0");
+    if (((uintptr_t)d_sections) & 15) return fail_arg("d_sections must be 16-byte aligned");
+    ON_CTX_DEVICE(c);
+    hipStream_t stream = (hipStream_t)stream_;
+    const int rc_res = sweep_reserve(c, (size_t)n_sets * n_images * c->dp.C, instances ? (size_t)n_sets * n_images : 0);
+    if (rc_res != IS_OK) return rc_res;
+    int slot = 0;
+    const int rc_stage = stage_call(c, h_gf, h_ng, h_is2, h_vhor, n_images, nullptr, &slot);
+    if (rc_stage != IS_OK) return rc_stage;
+    const int rc = sweep_enqueue(c, d_joined, d_seg, pairwise, n_images, h_sets, n_sets, d_sections, instances, stream,
+                                 slot);
+    if (rc != IS_OK) clear_call_state(c, stream);
+    return rc;
+}
+
+int is_recluster(is_ctx* c, const is_section* d_sections, int n_images, float eps, int min_pts, int size_filter,
+                 const is_instance_buffers* instances, void* stream_) {
+    if (!c || !d_sections || !instances) return fail_arg("null pointer");
+    if (n_images < 1 || n_images > c->max_batch || n_images > 65535) return fail_arg("n_images outside [1, max_batch]");
+    for (int i = 0; i < n_images; i++)
+        if (!instances[i].d_indices || !instances[i].d_centerofmass || !instances[i].d_core_candidates ||
+            !instances[i].d_instances_per_class || !instances[i].d_labels)
+            return fail_arg("d_indices, d_centerofmass, d_core_candidates, d_instances_per_class and d_labels are "
+                            "required for every image");
+    ON_CTX_DEVICE(c);
+    hipStream_t stream = (hipStream_t)stream_;
+    const int rc_res = sweep_reserve(c, 0, (size_t)n_images);
+    if (rc_res != IS_OK) return rc_res;
+    const int rc_stage = sweep_stage_instances(c, instances, (size_t)n_images, stream);
+    if (rc_stage != IS_OK) return rc_stage;
+    const int n_slots = c->dp.C * c->dp.S;
+    HIP_TRY(isk_launch_recore(n_slots, c->dp.S, size_filter, n_images, d_sections, c->d_sweep_inst, stream));
+    HIP_TRY(isk_launch_cluster(n_slots, eps, min_pts, n_images, c->d_sweep_inst, nullptr, c->d_cluster_scratch,
+                               stream));
+    return IS_OK;
 }

@@ -159,6 +159,17 @@ hipError_t isk_launch_compact(const DevParams* P, int n_images, const is_section
 hipError_t isk_launch_cluster(int n_slots, float eps, int min_pts, int n_images, const is_instance_buffers* d_tbl,
                               const is_instance_buffers* one, int32_t* scratch, hipStream_t stream);
 
+/* is_k_sweep.hip: a parameter sweep (is_compute_sweep) and the re-clustering (is_recluster) */
+#define IS_SWEEP_SCALE_SETS 64 /* sets per k_prune_scale launch: their factors travel as a kernel argument */
+struct SweepScale { /* per set: the two weights of PruneRec and the set's object slack (+inf: pruning off) */
+    float dw[IS_SWEEP_SCALE_SETS], iw[IS_SWEEP_SCALE_SETS], sigma_od[IS_SWEEP_SCALE_SETS];
+};
+hipError_t isk_launch_prune_scale(const PruneRec* base, PruneRec* out, int ncols, int n_sets, const SweepScale* sc,
+                                  hipStream_t stream);
+hipError_t isk_launch_sweep_state(int* n_generic, int* path_bad, int* saved, int restore, hipStream_t stream);
+hipError_t isk_launch_recore(int n_slots, int max_sections, int size_filter, int n_images, const is_section* sections,
+                             const is_instance_buffers* d_tbl, hipStream_t stream);
+
 /* is_k_frontend.hip */
 hipError_t isk_launch_join(const float* big, float* joined, int H, int W, int C, int step, int margin, int median,
                            float invalid, int n_images, hipStream_t stream);

@@ -228,3 +228,29 @@ class CityscapesInstanceEval:
             a50 = ap[:, o50].ravel()
             AP50 = float(a50[~np.isnan(a50)].mean()) if (~np.isnan(a50)).any() else float("nan")
         return dict(ap=ap, labels=labs, overlaps=self.overlaps.copy(), class_ap=class_ap, AP=AP, AP50=AP50)
+
+
+# ---- parameter sweeps: the reference's search objective without a re-initialisation per sample ----------------
+def sweep_scores(st, sets, gt_label, gt_instance, n_labels=CITYSCAPES_N_LABELS, stream=0):
+    """The raw scores of every set of the last st.SweepBatch(..., sets) of `st` (a host.Stixels), on the device: per
+    set SelectSweepSet, RenderBatch metrics-only (no image is written) against gt_label (device uint8
+    [frames][rows][cols], a pointer as int) and InstanceOverlapBatch against gt_instance (device int32, or None: a
+    sweep without instances).  `sets` are the sets that call was given: ValueError when their number is not the
+    number of sets the object holds.  Returns one dict per set: confusion ([n_labels][n_labels] uint64, gt x pred,
+    summed over the frames), stixel_count ([frames] int32) and overlaps (the per-frame tables, None without
+    gt_instance) -- what cityscapes_iou and CityscapesInstanceEval take.  tools/run_cityscapes.py:585-640 scores a
+    sample as mean IoU + 1.5 * AP."""
+    import torch
+    if len(sets) != st.SweepSets():
+        raise ValueError(f"sweep_scores: {len(sets)} sets given, the last SweepBatch of the object holds {st.SweepSets()}")
+    frames = st.LastFrames()
+    dev = torch.device("cuda", st.GetActiveDevice())
+    out = []
+    for k in range(len(sets)):
+        st.SelectSweepSet(k)
+        conf = torch.zeros((n_labels, n_labels), dtype=torch.int64, device=dev)
+        _, _, count = st.RenderBatch(frames, gt_label=gt_label, n_labels=n_labels, confusion=conf.data_ptr(),
+                                     stream=stream)
+        overlaps = None if gt_instance is None else st.InstanceOverlapBatch(frames, gt_instance, stream=stream)
+        out.append(dict(confusion=conf.cpu().numpy().astype(np.uint64), stixel_count=count, overlaps=overlaps))
+    return out

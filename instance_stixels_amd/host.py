@@ -34,6 +34,8 @@ EXPORTS = [
     "ish_world_batch", "ish_world_records", "ish_set_world_capacity",
     "ish_instance_objects_batch", "ish_instance_objects_records", "ish_set_instance_object_capacity",
     "ish_assign_instances_gt_batch", "ish_assign_instances_gt_quads", "ish_use_cluster_instances", "ish_set_gt_assignment_parameters",
+    "ish_core_sweep_set", "ish_sweep_batch", "ish_select_sweep_set", "ish_last_frames", "ish_sweep_sets",
+    "ish_active_device", "ish_sweep_sections", "ish_recluster_batch",
 ]
 WORLD_DTYPE = _core.WORLD_DTYPE  # is_world_stixel, the records of Stixels.WorldBatch
 OBJECT_DTYPE = _core.OBJECT_DTYPE    # is_instance_object, the objects of Stixels.InstanceObjectsBatch
@@ -127,6 +129,14 @@ def lib():
         L.ish_assign_instances_gt_quads.argtypes = [vp, vp, ctypes.c_int64]
         L.ish_use_cluster_instances.argtypes = [vp]
         L.ish_set_gt_assignment_parameters.argtypes = [vp, ctypes.c_double, vp, ci]
+        L.ish_core_sweep_set.argtypes = [vp, ctypes.POINTER(_core.SweepSet)]
+        L.ish_sweep_batch.argtypes = [vp, ci, ci, vp, vp, vp, vp, ci, ci, vp]
+        L.ish_select_sweep_set.argtypes = [vp, ci]
+        L.ish_last_frames.argtypes = [vp]
+        L.ish_sweep_sets.argtypes = [vp]
+        L.ish_active_device.argtypes = [vp]
+        L.ish_sweep_sections.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp]
+        L.ish_recluster_batch.argtypes = [vp, cf, ci, ci, ci, vp, ci, vp, vp]
         _LIB = L
     return _LIB
 
@@ -402,6 +412,76 @@ class Stixels:
             maps[f][(u, v)] = l
         return maps
 
+    # ---- parameter sweeps ------------------------------------------------------------
+    def SweepBatch(self, pairwise, d_disparity_big, d_segmentation, road, sets, with_instances=True, stream=0):
+        """Stixels::SweepBatch: ComputeBatch for every parameter set of `sets` on the same device-resident inputs in
+        one call.  sets: tuples (prior_weight, disparity_weight, segmentation_weight, instance_weight, eps, min_pts,
+        size_filter), the weights as SetWeightParameters takes them.  The results stay on the device; set 0 is
+        selected for the consumers (RenderBatch, InstanceOverlapBatch, WorldBatch, AssignInstancesGTBatch,
+        InstanceObjectsBatch), SelectSweepSet chooses another, SweepSections brings one to the host."""
+        n = len(road)
+        rp = np.ascontiguousarray(road, np.float32).reshape(n, 4)
+        ss = np.ascontiguousarray(sets, np.float32).reshape(len(sets), 7)
+        self._check(lib().ish_sweep_batch(self._h, int(bool(pairwise)), n, d_disparity_big, d_segmentation,
+                                          rp.ctypes.data, ss.ctypes.data, len(ss), int(bool(with_instances)),
+                                          stream), "SweepBatch")
+
+    def SelectSweepSet(self, k):
+        """Makes set k of the last SweepBatch what the consumers read; ValueError when k is out of range or the last
+        compute call was not a sweep."""
+        self._check(lib().ish_select_sweep_set(self._h, int(k)), "SelectSweepSet")
+
+    def _query(self, f, what):
+        v = int(f(self._h))
+        if v < -1:
+            raise ValueError(f"{what}: the object is closed")
+        return v
+
+    def LastFrames(self):
+        """Frames of the last compute call the consumers can read."""
+        return self._query(lib().ish_last_frames, "LastFrames")
+
+    def SweepSets(self):
+        """Sets of the last SweepBatch while it is what the consumers read; 0 when the last compute call was not a
+        sweep."""
+        return self._query(lib().ish_sweep_sets, "SweepSets")
+
+    def GetActiveDevice(self):
+        """The device the buffers of the last Initialize() live on (-1 before)."""
+        return self._query(lib().ish_active_device, "GetActiveDevice")
+
+    def SweepSections(self, k, with_instances=True):
+        """Stixels::SweepSections: set k of the last SweepBatch on the host, as ComputeBatch returns a batch:
+        (list of StixelsData, list of instance mappings or None)."""
+        n = self.LastFrames()
+        C, S = self.GetRealCols(), self.GetMaxSections()
+        sec = np.zeros((n, C, S), SECTION_DTYPE)
+        vh = np.zeros(n, np.int32)
+        alpha = np.zeros(n, np.float32)
+        cap = C * S
+        tri = np.zeros((n, cap, 3), np.int32) if with_instances else None
+        cnt = np.zeros(n, np.int32)
+        self._check(lib().ish_sweep_sections(self._h, int(k), sec.ctypes.data, vh.ctypes.data, alpha.ctypes.data,
+                                             tri.ctypes.data if with_instances else None, cap, cnt.ctypes.data),
+                    "SweepSections")
+        cfg = self._cfg
+        data = [StixelsData(sec[i], int(cfg.rows), int(cfg.cols), C, S, int(cfg.max_dis), int(cfg.column_step),
+                            int(cfg.n_semantic_classes), float(alpha[i]), int(vh[i])) for i in range(n)]
+        return data, (_maps(tri, cnt) if with_instances else None)
+
+    def ReclusterBatch(self, eps, min_pts, size_filter, with_mapping=True, stream=0):
+        """Stixels::ReclusterBatch: the clustering of the last compute call (or of the selected sweep set) again with
+        these parameters, without its DP.  Returns the per-frame instance mappings, or None without with_mapping.
+        ValueError before any compute call and after one without instances."""
+        n = self.LastFrames()
+        cap = self.GetRealCols() * self.GetMaxSections()
+        tri = np.zeros((n, cap, 3), np.int32) if with_mapping else None
+        cnt = np.zeros(max(n, 1), np.int32)
+        self._check(lib().ish_recluster_batch(self._h, float(eps), int(min_pts), int(size_filter), n,
+                                              tri.ctypes.data if with_mapping else None, cap, cnt.ctypes.data,
+                                              stream), "ReclusterBatch")
+        return _maps(tri, cnt[:n]) if with_mapping else None
+
     def UseClusterInstances(self):
         """Back to the cluster labels of the last compute call for RenderBatch / InstanceOverlapBatch / WorldBatch."""
         self._check(lib().ish_use_cluster_instances(self._h), "UseClusterInstances")
@@ -467,6 +547,22 @@ class Stixels:
                                                ig.ctypes.data, ctypes.byref(vh)),
                     "GetGroundModel")
         return gf, ng, ig, vh.value
+
+
+def _maps(tri, cnt):
+    """[frames][cap][3] (column, section, label) triples and their counts as one dict per frame"""
+    return [{(int(u), int(v)): int(l) for u, v, l in tri[i, :cnt[i]]} for i in range(len(cnt))]
+
+
+def core_sweep_set(prior_weight, disparity_weight, segmentation_weight, instance_weight, eps, min_pts, size_filter):
+    """Stixels::CoreSweepSet: a SweepBatch set as the core takes it (core.SweepSet): SetWeightParameters' rule for the
+    instance weight.  Needs no device."""
+    s = np.array([prior_weight, disparity_weight, segmentation_weight, instance_weight, eps, min_pts, size_filter],
+                 np.float32)
+    out = _core.SweepSet()
+    if lib().ish_core_sweep_set(s.ctypes.data, ctypes.byref(out)) < 0:
+        raise RuntimeError(lib().ish_last_error().decode())
+    return out
 
 
 def hough_lines(image, rho=1.0, theta=float(np.pi / 180), threshold=25, cap=4096):

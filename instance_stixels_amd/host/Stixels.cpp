@@ -472,6 +472,12 @@ float Stixels::Compute(const bool pairwise, StixelsData& stixels_data,
     return -1; /* the reference's timers are commented out, Stixels.cu:636 */
 }
 
+/* what the consumers read: the arrays of the last compute call, or of the selected set of a sweep (the compute calls
+ * themselves always write the object's own arrays, InstanceBuffers) */
+is_instance_buffers Stixels::LastInstanceBuffers(int image) const {
+    return m_sweep.sets > 0 ? SweepInstanceBuffers(m_sweep.selected, image) : InstanceBuffers(image);
+}
+
 is_instance_buffers Stixels::InstanceBuffers(int image) const {
     const size_t inst_n = (size_t)m_instance_classes * m_realcols * m_max_sections;
     const size_t i = (size_t)image;
@@ -618,6 +624,7 @@ void Stixels::RememberBatch(int frames, bool cluster_instances, const float* alp
     m_last.alpha.assign(alpha, alpha + frames);
     m_last.vhor.assign(vhor, vhor + frames);
     m_last.known_offsets.clear();
+    m_sweep = Sweep(); /* (a sweep lasts until the next compute call; SweepBatch sets it behind this) */
 }
 
 void Stixels::ForgetBatch() { RememberBatch(0, false, nullptr, nullptr); }
@@ -636,7 +643,7 @@ Stixels::ConsumerScope Stixels::BeginConsumer(const char* name, const char* verb
 
 template <class Args>
 void Stixels::FillGeometry(Args& a, int n_images, int first) const {
-    a.d_sections = (const is_section*)d_stixels + (size_t)first * m_realcols * m_max_sections;
+    a.d_sections = (const is_section*)LastSections() + (size_t)first * m_realcols * m_max_sections;
     a.n_images = n_images;
     a.realcols = m_realcols;
     a.max_sections = m_max_sections;
@@ -645,7 +652,7 @@ void Stixels::FillGeometry(Args& a, int n_images, int first) const {
 }
 
 void Stixels::FillGeometry(is_world_args& a, int n_images) const {
-    a.d_sections = (const is_section*)d_stixels;
+    a.d_sections = (const is_section*)LastSections();
     a.n_images = n_images;
     a.realcols = m_realcols;
     a.max_sections = m_max_sections;
@@ -704,7 +711,7 @@ const int32_t* Stixels::SectionInstanceMap(int n_images, void* stream) {
     if (!m_last.cluster_instances) return nullptr;
     d_section_instance.reserve((size_t)m_max_batch * m_realcols * m_max_sections);
     std::vector<is_instance_buffers> ibs;
-    for (int i = 0; i < n_images; i++) ibs.push_back(InstanceBuffers(i));
+    for (int i = 0; i < n_images; i++) ibs.push_back(LastInstanceBuffers(i));
     IS_CHECK_RETURN(is_section_instance_labels(ibs.data(), n_images, m_realcols, m_max_sections,
                                                d_section_instance.get(), stream));
     return d_section_instance.get();
@@ -1020,6 +1027,211 @@ Stixels::InstanceObjectsView Stixels::InstanceObjectsBatchView(int n_images, voi
     v.n_objects = h[0];
     v.n_points = h[1];
     return v;
+}
+
+/* ---------------------------------------------------------------- parameter sweeps */
+
+is_sweep_set Stixels::CoreSweepSet(const SweepSet& set) {
+    is_sweep_set s = {};
+    s.prior_weight = set.prior_weight;
+    s.disparity_weight = set.disparity_weight;
+    s.segmentation_weight = set.segmentation_weight;
+    /* SetWeightParameters: the instance weight is expressed relative to the segmentation weight */
+    s.instance_weight = 0.0;
+    if (set.segmentation_weight > 1e-5) {
+        s.instance_weight = set.instance_weight / set.segmentation_weight;
+        if (set.instance_weight < 1e-8) s.instance_weight = 0.0;
+    }
+    s.clustering_eps = set.eps;
+    s.clustering_min_pts = set.min_pts;
+    s.clustering_size_filter = set.size_filter;
+    return s;
+}
+
+/* One frame of d_sweep_instances, every part 16-byte aligned:
+ * [8] per-class counts | centres [inst_n][2] | indices [inst_n][2] | labels [inst_n] | packed [1 + 3 inst_n] | core flags */
+namespace {
+struct SweepFrameLayout {
+    size_t com, idx, labels, packed, core, stride;
+    explicit SweepFrameLayout(size_t inst_n) {
+        auto up = [](size_t b) { return (b + 15) / 16 * 16; };
+        com = up(IS_INSTANCE_CLASSES * sizeof(int32_t));
+        idx = com + up(inst_n * 2 * sizeof(float));
+        labels = idx + up(inst_n * 2 * sizeof(int32_t));
+        packed = labels + up(inst_n * sizeof(int32_t));
+        core = packed + up((1 + 3 * inst_n) * sizeof(int32_t));
+        stride = core + up(inst_n);
+    }
+};
+}  // namespace
+
+size_t Stixels::SweepInstanceStride() const {
+    return SweepFrameLayout((size_t)m_instance_classes * m_realcols * m_max_sections).stride;
+}
+
+is_instance_buffers Stixels::SweepInstanceBuffers(int set, int image) const {
+    const SweepFrameLayout l((size_t)m_instance_classes * m_realcols * m_max_sections);
+    char* const f = d_sweep_instances.get() + ((size_t)set * m_sweep.frames + image) * l.stride;
+    is_instance_buffers ib = {};
+    ib.d_instances_per_class = (int32_t*)f;
+    ib.d_centerofmass = (float*)(f + l.com);
+    ib.d_indices = (int32_t*)(f + l.idx);
+    ib.d_labels = (int32_t*)(f + l.labels);
+    ib.d_packed = (int32_t*)(f + l.packed);
+    ib.d_core_candidates = (uint8_t*)(f + l.core);
+    return ib;
+}
+
+const Section* Stixels::LastSections() const {
+    if (m_sweep.sets == 0) return d_stixels;
+    return d_sweep_stixels.get() + (size_t)m_sweep.selected * m_sweep.frames * m_realcols * m_max_sections;
+}
+
+void Stixels::SweepBatch(bool pairwise, int n_images, const pixel_t* d_big, const int32_t* d_seg,
+                         const RoadParameters* road, const std::vector<SweepSet>& sets, void* stream,
+                         bool with_instances) {
+    if (n_images < 1 || n_images > m_max_batch)
+        throw std::invalid_argument("n_images outside [1, max_batch] of InitializeBatch().");
+    if (sets.empty()) throw std::invalid_argument("SweepBatch: no parameter sets.");
+    const size_t cs = (size_t)m_realcols * m_max_sections;
+    const size_t frames = sets.size() * (size_t)n_images;
+    if (frames * cs > 0x7fffffffull)
+        throw std::invalid_argument("SweepBatch: sets * n_images * realcols * max_sections does not fit 31 bits.");
+    const DeviceGuard guard(m_ctx_device);
+    if (stream == nullptr) stream = m_stream;
+    ForgetBatch(); /* (a sweep that fails leaves nothing to consume) */
+    /* grow: only the array that is too small, into a local; the members after both exist */
+    const size_t want_inst = with_instances ? frames * SweepInstanceStride() : 0;
+    {
+        DeviceArray<Section> s_new;
+        DeviceArray<char> i_new;
+        const bool grow_s = frames * cs > d_sweep_stixels.capacity(), grow_i = want_inst > d_sweep_instances.capacity();
+        if (grow_s) s_new.reserve(frames * cs);
+        try {
+            if (grow_i) i_new.reserve(want_inst);
+        } catch (...) {
+            s_new.release();
+            throw;
+        }
+        if (grow_s) d_sweep_stixels = std::move(s_new); /* (a swap: the local now holds the old array) */
+        if (grow_i) d_sweep_instances = std::move(i_new);
+        s_new.release();
+        i_new.release();
+    }
+    GroundModel g;
+    std::vector<int> vh;
+    BatchGround(n_images, road, g, vh);
+    IS_CHECK_RETURN(is_join_columns(m_ctx, d_big, m_cols, m_median_join ? 1 : 0, d_disparity.get(), n_images, stream));
+    std::vector<is_sweep_set> core_sets;
+    for (const SweepSet& set : sets) core_sets.push_back(CoreSweepSet(set));
+    std::vector<float> alpha(n_images);
+    for (int i = 0; i < n_images; i++) alpha[i] = road[i].alpha_ground;
+    m_sweep.frames = n_images; /* (SweepInstanceBuffers: set k's frames lie behind k * frames frames) */
+    std::vector<is_instance_buffers> ibs;
+    if (with_instances)
+        for (size_t k = 0; k < sets.size(); k++)
+            for (int i = 0; i < n_images; i++) ibs.push_back(SweepInstanceBuffers((int)k, i));
+    CheckConsumer("SweepBatch", is_compute_sweep(m_ctx, d_disparity.get(), d_seg, g.function.data(),
+                                                 g.normalization.data(), g.inv_sigma2.data(), vh.data(), pairwise ? 1 : 0,
+                                                 n_images, core_sets.data(), (int)core_sets.size(),
+                                                 (is_section*)d_sweep_stixels.get(), with_instances ? ibs.data() : nullptr,
+                                                 stream));
+    RememberBatch(n_images, with_instances, alpha.data(), vh.data());
+    m_sweep.sets = (int)sets.size();
+    m_sweep.frames = n_images;
+    m_sweep.selected = 0;
+    m_sweep.instances = with_instances;
+}
+
+void Stixels::SelectSweepSet(int k) {
+    if (m_sweep.sets == 0) throw std::invalid_argument("SelectSweepSet: the last compute call was not a SweepBatch().");
+    if (k < 0 || k >= m_sweep.sets) throw std::invalid_argument("SelectSweepSet: k outside the sets of the last SweepBatch().");
+    m_sweep.selected = k;
+    m_last.cluster_instances = m_sweep.instances;
+    m_last.gt_instances = false;
+    m_last.known_offsets.clear();
+}
+
+void Stixels::FetchSections(const Section* d_sections, int n_images, const float* alpha, const int* vhor,
+                            std::vector<StixelsData>& out, void* stream) {
+    const size_t ncols = (size_t)n_images * m_realcols;
+    ReservePackBuffers();
+    IS_CHECK_RETURN(is_pack_sections((const is_section*)d_sections, (int)ncols, m_max_sections, d_pack_counts.get(),
+                                     d_pack_offsets.get(), (is_section*)d_pack_sections.get(), stream));
+    const int32_t* offsets = h_pack_offsets.get();
+    IS_CHECK_RETURN(is_memcpy_d2h(h_pack_offsets.get(), d_pack_offsets.get(), (ncols + 1) * sizeof(int32_t), stream));
+    IS_CHECK_RETURN(is_stream_synchronize(stream));
+    const size_t total = (size_t)offsets[ncols];
+    if (total > h_pack_sections.capacity()) h_pack_sections.reserve(total + total / 4 + 1024);
+    if (total > 0)
+        IS_CHECK_RETURN(is_memcpy_d2h(h_pack_sections.get(), d_pack_sections.get(), total * sizeof(Section), stream));
+    out.resize(n_images);
+    for (int i = 0; i < n_images; i++) FillHeader(out[i], alpha[i], vhor[i]);
+    std::vector<int32_t> counts(ncols);
+    for (size_t col = 0; col < ncols; col++) counts[col] = offsets[col + 1] - offsets[col];
+    IS_CHECK_RETURN(is_stream_synchronize(stream));
+    ScatterSections(counts.data(), h_pack_sections.get(), total, out);
+}
+
+void Stixels::FetchInstanceMappings(const std::vector<is_instance_buffers>& ibs, std::vector<InstanceMapping>& out,
+                                    void* stream) {
+    const size_t n = ibs.size();
+    const size_t slots = (size_t)m_instance_classes * m_realcols * m_max_sections;
+    std::vector<int32_t> head(n * m_instance_classes);
+    for (size_t i = 0; i < n; i++)
+        IS_CHECK_RETURN(is_memcpy_d2h(head.data() + i * m_instance_classes, ibs[i].d_instances_per_class,
+                                      m_instance_classes * sizeof(int32_t), stream));
+    IS_CHECK_RETURN(is_stream_synchronize(stream));
+    std::vector<size_t> totals(n, 0);
+    std::vector<std::vector<int32_t>> triples(n);
+    for (size_t i = 0; i < n; i++) {
+        for (int k = 0; k < m_instance_classes; k++)
+            totals[i] += (size_t)std::min<int64_t>(std::max<int32_t>(head[i * m_instance_classes + k], 0),
+                                                   (int64_t)m_realcols * m_max_sections);
+        totals[i] = std::min(totals[i], slots);
+        triples[i].resize(3 * totals[i] + 1);
+        if (totals[i] > 0)
+            IS_CHECK_RETURN(is_memcpy_d2h(triples[i].data(), ibs[i].d_packed, (1 + 3 * totals[i]) * sizeof(int32_t),
+                                          stream));
+    }
+    IS_CHECK_RETURN(is_stream_synchronize(stream));
+    out.assign(n, InstanceMapping());
+    for (size_t i = 0; i < n; i++) {
+        const int32_t* t = triples[i].data() + 1;
+        for (size_t j = 0; j < totals[i]; j++) out[i][std::make_pair(t[3 * j], t[3 * j + 1])] = t[3 * j + 2];
+    }
+}
+
+void Stixels::SweepSections(int k, std::vector<StixelsData>& out, std::vector<InstanceMapping>* instance_stixels) {
+    if (m_sweep.sets == 0) throw std::invalid_argument("SweepSections: the last compute call was not a SweepBatch().");
+    if (k < 0 || k >= m_sweep.sets) throw std::invalid_argument("SweepSections: k outside the sets of the last SweepBatch().");
+    if (instance_stixels && !m_sweep.instances)
+        throw std::invalid_argument("SweepSections: the mappings need a SweepBatch() with instances.");
+    const DeviceGuard guard(m_ctx_device);
+    const int n = m_last.frames;
+    FetchSections(d_sweep_stixels.get() + (size_t)k * n * m_realcols * m_max_sections, n, m_last.alpha.data(),
+                  m_last.vhor.data(), out, m_stream);
+    if (!instance_stixels) return;
+    std::vector<is_instance_buffers> ibs;
+    for (int i = 0; i < n; i++) ibs.push_back(SweepInstanceBuffers(k, i));
+    FetchInstanceMappings(ibs, *instance_stixels, m_stream);
+}
+
+void Stixels::ReclusterBatch(float eps, int min_pts, int size_filter, std::vector<InstanceMapping>* instance_stixels,
+                             void* stream) {
+    if (m_last.frames == 0)
+        throw std::invalid_argument("ReclusterBatch clusters the candidates of the last compute call: there are none.");
+    if (!m_last.cluster_instances)
+        throw std::invalid_argument("ReclusterBatch: needs a compute call with instances.");
+    const DeviceGuard guard(m_ctx_device);
+    if (stream == nullptr) stream = m_stream;
+    std::vector<is_instance_buffers> ibs;
+    for (int i = 0; i < m_last.frames; i++) ibs.push_back(LastInstanceBuffers(i));
+    CheckConsumer("ReclusterBatch", is_recluster(m_ctx, (const is_section*)LastSections(), m_last.frames, eps, min_pts,
+                                                 size_filter, ibs.data(), stream));
+    m_last.gt_instances = false; /* (as UseClusterInstances) */
+    m_labels_on_host = false;
+    if (instance_stixels) FetchInstanceMappings(ibs, *instance_stixels, stream);
 }
 
 /* The shard of this rank, then the compacted gather of every rank's Sections on `dst` (the

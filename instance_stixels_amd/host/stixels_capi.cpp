@@ -5,6 +5,7 @@
  * GetInstanceStixels] -> Finish  (call sequence of apps/run_cityscapes.cu:328-449).
  * C++ exceptions are turned into a negative return code + message.
  */
+#include <algorithm>
 #include <cstring>
 #include <ctime>
 #include <exception>
@@ -420,6 +421,87 @@ int ish_use_cluster_instances(void* h) {
 /* label_ids8: host [8] or null for Cityscapes */
 int ish_set_gt_assignment_parameters(void* h, double min_fraction, const int* label_ids8, int gt_is_train_ids) {
     return guard([&] { ((Stixels*)h)->SetGTAssignmentParameters(min_fraction, label_ids8, gt_is_train_ids != 0); });
+}
+
+/* ---- parameter sweeps.  sets: [n_sets][7] floats = (prior, disparity, segmentation, instance weight, eps, min_pts,
+ * size_filter), the weights in SetWeightParameters' user-facing form.  min_pts and size_filter travel as float32:
+ * exact up to 2^24, far above any number of sections or rows. ---- */
+static std::vector<Stixels::SweepSet> to_sets(const float* sets, int n) {
+    std::vector<Stixels::SweepSet> v((size_t)std::max(n, 0));
+    for (int k = 0; k < n; k++) {
+        const float* s = sets + 7 * (size_t)k;
+        v[k] = Stixels::SweepSet{s[0], s[1], s[2], s[3], s[4], (int)s[5], (int)s[6]};
+    }
+    return v;
+}
+static void copy_maps(const std::vector<Stixels::InstanceMapping>& maps, int* triples, int cap, int* counts) {
+    for (size_t i = 0; i < maps.size(); i++) {
+        int n = 0;
+        for (const auto& kv : maps[i]) {
+            if (n >= cap) break;
+            int* t = triples + (i * (size_t)cap + n) * 3;
+            t[0] = kv.first.first; t[1] = kv.first.second; t[2] = kv.second;
+            n++;
+        }
+        counts[i] = (int)maps[i].size();
+    }
+}
+/* Stixels::CoreSweepSet: needs no device */
+int ish_core_sweep_set(const float* set7, is_sweep_set* out) {
+    return guard([&] { *out = Stixels::CoreSweepSet(to_sets(set7, 1)[0]); });
+}
+int ish_sweep_batch(void* h, int pairwise, int n_images, const float* d_big, const int32_t* d_seg, const float* road,
+                    const float* sets, int n_sets, int with_instances, void* stream) {
+    return guard([&] {
+        const std::vector<Stixels::RoadParameters> rp = to_road(road, n_images > 0 ? n_images : 0);
+        ((Stixels*)h)->SweepBatch(pairwise != 0, n_images, d_big, d_seg, rp.data(), to_sets(sets, n_sets), stream,
+                                  with_instances != 0);
+    });
+}
+int ish_select_sweep_set(void* h, int k) {
+    return guard([&] { ((Stixels*)h)->SelectSweepSet(k); });
+}
+/* frames of the last compute call the consumers can read; sets of the last sweep (0: not a sweep); the device of
+ * the object's buffers (-1 before Initialize); each < -1 on a null handle */
+static int handle_query(void* h, int (*f)(Stixels*)) {
+    int v = 0;
+    const int rc = guard([&] {
+        if (!h) throw std::invalid_argument("null handle");
+        v = f((Stixels*)h);
+    });
+    return rc ? rc - 1 : v;
+}
+int ish_last_frames(void* h) { return handle_query(h, [](Stixels* s) { return s->LastFrames(); }); }
+int ish_sweep_sets(void* h) { return handle_query(h, [](Stixels* s) { return s->SweepSets(); }); }
+int ish_active_device(void* h) { return handle_query(h, [](Stixels* s) { return s->GetActiveDevice(); }); }
+/* SweepSections(k): sections [frames][realcols*max_sections], vhor_lib and alpha_ground [frames]; triples (optional):
+ * [frames][cap][3], counts [frames], as ish_compute_batch */
+int ish_sweep_sections(void* h, int k, Section* sections, int* vhor_lib, float* alpha_ground, int* triples, int cap,
+                       int* counts) {
+    return guard([&] {
+        std::vector<StixelsData> out;
+        std::vector<Stixels::InstanceMapping> maps;
+        ((Stixels*)h)->SweepSections(k, out, triples ? &maps : nullptr);
+        for (size_t i = 0; i < out.size(); i++) {
+            std::memcpy(sections + i * out[i].sections.size(), out[i].sections.data(),
+                        out[i].sections.size() * sizeof(Section));
+            vhor_lib[i] = out[i].vhor;
+            alpha_ground[i] = out[i].alpha_ground;
+        }
+        if (triples) copy_maps(maps, triples, cap, counts);
+    });
+}
+/* ReclusterBatch(): triples (optional): [n_frames][cap][3], counts [n_frames], n_frames = ish_last_frames() */
+int ish_recluster_batch(void* h, float eps, int min_pts, int size_filter, int n_frames, int* triples, int cap, int* counts,
+                        void* stream) {
+    return guard([&] {
+        Stixels* s = (Stixels*)h;
+        if (triples && n_frames != s->LastFrames())
+            throw std::invalid_argument("ish_recluster_batch: n_frames differs from the frames of the last compute call");
+        std::vector<Stixels::InstanceMapping> maps;
+        s->ReclusterBatch(eps, min_pts, size_filter, triples ? &maps : nullptr, stream);
+        if (triples) copy_maps(maps, triples, cap, counts);
+    });
 }
 
 int ish_set_device(void* h, int device) {
