@@ -95,6 +95,12 @@ struct StixelsBuffers {
      * on first use, grown on demand */
     DeviceArray<Section> d_sweep_stixels;
     DeviceArray<char> d_sweep_instances;
+    /* ClusterInstanceDisparityBatch: the core's scratch, the two images of a call whose inputs are host arrays, and
+     * [max_batch] key counts | the stixel medians of the batch (device and pinned host; allocated on first use) */
+    DeviceArray<char> d_idisp_scratch;
+    DeviceArray<char> d_idisp_inputs;
+    DeviceArray<char> d_idisp_out;
+    PinnedArray<char> h_idisp_out;
     void release_all() { /* in the order of the declarations */
         d_disparity.release(); d_disparity_big.release(); d_segmentation.release(); d_instance_centerofmass.release();
         d_instance_indices.release(); d_instance_core_candidates.release(); d_instance_labels.release();
@@ -107,10 +113,11 @@ struct StixelsBuffers {
         d_overlap_packed.release(); d_overlap_header.release(); h_overlap_header.release(); h_overlap_packed.release();
         d_world_counts.release(); d_world_offsets.release(); d_world_totals.release(); d_world.release();
         h_world_totals.release(); h_world.release(); d_objects_block.release(); h_objects_block.release();
-        d_sweep_stixels.release(); d_sweep_instances.release();
+        d_sweep_stixels.release(); d_sweep_instances.release(); d_idisp_scratch.release(); d_idisp_inputs.release();
+        d_idisp_out.release(); h_idisp_out.release();
     }
 };
-static_assert(sizeof(StixelsBuffers) == 42 * sizeof(DeviceArray<char>), "release_all() must release every array");
+static_assert(sizeof(StixelsBuffers) == 46 * sizeof(DeviceArray<char>), "release_all() must release every array");
 
 class Stixels : private StixelsBuffers {
 public:
@@ -343,6 +350,27 @@ public:
      * instances. */
     void ReclusterBatch(float eps, int min_pts, int size_filter, std::vector<InstanceMapping>* instance_stixels = nullptr,
                         void* stream = nullptr);
+    /* f10 (an addition): the instance ids of frames 0 .. n_images-1 of the last compute call -- or of the selected set
+     * of a sweep -- by the size-filtered DBSCAN over (instance_mean_x, instance_mean_y, instance disparity), the
+     * reference tooling's --use-disparity from_gt, as is_cluster_instance_disparity defines every step: the median
+     * disparity of every ground-truth instance, its median over every instance-class stixel, and the clustering in
+     * which the stixels whose median is 0 take no part.  gt_instance [n][rows][cols] int32 (Cityscapes instanceIds)
+     * and disparity_u8 [n][rows][cols] uint8 are device arrays, or host arrays with inputs_on_host (copied into the
+     * object's own buffers).  The labels of the frames are rewritten as ReclusterBatch rewrites them, so
+     * GetInstanceStixels, RenderBatch, InstanceOverlapBatch, WorldBatch* and InstanceObjectsBatch* see them; an active
+     * ground-truth map ends.  `instance_stixels`, when given, receives the mappings; `stixel_median`, when given, is a
+     * host array [n_images][realcols][max_sections] that receives every stixel's median.  The call synchronises once
+     * (it reads the frames' key counts).  Throws std::invalid_argument under RenderBatch's rules and after a compute
+     * call without instances, and std::runtime_error, with every label unchanged, when a frame holds more
+     * ground-truth instances than SetInstanceDisparityCapacity allows. */
+    void ClusterInstanceDisparityBatch(int n_images, const int32_t* gt_instance, const uint8_t* disparity_u8, float eps,
+                                       int min_pts, int size_filter,
+                                       std::vector<InstanceMapping>* instance_stixels = nullptr,
+                                       float* stixel_median = nullptr, void* stream = nullptr,
+                                       bool inputs_on_host = false);
+    /* Ground-truth instances (keys) per frame ClusterInstanceDisparityBatch has histogram slots for, 1 KiB each
+     * (default 256); throws std::invalid_argument outside [1, IS_INSTANCE_DISPARITY_KEYS]. */
+    void SetInstanceDisparityCapacity(int keys_per_frame);
     /* frames of the last compute call the consumers can read (0: none) */
     int LastFrames() const { return m_last.frames; }
     /* sets of the last SweepBatch while it is what the consumers read (0: the last compute call was not a sweep) */
@@ -442,6 +470,7 @@ private:
     bool m_gt_is_train_ids = false;
     int m_overlap_capacity = 4096; /* records per frame of InstanceOverlapBatch's first pass */
     int m_world_capacity = 0;      /* records per frame of SetWorldCapacity; 0: not set */
+    int m_idisp_capacity = 256;    /* keys per frame of ClusterInstanceDisparityBatch */
     /* InstanceObjectsBatch: objects per frame of the first pass, the capacities d_objects_block was laid out for */
     int m_object_capacity = 64;
     size_t m_objects_cap = 0, m_object_points_cap = 0;

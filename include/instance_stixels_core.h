@@ -546,6 +546,77 @@ int is_assign_instances_gt(const is_assign_gt_args* args, void* stream);
 int is_pack_section_labels(const int32_t* d_section_instance, int n_images, int realcols, int max_sections,
                            int capacity, int32_t* d_packed, void* stream);
 
+/* ---- f10: instance ids by clustering in (x, y, instance disparity) (is_k_instance_disparity.hip) -----------------
+ * Replaces the third way the reference's evaluation tooling gives a stixel its instance id: --use-disparity from_gt
+ * of tools/visualization/clustering_visualization.py, its "what if depth separated the instances" row between the
+ * CNN-offset clustering (is_recluster) and the ground-truth upper bound (is_assign_instances_gt).  Per frame, with
+ * w = cols / realcols (integer division):
+ *   1. instance medians (compute_instance_disparity :1024-1049 over the masks of load_instance_mask,
+ *      cityscapes_instance_loader.py:32-71): a ground-truth pixel id has a key when id > 1000 and id / 1000 is one of
+ *      the Cityscapes labelIds 24, 25, 26, 27, 28, 31, 32, 33 (classes 11..18); key = class index * 1000 + id % 1000,
+ *      8 * 1000 of them, and instance number 0 (labelId * 1000) is a key like any other.  The median of a key is
+ *      np.median of the NON-ZERO disparity_u8 values under its pixels -- the two middle values of an even count
+ *      averaged, so an integer number of half units in [2, 510] -- or 0 where it has none.  Every other pixel has no
+ *      key and the instance disparity 0.
+ *   2. stixel medians (add_instance_disparity :996-1022): for a section in front of its column's terminator with
+ *      semantic class 11..18, over the rectangle of is_assign_instances_gt (image rows rows-1-vT .. rows-1-vB, image
+ *      columns column*w .. column*w + w-1, clipped to the frame), the median of the pixels' instance disparities that
+ *      are not < 1, the middle pair averaged: an integer number of quarter units, exact in fp32; 0 where nothing is
+ *      left, for an empty rectangle, and for every other slot.
+ *   3. clustering (get_disparity_instance_centers :794-819, assign_instances :894-960 with use_instance_disparity):
+ *      per class, the points are the candidates whose stixel median is not 0, in candidate order; the others take no
+ *      part -- they do not count towards #large > min_pts, are never core or neighbour, and get the label -1.  Over
+ *      the points the rules of is_cluster_instances hold with dx*dx + dy*dy + dz*dz (fp32, no contraction, z the stixel
+ *      median) against eps*eps; the core-candidate flag is (vT + 1 - vB) >= size_filter, derived as is_recluster does.
+ * d_labels, d_core_candidates and d_packed (where given) of every frame are rewritten exactly as is_recluster
+ * rewrites them.  from_pred of the reference (a file layout it no longer writes) has no counterpart.
+ *
+ * The keys of a frame are found first and ranked to `capacity` histogram slots of 1 KiB.  A frame with more keys than
+ * that is never truncated: the call then changes NO frame's labels, flags or triples, and d_key_count reports the
+ * frame's TRUE count (> capacity), which is how the caller learns of it (the call itself is asynchronous); the
+ * per-key and per-stixel outputs are unspecified then.
+ *
+ * Zero-initialise before setting fields.  All device arrays are on the current device.
+ *   d_sections, n_images, realcols, max_sections, rows, cols   as in is_render_args; n_images <= 65535,
+ *                       rows * ceil(cols / 8), rows * (cols / realcols) and n_images * ceil(realcols / 4) fit 31 bits
+ *   d_gt_instance       [n_images][rows][cols] int32, as is_assign_instances_gt takes it (4-byte aligned)
+ *   d_disparity_u8      [n_images][rows][cols] uint8: what cv2.imread(path, IMREAD_GRAYSCALE) returns (:1074-1075)
+ *                       (with cols % 8 == 0, a 16-byte aligned d_gt_instance and an 8-byte aligned d_disparity_u8 the
+ *                       images are read with vector loads)
+ *   instances           host [n_images], read before the call returns: every frame needs d_indices, d_centerofmass,
+ *                       d_core_candidates, d_instances_per_class and d_labels; d_packed is optional
+ *   eps, min_pts, size_filter   the clustering parameters; eps finite, min_pts >= 1
+ *   capacity            histogram slots per frame, in [1, IS_INSTANCE_DISPARITY_KEYS]
+ *   d_scratch           16-byte aligned, scratch_bytes >= is_instance_disparity_scratch_bytes(n_images, realcols,
+ *                       max_sections, capacity); its contents mean nothing between calls
+ *   d_stixel_median     optional, [n_images][realcols][max_sections] float: step 2, every slot written
+ *   d_key_count         optional, [n_images] int32: the distinct keys of every frame
+ *   d_key_median        optional, [n_images][IS_INSTANCE_DISPARITY_KEYS] uint16: step 1 in half units, 0 for a key
+ *                       that is absent or has no non-zero disparity */
+#define IS_INSTANCE_DISPARITY_KEYS 8000
+typedef struct is_instance_disparity_args {
+    const is_section* d_sections;
+    const int32_t* d_gt_instance;
+    const uint8_t* d_disparity_u8;
+    int n_images, rows, cols, realcols, max_sections;
+    const is_instance_buffers* instances;
+    float eps;
+    int min_pts, size_filter, capacity;
+    void* d_scratch;
+    size_t scratch_bytes;
+    float* d_stixel_median;
+    int32_t* d_key_count;
+    uint16_t* d_key_median;
+} is_instance_disparity_args;
+
+/* Bytes of d_scratch for a call of that shape (0 for a shape or capacity the call refuses). */
+size_t is_instance_disparity_scratch_bytes(int n_images, int realcols, int max_sections, int capacity);
+/* The labels of n_images frames on `stream`, asynchronously and stream-ordered: one memset and six kinds of launch
+ * (one clustering launch per 32 frames), no allocation, copy or synchronisation.  IS_EINVAL, with the reason in
+ * is_last_error() and before any device call, for a null argument, a capacity outside its range, an eps that is not
+ * finite, min_pts < 1, and for the shape, alignment and scratch constraints above. */
+int is_cluster_instance_disparity(const is_instance_disparity_args* args, void* stream);
+
 /* ---- f9: per-instance objects and their contours (is_k_objects.hip) ------------------------------------------------
  * What the reference's consumers reduce on the host from the per-stixel output: the top-down view
  * (tools/visualization/clustering_visualization.py:563-792: per instance and column the closest stixel, connected

@@ -36,6 +36,7 @@ EXPORTS = [
     "is_assign_instances_gt", "is_pack_section_labels",
     "is_instance_objects",
     "is_compute_sweep", "is_recluster",
+    "is_cluster_instance_disparity", "is_instance_disparity_scratch_bytes",
 ]
 RENDER_MAX_LABELS = 64    # IS_RENDER_MAX_LABELS
 RENDER_MAX_CLASSES = 256  # IS_RENDER_MAX_CLASSES
@@ -137,6 +138,18 @@ class InstanceObjectsArgs(ctypes.Structure):
                 ("d_totals", vp)]
 
 
+INSTANCE_DISPARITY_KEYS = 8000  # IS_INSTANCE_DISPARITY_KEYS
+
+
+class InstanceDisparityArgs(ctypes.Structure):
+    """is_instance_disparity_args: zero-initialised by ctypes; device pointers as ints, instances a host pointer."""
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    _fields_ = [("d_sections", vp), ("d_gt_instance", vp), ("d_disparity_u8", vp), ("n_images", ci), ("rows", ci),
+                ("cols", ci), ("realcols", ci), ("max_sections", ci), ("instances", vp), ("eps", ctypes.c_float),
+                ("min_pts", ci), ("size_filter", ci), ("capacity", ci), ("d_scratch", vp),
+                ("scratch_bytes", ctypes.c_size_t), ("d_stixel_median", vp), ("d_key_count", vp), ("d_key_median", vp)]
+
+
 class CoreError(RuntimeError):
     pass
 
@@ -195,6 +208,9 @@ def lib():
         L.is_instance_objects.argtypes = [ctypes.POINTER(InstanceObjectsArgs), vp]
         L.is_compute_sweep.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, ci, vp, vp, vp]
         L.is_recluster.argtypes = [vp, vp, ci, cf, ci, ci, vp, vp]
+        L.is_cluster_instance_disparity.argtypes = [ctypes.POINTER(InstanceDisparityArgs), vp]
+        L.is_instance_disparity_scratch_bytes.argtypes = [ci, ci, ci, ci]
+        L.is_instance_disparity_scratch_bytes.restype = ctypes.c_size_t
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
         L.is_get_device.argtypes = [ctypes.POINTER(ci)]
@@ -595,6 +611,22 @@ def pack_section_labels_ptr(d_section_instance, n_images, realcols, max_sections
     _check(lib().is_pack_section_labels(d_section_instance, int(n_images), int(realcols), int(max_sections),
                                         int(capacity), d_packed, ctypes.c_void_p(int(stream))),
            "is_pack_section_labels")
+
+
+def instance_disparity_scratch_bytes(n_images, realcols, max_sections, capacity):
+    """is_instance_disparity_scratch_bytes: the scratch a call of that shape needs (0: a shape the call refuses)."""
+    return int(lib().is_instance_disparity_scratch_bytes(int(n_images), int(realcols), int(max_sections),
+                                                         int(capacity)))
+
+
+def cluster_instance_disparity_ptr(instances, stream=0, **fields):
+    """is_cluster_instance_disparity on raw device pointers (ints): fields are those of InstanceDisparityArgs except
+    `instances`, a sequence of n_images InstanceBuffers.  Asynchronous on `stream`; returns the return code and raises
+    nothing (the tests check IS_EINVAL)."""
+    a = InstanceDisparityArgs(**fields)
+    arr = (InstanceBuffers * max(len(instances), 1))(*instances)
+    a.instances = ctypes.cast(arr, ctypes.c_void_p)
+    return lib().is_cluster_instance_disparity(ctypes.byref(a), ctypes.c_void_p(int(stream)))
 
 
 def instance_objects_ptr(stream=0, **fields):

@@ -818,6 +818,48 @@ int is_pack_section_labels(const int32_t* d_section_instance, int n_images, int 
     return IS_OK;
 }
 
+/* ---- f10: clustering in (x, y, instance disparity) (is_k_instance_disparity.hip) ---- */
+static const char* instance_disparity_fault(const is_instance_disparity_args* a) {
+    if (!a) return "null args";
+    if (!a->d_sections || !a->d_gt_instance || !a->d_disparity_u8) return "null sections, gt or disparity";
+    if (!a->instances || !a->d_scratch) return "null instances or scratch";
+    if (a->capacity < 1 || a->capacity > IS_INSTANCE_DISPARITY_KEYS)
+        return "capacity outside [1, IS_INSTANCE_DISPARITY_KEYS]";
+    if (!(a->eps - a->eps == 0.0f)) return "eps is not finite";
+    if (a->min_pts < 1) return "min_pts < 1";
+    if (const char* fault = geometry_fault(a, a->n_images > 65535 ? "n_images outside [1, 65535]" : nullptr)) return fault;
+    if ((long long)a->realcols * a->max_sections > 0x7fffffffLL) return "realcols * max_sections does not fit 31 bits";
+    if ((long long)a->rows * ((a->cols + 7) / 8) > 0x7fffffffLL || (long long)a->rows * (a->cols / a->realcols) > 0x7fffffffLL)
+        return "rows * ceil(cols / 8) or rows * (cols / realcols) does not fit 31 bits";
+    if ((long long)a->n_images * ((a->realcols + 3) / 4) > 0x7fffffffLL) return "batch too large for one launch";
+    if (misaligned(16, a->d_sections, a->d_scratch)) return "d_sections and d_scratch must be 16-byte aligned";
+    if (misaligned(4, a->d_gt_instance, a->d_stixel_median, a->d_key_count))
+        return "d_gt_instance, d_stixel_median and d_key_count must be 4-byte aligned";
+    if (misaligned(2, a->d_key_median)) return "d_key_median must be 2-byte aligned";
+    if (a->scratch_bytes < isk_instance_disparity_scratch_bytes(a->n_images, a->realcols, a->max_sections, a->capacity))
+        return "scratch_bytes below is_instance_disparity_scratch_bytes()";
+    for (int i = 0; i < a->n_images; i++) {
+        const is_instance_buffers& ib = a->instances[i];
+        if (!ib.d_indices || !ib.d_centerofmass || !ib.d_core_candidates || !ib.d_instances_per_class || !ib.d_labels)
+            return "d_indices, d_centerofmass, d_core_candidates, d_instances_per_class and d_labels are required for "
+                   "every image";
+    }
+    return nullptr;
+}
+
+size_t is_instance_disparity_scratch_bytes(int n_images, int realcols, int max_sections, int capacity) {
+    if (n_images < 1 || n_images > 65535 || realcols < 1 || max_sections < 1 || max_sections > 32767 || capacity < 1 ||
+        capacity > IS_INSTANCE_DISPARITY_KEYS || (long long)realcols * max_sections > 0x7fffffffLL)
+        return 0;
+    return isk_instance_disparity_scratch_bytes(n_images, realcols, max_sections, capacity);
+}
+
+int is_cluster_instance_disparity(const is_instance_disparity_args* a, void* stream) {
+    if (const char* fault = instance_disparity_fault(a)) return fail_arg(fault);
+    HIP_TRY(isk_launch_instance_disparity(a, (hipStream_t)stream));
+    return IS_OK;
+}
+
 /* ---- f9: per-instance objects and contours (is_k_objects.hip) ---- */
 int is_instance_objects(const is_instance_objects_args* a, void* stream) {
     if (!a) return fail_arg("null args");

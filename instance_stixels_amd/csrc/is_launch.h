@@ -217,6 +217,10 @@ hipError_t isk_launch_assign_gt(const is_assign_gt_args* r, const int* label_ids
 hipError_t isk_launch_pack_section_labels(const int32_t* map, int n_images, int realcols, int max_sections,
                                           int capacity, int32_t* packed, hipStream_t stream);
 
+/* is_k_instance_disparity.hip */
+size_t isk_instance_disparity_scratch_bytes(int n_images, int realcols, int max_sections, int capacity);
+hipError_t isk_launch_instance_disparity(const is_instance_disparity_args* r, hipStream_t stream);
+
 /* is_k_objects.hip */
 hipError_t isk_launch_instance_objects(const is_instance_objects_args* r, hipStream_t stream);
 

@@ -254,3 +254,20 @@ def sweep_scores(st, sets, gt_label, gt_instance, n_labels=CITYSCAPES_N_LABELS, 
         overlaps = None if gt_instance is None else st.InstanceOverlapBatch(frames, gt_instance, stream=stream)
         out.append(dict(confusion=conf.cpu().numpy().astype(np.uint64), stixel_count=count, overlaps=overlaps))
     return out
+
+
+def instance_disparity_scores(st, gt_instance, disparity_u8, eps, min_pts, size_filter, evaluator=None, stream=0):
+    """The instance AP of the last compute call of `st` (a host.Stixels; or of its selected sweep set) with the
+    instance ids of the reference's --use-disparity from_gt clustering, without a per-frame loop:
+    ClusterInstanceDisparityBatch over (instance_mean_x, instance_mean_y, instance disparity), then
+    InstanceOverlapBatch against the same ground truth, then CityscapesInstanceEval.  gt_instance: device int32
+    [frames][rows][cols] (a pointer as int); disparity_u8: device uint8 of the same shape.  evaluator: a
+    CityscapesInstanceEval to add the frames to (one is made otherwise).  Returns dict(overlaps = the per-frame tables,
+    result = evaluator.result()); the labels stay on the device for RenderBatch / WorldBatch / InstanceObjectsBatch."""
+    frames = st.LastFrames()
+    st.ClusterInstanceDisparityBatch(frames, gt_instance, disparity_u8, eps, min_pts, size_filter, with_mapping=False,
+                                     stream=stream)
+    overlaps = st.InstanceOverlapBatch(frames, gt_instance, stream=stream)
+    ev = evaluator if evaluator is not None else CityscapesInstanceEval()
+    ev.add(overlaps)
+    return dict(overlaps=overlaps, result=ev.result())

@@ -36,6 +36,7 @@ EXPORTS = [
     "ish_assign_instances_gt_batch", "ish_assign_instances_gt_quads", "ish_use_cluster_instances", "ish_set_gt_assignment_parameters",
     "ish_core_sweep_set", "ish_sweep_batch", "ish_select_sweep_set", "ish_last_frames", "ish_sweep_sets",
     "ish_active_device", "ish_sweep_sections", "ish_recluster_batch",
+    "ish_cluster_instance_disparity_batch", "ish_set_instance_disparity_capacity",
 ]
 WORLD_DTYPE = _core.WORLD_DTYPE  # is_world_stixel, the records of Stixels.WorldBatch
 OBJECT_DTYPE = _core.OBJECT_DTYPE    # is_instance_object, the objects of Stixels.InstanceObjectsBatch
@@ -137,6 +138,8 @@ def lib():
         L.ish_active_device.argtypes = [vp]
         L.ish_sweep_sections.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp]
         L.ish_recluster_batch.argtypes = [vp, cf, ci, ci, ci, vp, ci, vp, vp]
+        L.ish_cluster_instance_disparity_batch.argtypes = [vp, ci, vp, vp, ci, cf, ci, ci, vp, ci, vp, vp, vp]
+        L.ish_set_instance_disparity_capacity.argtypes = [vp, ci]
         _LIB = L
     return _LIB
 
@@ -481,6 +484,48 @@ class Stixels:
                                               tri.ctypes.data if with_mapping else None, cap, cnt.ctypes.data,
                                               stream), "ReclusterBatch")
         return _maps(tri, cnt[:n]) if with_mapping else None
+
+    def ClusterInstanceDisparityBatch(self, n, gt_instance, disparity_u8, eps, min_pts, size_filter, with_mapping=True,
+                                      with_stixel_median=False, stream=0):
+        """Stixels::ClusterInstanceDisparityBatch: the instance ids of frames 0 .. n-1 of the last compute call (or of
+        the selected sweep set) by DBSCAN over (instance_mean_x, instance_mean_y, instance disparity), the reference
+        tooling's --use-disparity from_gt.  gt_instance (int32 [n][rows][cols], Cityscapes instanceIds) and
+        disparity_u8 (uint8 [n][rows][cols]) are both numpy arrays, copied to the device by the call, or both device
+        pointers (ints) of resident arrays.  The labels are rewritten as ReclusterBatch rewrites them.  Returns
+        (mappings or None, stixel medians float32 [n][realcols][max_sections] or None).  ValueError before any compute
+        call and after one without instances; RuntimeError, with every label unchanged, when a frame holds more
+        ground-truth instances than SetInstanceDisparityCapacity allows."""
+        n = int(n)
+        on_host = isinstance(gt_instance, np.ndarray)
+        if on_host != isinstance(disparity_u8, np.ndarray):
+            raise ValueError("ClusterInstanceDisparityBatch: gt_instance and disparity_u8 must both be numpy arrays "
+                             "or both be device pointers")
+        if on_host:
+            px = max(n, 0) * int(self._cfg.rows) * int(self._cfg.cols)
+            gt_instance = np.ascontiguousarray(gt_instance, np.int32)
+            disparity_u8 = np.ascontiguousarray(disparity_u8, np.uint8)
+            if gt_instance.size < px or disparity_u8.size < px:
+                raise ValueError("ClusterInstanceDisparityBatch: an image array holds fewer than n frames")
+            gt_p, disp_p = gt_instance.ctypes.data, disparity_u8.ctypes.data
+        else:
+            gt_p = ctypes.c_void_p(int(gt_instance)) if gt_instance else None
+            disp_p = ctypes.c_void_p(int(disparity_u8)) if disparity_u8 else None
+        C, S = self.GetRealCols(), self.GetMaxSections()
+        cap = C * S
+        tri = np.zeros((max(n, 0), cap, 3), np.int32) if with_mapping else None
+        cnt = np.zeros(max(n, 1), np.int32)
+        med = np.zeros((max(n, 0), C, S), np.float32) if with_stixel_median else None
+        self._check(lib().ish_cluster_instance_disparity_batch(
+            self._h, n, gt_p, disp_p, int(on_host), float(eps), int(min_pts), int(size_filter),
+            tri.ctypes.data if with_mapping else None, cap, cnt.ctypes.data,
+            med.ctypes.data if with_stixel_median else None, ctypes.c_void_p(int(stream))),
+            "ClusterInstanceDisparityBatch")
+        return (_maps(tri, cnt[:n]) if with_mapping else None), med
+
+    def SetInstanceDisparityCapacity(self, keys_per_frame):
+        """Ground-truth instances per frame ClusterInstanceDisparityBatch has histogram slots for (default 256)."""
+        self._check(lib().ish_set_instance_disparity_capacity(self._h, int(keys_per_frame)),
+                    "SetInstanceDisparityCapacity")
 
     def UseClusterInstances(self):
         """Back to the cluster labels of the last compute call for RenderBatch / InstanceOverlapBatch / WorldBatch."""

@@ -1234,6 +1234,69 @@ void Stixels::ReclusterBatch(float eps, int min_pts, int size_filter, std::vecto
     if (instance_stixels) FetchInstanceMappings(ibs, *instance_stixels, stream);
 }
 
+void Stixels::SetInstanceDisparityCapacity(int keys_per_frame) {
+    if (keys_per_frame < 1 || keys_per_frame > IS_INSTANCE_DISPARITY_KEYS)
+        throw std::invalid_argument("SetInstanceDisparityCapacity: keys_per_frame outside [1, IS_INSTANCE_DISPARITY_KEYS].");
+    m_idisp_capacity = keys_per_frame;
+}
+
+/* Replaces --use-disparity from_gt of the reference tooling (clustering_visualization.py:794-819, 894-960, 996-1049)
+ * for a batch. */
+void Stixels::ClusterInstanceDisparityBatch(int n_images, const int32_t* gt_instance, const uint8_t* disparity_u8,
+                                            float eps, int min_pts, int size_filter,
+                                            std::vector<InstanceMapping>* instance_stixels, float* stixel_median,
+                                            void* stream, bool inputs_on_host) {
+    const ConsumerScope scope = BeginConsumer("ClusterInstanceDisparityBatch", "clusters", n_images, stream);
+    if (!m_last.cluster_instances)
+        throw std::invalid_argument("ClusterInstanceDisparityBatch: needs a compute call with instances.");
+    if (gt_instance == nullptr || disparity_u8 == nullptr)
+        throw std::invalid_argument("ClusterInstanceDisparityBatch: null gt_instance or disparity_u8.");
+    const size_t cs = (size_t)m_realcols * m_max_sections, px = (size_t)n_images * m_rows * m_cols;
+    if (inputs_on_host) { /* gt | disparity, each 16-byte aligned */
+        const size_t gt_bytes = (px * sizeof(int32_t) + 15) & ~(size_t)15;
+        d_idisp_inputs.reserve(gt_bytes + px);
+        IS_CHECK_RETURN(is_memcpy_h2d(d_idisp_inputs.get(), gt_instance, px * sizeof(int32_t), stream));
+        IS_CHECK_RETURN(is_memcpy_h2d(d_idisp_inputs.get() + gt_bytes, disparity_u8, px, stream));
+        IS_CHECK_RETURN(is_stream_synchronize(stream)); /* (the caller's arrays are free again on every way out) */
+        gt_instance = (const int32_t*)d_idisp_inputs.get();
+        disparity_u8 = (const uint8_t*)(d_idisp_inputs.get() + gt_bytes);
+    }
+    std::vector<is_instance_buffers> ibs;
+    for (int i = 0; i < n_images; i++) ibs.push_back(LastInstanceBuffers(i));
+    const size_t counts_bytes = ((size_t)m_max_batch * sizeof(int32_t) + 15) & ~(size_t)15;
+    const size_t out_bytes = counts_bytes + (stixel_median ? (size_t)n_images * cs * sizeof(float) : 0);
+    d_idisp_out.reserve(out_bytes);
+    h_idisp_out.reserve(out_bytes);
+    is_instance_disparity_args a = {};
+    FillGeometry(a, n_images);
+    a.d_gt_instance = gt_instance;
+    a.d_disparity_u8 = disparity_u8;
+    a.instances = ibs.data();
+    a.eps = eps;
+    a.min_pts = min_pts;
+    a.size_filter = size_filter;
+    a.capacity = m_idisp_capacity;
+    a.scratch_bytes = is_instance_disparity_scratch_bytes(n_images, m_realcols, m_max_sections, m_idisp_capacity);
+    d_idisp_scratch.reserve(std::max<size_t>(a.scratch_bytes, 16));
+    a.d_scratch = d_idisp_scratch.get();
+    a.d_key_count = (int32_t*)d_idisp_out.get();
+    if (stixel_median) a.d_stixel_median = (float*)(d_idisp_out.get() + counts_bytes);
+    CheckConsumer("ClusterInstanceDisparityBatch", is_cluster_instance_disparity(&a, stream));
+    IS_CHECK_RETURN(is_memcpy_d2h(h_idisp_out.get(), d_idisp_out.get(), out_bytes, stream));
+    IS_CHECK_RETURN(is_stream_synchronize(stream));
+    const int32_t* keys = (const int32_t*)h_idisp_out.get();
+    for (int i = 0; i < n_images; i++)
+        if (keys[i] > m_idisp_capacity)
+            throw std::runtime_error("ClusterInstanceDisparityBatch: frame " + std::to_string(i) + " holds " +
+                                     std::to_string(keys[i]) + " ground-truth instances, the capacity is " +
+                                     std::to_string(m_idisp_capacity) +
+                                     " (SetInstanceDisparityCapacity); no label was changed.");
+    if (stixel_median) std::memcpy(stixel_median, h_idisp_out.get() + counts_bytes, (size_t)n_images * cs * sizeof(float));
+    m_last.gt_instances = false; /* (as ReclusterBatch) */
+    m_labels_on_host = false;
+    if (instance_stixels) FetchInstanceMappings(ibs, *instance_stixels, stream);
+}
+
 /* The shard of this rank, then the compacted gather of every rank's Sections on `dst` (the
  * C ABI underneath: is_pack_sections -> is_gather_sections -> is_unpack_sections). */
 void Stixels::ComputeBatchGather(bool pairwise, int n_images, const pixel_t* d_big, const int32_t* d_seg,

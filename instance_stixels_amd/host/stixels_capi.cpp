@@ -504,6 +504,23 @@ int ish_recluster_batch(void* h, float eps, int min_pts, int size_filter, int n_
     });
 }
 
+/* ClusterInstanceDisparityBatch(): gt_instance / disparity_u8 device arrays, or host arrays with inputs_on_host;
+ * triples (optional): [n][cap][3], counts [n]; stixel_median (optional): host [n][realcols][max_sections] */
+int ish_cluster_instance_disparity_batch(void* h, int n, const int32_t* gt_instance, const uint8_t* disparity_u8,
+                                         int inputs_on_host, float eps, int min_pts, int size_filter, int* triples,
+                                         int cap, int* counts, float* stixel_median, void* stream) {
+    return guard([&] {
+        std::vector<Stixels::InstanceMapping> maps;
+        ((Stixels*)h)->ClusterInstanceDisparityBatch(n, gt_instance, disparity_u8, eps, min_pts, size_filter,
+                                                     triples ? &maps : nullptr, stixel_median, stream,
+                                                     inputs_on_host != 0);
+        if (triples) copy_maps(maps, triples, cap, counts);
+    });
+}
+int ish_set_instance_disparity_capacity(void* h, int keys_per_frame) {
+    return guard([&] { ((Stixels*)h)->SetInstanceDisparityCapacity(keys_per_frame); });
+}
+
 int ish_set_device(void* h, int device) {
     return guard([&] { ((Stixels*)h)->SetDevice(device); });
 }
