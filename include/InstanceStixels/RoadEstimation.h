@@ -61,6 +61,17 @@ public:
      * single-frame getters (GetPitch() ...) are left as they are. */
     void ComputeBatch(const pixel_t* d_disparity, int n_images, Stixels::RoadParameters* out, uint8_t* ok,
                       void* stream = nullptr);
+    /* The same estimation with the line choice on the device and NOTHING returned to the host (an addition):
+     * v-disparity, Hough transform and is_road_choose_batch are queued on `stream`; no copy, no synchronisation.
+     *   d_road   [n_images] Stixels::RoadParameters, d_status [n_images] uint8 (IS_ROAD_* of
+     *            instance_stixels_core.h), both on the object's device: what Stixels::ComputeBatchRoad consumes
+     *   fallback the record of every frame whose status is not IS_ROAD_OK (no line, undecided, horizon outside
+     *            the image): the DP of such a frame then runs on defined numbers, and the status tells the caller
+     * The choice is ChooseLineShared's, bit for bit.  Against ComputeBatch: the same line, vhor and alpha; tilt
+     * within 1 ulp and height within 2 ulp (is_atanf / is_cosf in place of libm's).  An undecided frame
+     * (IS_ROAD_UNDECIDED: ComputeBatch would re-run HoughLines on its binary image) is reported, not finished. */
+    void ComputeBatchDevice(const pixel_t* d_disparity, int n_images, Stixels::RoadParameters* d_road,
+                            uint8_t* d_status, const Stixels::RoadParameters& fallback, void* stream = nullptr);
     /* Lines returned per frame (default 256) and local maxima kept per frame (default 4096, at most
      * IS_ROAD_MAX_CANDIDATES) by the device Hough transform of ComputeBatch. */
     void SetBatchLimits(int max_lines, int max_candidates);
@@ -79,7 +90,21 @@ public:
     static int ChooseLine(float camera_center_y, float baseline, float focal, int rows,
                           const std::pair<float, float>* lines, size_t n, Stixels::RoadParameters& out);
 
+    /* The host twin of is_road_choose_batch, without a device: ChooseLine with is_atanf / is_cosf of is_numerics.h
+     * in place of atanf / cosf(pitch), over the first min(total, max_lines) lines of `lines` [.][2] (rho, theta) as
+     * is_road_hough_batch leaves them, with the gate [min_pitch, max_pitch].  Returns the status (IS_ROAD_*) and
+     * sets out = the accepted line's record (IS_ROAD_OK) or `fallback`; *index (may be null) = the accepted
+     * line's index or -1.  A line whose theta is not 0.0f + n * (float)pi / 180 for 0 <= n < 180 is skipped. */
+    static int ChooseLineShared(float camera_center_y, float baseline, float focal, int rows, float min_pitch,
+                                float max_pitch, const float* lines, int total, int overflow, int max_lines,
+                                const Stixels::RoadParameters& fallback, Stixels::RoadParameters& out,
+                                int* index = nullptr);
+    /* the pitch gate of Initialize() (what ComputeBatchDevice passes) */
+    static void PitchGate(float& min_pitch, float& max_pitch);
+
 private:
+    /* the output blocks of the batched transforms for n_images frames (allocated on first need, grown on demand) */
+    void ReserveBatch(int n_images);
     /* the camera and the pitch gate of Initialize (everything the line choice reads) */
     void SetCamera(float camera_center_y, float baseline, float focal, int rows);
     void ComputeCameraProperties(int vdisp_rows, const float rho, const float theta,

@@ -101,6 +101,8 @@ struct StixelsBuffers {
     DeviceArray<char> d_idisp_inputs;
     DeviceArray<char> d_idisp_out;
     PinnedArray<char> h_idisp_out;
+    /* ComputeBatchRoad: [max_batch] RoadParameters | [max_batch] status bytes, the copy of the caller's device arrays */
+    PinnedArray<char> h_road;
     void release_all() { /* in the order of the declarations */
         d_disparity.release(); d_disparity_big.release(); d_segmentation.release(); d_instance_centerofmass.release();
         d_instance_indices.release(); d_instance_core_candidates.release(); d_instance_labels.release();
@@ -114,10 +116,10 @@ struct StixelsBuffers {
         d_world_counts.release(); d_world_offsets.release(); d_world_totals.release(); d_world.release();
         h_world_totals.release(); h_world.release(); d_objects_block.release(); h_objects_block.release();
         d_sweep_stixels.release(); d_sweep_instances.release(); d_idisp_scratch.release(); d_idisp_inputs.release();
-        d_idisp_out.release(); h_idisp_out.release();
+        d_idisp_out.release(); h_idisp_out.release(); h_road.release();
     }
 };
-static_assert(sizeof(StixelsBuffers) == 46 * sizeof(DeviceArray<char>), "release_all() must release every array");
+static_assert(sizeof(StixelsBuffers) == 47 * sizeof(DeviceArray<char>), "release_all() must release every array");
 
 class Stixels : private StixelsBuffers {
 public:
@@ -190,6 +192,32 @@ public:
                       const int32_t* d_segmentation, const RoadParameters* road,
                       std::vector<StixelsData>& out, void* stream = nullptr,
                       std::vector<InstanceMapping>* instance_stixels = nullptr);
+    /* ComputeBatch with the road parameters left on the device (an addition): d_road [n_images] RoadParameters and
+     * d_status [n_images] uint8, device, e.g. as RoadEstimation::ComputeBatchDevice queued them on the same stream.
+     * The ground model of every frame is built on the device (is_compute_road) -- nothing is computed per row on the
+     * host, and the chain disparity -> lines -> road -> ground model -> DP has no synchronisation before the one
+     * that delivers the Sections.  d_road and d_status come back in one small pinned copy behind the DP: the header
+     * of every StixelsData and every consumer of the batch (RenderBatch, WorldBatch, ...) take alpha_ground and vhor
+     * from it; road_out / status_out (optional) receive them.  A frame whose status is not IS_ROAD_OK was computed
+     * with the fallback record ComputeBatchDevice put in its place.
+     * The ground model is PrecomputeGroundShared's, bit for bit: is_erff in place of erff, everything else as
+     * PrecomputeGround (DESIGN.md 10j states the distance to ComputeBatch). */
+    void ComputeBatchRoad(bool pairwise, int n_images, const pixel_t* d_disparity_big, const int32_t* d_segmentation,
+                          const RoadParameters* d_road, const uint8_t* d_status, std::vector<StixelsData>& out,
+                          void* stream = nullptr, std::vector<InstanceMapping>* instance_stixels = nullptr,
+                          std::vector<RoadParameters>* road_out = nullptr,
+                          std::vector<uint8_t>* status_out = nullptr);
+    /* The host twin of the device ground model (k_ground_model), without a device: PrecomputeGround with is_erff of
+     * is_numerics.h in place of erff and the FastLog index clamped to the table, row for row is_ground_row of
+     * is_ground_model.h.  function / normalization / inv_sigma2: [rows]; range_index (may be null): [rows], the
+     * FastLog index of the a_range term. */
+    static void PrecomputeGroundShared(const is_ground_params& g, const float* log_lut, int lut_entries, int rows,
+                                       int vhor_lib, float camera_tilt, float camera_height, float alpha_ground,
+                                       float* function, float* normalization, float* inv_sigma2,
+                                       int* range_index = nullptr);
+    /* the constants of the ground model as this object holds them, and its FastLog table (after PrecomputeHost()) */
+    is_ground_params GroundParams() const;
+    const std::vector<float>& GetLogLUT() const { return m_log_lut; }
     /* Multi-GPU (an addition: the reference runs on one GPU): this rank's shard of a batch through
      * ComputeBatch's device path, then the compacted final gather of EVERY rank's Sections on rank `dst` of
      * `comm` over RCCL (an ncclComm_t passed as void*; plain-C++ callers create it with is_comm_unique_id /
@@ -403,6 +431,11 @@ private:
     void ScatterSections(const int32_t* counts, const Section* packed, size_t total,
                          std::vector<StixelsData>& out) const;
     void ReservePackBuffers();
+    /* The second half of ComputeBatch and ComputeBatchRoad: the Sections of the batch in d_stixels (and the instance
+     * mappings) to the host.  `road` [n_images] is read behind the first synchronisation (ComputeBatchRoad passes
+     * the pinned copy queued in front); remember: that is also where the batch is recorded for the consumers. */
+    void DeliverBatch(int n_images, const RoadParameters* road, bool remember, std::vector<StixelsData>& out,
+                      void* stream, std::vector<InstanceMapping>* instance_stixels);
     is_instance_buffers InstanceBuffers(int image = 0) const;     /* the object's own arrays: what Compute* writes */
     is_instance_buffers LastInstanceBuffers(int image) const;     /* what the consumers read (a sweep: its selected set) */
     /* the instance arrays of frame `image` of set `set` inside d_sweep_instances */
@@ -457,6 +490,9 @@ private:
      * are 12 us of a 0.26 ms frame.  Invalidated by Initialize(). */
     float m_ground_key[12] = {0};  /* every input of PrecomputeGround */
     bool m_ground_valid = false;
+    /* ComputeBatchRoad: the smallest library-convention horizon of the last batch, is_compute_road's vhor_min_hint for
+     * the next one (-1: none yet) */
+    int m_road_vhor_hint = -1;
 
     /* device (owned between Initialize and Finish, Stixels.cu:53-74, 136-163) */
     is_ctx* m_ctx = nullptr;

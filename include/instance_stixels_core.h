@@ -172,6 +172,39 @@ int is_compute(is_ctx* ctx, const float* d_joined, const int32_t* d_segmentation
                int n_images, is_section* d_sections, const is_instance_buffers* instances,
                float* d_cost_table, int32_t* d_index_table, void* stream);
 
+/* ---- the ground model of a batch on the device (k_ground_model, is_k_ground.hip) -------------------------------
+ * The constants of Stixels::PrecomputeGround, as the host class holds them (sigma_camera_tilt in radians). */
+typedef struct is_road_params { /* one frame's road, the layout of Stixels::RoadParameters (16 bytes) */
+    int vhor;                   /* image-convention horizon row */
+    float tilt, height, alpha;  /* camera pitch and height, slope of the ground line in the v-disparity image */
+} is_road_params;
+typedef struct is_ground_params {
+    float focal, baseline;
+    float max_dis; /* (float)max_dis */
+    float pout;
+    float sigma_disparity_ground, sigma_camera_height, sigma_camera_tilt;
+} is_ground_params;
+
+/* Stores the constants and uploads the table Stixels::FastLog reads (h_log_lut [n_entries] float, n_entries >= 2:
+ * entry i = logf(i / (n_entries - 1)); the host class has 10^6 + 1) once per context; synchronous.  Needed before
+ * is_compute_road; may be called again. */
+int is_ctx_set_ground_model(is_ctx* ctx, const is_ground_params* params, const float* h_log_lut, int n_entries);
+
+/* is_compute with the ground model of every frame built on the device from d_road [n_images] (is_road_params, device;
+ * e.g. what is_road_choose_batch left): k_ground_model writes the context's ground arrays and horizons -- row for row
+ * is_ground_row of is_ground_model.h, i.e. Stixels::PrecomputeGroundShared, bitwise -- and then exactly the launches
+ * of is_compute follow.  Nothing of the ground model crosses the host; the instance table is staged as in is_compute.
+ *   vhor_min_hint   < 0: unknown; else a lower bound of the library-convention horizons (rows - vhor - 1) of the
+ *                   call.  Launch geometry only (how many pairwise tiles stage an fn window), never results.
+ * Every other argument and constraint as is_compute. */
+int is_compute_road(is_ctx* ctx, const float* d_joined, const int32_t* d_segmentation, const is_road_params* d_road,
+                    int pairwise, int n_images, is_section* d_sections, const is_instance_buffers* instances,
+                    float* d_cost_table, int32_t* d_index_table, int vhor_min_hint, void* stream);
+
+/* (tests) the ground model of frame `frame` of the last compute call as the DP kernels read it: h_out [3][rows]
+ * (function, normalization, inv_sigma2) and its library-convention horizon; synchronises the device. */
+int is_debug_read_ground(is_ctx* ctx, int frame, float* h_out, int* vhor);
+
 /* Replaces Stixels::ClusterInstances (Stixels.cu:639-681: one ML::dbscanFit per instance class
  * with the size filter of the cuML fork) for the candidates of ONE image (is_compute clusters a
  * whole batch in one launch): size-filtered DBSCAN
@@ -325,6 +358,33 @@ int is_road_vdisparity_batch(is_road_ctx* ctx, const float* d_disparity, int n_i
  *                   HoughLines (the sort saw only some of the maxima), else 0 */
 int is_road_hough_batch(is_road_ctx* ctx, int n_images, int threshold, int max_lines, int max_candidates,
                         float* d_lines, int* d_votes, int* d_total, int* d_overflow, void* stream);
+
+/* ---- the road parameters of a batch chosen on the device, and the ground model built from them ----------------
+ * One road record per frame, in the layout of Stixels::RoadParameters (16 bytes): the image-convention horizon row,
+ * the camera pitch and height, and the slope of the ground line in the v-disparity image (is_road_params, above). */
+
+/* d_status of is_road_choose_batch */
+#define IS_ROAD_NONE 0      /* no line was accepted, and the device saw every line (total <= max_lines, no overflow) */
+#define IS_ROAD_OK 1        /* a line was accepted */
+#define IS_ROAD_UNDECIDED 2 /* the kept lines do not decide it: the candidate buffer overflowed (the lines are not
+                             * HoughLines' then, none is looked at), or total > max_lines and no kept line was
+                             * accepted -- where RoadEstimation::ComputeBatch re-runs HoughLines on the binary image */
+#define IS_ROAD_HORIZON 3   /* a line was accepted, but its horizon row lies outside [0, rows) */
+
+/* The line choice of RoadEstimation::ComputeHough for every frame, on `stream`, behind is_road_hough_batch: the
+ * first line in sorted order whose pitch lies in [min_pitch, max_pitch], with rho = |rho|, evaluated by
+ * the function is_road_line of is_ground_model.h -- bitwise RoadEstimation::ChooseLineShared.  One wave per frame.
+ *   d_lines, d_total, d_overflow   as is_road_hough_batch wrote them for the same max_lines (device)
+ *   cy, baseline, focal            the camera (RoadEstimation::Initialize); the v-disparity image has ctx rows
+ *   fallback                       the record every frame whose status is not IS_ROAD_OK receives, so that whatever
+ *                                  consumes d_road runs on defined numbers (a calibration, the last good frame)
+ *   d_road   [n_images] is_road_params, d_status [n_images] uint8 (IS_ROAD_*), device
+ * A line whose theta is not one of the transform's angles (0.0f + n * theta_step bitwise) is skipped: sin and cos
+ * of the angle come from a table of the host's sinf / cosf, computed at is_road_ctx_create. */
+int is_road_choose_batch(is_road_ctx* ctx, int n_images, const float* d_lines, const int* d_total,
+                         const int* d_overflow, int max_lines, float cy, float baseline, float focal,
+                         float min_pitch, float max_pitch, is_road_params fallback, is_road_params* d_road,
+                         uint8_t* d_status, void* stream);
 
 /* ---- f5: stixels to dense result maps, scored against ground truth on the device ----------------------------
  * The reference evaluates stixels through per-pixel images drawn on the host

@@ -29,6 +29,7 @@ EXPORTS = [
     "is_comm_unique_id", "is_comm_init_rank", "is_comm_destroy", "is_comm_rank", "is_gather_i32",
     "is_gather_sections",
     "is_road_ctx_create", "is_road_ctx_destroy", "is_road_ctx_device", "is_road_ctx_binary",
+    "is_road_choose_batch", "is_ctx_set_ground_model", "is_compute_road", "is_debug_read_ground",
     "is_road_vdisparity_batch", "is_road_hough_batch",
     "is_section_instance_labels", "is_render_sections",
     "is_instance_overlap", "is_pack_overlap_records",
@@ -150,6 +151,22 @@ class InstanceDisparityArgs(ctypes.Structure):
                 ("scratch_bytes", ctypes.c_size_t), ("d_stixel_median", vp), ("d_key_count", vp), ("d_key_median", vp)]
 
 
+class RoadParams(ctypes.Structure):
+    """is_road_params: one frame's road, the layout of Stixels::RoadParameters (16 bytes)"""
+    _fields_ = [("vhor", ctypes.c_int), ("tilt", ctypes.c_float), ("height", ctypes.c_float),
+                ("alpha", ctypes.c_float)]
+
+
+class GroundParams(ctypes.Structure):
+    """is_ground_params: the constants of the device ground model (is_ctx_set_ground_model)"""
+    _fields_ = [(k, ctypes.c_float) for k in ("focal", "baseline", "max_dis", "pout", "sigma_disparity_ground",
+                                              "sigma_camera_height", "sigma_camera_tilt")]
+
+
+ROAD_DTYPE = np.dtype([("vhor", np.int32), ("tilt", np.float32), ("height", np.float32), ("alpha", np.float32)])
+ROAD_NONE, ROAD_OK, ROAD_UNDECIDED, ROAD_HORIZON = 0, 1, 2, 3   # d_status of is_road_choose_batch
+
+
 class CoreError(RuntimeError):
     pass
 
@@ -197,6 +214,10 @@ def lib():
         L.is_road_ctx_binary.restype = vp
         L.is_road_vdisparity_batch.argtypes = [vp, vp, ci, cf, vp, vp, vp, vp]
         L.is_road_hough_batch.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]
+        L.is_road_choose_batch.argtypes = [vp, ci, vp, vp, vp, ci, cf, cf, cf, cf, cf, RoadParams, vp, vp, vp]
+        L.is_ctx_set_ground_model.argtypes = [vp, ctypes.POINTER(GroundParams), vp, ci]
+        L.is_compute_road.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, ci, vp]
+        L.is_debug_read_ground.argtypes = [vp, ci, vp, ctypes.POINTER(ci)]
         L.is_cluster_instances.argtypes = [vp, ctypes.POINTER(InstanceBuffers), vp]
         L.is_section_instance_labels.argtypes = [ctypes.POINTER(InstanceBuffers), ci, ci, ci, vp, vp]
         L.is_render_sections.argtypes = [ctypes.POINTER(RenderArgs), vp]
@@ -359,6 +380,34 @@ class Core:
                                 int(bool(pairwise)), int(n_images), d_sections, inst,
                                 d_cost_table, d_index_table, stream), "is_compute")
 
+    def set_ground_model(self, ground_params: GroundParams, log_lut):
+        """is_ctx_set_ground_model: the constants and the FastLog table of the device ground model (once per
+        context, before compute_road_ptr)."""
+        lut = np.ascontiguousarray(log_lut, np.float32)
+        gp = GroundParams.from_buffer_copy(ground_params)
+        _check(lib().is_ctx_set_ground_model(self._ctx, ctypes.byref(gp), _hp(lut), int(lut.size)),
+               "is_ctx_set_ground_model")
+
+    def compute_road_ptr(self, d_joined, d_seg, d_road, pairwise, n_images, d_sections, instances=None,
+                         d_cost_table=None, d_index_table=None, vhor_min_hint=-1, stream=0):
+        """is_compute_road on raw device pointers: compute_ptr with the ground model built on the device from
+        d_road [n_images] RoadParams."""
+        inst = None
+        if instances is not None:
+            arr = (InstanceBuffers * n_images)(*instances)
+            inst = ctypes.cast(arr, ctypes.c_void_p)
+        _check(lib().is_compute_road(self._ctx, d_joined, d_seg, d_road, int(bool(pairwise)), int(n_images),
+                                     d_sections, inst, d_cost_table, d_index_table, int(vhor_min_hint), stream),
+               "is_compute_road")
+
+    def read_ground(self, frame):
+        """(ground [3][rows] = function | normalization | inv_sigma2, vhor) of one frame as the DP kernels of the
+        last compute call read them (test hook)."""
+        out = np.zeros((3, self.params.rows), np.float32)
+        vh = ctypes.c_int(0)
+        _check(lib().is_debug_read_ground(self._ctx, int(frame), _hp(out), ctypes.byref(vh)), "is_debug_read_ground")
+        return out, int(vh.value)
+
     def compute_sweep_ptr(self, d_joined, d_seg, ground_function, normalization_ground, inv_sigma2_ground, vhor,
                           pairwise, n_images, sets, d_sections, instances=None, stream=0):
         """is_compute_sweep on raw device pointers: sets a sequence of SweepSet, instances [n_sets][n_images]
@@ -442,10 +491,11 @@ class Core:
     # ---- torch-tensor convenience API ----------------------------------------------------
     def run(self, disparity_big=None, joined=None, segmentation=None, ground_function=None,
             normalization_ground=None, inv_sigma2_ground=None, vhor=None, pairwise=False,
-            median_join=False, want_tables=False, want_instances=True):
+            median_join=False, want_tables=False, want_instances=True, road=None, vhor_min_hint=-1):
         """Runs a batch given numpy inputs; returns numpy outputs (one sync at the end).
 
-        disparity_big [n][H][W] or joined [n][C][H]; segmentation [n][C][CH][P2S]."""
+        disparity_big [n][H][W] or joined [n][C][H]; segmentation [n][C][CH][P2S].  road (n records of ROAD_DTYPE):
+        is_compute_road with the records uploaded, in place of is_compute with the four host arrays."""
         import torch
         p = self.params
         C, H, S = p.cols, p.rows, p.max_sections
@@ -475,11 +525,18 @@ class Core:
             inst_s = [InstanceBuffers(com[i].data_ptr(), idx[i].data_ptr(), core[i].data_ptr(),
                                       per[i].data_ptr(), lab[i].data_ptr(), None)
                       for i in range(n)]
-        self.compute_ptr(d_joined.data_ptr(), seg.data_ptr(), ground_function,
-                         normalization_ground, inv_sigma2_ground, vhor, pairwise, n,
-                         sections.data_ptr(), inst_s,
-                         cost.data_ptr() if cost is not None else None,
-                         index.data_ptr() if index is not None else None, stream)
+        if road is not None:
+            rp = np.ascontiguousarray(road, ROAD_DTYPE).reshape(n)
+            d_road = torch.from_numpy(rp.view(np.int32).reshape(n, 4)).to(dev)
+            self.compute_road_ptr(d_joined.data_ptr(), seg.data_ptr(), d_road.data_ptr(), pairwise, n,
+                                  sections.data_ptr(), inst_s, cost.data_ptr() if cost is not None else None,
+                                  index.data_ptr() if index is not None else None, vhor_min_hint, stream)
+        else:
+            self.compute_ptr(d_joined.data_ptr(), seg.data_ptr(), ground_function,
+                             normalization_ground, inv_sigma2_ground, vhor, pairwise, n,
+                             sections.data_ptr(), inst_s,
+                             cost.data_ptr() if cost is not None else None,
+                             index.data_ptr() if index is not None else None, stream)
         torch.cuda.synchronize(dev)
         out = dict(joined=d_joined.cpu().numpy(),
                    sections=sections.cpu().numpy().view(SECTION_DTYPE).reshape(n, C, S))
@@ -634,6 +691,15 @@ def instance_objects_ptr(stream=0, **fields):
     `stream`."""
     a = InstanceObjectsArgs(**fields)
     _check(lib().is_instance_objects(ctypes.byref(a), ctypes.c_void_p(int(stream))), "is_instance_objects")
+
+
+def road_choose_batch_ptr(road_ctx, n_images, d_lines, d_total, d_overflow, max_lines, cy, baseline, focal,
+                          min_pitch, max_pitch, fallback, d_road, d_status, stream=0):
+    """is_road_choose_batch on raw device pointers; fallback = (vhor_image, tilt, height, alpha).  Returns the return
+    code (the tests check IS_EINVAL)."""
+    fb = RoadParams(int(fallback[0]), float(fallback[1]), float(fallback[2]), float(fallback[3]))
+    return lib().is_road_choose_batch(road_ctx, int(n_images), d_lines, d_total, d_overflow, int(max_lines), cy,
+                                      baseline, focal, min_pitch, max_pitch, fb, d_road, d_status, stream)
 
 
 def flip_and_pad(cnn_out, rows_power2_segmentation, device=0):

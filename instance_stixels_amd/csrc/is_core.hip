@@ -97,6 +97,10 @@ struct is_ctx {
     char* h_stage[IS_STAGE_SLOTS];
     float* d_ground;         /* [max_batch][3][H]            (in d_stage) */
     int* d_vhor;             /* [max_batch]                  (in d_stage) */
+    /* is_compute_road: the constants of k_ground_model and the table Stixels::FastLog reads (is_ctx_set_ground_model) */
+    is_ground_params ground_params;
+    float* d_log_lut;        /* [log_lut_entries], null until is_ctx_set_ground_model */
+    int log_lut_entries;
     /* ring of pinned staging slots: a call blocks the host only when the slot it wants is still
      * being read by the H2D copy of the call IS_STAGE_SLOTS calls ago */
     float* h_ground_pinned[IS_STAGE_SLOTS];
@@ -469,6 +473,7 @@ int is_ctx_destroy(is_ctx* c) {
     }
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->sweep_inst_free) (void)hipEventDestroy(c->sweep_inst_free);
+    if (c->d_log_lut) (void)hipFree(c->d_log_lut);
     if (c->d_sweep_prune) (void)hipFree(c->d_sweep_prune);
     if (c->d_sweep_inst) (void)hipFree(c->d_sweep_inst);
     if (c->h_sweep_inst) (void)hipHostFree(c->h_sweep_inst);
@@ -553,6 +558,7 @@ struct is_road_ctx {
     float rho, theta;
     int last_n;                 /* frames of the last is_road_vdisparity_batch (0: none yet) */
     float* d_tab;               /* [2][numangle]: tabSin, tabCos of HoughLines */
+    float* d_tab_theta;         /* [2][numangle]: sinf, cosf of the lines' theta = 0.0f + n * theta (is_road_choose_batch) */
     int* d_vdisp;               /* [max_batch][rows][max_dis] */
     uint8_t* d_binary;          /* [max_batch][rows][max_dis] */
     int* d_counters;            /* [max_batch][isk_road_counters()]: maximum, non-zero pixels */
@@ -584,12 +590,19 @@ int is_road_ctx_create(is_road_ctx** out, int rows, int cols, int max_dis, int m
     const double min_theta = 0, max_theta = 3.1415926535897932384626433832795;
     const int numangle = (int)lrint((max_theta - min_theta) / theta);
     const int numrho = (int)lrint(((width + height) * 2 + 1) / rho);
-    float* tab = (float*)malloc(sizeof(float) * 2 * numangle);
+    float* tab = (float*)malloc(sizeof(float) * 4 * numangle); /* [tabSin | tabCos | sinf | cosf of a line's theta] */
     if (!tab) return IS_ENOMEM;
     float ang = (float)min_theta;
     for (int n = 0; n < numangle; ang += theta, n++) {
         tab[n] = (float)(sin((double)ang) * irho);
         tab[numangle + n] = (float)(cos((double)ang) * irho);
+    }
+    /* what RoadEstimation::ComputeCameraProperties evaluates for a line of angle index n (k_road_sort writes theta as
+     * exactly this expression): the device has no sinf / cosf with libm's bits, so the host's travel */
+    for (int n = 0; n < numangle; n++) {
+        const float line_theta = 0.0f + n * theta;
+        tab[2 * numangle + n] = sinf(line_theta);
+        tab[3 * numangle + n] = cosf(line_theta);
     }
     /* angles per workgroup: as many accumulator rows (plus the two halo rows) as 160 KiB of LDS hold */
     const size_t row_bytes = sizeof(int) * (size_t)(numrho + 2);
@@ -608,6 +621,7 @@ int is_road_ctx_create(is_road_ctx** out, int rows, int cols, int max_dis, int m
     hipError_t err = hipSuccess; /* (the first failure stops the allocations) */
     auto alloc = [&](auto** p, size_t bytes) { if (err == hipSuccess) err = c->owned.alloc(p, bytes); };
     alloc(&c->d_tab, sizeof(float) * 2 * numangle);
+    alloc(&c->d_tab_theta, sizeof(float) * 2 * numangle);
     alloc(&c->d_vdisp, sizeof(int) * B * cells);
     alloc(&c->d_binary, B * cells);
     alloc(&c->d_counters, sizeof(int) * B * isk_road_counters());
@@ -615,6 +629,8 @@ int is_road_ctx_create(is_road_ctx** out, int rows, int cols, int max_dis, int m
     alloc(&c->d_ncand, sizeof(int) * B);
     alloc(&c->d_cand, sizeof(int2) * B * IS_ROAD_MAX_CANDIDATES);
     if (err == hipSuccess) err = hipMemcpy(c->d_tab, tab, sizeof(float) * 2 * numangle, hipMemcpyHostToDevice);
+    if (err == hipSuccess)
+        err = hipMemcpy(c->d_tab_theta, tab + 2 * numangle, sizeof(float) * 2 * numangle, hipMemcpyHostToDevice);
     free(tab);
     if (err != hipSuccess) {
         (void)hipGetLastError();
@@ -672,6 +688,19 @@ int is_road_hough_batch(is_road_ctx* c, int n_images, int threshold, int max_lin
     HIP_TRY(isk_launch_road_hough(c->d_points, c->d_counters, c->d_ncand, c->d_tab, c->d_cand, d_lines, d_votes,
                                   d_total, d_overflow, n_images, c->rows * c->max_dis, c->numangle, c->numrho,
                                   c->band, threshold, max_candidates, max_lines, c->rho, c->theta, s));
+    return IS_OK;
+}
+
+int is_road_choose_batch(is_road_ctx* c, int n_images, const float* d_lines, const int* d_total, const int* d_overflow,
+                         int max_lines, float cy, float baseline, float focal, float min_pitch, float max_pitch,
+                         is_road_params fallback, is_road_params* d_road, uint8_t* d_status, void* stream) {
+    if (!c || !d_lines || !d_total || !d_overflow || !d_road || !d_status) return fail_arg("null pointer");
+    if (n_images < 1 || n_images > c->max_batch) return fail_arg("n_images outside [1, max_batch]");
+    if (max_lines < 1) return fail_arg("max_lines < 1");
+    ON_CTX_DEVICE(c);
+    HIP_TRY(isk_launch_road_choose(d_lines, d_total, d_overflow, c->d_tab_theta, d_road, d_status, n_images, max_lines,
+                                   c->numangle, c->theta, c->rows, cy, baseline, focal, min_pitch, max_pitch, fallback,
+                                   (hipStream_t)stream));
     return IS_OK;
 }
 
@@ -972,7 +1001,14 @@ int is_get_kernel_times_ms(is_ctx* c, float* prepare_ms, float* dp_ms, float* ba
 
 /* Every launch decision of one DP call (CallPlan, is_launch.h); the launchers launch what it says.  The choices decide
  * launch geometry and kernel instantiations only, never results. */
-static CallPlan plan_call(const is_ctx* c, const DevParams& P, int n_images, int pairwise, const int* h_vhor,
+/* the smallest horizon of a call's frames as plan_call takes it (at most H) */
+static int min_vhor(const int* h_vhor, int n_images, int H) {
+    int vmin = H;
+    for (int i = 0; i < n_images; i++) vmin = h_vhor[i] < vmin ? h_vhor[i] : vmin;
+    return vmin;
+}
+
+static CallPlan plan_call(const is_ctx* c, const DevParams& P, int n_images, int pairwise, int vhor_min,
                           bool tables_requested, bool want_inst) {
     const Knobs& k = c->knobs;
     const int ncols = n_images * P.C;
@@ -987,9 +1023,9 @@ static CallPlan plan_call(const is_ctx* c, const DevParams& P, int n_images, int
      * scene) -- measured at batch 64: 9 windowed tiles 7450, all 16: 7760 frames/s (pairwise 3780 / 3810, but its
      * unpruned floor 1720 / 1630).  IS_P1_WIN_TILES forces the window for that many tiles at any call size: tests. */
     if (IS_P1_WINDOWED(P.D) && (k.win_tiles >= 0 || ncols >= (pairwise ? IS_P1_WIN_MIN_COLS : ISF_WIN_MIN_COLS))) {
-        int w = k.win_tiles >= 0 ? k.win_tiles : P.ntiles, vmin = P.H;
+        int w = k.win_tiles >= 0 ? k.win_tiles : P.ntiles;
         if (k.win_tiles < 0 && pairwise) {
-            for (int i = 0; i < n_images; i++) vmin = h_vhor[i] < vmin ? h_vhor[i] : vmin;
+            const int vmin = vhor_min < P.H ? vhor_min : P.H;
             w = vmin > 0 ? (vmin + IS_TILE - 1) / IS_TILE : 0;
         }
         p.win_tiles = w < P.ntiles ? w : P.ntiles;
@@ -1069,8 +1105,16 @@ static CallPlan plan_call(const is_ctx* c, const DevParams& P, int n_images, int
 
 /* The H2D copies of a call's staging slot: the ground model and the horizons, with the per-image instance table in
  * the same copy where the batch is full (`inst_tbl`: a call with fewer frames copies the table by itself). */
-static int enqueue_staging(is_ctx* c, int n_images, bool inst_tbl, hipStream_t stream, int slot) {
+static int enqueue_staging(is_ctx* c, int n_images, bool inst_tbl, hipStream_t stream, int slot,
+                           bool ground = true) {
     const size_t H = c->dp.H;
+    if (!ground) { /* is_compute_road: the ground model and the horizons are written on the device */
+        if (inst_tbl)
+            HIP_TRY(hipMemcpyAsync(c->d_inst_tbl, c->h_inst_pinned[slot], sizeof(is_instance_buffers) * n_images,
+                                   hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipEventRecord(c->staging_free[slot], stream));
+        return IS_OK;
+    }
     const bool one_copy = n_images == c->max_batch;
     if (one_copy) {
         HIP_TRY(hipMemcpyAsync(c->d_stage, c->h_stage[slot], c->stage_bytes, hipMemcpyHostToDevice, stream));
@@ -1115,18 +1159,25 @@ static CallBuffers call_buffers(const is_ctx* c, const float* d_joined, const in
     return b;
 }
 
-/* Everything is_compute queues on `stream` behind the host-side staging of slot `slot`. */
+/* Everything is_compute and is_compute_road queue on `stream` behind the host-side staging of slot `slot`.  d_road
+ * null (is_compute): the slot's ground model is uploaded.  Else k_ground_model builds it from d_road in place, and
+ * the plan takes vhor_min_hint (< 0: unknown, planned as 0) for the smallest horizon. */
 static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_seg, int pairwise, int n_images,
                            is_section* d_sections, const is_instance_buffers* instances, float* d_cost_table,
-                           int32_t* d_index_table, hipStream_t stream, int slot) {
+                           int32_t* d_index_table, hipStream_t stream, int slot,
+                           const is_road_params* d_road = nullptr, int vhor_min_hint = -1) {
     const DevParams& P = c->dp;
     const bool timing = c->timing;
     bool want_inst = false, want_labels = false;
     instance_wants(instances, n_images, &want_inst, &want_labels);
-    const int rc_stage = enqueue_staging(c, n_images, want_inst, stream, slot);
+    const int rc_stage = enqueue_staging(c, n_images, want_inst, stream, slot, d_road == nullptr);
     if (rc_stage != IS_OK) return rc_stage;
+    if (d_road)
+        HIP_TRY(isk_launch_ground_model(&c->ground_params, c->d_log_lut, c->log_lut_entries, d_road, c->d_ground,
+                                        c->d_vhor, n_images, P.H, stream));
 
-    const CallPlan plan = plan_call(c, P, n_images, pairwise, c->h_vhor_pinned[slot],
+    const int vhor_min = d_road ? (vhor_min_hint < 0 ? 0 : vhor_min_hint) : min_vhor(c->h_vhor_pinned[slot], n_images, P.H);
+    const CallPlan plan = plan_call(c, P, n_images, pairwise, vhor_min,
                                     d_cost_table != nullptr || d_index_table != nullptr, want_inst);
     if (!pairwise) c->last_unary_path = plan.unary_walk;
     CallBuffers b = call_buffers(c, d_joined, d_seg);
@@ -1163,10 +1214,9 @@ static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_se
 }
 
 /* The argument checks is_compute and is_compute_sweep share (`n_inst` entries of `instances`). */
-static const char* compute_fault(const is_ctx* c, const float* d_joined, const int32_t* d_seg, const float* h_gf,
-                                 const float* h_ng, const float* h_is2, const int* h_vhor, int n_images,
+static const char* compute_fault(const is_ctx* c, const float* d_joined, const int32_t* d_seg, int n_images,
                                  const is_section* d_sections, const is_instance_buffers* instances, long long n_inst) {
-    if (!c || !d_joined || !d_seg || !h_gf || !h_ng || !h_is2 || !h_vhor || !d_sections) return "null pointer";
+    if (!c || !d_joined || !d_seg || !d_sections) return "null pointer";
     if (n_images < 1 || n_images > c->max_batch) return "n_images outside [1, max_batch]";
     if ((((uintptr_t)d_joined) | ((uintptr_t)d_seg)) & 15)
         return "d_joined / d_segmentation must be 16-byte aligned (vector loads)";
@@ -1187,7 +1237,7 @@ static int stage_call(is_ctx* c, const float* h_gf, const float* h_ng, const flo
     const int slot = c->stage_next;
     c->stage_next = (slot + 1) % IS_STAGE_SLOTS;
     if (c->staging_pending[slot]) HIP_TRY(hipEventSynchronize(c->staging_free[slot]));
-    for (int i = 0; i < n_images; i++) {
+    for (int i = 0; h_gf && i < n_images; i++) { /* (h_gf null, is_compute_road: the instance table only) */
         float* dst = c->h_ground_pinned[slot] + (size_t)i * 3 * H;
         memcpy(dst, h_gf + (size_t)i * H, sizeof(float) * H);
         memcpy(dst + H, h_ng + (size_t)i * H, sizeof(float) * H);
@@ -1215,8 +1265,8 @@ int is_compute(is_ctx* c, const float* d_joined, const int32_t* d_seg, const flo
                const float* h_ng, const float* h_is2, const int* h_vhor, int pairwise, int n_images,
                is_section* d_sections, const is_instance_buffers* instances, float* d_cost_table,
                int32_t* d_index_table, void* stream_) {
-    if (const char* fault = compute_fault(c, d_joined, d_seg, h_gf, h_ng, h_is2, h_vhor, n_images, d_sections,
-                                          instances, n_images))
+    if (!h_gf || !h_ng || !h_is2 || !h_vhor) return fail_arg("null pointer");
+    if (const char* fault = compute_fault(c, d_joined, d_seg, n_images, d_sections, instances, n_images))
         return fail_arg(fault);
     ON_CTX_DEVICE(c);
     hipStream_t stream = (hipStream_t)stream_;
@@ -1227,6 +1277,52 @@ int is_compute(is_ctx* c, const float* d_joined, const int32_t* d_seg, const flo
                                    d_index_table, stream, slot);
     if (rc != IS_OK) clear_call_state(c, stream);
     return rc;
+}
+
+int is_ctx_set_ground_model(is_ctx* c, const is_ground_params* params, const float* h_log_lut, int n_entries) {
+    if (!c || !params || !h_log_lut) return fail_arg("null pointer");
+    if (n_entries < 2) return fail_arg("n_entries < 2");
+    ON_CTX_DEVICE(c);
+    if (n_entries != c->log_lut_entries) {
+        HIP_TRY(hipDeviceSynchronize()); /* (a queued call may still read the old table) */
+        if (c->d_log_lut) (void)hipFree(c->d_log_lut);
+        c->d_log_lut = nullptr;
+        c->log_lut_entries = 0;
+        HIP_TRY(hipMalloc((void**)&c->d_log_lut, sizeof(float) * (size_t)n_entries));
+        c->log_lut_entries = n_entries;
+    }
+    HIP_TRY(hipMemcpy(c->d_log_lut, h_log_lut, sizeof(float) * (size_t)n_entries, hipMemcpyHostToDevice));
+    c->ground_params = *params;
+    return IS_OK;
+}
+
+int is_compute_road(is_ctx* c, const float* d_joined, const int32_t* d_seg, const is_road_params* d_road, int pairwise,
+                    int n_images, is_section* d_sections, const is_instance_buffers* instances, float* d_cost_table,
+                    int32_t* d_index_table, int vhor_min_hint, void* stream_) {
+    if (!d_road) return fail_arg("null pointer");
+    if (const char* fault = compute_fault(c, d_joined, d_seg, n_images, d_sections, instances, n_images))
+        return fail_arg(fault);
+    if (!c->d_log_lut) return fail_arg("is_compute_road before is_ctx_set_ground_model");
+    ON_CTX_DEVICE(c);
+    hipStream_t stream = (hipStream_t)stream_;
+    int slot = 0;
+    const int rc_stage = stage_call(c, nullptr, nullptr, nullptr, nullptr, n_images, instances, &slot);
+    if (rc_stage != IS_OK) return rc_stage;
+    const int rc = compute_enqueue(c, d_joined, d_seg, pairwise, n_images, d_sections, instances, d_cost_table,
+                                   d_index_table, stream, slot, d_road, vhor_min_hint);
+    if (rc != IS_OK) clear_call_state(c, stream);
+    return rc;
+}
+
+int is_debug_read_ground(is_ctx* c, int frame, float* h_out, int* vhor) {
+    if (!c || !h_out || !vhor) return fail_arg("null pointer");
+    if (frame < 0 || frame >= c->max_batch) return fail_arg("frame outside [0, max_batch)");
+    ON_CTX_DEVICE(c);
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t n = 3 * (size_t)c->dp.H;
+    HIP_TRY(hipMemcpy(h_out, c->d_ground + (size_t)frame * n, sizeof(float) * n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(vhor, c->d_vhor + frame, sizeof(int), hipMemcpyDeviceToHost));
+    return IS_OK;
 }
 
 /* ---- parameter sweeps ---- */
@@ -1310,7 +1406,7 @@ static int sweep_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_seg,
         P.sigma_od = weights_allow_pruning(P.dw, P.pw, P.sw, P.iw) ? c->sigma_od_free : __builtin_inff();
         bool want_inst = false, want_labels = false;
         instance_wants(instances ? instances + (size_t)k * n_images : nullptr, n_images, &want_inst, &want_labels);
-        plans[k] = plan_call(c, P, n_images, pairwise, c->h_vhor_pinned[slot], false, want_inst);
+        plans[k] = plan_call(c, P, n_images, pairwise, min_vhor(c->h_vhor_pinned[slot], n_images, P.H), false, want_inst);
         plans[k].lut_fused = 0;
         plans[k].prepare_lut = 1;
         if (!pairwise) (plans[k].unary_walk ? any_walk : any_tile) = true;
@@ -1374,7 +1470,8 @@ int is_compute_sweep(is_ctx* c, const float* d_joined, const int32_t* d_seg, con
                      int n_sets, is_section* d_sections, const is_instance_buffers* instances, void* stream_) {
     if (!h_sets) return fail_arg("null pointer");
     if (n_sets < 1) return fail_arg("n_sets < 1");
-    if (const char* fault = compute_fault(c, d_joined, d_seg, h_gf, h_ng, h_is2, h_vhor, n_images, d_sections,
+    if (!h_gf || !h_ng || !h_is2 || !h_vhor) return fail_arg("null pointer");
+    if (const char* fault = compute_fault(c, d_joined, d_seg, n_images, d_sections,
                                           instances, (long long)n_sets * (n_images > 0 ? n_images : 0)))
         return fail_arg(fault);
     if ((long long)n_sets * n_images * c->dp.C * c->dp.S > 0x7fffffffLL)

@@ -9,6 +9,7 @@
 
 #include <stdint.h>
 
+#include "is_ground_model.h"
 #include "is_launch.h"
 
 /* Per-frame counters of the batch scratch: [frame][IS_ROAD_CNT] ints. */
@@ -175,6 +176,55 @@ __global__ __launch_bounds__(256) void k_road_sort(const int2* __restrict__ cand
     }
 }
 
+/* The line choice of one frame per wave (RoadEstimation::ChooseLineShared, bitwise): the lanes evaluate the lines
+ * lane, lane + 64, ... of the sorted list with is_road_line, and the lowest accepted index of a round wins by
+ * ballot.  Only lines k < min(total, max_lines) are read: what k_road_sort wrote.  tabT: [sin | cos][numangle] of
+ * the transform's angles, the host's sinf / cosf. */
+__global__ __launch_bounds__(64) void k_road_choose(const float* __restrict__ lines, const int* __restrict__ total,
+                                                    const int* __restrict__ overflow, const float* __restrict__ tabT,
+                                                    is_road_params* __restrict__ road, uint8_t* __restrict__ status,
+                                                    int max_lines, int numangle, float step, int rows, float cy,
+                                                    float baseline, float focal, float min_pitch, float max_pitch,
+                                                    is_road_params fallback) {
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const int found = total[f];
+    const bool over = overflow[f] != 0;
+    const int nl = over ? 0 : min(found, max_lines); /* (an overflowed sort: not HoughLines' lines) */
+    const float* fl = lines + (size_t)f * max_lines * 2;
+    is_road_params out = fallback;
+    int st = over || found > max_lines ? IS_ROAD_UNDECIDED : IS_ROAD_NONE;
+    for (int base = 0; base < nl; base += 64) { /* (wave-uniform trip count) */
+        const int k = base + lane;
+        is_road_params mine = fallback;
+        int accepted = 0, vhor_ok = 0;
+        if (k < nl) {
+            const float rho = fabsf(fl[2 * k]);
+            const int n = is_road_angle_index(fl[2 * k + 1], step, numangle);
+            if (n >= 0)
+                accepted = is_road_line(rho, tabT[n], tabT[numangle + n], cy, baseline, focal, rows, min_pitch,
+                                        max_pitch, &mine, &vhor_ok);
+        }
+        const uint64_t mask = __ballot(accepted);
+        if (mask != 0) {
+            const int leader = __ffsll((unsigned long long)mask) - 1;
+            /* (every lane takes the leader's values: the stores below come from lane 0) */
+            const int ok = __shfl(vhor_ok, leader, 64);
+            st = ok ? IS_ROAD_OK : IS_ROAD_HORIZON;
+            if (ok) {
+                out.vhor = __shfl(mine.vhor, leader, 64);
+                out.tilt = __shfl(mine.tilt, leader, 64);
+                out.height = __shfl(mine.height, leader, 64);
+                out.alpha = __shfl(mine.alpha, leader, 64);
+            }
+            break;
+        }
+    }
+    if (lane == 0) {
+        road[f] = out;
+        status[f] = (uint8_t)st;
+    }
+}
+
 extern "C" {
 
 int isk_road_sort_max(void) { return IS_ROAD_SORT_MAX; }
@@ -207,6 +257,15 @@ hipError_t isk_launch_road_hough(const int* points, const int* counters, int* nc
                        ncand, n_cells, numangle, numrho, band, threshold, cap);
     hipLaunchKernelGGL(k_road_sort, dim3(n_images), dim3(256), 0, stream, cand, ncand, lines, votes, total,
                        overflow, cap, max_lines, numrho, rho, theta);
+    return hipGetLastError();
+}
+
+hipError_t isk_launch_road_choose(const float* lines, const int* total, const int* overflow, const float* tabT,
+                                  is_road_params* road, uint8_t* status, int n_images, int max_lines, int numangle,
+                                  float step, int rows, float cy, float baseline, float focal, float min_pitch,
+                                  float max_pitch, is_road_params fallback, hipStream_t stream) {
+    hipLaunchKernelGGL(k_road_choose, dim3(n_images), dim3(64), 0, stream, lines, total, overflow, tabT, road, status,
+                       max_lines, numangle, step, rows, cy, baseline, focal, min_pitch, max_pitch, fallback);
     return hipGetLastError();
 }
 

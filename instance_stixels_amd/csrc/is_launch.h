@@ -198,6 +198,16 @@ hipError_t isk_launch_road_hough(const int* points, const int* counters, int* nc
                                  int numangle, int numrho, int band, int threshold, int cap, int max_lines, float rho,
                                  float theta, hipStream_t stream);
 
+hipError_t isk_launch_road_choose(const float* lines, const int* total, const int* overflow, const float* tabT,
+                                  is_road_params* road, uint8_t* status, int n_images, int max_lines, int numangle,
+                                  float step, int rows, float cy, float baseline, float focal, float min_pitch,
+                                  float max_pitch, is_road_params fallback, hipStream_t stream);
+
+/* is_k_ground.hip */
+hipError_t isk_launch_ground_model(const is_ground_params* g, const float* log_lut, int lut_entries,
+                                   const is_road_params* road, float* ground, int* vhor, int n_images, int rows,
+                                   hipStream_t stream);
+
 /* is_k_render.hip */
 int isk_render_scatter_images(void);
 hipError_t isk_launch_section_instance(const is_instance_buffers* per_image, int n_images, int first_image,

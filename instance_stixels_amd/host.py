@@ -140,6 +140,17 @@ def lib():
         L.ish_recluster_batch.argtypes = [vp, cf, ci, ci, ci, vp, ci, vp, vp]
         L.ish_cluster_instance_disparity_batch.argtypes = [vp, ci, vp, vp, ci, cf, ci, ci, vp, ci, vp, vp, vp]
         L.ish_set_instance_disparity_capacity.argtypes = [vp, ci]
+        for f in (L.ish_erff, L.ish_atanf, L.ish_cosf):
+            f.argtypes, f.restype = [cf], cf
+        for f in (L.ish_erff_n, L.ish_atanf_n, L.ish_cosf_n):
+            f.argtypes, f.restype = [vp, vp, ctypes.c_size_t], None
+        L.ish_precompute_ground_shared.argtypes = [vp, ci, cf, cf, cf, vp, vp, vp, vp]
+        L.ish_ground_params.argtypes = [vp, ctypes.POINTER(_core.GroundParams)]
+        L.ish_log_lut.argtypes = [vp, vp, ci]
+        L.ish_compute_batch_road.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp]
+        L.ire_compute_batch_device.argtypes = [vp, vp, ci, vp, vp, vp, vp]
+        L.ire_choose_line_shared.argtypes = [cf, cf, cf, ci, vp, ci, ci, ci, vp, vp, ctypes.POINTER(ci)]
+        L.ire_pitch_gate.argtypes, L.ire_pitch_gate.restype = [ctypes.POINTER(cf), ctypes.POINTER(cf)], None
         _LIB = L
     return _LIB
 
@@ -275,6 +286,59 @@ class Stixels:
         if with_instances:
             maps = [{(int(u), int(v)): int(l) for u, v, l in tri[i, :cnt[i]]} for i in range(n)]
         return data, maps
+
+    def ComputeBatchRoad(self, pairwise, n, d_disparity_big, d_segmentation, d_road, d_status, with_instances=True,
+                         stream=0):
+        """Stixels::ComputeBatchRoad: ComputeBatch with the road records d_road [n] (16 bytes each) and the status
+        bytes d_status [n] on the device (RoadEstimation.ComputeBatchDevice); the ground model is built on the
+        device.  Returns (list of StixelsData, mappings or None, road, status): road n tuples (vhor_image,
+        camera_tilt, camera_height, alpha_ground) and status n ints (core.ROAD_*), from the copy the call fetched
+        behind the DP."""
+        C, S = self.GetRealCols(), self.GetMaxSections()
+        sec = np.zeros((n, C, S), SECTION_DTYPE)
+        vh = np.zeros(n, np.int32)
+        alpha = np.zeros(n, np.float32)
+        rp = np.zeros((n, 4), np.float32)
+        st = np.zeros(n, np.uint8)
+        cap = C * S
+        tri = np.zeros((n, cap, 3), np.int32) if with_instances else None
+        cnt = np.zeros(n, np.int32)
+        self._check(lib().ish_compute_batch_road(self._h, int(bool(pairwise)), int(n), d_disparity_big, d_segmentation,
+                                                 d_road, d_status, sec.ctypes.data, vh.ctypes.data, alpha.ctypes.data,
+                                                 rp.ctypes.data, st.ctypes.data,
+                                                 tri.ctypes.data if with_instances else None, cap, cnt.ctypes.data,
+                                                 stream), "ComputeBatchRoad")
+        cfg = self._cfg
+        data = [StixelsData(sec[i], int(cfg.rows), int(cfg.cols), C, S, int(cfg.max_dis), int(cfg.column_step),
+                            int(cfg.n_semantic_classes), float(alpha[i]), int(vh[i])) for i in range(n)]
+        maps = _maps(tri, cnt) if with_instances else None
+        road = [(int(r[0]), np.float32(r[1]), np.float32(r[2]), np.float32(r[3])) for r in rp]
+        return data, maps, road, [int(x) for x in st]
+
+    def PrecomputeGroundShared(self, vhor_lib, camera_tilt, camera_height, alpha_ground):
+        """Stixels::PrecomputeGroundShared with this object's constants (after PrecomputeHost() or Initialize()): the
+        host twin of the device ground model.  Returns (function, normalization, inv_sigma2, range_index), [rows]
+        each; range_index is the FastLog index of the a_range term."""
+        H = self.GetParameters().rows
+        gf, ng, ig = (np.zeros(H, np.float32) for _ in range(3))
+        idx = np.zeros(H, np.int32)
+        self._check(lib().ish_precompute_ground_shared(self._h, int(vhor_lib), camera_tilt, camera_height,
+                                                       alpha_ground, gf.ctypes.data, ng.ctypes.data, ig.ctypes.data,
+                                                       idx.ctypes.data), "PrecomputeGroundShared")
+        return gf, ng, ig, idx
+
+    def GroundParams(self):
+        """core.GroundParams of this object's configuration (Core.set_ground_model)."""
+        gp = _core.GroundParams()
+        self._check(lib().ish_ground_params(self._h, ctypes.byref(gp)), "GroundParams")
+        return gp
+
+    def GetLogLUT(self):
+        """The table Stixels::FastLog reads (after PrecomputeHost() or Initialize())."""
+        n = int(lib().ish_log_lut(self._h, None, 0))
+        out = np.zeros(n, np.float32)
+        lib().ish_log_lut(self._h, out.ctypes.data, n)
+        return out
 
     def ComputeBatchGather(self, pairwise, d_disparity_big, d_segmentation, road, comm, dst,
                            images_per_rank, road_all=None, stream=0):
@@ -632,6 +696,51 @@ def choose_line(lines, camera_center_y, baseline, focal, rows):
     return k, (int(r["vhor"]), np.float32(r["camera_tilt"]), np.float32(r["camera_height"]), np.float32(r["alpha_ground"]))
 
 
+def _shared(fn, x):
+    a = np.ascontiguousarray(x, np.float32)
+    out = np.empty_like(a)
+    fn(a.ctypes.data, out.ctypes.data, a.size)
+    return out
+
+
+def is_erff(x):
+    """is_erff of is_numerics.h, elementwise (float32 in, float32 out): the erf host and device share."""
+    return _shared(lib().ish_erff_n, x)
+
+
+def is_atanf(x):
+    return _shared(lib().ish_atanf_n, x)
+
+
+def is_cosf(x):
+    return _shared(lib().ish_cosf_n, x)
+
+
+def pitch_gate():
+    """(min_pitch, max_pitch) of RoadEstimation::Initialize, as float32"""
+    lo, hi = ctypes.c_float(), ctypes.c_float()
+    lib().ire_pitch_gate(ctypes.byref(lo), ctypes.byref(hi))
+    return np.float32(lo.value), np.float32(hi.value)
+
+
+def choose_line_shared(lines, total, overflow, max_lines, camera_center_y, baseline, focal, rows,
+                       fallback=(0, 0.0, 0.0, 0.0)):
+    """RoadEstimation::ChooseLineShared, the host twin of is_road_choose_batch: lines [>= min(total, max_lines)][2]
+    as is_road_hough_batch leaves them.  Returns (status, index, road): core.ROAD_*, the accepted line or -1, and
+    (vhor_image, camera_tilt, camera_height, alpha_ground) -- the fallback unless the status is ROAD_OK."""
+    l = np.ascontiguousarray(lines, np.float32).reshape(-1, 2)
+    assert len(l) >= min(int(total), int(max_lines)) or overflow
+    fb = np.array(fallback, np.float32)
+    out = np.zeros(1, ROAD_PARAMETERS_DTYPE)
+    idx = ctypes.c_int(-1)
+    st = int(lib().ire_choose_line_shared(camera_center_y, baseline, focal, int(rows), l.ctypes.data, int(total),
+                                          int(overflow), int(max_lines), fb.ctypes.data, out.ctypes.data,
+                                          ctypes.byref(idx)))
+    r = out[0]
+    return st, int(idx.value), (int(r["vhor"]), np.float32(r["camera_tilt"]), np.float32(r["camera_height"]),
+                                np.float32(r["alpha_ground"]))
+
+
 class RoadEstimation:
     """Python view of the C++ RoadEstimation class (RoadEstimation.h of the reference)."""
 
@@ -689,6 +798,19 @@ class RoadEstimation:
         road = [(int(r["vhor"]), float(r["camera_tilt"]), float(r["camera_height"]), float(r["alpha_ground"]))
                 for r in out]
         return road, [bool(x) for x in ok]
+
+    def ComputeBatchDevice(self, d_ptr, n, d_road, d_status, fallback, stream=0):
+        """RoadEstimation::ComputeBatchDevice: v-disparity, Hough transform and line choice of d_ptr [n][rows][cols]
+        queued on `stream`; d_road [n] 16-byte records and d_status [n] bytes (device pointers as ints) for
+        Stixels.ComputeBatchRoad; fallback = (vhor_image, tilt, height, alpha).  No copy, no synchronisation."""
+        fb = np.array(fallback, np.float32)
+        rc = lib().ire_compute_batch_device(self._h, ctypes.c_void_p(int(d_ptr)), int(n), ctypes.c_void_p(int(d_road)),
+                                            ctypes.c_void_p(int(d_status)), fb.ctypes.data,
+                                            ctypes.c_void_p(int(stream)))
+        if rc == -1:
+            raise ValueError(lib().ish_last_error().decode())
+        if rc < 0:
+            raise RuntimeError(lib().ish_last_error().decode())
 
     def SetBatchLimits(self, max_lines, max_candidates):
         """Lines per frame and local maxima kept per frame by the device Hough transform of ComputeBatch."""

@@ -7,6 +7,7 @@
  */
 #include "InstanceStixels/RoadEstimation.h"
 #include "DeviceGuard.h"
+#include "is_ground_model.h"
 
 #include <algorithm>
 #include <cmath>
@@ -52,8 +53,7 @@ void RoadEstimation::SetCamera(float camera_center_y, float baseline, float foca
     m_cy = camera_center_y; /* RE.cu:37-40 */
     m_b = baseline;
     m_focal = focal;
-    m_maxPitch = 50 * kPi / 180.0f; /* RE.cu:47-57 */
-    m_minPitch = -50 * kPi / 180.0f;
+    PitchGate(m_minPitch, m_maxPitch);
     m_rows = rows;
 }
 
@@ -88,15 +88,9 @@ void RoadEstimation::SetBatchLimits(int max_lines, int max_candidates) {
     m_batch_candidates = max_candidates;
 }
 
-void RoadEstimation::ComputeBatch(const pixel_t* d_im, int n_images, Stixels::RoadParameters* out, uint8_t* ok,
-                                  void* stream) {
-    if (!m_is_initialized) throw std::invalid_argument("RoadEstimation::ComputeBatch before Initialize()");
-    if (n_images < 1 || !d_im || !out || !ok) throw std::invalid_argument("ComputeBatch: empty batch or null pointer");
-    const DeviceGuard guard(m_ctx_device);
-    void* s = stream ? stream : m_stream;
+/* out block, in the order that lets ONE copy fetch n frames: [cap] totals, [cap] overflow flags, [cap][L][2] lines */
+void RoadEstimation::ReserveBatch(int n_images) { /* (under the caller's device guard) */
     const int L = m_batch_lines;
-    /* out block, in the order that lets ONE copy fetch n frames: [cap] totals, [cap] overflow flags,
-     * [cap][L][2] lines */
     if (n_images > m_batch_cap || L != m_batch_out_lines) {
         const int cap = std::max(n_images, m_batch_cap);
         FreeBatch();
@@ -107,6 +101,71 @@ void RoadEstimation::ComputeBatch(const pixel_t* d_im, int n_images, Stixels::Ro
         m_batch_cap = cap;
         m_batch_out_lines = L;
     }
+}
+
+void RoadEstimation::ComputeBatchDevice(const pixel_t* d_im, int n_images, Stixels::RoadParameters* d_road,
+                                        uint8_t* d_status, const Stixels::RoadParameters& fallback, void* stream) {
+    if (!m_is_initialized) throw std::invalid_argument("RoadEstimation::ComputeBatchDevice before Initialize()");
+    if (n_images < 1 || !d_im || !d_road || !d_status)
+        throw std::invalid_argument("ComputeBatchDevice: empty batch or null pointer");
+    const DeviceGuard guard(m_ctx_device);
+    void* s = stream ? stream : m_stream;
+    const int L = m_batch_lines;
+    ReserveBatch(n_images);
+    const int cap = m_batch_cap;
+    int* d_total = (int*)d_batch_out.get();
+    int* d_overflow = d_total + cap;
+    float* d_lines = (float*)(d_overflow + cap);
+    IS_CHECK_RETURN(is_road_vdisparity_batch(m_batch_ctx, d_im, n_images, m_binThr, nullptr, nullptr, nullptr, s));
+    IS_CHECK_RETURN(is_road_hough_batch(m_batch_ctx, n_images, m_HoughAccumThr, L, m_batch_candidates, d_lines,
+                                        nullptr, d_total, d_overflow, s));
+    static_assert(sizeof(Stixels::RoadParameters) == sizeof(is_road_params), "d_road holds is_road_params records");
+    const is_road_params fb = {fallback.vhor, fallback.camera_tilt, fallback.camera_height, fallback.alpha_ground};
+    IS_CHECK_RETURN(is_road_choose_batch(m_batch_ctx, n_images, d_lines, d_total, d_overflow, L, m_cy, m_b, m_focal,
+                                         m_minPitch, m_maxPitch, fb, (is_road_params*)d_road, d_status, s));
+}
+
+void RoadEstimation::PitchGate(float& min_pitch, float& max_pitch) {
+    max_pitch = 50 * kPi / 180.0f; /* RE.cu:47-57 */
+    min_pitch = -50 * kPi / 180.0f;
+}
+
+int RoadEstimation::ChooseLineShared(float camera_center_y, float baseline, float focal, int rows, float min_pitch,
+                                     float max_pitch, const float* lines, int total, int overflow, int max_lines,
+                                     const Stixels::RoadParameters& fallback, Stixels::RoadParameters& out,
+                                     int* index) { /* k_road_choose, line by line */
+    const float step = kPi / 180;
+    const int numangle = (int)lrint((3.1415926535897932384626433832795 - 0.0) / step); /* as HoughLines */
+    out = fallback;
+    if (index) *index = -1;
+    const int nl = overflow ? 0 : std::min(total, max_lines);
+    for (int k = 0; k < nl; k++) {
+        const float rho = std::abs(lines[2 * k]);
+        const float theta = lines[2 * k + 1];
+        const int n = is_road_angle_index(theta, step, numangle);
+        if (n < 0) continue;
+        const float line_theta = 0.0f + n * step; /* (== theta; the expression of the device's table) */
+        is_road_params r = {0, 0.0f, 0.0f, 0.0f};
+        int vhor_ok = 0;
+        if (!is_road_line(rho, sinf(line_theta), cosf(line_theta), camera_center_y, baseline, focal, rows, min_pitch,
+                          max_pitch, &r, &vhor_ok))
+            continue;
+        if (index) *index = k;
+        if (!vhor_ok) return IS_ROAD_HORIZON;
+        out = Stixels::RoadParameters{r.vhor, r.tilt, r.height, r.alpha};
+        return IS_ROAD_OK;
+    }
+    return overflow || total > max_lines ? IS_ROAD_UNDECIDED : IS_ROAD_NONE;
+}
+
+void RoadEstimation::ComputeBatch(const pixel_t* d_im, int n_images, Stixels::RoadParameters* out, uint8_t* ok,
+                                  void* stream) {
+    if (!m_is_initialized) throw std::invalid_argument("RoadEstimation::ComputeBatch before Initialize()");
+    if (n_images < 1 || !d_im || !out || !ok) throw std::invalid_argument("ComputeBatch: empty batch or null pointer");
+    const DeviceGuard guard(m_ctx_device);
+    void* s = stream ? stream : m_stream;
+    const int L = m_batch_lines;
+    ReserveBatch(n_images);
     const int cap = m_batch_cap;
     int* d_total = (int*)d_batch_out.get();
     int* d_overflow = d_total + cap;

@@ -19,6 +19,7 @@
 #include <thread>
 
 #include "DeviceGuard.h"
+#include "is_ground_model.h"
 
 Stixels::Stixels() {}
 Stixels::~Stixels() {} /* like the reference, buffers are released by Finish(), Stixels.cu:36-37 */
@@ -220,6 +221,19 @@ void Stixels::PrecomputeGround(int vhor_lib, float camera_tilt, float camera_hei
     }
 }
 
+is_ground_params Stixels::GroundParams() const {
+    return is_ground_params{m_focal, m_baseline, m_max_disf, m_pout, m_sigma_disparity_ground, m_sigma_camera_height,
+                            m_sigma_camera_tilt};
+}
+
+void Stixels::PrecomputeGroundShared(const is_ground_params& g, const float* log_lut, int lut_entries, int rows,
+                                     int vhor_lib, float camera_tilt, float camera_height, float alpha_ground,
+                                     float* function, float* normalization, float* inv_sigma2, int* range_index) {
+    for (int v = 0; v < rows; v++)
+        is_ground_row(&g, log_lut, lut_entries, vhor_lib, camera_tilt, camera_height, alpha_ground, v, function + v,
+                      normalization + v, inv_sigma2 + v, range_index ? range_index + v : nullptr);
+}
+
 void Stixels::GetGroundModel(std::vector<float>& ground_function,
                              std::vector<float>& normalization_ground,
                              std::vector<float>& inv_sigma2_ground, int& vhor_lib) {
@@ -347,6 +361,11 @@ void Stixels::InitializeBatch(int max_batch) { /* Stixels.cu:43-248 */
     h_instance_head.reserve(B * 16);
     h_instance_packed.reserve(1 + 3 * inst_n);
     h_instance_packed.get()[0] = 0;
+    /* ComputeBatchRoad: the constants and the FastLog table of the device ground model, once per context */
+    const is_ground_params gp = GroundParams();
+    IS_CHECK_RETURN(is_ctx_set_ground_model(m_ctx, &gp, m_log_lut.data(), (int)m_log_lut.size()));
+    h_road.reserve(B * (sizeof(RoadParameters) + 1));
+    m_road_vhor_hint = -1;
     m_ground_valid = false; /* (the ground model depends on the configuration just applied) */
     m_is_initialized = true;
 }
@@ -564,6 +583,45 @@ void Stixels::ComputeBatch(bool pairwise, int n_images, const pixel_t* d_big,
     std::vector<float> alpha(n_images);
     for (int i = 0; i < n_images; i++) alpha[i] = road[i].alpha_ground;
     RememberBatch(n_images, instance_stixels != nullptr, alpha.data(), vh.data());
+    DeliverBatch(n_images, road, false, out, stream, instance_stixels);
+}
+
+void Stixels::ComputeBatchRoad(bool pairwise, int n_images, const pixel_t* d_big, const int32_t* d_seg,
+                               const RoadParameters* d_road, const uint8_t* d_status, std::vector<StixelsData>& out,
+                               void* stream, std::vector<InstanceMapping>* instance_stixels,
+                               std::vector<RoadParameters>* road_out, std::vector<uint8_t>* status_out) {
+    if (n_images < 1 || n_images > m_max_batch)
+        throw std::invalid_argument("n_images outside [1, max_batch] of InitializeBatch().");
+    if (!d_road || !d_status) throw std::invalid_argument("ComputeBatchRoad: null road parameters or status.");
+    const DeviceGuard guard(m_ctx_device);
+    if (stream == nullptr) stream = m_stream;
+    ForgetBatch(); /* (the road of this batch is known behind the synchronisation: DeliverBatch records it) */
+    IS_CHECK_RETURN(is_join_columns(m_ctx, d_big, m_cols, m_median_join ? 1 : 0, d_disparity.get(),
+                                    n_images, stream));
+    std::vector<is_instance_buffers> ibs;
+    if (instance_stixels)
+        for (int i = 0; i < n_images; i++) ibs.push_back(InstanceBuffers(i));
+    static_assert(sizeof(RoadParameters) == sizeof(is_road_params), "d_road holds is_road_params records");
+    IS_CHECK_RETURN(is_compute_road(m_ctx, d_disparity.get(), d_seg, (const is_road_params*)d_road, pairwise ? 1 : 0,
+                                    n_images, d_stixels, instance_stixels ? ibs.data() : nullptr, nullptr, nullptr,
+                                    m_road_vhor_hint, stream));
+    /* the road records and the status bytes: one small pinned block, in the queue of the pack offsets */
+    RoadParameters* h_rp = (RoadParameters*)h_road.get();
+    uint8_t* h_st = (uint8_t*)(h_rp + m_max_batch);
+    IS_CHECK_RETURN(is_memcpy_d2h(h_rp, d_road, (size_t)n_images * sizeof(RoadParameters), stream));
+    IS_CHECK_RETURN(is_memcpy_d2h(h_st, d_status, (size_t)n_images, stream));
+    DeliverBatch(n_images, h_rp, true, out, stream, instance_stixels);
+    /* the horizons of this batch plan the next one's launches (a road moves slowly from batch to batch; the hint
+     * decides launch geometry only, never results) */
+    m_road_vhor_hint = m_rows;
+    for (int i = 0; i < n_images; i++) m_road_vhor_hint = std::min(m_road_vhor_hint, m_rows - h_rp[i].vhor - 1);
+    m_road_vhor_hint = std::max(m_road_vhor_hint, 0);
+    if (road_out) road_out->assign(h_rp, h_rp + n_images);
+    if (status_out) status_out->assign(h_st, h_st + n_images);
+}
+
+void Stixels::DeliverBatch(int n_images, const RoadParameters* road, bool remember, std::vector<StixelsData>& out,
+                           void* stream, std::vector<InstanceMapping>* instance_stixels) {
     /* Results to the host COMPACTED and through pinned memory: a column uses 10-60 of its 200 slots, and the
      * reference's fixed-stride copy (Stixels.cu:629-633: one frame) would move 1.6 MB per frame into pageable
      * vectors.  is_pack_sections leaves per-column offsets + the used sections; two pinned copies (the offsets, then
@@ -578,6 +636,13 @@ void Stixels::ComputeBatch(bool pairwise, int n_images, const pixel_t* d_big,
         IS_CHECK_RETURN(is_memcpy_d2h(h_instance_head.get(), d_instances_per_class,
                                       (size_t)n_images * m_instance_classes * sizeof(int32_t), stream));
     IS_CHECK_RETURN(is_stream_synchronize(stream));
+    std::vector<int> vh(n_images);
+    for (int i = 0; i < n_images; i++) vh[i] = m_rows - road[i].vhor - 1;
+    if (remember) {
+        std::vector<float> alpha(n_images);
+        for (int i = 0; i < n_images; i++) alpha[i] = road[i].alpha_ground;
+        RememberBatch(n_images, instance_stixels != nullptr, alpha.data(), vh.data());
+    }
     const size_t total = (size_t)offsets[ncols];
     m_last.known_offsets.resize(n_images + 1);
     for (int i = 0; i <= n_images; i++) m_last.known_offsets[i] = offsets[(size_t)i * m_realcols];

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "instance_stixels_core.h"
+#include "is_numerics.h"
 #include "InstanceStixels/RoadEstimation.h"
 #include "InstanceStixels/Stixels.hpp"
 
@@ -643,6 +644,134 @@ int ire_choose_line(float cy, float baseline, float focal, int rows, const float
     std::vector<std::pair<float, float>> l((size_t)std::max(n, 0));
     for (int i = 0; i < n; i++) l[i] = std::make_pair(lines[2 * i], lines[2 * i + 1]);
     return RoadEstimation::ChooseLine(cy, baseline, focal, rows, l.data(), l.size(), *(Stixels::RoadParameters*)out);
+}
+
+/* ---- the device-resident road chain: the shared numerics and the host twins, for tests and callers ---- */
+float ish_erff(float x) { return is_erff(x); }
+float ish_atanf(float x) { return is_atanf(x); }
+float ish_cosf(float x) { return is_cosf(x); }
+void ish_erff_n(const float* x, float* out, size_t n) { for (size_t i = 0; i < n; i++) out[i] = is_erff(x[i]); }
+void ish_atanf_n(const float* x, float* out, size_t n) { for (size_t i = 0; i < n; i++) out[i] = is_atanf(x[i]); }
+void ish_cosf_n(const float* x, float* out, size_t n) { for (size_t i = 0; i < n; i++) out[i] = is_cosf(x[i]); }
+
+/* Stixels::PrecomputeGroundShared with the object's constants and FastLog table (after PrecomputeHost() or
+ * Initialize()): gf / ng / ig [rows], range_index [rows] or null */
+int ish_precompute_ground_shared(void* h, int vhor_lib, float tilt, float height, float alpha, float* gf, float* ng,
+                                 float* ig, int* range_index) {
+    return guard([&] {
+        Stixels* s = (Stixels*)h;
+        const std::vector<float>& lut = s->GetLogLUT();
+        if (lut.empty()) throw std::invalid_argument("ish_precompute_ground_shared before PrecomputeHost()");
+        Stixels::PrecomputeGroundShared(s->GroundParams(), lut.data(), (int)lut.size(), s->GetParameters().rows,
+                                        vhor_lib, tilt, height, alpha, gf, ng, ig, range_index);
+    });
+}
+int ish_ground_params(void* h, is_ground_params* out) {
+    return guard([&] { *out = ((Stixels*)h)->GroundParams(); });
+}
+/* the object's FastLog table: returns its entries; copies min(cap, entries) of them when out is not null */
+int ish_log_lut(void* h, float* out, int cap) {
+    const std::vector<float>& lut = ((Stixels*)h)->GetLogLUT();
+    if (out) std::memcpy(out, lut.data(), sizeof(float) * std::min<size_t>(lut.size(), (size_t)std::max(cap, 0)));
+    return (int)lut.size();
+}
+
+/* ComputeBatchRoad(): as ish_compute_batch with d_road [n] records / d_status [n] bytes on the device; road_out
+ * [n][4] floats (vhor_image, tilt, height, alpha), status_out [n], alpha_ground [n]: from the copy the call fetched */
+int ish_compute_batch_road(void* h, int pairwise, int n_images, const float* d_big, const int32_t* d_seg,
+                           const void* d_road, const uint8_t* d_status, Section* sections, int* vhor_lib,
+                           float* alpha_ground, float* road_out, uint8_t* status_out, int* triples, int cap,
+                           int* counts, void* stream) {
+    return guard([&] {
+        Stixels* s = (Stixels*)h;
+        std::vector<StixelsData> out;
+        std::vector<Stixels::InstanceMapping> maps;
+        std::vector<Stixels::RoadParameters> rp;
+        std::vector<uint8_t> st;
+        s->ComputeBatchRoad(pairwise != 0, n_images, d_big, d_seg, (const Stixels::RoadParameters*)d_road, d_status,
+                            out, stream, triples ? &maps : nullptr, &rp, &st);
+        for (int i = 0; i < n_images; i++) {
+            std::memcpy(sections + (size_t)i * out[i].sections.size(), out[i].sections.data(),
+                        out[i].sections.size() * sizeof(Section));
+            vhor_lib[i] = out[i].vhor;
+            alpha_ground[i] = out[i].alpha_ground;
+            road_out[4 * i] = (float)rp[i].vhor; road_out[4 * i + 1] = rp[i].camera_tilt;
+            road_out[4 * i + 2] = rp[i].camera_height; road_out[4 * i + 3] = rp[i].alpha_ground;
+            status_out[i] = st[i];
+            if (triples) {
+                int n = 0;
+                for (const auto& kv : maps[i]) {
+                    if (n >= cap) break;
+                    int* t = triples + ((size_t)i * cap + n) * 3;
+                    t[0] = kv.first.first; t[1] = kv.first.second; t[2] = kv.second;
+                    n++;
+                }
+                counts[i] = (int)maps[i].size();
+            }
+        }
+    });
+}
+
+/* RoadEstimation::ComputeBatchDevice: d_road [n] records, d_status [n] bytes (device); fallback4 = (vhor_image, tilt,
+ * height, alpha) */
+int ire_compute_batch_device(void* h, const float* d_disparity, int n, void* d_road, uint8_t* d_status,
+                             const float* fallback4, void* stream) {
+    return guard([&] {
+        const Stixels::RoadParameters fb = {(int)fallback4[0], fallback4[1], fallback4[2], fallback4[3]};
+        ((RoadEstimation*)h)->ComputeBatchDevice(d_disparity, n, (Stixels::RoadParameters*)d_road, d_status, fb,
+                                                 stream);
+    });
+}
+/* RoadEstimation::ChooseLineShared with the pitch gate of Initialize(): returns the status (IS_ROAD_*); out: one
+ * record; *index: the accepted line or -1 */
+int ire_choose_line_shared(float cy, float baseline, float focal, int rows, const float* lines, int total,
+                           int overflow, int max_lines, const float* fallback4, void* out, int* index) {
+    float lo, hi;
+    RoadEstimation::PitchGate(lo, hi);
+    const Stixels::RoadParameters fb = {(int)fallback4[0], fallback4[1], fallback4[2], fallback4[3]};
+    return RoadEstimation::ChooseLineShared(cy, baseline, focal, rows, lo, hi, lines, total, overflow, max_lines, fb,
+                                            *(Stixels::RoadParameters*)out, index);
+}
+void ire_pitch_gate(float* lo, float* hi) { RoadEstimation::PitchGate(*lo, *hi); }
+
+/* Times the road estimation + stixel computation of one resident batch, n_iter times, as a C++ caller's loop would
+ * run it (outputs reused).  device_chain 0: RoadEstimation::ComputeBatch + Stixels::ComputeBatch; 1:
+ * ComputeBatchDevice + ComputeBatchRoad on one stream (d_road [n] records, d_status [n] bytes: device scratch of the
+ * caller).  One warm-up call, then s_each [n_iter]: seconds of every call by the host clock (each ends in the
+ * synchronisation that delivers the Sections). */
+int ish_time_road_chain(void* h, void* hre, int device_chain, int pairwise, int n_images, const float* d_big,
+                        const int32_t* d_seg, void* d_road, uint8_t* d_status, const float* fallback4, int n_iter,
+                        int with_instances, double* s_each) {
+    return guard([&] {
+        Stixels* s = (Stixels*)h;
+        RoadEstimation* r = (RoadEstimation*)hre;
+        const Stixels::RoadParameters fb = {(int)fallback4[0], fallback4[1], fallback4[2], fallback4[3]};
+        std::vector<Stixels::RoadParameters> rp(n_images);
+        std::vector<uint8_t> ok(n_images);
+        std::vector<StixelsData> out;
+        std::vector<Stixels::InstanceMapping> maps;
+        /* one queue for both objects of the device chain: the order of the launches is all that joins them */
+        void* chain = nullptr;
+        if (device_chain && is_stream_create(&chain, 1) != IS_OK) throw std::runtime_error(is_last_error());
+        struct Release { void* s; ~Release() { if (s) (void)is_stream_destroy(s); } } release{chain};
+        for (int i = -1; i < n_iter; i++) {
+            timespec t0, t1;
+            clock_gettime(CLOCK_MONOTONIC, &t0);
+            if (device_chain) {
+                r->ComputeBatchDevice(d_big, n_images, (Stixels::RoadParameters*)d_road, d_status, fb, chain);
+                s->ComputeBatchRoad(pairwise != 0, n_images, d_big, d_seg, (const Stixels::RoadParameters*)d_road,
+                                    d_status, out, chain, with_instances ? &maps : nullptr);
+            } else {
+                r->ComputeBatch(d_big, n_images, rp.data(), ok.data(), nullptr);
+                for (int k = 0; k < n_images; k++)
+                    if (!ok[k]) rp[k] = fb; /* (what a live caller does with a frame without a road) */
+                s->ComputeBatch(pairwise != 0, n_images, d_big, d_seg, rp.data(), out, nullptr,
+                                with_instances ? &maps : nullptr);
+            }
+            clock_gettime(CLOCK_MONOTONIC, &t1);
+            if (i >= 0) s_each[i] = (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec);
+        }
+    });
 }
 
 } /* extern "C" */
