@@ -7,15 +7,13 @@
  * is_stixel_world read, so the upper-bound rows of the instance evaluation never leave the device.
  *
  * One wave per (frame, stixel column), four adjacent columns per workgroup: at w == 8 the four 32-byte row pieces
- * of a workgroup's columns are one 128-byte line.  The wave takes its column's sections 64 at a time, one header
- * per lane; a ballot finds the terminator and the sections of an instance class (11..18), and only those touch the
- * ground truth.  For such a section the lanes take the rectangle's rows 64 at a time (w == 8, 8-pixel aligned rows:
- * two 16-byte loads per row, else pixel by pixel), tally runs of equal votes in registers and add them into the
- * wave's LDS histogram: bin 0 = background, bin 1 + k = instance k of the section's class, 1024 bins of which 1001
- * are used.  The lanes then scan the bins interleaved (lane l: l, l + 64, ...; conflict-free), clearing what they
- * read; a wave reduction picks the largest count, the smaller bin on a tie (bincount().argmax()).  Lane 0 applies
- * the minimum-fraction rule in binary64 and the result lands in the register of the lane that owns the section, so
- * the map is written once, 64 consecutive slots per store.  No global atomics, no allocation, no synchronisation.
+ * of a workgroup's columns are one 128-byte line.  The walk over the column's sections and their pixels is
+ * is_stixel_walk.h; the wave's LDS histogram has bin 0 = background, bin 1 + k = instance k of the section's class,
+ * 1024 bins of which 1001 are used.  The lanes then scan the bins interleaved (lane l: l, l + 64, ...; conflict-free),
+ * clearing what they read; a wave reduction picks the largest count, the smaller bin on a tie (bincount().argmax()).
+ * Lane 0 applies the minimum-fraction rule in binary64 and the result lands in the register of the lane that owns the
+ * section, so the map is written once, 64 consecutive slots per store.  No global atomics, no allocation, no
+ * synchronisation.
  */
 #include <hip/hip_runtime.h>
 
@@ -23,6 +21,7 @@
 
 #include "instance_stixels_core.h"
 #include "is_launch.h"
+#include "is_stixel_walk.h"
 
 #define IS_AGT_WAVES 4      /* waves = stixel columns per workgroup */
 #define IS_AGT_BINS 1024    /* per wave: background + 1000 instance numbers, padded to 16 bins per lane */
@@ -38,27 +37,12 @@ struct AssignGtArgs {
 };
 
 /* the bin of one ground-truth pixel for a section whose class owns [lo, lo + 1000) */
-__device__ __forceinline__ int agt_bin(int v, int lo) {
+__device__ __forceinline__ unsigned agt_bin(int v, int lo) {
     const unsigned k = (unsigned)v - (unsigned)lo; /* v in [lo, lo + 1000)  <=>  k < 1000 */
-    return (v > 1000 && k < 1000u) ? 1 + (int)k : 0;
+    return (v > 1000 && k < 1000u) ? 1u + k : 0u;
 }
 
-__device__ __forceinline__ void agt_add(unsigned* bins, int& key, unsigned& run, int b) {
-    if (b == key) {
-        run++;
-        return;
-    }
-    if (run) atomicAdd(&bins[key], run);
-    key = b;
-    run = 1;
-}
-
-__device__ __forceinline__ void agt_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-/* VEC: w == 8, cols % 8 == 0 and a 16-byte aligned image: a row of the rectangle is two 16-byte loads */
+/* VEC: as isw_tally */
 template <bool VEC>
 __global__ __launch_bounds__(64 * IS_AGT_WAVES) void k_assign_gt(const AssignGtArgs a) {
     __shared__ unsigned s_bins[IS_AGT_WAVES][IS_AGT_BINS];
@@ -68,7 +52,7 @@ __global__ __launch_bounds__(64 * IS_AGT_WAVES) void k_assign_gt(const AssignGtA
     if (c >= a.realcols) return; /* (whole waves; the kernel has no workgroup barrier) */
     unsigned* const bins = s_bins[wave];
     for (int i = lane; i < IS_AGT_BINS; i += 64) bins[i] = 0;
-    agt_wave_sync();
+    isw_wave_sync();
 
     const size_t column = ((size_t)f * a.realcols + c) * a.S;
     const is_section* const col = a.sections + column;
@@ -77,52 +61,15 @@ __global__ __launch_bounds__(64 * IS_AGT_WAVES) void k_assign_gt(const AssignGtA
     for (int base = 0; base < a.S; base += 64) {
         const int i = base + lane;
         int label = -1, votes = 0;
-        int vB = 0, vT = 0, cls = 0;
-        bool term = false;
-        if (open && i < a.S) {
-            const int4 h = *(const int4*)&col[i]; /* type, vB, vT, disparity */
-            term = h.x == -1;
-            vB = h.y;
-            vT = h.z;
-            cls = col[i].semantic_class;
-        }
-        uint64_t todo = 0;
-        if (open) {
-            const uint64_t terms = __ballot(term);
-            const uint64_t front = terms ? (terms & (0 - terms)) - 1 : ~0ull; /* lanes in front of the terminator */
-            todo = __ballot(i < a.S && cls >= IS_FIRST_INSTANCE_CLASS &&
-                            cls < IS_FIRST_INSTANCE_CLASS + IS_INSTANCE_CLASSES) & front;
-            if (terms) open = false;
-        }
+        int vB, vT, cls;
+        uint64_t todo = isw_round(col, i, a.S, open, vB, vT, cls);
         while (todo) {
             const int src = __builtin_ctzll(todo);
             todo &= todo - 1;
             const int sB = __shfl(vB, src, 64), sT = __shfl(vT, src, 64), sC = __shfl(cls, src, 64);
             const int lo = a.label_ids[sC - IS_FIRST_INSTANCE_CLASS] * 1000;
-            /* rows [rows-1-vT, rows-1-vB] of the image, clipped to the frame (64-bit: hostile vB / vT) */
-            const long long top = max((long long)a.rows - 1 - sT, 0ll);
-            const long long bot = min((long long)a.rows - 1 - sB, (long long)a.rows - 1);
-            if (top > bot) continue; /* an empty rectangle: -1, no vote */
-            int key = 0;
-            unsigned run = 0;
-            for (int y = (int)top + lane; y <= (int)bot; y += 64) {
-                const int32_t* const row = img + (size_t)y * a.cols;
-                if (VEC) {
-                    const int4 p = ((const int4*)row)[0], q = ((const int4*)row)[1];
-                    agt_add(bins, key, run, agt_bin(p.x, lo));
-                    agt_add(bins, key, run, agt_bin(p.y, lo));
-                    agt_add(bins, key, run, agt_bin(p.z, lo));
-                    agt_add(bins, key, run, agt_bin(p.w, lo));
-                    agt_add(bins, key, run, agt_bin(q.x, lo));
-                    agt_add(bins, key, run, agt_bin(q.y, lo));
-                    agt_add(bins, key, run, agt_bin(q.z, lo));
-                    agt_add(bins, key, run, agt_bin(q.w, lo));
-                } else {
-                    for (int k = 0; k < a.w; k++) agt_add(bins, key, run, agt_bin(row[k], lo));
-                }
-            }
-            if (run) atomicAdd(&bins[key], run);
-            agt_wave_sync();
+            const auto bin = [lo](int v) { return agt_bin(v, lo); };
+            if (!isw_tally<VEC, 0>(img, a.rows, a.cols, a.w, sB, sT, lane, bins, bin)) continue; /* empty: no vote */
             /* the largest count, the smaller bin on a tie: (count << 10 | 1023 - bin), maximised */
             unsigned long long best = 0;
             for (int j = 0; j < IS_AGT_BINS / 64; j++) {
@@ -139,7 +86,7 @@ __global__ __launch_bounds__(64 * IS_AGT_WAVES) void k_assign_gt(const AssignGtA
                 const unsigned long long other = __shfl_xor(best, o, 64);
                 best = other > best ? other : best;
             }
-            agt_wave_sync();
+            isw_wave_sync();
             const int win = IS_AGT_BINS - 1 - (int)(best & (IS_AGT_BINS - 1));
             const long long count = (long long)(best >> 10);
             /* the winner must NOT have fewer than (min_fraction * w) * (vT - vB) pixels (binary64, this order) */

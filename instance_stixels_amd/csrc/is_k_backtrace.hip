@@ -1,5 +1,6 @@
 /* is_k_backtrace.hip -- back-tracing of the DP tables into Sections, instance candidates.
  * See is_kernels.h. */
+#include "is_dbscan.h"
 #include "is_kernels.h"
 
 /* ====================================================================================== */
@@ -224,7 +225,7 @@ __global__ __launch_bounds__(ISC_THREADS) void k_compact_instances(
                     ib.d_centerofmass[o * 2 + 1] = s.instance_meany;
                 }
                 if (ib.d_indices) { ib.d_indices[o * 2] = c; ib.d_indices[o * 2 + 1] = i; }
-                if (ib.d_core_candidates) ib.d_core_candidates[o] = (s.vT + 1 - s.vB) >= P.size_filter;
+                if (ib.d_core_candidates) ib.d_core_candidates[o] = is_core_candidate(s.vB, s.vT, P.size_filter);
             }
             if (term) break;
         }

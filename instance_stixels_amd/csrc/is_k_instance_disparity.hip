@@ -16,15 +16,14 @@
  *                             only, so the histograms do not depend on the order of arrival;
  *   k_idisp_key_median        one wave per slot: four bins per lane, a wave scan, the two middle ranks -> their sum,
  *                             the median in HALF units (np.median averages the middle pair), into key -> median;
- *   k_idisp_stixel            the walk of k_assign_gt: one wave per (frame, stixel column), only sections of classes
- *                             11..18 touch memory; every pixel's value is median[key(pixel)], collected in a 512-bin
- *                             LDS histogram of half units per wave, read back interleaved (lane l: l, l + 64, ...:
- *                             conflict-free) and scanned chunk by chunk; the two middle ranks' sum * 0.25 is the
- *                             stixel's median, an integer number of quarter units, exact in fp32;
- *   k_idisp_cluster           the rules at the top of is_k_cluster.hip over three coordinates: the candidates whose
- *                             stixel median is 0 take no part (never large, core, neighbour or nearest-core target;
- *                             label -1).  It derives the core-candidate flag as k_recore does and writes d_labels,
- *                             d_core_candidates and d_packed as is_recluster leaves them.
+ *   k_idisp_stixel            the walk of is_stixel_walk.h, one wave per (frame, stixel column): every pixel's value
+ *                             is median[key(pixel)], collected in a 512-bin LDS histogram of half units per wave
+ *                             (the values < 1, bins 0 and 1, are dropped, :1012-1013), read back interleaved (lane l:
+ *                             l, l + 64, ...: conflict-free) and scanned chunk by chunk; the two middle ranks' sum *
+ *                             0.25 is the stixel's median, an integer number of quarter units, exact in fp32;
+ *   k_idisp_cluster           the clustering of is_dbscan.h over three coordinates: the candidates whose stixel
+ *                             median is 0 take no part.  It derives the core-candidate flag as k_recore does and
+ *                             writes d_labels, d_core_candidates and d_packed as is_recluster leaves them.
  *
  * The instance-disparity image of the reference is never built: a pixel's value is median[key(pixel)].
  */
@@ -33,15 +32,16 @@
 #include <stdint.h>
 
 #include "instance_stixels_core.h"
+#include "is_dbscan.h"
 #include "is_launch.h"
+#include "is_stixel_walk.h"
 
 #define IDK_KEYS IS_INSTANCE_DISPARITY_KEYS
 #define IDK_WORDS 256        /* bitmap words per frame: 250 used, one per lane of k_idisp_rank */
 #define IDK_BINS 256         /* disparity bins of a slot */
 #define IDK_WAVES 4          /* waves per workgroup of k_idisp_key_median and k_idisp_stixel */
 #define IDK_HALF_BINS 512    /* per wave: half units 0 .. 510 */
-#define IDK_THREADS 256
-#define IDK_LDS_N 2048       /* as CLU_LDS_N of is_k_cluster.hip */
+#define IDK_THREADS 256      /* of k_idisp_pixels */
 #define IDK_TABLE_IMAGES 32  /* frames per k_idisp_cluster launch: their arrays travel as a kernel argument */
 
 static_assert(IDK_KEYS == 8 * 1000 && IDK_KEYS <= 32 * IDK_WORDS && IDK_KEYS <= 65535, "keys: 8 classes x 1000");
@@ -261,22 +261,7 @@ struct IdispStixelArgs {
     IdispScratch s;
 };
 
-__device__ __forceinline__ void idk_add(unsigned* bins, unsigned& key, unsigned& run, unsigned b) {
-    if (b == key) {
-        run++;
-        return;
-    }
-    if (run && key >= 2u) atomicAdd(&bins[key], run); /* values < 1 are dropped (:1012-1013) */
-    key = b;
-    run = 1;
-}
-
-__device__ __forceinline__ void idk_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-/* VEC: w == 8, cols % 8 == 0 and a 16-byte aligned image, as k_assign_gt */
+/* VEC: as isw_tally */
 template <bool VEC>
 __global__ __launch_bounds__(64 * IDK_WAVES) void k_idisp_stixel(const IdispStixelArgs a) {
     __shared__ unsigned s_bins[IDK_WAVES][IDK_HALF_BINS];
@@ -287,7 +272,7 @@ __global__ __launch_bounds__(64 * IDK_WAVES) void k_idisp_stixel(const IdispStix
     if (c >= a.realcols) return; /* (whole waves; the kernel has no workgroup barrier) */
     unsigned* const bins = s_bins[wave];
     for (int i = lane; i < IDK_HALF_BINS; i += 64) bins[i] = 0;
-    idk_wave_sync();
+    isw_wave_sync();
 
     const size_t column = ((size_t)f * a.realcols + c) * a.S;
     const is_section* const col = a.sections + column;
@@ -297,51 +282,17 @@ __global__ __launch_bounds__(64 * IDK_WAVES) void k_idisp_stixel(const IdispStix
     for (int base = 0; base < a.S; base += 64) {
         const int i = base + lane;
         float result = 0.0f;
-        int vB = 0, vT = 0, cls = 0;
-        bool term = false;
-        if (open && i < a.S) {
-            const int4 h = *(const int4*)&col[i]; /* type, vB, vT, disparity */
-            term = h.x == -1;
-            vB = h.y;
-            vT = h.z;
-            cls = col[i].semantic_class;
-        }
-        uint64_t todo = 0;
-        if (open) {
-            const uint64_t terms = __ballot(term);
-            const uint64_t front = terms ? (terms & (0 - terms)) - 1 : ~0ull; /* lanes in front of the terminator */
-            todo = __ballot(i < a.S && cls >= IS_FIRST_INSTANCE_CLASS &&
-                            cls < IS_FIRST_INSTANCE_CLASS + IS_INSTANCE_CLASSES) & front;
-            if (terms) open = false;
-        }
+        int vB, vT, cls;
+        uint64_t todo = isw_round(col, i, a.S, open, vB, vT, cls);
         while (todo) {
             const int src = __builtin_ctzll(todo);
             todo &= todo - 1;
             const int sB = __shfl(vB, src, 64), sT = __shfl(vT, src, 64);
-            /* rows [rows-1-vT, rows-1-vB] of the image, clipped to the frame (64-bit: hostile vB / vT) */
-            const long long top = max((long long)a.rows - 1 - sT, 0ll);
-            const long long bot = min((long long)a.rows - 1 - sB, (long long)a.rows - 1);
-            if (top > bot) continue; /* an empty rectangle: 0 */
-            unsigned key = 0, run = 0;
-            for (int y = (int)top + lane; y <= (int)bot; y += 64) {
-                const int32_t* const row = img + (size_t)y * a.cols;
-                if (VEC) {
-                    const int4 p = ((const int4*)row)[0], q = ((const int4*)row)[1];
-                    const int v[8] = {p.x, p.y, p.z, p.w, q.x, q.y, q.z, q.w};
-#pragma unroll
-                    for (int k = 0; k < 8; k++) {
-                        const int g = idk_key(v[k]);
-                        idk_add(bins, key, run, g >= 0 ? (unsigned)median[g] : 0u);
-                    }
-                } else {
-                    for (int k = 0; k < a.w; k++) {
-                        const int g = idk_key(row[k]);
-                        idk_add(bins, key, run, g >= 0 ? (unsigned)median[g] : 0u);
-                    }
-                }
-            }
-            if (run && key >= 2u) atomicAdd(&bins[key], run);
-            idk_wave_sync();
+            const auto half_units = [median](int v) { /* values < 1 are dropped (:1012-1013): MIN_BIN = 2 */
+                const int g = idk_key(v);
+                return g >= 0 ? (unsigned)median[g] : 0u;
+            };
+            if (!isw_tally<VEC, 2>(img, a.rows, a.cols, a.w, sB, sT, lane, bins, half_units)) continue; /* empty: 0 */
             /* the bins in chunks of 64, lane l the bin 64 j + l of chunk j; incl: the prefix in bin order */
             unsigned n[IDK_HALF_BINS / 64], incl[IDK_HALF_BINS / 64], N = 0;
 #pragma unroll
@@ -352,7 +303,7 @@ __global__ __launch_bounds__(64 * IDK_WAVES) void k_idisp_stixel(const IdispStix
                 incl[j] = N + sc;
                 N += __shfl(sc, 63, 64);
             }
-            idk_wave_sync();
+            isw_wave_sync();
             unsigned half = 0;
             if (N) {
                 const unsigned r[2] = {(N - 1) / 2, N / 2};
@@ -371,156 +322,30 @@ __global__ __launch_bounds__(64 * IDK_WAVES) void k_idisp_stixel(const IdispStix
     }
 }
 
-/* ---- the clustering: cluster_body of is_k_cluster.hip with a third coordinate and a participation mask ---- */
-typedef float idk_f2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) idk_f2 idk_lds_f2;
-typedef __attribute__((address_space(3))) float idk_lds_f;
-typedef __attribute__((address_space(3))) uint8_t idk_lds_u8;
-typedef __attribute__((address_space(3))) int32_t idk_lds_i32;
-
-__device__ __forceinline__ float idk_d2(const idk_f2 a, const float az, const idk_f2 b, const float bz) {
-    const float dx = a.x - b.x, dy = a.y - b.y, dz = az - bz;
-    return dx * dx + dy * dy + dz * dz;
-}
-
-/* labels doubles as the component array while the kernel runs:
- *   >= 0  core point, value = smallest core index known to be in the same cluster
- *   -2    large, not core        -3   small        -4   no part: its stixel median is 0
- * rank / out are scratch of n ints each. */
-template <class XY, class Z, class CAND, class LAB>
-__device__ __forceinline__ void idisp_cluster_body(int n, float eps2, int min_pts, XY xy, Z z, CAND cand, LAB labels,
-                                                   int32_t* const labels_out, int32_t* rank, int32_t* out,
-                                                   int* s_red) {
-    const int tid = threadIdx.x;
-    /* number of large points among those that take part: the twin clusters only if it exceeds min_pts (:931) */
-    int cnt = 0;
-    for (int i = tid; i < n; i += IDK_THREADS) cnt += cand[i] != 0 && z[i] != 0.0f;
-    s_red[tid] = cnt;
-    __syncthreads();
-    for (int s = IDK_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) s_red[tid] += s_red[tid + s];
-        __syncthreads();
-    }
-    const int n_large = s_red[0];
-    __syncthreads();
-    if (n_large <= min_pts) {
-        for (int i = tid; i < n; i += IDK_THREADS) labels_out[i] = -1;
-        return;
-    }
-
-    /* core points */
-    for (int i = tid; i < n; i += IDK_THREADS) {
-        const float pz = z[i];
-        int l = pz != 0.0f ? -3 : -4;
-        if (l == -3 && cand[i]) {
-            const idk_f2 p = xy[i];
-            int c = 0;
-            for (int j = 0; j < n; j++) {
-                const float qz = z[j];
-                c += (cand[j] != 0) && (qz != 0.0f) && (idk_d2(p, pz, xy[j], qz) <= eps2);
-            }
-            l = (c >= min_pts) ? i : -2;
-        }
-        labels[i] = l;
-    }
-    __syncthreads();
-
-    /* connected components of the core points: minimum-index propagation with pointer jumping;
-     * labels only ever decrease, so reading a neighbour's value mid-update is harmless */
-    for (;;) {
-        int changed = 0;
-        for (int i = tid; i < n; i += IDK_THREADS) {
-            const int li = labels[i];
-            if (li < 0) continue;
-            const idk_f2 p = xy[i];
-            const float pz = z[i];
-            int m = li;
-            for (int j = 0; j < n; j++) {
-                const int lj = labels[j];
-                if (lj >= 0 && lj < m && idk_d2(p, pz, xy[j], z[j]) <= eps2) m = lj;
-            }
-            while (labels[m] < m) m = labels[m]; /* jump to the current root */
-            if (m < li) { labels[i] = m; changed = 1; }
-        }
-        if (!__syncthreads_or(changed)) break;
-    }
-
-    /* cluster number = rank of the root (smallest core index of the cluster) among the roots */
-    {
-        const int per = (n + IDK_THREADS - 1) / IDK_THREADS;
-        const int lo = min(tid * per, n), hi = min(lo + per, n);
-        int c = 0;
-        for (int i = lo; i < hi; i++) c += labels[i] == i;
-        s_red[tid] = c;
-        __syncthreads();
-        int base = 0;
-        for (int t = 0; t < tid; t++) base += s_red[t];
-        for (int i = lo; i < hi; i++) {
-            rank[i] = base;
-            base += labels[i] == i;
-        }
-    }
-    __syncthreads();
-
-    for (int i = tid; i < n; i += IDK_THREADS) {
-        const int li = labels[i];
-        int res = -1;
-        if (li >= 0) {
-            res = rank[li];
-        } else if (li != -4) {
-            const idk_f2 p = xy[i];
-            const float pz = z[i];
-            if (li == -2) { /* border point: lowest-numbered cluster among the core neighbours */
-                int best = n;
-                for (int j = 0; j < n; j++) {
-                    const int lj = labels[j];
-                    if (lj >= 0 && lj < best && idk_d2(p, pz, xy[j], z[j]) <= eps2) best = lj;
-                }
-                if (best < n) res = rank[best];
-            } else { /* small point: nearest core point, first one on ties, within eps */
-                float bd = __builtin_inff();
-                int bj = -1;
-                for (int j = 0; j < n; j++) {
-                    if (labels[j] < 0) continue;
-                    const float d = idk_d2(p, pz, xy[j], z[j]);
-                    if (d < bd) { bd = d; bj = j; }
-                }
-                if (bj >= 0 && bd <= eps2) res = rank[labels[bj]];
-            }
-        }
-        out[i] = res;
-    }
-    __syncthreads();
-    for (int i = tid; i < n; i += IDK_THREADS) labels_out[i] = out[i];
-}
-
+/* ---- the clustering: dbs_body (is_dbscan.h) over (x, y, stixel median) ---- */
 struct IdispTable {
     is_instance_buffers ib[IDK_TABLE_IMAGES];
 };
 
 /* One workgroup per (instance class, frame): grid = (8, frames of the launch). */
-__global__ __launch_bounds__(IDK_THREADS) void k_idisp_cluster(const IdispTable tbl, int first_image, int n_slots,
+__global__ __launch_bounds__(DBS_THREADS) void k_idisp_cluster(const IdispTable tbl, int first_image, int n_slots,
                                                                int S, int size_filter, float eps2, int min_pts,
                                                                const is_section* __restrict__ sections,
                                                                const IdispScratch s) {
-    __shared__ int s_red[IDK_THREADS];
-    __shared__ idk_f2 s_xy[IDK_LDS_N];
-    __shared__ float s_z[IDK_LDS_N];
-    __shared__ int32_t s_lab[IDK_LDS_N];
-    __shared__ uint8_t s_cand[IDK_LDS_N];
+    __shared__ int s_red[DBS_THREADS];
+    __shared__ dbs_f2 s_xy[DBS_LDS_N];
+    __shared__ float s_z[DBS_LDS_N];
+    __shared__ int32_t s_lab[DBS_LDS_N];
+    __shared__ uint8_t s_cand[DBS_LDS_N];
     if (s.overflow[0]) return;
     const int cls = blockIdx.x, img = first_image + (int)blockIdx.y, tid = threadIdx.x;
     const is_instance_buffers ib = tbl.ib[blockIdx.y];
     const int32_t* per_class = ib.d_instances_per_class;
-    const int n = min(max(per_class[cls], 0), n_slots);
+    const int n = dbs_class_count(per_class, cls, n_slots);
     int base = 0, total = 0;
-    for (int k = 0; k < IS_INSTANCE_CLASSES; k++) {
-        const int m = min(max(per_class[k], 0), n_slots);
-        if (k < cls) base += m;
-        total += m;
-    }
+    DBS_CLASS_RANGE(per_class, cls, n_slots, base, total);
     const size_t o = (size_t)cls * n_slots;
-    const idk_f2* xy = reinterpret_cast<const idk_f2*>(ib.d_centerofmass) + o;
+    const dbs_f2* xy = reinterpret_cast<const dbs_f2*>(ib.d_centerofmass) + o;
     uint8_t* cand = ib.d_core_candidates + o;
     int32_t* labels = ib.d_labels + o;
     const int32_t* idx = ib.d_indices + o * 2;
@@ -530,38 +355,35 @@ __global__ __launch_bounds__(IDK_THREADS) void k_idisp_cluster(const IdispTable 
         int32_t* rank = s.rank + (size_t)img * 2 * n_slots + base;
         const is_section* frame = sections + (size_t)img * n_slots;
         const float* stixel = s.stixel + (size_t)img * n_slots;
-        for (int i = tid; i < n; i += IDK_THREADS) {
+        for (int i = tid; i < n; i += DBS_THREADS) {
             const int c = idx[2 * i], si = idx[2 * i + 1];
             float zz = 0.0f;
-            if (c >= 0 && si >= 0 && si < S && (size_t)c * S + si < (size_t)n_slots) { /* an index of this frame */
+            if (IS_FRAME_SLOT(c, si, S, n_slots)) {
                 const is_section* sec = frame + (size_t)c * S + si;
-                cand[i] = (sec->vT + 1 - sec->vB) >= size_filter; /* as k_recore */
+                cand[i] = is_core_candidate(sec->vB, sec->vT, size_filter);
                 zz = stixel[(size_t)c * S + si];
             }
             z[i] = zz;
         }
         __syncthreads();
         if (n == 0) {
-        } else if (n <= IDK_LDS_N) {
-            for (int i = tid; i < n; i += IDK_THREADS) { s_xy[i] = xy[i]; s_z[i] = z[i]; s_cand[i] = cand[i]; }
+        } else if (n <= DBS_LDS_N) {
+            for (int i = tid; i < n; i += DBS_THREADS) { s_xy[i] = xy[i]; s_z[i] = z[i]; s_cand[i] = cand[i]; }
             __syncthreads();
-            idisp_cluster_body(n, eps2, min_pts, (const idk_lds_f2*)s_xy, (const idk_lds_f*)s_z,
-                               (const idk_lds_u8*)s_cand, (idk_lds_i32*)s_lab, labels, rank, rank + n_slots, s_red);
+            dbs_body(n, eps2, min_pts,
+                     dbs_points3<const lds_float2*, const lds_float*>{(const lds_float2*)s_xy, (const lds_float*)s_z},
+                     (const lds_u8*)s_cand, (lds_i32*)s_lab, labels, rank, rank + n_slots, s_red);
         } else {
-            idisp_cluster_body(n, eps2, min_pts, xy, (const float*)z, (const uint8_t*)cand, labels, labels, rank,
-                               rank + n_slots, s_red);
+            dbs_body(n, eps2, min_pts, dbs_points3<const dbs_f2*, const float*>{xy, z}, (const uint8_t*)cand, labels,
+                     labels, rank, rank + n_slots, s_red);
         }
     } else {
-        for (int i = tid; i < n; i += IDK_THREADS) labels[i] = -1;
+        for (int i = tid; i < n; i += DBS_THREADS) labels[i] = -1;
     }
     int32_t* packed = ib.d_packed;
     if (packed) {
         __syncthreads();
-        if (cls == 0 && tid == 0) packed[0] = total;
-        for (int i = tid; i < n; i += IDK_THREADS) {
-            int32_t* t = packed + 1 + (size_t)(base + i) * 3;
-            t[0] = idx[2 * i]; t[1] = idx[2 * i + 1]; t[2] = labels[i];
-        }
+        DBS_EMIT_PACKED(packed, cls, n, base, total, idx, labels);
     }
 }
 
@@ -639,7 +461,7 @@ hipError_t isk_launch_instance_disparity(const is_instance_disparity_args* r, hi
         const int m = n - first < IDK_TABLE_IMAGES ? n - first : IDK_TABLE_IMAGES;
         IdispTable tbl = {};
         for (int i = 0; i < m; i++) tbl.ib[i] = r->instances[first + i];
-        hipLaunchKernelGGL(k_idisp_cluster, dim3(IS_INSTANCE_CLASSES, (unsigned)m), dim3(IDK_THREADS), 0, stream, tbl,
+        hipLaunchKernelGGL(k_idisp_cluster, dim3(IS_INSTANCE_CLASSES, (unsigned)m), dim3(DBS_THREADS), 0, stream, tbl,
                            first, n_slots, r->max_sections, r->size_filter, r->eps * r->eps, r->min_pts,
                            r->d_sections, s);
         if ((e = hipGetLastError()) != hipSuccess) return e;

@@ -31,6 +31,7 @@
 
 #include "instance_stixels_core.h"
 #include "is_launch.h"
+#include "is_stixel_walk.h"
 
 static_assert(sizeof(is_instance_object) == 64 && sizeof(is_contour_point) == 32 && sizeof(is_section) == 32,
               "the object kernels move 16-byte chunks");
@@ -67,11 +68,6 @@ struct ObjArgs {
 /* fp32 bits -> unsigned, monotone over the non-NaN floats (-0 below +0); 0 and ~0 are NaN patterns */
 __device__ __forceinline__ unsigned obj_ord(unsigned bits) { return (bits & 0x80000000u) ? ~bits : bits | 0x80000000u; }
 __device__ __forceinline__ unsigned obj_unord(unsigned o) { return (o & 0x80000000u) ? o & 0x7fffffffu : ~o; }
-
-__device__ __forceinline__ void obj_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 __device__ __forceinline__ unsigned obj_wave_sum(unsigned v) {
 #pragma unroll
@@ -171,7 +167,7 @@ __global__ __launch_bounds__(64 * IS_OBJ_WAVES) void k_obj_columns(const ObjArgs
     const int f = gcol / a.realcols, c = gcol - f * a.realcols;
     unsigned* const seen = s_seen[wave];
     for (int i = lane; i < IS_OBJ_KEYS / 32; i += 64) seen[i] = 0;
-    obj_wave_sync();
+    isw_wave_sync();
 
     const int4* const src = reinterpret_cast<const int4*>(a.sections + (size_t)gcol * a.S);
     const int32_t* const map = a.map + (size_t)gcol * a.S;
@@ -196,7 +192,7 @@ __global__ __launch_bounds__(64 * IS_OBJ_WAVES) void k_obj_columns(const ObjArgs
                     if (terms2) break;
                 }
                 if (lane == 0) seen[K >> 5] |= 1u << (K & 31);
-                obj_wave_sync();
+                isw_wave_sync();
             }
             const unsigned pixels = obj_wave_sum(acc.hsum) * (unsigned)a.w;
             if (POINTS) {

@@ -7,6 +7,7 @@
  * or the explicit "off" state (every E1 = +inf) of a column whose pruning is off whatever the weights are: a generic
  * column, a wrapped offset channel, a slack that is not finite.  k_prune_scale writes each set's records from them.
  */
+#include "is_dbscan.h"
 #include "is_kernels.h"
 
 #define SWP_THREADS 256
@@ -54,7 +55,7 @@ __global__ void k_sweep_state(int* __restrict__ n_generic, int* __restrict__ pat
 }
 
 /* One lane per candidate slot, grid = (chunks of the slots, 8 classes, n_images): the core-candidate flag of
- * k_compact_instances again, (vT + 1 - vB) >= size_filter, from the candidate's (column, section index). */
+ * k_compact_instances again (is_core_candidate, is_dbscan.h), from the candidate's (column, section index). */
 __global__ __launch_bounds__(SWP_THREADS) void k_recore(int n_slots, int S, int size_filter,
                                                         const is_section* __restrict__ sections,
                                                         const is_instance_buffers* __restrict__ tbl) {
@@ -66,9 +67,9 @@ __global__ __launch_bounds__(SWP_THREADS) void k_recore(int n_slots, int S, int 
     if (i >= n) return;
     const size_t o = (size_t)cls * n_slots + i;
     const int c = ib.d_indices[o * 2], si = ib.d_indices[o * 2 + 1];
-    if (c < 0 || si < 0 || si >= S || (size_t)c * S + si >= (size_t)n_slots) return; /* (not an index of this frame) */
+    if (!IS_FRAME_SLOT(c, si, S, n_slots)) return;
     const is_section* s = sections + (size_t)img * n_slots + (size_t)c * S + si;
-    ib.d_core_candidates[o] = (s->vT + 1 - s->vB) >= size_filter;
+    ib.d_core_candidates[o] = is_core_candidate(s->vB, s->vT, size_filter);
 }
 
 extern "C" {

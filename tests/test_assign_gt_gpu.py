@@ -130,6 +130,30 @@ def test_c_abi_sections_outside_the_frame_and_column_ends():
     _same(_c_abi(secs, gt, gt_offset=12), want)
 
 
+def test_c_abi_terminator_in_the_second_round_of_headers():
+    """Columns of 70 one-row instance-class stixels whose terminator is the 71st entry: the second round of 64 headers
+    finds it.  The sections in front of it in that round are voted on; the instance-class sections behind it, over
+    rows full of their own class, stay -1 with no vote.  Vector and pixel-by-pixel path."""
+    rows, C, S, w, live = 70, 3, 80, 8, 70
+    secs = np.zeros((1, C, S), SECTION_DTYPE)
+    secs["type"] = -1
+    gt = np.zeros((1, rows, C * w), np.int32)
+    for y in range(rows):                                # row y is stixel i = rows - 1 - y: its class, number i % 3
+        i = rows - 1 - y
+        gt[0, y] = ag.CITYSCAPES_LABEL_IDS[i % 8] * 1000 + i % 3
+    for c in range(C):
+        for i in range(S):
+            if i != live:                                # slot 70 stays the terminator
+                v = i % rows
+                secs[0, c, i] = (1, v, v, 1.0, 11 + v % 8, 0, 0, 0)
+    want = ag.assign(secs, gt)
+    np.testing.assert_array_equal(want[0][0, :, :live], np.tile(np.arange(live) % 3, (C, 1)))
+    assert (want[1][0, :, :live] == w).all()
+    assert (want[0][0, :, live:] == -1).all() and (want[1][0, :, live:] == 0).all()
+    _same(_c_abi(secs, gt), want)
+    _same(_c_abi(secs, gt, gt_offset=4), want)
+
+
 def _batch(preset, n, k, rows=1024, cols=2048, D=128):
     """A ComputeBatch of n frames of which k are distinct (frame i = frame i % k)."""
     torch, dev = _torch()

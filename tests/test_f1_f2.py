@@ -293,7 +293,7 @@ def test_device_clustering_equals_twin_random(seed):
 
 @pytest.mark.gpu
 def test_device_clustering_large_classes_global_memory_path():
-    """Classes with more candidates than the LDS copies hold (CLU_LDS_N = 2048, is_k_cluster.hip)
+    """Classes with more candidates than the LDS copies hold (DBS_LDS_N = 2048, is_dbscan.h)
     are clustered out of global memory: exactly 2048 (last LDS size), 2049 (first global size), a
     few thousand, next to small classes in the same launch."""
     cfg = make_config("drn_d_22_unary", 256, 1024, 64)

@@ -15,6 +15,8 @@ import render_reference as rr
 from instance_stixels_amd import core as core_mod
 from instance_stixels_amd import host, make_config
 from instance_stixels_amd.config import SECTION_DTYPE
+from oracle import oracle
+from test_instance_disparity_cpu import BANDED, banded_frame, class_labels
 
 pytestmark = pytest.mark.gpu
 
@@ -247,9 +249,16 @@ def test_a_stixel_of_height_one_and_one_of_full_height():
         secs[0, 1, i] = (1, i, i, 5.0, 13 if i % 2 else 12, 0, 12.0, float(i))
     secs[0, 2, 0] = (1, 0, 0, 5.0, 18, 0, 20.0, 0.0)
     secs[0, 2, 1] = (1, 1, rows - 1, 5.0, 18, 0, 20.0, 35.0)
+    # behind the terminators (slot 70 of column 1: found in the second round; slot 2 of column 2): full-height sections
+    # of an instance class, which are no stixels -- median 0, no candidate
+    secs[0, 1, 71] = (1, 0, rows - 1, 5.0, 13, 0, 12.0, 35.0)
+    secs[0, 2, 3] = (1, 0, rows - 1, 5.0, 18, 0, 20.0, 35.0)
     gt, disp = make_images(1, rows, cols, seed=21, n_rects=20)
     _, want = _core_case(secs, gt, disp, 9.0, 1, 1)
     assert (want["stixel_median"][0, 1] != 0).sum() > 10 and want["stixel_median"][0, 0, 0] != 0
+    # (column 1 has pixels >= 1, so its full-height rectangle would have a median had the walk gone on)
+    assert want["stixel_median"][0, 1, 71] == 0 and want["stixel_median"][0, 2, 3] == 0
+    assert len(want["packed"][0]) == 1 + rows + 2
 
 
 def test_more_keys_than_capacity_fail_the_call():
@@ -275,6 +284,64 @@ def test_a_class_beyond_the_lds_path():
     call, want = _core_case(secs, gt, disp, 5.0, 3, 1)
     idx, lab, _ = want["per_class"][0][2]
     assert len(idx) > 2048 and (lab >= 0).sum() > 100 and (lab == -1).sum() > 100 and lab.max() >= 3
+
+
+# ---- the edges the clustering shares with k_cluster_instances (is_dbscan.h) ----------------------------------------
+def test_the_lds_boundary_with_candidates_that_take_no_part():
+    """64 x 2048, 256 columns of 9 slots.  Frame 0 holds exactly 2048 candidates of class 13, the last size clustered
+    out of the LDS copies; frame 1 exactly 2049 of class 15, the first size clustered out of global memory (a frame
+    has 2304 slots, so the two sizes are two frames).  In both, candidates over stuff have the median 0 and take no
+    part, next to clustered ones and to noise."""
+    frames = [banded_frame(256, [(13, 2048)], 32, seed=1), banded_frame(256, [(15, 2049)], 32, seed=2)]
+    secs, gt, disp = (np.stack(x) for x in zip(*frames))
+    assert gt.shape == (2, 64, 2048)
+    _, want = _core_case(secs, gt, disp, **BANDED)
+    for f, cls, n in ((0, 13, 2048), (1, 15, 2049)):
+        lab, part = class_labels(want, f, cls)
+        assert len(lab) == n and sum(len(v[0]) for v in want["per_class"][f]) == n
+        assert (lab >= 0).sum() > 0 and ((lab == -1) & part).sum() > 0 and (~part).sum() > 50
+
+
+def test_the_rank_scan_at_its_thread_boundaries():
+    """Classes of 1, 255, 256 and 257 candidates in one frame: per = ceil(n / 256) changes from 1 to 2 between the last
+    two, and at 257 the ranges of the threads from 129 on start beyond n.  Several clusters in each of the three."""
+    sizes = [(11, 1), (12, 255), (13, 256), (14, 257)]
+    secs, gt, disp = banded_frame(128, sizes, 4, seed=3)
+    _, want = _core_case(secs[None], gt[None], disp[None], **BANDED)
+    for cls, n in sizes:
+        lab, _ = class_labels(want, 0, cls)
+        assert len(lab) == n and (n == 1 or lab.max() >= 3)
+
+
+@pytest.mark.parametrize("n, C", [(300, 64), (2049, 256)])
+def test_one_z_for_every_candidate_equals_the_two_coordinate_kernel(n, C):
+    """One instance key over the whole image, one non-zero disparity: every candidate has the same z, dz * dz adds
+    exactly +0, and labels, flags and packed triples of is_cluster_instance_disparity are, bit for bit, those of
+    is_recluster (k_recore + k_cluster_instances) on the same candidates, eps, min_pts and size_filter.  The
+    restatement is held to the same equality in test_instance_disparity_cpu.py."""
+    torch, dev = _torch()
+    secs, gt, disp = banded_frame(C, [(13, n)], 32, seed=n, one_key=True)
+    call, want = _core_case(secs[None], gt[None], disp[None], capacity=1, **BANDED)
+    lab, part = class_labels(want, 0, 13)
+    assert len(lab) == n and part.all() and (lab >= 0).any() and (lab == -1).any()
+    params, lut, odr = oracle.host_initialize(make_config("drn_d_22_unary", 64, C * 8, 32))
+    params.max_sections = secs.shape[1]
+    assert params.cols == C
+    ctx = core_mod.Core(params, lut, odr, max_batch=1)
+    try:
+        cand = call.cand[0].clone()                       # the flags the three-coordinate call wrote
+        labels = torch.full_like(call.labels[0], POISON_LABEL)
+        packed = torch.full_like(call.packed[0], POISON_PACKED)
+        ib = core_mod.InstanceBuffers(call.com[0].data_ptr(), call.idx[0].data_ptr(), cand.data_ptr(),
+                                      call.d_per[0].data_ptr(), labels.data_ptr(), packed.data_ptr())
+        rc = ctx.recluster_ptr(call.d_sections.data_ptr(), 1, BANDED["eps"], BANDED["min_pts"], BANDED["size_filter"],
+                               [ib], stream=torch.cuda.current_stream(dev).cuda_stream)
+        assert rc == 0, core_mod.lib().is_last_error().decode()
+        torch.cuda.synchronize(dev)
+    finally:
+        ctx.close()
+    assert torch.equal(labels, call.labels[0]) and torch.equal(cand, call.cand[0])
+    assert torch.equal(packed, call.packed[0])
 
 
 # ---- the host class -----------------------------------------------------------------------------------------------
