@@ -31,6 +31,10 @@
  * The vT side, lutT[vT + 1][fn], is output vT & 31 of block vT / 32: picked from the first step's networks when that
  * block is among them, otherwise built two fn at a time (lut_row_entry), and kept per row in an LDS cache.
  *
+ * The held block: rows descend, and most hops start the next row in the 64-row block whose
+ * records the wave loaded last, so path_row keeps the records of its last full step in the lanes across rows and a
+ * step on that block loads nothing; record vT + 1 is then the previous hop's vB and comes from the lane that owns it.
+ *
  * Sections (CallPlan::walk_sections, a call without instance outputs): lane 0 records (vT, vB, type, cost) of every
  * hop in LDS; after a chain that succeeded the lanes build the Sections with k_backtrace's make_section and store them
  * with the terminator, and k_backtrace runs gated (generic columns, every column of a distrusted call).
@@ -46,6 +50,7 @@ struct LutCol {
     const float* __restrict__ costF; /* [fn][dis] */
     int* s_tag;
     float* s_val;
+    int* s_my; /* [32]: spread_of_lane */
     int H, D, nb;
 };
 
@@ -59,15 +64,40 @@ __device__ __forceinline__ float read_lane(float v, int l) {
  * (c[0] += add, block 0 included), then c[p] += c[p - j] for j = 1, 2, 4, 8, 16 within the half.  The same
  * additions on the same values: the same bits. */
 __device__ __forceinline__ float lut_network(const LutCol& L, int dis, int fn, int blk, int lane) {
+    asm volatile("" : "+v"(lane)); /* (the shuffle indices and the p >= j masks are rebuilt here, not kept per kernel) */
     const int p = lane & 31;
     float c = L.costF[(size_t)fn * L.D + dis];
     if (p == 0) c += L.ccol[(size_t)blk * L.D + fn];
 #pragma unroll
     for (int j = 1; j < 32; j <<= 1) {
-        const float t = __shfl_up(c, j, 32);
+        /* lane - j (mod 64): only p >= j takes it, and there it is __shfl_up(c, j, 32) */
+        const float t = __int_as_float(__builtin_amdgcn_ds_bpermute(4 * lane + 4 * (64 - j), __float_as_int(c)));
         if (p >= j) c += t;
     }
     return c;
+}
+
+/* A record whose address is the same in every lane, held in ONE VGPR: lane i (and i + 32) has dword i.  The fields
+ * come out with v_readlane (SGPR operands of the evaluation), so the record costs one VGPR instead of 32. */
+__device__ __forceinline__ int load_rec_spread(const RowRec* p, int lane) { return ((const int*)p)[lane & 31]; }
+__device__ __forceinline__ RowRec rec_of_spread(int v) {
+    RowRec r;
+    int* d = (int*)&r;
+#pragma unroll
+    for (int i = 0; i < 32; i++) d[i] = __builtin_amdgcn_readlane(v, i);
+    return r;
+}
+/* ... and the record that lane l of a block of records (one per lane) holds, in that form: through 128 bytes of
+ * LDS (eight 16-byte writes of one lane, one read), about a tenth of the latency of the load it replaces */
+__device__ __forceinline__ int spread_of_lane(const RowRec& blk, int l, int lane, int* s_my) {
+    if (lane == l) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) ((int4*)s_my)[i] = ((const int4*)&blk)[i];
+    }
+    __syncthreads(); /* (one wave) */
+    int v = s_my[lane & 31];
+    asm volatile("" : "+v"(v)); /* (an LDS read: not merged with the miss's global load into one flat load) */
+    return v;
 }
 
 /* lutT[vT + 1][fni] for the lanes in `need` (others: 0).  Cache misses are built two fn per pass, one per half,
@@ -113,9 +143,26 @@ __device__ __forceinline__ void path_take(float& c, int& v, float c2, int v2) {
 template <bool HAS_INVALID>
 __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* __restrict__ rcol, const LutCol& L,
                                              const float* __restrict__ rcp, const PruneRec& pr, int vT, int vhor,
-                                             int lane) {
+                                             int lane, int& cs, RowRec& cb) {
     const int D = P.D;
-    const RowRec my = load_rec(rcol + vT + 1); /* (in VGPRs: the scalar form spills SGPRs) */
+    /* The block of the last full step stays in the lanes across rows (cs: its index s, cb: the record of candidate
+     * 64 cs + 1 + lane).  Rows descend, so a lane that is live in a later row of the same block (vB <= vT) was live
+     * when the block was loaded and holds its own record; the dead lanes (vB > vT) hold their own record or the
+     * clamped one of the loading row (a row >= vT + 1 of this column): every index derived from them is clamped --
+     * h = vT + 1 - vBc = 1 (rcp[1]), the valid count through cvt_u32_sat into rcp[0 .. H] (V differences are in
+     * [-H, H]), fni into [0, D - 1] -- and nothing of them passes `live`.
+     * Record vT + 1 (`my`) is one VGPR for the wave (load_rec_spread): 32 VGPRs go to the block instead.  When the
+     * row starts in the held block and vT + 1 is one of its candidates (the previous hop's vB, lane vT - 64 cs), the
+     * owning lane hands it over; otherwise (a miss, or vT = 64 s + 64: vT + 1 belongs to the block above) one
+     * 128-byte load. */
+    int myv;
+    {
+        const int s0 = (vT - 1) >> 6, l0 = vT - 64 * s0;
+        if (s0 >= 0 && s0 == cs && l0 < 64) myv = spread_of_lane(cb, l0, lane, L.s_my);
+        else myv = load_rec_spread(rcol + vT + 1, lane);
+    }
+#define IS_MY_REC() asm volatile("" : "+v"(myv)); const RowRec my = rec_of_spread(myv) /* (not hoisted: SGPRs) */
+    const float myG = __int_as_float(__builtin_amdgcn_readlane(myv, offsetof(RowRec, G) / 4));
     const int disT = lut_bin(lut_row_d(L.dcol, (vT & ~31) + (lane & 31), L.H), D);
     const int s_first = (vT - 1) >> 6;
     float bg = IS_INF, bo = IS_INF, bs = IS_INF;
@@ -123,7 +170,7 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
     const bool prune_on = pr.E1o < IS_INF;
     bool open_o = true, open_s = true;
     /* ground data cost +inf from this row on (at / above the horizon): no ground candidate can win */
-    bool open_g = !(my.G == IS_INF);
+    bool open_g = !(myG == IS_INF);
     /* Full steps while the object type is open, then ground- / sky-only steps: the close is monotone within a row.
      * `ended`: the exit test fired, nothing below can win (the first segment included). */
     bool ended = false;
@@ -132,13 +179,39 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
         const int vB = 64 * s + 1 + lane;
         const bool live = vB <= vT;
         const int vBc = live ? vB : vT;
-        const RowRec rb = load_rec(rcol + vBc);
+        IS_MY_REC();
+        if (s != cs) { cb = load_rec(rcol + vBc); cs = s; }
+        const RowRec& rb = cb;
         const int disS = lut_bin(lut_row_d(L.dcol, 64 * s + lane, L.H), D); /* rows of the step's two LUT blocks */
         const int h = vT + 1 - vBc;
         const float r = rcp[h]; /* RN(1/h) */
         const SegTerms t = eval_segment<true, HAS_INVALID>(my, rb, (float)h, r, D, P.iw, rcp);
         const float pwih = P.pw * r;
         /* cost = dw*data + pw*(1/h) + sw*seg, left to right (unary_step) */
+        /* (ground and sky, and everything of the bounds but the object type's ballot, in front of the networks:
+         * their terms are out of the registers while the passes run) */
+        if (vB - 1 >= vhor) {
+            const float cost_s = P.dw * t.sd + pwih + P.sw * t.seg_s;
+            if (open_s && live && cost_s <= bs) { bs = cost_s; vs = vB; }
+        } else {
+            const float cost_g = P.dw * t.gd + pwih + P.sw * t.seg_g;
+            if (open_g && live && cost_g <= bg) { bg = cost_g; vg = vB; }
+        }
+        float lb_o = 0.0f;
+        if (prune_on) {
+            /* the longest segment of the step: lane 0 (vB = 64 s + 1 <= vT) */
+            const float f_on = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.f_on)));
+            const float f_oi = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.f_oi)));
+            const float f_sky = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.f_sky)));
+            const float f_g = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.f_g)));
+            /* (wave-uniform, and live across the networks: in an SGPR) */
+            lb_o = __int_as_float(__builtin_amdgcn_readfirstlane(
+                __float_as_int(P.sw * __builtin_fminf(f_on, f_oi - pr.E2) - pr.E1o)));
+            const float lb_s = P.sw * f_sky - pr.E1s;
+            const float lb_g = P.sw * f_g - pr.E1g;
+            if (__builtin_amdgcn_ballot_w64(lb_s > bs) != 0ull) open_s = false;
+            if (__builtin_amdgcn_ballot_w64(lb_g > bg) != 0ull) open_g = false;
+        }
         {
             /* lutT[vB][fni]: one network pass per distinct fn of the live lanes; the first step of the row also
              * leaves lutT[vT + 1][fn] (lane vT - 64 s) in the row cache */
@@ -161,26 +234,9 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
             const float cost_o = P.dw * od + pwih + P.sw * t.seg_o;
             if (live && cost_o <= bo) { bo = cost_o; vo = vB; }
         }
-        if (vB - 1 >= vhor) {
-            const float cost_s = P.dw * t.sd + pwih + P.sw * t.seg_s;
-            if (open_s && live && cost_s <= bs) { bs = cost_s; vs = vB; }
-        } else {
-            const float cost_g = P.dw * t.gd + pwih + P.sw * t.seg_g;
-            if (open_g && live && cost_g <= bg) { bg = cost_g; vg = vB; }
-        }
         if (prune_on) {
-            /* the longest segment of the step: lane 0 (vB = 64 s + 1 <= vT) */
-            const float f_on = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.f_on)));
-            const float f_oi = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.f_oi)));
-            const float f_sky = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.f_sky)));
-            const float f_g = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.f_g)));
-            const float lb_o = P.sw * __builtin_fminf(f_on, f_oi - pr.E2) - pr.E1o;
-            const float lb_s = P.sw * f_sky - pr.E1s;
-            const float lb_g = P.sw * f_g - pr.E1g;
             /* lb > (the row's best) <=> some lane's best is below lb (a best is never NaN) */
             if (__builtin_amdgcn_ballot_w64(lb_o > bo) != 0ull) open_o = false;
-            if (__builtin_amdgcn_ballot_w64(lb_s > bs) != 0ull) open_s = false;
-            if (__builtin_amdgcn_ballot_w64(lb_g > bg) != 0ull) open_g = false;
             /* candidates left: vB' <= 64 s; sky ones need vB' - 1 >= vhor */
             const bool sky_left = 64 * s - 1 >= vhor;
             if (!open_o && !open_g && (!open_s || !sky_left)) { ended = true; break; }
@@ -195,6 +251,7 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
         const int vBc = live ? vB : vT;
         const int h = vT + 1 - vBc;
         const float pwih = P.pw * rcp[h];
+        IS_MY_REC();
         SegTerms t;
         if (open_g) t = eval_segment_gs<IS_WANT_GROUND | IS_WANT_SKY>(my, load_rec_gs<IS_WANT_GROUND | IS_WANT_SKY>(rcol + vBc), P.iw);
         else t = eval_segment_gs<IS_WANT_SKY>(my, load_rec_gs<IS_WANT_SKY>(rcol + vBc), P.iw);
@@ -221,8 +278,9 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
         const int h0 = vT + 1;
         const float r0 = rcp[h0];
         const float pwih0 = P.pw * r0;
+        IS_MY_REC();
         if (open_o) {
-            const RowRec rb0 = load_rec(rcol);
+            const RowRec rb0 = rec_of_spread(load_rec_spread(rcol, lane)); /* (the block stays in its VGPRs) */
             const SegTerms t0 = eval_segment<true, HAS_INVALID>(my, rb0, (float)h0, r0, D, P.iw, rcp);
             const float od = lut_row_entry(L, disT, vT, t0.fni, lane == 0, lane) - 0.0f; /* lutT[0] = 0 */
             const float cost_o = P.dw * od + pwih0 + P.sw * t0.seg_o;
@@ -238,7 +296,8 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
         }
     }
     if (vT == 0) { /* the first segment is the only candidate */
-        const RowRec rb0 = load_rec(rcol);
+        IS_MY_REC();
+        const RowRec rb0 = rec_of_spread(load_rec_spread(rcol, lane));
         const float r0 = rcp[1];
         const SegTerms t0 = eval_segment<true, HAS_INVALID>(my, rb0, 1.0f, r0, D, P.iw, rcp);
         const float pwih0 = P.pw * r0;
@@ -261,17 +320,18 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
     b.v[IS_OBJECT] = (bo < IS_INF) ? vo : 0;
     b.v[IS_SKY] = (bs < IS_INF) ? vs : -1;
     return b;
+#undef IS_MY_REC
 }
 
+/* (7 waves per SIMD, 72 VGPRs: what the LDS of 28 waves per CU allows; the held block leaves no slack below it) */
 template <bool HAS_INVALID>
-__global__ __launch_bounds__(64) void k_unary_path(const DevParams P, int ncols, const RowRec* __restrict__ recs,
-                                                   const float* __restrict__ joined, const float* __restrict__ lutC,
-                                                   const float* __restrict__ cost_F, const float* __restrict__ rcp,
-                                                   const int* __restrict__ vhor_arr, const int* __restrict__ col_flags,
-                                                   const PruneRec* __restrict__ prune, float* __restrict__ cost_table,
-                                                   int32_t* __restrict__ index_table,
-                                                   is_section* __restrict__ sections /* or null */,
-                                                   int* __restrict__ bad, int force_bad) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 7)))
+void k_unary_path(const DevParams P, int ncols, const RowRec* __restrict__ recs, const float* __restrict__ joined,
+                  const float* __restrict__ lutC, const float* __restrict__ cost_F, const float* __restrict__ rcp,
+                  const int* __restrict__ vhor_arr, const int* __restrict__ col_flags,
+                  const PruneRec* __restrict__ prune, float* __restrict__ cost_table,
+                  int32_t* __restrict__ index_table, is_section* __restrict__ sections /* or null */,
+                  int* __restrict__ bad, int force_bad) {
     const int colg = (int)blockIdx.x, lane = (int)threadIdx.x;
     if (force_bad && colg == 0 && lane == 0) /* (IS_UNARY_PATH=3, tests: distrust every call) */
         __hip_atomic_fetch_or(bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -280,7 +340,9 @@ __global__ __launch_bounds__(64) void k_unary_path(const DevParams P, int ncols,
     const int H = P.H, S = P.S;
     const int vhor = __builtin_amdgcn_readfirstlane(vhor_arr[colg / P.C]);
     const RowRec* rcol = recs + (size_t)colg * (H + 1);
-    extern __shared__ int s_lut_row[]; /* [2][D]: the row cache of lut_row_entry, then [S][4]: the chain's hops */
+    /* [32]: one record (spread_of_lane), [2][D]: the row cache of lut_row_entry, [S][4]: the chain's hops */
+    extern __shared__ __attribute__((aligned(16))) int s_walk[];
+    int* s_lut_row = s_walk + 32;
     LutCol L;
     L.H = H; L.D = P.D; L.nb = isk_lut_carry_rows(H);
     L.dcol = joined + (size_t)colg * H;
@@ -289,6 +351,7 @@ __global__ __launch_bounds__(64) void k_unary_path(const DevParams P, int ncols,
     L.s_tag = s_lut_row;
     L.s_val = (float*)(s_lut_row + P.D);
     for (int i = lane; i < P.D; i += 64) L.s_tag[i] = -1;
+    L.s_my = s_walk;
     int* s_cut = s_lut_row + 2 * P.D; /* [S][4]: vT, vB, type, cost bits of every hop (CallPlan::walk_sections) */
     float* ct = cost_table + (size_t)colg * H * 3;
     int32_t* it = index_table + (size_t)colg * H * 3;
@@ -301,8 +364,15 @@ __global__ __launch_bounds__(64) void k_unary_path(const DevParams P, int ncols,
      * vB - 1 with its tie rules; at most S - 1 Sections, and the row vB - 1 of the last one is still read */
     int vT = H - 1, n = 0, type = IS_OBJECT;
     bool last = false;
+    int cs = -1; /* the block path_row holds across rows: none yet */
+    RowRec cb;
+    {
+        int* d = (int*)&cb;
+#pragma unroll
+        for (int i = 0; i < 32; i++) d[i] = 0;
+    }
     for (;;) {
-        const PathBest b = path_row<HAS_INVALID>(P, rcol, L, rcp, pr, vT, vhor, lane);
+        const PathBest b = path_row<HAS_INVALID>(P, rcol, L, rcp, pr, vT, vhor, lane, cs, cb);
         if (lane == 0) {
             ct[vT * 3 + 0] = b.c[0]; ct[vT * 3 + 1] = b.c[1]; ct[vT * 3 + 2] = b.c[2];
             it[vT * 3 + 0] = b.v[0]; it[vT * 3 + 1] = b.v[1]; it[vT * 3 + 2] = b.v[2];
@@ -346,8 +416,10 @@ __global__ __launch_bounds__(64) void k_unary_path(const DevParams P, int ncols,
 
 extern "C" {
 
-/* the row cache [2][D] and the hops [S][4] */
-size_t isk_unary_path_lds_bytes(const DevParams* P) { return sizeof(int) * (2 * (size_t)P->D + 4 * (size_t)P->S); }
+/* one record, the row cache [2][D] and the hops [S][4] */
+size_t isk_unary_path_lds_bytes(const DevParams* P) {
+    return sizeof(int) * (2 * (size_t)P->D + 4 * (size_t)P->S + 32);
+}
 
 hipError_t isk_set_lds_unary_path(const DevParams* P) {
     const int b = (int)isk_unary_path_lds_bytes(P);
