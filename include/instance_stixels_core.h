@@ -799,6 +799,17 @@ int is_device_synchronize(void);
  * every column of a repaired call, are complete. */
 int is_debug_read_object_lut(is_ctx* ctx, int column, float* h_out);
 
+/* Test hook: the block carries of the object table of ONE stixel column as the last walk call (is_debug_unary_path:
+ * path 1) left them, h_out[ceil(rows / 32)][max_dis] = lutT[32 k][fn] (row 0 is zero).  A call on the tile path does
+ * not write them.  Synchronises the device. */
+int is_debug_read_lut_carries(is_ctx* ctx, int column, float* h_out);
+
+/* Test hook: *on = 1 when the prepare step of the last is_compute / is_compute_sweep call of this context built the
+ * carry rows with the kernel that keeps the cost table in LDS (walk calls with max_dis <= 128), 0 when it did not (tile
+ * and pairwise calls, max_dis = 256), -1 before the first call; *pass_columns = the columns one pass of that kernel's
+ * grid takes (a call with more columns runs its column loop more than once). */
+int is_debug_lut_carry_lds(is_ctx* ctx, int* on, int* pass_columns);
+
 /* Test hook: did the last unary is_compute call on this context run its repair launches?  A unary call whose every
  * tile is windowed builds the object data-cost table INSIDE its DP launch (the units of a column ahead of the
  * column's DP workgroups, which wait for a per-column count); a DP workgroup that cannot trust the hand-over -- its

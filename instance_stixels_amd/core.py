@@ -25,7 +25,7 @@ EXPORTS = [
     "is_ctx_device", "is_set_eval_counters", "is_get_eval_counters",
     "is_pack_sections", "is_unpack_sections", "is_stream_create", "is_stream_destroy",
     "is_debug_read_object_lut", "is_debug_read_block_summaries", "is_debug_lut_fused_state",
-    "is_lut_fused_repairs", "is_debug_unary_path",
+    "is_lut_fused_repairs", "is_debug_unary_path", "is_debug_read_lut_carries", "is_debug_lut_carry_lds",
     "is_comm_unique_id", "is_comm_init_rank", "is_comm_destroy", "is_comm_rank", "is_gather_i32",
     "is_gather_sections",
     "is_road_ctx_create", "is_road_ctx_destroy", "is_road_ctx_device", "is_road_ctx_binary",
@@ -253,8 +253,10 @@ def lib():
         L.is_debug_lut_fused_state.argtypes = [vp, ctypes.POINTER(ci)]
         L.is_lut_fused_repairs.argtypes = [vp, ctypes.POINTER(ci)]
         L.is_debug_unary_path.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]
-        try:   # (an experiment library built from an older tree may lack the newest test hook)
+        try:   # (an experiment library built from an older tree may lack the newest test hooks)
             L.is_debug_read_block_summaries.argtypes = [vp, ci, vp, ci, ctypes.POINTER(ci)]
+            L.is_debug_read_lut_carries.argtypes = [vp, ci, vp]
+            L.is_debug_lut_carry_lds.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]
         except AttributeError:
             pass
         _LIB = L
@@ -344,6 +346,20 @@ class Core:
         out = np.zeros((self.params.rows + 1, self.params.max_dis), np.float32)
         _check(lib().is_debug_read_object_lut(self._ctx, int(column), _hp(out)), "is_debug_read_object_lut")
         return out
+
+    def read_lut_carries(self, column):
+        """lutC[k][fn] = lutT[32 k][fn], the object table's block carries of one stixel column as the last walk call
+        left them (test hook)."""
+        out = np.zeros(((self.params.rows + 31) // 32, self.params.max_dis), np.float32)
+        _check(lib().is_debug_read_lut_carries(self._ctx, int(column), _hp(out)), "is_debug_read_lut_carries")
+        return out
+
+    def lut_carry_lds(self):
+        """(on, pass_columns): on = 1 when the last call's prepare step built the carry rows from a cost table in LDS
+        (k_lut_carry), 0 when not, -1 before any call; pass_columns = columns per pass of that kernel's grid."""
+        on, n = ctypes.c_int(-1), ctypes.c_int(0)
+        _check(lib().is_debug_lut_carry_lds(self._ctx, ctypes.byref(on), ctypes.byref(n)), "is_debug_lut_carry_lds")
+        return int(on.value), int(n.value)
 
     def read_block_summaries(self, column):
         """[n_blocks][24] bound-block summaries of one column after a pairwise call (test hook)."""

@@ -88,6 +88,7 @@ struct is_ctx {
     int* d_n_generic;        /* [1] generic-encoding columns of the current call */
     int* d_path_bad;         /* [2] k_unary_path's distrust word of the current call (cleared by the next prepare launch), calls repaired (k_backtrace) */
     int last_unary_path = -1; /* the unary DP of the last unary call: 1 = k_unary_path, 0 = tile path (CallPlan::unary_walk) */
+    int last_lut_carry_lds = -1; /* CallPlan::lut_carry_lds of the last call's prepare step (is_debug_lut_carry_lds) */
     /* per-call device inputs */
     /* one block [ground: max_batch x 3 x H floats][instance table: max_batch][vhor: max_batch ints], on
      * the device and in every pinned staging slot: a full batch (the host class's single frame
@@ -313,6 +314,7 @@ static int ctx_init(is_ctx* c, const is_stixel_params* p, const float* obj_cost_
         k.unary_path = knob("IS_UNARY_PATH"); /* the unary DP of the visited rows only (k_unary_path) */
         d.lutf_wrong_xcc = k.lut_fused >= 2 ? 1 : 0;
         c->last_unary_path = -1;
+        c->last_lut_carry_lds = -1;
     }
     {
         /* branch-and-bound constants (PruneRec, is_device.h).  gamma_d bounds the relative error of
@@ -340,7 +342,8 @@ static int ctx_init(is_ctx* c, const is_stixel_params* p, const float* obj_cost_
     c->nwaves_pairwise = IS_UNARY_WAVES;
     if (sizeof(int) * (6 * (size_t)d.H + 3 * (size_t)d.S + 4) > 160 * 1024 ||
         isk_unary_lds_bytes(&d) > 160 * 1024 || isk_pairwise_lds_bytes(&d, c->nwaves_pairwise) > 160 * 1024 ||
-        isk_prepare_lds_bytes(&d) > 160 * 1024 || isk_phase2_lds_bytes(&d) > 64 * 1024 ||
+        isk_prepare_lds_bytes(&d) > 160 * 1024 || isk_lut_carry_lds_bytes(&d) > 160 * 1024 ||
+        isk_phase2_lds_bytes(&d) > 64 * 1024 ||
         isk_phase2s_lds_bytes(&d) > 64 * 1024 || /* (both far below: no attribute is set for them) */
         sizeof(int) * (size_t)d.C * IS_INSTANCE_CLASSES + 16 > 160 * 1024)
         return fail_arg("shape needs more than 160 KiB of LDS per workgroup");
@@ -447,6 +450,7 @@ static int ctx_init(is_ctx* c, const is_stixel_params* p, const float* obj_cost_
         if (!same) return fail_arg("internal: (float)(1./h) != 1.0f/h for some h <= rows");
     }
     HIP_TRY(isk_set_lds_prepare(&d));
+    HIP_TRY(isk_set_lds_lut_carry(&d));
     HIP_TRY(isk_set_lds_unary(&d));
     HIP_TRY(isk_set_lds_unary_path(&d));
     HIP_TRY(isk_set_lds_pairwise(&d, c->nwaves_pairwise));
@@ -939,6 +943,23 @@ int is_debug_read_object_lut(is_ctx* c, int column, float* h_out) {
     return IS_OK;
 }
 
+int is_debug_read_lut_carries(is_ctx* c, int column, float* h_out) {
+    if (!c || !h_out) return fail_arg("null pointer");
+    if (column < 0 || column >= c->max_batch * c->dp.C) return fail_arg("column outside the context's scratch");
+    ON_CTX_DEVICE(c);
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t n = (size_t)isk_lut_carry_rows(c->dp.H) * c->dp.D;
+    HIP_TRY(hipMemcpy(h_out, c->d_lutC + (size_t)column * n, sizeof(float) * n, hipMemcpyDeviceToHost));
+    return IS_OK;
+}
+
+int is_debug_lut_carry_lds(is_ctx* c, int* on, int* pass_columns) {
+    if (!c || !on || !pass_columns) return fail_arg("null pointer");
+    *on = c->last_lut_carry_lds;
+    *pass_columns = isk_lut_carry_pass_columns();
+    return IS_OK;
+}
+
 int is_debug_lut_fused_state(is_ctx* c, int* repaired) {
     if (!c || !repaired) return fail_arg("null pointer");
     ON_CTX_DEVICE(c);
@@ -1074,6 +1095,9 @@ static CallPlan plan_call(const is_ctx* c, const DevParams& P, int n_images, int
     /* the walk rebuilds the table entries it reads from the block carries (k_unary_path); the launches behind it that
      * read the complete table build it first for the columns they take (isk_launch_dp_unary) */
     p.lut_carry = p.unary_walk;
+    /* ... and builds them from a cost table in LDS where it fits beside a second workgroup (k_lut_carry, D <= 128);
+     * other shapes keep the carry units of k_prepare_fused */
+    p.lut_carry_lds = p.lut_carry && p.prepare_lut && isk_lut_carry_lds_bytes(&P) != 0;
 
     if (pairwise) {
         /* few columns: two workgroups per (column, tile) in phase 1 */
@@ -1180,6 +1204,7 @@ static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_se
     const CallPlan plan = plan_call(c, P, n_images, pairwise, vhor_min,
                                     d_cost_table != nullptr || d_index_table != nullptr, want_inst);
     if (!pairwise) c->last_unary_path = plan.unary_walk;
+    c->last_lut_carry_lds = plan.lut_carry_lds;
     CallBuffers b = call_buffers(c, d_joined, d_seg);
     if (d_cost_table) b.cost_table = d_cost_table;
     if (d_index_table) b.index_table = d_index_table;
@@ -1420,6 +1445,8 @@ static int sweep_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_seg,
     P0.sigma_od = c->sigma_od_free;
     CallPlan prep = plans[0];
     prep.lut_carry = any_walk ? 1 : 0;
+    prep.lut_carry_lds = prep.lut_carry && isk_lut_carry_lds_bytes(&P0) != 0;
+    c->last_lut_carry_lds = prep.lut_carry_lds;
     CallBuffers b = call_buffers(c, d_joined, d_seg);
     HIP_TRY(isk_launch_prepare(&P0, &prep, &b, stream));
     if (any_walk && any_tile) /* the sets disagree: the complete table of every column beside the carry rows */

@@ -822,6 +822,105 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prepare_fused(
     }
 }
 
+/* The carry rows of a walk call from a cost table in LDS (CallPlan::lut_carry_lds; D <= 128).  object_lut_body<true>
+ * loads one 256-byte piece of cost_T[dis] per row, column and 64 fn: at 16 384 columns x 1024 rows x 128 fn that is
+ * 8.6 GB read through L1 / L2 out of a 64 KB table.  Here a workgroup stages the table once ([dis][NF * 64] floats;
+ * the fn beyond D of a row are zero and are never stored) and then takes whole columns, one wave per column; lane l
+ * owns the NF consecutive fn NF l .. NF l + NF - 1, so a row is one ds_read_b32 / ds_read_b64 per lane without bank
+ * conflicts (a 32-lane half covers 64 consecutive dwords at NF = 2) and a carry row one contiguous store per wave.
+ * The bins of 64 rows (two LUT blocks) come with one coalesced load, two loads ahead of their use.  Per block exactly
+ * the additions that end in c[31] of object_lut_body's network, in its order on its values: l = 31, 31 - 2 j, .. of
+ * step j read the lanes l - j, which that step does not write.  The block whose carry nothing reads (the last one) is
+ * not evaluated. */
+#define LUTC_THREADS 512
+#define LUTC_MAX_WGS 512 /* two workgroups of 64 KB per CU */
+typedef float lutc_f2 __attribute__((ext_vector_type(2)));
+template <int NF>
+__global__ __launch_bounds__(LUTC_THREADS) void k_lut_carry(const DevParams P, int ncols,
+                                                            const float* __restrict__ joined,
+                                                            const float* __restrict__ cost_T /*[dis][fn]*/,
+                                                            float* __restrict__ lutC) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int W = NF * 64; /* floats per staged row */
+    float* s_tab = reinterpret_cast<float*>(smem);
+    const int H = P.H, D = P.D, nb = isk_lut_carry_rows(H);
+    if ((D & 3) == 0) { /* 16-byte loads: a row of cost_T starts on a 16-byte boundary */
+        for (int q = (int)threadIdx.x; q < D * (W / 4); q += LUTC_THREADS) {
+            const int dis = q / (W / 4), f4 = (q - dis * (W / 4)) * 4;
+            float4 x = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (f4 < D) x = *reinterpret_cast<const float4*>(cost_T + (size_t)dis * D + f4);
+            *reinterpret_cast<float4*>(s_tab + dis * W + f4) = x;
+        }
+    } else {
+        for (int q = (int)threadIdx.x; q < D * W; q += LUTC_THREADS) {
+            const int dis = q / W, f = q - dis * W;
+            s_tab[q] = f < D ? cost_T[(size_t)dis * D + f] : 0.0f;
+        }
+    }
+    __syncthreads();
+    const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+    const int fn = NF * lane;
+    const bool pair = NF == 2 && (D & 1) == 0; /* both fn of a lane on one side of D: 8-byte stores */
+    for (int colg = (int)blockIdx.x * (LUTC_THREADS / 64) + wave; colg < ncols;
+         colg += (int)gridDim.x * (LUTC_THREADS / 64)) {
+        const float* dcol = joined + (size_t)colg * H;
+        float* lcol = lutC + (size_t)colg * nb * D;
+        auto store_row = [&](int k, const float (&v)[NF]) {
+            float* p = lcol + (size_t)k * D + fn;
+            if (pair) {
+                if (fn < D) {
+                    lutc_f2 x = {v[0], v[NF - 1]};
+                    __builtin_nontemporal_store(x, reinterpret_cast<lutc_f2*>(p));
+                }
+            } else {
+#pragma unroll
+                for (int f = 0; f < NF; f++)
+                    if (fn + f < D) __builtin_nontemporal_store(v[f], p + f);
+            }
+        };
+        float add[NF];
+#pragma unroll
+        for (int f = 0; f < NF; f++) add[f] = 0.0f;
+        store_row(0, add); /* arr[0] = 0, :283-285: the carry of block 0 */
+        float d_here = lut_row_d(dcol, lane, H), d_next = lut_row_d(dcol, 64 + lane, H);
+        for (int i0 = 0; i0 + LUT_BLOCK < H; i0 += 2 * LUT_BLOCK) {
+            const int dis_l = lut_bin(d_here, D);
+            d_here = d_next;
+            d_next = lut_row_d(dcol, i0 + 4 * LUT_BLOCK + lane, H);
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const int i = i0 + h * LUT_BLOCK;
+                if (i + LUT_BLOCK < H) { /* (wave-uniform) the blocks in front of the last one */
+                    float c[LUT_BLOCK][NF];
+#pragma unroll
+                    for (int l = 0; l < LUT_BLOCK; l++) { /* wave-uniform broadcasts */
+                        const int dis = __builtin_amdgcn_readlane(dis_l, h * LUT_BLOCK + l);
+                        const float* row = s_tab + dis * W + fn;
+                        if (NF == 2) {
+                            const lutc_f2 x = *reinterpret_cast<const lutc_f2*>(row);
+                            c[l][0] = x.x;
+                            c[l][NF - 1] = x.y;
+                        } else {
+                            c[l][0] = row[0];
+                        }
+                    }
+#pragma unroll
+                    for (int f = 0; f < NF; f++) {
+                        c[0][f] += add[f]; /* :249-251 */
+#pragma unroll
+                        for (int j = 1; j < LUT_BLOCK; j <<= 1) {
+#pragma unroll
+                            for (int l = LUT_BLOCK - 1; l >= j; l -= 2 * j) c[l][f] += c[l - j][f];
+                        }
+                        add[f] = c[LUT_BLOCK - 1][f]; /* :268-272 */
+                    }
+                    store_row(i / LUT_BLOCK + 1, add);
+                }
+            }
+        }
+    }
+}
+
 /* ====================================================================================== */
 /* Pairwise transition priors that depend only on vB and the frame's ground model          */
 /* ====================================================================================== */
@@ -872,14 +971,42 @@ hipError_t isk_launch_lut_generic(const DevParams* P, const CallPlan* plan, cons
     return hipGetLastError();
 }
 
+/* k_lut_carry serves a shape when a lane holds one or two fn (D <= 128) and the staged table leaves room for a second
+ * workgroup on the CU (64 of 160 KB); 0: it does not (CallPlan::lut_carry_lds stays off) */
+size_t isk_lut_carry_lds_bytes(const DevParams* P) {
+    const size_t nf = ((size_t)P->D + 63) / 64, bytes = sizeof(float) * (size_t)P->D * nf * 64;
+    return nf <= 2 && bytes <= 64 * 1024 ? bytes : 0;
+}
+
+hipError_t isk_launch_lut_carry(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream) {
+    const int per_wg = LUTC_THREADS / 64, wgs = (plan->ncols + per_wg - 1) / per_wg;
+    const dim3 grid(wgs < LUTC_MAX_WGS ? wgs : LUTC_MAX_WGS);
+    if (P->D <= 64)
+        hipLaunchKernelGGL(k_lut_carry<1>, grid, dim3(LUTC_THREADS), isk_lut_carry_lds_bytes(P), stream, *P, plan->ncols,
+                           b->joined, b->cost_T, b->lutC);
+    else
+        hipLaunchKernelGGL(k_lut_carry<2>, grid, dim3(LUTC_THREADS), isk_lut_carry_lds_bytes(P), stream, *P, plan->ncols,
+                           b->joined, b->cost_T, b->lutC);
+    return hipGetLastError();
+}
+
+/* columns one pass of k_lut_carry's grid-stride loop takes (tests: a call with more than that) */
+int isk_lut_carry_pass_columns(void) { return LUTC_MAX_WGS * (LUTC_THREADS / 64); }
+
 hipError_t isk_launch_prepare(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream) {
     const int ncols = plan->ncols;
     float* sv = plan->pairwise ? b->sv : nullptr; /* (only the pairwise phase 2 reads the S / V copies) */
-    if (!plan->prepare_lut) { /* the LUT units run inside the unary DP launch (k_dp_unary_fast, LUTF): records only here */
+    const bool carry_lds = plan->prepare_lut && plan->lut_carry && plan->lut_carry_lds;
+    /* the records alone: the LUT units run inside the unary DP launch (k_dp_unary_fast, LUTF), or the carry rows are
+     * k_lut_carry's -- both kernels only read `joined`, kernel boundaries order them in front of the DP (measured in
+     * both orders: 952 + 145 and 958 + 141 us per 64 frames) */
+    if (!plan->prepare_lut || carry_lds) {
         hipLaunchKernelGGL(k_prepare_columns, dim3(ncols), dim3(PREP_THREADS), isk_prepare_lds_bytes(P), stream, *P,
                            b->joined, b->seg, b->ground, b->vhor, b->recs, b->col_flags, sv, b->prune, b->n_generic,
                            b->path_bad);
-        return hipGetLastError();
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess || !carry_lds) return e;
+        return isk_launch_lut_carry(P, plan, b, stream);
     }
     /* the two prepare kernels are independent: one launch with workgroups of both kinds (k_prepare_fused) */
     const int units = ncols * ((P->D + 63) / 64);
@@ -910,6 +1037,14 @@ hipError_t isk_set_lds_prepare(const DevParams* P) {
     if (e != hipSuccess) return e;
     return hipFuncSetAttribute((const void*)k_prepare_fused<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)isk_prepare_lds_bytes(P));
+}
+
+hipError_t isk_set_lds_lut_carry(const DevParams* P) {
+    const int bytes = (int)isk_lut_carry_lds_bytes(P);
+    if (bytes == 0) return hipSuccess; /* the shape keeps k_prepare_fused<true> */
+    if (P->D <= 64)
+        return hipFuncSetAttribute((const void*)k_lut_carry<1>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    return hipFuncSetAttribute((const void*)k_lut_carry<2>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
 } /* extern "C" */

@@ -65,6 +65,7 @@ struct CallPlan {
     /* prepare */
     int prepare_lut;   /* 1: k_prepare_fused (records + object LUT); 0: k_prepare_columns (records only) */
     int lut_carry;     /* 1 (with unary_walk): the prepare launch stores only the LUT's block carries (lutC) */
+    int lut_carry_lds; /* 1 (with lut_carry, D <= 128): k_prepare_columns + k_lut_carry, the cost table in LDS */
     /* pairwise */
     int groups;        /* column groups, one stream each */
     int nsplit;        /* phase-1 workgroups per (column, tile) */
@@ -120,6 +121,10 @@ hipError_t isk_launch_priors(const DevParams* P, const float* ground, PriorRec* 
 hipError_t isk_launch_lut_repair(const DevParams* P, int ncols, const float* joined, const float* cost_T, float* lutT,
                                  const int* run_if, hipStream_t stream);
 hipError_t isk_launch_lut_generic(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream);
+size_t isk_lut_carry_lds_bytes(const DevParams* P);
+hipError_t isk_set_lds_lut_carry(const DevParams* P);
+hipError_t isk_launch_lut_carry(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream);
+int isk_lut_carry_pass_columns(void);
 
 /* is_k_unary.hip */
 size_t isk_unary_lds_bytes(const DevParams* P);
