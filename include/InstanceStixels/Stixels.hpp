@@ -101,6 +101,8 @@ struct StixelsBuffers {
     DeviceArray<char> d_idisp_inputs;
     DeviceArray<char> d_idisp_out;
     PinnedArray<char> h_idisp_out;
+    /* GroundTruthOffsetsBatch: the core's scratch (allocated on first use) */
+    DeviceArray<char> d_gt_targets_scratch;
     /* ComputeBatchRoad: [max_batch] RoadParameters | [max_batch] status bytes, the copy of the caller's device arrays */
     PinnedArray<char> h_road;
     void release_all() { /* in the order of the declarations */
@@ -116,10 +118,10 @@ struct StixelsBuffers {
         d_world_counts.release(); d_world_offsets.release(); d_world_totals.release(); d_world.release();
         h_world_totals.release(); h_world.release(); d_objects_block.release(); h_objects_block.release();
         d_sweep_stixels.release(); d_sweep_instances.release(); d_idisp_scratch.release(); d_idisp_inputs.release();
-        d_idisp_out.release(); h_idisp_out.release(); h_road.release();
+        d_idisp_out.release(); h_idisp_out.release(); d_gt_targets_scratch.release(); h_road.release();
     }
 };
-static_assert(sizeof(StixelsBuffers) == 47 * sizeof(DeviceArray<char>), "release_all() must release every array");
+static_assert(sizeof(StixelsBuffers) == 48 * sizeof(DeviceArray<char>), "release_all() must release every array");
 
 class Stixels : private StixelsBuffers {
 public:
@@ -309,6 +311,16 @@ public:
      * std::invalid_argument under RenderBatch's rules (before any compute, n_images beyond the last batch). */
     void AssignInstancesGTBatch(int n_images, const int32_t* d_gt_instance, void* stream = nullptr,
                                 std::vector<InstanceMapping>* mapping = nullptr);
+    /* f11 (an addition): the two offset channels of a DP input from the ground truth, the producer of the reference's
+     * "gt offsets" row (--usegtoffsets of tools/run_cityscapes.py: inference.py:388-396 with the 1/8-resolution
+     * targets of its training, datasets/cityscapes.py:146-167), as is_gt_instance_targets defines it.  Channels 19 and
+     * 20 of d_segmentation [n_images][cols / 8][21][rows_power2_segmentation] int32 are rewritten from d_gt_instance
+     * [n_images][rows][cols] int32 with the object's rows and cols, padding rows included; the class channels are not
+     * touched.  It is a producer like the CNN wrapper: valid before any compute call, asynchronous on `stream`, and
+     * it leaves the record of the last batch alone.  Throws std::invalid_argument for n_images outside [1, max_batch],
+     * a null pointer, or rows / cols that are no multiples of 8. */
+    void GroundTruthOffsetsBatch(int n_images, const int32_t* d_gt_instance, int32_t* d_segmentation,
+                                 void* stream = nullptr);
     /* Back to the cluster labels of the last compute call. */
     void UseClusterInstances() { m_last.gt_instances = false; }
     /* The vote's parameters (defaults: the reference's): the minimum fraction of the 10 % rule, the labelIds of

@@ -677,6 +677,89 @@ size_t is_instance_disparity_scratch_bytes(int n_images, int realcols, int max_s
  * finite, min_pts < 1, and for the shape, alignment and scratch constraints above. */
 int is_cluster_instance_disparity(const is_instance_disparity_args* args, void* stream);
 
+/* ---- f11: ground-truth offset targets and CNN offset channels (is_k_gt_targets.hip) ---------------------------------
+ * Replaces the producer of the third "what if" row of the reference's instance evaluation, the CNN's two offset
+ * channels taken from the ground truth (--usegtoffsets: tools/run_cityscapes.py:228,255-256 ->
+ * tools/CNN_training/inference.py:388-396), which is also the producer of its training's regression targets
+ * (tools/CNN_training/datasets/cityscapes.py:114-167 on images mode-downsampled by 8, datasets/transforms.py:49-70).
+ * Per frame, with Hs = rows / 8 and Ws = cols / 8; rows and cols must be multiples of 8 (the reference's filter
+ * raises on anything else):
+ *   1. mode-downsample (modefilter_np, transforms.py:59-70): cell (y, x) takes the most frequent value of the block
+ *      [8y, 8y + 8) x [8x, 8x + 8); ties go to the SMALLEST value (np.bincount(..).argmax()).  Negative int32 values
+ *      are outside the reference's domain (bincount raises); here they are compared as signed values like any other.
+ *   2. keys: a cell whose downsampled id is > 1000 has a key, the id itself (1000 has none, 1001 has one).  There is
+ *      no class filter, as the reference has none: caravan and trailer ids and instanceTrainIds values work alike.
+ *   3. offsets (_instance_offsets, cityscapes.py:146-167): per key, n = its cells, sy and sx = the INTEGER sums of
+ *      their cell row and column indices; for each of its cells, in fp32 without contraction and with IEEE division
+ *      (not a reciprocal: sum * (1 / n) differs from the reference, also after the conversion of step 5),
+ *          off_y = (float)sy / (float)n - (float)y,    off_x = (float)sx / (float)n - (float)x;
+ *      every other cell is (0, 0).  The reference sums in fp32, which is exact while a key's sums stay below 2^24 --
+ *      always at Hs * Ws * max(Hs, Ws) < 2^24, e.g. 128 x 256 cells; beyond that the 64-bit integer sum rounded once
+ *      is the definition.  The sums cannot wrap.
+ *   4. disparity plane (_instance_offsets_disparity, :114-144), with the raw uint16 disparity image: mode-downsample
+ *      it, q = v / 256 (integer); per key the LOWER median (torch.median) of its non-zero q, 0 where it has none, in
+ *      every cell of the key; 0 in cells without a key.
+ *   5. as prediction (inference.py:393-396 followed by FlipAndPad, wrappers.py:35-61): into d_segmentation
+ *      [n_images][Ws][21][P2S] int32, for cell (y, x):
+ *          seg[f][x][19][Hs-1-y] = (int32)(8.0f * off_y),    seg[f][x][20][Hs-1-y] = (int32)(8.0f * off_x)
+ *      (truncation toward zero); rows Hs .. P2S-1 of both channels are written 0 and the 19 class channels are not
+ *      touched: is_flip_and_pad of a CNN output whose last two channels were replaced by step 3, in the order (y, x)
+ *      of the DP's channels 19 and 20 (StixelsKernels.cu:393-405).
+ * The reference's own as_prediction assignment only fits its full-resolution models, the shapes do not match for the
+ * downsampled ones it ships configs for; the 1/8-resolution semantics here are those of its training pipeline, the
+ * only ones its DRNDS* models were ever given.
+ *
+ * With a disparity image the keys of a frame are numbered to `capacity` histograms of 1 KiB.  A frame with more keys
+ * than that is never truncated: the call then writes NO output of any frame (targets, ids, segmentation) and
+ * d_key_count reports the frame's TRUE count (> capacity), which is how the caller learns of it.
+ *
+ * Zero-initialise before setting fields.  All device arrays are on the current device.
+ *   d_gt_instance       [n_images][rows][cols] int32, 4-byte aligned (16-byte aligned: vector loads); any value
+ *   d_disparity_u16     optional, [n_images][rows][cols] uint16, 2-byte aligned (16-byte aligned: vector loads)
+ *   n_images, rows, cols   n_images in [1, 65535]; rows, cols multiples of 8, >= 8; Hs * Ws <= 2^28
+ *   d_targets, target_planes   optional, [n_images][target_planes][Hs][Ws] float: planes (off_y, off_x) with 2,
+ *                       (disparity, off_y, off_x) with 3, which needs d_disparity_u16; target_planes is 0 without
+ *   d_ids8              optional, [n_images][Hs][Ws] int32: step 1 of d_gt_instance
+ *   d_segmentation, rows_power2_segmentation, channels   optional: step 5; P2S a power of two > Hs, channels == 21
+ *                       (both 0 without d_segmentation).  At least one of the three outputs is required.
+ *   capacity            histograms per frame, in [1, min(Hs * Ws, IS_GT_TARGETS_MAX_CAPACITY)]; 0 selects
+ *                       min(256, Hs * Ws).  Without d_disparity_u16 it only has to be in range.
+ *   d_scratch           16-byte aligned, scratch_bytes >= is_gt_targets_scratch_bytes(n_images, rows, cols,
+ *                       with_disparity, capacity); its contents mean nothing between calls
+ *   d_key_count         optional, [n_images] int32: the distinct keys of every frame, written also on overflow */
+#define IS_GT_TARGETS_CHANNELS 21
+#define IS_GT_TARGETS_MAX_CAPACITY 8192
+#define IS_DTYPE_UINT8 0
+#define IS_DTYPE_UINT16 1
+#define IS_DTYPE_INT32 2
+typedef struct is_gt_targets_args {
+    const int32_t* d_gt_instance;
+    const uint16_t* d_disparity_u16;
+    int n_images, rows, cols;
+    float* d_targets;
+    int target_planes;
+    int32_t* d_ids8;
+    int32_t* d_segmentation;
+    int rows_power2_segmentation, channels;
+    int capacity;
+    void* d_scratch;
+    size_t scratch_bytes;
+    int32_t* d_key_count;
+} is_gt_targets_args;
+
+/* Step 1 alone for n_images images [rows][cols] of dtype IS_DTYPE_* (instance ids, raw disparity, semantic gt):
+ * d_dst [n_images][rows / 8][cols / 8] of the same type.  d_src and d_dst aligned to their element (a 16-byte aligned
+ * d_src takes vector loads); rows and cols multiples of 8.  One launch on `stream`. */
+int is_mode_downsample(const void* d_src, int dtype, int n_images, int rows, int cols, void* d_dst, void* stream);
+/* Bytes of d_scratch for a call of that shape (0 for a shape or capacity the call refuses); capacity 0 as above. */
+size_t is_gt_targets_scratch_bytes(int n_images, int rows, int cols, int with_disparity, int capacity);
+/* The outputs of n_images frames on `stream`, asynchronously and stream-ordered: one memset and three launches
+ * (six with a disparity image), no allocation, copy or synchronisation.  Integer atomics only: the same bytes on
+ * every run.  IS_EINVAL, with the reason in is_last_error() and before any device call, for null or inconsistent
+ * outputs, 3 planes without a disparity image, shapes that are not multiples of 8, a P2S that is not a power of two
+ * > Hs, channels != 21, misaligned or undersized scratch and a capacity out of range. */
+int is_gt_instance_targets(const is_gt_targets_args* args, void* stream);
+
 /* ---- f9: per-instance objects and their contours (is_k_objects.hip) ------------------------------------------------
  * What the reference's consumers reduce on the host from the per-stixel output: the top-down view
  * (tools/visualization/clustering_visualization.py:563-792: per instance and column the closest stixel, connected

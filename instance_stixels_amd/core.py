@@ -38,6 +38,7 @@ EXPORTS = [
     "is_instance_objects",
     "is_compute_sweep", "is_recluster",
     "is_cluster_instance_disparity", "is_instance_disparity_scratch_bytes",
+    "is_mode_downsample", "is_gt_targets_scratch_bytes", "is_gt_instance_targets",
 ]
 RENDER_MAX_LABELS = 64    # IS_RENDER_MAX_LABELS
 RENDER_MAX_CLASSES = 256  # IS_RENDER_MAX_CLASSES
@@ -151,6 +152,19 @@ class InstanceDisparityArgs(ctypes.Structure):
                 ("scratch_bytes", ctypes.c_size_t), ("d_stixel_median", vp), ("d_key_count", vp), ("d_key_median", vp)]
 
 
+GT_TARGETS_MAX_CAPACITY = 8192  # IS_GT_TARGETS_MAX_CAPACITY
+DTYPE_UINT8, DTYPE_UINT16, DTYPE_INT32 = 0, 1, 2  # IS_DTYPE_*
+
+
+class GtTargetsArgs(ctypes.Structure):
+    """is_gt_targets_args: zero-initialised by ctypes; device pointers as ints."""
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    _fields_ = [("d_gt_instance", vp), ("d_disparity_u16", vp), ("n_images", ci), ("rows", ci), ("cols", ci),
+                ("d_targets", vp), ("target_planes", ci), ("d_ids8", vp), ("d_segmentation", vp),
+                ("rows_power2_segmentation", ci), ("channels", ci), ("capacity", ci), ("d_scratch", vp),
+                ("scratch_bytes", ctypes.c_size_t), ("d_key_count", vp)]
+
+
 class RoadParams(ctypes.Structure):
     """is_road_params: one frame's road, the layout of Stixels::RoadParameters (16 bytes)"""
     _fields_ = [("vhor", ctypes.c_int), ("tilt", ctypes.c_float), ("height", ctypes.c_float),
@@ -232,6 +246,10 @@ def lib():
         L.is_cluster_instance_disparity.argtypes = [ctypes.POINTER(InstanceDisparityArgs), vp]
         L.is_instance_disparity_scratch_bytes.argtypes = [ci, ci, ci, ci]
         L.is_instance_disparity_scratch_bytes.restype = ctypes.c_size_t
+        L.is_mode_downsample.argtypes = [vp, ci, ci, ci, ci, vp, vp]
+        L.is_gt_targets_scratch_bytes.argtypes = [ci, ci, ci, ci, ci]
+        L.is_gt_targets_scratch_bytes.restype = ctypes.c_size_t
+        L.is_gt_instance_targets.argtypes = [ctypes.POINTER(GtTargetsArgs), vp]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
         L.is_get_device.argtypes = [ctypes.POINTER(ci)]
@@ -730,3 +748,119 @@ def flip_and_pad(cnn_out, rows_power2_segmentation, device=0):
                                  torch.cuda.current_stream(dev).cuda_stream), "is_flip_and_pad")
     torch.cuda.synchronize(dev)
     return out.cpu().numpy()
+
+
+def mode_downsample_ptr(d_src, dtype, n_images, rows, cols, d_dst, stream=0):
+    """is_mode_downsample on raw device pointers (ints).  Returns the return code and raises nothing (the tests check
+    IS_EINVAL)."""
+    return lib().is_mode_downsample(d_src, int(dtype), int(n_images), int(rows), int(cols), d_dst,
+                                    ctypes.c_void_p(int(stream)))
+
+
+def gt_targets_scratch_bytes(n_images, rows, cols, with_disparity=False, capacity=0):
+    """is_gt_targets_scratch_bytes: the scratch a call of that shape needs (0: a shape the call refuses)."""
+    return int(lib().is_gt_targets_scratch_bytes(int(n_images), int(rows), int(cols), int(bool(with_disparity)),
+                                                 int(capacity)))
+
+
+def gt_instance_targets_ptr(stream=0, **fields):
+    """is_gt_instance_targets on raw device pointers (ints): fields are those of GtTargetsArgs.  Asynchronous on
+    `stream`; returns the return code and raises nothing (the tests check IS_EINVAL)."""
+    a = GtTargetsArgs(**fields)
+    return lib().is_gt_instance_targets(ctypes.byref(a), ctypes.c_void_p(int(stream)))
+
+
+def _torch_dtype_code(t):
+    import torch
+    codes = {torch.uint8: DTYPE_UINT8, torch.uint16: DTYPE_UINT16, torch.int32: DTYPE_INT32}
+    if t.dtype not in codes:
+        raise CoreError(f"dtype {t.dtype} is none of uint8, uint16, int32")
+    return codes[t.dtype]
+
+
+def mode_downsample(t):
+    """The reference's ModeDownsample(8) of a device tensor [n][rows][cols] (or [rows][cols]) of dtype uint8, uint16
+    or int32: the most frequent value of every 8x8 block, the smallest among equals.  A tensor of the same dtype
+    [n][rows / 8][cols / 8] on the input's device, enqueued on the current torch stream."""
+    import torch
+    if not t.is_cuda:
+        raise CoreError("mode_downsample takes a device tensor")
+    x = t.contiguous()
+    if x.dim() not in (2, 3):
+        raise CoreError("mode_downsample takes [n][rows][cols] or [rows][cols]")
+    n = x.shape[0] if x.dim() == 3 else 1
+    rows, cols = x.shape[-2:]
+    with torch.cuda.device(x.device):
+        out = torch.empty(tuple(x.shape[:-2]) + (rows // 8, cols // 8), dtype=x.dtype, device=x.device)
+        _check(lib().is_mode_downsample(x.data_ptr(), _torch_dtype_code(x), n, rows, cols, out.data_ptr(),
+                                        torch.cuda.current_stream(x.device).cuda_stream), "is_mode_downsample")
+    return out
+
+
+def gt_instance_targets(gt_instance, disparity_u16=None, segmentation=None, rows_power2_segmentation=None,
+                        out=None, capacity=0, return_key_count=False):
+    """The ground-truth offset targets of a batch (is_gt_instance_targets, instance_stixels_core.h f11).
+
+    gt_instance      device int32 [n][rows][cols], rows and cols multiples of 8
+    disparity_u16    optional device uint16 [n][rows][cols]: the targets get the disparity plane in front
+    segmentation     optional device int32 [n][cols / 8][21][P2S]: channels 19 and 20 are rewritten in place
+    rows_power2_segmentation   its last dimension (default: taken from the tensor)
+    out              optional device float32 [n][2 or 3][rows / 8][cols / 8] to write the targets into
+
+    Returns (targets, ids8) as torch tensors on the inputs' device, enqueued on the current torch stream; with
+    return_key_count the frames' key counts as a third tensor.  With a disparity image the frames' key counts are
+    read back (one synchronisation), and a frame with more keys than `capacity` (0: the default of the C ABI) makes
+    the call repeat with that count, so the result is always complete."""
+    import torch
+    g = gt_instance
+    if not g.is_cuda or g.dtype != torch.int32 or g.dim() != 3:
+        raise CoreError("gt_instance must be a device int32 tensor [n][rows][cols]")
+    g = g.contiguous()
+    dev = g.device
+    n, rows, cols = g.shape
+    planes = 3 if disparity_u16 is not None else 2
+    d = None
+    if disparity_u16 is not None:
+        d = disparity_u16
+        if d.device != dev or d.dtype != torch.uint16 or tuple(d.shape) != tuple(g.shape):
+            raise CoreError("disparity_u16 must be a uint16 tensor of gt_instance's shape and device")
+        d = d.contiguous()
+    Hs, Ws = rows // 8, cols // 8
+    if out is None:
+        out = torch.empty((n, planes, Hs, Ws), dtype=torch.float32, device=dev)
+    elif (out.device != dev or out.dtype != torch.float32 or tuple(out.shape) != (n, planes, Hs, Ws)
+          or not out.is_contiguous()):
+        raise CoreError(f"out must be a contiguous float32 tensor {(n, planes, Hs, Ws)} on gt_instance's device")
+    p2s = 0
+    if segmentation is not None:
+        s = segmentation
+        p2s = int(rows_power2_segmentation) if rows_power2_segmentation is not None else int(s.shape[-1])
+        if (s.device != dev or s.dtype != torch.int32 or tuple(s.shape) != (n, Ws, 21, p2s)
+                or not s.is_contiguous()):
+            raise CoreError(f"segmentation must be a contiguous int32 tensor {(n, Ws, 21, p2s)} on gt_instance's device")
+    with torch.cuda.device(dev):
+        ids8 = torch.empty((n, Hs, Ws), dtype=torch.int32, device=dev)
+        count = torch.empty((n,), dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        while True:
+            nbytes = gt_targets_scratch_bytes(n, rows, cols, d is not None, capacity)
+            if nbytes == 0:
+                raise CoreError("is_gt_targets_scratch_bytes refuses the shape or the capacity "
+                                f"(n_images {n}, rows {rows}, cols {cols}, capacity {capacity})")
+            scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            a = GtTargetsArgs(d_gt_instance=g.data_ptr(), d_disparity_u16=d.data_ptr() if d is not None else None,
+                              n_images=n, rows=rows, cols=cols, d_targets=out.data_ptr(), target_planes=planes,
+                              d_ids8=ids8.data_ptr(),
+                              d_segmentation=segmentation.data_ptr() if segmentation is not None else None,
+                              rows_power2_segmentation=p2s, channels=21 if segmentation is not None else 0,
+                              capacity=int(capacity), d_scratch=scratch.data_ptr(), scratch_bytes=nbytes,
+                              d_key_count=count.data_ptr())
+            _check(lib().is_gt_instance_targets(ctypes.byref(a), ctypes.c_void_p(stream)), "is_gt_instance_targets")
+            if d is None:
+                break
+            most = int(count.max().item())
+            effective = int(capacity) if capacity else min(256, Hs * Ws)
+            if most <= effective:
+                break
+            capacity = most   # (never above the cells of a frame; above IS_GT_TARGETS_MAX_CAPACITY it is refused)
+    return (out, ids8, count) if return_key_count else (out, ids8)

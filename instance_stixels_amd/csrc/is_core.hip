@@ -893,6 +893,69 @@ int is_cluster_instance_disparity(const is_instance_disparity_args* a, void* str
     return IS_OK;
 }
 
+/* ---- f11: ground-truth offset targets (is_k_gt_targets.hip) ---- */
+/* a frame of 8x8 cells: rows and cols multiples of 8, at most 2^28 cells */
+static const char* cells_fault(int n_images, int rows, int cols) {
+    if (n_images < 1 || n_images > 65535) return "n_images outside [1, 65535]";
+    if (rows < 8 || cols < 8 || rows % 8 != 0 || cols % 8 != 0) return "rows and cols must be multiples of 8, >= 8";
+    if ((long long)(rows / 8) * (cols / 8) > (1LL << 28)) return "more than 2^28 cells per frame";
+    if ((long long)n_images * (rows / 8) * ((cols / 8 + 63) / 64) > 0x7fffffffLL) return "batch too large for one launch";
+    return nullptr;
+}
+/* the capacity a call works with (0 selects min(256, cells)), or 0 where it is out of range */
+static int gt_targets_capacity(int rows, int cols, int capacity) {
+    const long long cells = (long long)(rows / 8) * (cols / 8);
+    const int most = (int)(cells < IS_GT_TARGETS_MAX_CAPACITY ? cells : IS_GT_TARGETS_MAX_CAPACITY);
+    if (capacity == 0) return most < 256 ? most : 256;
+    return capacity < 1 || capacity > most ? 0 : capacity;
+}
+
+int is_mode_downsample(const void* d_src, int dtype, int n_images, int rows, int cols, void* d_dst, void* stream) {
+    if (!d_src || !d_dst) return fail_arg("null pointer");
+    if (dtype != IS_DTYPE_UINT8 && dtype != IS_DTYPE_UINT16 && dtype != IS_DTYPE_INT32)
+        return fail_arg("dtype is none of IS_DTYPE_UINT8, IS_DTYPE_UINT16, IS_DTYPE_INT32");
+    if (const char* fault = cells_fault(n_images, rows, cols)) return fail_arg(fault);
+    const uintptr_t element = dtype == IS_DTYPE_INT32 ? 4 : dtype == IS_DTYPE_UINT16 ? 2 : 1;
+    if (misaligned(element, d_src, d_dst)) return fail_arg("d_src and d_dst must be aligned to their element");
+    HIP_TRY(isk_launch_mode_downsample(d_src, dtype, n_images, rows / 8, cols / 8, d_dst, (hipStream_t)stream));
+    return IS_OK;
+}
+
+size_t is_gt_targets_scratch_bytes(int n_images, int rows, int cols, int with_disparity, int capacity) {
+    if (cells_fault(n_images, rows, cols)) return 0;
+    const int cap = gt_targets_capacity(rows, cols, capacity);
+    return cap ? isk_gt_targets_scratch_bytes(n_images, rows / 8, cols / 8, with_disparity, cap) : 0;
+}
+
+int is_gt_instance_targets(const is_gt_targets_args* a, void* stream) {
+    if (!a) return fail_arg("null args");
+    if (!a->d_gt_instance) return fail_arg("null d_gt_instance");
+    if (!a->d_targets && !a->d_ids8 && !a->d_segmentation) return fail_arg("no output: d_targets, d_ids8 and d_segmentation are all null");
+    if (a->d_targets ? a->target_planes != 2 && a->target_planes != 3 : a->target_planes != 0)
+        return fail_arg("target_planes must be 2 or 3 with d_targets, 0 without");
+    if (a->target_planes == 3 && !a->d_disparity_u16) return fail_arg("3 target planes need d_disparity_u16");
+    if (const char* fault = cells_fault(a->n_images, a->rows, a->cols)) return fail_arg(fault);
+    if (a->d_segmentation) {
+        const int p2s = a->rows_power2_segmentation;
+        if (p2s < a->rows / 8 + 1 || (p2s & (p2s - 1)) != 0)
+            return fail_arg("rows_power2_segmentation must be a power of two > rows/8 (Stixels.cu:132-133)");
+        if (a->channels != IS_GT_TARGETS_CHANNELS) return fail_arg("channels must be 21 with d_segmentation");
+    } else if (a->rows_power2_segmentation != 0 || a->channels != 0) {
+        return fail_arg("rows_power2_segmentation and channels must be 0 without d_segmentation");
+    }
+    const int capacity = gt_targets_capacity(a->rows, a->cols, a->capacity);
+    if (!capacity) return fail_arg("capacity outside [1, min(rows/8 * cols/8, IS_GT_TARGETS_MAX_CAPACITY)]");
+    if (!a->d_scratch) return fail_arg("null d_scratch");
+    if (misaligned(16, a->d_scratch)) return fail_arg("d_scratch must be 16-byte aligned");
+    if (misaligned(4, a->d_gt_instance, a->d_targets, a->d_ids8, a->d_segmentation, a->d_key_count))
+        return fail_arg("d_gt_instance, d_targets, d_ids8, d_segmentation and d_key_count must be 4-byte aligned");
+    if (misaligned(2, a->d_disparity_u16)) return fail_arg("d_disparity_u16 must be 2-byte aligned");
+    if (a->scratch_bytes < isk_gt_targets_scratch_bytes(a->n_images, a->rows / 8, a->cols / 8, a->d_disparity_u16 != nullptr, capacity))
+        return fail_arg("scratch_bytes below is_gt_targets_scratch_bytes()");
+    HIP_TRY(isk_launch_gt_targets(a, capacity, (hipStream_t)stream));
+    return IS_OK;
+}
+
 /* ---- f9: per-instance objects and contours (is_k_objects.hip) ---- */
 int is_instance_objects(const is_instance_objects_args* a, void* stream) {
     if (!a) return fail_arg("null args");

@@ -236,6 +236,12 @@ hipError_t isk_launch_pack_section_labels(const int32_t* map, int n_images, int 
 size_t isk_instance_disparity_scratch_bytes(int n_images, int realcols, int max_sections, int capacity);
 hipError_t isk_launch_instance_disparity(const is_instance_disparity_args* r, hipStream_t stream);
 
+/* is_k_gt_targets.hip */
+hipError_t isk_launch_mode_downsample(const void* src, int dtype, int n, int Hs, int Ws, void* dst,
+                                      hipStream_t stream);
+size_t isk_gt_targets_scratch_bytes(int n_images, int Hs, int Ws, int disparity, int capacity);
+hipError_t isk_launch_gt_targets(const is_gt_targets_args* r, int capacity, hipStream_t stream);
+
 /* is_k_objects.hip */
 hipError_t isk_launch_instance_objects(const is_instance_objects_args* r, hipStream_t stream);
 

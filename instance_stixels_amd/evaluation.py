@@ -271,3 +271,20 @@ def instance_disparity_scores(st, gt_instance, disparity_u8, eps, min_pts, size_
     ev = evaluator if evaluator is not None else CityscapesInstanceEval()
     ev.add(overlaps)
     return dict(overlaps=overlaps, result=ev.result())
+
+
+def gt_offset_scores(st, pairwise, d_disparity_big, d_segmentation, road, gt_instance, evaluator=None, stream=0):
+    """The instance AP of a resident batch with the CNN's two offset channels replaced by the ground truth, the
+    reference's --usegtoffsets row, without a per-frame loop: GroundTruthOffsetsBatch rewrites channels 19 and 20 of
+    d_segmentation (device int32 [frames][cols / 8][21][P2S], a pointer as int; it is CHANGED), then ComputeBatch on
+    d_disparity_big and that tensor with `road` (one tuple per frame), InstanceOverlapBatch against the same ground
+    truth, then CityscapesInstanceEval.  gt_instance: device int32 [frames][rows][cols] (a pointer as int).
+    evaluator: a CityscapesInstanceEval to add the frames to (one is made otherwise).  Returns dict(stixels = the
+    frames' StixelsData, overlaps = the per-frame tables, result = evaluator.result())."""
+    frames = len(road)
+    st.GroundTruthOffsetsBatch(frames, gt_instance, d_segmentation, stream=stream)
+    stixels, _ = st.ComputeBatch(pairwise, d_disparity_big, d_segmentation, road, with_instances=True, stream=stream)
+    overlaps = st.InstanceOverlapBatch(frames, gt_instance, stream=stream)
+    ev = evaluator if evaluator is not None else CityscapesInstanceEval()
+    ev.add(overlaps)
+    return dict(stixels=stixels, overlaps=overlaps, result=ev.result())

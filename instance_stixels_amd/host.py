@@ -34,6 +34,7 @@ EXPORTS = [
     "ish_world_batch", "ish_world_records", "ish_set_world_capacity",
     "ish_instance_objects_batch", "ish_instance_objects_records", "ish_set_instance_object_capacity",
     "ish_assign_instances_gt_batch", "ish_assign_instances_gt_quads", "ish_use_cluster_instances", "ish_set_gt_assignment_parameters",
+    "ish_ground_truth_offsets_batch",
     "ish_core_sweep_set", "ish_sweep_batch", "ish_select_sweep_set", "ish_last_frames", "ish_sweep_sets",
     "ish_active_device", "ish_sweep_sections", "ish_recluster_batch",
     "ish_cluster_instance_disparity_batch", "ish_set_instance_disparity_capacity",
@@ -129,6 +130,7 @@ def lib():
         L.ish_assign_instances_gt_batch.argtypes = [vp, ci, vp, ctypes.POINTER(ctypes.c_int64), vp]
         L.ish_assign_instances_gt_quads.argtypes = [vp, vp, ctypes.c_int64]
         L.ish_use_cluster_instances.argtypes = [vp]
+        L.ish_ground_truth_offsets_batch.argtypes = [vp, ci, vp, vp, vp]
         L.ish_set_gt_assignment_parameters.argtypes = [vp, ctypes.c_double, vp, ci]
         L.ish_core_sweep_set.argtypes = [vp, ctypes.POINTER(_core.SweepSet)]
         L.ish_sweep_batch.argtypes = [vp, ci, ci, vp, vp, vp, vp, ci, ci, vp]
@@ -478,6 +480,16 @@ class Stixels:
         for f, u, v, l in quads.tolist():
             maps[f][(u, v)] = l
         return maps
+
+    def GroundTruthOffsetsBatch(self, n, d_gt, d_segmentation, stream=0):
+        """Stixels::GroundTruthOffsetsBatch: channels 19 and 20 of d_segmentation (device int32
+        [n][cols / 8][21][P2S], an int pointer) from the ground-truth instanceIds d_gt (device int32 [n][rows][cols]),
+        the reference's --usegtoffsets producer; the class channels are not touched.  A producer: legal before any
+        compute call, asynchronous on `stream`."""
+        self._check(lib().ish_ground_truth_offsets_batch(
+            self._h, int(n), ctypes.c_void_p(int(d_gt)) if d_gt else None,
+            ctypes.c_void_p(int(d_segmentation)) if d_segmentation else None, ctypes.c_void_p(int(stream))),
+            "GroundTruthOffsetsBatch")
 
     # ---- parameter sweeps ------------------------------------------------------------
     def SweepBatch(self, pairwise, d_disparity_big, d_segmentation, road, sets, with_instances=True, stream=0):

@@ -782,6 +782,30 @@ const int32_t* Stixels::SectionInstanceMap(int n_images, void* stream) {
     return d_section_instance.get();
 }
 
+/* Replaces the reference's --usegtoffsets producer (inference.py:388-396 over cityscapes.py:146-167) for a batch. */
+void Stixels::GroundTruthOffsetsBatch(int n_images, const int32_t* d_gt, int32_t* d_seg, void* stream) {
+    if (n_images < 1 || n_images > m_max_batch)
+        throw std::invalid_argument("GroundTruthOffsetsBatch: n_images outside [1, max_batch] of InitializeBatch().");
+    if (d_gt == nullptr || d_seg == nullptr)
+        throw std::invalid_argument("GroundTruthOffsetsBatch: null d_gt_instance or d_segmentation.");
+    const DeviceGuard guard(m_ctx_device);
+    if (stream == nullptr) stream = m_stream;
+    is_gt_targets_args a = {};
+    a.d_gt_instance = d_gt;
+    a.n_images = n_images;
+    a.rows = m_rows;
+    a.cols = m_cols;
+    a.d_segmentation = d_seg;
+    a.rows_power2_segmentation = m_params.rows_power2_segmentation;
+    a.channels = m_segmentation_channels;
+    a.scratch_bytes = is_gt_targets_scratch_bytes(m_max_batch, m_rows, m_cols, 0, 0);
+    if (a.scratch_bytes == 0)
+        throw std::invalid_argument("GroundTruthOffsetsBatch: rows and cols must be multiples of 8.");
+    d_gt_targets_scratch.reserve(a.scratch_bytes);
+    a.d_scratch = d_gt_targets_scratch.get();
+    CheckConsumer("GroundTruthOffsetsBatch", is_gt_instance_targets(&a, stream));
+}
+
 void Stixels::SetGTAssignmentParameters(double min_fraction, const int* label_ids8, bool gt_is_train_ids) {
     static const int kCityscapes[IS_INSTANCE_CLASSES] = {24, 25, 26, 27, 28, 31, 32, 33};
     if (min_fraction != min_fraction) throw std::invalid_argument("SetGTAssignmentParameters: min_fraction is NaN.");

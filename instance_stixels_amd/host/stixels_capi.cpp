@@ -416,6 +416,11 @@ int ish_assign_instances_gt_quads(void* h, int32_t* out, int64_t cap) {
         if (!q.empty()) std::memcpy(out, q.data(), q.size() * sizeof(int32_t));
     });
 }
+/* GroundTruthOffsetsBatch(): channels 19 and 20 of d_segmentation from the ground truth; asynchronous on `stream`. */
+int ish_ground_truth_offsets_batch(void* h, int n, const int32_t* d_gt_instance, int32_t* d_segmentation,
+                                   void* stream) {
+    return guard([&] { ((Stixels*)h)->GroundTruthOffsetsBatch(n, d_gt_instance, d_segmentation, stream); });
+}
 int ish_use_cluster_instances(void* h) {
     return guard([&] { ((Stixels*)h)->UseClusterInstances(); });
 }
