@@ -760,6 +760,96 @@ size_t is_gt_targets_scratch_bytes(int n_images, int rows, int cols, int with_di
  * > Hs, channels != 21, misaligned or undersized scratch and a capacity out of range. */
 int is_gt_instance_targets(const is_gt_targets_args* args, void* stream);
 
+/* ---- f12: the offset and disparity training losses of a batch, with their gradient (is_k_offset_loss.hip) ----------
+ * The two "SL" regression losses the reference's DRN models were trained with (tools/CNN_training/losses.py:
+ * OffsetLossSL :127-175, DisparityOffsetLossSL :24-125; used at train.py:127, 279, 322, 719-727), on the tensors f11
+ * leaves on the device: the network's 2 or 3 regression channels at 1/8 resolution, the instance ids mode-downsampled
+ * by 8 and the raw disparity mode-downsampled by 8.  One asynchronous call gives the loss, its four parts and
+ * d loss / d prediction.  The definition is the reference's code evaluated in binary64 on the fp32 inputs (the
+ * weights included, which arrive here as floats); the outputs are rounded to fp32 once, at the store.  Per frame:
+ *
+ *   Inputs.  P [planes][Hs][Ws] fp32: (off_y, off_x) with 2 planes, (disp, off_y, off_x) with 3 (the plane order of
+ *   f11's targets).  ids [Hs][Ws] int32.  With 3 planes d8 [Hs][Ws] uint16 and q = d8 >> 8.  Cell (y, x) has the
+ *   position (y, x) in image order: pos_y = off_y + y, pos_x = off_x + x.
+ *   Keys.  Every id > 1000 is a key (1000 is none, 1001 is one; no class filter).  Per key k over its n cells:
+ *   g = (sum y / n, sum x / n); m = the per-axis mean of pos; md = the mean of disp; med = the LOWER median
+ *   (torch.median) of its non-zero q, which a key without a non-zero q does not have.
+ *   Stuff.  A cell with id < 11 (negative ids included) or id == 255; there are s of them.  Every other cell
+ *   (ids 11 .. 1000 without 255) contributes nothing and has the gradient 0.
+ *   Terms.
+ *     offset_mean          sum_k sum_cells (|pos_y - g_y| + |pos_x - g_x|) / n / 2  +  sum_stuff (|off_y| + |off_x|) / s / 2
+ *     offset_variance      abs_variance == 0: sum_k (var_y + var_x) / 2, the population variance (0 for n == 1)
+ *                          abs_variance != 0: sum_{k: n > 2} sum_cells (|pos_y - m_y| + |pos_x - m_x|) / n / 2
+ *     disparity_variance   (3 planes) abs_variance == 0: sum_k var(disp);  else sum_{k: n > 2} sum_cells |disp - md| / n
+ *     disparity_mean       (3 planes) sum_{k with a med} sum_cells |disp - med| / n  +  sum_stuff |disp| / s
+ *                          (n counts ALL cells of the key)
+ *     loss = w_offset_mean * offset_mean + w_offset_variance * offset_variance + w_disparity_mean * disparity_mean
+ *            + w_disparity_variance * disparity_variance, each term summed over the frames first and NOT divided by
+ *            the batch size.  With 2 planes the two disparity terms are 0 and are left out of the loss.
+ *     A frame without stuff has NaN in offset_mean (and disparity_mean): the reference computes 0 / 0 there, and so
+ *     does this; the frame's gradient stays finite.
+ *   Gradient.  torch's, with d|v|/dv = sign(v) and sign(0) = 0; each line times its weight, the lines added:
+ *     keyed, offset axes   offset_mean: sign(pos - g) / (2n)
+ *                          offset_variance: (pos - m) / n;  abs form, n > 2: (sign(pos - m) - sum_j sign(pos_j - m) / n) / (2n)
+ *                          (the reference does not detach the predicted mean)
+ *     keyed, disparity     disparity_mean: sign(disp - med) / n where the key has a med
+ *                          disparity_variance: 2 (disp - md) / n;  abs form, n > 2: (sign(disp - md) - sum_j sign(disp_j - md) / n) / n
+ *     stuff                sign(off) / (2s) and sign(disp) / s
+ *     A weight of 0 removes its lines from the gradient; the term itself is still reported.
+ *   A non-finite prediction in a contributing cell makes the affected terms of ITS frame non-finite; the terms and
+ *   gradients of the other frames are those of the clean batch.
+ *
+ * Every sum over predictions is binary64 and combined in an order the input alone decides (no floating-point
+ * atomics; integer atomics for the key table and the q histograms): the same bytes on every run, the same bytes for a
+ * frame alone and inside a batch, and the frames' terms and gradients follow a permutation of the frames.
+ *
+ * A frame's keys are ranked into `capacity` rows.  A frame with more keys than that is never truncated: d_loss and
+ * d_terms become NaN, d_grad is left unwritten and d_key_count reports the TRUE counts.
+ *
+ * Zero-initialise before setting fields.  All device arrays are on the current device; floats and int32 4-byte
+ * aligned, d_disparity8_u16 2-byte aligned.
+ *   d_prediction, prediction_image_stride   frame f starts at d_prediction + f * stride (elements), its planes are
+ *                       contiguous [planes][rows8][cols8]; stride >= planes * rows8 * cols8 (the last channels of a
+ *                       wider tensor need no copy)
+ *   d_ids8              [n_images][rows8][cols8] int32
+ *   d_disparity8_u16    [n_images][rows8][cols8] uint16 with 3 planes, null with 2
+ *   n_images, planes, rows8, cols8   n_images in [1, 65535]; planes 2 or 3; rows8 = Hs, cols8 = Ws >= 1; Hs * Ws <= 2^28
+ *   w_*, abs_variance   the weights and the reference's abs_variance switch
+ *   d_loss              [5] float: loss, offset_mean, offset_variance, disparity_mean, disparity_variance (batch sums)
+ *   d_terms             optional, [n_images][4] float: the frames' four terms
+ *   d_grad, grad_image_stride   optional: d loss / d prediction laid out as the prediction with its own stride
+ *                       (>= planes * rows8 * cols8); all planes of every frame are written, zeros included
+ *   capacity            rows per frame, in [1, min(Hs * Ws, IS_GT_TARGETS_MAX_CAPACITY)]; 0 selects min(256, Hs * Ws)
+ *   d_scratch           16-byte aligned, scratch_bytes >= is_offset_loss_scratch_bytes(n_images, planes, rows8, cols8,
+ *                       capacity); its contents mean nothing between calls
+ *   d_key_count         optional, [n_images] int32: the distinct keys of every frame, written also on overflow */
+typedef struct is_offset_loss_args {
+    const float* d_prediction;
+    long long prediction_image_stride;
+    const int32_t* d_ids8;
+    const uint16_t* d_disparity8_u16;
+    int n_images, planes, rows8, cols8;
+    float w_offset_mean, w_offset_variance, w_disparity_mean, w_disparity_variance;
+    int abs_variance;
+    float* d_loss;
+    float* d_terms;
+    float* d_grad;
+    long long grad_image_stride;
+    int capacity;
+    void* d_scratch;
+    size_t scratch_bytes;
+    int32_t* d_key_count;
+} is_offset_loss_args;
+
+/* Bytes of d_scratch for a call of that shape (0 for a shape or capacity the call refuses); capacity 0 as above. */
+size_t is_offset_loss_scratch_bytes(int n_images, int planes, int rows8, int cols8, int capacity);
+/* The losses of n_images frames on `stream`, asynchronously and stream-ordered: one memset and eight launches (nine
+ * with d_grad), no allocation, copy or synchronisation.  IS_EINVAL, with the reason in is_last_error() and before any
+ * device call, for a null required pointer, planes outside {2, 3}, a disparity pointer that does not go with planes,
+ * non-positive shapes, Hs * Ws > 2^28, a stride below planes * Hs * Ws, misaligned pointers, misaligned or undersized
+ * scratch, a capacity out of range and n_images outside [1, 65535]. */
+int is_offset_loss(const is_offset_loss_args* args, void* stream);
+
 /* ---- f9: per-instance objects and their contours (is_k_objects.hip) ------------------------------------------------
  * What the reference's consumers reduce on the host from the per-stixel output: the top-down view
  * (tools/visualization/clustering_visualization.py:563-792: per instance and column the closest stixel, connected

@@ -39,6 +39,7 @@ EXPORTS = [
     "is_compute_sweep", "is_recluster",
     "is_cluster_instance_disparity", "is_instance_disparity_scratch_bytes",
     "is_mode_downsample", "is_gt_targets_scratch_bytes", "is_gt_instance_targets",
+    "is_offset_loss_scratch_bytes", "is_offset_loss",
 ]
 RENDER_MAX_LABELS = 64    # IS_RENDER_MAX_LABELS
 RENDER_MAX_CLASSES = 256  # IS_RENDER_MAX_CLASSES
@@ -165,6 +166,16 @@ class GtTargetsArgs(ctypes.Structure):
                 ("scratch_bytes", ctypes.c_size_t), ("d_key_count", vp)]
 
 
+class OffsetLossArgs(ctypes.Structure):
+    """is_offset_loss_args: zero-initialised by ctypes; device pointers as ints."""
+    vp, ci, cf, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_longlong
+    _fields_ = [("d_prediction", vp), ("prediction_image_stride", ll), ("d_ids8", vp), ("d_disparity8_u16", vp),
+                ("n_images", ci), ("planes", ci), ("rows8", ci), ("cols8", ci), ("w_offset_mean", cf),
+                ("w_offset_variance", cf), ("w_disparity_mean", cf), ("w_disparity_variance", cf),
+                ("abs_variance", ci), ("d_loss", vp), ("d_terms", vp), ("d_grad", vp), ("grad_image_stride", ll),
+                ("capacity", ci), ("d_scratch", vp), ("scratch_bytes", ctypes.c_size_t), ("d_key_count", vp)]
+
+
 class RoadParams(ctypes.Structure):
     """is_road_params: one frame's road, the layout of Stixels::RoadParameters (16 bytes)"""
     _fields_ = [("vhor", ctypes.c_int), ("tilt", ctypes.c_float), ("height", ctypes.c_float),
@@ -250,6 +261,9 @@ def lib():
         L.is_gt_targets_scratch_bytes.argtypes = [ci, ci, ci, ci, ci]
         L.is_gt_targets_scratch_bytes.restype = ctypes.c_size_t
         L.is_gt_instance_targets.argtypes = [ctypes.POINTER(GtTargetsArgs), vp]
+        L.is_offset_loss_scratch_bytes.argtypes = [ci, ci, ci, ci, ci]
+        L.is_offset_loss_scratch_bytes.restype = ctypes.c_size_t
+        L.is_offset_loss.argtypes = [ctypes.POINTER(OffsetLossArgs), vp]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
         L.is_get_device.argtypes = [ctypes.POINTER(ci)]
@@ -864,3 +878,84 @@ def gt_instance_targets(gt_instance, disparity_u16=None, segmentation=None, rows
                 break
             capacity = most   # (never above the cells of a frame; above IS_GT_TARGETS_MAX_CAPACITY it is refused)
     return (out, ids8, count) if return_key_count else (out, ids8)
+
+
+OFFSET_LOSS_WEIGHTS = (1e-3, 1e-4, 1e-3, 1e-4)   # offset_mean, offset_variance, disparity_mean, disparity_variance
+
+
+def offset_loss_scratch_bytes(n_images, planes, rows8, cols8, capacity=0):
+    """is_offset_loss_scratch_bytes: the scratch a call of that shape needs (0: a shape the call refuses)."""
+    return int(lib().is_offset_loss_scratch_bytes(int(n_images), int(planes), int(rows8), int(cols8), int(capacity)))
+
+
+def offset_loss_ptr(stream=0, **fields):
+    """is_offset_loss on raw device pointers (ints): fields are those of OffsetLossArgs.  Asynchronous on `stream`;
+    returns the return code and raises nothing (the tests check IS_EINVAL)."""
+    a = OffsetLossArgs(**fields)
+    return lib().is_offset_loss(ctypes.byref(a), ctypes.c_void_p(int(stream)))
+
+
+def offset_loss(prediction, ids8, disparity8_u16=None, weights=OFFSET_LOSS_WEIGHTS, abs_variance=False, capacity=0,
+                check=True, return_key_count=False):
+    """The reference's OffsetLossSL / DisparityOffsetLossSL of a batch with the gradient (is_offset_loss,
+    instance_stixels_core.h f12).
+
+    prediction       device float32 [n][2 or 3][Hs][Ws]; a channel slice of a wider tensor (outputs[:, -3:]) is read
+                     in place when its planes are contiguous, anything else is copied
+    ids8             device int32 [n][Hs][Ws]: the instance ids mode-downsampled by 8
+    disparity8_u16   device uint16 [n][Hs][Ws] with 3 planes: the raw disparity mode-downsampled by 8
+    weights          (offset_mean, offset_variance, disparity_mean, disparity_variance), rounded to float32
+
+    Returns (loss5, terms, grad): float32 [5] (loss and the four batch sums), [n][4] and the gradient in the
+    prediction's shape, on the inputs' device, enqueued on the current torch stream.  With check=True the key counts
+    are read back (one synchronisation) and a frame with more keys than `capacity` (0: the default of the C ABI) makes
+    the call repeat with that count; with check=False such a batch returns NaN losses and an unwritten gradient."""
+    import torch
+    p = prediction
+    if not p.is_cuda or p.dtype != torch.float32 or p.dim() != 4 or p.shape[1] not in (2, 3):
+        raise CoreError("prediction must be a device float32 tensor [n][2 or 3][Hs][Ws]")
+    dev = p.device
+    n, planes, Hs, Ws = p.shape
+    if p.stride(3) != 1 or p.stride(2) != Ws or p.stride(1) != Hs * Ws or (n > 1 and p.stride(0) < planes * Hs * Ws):
+        p = p.contiguous()
+    p_stride = p.stride(0) if n > 1 else planes * Hs * Ws
+    if ids8.device != dev or ids8.dtype != torch.int32 or tuple(ids8.shape) != (n, Hs, Ws):
+        raise CoreError(f"ids8 must be an int32 tensor {(n, Hs, Ws)} on the prediction's device")
+    i8 = ids8.contiguous()
+    d8 = None
+    if planes == 3:
+        d8 = disparity8_u16
+        if d8 is None or d8.device != dev or d8.dtype != torch.uint16 or tuple(d8.shape) != (n, Hs, Ws):
+            raise CoreError(f"3 planes need disparity8_u16, a uint16 tensor {(n, Hs, Ws)} on the prediction's device")
+        d8 = d8.contiguous()
+    elif disparity8_u16 is not None:
+        raise CoreError("disparity8_u16 goes with 3 planes")
+    w = [float(v) for v in weights]
+    with torch.cuda.device(dev):
+        loss5 = torch.empty((5,), dtype=torch.float32, device=dev)
+        terms = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        grad = torch.empty((n, planes, Hs, Ws), dtype=torch.float32, device=dev)
+        count = torch.empty((n,), dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        while True:
+            nbytes = offset_loss_scratch_bytes(n, planes, Hs, Ws, capacity)
+            if nbytes == 0:
+                raise CoreError("is_offset_loss_scratch_bytes refuses the shape or the capacity "
+                                f"(n_images {n}, planes {planes}, rows8 {Hs}, cols8 {Ws}, capacity {capacity})")
+            scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            a = OffsetLossArgs(d_prediction=p.data_ptr(), prediction_image_stride=p_stride, d_ids8=i8.data_ptr(),
+                               d_disparity8_u16=d8.data_ptr() if d8 is not None else None, n_images=n, planes=planes,
+                               rows8=Hs, cols8=Ws, w_offset_mean=w[0], w_offset_variance=w[1], w_disparity_mean=w[2],
+                               w_disparity_variance=w[3], abs_variance=int(bool(abs_variance)),
+                               d_loss=loss5.data_ptr(), d_terms=terms.data_ptr(), d_grad=grad.data_ptr(),
+                               grad_image_stride=planes * Hs * Ws, capacity=int(capacity),
+                               d_scratch=scratch.data_ptr(), scratch_bytes=nbytes, d_key_count=count.data_ptr())
+            _check(lib().is_offset_loss(ctypes.byref(a), ctypes.c_void_p(stream)), "is_offset_loss")
+            if not check:
+                break
+            most = int(count.max().item())
+            effective = int(capacity) if capacity else min(256, Hs * Ws)
+            if most <= effective:
+                break
+            capacity = most   # (never above the cells of a frame; above IS_GT_TARGETS_MAX_CAPACITY it is refused)
+    return (loss5, terms, grad, count) if return_key_count else (loss5, terms, grad)

@@ -956,6 +956,52 @@ int is_gt_instance_targets(const is_gt_targets_args* a, void* stream) {
     return IS_OK;
 }
 
+/* ---- f12: offset and disparity training losses (is_k_offset_loss.hip) ---- */
+static const char* offset_loss_shape_fault(int n_images, int planes, int rows8, int cols8) {
+    if (n_images < 1 || n_images > 65535) return "n_images outside [1, 65535]";
+    if (planes != 2 && planes != 3) return "planes must be 2 or 3";
+    if (rows8 < 1 || cols8 < 1) return "rows8 and cols8 must be positive";
+    if ((long long)rows8 * cols8 > (1LL << 28)) return "more than 2^28 cells per frame";
+    return nullptr;
+}
+/* as gt_targets_capacity, on the cells themselves */
+static int offset_loss_capacity(int rows8, int cols8, int capacity) {
+    const long long cells = (long long)rows8 * cols8;
+    const int most = (int)(cells < IS_GT_TARGETS_MAX_CAPACITY ? cells : IS_GT_TARGETS_MAX_CAPACITY);
+    if (capacity == 0) return most < 256 ? most : 256;
+    return capacity < 1 || capacity > most ? 0 : capacity;
+}
+
+size_t is_offset_loss_scratch_bytes(int n_images, int planes, int rows8, int cols8, int capacity) {
+    if (offset_loss_shape_fault(n_images, planes, rows8, cols8)) return 0;
+    const int cap = offset_loss_capacity(rows8, cols8, capacity);
+    return cap ? isk_offset_loss_scratch_bytes(n_images, planes, rows8, cols8, cap) : 0;
+}
+
+int is_offset_loss(const is_offset_loss_args* a, void* stream) {
+    if (!a) return fail_arg("null args");
+    if (!a->d_prediction) return fail_arg("null d_prediction");
+    if (!a->d_ids8) return fail_arg("null d_ids8");
+    if (!a->d_loss) return fail_arg("null d_loss");
+    if (const char* fault = offset_loss_shape_fault(a->n_images, a->planes, a->rows8, a->cols8)) return fail_arg(fault);
+    if (a->planes == 3 && !a->d_disparity8_u16) return fail_arg("3 planes need d_disparity8_u16");
+    if (a->planes == 2 && a->d_disparity8_u16) return fail_arg("d_disparity8_u16 must be null with 2 planes");
+    const long long frame = (long long)a->planes * a->rows8 * a->cols8;
+    if (a->prediction_image_stride < frame) return fail_arg("prediction_image_stride below planes * rows8 * cols8");
+    if (a->d_grad && a->grad_image_stride < frame) return fail_arg("grad_image_stride below planes * rows8 * cols8");
+    const int capacity = offset_loss_capacity(a->rows8, a->cols8, a->capacity);
+    if (!capacity) return fail_arg("capacity outside [1, min(rows8 * cols8, IS_GT_TARGETS_MAX_CAPACITY)]");
+    if (!a->d_scratch) return fail_arg("null d_scratch");
+    if (misaligned(16, a->d_scratch)) return fail_arg("d_scratch must be 16-byte aligned");
+    if (misaligned(4, a->d_prediction, a->d_ids8, a->d_loss, a->d_terms, a->d_grad, a->d_key_count))
+        return fail_arg("d_prediction, d_ids8, d_loss, d_terms, d_grad and d_key_count must be 4-byte aligned");
+    if (misaligned(2, a->d_disparity8_u16)) return fail_arg("d_disparity8_u16 must be 2-byte aligned");
+    if (a->scratch_bytes < isk_offset_loss_scratch_bytes(a->n_images, a->planes, a->rows8, a->cols8, capacity))
+        return fail_arg("scratch_bytes below is_offset_loss_scratch_bytes()");
+    HIP_TRY(isk_launch_offset_loss(a, capacity, (hipStream_t)stream));
+    return IS_OK;
+}
+
 /* ---- f9: per-instance objects and contours (is_k_objects.hip) ---- */
 int is_instance_objects(const is_instance_objects_args* a, void* stream) {
     if (!a) return fail_arg("null args");

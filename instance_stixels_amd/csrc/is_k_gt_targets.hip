@@ -31,22 +31,12 @@
 #include <stdint.h>
 
 #include "instance_stixels_core.h"
+#include "is_gt_keys.h"
 #include "is_launch.h"
 
 #define GTT_THREADS 256
 #define GTT_WAVES (GTT_THREADS / 64)
-#define GTT_BINS 256 /* q = uint16 / 256 */
 #define GTT_TILE 64
-
-/* One slot of a frame's table; key 0 = free (a key is > 1000). */
-struct GttEntry {
-    int key;
-    unsigned n;
-    unsigned long long sy, sx;
-    int number; /* the key's number in order of arrival: its histogram */
-    int pad;
-};
-static_assert(sizeof(GttEntry) == 32, "one table slot is 32 bytes");
 
 struct GttScratch {
     int* overflow;     /* [4]: word 0 != 0: a frame has more keys than histograms, no output is written */
@@ -61,12 +51,6 @@ struct GttScratch {
 struct GttLayout {
     size_t overflow, count, table, hist, zero_end, median, ids, disp, total;
 };
-
-static unsigned gtt_log_slots(size_t cells) {
-    unsigned lg = 1; /* 2 * pow2(cells) */
-    while (((size_t)1 << (lg - 1)) < cells) lg++;
-    return lg;
-}
 
 static GttLayout gtt_layout(size_t n, size_t cells, bool disparity, size_t capacity) {
     GttLayout l;
@@ -218,23 +202,6 @@ struct GttArgs {
     int32_t* key_count;
 };
 
-__device__ __forceinline__ unsigned gtt_hash(int key, unsigned log_slots) {
-    return ((unsigned)key * 2654435761u) >> (32 - log_slots);
-}
-
-/* The slot of a key that k_gtt_moments entered (later launches); NULL cannot happen for such a key, the table is
- * never full and the walk ends at a free slot. */
-__device__ __forceinline__ const GttEntry* gtt_find(const GttEntry* table, unsigned log_slots, int key) {
-    const unsigned mask = (1u << log_slots) - 1u;
-    unsigned at = gtt_hash(key, log_slots);
-    for (;;) {
-        const int k = table[at].key;
-        if (k == key) return &table[at];
-        if (k == 0) return nullptr;
-        at = (at + 1) & mask;
-    }
-}
-
 /* The wave's cell of this lane, as k_mode_downsample maps them.  False: no cell. */
 __device__ __forceinline__ bool gtt_cell(const GttArgs& a, long long& w, int& f, int& y, int& x) {
     w = (long long)blockIdx.x * GTT_WAVES + (threadIdx.x >> 6);
@@ -244,15 +211,6 @@ __device__ __forceinline__ bool gtt_cell(const GttArgs& a, long long& w, int& f,
     y = (int)(fy % a.Hs);
     x = (int)(w % a.chunks) * 64 + (int)(threadIdx.x & 63);
     return true;
-}
-
-/* The runs of equal `tag` (0: none) along the wave's lanes: true in the first lane of a run with a tag, `next` the
- * lane behind the run's last. */
-__device__ __forceinline__ bool gtt_run_head(bool differs, bool tagged, int lane, int& next) {
-    const uint64_t starts = __ballot(lane == 0 || differs);
-    const uint64_t above = lane == 63 ? 0 : starts >> (lane + 1);
-    next = above ? lane + 1 + __builtin_ctzll(above) : 64;
-    return tagged && ((starts >> lane) & 1);
 }
 
 __global__ __launch_bounds__(GTT_THREADS) void k_gtt_moments(const GttArgs a) {
@@ -274,19 +232,9 @@ __global__ __launch_bounds__(GTT_THREADS) void k_gtt_moments(const GttArgs a) {
     /* columns x0 + lane .. x0 + next - 1 */
     const unsigned long long sx = len * x0 + (unsigned long long)(lane + next - 1) * len / 2;
     GttEntry* const table = a.s.table + ((size_t)f << a.log_slots);
-    const unsigned mask = (1u << a.log_slots) - 1u;
-    unsigned at = gtt_hash(key, a.log_slots);
-    for (;;) { /* ends: a frame has no more keys than cells, and the table has twice as many slots */
-        const int k = atomicCAS(&table[at].key, 0, key);
-        if (k == 0) {
-            const int number = atomicAdd(&a.s.count[f], 1);
-            table[at].number = number;
-            if (a.disparity && number >= a.capacity) a.s.overflow[0] = 1;
-            break;
-        }
-        if (k == key) break;
-        at = (at + 1) & mask;
-    }
+    int fresh;
+    const unsigned at = gtt_enter(table, a.log_slots, key, &a.s.count[f], fresh);
+    if (a.disparity && fresh >= a.capacity) a.s.overflow[0] = 1;
     atomicAdd(&table[at].n, (unsigned)len);
     atomicAdd(&table[at].sy, len * (unsigned long long)y);
     atomicAdd(&table[at].sx, sx);
@@ -315,28 +263,14 @@ __global__ __launch_bounds__(GTT_THREADS) void k_gtt_hist(const GttArgs a) {
     atomicAdd(&a.s.hist[((size_t)f * a.capacity + e->number) * GTT_BINS + q], (unsigned)(next - lane));
 }
 
-/* One wave per key number: rank (N - 1) / 2 of its histogram, the lower of the middle pair. */
+/* One wave per key number: the lower median of its histogram. */
 __global__ __launch_bounds__(GTT_THREADS) void k_gtt_median(const GttArgs a) {
     if (a.s.overflow[0]) return;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, f = blockIdx.y;
     const int number = blockIdx.x * GTT_WAVES + wave;
     if (number >= min(a.s.count[f], a.capacity)) return; /* (whole waves; the kernel has no workgroup barrier) */
-    const uint4 c = ((const uint4*)(a.s.hist + ((size_t)f * a.capacity + number) * GTT_BINS))[lane];
-    const unsigned sum = c.x + c.y + c.z + c.w; /* (bin 0 is never added to) */
-    unsigned incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned up = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += up;
-    }
-    const unsigned N = __shfl(incl, 63, 64);
-    int median = 0;
-    if (N) {
-        const unsigned r = (N - 1) / 2, excl = incl - sum, rr = r - excl;
-        const bool hit = excl <= r && r < incl;
-        const int bin = 4 * lane + (rr < c.x ? 0 : rr < c.x + c.y ? 1 : rr < c.x + c.y + c.z ? 2 : 3);
-        median = __shfl(bin, __builtin_ctzll(__ballot(hit)), 64);
-    }
+    unsigned N;
+    const int median = gtt_lower_median(a.s.hist + ((size_t)f * a.capacity + number) * GTT_BINS, lane, N);
     if (lane == 0) a.s.median[(size_t)f * a.capacity + number] = median;
 }
 

@@ -242,6 +242,10 @@ hipError_t isk_launch_mode_downsample(const void* src, int dtype, int n, int Hs,
 size_t isk_gt_targets_scratch_bytes(int n_images, int Hs, int Ws, int disparity, int capacity);
 hipError_t isk_launch_gt_targets(const is_gt_targets_args* r, int capacity, hipStream_t stream);
 
+/* is_k_offset_loss.hip */
+size_t isk_offset_loss_scratch_bytes(int n_images, int planes, int Hs, int Ws, int capacity);
+hipError_t isk_launch_offset_loss(const is_offset_loss_args* r, int capacity, hipStream_t stream);
+
 /* is_k_objects.hip */
 hipError_t isk_launch_instance_objects(const is_instance_objects_args* r, hipStream_t stream);
 
