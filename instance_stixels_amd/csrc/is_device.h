@@ -27,10 +27,9 @@
  * a separable summary every IS_QB candidate rows.  A bound loses up to one block of accumulated path
  * cost, so smaller blocks close a type sooner but cost more block tops per tile (64: the tile, round
  * 3; 32 measured best in round 4).  Block j >= 1 = the candidate rows IS_QB (j - 1) + 1 .. IS_QB j,
- * block 0 = the first segment vB = 0. */
-#ifndef IS_QB_LOG
+ * block 0 = the first segment vB = 0.  Not a knob: the summaries are reduced over groups of 32 lanes
+ * with DPP / permlane instructions (l78_store32, is_k_pairwise.hip). */
 #define IS_QB_LOG 5
-#endif
 #define IS_QB (1 << IS_QB_LOG)
 #define IS_QPT (IS_TILE / IS_QB) /* bound blocks per tile */
 #define IS_PW_MAX_SPLIT 4            /* phase-1 workgroups per (column, tile) at small batches */

@@ -18,7 +18,7 @@ struct __attribute__((aligned(64))) StepRec {
     float p2_hi, p2_lo, p2_mid; /* cO + pw * GetPriorCostObjectFromObject, three cases :146-171 */
     float p3_yes, p3_no;        /* cS + pw * GetPriorCostObjectFromSky, fn > eps or not :173-183 */
     /* branch-and-bound (DESIGN.md "Pruning"): running minima over the rows vB' <= vB of the SAME
-     * 64-row block (= the StepRecs one phase-2 launch builds) of what a segment starting at vB'
+     * bound block (IS_QB rows, half of the StepRecs one phase-2 launch builds) of what a segment starting at vB'
      * adds before its own data / semantic terms: q_o = pw * (smallest of the eight p fields),
      * q_gs = pwmp */
     float q_o, q_gs;
@@ -33,12 +33,45 @@ struct StepVals { /* register copy of a StepRec, always passed by value */
         p3_no, q_o, q_gs;
 };
 
+/* StepVals <-> the sixteen dwords of a StepRec: the one place besides the two structs that knows the field order */
+__device__ __forceinline__ void step_pack(const StepVals& v, float4 (&q)[4]) {
+    q[0] = make_float4(v.pwmp, __builtin_bit_cast(float, v.idx_gs), v.g_hi_thr, v.g_lo_thr);
+    q[1] = make_float4(v.p1_hi, v.p1_lo, v.p1_mid, v.o_hi_thr);
+    q[2] = make_float4(v.o_lo_thr, v.p2_hi, v.p2_lo, v.p2_mid);
+    q[3] = make_float4(v.p3_yes, v.p3_no, v.q_o, v.q_gs);
+}
+__device__ __forceinline__ StepVals step_unpack(const float4 (&q)[4]) {
+    StepVals v;
+    v.pwmp = q[0].x; v.idx_gs = __builtin_bit_cast(int, q[0].y); v.g_hi_thr = q[0].z; v.g_lo_thr = q[0].w;
+    v.p1_hi = q[1].x; v.p1_lo = q[1].y; v.p1_mid = q[1].z; v.o_hi_thr = q[1].w;
+    v.o_lo_thr = q[2].x; v.p2_hi = q[2].y; v.p2_lo = q[2].z; v.p2_mid = q[2].w;
+    v.p3_yes = q[3].x; v.p3_no = q[3].y; v.q_o = q[3].z; v.q_gs = q[3].w;
+    return v;
+}
+/* to / from a StepRec in global memory, four dwordx4 per lane (the scalar way in: sload_step) */
 __device__ __forceinline__ void store_step(StepRec* dst, const StepVals v) {
+    float4 q[4];
+    step_pack(v, q);
     float4* d = reinterpret_cast<float4*>(dst);
-    d[0] = make_float4(v.pwmp, __builtin_bit_cast(float, v.idx_gs), v.g_hi_thr, v.g_lo_thr);
-    d[1] = make_float4(v.p1_hi, v.p1_lo, v.p1_mid, v.o_hi_thr);
-    d[2] = make_float4(v.o_lo_thr, v.p2_hi, v.p2_lo, v.p2_mid);
-    d[3] = make_float4(v.p3_yes, v.p3_no, v.q_o, v.q_gs);
+    d[0] = q[0]; d[1] = q[1]; d[2] = q[2]; d[3] = q[3];
+}
+__device__ __forceinline__ StepVals vload_step(const StepRec* src) {
+    const float4* s = reinterpret_cast<const float4*>(src);
+    const float4 q[4] = {s[0], s[1], s[2], s[3]};
+    return step_unpack(q);
+}
+/* to / from sixteen floats that are not 16-byte aligned (the LDS hand-over of k_pw_phase2x) */
+__device__ __forceinline__ void store_step_f(float* d, const StepVals v) {
+    float4 q[4];
+    step_pack(v, q);
+#pragma unroll
+    for (int k = 0; k < 4; k++) { d[4 * k] = q[k].x; d[4 * k + 1] = q[k].y; d[4 * k + 2] = q[k].z; d[4 * k + 3] = q[k].w; }
+}
+__device__ __forceinline__ StepVals load_step_f(const float* d) {
+    float4 q[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) q[k] = make_float4(d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3]);
+    return step_unpack(q);
 }
 
 /* A scalar-loaded value made opaque to the optimiser: without this, LLVM rewrites the selects
@@ -238,9 +271,9 @@ struct PairBest {
  * rounding of the subtraction below, the rest covers mu^ >= (1 - u)^4 mu),
  *     alo_c = fl(a^_c - slack(mu^_c)) <= a_c - 10.02 u mu_c,   ahi_c = fl(a^_c + slack(mu^_c)) >= a_c + 10.02 u mu_c
  * and likewise blo_c / bhi_c:   min_c (alo_c(vB) + blo_c(vT)) <= C(vB, vT) <= ahi_c(vB) + bhi_c(vT) for EVERY c.
- * Phase 2 leaves, per 64-row block of candidates (= the rows whose StepRecs one launch builds) and
- * class, the minima of alo_c and ahi_c over the block's rows of the type (l7_row_bounds + a wave
- * minimum; rows of the other type, rows beyond the image and NaN / +inf rows -- whose candidates
+ * Phase 2 leaves, per bound block of IS_QB candidate rows (two blocks per launch: a launch builds the
+ * StepRecs of a tile) and class, the minima of alo_c and ahi_c over the block's rows of the type
+ * (l7_row_bounds + a minimum over the block's 32 lanes; rows of the other type, rows beyond the image and NaN / +inf rows -- whose candidates
  * cost NaN / +inf and never win -- count as +inf).  Phase 1 turns them into a lower bound of every
  * candidate of the block and an upper bound of the block's best one per lane (pw_phase1_body). */
 #define IS_L7_REL 0x1p-20f
@@ -268,20 +301,6 @@ __device__ __forceinline__ L7Row l7_row_bounds(const DevParams& P, float T, floa
     r.lo_g0 = g ? r.lo_g0 : IS_INF; r.hi_g0 = g ? r.hi_g0 : IS_INF;
     r.lo_g1 = g ? r.lo_g1 : IS_INF; r.hi_g1 = g ? r.hi_g1 : IS_INF;
     r.lo_s = s ? r.lo_s : IS_INF;   r.hi_s = s ? r.hi_s : IS_INF;
-    return r;
-}
-/* minimum over a group of 2^LOG lanes (NaN-skipping), every lane gets it */
-template <int LOG>
-__device__ __forceinline__ float l7_group_min(float x) {
-    x = __builtin_fminf(x, IS_INF); /* a NaN becomes +inf */
-#pragma unroll
-    for (int m = (1 << LOG) >> 1; m >= 1; m >>= 1) x = __builtin_fminf(x, __shfl_xor(x, m, 64));
-    return x;
-}
-template <int LOG>
-__device__ __forceinline__ L7Row l7_group_min_row(L7Row r) {
-    r.lo_g0 = l7_group_min<LOG>(r.lo_g0); r.lo_g1 = l7_group_min<LOG>(r.lo_g1); r.lo_s = l7_group_min<LOG>(r.lo_s);
-    r.hi_g0 = l7_group_min<LOG>(r.hi_g0); r.hi_g1 = l7_group_min<LOG>(r.hi_g1); r.hi_s = l7_group_min<LOG>(r.hi_s);
     return r;
 }
 __device__ __forceinline__ void l7_store(float* dst /* 8 floats, 32-byte aligned */, const L7Row& r) {
@@ -314,71 +333,14 @@ __device__ __forceinline__ L7Row l7_never() {
  * best cost (s_lb).  Where round 3 evaluated the block's TOP row (the smallest transition term of the
  * block + the smallest semantic term of the block: a chain of short objects, every split near-optimal,
  * lost a whole block of accumulated path cost), the per-class form loses nothing but the instance term. */
-/* Per lane the sixteen alo_c of its candidate row (record `rec`, T8 = pw * m8 of its StepRec; `ok`: the row
- * is a candidate, 1 <= vB <= H - 1), then the minima over a group of 2^LOG lanes (LOG = 4 or 5) as a
- * reduce-scatter, eight classes at a time (the kernels that call this have no registers to spare):
- * every exchange halves the classes a lane is responsible for, 4 + 2 + 1 shuffles + the full-minimum
- * steps of the remaining strides instead of eight full butterflies; the lanes that end up with a class
- * store it.  dst: the group's 16 floats. */
-template <int LOG>
-__device__ __forceinline__ void l8_group_min_store(const DevParams& P, float T8, const RowRec* rec /* global */,
-                                                   bool ok, float* dst) {
-    static_assert(LOG == 4 || LOG == 5, "groups of 16 or 32 lanes");
-    const int lane = threadIdx.x;
-    /* the class prefixes are RE-READ from the record in memory (an L2 hit), eight at a time: the lane's
-     * register copy would have to stay alive across the whole walk of the calling kernel, which has no
-     * registers to spare (k_pw_phase2x: 124 of 128) */
-    asm volatile("" ::: "memory");
-    const float4* r4 = reinterpret_cast<const float4*>(rec);
-    const float n = P.iw * (float)__float_as_int(r4[4].w); /* Fnic, dword 19 */
-#pragma unroll
-    for (int bq = 0; bq < 2; bq++) { /* the non-instance classes 2..9, then the instance classes 11..18 */
-        float f[8];
-        if (bq == 0) { /* Fon[0..7] = dwords 2..9 */
-            const float4 a = r4[0], b = r4[1], c = r4[2];
-            f[0] = a.z; f[1] = a.w; f[2] = b.x; f[3] = b.y; f[4] = b.z; f[5] = b.w; f[6] = c.x; f[7] = c.y;
-        } else { /* Foi[0..7] = dwords 10..17 */
-            const float4 a = r4[2], b = r4[3], c = r4[4];
-            f[0] = a.z; f[1] = a.w; f[2] = b.x; f[3] = b.y; f[4] = b.z; f[5] = b.w; f[6] = c.x; f[7] = c.y;
-        }
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const float ft = P.sw * (bq == 0 ? f[j] + n : f[j]);
-            const float a = T8 - ft;
-            const float mu = __builtin_fabsf(T8) + ft;
-            const float lo = a - (mu * IS_L7_REL + IS_L7_ABS);
-            /* (a NaN bound -- NaN / infinite T8: the candidates cost NaN / +inf -- counts as +inf) */
-            v[j] = ok ? __builtin_fminf(lo, IS_INF) : IS_INF;
-        }
-        int base = 0;
-#pragma unroll
-        for (int step = 0; step < 3; step++) { /* 8 -> 4 -> 2 -> 1 classes per lane */
-            const int m = 1 << (LOG - 1 - step);
-            const int half = 4 >> step;
-            const bool up = (lane & m) != 0;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                if (j < half) {
-                    const float send = up ? v[j] : v[j + half];
-                    const float keep = up ? v[j + half] : v[j];
-                    v[j] = __builtin_fminf(keep, __shfl_xor(send, m, 64));
-                }
-            }
-            base += up ? half : 0;
-        }
-#pragma unroll
-        for (int m = 1 << (LOG - 4); m >= 1; m >>= 1) v[0] = __builtin_fminf(v[0], __shfl_xor(v[0], m, 64));
-        if ((lane & ((1 << (LOG - 3)) - 1)) == 0) dst[bq * 8 + base] = v[0];
-    }
-}
-/* ---- the same minima on the DPP / permlane path (groups of 32 lanes) ------------------------------
- * __shfl_xor is a ds_bpermute (LDS crossbar, an address VGPR, an lgkmcnt wait) and __builtin_fminf
- * re-quiets a value that went through a bitcast (v_max x, x): 3 instructions and a round trip per
- * exchange.  Here an exchange is v_permlane16_swap (distance 16: the rows of TWO values swapped by one
- * instruction, so that one minimum reduces both -- each lands in its own row parity) or a v_mov_b32_dpp
- * (row_ror / quad_perm, bank-masked where the two halves of a pair go different ways) + a bare v_min_f32.
- * The results are the minima of the same numbers: bit-identical to the shuffle version. */
+/* ---- the block minima of lemmas L7 / L8 over groups of 32 lanes, on the DPP / permlane path ---------
+ * An exchange is v_permlane16_swap (distance 16: the rows of TWO values swapped by one instruction, so
+ * that one minimum reduces both -- each lands in its own row parity) or a v_mov_b32_dpp (row_ror /
+ * quad_perm, bank-masked where the two halves of a pair go different ways) + a bare v_min_f32: no LDS
+ * crossbar, no address VGPR, no lgkmcnt wait and no re-quieting v_max as with __shfl_xor + fminf.  The
+ * sixteen classes of L8 go through a reduce-scatter (every exchange halves the classes a lane is
+ * responsible for; the lanes that end up with a class store it).  The group is 32 lanes = IS_QB rows. */
+static_assert(IS_QB == 32, "pair_min32 / scatter_min32x16 reduce over groups of 32 lanes, one lane per row of a bound block");
 template <int CTRL, int BANK = 0xf>
 __device__ __forceinline__ float dpp_mov(float old, float src) {
     return __uint_as_float(__builtin_amdgcn_update_dpp(__float_as_uint(old), __float_as_uint(src), CTRL, 0xf, BANK, false));
@@ -426,7 +388,8 @@ __device__ __forceinline__ float scatter_min32x16(const float (&v)[16], int lane
     float z = min_raw(keep, dpp_mov<IS_DPP_XOR2>(send, send));
     return min_raw(z, dpp_mov<IS_DPP_XOR1>(z, z));
 }
-/* l7_row_bounds + l7_group_min_row + l7_store and l8_group_min_store for groups of 32 lanes */
+/* One bound block = one group of 32 lanes, a lane per candidate row: l7_row_bounds and the sixteen alo_c of lemma L8
+ * (T8 = pw * m8 of the row's StepRec), their minima over the group, the 24 floats of the block's summary to `slot` */
 __device__ __forceinline__ void l78_store32(const DevParams& P, float T, float T8, const RowRec* rec /* global */,
                                             bool ground_row, bool ok, float* slot, int lane) {
     const float4* r4 = reinterpret_cast<const float4*>(rec);
@@ -453,35 +416,6 @@ __device__ __forceinline__ void l78_store32(const DevParams& P, float T, float T
     if ((lane & 1) == 0) slot[8 + ((lane & 31) >> 1)] = z;
 }
 
-/* The summaries (lemmas L7, L8) of the bound blocks of the candidate rows vB = tile_lo + base + g + 1, g = this
- * lane's index in its group of 2^LOG lanes (one lane per row, one group per block).  Called at the END of
- * a phase-2 walk, when nothing else is alive: the per-row transition terms -- pwmp = StepRec field 0 and
- * T8 = pw * m8 from the side array t8col -- are read back from memory (this wave stored them during
- * the walk; the caller has waited for its stores), the record fields from the record. */
-template <int LOG>
-__device__ __forceinline__ void l78_block_summaries(const DevParams& P, const RowRec* rcol, const StepRec* scol,
-                                                    const float* t8col, float* bsum_col /* the column's summaries */,
-                                                    int tile_lo, int row /* of the tile: base + g */, int vhor) {
-    const int H = P.H;
-    const int vB = tile_lo + row + 1;
-    const bool ok = vB < H;
-    const int vBc = min(vB, H - 1);
-    const float T = ((const float*)(scol + vBc))[0];
-    const float T8 = t8col[vBc];
-    const RowRec* rec = rcol + vBc;
-    float* const slot = bsum_col + (size_t)(((tile_lo >> 6) * IS_QPT) + (row >> IS_QB_LOG) + 1) * IS_L7_F;
-    if (LOG == 5) {
-        l78_store32(P, T, T8, rec, vB - 1 < vhor, ok, slot, (int)(threadIdx.x & 63));
-        return;
-    }
-    const float4* r4 = reinterpret_cast<const float4*>(rec);
-    const float4 c0 = r4[0], c4 = r4[4];      /* Fg0 Fg1 . . | Foi6 Foi7 Fsky Fnic */
-    const float2 gk = *reinterpret_cast<const float2*>((const float*)rec + 20); /* G K */
-    L7Row sum = l7_row_bounds(P, T, gk.x, gk.y, c0.x, c0.y, c4.z, __float_as_int(c4.w), vB - 1 < vhor, ok);
-    sum = l7_group_min_row<LOG>(sum);
-    if ((threadIdx.x & ((1 << LOG) - 1)) == 0) l7_store(slot, sum);
-    l8_group_min_store<LOG>(P, T8, rec, ok, slot + 8);
-}
 /* (generic columns: never a bound) */
 __device__ __forceinline__ void l8_store_never(float* dst, bool writer) {
     if (writer) {
@@ -506,7 +440,6 @@ __device__ __forceinline__ void l8_store_never(float* dst, bool writer) {
  * 8 instance-prefix dwords of the record at its top row */
 #define IS_P1_SUM_F (IS_L7_F + 8)
 #define IS_P1_BLK_WORDS (64 + IS_P1_SUM_F)
-static_assert(IS_QB_LOG >= 3 && IS_QB_LOG <= 5, "bound blocks: 8 .. 32 rows (a phase of k_pw_phase2x holds 32 rows)");
 struct L7B { float lo_g0, lo_g1, lo_s, hi_g0, hi_g1, hi_s; };
 __device__ __forceinline__ void l7_b(float dterm, float fterm, float* lo, float* hi) {
     const float b = dterm + fterm;
@@ -1371,6 +1304,176 @@ __device__ __forceinline__ float wave_max_f(float x) {
     return x;
 }
 
+/* ---- what the three phase-2 walks share ------------------------------------------------------
+ * pw_phase2_body (a wave per column), pw_phase2x_body (two columns per wave) and pw_phase2s_body (a
+ * chain wave + evaluator waves) differ in who holds a row and how a finished row is broadcast.  The
+ * pieces below are the same in all of them and exist here only. */
+
+/* The fn window [*lo, *lo + *W) of lutT columns, W <= WMAX, from the smallest / largest valid disparity
+ * of the tile's rows (+inf / -inf where there is none).  Any junk (NaN, no valid row, values outside
+ * [0, D)) still yields a window inside the table; lanes that leave it take the global path. */
+template <int WMAX>
+__device__ __forceinline__ void p2_window(float dmin, float dmax, int D, int* lo, int* W) {
+    int l = (int)__builtin_fminf(__builtin_fmaxf(dmin, 1.0f), (float)D) - 1;
+    l = min(max(l, 0), D - 1);
+    int h = (int)__builtin_fminf(__builtin_fmaxf(dmax, 0.0f), (float)(D - 1)) + 1;
+    h = min(max(h, l), min(D - 1, l + WMAX - 1));
+    *lo = l;
+    *W = h - l + 1;
+}
+
+/* The window rows tile_lo .. tile_lo + 64 (vB side: row r, vT side: row vT + 1; clamped to row H) x the
+ * window columns of one column into s_win, by the NT threads of a workgroup.  A wave instruction covers
+ * 64 / Wp rows of Wp = 2^k >= W columns; every load is issued before the first LDS store (fully
+ * unrolled: one memory round trip for the whole window). */
+template <int NT>
+__device__ __forceinline__ void p2_stage_window(float* s_win, const float* __restrict__ lcol, int tile_lo, int H,
+                                                int D, int lo, int W, int tid) {
+    int lg = 0;
+    while ((1 << lg) < W) lg++;
+    lg = __builtin_amdgcn_readfirstlane(lg);
+    const int f = tid & ((1 << lg) - 1);
+    const int j0 = tid >> lg, dj = NT >> lg;
+    constexpr int NL = (ISP2_ROWS * ISP2_WMAX + NT - 1) / NT; /* loads per thread at the widest window */
+    float tmp[NL];
+#pragma unroll
+    for (int k = 0; k < NL; k++) {
+        const int j = j0 + k * dj;
+        tmp[k] = (j < ISP2_ROWS && f < W) ? lcol[(size_t)min(tile_lo + j, H) * D + lo + f] : 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < NL; k++) {
+        const int j = j0 + k * dj;
+        if (j < ISP2_ROWS && f < W) s_win[j * ISP2_WS + f] = tmp[k];
+    }
+}
+
+/* the logarithm tables, object_disparity_range and RN(1 / h), h <= 64, into LDS by NT threads */
+template <int NT>
+__device__ __forceinline__ void p2_stage_tables(double* s_invc, double* s_logc, float* s_odr, float* s_rcp,
+                                                const float* __restrict__ odr, const float* __restrict__ rcp,
+                                                int D, int H, int tid) {
+    if (tid == 0) is_log_tables(s_invc, s_logc);
+    for (int i = tid; i < D; i += NT) s_odr[i] = odr[i];
+    for (int i = tid; i <= IS_TILE; i += NT) s_rcp[i] = rcp[min(i, H)];
+}
+
+/* The partial minima of phase 1 of one row (o: the row's slot of the first of the column's nsplit
+ * workgroups), merged.  The tie rule is that of the wave merge of phase 1: min cost, then the smallest
+ * vB; two +inf costs do not tie (`c2 < IS_INF`), so a row without a finite candidate keeps the initial
+ * index the first workgroup left there. */
+__device__ __forceinline__ void p2_load_best(const float* __restrict__ part_cost, const int* __restrict__ part_idx,
+                                             size_t o, int nsplit, PairBest& b) {
+    b.g = part_cost[o]; b.ig = part_idx[o];
+    b.o = part_cost[o + 64]; b.io = part_idx[o + 64];
+    b.s = part_cost[o + 128]; b.is = part_idx[o + 128];
+    for (int sp = 1; sp < nsplit; sp++) {
+        const size_t q = o + (size_t)sp * 3 * 64;
+        float c2 = part_cost[q]; int i2 = part_idx[q];
+        if ((c2 < b.g) || (c2 == b.g && c2 < IS_INF && (i2 / 3) < (b.ig / 3))) { b.g = c2; b.ig = i2; }
+        c2 = part_cost[q + 64]; i2 = part_idx[q + 64];
+        if ((c2 < b.o) || (c2 == b.o && c2 < IS_INF && (i2 / 3) < (b.io / 3))) { b.o = c2; b.io = i2; }
+        c2 = part_cost[q + 128]; i2 = part_idx[q + 128];
+        if ((c2 < b.s) || (c2 == b.s && c2 < IS_INF && (i2 / 3) < (b.is / 3))) { b.s = c2; b.is = i2; }
+    }
+}
+
+/* a lane's final row vT into the tables (rows beyond the image: nothing) */
+__device__ __forceinline__ void p2_store_row(float* __restrict__ cost_table, int32_t* __restrict__ index_table,
+                                             int colg, int H, int vT, const PairBest& b) {
+    if (vT < H) {
+        const size_t o = ((size_t)colg * H + vT) * 3;
+        cost_table[o + 0] = b.g; cost_table[o + 1] = b.o; cost_table[o + 2] = b.s;
+        index_table[o + 0] = b.ig; index_table[o + 1] = b.io; index_table[o + 2] = b.is;
+    }
+}
+
+/* The StepVals a tile starts with (step 0 has no candidates; nothing reads the zeros), its running
+ * minima q_o / q_gs at +inf.  The minima of the transition terms run over the rows of ONE bound block:
+ * phase 1 bounds block by block (see pw_phase1_body, P2_ROW_FINAL). */
+__device__ __forceinline__ StepVals p2_step_zero() {
+    StepVals st;
+    st.pwmp = IS_INF; st.idx_gs = -1;
+    st.g_hi_thr = st.g_lo_thr = st.p1_hi = st.p1_lo = st.p1_mid = st.o_hi_thr = st.o_lo_thr = 0.0f;
+    st.p2_hi = st.p2_lo = st.p2_mid = st.p3_yes = st.p3_no = 0.0f;
+    st.q_o = st.q_gs = IS_INF;
+    return st;
+}
+
+/* od = the object data term lutT[vT + 1][fn] - lutT[r][fn] of a candidate (r, vT): from the window
+ * in LDS (my_win: the lane's row vT + 1, vb_win: row r) where fn = fni lies inside [lo, lo + W), from
+ * global memory (my_row: row vT + 1 of lcol) where not.  Only the lanes outside fetch: with every lane
+ * gathering, a step of this kind pulled up to 128 lines -- 16 KB -- for the few values it needed.
+ * Reads lo, W, lcol and D of the walk.  (This and P2_ROW_FINAL are macros for a measured reason: as
+ * inlined functions they cost k_pw_phase2, which sits on the edge of its 80 registers, 0.9 % of a
+ * 64-frame step -- the allocator moves when a block of the loop becomes a function) */
+#define P2_OBJECT_DATA(od, my_win, vb_win, my_row, r, fni, live)                                        \
+    do {                                                                                                \
+        const int fo_ = (fni) - lo;                                                                     \
+        const bool inwin_ = (unsigned)fo_ < (unsigned)W;                                                \
+        const int foc_ = inwin_ ? fo_ : 0;                                                              \
+        od = (my_win)[foc_] - (vb_win)[foc_];                                                           \
+        if (__builtin_amdgcn_ballot_w64((live) && !inwin_) != 0ull) { /* outside the window: rare */    \
+            if ((live) && !inwin_) {                                                                    \
+                const float og_ = (my_row)[(unsigned)(fni)] - (lcol + (size_t)(r) * D)[(unsigned)(fni)]; \
+                od = inwin_ ? od : og_;                                                                 \
+            }                                                                                           \
+        }                                                                                               \
+    } while (0)
+
+/* Row r = tile_lo + s is final and `st` = make_step(...) is the StepRec of vB = r + 1: the running
+ * minima of its bound block into st.q_o / st.q_gs, then StepRec and T8 (lemma L8: the row's own
+ * transition bound) to memory through the lane(s) `writer`.  The walks assign `st` for EVERY row, the
+ * last row of the image included, whose StepRec nobody reads: an unconditional assignment keeps `st`
+ * in place -- a guarded one costs 16 register moves per step; only the stores are guarded.
+ * Reads P, H, scol, t8row and colg of the walk, updates its st, q_o and q_gs. */
+#define P2_ROW_FINAL(s, r, writer)                                                                      \
+    do {                                                                                                \
+        /* fminf skips NaN fields: a candidate that selects one costs NaN and never wins */             \
+        const float m8_ = min_raw(min3_raw(st.p1_hi, st.p1_lo, st.p1_mid),                              \
+                                  min3_raw(min3_raw(st.p2_hi, st.p2_lo, st.p2_mid), st.p3_yes, st.p3_no)); \
+        if (((s) & (IS_QB - 1)) == 0) q_o = q_gs = IS_INF; /* vB = r + 1 starts a bound block */        \
+        const float pwm8_ = P.pw * m8_;                                                                 \
+        q_o = min_raw(q_o, pwm8_);                                                                      \
+        q_gs = min_raw(q_gs, st.pwmp);                                                                  \
+        st.q_o = q_o; st.q_gs = q_gs;                                                                   \
+        if ((writer) && (r) + 1 < H) {                                                                  \
+            store_step(scol + (r) + 1, st);                                                             \
+            t8row[(size_t)colg * H + (r) + 1] = pwm8_;                                                  \
+        }                                                                                               \
+    } while (0)
+
+/* The summaries (lemmas L7, L8) of the bound blocks of the candidate rows vB = tile_lo + 1 .. tile_lo + rows, at the
+ * very END of a walk, when nothing of it is alive any more (computed inside the walk they cost it registers it does
+ * not have).  One lane per row, one group of IS_QB lanes per block: `row` is this lane's row of the first sweep,
+ * `sweep` the rows the wave covers at once (64: one column per wave, 32: two).  The per-row transition terms -- pwmp =
+ * StepRec field 0 and T8 = pw * m8 from the side array t8row -- are read back from memory (this wave stored them
+ * during the walk), the record fields from the record.  Generic columns (one per wave) get summaries that never
+ * bound; phase 1 ignores the summaries of a column whose pruning is off anyway. */
+template <bool FAST>
+__device__ __forceinline__ void p2_block_summaries(const DevParams& P, const RowRec* rcol, const StepRec* scol,
+                                                   const float* __restrict__ t8row, float* __restrict__ blksum,
+                                                   int colg, int tile_lo, int row, int sweep, int rows, int vhor) {
+    const int H = P.H;
+    float* const slot0 = blksum + ((size_t)colg * (P.ntiles * IS_QPT + 1) + (tile_lo >> 6) * IS_QPT + 1) * IS_L7_F;
+    if (FAST) {
+        __builtin_amdgcn_s_waitcnt(0); /* this wave's StepRec / T8 stores have reached the L2 */
+        for (int rw = row; rw < rows; rw += sweep) { /* (row < sweep, sweep divides rows: every lane takes every trip) */
+            const int vB = tile_lo + rw + 1;
+            const int vBc = min(vB, H - 1); /* (rows beyond the image: not candidates, `ok`) */
+            const float T = ((const float*)(scol + vBc))[0];
+            const float T8 = t8row[(size_t)colg * H + vBc];
+            l78_store32(P, T, T8, rcol + vBc, vB - 1 < vhor, vB < H, slot0 + (size_t)(rw >> IS_QB_LOG) * IS_L7_F,
+                        (int)(threadIdx.x & 63));
+        }
+    } else {
+        float* const slot = slot0 + (size_t)(row >> IS_QB_LOG) * IS_L7_F;
+        const bool writer = (row & (IS_QB - 1)) == 0;
+        if (writer) l7_store(slot, l7_never());
+        l8_store_never(slot + 8, writer);
+    }
+}
+
 template <bool FAST, bool HAS_INVALID>
 __device__ __forceinline__ void pw_phase2_body(const DevParams& P, char* smem, int colg, int tile,
                                                const RowRec* __restrict__ recs,
@@ -1409,70 +1512,22 @@ __device__ __forceinline__ void pw_phase2_body(const DevParams& P, char* smem, i
         const bool ok = (vT < H) && !(HAS_INVALID && d == P.invalid);
         const float dmin = wave_min_f(ok ? d : IS_INF);
         const float dmax = wave_max_f(ok ? d : -IS_INF);
-        /* any junk (NaN, no valid row, values outside [0, D)) still yields a window inside the
-         * table; lanes that leave it take the global path */
-        int l = (int)__builtin_fminf(__builtin_fmaxf(dmin, 1.0f), (float)D) - 1;
-        l = min(max(l, 0), D - 1);
-        int h = (int)__builtin_fminf(__builtin_fmaxf(dmax, 0.0f), (float)(D - 1)) + 1;
-        h = min(max(h, l), min(D - 1, l + ISP2_WMAX - 1));
-        lo = __builtin_amdgcn_readfirstlane(l);
-        W = __builtin_amdgcn_readfirstlane(h - l + 1);
+        p2_window<ISP2_WMAX>(dmin, dmax, D, &lo, &W);
+        lo = __builtin_amdgcn_readfirstlane(lo);
+        W = __builtin_amdgcn_readfirstlane(W);
     }
-    /* rows tile_lo .. tile_lo + 64 (vB side: row r, vT side: row vT + 1) x window columns.  A
-     * wave instruction covers 64 / Wp rows of Wp = 2^k >= W columns; every load is issued before
-     * the first LDS store (fully unrolled: one memory round trip for the whole window). */
-    {
-        int lg = 0;
-        while ((1 << lg) < W) lg++;
-        lg = __builtin_amdgcn_readfirstlane(lg);
-        const int f = lane & ((1 << lg) - 1);
-        const int j0 = lane >> lg, dj = 64 >> lg;
-        constexpr int NL = (ISP2_ROWS * ISP2_WMAX + 63) / 64; /* loads per lane at the widest window */
-        float tmp[NL];
-#pragma unroll
-        for (int k = 0; k < NL; k++) {
-            const int j = j0 + k * dj;
-            tmp[k] = (j < ISP2_ROWS && f < W) ? lcol[(size_t)min(tile_lo + j, H) * D + lo + f] : 0.0f;
-        }
-#pragma unroll
-        for (int k = 0; k < NL; k++) {
-            const int j = j0 + k * dj;
-            if (j < ISP2_ROWS && f < W) s_win[j * ISP2_WS + f] = tmp[k];
-        }
-    }
-    if (lane == 0) is_log_tables(s_invc, s_logc);
-    for (int i = lane; i < D; i += 64) s_odr[i] = odr[i];
-    for (int i = lane; i <= IS_TILE; i += 64) s_rcp[i] = rcp[min(i, H)];
+    p2_stage_window<64>(s_win, lcol, tile_lo, H, D, lo, W, lane);
+    p2_stage_tables<64>(s_invc, s_logc, s_odr, s_rcp, odr, rcp, D, H, lane);
     const RowRec my = load_rec(rcol + vTc + 1);
     const float* my_row = lcol + (size_t)(vTc + 1) * D;
     const float* my_win = s_win + (vTc + 1 - tile_lo) * ISP2_WS;
-    PairBest b; /* partial minima of phase 1 (its nsplit workgroups merged: min cost, then smallest vB) */
-    {
-        const size_t o = (size_t)colg * nsplit * 3 * 64 + lane;
-        b.g = part_cost[o]; b.ig = part_idx[o];
-        b.o = part_cost[o + 64]; b.io = part_idx[o + 64];
-        b.s = part_cost[o + 128]; b.is = part_idx[o + 128];
-        for (int sp = 1; sp < nsplit; sp++) {
-            const size_t q = o + (size_t)sp * 3 * 64;
-            float c2 = part_cost[q]; int i2 = part_idx[q];
-            if ((c2 < b.g) || (c2 == b.g && c2 < IS_INF && (i2 / 3) < (b.ig / 3))) { b.g = c2; b.ig = i2; }
-            c2 = part_cost[q + 64]; i2 = part_idx[q + 64];
-            if ((c2 < b.o) || (c2 == b.o && c2 < IS_INF && (i2 / 3) < (b.io / 3))) { b.o = c2; b.io = i2; }
-            c2 = part_cost[q + 128]; i2 = part_idx[q + 128];
-            if ((c2 < b.s) || (c2 == b.s && c2 < IS_INF && (i2 / 3) < (b.is / 3))) { b.s = c2; b.is = i2; }
-        }
-    }
+    PairBest b;
+    p2_load_best(part_cost, part_idx, (size_t)colg * nsplit * 3 * 64 + lane, nsplit, b);
     __syncthreads();
 
     const int n_rows = min(IS_TILE, H - tile_lo);
-    StepVals st;
-    st.pwmp = IS_INF; st.idx_gs = -1;
-    st.g_hi_thr = st.g_lo_thr = st.p1_hi = st.p1_lo = st.p1_mid = st.o_hi_thr = st.o_lo_thr = 0.0f;
-    st.p2_hi = st.p2_lo = st.p2_mid = st.p3_yes = st.p3_no = 0.0f;
-    /* running minima of the transition terms (StepRec.q_o / q_gs) over the rows of THIS tile:
-     * phase 1 bounds block by block (see pw_phase1_body) */
-    float q_o = IS_INF, q_gs = IS_INF;
-    st.q_o = q_o; st.q_gs = q_gs;
+    StepVals st = p2_step_zero();
+    float q_o = st.q_o, q_gs = st.q_gs;
     int ob_cached = -1;
     float S_obc = 0.0f, V_obc = 0.0f;
     for (int s = 0; s < n_rows; s++) {
@@ -1484,26 +1539,14 @@ __device__ __forceinline__ void pw_phase2_body(const DevParams& P, char* smem, i
             const int hc = max(vTc + 1 - r, 1);
             const bool live = (vT < H) && (vT >= r);
             const SegTerms t = eval_segment<FAST, HAS_INVALID>(my, rb, (float)hc, s_rcp[hc], D, P.iw, s_rcp);
-            const int fo = t.fni - lo;
-            const bool inwin = (unsigned)fo < (unsigned)W;
-            const int foc = inwin ? fo : 0;
-            float od = my_win[foc] - s_win[s * ISP2_WS + foc];
-            if (__builtin_amdgcn_ballot_w64(live && !inwin) != 0ull) { /* outside the window: rare */
-                /* (only the lanes outside fetch: with every lane gathering, a step of this kind pulled up to
-                 * 128 lines -- 16 KB -- for the few values it needed) */
-                if (live && !inwin) {
-                    const float og = my_row[(unsigned)t.fni] - (lcol + (size_t)r * D)[(unsigned)t.fni];
-                    od = inwin ? od : og;
-                }
-            }
+            float od;
+            P2_OBJECT_DATA(od, my_win, s_win + s * ISP2_WS, my_row, r, t.fni, live);
             if (r - 1 < vhor)
                 pairwise_step<false>(P, st, r, live, od, t, b);
             else
                 pairwise_step<true>(P, st, r, live, od, t, b);
         }
-        /* lane s holds the final values of row r: broadcast, derive the StepRec of vB = r+1.
-         * (Also for the last row of the image, whose StepRec nobody reads: an unconditional
-         * assignment keeps `st` in place -- a guarded one costs 16 register moves per step.) */
+        /* lane s holds the final values of row r: broadcast, derive the StepRec of vB = r+1 */
         {
             const float cG = readlane_f(b.g, s), cO = readlane_f(b.o, s), cS = readlane_f(b.s, s);
             const int ob = __builtin_amdgcn_readlane(b.io, s) / 3; /* start of the best object chain */
@@ -1531,37 +1574,11 @@ __device__ __forceinline__ void pw_phase2_body(const DevParams& P, char* smem, i
             }
             st = make_step<HAS_INVALID>(P, S_r1, V_r1, S_ob, V_ob, s_odr, s_invc, s_logc, &pv, vhor, r,
                                         cG, cO, cS, ob, rcp_h);
-            /* fminf skips NaN fields: a candidate that selects one costs NaN and never wins */
-            const float m8 = min_raw(min3_raw(st.p1_hi, st.p1_lo, st.p1_mid),
-                                     min3_raw(min3_raw(st.p2_hi, st.p2_lo, st.p2_mid), st.p3_yes, st.p3_no));
-            if ((s & (IS_QB - 1)) == 0) q_o = q_gs = IS_INF; /* vB = r + 1 starts a bound block */
-            const float pwm8 = P.pw * m8;
-            q_o = min_raw(q_o, pwm8);
-            q_gs = min_raw(q_gs, st.pwmp);
-            st.q_o = q_o; st.q_gs = q_gs;
-            if (lane == 0 && r + 1 < H) {
-                store_step(scol + r + 1, st);
-                t8row[(size_t)colg * H + r + 1] = pwm8; /* (lemma L8: the row's own transition bound) */
-            }
+            P2_ROW_FINAL(s, r, lane == 0);
         }
     }
-    if (vT < H) {
-        const size_t o = ((size_t)colg * H + vT) * 3;
-        cost_table[o + 0] = b.g; cost_table[o + 1] = b.o; cost_table[o + 2] = b.s;
-        index_table[o + 0] = b.ig; index_table[o + 1] = b.io; index_table[o + 2] = b.is;
-    }
-    { /* summaries of the bound blocks of the candidate rows vB = tile_lo + 1 .. tile_lo + 64 (lemmas L7, L8) */
-        float* const bcolw = blksum + (size_t)colg * (P.ntiles * IS_QPT + 1) * IS_L7_F;
-        if (FAST) {
-            __builtin_amdgcn_s_waitcnt(0); /* this wave's StepRec / T8 stores have reached the L2 */
-            l78_block_summaries<IS_QB_LOG>(P, rcol, scol, t8row + (size_t)colg * H, bcolw, tile_lo, lane, vhor);
-        } else {
-            float* const slot = bcolw + (size_t)(tile * IS_QPT + (lane >> IS_QB_LOG) + 1) * IS_L7_F;
-            const bool writer = (lane & (IS_QB - 1)) == 0;
-            if (writer) l7_store(slot, l7_never());
-            l8_store_never(slot + 8, writer);
-        }
-    }
+    p2_store_row(cost_table, index_table, colg, H, vT, b);
+    p2_block_summaries<FAST>(P, rcol, scol, t8row, blksum, colg, tile_lo, lane, 64, 64, vhor);
 }
 
 #ifndef ISP2_OCC
@@ -1681,7 +1698,7 @@ __device__ __forceinline__ void pw_phase2x_body(const DevParams& P, char* smem, 
     unsigned char* my_Vb = s_Vb + half * 68; /* (never touched without an invalid value) */
     float* my_Vbase = s_SV + 2 * 66 + 34 + half; /* the count at the tile's first row (an exact integer), kept in LDS: a register held through the walk spilled */
 
-    /* ---- prologue: per column the fn window [lo, lo + W) of the tile's rows (pw_phase2_body) */
+    /* ---- prologue: per column the fn window [lo, lo + W) of the tile's rows */
     int lo, W;
     {
         float dmin = IS_INF, dmax = -IS_INF;
@@ -1694,12 +1711,7 @@ __device__ __forceinline__ void pw_phase2x_body(const DevParams& P, char* smem, 
         }
         dmin = half_min_f(dmin);
         dmax = half_max_f(dmax);
-        int l = (int)__builtin_fminf(__builtin_fmaxf(dmin, 1.0f), (float)D) - 1;
-        l = min(max(l, 0), D - 1);
-        int hh = (int)__builtin_fminf(__builtin_fmaxf(dmax, 0.0f), (float)(D - 1)) + 1;
-        hh = min(max(hh, l), min(D - 1, l + ISP2X_WMAX - 1));
-        lo = l;
-        W = hh - l + 1;
+        p2_window<ISP2X_WMAX>(dmin, dmax, D, &lo, &W);
     }
     { /* the window rows tile_lo .. tile_lo + 64 of this lane's column: 32 lanes, 16 columns at most */
         constexpr int NL = (ISP2_ROWS * 16 + 31) / 32; /* sixteen lanes per row, those beyond the window idle */
@@ -1725,42 +1737,13 @@ __device__ __forceinline__ void pw_phase2x_body(const DevParams& P, char* smem, 
             if (j == 0) *my_Vbase = vb0;
         }
     }
-    if (lane == 0) is_log_tables(s_invc, s_logc);
-    for (int i = lane; i < D; i += 64) s_odr[i] = odr[i];
-    for (int i = lane; i <= IS_TILE; i += 64) s_rcp[i] = rcp[min(i, H)];
+    p2_stage_tables<64>(s_invc, s_logc, s_odr, s_rcp, odr, rcp, D, H, lane);
     __syncthreads();
 
-    StepVals st;
-    st.pwmp = IS_INF; st.idx_gs = -1;
-    st.g_hi_thr = st.g_lo_thr = st.p1_hi = st.p1_lo = st.p1_mid = st.o_hi_thr = st.o_lo_thr = 0.0f;
-    st.p2_hi = st.p2_lo = st.p2_mid = st.p3_yes = st.p3_no = 0.0f;
-    float q_o = IS_INF, q_gs = IS_INF; /* (per tile, see pw_phase2_body) */
-    st.q_o = q_o; st.q_gs = q_gs;
+    StepVals st = p2_step_zero();
+    float q_o = st.q_o, q_gs = st.q_gs;
     int ob_cached = -1;
     float S_obc = 0.0f, V_obc = 0.0f;
-    /* partial minima of phase 1 for the rows base + li (its nsplit workgroups merged) */
-    auto load_best = [&](int row_off, PairBest& b) {
-        const size_t o = (size_t)colg * nsplit * 3 * 64 + row_off + li;
-        b.g = part_cost[o]; b.ig = part_idx[o];
-        b.o = part_cost[o + 64]; b.io = part_idx[o + 64];
-        b.s = part_cost[o + 128]; b.is = part_idx[o + 128];
-        for (int sp = 1; sp < nsplit; sp++) {
-            const size_t q = o + (size_t)sp * 3 * 64;
-            float c2 = part_cost[q]; int i2 = part_idx[q];
-            if ((c2 < b.g) || (c2 == b.g && c2 < IS_INF && (i2 / 3) < (b.ig / 3))) { b.g = c2; b.ig = i2; }
-            c2 = part_cost[q + 64]; i2 = part_idx[q + 64];
-            if ((c2 < b.o) || (c2 == b.o && c2 < IS_INF && (i2 / 3) < (b.io / 3))) { b.o = c2; b.io = i2; }
-            c2 = part_cost[q + 128]; i2 = part_idx[q + 128];
-            if ((c2 < b.s) || (c2 == b.s && c2 < IS_INF && (i2 / 3) < (b.is / 3))) { b.s = c2; b.is = i2; }
-        }
-    };
-    auto store_rows = [&](int vT, const PairBest& b) {
-        if (vT < H) {
-            const size_t o = ((size_t)colg * H + vT) * 3;
-            cost_table[o + 0] = b.g; cost_table[o + 1] = b.o; cost_table[o + 2] = b.s;
-            index_table[o + 0] = b.ig; index_table[o + 1] = b.io; index_table[o + 2] = b.is;
-        }
-    };
     /* the candidates that start at vB = r for the lanes `live`: eval + lutT values + update */
     auto candidates = [&](const RowRec& my, int vTc, const float* my_win, int r, bool live, float R0, float R1,
                           const StepVals& stv, PairBest& b) {
@@ -1770,16 +1753,8 @@ __device__ __forceinline__ void pw_phase2x_body(const DevParams& P, char* smem, 
         SegTerms t;
         if (sky) t = eval_segment_dpp<HAS_INVALID, IS_WANT_SKY>(my, R0, R1, (float)hc, rh, D, P.iw, s_rcp);
         else t = eval_segment_dpp<HAS_INVALID, IS_WANT_GROUND>(my, R0, R1, (float)hc, rh, D, P.iw, s_rcp);
-        const int fo = t.fni - lo;
-        const bool inwin = (unsigned)fo < (unsigned)W;
-        const int foc = inwin ? fo : 0;
-        float od = my_win[foc] - my_winbase[(r - tile_lo) * ISP2X_WS + foc];
-        if (__builtin_amdgcn_ballot_w64(live && !inwin) != 0ull) { /* outside the window: rare */
-            if (live && !inwin) { /* (only the lanes outside fetch, see pw_phase2_body) */
-                const float og = (lcol + (size_t)(vTc + 1) * D)[(unsigned)t.fni] - (lcol + (size_t)r * D)[(unsigned)t.fni];
-                od = inwin ? od : og;
-            }
-        }
+        float od;
+        P2_OBJECT_DATA(od, my_win, my_winbase + (r - tile_lo) * ISP2X_WS, lcol + (size_t)(vTc + 1) * D, r, t.fni, live);
         if (sky) pairwise_step<true>(P, stv, r, live, od, t, b);
         else pairwise_step<false>(P, stv, r, live, od, t, b);
     };
@@ -1805,17 +1780,7 @@ __device__ __forceinline__ void pw_phase2x_body(const DevParams& P, char* smem, 
         if (HAS_INVALID) V_ob = below ? V_obc : *my_Vbase + (float)my_Vb[oi];
         st = make_step<HAS_INVALID, true>(P, S_r1, V_r1, S_ob, V_ob, s_odr, s_invc, s_logc, &pv, vhor, r, cG,
                                           cO, cS, ob);
-        const float m8 = min_raw(min3_raw(st.p1_hi, st.p1_lo, st.p1_mid),
-                                 min3_raw(min3_raw(st.p2_hi, st.p2_lo, st.p2_mid), st.p3_yes, st.p3_no));
-        if (((r - tile_lo) & (IS_QB - 1)) == 0) q_o = q_gs = IS_INF; /* vB = r + 1 starts a bound block */
-        const float pwm8 = P.pw * m8;
-        q_o = min_raw(q_o, pwm8);
-        q_gs = min_raw(q_gs, st.pwmp);
-        st.q_o = q_o; st.q_gs = q_gs;
-        if (li == 0 && r + 1 < H) {
-            store_step(scol + r + 1, st);
-            t8row[(size_t)colg * H + r + 1] = pwm8; /* (lemma L8: the row's own transition bound) */
-        }
+        P2_ROW_FINAL(r - tile_lo, r, li == 0);
     };
     auto rec_dpp = [&](int v, float& R0, float& R1) { /* the record of v of this lane's column, DPP layout */
         const float* q = (const float*)(rcol + min(v, H));
@@ -1829,7 +1794,7 @@ __device__ __forceinline__ void pw_phase2x_body(const DevParams& P, char* smem, 
         const RowRec my = load_rec(rcol + vTc + 1);
         const float* my_win = my_winbase + (vTc + 1 - tile_lo) * ISP2X_WS;
         PairBest b;
-        load_best(0, b);
+        p2_load_best(part_cost, part_idx, (size_t)colg * nsplit * 3 * 64 + li, nsplit, b);
         float n0, n1;
         rec_dpp(tile_lo + 1, n0, n1);
         const int nL = min(32, n_rows);
@@ -1842,25 +1807,11 @@ __device__ __forceinline__ void pw_phase2x_body(const DevParams& P, char* smem, 
             }
             finalize(r, s, b, my.S, my.V);
         }
-        store_rows(vT, b);
-        if (li == 0) { /* StepRec(tile_lo + 32) for phase U */
-            float* d = s_st + half * 16;
-            d[0] = st.pwmp; d[1] = __builtin_bit_cast(float, st.idx_gs); d[2] = st.g_hi_thr; d[3] = st.g_lo_thr;
-            d[4] = st.p1_hi; d[5] = st.p1_lo; d[6] = st.p1_mid; d[7] = st.o_hi_thr; d[8] = st.o_lo_thr;
-            d[9] = st.p2_hi; d[10] = st.p2_lo; d[11] = st.p2_mid; d[12] = st.p3_yes; d[13] = st.p3_no;
-            d[14] = st.q_o; d[15] = st.q_gs;
-        }
+        p2_store_row(cost_table, index_table, colg, H, vT, b);
+        if (li == 0) store_step_f(s_st + half * 16, st); /* StepRec(tile_lo + 32) for phase U */
     }
-    /* the summaries of the bound blocks (lemmas L7, L8) of both phases' rows, at the very end: nothing of
-     * the walk is alive any more (computed inside the phases they cost the walk registers it does not have) */
-    auto summaries = [&](int rows_done) {
-        __builtin_amdgcn_s_waitcnt(0); /* this wave's StepRec / T8 stores have reached the L2 */
-        float* const bcolw = blksum + (size_t)colg * (P.ntiles * IS_QPT + 1) * IS_L7_F;
-        for (int base = 0; base < rows_done; base += 32)
-            l78_block_summaries<IS_QB_LOG>(P, rcol, scol, t8row + (size_t)colg * H, bcolw, tile_lo, base + li, vhor);
-    };
-    if (n_rows <= 32) {
-        summaries(32);
+    if (n_rows <= 32) { /* a short last tile: the bound block of phase L's rows */
+        p2_block_summaries<true>(P, rcol, scol, t8row, blksum, colg, tile_lo, li, 32, 32, vhor);
         return;
     }
     /* this wave's StepRec stores of phase L must have reached the L2 before phase S reads them */
@@ -1873,7 +1824,7 @@ __device__ __forceinline__ void pw_phase2x_body(const DevParams& P, char* smem, 
         const RowRec my = load_rec(rcol + vTc + 1);
         const float* my_win = my_winbase + (vTc + 1 - tile_lo) * ISP2X_WS;
         PairBest b;
-        load_best(32, b);
+        p2_load_best(part_cost, part_idx, (size_t)colg * nsplit * 3 * 64 + 32 + li, nsplit, b);
         const bool live_all = vT < H;
         float n0, n1;
         rec_dpp(tile_lo + 1, n0, n1);
@@ -1882,23 +1833,11 @@ __device__ __forceinline__ void pw_phase2x_body(const DevParams& P, char* smem, 
             const float R0 = n0, R1 = n1;
             rec_dpp(r + 1, n0, n1);
             /* the StepRec of r (built in phase L by this wave): requested now, needed after the eval */
-            const float4* sq = reinterpret_cast<const float4*>(scol + r);
-            const float4 a0 = sq[0], a1 = sq[1], a2 = sq[2], a3 = sq[3];
-            StepVals sv_;
-            sv_.pwmp = a0.x; sv_.idx_gs = __builtin_bit_cast(int, a0.y); sv_.g_hi_thr = a0.z; sv_.g_lo_thr = a0.w;
-            sv_.p1_hi = a1.x; sv_.p1_lo = a1.y; sv_.p1_mid = a1.z; sv_.o_hi_thr = a1.w;
-            sv_.o_lo_thr = a2.x; sv_.p2_hi = a2.y; sv_.p2_lo = a2.z; sv_.p2_mid = a2.w;
-            sv_.p3_yes = a3.x; sv_.p3_no = a3.y; sv_.q_o = a3.z; sv_.q_gs = a3.w;
+            const StepVals sv_ = vload_step(scol + r);
             candidates(my, vTc, my_win, r, live_all, R0, R1, sv_, b);
         }
-        { /* StepRec(tile_lo + 32), the running minima with it */
-            const float* d = s_st + half * 16;
-            st.pwmp = d[0]; st.idx_gs = __builtin_bit_cast(int, d[1]); st.g_hi_thr = d[2]; st.g_lo_thr = d[3];
-            st.p1_hi = d[4]; st.p1_lo = d[5]; st.p1_mid = d[6]; st.o_hi_thr = d[7]; st.o_lo_thr = d[8];
-            st.p2_hi = d[9]; st.p2_lo = d[10]; st.p2_mid = d[11]; st.p3_yes = d[12]; st.p3_no = d[13];
-            st.q_o = d[14]; st.q_gs = d[15];
-            q_o = st.q_o; q_gs = st.q_gs;
-        }
+        st = load_step_f(s_st + half * 16); /* StepRec(tile_lo + 32), the running minima with it */
+        q_o = st.q_o; q_gs = st.q_gs;
         rec_dpp(tile_lo + 32, n0, n1);
         for (int s = 32; s < n_rows; s++) {
             const int r = tile_lo + s;
@@ -1907,9 +1846,9 @@ __device__ __forceinline__ void pw_phase2x_body(const DevParams& P, char* smem, 
             candidates(my, vTc, my_win, r, (vT < H) && (vT >= r), R0, R1, st, b);
             finalize(r, s - 32, b, my.S, my.V);
         }
-        store_rows(vT, b);
+        p2_store_row(cost_table, index_table, colg, H, vT, b);
     }
-    summaries(64);
+    p2_block_summaries<true>(P, rcol, scol, t8row, blksum, colg, tile_lo, li, 32, 64, vhor);
 }
 
 template <bool HAS_INVALID>
@@ -2081,35 +2020,12 @@ __device__ __forceinline__ void pw_phase2s_body(const DevParams& P, char* smem, 
         const bool ok = (vT < H) && !(HAS_INVALID && d == P.invalid);
         const float dmin = wave_min_f(ok ? d : IS_INF);
         const float dmax = wave_max_f(ok ? d : -IS_INF);
-        int l = (int)__builtin_fminf(__builtin_fmaxf(dmin, 1.0f), (float)D) - 1;
-        l = min(max(l, 0), D - 1);
-        int h = (int)__builtin_fminf(__builtin_fmaxf(dmax, 0.0f), (float)(D - 1)) + 1;
-        h = min(max(h, l), min(D - 1, l + ISP2_WMAX - 1));
-        lo = __builtin_amdgcn_readfirstlane(l);
-        W = __builtin_amdgcn_readfirstlane(h - l + 1);
+        p2_window<ISP2_WMAX>(dmin, dmax, D, &lo, &W);
+        lo = __builtin_amdgcn_readfirstlane(lo);
+        W = __builtin_amdgcn_readfirstlane(W);
     }
-    { /* window rows: every load issued before the first LDS store (see pw_phase2_body) */
-        int lg = 0;
-        while ((1 << lg) < W) lg++;
-        lg = __builtin_amdgcn_readfirstlane(lg);
-        const int f = tid & ((1 << lg) - 1);
-        const int j0 = tid >> lg, dj = (ISP2S_WAVES * 64) >> lg;
-        constexpr int NL = (ISP2_ROWS * ISP2_WMAX + ISP2S_WAVES * 64 - 1) / (ISP2S_WAVES * 64);
-        float tmp[NL];
-#pragma unroll
-        for (int k = 0; k < NL; k++) {
-            const int j = j0 + k * dj;
-            tmp[k] = (j < ISP2_ROWS && f < W) ? lcol[(size_t)min(tile_lo + j, H) * D + lo + f] : 0.0f;
-        }
-#pragma unroll
-        for (int k = 0; k < NL; k++) {
-            const int j = j0 + k * dj;
-            if (j < ISP2_ROWS && f < W) s_win[j * ISP2_WS + f] = tmp[k];
-        }
-    }
-    if (tid == 0) is_log_tables(s_invc, s_logc);
-    for (int i = tid; i < D; i += ISP2S_WAVES * 64) s_odr[i] = odr[i];
-    for (int i = tid; i <= IS_TILE; i += ISP2S_WAVES * 64) s_rcp[i] = rcp[min(i, H)];
+    p2_stage_window<ISP2S_WAVES * 64>(s_win, lcol, tile_lo, H, D, lo, W, tid);
+    p2_stage_tables<ISP2S_WAVES * 64>(s_invc, s_logc, s_odr, s_rcp, odr, rcp, D, H, tid);
     if (tid < ISP2S_SLOTS) s_seq[tid] = -1;
     if (tid == ISP2S_SLOTS) *s_cons = 0;
     __syncthreads();
@@ -2123,21 +2039,7 @@ __device__ __forceinline__ void pw_phase2s_body(const DevParams& P, char* smem, 
             if (HAS_INVALID) myV = mr->V;
         }
         PairBest b;
-        {
-            const size_t o = (size_t)colg * nsplit * 3 * 64 + lane;
-            b.g = part_cost[o]; b.ig = part_idx[o];
-            b.o = part_cost[o + 64]; b.io = part_idx[o + 64];
-            b.s = part_cost[o + 128]; b.is = part_idx[o + 128];
-            for (int sp = 1; sp < nsplit; sp++) {
-                const size_t q = o + (size_t)sp * 3 * 64;
-                float c2 = part_cost[q]; int i2 = part_idx[q];
-                if ((c2 < b.g) || (c2 == b.g && c2 < IS_INF && (i2 / 3) < (b.ig / 3))) { b.g = c2; b.ig = i2; }
-                c2 = part_cost[q + 64]; i2 = part_idx[q + 64];
-                if ((c2 < b.o) || (c2 == b.o && c2 < IS_INF && (i2 / 3) < (b.io / 3))) { b.o = c2; b.io = i2; }
-                c2 = part_cost[q + 128]; i2 = part_idx[q + 128];
-                if ((c2 < b.s) || (c2 == b.s && c2 < IS_INF && (i2 / 3) < (b.is / 3))) { b.s = c2; b.is = i2; }
-            }
-        }
+        p2_load_best(part_cost, part_idx, (size_t)colg * nsplit * 3 * 64 + lane, nsplit, b);
         /* S (and V) prefix at the START row of this lane's best object candidate, carried beside b.io: the row that
          * becomes final hands it to make_step through one v_readlane.  (Until round 6 the chain fetched it with a scalar
          * load from global memory whenever the start lay below the tile -- a round trip of its own on every such row:
@@ -2149,12 +2051,8 @@ __device__ __forceinline__ void pw_phase2s_body(const DevParams& P, char* smem, 
             if (HAS_INVALID) Vo = sv[(H + 1) + ob0];
         }
         float S_vb = 0.0f, V_vb = 0.0f; /* the prefixes at index r = the start row of this step's candidates */
-        StepVals st;
-        st.pwmp = IS_INF; st.idx_gs = -1;
-        st.g_hi_thr = st.g_lo_thr = st.p1_hi = st.p1_lo = st.p1_mid = st.o_hi_thr = st.o_lo_thr = 0.0f;
-        st.p2_hi = st.p2_lo = st.p2_mid = st.p3_yes = st.p3_no = 0.0f;
-        float q_o = IS_INF, q_gs = IS_INF; /* (per tile, see pw_phase2_body) */
-        st.q_o = q_o; st.q_gs = q_gs;
+        StepVals st = p2_step_zero();
+        float q_o = st.q_o, q_gs = st.q_gs;
         for (int s = 0; s < n_rows; s++) {
             const int r = tile_lo + s;
             PriorVals pv;
@@ -2197,7 +2095,7 @@ __device__ __forceinline__ void pw_phase2s_body(const DevParams& P, char* smem, 
             } else {
                 pv = sload_prior(pcol + min(r + 1, H - 1));
             }
-            { /* (unconditional: see pw_phase2_body) */
+            { /* (for every row: see P2_ROW_FINAL) */
                 const float cG = readlane_f(b.g, s), cO = readlane_f(b.o, s), cS = readlane_f(b.s, s);
                 const int ob = __builtin_amdgcn_readlane(b.io, s) / 3;
                 const float S_r1 = readlane_f(myS, s), V_r1 = HAS_INVALID ? readlane_f(myV, s) : 0.0f;
@@ -2209,36 +2107,11 @@ __device__ __forceinline__ void pw_phase2s_body(const DevParams& P, char* smem, 
                  * in the code --, and object_disparity_range[k] out of registers instead of LDS -- no measurable change) */
                 st = make_step<HAS_INVALID>(P, S_r1, V_r1, S_ob, V_ob, s_odr, s_invc, s_logc, &pv, vhor, r,
                                             cG, cO, cS, ob);
-                const float m8 = min_raw(min3_raw(st.p1_hi, st.p1_lo, st.p1_mid),
-                                         min3_raw(min3_raw(st.p2_hi, st.p2_lo, st.p2_mid), st.p3_yes, st.p3_no));
-                if ((s & (IS_QB - 1)) == 0) q_o = q_gs = IS_INF; /* vB = r + 1 starts a bound block */
-                const float pwm8 = P.pw * m8;
-                q_o = min_raw(q_o, pwm8);
-                q_gs = min_raw(q_gs, st.pwmp);
-                st.q_o = q_o; st.q_gs = q_gs;
-                if (lane == 0 && r + 1 < H) {
-                    store_step(scol + r + 1, st);
-                    t8row[(size_t)colg * H + r + 1] = pwm8;
-                }
+                P2_ROW_FINAL(s, r, lane == 0);
             }
         }
-        if (vT < H) {
-            const size_t o = ((size_t)colg * H + vT) * 3;
-            cost_table[o + 0] = b.g; cost_table[o + 1] = b.o; cost_table[o + 2] = b.s;
-            index_table[o + 0] = b.ig; index_table[o + 1] = b.io; index_table[o + 2] = b.is;
-        }
-        { /* block summaries (lemmas L7, L8, see pw_phase2_body) */
-            float* const bcolw = blksum + (size_t)colg * (P.ntiles * IS_QPT + 1) * IS_L7_F;
-            if (FAST) {
-                __builtin_amdgcn_s_waitcnt(0);
-                l78_block_summaries<IS_QB_LOG>(P, rcol, scol, t8row + (size_t)colg * H, bcolw, tile_lo, lane, vhor);
-            } else {
-                float* const slot = bcolw + (size_t)(tile * IS_QPT + (lane >> IS_QB_LOG) + 1) * IS_L7_F;
-                const bool writer = (lane & (IS_QB - 1)) == 0;
-                if (writer) l7_store(slot, l7_never());
-                l8_store_never(slot + 8, writer);
-            }
-        }
+        p2_store_row(cost_table, index_table, colg, H, vT, b);
+        p2_block_summaries<FAST>(P, rcol, scol, t8row, blksum, colg, tile_lo, lane, 64, 64, vhor);
     } else {
         /* ================================ evaluator waves ================================ */
         const RowRec my = load_rec(rcol + vTc + 1);
@@ -2251,31 +2124,24 @@ __device__ __forceinline__ void pw_phase2s_body(const DevParams& P, char* smem, 
             const int hc = max(vTc + 1 - r, 1);
             const bool live = (vT < H) && (vT >= r);
             const SegTerms t = eval_segment<FAST, HAS_INVALID>(my, rb, (float)hc, s_rcp[hc], D, P.iw, s_rcp);
-            const int fo = t.fni - lo;
-            const bool inwin = (unsigned)fo < (unsigned)W;
-            const int foc = inwin ? fo : 0;
-            float od = my_win[foc] - s_win[s * ISP2_WS + foc];
-            if (__builtin_amdgcn_ballot_w64(live && !inwin) != 0ull) { /* outside the window: rare */
-                /* (only the lanes outside fetch: with every lane gathering, a step of this kind pulled up to
-                 * 128 lines -- 16 KB -- for the few values it needed) */
-                if (live && !inwin) {
-                    const float og = my_row[(unsigned)t.fni] - (lcol + (size_t)r * D)[(unsigned)t.fni];
-                    od = inwin ? od : og;
-                }
-            }
+            float od;
+            P2_OBJECT_DATA(od, my_win, s_win + s * ISP2_WS, my_row, r, t.fni, live);
             const bool ground = r - 1 < vhor; /* :687 / :729 */
             const float a_gs = live ? P.dw * (ground ? t.gd : t.sd) : IS_INF;
             const float b_gs = P.sw * (ground ? t.seg_g : t.seg_s);
             const float a_o = live ? P.dw * od : IS_INF;
             const float b_o = P.sw * t.seg_o;
             const int q = s % ISP2S_SLOTS;
-            float* slot = s_ring + q * ISP2S_SLOT_F;
+            /* the slot through the LDS-typed pointers the chain wave reads it with: the LDS-only fences order exactly
+             * these stores and the flag */
+            isp2s_lds_f_t* slot = (isp2s_lds_f_t*)(s_ring + q * ISP2S_SLOT_F);
+            isp2s_lds_f4_t* slot4 = (isp2s_lds_f4_t*)(s_ring + q * ISP2S_SLOT_F);
             if (s >= ISP2S_SLOTS) isp2s_wait_ge(s_cons, s - ISP2S_SLOTS); /* the slot's last tenant is consumed */
-            *reinterpret_cast<float4*>(slot + 8 * lane) = make_float4(a_gs, b_gs, a_o, b_o);
+            slot4[2 * lane] = isp2s_f4{a_gs, b_gs, a_o, b_o};
             slot[8 * lane + 4] = t.mean;
             if (lane == 0) {
-                *reinterpret_cast<float4*>(slot + 512) = make_float4(pv.pc, pv.g_from, pv.s_from_g, pv.o_from_s);
-                *reinterpret_cast<float4*>(slot + 516) = make_float4(pv.og_hi, pv.og_lo, pv.og_mid, pv.g_prev);
+                slot4[128] = isp2s_f4{pv.pc, pv.g_from, pv.s_from_g, pv.o_from_s};
+                slot4[129] = isp2s_f4{pv.og_hi, pv.og_lo, pv.og_mid, pv.g_prev};
             }
             ISP2S_FENCE_RELEASE();
             if (lane == 0) s_seq[q] = s;
