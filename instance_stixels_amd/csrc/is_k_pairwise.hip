@@ -135,10 +135,6 @@ __device__ __forceinline__ RowRec sload_rec_pinned(const RowRec* p) {
     return r;
 }
 
-__device__ __forceinline__ float readlane_f(float x, int l) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), l));
-}
-
 /* -is_logf(v) + is_logf(v2) (NegFastLogDiv, :35-38) for TWO argument pairs at once: the lower
  * half of the wave evaluates pair A, the upper half pair B, so the serial chain pays for one
  * logarithm instead of two.  v is a compile-time-like constant whose log is passed in. */

@@ -1,29 +1,18 @@
 /* is_k_unary.hip -- the unary column DP.  See is_kernels.h. */
-#include "is_kernels.h"
+#include "is_unary.h"
 
 /* ====================================================================================== */
 /* A7-A9  unary DP: one workgroup = (column, 64-row tile)                                  */
 /* ====================================================================================== */
-/* In unary mode the predecessor cost is never added: cost_table[vT][t] is the
- * minimum over vB of a single-segment cost, so all (vB, vT) pairs are independent and the only
- * order that matters is the strict-< tie rule (smallest vB wins).  index_table holds the winning
- * vB (or -1); the predecessor TYPE is resolved in k_backtrace from the final cost_table. */
-struct UnaryBest {
-    float g, o, s;
-    int vg, vo, vs;
-};
-
-/* One (vB, vT) evaluation of the unary model.
- *   SKY   the segment's lower neighbour is at / above the horizon (vB-1 >= vhor, :729): the
- *         non-object candidate is SKY, otherwise GROUND (:687); wave-uniform, so the caller runs
- *         separate loops and each loop has ONE accumulator pair live in its body;
- *   DIAG  the segment start may lie above this lane's vT (diagonal 64x64 block): masked lanes;
- *   FIRST vB = 0: ground additionally needs vT <= vhor (:542-545). */
+/* One (vB, vT) evaluation of the unary model (UnaryBest, unary_update: is_unary.h): the record of vB is a scalar
+ * record, the vB side of the object data term comes out of the wave's lutT row (pick_lut).
+ *   FAST  a column of the FAST encoding, walked DOWNWARDS with the `<=` update (below); the generic encoding is
+ *         walked upwards with the reference's strict `<`.  The terms are returned for the bounds of the FAST walk. */
 template <bool FAST, bool HAS_INVALID, bool SKY, bool DIAG, bool FIRST, int NR, bool NOGROUND = false>
-__device__ __forceinline__ void unary_step(const DevParams& P, const RowRec& my, const RowRec& rb,
-                                           const LutRow<NR>& lrow, const float* my_tile,
-                                           const float* s_rcp, int vT, int vTc, int vhor, int vB,
-                                           float hf_full, bool row_ok, UnaryBest& b) {
+__device__ __forceinline__ SegTerms unary_step(const DevParams& P, const RowRec& my, const RowRec& rb,
+                                               const LutRow<NR>& lrow, const float* my_tile,
+                                               const float* s_rcp, int vT, int vTc, int vhor, int vB,
+                                               float hf_full, bool row_ok, UnaryBest& b) {
     const int h = vTc + 1 - vB;
     const bool live = DIAG ? ((h > 0) && row_ok) : row_ok;
     const int hc = DIAG ? max(h, 1) : h;
@@ -33,43 +22,11 @@ __device__ __forceinline__ void unary_step(const DevParams& P, const RowRec& my,
     const float hf = (DIAG || FIRST) ? (float)hc : hf_full;
     const SegTerms t = eval_segment<FAST, HAS_INVALID>(my, rb, hf, r, P.D, P.iw);
     const float od = my_tile[t.fni] - pick_lut<NR>(lrow, t.fni);
-    const float pwih = P.pw * r;
-    /* cost = dw*data + pw*(1/h) + sw*seg, left to right (:716-719, 762-765, 820-823) */
-    const float cost_o = P.dw * od + pwih + P.sw * t.seg_o;
-    /* full steps: every lane with vT < H is live, and rows vT >= H are never stored */
-    constexpr bool ALL_LANES = FAST && !DIAG && !FIRST;
-    if (ALL_LANES) {
-        take_if_less(b.o, b.vo, cost_o, vB);
-    } else {
-        const bool uo = live && (cost_o < b.o);
-        b.o = uo ? cost_o : b.o;
-        b.vo = uo ? vB : b.vo;
-    }
-    if (SKY) {
-        const float cost_s = P.dw * t.sd + pwih + P.sw * t.seg_s;
-        if (ALL_LANES) {
-            take_if_less(b.s, b.vs, cost_s, vB);
-        } else {
-            const bool us = live && (cost_s < b.s);
-            b.s = us ? cost_s : b.s;
-            b.vs = us ? vB : b.vs;
-        }
-    } else if (!NOGROUND) {
-        /* NOGROUND: every lane of the tile lies at or above the horizon, where the ground data
-         * cost prefix is +inf (StixelsKernels.cu:435-446): dw * inf is inf (or NaN for dw = 0)
-         * and never passes the strict < test, so the candidate is not evaluated at all */
-        const float cost_g = P.dw * t.gd + pwih + P.sw * t.seg_g;
-        if (ALL_LANES) {
-            take_if_less(b.g, b.vg, cost_g, vB);
-        } else {
-            const bool ug = (FIRST ? (live && (vT <= vhor)) : live) && (cost_g < b.g);
-            b.g = ug ? cost_g : b.g;
-            b.vg = ug ? vB : b.vg;
-        }
-    }
+    unary_update<FAST, SKY, DIAG, FIRST, NOGROUND>(P, t, od, P.pw * r, vB, live, vT <= vhor, b);
+    return t;
 }
 
-template <bool FAST, bool HAS_INVALID, bool SKY, bool DIAG, int NR, bool NOGROUND = false>
+template <bool HAS_INVALID, bool SKY, bool DIAG, int NR, bool NOGROUND = false>
 __device__ __forceinline__ int unary_range(const DevParams& P, const RowRec& my,
                                            const RowRec* __restrict__ rcol,
                                            const float* __restrict__ lcol, const float* my_tile,
@@ -83,8 +40,8 @@ __device__ __forceinline__ int unary_range(const DevParams& P, const RowRec& my,
         const RowRec cur = sload_rec(rcol + vB);
         const LutRow<NR> row = next_row;
         load_lut_row<NR>(next_row, lrsrc, lcol, min(vB + nw, P.H), P.D, lane4); /* row H exists */
-        unary_step<FAST, HAS_INVALID, SKY, DIAG, false, NR, NOGROUND>(P, my, cur, row, my_tile, s_rcp, vT,
-                                                                      vTc, vhor, vB, hf, row_ok, b);
+        unary_step<false, HAS_INVALID, SKY, DIAG, false, NR, NOGROUND>(P, my, cur, row, my_tile, s_rcp, vT, vTc,
+                                                                       vhor, vB, hf, row_ok, b);
         hf -= nwf;
     }
     return vB;
@@ -93,7 +50,7 @@ __device__ __forceinline__ int unary_range(const DevParams& P, const RowRec& my,
 /* The wave walks vB = w, w+nw, ... <= vB_end in ascending order through (at most) four ranges:
  * ground/full, ground/diagonal, sky/full, sky/diagonal (ground while vB <= vhor; "full" while
  * every lane of the tile has vT >= vB, i.e. vB <= tile_lo). */
-template <bool FAST, bool HAS_INVALID, int NR>
+template <bool HAS_INVALID, int NR>
 __device__ __forceinline__ void unary_loop(const DevParams& P, const RowRec& my,
                                            const RowRec* __restrict__ rcol,
                                            const float* __restrict__ lcol, const float* my_tile,
@@ -110,29 +67,27 @@ __device__ __forceinline__ void unary_loop(const DevParams& P, const RowRec& my,
         const LutRow<NR> row = next_row;
         load_lut_row<NR>(next_row, lrsrc, lcol, min(nw, P.H), P.D, lane4);
         if (tile_lo == 0)
-            unary_step<FAST, HAS_INVALID, false, true, true, NR>(P, my, cur, row, my_tile, s_rcp, vT,
-                                                                 vTc, vhor, 0, 0.0f, row_ok, b);
+            unary_step<false, HAS_INVALID, false, true, true, NR>(P, my, cur, row, my_tile, s_rcp, vT, vTc, vhor,
+                                                                  0, 0.0f, row_ok, b);
         else
-            unary_step<FAST, HAS_INVALID, false, false, true, NR>(P, my, cur, row, my_tile, s_rcp, vT,
-                                                                  vTc, vhor, 0, 0.0f, row_ok, b);
+            unary_step<false, HAS_INVALID, false, false, true, NR>(P, my, cur, row, my_tile, s_rcp, vT, vTc, vhor,
+                                                                   0, 0.0f, row_ok, b);
         vB += nw;
     }
     if (tile_lo >= vhor) /* whole tile at / above the horizon */
-        vB = unary_range<FAST, HAS_INVALID, false, false, NR, true>(
+        vB = unary_range<HAS_INVALID, false, false, NR, true>(
             P, my, rcol, lcol, my_tile, s_rcp, vT, vTc, vhor, vB, nw, min(min(vhor, tile_lo), vB_end),
             row_ok, lane4, lrsrc, next_row, b);
     else
-        vB = unary_range<FAST, HAS_INVALID, false, false, NR>(P, my, rcol, lcol, my_tile, s_rcp, vT, vTc,
-                                                              vhor, vB, nw, min(min(vhor, tile_lo), vB_end),
-                                                              row_ok, lane4, lrsrc, next_row, b);
-    vB = unary_range<FAST, HAS_INVALID, false, true, NR>(P, my, rcol, lcol, my_tile, s_rcp, vT, vTc,
-                                                         vhor, vB, nw, min(vhor, vB_end), row_ok, lane4,
-                                                         lrsrc, next_row, b);
-    vB = unary_range<FAST, HAS_INVALID, true, false, NR>(P, my, rcol, lcol, my_tile, s_rcp, vT, vTc,
-                                                         vhor, vB, nw, min(tile_lo, vB_end), row_ok,
-                                                         lane4, lrsrc, next_row, b);
-    unary_range<FAST, HAS_INVALID, true, true, NR>(P, my, rcol, lcol, my_tile, s_rcp, vT, vTc, vhor, vB,
-                                                   nw, vB_end, row_ok, lane4, lrsrc, next_row, b);
+        vB = unary_range<HAS_INVALID, false, false, NR>(P, my, rcol, lcol, my_tile, s_rcp, vT, vTc, vhor, vB, nw,
+                                                        min(min(vhor, tile_lo), vB_end), row_ok, lane4, lrsrc,
+                                                        next_row, b);
+    vB = unary_range<HAS_INVALID, false, true, NR>(P, my, rcol, lcol, my_tile, s_rcp, vT, vTc, vhor, vB, nw,
+                                                   min(vhor, vB_end), row_ok, lane4, lrsrc, next_row, b);
+    vB = unary_range<HAS_INVALID, true, false, NR>(P, my, rcol, lcol, my_tile, s_rcp, vT, vTc, vhor, vB, nw,
+                                                   min(tile_lo, vB_end), row_ok, lane4, lrsrc, next_row, b);
+    unary_range<HAS_INVALID, true, true, NR>(P, my, rcol, lcol, my_tile, s_rcp, vT, vTc, vhor, vB, nw, vB_end, row_ok,
+                                             lane4, lrsrc, next_row, b);
 }
 
 
@@ -150,57 +105,6 @@ __device__ __forceinline__ void unary_loop(const DevParams& P, const RowRec& my,
  * holds for the COMPUTED costs, not just the real-valued ones.  Once LB > best in every lane and
  * every type that can still receive candidates, the wave stops: nothing below can win, and nothing
  * below can tie (ties go to the smaller vB, hence the strict >). */
-template <bool HAS_INVALID, bool SKY, bool DIAG, bool FIRST, int NR, bool NOGROUND>
-__device__ __forceinline__ SegTerms unary_step_desc(const DevParams& P, const RowRec& my,
-                                                    const RowRec& rb, const LutRow<NR>& lrow,
-                                                    const float* my_tile, const float* s_rcp, int vT,
-                                                    int vTc, int vhor, int vB, float hf_full,
-                                                    bool row_ok, UnaryBest& b) {
-    const int h = vTc + 1 - vB;
-    const bool live = DIAG ? ((h > 0) && row_ok) : row_ok;
-    const int hc = DIAG ? max(h, 1) : h;
-    const float r = s_rcp[hc];
-    const float hf = (DIAG || FIRST) ? (float)hc : hf_full;
-    const SegTerms t = eval_segment<true, HAS_INVALID>(my, rb, hf, r, P.D, P.iw);
-    const float od = my_tile[t.fni] - pick_lut<NR>(lrow, t.fni);
-    const float pwih = P.pw * r;
-    const float cost_o = P.dw * od + pwih + P.sw * t.seg_o;
-    constexpr bool ALL_LANES = !DIAG && !FIRST;
-    if (ALL_LANES) {
-        take_if_le(b.o, b.vo, cost_o, vB);
-    } else {
-        const bool uo = live && (cost_o <= b.o);
-        b.o = uo ? cost_o : b.o;
-        b.vo = uo ? vB : b.vo;
-    }
-    if (SKY) {
-        const float cost_s = P.dw * t.sd + pwih + P.sw * t.seg_s;
-        if (ALL_LANES) {
-            take_if_le(b.s, b.vs, cost_s, vB);
-        } else {
-            const bool us = live && (cost_s <= b.s);
-            b.s = us ? cost_s : b.s;
-            b.vs = us ? vB : b.vs;
-        }
-    } else if (!NOGROUND) {
-        const float cost_g = P.dw * t.gd + pwih + P.sw * t.seg_g;
-        if (ALL_LANES) {
-            take_if_le(b.g, b.vg, cost_g, vB);
-        } else {
-            const bool ug = (FIRST ? (live && (vT <= vhor)) : live) && (cost_g <= b.g);
-            b.g = ug ? cost_g : b.g;
-            b.vg = ug ? vB : b.vg;
-        }
-    }
-    return t;
-}
-
-struct PruneVals { /* register copy of a PruneRec + the lanes that need no bound */
-    float E1o, E1g, E1s, E2;
-    unsigned long long dead;  /* lanes with vT >= H: never stored                         */
-    unsigned long long gdead; /* dead, or the ground data term of the lane is +inf for good */
-};
-
 template <bool SKY, bool NOGROUND>
 __device__ __forceinline__ bool nothing_below_can_win(const DevParams& P, const PruneVals& pv,
                                                       const SegTerms& t, const UnaryBest& b) {
@@ -232,7 +136,7 @@ __device__ __forceinline__ int unary_range_desc(const DevParams& P, const RowRec
         const RowRec cur = sload_rec(rcol + vB);
         const LutRow<NR> row = next_row;
         load_lut_row<NR>(next_row, lrsrc, lcol, max(vB - nw, 0), P.D, lane4);
-        const SegTerms t = unary_step_desc<HAS_INVALID, SKY, DIAG, false, NR, NOGROUND>(
+        const SegTerms t = unary_step<true, HAS_INVALID, SKY, DIAG, false, NR, NOGROUND>(
             P, my, cur, row, my_tile, s_rcp, vT, vTc, vhor, vB, hf, row_ok, b);
         hf += nwf;
         if (PRUNE && nothing_below_can_win<SKY, NOGROUND>(P, pv, t, b)) return IS_WAVE_DONE;
@@ -251,13 +155,8 @@ __device__ __forceinline__ void unary_loop_desc(const DevParams& P, const RowRec
     const bool row_ok = vT < P.H;
     if (w > vB_end) return;
     int vB = vB_end - (vB_end - w) % nw; /* the wave's largest vB: vB == w (mod nw) */
-    PruneVals pv;
-    {
-        cprune_t q = (cprune_t)prec;
-        pv.E1o = q->E1o; pv.E1g = q->E1g; pv.E1s = q->E1s; pv.E2 = q->E2;
-        pv.dead = ~__builtin_amdgcn_ballot_w64(row_ok);
-        pv.gdead = pv.dead | __builtin_amdgcn_ballot_w64(my.G == IS_INF);
-    }
+    PruneVals pv = load_prune_vals(prec, 1.0f, row_ok);
+    pv.gdead = pv.dead | __builtin_amdgcn_ballot_w64(my.G == IS_INF);
     LutRow<NR> next_row;
     load_lut_row<NR>(next_row, lrsrc, lcol, vB, P.D, lane4);
     const bool nog = tile_lo >= vhor;
@@ -280,11 +179,11 @@ __device__ __forceinline__ void unary_loop_desc(const DevParams& P, const RowRec
         const RowRec cur = sload_rec(rcol);
         const LutRow<NR> row = next_row;
         if (tile_lo == 0)
-            unary_step_desc<HAS_INVALID, false, true, true, NR, false>(P, my, cur, row, my_tile, s_rcp, vT,
-                                                                       vTc, vhor, 0, 0.0f, row_ok, b);
+            unary_step<true, HAS_INVALID, false, true, true, NR, false>(P, my, cur, row, my_tile, s_rcp, vT, vTc,
+                                                                        vhor, 0, 0.0f, row_ok, b);
         else
-            unary_step_desc<HAS_INVALID, false, false, true, NR, false>(P, my, cur, row, my_tile, s_rcp, vT,
-                                                                        vTc, vhor, 0, 0.0f, row_ok, b);
+            unary_step<true, HAS_INVALID, false, false, true, NR, false>(P, my, cur, row, my_tile, s_rcp, vT, vTc,
+                                                                         vhor, 0, 0.0f, row_ok, b);
     }
 }
 
@@ -361,54 +260,19 @@ __global__ __launch_bounds__(IS_UNARY_WAVES * 64, IS_UNARY_OCC) void k_dp_unary(
     __syncthreads();
 
     UnaryBest b;
-    b.g = b.o = b.s = IS_INF;
-    b.vg = b.vs = -1;
-    b.vo = 0; /* index_table[vT*3+OBJECT] = OBJECT at vB = 0, :592 */
+    unary_best_init(b);
     const float* my_tile = s_tile + lane * DP;
     const int vB_end = min(tile_lo + IS_TILE - 1, H - 1);
     if (FASTCOLS)
         unary_loop_desc<HAS_INVALID, NR>(P, my, rcol, lcol, my_tile, s_rcp, vT, vTc, vhor, w, nw, tile_lo,
                                          vB_end, lane * 4, lrsrc, prune + colg, b);
     else
-        unary_loop<false, HAS_INVALID, NR>(P, my, rcol, lcol, my_tile, s_rcp, vT, vTc, vhor, w, nw, tile_lo,
-                                           vB_end, lane * 4, lrsrc, b);
+        unary_loop<HAS_INVALID, NR>(P, my, rcol, lcol, my_tile, s_rcp, vT, vTc, vhor, w, nw, tile_lo, vB_end,
+                                    lane * 4, lrsrc, b);
 
-    /* merge the waves' partial minima: min cost, ties -> smallest vB (= first strict minimum
-     * of the reference's ascending-vB loop) */
-    __syncthreads();
-    float* m_cost = s_tile;                        /* [nw][3][64] (aliases the LUT tile) */
-    int* m_vb = (int*)(m_cost + nw * 3 * 64);      /* [nw][3][64] */
-    m_cost[(w * 3 + 0) * 64 + lane] = b.g; m_vb[(w * 3 + 0) * 64 + lane] = b.vg;
-    m_cost[(w * 3 + 1) * 64 + lane] = b.o; m_vb[(w * 3 + 1) * 64 + lane] = b.vo;
-    m_cost[(w * 3 + 2) * 64 + lane] = b.s; m_vb[(w * 3 + 2) * 64 + lane] = b.vs;
-    __syncthreads();
-    if (tid < 3 * 64) {
-        const int type = tid >> 6;
-        float c = m_cost[(0 * 3 + type) * 64 + lane];
-        int vb = m_vb[(0 * 3 + type) * 64 + lane];
-        for (int ww = 1; ww < nw; ww++) {
-            const float c2 = m_cost[(ww * 3 + type) * 64 + lane];
-            const int vb2 = m_vb[(ww * 3 + type) * 64 + lane];
-            const bool take = (c2 < c) || (c2 == c && vb2 >= 0 && (vb < 0 || vb2 < vb));
-            if (take) { c = c2; vb = vb2; }
-        }
-        /* a row without a finite candidate keeps the initial index (the descending walk records
-         * +inf candidates, the reference's strict < never does; :592 for the object type) */
-        if (!(c < IS_INF)) vb = (type == IS_OBJECT) ? 0 : -1;
-        /* final (cost, vB) of this type back to LDS: one wave then writes the three types of a
-         * row as 12 contiguous bytes (a wave-wide contiguous 768-byte store) instead of three
-         * waves writing every third dword */
-        m_cost[type * 64 + lane] = c;
-        m_vb[type * 64 + lane] = vb;
-    }
-    __syncthreads();
-    if (w == 0 && vT < H) {
-        const size_t o = ((size_t)colg * H + vT) * 3;
-        float* cd = cost_table + o;
-        int32_t* id = index_table + o;
-        cd[0] = m_cost[0 * 64 + lane]; cd[1] = m_cost[1 * 64 + lane]; cd[2] = m_cost[2 * 64 + lane];
-        id[0] = m_vb[0 * 64 + lane]; id[1] = m_vb[1 * 64 + lane]; id[2] = m_vb[2 * 64 + lane];
-    }
+    /* merge the waves' partial minima and store the tile's rows (the merge area aliases the LUT tile, the finals
+     * wave 0's slot of it) */
+    UNARY_MERGE_STORE(s_tile, s_tile, b, nw, w, tid, lane, colg, H, vT, cost_table, index_table);
     } /* pass */
     } /* pair */
     } /* item */
@@ -419,7 +283,8 @@ extern "C" {
 size_t isk_unary_lds_bytes(const DevParams* P) {
     const size_t rcp = sizeof(float) * (((size_t)P->H + 1 + 3) & ~(size_t)3);
     const size_t tile = sizeof(float) * (size_t)IS_TILE * (P->D + 1);
-    const size_t merge = (size_t)IS_UNARY_WAVES * 3 * 64 * 8; /* aliases the tile after the loop */
+    /* (aliases the tile after the loop) */
+    const size_t merge = sizeof(float) * UNARY_MERGE_FLOATS((size_t)IS_UNARY_WAVES);
     return rcp + (tile > merge ? tile : merge) + 16;
 }
 

@@ -36,7 +36,7 @@
  * of sixteen; + 8 KB for the tile's 64 records, a ring of two slots = 22.8 KB per workgroup, seven per CU): 3.67 ms per 64 frames, and
  * the windowed launch at every call size (ISF_WIN_MIN_COLS).
  */
-#include "is_kernels.h"
+#include "is_unary.h"
 
 #ifndef ISF_WAVES
 #define ISF_WAVES 8
@@ -53,13 +53,8 @@
 #define ISF_THREADS (ISF_WAVES * 64)
 static_assert(ISF_WIN_WAVES >= 3 && ISF_WIN_WAVES <= ISF_WAVES, "the merge runs on 3 x 64 threads (one wave per type)");
 
-struct UnaryBestF {
-    float g, o, s;
-    int vg, vo, vs;
-};
-
-/* One (vB, vT) evaluation; semantics of unary_step (is_k_unary.hip) with the `<=` update of a
- * descending walk.  lrow: the lutT row of vB in LDS. */
+/* One (vB, vT) evaluation; unary_step (is_k_unary.hip) with the record of vB as DPP / scalar operands and the `<=`
+ * update of a descending walk (unary_update, is_unary.h).  lrow: the lutT row of vB in LDS. */
 /* WIN: my_tile holds the fn window [win.lo, win.lo + IS_P1_WIN) of the lane's lutT row (is_device.h); a lane
  * outside it reads global memory -- the one access of the loop that waits for memory (the compiler's
  * vmcnt(0) for it also drains the ring's prefetches: correct, and rare below the horizon). */
@@ -74,7 +69,7 @@ template <bool HAS_INVALID, bool SKY, bool DIAG, bool FIRST, bool NOGROUND, bool
 __device__ __forceinline__ SegTerms fast_step(const DevParams& P, const RowRec& my, const float* srec,
                                               const float* lrow, const float* my_tile,
                                               const float* s_rcp, int vT, int vTc, int vhor, int vB,
-                                              bool row_ok, UnaryBestF& b, const isk_f16v& S,
+                                              bool row_ok, UnaryBest& b, const isk_f16v& S,
                                               const FastWin win = FastWin()) {
     const int h = vTc + 1 - vB;
     const bool live = DIAG ? ((h > 0) && row_ok) : row_ok;
@@ -110,51 +105,15 @@ __device__ __forceinline__ SegTerms fast_step(const DevParams& P, const RowRec& 
         vtv = my_tile[t.fni];
         vbv = lrow[t.fni];
     }
-    const float od = vtv - vbv;
-    const float pwih = P.pw * r;
-    /* cost = dw*data + pw*(1/h) + sw*seg, left to right (:716-719, 762-765, 820-823) */
-    const float cost_o = P.dw * od + pwih + P.sw * t.seg_o;
-    constexpr bool ALL_LANES = !DIAG && !FIRST;
-    if (ALL_LANES) {
-        take_if_le(b.o, b.vo, cost_o, vB);
-    } else {
-        const bool uo = live && (cost_o <= b.o);
-        b.o = uo ? cost_o : b.o;
-        b.vo = uo ? vB : b.vo;
-    }
-    if (SKY) {
-        const float cost_s = P.dw * t.sd + pwih + P.sw * t.seg_s;
-        if (ALL_LANES) {
-            take_if_le(b.s, b.vs, cost_s, vB);
-        } else {
-            const bool us = live && (cost_s <= b.s);
-            b.s = us ? cost_s : b.s;
-            b.vs = us ? vB : b.vs;
-        }
-    } else if (!NOGROUND) {
-        const float cost_g = P.dw * t.gd + pwih + P.sw * t.seg_g;
-        if (ALL_LANES) {
-            take_if_le(b.g, b.vg, cost_g, vB);
-        } else {
-            const bool ug = (FIRST ? (live && (vT <= vhor)) : live) && (cost_g <= b.g);
-            b.g = ug ? cost_g : b.g;
-            b.vg = ug ? vB : b.vg;
-        }
-    }
+    unary_update<true, SKY, DIAG, FIRST, NOGROUND>(P, t, vtv - vbv, P.pw * r, vB, live, vT <= vhor, b);
     return t;
 }
 
-struct PruneValsF {
-    float E1o, E1g, E1s, E2; /* E2: three times PruneRec.E2, see seg_o_lower_bound */
-    unsigned long long dead;  /* lanes with vT >= H: never stored                            */
-    unsigned long long gdead; /* dead, or the ground data term of the lane is +inf for good   */
-};
-
-/* see the proof sketch at unary_step_desc (is_k_unary.hip) and DESIGN.md "Pruning".  Bit 0: the
+/* see the proof sketch at nothing_below_can_win (is_k_unary.hip) and DESIGN.md "Pruning".  Bit 0: the
  * object bound holds in every lane, bit 1: the ground / sky bound does. */
 template <bool SKY, bool NOGROUND>
-__device__ __forceinline__ int fast_bounds(const DevParams& P, const PruneValsF& pv, const SegTerms& t,
-                                           const UnaryBestF& b) {
+__device__ __forceinline__ int fast_bounds(const DevParams& P, const PruneVals& pv, const SegTerms& t,
+                                           const UnaryBest& b) {
     const float lb_o = P.sw * seg_o_lower_bound(t, pv.E2) - pv.E1o; /* (pv.E2 holds 3 * PruneRec.E2) */
     const bool ok_o = (__builtin_amdgcn_ballot_w64(lb_o > b.o) | pv.dead) == ~0ull;
     bool ok_x = true;
@@ -176,14 +135,14 @@ __device__ __forceinline__ int fast_bounds(const DevParams& P, const PruneValsF&
  * the next batch is requested before this one is walked, and step j takes its operands out of lane j with
  * v_readlane (a ROLLED loop: unrolled with DPP operands the sixteen steps of both types cost the walk's loop 30
  * spilled SGPRs, scene -7 %).  A candidate is two class differences, no instance term, no mean, no LUT value: a
- * fifth of the instructions of fast_step, same operand order (cost = dw * data + pw / h + sw * (f + nic)); the
+ * fifth of the instructions of fast_step, same cost (unary_cost on seg = f + nic); the
  * object bound is sticky (the class minima only grow and the best cost cannot change any more).  Returns true when the type's
  * bound holds (the wave is done), else vB < lo.  lo = 0 includes the first segment: with the object type closed it
  * is a ground candidate like the others (record 0 is all zeros), for the lanes first_ok. */
 template <bool SKY>
-__device__ __forceinline__ bool gs_walk(const DevParams& P, const PruneValsF& pv, const RowRec& my,
+__device__ __forceinline__ bool gs_walk(const DevParams& P, const PruneVals& pv, const RowRec& my,
                                         const RowRec* __restrict__ rcol, const float* s_rcp, int vTc, int& vB,
-                                        const int lo, const int nwv, UnaryBestF& b, int& n_gs,
+                                        const int lo, const int nwv, UnaryBest& b, int& n_gs,
                                         const bool first_ok /* may this lane take the first segment (vB = 0)? */) {
     const int j16 = (int)(threadIdx.x & 15);
     /* SKY: Fsky (dword 18), Fnic (19), K (21); ground: Fg0 (0), Fg1 (1), Fnic (19), G (20) */
@@ -204,23 +163,23 @@ __device__ __forceinline__ bool gs_walk(const DevParams& P, const PruneValsF& pv
             const int v = vB - jj * nwv;
             const float r = s_rcp[vTc + 1 - v];
             const float pwih = P.pw * r;
-            const float q0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a0), jj));
-            const float q1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a1), jj));
-            const float q2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a2), jj));
+            const float q0 = readlane_f(a0, jj);
+            const float q1 = readlane_f(a1, jj);
+            const float q2 = readlane_f(a2, jj);
             if (SKY) {
                 const float f = my.Fsky - q0;
                 const float nic = P.iw * (float)(my.Fnic - __float_as_int(q1));
                 const float seg = f + nic;
-                const float cost = P.dw * (my.K - q2) + pwih + P.sw * seg;
+                const float cost = unary_cost(P, my.K - q2, pwih, seg);
                 take_if_le(b.s, b.vs, cost, v);
                 const float lb = P.sw * seg - pv.E1s;
                 closed = (__builtin_amdgcn_ballot_w64(lb > b.s) | pv.dead) == ~0ull;
             } else {
-                const float q3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a3), jj));
+                const float q3 = readlane_f(a3, jj);
                 const float f = __builtin_fminf(my.Fg0 - q0, my.Fg1 - q1);
                 const float nic = P.iw * (float)(my.Fnic - __float_as_int(q2));
                 const float seg = f + nic;
-                float cost = P.dw * (my.G - q3) + pwih + P.sw * seg;
+                float cost = unary_cost(P, my.G - q3, pwih, seg);
                 if (v == 0 && !first_ok) cost = IS_INF; /* :509: the first segment is ground only up to the horizon */
                 take_if_le(b.g, b.vg, cost, v);
                 const float lb = P.sw * seg - pv.E1g;
@@ -289,8 +248,8 @@ __device__ __forceinline__ void ring_prefetch_win(const WinLane& wl, int vB, flo
  * (entry 15 does not exist for w = 3: a dead quarter-step).  A quarter that changes rows hands its partial minima to
  * the lanes that own those rows (ds_bpermute + the merge rule of the waves: smaller cost, ties -> smaller vB) and
  * loads its own rows' record.  Everything a step reads is in LDS: both lutT windows (vB > tile_lo is a row of the
- * tile itself) and the records, of vB and of the lanes' rows alike (s_nat, below); candidates, operand order and the
- * `<=` update of a descending walk are fast_step's.  The tile that contains the horizon keeps the uniform steps (its
+ * tile itself) and the records, of vB and of the lanes' rows alike (s_nat, below); candidates, cost and the `<=`
+ * update of a descending walk are fast_step's (unary_update).  The tile that contains the horizon keeps the uniform steps (its
  * vB change from ground to sky candidates on the way).  Afterwards every lane holds its own row again and the wave
  * goes on below the tile. */
 /* Every record of the tile is staged in LDS (s_nat): the record of vB = tile_lo + a IS the record of row a - 1, so the
@@ -316,7 +275,7 @@ __device__ __forceinline__ int qd_first_row(const int lane) {
     return (q == 0) ? 48 + l15 : ((q == 1) ? 32 + l15 : lane);
 }
 template <bool HAS_INVALID, bool SKY>
-__device__ __forceinline__ void diag_quarters(const DevParams& P, RowRec& my, UnaryBestF& b,
+__device__ __forceinline__ void diag_quarters(const DevParams& P, RowRec& my, UnaryBest& b,
                                               const float* __restrict__ lcol,
                                               const float* s_tile, const float* s_rcp, const float* s_nat,
                                               const int tile_lo, const int w, const int win_lo, int& n_winmiss) {
@@ -329,11 +288,6 @@ __device__ __forceinline__ void diag_quarters(const DevParams& P, RowRec& my, Un
     int r, hr, a;
     unsigned lim;
     const float* trow;
-    auto init_best = [&]() {
-        b.g = b.o = b.s = IS_INF;
-        b.vg = b.vs = -1;
-        b.vo = 0;
-    };
     /* dwords l15 and 16 + l15 of the record of vB = tile_lo + max(aa, 1) = the staged record of row max(aa, 1) - 1 */
     auto rec_dw = [&](int aa, float& r0, float& r1) {
         const float* pl = s_nat + (max(aa, 1) - 1) * ISF_NAT_STRIDE + l15;
@@ -347,7 +301,7 @@ __device__ __forceinline__ void diag_quarters(const DevParams& P, RowRec& my, Un
         lim = (tile_lo + r < H) ? (unsigned)(hr - 1) : 0u;
         trow = s_tile + r * DPW;
         a = a0 - 4 * entry;
-        init_best();
+        unary_best_init(b);
     };
     /* the partial minima of the lanes `delta` below, which worked for the same rows, merged into the lanes `mine` */
     auto hand_over = [&](const int delta, const bool mine) {
@@ -355,7 +309,7 @@ __device__ __forceinline__ void diag_quarters(const DevParams& P, RowRec& my, Un
         auto one = [&](float& c, int& vb) {
             const float c2 = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src, __builtin_bit_cast(int, c)));
             const int vb2 = __builtin_amdgcn_ds_bpermute(src, vb);
-            const bool take = mine && ((c2 < c) || (c2 == c && vb2 >= 0 && (vb < 0 || vb2 < vb)));
+            const bool take = mine && UNARY_MERGE_WINS(c, vb, c2, vb2);
             c = take ? c2 : c;
             vb = take ? vb2 : vb;
         };
@@ -399,23 +353,7 @@ __device__ __forceinline__ void diag_quarters(const DevParams& P, RowRec& my, Un
             }
             n_winmiss++;
         }
-        const float od = vtv - vbv;
-        const float pwih = P.pw * rh;
-        const float cost_o = P.dw * od + pwih + P.sw * t.seg_o; /* left to right, fast_step */
-        const bool uo = live && (cost_o <= b.o);
-        b.o = uo ? cost_o : b.o;
-        b.vo = uo ? vB : b.vo;
-        if (SKY) {
-            const float cost_s = P.dw * t.sd + pwih + P.sw * t.seg_s;
-            const bool us = live && (cost_s <= b.s);
-            b.s = us ? cost_s : b.s;
-            b.vs = us ? vB : b.vs;
-        } else {
-            const float cost_g = P.dw * t.gd + pwih + P.sw * t.seg_g;
-            const bool ug = live && (cost_g <= b.g);
-            b.g = ug ? cost_g : b.g;
-            b.vg = ug ? vB : b.vg;
-        }
+        unary_update<true, SKY, true, false, false>(P, t, vtv - vbv, P.pw * rh, vB, live, false, b);
         a -= 4;
         R0 = N0;
         R1 = N1;
@@ -547,8 +485,8 @@ __global__ __launch_bounds__(ISF_THREADS, LUTF ? (HAS_INVALID ? ISF_OCC_LUTF_INV
     constexpr int SLOT = ROWF + ISF_REC_F;     /* floats of a ring slot */
     float* s_rcp = (float*)smem;                        /* [H+1 -> x4]                       */
     float* s_tile = s_rcp + ((H + 1 + 3) & ~3);         /* [64][D+1] lutT rows tile_lo+1 ..   */
-    /* (the tile's space also holds the merge area after the walk: at least ISF_MERGE_F floats) */
-    const int merge_f = 2 * nwv * 3 * 64 + 2 * 3 * 64;
+    /* (the tile's space also holds the merge area after the walk) */
+    const int merge_f = UNARY_MERGE_FLOATS(nwv) + UNARY_SLOT_FLOATS;
     const int tile_f = max((IS_TILE * DP + 3) & ~3, merge_f);
     float* s_ring = s_tile + tile_f;                    /* [8 waves][K][SLOT]                */
     float* s_nat = s_ring + (size_t)nwv * K * SLOT;     /* QDIAG: [32][ISF_NAT_STRIDE] the records of the rows 0 .. 31 of the tile */
@@ -673,17 +611,10 @@ next_item: /* (REPAIR: the next (column, tile) item of this workgroup) */
     fwin.misses = &n_winmiss;
     fwin.vT1 = min(vT + 1, H);
 
-    PruneValsF pv;
-    {
-        cprune_t pq = (cprune_t)(prune + colg);
-        pv.E1o = pq->E1o; pv.E1g = pq->E1g; pv.E1s = pq->E1s; pv.E2 = 3.0f * pq->E2;
-        pv.dead = ~__builtin_amdgcn_ballot_w64(row_ok);
-        pv.gdead = pv.dead; /* (completed below, once this lane's record is here) */
-    }
-    UnaryBestF b;
-    b.g = b.o = b.s = IS_INF;
-    b.vg = b.vs = -1;
-    b.vo = 0; /* index_table[vT*3+OBJECT] = OBJECT at vB = 0, :592 */
+    /* (3 E2: seg_o_lower_bound; gdead is completed below, once this lane's record is here) */
+    PruneVals pv = load_prune_vals(prune + colg, 3.0f, row_ok);
+    UnaryBest b;
+    unary_best_init(b);
     const float* my_tile = s_tile + lane * DP;
     const bool nog = tile_lo >= vhor;
     __syncthreads(); /* the tile and the 1/h table: the only data the waves share */
@@ -788,40 +719,10 @@ next_item: /* (REPAIR: the next (column, tile) item of this workgroup) */
      * wave reads the lutT tile any more, so the merge runs in ITS space; the rings may still
      * receive prefetched slots (a wave that left early has up to K fills in flight), and nothing
      * has to wait for them until the very end: the drain hides behind the barrier and the merge
-     * (it used to sit in front of them: an HBM latency per workgroup). */
-    __syncthreads();
-    float* m_cost = s_tile;                              /* [8][3][64] */
-    int* m_vb = (int*)(m_cost + nwv * 3 * 64);           /* [8][3][64] */
-    float* f_cost = m_cost + 2 * nwv * 3 * 64;           /* [3][64] final values */
-    int* f_vb = (int*)(f_cost + 3 * 64);                 /* [3][64] */
-    m_cost[(w * 3 + 0) * 64 + lane] = b.g; m_vb[(w * 3 + 0) * 64 + lane] = b.vg;
-    m_cost[(w * 3 + 1) * 64 + lane] = b.o; m_vb[(w * 3 + 1) * 64 + lane] = b.vo;
-    m_cost[(w * 3 + 2) * 64 + lane] = b.s; m_vb[(w * 3 + 2) * 64 + lane] = b.vs;
-    __syncthreads();
-    if (tid < 3 * 64) {
-        const int type = tid >> 6;
-        float c = m_cost[(0 * 3 + type) * 64 + lane];
-        int vb = m_vb[(0 * 3 + type) * 64 + lane];
-        for (int ww = 1; ww < nwv; ww++) {
-            const float c2 = m_cost[(ww * 3 + type) * 64 + lane];
-            const int vb2 = m_vb[(ww * 3 + type) * 64 + lane];
-            const bool take = (c2 < c) || (c2 == c && vb2 >= 0 && (vb < 0 || vb2 < vb));
-            if (take) { c = c2; vb = vb2; }
-        }
-        /* a row without a finite candidate keeps the initial index (the descending walk records
-         * +inf candidates, the reference's strict < never does; :592 for the object type) */
-        if (!(c < IS_INF)) vb = (type == IS_OBJECT) ? 0 : -1;
-        f_cost[type * 64 + lane] = c;
-        f_vb[type * 64 + lane] = vb;
-    }
-    __syncthreads();
-    if (w == 0 && row_ok) {
-        const size_t o = ((size_t)colg * H + vT) * 3;
-        float* cd = cost_table + o;
-        int32_t* id = index_table + o;
-        cd[0] = f_cost[0 * 64 + lane]; cd[1] = f_cost[1 * 64 + lane]; cd[2] = f_cost[2 * 64 + lane];
-        id[0] = f_vb[0 * 64 + lane]; id[1] = f_vb[1 * 64 + lane]; id[2] = f_vb[2 * 64 + lane];
-    }
+     * (it used to sit in front of them: an HBM latency per workgroup).  UNARY_MERGE_STORE: is_unary.h;
+     * the finals in a slot of their own behind the waves'. */
+    UNARY_MERGE_STORE(s_tile, s_tile + UNARY_MERGE_FLOATS(nwv), b, nwv, w, tid, lane, colg, H, vT, cost_table,
+                      index_table);
     wait_vmcnt<0>(); /* no LDS-DMA may land after the workgroup has gone (its LDS is reassigned) */
     }
 item_done:
@@ -847,7 +748,7 @@ static size_t isf_lds_bytes(const DevParams* P, int nvr, int nwaves, bool window
     size_t tile = ((size_t)IS_TILE * DP + 3) & ~(size_t)3;
     size_t ring = (size_t)nwaves * ISF_RING * ((windowed ? (size_t)IS_P1_WIN : 64 * (size_t)nvr) + ISF_REC_F);
     if (windowed) ring += ISF_NAT_F; /* the records of the rows 0 .. 31 (diag_quarters) */
-    const size_t merge = (size_t)nwaves * 3 * 64 * 2 + 2 * 3 * 64; /* lives in the tile's space */
+    const size_t merge = UNARY_MERGE_FLOATS((size_t)nwaves) + UNARY_SLOT_FLOATS; /* lives in the tile's space */
     if (tile < merge) tile = merge;
     return sizeof(float) * (rcp + tile + ring) + 16;
 }

@@ -1,5 +1,5 @@
 /* is_k_unary_path.hip -- the unary DP along the back-trace's own path.  See is_kernels.h. */
-#include "is_kernels.h"
+#include "is_unary.h"
 
 /* ====================================================================================== */
 /* Unary DP of the visited rows only: one wave per column                                  */
@@ -53,10 +53,6 @@ struct LutCol {
     int* s_my; /* [32]: spread_of_lane */
     int H, D, nb;
 };
-
-__device__ __forceinline__ float read_lane(float v, int l) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
 
 /* Half h of the wave (lanes 32 h .. 32 h + 31) runs LUT block blk of fn (both per half): lane 32 h + p returns
  * lutT[32 blk + p + 1][fn].  object_lut_body's network with lanes = rows -- the reference's own layout
@@ -118,7 +114,7 @@ __device__ __forceinline__ float lut_row_entry(const LutCol& L, int disT, int vT
         const int fb = m != 0ull ? __builtin_amdgcn_readlane(fni, __builtin_ctzll(m)) : fa;
         m &= ~__builtin_amdgcn_ballot_w64(fni == fb);
         const float out = lut_network(L, disT, lane < 32 ? fa : fb, kT, lane);
-        const float va = read_lane(out, pT), vb = read_lane(out, 32 + pT);
+        const float va = readlane_f(out, pT), vb = readlane_f(out, 32 + pT);
         v = fni == fa ? va : (fni == fb ? vb : v);
         if (lane == 0) {
             L.s_tag[fa] = tag; L.s_val[fa] = va;
@@ -132,13 +128,6 @@ struct PathBest {
     float c[3];
     int v[3];
 };
-
-/* the merge of the tile kernels (k_dp_unary, k_dp_unary_fast): min cost, ties -> the smallest recorded vB */
-__device__ __forceinline__ void path_take(float& c, int& v, float c2, int v2) {
-    const bool take = (c2 < c) || (c2 == c && v2 >= 0 && (v < 0 || v2 < v));
-    c = take ? c2 : c;
-    v = take ? v2 : v;
-}
 
 template <bool HAS_INVALID>
 __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* __restrict__ rcol, const LutCol& L,
@@ -187,26 +176,25 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
         const float r = rcp[h]; /* RN(1/h) */
         const SegTerms t = eval_segment<true, HAS_INVALID>(my, rb, (float)h, r, D, P.iw, rcp);
         const float pwih = P.pw * r;
-        /* cost = dw*data + pw*(1/h) + sw*seg, left to right (unary_step) */
         /* (ground and sky, and everything of the bounds but the object type's ballot, in front of the networks:
          * their terms are out of the registers while the passes run) */
         if (vB - 1 >= vhor) {
-            const float cost_s = P.dw * t.sd + pwih + P.sw * t.seg_s;
+            const float cost_s = unary_cost(P, t.sd, pwih, t.seg_s);
             if (open_s && live && cost_s <= bs) { bs = cost_s; vs = vB; }
         } else {
-            const float cost_g = P.dw * t.gd + pwih + P.sw * t.seg_g;
+            const float cost_g = unary_cost(P, t.gd, pwih, t.seg_g);
             if (open_g && live && cost_g <= bg) { bg = cost_g; vg = vB; }
         }
         float lb_o = 0.0f;
         if (prune_on) {
             /* the longest segment of the step: lane 0 (vB = 64 s + 1 <= vT) */
+            /* (the long form on purpose: through readfirstlane_f these reads give the kernel other code) */
             const float f_on = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.f_on)));
             const float f_oi = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.f_oi)));
             const float f_sky = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.f_sky)));
             const float f_g = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.f_g)));
             /* (wave-uniform, and live across the networks: in an SGPR) */
-            lb_o = __int_as_float(__builtin_amdgcn_readfirstlane(
-                __float_as_int(P.sw * __builtin_fminf(f_on, f_oi - pr.E2) - pr.E1o)));
+            lb_o = readfirstlane_f(P.sw * __builtin_fminf(f_on, f_oi - pr.E2) - pr.E1o);
             const float lb_s = P.sw * f_sky - pr.E1s;
             const float lb_g = P.sw * f_g - pr.E1g;
             if (__builtin_amdgcn_ballot_w64(lb_s > bs) != 0ull) open_s = false;
@@ -226,12 +214,12 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
                 const float out = lut_network(L, disS, fn, blk, lane);
                 ent = t.fni == fn ? out : ent;
                 if (keep_row) {
-                    const float v = read_lane(out, lT);
+                    const float v = readlane_f(out, lT);
                     if (lane == 0) { L.s_tag[fn] = vT + 1; L.s_val[fn] = v; }
                 }
             }
             const float od = lut_row_entry(L, disT, vT, t.fni, live, lane) - ent;
-            const float cost_o = P.dw * od + pwih + P.sw * t.seg_o;
+            const float cost_o = unary_cost(P, od, pwih, t.seg_o);
             if (live && cost_o <= bo) { bo = cost_o; vo = vB; }
         }
         if (prune_on) {
@@ -256,10 +244,10 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
         if (open_g) t = eval_segment_gs<IS_WANT_GROUND | IS_WANT_SKY>(my, load_rec_gs<IS_WANT_GROUND | IS_WANT_SKY>(rcol + vBc), P.iw);
         else t = eval_segment_gs<IS_WANT_SKY>(my, load_rec_gs<IS_WANT_SKY>(rcol + vBc), P.iw);
         if (vB - 1 >= vhor) {
-            const float cost_s = P.dw * t.sd + pwih + P.sw * t.seg_s;
+            const float cost_s = unary_cost(P, t.sd, pwih, t.seg_s);
             if (open_s && live && cost_s <= bs) { bs = cost_s; vs = vB; }
         } else if (open_g) {
-            const float cost_g = P.dw * t.gd + pwih + P.sw * t.seg_g;
+            const float cost_g = unary_cost(P, t.gd, pwih, t.seg_g);
             if (live && cost_g <= bg) { bg = cost_g; vg = vB; }
         }
         /* (prune_on holds: only a bound closes the object type) */
@@ -283,15 +271,15 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
             const RowRec rb0 = rec_of_spread(load_rec_spread(rcol, lane)); /* (the block stays in its VGPRs) */
             const SegTerms t0 = eval_segment<true, HAS_INVALID>(my, rb0, (float)h0, r0, D, P.iw, rcp);
             const float od = lut_row_entry(L, disT, vT, t0.fni, lane == 0, lane) - 0.0f; /* lutT[0] = 0 */
-            const float cost_o = P.dw * od + pwih0 + P.sw * t0.seg_o;
+            const float cost_o = unary_cost(P, od, pwih0, t0.seg_o);
             if (lane == 0 && cost_o <= bo) { bo = cost_o; vo = 0; }
             if (open_g) {
-                const float cost_g = P.dw * t0.gd + pwih0 + P.sw * t0.seg_g;
+                const float cost_g = unary_cost(P, t0.gd, pwih0, t0.seg_g);
                 if (lane == 0 && vT <= vhor && cost_g <= bg) { bg = cost_g; vg = 0; }
             }
         } else if (open_g) {
             const SegTerms t0 = eval_segment_gs<IS_WANT_GROUND>(my, load_rec_gs<IS_WANT_GROUND>(rcol), P.iw);
-            const float cost_g = P.dw * t0.gd + pwih0 + P.sw * t0.seg_g;
+            const float cost_g = unary_cost(P, t0.gd, pwih0, t0.seg_g);
             if (lane == 0 && vT <= vhor && cost_g <= bg) { bg = cost_g; vg = 0; }
         }
     }
@@ -302,23 +290,22 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
         const SegTerms t0 = eval_segment<true, HAS_INVALID>(my, rb0, 1.0f, r0, D, P.iw, rcp);
         const float pwih0 = P.pw * r0;
         const float od = lut_row_entry(L, disT, vT, t0.fni, lane == 0, lane) - 0.0f; /* lutT[0] = 0 */
-        const float cost_o = P.dw * od + pwih0 + P.sw * t0.seg_o;
+        const float cost_o = unary_cost(P, od, pwih0, t0.seg_o);
         if (lane == 0 && cost_o <= bo) { bo = cost_o; vo = 0; }
-        const float cost_g = P.dw * t0.gd + pwih0 + P.sw * t0.seg_g;
+        const float cost_g = unary_cost(P, t0.gd, pwih0, t0.seg_g);
         if (open_g && lane == 0 && vT <= vhor && cost_g <= bg) { bg = cost_g; vg = 0; }
     }
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) {
-        path_take(bg, vg, __shfl_xor(bg, m), __shfl_xor(vg, m));
-        path_take(bo, vo, __shfl_xor(bo, m), __shfl_xor(vo, m));
-        path_take(bs, vs, __shfl_xor(bs, m), __shfl_xor(vs, m));
+        unary_merge_take(bg, vg, __shfl_xor(bg, m), __shfl_xor(vg, m));
+        unary_merge_take(bo, vo, __shfl_xor(bo, m), __shfl_xor(vo, m));
+        unary_merge_take(bs, vs, __shfl_xor(bs, m), __shfl_xor(vs, m));
     }
     PathBest b;
     b.c[IS_GROUND] = bg; b.c[IS_OBJECT] = bo; b.c[IS_SKY] = bs;
-    /* a type without a finite candidate keeps the initial index (:592 for the object type) */
-    b.v[IS_GROUND] = (bg < IS_INF) ? vg : -1;
-    b.v[IS_OBJECT] = (bo < IS_INF) ? vo : 0;
-    b.v[IS_SKY] = (bs < IS_INF) ? vs : -1;
+    b.v[IS_GROUND] = unary_final_index(IS_GROUND, bg, vg);
+    b.v[IS_OBJECT] = unary_final_index(IS_OBJECT, bo, vo);
+    b.v[IS_SKY] = unary_final_index(IS_SKY, bs, vs);
     return b;
 #undef IS_MY_REC
 }

@@ -16,6 +16,10 @@
  *                                           independent (column, tile pair) work items, one lane
  *                                           per vT, vB-side operands in SGPRs via scalar loads,
  *                                           vT-side LUT rows in LDS
+ *   is_k_unary_fast.hip k_dp_unary_fast     the FAST columns in the pruned regime: LDS rings, fn windows
+ *   is_k_unary_path.hip k_unary_path        the rows the back-trace visits only
+ *   is_unary.h                              what the three unary kernels share: UnaryBest, PruneVals, the
+ *                                           cost, the update of the bests, the merge, the final index
  *   is_k_pairwise.hip   k_pw_phase1/2       A7-A9 PAIRWISE=true: per 64-row tile, a parallel
  *                                           launch for segments starting in earlier tiles + a
  *                                           one-wave-per-column diagonal walk
@@ -88,6 +92,14 @@ __device__ __forceinline__ float mean_valid_fast(float sdif, float valid_dif, co
     const float rv = rcp_tab[cvt_u32_sat(valid_dif)];
     const float q = fast_div(sdif, valid_dif, rv);
     return (valid_dif == 0) ? 0.0f : q;
+}
+
+/* v_readlane / v_readfirstlane of a float */
+__device__ __forceinline__ float readlane_f(float v, int l) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+__device__ __forceinline__ float readfirstlane_f(float v) {
+    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
 
 /* wave-uniform record through the constant address space: scalar loads, values live in SGPRs */
@@ -635,6 +647,52 @@ __device__ __forceinline__ float seg_o_lower_bound(const SegTerms& t, float E2x3
 /* what a step needs besides the object terms: the ground candidate's, the sky candidate's, both
  * (the first segment of the pairwise model, generic callers) or neither (tiles above the horizon) */
 
+/* The second half of eval_segment_dpp / eval_segment_mix: everything that takes its vB operand from R1 (the sky
+ * minimum, the six moment differences, ic, the seg_* assembly, gd / sd, the mean -> fni), behind class minima
+ * f_g / f_on / f_oi that the caller obtained its own way.  The DPP subtractions are `asm volatile`: their source
+ * order is their issue order. */
+template <bool HAS_INVALID, int WANT>
+__device__ __forceinline__ SegTerms eval_segment_r1(const RowRec& my, const float R1, const float nic, const float f_g,
+                                                    const float f_on, const float f_oi, const float height,
+                                                    const float r, const int D, const float iw, const float* rcp_tab) {
+    SegTerms t;
+    float f_sky = 0.0f;
+    if (WANT & IS_WANT_SKY) f_sky = dpp_sub<2>(my.Fsky, R1);
+    const float meanx = dpp_sub<8>(my.MX, R1);
+    const float meany = dpp_sub<9>(my.MY, R1);
+    const float d_x2h = dpp_sub<10>(my.MX2h, R1);
+    const float d_x2l = dpp_sub<11>(my.MX2l, R1);
+    const float d_y2h = dpp_sub<12>(my.MY2h, R1);
+    const float d_y2l = dpp_sub<13>(my.MY2l, R1);
+    const float meanx2 = d_x2h + d_x2l;
+    const float meany2 = d_y2h + d_y2l;
+    const float ic = iw * (meanx2 - fast_div(meanx * meanx, height, r) + meany2 -
+                           fast_div(meany * meany, height, r));
+    t.f_g = f_g; t.f_on = f_on; t.f_oi = f_oi; t.f_sky = f_sky;
+    t.seg_g = f_g + nic;
+    const float on = nic + f_on;
+    const float oi = ic + f_oi;
+    t.on = on; t.ic = ic;
+    t.seg_o = min_raw(oi, on); /* both finite in a FAST column */
+    t.seg_s = f_sky + nic;
+    t.gd = 0.0f;
+    t.sd = 0.0f;
+    if (WANT & IS_WANT_GROUND) t.gd = dpp_sub<4>(my.G, R1);
+    if (WANT & IS_WANT_SKY) t.sd = dpp_sub<5>(my.K, R1);
+    float mean;
+    if (HAS_INVALID) {
+        const float valid_dif = dpp_sub<7>(my.V, R1);
+        const float sdif = dpp_sub<6>(my.S, R1);
+        if (rcp_tab != nullptr) mean = mean_valid_fast(sdif, valid_dif, rcp_tab);
+        else mean = (valid_dif == 0) ? 0 : sdif / valid_dif;
+    } else {
+        mean = fast_div(dpp_sub<6>(my.S, R1), height, r);
+    }
+    t.fni = (int)min(cvt_u32_sat(mean), (unsigned)(D - 1));
+    t.mean = __builtin_fmaxf(mean, 0.0f);
+    return t;
+}
+
 /* eval_segment<true, HAS_INVALID> (is_kernels.h) with the vB record in (R0, R1): identical
  * operations in identical order, only the source of the vB operand differs.  WANT: which of the
  * ground / sky terms are computed at all -- the DPP instructions are `asm volatile` and would
@@ -642,7 +700,6 @@ __device__ __forceinline__ float seg_o_lower_bound(const SegTerms& t, float E2x3
 template <bool HAS_INVALID, int WANT = IS_WANT_GROUND | IS_WANT_SKY>
 __device__ __forceinline__ SegTerms eval_segment_dpp(const RowRec& my, float R0, float R1, float height,
                                                      float r, int D, float iw, const float* rcp_tab = nullptr) {
-    SegTerms t;
     const float nic = iw * (float)dpp_sub_i_first<3>(my.Fnic, R1);
     float f_g = 0.0f;
     float f_on;
@@ -673,41 +730,7 @@ __device__ __forceinline__ SegTerms eval_segment_dpp(const RowRec& my, float R0,
         f_oi = min3_raw(f_oi, a5, a6);
         f_oi = min_raw(f_oi, dpp_sub<1>(my.Foi[7], R1));
     }
-    float f_sky = 0.0f;
-    if (WANT & IS_WANT_SKY) f_sky = dpp_sub<2>(my.Fsky, R1);
-    const float meanx = dpp_sub<8>(my.MX, R1);
-    const float meany = dpp_sub<9>(my.MY, R1);
-    const float d_x2h = dpp_sub<10>(my.MX2h, R1);
-    const float d_x2l = dpp_sub<11>(my.MX2l, R1);
-    const float d_y2h = dpp_sub<12>(my.MY2h, R1);
-    const float d_y2l = dpp_sub<13>(my.MY2l, R1);
-    const float meanx2 = d_x2h + d_x2l;
-    const float meany2 = d_y2h + d_y2l;
-    const float ic = iw * (meanx2 - fast_div(meanx * meanx, height, r) + meany2 -
-                           fast_div(meany * meany, height, r));
-    t.f_g = f_g; t.f_on = f_on; t.f_oi = f_oi; t.f_sky = f_sky;
-    t.seg_g = f_g + nic;
-    const float on = nic + f_on;
-    const float oi = ic + f_oi;
-    t.on = on; t.ic = ic;
-    t.seg_o = min_raw(oi, on); /* both finite in a FAST column */
-    t.seg_s = f_sky + nic;
-    t.gd = 0.0f;
-    t.sd = 0.0f;
-    if (WANT & IS_WANT_GROUND) t.gd = dpp_sub<4>(my.G, R1);
-    if (WANT & IS_WANT_SKY) t.sd = dpp_sub<5>(my.K, R1);
-    float mean;
-    if (HAS_INVALID) {
-        const float valid_dif = dpp_sub<7>(my.V, R1);
-        const float sdif = dpp_sub<6>(my.S, R1);
-        if (rcp_tab != nullptr) mean = mean_valid_fast(sdif, valid_dif, rcp_tab);
-        else mean = (valid_dif == 0) ? 0 : sdif / valid_dif;
-    } else {
-        mean = fast_div(dpp_sub<6>(my.S, R1), height, r);
-    }
-    t.fni = (int)min(cvt_u32_sat(mean), (unsigned)(D - 1));
-    t.mean = __builtin_fmaxf(mean, 0.0f);
-    return t;
+    return eval_segment_r1<HAS_INVALID, WANT>(my, R1, nic, f_g, f_on, f_oi, height, r, D, iw, rcp_tab);
 }
 
 /* eval_segment_dpp with the FIRST half of the vB record (the 16 class prefixes Fg0, Fg1, Fon[8],
@@ -731,7 +754,6 @@ template <bool HAS_INVALID, int WANT = IS_WANT_GROUND | IS_WANT_SKY>
 __device__ __forceinline__ SegTerms eval_segment_mix(const RowRec& my, const isk_f16v& S, float R1,
                                                      float height, float r, int D, float iw,
                                                      const float* rcp_tab = nullptr) {
-    SegTerms t;
     const float nic = iw * (float)dpp_sub_i_first<3>(my.Fnic, R1);
     float f_g = 0.0f;
     /* the sixteen scalar-operand subtractions as eight v_pk_add_f32 (neg modifiers): -1.5 % */
@@ -760,41 +782,7 @@ __device__ __forceinline__ SegTerms eval_segment_mix(const RowRec& my, const isk
         const float a6 = dpp_sub<0>(my.Foi[6], R1), a7 = dpp_sub<1>(my.Foi[7], R1);
         f_oi = min3_raw(f_oi, a6, a7);
     }
-    float f_sky = 0.0f;
-    if (WANT & IS_WANT_SKY) f_sky = dpp_sub<2>(my.Fsky, R1);
-    const float meanx = dpp_sub<8>(my.MX, R1);
-    const float meany = dpp_sub<9>(my.MY, R1);
-    const float d_x2h = dpp_sub<10>(my.MX2h, R1);
-    const float d_x2l = dpp_sub<11>(my.MX2l, R1);
-    const float d_y2h = dpp_sub<12>(my.MY2h, R1);
-    const float d_y2l = dpp_sub<13>(my.MY2l, R1);
-    const float meanx2 = d_x2h + d_x2l;
-    const float meany2 = d_y2h + d_y2l;
-    const float ic = iw * (meanx2 - fast_div(meanx * meanx, height, r) + meany2 -
-                           fast_div(meany * meany, height, r));
-    t.f_g = f_g; t.f_on = f_on; t.f_oi = f_oi; t.f_sky = f_sky;
-    t.seg_g = f_g + nic;
-    const float on = nic + f_on;
-    const float oi = ic + f_oi;
-    t.on = on; t.ic = ic;
-    t.seg_o = min_raw(oi, on); /* both finite in a FAST column */
-    t.seg_s = f_sky + nic;
-    t.gd = 0.0f;
-    t.sd = 0.0f;
-    if (WANT & IS_WANT_GROUND) t.gd = dpp_sub<4>(my.G, R1);
-    if (WANT & IS_WANT_SKY) t.sd = dpp_sub<5>(my.K, R1);
-    float mean;
-    if (HAS_INVALID) {
-        const float valid_dif = dpp_sub<7>(my.V, R1);
-        const float sdif = dpp_sub<6>(my.S, R1);
-        if (rcp_tab != nullptr) mean = mean_valid_fast(sdif, valid_dif, rcp_tab);
-        else mean = (valid_dif == 0) ? 0 : sdif / valid_dif;
-    } else {
-        mean = fast_div(dpp_sub<6>(my.S, R1), height, r);
-    }
-    t.fni = (int)min(cvt_u32_sat(mean), (unsigned)(D - 1));
-    t.mean = __builtin_fmaxf(mean, 0.0f);
-    return t;
+    return eval_segment_r1<HAS_INVALID, WANT>(my, R1, nic, f_g, f_on, f_oi, height, r, D, iw, rcp_tab);
 }
 
 /* ====================================================================================== */
