@@ -6,9 +6,7 @@
 /* A4-A6  per-column preparation                                                           */
 /* ====================================================================================== */
 #define PREP_THREADS 256
-#ifndef PREP_EPI_ROWS
-#define PREP_EPI_ROWS 256 /* rows per block of the record epilogue */
-#endif
+#define PREP_MAXR 9 /* rows per thread whose fp32 prefixes are held in registers: H + 1 <= 9 * 256 */
 
 /* LDS stride of a segmentation channel: H/8 + 1 prefix entries, rounded up to 16 bytes */
 __host__ __device__ static inline int prep_seg_stride(int H) { return (((H >> 3) + 1) + 3) & ~3; }
@@ -57,6 +55,20 @@ __device__ __forceinline__ int64_t block_excl_scan_i64(int64_t v, int64_t* s_wav
     return base + inc - v;
 }
 
+/* Block totals of N 64-bit values per thread, through s_abs (N <= 4 words that alias s_wave).  Three barriers: the
+ * zeroes, the sums, and the last one frees the words for their next user. */
+template <int N>
+__device__ __forceinline__ void block_sum_u64(unsigned long long (&v)[N], unsigned long long* s_abs) {
+    if (threadIdx.x < N) s_abs[threadIdx.x] = 0ull;
+    __syncthreads();
+#pragma unroll
+    for (int n = 0; n < N; n++) atomicAdd(&s_abs[n], v[n]);
+    __syncthreads();
+#pragma unroll
+    for (int n = 0; n < N; n++) v[n] = s_abs[n];
+    __syncthreads();
+}
+
 /* (sum, min) over the block; s_red holds 8 floats.  Only used for slack bounds (PruneRec), which
  * carry their own safety factor, so the summation order does not matter. */
 __device__ __forceinline__ float2 block_sum_min(float s, float m, float* s_red) {
@@ -98,199 +110,188 @@ __device__ __forceinline__ float data_cost_ground(float fn, float d, float norm_
     return data_cost;
 }
 
-/* full-resolution prefix from the 1/8-resolution exclusive prefix ps (see RowRec) */
-__device__ __forceinline__ int32_t full_prefix(const int32_t* ps, int v) {
-    const int k = v >> 3, m = v & 7;
-    int32_t r = (int32_t)((uint32_t)ps[k] * 8u);
-    if (m) r = (int32_t)((uint32_t)r + (uint32_t)(ps[k + 1] - ps[k]) * (uint32_t)m);
-    return r;
+/* The LDS of a column's workgroup.  Reuse, in the order of prepare_columns_body: `seg` holds the raw channels, then
+ * the offset channels squared in place, then every channel's exclusive prefix in place; `wave` serves block_sum_u64
+ * (as s_abs) and block_excl_scan_i64 in turn; `pyr` is refilled for each of the four fp32 planes. */
+struct PrepLds {
+    float* d;      /* [NP]     disparity column, zero beyond H                        */
+    float* pyr;    /* [2 * NP] scan tree                                              */
+    int32_t* seg;  /* [CH][SS] segmentation channels at 1/8 resolution                */
+    int64_t* wave; /* [4]      wave totals of the int64 scans / s_abs of the block sums */
+    float* red;    /* [8]      block_sum_min                                          */
+    float* tot;    /* [2]      tot[0] = sum mx^2 + my^2 of the column                 */
+};
+#define PREP_LDS_TAIL 192 /* wave + red + tot: 72 bytes, with room to the next 64 */
+__device__ __forceinline__ PrepLds prep_lds(char* smem, int NP, int CH, int SS) {
+    float* d = (float*)smem;
+    int32_t* seg = (int32_t*)(d + 3 * NP);
+    int64_t* wave = (int64_t*)(seg + CH * SS);
+    return {d, d + NP, seg, wave, (float*)(wave + 4), (float*)(wave + 4) + 8};
+}
+extern "C" size_t isk_prepare_lds_bytes(const DevParams* P) {
+    return sizeof(float) * (size_t)prep_scan_leaves(P->H, P->P2) * 3 +
+           sizeof(int32_t) * (size_t)P->CH * prep_seg_stride(P->H) + PREP_LDS_TAIL;
 }
 
-/* one 16-byte piece of a record */
-__device__ __forceinline__ void prep_store16(int4* dst, int4 x) { *dst = x; }
-__device__ __forceinline__ void store_instance_prefix(RowRec* o, int slow, int64_t mx, int64_t my,
-                                                      int64_t mx2, int64_t my2) {
-    /* dwords 24..31 of the record as two 16-byte stores */
-    int4 a, b;
-    if (slow) { /* RowRecWide: four int64 */
-        a = make_int4((int)(uint32_t)mx, (int)(uint32_t)((uint64_t)mx >> 32), (int)(uint32_t)my,
-                      (int)(uint32_t)((uint64_t)my >> 32));
-        b = make_int4((int)(uint32_t)mx2, (int)(uint32_t)((uint64_t)mx2 >> 32), (int)(uint32_t)my2,
-                      (int)(uint32_t)((uint64_t)my2 >> 32));
-    } else { /* exact fp32 encodings, see RowRec */
-        const int64_t lo_mask = ((int64_t)1 << IS_FAST_SPLIT_BITS) - 1;
-        a = make_int4(__float_as_int((float)mx), __float_as_int((float)my),
-                      __float_as_int((float)(mx2 - (mx2 & lo_mask))), __float_as_int((float)(mx2 & lo_mask)));
-        b = make_int4(__float_as_int((float)(my2 - (my2 & lo_mask))), __float_as_int((float)(my2 & lo_mask)),
-                      0, 0);
-    }
-    int4* d = reinterpret_cast<int4*>(o);
-    prep_store16(d + 6, a);
-    prep_store16(d + 7, b);
+/* What the stages of one column share: its shape, which column it is, who owns which rows, where its data lie. */
+struct PrepCol {
+    int H, K, CH;
+    /* LDS stride of a segmentation channel: only its first H/8 + 1 entries matter (an exclusive prefix at index <= H/8
+     * never sees the zero padding up to P2S), and 21 channels of P2S = 256 entries were 21.5 of the kernel's 46 KB of
+     * LDS: with 132 the CU holds four workgroups, not three */
+    int SS;
+    /* The scans run over P2 >= H + 1 zero-padded elements (StixelsKernels.h:73-103).  When H is a power of two (P2 =
+     * 2H) everything a prefix at index <= H needs lies in the LEFT half of that tree: indices < H walk the same nodes
+     * as in a tree over H leaves, and index H is the left child of the root = the root of the H-leaf tree.  The tree is
+     * then built over NP = H leaves: identical sums, half the LDS (12 instead of 24 KB at H = 1024). */
+    int NP, LNP;
+    int colg, img, col, tid;
+    int R, r_lo; /* instance sums: thread t owns rows [t * R, t * R + R) */
+    /* fp32 prefixes: thread t owns rows t + k * PREP_THREADS.  regs: it keeps them in registers (PrepPlanes) and the
+     * records get {G, K, S, V} as ONE 16-byte store per row at the end, block by block (prep_store_records); else each
+     * prefix goes to its record field at once */
+    bool regs;
+    const int32_t* scol; /* [CH][P2S]  its segmentation channels */
+    RowRec* rcol;        /* [H + 1]    its records               */
+};
+__device__ __forceinline__ PrepCol prep_col(const DevParams& P, int colg, const int32_t* seg, RowRec* recs) {
+    PrepCol c;
+    c.H = P.H, c.K = P.K, c.CH = P.CH;
+    c.SS = prep_seg_stride(c.H);
+    c.NP = prep_scan_leaves(c.H, P.P2);
+    c.LNP = (c.NP == P.P2) ? P.log2P2 : P.log2P2 - 1;
+    c.colg = colg, c.img = colg / P.C, c.col = colg % P.C, c.tid = threadIdx.x;
+    c.R = (c.H + PREP_THREADS - 1) / PREP_THREADS, c.r_lo = c.tid * c.R;
+    c.regs = (c.H + 1) <= PREP_MAXR * PREP_THREADS;
+    c.scol = seg + (size_t)colg * c.CH * P.P2S;
+    c.rcol = recs + (size_t)colg * (c.H + 1);
+    return c;
 }
 
-__device__ __forceinline__ void prepare_columns_body(
-    const DevParams& P, const int colg, char* smem, const float* __restrict__ joined,
-    const int32_t* __restrict__ seg, const float* __restrict__ ground /*[img][3][H]*/,
-    const int* __restrict__ vhor_arr, RowRec* __restrict__ recs, int* __restrict__ col_flags,
-    float* __restrict__ sv_arr /* null: a unary call, nothing reads the copies */, PruneRec* __restrict__ prune,
-    int* __restrict__ n_generic, int* __restrict__ path_bad) {
-    const int H = P.H, P2 = P.P2, P2S = P.P2S, CH = P.CH, K = P.K;
-    /* the distrust word of the last call's walk: every wave of a gated k_backtrace reads it, so that launch cannot
-     * clear it; the next call does, in front of its own walk */
-    if (colg == 0 && threadIdx.x == 0) path_bad[0] = 0;
-    if (P.lut_ready != nullptr && threadIdx.x == 0) {
-        P.lut_ready[colg] = 0; /* (the fused LUT units of the DP launch count up) */
-        if (colg == 0 && P.lutf_bad != nullptr) *P.lutf_bad = 0;
-    }
-    /* LDS stride of a segmentation channel: only its first H/8 + 1 entries matter (an exclusive
-     * prefix at index <= H/8 never sees the zero padding up to P2S), and 21 channels of P2S = 256
-     * entries were 21.5 of the kernel's 46 KB of LDS: with 132 the CU holds four workgroups, not three */
-    const int SS = prep_seg_stride(H);
-    /* The scans run over P2 >= H + 1 zero-padded elements (StixelsKernels.h:73-103).  When H is a
-     * power of two (P2 = 2H) everything a prefix at index <= H needs lies in the LEFT half of that
-     * tree: indices < H walk the same nodes as in a tree over H leaves, and index H is the left
-     * child of the root = the root of the H-leaf tree.  The tree is then built over NP = H leaves:
-     * identical sums, half the LDS (12 instead of 24 KB at H = 1024). */
-    const int NP = prep_scan_leaves(H, P2);
-    const int LNP = (NP == P2) ? P.log2P2 : P.log2P2 - 1;
-    float* s_d = (float*)smem;                          /* [NP]   disparity column        */
-    float* s_pyr = s_d + NP;                            /* [2*NP] scan tree                */
-    int32_t* s_seg = (int32_t*)(s_pyr + 2 * NP);        /* [CH][SS]                        */
-    auto prefix_at = [&](int v) -> float { /* exclusive prefix at v <= H */
-        return (v == NP) ? s_pyr[2 * NP - 2] : blelloch_prefix(s_pyr, NP, LNP, v);
-    };
-    int64_t* s_wave = (int64_t*)(s_seg + CH * SS);      /* [4]                             */
-    float* s_red = (float*)(s_wave + 4);                /* [8] block reductions            */
-    float* s_tot = s_red + 8;                           /* [2] sum mx^2 + my^2 of the column */
-
-    const int img = colg / P.C, col = colg % P.C;
-    const int vhor = vhor_arr[img];
-    const float* gfun = ground + (size_t)img * 3 * H;
-    const float* gnorm = gfun + H;
-    const float* gis2 = gnorm + H;
-    const float* dcol = joined + (size_t)colg * H;
-    const int32_t* scol = seg + (size_t)colg * CH * P2S;
-    RowRec* rcol = recs + (size_t)colg * (H + 1);
-    const int tid = threadIdx.x;
-
-    /* column inputs into LDS with 16-byte loads (H is a multiple of 8; the segmentation column is
-     * 16-byte aligned when P2S is a multiple of 4) */
-    {
-        const float4* d4 = reinterpret_cast<const float4*>(dcol);
-        float4* sd4 = reinterpret_cast<float4*>(s_d);
-        for (int i = tid; i < (H >> 2); i += PREP_THREADS) sd4[i] = d4[i];
-        for (int i = H + tid; i < NP; i += PREP_THREADS) s_d[i] = 0.0f;
-        if ((P2S & 3) == 0 && SS <= P2S) {
-            const int4* g4 = reinterpret_cast<const int4*>(scol);
-            int4* s4 = reinterpret_cast<int4*>(s_seg);
-            const int sq = SS >> 2, gq = P2S >> 2;
+/* ---- the column inputs into LDS with 16-byte loads (H is a multiple of 8; the segmentation column is
+ * 16-byte aligned when P2S is a multiple of 4) */
+__device__ __forceinline__ void prep_stage_column(const DevParams& P, const PrepLds& L, const PrepCol& c,
+                                                  const float* __restrict__ joined) {
+    const int H = c.H, SS = c.SS, CH = c.CH, P2S = P.P2S, tid = c.tid;
+    const float4* d4 = reinterpret_cast<const float4*>(joined + (size_t)c.colg * H);
+    float4* sd4 = reinterpret_cast<float4*>(L.d);
+    for (int i = tid; i < (H >> 2); i += PREP_THREADS) sd4[i] = d4[i];
+    for (int i = H + tid; i < c.NP; i += PREP_THREADS) L.d[i] = 0.0f;
+    if ((P2S & 3) == 0 && SS <= P2S) {
+        const int4* g4 = reinterpret_cast<const int4*>(c.scol);
+        int4* s4 = reinterpret_cast<int4*>(L.seg);
+        const int sq = SS >> 2, gq = P2S >> 2;
 #pragma unroll 4
-            for (int i = tid; i < CH * sq; i += PREP_THREADS) {
-                const int c = i / sq, q = i - c * sq;
-                s4[i] = g4[c * gq + q];
-            }
-        } else {
-            for (int i = tid; i < CH * SS; i += PREP_THREADS) {
-                const int c = i / SS, k = i - c * SS;
-                s_seg[i] = k < P2S ? scol[c * P2S + k] : 0;
-            }
+        for (int i = tid; i < CH * sq; i += PREP_THREADS) {
+            const int ch = i / sq, q = i - ch * sq;
+            s4[i] = g4[ch * gq + q];
+        }
+    } else {
+        for (int i = tid; i < CH * SS; i += PREP_THREADS) {
+            const int ch = i / SS, k = i - ch * SS;
+            L.seg[i] = k < P2S ? c.scol[ch * P2S + k] : 0;
         }
     }
-    __syncthreads();
+}
 
-    /* ---- fn windows of the pairwise phase 1 (is_device.h, IS_P1_WIN): per 64-row tile the smallest valid
-     * disparity, rounded down to a multiple of 4 columns (16-byte loads), one below for the rounding of
-     * the prefix sums a mean is computed from */
-    if (IS_P1_WINDOWED(P.D) && P.win_lo != nullptr) {
-        const int lane = tid & 63, wv = tid >> 6;
-        for (int t = wv; t < P.ntiles; t += PREP_THREADS / 64) {
-            const int r = t * 64 + lane;
-            float d = IS_INF, dx = -IS_INF;
-            bool ok = false;
-            if (r < H) {
-                const float x = s_d[r];
-                if (!(P.invalid >= 0 && x == P.invalid) && x == x) { d = dx = x; ok = true; }
-            }
-            const float mine = d;
+/* ---- fn windows of the pairwise phase 1 (is_device.h, IS_P1_WIN): per 64-row tile the smallest valid
+ * disparity, rounded down to a multiple of 4 columns (16-byte loads), one below for the rounding of
+ * the prefix sums a mean is computed from.  Reads L.d. */
+__device__ __forceinline__ void prep_fn_windows(const DevParams& P, const PrepLds& L, const PrepCol& c) {
+    if (!(IS_P1_WINDOWED(P.D) && P.win_lo != nullptr)) return;
+    const int lane = c.tid & 63, wv = c.tid >> 6;
+    for (int t = wv; t < P.ntiles; t += PREP_THREADS / 64) {
+        const int r = t * 64 + lane;
+        float d = IS_INF, dx = -IS_INF;
+        bool ok = false;
+        if (r < c.H) {
+            const float x = L.d[r];
+            if (!(P.invalid >= 0 && x == P.invalid) && x == x) { d = dx = x; ok = true; }
+        }
+        const float mine = d;
 #pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                d = __builtin_fminf(d, __shfl_xor(d, m, 64));
-                dx = __builtin_fmaxf(dx, __shfl_xor(dx, m, 64));
-            }
-            /* three candidates: the contiguous window that starts at the tile's smallest disparity (the segments of
-             * a lane start below its row -- nearer, larger disparities), the contiguous one that ends at its largest,
-             * and the SPLIT one: half A from the smallest disparity on, half B up to the largest -- a tile above the
-             * horizon can hold sky (d ~ 0) AND an object.  Whichever holds most of the tile's rows (ties: contiguous). */
-            constexpr int HW = IS_WIN_HALF;
-            int lo_a = 0, lo_b = 0, hi_b = 0;
-            if (d < IS_INF) {
-                lo_a = (int)__builtin_fminf(__builtin_fmaxf(d, 1.0f), (float)P.D) - 1;
-                lo_b = (int)__builtin_fminf(__builtin_fmaxf(dx, 0.0f), (float)(P.D - 1)) + 2 - IS_P1_WIN;
-                hi_b = (int)__builtin_fminf(__builtin_fmaxf(dx, 0.0f), (float)(P.D - 1)) + 2 - HW;
-            }
-            lo_a = min(max(lo_a, 0) & ~3, P.D - IS_P1_WIN);
-            lo_b = min(max(lo_b, 0) & ~3, P.D - IS_P1_WIN);
-            hi_b = min(max(hi_b, 0) & ~3, P.D - HW);
-            const int w_a = IS_WIN_PACK(lo_a, lo_a + HW), w_b = IS_WIN_PACK(lo_b, lo_b + HW);
-            const int w_s = IS_WIN_PACK(lo_a, max(hi_b, lo_a + HW)); /* (never overlapping halves) */
-            const int fl = (int)__builtin_fminf(__builtin_fmaxf(mine, 0.0f), (float)(P.D - 1));
-            const int n_a = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ok && IS_WIN_FIND(w_a, fl) >= 0));
-            const int n_b = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ok && IS_WIN_FIND(w_b, fl) >= 0));
-            const int n_s = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ok && IS_WIN_FIND(w_s, fl) >= 0));
-            int w_best = n_b > n_a ? w_b : w_a;
-            if (n_s > max(n_a, n_b)) w_best = w_s;
-            if (lane == 0) P.win_lo[(size_t)colg * P.ntiles + t] = w_best;
+        for (int m = 32; m >= 1; m >>= 1) {
+            d = __builtin_fminf(d, __shfl_xor(d, m, 64));
+            dx = __builtin_fmaxf(dx, __shfl_xor(dx, m, 64));
         }
+        /* three candidates: the contiguous window that starts at the tile's smallest disparity (the segments of
+         * a lane start below its row -- nearer, larger disparities), the contiguous one that ends at its largest,
+         * and the SPLIT one: half A from the smallest disparity on, half B up to the largest -- a tile above the
+         * horizon can hold sky (d ~ 0) AND an object.  Whichever holds most of the tile's rows (ties: contiguous). */
+        constexpr int HW = IS_WIN_HALF;
+        int lo_a = 0, lo_b = 0, hi_b = 0;
+        if (d < IS_INF) {
+            lo_a = (int)__builtin_fminf(__builtin_fmaxf(d, 1.0f), (float)P.D) - 1;
+            lo_b = (int)__builtin_fminf(__builtin_fmaxf(dx, 0.0f), (float)(P.D - 1)) + 2 - IS_P1_WIN;
+            hi_b = (int)__builtin_fminf(__builtin_fmaxf(dx, 0.0f), (float)(P.D - 1)) + 2 - HW;
+        }
+        lo_a = min(max(lo_a, 0) & ~3, P.D - IS_P1_WIN);
+        lo_b = min(max(lo_b, 0) & ~3, P.D - IS_P1_WIN);
+        hi_b = min(max(hi_b, 0) & ~3, P.D - HW);
+        const int w_a = IS_WIN_PACK(lo_a, lo_a + HW), w_b = IS_WIN_PACK(lo_b, lo_b + HW);
+        const int w_s = IS_WIN_PACK(lo_a, max(hi_b, lo_a + HW)); /* (never overlapping halves) */
+        const int fl = (int)__builtin_fminf(__builtin_fmaxf(mine, 0.0f), (float)(P.D - 1));
+        const int n_a = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ok && IS_WIN_FIND(w_a, fl) >= 0));
+        const int n_b = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ok && IS_WIN_FIND(w_b, fl) >= 0));
+        const int n_s = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ok && IS_WIN_FIND(w_s, fl) >= 0));
+        int w_best = n_b > n_a ? w_b : w_a;
+        if (n_s > max(n_a, n_b)) w_best = w_s;
+        if (lane == 0) P.win_lo[(size_t)c.colg * P.ntiles + t] = w_best;
     }
+}
 
-    /* ---- instance-centre values per row from the RAW offsets (StixelsKernels.cu:401-409);
-     * thread t owns rows [t*R, t*R+R).  mx = 8*col + 3.5 + offx + 0.5 is an exact integer;
-     * my = trunc(row - offy + 0.5): n for n >= 0, n + 1 for n < 0 (truncation toward zero). */
-    const int R = (H + PREP_THREADS - 1) / PREP_THREADS;
-    const int r_lo = tid * R;
-    const int32_t* offy = s_seg + K * SS;
-    const int32_t* offx = s_seg + (K + 1) * SS;
-    int64_t sum_mx = 0, sum_my = 0, sum_mx2 = 0, sum_my2 = 0;
-    uint64_t abs_mx = 0, abs_my = 0;
-    int slow = 0; /* column needs the generic (int64 / IEEE-division) DP path, see RowRec */
-    for (int r = r_lo; r < r_lo + R && r < H; r++) {
-        const double fx = ((double)(P.column_step * col) + 0.5 * ((double)P.column_step - 1.0)) +
-                          (double)offx[r >> 3] + 0.5;
-        const int64_t mx = (int64_t)fx;
-        const int32_t n32 = (int32_t)((uint32_t)r - (uint32_t)offy[r >> 3]);
-        const int64_t my = (int64_t)((double)n32 + 0.5);
-        abs_mx += (uint64_t)(mx < 0 ? -mx : mx);
-        abs_my += (uint64_t)(my < 0 ? -my : my);
-        const float ad = __builtin_fabsf(s_d[r]);
+/* Running sums of the instance-centre values of a column's rows (StixelsKernels.cu:401-409): the squares in wrapping
+ * 64-bit arithmetic. */
+struct InstSums { int64_t mx, my, mx2, my2; };
+/* The instance centre (mx, my) of row r from the RAW offset values of its 1/8-resolution block, added to s.
+ * mx = 8*col + 3.5 + offx + 0.5 is an exact integer; my = trunc(row - offy + 0.5): n for n >= 0, n + 1 for n < 0
+ * (truncation toward zero). */
+__device__ __forceinline__ void instance_centre_add(const DevParams& P, int col, int r, int32_t offx, int32_t offy,
+                                                    InstSums& s, int64_t& mx, int64_t& my) {
+    const double fx = ((double)(P.column_step * col) + 0.5 * ((double)P.column_step - 1.0)) + (double)offx + 0.5;
+    mx = (int64_t)fx;
+    const int32_t n32 = (int32_t)((uint32_t)r - (uint32_t)offy);
+    my = (int64_t)((double)n32 + 0.5);
+    s.mx += mx;
+    s.my += my;
+    s.mx2 = (int64_t)((uint64_t)s.mx2 + (uint64_t)mx * (uint64_t)mx);
+    s.my2 = (int64_t)((uint64_t)s.my2 + (uint64_t)my * (uint64_t)my);
+}
+
+/* ---- instance sums of this thread's rows and the three checks of the FAST encodings (RowRec).  Returns `slow`, the
+ * same in every thread: the column needs the generic (int64 / IEEE-division) DP path; `base`: the exclusive prefixes of
+ * the four sums at row r_lo; L.tot[0]: the column totals of the squares.  L.wave: block_sum_u64, then the four scans. */
+__device__ __forceinline__ int prep_instance_sums(const DevParams& P, const PrepLds& L, const PrepCol& c,
+                                                  int* __restrict__ col_flags, int* __restrict__ n_generic,
+                                                  InstSums& base) {
+    const int H = c.H, K = c.K, SS = c.SS, tid = c.tid;
+    const int32_t* offy = L.seg + K * SS;
+    const int32_t* offx = L.seg + (K + 1) * SS;
+    InstSums sum = {0, 0, 0, 0};
+    unsigned long long abs_m[2] = {0ull, 0ull};
+    int slow = 0;
+    for (int r = c.r_lo; r < c.r_lo + c.R && r < H; r++) {
+        int64_t mx, my;
+        instance_centre_add(P, c.col, r, offx[r >> 3], offy[r >> 3], sum, mx, my);
+        abs_m[0] += (uint64_t)(mx < 0 ? -mx : mx);
+        abs_m[1] += (uint64_t)(my < 0 ? -my : my);
+        const float ad = __builtin_fabsf(L.d[r]);
         slow |= !((ad == 0.0f) || (ad >= IS_FAST_DISP_MIN && ad <= IS_FAST_DISP_MAX));
-        sum_mx += mx;
-        sum_my += my;
-        sum_mx2 = (int64_t)((uint64_t)sum_mx2 + (uint64_t)mx * (uint64_t)mx);
-        sum_my2 = (int64_t)((uint64_t)sum_my2 + (uint64_t)my * (uint64_t)my);
     }
-    { /* instance centres of a FAST column: sum|mx|, sum|my| < 2^23 (block totals through LDS) */
-        unsigned long long* s_abs = (unsigned long long*)s_wave;
-        if (tid < 2) s_abs[tid] = 0ull;
-        __syncthreads();
-        atomicAdd(&s_abs[0], (unsigned long long)abs_mx);
-        atomicAdd(&s_abs[1], (unsigned long long)abs_my);
-        __syncthreads();
-        slow |= (s_abs[0] >= (unsigned long long)IS_FAST_INSTANCE_LIMIT) |
-                (s_abs[1] >= (unsigned long long)IS_FAST_INSTANCE_LIMIT);
-        __syncthreads(); /* s_wave is reused by the scans below */
-    }
-    { /* class channels of a FAST column: values >= 0, full-resolution total < 2^24.  One wave per
-       * channel (round robin), a lane sums every 64th entry, the wave adds the lane sums (the
-       * nineteen channels used to be walked by nineteen lanes of wave 0: 132 serial iterations
-       * with an integer modulo each, a tenth of the workgroup's life) */
+    /* instance centres of a FAST column: sum|mx|, sum|my| < 2^23 */
+    block_sum_u64(abs_m, (unsigned long long*)L.wave);
+    slow |= (abs_m[0] >= (unsigned long long)IS_FAST_INSTANCE_LIMIT) |
+            (abs_m[1] >= (unsigned long long)IS_FAST_INSTANCE_LIMIT);
+    { /* class channels of a FAST column: values >= 0, full-resolution total < 2^24.  One wave per channel (round
+       * robin), a lane sums every 64th entry, the wave adds the lane sums (the nineteen channels used to be walked by
+       * nineteen lanes of wave 0: 132 serial iterations with an integer modulo each, a tenth of the workgroup's life) */
         const int lane = tid & 63, wv = tid >> 6;
-        for (int c = wv; c < K; c += PREP_THREADS / 64) {
-            const int32_t* ch = s_seg + c * SS;
+        for (int ch = wv; ch < K; ch += PREP_THREADS / 64) {
+            const int32_t* p = L.seg + ch * SS;
             uint64_t total = 0;
             int negative = 0;
             for (int k = lane; k < SS; k += 64) {
-                const int32_t x = ch[k];
+                const int32_t x = p[k];
                 negative |= (x < 0);
                 total += (uint64_t)(uint32_t)x;
             }
@@ -304,175 +305,108 @@ __device__ __forceinline__ void prepare_columns_body(
     }
     slow = __syncthreads_or(slow);
     if (tid == 0) {
-        col_flags[colg] = slow;
+        col_flags[c.colg] = slow;
         if (slow) atomicAdd(n_generic, 1); /* (zeroed by the caller before the launch) */
     }
-    int64_t base_mx = block_excl_scan_i64(sum_mx, s_wave);
-    int64_t base_my = block_excl_scan_i64(sum_my, s_wave);
-    int64_t base_mx2 = block_excl_scan_i64(sum_mx2, s_wave);
-    int64_t base_my2 = block_excl_scan_i64(sum_my2, s_wave);
-    /* the owner of rows [r_lo, r_lo+R) writes the exclusive prefix at those indices; the owner
-     * of row H-1 also writes index H (the total).  Every piece of a 128-byte record
-     * (instance prefixes, class chunks, the four fp32 prefixes) is stored at the END of the kernel,
-     * back to back, so that the pieces of a line meet in the L2 instead of reaching the memory as
-     * eight partial writes spread over the workgroup's life. */
-    /* (the raw offsets from the input tensor: the LDS copies are squared in place further down) */
-    auto offx_raw = [&](int i) -> int32_t { return scol[(K + 1) * P2S + i]; };
-    auto offy_raw = [&](int i) -> int32_t { return scol[K * P2S + i]; };
-    /* (dst_row(r): where the record of row r goes) */
-    auto instance_rows = [&](bool store, auto dst_row) {
-        int64_t bx = base_mx, by = base_my, bx2 = base_mx2, by2 = base_my2;
-        for (int r = r_lo; r < r_lo + R && r < H; r++) {
-            if (store) store_instance_prefix(dst_row(r), slow, bx, by, bx2, by2);
-            const double fx = ((double)(P.column_step * col) + 0.5 * ((double)P.column_step - 1.0)) +
-                              (double)offx_raw(r >> 3) + 0.5;
-            const int64_t mx = (int64_t)fx;
-            const int32_t n32 = (int32_t)((uint32_t)r - (uint32_t)offy_raw(r >> 3));
-            const int64_t my = (int64_t)((double)n32 + 0.5);
-            bx += mx;
-            by += my;
-            bx2 = (int64_t)((uint64_t)bx2 + (uint64_t)mx * (uint64_t)mx);
-            by2 = (int64_t)((uint64_t)by2 + (uint64_t)my * (uint64_t)my);
-        }
-        if (r_lo <= H - 1 && H - 1 < r_lo + R) {
-            if (store) store_instance_prefix(dst_row(H), slow, bx, by, bx2, by2);
-            s_tot[0] = (float)((double)bx2 + (double)by2); /* column totals (PruneRec.E2) */
-        }
-    };
-    auto rec_row = [&](int r) -> RowRec* { return rcol + r; };
-    /* (the records are stored in the epilogue; here only the column totals are needed, and the owner of row
-     * H - 1 has them: its exclusive prefix + its own rows -- the integers instance_rows will end with) */
-    if (r_lo <= H - 1 && H - 1 < r_lo + R)
-        s_tot[0] = (float)((double)(int64_t)((uint64_t)base_mx2 + (uint64_t)sum_mx2) +
-                           (double)(int64_t)((uint64_t)base_my2 + (uint64_t)sum_my2));
-    __syncthreads();
+    base.mx = block_excl_scan_i64(sum.mx, L.wave);
+    base.my = block_excl_scan_i64(sum.my, L.wave);
+    base.mx2 = block_excl_scan_i64(sum.mx2, L.wave);
+    base.my2 = block_excl_scan_i64(sum.my2, L.wave);
+    /* the column totals (PruneRec.E2): the owner of row H - 1 has them, its exclusive prefix + its own rows -- the
+     * integers prep_store_instance_rows will end with */
+    if (c.r_lo <= H - 1 && H - 1 < c.r_lo + c.R)
+        L.tot[0] = (float)((double)(int64_t)((uint64_t)base.mx2 + (uint64_t)sum.mx2) +
+                           (double)(int64_t)((uint64_t)base.my2 + (uint64_t)sum.my2));
+    return slow;
+}
 
-    /* ---- square the offset channels in place (StixelsKernels.cu:411-416), then exclusive
-     * prefix of every channel at 1/8 resolution (:462-469); integer, so any order is exact */
-    for (int i = tid; i < 2 * SS; i += PREP_THREADS) {
-        const uint32_t x = (uint32_t)s_seg[K * SS + i];
-        s_seg[K * SS + i] = (int32_t)(x * x);
+/* ---- square the offset channels of L.seg in place (StixelsKernels.cu:411-416).  Returns nic_bad, the same in every
+ * thread: the branch-and-bound precondition fails.  The non-instance offset term is >= 0 and monotone when no
+ * squared entry is negative as int32 (the reference squares in wrapping int32) and the full-resolution total stays
+ * below 2^31.  L.wave: block_sum_u64. */
+__device__ __forceinline__ int prep_square_offsets(const PrepLds& L, const PrepCol& c) {
+    int32_t* off = L.seg + c.K * c.SS; /* offy, then offx */
+    for (int i = c.tid; i < 2 * c.SS; i += PREP_THREADS) {
+        const uint32_t x = (uint32_t)off[i];
+        off[i] = (int32_t)(x * x);
     }
     __syncthreads();
-    /* branch-and-bound precondition: the non-instance offset term is >= 0 and monotone when no
-     * squared entry is negative as int32 (the reference squares in wrapping int32) and the
-     * full-resolution total stays below 2^31 */
     int nic_bad = 0;
-    {
-        unsigned long long sq_sum = 0;
-        for (int i = tid; i < 2 * SS; i += PREP_THREADS) {
-            const int32_t v = s_seg[K * SS + i];
-            nic_bad |= v < 0;
-            sq_sum += (unsigned long long)(uint32_t)v;
-        }
-        unsigned long long* s_abs = (unsigned long long*)s_wave;
-        if (tid == 0) s_abs[0] = 0ull;
-        __syncthreads();
-        atomicAdd(&s_abs[0], sq_sum);
-        __syncthreads();
-        nic_bad |= (s_abs[0] * IS_DOWNSAMPLE_FACTOR) >= (1ull << 31);
-        __syncthreads();
+    unsigned long long sq_sum[1] = {0ull};
+    for (int i = c.tid; i < 2 * c.SS; i += PREP_THREADS) {
+        const int32_t v = off[i];
+        nic_bad |= v < 0;
+        sq_sum[0] += (unsigned long long)(uint32_t)v;
     }
-    nic_bad = __syncthreads_or(nic_bad);
-    /* one wave per channel (round robin): lane l owns `per` consecutive entries of the SS */
-    {
-        const int lane = tid & 63, wv = tid >> 6, per = (SS + 63) >> 6;
-        for (int c = wv; c < CH; c += PREP_THREADS / 64) {
-            int32_t* ch = s_seg + c * SS;
-            uint32_t local = 0;
-            for (int k = 0; k < per; k++) {
-                const int idx = lane * per + k;
-                if (idx < SS) local += (uint32_t)ch[idx];
-            }
-            uint32_t inc = local; /* inclusive wave scan of the lane totals */
-#pragma unroll
-            for (int j = 1; j < 64; j <<= 1) {
-                const uint32_t n = (uint32_t)__shfl_up((int)inc, j, 64);
-                if (lane >= j) inc += n;
-            }
-            uint32_t run = inc - local;
-            for (int k = 0; k < per; k++) {
-                const int idx = lane * per + k;
-                if (idx < SS) {
-                    const uint32_t x = (uint32_t)ch[idx];
-                    ch[idx] = (int32_t)run;
-                    run += x;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    /* one (1/8-resolution block kb, chunk q) item of the class prefixes: emit(v, q, chunk) for its rows */
-    auto class_item = [&](int kb, int q, auto emit) {
-        const int kn = min(kb + 1, SS - 1); /* (the last block has one row: its increment is never used) */
-        uint32_t cur[4], dif[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int dw = q * 4 + j; /* dword of RowRec: Fg0 Fg1 Fon[8] Foi[8] Fsky Fnic */
-            if (dw == 19) {
-                const int32_t* px = s_seg + (K + 1) * SS;
-                const int32_t* py = s_seg + K * SS;
-                const uint32_t ax = (uint32_t)px[kb], ay = (uint32_t)py[kb];
-                cur[j] = ax * 8u + ay * 8u;
-                dif[j] = ((uint32_t)px[kn] - ax) + ((uint32_t)py[kn] - ay);
-            } else {
-                const int chn = dw < 10 ? dw : (dw < 18 ? dw + 1 : 10);
-                const int32_t* ps = s_seg + chn * SS;
-                const uint32_t a = (uint32_t)ps[kb];
-                cur[j] = a * 8u;
-                dif[j] = (uint32_t)ps[kn] - a;
-            }
-        }
-        const bool is_count = (q == 4); /* dword 19 (Fnic) stays an integer in both encodings */
-#pragma unroll
-        for (int m = 0; m < 8; m++) {
-            const int v = kb * 8 + m;
-            if (v <= H) {
-                int32_t x[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const int32_t f = (int32_t)cur[j];
-                    x[j] = (slow || (is_count && j == 3)) ? f : __float_as_int((float)f);
-                    cur[j] += dif[j];
-                }
-                emit(v, q, make_int4(x[0], x[1], x[2], x[3]));
-            }
-        }
-    };
-    auto class_chunks = [&]() {
-    /* dwords 0..19 of every record (class prefixes + squared-offset prefix) as five 16-byte
-     * chunks.  A thread owns one chunk of the EIGHT rows of a 1/8-resolution block: the full-resolution
-     * prefix at row 8 kb + m is ps[kb] * 8 + (ps[kb + 1] - ps[kb]) * m (full_prefix, wrapping
-     * uint32 arithmetic), so the two table entries are read once per block and the rows follow by
-     * repeated addition -- an eighth of the LDS reads and a fifth of the instructions of one
-     * (row, chunk) item per thread. */
-    {
-        const int NB = (H >> 3) + 1; /* blocks; the last one holds row H only */
-        for (int it = tid; it < NB * 5; it += PREP_THREADS) {
-            const int kb = it / 5, q = it - kb * 5;
-            class_item(kb, q, [&](int v, int qq, int4 x) {
-                prep_store16(reinterpret_cast<int4*>(rcol + v) + qq, x);
-            });
-        }
-    }
-    };
+    block_sum_u64(sq_sum, (unsigned long long*)L.wave);
+    nic_bad |= (sq_sum[0] * IS_DOWNSAMPLE_FACTOR) >= (1ull << 31);
+    return __syncthreads_or(nic_bad);
+}
 
-    /* ---- fp32 prefixes with the reference's block-scan association (:452-461).  A thread keeps
-     * the four prefixes of its rows (v = tid + k * PREP_THREADS) and writes dwords 20..23 of the
-     * record {G, K, S, V} as ONE 16-byte store per row at the end. */
-    constexpr int MAXR = 9; /* rows per thread held in registers: H + 1 <= 9 * 256 */
-    const bool regs = (H + 1) <= MAXR * PREP_THREADS;
-    const bool epi = regs && R > 0 && (PREP_EPI_ROWS % (R > 0 ? R : 1)) == 0;
-    float pS[MAXR], pV[MAXR], pG[MAXR], pK[MAXR];
+/* ---- every channel of L.seg becomes its exclusive prefix at 1/8 resolution, in place (:462-469); integer, so any
+ * order is exact.  One wave per channel (round robin): lane l owns `per` consecutive entries of the SS */
+__device__ __forceinline__ void prep_class_prefixes(const PrepLds& L, const PrepCol& c) {
+    const int SS = c.SS, lane = c.tid & 63, wv = c.tid >> 6, per = (SS + 63) >> 6;
+    for (int chn = wv; chn < c.CH; chn += PREP_THREADS / 64) {
+        int32_t* ch = L.seg + chn * SS;
+        uint32_t local = 0;
+        for (int k = 0; k < per; k++) {
+            const int idx = lane * per + k;
+            if (idx < SS) local += (uint32_t)ch[idx];
+        }
+        uint32_t inc = local; /* inclusive wave scan of the lane totals */
 #pragma unroll
-    for (int k = 0; k < MAXR; k++) pS[k] = pV[k] = pG[k] = pK[k] = 0.0f;
-    /* compact copies for the pairwise phase 2 */
-    float* svcol = sv_arr != nullptr ? sv_arr + (size_t)colg * 2 * (H + 1) : nullptr;
-    /* S: disparity (valid-masked when invalid >= 0, :382-389) */
-    for (int i = tid; i < NP; i += PREP_THREADS) {
+        for (int j = 1; j < 64; j <<= 1) {
+            const uint32_t n = (uint32_t)__shfl_up((int)inc, j, 64);
+            if (lane >= j) inc += n;
+        }
+        uint32_t run = inc - local;
+        for (int k = 0; k < per; k++) {
+            const int idx = lane * per + k;
+            if (idx < SS) {
+                const uint32_t x = (uint32_t)ch[idx];
+                ch[idx] = (int32_t)run;
+                run += x;
+            }
+        }
+    }
+}
+
+/* ---- fp32 prefixes with the reference's block-scan association (:452-461): the four planes of a column.  A call
+ * site fills L.pyr with the plane's NP values; prep_scan_plane syncs, builds the tree and delivers the prefixes of this
+ * thread's rows v = tid + k * PREP_THREADS <= H: into p[k] (c.regs), else into the record field `field`; and into
+ * copy[v] where a compact copy is wanted (the S / V copies of the pairwise phase 2).  The caller puts a barrier in
+ * front of the next fill. */
+struct PrepPlanes { float G[PREP_MAXR], K[PREP_MAXR], S[PREP_MAXR], V[PREP_MAXR]; }; /* this thread's prefixes */
+__device__ __forceinline__ void prep_scan_plane(const PrepLds& L, const PrepCol& c, float (&p)[PREP_MAXR],
+                                                float RowRec::*field, float* __restrict__ copy) {
+    const int NP = c.NP, LNP = c.LNP, H = c.H;
+    __syncthreads();
+    blelloch_build(L.pyr, NP, LNP);
+    auto prefix_at = [&](int v) -> float { /* exclusive prefix at v <= H */
+        return (v == NP) ? L.pyr[2 * NP - 2] : blelloch_prefix(L.pyr, NP, LNP, v);
+    };
+    if (c.regs) {
+#pragma unroll
+        for (int k = 0; k < PREP_MAXR; k++) {
+            const int v = c.tid + k * PREP_THREADS;
+            if (v <= H) { p[k] = prefix_at(v); if (copy) copy[v] = p[k]; }
+        }
+    } else {
+        for (int v = c.tid; v <= H; v += PREP_THREADS) {
+            const float x = prefix_at(v);
+            c.rcol[v].*field = x;
+            if (copy) copy[v] = x;
+        }
+    }
+}
+
+/* S: disparity (valid-masked when invalid >= 0, :382-389) */
+__device__ __forceinline__ void prep_fill_S(const DevParams& P, const PrepLds& L, const PrepCol& c) {
+    for (int i = c.tid; i < c.NP; i += PREP_THREADS) {
         float x = 0.0f;
-        if (i < H) {
-            const float d = s_d[i];
+        if (i < c.H) {
+            const float d = L.d[i];
             if (P.invalid >= 0) {
                 const int va = d != P.invalid;
                 x = ((float)va) * d;
@@ -480,178 +414,251 @@ __device__ __forceinline__ void prepare_columns_body(
                 x = d;
             }
         }
-        s_pyr[i] = x;
+        L.pyr[i] = x;
     }
-    __syncthreads();
-    blelloch_build(s_pyr, NP, LNP);
-    if (regs) {
-#pragma unroll
-        for (int k = 0; k < MAXR; k++) {
-            const int v = tid + k * PREP_THREADS;
-            if (v <= H) { pS[k] = prefix_at(v); if (svcol) svcol[v] = pS[k]; }
+}
+/* V: valid count (only with an invalid-disparity value) */
+__device__ __forceinline__ void prep_fill_V(const DevParams& P, const PrepLds& L, const PrepCol& c) {
+    for (int i = c.tid; i < c.NP; i += PREP_THREADS) L.pyr[i] = (i < c.H) ? (float)(L.d[i] != P.invalid) : 0.0f;
+}
+/* G: ground data cost, +inf at / above the horizon (:435-446).  Returns (sum |x|, min x) over the finite rows: the
+ * slack of the ground data term */
+__device__ __forceinline__ float2 prep_fill_G(const DevParams& P, const PrepLds& L, const PrepCol& c,
+                                              const float* __restrict__ ground /*[img][3][H]*/, int vhor) {
+    const float* gfun = ground + (size_t)c.img * 3 * c.H;
+    const float* gnorm = gfun + c.H;
+    const float* gis2 = gnorm + c.H;
+    float g_abs = 0.0f, g_min = 0.0f;
+    for (int i = c.tid; i < c.NP; i += PREP_THREADS) {
+        float x = 0.0f;
+        if (i < c.H) {
+            x = (i >= vhor) ? IS_INF : data_cost_ground(gfun[i], L.d[i], gnorm[i], gis2[i], P);
+            if (i < vhor) { g_abs += __builtin_fabsf(x); g_min = __builtin_fminf(g_min, x); }
         }
-    } else {
-        for (int v = tid; v <= H; v += PREP_THREADS) {
-            const float x = prefix_at(v);
-            rcol[v].S = x;
-            if (svcol) svcol[v] = x;
-        }
+        L.pyr[i] = x;
     }
-    __syncthreads();
-    /* V: valid count (all zero without an invalid-disparity value: no scan needed) */
-    if (P.invalid >= 0) {
-        for (int i = tid; i < NP; i += PREP_THREADS)
-            s_pyr[i] = (i < H) ? (float)(s_d[i] != P.invalid) : 0.0f;
-        __syncthreads();
-        blelloch_build(s_pyr, NP, LNP);
-        if (regs) {
+    return block_sum_min(g_abs, g_min, L.red);
+}
+/* K: sky data cost, 0 below the horizon (:424-433).  Returns (sum |x|, min x) */
+__device__ __forceinline__ float2 prep_fill_K(const DevParams& P, const PrepLds& L, const PrepCol& c, int vhor) {
+    float k_abs = 0.0f, k_min = 0.0f;
+    for (int i = c.tid; i < c.NP; i += PREP_THREADS) {
+        float x = 0.0f;
+        if (i < c.H) x = (i < vhor) ? 0.0f : data_cost_sky(L.d[i], P);
+        k_abs += __builtin_fabsf(x);
+        k_min = __builtin_fminf(k_min, x);
+        L.pyr[i] = x;
+    }
+    return block_sum_min(k_abs, k_min, L.red);
+}
+
+/* ---- PruneRec of the column (thread 0): see is_device.h.  A prefix difference P[a] - P[b] of per-row values x >= -nu
+ * with sum|x| = T is >= -(nu * H + gamma2 * T); NaN anywhere makes the slack NaN, and a NaN slack makes every bound
+ * NaN, which never passes the `>` test: no pruning.  Reads L.tot[0]. */
+__device__ __forceinline__ void prep_prune_rec(const DevParams& P, const PrepLds& L, const PrepCol& c, float2 g_red,
+                                               float2 k_red, int slow, int nic_bad, PruneRec* __restrict__ prune) {
+    if (c.tid != 0) return;
+    const float safe = 1.0f + 0x1p-10f;
+    const float hf = (float)c.H;
+    const float sig_g = ((0.0f - g_red.y) * hf + P.gamma2 * g_red.x) * safe;
+    const float sig_k = ((0.0f - k_red.y) * hf + P.gamma2 * k_red.x) * safe;
+    PruneRec pr;
+    pr.E1o = P.dw * P.sigma_od;
+    pr.E1g = P.dw * sig_g;
+    pr.E1s = P.dw * sig_k;
+    pr.E2 = P.iw * (0x1p-21f * safe) * L.tot[0]; /* 8 * 2^-24 * (sum mx^2 + sum my^2) */
+    /* 0 * inf above would be NaN = off as well; make the "off" states explicit */
+    if (slow || nic_bad || !(P.sigma_od < IS_INF) || !(pr.E1g < IS_INF) || !(pr.E1s < IS_INF) ||
+        !(pr.E2 < IS_INF))
+        pr.E1o = pr.E1g = pr.E1s = IS_INF; /* every type: the bounds are tested one by one */
+    pr.pad[0] = pr.pad[1] = pr.pad[2] = pr.pad[3] = 0.0f;
+    prune[c.colg] = pr;
+}
+
+/* ---- the pieces of a 128-byte record, each a 16-byte store: dwords 0..19 the class chunks, 20..23 {G, K, S, V},
+ * 24..31 the instance prefixes */
+__device__ __forceinline__ void store_gksv(RowRec* o, float g, float k, float s, float v) {
+    reinterpret_cast<int4*>(o)[5] = make_int4(__float_as_int(g), __float_as_int(k), __float_as_int(s), __float_as_int(v));
+}
+__device__ __forceinline__ void store_instance_prefix(RowRec* o, int slow, const InstSums& s) {
+    int4 a, b;
+    if (slow) { /* RowRecWide: four int64 */
+        a = make_int4((int)(uint32_t)s.mx, (int)(uint32_t)((uint64_t)s.mx >> 32), (int)(uint32_t)s.my,
+                      (int)(uint32_t)((uint64_t)s.my >> 32));
+        b = make_int4((int)(uint32_t)s.mx2, (int)(uint32_t)((uint64_t)s.mx2 >> 32), (int)(uint32_t)s.my2,
+                      (int)(uint32_t)((uint64_t)s.my2 >> 32));
+    } else { /* exact fp32 encodings, see RowRec */
+        const int64_t lo_mask = ((int64_t)1 << IS_FAST_SPLIT_BITS) - 1;
+        a = make_int4(__float_as_int((float)s.mx), __float_as_int((float)s.my),
+                      __float_as_int((float)(s.mx2 - (s.mx2 & lo_mask))), __float_as_int((float)(s.mx2 & lo_mask)));
+        b = make_int4(__float_as_int((float)(s.my2 - (s.my2 & lo_mask))), __float_as_int((float)(s.my2 & lo_mask)),
+                      0, 0);
+    }
+    int4* d = reinterpret_cast<int4*>(o);
+    d[6] = a;
+    d[7] = b;
+}
+/* The instance prefixes of this thread's rows [r_lo, r_lo + R): the exclusive prefix at those indices; the owner of
+ * row H - 1 also writes index H (the total).  (The raw offsets from the input tensor: the LDS copies have been squared
+ * in place.) */
+__device__ __forceinline__ void prep_store_instance_rows(const DevParams& P, const PrepCol& c, int slow,
+                                                         const InstSums& base) {
+    const int H = c.H;
+    const int32_t* offy = c.scol + c.K * P.P2S;
+    const int32_t* offx = c.scol + (c.K + 1) * P.P2S;
+    InstSums b = base;
+    for (int r = c.r_lo; r < c.r_lo + c.R && r < H; r++) {
+        store_instance_prefix(c.rcol + r, slow, b);
+        int64_t mx, my;
+        instance_centre_add(P, c.col, r, offx[r >> 3], offy[r >> 3], b, mx, my);
+    }
+    if (c.r_lo <= H - 1 && H - 1 < c.r_lo + c.R) store_instance_prefix(c.rcol + H, slow, b);
+}
+/* Chunk q (0..4) of dwords 0..19 (class prefixes + squared-offset prefix) of the EIGHT rows of the 1/8-resolution
+ * block kb: the full-resolution prefix at row 8 kb + m is ps[kb] * 8 + (ps[kb + 1] - ps[kb]) * m in wrapping uint32
+ * arithmetic, so the two table entries are read once per block and the rows follow by repeated addition -- an eighth of
+ * the LDS reads and a fifth of the instructions of one (row, chunk) item per thread. */
+__device__ __forceinline__ void prep_store_class_item(const PrepLds& L, const PrepCol& c, int slow, int kb, int q) {
+    const int SS = c.SS, K = c.K;
+    const int kn = min(kb + 1, SS - 1); /* (the last block has one row: its increment is never used) */
+    uint32_t cur[4], dif[4];
 #pragma unroll
-            for (int k = 0; k < MAXR; k++) {
-                const int v = tid + k * PREP_THREADS;
-                if (v <= H) { pV[k] = prefix_at(v); if (svcol) svcol[H + 1 + v] = pV[k]; }
-            }
+    for (int j = 0; j < 4; j++) {
+        const int dw = q * 4 + j; /* dword of RowRec: Fg0 Fg1 Fon[8] Foi[8] Fsky Fnic */
+        if (dw == 19) {
+            const int32_t* px = L.seg + (K + 1) * SS;
+            const int32_t* py = L.seg + K * SS;
+            const uint32_t ax = (uint32_t)px[kb], ay = (uint32_t)py[kb];
+            cur[j] = ax * 8u + ay * 8u;
+            dif[j] = ((uint32_t)px[kn] - ax) + ((uint32_t)py[kn] - ay);
         } else {
-            for (int v = tid; v <= H; v += PREP_THREADS) {
-                const float x = prefix_at(v);
-                rcol[v].V = x;
-                if (svcol) svcol[H + 1 + v] = x;
+            const int chn = dw < 10 ? dw : (dw < 18 ? dw + 1 : 10);
+            const int32_t* ps = L.seg + chn * SS;
+            const uint32_t a = (uint32_t)ps[kb];
+            cur[j] = a * 8u;
+            dif[j] = (uint32_t)ps[kn] - a;
+        }
+    }
+    const bool is_count = (q == 4); /* dword 19 (Fnic) stays an integer in both encodings */
+#pragma unroll
+    for (int m = 0; m < 8; m++) {
+        const int v = kb * 8 + m;
+        if (v <= c.H) {
+            int32_t x[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int32_t f = (int32_t)cur[j];
+                x[j] = (slow || (is_count && j == 3)) ? f : __float_as_int((float)f);
+                cur[j] += dif[j];
+            }
+            reinterpret_cast<int4*>(c.rcol + v)[q] = make_int4(x[0], x[1], x[2], x[3]);
+        }
+    }
+}
+
+/* ---- every piece of a 128-byte record that is still in registers or LDS (instance prefixes, class chunks, with c.regs
+ * the four fp32 prefixes) is stored at the END of the kernel, back to back, so that the pieces of a line meet in the L2
+ * instead of reaching the memory as eight partial writes spread over the workgroup's life.  (round 4, measured and
+ * removed: the records staged 64 rows at a time in LDS and stored as whole 128-byte lines, eight lanes per record -- 1.53
+ * instead of 1.21 ms for the column blocks of a batch of 64: the 34 extra barriers cost more than the partial lines do;
+ * the kernel is bound by its LDS / VALU work, not by its 2.15 GB of stores) */
+__device__ __forceinline__ void prep_store_records(const DevParams& P, const PrepLds& L, const PrepCol& c, int slow,
+                                                   const InstSums& base, const PrepPlanes& pl) {
+    const int H = c.H, tid = c.tid;
+    if (c.regs) {
+        /* The epilogue walks the column in blocks of PREP_THREADS rows, one row per thread (slot k of PrepPlanes is row
+         * k * PREP_THREADS + tid), and every producer stores its pieces of the block's records before anyone goes on
+         * to the next block -- no barrier, the waves only have to stay roughly together: the partial lines a workgroup
+         * has in flight are 256 x 128 bytes instead of the whole column's 131 KB (x 128 workgroups per XCD: 16.8 MB
+         * against 4 MB of L2 -- lines left the L2 before their last piece arrived). */
+        static_assert(PREP_THREADS % 64 == 0, "a block of the epilogue: one row per thread, whole waves");
+#pragma unroll
+        for (int k = 0; k < PREP_MAXR; k++) {
+            const int row0 = k * PREP_THREADS;
+            if (row0 <= H) {
+                const int v = row0 + tid;
+                if (v <= H) store_gksv(c.rcol + v, pl.G[k], pl.K[k], pl.S[k], pl.V[k]);
+                /* the class chunks of a wave's OWN 64 rows (the rows whose {G, K, S, V} it has just stored):
+                 * lanes 0..39 = 8 blocks x 5 chunks.  Measured against a block-strided loop over the block's items:
+                 * column blocks 1.04 -> 0.95 ms, fused launch 2.56 -> 2.48 ms per batch of 64 */
+                const int ln = tid & 63, wv = tid >> 6;
+                if (ln < 40) {
+                    const int kbl = ln / 5, q = ln - kbl * 5, kb = ((row0 + 64 * wv) >> 3) + kbl;
+                    if (kb * 8 <= H) prep_store_class_item(L, c, slow, kb, q);
+                }
+                /* (with the block that holds its first row: when R does not divide PREP_THREADS they reach into the
+                 * next one) */
+                if (c.r_lo >= row0 && c.r_lo < row0 + PREP_THREADS) prep_store_instance_rows(P, c, slow, base);
             }
         }
+        /* (row H when it starts a block of its own -- H a multiple of PREP_THREADS: its class chunk and
+         * {G, K, S, V} went out with that block above, its instance piece with row H - 1's owner) */
+        return;
+    }
+    /* H + 1 > PREP_MAXR * PREP_THREADS rows, the prefixes are in the records already: the whole column, piece by piece */
+    const int NB = (H >> 3) + 1; /* 1/8-resolution blocks; the last one holds row H only */
+    for (int it = tid; it < NB * 5; it += PREP_THREADS) {
+        const int kb = it / 5, q = it - kb * 5;
+        prep_store_class_item(L, c, slow, kb, q);
+    }
+    prep_store_instance_rows(P, c, slow, base);
+}
+
+/* One column of a call: its records (RowRec), PruneRec, col_flags entry and fn windows.  The stages in order, with the
+ * barriers between them and the LDS each one takes over (PrepLds). */
+__device__ __forceinline__ void prepare_columns_body(
+    const DevParams& P, const int colg, char* smem, const float* __restrict__ joined,
+    const int32_t* __restrict__ seg, const float* __restrict__ ground /*[img][3][H]*/,
+    const int* __restrict__ vhor_arr, RowRec* __restrict__ recs, int* __restrict__ col_flags,
+    float* __restrict__ sv_arr /* null: a unary call, nothing reads the copies */, PruneRec* __restrict__ prune,
+    int* __restrict__ n_generic, int* __restrict__ path_bad) {
+    /* the distrust word of the last call's walk: every wave of a gated k_backtrace reads it, so that launch cannot
+     * clear it; the next call does, in front of its own walk */
+    if (colg == 0 && threadIdx.x == 0) path_bad[0] = 0;
+    if (P.lut_ready != nullptr && threadIdx.x == 0) {
+        P.lut_ready[colg] = 0; /* (the fused LUT units of the DP launch count up) */
+        if (colg == 0 && P.lutf_bad != nullptr) *P.lutf_bad = 0;
+    }
+    const PrepCol c = prep_col(P, colg, seg, recs);
+    const PrepLds L = prep_lds(smem, c.NP, c.CH, c.SS);
+    const int vhor = vhor_arr[c.img];
+    const int H = c.H, tid = c.tid;
+
+    prep_stage_column(P, L, c, joined); /* L.d, L.seg */
+    __syncthreads();
+    prep_fn_windows(P, L, c);
+    InstSums base;
+    const int slow = prep_instance_sums(P, L, c, col_flags, n_generic, base); /* L.wave; writes L.tot[0] */
+    __syncthreads();
+    const int nic_bad = prep_square_offsets(L, c); /* L.seg: the raw offsets are gone; L.wave */
+    prep_class_prefixes(L, c);                     /* L.seg: prefixes */
+    __syncthreads();
+
+    PrepPlanes pl;
+#pragma unroll
+    for (int k = 0; k < PREP_MAXR; k++) pl.S[k] = pl.V[k] = pl.G[k] = pl.K[k] = 0.0f;
+    /* compact copies for the pairwise phase 2 */
+    float* svcol = sv_arr != nullptr ? sv_arr + (size_t)colg * 2 * (H + 1) : nullptr;
+    prep_fill_S(P, L, c);
+    prep_scan_plane(L, c, pl.S, &RowRec::S, svcol);
+    __syncthreads();
+    if (P.invalid >= 0) {
+        prep_fill_V(P, L, c);
+        prep_scan_plane(L, c, pl.V, &RowRec::V, svcol ? svcol + H + 1 : nullptr);
         __syncthreads();
-    } else {
+    } else { /* all zero without an invalid-disparity value: no scan needed */
         for (int v = tid; v <= H; v += PREP_THREADS) {
-            if (!regs) rcol[v].V = 0.0f;
+            if (!c.regs) c.rcol[v].V = 0.0f;
             if (svcol) svcol[H + 1 + v] = 0.0f;
         }
     }
-    /* G: ground data cost, +inf at / above the horizon (:435-446) */
-    float g_abs = 0.0f, g_min = 0.0f; /* over the finite rows: slack of the ground data term */
-    for (int i = tid; i < NP; i += PREP_THREADS) {
-        float x = 0.0f;
-        if (i < H) {
-            x = (i >= vhor) ? IS_INF : data_cost_ground(gfun[i], s_d[i], gnorm[i], gis2[i], P);
-            if (i < vhor) { g_abs += __builtin_fabsf(x); g_min = __builtin_fminf(g_min, x); }
-        }
-        s_pyr[i] = x;
-    }
-    const float2 g_red = block_sum_min(g_abs, g_min, s_red);
+    const float2 g_red = prep_fill_G(P, L, c, ground, vhor); /* L.red */
+    prep_scan_plane(L, c, pl.G, &RowRec::G, nullptr);
     __syncthreads();
-    blelloch_build(s_pyr, NP, LNP);
-    if (regs) {
-#pragma unroll
-        for (int k = 0; k < MAXR; k++) {
-            const int v = tid + k * PREP_THREADS;
-            if (v <= H) pG[k] = prefix_at(v);
-        }
-    } else {
-        for (int v = tid; v <= H; v += PREP_THREADS) rcol[v].G = prefix_at(v);
-    }
-    __syncthreads();
-    /* K: sky data cost, 0 below the horizon (:424-433) */
-    float k_abs = 0.0f, k_min = 0.0f;
-    for (int i = tid; i < NP; i += PREP_THREADS) {
-        float x = 0.0f;
-        if (i < H) x = (i < vhor) ? 0.0f : data_cost_sky(s_d[i], P);
-        k_abs += __builtin_fabsf(x);
-        k_min = __builtin_fminf(k_min, x);
-        s_pyr[i] = x;
-    }
-    const float2 k_red = block_sum_min(k_abs, k_min, s_red);
-    if (tid == 0) {
-        /* PruneRec: see is_device.h.  A prefix difference P[a] - P[b] of per-row values x >= -nu
-         * with sum|x| = T is >= -(nu * H + gamma2 * T); NaN anywhere makes the slack NaN, and a NaN
-         * slack makes every bound NaN, which never passes the `>` test: no pruning. */
-        const float safe = 1.0f + 0x1p-10f;
-        const float hf = (float)H;
-        const float sig_g = ((0.0f - g_red.y) * hf + P.gamma2 * g_red.x) * safe;
-        const float sig_k = ((0.0f - k_red.y) * hf + P.gamma2 * k_red.x) * safe;
-        PruneRec pr;
-        pr.E1o = P.dw * P.sigma_od;
-        pr.E1g = P.dw * sig_g;
-        pr.E1s = P.dw * sig_k;
-        pr.E2 = P.iw * (0x1p-21f * safe) * s_tot[0]; /* 8 * 2^-24 * (sum mx^2 + sum my^2) */
-        /* 0 * inf above would be NaN = off as well; make the "off" states explicit */
-        if (slow || nic_bad || !(P.sigma_od < IS_INF) || !(pr.E1g < IS_INF) || !(pr.E1s < IS_INF) ||
-            !(pr.E2 < IS_INF))
-            pr.E1o = pr.E1g = pr.E1s = IS_INF; /* every type: the bounds are tested one by one */
-        pr.pad[0] = pr.pad[1] = pr.pad[2] = pr.pad[3] = 0.0f;
-        prune[colg] = pr;
-    }
-    __syncthreads();
-    blelloch_build(s_pyr, NP, LNP);
-    if (regs) {
-#pragma unroll
-        for (int k = 0; k < MAXR; k++) {
-            const int v = tid + k * PREP_THREADS;
-            if (v <= H) {
-                pK[k] = prefix_at(v);
-                if (!epi) prep_store16(reinterpret_cast<int4*>(rcol + v) + 5, make_int4(__float_as_int(pG[k]), __float_as_int(pK[k]), __float_as_int(pS[k]), __float_as_int(pV[k])));
-            }
-        }
-    } else {
-        for (int v = tid; v <= H; v += PREP_THREADS) rcol[v].K = prefix_at(v);
-    }
-    /* (round 4, measured and removed: the records staged 64 rows at a time in LDS and stored as whole
-     * 128-byte lines, eight lanes per record -- 1.53 instead of 1.21 ms for the column blocks of a batch of
-     * 64: the 34 extra barriers cost more than the partial lines do; the kernel is bound by its LDS /
-     * VALU work, not by its 2.15 GB of stores) */
-    if (epi) {
-        /* The epilogue walks the column in blocks of rows and every producer stores its
-         * pieces of the block's records before anyone goes on to the next block -- no barrier, the waves
-         * only have to stay roughly together: the partial lines a workgroup has in flight are
-         * PREP_EPI_ROWS x 128 bytes instead of the whole column's 131 KB (x 128 workgroups per XCD: 16.8 MB
-         * against 4 MB of L2 -- lines left the L2 before their last piece arrived). */
-        constexpr int ER = PREP_EPI_ROWS;
-        constexpr int M = ER >= PREP_THREADS ? ER / PREP_THREADS : 1; /* register slots per block */
-        constexpr int SUBS = ER >= PREP_THREADS ? 1 : PREP_THREADS / ER; /* blocks per register slot */
-        static_assert(ER % 8 == 0 && (ER >= PREP_THREADS ? ER % PREP_THREADS == 0 : PREP_THREADS % ER == 0),
-                      "PREP_EPI_ROWS: a multiple of 8 that divides PREP_THREADS or is a multiple of it");
-#pragma unroll
-        for (int kk = 0; kk < (MAXR + M - 1) / M; kk++) {
-            for (int sub = 0; sub < SUBS; sub++) {
-                const int row0 = kk * M * PREP_THREADS + sub * ER;
-                if (row0 <= H) {
-#pragma unroll
-                    for (int j = 0; j < M; j++) { /* {G, K, S, V}: row k * PREP_THREADS + tid is this thread's slot k */
-                        const int k = kk * M + j;
-                        if (k < MAXR) {
-                            const int v = k * PREP_THREADS + tid;
-                            if ((SUBS == 1 || tid / ER == sub) && v <= H)
-                                prep_store16(reinterpret_cast<int4*>(rcol + v) + 5,
-                                             make_int4(__float_as_int(pG[k]), __float_as_int(pK[k]),
-                                                       __float_as_int(pS[k]), __float_as_int(pV[k])));
-                        }
-                    }
-                    /* the class chunks of a wave's OWN 64 rows (the rows whose {G, K, S, V} it has just stored):
-                     * lanes 0..39 = 8 blocks x 5 chunks.  Measured against the block-strided loop below: column
-                     * blocks 1.04 -> 0.95 ms, fused launch 2.56 -> 2.48 ms per batch of 64 */
-                    if (ER == PREP_THREADS) {
-                        const int ln = tid & 63, wv = tid >> 6;
-                        if (ln < 40) {
-                            const int kbl = ln / 5, q = ln - kbl * 5, kb = ((row0 + 64 * wv) >> 3) + kbl;
-                            if (kb * 8 <= H)
-                                class_item(kb, q, [&](int vv, int qq, int4 x) {
-                                    prep_store16(reinterpret_cast<int4*>(rcol + vv) + qq, x);
-                                });
-                        }
-                    } else
-                    for (int it = tid; it < (ER / 8) * 5; it += PREP_THREADS) { /* class chunks: 1/8-resolution blocks x 5 */
-                        const int kbl = it / 5, q = it - kbl * 5, kb = (row0 >> 3) + kbl;
-                        if (kb * 8 <= H)
-                            class_item(kb, q, [&](int v, int qq, int4 x) {
-                                prep_store16(reinterpret_cast<int4*>(rcol + v) + qq, x);
-                            });
-                    }
-                    if (r_lo >= row0 && r_lo < row0 + ER) instance_rows(true, rec_row);
-                }
-            }
-        }
-        /* (row H when it starts a block of its own -- H a multiple of PREP_EPI_ROWS: its class chunk and
-         * {G, K, S, V} went out with that block above, its instance piece with row H - 1's owner) */
-    } else {
-        class_chunks();
-        instance_rows(true, rec_row);
-    }
+    const float2 k_red = prep_fill_K(P, L, c, vhor); /* L.red */
+    prep_prune_rec(P, L, c, g_red, k_red, slow, nic_bad, prune);
+    prep_scan_plane(L, c, pl.K, &RowRec::K, nullptr);
+    prep_store_records(P, L, c, slow, base, pl); /* no barrier: reads L.seg and registers only */
 }
 
 __global__ __launch_bounds__(PREP_THREADS) void k_prepare_columns(
@@ -761,31 +768,21 @@ __device__ __forceinline__ void object_lut_body(const DevParams& P, const int co
     if (i < H) block(i, false);
 }
 
-/* Behind a fused LUT + DP launch (k_dp_unary_fast, LUTF) whose workgroups could not trust the hand-over: the complete
- * table again, by the ordinary units.  Leaves at once while the word is 0 -- the normal case. */
-__global__ __launch_bounds__(64) void k_object_lut_repair(const DevParams P, int ncols, const float* __restrict__ joined,
-                                                          const float* __restrict__ cost_T, float* __restrict__ lutT,
-                                                          const int* __restrict__ run_if) {
+/* The complete table by the ordinary units, behind a gate word: leaves at once while *run_if is 0 -- the normal case.
+ * col_flags null: every column, else only the flagged ones.
+ *  - isk_launch_lut_repair: behind a fused LUT + DP launch (k_dp_unary_fast, LUTF) whose workgroups could not trust the
+ *    hand-over, or a distrusted walk: every column again;
+ *  - isk_launch_lut_generic: in front of the tile launches that read the table in a walk call (k_dp_unary<.., false> for
+ *    the generic-encoding columns, which the walk leaves alone): exactly those columns, gated by *n_generic. */
+__global__ __launch_bounds__(64) void k_object_lut_gated(const DevParams P, int ncols, const float* __restrict__ joined,
+                                                         const float* __restrict__ cost_T, float* __restrict__ lutT,
+                                                         const int* __restrict__ run_if,
+                                                         const int* __restrict__ col_flags) {
     if (__builtin_amdgcn_readfirstlane(*run_if) == 0) return;
     const int fn_blocks = (P.D + 63) / 64;
     for (int u = (int)blockIdx.x; u < ncols * fn_blocks; u += (int)gridDim.x) {
         const int colg = u / fn_blocks;
-        object_lut_body<false>(P, colg, u - colg * fn_blocks, (int)threadIdx.x, joined, cost_T, lutT);
-    }
-}
-
-/* In front of the tile launches that read the table in a walk call (k_dp_unary<.., false> for the generic-encoding
- * columns, which the walk leaves alone): the complete table of exactly those columns.  Leaves at once while the call
- * has none (*n_generic == 0, the normal case). */
-__global__ __launch_bounds__(64) void k_object_lut_generic(const DevParams P, int ncols, const float* __restrict__ joined,
-                                                           const float* __restrict__ cost_T, float* __restrict__ lutT,
-                                                           const int* __restrict__ col_flags,
-                                                           const int* __restrict__ n_generic) {
-    if (__builtin_amdgcn_readfirstlane(*n_generic) == 0) return;
-    const int fn_blocks = (P.D + 63) / 64;
-    for (int u = (int)blockIdx.x; u < ncols * fn_blocks; u += (int)gridDim.x) {
-        const int colg = u / fn_blocks;
-        if (__builtin_amdgcn_readfirstlane(col_flags[colg]) == 0) continue;
+        if (col_flags != nullptr && __builtin_amdgcn_readfirstlane(col_flags[colg]) == 0) continue;
         object_lut_body<false>(P, colg, u - colg * fn_blocks, (int)threadIdx.x, joined, cost_T, lutT);
     }
 }
@@ -802,7 +799,7 @@ __global__ __launch_bounds__(64) void k_object_lut_generic(const DevParams P, in
  * launch cost a large batch the occupancy both bodies live on: 8.2 ms.) */
 template <bool CARRY> /* lut: lutT, or CARRY: the walk's carry rows lutC (object_lut_body) */
 __global__ __launch_bounds__(PREP_THREADS) void k_prepare_fused(
-    const DevParams P, int ncols, int n_lut, const float* __restrict__ joined, const int32_t* __restrict__ seg,
+    const DevParams P, int ncols, const float* __restrict__ joined, const int32_t* __restrict__ seg,
     const float* __restrict__ ground, const int* __restrict__ vhor_arr, const float* __restrict__ cost_T,
     RowRec* __restrict__ recs, float* __restrict__ lut, int* __restrict__ col_flags,
     float* __restrict__ sv_arr, PruneRec* __restrict__ prune, int* __restrict__ n_generic,
@@ -951,23 +948,18 @@ __global__ void k_prior_tables(const DevParams P, const float* __restrict__ grou
 
 extern "C" {
 
-size_t isk_prepare_lds_bytes(const DevParams* P) {
-    return sizeof(float) * (size_t)prep_scan_leaves(P->H, P->P2) * 3 +
-           sizeof(int32_t) * (size_t)P->CH * prep_seg_stride(P->H) + 192;
-}
-
 hipError_t isk_launch_lut_repair(const DevParams* P, int ncols, const float* joined, const float* cost_T, float* lutT,
                                  const int* run_if, hipStream_t stream) {
     const int units = ncols * ((P->D + 63) / 64);
-    hipLaunchKernelGGL(k_object_lut_repair, dim3(units < 8192 ? units : 8192), dim3(64), 0, stream, *P, ncols, joined,
-                       cost_T, lutT, run_if);
+    hipLaunchKernelGGL(k_object_lut_gated, dim3(units < 8192 ? units : 8192), dim3(64), 0, stream, *P, ncols, joined,
+                       cost_T, lutT, run_if, (const int*)nullptr);
     return hipGetLastError();
 }
 
 hipError_t isk_launch_lut_generic(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream) {
     const int units = plan->ncols * ((P->D + 63) / 64);
-    hipLaunchKernelGGL(k_object_lut_generic, dim3(units < 2048 ? units : 2048), dim3(64), 0, stream, *P, plan->ncols,
-                       b->joined, b->cost_T, b->lutT, b->col_flags, b->n_generic);
+    hipLaunchKernelGGL(k_object_lut_gated, dim3(units < 2048 ? units : 2048), dim3(64), 0, stream, *P, plan->ncols,
+                       b->joined, b->cost_T, b->lutT, (const int*)b->n_generic, (const int*)b->col_flags);
     return hipGetLastError();
 }
 
@@ -1013,7 +1005,7 @@ hipError_t isk_launch_prepare(const DevParams* P, const CallPlan* plan, const Ca
     const int n_lut = (units + PREP_THREADS / 64 - 1) / (PREP_THREADS / 64);
 #define IS_LAUNCH_PREPARE(CARRY, LUT)                                                                                 \
     hipLaunchKernelGGL(k_prepare_fused<CARRY>, dim3(ncols + n_lut), dim3(PREP_THREADS), isk_prepare_lds_bytes(P), stream, \
-                       *P, ncols, n_lut, b->joined, b->seg, b->ground, b->vhor, b->cost_T, b->recs, LUT, b->col_flags,  \
+                       *P, ncols, b->joined, b->seg, b->ground, b->vhor, b->cost_T, b->recs, LUT, b->col_flags,  \
                        sv, b->prune, b->n_generic, b->path_bad)
     if (plan->lut_carry) IS_LAUNCH_PREPARE(true, b->lutC); else IS_LAUNCH_PREPARE(false, b->lutT);
 #undef IS_LAUNCH_PREPARE
@@ -1029,14 +1021,14 @@ hipError_t isk_launch_priors(const DevParams* P, const float* ground, PriorRec* 
 }
 
 hipError_t isk_set_lds_prepare(const DevParams* P) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_prepare_columns, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)isk_prepare_lds_bytes(P));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute((const void*)k_prepare_fused<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)isk_prepare_lds_bytes(P));
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute((const void*)k_prepare_fused<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)isk_prepare_lds_bytes(P));
+    const void* kernels[3] = {(const void*)k_prepare_columns, (const void*)k_prepare_fused<false>,
+                              (const void*)k_prepare_fused<true>};
+    for (const void* k : kernels) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)isk_prepare_lds_bytes(P));
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t isk_set_lds_lut_carry(const DevParams* P) {

@@ -293,7 +293,7 @@ size_t isk_unary_lds_bytes(const DevParams* P) {
  *    once when the call has none), then the repair: the tile-path DP of every FAST column again, leaving at once
  *    while k_unary_path has not set path_bad.  The prepare launch stored only the LUT's block carries (lutC), so each
  *    of the two is preceded by a gated launch that builds the complete lutT of the columns it takes
- *    (k_object_lut_generic: the generic columns; k_object_lut_repair on path_bad: every column);
+ *    (isk_launch_lut_generic: the generic columns; isk_launch_lut_repair on path_bad: every column);
  *  - the tile path: the FAST columns through k_dp_unary_fast (plan->unary_nvr) or the kernel of this file, then the
  *    generic columns. */
 hipError_t isk_launch_dp_unary(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream) {
