@@ -15,8 +15,9 @@
  * segment vB = 0 in lane 0.  Each candidate is the tile path's evaluation (eval_segment with my = record vT + 1,
  * rb = record vB, the cost assembly of unary_step) with the per-lane cases of the tile kernels: SKY when
  * vB - 1 >= vhor, otherwise GROUND; FIRST (vB = 0): ground only when vT <= vhor.  A lane's candidates descend,
- * so it keeps the LAST of equal costs (<=, take_if_le's rule); the lanes merge with the tile path's merge
- * (min cost, ties -> smallest vB, +inf -> the initial index).  NaN candidates never pass <=.
+ * so it keeps the LAST of equal costs (<=, take_if_le's rule); the lanes merge by the tile path's rule
+ * (min cost, ties -> smallest vB, +inf -> the initial index), evaluated as two DPP minima per type on the VALU
+ * (unary_merge_lanes); the row's six numbers come out as scalars.  NaN candidates never pass <=.
  *
  * Pruning (lemma L5): the class-group minima f_* of the LONGEST segment of a step (lane 0,
  * vB = 64 s + 1) bound the cost of every candidate vB' <= vB of the row, per type.  A type whose bound exceeds
@@ -75,7 +76,10 @@ __device__ __forceinline__ float lut_network(const LutCol& L, int dis, int fn, i
 
 /* A record whose address is the same in every lane, held in ONE VGPR: lane i (and i + 32) has dword i.  The fields
  * come out with v_readlane (SGPR operands of the evaluation), so the record costs one VGPR instead of 32. */
-__device__ __forceinline__ int load_rec_spread(const RowRec* p, int lane) { return ((const int*)p)[lane & 31]; }
+__device__ __forceinline__ int load_rec_spread(const RowRec* p, int lane) {
+    asm volatile("" : "+v"(lane)); /* (the address is rebuilt at the load, not kept in two VGPRs for the kernel) */
+    return ((const int*)p)[lane & 31];
+}
 __device__ __forceinline__ RowRec rec_of_spread(int v) {
     RowRec r;
     int* d = (int*)&r;
@@ -124,10 +128,65 @@ __device__ __forceinline__ float lut_row_entry(const LutCol& L, int disT, int vT
     return v;
 }
 
+/* The lanes' partial minima of a row merged: unary_merge_take's rule (is_unary.h) evaluated as a reduction, all on
+ * the VALU -- no LDS round trip, no wait, no branch.  Per type two wave-wide minima by DPP (row_shr:1/2/4/8 leave a
+ * row's minimum in its lane 15, row_bcast:15 / row_bcast:31 carry it on: lane 63 holds the wave's), each read with
+ * v_readlane:
+ *   m    = min of c (a best is never NaN);
+ *   vmin = the smallest recorded vB among the lanes with c == m, as an unsigned minimum of a key: v where c == m,
+ *          -1 = 0xFFFFFFFF in the lanes that lost -- and a lane that recorded nothing has v = -1, the same key, of
+ *          itself; recorded vB of different lanes differ;
+ *   the cost that goes on: the bits of the one lane whose key is vmin (equal-comparing costs, -0 / +0, take the bits
+ *          of the smaller vB, as a butterfly of takes does).  When no lane has a key, the lanes at the minimum hold
+ *          the initial pair, m is +inf and so is every lane's cost: vmin = -1 matches them all and any lane's bits do.
+ * The results are wave-uniform: scalars. */
+/* (one statement for the three types: between the write of a register and its next DPP read stand the two other
+ * types' instructions, the two wait states that read needs; the compiler does not look inside, so the s_nop in front
+ * -- five wait states: a VALU write of the registers (two) or of EXEC (five) may stand right before the statement --
+ * travels with it.  dst = src: a lane
+ * without a source or outside the row mask is not written and keeps its own value, bound_ctrl off.) */
+#define IS_WAVE_MIN3(OP)                                                                                             \
+    asm("s_nop 4\n\t"                                                                                                \
+        IS_WAVE_MIN3_STEP(OP, "row_shr:1 row_mask:0xf") IS_WAVE_MIN3_STEP(OP, "row_shr:2 row_mask:0xf")              \
+        IS_WAVE_MIN3_STEP(OP, "row_shr:4 row_mask:0xf") IS_WAVE_MIN3_STEP(OP, "row_shr:8 row_mask:0xf")              \
+        IS_WAVE_MIN3_STEP(OP, "row_bcast:15 row_mask:0xa") IS_WAVE_MIN3_STEP(OP, "row_bcast:31 row_mask:0xc")        \
+        : "+v"(a), "+v"(b), "+v"(c))
+#define IS_WAVE_MIN3_STEP(OP, CTRL)                                                                                  \
+    OP " %0, %0, %0 " CTRL " bank_mask:0xf\n\t" OP " %1, %1, %1 " CTRL " bank_mask:0xf\n\t"                          \
+    OP " %2, %2, %2 " CTRL " bank_mask:0xf\n\t"
+/* lane 63 of a, b, c: their minima over the wave (floats: no NaN among them) */
+__device__ __forceinline__ void wave_min3_f(float& a, float& b, float& c) { IS_WAVE_MIN3("v_min_f32_dpp"); }
+__device__ __forceinline__ void wave_min3_u(unsigned& a, unsigned& b, unsigned& c) { IS_WAVE_MIN3("v_min_u32_dpp"); }
+#undef IS_WAVE_MIN3_STEP
+#undef IS_WAVE_MIN3
+
 struct PathBest {
     float c[3];
     int v[3];
 };
+
+/* c / v: the lanes' (cost, vB) pairs in the order of the types (IS_GROUND, IS_OBJECT, IS_SKY) */
+__device__ __forceinline__ PathBest unary_merge_lanes(const float (&c)[3], const int (&v)[3]) {
+    float m[3] = {c[0], c[1], c[2]};
+    wave_min3_f(m[0], m[1], m[2]);
+    unsigned key[3], k[3];
+#pragma unroll
+    for (int t = 0; t < 3; t++) {
+        key[t] = c[t] == readlane_f(m[t], 63) ? (unsigned)v[t] : 0xFFFFFFFFu; /* (v = -1: no key as it stands) */
+        k[t] = key[t];
+    }
+    wave_min3_u(k[0], k[1], k[2]);
+    PathBest b;
+#pragma unroll
+    for (int t = 0; t < 3; t++) {
+        /* (no lane qualifies: vmin = -1 matches every lane, and every lane's cost is m = +inf) */
+        const unsigned vmin = (unsigned)__builtin_amdgcn_readlane((int)k[t], 63);
+        const uint64_t own = __builtin_amdgcn_ballot_w64(key[t] == vmin);
+        b.c[t] = readlane_f(c[t], __builtin_ctzll(own));
+        b.v[t] = unary_final_index(t, b.c[t], (int)vmin);
+    }
+    return b;
+}
 
 template <bool HAS_INVALID>
 __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* __restrict__ rcol, const LutCol& L,
@@ -262,7 +321,9 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
         const bool sky_left = 64 * s - 1 >= vhor;
         if (!open_g && (!open_s || !sky_left)) ended = true;
     }
-    if (vT > 0 && !ended) { /* first segment vB = 0 (:481-594): ground + object, lane 0 */
+    /* first segment vB = 0 (:481-594): ground + object, lane 0.  In row 0 it is the only candidate (no step ran: the
+     * object type is open, h0 = 1): the same code, once -- a second copy of it costs its spilled SGPRs again. */
+    if (!ended) {
         const int h0 = vT + 1;
         const float r0 = rcp[h0];
         const float pwih0 = P.pw * r0;
@@ -283,30 +344,8 @@ __device__ __forceinline__ PathBest path_row(const DevParams& P, const RowRec* _
             if (lane == 0 && vT <= vhor && cost_g <= bg) { bg = cost_g; vg = 0; }
         }
     }
-    if (vT == 0) { /* the first segment is the only candidate */
-        IS_MY_REC();
-        const RowRec rb0 = rec_of_spread(load_rec_spread(rcol, lane));
-        const float r0 = rcp[1];
-        const SegTerms t0 = eval_segment<true, HAS_INVALID>(my, rb0, 1.0f, r0, D, P.iw, rcp);
-        const float pwih0 = P.pw * r0;
-        const float od = lut_row_entry(L, disT, vT, t0.fni, lane == 0, lane) - 0.0f; /* lutT[0] = 0 */
-        const float cost_o = unary_cost(P, od, pwih0, t0.seg_o);
-        if (lane == 0 && cost_o <= bo) { bo = cost_o; vo = 0; }
-        const float cost_g = unary_cost(P, t0.gd, pwih0, t0.seg_g);
-        if (open_g && lane == 0 && vT <= vhor && cost_g <= bg) { bg = cost_g; vg = 0; }
-    }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        unary_merge_take(bg, vg, __shfl_xor(bg, m), __shfl_xor(vg, m));
-        unary_merge_take(bo, vo, __shfl_xor(bo, m), __shfl_xor(vo, m));
-        unary_merge_take(bs, vs, __shfl_xor(bs, m), __shfl_xor(vs, m));
-    }
-    PathBest b;
-    b.c[IS_GROUND] = bg; b.c[IS_OBJECT] = bo; b.c[IS_SKY] = bs;
-    b.v[IS_GROUND] = unary_final_index(IS_GROUND, bg, vg);
-    b.v[IS_OBJECT] = unary_final_index(IS_OBJECT, bo, vo);
-    b.v[IS_SKY] = unary_final_index(IS_SKY, bs, vs);
-    return b;
+    static_assert(IS_GROUND == 0 && IS_OBJECT == 1 && IS_SKY == 2, "the order of unary_merge_lanes' pairs");
+    return unary_merge_lanes({bg, bo, bs}, {vg, vo, vs}); /* (wave-uniform) */
 #undef IS_MY_REC
 }
 
@@ -370,8 +409,7 @@ void k_unary_path(const DevParams P, int ncols, const RowRec* __restrict__ recs,
         if (cG < cO) t = IS_GROUND;
         if ((n == 0 || type == IS_OBJECT) && cS < __builtin_fminf(cG, cO)) t = IS_SKY;
         type = t;
-        const int raw = type == IS_GROUND ? b.v[IS_GROUND] : (type == IS_OBJECT ? b.v[IS_OBJECT] : b.v[IS_SKY]);
-        const int vB = __builtin_amdgcn_readfirstlane(raw);
+        const int vB = type == IS_GROUND ? b.v[IS_GROUND] : (type == IS_OBJECT ? b.v[IS_OBJECT] : b.v[IS_SKY]);
         if (vB < 0 || vB > vT) { /* the back-trace would leave the rows this walk can vouch for */
             if (lane == 0) __hip_atomic_fetch_or(bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             return; /* no Section of this column is written: the ungated k_backtrace of the repair writes them */

@@ -97,7 +97,8 @@ __device__ __forceinline__ void unary_update(const DevParams& P, const SegTerms&
 
 /* The merge of partial minima of one row and type -- of the waves of a tile kernel, of the quarters of a diagonal
  * block, of the lanes of the walk: min cost, ties -> the smallest recorded vB (= the first strict minimum of the
- * reference's ascending-vB loop; a partial minimum without a candidate has v < 0 and never wins a tie). */
+ * reference's ascending-vB loop; a partial minimum without a candidate has v < 0 and never wins a tie).
+ * The walk evaluates the same rule over its 64 lanes as a reduction (unary_merge_lanes, is_k_unary_path.hip). */
 /* (a macro under the function: with the rule in a function of its own under unary_merge_take, k_unary_path compiled to
  * other code than before and its call measured 1.4 % slower) */
 #define UNARY_MERGE_WINS(c, v, c2, v2) (((c2) < (c)) || ((c2) == (c) && (v2) >= 0 && ((v) < 0 || (v2) < (v))))
