@@ -53,6 +53,25 @@ def make_hostile(case, seed):
     return case
 
 
+def ramp_columns(case):
+    """Overwrites the image columns of stixel column 0 with a ramp over the rows from 0.25 up to max_dis - 0.25 and
+    those of stixel column 1 with the constant max_dis - 0.5, in every image: the joined disparity then reaches the
+    first and the last disparity bin, (int)d == 0 and (int)d == max_dis - 1, the last column of the object cost
+    table included (make_frame stays under about 0.8 max_dis, make_hostile under bin max_dis - 2).  All values lie
+    inside [0, max_dis).  In place; returns the case."""
+    d = case["disparity"]                                    # [n][H][W]
+    D = int(case["cfg"].max_dis)
+    d[:, :, 0:8] = np.linspace(0.25, D - 0.25, d.shape[1], dtype=np.float32)[None, :, None]
+    d[:, :, 8:16] = np.float32(D - 0.5)
+    return case
+
+
+def reaches_both_end_bins(joined, max_dis):
+    """The condition ramp_columns exists for, on the oracle's joined disparity [C][H]."""
+    b = np.trunc(joined).astype(np.int64)
+    return bool((b == 0).any() and (b == max_dis - 1).any())
+
+
 def run_oracle(case, image=0, col_range=None, joined=None):
     cfg = case["cfg"]
     if joined is None:

@@ -42,7 +42,12 @@ def test_independent_evaluator_equals_oracle_on_golden_cases(path):
     ("drn_d_22_unary", 64, 64, 32, {}, 1), ("drn_d_38_pairwise", 64, 64, 32, {}, 2),
     ("drn_d_22_pairwise", 64, 32, 16, dict(invalid_disparity=0.0), 3),
     ("drn_d_38_unary", 56, 32, 32, dict(invalid_disparity=0.0), 4),
-    ("drn_d_38_pairwise", 40, 64, 16, dict(prior_weight=0.5, epsilon=1.0), 5)])
+    ("drn_d_38_pairwise", 40, 64, 16, dict(prior_weight=0.5, epsilon=1.0), 5)] +
+    # the disparity counts of tests/test_disparity_axis_gpu.py: fewer than four, no multiple of 4 on either side of
+    # 32, 64, 128 and 256, and one next to the largest a context accepts
+    [(preset, 72 if D == 130 else 40, 16, D, ov, D)
+     for preset, ov in (("drn_d_22_unary", {}), ("drn_d_38_pairwise", dict(invalid_disparity=0.0)))
+     for D in (2, 3, 7, 33, 65, 130, 257, 600)])
 def test_independent_evaluator_equals_oracle_on_seeded_cases(preset, rows, cols, D, ov, seed):
     case = helpers.build_case(preset, rows, cols, D, seed=seed, **ov)
     ref = helpers.run_oracle(case)

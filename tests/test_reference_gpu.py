@@ -82,6 +82,18 @@ def test_frame_shapes(preset, shape):
     _three_way(case, hip=_run_hip(case))
 
 
+@pytest.mark.parametrize("D", [2, 3, 5, 7, 33, 34, 63, 65, 66, 127, 129, 130, 136])
+@pytest.mark.parametrize("preset", ["drn_d_22_unary", "drn_d_38_pairwise"])
+def test_disparity_counts_where_the_dp_changes_path(preset, D):
+    """The oracle that tests/test_disparity_axis_gpu.py trusts, pinned on the reference at the counts of its table that
+    lie in the reference's domain (1 <= max_dis <= rows): fewer than four disparities, counts that are no multiple of 4
+    on either side of 32, 64 and 128, and D = rows at a row count that is no power of two.  136 x 64, the ramp columns
+    of that test (bins 0 and D - 1 are reached by a mean; all values inside [0, D))."""
+    case = helpers.ramp_columns(helpers.build_case(preset, 136, 64, D, seed=D))
+    assert helpers.reaches_both_end_bins(oracle.join_columns(case["cfg"], case["disparity"][0]), D)
+    _three_way(case, hip=_run_hip(case))
+
+
 @pytest.mark.parametrize("family", synthetic.FAMILIES)
 def test_input_families(family):
     preset = ("drn_d_22_unary", "drn_d_38_pairwise")[synthetic.FAMILIES.index(family) % 2]
