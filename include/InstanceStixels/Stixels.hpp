@@ -105,6 +105,8 @@ struct StixelsBuffers {
     DeviceArray<char> d_gt_targets_scratch;
     /* ComputeBatchRoad: [max_batch] RoadParameters | [max_batch] status bytes, the copy of the caller's device arrays */
     PinnedArray<char> h_road;
+    /* SegmentationHeadBatch: [channels][K] weights | [channels] bias of SetSegmentationHead (uploaded on first use) */
+    DeviceArray<float> d_head_weights;
     void release_all() { /* in the order of the declarations */
         d_disparity.release(); d_disparity_big.release(); d_segmentation.release(); d_instance_centerofmass.release();
         d_instance_indices.release(); d_instance_core_candidates.release(); d_instance_labels.release();
@@ -119,9 +121,10 @@ struct StixelsBuffers {
         h_world_totals.release(); h_world.release(); d_objects_block.release(); h_objects_block.release();
         d_sweep_stixels.release(); d_sweep_instances.release(); d_idisp_scratch.release(); d_idisp_inputs.release();
         d_idisp_out.release(); h_idisp_out.release(); d_gt_targets_scratch.release(); h_road.release();
+        d_head_weights.release();
     }
 };
-static_assert(sizeof(StixelsBuffers) == 48 * sizeof(DeviceArray<char>), "release_all() must release every array");
+static_assert(sizeof(StixelsBuffers) == 49 * sizeof(DeviceArray<char>), "release_all() must release every array");
 
 class Stixels : private StixelsBuffers {
 public:
@@ -321,6 +324,25 @@ public:
      * a null pointer, or rows / cols that are no multiples of 8. */
     void GroundTruthOffsetsBatch(int n_images, const int32_t* d_gt_instance, int32_t* d_segmentation,
                                  void* stream = nullptr);
+    /* f13 (an addition): the CNN's segmentation head, the last layers of the reference's models and its export
+     * wrapper (DRNDownsampled.py:97-102 and :128-137, wrappers.py:35-61), as is_segmentation_head defines it.
+     * SetSegmentationHead takes `seg.weight` [channels][K] and `seg.bias` [channels] of the 1x1 convolution, channels
+     * = the classes + instance channels of SetSegmentationParameters; throws std::invalid_argument unless bias.size()
+     * is that number, weight.size() == bias.size() * K and K >= 8 is a multiple of 8.  Needs no device: the object
+     * keeps the values and uploads them on the first SegmentationHeadBatch after Initialize. */
+    void SetSegmentationHead(const std::vector<float>& weight, const std::vector<float>& bias, int K);
+    /* The clamp of one regression channel (DRNDSOffsetDisparity's disparity channel: [0, 128]); channel -1: none
+     * (the default).  Throws std::invalid_argument unless lo <= hi. */
+    void SetSegmentationHeadClamp(int channel, float lo, float hi);
+    /* d_features [n_images][K][rows / 8][realcols] of dtype IS_HEAD_F32 / _F16 / _BF16 (backbone output, contiguous
+     * NCHW) -> d_segmentation [n_images][realcols][channels][rows_power2_segmentation] int32, what ComputeBatch,
+     * ComputeBatchRoad and SweepBatch take, and optionally d_cnn_out [n_images][channels][rows / 8][realcols] fp32.
+     * rows / 8, realcols, the channel split and rows_power2_segmentation are the initialised object's, so a caller
+     * cannot mismatch them.  A producer like GroundTruthOffsetsBatch: valid before any compute call, one asynchronous
+     * launch on `stream`, the record of the last batch untouched.  Throws std::invalid_argument before
+     * SetSegmentationHead, for n_images outside [1, max_batch] and for what is_segmentation_head refuses. */
+    void SegmentationHeadBatch(int n_images, const void* d_features, int dtype, int32_t* d_segmentation,
+                               float* d_cnn_out = nullptr, void* stream = nullptr);
     /* Back to the cluster labels of the last compute call. */
     void UseClusterInstances() { m_last.gt_instances = false; }
     /* The vote's parameters (defaults: the reference's): the minimum fraction of the 10 % rule, the labelIds of
@@ -519,6 +541,12 @@ private:
     int m_overlap_capacity = 4096; /* records per frame of InstanceOverlapBatch's first pass */
     int m_world_capacity = 0;      /* records per frame of SetWorldCapacity; 0: not set */
     int m_idisp_capacity = 256;    /* keys per frame of ClusterInstanceDisparityBatch */
+    /* SetSegmentationHead: weights | bias on the host, their K (0: not set), whether d_head_weights is behind them */
+    std::vector<float> m_seghead_values;
+    int m_seghead_K = 0;
+    bool m_seghead_uploaded = false;
+    int m_seghead_clamp_channel = -1;
+    float m_seghead_clamp_lo = 0, m_seghead_clamp_hi = 0;
     /* InstanceObjectsBatch: objects per frame of the first pass, the capacities d_objects_block was laid out for */
     int m_object_capacity = 64;
     size_t m_objects_cap = 0, m_object_points_cap = 0;

@@ -850,6 +850,62 @@ size_t is_offset_loss_scratch_bytes(int n_images, int planes, int rows8, int col
  * scratch, a capacity out of range and n_images outside [1, 65535]. */
 int is_offset_loss(const is_offset_loss_args* args, void* stream);
 
+/* ---- f13: the CNN's segmentation head of a batch, straight to the DP's input (is_k_head.hip) ------------------------
+ * The last layers of the reference's models and its export wrapper in one launch with fixed numerics:
+ * DRNDSDoubleSeg.forward (tools/CNN_training/models/DRNDownsampled.py:97-102: `seg`, a 1x1 convolution from the
+ * backbone's K features to n_classes + n_regression channels, -LogSoftmax over the classes, the concatenation),
+ * DRNDSOffsetDisparity.forward (:128-137: the same with a disparity channel, clamped to [0, 128] in eval mode),
+ * FlipAndPad (models/wrappers.py:35-61) and the sign that inference.py:374 gives the other models' output.
+ * Backbone features in, the DP's d_segmentation out, optionally the float network output that is_flip_and_pad takes.
+ *
+ *   Logits.   z[c] = fmaf(w[c][K-1], x[K-1], ... fmaf(w[c][0], x[0], bias[c]) ...): one fp32 chain in increasing k,
+ *             started from the bias; no split-K, no partial sums combined afterwards.  (On the device the f32-input
+ *             MFMA, issued in k order onto one accumulator: bit for bit that chain.)
+ *   Classes.  c < n_classes: y[c] = (m + log(sum_j exp(z[j] - m))) - z[c], m = max_j z[j] over the n_classes logits,
+ *             evaluated in binary64 and rounded to fp32 once: -log_softmax.
+ *   Regression channels pass through unchanged; channel clamp_channel is clamped to [clamp_lo, clamp_hi].
+ *   d_cnn_out holds those values; d_segmentation holds (int32)(8.0f * value), rows flipped, zero in every pad row:
+ *             byte for byte what is_flip_and_pad makes of d_cnn_out.  Every element of both is written (no memset).
+ *   The same bytes on every run; a frame's result does not depend on its position in the batch or on n_images.
+ *   Non-finite logits give unspecified values, never a write outside the outputs.
+ *
+ * Zero-initialise, then set the fields (clamp_channel = -1 for no clamp).  All arrays on the current device.
+ *   d_features          [n_images][K][rows8][cols8], contiguous NCHW, of dtype IS_HEAD_F32 / _F16 / _BF16, aligned to
+ *                       its element; halves are widened to fp32 at the load, which is exact
+ *   d_weight, d_bias    [channels_out][K] and [channels_out] fp32 (seg.weight without its two unit dimensions)
+ *   n_images, K, rows8, cols8   n_images in [1, 65535]; K >= 8 and a multiple of 8; rows8, cols8 >= 1
+ *   n_classes, n_regression     n_classes >= 1, n_regression >= 0, channels_out = their sum <= IS_HEAD_MAX_CHANNELS
+ *   rows_power2_segmentation    a power of two >= rows8 + 1
+ *   clamp_channel, clamp_lo, clamp_hi   -1, or a regression channel (>= n_classes) and clamp_lo <= clamp_hi
+ *   d_cnn_out           optional, [n_images][channels_out][rows8][cols8] fp32
+ *   d_segmentation      optional, [n_images][cols8][channels_out][rows_power2_segmentation] int32; at least one of
+ *                       the two outputs is given
+ *   reserved            0 */
+#define IS_HEAD_MAX_CHANNELS 32
+#define IS_HEAD_F32 0
+#define IS_HEAD_F16 1
+#define IS_HEAD_BF16 2
+typedef struct is_segmentation_head_args {
+    const void* d_features;
+    int dtype;
+    int n_images, K, rows8, cols8;
+    const float* d_weight;
+    const float* d_bias;
+    int n_classes, n_regression;
+    int rows_power2_segmentation;
+    int clamp_channel;
+    float clamp_lo, clamp_hi;
+    float* d_cnn_out;
+    int32_t* d_segmentation;
+    int reserved[4]; /* 0 */
+} is_segmentation_head_args;
+
+/* One launch on `stream`, asynchronous and stream-ordered; no allocation, copy or synchronisation.  IS_EINVAL, with
+ * the reason in is_last_error() and before the device is touched, for null args, a null input, both outputs null, an
+ * unknown dtype, a shape, channel split, K or rows_power2_segmentation outside the ranges above, a clamp_channel that
+ * is no regression channel, misaligned pointers and a non-zero reserved field. */
+int is_segmentation_head(const is_segmentation_head_args* args, void* stream);
+
 /* ---- f9: per-instance objects and their contours (is_k_objects.hip) ------------------------------------------------
  * What the reference's consumers reduce on the host from the per-stixel output: the top-down view
  * (tools/visualization/clustering_visualization.py:563-792: per instance and column the closest stixel, connected

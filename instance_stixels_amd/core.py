@@ -40,6 +40,7 @@ EXPORTS = [
     "is_cluster_instance_disparity", "is_instance_disparity_scratch_bytes",
     "is_mode_downsample", "is_gt_targets_scratch_bytes", "is_gt_instance_targets",
     "is_offset_loss_scratch_bytes", "is_offset_loss",
+    "is_segmentation_head",
 ]
 RENDER_MAX_LABELS = 64    # IS_RENDER_MAX_LABELS
 RENDER_MAX_CLASSES = 256  # IS_RENDER_MAX_CLASSES
@@ -176,6 +177,20 @@ class OffsetLossArgs(ctypes.Structure):
                 ("capacity", ci), ("d_scratch", vp), ("scratch_bytes", ctypes.c_size_t), ("d_key_count", vp)]
 
 
+HEAD_MAX_CHANNELS = 32  # IS_HEAD_MAX_CHANNELS
+HEAD_F32, HEAD_F16, HEAD_BF16 = 0, 1, 2  # IS_HEAD_*
+
+
+class SegmentationHeadArgs(ctypes.Structure):
+    """is_segmentation_head_args: zero-initialised by ctypes (set clamp_channel = -1 for no clamp); device pointers
+    as ints."""
+    vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    _fields_ = [("d_features", vp), ("dtype", ci), ("n_images", ci), ("K", ci), ("rows8", ci), ("cols8", ci),
+                ("d_weight", vp), ("d_bias", vp), ("n_classes", ci), ("n_regression", ci),
+                ("rows_power2_segmentation", ci), ("clamp_channel", ci), ("clamp_lo", cf), ("clamp_hi", cf),
+                ("d_cnn_out", vp), ("d_segmentation", vp), ("reserved", ci * 4)]
+
+
 class RoadParams(ctypes.Structure):
     """is_road_params: one frame's road, the layout of Stixels::RoadParameters (16 bytes)"""
     _fields_ = [("vhor", ctypes.c_int), ("tilt", ctypes.c_float), ("height", ctypes.c_float),
@@ -264,6 +279,7 @@ def lib():
         L.is_offset_loss_scratch_bytes.argtypes = [ci, ci, ci, ci, ci]
         L.is_offset_loss_scratch_bytes.restype = ctypes.c_size_t
         L.is_offset_loss.argtypes = [ctypes.POINTER(OffsetLossArgs), vp]
+        L.is_segmentation_head.argtypes = [ctypes.POINTER(SegmentationHeadArgs), vp]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
         L.is_get_device.argtypes = [ctypes.POINTER(ci)]
@@ -959,3 +975,89 @@ def offset_loss(prediction, ids8, disparity8_u16=None, weights=OFFSET_LOSS_WEIGH
                 break
             capacity = most   # (never above the cells of a frame; above IS_GT_TARGETS_MAX_CAPACITY it is refused)
     return (loss5, terms, grad, count) if return_key_count else (loss5, terms, grad)
+
+
+def segmentation_head_ptr(stream=0, **fields):
+    """is_segmentation_head on raw device pointers (ints): fields are those of SegmentationHeadArgs (clamp_channel
+    defaults to -1 here).  Asynchronous on `stream`; returns the return code and raises nothing (the tests check
+    IS_EINVAL)."""
+    fields.setdefault("clamp_channel", -1)
+    reserved = fields.pop("reserved", None)
+    a = SegmentationHeadArgs(**fields)
+    if reserved is not None:
+        for i, v in enumerate(reserved):
+            a.reserved[i] = int(v)
+    return lib().is_segmentation_head(ctypes.byref(a), ctypes.c_void_p(int(stream)))
+
+
+def segmentation_head(features, weight, bias, n_classes, rows_power2_segmentation, want_cnn_out=False, clamp=None,
+                      device=0, want_segmentation=True, canary=0):
+    """The CNN's segmentation head of a batch in one launch (is_segmentation_head, instance_stixels_core.h f13): the
+    1x1 convolution `seg`, -log_softmax over the first n_classes channels, the regression channels passed through
+    (clamp = (channel, lo, hi) clamps one of them) and FlipAndPad, with the numerics the header fixes.
+
+    features    [n][K][rows8][cols8] float32, float16 or bfloat16: a torch tensor on the device, or an array that is
+                copied to cuda:`device`; made contiguous NCHW, its dtype selects the kernel's
+    weight      [channels][K] (or seg.weight's [channels][K][1][1]) and bias [channels]: tensors or arrays, float32
+
+    Returns the DP input, an int32 tensor [n][cols8][channels][rows_power2_segmentation] on the features' device
+    (what Core.compute_ptr, ComputeBatch and SweepBatch take), and with want_cnn_out the float32 network output
+    [n][channels][rows8][cols8] behind it; enqueued on the current torch stream.  want_segmentation=False leaves
+    the int tensor out (then want_cnn_out is implied and the float tensor alone is returned).  canary > 0: both
+    outputs are allocated with that many guard words in front and behind, filled with a pattern, and a dict
+    {"segmentation": (front, back, pattern), "cnn_out": ...} of numpy copies of the guards is returned last (one
+    synchronisation)."""
+    import torch
+    x = features
+    if not torch.is_tensor(x):
+        x = torch.from_numpy(np.ascontiguousarray(x)).to(torch.device("cuda", device))
+    if not x.is_cuda or x.dim() != 4:
+        raise CoreError("features must be a device tensor [n][K][rows8][cols8]")
+    codes = {torch.float32: HEAD_F32, torch.float16: HEAD_F16, torch.bfloat16: HEAD_BF16}
+    if x.dtype not in codes:
+        raise CoreError(f"features dtype {x.dtype} is none of float32, float16, bfloat16")
+    x = x.contiguous()
+    dev = x.device
+    n, K, Hs, Ws = x.shape
+
+    def f32(v, what):
+        t = v if torch.is_tensor(v) else torch.tensor(np.asarray(v, np.float32))
+        return t.detach().to(device=dev, dtype=torch.float32).contiguous()
+    b = f32(bias, "bias").reshape(-1)
+    CH = int(b.numel())
+    w = f32(weight, "weight").reshape(CH, -1)
+    if w.shape[1] != K:
+        raise CoreError(f"weight holds {w.shape[1]} values per channel, the features have K = {K}")
+    P2S = int(rows_power2_segmentation)
+    if not want_segmentation:
+        want_cnn_out = True
+    g = int(canary)
+    pat_i, pat_f = 0x5A5A5A5A, -12345.0
+    with torch.cuda.device(dev):
+        seg = seg_all = cnn = cnn_all = None
+        if want_segmentation:
+            seg_all = torch.full((n * Ws * CH * P2S + 2 * g,), pat_i, dtype=torch.int32, device=dev) if g else \
+                torch.empty((n * Ws * CH * P2S,), dtype=torch.int32, device=dev)
+            seg = seg_all[g: g + n * Ws * CH * P2S].view(n, Ws, CH, P2S)
+        if want_cnn_out:
+            cnn_all = torch.full((n * CH * Hs * Ws + 2 * g,), pat_f, dtype=torch.float32, device=dev) if g else \
+                torch.empty((n * CH * Hs * Ws,), dtype=torch.float32, device=dev)
+            cnn = cnn_all[g: g + n * CH * Hs * Ws].view(n, CH, Hs, Ws)
+        a = SegmentationHeadArgs(d_features=x.data_ptr(), dtype=codes[x.dtype], n_images=n, K=K, rows8=Hs, cols8=Ws,
+                                 d_weight=w.data_ptr(), d_bias=b.data_ptr(), n_classes=int(n_classes),
+                                 n_regression=CH - int(n_classes), rows_power2_segmentation=P2S, clamp_channel=-1,
+                                 d_cnn_out=cnn.data_ptr() if cnn is not None else None,
+                                 d_segmentation=seg.data_ptr() if seg is not None else None)
+        if clamp is not None:
+            a.clamp_channel, a.clamp_lo, a.clamp_hi = int(clamp[0]), float(clamp[1]), float(clamp[2])
+        _check(lib().is_segmentation_head(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+               "is_segmentation_head")
+        out = [t for t in (seg, cnn) if t is not None]
+        if g:
+            guards = {}
+            for name, full, pat in (("segmentation", seg_all, np.int32(pat_i)), ("cnn_out", cnn_all, np.float32(pat_f))):
+                if full is not None:
+                    h = full.cpu().numpy()
+                    guards[name] = (h[:g].copy(), h[h.size - g:].copy(), pat)
+            out.append(guards)
+    return out[0] if len(out) == 1 else tuple(out)

@@ -1002,6 +1002,37 @@ int is_offset_loss(const is_offset_loss_args* a, void* stream) {
     return IS_OK;
 }
 
+/* ---- f13: the CNN's segmentation head (is_k_head.hip) ---- */
+int is_segmentation_head(const is_segmentation_head_args* a, void* stream) {
+    if (!a) return fail_arg("null args");
+    if (!a->d_features || !a->d_weight || !a->d_bias) return fail_arg("null d_features, d_weight or d_bias");
+    if (!a->d_cnn_out && !a->d_segmentation) return fail_arg("d_cnn_out and d_segmentation are both null");
+    if (a->dtype != IS_HEAD_F32 && a->dtype != IS_HEAD_F16 && a->dtype != IS_HEAD_BF16)
+        return fail_arg("dtype is none of IS_HEAD_F32, IS_HEAD_F16, IS_HEAD_BF16");
+    if (a->n_images < 1 || a->n_images > 65535) return fail_arg("n_images outside [1, 65535]");
+    if (a->rows8 < 1 || a->cols8 < 1) return fail_arg("rows8 and cols8 must be >= 1");
+    if (a->K < 8 || a->K % 8) return fail_arg("K must be >= 8 and a multiple of 8");
+    if (a->n_classes < 1) return fail_arg("n_classes must be >= 1");
+    if (a->n_regression < 0) return fail_arg("n_regression must be >= 0");
+    if ((long long)a->n_classes + a->n_regression > IS_HEAD_MAX_CHANNELS)
+        return fail_arg("n_classes + n_regression above IS_HEAD_MAX_CHANNELS");
+    const int P2S = a->rows_power2_segmentation;
+    if (P2S < 1 || (P2S & (P2S - 1))) return fail_arg("rows_power2_segmentation is not a power of two");
+    if (P2S <= a->rows8) return fail_arg("rows_power2_segmentation must be >= rows8 + 1");
+    if (a->clamp_channel != -1) {
+        if (a->clamp_channel < a->n_classes || a->clamp_channel >= a->n_classes + a->n_regression)
+            return fail_arg("clamp_channel is neither -1 nor a regression channel");
+        if (!(a->clamp_lo <= a->clamp_hi)) return fail_arg("clamp_lo must be <= clamp_hi");
+    }
+    for (int r : a->reserved)
+        if (r) return fail_arg("reserved must be 0");
+    if (misaligned(a->dtype == IS_HEAD_F32 ? 4 : 2, a->d_features)) return fail_arg("d_features must be aligned to its element");
+    if (misaligned(4, a->d_weight, a->d_bias, a->d_cnn_out, a->d_segmentation))
+        return fail_arg("d_weight, d_bias, d_cnn_out and d_segmentation must be 4-byte aligned");
+    HIP_TRY(isk_launch_segmentation_head(a, (hipStream_t)stream));
+    return IS_OK;
+}
+
 /* ---- f9: per-instance objects and contours (is_k_objects.hip) ---- */
 int is_instance_objects(const is_instance_objects_args* a, void* stream) {
     if (!a) return fail_arg("null args");

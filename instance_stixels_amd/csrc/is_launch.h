@@ -246,6 +246,9 @@ hipError_t isk_launch_gt_targets(const is_gt_targets_args* r, int capacity, hipS
 size_t isk_offset_loss_scratch_bytes(int n_images, int planes, int Hs, int Ws, int capacity);
 hipError_t isk_launch_offset_loss(const is_offset_loss_args* r, int capacity, hipStream_t stream);
 
+/* is_k_head.hip */
+hipError_t isk_launch_segmentation_head(const is_segmentation_head_args* a, hipStream_t stream);
+
 /* is_k_objects.hip */
 hipError_t isk_launch_instance_objects(const is_instance_objects_args* r, hipStream_t stream);
 

@@ -38,6 +38,7 @@ EXPORTS = [
     "ish_core_sweep_set", "ish_sweep_batch", "ish_select_sweep_set", "ish_last_frames", "ish_sweep_sets",
     "ish_active_device", "ish_sweep_sections", "ish_recluster_batch",
     "ish_cluster_instance_disparity_batch", "ish_set_instance_disparity_capacity",
+    "ish_set_segmentation_head", "ish_set_segmentation_head_clamp", "ish_segmentation_head_batch",
 ]
 WORLD_DTYPE = _core.WORLD_DTYPE  # is_world_stixel, the records of Stixels.WorldBatch
 OBJECT_DTYPE = _core.OBJECT_DTYPE    # is_instance_object, the objects of Stixels.InstanceObjectsBatch
@@ -132,6 +133,9 @@ def lib():
         L.ish_use_cluster_instances.argtypes = [vp]
         L.ish_ground_truth_offsets_batch.argtypes = [vp, ci, vp, vp, vp]
         L.ish_set_gt_assignment_parameters.argtypes = [vp, ctypes.c_double, vp, ci]
+        L.ish_set_segmentation_head.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ci]
+        L.ish_set_segmentation_head_clamp.argtypes = [vp, ci, cf, cf]
+        L.ish_segmentation_head_batch.argtypes = [vp, ci, vp, ci, vp, vp, vp]
         L.ish_core_sweep_set.argtypes = [vp, ctypes.POINTER(_core.SweepSet)]
         L.ish_sweep_batch.argtypes = [vp, ci, ci, vp, vp, vp, vp, ci, ci, vp]
         L.ish_select_sweep_set.argtypes = [vp, ci]
@@ -490,6 +494,32 @@ class Stixels:
             self._h, int(n), ctypes.c_void_p(int(d_gt)) if d_gt else None,
             ctypes.c_void_p(int(d_segmentation)) if d_segmentation else None, ctypes.c_void_p(int(stream))),
             "GroundTruthOffsetsBatch")
+
+    # ---- the CNN's segmentation head ----------------------------------------------------
+    def SetSegmentationHead(self, weight, bias, K):
+        """Stixels::SetSegmentationHead: seg.weight [channels][K] and seg.bias [channels] of the head's 1x1 convolution
+        (host arrays), channels = the configured classes + instance channels.  ValueError on mismatched sizes; needs
+        no device."""
+        w = np.ascontiguousarray(weight, np.float32).reshape(-1)
+        b = np.ascontiguousarray(bias, np.float32).reshape(-1)
+        self._check(lib().ish_set_segmentation_head(self._h, w.ctypes.data, w.size, b.ctypes.data, b.size, int(K)),
+                    "SetSegmentationHead")
+
+    def SetSegmentationHeadClamp(self, channel, lo=0.0, hi=0.0):
+        """Stixels::SetSegmentationHeadClamp: one regression channel clamped to [lo, hi]; channel -1: none."""
+        self._check(lib().ish_set_segmentation_head_clamp(self._h, int(channel), float(lo), float(hi)),
+                    "SetSegmentationHeadClamp")
+
+    def SegmentationHeadBatch(self, n, d_features, dtype, d_segmentation, d_cnn_out=0, stream=0):
+        """Stixels::SegmentationHeadBatch (device pointers as ints): d_features [n][K][rows / 8][realcols] of dtype
+        core.HEAD_F32 / HEAD_F16 / HEAD_BF16 -> d_segmentation [n][realcols][channels][P2S] int32, what ComputeBatch
+        takes, and optionally d_cnn_out [n][channels][rows / 8][realcols] float32.  A producer: legal before any
+        compute call, one asynchronous launch on `stream`."""
+        self._check(lib().ish_segmentation_head_batch(
+            self._h, int(n), ctypes.c_void_p(int(d_features)) if d_features else None, int(dtype),
+            ctypes.c_void_p(int(d_segmentation)) if d_segmentation else None,
+            ctypes.c_void_p(int(d_cnn_out)) if d_cnn_out else None, ctypes.c_void_p(int(stream))),
+            "SegmentationHeadBatch")
 
     # ---- parameter sweeps ------------------------------------------------------------
     def SweepBatch(self, pairwise, d_disparity_big, d_segmentation, road, sets, with_instances=True, stream=0):

@@ -806,6 +806,65 @@ void Stixels::GroundTruthOffsetsBatch(int n_images, const int32_t* d_gt, int32_t
     CheckConsumer("GroundTruthOffsetsBatch", is_gt_instance_targets(&a, stream));
 }
 
+/* The head of the reference's models (DRNDownsampled.py:97-102, :128-137) and its wrapper (wrappers.py:35-61). */
+void Stixels::SetSegmentationHead(const std::vector<float>& weight, const std::vector<float>& bias, int K) {
+    if (m_segmentation_channels < 1 || bias.size() != (size_t)m_segmentation_channels)
+        throw std::invalid_argument("SetSegmentationHead: bias.size() is not the classes + instance channels of "
+                                    "SetSegmentationParameters.");
+    if (K < 8 || K % 8) throw std::invalid_argument("SetSegmentationHead: K must be >= 8 and a multiple of 8.");
+    if (weight.size() != bias.size() * (size_t)K)
+        throw std::invalid_argument("SetSegmentationHead: weight.size() is not bias.size() * K.");
+    m_seghead_values.assign(weight.begin(), weight.end());
+    m_seghead_values.insert(m_seghead_values.end(), bias.begin(), bias.end());
+    m_seghead_K = K;
+    m_seghead_uploaded = false;
+}
+
+void Stixels::SetSegmentationHeadClamp(int channel, float lo, float hi) {
+    if (channel != -1 && !(lo <= hi)) throw std::invalid_argument("SetSegmentationHeadClamp: lo must be <= hi.");
+    m_seghead_clamp_channel = channel;
+    m_seghead_clamp_lo = lo;
+    m_seghead_clamp_hi = hi;
+}
+
+void Stixels::SegmentationHeadBatch(int n_images, const void* d_features, int dtype, int32_t* d_seg, float* d_cnn_out,
+                                    void* stream) {
+    if (!m_is_initialized) throw std::invalid_argument("SegmentationHeadBatch: the object is not initialised.");
+    if (m_seghead_K == 0 || m_seghead_values.size() != (size_t)m_segmentation_channels * (m_seghead_K + 1))
+        throw std::invalid_argument("SegmentationHeadBatch: SetSegmentationHead() has not been called for the "
+                                    "configured channels.");
+    if (n_images < 1 || n_images > m_max_batch)
+        throw std::invalid_argument("SegmentationHeadBatch: n_images outside [1, max_batch] of InitializeBatch().");
+    const DeviceGuard guard(m_ctx_device);
+    if (stream == nullptr) stream = m_stream;
+    if (!m_seghead_uploaded || d_head_weights.get() == nullptr) {
+        /* (on the object's stream and finished here: the caller's stream may be any other) */
+        d_head_weights.reserve(m_seghead_values.size());
+        IS_CHECK_RETURN(is_memcpy_h2d(d_head_weights.get(), m_seghead_values.data(), sizeof(float) * m_seghead_values.size(),
+                                      m_stream));
+        IS_CHECK_RETURN(is_stream_synchronize(m_stream));
+        m_seghead_uploaded = true;
+    }
+    is_segmentation_head_args a = {};
+    a.d_features = d_features;
+    a.dtype = dtype;
+    a.n_images = n_images;
+    a.K = m_seghead_K;
+    a.rows8 = m_rows / 8;
+    a.cols8 = m_realcols;
+    a.d_weight = d_head_weights.get();
+    a.d_bias = d_head_weights.get() + (size_t)m_segmentation_channels * m_seghead_K;
+    a.n_classes = m_segmentation_classes;
+    a.n_regression = m_segmentation_channels - m_segmentation_classes;
+    a.rows_power2_segmentation = m_params.rows_power2_segmentation;
+    a.clamp_channel = m_seghead_clamp_channel;
+    a.clamp_lo = m_seghead_clamp_lo;
+    a.clamp_hi = m_seghead_clamp_hi;
+    a.d_cnn_out = d_cnn_out;
+    a.d_segmentation = d_seg;
+    CheckConsumer("SegmentationHeadBatch", is_segmentation_head(&a, stream));
+}
+
 void Stixels::SetGTAssignmentParameters(double min_fraction, const int* label_ids8, bool gt_is_train_ids) {
     static const int kCityscapes[IS_INSTANCE_CLASSES] = {24, 25, 26, 27, 28, 31, 32, 33};
     if (min_fraction != min_fraction) throw std::invalid_argument("SetGTAssignmentParameters: min_fraction is NaN.");

@@ -421,6 +421,22 @@ int ish_ground_truth_offsets_batch(void* h, int n, const int32_t* d_gt_instance,
                                    void* stream) {
     return guard([&] { ((Stixels*)h)->GroundTruthOffsetsBatch(n, d_gt_instance, d_segmentation, stream); });
 }
+/* SetSegmentationHead(): weight [channels][K], bias [channels] host floats.  Needs no device. */
+int ish_set_segmentation_head(void* h, const float* weight, size_t n_weight, const float* bias, size_t n_bias, int K) {
+    return guard([&] {
+        if ((n_weight && !weight) || (n_bias && !bias)) throw std::invalid_argument("SetSegmentationHead: null array.");
+        ((Stixels*)h)->SetSegmentationHead(std::vector<float>(weight, weight + n_weight),
+                                           std::vector<float>(bias, bias + n_bias), K);
+    });
+}
+int ish_set_segmentation_head_clamp(void* h, int channel, float lo, float hi) {
+    return guard([&] { ((Stixels*)h)->SetSegmentationHeadClamp(channel, lo, hi); });
+}
+/* SegmentationHeadBatch(): backbone features -> d_segmentation (and d_cnn_out, may be null); asynchronous on `stream`. */
+int ish_segmentation_head_batch(void* h, int n, const void* d_features, int dtype, int32_t* d_segmentation,
+                                float* d_cnn_out, void* stream) {
+    return guard([&] { ((Stixels*)h)->SegmentationHeadBatch(n, d_features, dtype, d_segmentation, d_cnn_out, stream); });
+}
 int ish_use_cluster_instances(void* h) {
     return guard([&] { ((Stixels*)h)->UseClusterInstances(); });
 }
