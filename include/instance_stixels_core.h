@@ -906,6 +906,115 @@ typedef struct is_segmentation_head_args {
  * is no regression channel, misaligned pointers and a non-zero reserved field. */
 int is_segmentation_head(const is_segmentation_head_args* args, void* stream);
 
+/* ---- f14: the backward pass of the segmentation head and the semantic NLL loss (is_k_head_backward.hip) -------------
+ * What training through f13's head needs (the reference trains every model as closs + rloss, tools/CNN_training/
+ * train.py:698-732, closs = nn.NLLLoss(reduction='mean', ignore_index=255) on the class channels, train.py:281-282,
+ * 325-326; optim_seg_parameters, DRNDownsampled.py:139-143, is head-only fine-tuning): the gradient of f13's float
+ * output with respect to the features, the weight and the bias, and the classification loss with its gradient.  The
+ * rule is f13's: every summation order is fixed by the input's shape alone, no floating-point atomics, the same bytes
+ * on every run.
+ *
+ * Notation.  CH = n_classes + n_regression <= IS_HEAD_MAX_CHANNELS, P = rows8 * cols8, pixel p = row * cols8 + col.
+ * y is f13's d_cnn_out [n][CH][rows8][cols8] fp32, saved from the forward and not recomputed; gy is the upstream
+ * gradient with respect to y, in the same layout with its own image stride.
+ *
+ *   Logit gradient dz [n][CH][P] fp32.  Class channel j < n_classes: S = sum_{c < n_classes} (double)gy[c] in
+ *             increasing c, dz[j] = (float)(exp(-(double)y[j]) * S - (double)gy[j]), in binary64 and rounded once
+ *             (from y[c] = lse - z[c]).  Regression channel: dz[c] = gy[c], bit for bit.  No clamp: the reference
+ *             clamps only in eval mode (DRNDownsampled.py:133-134).
+ *   d_grad_features [n][K][rows8][cols8] in the dtype of the features: dX[k][p] is the fp32 chain
+ *             acc = fmaf(w[c][k], dz[c][p], acc) for c = 0 .. CH-1, started from +0.0f; rounded once (to nearest
+ *             even) for fp16 / bf16 features.  Every element is written.  A frame's dX does not depend on n_images
+ *             or on its position in the batch.
+ *   d_grad_weight [CH][K], d_grad_bias [CH] fp32.  The contraction over all n * P pixels is split, and the split is
+ *             part of the contract: chunk j of image i covers p in [j T, min((j + 1) T, P)), T =
+ *             IS_HEAD_BACKWARD_CHUNK for every shape.  part[i][j][c][k] is the fp32 chain
+ *             acc = fmaf(dz[c][p], x[k][p], acc) in increasing p from +0.0f;
+ *             dW[c][k] = (float) sum (double)part[i][j][c][k], i outer and j inner, both increasing, rounded once.
+ *             db[c] is the same with x = 1, i.e. acc = acc + dz[c][p] in fp32.  Halves are widened at the load.
+ *   d_grad_logits [n][CH][rows8][cols8] fp32 receives dz (so that the two contractions can be checked bit for bit on
+ *             the device's own dz).
+ *   No floating-point atomics, nothing depends on the grid, the same bytes on every run and for every choice of the
+ *   optional outputs.  Non-finite inputs give unspecified values, never a write outside the outputs; no address
+ *   depends on a value.
+ *
+ * Zero-initialise, then set the fields.  All arrays on the current device.
+ *   d_features, dtype, n_images, K, rows8, cols8, d_weight, n_classes, n_regression   as in f13, the same ranges, and
+ *                       rows8 * cols8 <= 2^28
+ *   d_cnn_out           y, [n_images][CH][rows8][cols8] fp32, contiguous
+ *   d_grad_out, grad_image_stride   gy: frame f starts at d_grad_out + f * stride (elements), its planes are
+ *                       contiguous [CH][rows8][cols8]; stride >= CH * P
+ *   d_grad_features, d_grad_weight, d_grad_bias, d_grad_logits   optional, at least one of them is given
+ *   d_scratch           16-byte aligned, scratch_bytes >= is_segmentation_head_backward_scratch_bytes(...); its
+ *                       contents mean nothing between calls
+ *   reserved            0 */
+#define IS_HEAD_BACKWARD_CHUNK 2048
+typedef struct is_segmentation_head_backward_args {
+    const void* d_features;
+    int dtype;
+    int n_images, K, rows8, cols8;
+    const float* d_weight;
+    int n_classes, n_regression;
+    const float* d_cnn_out;
+    const float* d_grad_out;
+    long long grad_image_stride;
+    void* d_grad_features;
+    float* d_grad_weight;
+    float* d_grad_bias;
+    float* d_grad_logits;
+    void* d_scratch;
+    size_t scratch_bytes;
+    int reserved[4]; /* 0 */
+} is_segmentation_head_backward_args;
+
+/* Bytes of d_scratch for a call of that shape, channels = n_classes + n_regression (0 for a shape the call refuses). */
+size_t is_segmentation_head_backward_scratch_bytes(int n_images, int K, int rows8, int cols8, int channels);
+/* One to three launches on `stream` (dz and dX; the chunk partials; their reduction), asynchronous and
+ * stream-ordered; no allocation, copy or synchronisation.  IS_EINVAL, with the reason in is_last_error() and before
+ * the device is touched, for null args, a null required pointer, all four outputs null, an unknown dtype, a shape,
+ * channel split or K outside the ranges above, a stride below CH * P, misaligned pointers, scratch that is too small
+ * or misaligned and a non-zero reserved field. */
+int is_segmentation_head_backward(const is_segmentation_head_backward_args* args, void* stream);
+
+/* The classification loss of the reference's training, nn.NLLLoss(reduction='mean', ignore_index) on f13's class
+ * planes (which hold -log p), with its gradient:
+ *   d_cnn_out, cnn_image_stride   frame f starts at d_cnn_out + f * stride (elements); its first n_classes planes
+ *                       [rows8][cols8] are read; stride >= n_classes * P
+ *   d_target, target_dtype   [n_images][rows8][cols8], IS_DTYPE_UINT8 or IS_DTYPE_INT32 (what is_mode_downsample
+ *                       writes for the semantic ground truth)
+ *   n_images, rows8, cols8, n_classes   n_images in [1, 65535], rows8, cols8 >= 1, P <= 2^28, n_images * P < 2^31,
+ *                       n_classes in [1, IS_HEAD_MAX_CHANNELS]
+ *   d_loss              [1] float: (float)(sum_valid (double)y[t_p](p) / V); the sum is binary64, combined in an order
+ *                       the shape alone decides; V = 0 gives NaN, as torch does
+ *   d_valid_count       [1] int32: V, the pixels whose target is a class
+ *   d_bad_count         [1] int32: targets outside [0, n_classes) that are not ignore_index; they count as ignored
+ *   d_grad, grad_image_stride   optional: [c == t_p] * (float)(1.0 / V) in all n_classes planes of every frame, zeros
+ *                       included, laid out as d_cnn_out with its own stride (>= n_classes * P); all zero with V = 0.
+ *                       With f12's d_grad on the regression planes this assembles one gy without memset or copy.
+ *   d_scratch           16-byte aligned, scratch_bytes >= is_semantic_nll_scratch_bytes(n_images, rows8, cols8)
+ *   reserved            0
+ * Two launches (three with d_grad), asynchronous and stream-ordered, no allocation, copy, synchronisation or atomics.
+ * IS_EINVAL as above. */
+typedef struct is_semantic_nll_args {
+    const float* d_cnn_out;
+    long long cnn_image_stride;
+    const void* d_target;
+    int target_dtype;
+    int ignore_index;
+    int n_images, rows8, cols8, n_classes;
+    float* d_loss;
+    int32_t* d_valid_count;
+    int32_t* d_bad_count;
+    float* d_grad;
+    long long grad_image_stride;
+    void* d_scratch;
+    size_t scratch_bytes;
+    int reserved[4]; /* 0 */
+} is_semantic_nll_args;
+
+size_t is_semantic_nll_scratch_bytes(int n_images, int rows8, int cols8);
+int is_semantic_nll(const is_semantic_nll_args* args, void* stream);
+
 /* ---- f9: per-instance objects and their contours (is_k_objects.hip) ------------------------------------------------
  * What the reference's consumers reduce on the host from the per-stixel output: the top-down view
  * (tools/visualization/clustering_visualization.py:563-792: per instance and column the closest stixel, connected

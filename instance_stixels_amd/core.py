@@ -41,6 +41,8 @@ EXPORTS = [
     "is_mode_downsample", "is_gt_targets_scratch_bytes", "is_gt_instance_targets",
     "is_offset_loss_scratch_bytes", "is_offset_loss",
     "is_segmentation_head",
+    "is_segmentation_head_backward_scratch_bytes", "is_segmentation_head_backward",
+    "is_semantic_nll_scratch_bytes", "is_semantic_nll",
 ]
 RENDER_MAX_LABELS = 64    # IS_RENDER_MAX_LABELS
 RENDER_MAX_CLASSES = 256  # IS_RENDER_MAX_CLASSES
@@ -191,6 +193,28 @@ class SegmentationHeadArgs(ctypes.Structure):
                 ("d_cnn_out", vp), ("d_segmentation", vp), ("reserved", ci * 4)]
 
 
+HEAD_BACKWARD_CHUNK = 2048  # IS_HEAD_BACKWARD_CHUNK
+
+
+class SegmentationHeadBackwardArgs(ctypes.Structure):
+    """is_segmentation_head_backward_args: zero-initialised by ctypes; device pointers as ints."""
+    vp, ci, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    _fields_ = [("d_features", vp), ("dtype", ci), ("n_images", ci), ("K", ci), ("rows8", ci), ("cols8", ci),
+                ("d_weight", vp), ("n_classes", ci), ("n_regression", ci), ("d_cnn_out", vp), ("d_grad_out", vp),
+                ("grad_image_stride", ll), ("d_grad_features", vp), ("d_grad_weight", vp), ("d_grad_bias", vp),
+                ("d_grad_logits", vp), ("d_scratch", vp), ("scratch_bytes", ctypes.c_size_t), ("reserved", ci * 4)]
+
+
+class SemanticNllArgs(ctypes.Structure):
+    """is_semantic_nll_args: zero-initialised by ctypes; device pointers as ints."""
+    vp, ci, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    _fields_ = [("d_cnn_out", vp), ("cnn_image_stride", ll), ("d_target", vp), ("target_dtype", ci),
+                ("ignore_index", ci), ("n_images", ci), ("rows8", ci), ("cols8", ci), ("n_classes", ci),
+                ("d_loss", vp), ("d_valid_count", vp), ("d_bad_count", vp), ("d_grad", vp),
+                ("grad_image_stride", ll), ("d_scratch", vp), ("scratch_bytes", ctypes.c_size_t),
+                ("reserved", ci * 4)]
+
+
 class RoadParams(ctypes.Structure):
     """is_road_params: one frame's road, the layout of Stixels::RoadParameters (16 bytes)"""
     _fields_ = [("vhor", ctypes.c_int), ("tilt", ctypes.c_float), ("height", ctypes.c_float),
@@ -280,6 +304,12 @@ def lib():
         L.is_offset_loss_scratch_bytes.restype = ctypes.c_size_t
         L.is_offset_loss.argtypes = [ctypes.POINTER(OffsetLossArgs), vp]
         L.is_segmentation_head.argtypes = [ctypes.POINTER(SegmentationHeadArgs), vp]
+        L.is_segmentation_head_backward_scratch_bytes.argtypes = [ci, ci, ci, ci, ci]
+        L.is_segmentation_head_backward_scratch_bytes.restype = ctypes.c_size_t
+        L.is_segmentation_head_backward.argtypes = [ctypes.POINTER(SegmentationHeadBackwardArgs), vp]
+        L.is_semantic_nll_scratch_bytes.argtypes = [ci, ci, ci]
+        L.is_semantic_nll_scratch_bytes.restype = ctypes.c_size_t
+        L.is_semantic_nll.argtypes = [ctypes.POINTER(SemanticNllArgs), vp]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
         L.is_get_device.argtypes = [ctypes.POINTER(ci)]
@@ -1061,3 +1091,222 @@ def segmentation_head(features, weight, bias, n_classes, rows_power2_segmentatio
                     guards[name] = (h[:g].copy(), h[h.size - g:].copy(), pat)
             out.append(guards)
     return out[0] if len(out) == 1 else tuple(out)
+
+
+def _with_reserved(cls, fields):
+    reserved = fields.pop("reserved", None)
+    a = cls(**fields)
+    if reserved is not None:
+        for i, v in enumerate(reserved):
+            a.reserved[i] = int(v)
+    return a
+
+
+def _guarded(numel, dtype, dev, g, pattern):
+    """A flat device tensor of numel elements, with g guard elements of `pattern` in front and behind when g > 0:
+    (the whole allocation or None, the view of the numel elements)."""
+    import torch
+    if not g:
+        return None, torch.empty((numel,), dtype=dtype, device=dev)
+    full = torch.full((numel + 2 * g,), pattern, dtype=dtype, device=dev)
+    return full, full[g: g + numel]
+
+
+def _guards(named, g, g_scratch):
+    """{name: (front, back, pattern)} as numpy copies of the guard elements (one synchronisation)."""
+    import torch
+    out = {}
+    for name, (full, pattern) in named.items():
+        h = full.view(torch.uint8).cpu().numpy().view(np.asarray(pattern).dtype)
+        k = g_scratch if name == "scratch" else g
+        out[name] = (h[:k].copy(), h[h.size - k:].copy(), pattern)
+    return out
+
+
+def segmentation_head_backward_scratch_bytes(n_images, K, rows8, cols8, channels):
+    """is_segmentation_head_backward_scratch_bytes: the scratch a call of that shape needs (0: a refused shape)."""
+    return int(lib().is_segmentation_head_backward_scratch_bytes(int(n_images), int(K), int(rows8), int(cols8),
+                                                                 int(channels)))
+
+
+def segmentation_head_backward_ptr(stream=0, **fields):
+    """is_segmentation_head_backward on raw device pointers (ints): fields are those of SegmentationHeadBackwardArgs.
+    Asynchronous on `stream`; returns the return code and raises nothing (the tests check IS_EINVAL)."""
+    a = _with_reserved(SegmentationHeadBackwardArgs, fields)
+    return lib().is_segmentation_head_backward(ctypes.byref(a), ctypes.c_void_p(int(stream)))
+
+
+def segmentation_head_backward(features, weight, cnn_out, grad_out, n_classes, want_features=True, want_weight=True,
+                               want_bias=True, want_logits=False, canary=0):
+    """The backward pass of the segmentation head (is_segmentation_head_backward, instance_stixels_core.h f14).
+
+    features    device tensor [n][K][rows8][cols8], float32, float16 or bfloat16 (made contiguous)
+    weight      [channels][K] (or [channels][K][1][1]) float32
+    cnn_out     device float32 [n][channels][rows8][cols8]: the float output of core.segmentation_head, saved
+    grad_out    device float32 [n][channels][rows8][cols8]: the gradient with respect to cnn_out; read in place when
+                each frame's planes are contiguous (a batch stride above channels * rows8 * cols8 is allowed)
+
+    Returns a dict with the requested ones of "features" (the features' shape and dtype), "weight" [channels][K],
+    "bias" [channels] and "logits" [n][channels][rows8][cols8] (float32), on the features' device, enqueued on the
+    current torch stream; the scratch is allocated here.  canary > 0: every output and the scratch get that many guard
+    elements in front and behind, and the dict has "guards": {name: (front, back, pattern)} (one synchronisation)."""
+    import torch
+    x = features
+    if not torch.is_tensor(x) or not x.is_cuda or x.dim() != 4:
+        raise CoreError("features must be a device tensor [n][K][rows8][cols8]")
+    codes = {torch.float32: HEAD_F32, torch.float16: HEAD_F16, torch.bfloat16: HEAD_BF16}
+    if x.dtype not in codes:
+        raise CoreError(f"features dtype {x.dtype} is none of float32, float16, bfloat16")
+    x = x.detach().contiguous()
+    dev = x.device
+    n, K, Hs, Ws = x.shape
+    w = weight.detach().to(device=dev, dtype=torch.float32).contiguous()
+    CH = int(w.shape[0])
+    w = w.reshape(CH, -1)
+    if w.shape[1] != K:
+        raise CoreError(f"weight holds {w.shape[1]} values per channel, the features have K = {K}")
+    shape = (n, CH, Hs, Ws)
+    y = cnn_out
+    if y.device != dev or y.dtype != torch.float32 or tuple(y.shape) != shape:
+        raise CoreError(f"cnn_out must be a float32 tensor {shape} on the features' device")
+    y = y.detach().contiguous()
+    gy = grad_out
+    if gy.device != dev or gy.dtype != torch.float32 or tuple(gy.shape) != shape:
+        raise CoreError(f"grad_out must be a float32 tensor {shape} on the features' device")
+    gy = gy.detach()
+    frame = CH * Hs * Ws
+    if gy.stride(3) != 1 or gy.stride(2) != Ws or gy.stride(1) != Hs * Ws or (n > 1 and gy.stride(0) < frame):
+        gy = gy.contiguous()
+    gy_stride = gy.stride(0) if n > 1 else frame
+    if not (want_features or want_weight or want_bias or want_logits):
+        raise CoreError("no gradient is asked for")
+    g = int(canary)
+    with torch.cuda.device(dev):
+        nbytes = segmentation_head_backward_scratch_bytes(n, K, Hs, Ws, CH)
+        if nbytes == 0:
+            raise CoreError("is_segmentation_head_backward_scratch_bytes refuses the shape "
+                            f"(n_images {n}, K {K}, rows8 {Hs}, cols8 {Ws}, channels {CH})")
+        pat_f = np.float32(-12345.0)
+        pat_x = {torch.float32: pat_f, torch.float16: np.uint16(0x5A5A), torch.bfloat16: np.uint16(0x5A5A)}[x.dtype]
+        named, out = {}, {}
+        ptr = {"features": None, "weight": None, "bias": None, "logits": None}
+        for name, want, numel, view, dtype, pat in (
+                ("features", want_features, n * K * Hs * Ws, (n, K, Hs, Ws), x.dtype, pat_x),
+                ("weight", want_weight, CH * K, (CH, K), torch.float32, pat_f),
+                ("bias", want_bias, CH, (CH,), torch.float32, pat_f),
+                ("logits", want_logits, n * frame, shape, torch.float32, pat_f)):
+            if not want:
+                continue
+            if g and dtype != torch.float32:   # (the guard pattern of a half as its 16 bits)
+                full = torch.full((numel + 2 * g,), int(pat), dtype=torch.int16, device=dev).view(dtype)
+                t = full[g: g + numel]
+            else:
+                full, t = _guarded(numel, dtype, dev, g, float(pat))
+            named[name] = (full, pat)
+            out[name] = t.view(view)
+            ptr[name] = t.data_ptr()
+        # (16 guard bytes keep the scratch 16-byte aligned; torch's allocations are)
+        gs = (g + 15) // 16 * 16
+        sfull, scratch = _guarded(nbytes, torch.uint8, dev, gs, 0xA5)
+        named["scratch"] = (sfull, np.uint8(0xA5))
+        a = SegmentationHeadBackwardArgs(
+            d_features=x.data_ptr(), dtype=codes[x.dtype], n_images=n, K=K, rows8=Hs, cols8=Ws, d_weight=w.data_ptr(),
+            n_classes=int(n_classes), n_regression=CH - int(n_classes), d_cnn_out=y.data_ptr(),
+            d_grad_out=gy.data_ptr(), grad_image_stride=gy_stride, d_grad_features=ptr["features"],
+            d_grad_weight=ptr["weight"], d_grad_bias=ptr["bias"], d_grad_logits=ptr["logits"],
+            d_scratch=scratch.data_ptr(), scratch_bytes=nbytes)
+        _check(lib().is_segmentation_head_backward(ctypes.byref(a),
+                                                   ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+               "is_segmentation_head_backward")
+        if g:
+            out["guards"] = _guards(named, g, gs)
+    return out
+
+
+def semantic_nll_scratch_bytes(n_images, rows8, cols8):
+    """is_semantic_nll_scratch_bytes: the scratch a call of that shape needs (0: a refused shape)."""
+    return int(lib().is_semantic_nll_scratch_bytes(int(n_images), int(rows8), int(cols8)))
+
+
+def semantic_nll_ptr(stream=0, **fields):
+    """is_semantic_nll on raw device pointers (ints): fields are those of SemanticNllArgs.  Asynchronous on `stream`;
+    returns the return code and raises nothing (the tests check IS_EINVAL)."""
+    a = _with_reserved(SemanticNllArgs, fields)
+    return lib().is_semantic_nll(ctypes.byref(a), ctypes.c_void_p(int(stream)))
+
+
+def semantic_nll(cnn_out, target, n_classes, ignore_index=255, grad=True, check=True, canary=0):
+    """nn.NLLLoss(reduction='mean', ignore_index) on the class planes of the head's float output, with its gradient
+    (is_semantic_nll, instance_stixels_core.h f14).
+
+    cnn_out     device float32 [n][C >= n_classes][rows8][cols8]; read in place when each frame's planes are contiguous
+    target      device uint8 or int32 [n][rows8][cols8] (what core.mode_downsample writes for the semantic labels)
+    grad        True: a new float32 tensor [n][n_classes][rows8][cols8]; a device float32 tensor [n][C'][rows8][cols8]
+                with C' >= n_classes and contiguous planes: its first n_classes planes are written in place (the
+                regression planes are left to core.offset_loss); False: no gradient
+
+    Returns (loss [1] float32, valid_count [1] int32, bad_count [1] int32, grad or None) on cnn_out's device, enqueued
+    on the current torch stream.  check=True reads bad_count back (one synchronisation) and raises CoreError when a
+    target is neither a class nor ignore_index.  canary > 0: fresh outputs and the scratch get guards, returned as a
+    dict {name: (front, back, pattern)} in fifth place."""
+    import torch
+    y = cnn_out
+    if not torch.is_tensor(y) or not y.is_cuda or y.dtype != torch.float32 or y.dim() != 4 or y.shape[1] < n_classes:
+        raise CoreError("cnn_out must be a device float32 tensor [n][C >= n_classes][rows8][cols8]")
+    dev = y.device
+    n, C, Hs, Ws = y.shape
+    y = y.detach()
+
+    def in_place(t, planes):
+        return t.stride(3) == 1 and t.stride(2) == Ws and t.stride(1) == Hs * Ws and \
+            (n == 1 or t.stride(0) >= planes * Hs * Ws)
+    if not in_place(y, n_classes):
+        y = y.contiguous()
+    y_stride = y.stride(0) if n > 1 else C * Hs * Ws
+    dtypes = {torch.uint8: DTYPE_UINT8, torch.int32: DTYPE_INT32}
+    if target.device != dev or target.dtype not in dtypes or tuple(target.shape) != (n, Hs, Ws):
+        raise CoreError(f"target must be a uint8 or int32 tensor {(n, Hs, Ws)} on cnn_out's device")
+    t = target.contiguous()
+    g = int(canary)
+    pat_f, pat_i = np.float32(-12345.0), np.int32(0x5A5A5A5A)
+    with torch.cuda.device(dev):
+        nbytes = semantic_nll_scratch_bytes(n, Hs, Ws)
+        if nbytes == 0:
+            raise CoreError(f"is_semantic_nll_scratch_bytes refuses the shape (n_images {n}, rows8 {Hs}, cols8 {Ws})")
+        named = {}
+        lfull, loss = _guarded(1, torch.float32, dev, g, float(pat_f))
+        vfull, valid = _guarded(1, torch.int32, dev, g, int(pat_i))
+        bfull, bad = _guarded(1, torch.int32, dev, g, int(pat_i))
+        named.update(loss=(lfull, pat_f), valid_count=(vfull, pat_i), bad_count=(bfull, pat_i))
+        gr, g_stride = None, 0
+        if torch.is_tensor(grad):
+            gr = grad
+            if gr.device != dev or gr.dtype != torch.float32 or gr.dim() != 4 or gr.shape[0] != n or \
+                    gr.shape[1] < n_classes or tuple(gr.shape[2:]) != (Hs, Ws) or not in_place(gr, n_classes):
+                raise CoreError("grad must be a device float32 tensor [n][C' >= n_classes][rows8][cols8] whose "
+                                "planes are contiguous")
+            g_stride = gr.stride(0) if n > 1 else n_classes * Hs * Ws
+        elif grad:
+            gfull, flat = _guarded(n * n_classes * Hs * Ws, torch.float32, dev, g, float(pat_f))
+            named["grad"] = (gfull, pat_f)
+            gr, g_stride = flat.view(n, n_classes, Hs, Ws), n_classes * Hs * Ws
+        gs = (g + 15) // 16 * 16
+        sfull, scratch = _guarded(nbytes, torch.uint8, dev, gs, 0xA5)
+        named["scratch"] = (sfull, np.uint8(0xA5))
+        a = SemanticNllArgs(d_cnn_out=y.data_ptr(), cnn_image_stride=y_stride, d_target=t.data_ptr(),
+                            target_dtype=dtypes[t.dtype], ignore_index=int(ignore_index), n_images=n, rows8=Hs,
+                            cols8=Ws, n_classes=int(n_classes), d_loss=loss.data_ptr(),
+                            d_valid_count=valid.data_ptr(), d_bad_count=bad.data_ptr(),
+                            d_grad=gr.data_ptr() if gr is not None else None, grad_image_stride=g_stride,
+                            d_scratch=scratch.data_ptr(), scratch_bytes=nbytes)
+        _check(lib().is_semantic_nll(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+               "is_semantic_nll")
+        if check:
+            nb = int(bad.item())
+            if nb:
+                raise CoreError(f"{nb} targets are neither a class in [0, {int(n_classes)}) nor ignore_index "
+                                f"{int(ignore_index)}")
+        out = (loss, valid, bad, gr)
+        if g:
+            out = out + (_guards(named, g, gs),)
+    return out

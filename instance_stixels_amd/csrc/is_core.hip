@@ -1033,6 +1033,88 @@ int is_segmentation_head(const is_segmentation_head_args* a, void* stream) {
     return IS_OK;
 }
 
+/* ---- f14: the head's backward pass and the semantic NLL loss (is_k_head_backward.hip) ---- */
+static const char* head_backward_shape_fault(int n_images, int K, int rows8, int cols8, int n_classes, long long channels) {
+    if (n_images < 1 || n_images > 65535) return "n_images outside [1, 65535]";
+    if (rows8 < 1 || cols8 < 1) return "rows8 and cols8 must be >= 1";
+    if ((long long)rows8 * cols8 > (1LL << 28)) return "rows8 * cols8 above 2^28";
+    if (K < 8 || K % 8) return "K must be >= 8 and a multiple of 8";
+    if (n_classes < 1) return "n_classes must be >= 1";
+    if (channels < n_classes) return "n_regression must be >= 0";
+    if (channels > IS_HEAD_MAX_CHANNELS) return "n_classes + n_regression above IS_HEAD_MAX_CHANNELS";
+    return nullptr;
+}
+
+size_t is_segmentation_head_backward_scratch_bytes(int n_images, int K, int rows8, int cols8, int channels) {
+    if (head_backward_shape_fault(n_images, K, rows8, cols8, 1, channels)) return 0;
+    return isk_head_backward_scratch_bytes(n_images, K, rows8, cols8, channels);
+}
+
+int is_segmentation_head_backward(const is_segmentation_head_backward_args* a, void* stream) {
+    if (!a) return fail_arg("null args");
+    if (!a->d_features || !a->d_weight || !a->d_cnn_out || !a->d_grad_out)
+        return fail_arg("null d_features, d_weight, d_cnn_out or d_grad_out");
+    if (!a->d_grad_features && !a->d_grad_weight && !a->d_grad_bias && !a->d_grad_logits)
+        return fail_arg("d_grad_features, d_grad_weight, d_grad_bias and d_grad_logits are all null");
+    if (a->dtype != IS_HEAD_F32 && a->dtype != IS_HEAD_F16 && a->dtype != IS_HEAD_BF16)
+        return fail_arg("dtype is none of IS_HEAD_F32, IS_HEAD_F16, IS_HEAD_BF16");
+    const long long CH = (long long)a->n_classes + a->n_regression;
+    if (a->n_regression < 0) return fail_arg("n_regression must be >= 0");
+    if (const char* fault = head_backward_shape_fault(a->n_images, a->K, a->rows8, a->cols8, a->n_classes, CH))
+        return fail_arg(fault);
+    if (a->grad_image_stride < CH * a->rows8 * a->cols8) return fail_arg("grad_image_stride below channels * rows8 * cols8");
+    for (int r : a->reserved)
+        if (r) return fail_arg("reserved must be 0");
+    const uintptr_t element = a->dtype == IS_HEAD_F32 ? 4 : 2;
+    if (misaligned(element, a->d_features, a->d_grad_features))
+        return fail_arg("d_features and d_grad_features must be aligned to their element");
+    if (misaligned(4, a->d_weight, a->d_cnn_out, a->d_grad_out, a->d_grad_weight, a->d_grad_bias, a->d_grad_logits))
+        return fail_arg("d_weight, d_cnn_out, d_grad_out, d_grad_weight, d_grad_bias and d_grad_logits must be 4-byte aligned");
+    if (!a->d_scratch) return fail_arg("null d_scratch");
+    if (misaligned(16, a->d_scratch)) return fail_arg("d_scratch must be 16-byte aligned");
+    if (a->scratch_bytes < isk_head_backward_scratch_bytes(a->n_images, a->K, a->rows8, a->cols8, (int)CH))
+        return fail_arg("scratch_bytes below is_segmentation_head_backward_scratch_bytes()");
+    HIP_TRY(isk_launch_segmentation_head_backward(a, (hipStream_t)stream));
+    return IS_OK;
+}
+
+static const char* semantic_nll_shape_fault(int n_images, int rows8, int cols8) {
+    if (n_images < 1 || n_images > 65535) return "n_images outside [1, 65535]";
+    if (rows8 < 1 || cols8 < 1) return "rows8 and cols8 must be >= 1";
+    if ((long long)rows8 * cols8 > (1LL << 28)) return "rows8 * cols8 above 2^28";
+    return nullptr;
+}
+
+size_t is_semantic_nll_scratch_bytes(int n_images, int rows8, int cols8) {
+    if (semantic_nll_shape_fault(n_images, rows8, cols8) || (long long)n_images * rows8 * cols8 > 0x7fffffffLL) return 0;
+    return isk_semantic_nll_scratch_bytes(n_images, rows8, cols8);
+}
+
+int is_semantic_nll(const is_semantic_nll_args* a, void* stream) {
+    if (!a) return fail_arg("null args");
+    if (!a->d_cnn_out || !a->d_target) return fail_arg("null d_cnn_out or d_target");
+    if (!a->d_loss || !a->d_valid_count || !a->d_bad_count) return fail_arg("null d_loss, d_valid_count or d_bad_count");
+    if (a->target_dtype != IS_DTYPE_UINT8 && a->target_dtype != IS_DTYPE_INT32)
+        return fail_arg("target_dtype is neither IS_DTYPE_UINT8 nor IS_DTYPE_INT32");
+    if (const char* fault = semantic_nll_shape_fault(a->n_images, a->rows8, a->cols8)) return fail_arg(fault);
+    if ((long long)a->n_images * a->rows8 * a->cols8 > 0x7fffffffLL) return fail_arg("n_images * rows8 * cols8 does not fit 31 bits");
+    if (a->n_classes < 1 || a->n_classes > IS_HEAD_MAX_CHANNELS) return fail_arg("n_classes outside [1, IS_HEAD_MAX_CHANNELS]");
+    const long long planes = (long long)a->n_classes * a->rows8 * a->cols8;
+    if (a->cnn_image_stride < planes) return fail_arg("cnn_image_stride below n_classes * rows8 * cols8");
+    if (a->d_grad && a->grad_image_stride < planes) return fail_arg("grad_image_stride below n_classes * rows8 * cols8");
+    for (int r : a->reserved)
+        if (r) return fail_arg("reserved must be 0");
+    if (misaligned(4, a->d_cnn_out, a->d_loss, a->d_valid_count, a->d_bad_count, a->d_grad))
+        return fail_arg("d_cnn_out, d_loss, d_valid_count, d_bad_count and d_grad must be 4-byte aligned");
+    if (a->target_dtype == IS_DTYPE_INT32 && misaligned(4, a->d_target)) return fail_arg("d_target must be aligned to its element");
+    if (!a->d_scratch) return fail_arg("null d_scratch");
+    if (misaligned(16, a->d_scratch)) return fail_arg("d_scratch must be 16-byte aligned");
+    if (a->scratch_bytes < isk_semantic_nll_scratch_bytes(a->n_images, a->rows8, a->cols8))
+        return fail_arg("scratch_bytes below is_semantic_nll_scratch_bytes()");
+    HIP_TRY(isk_launch_semantic_nll(a, (hipStream_t)stream));
+    return IS_OK;
+}
+
 /* ---- f9: per-instance objects and contours (is_k_objects.hip) ---- */
 int is_instance_objects(const is_instance_objects_args* a, void* stream) {
     if (!a) return fail_arg("null args");

@@ -5,7 +5,13 @@ frame and per instance id and of the autograd replay behind it.
 
 The classes keep the reference's constructor keywords and call signatures.  The weights reach the device as float32
 (1e-3 becomes 0.001000000047..), the one deviation from the reference's Python floats.  Predictions in fp16 / bf16 are
-converted with .float()."""
+converted with .float().
+
+SegmentationHead and SemanticNLLLoss (f14) close the path to the parameters: the head module runs f13's launch in its
+forward and one call of is_segmentation_head_backward in its backward, so a model is trained with the numerics it is
+deployed with, and a training step gives the same bytes on every run."""
+import math
+
 import torch
 
 from . import core
@@ -97,3 +103,100 @@ class OffsetLossSL:
         loss5, _ = _OffsetLossFunction.apply(p, _ids8(batch_instance_gt, p.device), None, w, False, self.capacity,
                                              self.check)
         return loss5[0]
+
+
+class _SegmentationHeadFunction(torch.autograd.Function):
+    """Forward: f13's launch (the float output only).  Backward: one call of is_segmentation_head_backward that asks
+    for the gradients autograd needs and no others."""
+
+    @staticmethod
+    def forward(ctx, features, weight, bias, n_classes):
+        rows8 = features.shape[2]
+        p2s = 1 << rows8.bit_length()                     # a power of two >= rows8 + 1; the int tensor is not made
+        y = core.segmentation_head(features.detach(), weight.detach(), bias.detach(), n_classes, p2s,
+                                   want_segmentation=False)
+        ctx.save_for_backward(features, weight, y)
+        ctx.n_classes = n_classes
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        features, weight, y = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        if not (need_x or need_w or need_b):
+            return None, None, None, None
+        g = core.segmentation_head_backward(features, weight, y, grad_y.float(), ctx.n_classes, want_features=need_x,
+                                            want_weight=need_w, want_bias=need_b)
+        gw = g["weight"].view(weight.shape) if need_w else None
+        return g.get("features"), gw, g.get("bias"), None
+
+
+class SegmentationHead(torch.nn.Module):
+    """The head of the reference's models (DRNDownsampled.py:80-102, 119-137) on the device with fixed numerics: the
+    1x1 convolution `seg`, -log_softmax over the first n_classes channels, the regression channels behind them.
+    `weight` [channels][K][1][1] and `bias` [channels] take the reference's `seg` state; the initialisation is the
+    reference's (DRNDownsampled.py:82-85).  forward(features) returns float32 [n][channels][rows8][cols8], features
+    being float32, float16 or bfloat16 [n][K][rows8][cols8] on the device; it is differentiable in the features, the
+    weight and the bias.  clamp = (channel, lo, hi) clamps one regression channel in eval mode only, as
+    DRNDSOffsetDisparity does (:133-134); that output cannot be differentiated."""
+
+    def __init__(self, in_features, n_classes, n_regression=2, clamp=None):
+        super().__init__()
+        channels = n_classes + n_regression
+        if not 1 <= n_classes <= channels <= core.HEAD_MAX_CHANNELS:
+            raise core.CoreError(f"n_classes >= 1, n_regression >= 0 and at most {core.HEAD_MAX_CHANNELS} channels")
+        self.n_classes, self.clamp = int(n_classes), clamp
+        self.weight = torch.nn.Parameter(torch.empty(channels, in_features, 1, 1))
+        self.bias = torch.nn.Parameter(torch.zeros(channels))
+        with torch.no_grad():
+            self.weight.normal_(0, math.sqrt(2.0 / channels))   # n = 1 * 1 * out_channels
+
+    def forward(self, features):
+        if not self.training and self.clamp is not None:
+            if torch.is_grad_enabled() and (features.requires_grad or self.weight.requires_grad
+                                            or self.bias.requires_grad):
+                raise core.CoreError("the clamped eval-mode output is not differentiable: call it under "
+                                     "torch.no_grad(), or train() the module")
+            p2s = 1 << int(features.shape[2]).bit_length()
+            return core.segmentation_head(features, self.weight, self.bias, self.n_classes, p2s,
+                                          want_segmentation=False, clamp=self.clamp)
+        return _SegmentationHeadFunction.apply(features, self.weight, self.bias, self.n_classes)
+
+
+class _SemanticNLLFunction(torch.autograd.Function):
+    """As _OffsetLossFunction: the forward makes the gradient at unit scale, the backward scales it."""
+
+    @staticmethod
+    def forward(ctx, classes, target, ignore_index, check):
+        loss, _, _, grad = core.semantic_nll(classes.detach(), target, classes.shape[1], ignore_index=ignore_index,
+                                             grad=True, check=check)
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        grad, = ctx.saved_tensors
+        return grad * grad_loss[0], None, None, None
+
+
+class SemanticNLLLoss:
+    """nn.NLLLoss(reduction='mean', ignore_index=255) of the reference's training (train.py:281-282, 325-326) on the
+    head's class channels, which hold -log p: output [n][C][rows8][cols8] float32, all of whose channels are classes
+    unless n_classes says that only the first n_classes are (a channel slice of the head's output is read in place);
+    target [n][rows8][cols8] uint8 or int32 (other integer types are converted to int32).  Returns the loss, a scalar
+    on the device; loss.backward() works.  check: see core.semantic_nll."""
+
+    def __init__(self, ignore_index=255, n_classes=None, check=True):
+        self.ignore_index, self.n_classes, self.check = int(ignore_index), n_classes, check
+
+    def __call__(self, output, target):
+        t = target
+        if t.dim() == 4 and t.shape[1] == 1:
+            t = t[:, 0]
+        t = t.to(output.device)
+        if t.dtype not in (torch.uint8, torch.int32):
+            t = t.to(torch.int32)
+        out = output if output.dtype == torch.float32 else output.float()
+        if self.n_classes is not None:
+            out = out[:, :int(self.n_classes)]
+        return _SemanticNLLFunction.apply(out, t, self.ignore_index, self.check)[0]
