@@ -343,6 +343,22 @@ public:
      * SetSegmentationHead, for n_images outside [1, max_batch] and for what is_segmentation_head refuses. */
     void SegmentationHeadBatch(int n_images, const void* d_features, int dtype, int32_t* d_segmentation,
                                float* d_cnn_out = nullptr, void* stream = nullptr);
+    /* f15 (an addition): the CNN's own label image of a batch at full resolution and its confusion table, the row the
+     * reference's evaluation prints beside the stixels' (tools/run_cityscapes.py:353-365, 551), as is_cnn_label_maps
+     * defines it.  d_cnn_out [n_images][channels][rows / 8][realcols] fp32 is SegmentationHeadBatch's float output;
+     * mode is IS_CNN_UP_NEAREST or IS_CNN_UP_DECONV.  rows, cols, rows / 8, realcols and the channel split are the
+     * initialised object's, so a caller cannot mismatch them.  A producer like SegmentationHeadBatch: valid before any
+     * compute call, one asynchronous launch on `stream`, the record of the last batch untouched.  Throws
+     * std::invalid_argument for n_images outside [1, max_batch] and for what is_cnn_label_maps refuses. */
+    struct CnnLabelTargets {
+        uint8_t* class8 = nullptr;          /* [n][rows / 8][realcols]: the class of every cell */
+        uint8_t* label = nullptr;           /* [n][rows][cols] labelIds (Cityscapes trainId -> labelId) */
+        const uint8_t* gt_label = nullptr;  /* [n][rows][cols], with confusion */
+        int n_labels = 34;
+        unsigned long long* confusion = nullptr; /* [n_labels][n_labels], added to */
+    };
+    void CnnLabelBatch(int n_images, const float* d_cnn_out, int mode, const CnnLabelTargets& targets,
+                       void* stream = nullptr);
     /* Back to the cluster labels of the last compute call. */
     void UseClusterInstances() { m_last.gt_instances = false; }
     /* The vote's parameters (defaults: the reference's): the minimum fraction of the 10 % rule, the labelIds of

@@ -1015,6 +1015,75 @@ typedef struct is_semantic_nll_args {
 size_t is_semantic_nll_scratch_bytes(int n_images, int rows8, int cols8);
 int is_semantic_nll(const is_semantic_nll_args* args, void* stream);
 
+/* ---- f15: the CNN's own label maps of a batch at full resolution, scored on the device (is_k_cnn_labels.hip) -------
+ * The reference's evaluation prints the IoU of the CNN alone beside the stixels' (tools/run_cityscapes.py:353-365,
+ * 551: run_cityscapesevaluation_CNN on the labelImg.png files under probs/) and its training selects models by it
+ * (tools/CNN_training/train.py:559-605, validation_snapshot).  The label image behind that row is the per-pixel
+ * arg-min of the network output brought to full resolution: by interpolate(scale_factor=8, mode='nearest') for the
+ * downsampled models (tools/CNN_training/inference.py:286-292, 373-381), by the fixed bilinear `up` layer for the
+ * full-resolution ones (models/DRNSeg.py:35-44, 64-79: ConvTranspose2d(C, C, 16, stride=8, padding=4, groups=C)
+ * with fill_up_weights).  Here in one launch from f13's d_cnn_out: no upsampled plane is ever written, the label
+ * image is written once and the ground truth is read once for f5's confusion table.
+ *
+ *   Inputs.   The planes are costs, as the DP reads them: v[c] = d_cnn_out[i][c][y][x] for c < n_classes (f13's
+ *             -log_softmax).  Planes n_classes .. channels-1 are not read.
+ *   Arg-min.  The class of a value vector is the first strict minimum in increasing c:
+ *             best = 0; for c = 1 ..: if (v[c] < v[best]) best = c.  A NaN never replaces the current best; all-NaN
+ *             gives 0.
+ *   d_class8  the class of the cell's own n_classes values, in both modes.
+ *   IS_CNN_UP_NEAREST   pixel (Y, X) with X < 8 * cols8 takes the class of cell (Y / 8, X / 8).
+ *   IS_CNN_UP_DECONV    the 1-D weight of tap k in 0..15 is W[k] = (2 * min(k, 15 - k) + 1) / 16.0f.  Output
+ *             coordinate o receives input i in {(o + 4) / 8 - 1, (o + 4) / 8} intersected with [0, n), with
+ *             k = o + 4 - 8 i; the 2-D weight is W[ky] * W[kx], exact in fp32.  The upsampled value of class c is the
+ *             fp32 chain acc = fmaf(w, v, acc) from +0.0f over the taps in the order (iy low, ix low), (iy low,
+ *             ix high), (iy high, ix low), (iy high, ix high).  A tap outside the plane is SKIPPED, not multiplied by
+ *             zero: +inf in a border cell stays +inf and never becomes NaN.  The pixel's class is the arg-min rule
+ *             on those values.  (The reference applies `up` to the logits and takes the arg-max of their log-softmax.
+ *             By linearity the upsampled cost planes differ from the upsampled logits by a per-pixel constant and
+ *             the sign, so the two agree in exact arithmetic; in fp32 they may differ at near-ties.  The contract is
+ *             the chain on the cost planes.)
+ *   d_label   class_to_label[class]; a class outside the table gives 0; pixels with X >= 8 * cols8 are 0.  Every
+ *             element is written.
+ *   d_confusion   f5's convention, what evaluation.cityscapes_iou takes: [n_labels][n_labels] uint64, ADDED to:
+ *             conf[gt][pred] += 1 for every pixel with X < 8 * cols8, gt < n_labels and pred < n_labels, summed over
+ *             the batch.  Integer atomics only: the same table on every run.
+ *   A frame's outputs do not depend on its position in the batch or on n_images; no address depends on a value.
+ *
+ * Zero-initialise, then set the fields.  All device arrays on the current device.
+ *   d_cnn_out           [n_images][channels][rows8][cols8] fp32, 4-byte aligned
+ *   n_images, channels, n_classes, rows8, cols8   n_images in [1, 65535]; n_classes in [1, IS_HEAD_MAX_CHANNELS];
+ *                       channels >= n_classes; rows8, cols8 >= 1; channels * rows8 * cols8 < 2^31
+ *   mode                IS_CNN_UP_NEAREST or IS_CNN_UP_DECONV
+ *   rows, cols          the image: rows == 8 * rows8, cols >= 8 * cols8, rows * cols < 2^31
+ *   h_class_to_label    host [n_classes]; NULL: Cityscapes trainId -> labelId, as f5 (19 entries)
+ *   d_class8            optional [n_images][rows8][cols8] uint8
+ *   d_label             optional [n_images][rows][cols] uint8
+ *   d_gt_label, d_confusion   both or neither: gt [n_images][rows][cols] uint8; the table 8-byte aligned, n_labels in
+ *                       [1, IS_RENDER_MAX_LABELS]
+ *   reserved            0 */
+#define IS_CNN_UP_NEAREST 0   /* inference.py:286-292 */
+#define IS_CNN_UP_DECONV  1   /* DRNSeg.py: the fixed 16 / 8 / 4 transposed convolution */
+typedef struct is_cnn_label_args {
+    const float* d_cnn_out;
+    int n_images, channels, n_classes, rows8, cols8;
+    int mode;
+    int rows, cols;
+    const uint8_t* h_class_to_label;
+    uint8_t* d_class8;
+    uint8_t* d_label;
+    const uint8_t* d_gt_label;
+    int n_labels;
+    unsigned long long* d_confusion;
+    int reserved[4]; /* 0 */
+} is_cnn_label_args;
+
+/* One launch on `stream`, asynchronous and stream-ordered; no allocation, copy or synchronisation.  IS_EINVAL, with
+ * the reason in is_last_error() and before the device is touched, for null args, a null d_cnn_out, no output at all,
+ * only one of d_gt_label and d_confusion, an unknown mode, rows != 8 * rows8 or cols < 8 * cols8, a shape, n_classes,
+ * channels or n_labels outside the ranges above, n_images outside [1, 65535], rows * cols or channels * rows8 * cols8
+ * of 2^31 or more, a misaligned d_cnn_out or d_confusion and a non-zero reserved field. */
+int is_cnn_label_maps(const is_cnn_label_args* args, void* stream);
+
 /* ---- f9: per-instance objects and their contours (is_k_objects.hip) ------------------------------------------------
  * What the reference's consumers reduce on the host from the per-stixel output: the top-down view
  * (tools/visualization/clustering_visualization.py:563-792: per instance and column the closest stixel, connected

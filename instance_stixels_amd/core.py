@@ -10,6 +10,7 @@ import os
 import numpy as np
 
 from .config import StixelParams, SECTION_DTYPE, INSTANCE_CLASSES
+from .evaluation import CITYSCAPES_N_LABELS
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IS_CORE_LIB", os.path.join(_HERE, "lib", "libis_core.so"))
@@ -43,6 +44,7 @@ EXPORTS = [
     "is_segmentation_head",
     "is_segmentation_head_backward_scratch_bytes", "is_segmentation_head_backward",
     "is_semantic_nll_scratch_bytes", "is_semantic_nll",
+    "is_cnn_label_maps",
 ]
 RENDER_MAX_LABELS = 64    # IS_RENDER_MAX_LABELS
 RENDER_MAX_CLASSES = 256  # IS_RENDER_MAX_CLASSES
@@ -215,6 +217,18 @@ class SemanticNllArgs(ctypes.Structure):
                 ("reserved", ci * 4)]
 
 
+CNN_UP_NEAREST, CNN_UP_DECONV = 0, 1  # IS_CNN_UP_*
+CNN_UP_MODES = {"nearest": CNN_UP_NEAREST, "deconv": CNN_UP_DECONV}
+
+
+class CnnLabelArgs(ctypes.Structure):
+    """is_cnn_label_args: zero-initialised by ctypes; device pointers as ints, h_class_to_label a host pointer."""
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    _fields_ = [("d_cnn_out", vp), ("n_images", ci), ("channels", ci), ("n_classes", ci), ("rows8", ci), ("cols8", ci),
+                ("mode", ci), ("rows", ci), ("cols", ci), ("h_class_to_label", vp), ("d_class8", vp), ("d_label", vp),
+                ("d_gt_label", vp), ("n_labels", ci), ("d_confusion", vp), ("reserved", ci * 4)]
+
+
 class RoadParams(ctypes.Structure):
     """is_road_params: one frame's road, the layout of Stixels::RoadParameters (16 bytes)"""
     _fields_ = [("vhor", ctypes.c_int), ("tilt", ctypes.c_float), ("height", ctypes.c_float),
@@ -310,6 +324,7 @@ def lib():
         L.is_semantic_nll_scratch_bytes.argtypes = [ci, ci, ci]
         L.is_semantic_nll_scratch_bytes.restype = ctypes.c_size_t
         L.is_semantic_nll.argtypes = [ctypes.POINTER(SemanticNllArgs), vp]
+        L.is_cnn_label_maps.argtypes = [ctypes.POINTER(CnnLabelArgs), vp]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
         L.is_get_device.argtypes = [ctypes.POINTER(ci)]
@@ -1309,4 +1324,99 @@ def semantic_nll(cnn_out, target, n_classes, ignore_index=255, grad=True, check=
         out = (loss, valid, bad, gr)
         if g:
             out = out + (_guards(named, g, gs),)
+    return out
+
+
+def cnn_label_maps_ptr(stream=0, class_to_label=None, **fields):
+    """is_cnn_label_maps on raw device pointers (ints): fields are those of CnnLabelArgs; class_to_label: a host
+    sequence of n_classes label values, None for Cityscapes trainId -> labelId.  Asynchronous on `stream`; returns the
+    return code and raises nothing (the tests check IS_EINVAL)."""
+    a = _with_reserved(CnnLabelArgs, fields)
+    table = None
+    if class_to_label is not None:
+        table = np.ascontiguousarray(class_to_label, np.uint8)
+        a.h_class_to_label = table.ctypes.data
+    return lib().is_cnn_label_maps(ctypes.byref(a), ctypes.c_void_p(int(stream)))
+
+
+def cnn_label_maps(cnn_out, n_classes, mode="nearest", cols=None, gt_label=None, n_labels=CITYSCAPES_N_LABELS,
+                   confusion=None, want_label=True, want_class8=False, class_to_label=None, canary=0, stream=0):
+    """The CNN's own label image of a batch at full resolution and its confusion table in one launch
+    (is_cnn_label_maps, instance_stixels_core.h f15).
+
+    cnn_out     device float32 [n][channels >= n_classes][rows8][cols8]: the float output of core.segmentation_head
+                (costs: the arg-min is the class); made contiguous
+    mode        "nearest" (each cell's class in its 8 x 8 pixels) or "deconv" (the reference's fixed bilinear
+                transposed convolution of the planes, then the arg-min per pixel)
+    cols        the image width, >= 8 * cols8 (the default); the pixels right of 8 * cols8 are 0 and are not scored
+    gt_label    device uint8 [n][8 * rows8][cols]: with it the confusion table [n_labels][n_labels] (int64 on the
+                device, gt x pred; n_labels defaults to the 34 Cityscapes labelIds) is ADDED to `confusion` (a device
+                int64 tensor of that shape), or to a new zero table; what evaluation.cityscapes_iou takes
+    class_to_label   a host sequence of n_classes label values; None: Cityscapes trainId -> labelId
+
+    Returns a dict with the requested ones of "label" (uint8 [n][8 * rows8][cols]), "class8" (uint8 [n][rows8][cols8])
+    and "confusion", on cnn_out's device, enqueued on `stream` or else the current torch stream.  canary > 0: fresh
+    outputs get that many guard elements in front and behind, and the dict has "guards": {name: (front, back,
+    pattern)} (one synchronisation)."""
+    import torch
+    y = cnn_out
+    if not torch.is_tensor(y) or not y.is_cuda or y.dtype != torch.float32 or y.dim() != 4:
+        raise CoreError("cnn_out must be a device float32 tensor [n][channels][rows8][cols8]")
+    if mode not in CNN_UP_MODES:
+        raise CoreError(f"mode {mode!r} is neither 'nearest' nor 'deconv'")
+    y = y.detach().contiguous()
+    dev = y.device
+    n, CH, Hs, Ws = y.shape
+    rows = 8 * Hs
+    cols = 8 * Ws if cols is None else int(cols)
+    if cols < 8 * Ws:
+        raise CoreError(f"cols {cols} is below 8 * cols8 = {8 * Ws}")
+    if confusion is not None and gt_label is None:
+        raise CoreError("a confusion table needs gt_label")
+    if not (want_label or want_class8 or gt_label is not None):
+        raise CoreError("no output is asked for")
+    table = None if class_to_label is None else np.ascontiguousarray(class_to_label, np.uint8)
+    if table is not None and table.size != int(n_classes):
+        raise CoreError(f"class_to_label holds {table.size} values, n_classes is {int(n_classes)}")
+    g = int(canary)
+    pat8, pat64 = np.uint8(0xA5), np.int64(0x5A5A5A5A5A5A5A5A)
+    with torch.cuda.device(dev):
+        named, out = {}, {}
+        ptr = {"label": None, "class8": None}
+        for name, want, shape in (("label", want_label, (n, rows, cols)), ("class8", want_class8, (n, Hs, Ws))):
+            if want:
+                full, t = _guarded(n * shape[1] * shape[2], torch.uint8, dev, g, int(pat8))
+                named[name] = (full, pat8)
+                out[name] = t.view(shape)
+                ptr[name] = t.data_ptr()
+        gt = conf = None
+        if gt_label is not None:
+            gt, nl = gt_label, int(n_labels)
+            if not torch.is_tensor(gt) or gt.device != dev or gt.dtype != torch.uint8 or \
+                    tuple(gt.shape) != (n, rows, cols):
+                raise CoreError(f"gt_label must be a uint8 tensor {(n, rows, cols)} on cnn_out's device")
+            gt = gt.contiguous()
+            if confusion is None:
+                full, flat = _guarded(nl * nl, torch.int64, dev, g, int(pat64))
+                flat.zero_()   # (the table is added to)
+                conf = flat.view(nl, nl)
+                if g:
+                    named["confusion"] = (full, pat64)
+            else:
+                conf = confusion
+                if not torch.is_tensor(conf) or conf.device != dev or conf.dtype != torch.int64 or \
+                        tuple(conf.shape) != (nl, nl) or not conf.is_contiguous():
+                    raise CoreError(f"confusion must be a contiguous int64 tensor {(nl, nl)} on cnn_out's device")
+            out["confusion"] = conf
+        a = CnnLabelArgs(d_cnn_out=y.data_ptr(), n_images=n, channels=CH, n_classes=int(n_classes), rows8=Hs, cols8=Ws,
+                         mode=CNN_UP_MODES[mode], rows=rows, cols=cols,
+                         h_class_to_label=table.ctypes.data if table is not None else None,
+                         d_class8=ptr["class8"], d_label=ptr["label"],
+                         d_gt_label=gt.data_ptr() if gt is not None else None,
+                         n_labels=int(n_labels) if gt is not None else 0,
+                         d_confusion=conf.data_ptr() if conf is not None else None)
+        s = int(stream) if stream else torch.cuda.current_stream(dev).cuda_stream
+        _check(lib().is_cnn_label_maps(ctypes.byref(a), ctypes.c_void_p(s)), "is_cnn_label_maps")
+        if g:
+            out["guards"] = _guards(named, g, g)
     return out

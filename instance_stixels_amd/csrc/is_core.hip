@@ -1115,6 +1115,40 @@ int is_semantic_nll(const is_semantic_nll_args* a, void* stream) {
     return IS_OK;
 }
 
+/* ---- f15: the CNN's label maps and their confusion table (is_k_cnn_labels.hip) ---- */
+int is_cnn_label_maps(const is_cnn_label_args* a, void* stream) {
+    if (!a) return fail_arg("null args");
+    if (!a->d_cnn_out) return fail_arg("null d_cnn_out");
+    if (!a->d_class8 && !a->d_label && !a->d_confusion) return fail_arg("no output: d_class8, d_label and d_confusion are all null");
+    if (!a->d_confusion != !a->d_gt_label) return fail_arg("d_confusion and d_gt_label go together");
+    if (a->mode != IS_CNN_UP_NEAREST && a->mode != IS_CNN_UP_DECONV)
+        return fail_arg("mode is neither IS_CNN_UP_NEAREST nor IS_CNN_UP_DECONV");
+    if (a->n_images < 1 || a->n_images > 65535) return fail_arg("n_images outside [1, 65535]");
+    if (a->rows8 < 1 || a->cols8 < 1) return fail_arg("rows8 and cols8 must be >= 1");
+    if (a->n_classes < 1 || a->n_classes > IS_HEAD_MAX_CHANNELS) return fail_arg("n_classes outside [1, IS_HEAD_MAX_CHANNELS]");
+    if (a->channels < a->n_classes) return fail_arg("channels below n_classes");
+    if ((long long)a->rows != 8LL * a->rows8) return fail_arg("rows must be 8 * rows8");
+    if ((long long)a->cols < 8LL * a->cols8) return fail_arg("cols below 8 * cols8");
+    if ((long long)a->rows * a->cols > 0x7fffffffLL) return fail_arg("rows * cols does not fit 31 bits");
+    if ((long long)a->channels * a->rows8 * a->cols8 > 0x7fffffffLL)
+        return fail_arg("channels * rows8 * cols8 does not fit 31 bits");
+    if (a->d_confusion && (a->n_labels < 1 || a->n_labels > IS_RENDER_MAX_LABELS))
+        return fail_arg("n_labels outside [1, IS_RENDER_MAX_LABELS]");
+    for (int r : a->reserved)
+        if (r) return fail_arg("reserved must be 0");
+    if (misaligned(4, a->d_cnn_out)) return fail_arg("d_cnn_out must be 4-byte aligned");
+    if (misaligned(8, a->d_confusion)) return fail_arg("d_confusion must be 8-byte aligned");
+    /* Cityscapes trainId -> labelId, the default table of is_render_sections */
+    static const uint8_t kCityscapes[19] = {7, 8, 11, 12, 13, 17, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 31, 32, 33};
+    uint8_t table[IS_HEAD_MAX_CHANNELS] = {0};
+    if (a->h_class_to_label)
+        memcpy(table, a->h_class_to_label, a->n_classes);
+    else
+        memcpy(table, kCityscapes, sizeof(kCityscapes));
+    HIP_TRY(isk_launch_cnn_labels(a, table, (hipStream_t)stream));
+    return IS_OK;
+}
+
 /* ---- f9: per-instance objects and contours (is_k_objects.hip) ---- */
 int is_instance_objects(const is_instance_objects_args* a, void* stream) {
     if (!a) return fail_arg("null args");

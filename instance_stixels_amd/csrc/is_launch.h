@@ -255,6 +255,9 @@ hipError_t isk_launch_segmentation_head_backward(const is_segmentation_head_back
 size_t isk_semantic_nll_scratch_bytes(int n_images, int Hs, int Ws);
 hipError_t isk_launch_semantic_nll(const is_semantic_nll_args* a, hipStream_t stream);
 
+/* is_k_cnn_labels.hip */
+hipError_t isk_launch_cnn_labels(const is_cnn_label_args* r, const uint8_t* table, hipStream_t stream);
+
 /* is_k_objects.hip */
 hipError_t isk_launch_instance_objects(const is_instance_objects_args* r, hipStream_t stream);
 

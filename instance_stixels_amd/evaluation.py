@@ -288,3 +288,31 @@ def gt_offset_scores(st, pairwise, d_disparity_big, d_segmentation, road, gt_ins
     ev = evaluator if evaluator is not None else CityscapesInstanceEval()
     ev.add(overlaps)
     return dict(stixels=stixels, overlaps=overlaps, result=ev.result())
+
+
+# ---- the CNN alone: the second semantic row of the reference's evaluation --------------------------------------------
+def cnn_scores(cnn_out, gt_label, n_classes=19, mode="nearest", confusion=None):
+    """The IoU of the CNN's own label image, the row the reference prints beside the stixels'
+    (tools/run_cityscapes.py:353-365, 551) and selects models by (tools/CNN_training/train.py:559-605), on the device:
+    core.cnn_label_maps without a label image (is_cnn_label_maps, metrics only) adds the batch to the confusion
+    table, and cityscapes_iou scores the table.
+
+    cnn_out     device float32 [n][channels >= n_classes][rows8][cols8], the float output of core.segmentation_head
+    gt_label    device uint8 [n][8 * rows8][cols >= 8 * cols8] of Cityscapes labelIds
+    mode        "nearest" (the downsampled models) or "deconv" (the full-resolution ones)
+    confusion   the "confusion" of an earlier call (a device int64 tensor [34][34]): this batch is added to it, so a
+                validation loop passes it back in batch after batch; None: a new table
+
+    Returns dict(confusion = the table on the device, iou = per-class IoU [19], mean_iou); reading the table back is
+    the call's one synchronisation.  With cnn_out None nothing is launched and `confusion` (a tensor or an array) is
+    scored as it is."""
+    if cnn_out is not None:
+        from . import core
+        confusion = core.cnn_label_maps(cnn_out, n_classes, mode=mode, cols=int(gt_label.shape[-1]), gt_label=gt_label,
+                                        n_labels=CITYSCAPES_N_LABELS, confusion=confusion,
+                                        want_label=False)["confusion"]
+    elif confusion is None:
+        raise ValueError("cnn_scores: neither a network output nor a table")
+    host = confusion.cpu().numpy() if hasattr(confusion, "cpu") else np.asarray(confusion)
+    iou, mean = cityscapes_iou(host)
+    return dict(confusion=confusion, iou=iou, mean_iou=mean)

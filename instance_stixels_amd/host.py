@@ -39,6 +39,7 @@ EXPORTS = [
     "ish_active_device", "ish_sweep_sections", "ish_recluster_batch",
     "ish_cluster_instance_disparity_batch", "ish_set_instance_disparity_capacity",
     "ish_set_segmentation_head", "ish_set_segmentation_head_clamp", "ish_segmentation_head_batch",
+    "ish_cnn_label_batch",
 ]
 WORLD_DTYPE = _core.WORLD_DTYPE  # is_world_stixel, the records of Stixels.WorldBatch
 OBJECT_DTYPE = _core.OBJECT_DTYPE    # is_instance_object, the objects of Stixels.InstanceObjectsBatch
@@ -136,6 +137,7 @@ def lib():
         L.ish_set_segmentation_head.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ci]
         L.ish_set_segmentation_head_clamp.argtypes = [vp, ci, cf, cf]
         L.ish_segmentation_head_batch.argtypes = [vp, ci, vp, ci, vp, vp, vp]
+        L.ish_cnn_label_batch.argtypes = [vp, ci, vp, ci, vp, vp, vp, ci, vp, vp]
         L.ish_core_sweep_set.argtypes = [vp, ctypes.POINTER(_core.SweepSet)]
         L.ish_sweep_batch.argtypes = [vp, ci, ci, vp, vp, vp, vp, ci, ci, vp]
         L.ish_select_sweep_set.argtypes = [vp, ci]
@@ -520,6 +522,19 @@ class Stixels:
             ctypes.c_void_p(int(d_segmentation)) if d_segmentation else None,
             ctypes.c_void_p(int(d_cnn_out)) if d_cnn_out else None, ctypes.c_void_p(int(stream))),
             "SegmentationHeadBatch")
+
+    def CnnLabelBatch(self, n, d_cnn_out, mode, d_class8=0, d_label=0, d_gt_label=0, n_labels=34, d_confusion=0,
+                      stream=0):
+        """Stixels::CnnLabelBatch (device pointers as ints): d_cnn_out [n][channels][rows / 8][realcols] float32, the
+        float output of SegmentationHeadBatch, and mode core.CNN_UP_NEAREST / CNN_UP_DECONV -> the optional d_class8
+        [n][rows / 8][realcols] and d_label [n][rows][cols] uint8, and with d_gt_label [n][rows][cols] uint8 the
+        confusion table d_confusion [n_labels][n_labels] uint64, which is added to.  A producer: legal before any
+        compute call, one asynchronous launch on `stream`."""
+        def p(v):
+            return ctypes.c_void_p(int(v)) if v else None
+        self._check(lib().ish_cnn_label_batch(self._h, int(n), p(d_cnn_out), int(mode), p(d_class8), p(d_label),
+                                              p(d_gt_label), int(n_labels), p(d_confusion), p(stream)),
+                    "CnnLabelBatch")
 
     # ---- parameter sweeps ------------------------------------------------------------
     def SweepBatch(self, pairwise, d_disparity_big, d_segmentation, road, sets, with_instances=True, stream=0):

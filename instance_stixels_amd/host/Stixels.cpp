@@ -865,6 +865,31 @@ void Stixels::SegmentationHeadBatch(int n_images, const void* d_features, int dt
     CheckConsumer("SegmentationHeadBatch", is_segmentation_head(&a, stream));
 }
 
+/* The CNN row of the reference's evaluation (tools/run_cityscapes.py:353-365, 551) from the head's float output. */
+void Stixels::CnnLabelBatch(int n_images, const float* d_cnn_out, int mode, const CnnLabelTargets& t, void* stream) {
+    if (!m_is_initialized) throw std::invalid_argument("CnnLabelBatch: the object is not initialised.");
+    if (n_images < 1 || n_images > m_max_batch)
+        throw std::invalid_argument("CnnLabelBatch: n_images outside [1, max_batch] of InitializeBatch().");
+    const DeviceGuard guard(m_ctx_device);
+    if (stream == nullptr) stream = m_stream;
+    is_cnn_label_args a = {};
+    a.d_cnn_out = d_cnn_out;
+    a.n_images = n_images;
+    a.channels = m_segmentation_channels;
+    a.n_classes = m_segmentation_classes;
+    a.rows8 = m_rows / 8;
+    a.cols8 = m_realcols;
+    a.mode = mode;
+    a.rows = m_rows;
+    a.cols = m_cols;
+    a.d_class8 = t.class8;
+    a.d_label = t.label;
+    a.d_gt_label = t.gt_label;
+    a.n_labels = t.n_labels;
+    a.d_confusion = t.confusion;
+    CheckConsumer("CnnLabelBatch", is_cnn_label_maps(&a, stream));
+}
+
 void Stixels::SetGTAssignmentParameters(double min_fraction, const int* label_ids8, bool gt_is_train_ids) {
     static const int kCityscapes[IS_INSTANCE_CLASSES] = {24, 25, 26, 27, 28, 31, 32, 33};
     if (min_fraction != min_fraction) throw std::invalid_argument("SetGTAssignmentParameters: min_fraction is NaN.");

@@ -437,6 +437,20 @@ int ish_segmentation_head_batch(void* h, int n, const void* d_features, int dtyp
                                 float* d_cnn_out, void* stream) {
     return guard([&] { ((Stixels*)h)->SegmentationHeadBatch(n, d_features, dtype, d_segmentation, d_cnn_out, stream); });
 }
+/* CnnLabelBatch(): the head's float output -> the CNN's label image, cell classes and confusion table (each may be
+ * null; gt_label and confusion go together); asynchronous on `stream`. */
+int ish_cnn_label_batch(void* h, int n, const float* d_cnn_out, int mode, uint8_t* d_class8, uint8_t* d_label,
+                        const uint8_t* d_gt_label, int n_labels, unsigned long long* d_confusion, void* stream) {
+    return guard([&] {
+        Stixels::CnnLabelTargets t;
+        t.class8 = d_class8;
+        t.label = d_label;
+        t.gt_label = d_gt_label;
+        t.n_labels = n_labels;
+        t.confusion = d_confusion;
+        ((Stixels*)h)->CnnLabelBatch(n, d_cnn_out, mode, t, stream);
+    });
+}
 int ish_use_cluster_instances(void* h) {
     return guard([&] { ((Stixels*)h)->UseClusterInstances(); });
 }
