@@ -1084,6 +1084,83 @@ typedef struct is_cnn_label_args {
  * of 2^31 or more, a misaligned d_cnn_out or d_confusion and a non-zero reserved field. */
 int is_cnn_label_maps(const is_cnn_label_args* args, void* stream);
 
+/* ---- f16: the full-resolution semantic NLL through the fixed `up` layer, with its gradient (is_k_nll_up.hip) -------
+ * The training counterpart of f15's IS_CNN_UP_DECONV.  The reference's full-resolution models (tools/CNN_training/
+ * models/DRNSeg.py:46-225: DRNSeg, DRNDoubleSeg, DRNOffsetDisparity) compute seg -> up -> LogSoftmax and are trained
+ * with nn.NLLLoss(reduction='mean', ignore_index=255) on full-resolution ground truth (train.py:69-232).  Here on
+ * f13's cost planes y = -log_softmax(z): `up` is linear with the same weights for every class, so -up(y) differs from
+ * up(z) by one constant per pixel (also at the border, where taps are skipped) and log_softmax(-up(y)) ==
+ * log_softmax(up(z)) in exact arithmetic.  The gradient with respect to y sums to zero over the classes of a cell, so
+ * is_segmentation_head_backward turns it into the reference's dL/dz.  No upsampled plane is ever stored.
+ *
+ *   u_c       of pixel (Y, X), X < 8 * cols8: f15's IS_CNN_UP_DECONV fmaf chain on the cost planes of class c, bit for
+ *             bit the value is_cnn_label_maps compares.
+ *   Per pixel, in fp32, each operation rounded once: m = min_c u_c; S = sum_c expf(m - u_c) in increasing c from
+ *             +0.0f; K = m - logf(S); L_pix = u_t - K; p_c = expf(K - u_c); the residual r_c = [c == t] - p_c.
+ *             expf and logf are the device library's (the OpenCL C bounds they are built to: 3 ulp each).
+ *   Valid     a pixel with X < 8 * cols8 whose target t is in [0, n_classes) and is not ignore_index.  V is their
+ *             number; d_bad_count the pixels with X < 8 * cols8 whose target is neither a class nor ignore_index
+ *             (they count as ignored, as in f14).  Pixels with X >= 8 * cols8 take no part.
+ *   d_loss    (float)(sum_valid (double)L_pix / V): a binary64 sum, combined in an order the shape alone decides (per
+ *             frame first, then over the frames in increasing order, so that a batch of equal frames has the loss of
+ *             one); V = 0 gives NaN, as torch does.
+ *   d_grad    grad[i][c][cy][cx] = inv_V * sum W[ky] W[kx] r_c over the valid pixels of the cell's 16 x 16 footprint
+ *             that lie inside the image (W as in f15), inv_V = (float)(1.0 / V) applied as one final fp32 multiply;
+ *             all zero with V = 0.  The fp32 order of the sum, fixed by the shape: the footprint is the four 8 x 8
+ *             blocks Y = 8a-4 .. 8a+3, X = 8b-4 .. 8b+3 for a in {cy, cy+1}, b in {cx, cx+1}.  In a block, a row's
+ *             h = fmaf(W[kx], r, h) in increasing X from +0.0f, then G = fmaf(W[ky], h, G) in increasing Y from +0.0f
+ *             (rows outside the image skipped, pixels that do not count have r = +0.0f); the cell is
+ *             ((G(cy, cx) + G(cy, cx+1)) + G(cy+1, cx)) + G(cy+1, cx+1).  All n_classes planes of every frame are
+ *             written, zeros included, laid out as d_cnn_out with its own stride: with f12's d_grad on the regression
+ *             planes this assembles one gy without memset or copy.
+ *   No floating-point atomics; nothing depends on the grid, on a frame's position in the batch or on n_images other
+ *   than through inv_V; the same bytes on every run, and the same loss and counts with and without d_grad.
+ *   Non-finite planes give unspecified values, never a write outside the outputs; no address depends on a plane's
+ *   value.
+ *
+ * Zero-initialise, then set the fields.  All arrays on the current device.
+ *   d_cnn_out, cnn_image_stride   frame f starts at d_cnn_out + f * stride (elements); its first n_classes planes
+ *                       [rows8][cols8] are read; stride >= n_classes * rows8 * cols8
+ *   d_target            [n_images][rows][cols] uint8 class ids (trainIds)
+ *   n_images, rows8, cols8, n_classes, rows, cols   n_images in [1, 65535]; rows8, cols8 >= 1; n_classes in
+ *                       [1, IS_HEAD_MAX_CHANNELS]; rows == 8 * rows8, cols >= 8 * cols8; rows * cols < 2^31 and
+ *                       n_classes * rows8 * cols8 < 2^31 (the offsets inside a frame)
+ *   mode                IS_CNN_UP_DECONV; IS_CNN_UP_NEAREST is refused: the loss at 1/8 resolution is is_semantic_nll
+ *   d_loss              [1] float
+ *   d_valid_count, d_bad_count   [1] int64 each, 8-byte aligned: n_images * rows * cols < 2^47 always fits
+ *   d_grad, grad_image_stride   optional, stride >= n_classes * rows8 * cols8; without it the call is the validation
+ *                       loss and computes no residual
+ *   d_scratch           16-byte aligned, scratch_bytes >= is_semantic_nll_up_scratch_bytes(...); its contents mean
+ *                       nothing between calls
+ *   reserved            0 */
+typedef struct is_semantic_nll_up_args {
+    const float* d_cnn_out;
+    long long cnn_image_stride;
+    const uint8_t* d_target;
+    int ignore_index;
+    int n_images, rows8, cols8, n_classes;
+    int mode;
+    int rows, cols;
+    float* d_loss;
+    int64_t* d_valid_count;
+    int64_t* d_bad_count;
+    float* d_grad;
+    long long grad_image_stride;
+    void* d_scratch;
+    size_t scratch_bytes;
+    int reserved[4]; /* 0 */
+} is_semantic_nll_up_args;
+
+/* Bytes of d_scratch for a call of that shape (0 for a shape the call refuses). */
+size_t is_semantic_nll_up_scratch_bytes(int n_images, int rows8, int cols8, int n_classes);
+/* Two launches (three with d_grad: the tiles, the reduction of their records, the scaling by inv_V), asynchronous and
+ * stream-ordered; no allocation, copy or synchronisation.  IS_EINVAL, with the reason in is_last_error() and before
+ * the device is touched, for null args, a null d_cnn_out or d_target, a null d_loss, d_valid_count or d_bad_count, an
+ * unknown mode or IS_CNN_UP_NEAREST, rows != 8 * rows8 or cols < 8 * cols8, a shape or n_classes outside the ranges
+ * above, n_images outside [1, 65535], a stride below n_classes * rows8 * cols8, misaligned pointers, scratch that is
+ * null, too small or misaligned and a non-zero reserved field. */
+int is_semantic_nll_up(const is_semantic_nll_up_args* args, void* stream);
+
 /* ---- f9: per-instance objects and their contours (is_k_objects.hip) ------------------------------------------------
  * What the reference's consumers reduce on the host from the per-stixel output: the top-down view
  * (tools/visualization/clustering_visualization.py:563-792: per instance and column the closest stixel, connected

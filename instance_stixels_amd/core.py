@@ -45,6 +45,7 @@ EXPORTS = [
     "is_segmentation_head_backward_scratch_bytes", "is_segmentation_head_backward",
     "is_semantic_nll_scratch_bytes", "is_semantic_nll",
     "is_cnn_label_maps",
+    "is_semantic_nll_up_scratch_bytes", "is_semantic_nll_up",
 ]
 RENDER_MAX_LABELS = 64    # IS_RENDER_MAX_LABELS
 RENDER_MAX_CLASSES = 256  # IS_RENDER_MAX_CLASSES
@@ -229,6 +230,16 @@ class CnnLabelArgs(ctypes.Structure):
                 ("d_gt_label", vp), ("n_labels", ci), ("d_confusion", vp), ("reserved", ci * 4)]
 
 
+class SemanticNllUpArgs(ctypes.Structure):
+    """is_semantic_nll_up_args: zero-initialised by ctypes; device pointers as ints."""
+    vp, ci, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    _fields_ = [("d_cnn_out", vp), ("cnn_image_stride", ll), ("d_target", vp), ("ignore_index", ci),
+                ("n_images", ci), ("rows8", ci), ("cols8", ci), ("n_classes", ci), ("mode", ci), ("rows", ci),
+                ("cols", ci), ("d_loss", vp), ("d_valid_count", vp), ("d_bad_count", vp), ("d_grad", vp),
+                ("grad_image_stride", ll), ("d_scratch", vp), ("scratch_bytes", ctypes.c_size_t),
+                ("reserved", ci * 4)]
+
+
 class RoadParams(ctypes.Structure):
     """is_road_params: one frame's road, the layout of Stixels::RoadParameters (16 bytes)"""
     _fields_ = [("vhor", ctypes.c_int), ("tilt", ctypes.c_float), ("height", ctypes.c_float),
@@ -325,6 +336,9 @@ def lib():
         L.is_semantic_nll_scratch_bytes.restype = ctypes.c_size_t
         L.is_semantic_nll.argtypes = [ctypes.POINTER(SemanticNllArgs), vp]
         L.is_cnn_label_maps.argtypes = [ctypes.POINTER(CnnLabelArgs), vp]
+        L.is_semantic_nll_up_scratch_bytes.argtypes = [ci, ci, ci, ci]
+        L.is_semantic_nll_up_scratch_bytes.restype = ctypes.c_size_t
+        L.is_semantic_nll_up.argtypes = [ctypes.POINTER(SemanticNllUpArgs), vp]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
         L.is_get_device.argtypes = [ctypes.POINTER(ci)]
@@ -1316,6 +1330,100 @@ def semantic_nll(cnn_out, target, n_classes, ignore_index=255, grad=True, check=
                             d_scratch=scratch.data_ptr(), scratch_bytes=nbytes)
         _check(lib().is_semantic_nll(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
                "is_semantic_nll")
+        if check:
+            nb = int(bad.item())
+            if nb:
+                raise CoreError(f"{nb} targets are neither a class in [0, {int(n_classes)}) nor ignore_index "
+                                f"{int(ignore_index)}")
+        out = (loss, valid, bad, gr)
+        if g:
+            out = out + (_guards(named, g, gs),)
+    return out
+
+
+def semantic_nll_up_scratch_bytes(n_images, rows8, cols8, n_classes):
+    """is_semantic_nll_up_scratch_bytes: the scratch a call of that shape needs (0: a refused shape)."""
+    return int(lib().is_semantic_nll_up_scratch_bytes(int(n_images), int(rows8), int(cols8), int(n_classes)))
+
+
+def semantic_nll_up_ptr(stream=0, **fields):
+    """is_semantic_nll_up on raw device pointers (ints): fields are those of SemanticNllUpArgs.  Asynchronous on
+    `stream`; returns the return code and raises nothing (the tests check IS_EINVAL)."""
+    a = _with_reserved(SemanticNllUpArgs, fields)
+    return lib().is_semantic_nll_up(ctypes.byref(a), ctypes.c_void_p(int(stream)))
+
+
+def semantic_nll_up(cnn_out, target_full, n_classes, ignore_index=255, grad=True, check=True, canary=0):
+    """The classification loss of the reference's full-resolution models on the head's float output:
+    nn.NLLLoss(reduction='mean', ignore_index)(log_softmax(up(.))) with the fixed bilinear `up` layer, and its gradient
+    with respect to the class planes (is_semantic_nll_up, instance_stixels_core.h f16).
+
+    cnn_out     device float32 [n][C >= n_classes][rows8][cols8]; read in place when each frame's planes are contiguous
+    target_full device uint8 [n][8 * rows8][cols], cols >= 8 * cols8: class ids at full resolution (the pixels right
+                of 8 * cols8 take no part)
+    grad        True: a new float32 tensor [n][n_classes][rows8][cols8]; a device float32 tensor [n][C'][rows8][cols8]
+                with C' >= n_classes and contiguous planes: its first n_classes planes are written in place (the
+                regression planes are left to core.offset_loss); False: the loss alone, no residual is computed
+
+    Returns (loss [1] float32, valid_count [1] int64, bad_count [1] int64, grad or None) on cnn_out's device, enqueued
+    on the current torch stream.  check=True reads bad_count back (one synchronisation) and raises CoreError when a
+    target is neither a class nor ignore_index.  canary > 0: fresh outputs and the scratch get guards, returned as a
+    dict {name: (front, back, pattern)} in fifth place."""
+    import torch
+    y = cnn_out
+    if not torch.is_tensor(y) or not y.is_cuda or y.dtype != torch.float32 or y.dim() != 4 or y.shape[1] < n_classes:
+        raise CoreError("cnn_out must be a device float32 tensor [n][C >= n_classes][rows8][cols8]")
+    dev = y.device
+    n, C, Hs, Ws = y.shape
+    y = y.detach()
+
+    def in_place(t, planes):
+        return t.stride(3) == 1 and t.stride(2) == Ws and t.stride(1) == Hs * Ws and \
+            (n == 1 or t.stride(0) >= planes * Hs * Ws)
+    if not in_place(y, n_classes):
+        y = y.contiguous()
+    y_stride = y.stride(0) if n > 1 else C * Hs * Ws
+    t = target_full
+    if not torch.is_tensor(t) or t.device != dev or t.dtype != torch.uint8 or t.dim() != 3 or \
+            tuple(t.shape[:2]) != (n, 8 * Hs) or t.shape[2] < 8 * Ws:
+        raise CoreError(f"target_full must be a uint8 tensor {(n, 8 * Hs)} x (cols >= {8 * Ws}) on cnn_out's device")
+    t = t.contiguous()
+    cols = int(t.shape[2])
+    g = int(canary)
+    pat_f, pat_i = np.float32(-12345.0), np.int64(0x5A5A5A5A5A5A5A5A)
+    with torch.cuda.device(dev):
+        nbytes = semantic_nll_up_scratch_bytes(n, Hs, Ws, n_classes)
+        if nbytes == 0:
+            raise CoreError(f"is_semantic_nll_up_scratch_bytes refuses the shape (n_images {n}, rows8 {Hs}, "
+                            f"cols8 {Ws}, n_classes {int(n_classes)})")
+        named = {}
+        lfull, loss = _guarded(1, torch.float32, dev, g, float(pat_f))
+        vfull, valid = _guarded(1, torch.int64, dev, g, int(pat_i))
+        bfull, bad = _guarded(1, torch.int64, dev, g, int(pat_i))
+        named.update(loss=(lfull, pat_f), valid_count=(vfull, pat_i), bad_count=(bfull, pat_i))
+        gr, g_stride = None, 0
+        if torch.is_tensor(grad):
+            gr = grad
+            if gr.device != dev or gr.dtype != torch.float32 or gr.dim() != 4 or gr.shape[0] != n or \
+                    gr.shape[1] < n_classes or tuple(gr.shape[2:]) != (Hs, Ws) or not in_place(gr, n_classes):
+                raise CoreError("grad must be a device float32 tensor [n][C' >= n_classes][rows8][cols8] whose "
+                                "planes are contiguous")
+            g_stride = gr.stride(0) if n > 1 else n_classes * Hs * Ws
+        elif grad:
+            gfull, flat = _guarded(n * n_classes * Hs * Ws, torch.float32, dev, g, float(pat_f))
+            named["grad"] = (gfull, pat_f)
+            gr, g_stride = flat.view(n, n_classes, Hs, Ws), n_classes * Hs * Ws
+        gs = (g + 15) // 16 * 16
+        sfull, scratch = _guarded(nbytes, torch.uint8, dev, gs, 0xA5)
+        named["scratch"] = (sfull, np.uint8(0xA5))
+        a = SemanticNllUpArgs(d_cnn_out=y.data_ptr(), cnn_image_stride=y_stride, d_target=t.data_ptr(),
+                              ignore_index=int(ignore_index), n_images=n, rows8=Hs, cols8=Ws,
+                              n_classes=int(n_classes), mode=CNN_UP_DECONV, rows=8 * Hs, cols=cols,
+                              d_loss=loss.data_ptr(), d_valid_count=valid.data_ptr(), d_bad_count=bad.data_ptr(),
+                              d_grad=gr.data_ptr() if gr is not None else None, grad_image_stride=g_stride,
+                              d_scratch=scratch.data_ptr(), scratch_bytes=nbytes)
+        _check(lib().is_semantic_nll_up(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+               "is_semantic_nll_up")
         if check:
             nb = int(bad.item())
             if nb:

@@ -1149,6 +1149,47 @@ int is_cnn_label_maps(const is_cnn_label_args* a, void* stream) {
     return IS_OK;
 }
 
+/* ---- f16: the full-resolution semantic NLL through the `up` layer (is_k_nll_up.hip) ---- */
+static const char* semantic_nll_up_shape_fault(int n_images, int rows8, int cols8, int n_classes) {
+    if (n_images < 1 || n_images > 65535) return "n_images outside [1, 65535]";
+    if (rows8 < 1 || cols8 < 1) return "rows8 and cols8 must be >= 1";
+    if (n_classes < 1 || n_classes > IS_HEAD_MAX_CHANNELS) return "n_classes outside [1, IS_HEAD_MAX_CHANNELS]";
+    if ((long long)n_classes * rows8 * cols8 > 0x7fffffffLL) return "n_classes * rows8 * cols8 does not fit 31 bits";
+    if (64LL * rows8 * cols8 > 0x7fffffffLL) return "rows * cols does not fit 31 bits";
+    return nullptr;
+}
+
+size_t is_semantic_nll_up_scratch_bytes(int n_images, int rows8, int cols8, int n_classes) {
+    if (semantic_nll_up_shape_fault(n_images, rows8, cols8, n_classes)) return 0;
+    return isk_semantic_nll_up_scratch_bytes(n_images, rows8, cols8);
+}
+
+int is_semantic_nll_up(const is_semantic_nll_up_args* a, void* stream) {
+    if (!a) return fail_arg("null args");
+    if (!a->d_cnn_out || !a->d_target) return fail_arg("null d_cnn_out or d_target");
+    if (!a->d_loss || !a->d_valid_count || !a->d_bad_count) return fail_arg("null d_loss, d_valid_count or d_bad_count");
+    if (a->mode == IS_CNN_UP_NEAREST)
+        return fail_arg("mode IS_CNN_UP_NEAREST: the loss at 1/8 resolution is is_semantic_nll");
+    if (a->mode != IS_CNN_UP_DECONV) return fail_arg("mode is not IS_CNN_UP_DECONV");
+    if (const char* fault = semantic_nll_up_shape_fault(a->n_images, a->rows8, a->cols8, a->n_classes)) return fail_arg(fault);
+    if ((long long)a->rows != 8LL * a->rows8) return fail_arg("rows must be 8 * rows8");
+    if ((long long)a->cols < 8LL * a->cols8) return fail_arg("cols below 8 * cols8");
+    if ((long long)a->rows * a->cols > 0x7fffffffLL) return fail_arg("rows * cols does not fit 31 bits");
+    const long long planes = (long long)a->n_classes * a->rows8 * a->cols8;
+    if (a->cnn_image_stride < planes) return fail_arg("cnn_image_stride below n_classes * rows8 * cols8");
+    if (a->d_grad && a->grad_image_stride < planes) return fail_arg("grad_image_stride below n_classes * rows8 * cols8");
+    for (int r : a->reserved)
+        if (r) return fail_arg("reserved must be 0");
+    if (misaligned(4, a->d_cnn_out, a->d_loss, a->d_grad)) return fail_arg("d_cnn_out, d_loss and d_grad must be 4-byte aligned");
+    if (misaligned(8, a->d_valid_count, a->d_bad_count)) return fail_arg("d_valid_count and d_bad_count must be 8-byte aligned");
+    if (!a->d_scratch) return fail_arg("null d_scratch");
+    if (misaligned(16, a->d_scratch)) return fail_arg("d_scratch must be 16-byte aligned");
+    if (a->scratch_bytes < isk_semantic_nll_up_scratch_bytes(a->n_images, a->rows8, a->cols8))
+        return fail_arg("scratch_bytes below is_semantic_nll_up_scratch_bytes()");
+    HIP_TRY(isk_launch_semantic_nll_up(a, (hipStream_t)stream));
+    return IS_OK;
+}
+
 /* ---- f9: per-instance objects and contours (is_k_objects.hip) ---- */
 int is_instance_objects(const is_instance_objects_args* a, void* stream) {
     if (!a) return fail_arg("null args");

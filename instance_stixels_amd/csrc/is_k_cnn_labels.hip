@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "instance_stixels_core.h"
+#include "is_cnn_up.h"
 #include "is_launch.h"
 
 #define IS_CNN_TW 32                                   /* cells per tile row: one half wave */
@@ -49,10 +50,6 @@ __device__ __forceinline__ void cnn_conf_add(unsigned* bins, int& key, unsigned&
     key = k;
     run = n;
 }
-
-/* the 1-D weights of output position r = (o + 4) % 8: the tap on cell (o + 4) / 8 - 1 and the one on (o + 4) / 8 */
-__device__ __forceinline__ float cnn_w_low(int r) { return (float)(15 - 2 * r) / 16.0f; }
-__device__ __forceinline__ float cnn_w_high(int r) { return (float)(2 * r + 1) / 16.0f; }
 
 /* DECONV: IS_CNN_UP_DECONV, else IS_CNN_UP_NEAREST.  VEC: cols % 8 == 0 and 8-byte aligned label images, so that a
  * lane's 8 pixels of a row are one 64-bit access; else byte by byte. */

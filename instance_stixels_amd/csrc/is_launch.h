@@ -258,6 +258,10 @@ hipError_t isk_launch_semantic_nll(const is_semantic_nll_args* a, hipStream_t st
 /* is_k_cnn_labels.hip */
 hipError_t isk_launch_cnn_labels(const is_cnn_label_args* r, const uint8_t* table, hipStream_t stream);
 
+/* is_k_nll_up.hip */
+size_t isk_semantic_nll_up_scratch_bytes(int n_images, int rows8, int cols8);
+hipError_t isk_launch_semantic_nll_up(const is_semantic_nll_up_args* r, hipStream_t stream);
+
 /* is_k_objects.hip */
 hipError_t isk_launch_instance_objects(const is_instance_objects_args* r, hipStream_t stream);
 

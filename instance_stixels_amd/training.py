@@ -9,7 +9,8 @@ converted with .float().
 
 SegmentationHead and SemanticNLLLoss (f14) close the path to the parameters: the head module runs f13's launch in its
 forward and one call of is_segmentation_head_backward in its backward, so a model is trained with the numerics it is
-deployed with, and a training step gives the same bytes on every run."""
+deployed with, and a training step gives the same bytes on every run.  SemanticNLLLossUp (f16) is the loss of the
+full-resolution models: the same head, scored through the reference's fixed bilinear `up` layer."""
 import math
 
 import torch
@@ -200,3 +201,48 @@ class SemanticNLLLoss:
         if self.n_classes is not None:
             out = out[:, :int(self.n_classes)]
         return _SemanticNLLFunction.apply(out, t, self.ignore_index, self.check)[0]
+
+
+class _SemanticNLLUpFunction(torch.autograd.Function):
+    """As _SemanticNLLFunction, through the fixed `up` layer (f16)."""
+
+    @staticmethod
+    def forward(ctx, classes, target_full, ignore_index, check):
+        loss, _, _, grad = core.semantic_nll_up(classes.detach(), target_full, classes.shape[1],
+                                                ignore_index=ignore_index, grad=True, check=check)
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        grad, = ctx.saved_tensors
+        return grad * grad_loss[0], None, None, None
+
+
+class SemanticNLLLossUp:
+    """The classification loss of the reference's full-resolution models (DRNSeg.py:46-225: seg -> up -> LogSoftmax;
+    train.py:69-232: nn.NLLLoss(reduction='mean', ignore_index=255) on full-resolution ground truth) on the head's
+    1/8-resolution output, whose class channels hold -log p: output [n][C][rows8][cols8] float32, all of whose channels
+    are classes unless n_classes says that only the first n_classes are (a channel slice is read in place);
+    target_full [n][8 * rows8][cols >= 8 * cols8] or [n][1][..][..] of class ids, converted to uint8 after a range
+    check (one synchronisation, for other integer types only).  The upsampled planes are never stored.  Returns the
+    loss, a scalar on the device; loss.backward() works.  check: see core.semantic_nll_up."""
+
+    def __init__(self, ignore_index=255, n_classes=None, check=True):
+        self.ignore_index, self.n_classes, self.check = int(ignore_index), n_classes, check
+
+    def __call__(self, output, target_full):
+        t = target_full
+        if t.dim() == 4 and t.shape[1] == 1:
+            t = t[:, 0]
+        t = t.to(output.device)
+        if t.dtype != torch.uint8:
+            if t.is_floating_point() or t.dtype == torch.bool:
+                raise core.CoreError("target_full must hold integer class ids")
+            if t.numel() and (int(t.min()) < 0 or int(t.max()) > 255):
+                raise core.CoreError("target_full holds class ids outside [0, 255]")
+            t = t.to(torch.uint8)
+        out = output if output.dtype == torch.float32 else output.float()
+        if self.n_classes is not None:
+            out = out[:, :int(self.n_classes)]
+        return _SemanticNLLUpFunction.apply(out, t, self.ignore_index, self.check)[0]
