@@ -906,7 +906,7 @@ typedef struct is_segmentation_head_args {
  * is no regression channel, misaligned pointers and a non-zero reserved field. */
 int is_segmentation_head(const is_segmentation_head_args* args, void* stream);
 
-/* ---- f14: the backward pass of the segmentation head and the semantic NLL loss (is_k_head_backward.hip) -------------
+/* ---- f14: the backward pass of the segmentation head and the semantic NLL loss (is_k_head_backward.hip, is_k_nll.hip)
  * What training through f13's head needs (the reference trains every model as closs + rloss, tools/CNN_training/
  * train.py:698-732, closs = nn.NLLLoss(reduction='mean', ignore_index=255) on the class channels, train.py:281-282,
  * 325-326; optim_seg_parameters, DRNDownsampled.py:139-143, is head-only fine-tuning): the gradient of f13's float

@@ -867,6 +867,48 @@ def _torch_dtype_code(t):
     return codes[t.dtype]
 
 
+def _current_stream(dev):
+    """The current torch stream of device `dev`, as the C ABI takes it."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _scratch_or_raise(fn, shape, **unnamed):
+    """The scratch bytes fn(**shape, **unnamed) of a call; CoreError with the shape where the C ABI refuses it (0)."""
+    nbytes = fn(**shape, **unnamed)
+    if nbytes == 0:
+        what = "the shape or the capacity" if "capacity" in shape else "the shape"
+        raise CoreError(f"is_{fn.__name__} refuses {what} ({', '.join(f'{k} {v}' for k, v in shape.items())})")
+    return nbytes
+
+
+def _planes_in_place(t, planes):
+    """t [n][C >= planes][H][W] can be read or written where it is: each frame's planes are contiguous, the batch
+    stride is free."""
+    n, _, H, W = t.shape
+    return t.stride(3) == 1 and t.stride(2) == W and t.stride(1) == H * W and (n == 1 or t.stride(0) >= planes * H * W)
+
+
+def _frame_planes(t, planes):
+    """(tensor, image stride in elements): t itself where _planes_in_place, else a contiguous copy."""
+    if not _planes_in_place(t, planes):
+        t = t.contiguous()
+    return t, t.stride(0) if t.shape[0] > 1 else t.shape[1] * t.shape[2] * t.shape[3]
+
+
+def _until_keys_fit(call, count, cells, capacity, read_back):
+    """call(capacity), repeated with the frames' largest key count (read back from `count`: one synchronisation) while
+    that is above the capacity the call worked with; capacity 0 is the C ABI's default, min(256, cells)."""
+    while True:
+        call(capacity)
+        if not read_back:
+            return
+        most = int(count.max().item())
+        if most <= (int(capacity) if capacity else min(256, cells)):
+            return
+        capacity = most   # (never above the cells of a frame; above IS_GT_TARGETS_MAX_CAPACITY it is refused)
+
+
 def mode_downsample(t):
     """The reference's ModeDownsample(8) of a device tensor [n][rows][cols] (or [rows][cols]) of dtype uint8, uint16
     or int32: the most frequent value of every 8x8 block, the smallest among equals.  A tensor of the same dtype
@@ -930,12 +972,10 @@ def gt_instance_targets(gt_instance, disparity_u16=None, segmentation=None, rows
     with torch.cuda.device(dev):
         ids8 = torch.empty((n, Hs, Ws), dtype=torch.int32, device=dev)
         count = torch.empty((n,), dtype=torch.int32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        while True:
-            nbytes = gt_targets_scratch_bytes(n, rows, cols, d is not None, capacity)
-            if nbytes == 0:
-                raise CoreError("is_gt_targets_scratch_bytes refuses the shape or the capacity "
-                                f"(n_images {n}, rows {rows}, cols {cols}, capacity {capacity})")
+
+        def call(capacity):
+            shape = dict(n_images=n, rows=rows, cols=cols, capacity=capacity)
+            nbytes = _scratch_or_raise(gt_targets_scratch_bytes, shape, with_disparity=d is not None)
             scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
             a = GtTargetsArgs(d_gt_instance=g.data_ptr(), d_disparity_u16=d.data_ptr() if d is not None else None,
                               n_images=n, rows=rows, cols=cols, d_targets=out.data_ptr(), target_planes=planes,
@@ -944,14 +984,8 @@ def gt_instance_targets(gt_instance, disparity_u16=None, segmentation=None, rows
                               rows_power2_segmentation=p2s, channels=21 if segmentation is not None else 0,
                               capacity=int(capacity), d_scratch=scratch.data_ptr(), scratch_bytes=nbytes,
                               d_key_count=count.data_ptr())
-            _check(lib().is_gt_instance_targets(ctypes.byref(a), ctypes.c_void_p(stream)), "is_gt_instance_targets")
-            if d is None:
-                break
-            most = int(count.max().item())
-            effective = int(capacity) if capacity else min(256, Hs * Ws)
-            if most <= effective:
-                break
-            capacity = most   # (never above the cells of a frame; above IS_GT_TARGETS_MAX_CAPACITY it is refused)
+            _check(lib().is_gt_instance_targets(ctypes.byref(a), _current_stream(dev)), "is_gt_instance_targets")
+        _until_keys_fit(call, count, Hs * Ws, capacity, read_back=d is not None)
     return (out, ids8, count) if return_key_count else (out, ids8)
 
 
@@ -991,9 +1025,7 @@ def offset_loss(prediction, ids8, disparity8_u16=None, weights=OFFSET_LOSS_WEIGH
         raise CoreError("prediction must be a device float32 tensor [n][2 or 3][Hs][Ws]")
     dev = p.device
     n, planes, Hs, Ws = p.shape
-    if p.stride(3) != 1 or p.stride(2) != Ws or p.stride(1) != Hs * Ws or (n > 1 and p.stride(0) < planes * Hs * Ws):
-        p = p.contiguous()
-    p_stride = p.stride(0) if n > 1 else planes * Hs * Ws
+    p, p_stride = _frame_planes(p, planes)
     if ids8.device != dev or ids8.dtype != torch.int32 or tuple(ids8.shape) != (n, Hs, Ws):
         raise CoreError(f"ids8 must be an int32 tensor {(n, Hs, Ws)} on the prediction's device")
     i8 = ids8.contiguous()
@@ -1011,12 +1043,10 @@ def offset_loss(prediction, ids8, disparity8_u16=None, weights=OFFSET_LOSS_WEIGH
         terms = torch.empty((n, 4), dtype=torch.float32, device=dev)
         grad = torch.empty((n, planes, Hs, Ws), dtype=torch.float32, device=dev)
         count = torch.empty((n,), dtype=torch.int32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        while True:
-            nbytes = offset_loss_scratch_bytes(n, planes, Hs, Ws, capacity)
-            if nbytes == 0:
-                raise CoreError("is_offset_loss_scratch_bytes refuses the shape or the capacity "
-                                f"(n_images {n}, planes {planes}, rows8 {Hs}, cols8 {Ws}, capacity {capacity})")
+
+        def call(capacity):
+            nbytes = _scratch_or_raise(offset_loss_scratch_bytes,
+                                       dict(n_images=n, planes=planes, rows8=Hs, cols8=Ws, capacity=capacity))
             scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
             a = OffsetLossArgs(d_prediction=p.data_ptr(), prediction_image_stride=p_stride, d_ids8=i8.data_ptr(),
                                d_disparity8_u16=d8.data_ptr() if d8 is not None else None, n_images=n, planes=planes,
@@ -1025,14 +1055,8 @@ def offset_loss(prediction, ids8, disparity8_u16=None, weights=OFFSET_LOSS_WEIGH
                                d_loss=loss5.data_ptr(), d_terms=terms.data_ptr(), d_grad=grad.data_ptr(),
                                grad_image_stride=planes * Hs * Ws, capacity=int(capacity),
                                d_scratch=scratch.data_ptr(), scratch_bytes=nbytes, d_key_count=count.data_ptr())
-            _check(lib().is_offset_loss(ctypes.byref(a), ctypes.c_void_p(stream)), "is_offset_loss")
-            if not check:
-                break
-            most = int(count.max().item())
-            effective = int(capacity) if capacity else min(256, Hs * Ws)
-            if most <= effective:
-                break
-            capacity = most   # (never above the cells of a frame; above IS_GT_TARGETS_MAX_CAPACITY it is refused)
+            _check(lib().is_offset_loss(ctypes.byref(a), _current_stream(dev)), "is_offset_loss")
+        _until_keys_fit(call, count, Hs * Ws, capacity, read_back=check)
     return (loss5, terms, grad, count) if return_key_count else (loss5, terms, grad)
 
 
@@ -1041,11 +1065,7 @@ def segmentation_head_ptr(stream=0, **fields):
     defaults to -1 here).  Asynchronous on `stream`; returns the return code and raises nothing (the tests check
     IS_EINVAL)."""
     fields.setdefault("clamp_channel", -1)
-    reserved = fields.pop("reserved", None)
-    a = SegmentationHeadArgs(**fields)
-    if reserved is not None:
-        for i, v in enumerate(reserved):
-            a.reserved[i] = int(v)
+    a = _with_reserved(SegmentationHeadArgs, fields)
     return lib().is_segmentation_head(ctypes.byref(a), ctypes.c_void_p(int(stream)))
 
 
@@ -1091,17 +1111,15 @@ def segmentation_head(features, weight, bias, n_classes, rows_power2_segmentatio
     if not want_segmentation:
         want_cnn_out = True
     g = int(canary)
-    pat_i, pat_f = 0x5A5A5A5A, -12345.0
+    pat_i, pat_f = np.int32(0x5A5A5A5A), np.float32(-12345.0)
     with torch.cuda.device(dev):
-        seg = seg_all = cnn = cnn_all = None
+        named, seg, cnn = {}, None, None
         if want_segmentation:
-            seg_all = torch.full((n * Ws * CH * P2S + 2 * g,), pat_i, dtype=torch.int32, device=dev) if g else \
-                torch.empty((n * Ws * CH * P2S,), dtype=torch.int32, device=dev)
-            seg = seg_all[g: g + n * Ws * CH * P2S].view(n, Ws, CH, P2S)
+            full, flat = _guarded(n * Ws * CH * P2S, torch.int32, dev, g, int(pat_i))
+            named["segmentation"], seg = (full, pat_i), flat.view(n, Ws, CH, P2S)
         if want_cnn_out:
-            cnn_all = torch.full((n * CH * Hs * Ws + 2 * g,), pat_f, dtype=torch.float32, device=dev) if g else \
-                torch.empty((n * CH * Hs * Ws,), dtype=torch.float32, device=dev)
-            cnn = cnn_all[g: g + n * CH * Hs * Ws].view(n, CH, Hs, Ws)
+            full, flat = _guarded(n * CH * Hs * Ws, torch.float32, dev, g, float(pat_f))
+            named["cnn_out"], cnn = (full, pat_f), flat.view(n, CH, Hs, Ws)
         a = SegmentationHeadArgs(d_features=x.data_ptr(), dtype=codes[x.dtype], n_images=n, K=K, rows8=Hs, cols8=Ws,
                                  d_weight=w.data_ptr(), d_bias=b.data_ptr(), n_classes=int(n_classes),
                                  n_regression=CH - int(n_classes), rows_power2_segmentation=P2S, clamp_channel=-1,
@@ -1109,16 +1127,10 @@ def segmentation_head(features, weight, bias, n_classes, rows_power2_segmentatio
                                  d_segmentation=seg.data_ptr() if seg is not None else None)
         if clamp is not None:
             a.clamp_channel, a.clamp_lo, a.clamp_hi = int(clamp[0]), float(clamp[1]), float(clamp[2])
-        _check(lib().is_segmentation_head(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-               "is_segmentation_head")
+        _check(lib().is_segmentation_head(ctypes.byref(a), _current_stream(dev)), "is_segmentation_head")
         out = [t for t in (seg, cnn) if t is not None]
         if g:
-            guards = {}
-            for name, full, pat in (("segmentation", seg_all, np.int32(pat_i)), ("cnn_out", cnn_all, np.float32(pat_f))):
-                if full is not None:
-                    h = full.cpu().numpy()
-                    guards[name] = (h[:g].copy(), h[h.size - g:].copy(), pat)
-            out.append(guards)
+            out.append(_guards(named, g, g))
     return out[0] if len(out) == 1 else tuple(out)
 
 
@@ -1202,19 +1214,14 @@ def segmentation_head_backward(features, weight, cnn_out, grad_out, n_classes, w
     gy = grad_out
     if gy.device != dev or gy.dtype != torch.float32 or tuple(gy.shape) != shape:
         raise CoreError(f"grad_out must be a float32 tensor {shape} on the features' device")
-    gy = gy.detach()
+    gy, gy_stride = _frame_planes(gy.detach(), CH)
     frame = CH * Hs * Ws
-    if gy.stride(3) != 1 or gy.stride(2) != Ws or gy.stride(1) != Hs * Ws or (n > 1 and gy.stride(0) < frame):
-        gy = gy.contiguous()
-    gy_stride = gy.stride(0) if n > 1 else frame
     if not (want_features or want_weight or want_bias or want_logits):
         raise CoreError("no gradient is asked for")
     g = int(canary)
     with torch.cuda.device(dev):
-        nbytes = segmentation_head_backward_scratch_bytes(n, K, Hs, Ws, CH)
-        if nbytes == 0:
-            raise CoreError("is_segmentation_head_backward_scratch_bytes refuses the shape "
-                            f"(n_images {n}, K {K}, rows8 {Hs}, cols8 {Ws}, channels {CH})")
+        nbytes = _scratch_or_raise(segmentation_head_backward_scratch_bytes,
+                                   dict(n_images=n, K=K, rows8=Hs, cols8=Ws, channels=CH))
         pat_f = np.float32(-12345.0)
         pat_x = {torch.float32: pat_f, torch.float16: np.uint16(0x5A5A), torch.bfloat16: np.uint16(0x5A5A)}[x.dtype]
         named, out = {}, {}
@@ -1244,8 +1251,7 @@ def segmentation_head_backward(features, weight, cnn_out, grad_out, n_classes, w
             d_grad_out=gy.data_ptr(), grad_image_stride=gy_stride, d_grad_features=ptr["features"],
             d_grad_weight=ptr["weight"], d_grad_bias=ptr["bias"], d_grad_logits=ptr["logits"],
             d_scratch=scratch.data_ptr(), scratch_bytes=nbytes)
-        _check(lib().is_segmentation_head_backward(ctypes.byref(a),
-                                                   ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+        _check(lib().is_segmentation_head_backward(ctypes.byref(a), _current_stream(dev)),
                "is_segmentation_head_backward")
         if g:
             out["guards"] = _guards(named, g, gs)
@@ -1264,6 +1270,61 @@ def semantic_nll_ptr(stream=0, **fields):
     return lib().is_semantic_nll(ctypes.byref(a), ctypes.c_void_p(int(stream)))
 
 
+def _semantic_nll(entry, args_cls, scratch_fn, scratch_more, count, target_fields, cnn_out, n_classes, ignore_index,
+                  grad, check, canary):
+    """The call sequence of semantic_nll and semantic_nll_up: the entry point `entry` of the C ABI with its args class
+    and the scratch of scratch_fn(n_images, rows8, cols8, **scratch_more).  count: the torch dtype and the guard
+    pattern of valid_count and bad_count.  target_fields(n, rows8, cols8, dev) checks the caller's target and returns
+    the tensor to pass and the args fields that are the entry point's own."""
+    import torch
+    y = cnn_out
+    if not torch.is_tensor(y) or not y.is_cuda or y.dtype != torch.float32 or y.dim() != 4 or y.shape[1] < n_classes:
+        raise CoreError("cnn_out must be a device float32 tensor [n][C >= n_classes][rows8][cols8]")
+    dev = y.device
+    n, _, Hs, Ws = y.shape
+    y, y_stride = _frame_planes(y.detach(), n_classes)
+    t, own = target_fields(n, Hs, Ws, dev)
+    g = int(canary)
+    pat_f, (count_dtype, pat_i) = np.float32(-12345.0), count
+    with torch.cuda.device(dev):
+        nbytes = _scratch_or_raise(scratch_fn, dict(n_images=n, rows8=Hs, cols8=Ws, **scratch_more))
+        named = {}
+        lfull, loss = _guarded(1, torch.float32, dev, g, float(pat_f))
+        vfull, valid = _guarded(1, count_dtype, dev, g, int(pat_i))
+        bfull, bad = _guarded(1, count_dtype, dev, g, int(pat_i))
+        named.update(loss=(lfull, pat_f), valid_count=(vfull, pat_i), bad_count=(bfull, pat_i))
+        gr, g_stride = None, 0
+        if torch.is_tensor(grad):
+            gr = grad
+            if gr.device != dev or gr.dtype != torch.float32 or gr.dim() != 4 or gr.shape[0] != n or \
+                    gr.shape[1] < n_classes or tuple(gr.shape[2:]) != (Hs, Ws) or not _planes_in_place(gr, n_classes):
+                raise CoreError("grad must be a device float32 tensor [n][C' >= n_classes][rows8][cols8] whose "
+                                "planes are contiguous")
+            g_stride = gr.stride(0) if n > 1 else n_classes * Hs * Ws
+        elif grad:
+            gfull, flat = _guarded(n * n_classes * Hs * Ws, torch.float32, dev, g, float(pat_f))
+            named["grad"] = (gfull, pat_f)
+            gr, g_stride = flat.view(n, n_classes, Hs, Ws), n_classes * Hs * Ws
+        gs = (g + 15) // 16 * 16
+        sfull, scratch = _guarded(nbytes, torch.uint8, dev, gs, 0xA5)
+        named["scratch"] = (sfull, np.uint8(0xA5))
+        a = args_cls(d_cnn_out=y.data_ptr(), cnn_image_stride=y_stride, d_target=t.data_ptr(),
+                     ignore_index=int(ignore_index), n_images=n, rows8=Hs, cols8=Ws, n_classes=int(n_classes),
+                     d_loss=loss.data_ptr(), d_valid_count=valid.data_ptr(), d_bad_count=bad.data_ptr(),
+                     d_grad=gr.data_ptr() if gr is not None else None, grad_image_stride=g_stride,
+                     d_scratch=scratch.data_ptr(), scratch_bytes=nbytes, **own)
+        _check(getattr(lib(), entry)(ctypes.byref(a), _current_stream(dev)), entry)
+        if check:
+            nb = int(bad.item())
+            if nb:
+                raise CoreError(f"{nb} targets are neither a class in [0, {int(n_classes)}) nor ignore_index "
+                                f"{int(ignore_index)}")
+        out = (loss, valid, bad, gr)
+        if g:
+            out = out + (_guards(named, g, gs),)
+    return out
+
+
 def semantic_nll(cnn_out, target, n_classes, ignore_index=255, grad=True, check=True, canary=0):
     """nn.NLLLoss(reduction='mean', ignore_index) on the class planes of the head's float output, with its gradient
     (is_semantic_nll, instance_stixels_core.h f14).
@@ -1279,66 +1340,15 @@ def semantic_nll(cnn_out, target, n_classes, ignore_index=255, grad=True, check=
     target is neither a class nor ignore_index.  canary > 0: fresh outputs and the scratch get guards, returned as a
     dict {name: (front, back, pattern)} in fifth place."""
     import torch
-    y = cnn_out
-    if not torch.is_tensor(y) or not y.is_cuda or y.dtype != torch.float32 or y.dim() != 4 or y.shape[1] < n_classes:
-        raise CoreError("cnn_out must be a device float32 tensor [n][C >= n_classes][rows8][cols8]")
-    dev = y.device
-    n, C, Hs, Ws = y.shape
-    y = y.detach()
 
-    def in_place(t, planes):
-        return t.stride(3) == 1 and t.stride(2) == Ws and t.stride(1) == Hs * Ws and \
-            (n == 1 or t.stride(0) >= planes * Hs * Ws)
-    if not in_place(y, n_classes):
-        y = y.contiguous()
-    y_stride = y.stride(0) if n > 1 else C * Hs * Ws
-    dtypes = {torch.uint8: DTYPE_UINT8, torch.int32: DTYPE_INT32}
-    if target.device != dev or target.dtype not in dtypes or tuple(target.shape) != (n, Hs, Ws):
-        raise CoreError(f"target must be a uint8 or int32 tensor {(n, Hs, Ws)} on cnn_out's device")
-    t = target.contiguous()
-    g = int(canary)
-    pat_f, pat_i = np.float32(-12345.0), np.int32(0x5A5A5A5A)
-    with torch.cuda.device(dev):
-        nbytes = semantic_nll_scratch_bytes(n, Hs, Ws)
-        if nbytes == 0:
-            raise CoreError(f"is_semantic_nll_scratch_bytes refuses the shape (n_images {n}, rows8 {Hs}, cols8 {Ws})")
-        named = {}
-        lfull, loss = _guarded(1, torch.float32, dev, g, float(pat_f))
-        vfull, valid = _guarded(1, torch.int32, dev, g, int(pat_i))
-        bfull, bad = _guarded(1, torch.int32, dev, g, int(pat_i))
-        named.update(loss=(lfull, pat_f), valid_count=(vfull, pat_i), bad_count=(bfull, pat_i))
-        gr, g_stride = None, 0
-        if torch.is_tensor(grad):
-            gr = grad
-            if gr.device != dev or gr.dtype != torch.float32 or gr.dim() != 4 or gr.shape[0] != n or \
-                    gr.shape[1] < n_classes or tuple(gr.shape[2:]) != (Hs, Ws) or not in_place(gr, n_classes):
-                raise CoreError("grad must be a device float32 tensor [n][C' >= n_classes][rows8][cols8] whose "
-                                "planes are contiguous")
-            g_stride = gr.stride(0) if n > 1 else n_classes * Hs * Ws
-        elif grad:
-            gfull, flat = _guarded(n * n_classes * Hs * Ws, torch.float32, dev, g, float(pat_f))
-            named["grad"] = (gfull, pat_f)
-            gr, g_stride = flat.view(n, n_classes, Hs, Ws), n_classes * Hs * Ws
-        gs = (g + 15) // 16 * 16
-        sfull, scratch = _guarded(nbytes, torch.uint8, dev, gs, 0xA5)
-        named["scratch"] = (sfull, np.uint8(0xA5))
-        a = SemanticNllArgs(d_cnn_out=y.data_ptr(), cnn_image_stride=y_stride, d_target=t.data_ptr(),
-                            target_dtype=dtypes[t.dtype], ignore_index=int(ignore_index), n_images=n, rows8=Hs,
-                            cols8=Ws, n_classes=int(n_classes), d_loss=loss.data_ptr(),
-                            d_valid_count=valid.data_ptr(), d_bad_count=bad.data_ptr(),
-                            d_grad=gr.data_ptr() if gr is not None else None, grad_image_stride=g_stride,
-                            d_scratch=scratch.data_ptr(), scratch_bytes=nbytes)
-        _check(lib().is_semantic_nll(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-               "is_semantic_nll")
-        if check:
-            nb = int(bad.item())
-            if nb:
-                raise CoreError(f"{nb} targets are neither a class in [0, {int(n_classes)}) nor ignore_index "
-                                f"{int(ignore_index)}")
-        out = (loss, valid, bad, gr)
-        if g:
-            out = out + (_guards(named, g, gs),)
-    return out
+    def target_fields(n, Hs, Ws, dev):
+        dtypes = {torch.uint8: DTYPE_UINT8, torch.int32: DTYPE_INT32}
+        if target.device != dev or target.dtype not in dtypes or tuple(target.shape) != (n, Hs, Ws):
+            raise CoreError(f"target must be a uint8 or int32 tensor {(n, Hs, Ws)} on cnn_out's device")
+        return target.contiguous(), dict(target_dtype=dtypes[target.dtype])
+    return _semantic_nll("is_semantic_nll", SemanticNllArgs, semantic_nll_scratch_bytes, {},
+                         (torch.int32, np.int32(0x5A5A5A5A)), target_fields, cnn_out, n_classes, ignore_index, grad,
+                         check, canary)
 
 
 def semantic_nll_up_scratch_bytes(n_images, rows8, cols8, n_classes):
@@ -1370,69 +1380,16 @@ def semantic_nll_up(cnn_out, target_full, n_classes, ignore_index=255, grad=True
     target is neither a class nor ignore_index.  canary > 0: fresh outputs and the scratch get guards, returned as a
     dict {name: (front, back, pattern)} in fifth place."""
     import torch
-    y = cnn_out
-    if not torch.is_tensor(y) or not y.is_cuda or y.dtype != torch.float32 or y.dim() != 4 or y.shape[1] < n_classes:
-        raise CoreError("cnn_out must be a device float32 tensor [n][C >= n_classes][rows8][cols8]")
-    dev = y.device
-    n, C, Hs, Ws = y.shape
-    y = y.detach()
 
-    def in_place(t, planes):
-        return t.stride(3) == 1 and t.stride(2) == Ws and t.stride(1) == Hs * Ws and \
-            (n == 1 or t.stride(0) >= planes * Hs * Ws)
-    if not in_place(y, n_classes):
-        y = y.contiguous()
-    y_stride = y.stride(0) if n > 1 else C * Hs * Ws
-    t = target_full
-    if not torch.is_tensor(t) or t.device != dev or t.dtype != torch.uint8 or t.dim() != 3 or \
-            tuple(t.shape[:2]) != (n, 8 * Hs) or t.shape[2] < 8 * Ws:
-        raise CoreError(f"target_full must be a uint8 tensor {(n, 8 * Hs)} x (cols >= {8 * Ws}) on cnn_out's device")
-    t = t.contiguous()
-    cols = int(t.shape[2])
-    g = int(canary)
-    pat_f, pat_i = np.float32(-12345.0), np.int64(0x5A5A5A5A5A5A5A5A)
-    with torch.cuda.device(dev):
-        nbytes = semantic_nll_up_scratch_bytes(n, Hs, Ws, n_classes)
-        if nbytes == 0:
-            raise CoreError(f"is_semantic_nll_up_scratch_bytes refuses the shape (n_images {n}, rows8 {Hs}, "
-                            f"cols8 {Ws}, n_classes {int(n_classes)})")
-        named = {}
-        lfull, loss = _guarded(1, torch.float32, dev, g, float(pat_f))
-        vfull, valid = _guarded(1, torch.int64, dev, g, int(pat_i))
-        bfull, bad = _guarded(1, torch.int64, dev, g, int(pat_i))
-        named.update(loss=(lfull, pat_f), valid_count=(vfull, pat_i), bad_count=(bfull, pat_i))
-        gr, g_stride = None, 0
-        if torch.is_tensor(grad):
-            gr = grad
-            if gr.device != dev or gr.dtype != torch.float32 or gr.dim() != 4 or gr.shape[0] != n or \
-                    gr.shape[1] < n_classes or tuple(gr.shape[2:]) != (Hs, Ws) or not in_place(gr, n_classes):
-                raise CoreError("grad must be a device float32 tensor [n][C' >= n_classes][rows8][cols8] whose "
-                                "planes are contiguous")
-            g_stride = gr.stride(0) if n > 1 else n_classes * Hs * Ws
-        elif grad:
-            gfull, flat = _guarded(n * n_classes * Hs * Ws, torch.float32, dev, g, float(pat_f))
-            named["grad"] = (gfull, pat_f)
-            gr, g_stride = flat.view(n, n_classes, Hs, Ws), n_classes * Hs * Ws
-        gs = (g + 15) // 16 * 16
-        sfull, scratch = _guarded(nbytes, torch.uint8, dev, gs, 0xA5)
-        named["scratch"] = (sfull, np.uint8(0xA5))
-        a = SemanticNllUpArgs(d_cnn_out=y.data_ptr(), cnn_image_stride=y_stride, d_target=t.data_ptr(),
-                              ignore_index=int(ignore_index), n_images=n, rows8=Hs, cols8=Ws,
-                              n_classes=int(n_classes), mode=CNN_UP_DECONV, rows=8 * Hs, cols=cols,
-                              d_loss=loss.data_ptr(), d_valid_count=valid.data_ptr(), d_bad_count=bad.data_ptr(),
-                              d_grad=gr.data_ptr() if gr is not None else None, grad_image_stride=g_stride,
-                              d_scratch=scratch.data_ptr(), scratch_bytes=nbytes)
-        _check(lib().is_semantic_nll_up(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-               "is_semantic_nll_up")
-        if check:
-            nb = int(bad.item())
-            if nb:
-                raise CoreError(f"{nb} targets are neither a class in [0, {int(n_classes)}) nor ignore_index "
-                                f"{int(ignore_index)}")
-        out = (loss, valid, bad, gr)
-        if g:
-            out = out + (_guards(named, g, gs),)
-    return out
+    def target_fields(n, Hs, Ws, dev):
+        t = target_full
+        if not torch.is_tensor(t) or t.device != dev or t.dtype != torch.uint8 or t.dim() != 3 or \
+                tuple(t.shape[:2]) != (n, 8 * Hs) or t.shape[2] < 8 * Ws:
+            raise CoreError(f"target_full must be a uint8 tensor {(n, 8 * Hs)} x (cols >= {8 * Ws}) on cnn_out's device")
+        return t.contiguous(), dict(mode=CNN_UP_DECONV, rows=8 * Hs, cols=int(t.shape[2]))
+    return _semantic_nll("is_semantic_nll_up", SemanticNllUpArgs, semantic_nll_up_scratch_bytes,
+                         dict(n_classes=int(n_classes)), (torch.int64, np.int64(0x5A5A5A5A5A5A5A5A)), target_fields,
+                         cnn_out, n_classes, ignore_index, grad, check, canary)
 
 
 def cnn_label_maps_ptr(stream=0, class_to_label=None, **fields):
@@ -1523,8 +1480,8 @@ def cnn_label_maps(cnn_out, n_classes, mode="nearest", cols=None, gt_label=None,
                          d_gt_label=gt.data_ptr() if gt is not None else None,
                          n_labels=int(n_labels) if gt is not None else 0,
                          d_confusion=conf.data_ptr() if conf is not None else None)
-        s = int(stream) if stream else torch.cuda.current_stream(dev).cuda_stream
-        _check(lib().is_cnn_label_maps(ctypes.byref(a), ctypes.c_void_p(s)), "is_cnn_label_maps")
+        s = ctypes.c_void_p(int(stream)) if stream else _current_stream(dev)
+        _check(lib().is_cnn_label_maps(ctypes.byref(a), s), "is_cnn_label_maps")
         if g:
             out["guards"] = _guards(named, g, g)
     return out

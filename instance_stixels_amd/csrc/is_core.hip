@@ -740,6 +740,9 @@ static const char* geometry_fault(const A* a, const char* own = nullptr) {
 }
 /* one of the pointers (a NULL passes) is not a multiple of `bytes`, a power of two */
 template <class... P> static bool misaligned(uintptr_t bytes, P... p) { return ((... | (uintptr_t)p) & (bytes - 1)) != 0; }
+/* Cityscapes trainId -> labelId (cityscapesscripts' labels.py, trainId2label[c].id): the default table of
+ * is_render_sections and is_cnn_label_maps */
+static const uint8_t kCityscapesLabel[19] = {7, 8, 11, 12, 13, 17, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 31, 32, 33};
 
 int is_render_sections(const is_render_args* a, void* stream) {
     if (!a || !a->d_sections) return fail_arg("null sections");
@@ -754,11 +757,9 @@ int is_render_sections(const is_render_args* a, void* stream) {
         return fail_arg("d_gt_disparity, d_disp_abs_sum and d_disp_count go together");
     if (a->h_class_to_label && (a->n_classes < 1 || a->n_classes > IS_RENDER_MAX_CLASSES))
         return fail_arg("n_classes outside [1, IS_RENDER_MAX_CLASSES]");
-    /* Cityscapes trainId -> labelId (cityscapesscripts' labels.py, trainId2label[c].id) */
-    static const uint8_t kCityscapes[19] = {7, 8, 11, 12, 13, 17, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 31, 32, 33};
     uint8_t table[IS_RENDER_MAX_CLASSES] = {0};
-    const uint8_t* src = a->h_class_to_label ? a->h_class_to_label : kCityscapes;
-    const int n_classes = a->h_class_to_label ? a->n_classes : 19;
+    const uint8_t* src = a->h_class_to_label ? a->h_class_to_label : kCityscapesLabel;
+    const int n_classes = a->h_class_to_label ? a->n_classes : (int)sizeof(kCityscapesLabel);
     memcpy(table, src, n_classes);
     HIP_TRY(isk_launch_render(a, table, n_classes, (hipStream_t)stream));
     return IS_OK;
@@ -893,6 +894,56 @@ int is_cluster_instance_disparity(const is_instance_disparity_args* a, void* str
     return IS_OK;
 }
 
+/* ---- f11 .. f16: what the CNN and training entry points check alike, as geometry_fault above: a message, or NULL
+ * where all is sound, called where the entry point's own sequence of refusals has always had the check. ---- */
+/* The batch and its 1/8-resolution planes: n_images, then the entry point's own condition (`own`: its message where
+ * that is broken, else NULL), then the planes' shape, with at most 2^28 cells where the entry point has that limit. */
+static const char* planes_fault(int n_images, int rows8, int cols8, bool cell_limit, const char* own = nullptr) {
+    if (n_images < 1 || n_images > 65535) return "n_images outside [1, 65535]";
+    if (own) return own;
+    if (rows8 < 1 || cols8 < 1) return "rows8 and cols8 must be positive";
+    if (cell_limit && (long long)rows8 * cols8 > (1LL << 28)) return "more than 2^28 cells per frame";
+    return nullptr;
+}
+static const char* head_dtype_fault(int dtype) {
+    if (dtype != IS_HEAD_F32 && dtype != IS_HEAD_F16 && dtype != IS_HEAD_BF16)
+        return "dtype is none of IS_HEAD_F32, IS_HEAD_F16, IS_HEAD_BF16";
+    return nullptr;
+}
+static const char* reserved_fault(const int (&reserved)[4]) {
+    for (int r : reserved)
+        if (r) return "reserved must be 0";
+    return nullptr;
+}
+/* the full-resolution image over planes of rows8 x cols8 cells: cols may end in a margin right of the planes */
+static const char* image_fault(int rows, int cols, int rows8, int cols8) {
+    if ((long long)rows != 8LL * rows8) return "rows must be 8 * rows8";
+    if ((long long)cols < 8LL * cols8) return "cols below 8 * cols8";
+    if ((long long)rows * cols > 0x7fffffffLL) return "rows * cols does not fit 31 bits";
+    return nullptr;
+}
+/* a frame's planes reach past its image stride: the input's (`input`: its message), then the gradient's where there
+ * is one */
+static const char* stride_fault(long long planes, long long stride, const char* input, const void* d_grad,
+                                long long grad_stride) {
+    if (stride < planes) return input;
+    if (d_grad && grad_stride < planes) return "grad_image_stride below the planes of a frame";
+    return nullptr;
+}
+/* the scratch pointer and, with `need`, its size (the entry points that check other pointers in between call twice) */
+static const char* scratch_fault(const void* d_scratch, size_t have = 0, size_t need = 0) {
+    if (!d_scratch) return "null d_scratch";
+    if (misaligned(16, d_scratch)) return "d_scratch must be 16-byte aligned";
+    if (have < need) return "scratch_bytes below what the entry point's *_scratch_bytes() returns";
+    return nullptr;
+}
+/* the key capacity a call works with (0 selects min(256, cells)), or 0 where it is out of range */
+static int keys_capacity(long long cells, int capacity) {
+    const int most = (int)(cells < IS_GT_TARGETS_MAX_CAPACITY ? cells : IS_GT_TARGETS_MAX_CAPACITY);
+    if (capacity == 0) return most < 256 ? most : 256;
+    return capacity < 1 || capacity > most ? 0 : capacity;
+}
+
 /* ---- f11: ground-truth offset targets (is_k_gt_targets.hip) ---- */
 /* a frame of 8x8 cells: rows and cols multiples of 8, at most 2^28 cells */
 static const char* cells_fault(int n_images, int rows, int cols) {
@@ -901,13 +952,6 @@ static const char* cells_fault(int n_images, int rows, int cols) {
     if ((long long)(rows / 8) * (cols / 8) > (1LL << 28)) return "more than 2^28 cells per frame";
     if ((long long)n_images * (rows / 8) * ((cols / 8 + 63) / 64) > 0x7fffffffLL) return "batch too large for one launch";
     return nullptr;
-}
-/* the capacity a call works with (0 selects min(256, cells)), or 0 where it is out of range */
-static int gt_targets_capacity(int rows, int cols, int capacity) {
-    const long long cells = (long long)(rows / 8) * (cols / 8);
-    const int most = (int)(cells < IS_GT_TARGETS_MAX_CAPACITY ? cells : IS_GT_TARGETS_MAX_CAPACITY);
-    if (capacity == 0) return most < 256 ? most : 256;
-    return capacity < 1 || capacity > most ? 0 : capacity;
 }
 
 int is_mode_downsample(const void* d_src, int dtype, int n_images, int rows, int cols, void* d_dst, void* stream) {
@@ -923,7 +967,7 @@ int is_mode_downsample(const void* d_src, int dtype, int n_images, int rows, int
 
 size_t is_gt_targets_scratch_bytes(int n_images, int rows, int cols, int with_disparity, int capacity) {
     if (cells_fault(n_images, rows, cols)) return 0;
-    const int cap = gt_targets_capacity(rows, cols, capacity);
+    const int cap = keys_capacity((long long)(rows / 8) * (cols / 8), capacity);
     return cap ? isk_gt_targets_scratch_bytes(n_images, rows / 8, cols / 8, with_disparity, cap) : 0;
 }
 
@@ -943,38 +987,26 @@ int is_gt_instance_targets(const is_gt_targets_args* a, void* stream) {
     } else if (a->rows_power2_segmentation != 0 || a->channels != 0) {
         return fail_arg("rows_power2_segmentation and channels must be 0 without d_segmentation");
     }
-    const int capacity = gt_targets_capacity(a->rows, a->cols, a->capacity);
+    const int capacity = keys_capacity((long long)(a->rows / 8) * (a->cols / 8), a->capacity);
     if (!capacity) return fail_arg("capacity outside [1, min(rows/8 * cols/8, IS_GT_TARGETS_MAX_CAPACITY)]");
-    if (!a->d_scratch) return fail_arg("null d_scratch");
-    if (misaligned(16, a->d_scratch)) return fail_arg("d_scratch must be 16-byte aligned");
+    if (const char* fault = scratch_fault(a->d_scratch)) return fail_arg(fault);
     if (misaligned(4, a->d_gt_instance, a->d_targets, a->d_ids8, a->d_segmentation, a->d_key_count))
         return fail_arg("d_gt_instance, d_targets, d_ids8, d_segmentation and d_key_count must be 4-byte aligned");
     if (misaligned(2, a->d_disparity_u16)) return fail_arg("d_disparity_u16 must be 2-byte aligned");
-    if (a->scratch_bytes < isk_gt_targets_scratch_bytes(a->n_images, a->rows / 8, a->cols / 8, a->d_disparity_u16 != nullptr, capacity))
-        return fail_arg("scratch_bytes below is_gt_targets_scratch_bytes()");
+    const size_t need = isk_gt_targets_scratch_bytes(a->n_images, a->rows / 8, a->cols / 8, a->d_disparity_u16 != nullptr, capacity);
+    if (const char* fault = scratch_fault(a->d_scratch, a->scratch_bytes, need)) return fail_arg(fault);
     HIP_TRY(isk_launch_gt_targets(a, capacity, (hipStream_t)stream));
     return IS_OK;
 }
 
 /* ---- f12: offset and disparity training losses (is_k_offset_loss.hip) ---- */
 static const char* offset_loss_shape_fault(int n_images, int planes, int rows8, int cols8) {
-    if (n_images < 1 || n_images > 65535) return "n_images outside [1, 65535]";
-    if (planes != 2 && planes != 3) return "planes must be 2 or 3";
-    if (rows8 < 1 || cols8 < 1) return "rows8 and cols8 must be positive";
-    if ((long long)rows8 * cols8 > (1LL << 28)) return "more than 2^28 cells per frame";
-    return nullptr;
-}
-/* as gt_targets_capacity, on the cells themselves */
-static int offset_loss_capacity(int rows8, int cols8, int capacity) {
-    const long long cells = (long long)rows8 * cols8;
-    const int most = (int)(cells < IS_GT_TARGETS_MAX_CAPACITY ? cells : IS_GT_TARGETS_MAX_CAPACITY);
-    if (capacity == 0) return most < 256 ? most : 256;
-    return capacity < 1 || capacity > most ? 0 : capacity;
+    return planes_fault(n_images, rows8, cols8, true, planes != 2 && planes != 3 ? "planes must be 2 or 3" : nullptr);
 }
 
 size_t is_offset_loss_scratch_bytes(int n_images, int planes, int rows8, int cols8, int capacity) {
     if (offset_loss_shape_fault(n_images, planes, rows8, cols8)) return 0;
-    const int cap = offset_loss_capacity(rows8, cols8, capacity);
+    const int cap = keys_capacity((long long)rows8 * cols8, capacity);
     return cap ? isk_offset_loss_scratch_bytes(n_images, planes, rows8, cols8, cap) : 0;
 }
 
@@ -987,17 +1019,17 @@ int is_offset_loss(const is_offset_loss_args* a, void* stream) {
     if (a->planes == 3 && !a->d_disparity8_u16) return fail_arg("3 planes need d_disparity8_u16");
     if (a->planes == 2 && a->d_disparity8_u16) return fail_arg("d_disparity8_u16 must be null with 2 planes");
     const long long frame = (long long)a->planes * a->rows8 * a->cols8;
-    if (a->prediction_image_stride < frame) return fail_arg("prediction_image_stride below planes * rows8 * cols8");
-    if (a->d_grad && a->grad_image_stride < frame) return fail_arg("grad_image_stride below planes * rows8 * cols8");
-    const int capacity = offset_loss_capacity(a->rows8, a->cols8, a->capacity);
+    if (const char* fault = stride_fault(frame, a->prediction_image_stride, "prediction_image_stride below the planes of a frame",
+                                         a->d_grad, a->grad_image_stride))
+        return fail_arg(fault);
+    const int capacity = keys_capacity((long long)a->rows8 * a->cols8, a->capacity);
     if (!capacity) return fail_arg("capacity outside [1, min(rows8 * cols8, IS_GT_TARGETS_MAX_CAPACITY)]");
-    if (!a->d_scratch) return fail_arg("null d_scratch");
-    if (misaligned(16, a->d_scratch)) return fail_arg("d_scratch must be 16-byte aligned");
+    if (const char* fault = scratch_fault(a->d_scratch)) return fail_arg(fault);
     if (misaligned(4, a->d_prediction, a->d_ids8, a->d_loss, a->d_terms, a->d_grad, a->d_key_count))
         return fail_arg("d_prediction, d_ids8, d_loss, d_terms, d_grad and d_key_count must be 4-byte aligned");
     if (misaligned(2, a->d_disparity8_u16)) return fail_arg("d_disparity8_u16 must be 2-byte aligned");
-    if (a->scratch_bytes < isk_offset_loss_scratch_bytes(a->n_images, a->planes, a->rows8, a->cols8, capacity))
-        return fail_arg("scratch_bytes below is_offset_loss_scratch_bytes()");
+    const size_t need = isk_offset_loss_scratch_bytes(a->n_images, a->planes, a->rows8, a->cols8, capacity);
+    if (const char* fault = scratch_fault(a->d_scratch, a->scratch_bytes, need)) return fail_arg(fault);
     HIP_TRY(isk_launch_offset_loss(a, capacity, (hipStream_t)stream));
     return IS_OK;
 }
@@ -1007,10 +1039,8 @@ int is_segmentation_head(const is_segmentation_head_args* a, void* stream) {
     if (!a) return fail_arg("null args");
     if (!a->d_features || !a->d_weight || !a->d_bias) return fail_arg("null d_features, d_weight or d_bias");
     if (!a->d_cnn_out && !a->d_segmentation) return fail_arg("d_cnn_out and d_segmentation are both null");
-    if (a->dtype != IS_HEAD_F32 && a->dtype != IS_HEAD_F16 && a->dtype != IS_HEAD_BF16)
-        return fail_arg("dtype is none of IS_HEAD_F32, IS_HEAD_F16, IS_HEAD_BF16");
-    if (a->n_images < 1 || a->n_images > 65535) return fail_arg("n_images outside [1, 65535]");
-    if (a->rows8 < 1 || a->cols8 < 1) return fail_arg("rows8 and cols8 must be >= 1");
+    if (const char* fault = head_dtype_fault(a->dtype)) return fail_arg(fault);
+    if (const char* fault = planes_fault(a->n_images, a->rows8, a->cols8, false)) return fail_arg(fault);
     if (a->K < 8 || a->K % 8) return fail_arg("K must be >= 8 and a multiple of 8");
     if (a->n_classes < 1) return fail_arg("n_classes must be >= 1");
     if (a->n_regression < 0) return fail_arg("n_regression must be >= 0");
@@ -1024,8 +1054,7 @@ int is_segmentation_head(const is_segmentation_head_args* a, void* stream) {
             return fail_arg("clamp_channel is neither -1 nor a regression channel");
         if (!(a->clamp_lo <= a->clamp_hi)) return fail_arg("clamp_lo must be <= clamp_hi");
     }
-    for (int r : a->reserved)
-        if (r) return fail_arg("reserved must be 0");
+    if (const char* fault = reserved_fault(a->reserved)) return fail_arg(fault);
     if (misaligned(a->dtype == IS_HEAD_F32 ? 4 : 2, a->d_features)) return fail_arg("d_features must be aligned to its element");
     if (misaligned(4, a->d_weight, a->d_bias, a->d_cnn_out, a->d_segmentation))
         return fail_arg("d_weight, d_bias, d_cnn_out and d_segmentation must be 4-byte aligned");
@@ -1033,11 +1062,9 @@ int is_segmentation_head(const is_segmentation_head_args* a, void* stream) {
     return IS_OK;
 }
 
-/* ---- f14: the head's backward pass and the semantic NLL loss (is_k_head_backward.hip) ---- */
+/* ---- f14: the head's backward pass and the semantic NLL loss (is_k_head_backward.hip, is_k_nll.hip) ---- */
 static const char* head_backward_shape_fault(int n_images, int K, int rows8, int cols8, int n_classes, long long channels) {
-    if (n_images < 1 || n_images > 65535) return "n_images outside [1, 65535]";
-    if (rows8 < 1 || cols8 < 1) return "rows8 and cols8 must be >= 1";
-    if ((long long)rows8 * cols8 > (1LL << 28)) return "rows8 * cols8 above 2^28";
+    if (const char* fault = planes_fault(n_images, rows8, cols8, true)) return fault;
     if (K < 8 || K % 8) return "K must be >= 8 and a multiple of 8";
     if (n_classes < 1) return "n_classes must be >= 1";
     if (channels < n_classes) return "n_regression must be >= 0";
@@ -1056,37 +1083,26 @@ int is_segmentation_head_backward(const is_segmentation_head_backward_args* a, v
         return fail_arg("null d_features, d_weight, d_cnn_out or d_grad_out");
     if (!a->d_grad_features && !a->d_grad_weight && !a->d_grad_bias && !a->d_grad_logits)
         return fail_arg("d_grad_features, d_grad_weight, d_grad_bias and d_grad_logits are all null");
-    if (a->dtype != IS_HEAD_F32 && a->dtype != IS_HEAD_F16 && a->dtype != IS_HEAD_BF16)
-        return fail_arg("dtype is none of IS_HEAD_F32, IS_HEAD_F16, IS_HEAD_BF16");
+    if (const char* fault = head_dtype_fault(a->dtype)) return fail_arg(fault);
     const long long CH = (long long)a->n_classes + a->n_regression;
     if (a->n_regression < 0) return fail_arg("n_regression must be >= 0");
     if (const char* fault = head_backward_shape_fault(a->n_images, a->K, a->rows8, a->cols8, a->n_classes, CH))
         return fail_arg(fault);
-    if (a->grad_image_stride < CH * a->rows8 * a->cols8) return fail_arg("grad_image_stride below channels * rows8 * cols8");
-    for (int r : a->reserved)
-        if (r) return fail_arg("reserved must be 0");
+    if (a->grad_image_stride < CH * a->rows8 * a->cols8) return fail_arg("grad_image_stride below the planes of a frame");
+    if (const char* fault = reserved_fault(a->reserved)) return fail_arg(fault);
     const uintptr_t element = a->dtype == IS_HEAD_F32 ? 4 : 2;
     if (misaligned(element, a->d_features, a->d_grad_features))
         return fail_arg("d_features and d_grad_features must be aligned to their element");
     if (misaligned(4, a->d_weight, a->d_cnn_out, a->d_grad_out, a->d_grad_weight, a->d_grad_bias, a->d_grad_logits))
         return fail_arg("d_weight, d_cnn_out, d_grad_out, d_grad_weight, d_grad_bias and d_grad_logits must be 4-byte aligned");
-    if (!a->d_scratch) return fail_arg("null d_scratch");
-    if (misaligned(16, a->d_scratch)) return fail_arg("d_scratch must be 16-byte aligned");
-    if (a->scratch_bytes < isk_head_backward_scratch_bytes(a->n_images, a->K, a->rows8, a->cols8, (int)CH))
-        return fail_arg("scratch_bytes below is_segmentation_head_backward_scratch_bytes()");
+    const size_t need = isk_head_backward_scratch_bytes(a->n_images, a->K, a->rows8, a->cols8, (int)CH);
+    if (const char* fault = scratch_fault(a->d_scratch, a->scratch_bytes, need)) return fail_arg(fault);
     HIP_TRY(isk_launch_segmentation_head_backward(a, (hipStream_t)stream));
     return IS_OK;
 }
 
-static const char* semantic_nll_shape_fault(int n_images, int rows8, int cols8) {
-    if (n_images < 1 || n_images > 65535) return "n_images outside [1, 65535]";
-    if (rows8 < 1 || cols8 < 1) return "rows8 and cols8 must be >= 1";
-    if ((long long)rows8 * cols8 > (1LL << 28)) return "rows8 * cols8 above 2^28";
-    return nullptr;
-}
-
 size_t is_semantic_nll_scratch_bytes(int n_images, int rows8, int cols8) {
-    if (semantic_nll_shape_fault(n_images, rows8, cols8) || (long long)n_images * rows8 * cols8 > 0x7fffffffLL) return 0;
+    if (planes_fault(n_images, rows8, cols8, true) || (long long)n_images * rows8 * cols8 > 0x7fffffffLL) return 0;
     return isk_semantic_nll_scratch_bytes(n_images, rows8, cols8);
 }
 
@@ -1096,21 +1112,19 @@ int is_semantic_nll(const is_semantic_nll_args* a, void* stream) {
     if (!a->d_loss || !a->d_valid_count || !a->d_bad_count) return fail_arg("null d_loss, d_valid_count or d_bad_count");
     if (a->target_dtype != IS_DTYPE_UINT8 && a->target_dtype != IS_DTYPE_INT32)
         return fail_arg("target_dtype is neither IS_DTYPE_UINT8 nor IS_DTYPE_INT32");
-    if (const char* fault = semantic_nll_shape_fault(a->n_images, a->rows8, a->cols8)) return fail_arg(fault);
+    if (const char* fault = planes_fault(a->n_images, a->rows8, a->cols8, true)) return fail_arg(fault);
     if ((long long)a->n_images * a->rows8 * a->cols8 > 0x7fffffffLL) return fail_arg("n_images * rows8 * cols8 does not fit 31 bits");
     if (a->n_classes < 1 || a->n_classes > IS_HEAD_MAX_CHANNELS) return fail_arg("n_classes outside [1, IS_HEAD_MAX_CHANNELS]");
     const long long planes = (long long)a->n_classes * a->rows8 * a->cols8;
-    if (a->cnn_image_stride < planes) return fail_arg("cnn_image_stride below n_classes * rows8 * cols8");
-    if (a->d_grad && a->grad_image_stride < planes) return fail_arg("grad_image_stride below n_classes * rows8 * cols8");
-    for (int r : a->reserved)
-        if (r) return fail_arg("reserved must be 0");
+    if (const char* fault = stride_fault(planes, a->cnn_image_stride, "cnn_image_stride below the planes of a frame", a->d_grad,
+                                         a->grad_image_stride))
+        return fail_arg(fault);
+    if (const char* fault = reserved_fault(a->reserved)) return fail_arg(fault);
     if (misaligned(4, a->d_cnn_out, a->d_loss, a->d_valid_count, a->d_bad_count, a->d_grad))
         return fail_arg("d_cnn_out, d_loss, d_valid_count, d_bad_count and d_grad must be 4-byte aligned");
     if (a->target_dtype == IS_DTYPE_INT32 && misaligned(4, a->d_target)) return fail_arg("d_target must be aligned to its element");
-    if (!a->d_scratch) return fail_arg("null d_scratch");
-    if (misaligned(16, a->d_scratch)) return fail_arg("d_scratch must be 16-byte aligned");
-    if (a->scratch_bytes < isk_semantic_nll_scratch_bytes(a->n_images, a->rows8, a->cols8))
-        return fail_arg("scratch_bytes below is_semantic_nll_scratch_bytes()");
+    const size_t need = isk_semantic_nll_scratch_bytes(a->n_images, a->rows8, a->cols8);
+    if (const char* fault = scratch_fault(a->d_scratch, a->scratch_bytes, need)) return fail_arg(fault);
     HIP_TRY(isk_launch_semantic_nll(a, (hipStream_t)stream));
     return IS_OK;
 }
@@ -1123,36 +1137,29 @@ int is_cnn_label_maps(const is_cnn_label_args* a, void* stream) {
     if (!a->d_confusion != !a->d_gt_label) return fail_arg("d_confusion and d_gt_label go together");
     if (a->mode != IS_CNN_UP_NEAREST && a->mode != IS_CNN_UP_DECONV)
         return fail_arg("mode is neither IS_CNN_UP_NEAREST nor IS_CNN_UP_DECONV");
-    if (a->n_images < 1 || a->n_images > 65535) return fail_arg("n_images outside [1, 65535]");
-    if (a->rows8 < 1 || a->cols8 < 1) return fail_arg("rows8 and cols8 must be >= 1");
+    if (const char* fault = planes_fault(a->n_images, a->rows8, a->cols8, false)) return fail_arg(fault);
     if (a->n_classes < 1 || a->n_classes > IS_HEAD_MAX_CHANNELS) return fail_arg("n_classes outside [1, IS_HEAD_MAX_CHANNELS]");
     if (a->channels < a->n_classes) return fail_arg("channels below n_classes");
-    if ((long long)a->rows != 8LL * a->rows8) return fail_arg("rows must be 8 * rows8");
-    if ((long long)a->cols < 8LL * a->cols8) return fail_arg("cols below 8 * cols8");
-    if ((long long)a->rows * a->cols > 0x7fffffffLL) return fail_arg("rows * cols does not fit 31 bits");
+    if (const char* fault = image_fault(a->rows, a->cols, a->rows8, a->cols8)) return fail_arg(fault);
     if ((long long)a->channels * a->rows8 * a->cols8 > 0x7fffffffLL)
         return fail_arg("channels * rows8 * cols8 does not fit 31 bits");
     if (a->d_confusion && (a->n_labels < 1 || a->n_labels > IS_RENDER_MAX_LABELS))
         return fail_arg("n_labels outside [1, IS_RENDER_MAX_LABELS]");
-    for (int r : a->reserved)
-        if (r) return fail_arg("reserved must be 0");
+    if (const char* fault = reserved_fault(a->reserved)) return fail_arg(fault);
     if (misaligned(4, a->d_cnn_out)) return fail_arg("d_cnn_out must be 4-byte aligned");
     if (misaligned(8, a->d_confusion)) return fail_arg("d_confusion must be 8-byte aligned");
-    /* Cityscapes trainId -> labelId, the default table of is_render_sections */
-    static const uint8_t kCityscapes[19] = {7, 8, 11, 12, 13, 17, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 31, 32, 33};
     uint8_t table[IS_HEAD_MAX_CHANNELS] = {0};
     if (a->h_class_to_label)
         memcpy(table, a->h_class_to_label, a->n_classes);
     else
-        memcpy(table, kCityscapes, sizeof(kCityscapes));
+        memcpy(table, kCityscapesLabel, sizeof(kCityscapesLabel));
     HIP_TRY(isk_launch_cnn_labels(a, table, (hipStream_t)stream));
     return IS_OK;
 }
 
 /* ---- f16: the full-resolution semantic NLL through the `up` layer (is_k_nll_up.hip) ---- */
 static const char* semantic_nll_up_shape_fault(int n_images, int rows8, int cols8, int n_classes) {
-    if (n_images < 1 || n_images > 65535) return "n_images outside [1, 65535]";
-    if (rows8 < 1 || cols8 < 1) return "rows8 and cols8 must be >= 1";
+    if (const char* fault = planes_fault(n_images, rows8, cols8, false)) return fault;
     if (n_classes < 1 || n_classes > IS_HEAD_MAX_CHANNELS) return "n_classes outside [1, IS_HEAD_MAX_CHANNELS]";
     if ((long long)n_classes * rows8 * cols8 > 0x7fffffffLL) return "n_classes * rows8 * cols8 does not fit 31 bits";
     if (64LL * rows8 * cols8 > 0x7fffffffLL) return "rows * cols does not fit 31 bits";
@@ -1172,20 +1179,16 @@ int is_semantic_nll_up(const is_semantic_nll_up_args* a, void* stream) {
         return fail_arg("mode IS_CNN_UP_NEAREST: the loss at 1/8 resolution is is_semantic_nll");
     if (a->mode != IS_CNN_UP_DECONV) return fail_arg("mode is not IS_CNN_UP_DECONV");
     if (const char* fault = semantic_nll_up_shape_fault(a->n_images, a->rows8, a->cols8, a->n_classes)) return fail_arg(fault);
-    if ((long long)a->rows != 8LL * a->rows8) return fail_arg("rows must be 8 * rows8");
-    if ((long long)a->cols < 8LL * a->cols8) return fail_arg("cols below 8 * cols8");
-    if ((long long)a->rows * a->cols > 0x7fffffffLL) return fail_arg("rows * cols does not fit 31 bits");
+    if (const char* fault = image_fault(a->rows, a->cols, a->rows8, a->cols8)) return fail_arg(fault);
     const long long planes = (long long)a->n_classes * a->rows8 * a->cols8;
-    if (a->cnn_image_stride < planes) return fail_arg("cnn_image_stride below n_classes * rows8 * cols8");
-    if (a->d_grad && a->grad_image_stride < planes) return fail_arg("grad_image_stride below n_classes * rows8 * cols8");
-    for (int r : a->reserved)
-        if (r) return fail_arg("reserved must be 0");
+    if (const char* fault = stride_fault(planes, a->cnn_image_stride, "cnn_image_stride below the planes of a frame", a->d_grad,
+                                         a->grad_image_stride))
+        return fail_arg(fault);
+    if (const char* fault = reserved_fault(a->reserved)) return fail_arg(fault);
     if (misaligned(4, a->d_cnn_out, a->d_loss, a->d_grad)) return fail_arg("d_cnn_out, d_loss and d_grad must be 4-byte aligned");
     if (misaligned(8, a->d_valid_count, a->d_bad_count)) return fail_arg("d_valid_count and d_bad_count must be 8-byte aligned");
-    if (!a->d_scratch) return fail_arg("null d_scratch");
-    if (misaligned(16, a->d_scratch)) return fail_arg("d_scratch must be 16-byte aligned");
-    if (a->scratch_bytes < isk_semantic_nll_up_scratch_bytes(a->n_images, a->rows8, a->cols8))
-        return fail_arg("scratch_bytes below is_semantic_nll_up_scratch_bytes()");
+    const size_t need = isk_semantic_nll_up_scratch_bytes(a->n_images, a->rows8, a->cols8);
+    if (const char* fault = scratch_fault(a->d_scratch, a->scratch_bytes, need)) return fail_arg(fault);
     HIP_TRY(isk_launch_semantic_nll_up(a, (hipStream_t)stream));
     return IS_OK;
 }

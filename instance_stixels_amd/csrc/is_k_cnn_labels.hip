@@ -4,10 +4,7 @@
  * of tests/cnn_labels_reference.py is the contract restated).
  *
  * A workgroup owns IS_CNN_TH x IS_CNN_TW cells, 64 x 256 pixels.  It stages the n_classes values of those cells and
- * of a one-cell halo in LDS, a cell outside the plane as +0.0f: the transposed convolution's taps have finite
- * weights, so a tap on such a cell leaves the fmaf chain's value as it is (fmaf(w, 0, acc) == acc), which is the
- * contract's "skipped" and never 0 * inf.  (The one difference, a -0.0f accumulator that becomes +0.0f, compares
- * equal and so cannot move an arg-min.)
+ * of a one-cell halo in LDS (cnn_up_stage in is_cnn_up.h: a cell outside the plane is the contract's skipped tap).
  * One lane owns one cell: 8 image rows of 8 pixels.  The 8 pixels of a row read 3 x 2 cells per class (pixels 0..3
  * the cells left and centre, 4..7 centre and right; rows 0..3 the cells above and centre, 4..7 centre and below),
  * so a class costs 6 LDS reads and 32 fmaf per row, and no upsampled value is ever stored.  The 32 lanes of a half
@@ -69,17 +66,9 @@ __global__ __launch_bounds__(256) void k_cnn_labels(const CnnLabelArgs a) {
     if (tid < IS_HEAD_MAX_CHANNELS) table[tid] = a.table[tid];
     if (conf)
         for (int i = tid; i < nl * nl; i += 256) bins[i] = 0;
-    if (tx0 < a.cols8) { /* (a tile of margin cells alone reads nothing) */
-        const float* frame = a.cnn + (size_t)f * a.channels * P;
-        for (int i = tid; i < ncls * IS_CNN_CELLS; i += 256) {
-            const int cls = i / IS_CNN_CELLS, rem = i - cls * IS_CNN_CELLS;
-            const int ry = rem / IS_CNN_PITCH, rx = rem - ry * IS_CNN_PITCH;
-            const int cy = ty0 - 1 + ry, cx = tx0 - 1 + rx;
-            float v = 0.0f;
-            if (cy >= 0 && cy < a.rows8 && cx >= 0 && cx < a.cols8) v = frame[(size_t)cls * P + cy * a.cols8 + cx];
-            tile[i] = v;
-        }
-    }
+    if (tx0 < a.cols8) /* (a tile of margin cells alone reads nothing) */
+        cnn_up_stage<IS_CNN_TH + 2, IS_CNN_PITCH, 256>(tile, a.cnn + (size_t)f * a.channels * P, ncls, ty0 - 1, tx0 - 1,
+                                                        a.rows8, a.cols8, tid);
     __syncthreads();
 
     const int lx = tid & (IS_CNN_TW - 1), ly = tid / IS_CNN_TW;
@@ -119,16 +108,8 @@ __global__ __launch_bounds__(256) void k_cnn_labels(const CnnLabelArgs a) {
                      * and below.  The same for the pixels of the row with the cells left, centre and right. */
                     const int rj = (j + 4) & 7;
                     const float* p = t0 + (j < 4 ? -IS_CNN_PITCH : 0);
-                    const float wyl = cnn_w_low(rj), wyh = cnn_w_high(rj);
                     float w[8][4];
-#pragma unroll
-                    for (int k = 0; k < 8; k++) {
-                        const int rk = (k + 4) & 7;
-                        w[k][0] = wyl * cnn_w_low(rk);
-                        w[k][1] = wyl * cnn_w_high(rk);
-                        w[k][2] = wyh * cnn_w_low(rk);
-                        w[k][3] = wyh * cnn_w_high(rk);
-                    }
+                    cnn_up_weights(w, cnn_w_low(rj), cnn_w_high(rj), 4);
                     float best[8];
                     for (int cls = 0; cls < ncls; cls++, p += IS_CNN_CELLS) {
                         const float u[3] = {p[-1], p[0], p[1]};
@@ -136,10 +117,7 @@ __global__ __launch_bounds__(256) void k_cnn_labels(const CnnLabelArgs a) {
 #pragma unroll
                         for (int k = 0; k < 8; k++) {
                             const int x = k < 4 ? 0 : 1;
-                            float acc = fmaf(w[k][0], u[x], 0.0f);
-                            acc = fmaf(w[k][1], u[x + 1], acc);
-                            acc = fmaf(w[k][2], d[x], acc);
-                            acc = fmaf(w[k][3], d[x + 1], acc);
+                            const float acc = cnn_up_chain(w[k], u[x], u[x + 1], d[x], d[x + 1]);
                             if (cls == 0) {
                                 best[k] = acc;
                                 idx[k] = 0;

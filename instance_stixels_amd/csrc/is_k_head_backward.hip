@@ -1,6 +1,6 @@
 /*
- * is_k_head_backward.hip -- f14: the backward pass of the segmentation head (is_segmentation_head_backward) and the
- * semantic NLL loss with its gradient (is_semantic_nll).  The contract is the header's section f14.
+ * is_k_head_backward.hip -- f14: the backward pass of the segmentation head (is_segmentation_head_backward).  The
+ * contract is the header's section f14; the section's loss, is_semantic_nll, is is_k_nll.hip.
  *
  * k_head_backward_dx.  A wave owns 32 consecutive pixels of a frame, a lane one of them (l & 31) and the channels
  *   c = 2 s + (l >> 5), s = 0 .. 15: exactly the B operand of v_mfma_f32_32x32x2_f32 (lane l holds B[l >> 5][l & 31])
@@ -22,8 +22,6 @@
  *   wave 0.
  * k_head_backward_reduce.  One thread per (c, k) and per c adds the partials in binary64, frame by frame, chunk by
  *   chunk.
- * k_nll_*.  The sum in binary64 over a number of blocks, and ranges per block, that the shape alone decides; a
- *   thread adds its pixels in increasing order, a tree in LDS joins the threads, one block joins the blocks.
  */
 #include "is_launch.h"
 
@@ -31,8 +29,6 @@
 #define HB_WSTRIDE 160                   /* floats per channel of it: 32 mod 64, the half-waves on different banks */
 #define HB_TSTRIDE 33                    /* floats per row of a [32][32] operand tile */
 #define HB_TILE (32 * HB_TSTRIDE)
-#define NLL_THREADS 256
-#define NLL_MAX_BLOCKS 1024
 static_assert(IS_HEAD_MAX_CHANNELS == 32, "channels are one side of a 32x32 tile");
 static_assert(IS_HEAD_BACKWARD_CHUNK % 64 == 0, "a chunk is whole tiles");
 
@@ -287,115 +283,5 @@ extern "C" hipError_t isk_launch_segmentation_head_backward(const is_segmentatio
     if (contract)
         hipLaunchKernelGGL(k_head_backward_reduce, dim3((CH * (a->K + 1) + 255) / 256), dim3(256), 0, stream,
                            (const float*)part, a->n_images * chunks, a->K, CH, a->d_grad_weight, a->d_grad_bias);
-    return hipGetLastError();
-}
-
-/* ---- is_semantic_nll ---- */
-struct nll_partial {
-    double sum;
-    int valid, bad;
-};
-static_assert(sizeof(nll_partial) == 16, "one 16-byte record per block");
-
-/* the blocks of a shape and the pixels (a multiple of the block size) of each */
-static void nll_plan(int n_images, int Hs, int Ws, int* blocks, long long* span) {
-    const long long total = (long long)n_images * Hs * Ws;
-    long long s = (total + NLL_MAX_BLOCKS - 1) / NLL_MAX_BLOCKS;
-    s = (s + 4095) / 4096 * 4096;
-    *span = s;
-    *blocks = (int)((total + s - 1) / s);
-}
-
-__device__ __forceinline__ void nll_tree(double& s, int& v, int& b, double* sd, int* sv, int* sb, int tid) {
-    sd[tid] = s, sv[tid] = v, sb[tid] = b;
-    __syncthreads();
-    for (int step = NLL_THREADS / 2; step > 0; step >>= 1) {
-        if (tid < step) sd[tid] += sd[tid + step], sv[tid] += sv[tid + step], sb[tid] += sb[tid + step];
-        __syncthreads();
-    }
-    s = sd[0], v = sv[0], b = sb[0];
-}
-
-__device__ __forceinline__ int nll_target(const void* target, int dtype, long long q) {
-    return dtype == IS_DTYPE_UINT8 ? (int)((const uint8_t*)target)[q] : ((const int32_t*)target)[q];
-}
-
-__global__ __launch_bounds__(NLL_THREADS) void k_nll_partials(const float* __restrict__ y, long long y_stride,
-                                                              const void* __restrict__ target, int dtype, int ignore,
-                                                              int n_classes, int P, long long total, long long span,
-                                                              nll_partial* __restrict__ out) {
-    __shared__ double sd[NLL_THREADS];
-    __shared__ int sv[NLL_THREADS], sb[NLL_THREADS];
-    const int tid = threadIdx.x;
-    const long long beg = blockIdx.x * span, end = beg + span < total ? beg + span : total;
-    double s = 0.0;
-    int v = 0, b = 0;
-    for (long long q = beg + tid; q < end; q += NLL_THREADS) {
-        const int t = nll_target(target, dtype, q);
-        const bool cls = t >= 0 && t < n_classes && t != ignore;
-        const long long i = q / P, p = q - i * P;
-        const float yv = y[i * y_stride + (long long)(cls ? t : 0) * P + p]; /* (the address is inside for any target) */
-        if (cls) s += (double)yv, ++v;
-        else if (t != ignore) ++b;
-    }
-    nll_tree(s, v, b, sd, sv, sb, tid);
-    if (tid == 0) out[blockIdx.x] = nll_partial{s, v, b};
-}
-
-__global__ __launch_bounds__(NLL_THREADS) void k_nll_final(const nll_partial* __restrict__ in, int blocks,
-                                                           float* __restrict__ loss, int32_t* __restrict__ valid,
-                                                           int32_t* __restrict__ bad) {
-    __shared__ double sd[NLL_THREADS];
-    __shared__ int sv[NLL_THREADS], sb[NLL_THREADS];
-    const int tid = threadIdx.x;
-    double s = 0.0;
-    int v = 0, b = 0;
-    for (int i = tid; i < blocks; i += NLL_THREADS) s += in[i].sum, v += in[i].valid, b += in[i].bad;
-    nll_tree(s, v, b, sd, sv, sb, tid);
-    if (tid == 0) {
-        *loss = (float)(s / (double)v); /* 0 / 0 = NaN without a valid pixel, as torch */
-        *valid = v;
-        *bad = b;
-    }
-}
-
-__global__ __launch_bounds__(NLL_THREADS) void k_nll_grad(const void* __restrict__ target, int dtype, int ignore,
-                                                          int n_classes, int P, long long total,
-                                                          const int32_t* __restrict__ valid, float* __restrict__ grad,
-                                                          long long grad_stride) {
-    const long long q = (long long)blockIdx.x * NLL_THREADS + threadIdx.x;
-    if (q >= total) return;
-    const int V = *valid;
-    const float unit = V > 0 ? (float)(1.0 / (double)V) : 0.0f;
-    const int t = nll_target(target, dtype, q);
-    const int hit = (t >= 0 && t < n_classes && t != ignore) ? t : -1;
-    const long long i = q / P, p = q - i * P;
-    float* g = grad + i * grad_stride + p;
-    for (int c = 0; c < n_classes; ++c) g[(long long)c * P] = c == hit ? unit : 0.0f;
-}
-
-extern "C" size_t isk_semantic_nll_scratch_bytes(int n_images, int Hs, int Ws) {
-    int blocks;
-    long long span;
-    nll_plan(n_images, Hs, Ws, &blocks, &span);
-    return (size_t)blocks * sizeof(nll_partial);
-}
-
-/* The arguments are checked by is_semantic_nll (n_images * Hs * Ws fits 31 bits). */
-extern "C" hipError_t isk_launch_semantic_nll(const is_semantic_nll_args* a, hipStream_t stream) {
-    int blocks;
-    long long span;
-    nll_plan(a->n_images, a->rows8, a->cols8, &blocks, &span);
-    const int P = a->rows8 * a->cols8;
-    const long long total = (long long)a->n_images * P;
-    nll_partial* partials = (nll_partial*)a->d_scratch;
-    hipLaunchKernelGGL(k_nll_partials, dim3(blocks), dim3(NLL_THREADS), 0, stream, a->d_cnn_out, a->cnn_image_stride,
-                       a->d_target, a->target_dtype, a->ignore_index, a->n_classes, P, total, span, partials);
-    hipLaunchKernelGGL(k_nll_final, dim3(1), dim3(NLL_THREADS), 0, stream, (const nll_partial*)partials, blocks,
-                       a->d_loss, a->d_valid_count, a->d_bad_count);
-    if (a->d_grad)
-        hipLaunchKernelGGL(k_nll_grad, dim3((unsigned)((total + NLL_THREADS - 1) / NLL_THREADS)), dim3(NLL_THREADS), 0,
-                           stream, a->d_target, a->target_dtype, a->ignore_index, a->n_classes, P, total,
-                           (const int32_t*)a->d_valid_count, a->d_grad, a->grad_image_stride);
     return hipGetLastError();
 }

@@ -14,7 +14,7 @@
  * A workgroup is NU_TH x NU_TW corner blocks, one per lane, and writes the (NU_TH - 1) x (NU_TW - 1) cells between
  * them: the last block row and column of a tile are computed again by the next tile (1.18 x the arithmetic, no
  * hand-over through memory and no atomics).  The loss and the counts of a block are taken by exactly one tile.
- * Cells outside the plane are staged as +0.0f, f15's argument: fmaf(w, 0, acc) == acc is the contract's skipped tap.
+ * Cells outside the plane are staged as +0.0f, the contract's skipped tap (cnn_up_stage in is_cnn_up.h).
  * A pixel outside the image, with an ignored target or in a row half that is outside has K = -inf and a target byte
  * of 255: p = 0, no one-hot, residual +0.
  */
@@ -26,19 +26,15 @@
 #include "instance_stixels_core.h"
 #include "is_cnn_up.h"
 #include "is_launch.h"
+#include "is_nll.h"
 
 #define NU_TW 32                                       /* corner blocks per tile row: one half wave */
 #define NU_TH 8                                        /* corner block rows per tile */
 #define NU_PITCH (NU_TW + 1)                           /* cells tx0 - 1 .. tx0 + NU_TW - 1 */
 #define NU_CELLS ((NU_TH + 1) * NU_PITCH)              /* one class of a tile */
 #define NU_THREADS (NU_TW * NU_TH)
+static_assert(NU_THREADS == NLL_THREADS, "one corner block per thread of nll_tree");
 #define NU_SCALE_ITEMS 4                               /* elements per thread of the scaling launch */
-
-struct nll_up_partial {
-    double sum;
-    int valid, bad;
-};
-static_assert(sizeof(nll_up_partial) == 16, "one 16-byte record per workgroup");
 
 struct NllUpArgs {
     const float* cnn;
@@ -46,18 +42,9 @@ struct NllUpArgs {
     const uint8_t* target;
     float* grad;
     long long grad_stride;
-    nll_up_partial* partials;
+    nll_partial* partials;
     int n_classes, rows8, cols8, cols, xtiles, ignore;
 };
-
-/* the upsampled value of one pixel: f15's chain on the four cells, bit for bit */
-__device__ __forceinline__ float nu_chain(float w00, float w01, float w10, float w11, float v00, float v01, float v10,
-                                          float v11) {
-    float acc = fmaf(w00, v00, 0.0f);
-    acc = fmaf(w01, v01, acc);
-    acc = fmaf(w10, v10, acc);
-    return fmaf(w11, v11, acc);
-}
 
 /* GRAD: the gradient is written (unscaled; k_nll_up_scale multiplies by 1 / V).  VEC: cols % 4 == 0 and a 4-byte
  * aligned target, so that the 4 pixels of a block's row half are one 32-bit load; else byte by byte. */
@@ -75,17 +62,8 @@ __global__ __launch_bounds__(NU_THREADS) void k_nll_up(const NllUpArgs a) {
     const int tid = threadIdx.x;
     const int P = a.rows8 * a.cols8;
 
-    {
-        const float* frame = a.cnn + (long long)f * a.cnn_stride;
-        for (int i = tid; i < ncls * NU_CELLS; i += NU_THREADS) {
-            const int cls = i / NU_CELLS, rem = i - cls * NU_CELLS;
-            const int ry = rem / NU_PITCH, rx = rem - ry * NU_PITCH;
-            const int cy = ty0 - 1 + ry, cx = tx0 - 1 + rx;
-            float v = 0.0f;
-            if (cy >= 0 && cy < a.rows8 && cx >= 0 && cx < a.cols8) v = frame[(size_t)cls * P + cy * a.cols8 + cx];
-            tile[i] = v;
-        }
-    }
+    cnn_up_stage<NU_TH + 1, NU_PITCH, NU_THREADS>(tile, a.cnn + (long long)f * a.cnn_stride, ncls, ty0 - 1, tx0 - 1,
+                                                  a.rows8, a.cols8, tid);
     __syncthreads();
 
     const int lx = tid & (NU_TW - 1), ly = tid / NU_TW;
@@ -128,15 +106,8 @@ __global__ __launch_bounds__(NU_THREADS) void k_nll_up(const NllUpArgs a) {
 #pragma unroll
             for (int k = 0; k < 8; k++) K[j][k] = -INFINITY;
             if (rowin) {
-                const float wyl = cnn_w_low(j), wyh = cnn_w_high(j);
                 float w[8][4];
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    w[k][0] = wyl * cnn_w_low(k);
-                    w[k][1] = wyl * cnn_w_high(k);
-                    w[k][2] = wyh * cnn_w_low(k);
-                    w[k][3] = wyh * cnn_w_high(k);
-                }
+                cnn_up_weights(w, cnn_w_low(j), cnn_w_high(j), 0);
                 float m[8], S[8];
 #pragma unroll
                 for (int k = 0; k < 8; k++) m[k] = INFINITY;
@@ -145,7 +116,7 @@ __global__ __launch_bounds__(NU_THREADS) void k_nll_up(const NllUpArgs a) {
                     const float v00 = p[0], v01 = p[1], v10 = p[NU_PITCH], v11 = p[NU_PITCH + 1];
 #pragma unroll
                     for (int k = 0; k < 8; k++) {
-                        const float u = nu_chain(w[k][0], w[k][1], w[k][2], w[k][3], v00, v01, v10, v11);
+                        const float u = cnn_up_chain(w[k], v00, v01, v10, v11);
                         m[k] = u < m[k] ? u : m[k];
                     }
                 }
@@ -156,7 +127,7 @@ __global__ __launch_bounds__(NU_THREADS) void k_nll_up(const NllUpArgs a) {
                     const float v00 = p[0], v01 = p[1], v10 = p[NU_PITCH], v11 = p[NU_PITCH + 1];
 #pragma unroll
                     for (int k = 0; k < 8; k++) {
-                        const float u = nu_chain(w[k][0], w[k][1], w[k][2], w[k][3], v00, v01, v10, v11);
+                        const float u = cnn_up_chain(w[k], v00, v01, v10, v11);
                         S[k] += expf(m[k] - u);
                     }
                 }
@@ -169,8 +140,7 @@ __global__ __launch_bounds__(NU_THREADS) void k_nll_up(const NllUpArgs a) {
                     if (cls) {
                         const float Kv = m[k] - logf(S[k]);
                         const float* q = t0 + t * NU_CELLS; /* (inside the tile: t < ncls) */
-                        const float ut = nu_chain(w[k][0], w[k][1], w[k][2], w[k][3], q[0], q[1], q[NU_PITCH],
-                                                  q[NU_PITCH + 1]);
+                        const float ut = cnn_up_chain(w[k], q[0], q[1], q[NU_PITCH], q[NU_PITCH + 1]);
                         if (owner) {
                             lsum += (double)(ut - Kv);
                             ++nvalid;
@@ -200,7 +170,8 @@ __global__ __launch_bounds__(NU_THREADS) void k_nll_up(const NllUpArgs a) {
 #pragma unroll
                         for (int k = 0; k < 8; k++) {
                             const float wxl = cnn_w_low(k), wxh = cnn_w_high(k);
-                            const float u = nu_chain(wyl * wxl, wyl * wxh, wyh * wxl, wyh * wxh, v00, v01, v10, v11);
+                            const float w[4] = {wyl * wxl, wyl * wxh, wyh * wxl, wyh * wxh};
+                            const float u = cnn_up_chain(w, v00, v01, v10, v11);
                             const float pr = expf(K[j][k] - u);
                             const int t = (int)((tg[j][k >> 2] >> (8 * (k & 3))) & 255u);
                             const float r = (t == cls ? 1.0f : 0.0f) - pr;
@@ -231,19 +202,14 @@ __global__ __launch_bounds__(NU_THREADS) void k_nll_up(const NllUpArgs a) {
         }
     }
 
-    sd[tid] = lsum, sv[tid] = nvalid, sb[tid] = nbad;
-    __syncthreads();
-    for (int step = NU_THREADS / 2; step > 0; step >>= 1) {
-        if (tid < step) sd[tid] += sd[tid + step], sv[tid] += sv[tid + step], sb[tid] += sb[tid + step];
-        __syncthreads();
-    }
-    if (tid == 0) a.partials[(size_t)f * gridDim.x + blockIdx.x] = nll_up_partial{sd[0], sv[0], sb[0]};
+    nll_tree(lsum, nvalid, nbad, sd, sv, sb, tid);
+    if (tid == 0) a.partials[(size_t)f * gridDim.x + blockIdx.x] = nll_partial{lsum, nvalid, nbad};
 }
 
 /* One workgroup.  A frame's records are summed by one wave: lane l takes records l, l + 64, .. in increasing order,
  * the 64 lane sums are folded in halves; a wave adds its frames w, w + 4, .. in increasing order and the four wave
  * sums are added as (0 + 1) + (2 + 3).  So equal frames give equal frame sums, whatever the batch. */
-__global__ __launch_bounds__(256) void k_nll_up_final(const nll_up_partial* __restrict__ in, int n_images, int tiles,
+__global__ __launch_bounds__(256) void k_nll_up_final(const nll_partial* __restrict__ in, int n_images, int tiles,
                                                       float* __restrict__ loss, long long* __restrict__ valid,
                                                       long long* __restrict__ bad) {
     __shared__ double sd[256];
@@ -252,7 +218,7 @@ __global__ __launch_bounds__(256) void k_nll_up_final(const nll_up_partial* __re
     double total = 0.0;                                    /* (lane 0's is the wave's) */
     long long v = 0, b = 0;
     for (int i = wave; i < n_images; i += 4) {
-        const nll_up_partial* rec = in + (size_t)i * tiles;
+        const nll_partial* rec = in + (size_t)i * tiles;
         double s = 0.0;
         for (int k = lane; k < tiles; k += 64) s += rec[k].sum, v += rec[k].valid, b += rec[k].bad;
         for (int step = 32; step > 0; step >>= 1) s += __shfl_down(s, step, 64);
@@ -299,7 +265,7 @@ static size_t nll_up_lds_bytes(int n_classes, bool grad) {
 extern "C" size_t isk_semantic_nll_up_scratch_bytes(int n_images, int rows8, int cols8) {
     int xtiles, ytiles;
     nll_up_tiles(rows8, cols8, &xtiles, &ytiles);
-    return (size_t)n_images * xtiles * ytiles * sizeof(nll_up_partial);
+    return (size_t)n_images * xtiles * ytiles * sizeof(nll_partial);
 }
 
 /* The arguments are checked by is_semantic_nll_up (in-frame offsets fit 31 bits, n_images fits the grid). */
@@ -310,7 +276,7 @@ extern "C" hipError_t isk_launch_semantic_nll_up(const is_semantic_nll_up_args* 
     a.target = r->d_target;
     a.grad = r->d_grad;
     a.grad_stride = r->grad_image_stride;
-    a.partials = (nll_up_partial*)r->d_scratch;
+    a.partials = (nll_partial*)r->d_scratch;
     a.n_classes = r->n_classes;
     a.rows8 = r->rows8;
     a.cols8 = r->cols8;
@@ -331,7 +297,7 @@ extern "C" hipError_t isk_launch_semantic_nll_up(const is_semantic_nll_up_args* 
         hipLaunchKernelGGL((k_nll_up<false, true>), grid, dim3(NU_THREADS), lds, stream, a);
     else
         hipLaunchKernelGGL((k_nll_up<false, false>), grid, dim3(NU_THREADS), lds, stream, a);
-    hipLaunchKernelGGL(k_nll_up_final, dim3(1), dim3(256), 0, stream, (const nll_up_partial*)a.partials, r->n_images,
+    hipLaunchKernelGGL(k_nll_up_final, dim3(1), dim3(256), 0, stream, (const nll_partial*)a.partials, r->n_images,
                        tiles, r->d_loss, (long long*)r->d_valid_count, (long long*)r->d_bad_count);
     if (grad) {
         const int planes = r->n_classes * r->rows8 * r->cols8;

@@ -252,6 +252,8 @@ hipError_t isk_launch_segmentation_head(const is_segmentation_head_args* a, hipS
 /* is_k_head_backward.hip */
 size_t isk_head_backward_scratch_bytes(int n_images, int K, int Hs, int Ws, int channels);
 hipError_t isk_launch_segmentation_head_backward(const is_segmentation_head_backward_args* a, hipStream_t stream);
+
+/* is_k_nll.hip */
 size_t isk_semantic_nll_scratch_bytes(int n_images, int Hs, int Ws);
 hipError_t isk_launch_semantic_nll(const is_semantic_nll_args* a, hipStream_t stream);
 

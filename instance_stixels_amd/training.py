@@ -37,10 +37,19 @@ class _OffsetLossFunction(torch.autograd.Function):
         return grad * grad_loss5[0], None, None, None, None, None, None
 
 
+def _squeeze_channel(t):
+    """[n][1][H][W] -> [n][H][W]; anything else as it is."""
+    return t[:, 0] if t.dim() == 4 and t.shape[1] == 1 else t
+
+
+def _class_planes(output, n_classes):
+    """The head's output as float32, its first n_classes channels where that is given (a slice, read in place)."""
+    out = output if output.dtype == torch.float32 else output.float()
+    return out if n_classes is None else out[:, :int(n_classes)]
+
+
 def _ids8(batch_instance_gt, device):
-    ids = batch_instance_gt
-    if ids.dim() == 4 and ids.shape[1] == 1:
-        ids = ids[:, 0]
+    ids = _squeeze_channel(batch_instance_gt)
     if ids.dim() != 3:
         raise core.CoreError("the instance ids must be [n][Hs][Ws] or [n][1][Hs][Ws]")
     return ids.to(device=device, dtype=torch.int32).contiguous()
@@ -48,9 +57,7 @@ def _ids8(batch_instance_gt, device):
 
 def _disparity8(batch_disparity_gt, device):
     """uint16 raw as it is; anything else is the reference's tensor of integral q = raw // 256 in 0 .. 255."""
-    d = batch_disparity_gt
-    if d.dim() == 4 and d.shape[1] == 1:
-        d = d[:, 0]
+    d = _squeeze_channel(batch_disparity_gt)
     if d.dim() != 3:
         raise core.CoreError("the disparity must be [n][Hs][Ws] or [n][1][Hs][Ws]")
     d = d.to(device)
@@ -165,19 +172,20 @@ class SegmentationHead(torch.nn.Module):
 
 
 class _SemanticNLLFunction(torch.autograd.Function):
-    """As _OffsetLossFunction: the forward makes the gradient at unit scale, the backward scales it."""
+    """As _OffsetLossFunction: the forward makes the gradient at unit scale, the backward scales it.  loss_name:
+    "semantic_nll", or "semantic_nll_up" for the loss through the fixed `up` layer (f16), looked up in core per call."""
 
     @staticmethod
-    def forward(ctx, classes, target, ignore_index, check):
-        loss, _, _, grad = core.semantic_nll(classes.detach(), target, classes.shape[1], ignore_index=ignore_index,
-                                             grad=True, check=check)
+    def forward(ctx, classes, target, ignore_index, check, loss_name):
+        loss, _, _, grad = getattr(core, loss_name)(classes.detach(), target, classes.shape[1],
+                                                    ignore_index=ignore_index, grad=True, check=check)
         ctx.save_for_backward(grad)
         return loss
 
     @staticmethod
     def backward(ctx, grad_loss):
         grad, = ctx.saved_tensors
-        return grad * grad_loss[0], None, None, None
+        return grad * grad_loss[0], None, None, None, None
 
 
 class SemanticNLLLoss:
@@ -191,32 +199,11 @@ class SemanticNLLLoss:
         self.ignore_index, self.n_classes, self.check = int(ignore_index), n_classes, check
 
     def __call__(self, output, target):
-        t = target
-        if t.dim() == 4 and t.shape[1] == 1:
-            t = t[:, 0]
-        t = t.to(output.device)
+        t = _squeeze_channel(target).to(output.device)
         if t.dtype not in (torch.uint8, torch.int32):
             t = t.to(torch.int32)
-        out = output if output.dtype == torch.float32 else output.float()
-        if self.n_classes is not None:
-            out = out[:, :int(self.n_classes)]
-        return _SemanticNLLFunction.apply(out, t, self.ignore_index, self.check)[0]
-
-
-class _SemanticNLLUpFunction(torch.autograd.Function):
-    """As _SemanticNLLFunction, through the fixed `up` layer (f16)."""
-
-    @staticmethod
-    def forward(ctx, classes, target_full, ignore_index, check):
-        loss, _, _, grad = core.semantic_nll_up(classes.detach(), target_full, classes.shape[1],
-                                                ignore_index=ignore_index, grad=True, check=check)
-        ctx.save_for_backward(grad)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        grad, = ctx.saved_tensors
-        return grad * grad_loss[0], None, None, None
+        out = _class_planes(output, self.n_classes)
+        return _SemanticNLLFunction.apply(out, t, self.ignore_index, self.check, "semantic_nll")[0]
 
 
 class SemanticNLLLossUp:
@@ -232,17 +219,12 @@ class SemanticNLLLossUp:
         self.ignore_index, self.n_classes, self.check = int(ignore_index), n_classes, check
 
     def __call__(self, output, target_full):
-        t = target_full
-        if t.dim() == 4 and t.shape[1] == 1:
-            t = t[:, 0]
-        t = t.to(output.device)
+        t = _squeeze_channel(target_full).to(output.device)
         if t.dtype != torch.uint8:
             if t.is_floating_point() or t.dtype == torch.bool:
                 raise core.CoreError("target_full must hold integer class ids")
             if t.numel() and (int(t.min()) < 0 or int(t.max()) > 255):
                 raise core.CoreError("target_full holds class ids outside [0, 255]")
             t = t.to(torch.uint8)
-        out = output if output.dtype == torch.float32 else output.float()
-        if self.n_classes is not None:
-            out = out[:, :int(self.n_classes)]
-        return _SemanticNLLUpFunction.apply(out, t, self.ignore_index, self.check)[0]
+        out = _class_planes(output, self.n_classes)
+        return _SemanticNLLFunction.apply(out, t, self.ignore_index, self.check, "semantic_nll_up")[0]
