@@ -1161,6 +1161,76 @@ size_t is_semantic_nll_up_scratch_bytes(int n_images, int rows8, int cols8, int 
  * null, too small or misaligned and a non-zero reserved field. */
 int is_semantic_nll_up(const is_semantic_nll_up_args* args, void* stream);
 
+/* ---- f17: the backbone's tail, a dilated 3x3 convolution + BatchNorm + ReLU of a batch (is_k_conv3x3.hip) ------------
+ * The two layers in front of f13's head, the same in every model of the reference: layer7 and layer8 of the DRN
+ * (tools/CNN_training/models/drn.py:181-185, built by _make_conv_layers, drn.py:223-233: Conv2d(C, C, 3, padding =
+ * dilation, dilation = 2 and 1, bias = False) + BatchNorm2d + ReLU), which the reference runs in half precision
+ * (amp "O1", inference.py:278).  In one launch per layer on the half-precision MFMA, with BatchNorm folded to one
+ * scale and shift per channel, so that layer7 -> layer8 -> is_segmentation_head is three launches of this library
+ * with nothing in between.  fp32 features are out of scope (the f32-input MFMA has 1/16 of the rate): convert first.
+ *
+ *   Operands.    The half values: the features as given, the weights as is_conv3x3_pack_weights rounded them (round to
+ *                nearest even).  A product of two of them is exact in fp32.
+ *   Summation.   a[n][co][y][x] = sum over the 9 taps and all channels_in of
+ *                w[co][ci][ky][kx] * x[n][ci][y + (ky - 1) dilation][x + (kx - 1) dilation]; a tap outside the image
+ *                contributes nothing (zero padding = dilation, stride 1).  Accumulated in fp32 MFMA accumulators by
+ *                v_mfma_f32_32x32x16_f16 / _bf16, one accumulator chain per output element: no split over workgroups,
+ *                no atomics, no partial sums combined afterwards.
+ *   Order.       The order of the MFMA instructions along (tap, channel) is fixed by the shape alone: 16-channel chunks
+ *                in increasing order, the taps 3 ky + kx of a chunk in increasing order.  The summation INSIDE one
+ *                instruction (16 products) is the hardware's and is not specified.  This entry point is therefore
+ *                pinned by a derived error bound plus inputs whose arithmetic is exact in every order, NOT by a C loop
+ *                that gives its bits -- a weaker contract than f13's fmaf chain, and said so here on purpose.
+ *   Epilogue.    v = fmaf(scale[co], a, shift[co]) in fp32, then max(v, 0) when relu is set.  With out_dtype =
+ *                IS_HEAD_F32 that value is stored, with a half out_dtype its round-to-nearest-even conversion.
+ *   Determinism. The same bytes on every run; a frame's result does not depend on its position in the batch or on
+ *                n_images.
+ *   Non-finite values give unspecified values, never an access outside the buffers; no address depends on a value.
+ *
+ * Weights: d_weight is conv.weight, [channels_out][channels_in][3][3] fp32.  is_conv3x3_pack_weights rounds each to the
+ * half dtype (round to nearest even) and writes them in an opaque layout of the kernel's choosing that holds exactly
+ * those values, is_conv3x3_packed_bytes(...) bytes at a 16-byte aligned d_packed: one small launch, once per model.
+ *
+ * Zero-initialise, then set the fields.  All arrays on the current device.
+ *   d_features, dtype   [n_images][channels_in][rows8][cols8], contiguous NCHW, IS_HEAD_F16 or IS_HEAD_BF16, aligned to
+ *                       the element; no row alignment is asked for (cols8 = 7 is legal)
+ *   n_images            in [1, 65535];  rows8, cols8 in [1, 32767]
+ *   channels_in         a multiple of 16 in [16, 2048];  channels_out a multiple of 32 in [32, 2048]
+ *   dilation            in [1, 8]
+ *   d_packed            from is_conv3x3_pack_weights with the same channels and dtype, 16-byte aligned
+ *   d_scale, d_shift    [channels_out] fp32: the folded BatchNorm (scale = gamma / sqrt(var + eps), shift = beta -
+ *                       mean * scale)
+ *   relu                0 or 1
+ *   d_out, out_dtype    [n_images][channels_out][rows8][cols8] of the input's dtype or IS_HEAD_F32, aligned to its
+ *                       element; every element is written; its bytes must not overlap the features' (the halo makes
+ *                       an in-place call wrong)
+ *   reserved            0 */
+typedef struct is_conv3x3_args {
+    const void* d_features;
+    int dtype;
+    int n_images, channels_in, channels_out, rows8, cols8, dilation;
+    const void* d_packed;
+    const float* d_scale;
+    const float* d_shift;
+    int relu;
+    void* d_out;
+    int out_dtype;
+    int reserved[4]; /* 0 */
+} is_conv3x3_args;
+
+/* Bytes of d_packed (0 for arguments outside the ranges above). */
+size_t is_conv3x3_packed_bytes(int channels_out, int channels_in, int dtype);
+/* One launch on `stream`, asynchronous.  IS_EINVAL before the device is touched for null pointers, channels or a dtype
+ * outside the ranges above and misaligned pointers. */
+int is_conv3x3_pack_weights(const float* d_weight, int channels_out, int channels_in, int dtype, void* d_packed,
+                            void* stream);
+/* One launch on `stream`, asynchronous and stream-ordered; no allocation, copy or synchronisation.  IS_EINVAL, with
+ * the reason in is_last_error() and before the device is touched, for null args or pointers, dtype IS_HEAD_F32 or
+ * unknown, an out_dtype that is neither the input's nor IS_HEAD_F32, any argument outside the ranges above, relu
+ * outside {0, 1}, a misaligned d_packed (or another pointer off its element), output and feature byte ranges that
+ * overlap and a non-zero reserved field. */
+int is_conv3x3_bn_relu(const is_conv3x3_args* args, void* stream);
+
 /* ---- f9: per-instance objects and their contours (is_k_objects.hip) ------------------------------------------------
  * What the reference's consumers reduce on the host from the per-stixel output: the top-down view
  * (tools/visualization/clustering_visualization.py:563-792: per instance and column the closest stixel, connected
