@@ -1,5 +1,6 @@
 /* is_k_pairwise.hip -- the pairwise column DP (two launches per 64-row tile).  See is_kernels.h. */
 #include "is_kernels.h"
+#include "is_unary.h" /* PruneVals: the register copy of a column's PruneRec */
 
 /* ====================================================================================== */
 /* A7-A9  pairwise DP                                                                      */
@@ -432,10 +433,9 @@ __device__ __forceinline__ void l8_store_never(float* dst, bool writer) {
  * never close, every split being a near-optimal candidate -- exactly the block with the stretch's
  * first row survives (tools/l7_study.py). */
 #define IS_P1_L7_WORDS 136 /* LDS words of the exchange: [2][64] threshold keys + 2 x 64-bit masks, padded */
-/* LDS words per bound block of a phase-1 launch: 64 object bounds (one per lane) + its 24-float summary + the
- * 8 instance-prefix dwords of the record at its top row */
+/* LDS words of a bound block's summary in a phase-1 launch: its 24 floats + the 8 instance-prefix dwords of the record
+ * at its top row (P1Lds::sum; beside them 64 object bounds, one per lane: P1Lds::lb) */
 #define IS_P1_SUM_F (IS_L7_F + 8)
-#define IS_P1_BLK_WORDS (64 + IS_P1_SUM_F)
 struct L7B { float lo_g0, lo_g1, lo_s, hi_g0, hi_g1, hi_s; };
 __device__ __forceinline__ void l7_b(float dterm, float fterm, float* lo, float* hi) {
     const float b = dterm + fterm;
@@ -605,29 +605,322 @@ __device__ __forceinline__ void touch_round(const RowRec* rcol, const StepRec* s
 #define IS_P1_SREC 1 /* class-prefix half of the vB record as scalar operands (see eval_segment_mix) */
 #endif
 
+/* ---- phase 1: the LDS of a launch ---------------------------------------------------------------
+ * The regions of the dynamic LDS of the launch of one tile, in their order, each as a number of 4-byte words: the
+ * kernel carves them in this order and the launcher sizes the launch from the same description (p1_lds_bytes). */
+struct P1Lds {
+    int nlb;   /* bound blocks 0 .. tile * IS_QPT of this tile's candidates                                          */
+    int dp;    /* row stride of the tile: D lutT columns or the IS_P1_WIN of the fn window (is_device.h), + 1 of padding */
+    int tile;  /* [IS_TILE][dp] the vT-side tile; the merge area aliases it (and what follows it, where it is larger) */
+    int rcp;   /* [H + 1] 1/h, padded to a multiple of four words                                                    */
+    int scr;   /* [8 per wave] landing words of the L2-warming DMAs                                                  */
+    int thr;   /* lemma L7: [2][64] threshold keys + the two 64-bit survive masks, padded (IS_P1_L7_WORDS)            */
+    int lb;    /* [nlb][64 lanes] object block bounds                                                                */
+    int sum;   /* [nlb][IS_P1_SUM_F]: 24 summary floats + the instance prefixes of the record at the block's TOP row    */
+    int merge; /* [2][nwl][3][64] the waves' minima: costs, then indices, from word 0 on                             */
+};
+__host__ __device__ __forceinline__ P1Lds p1_lds(const DevParams& P, int nwl, int tile, bool windowed) {
+    const int nlb = tile * IS_QPT + 1, dp = (windowed ? IS_P1_WIN : P.D) + 1;
+    return {nlb, dp, IS_TILE * dp, (P.H + 1 + 3) & ~3, 8 * nwl, IS_P1_L7_WORDS, nlb * 64, nlb * IS_P1_SUM_F, 2 * nwl * 3 * 64};
+}
+static size_t p1_lds_bytes(const DevParams* P, int nwaves, int tile, bool windowed) {
+    const P1Lds L = p1_lds(*P, nwaves, tile, windowed);
+    return sizeof(float) * ((size_t)(L.tile > L.merge ? L.tile : L.merge) + L.rcp + L.scr + L.thr + L.lb + L.sum) + 32;
+}
+/* lemma L7: no block at or below block k / strictly below block k holds a possible winner */
+__device__ __forceinline__ bool l7_none_le(unsigned long long mask, int k) { return (mask & ((2ull << min(k, 62)) - 1ull)) == 0ull; }
+__device__ __forceinline__ bool l7_none_below(unsigned long long mask, int k) { return (mask & ((1ull << min(k, 63)) - 1ull)) == 0ull; }
+__device__ __forceinline__ void pair_best_init(PairBest& b) {
+    b.g = b.o = b.s = IS_INF;
+    b.ig = b.is = -1;
+    b.io = IS_OBJECT; /* :592 */
+}
+/* ---- phase 1: the first segment, the generic step and the pieces of the FAST walk: file-scope macros, every name they
+ * touch an argument.  As __forceinline__ functions each took some tools/kres.sh figure of the six k_pw_phase1 above the
+ * parent's (the table: DESIGN.md 10v); as text the instruction streams are the parent's.
+ * The vB = 0 candidate (:481-594), stated once.  rh / rcp_tab: 1/h of the lane and its table (global memory in tile 0, the
+ * staged copy elsewhere); vt_value(fni): lutT[vT + 1][fni] of the lane; CMP: the descending FAST walk meets vB = 0 LAST and
+ * lets it replace a candidate of equal cost (<=), the ascending walks and tile 0 meet it FIRST and take it with the
+ * reference's strict < (the tie rule: the smallest vB among equal costs; a +inf candidate keeps the initial index). */
+#define IS_P1_FIRST_SEGMENT(FASTF, HAS_INVALID, CMP, P, my, rcol, lcol, vT, vTc, live, vhor, D, rh, rcp_tab, vt_value, bg, \
+                            big, bo, bio)                                                                                 \
+    {                                                                                                                     \
+        const RowRec rb = sload_rec(rcol);                                                                                \
+        const int h = vTc + 1;                                                                                            \
+        const SegTerms t = eval_segment<FASTF, HAS_INVALID>(my, rb, (float)h, rh, D, P.iw, rcp_tab);                      \
+        const float od = vt_value(t.fni) - lcol[(unsigned)t.fni];                                                         \
+        const bool below = vT <= vhor;                                                                                    \
+        const float cost_g = P.dw * t.gd + P.pw * P.first_g + P.sw * t.seg_g;                                             \
+        const bool ug = live && below && (cost_g CMP bg);                                                                 \
+        bg = ug ? cost_g : bg;                                                                                            \
+        big = ug ? IS_GROUND : big;                                                                                       \
+        const float prior = below ? P.first_o_below : P.first_o_above;                                                    \
+        const float cost = P.dw * od + P.pw * prior + P.sw * t.seg_o;                                                     \
+        const bool uo = live && (cost CMP bo);                                                                            \
+        bo = uo ? cost : bo;                                                                                              \
+        bio = uo ? IS_OBJECT : bio;                                                                                       \
+    }
+/* One step of the generic ascending walk (columns outside the FAST encodings): the reference's strict <, no bound. */
+#define IS_P1_GENERIC_STEP(SKY, NOG, HAS_INVALID,        NRW, P, my, b, vB, nw, H, D, vTc, live, rcol, scol, lcol, lrsrc, \
+                           lane4r, s_rcp, od_value, next_row)                                                             \
+    {                                                                                                                     \
+        const RowRec rb = sload_rec(rcol + vB);                                                                           \
+        const StepVals st = sload_step(scol + vB);                                                                        \
+        const LutRow<NRW> row = next_row;                                                                                 \
+        load_lut_row<NRW>(next_row, lrsrc, lcol, min(vB + nw, H), D, lane4r);                                             \
+        const int h = vTc + 1 - vB;                                                                                       \
+        const SegTerms t = eval_segment<false, HAS_INVALID>(my, rb, (float)h, s_rcp[h], D, P.iw, s_rcp);                  \
+        const float od = od_value(row, t.fni, vB);                                                                        \
+        pairwise_step<SKY, true, NOG>(P, st, vB, live, od, t, b);                                                         \
+    }
+/* One full step at vB: all three candidates of (vB, vT), then the bounds -> ok_o / ok_x (declared here): the object type /
+ * the step's ground or sky type can be closed.  Its tail (IS_P1_SREC) requests the StepRec and the scalar half of the record
+ * of the next step when the step has read its own for the last time (the bounds): one set of registers each instead of two,
+ * and the loads have the first half of the next step to arrive.  (As functions over a walk-state struct the step, the round
+ * and the skip leave k_pw_phase1<false, 2, false> uncompilable: the "+s" pin of vB * 3 in pairwise_step meets a VGPR.)
+ * (an invalid-disparity value takes the same step: valid-count operands and an IEEE division per step took it to 90+
+ * VGPRs; the mean of a FAST column goes through mean_valid_fast -- a table read and the exact-division shortcut) */
+#define IS_P1_STEP(SKY, NOG, HAS_INVALID, NRW, P, my, b, vB, nw, lane, l15, vTc, live, D, rcol, scol, lcol, lrsrc,     \
+                   lane4r, scr, s_rcp, s_lb, od_value, next_row, c_r0, c_r1, n_r0, n_r1, st_next, S, n_full, E1o, E2,  \
+                   E1gs, dead, gdead, mask_g, mask_s, ok_o, ok_x)                                                      \
+    const LutRow<NRW> row = next_row;                                                                                  \
+    if (IS_P1_TOUCH_AHEAD > 0)                                                                                         \
+        touch_step(rcol, scol, max(vB - IS_P1_TOUCH_AHEAD * nw, 0), lane, scr);                                        \
+    load_lut_row<NRW>(next_row, lrsrc, lcol, max(vB - nw, 0), D, lane4r);                                              \
+    const int h = vTc + 1 - vB;                                                                                        \
+    const int kb = (vB + IS_QB - 1) >> IS_QB_LOG; /* the bound block of vB (>= 1) */                                   \
+    const float* lbp = s_lb + kb * 64 + lane;                                                                          \
+    bool ok_o = false, ok_x = (NOG);                                                                                   \
+    {                                                                                                                  \
+        n_full++;                                                                                                      \
+        const float r0 = c_r0, r1 = c_r1;                                                                              \
+        StepVals st = st_next;                                                                                         \
+        c_r0 = n_r0; c_r1 = n_r1;                                                                                      \
+        {                                                                                                              \
+            const float* q2 = (const float*)(rcol + max(vB - 2 * nw, 0));                                              \
+            if (!IS_P1_SREC) n_r0 = q2[l15];                                                                           \
+            n_r1 = q2[16 + l15];                                                                                       \
+        }                                                                                                              \
+        constexpr int WANT = (SKY) ? IS_WANT_SKY : ((NOG) ? 0 : IS_WANT_GROUND);                                       \
+        SegTerms t;                                                                                                    \
+        if (IS_P1_SREC) {                                                                                              \
+            pin_step(st);                                                                                              \
+            srec_arrived(S);                                                                                           \
+            t = eval_segment_mix<HAS_INVALID, WANT>(my, S, r1, (float)h, s_rcp[h], D, P.iw, s_rcp);                    \
+        } else {                                                                                                       \
+            t = eval_segment_dpp<HAS_INVALID, WANT>(my, r0, r1, (float)h, s_rcp[h], D, P.iw, s_rcp);                   \
+        }                                                                                                              \
+        const float od = od_value(row, t.fni, vB);                                                                     \
+        if (!IS_P1_SREC) {                                                                                             \
+            /* the next StepRec: requested only now -- every LDS wait is an lgkmcnt(0)                                 \
+             * wait and would wait for this scalar load too (SMEM returns out of order) */                             \
+            const StepRec* sn = scol + max(vB - nw, 0);                                                                \
+            asm volatile("" : "+s"(sn) : "v"(od));                                                                     \
+            st_next = sload_step(sn);                                                                                  \
+        }                                                                                                              \
+        pairwise_step<SKY, true, NOG, true>(P, st, vB, live, od, t, b);                                                \
+        const float lb_o = min_raw((st.q_o - E1o) + P.sw * seg_o_lower_bound(t, E2), lbp[0]);                          \
+        ok_o = (__builtin_amdgcn_ballot_w64(lb_o > b.o) | dead) == ~0ull;                                              \
+        if (SKY) {                                                                                                     \
+            const float lb_s = (st.q_gs - E1gs) + P.sw * t.seg_s;                                                      \
+            ok_x = (__builtin_amdgcn_ballot_w64(lb_s > b.s) | dead) == ~0ull &&                                        \
+                   l7_none_below(mask_s, kb);                                                                          \
+        } else if (!(NOG)) {                                                                                           \
+            const float lb_g = (st.q_gs - E1gs) + P.sw * t.seg_g;                                                      \
+            ok_x = (__builtin_amdgcn_ballot_w64(lb_g > b.g) | gdead) == ~0ull &&                                       \
+                   l7_none_below(mask_g, kb);                                                                          \
+        }                                                                                                              \
+    }                                                                                                                  \
+    if (!(NOG)) ok_x = ok_x || l7_none_le((SKY) ? mask_s : mask_g, kb);                                                \
+    if (IS_P1_SREC) {                                                                                                  \
+        const int vn = max(vB - nw, 0);                                                                                \
+        const StepRec* sn = scol + vn;                                                                                 \
+        asm volatile("" : "+s"(sn) : "s"(__builtin_amdgcn_readfirstlane((int)((NOG) ? ok_o : ok_x))));                 \
+        st_next = sload_step_raw(sn); /* pinned (= waited for) at its use */                                           \
+        srec_request_next(S, rcol + vn);                                                                               \
+    }
+/* ground / sky candidates of up to four vB (vB, vB - nw, ...) >= lo; closes `x_closed`
+ * when the bound of the last one holds; leaves vB at the next unvisited value */
+#define IS_P1_GS4(SKY, lo, x_dead, x_closed, P, my, b, vB, nw, lane, rcol, scol, scr, n_gs, E1gs, mask_g, mask_s)      \
+    {                                                                                                                  \
+        const int n_here = min(4, (vB - (lo)) / nw + 1);                                                               \
+        n_gs += n_here;                                                                                                \
+        if (IS_P1_TOUCH_AHEAD > 0) touch_round(rcol, scol, vB - 4 * nw, nw, (lo), lane, scr);                          \
+        float c_f[4], c_cost[4];                                                                                       \
+        int c_idx[4];                                                                                                  \
+        float c_q[4];                                                                                                  \
+        _Pragma("unroll") for (int j = 0; j < 4; j++) {                                                                \
+            const int vj = max(vB - j * nw, (lo)); /* clamped: the loads are unconditional */                          \
+            crec_t rq = (crec_t)(rcol + vj);                                                                           \
+            cstep_t sq = (cstep_t)(scol + vj);                                                                         \
+            const float nic = P.iw * (float)(my.Fnic - rq->Fnic);                                                      \
+            c_f[j] = (SKY) ? (my.Fsky - rq->Fsky)                                                                      \
+                       : __builtin_fminf(my.Fg0 - rq->Fg0, my.Fg1 - rq->Fg1);                                          \
+            const float data = (SKY) ? (my.K - rq->K) : (my.G - rq->G);                                                \
+            c_f[j] += nic; /* f + nic: also monotone (lemma L2), and part of the cost */                               \
+            c_cost[j] = P.dw * data + sq->pwmp + P.sw * c_f[j];                                                        \
+            c_idx[j] = sq->idx_gs;                                                                                     \
+            c_q[j] = sq->q_gs;                                                                                         \
+        }                                                                                                              \
+        float f_last = c_f[0], q_last = c_q[0];                                                                        \
+        _Pragma("unroll") for (int j = 0; j < 4; j++) {                                                                \
+            if (j < n_here) {                                                                                          \
+                if (SKY) take_if_le(b.s, b.is, c_cost[j], c_idx[j]);                                                   \
+                else take_if_le(b.g, b.ig, c_cost[j], c_idx[j]);                                                       \
+                f_last = c_f[j]; q_last = c_q[j];                                                                      \
+            }                                                                                                          \
+        }                                                                                                              \
+        const int vb_l = vB - (n_here - 1) * nw; /* the lowest vB just evaluated */                                    \
+        const float lb_x = (q_last - E1gs) + P.sw * f_last;                                                            \
+        if ((__builtin_amdgcn_ballot_w64(lb_x > ((SKY) ? b.s : b.g)) | (x_dead)) == ~0ull &&                           \
+            l7_none_below((SKY) ? mask_s : mask_g, (vb_l + IS_QB - 1) >> IS_QB_LOG))                                   \
+            x_closed = true;                                                                                           \
+        vB -= n_here * nw;                                                                                             \
+    }
+/* in front of a ground / sky round, INSIDE the round's loop: close the type (x_closed, and leave the loop) when no
+ * surviving block is left at or below the block of vB; jump over the blocks that cannot hold the winner to this wave's
+ * largest vB in the next surviving block (block 0 = the first segment, vB = 0) and test the loop's range again.  The
+ * `break` / `continue` are the caller's loop's: with the outcome handed back instead (an action the caller switches on,
+ * as a macro or as a function) three instantiations spill more SGPRs than the parent's -- <false, 0, false> 87 (80),
+ * <false, 2, false> 78 (73), <false, 2, true> 89 (85). */
+#define IS_P1_L7_SKIP(mask, x_closed, vB, w, nw)                                                   \
+    {                                                                                              \
+        const int kb = min((vB + IS_QB - 1) >> IS_QB_LOG, 62);                                     \
+        const unsigned long long at_or_below = (mask) & ((2ull << kb) - 1ull);                     \
+        if (at_or_below == 0ull) { x_closed = true; break; }                                       \
+        if (!(((mask) >> kb) & 1ull)) {                                                            \
+            const int top = (63 - __builtin_clzll(at_or_below)) << IS_QB_LOG;                      \
+            int dd = (top - w) % nw;                                                               \
+            dd = dd < 0 ? dd + nw : dd;                                                            \
+            vB = top - dd;                                                                         \
+            continue;                                                                              \
+        }                                                                                          \
+    }
+/* ---- phase 1: the summary prefetch: request into registers in front of the tile staging, commit to LDS behind it ---- */
+#define IS_P1_PRE_N 2 /* floats per thread: NLB * 32 <= IS_P1_PRE_N * nthreads at 1024 rows */
+struct P1SumRegs { float v[IS_P1_PRE_N]; };
+/* entry i of the summaries' LDS copy (P1Lds::sum) */
+__device__ __forceinline__ float p1_sum_entry(const RowRec* rcol, const float* bcol, int i) {
+    const int k = i / IS_P1_SUM_F, j = i - k * IS_P1_SUM_F;
+    if (j >= IS_L7_F) return ((const float*)(rcol + (size_t)k * IS_QB))[24 + (j - IS_L7_F)];
+    return k >= 1 ? bcol[k * IS_L7_F + j] : 0.0f; /* (the summary of block 0 is analytic) */
+}
+/* request: the thread's entries into registers, where the whole copy fits them (n <= IS_P1_PRE_N * nthr) ... */
+__device__ __forceinline__ P1SumRegs p1_sum_request(const RowRec* rcol, const float* bcol, int tid, int n, int nthr) {
+    P1SumRegs r;
+    if (n <= IS_P1_PRE_N * nthr) {
+#pragma unroll
+        for (int j = 0; j < IS_P1_PRE_N; j++) {
+            const int i = tid + j * nthr;
+            r.v[j] = i < n ? p1_sum_entry(rcol, bcol, i) : 0.0f;
+        }
+    }
+    return r;
+}
+/* ... commit: to LDS (tall frames: a plain loop) */
+__device__ __forceinline__ void p1_sum_commit(const RowRec* rcol, const float* bcol, int tid, int n, int nthr,
+                                              const P1SumRegs& r, float* s_sum) {
+    if (n <= IS_P1_PRE_N * nthr) {
+#pragma unroll
+        for (int j = 0; j < IS_P1_PRE_N; j++)
+            if (tid + j * nthr < n) s_sum[tid + j * nthr] = r.v[j];
+    } else {
+        for (int i = tid; i < n; i += nthr) s_sum[i] = p1_sum_entry(rcol, bcol, i);
+    }
+}
+/* ---- phase 1, stage: the tile-0 shortcut ------------------------------------------------------------------------
+ * Tile 0 has ONE candidate per row, the first segment (vB = 0, :481-594), and it belongs to wave 0
+ * of split 0: that wave computes it with its operands straight from global memory (1/h, the two
+ * lutT values of the lane) and writes the partial minima in the form the merge below would; no
+ * tile staging, no barrier, the other waves leave at once.  (The full prologue + merge made the
+ * tile-0 launch as long as a launch with work: 0.24 ms per 64 frames.) */
+template <bool FAST, bool HAS_INVALID>
+__device__ __forceinline__ void p1_tile0(const DevParams& P, const RowRec* rcol, const float* lcol, const float* __restrict__ rcp,
+                                         int H, int D, int lane, int wl, int vhor, int colg, int split, int nsplit,
+                                         float* __restrict__ part_cost, int* __restrict__ part_idx,
+                                         unsigned long long* __restrict__ counters) {
+    if (wl != 0) return;
+    const int vT = lane;
+    const int vTc = min(vT, H - 1);
+    const bool live = vT < H;
+    float cg = IS_INF, co = IS_INF;
+    int ig = -1, io = IS_OBJECT;
+    if (split == 0) {
+        const RowRec my = load_rec(rcol + vTc + 1);
+        auto vt_global = [&](int fni) -> float { return lcol[(size_t)min(vT + 1, H) * D + (unsigned)fni]; };
+        IS_P1_FIRST_SEGMENT(FAST, HAS_INVALID, <, P, my, rcol, lcol, vT, vTc, live, vhor, D, rcp[min(vTc + 1, H)], rcp,
+                            vt_global, cg, ig, co, io)
+    }
+    const size_t o = (((size_t)colg * nsplit + split) * 3) * 64 + lane;
+    part_cost[o] = cg;            part_idx[o] = ig;
+    part_cost[o + 64] = co;       part_idx[o + 64] = io;
+    part_cost[o + 128] = IS_INF;  part_idx[o + 128] = -1;
+    if (counters != nullptr && lane == 0 && split == 0) atomicAdd(counters + IS_CNT_P1_FULL, 1ull);
+}
+/* ---- phase 1, stage: the generic ascending walk (columns outside the FAST encodings), the first segment at its head -- */
+template <bool HAS_INVALID, int NRW, class OD, class VT>
+__device__ __forceinline__ void p1_generic_walk(const DevParams& P, const RowRec& my, PairBest& b, int w, int nw, int vT, int vTc,
+                                                bool live, int vhor, int tile_lo, int vB_last, int H, int D, const RowRec* rcol,
+                                                const StepRec* scol, const float* lcol, __amdgpu_buffer_rsrc_t lrsrc,
+                                                int lane4r, const float* s_rcp, OD&& od_value, VT&& vt_value) {
+    int vB = w;
+    LutRow<NRW> next_row;
+    if (vB <= vB_last) load_lut_row<NRW>(next_row, lrsrc, lcol, vB == 0 ? min(nw, H) : vB, D, lane4r);
+    if (vB == 0) {
+        IS_P1_FIRST_SEGMENT(false, HAS_INVALID, <, P, my, rcol, lcol, vT, vTc, live, vhor, D, s_rcp[vTc + 1], s_rcp,
+                            vt_value, b.g, b.ig, b.o, b.io)
+        vB += nw;
+    }
+    if (tile_lo >= vhor)
+        for (; vB <= min(vhor, vB_last); vB += nw) /* ground range, ground candidate = +inf */
+            IS_P1_GENERIC_STEP(false, true, HAS_INVALID, NRW, P, my, b, vB, nw, H, D, vTc, live, rcol, scol, lcol, lrsrc, lane4r,
+                               s_rcp, od_value, next_row)
+    for (; vB <= min(vhor, vB_last); vB += nw) /* ground range: vB-1 < vhor */
+        IS_P1_GENERIC_STEP(false, false, HAS_INVALID, NRW, P, my, b, vB, nw, H, D, vTc, live, rcol, scol, lcol, lrsrc, lane4r,
+                               s_rcp, od_value, next_row)
+    for (; vB <= vB_last; vB += nw) /* sky range */
+        IS_P1_GENERIC_STEP(true, false, HAS_INVALID, NRW, P, my, b, vB, nw, H, D, vTc, live, rcol, scol, lcol, lrsrc, lane4r,
+                               s_rcp, od_value, next_row)
+}
+/* ---- phase 1, stage: staging, with the summary prefetch -> the lane's record (row vT + 1), *win_lo ---------------------
+ * What the pre-pass of the branch-and-bound reads -- the separable summaries of the lower bound
+ * blocks (lemmas L7, L8: 24 floats per block) -- is requested in front of the tile staging, and
+ * lands in LDS with it: one memory round trip for the whole prologue (round 3 chased a record and a
+ * StepRec per block top through scalar loads, one after the other: the 0.25 ms floor of a launch is
+ * a chain of such round trips).
+ * Ends with the barrier behind which the tile, 1/h, the summaries and the reset exchange of lemma L7 are in LDS. */
+template <bool FAST, bool WIN>
+__device__ __forceinline__ RowRec p1_stage(const DevParams& P, const P1Lds& L, float* s_tile, float* s_rcp, float* s_sum,
+                                           unsigned* s_thr, const RowRec* rcol, const float* lcol,
+                                           const float* __restrict__ rcp, const float* __restrict__ blksum, int colg, int tile,
+                                           int tile_lo, int vTc, int H, int D, int tid, int* win_lo) {
+    const float* bcol = blksum + (size_t)colg * (P.ntiles * IS_QPT + 1) * IS_L7_F;
+    const int nthr = (int)blockDim.x, n_sum = L.nlb * IS_P1_SUM_F;
+    P1SumRegs pre;
+    if (FAST) pre = p1_sum_request(rcol, bcol, tid, n_sum, nthr);
+    *win_lo = WIN ? __builtin_amdgcn_readfirstlane(P.win_lo[(size_t)colg * P.ntiles + tile]) : 0;
+    if (WIN) stage_window_and_rcp(s_tile, s_rcp, lcol, rcp, tile_lo, H, D, *win_lo, tid, nthr);
+    else stage_tile_and_rcp(s_tile, s_rcp, lcol, rcp, tile_lo, H, D, tid, nthr);
+    const RowRec my = load_rec(rcol + vTc + 1);
+    if (FAST) p1_sum_commit(rcol, bcol, tid, n_sum, nthr, pre, s_sum);
+    /* (round 6, one frame per call: the record / StepRec lines of the wave's first 3 or 5 steps touched here, in front
+     * of the barrier and the pre-pass -- 1.563-1.588 against 1.574-1.576 ms per frame: nothing, as in round 4) */
+    /* lemma L7: per-lane thresholds (order-preserving keys, +inf) and the two survive masks */
+    if (tid < 2 * 64) s_thr[tid] = 0xFF800000u;
+    if (tid < 4) s_thr[2 * 64 + tid] = 0u;
+    __syncthreads();
+    return my;
+}
+
 template <bool FAST, bool HAS_INVALID, int NR, bool WIN>
-__device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, int colg, int tile,
-                                               const RowRec* __restrict__ recs,
-                                               const float* __restrict__ lutT,
-                                               const StepRec* __restrict__ steps,
-                                               const float* __restrict__ rcp, int vhor,
-                                               int split, int nsplit,
-                                               const PruneRec* __restrict__ prec,
-                                               float* __restrict__ part_cost,
-                                               int* __restrict__ part_idx,
-                                               unsigned long long* __restrict__ counters,
-                                               const float* __restrict__ joined,
-                                               const float* __restrict__ cost_T,
-                                               const float* __restrict__ blksum) {
+__device__ __forceinline__ void pw_phase1_body(
+    const DevParams& P, char* smem, int colg, int tile, const RowRec* __restrict__ recs, const float* __restrict__ lutT,
+    const StepRec* __restrict__ steps, const float* __restrict__ rcp, int vhor, int split, int nsplit,
+    const PruneRec* __restrict__ prec, float* __restrict__ part_cost, int* __restrict__ part_idx,
+    unsigned long long* __restrict__ counters, const float* __restrict__ blksum) {
     const int H = P.H, D = P.D;
-    /* the vT-side tile: all D lutT columns of the 64 rows, or the fn window [win_lo, win_lo + IS_P1_WIN) of
-     * wide tables (is_device.h) */
     constexpr bool windowed = WIN; /* (the launch picks the instantiation: tile < CallPlan::win_tiles) */
-    const int win_w = windowed ? IS_P1_WIN : D;
-    const int DP = win_w + 1;
-    float* s_tile = (float*)smem;             /* [64][win_w + 1] */
-    float* s_rcp = s_tile + IS_TILE * DP;     /* [H+1]     */
-    float* s_scr = s_rcp + ((H + 1 + 3) & ~3); /* [8 per wave] landing area of the L2-warming DMAs */
+    float* lds = (float*)smem;
     const int tid = threadIdx.x, lane = tid & 63;
     /* `nsplit` workgroups share the vB range of one (column, tile): together they behave like
      * one workgroup of nsplit * nwl waves (few columns = small batches: more of the chip works
@@ -637,109 +930,34 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
     const int nw = nwl * nsplit;
     const int w = split * nwl + wl;
     const int tile_lo = tile * IS_TILE;
-    const int colr = colg;
-    const RowRec* rcol = recs + (size_t)colr * (H + 1);
-    const float* lcol = lutT + (size_t)colr * (H + 1) * D;
-    const StepRec* scol = steps + (size_t)colr * H;
-
-    /* Tile 0 has ONE candidate per row, the first segment (vB = 0, :481-594), and it belongs to wave 0
-     * of split 0: that wave computes it with its operands straight from global memory (1/h, the two
-     * lutT values of the lane) and writes the partial minima in the form the merge below would; no
-     * tile staging, no barrier, the other waves leave at once.  (The full prologue + merge made the
-     * tile-0 launch as long as a launch with work: 0.24 ms per 64 frames.) */
+    const RowRec* rcol = recs + (size_t)colg * (H + 1);
+    const float* lcol = lutT + (size_t)colg * (H + 1) * D;
+    const StepRec* scol = steps + (size_t)colg * H;
     if (tile == 0) {
-        if (wl != 0) return;
-        const int vT = lane;
-        const int vTc = min(vT, H - 1);
-        const bool live = vT < H;
-        float cg = IS_INF, co = IS_INF;
-        int ig = -1, io = IS_OBJECT;
-        if (split == 0) {
-            const RowRec my = load_rec(rcol + vTc + 1);
-            const RowRec rb = sload_rec(rcol);
-            const int h = vTc + 1;
-            const SegTerms t = eval_segment<FAST, HAS_INVALID>(my, rb, (float)h, rcp[min(h, H)], D, P.iw, rcp);
-            const float od = lcol[(size_t)min(vT + 1, H) * D + (unsigned)t.fni] - lcol[(unsigned)t.fni];
-            const bool below = vT <= vhor;
-            const float cost_g = P.dw * t.gd + P.pw * P.first_g + P.sw * t.seg_g;
-            const bool ug = live && below && (cost_g < IS_INF); /* (a +inf candidate keeps the initial index) */
-            cg = ug ? cost_g : cg;
-            ig = ug ? IS_GROUND : ig;
-            const float prior = below ? P.first_o_below : P.first_o_above;
-            const float cost = P.dw * od + P.pw * prior + P.sw * t.seg_o;
-            co = (live && cost < IS_INF) ? cost : co;
-        }
-        const size_t o = (((size_t)colg * nsplit + split) * 3) * 64 + lane;
-        part_cost[o] = cg;            part_idx[o] = ig;
-        part_cost[o + 64] = co;       part_idx[o + 64] = io;
-        part_cost[o + 128] = IS_INF;  part_idx[o + 128] = -1;
-        if (counters != nullptr && lane == 0 && split == 0) atomicAdd(counters + IS_CNT_P1_FULL, 1ull);
+        p1_tile0<FAST, HAS_INVALID>(P, rcol, lcol, rcp, H, D, lane, wl, vhor, colg, split, nsplit, part_cost, part_idx, counters);
         return;
     }
-
     const int vB_last = min(tile_lo, H - 1);
     const int vT = tile_lo + lane;
     const int vTc = min(vT, H - 1);
-    /* What the pre-pass of the branch-and-bound reads -- the separable summaries of the lower bound
-     * blocks (lemmas L7, L8: 24 floats per block) -- is requested HERE, in front of the tile staging, and
-     * lands in LDS with it: one memory round trip for the whole prologue (round 3 chased a record and a
-     * StepRec per block top through scalar loads, one after the other: the 0.25 ms floor of a launch is
-     * a chain of such round trips). */
-    const int NLB = tile * IS_QPT + 1; /* bound blocks 0 .. tile * IS_QPT of this tile's candidates */
-    float* s_lb = s_scr + 8 * nwl + IS_P1_L7_WORDS;   /* [NLB][64 lanes] object block bounds      */
-    float* s_sum = s_lb + NLB * 64;                   /* [NLB][IS_P1_SUM_F]: 24 summary floats + the instance
-                                                       * prefixes (dwords 24..31) of the record at the block's TOP row */
-    const float* bcol = blksum + (size_t)colr * (P.ntiles * IS_QPT + 1) * IS_L7_F;
-    constexpr int PRE_N = 2; /* floats per thread: NLB * 32 <= PRE_N * nthreads at 1024 rows */
-    float pre_v[PRE_N];
-    const int nthr = (int)blockDim.x;
-    const bool pre_regs = FAST && NLB * IS_P1_SUM_F <= PRE_N * nthr;
-    auto pre_load = [&](int i) -> float { /* entry i of s_sum */
-        const int k = i / IS_P1_SUM_F, j = i - k * IS_P1_SUM_F;
-        if (j >= IS_L7_F) return ((const float*)(rcol + (size_t)k * IS_QB))[24 + (j - IS_L7_F)];
-        return k >= 1 ? bcol[k * IS_L7_F + j] : 0.0f; /* (the summary of block 0 is analytic) */
-    };
-    if (pre_regs) {
-#pragma unroll
-        for (int j = 0; j < PRE_N; j++) {
-            const int i = tid + j * nthr;
-            pre_v[j] = i < NLB * IS_P1_SUM_F ? pre_load(i) : 0.0f;
-        }
-    }
-    const int win_lo = windowed ? __builtin_amdgcn_readfirstlane(P.win_lo[(size_t)colr * P.ntiles + tile]) : 0;
-    if (windowed) stage_window_and_rcp(s_tile, s_rcp, lcol, rcp, tile_lo, H, D, win_lo, tid, (int)blockDim.x);
-    else stage_tile_and_rcp(s_tile, s_rcp, lcol, rcp, tile_lo, H, D, tid, (int)blockDim.x);
-    const RowRec my = load_rec(rcol + vTc + 1);
-    if (pre_regs) {
-#pragma unroll
-        for (int j = 0; j < PRE_N; j++) {
-            const int i = tid + j * nthr;
-            if (i < NLB * IS_P1_SUM_F) s_sum[i] = pre_v[j];
-        }
-    } else if (FAST) { /* tall frames: a plain loop */
-        for (int i = tid; i < NLB * IS_P1_SUM_F; i += nthr) s_sum[i] = pre_load(i);
-    }
+    const P1Lds L = p1_lds(P, nwl, tile, windowed);
+    float *s_tile = lds, *s_rcp = s_tile + L.tile, *s_scr = s_rcp + L.rcp;
+    unsigned* s_thr = (unsigned*)(s_scr + L.scr);
+    float *s_lb = s_scr + L.scr + L.thr, *s_sum = s_lb + L.lb;
+    const int DP = L.dp, NLB = L.nlb;
+    int win_lo;
+    const RowRec my = p1_stage<FAST, WIN>(P, L, s_tile, s_rcp, s_sum, s_thr, rcol, lcol, rcp, blksum, colg, tile, tile_lo, vTc, H, D,
+                                          tid, &win_lo);
     const float* my_tile = s_tile + lane * DP;
     const bool live = vT < H;
-    /* (round 6, one frame per call: the record / StepRec lines of the wave's first 3 or 5 steps touched here, in front
-     * of the barrier and the pre-pass -- 1.563-1.588 against 1.574-1.576 ms per frame: nothing, as in round 4) */
-    /* lemma L7: per-lane thresholds (order-preserving keys, +inf) and the two survive masks */
-    unsigned* s_thr = (unsigned*)(s_scr + 8 * nwl); /* [2][64] + [4] */
-    if (tid < 2 * 64) s_thr[tid] = 0xFF800000u;
-    if (tid < 4) s_thr[2 * 64 + tid] = 0u;
-    __syncthreads();
-
     PairBest b;
-    b.g = b.o = b.s = IS_INF;
-    b.ig = b.is = -1;
-    b.io = IS_OBJECT; /* :592 */
+    pair_best_init(b);
     const __amdgpu_buffer_rsrc_t lrsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void*)lcol, 0, (H + 1) * D * (int)sizeof(float), 0x00020000);
-    const int lane4 = lane * 4;
     /* WIN: ONE load fetches the window columns of a vB row (lane l: staged column l & 31 -- both ends of a segment
      * read the SAME lutT column, so the row needs what the tile holds); classic: NR loads, the whole row */
     constexpr int NRW = windowed ? 1 : NR;
-    const int lane4r = windowed ? IS_WIN_COL(win_lo, lane & (IS_P1_WIN - 1)) * 4 : lane4;
+    const int lane4r = windowed ? IS_WIN_COL(win_lo, lane & (IS_P1_WIN - 1)) * 4 : lane * 4;
     const unsigned scr = lds_addr(s_scr + 8 * wl);
     /* lutT[vT + 1][fni] of this lane: from the staged tile / window; outside the window from global memory */
     int n_winmiss = 0; /* steps in which some lane read outside the window (evaluation counters) */
@@ -759,55 +977,49 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
         if (!windowed) return my_tile[fni] - pick_lut<NRW>(row, fni);
         const int fo = IS_WIN_FIND(win_lo, fni);
         const bool in_t = fo >= 0; /* the tile's window = the row registers' */
-        const bool in_r = in_t;
         float vt = my_tile[in_t ? fo : 0];
         float vb = pick_lut<NRW>(row, in_t ? fo : 0);
         if (__builtin_amdgcn_ballot_w64(!in_t) != 0ull) {
             n_winmiss++;
             if (!in_t) vt = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(lrsrc, ((vTc + 1) * D + fni) * 4, 0, 0));
-            if (!in_r) vb = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(lrsrc, (vB_row * D + fni) * 4, 0, 0));
+            if (!in_t) vb = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(lrsrc, (vB_row * D + fni) * 4, 0, 0));
         }
         return vt - vb;
     };
     if (FAST) {
-        /* FAST columns: vB downwards with the exact branch-and-bound of DESIGN.md "Pruning".  The
-         * candidates of a tile fall into BLOCKS: block k >= 1 = the vB values 64 (k-1) + 1 .. 64 k
-         * whose StepRecs phase 2 of tile k - 1 built, block 0 = the first segment vB = 0.  A
-         * candidate vB' of block k with vB' <= vB costs lane vT at least
+        /* FAST columns: vB downwards with the exact branch-and-bound of DESIGN.md "Pruning".  The candidates of a tile
+         * fall into BLOCKS: block k >= 1 = the vB values 64 (k-1) + 1 .. 64 k whose StepRecs phase 2 of tile k - 1
+         * built, block 0 = the first segment vB = 0.  A candidate vB' of block k with vB' <= vB costs lane vT at least
          *     fl(fl(q[vB] - E1) + fl(sw * m(vB, vT)))      (same block as vB)
          *     fl(fl(q[64 k] - E1) + fl(sw * m(64 k, vT)))  (lower block, from its TOP row)
-         * m = the monotone semantic term of the type (seg_g / seg_s / seg_o_lower_bound), q =
-         * StepRec.q_o / q_gs = the smallest transition term pw * min_prev of the block's rows up to
-         * vB (phase 2 restarts the running minimum with every tile, so q[64 k] is the minimum of
-         * the whole block), E1 / E2 the slacks of PruneRec: the monotonicity argument of the unary
-         * kernel, block by block.  The accumulated path cost inside q grows with vB, so a bound
-         * that may use the block's own q instead of the minimum over ALL lower rows closes a type a
-         * few rows below the region of the lane instead of vT / 16 rows further down.
+         * m = the monotone semantic term of the type (seg_g / seg_s / seg_o_lower_bound), q = StepRec.q_o / q_gs = the
+         * smallest transition term pw * min_prev of the block's rows up to vB (phase 2 restarts the running minimum
+         * with every tile, so q[64 k] is the minimum of the whole block), E1 / E2 the slacks of PruneRec: the
+         * monotonicity argument of the unary kernel, block by block.  The accumulated path cost inside q grows with vB,
+         * so a bound that may use the block's own q instead of the minimum over ALL lower rows closes a type a few rows
+         * below the region of the lane instead of vT / 16 rows further down.
          *
-         * Pre-pass: the waves evaluate the semantic terms at the tops of all lower blocks (at most
-         * tile values of vB, no LUT access, no update) and leave, per type and block k, the
-         * smallest bound of the blocks BELOW k in LDS (s_lb); the walk closes a type for good when
-         * the bound of its own block and that entry both exceed the lane's best cost. */
-        /* (round 4: the BOUND blocks are IS_QB = 32 rows, half a tile -- see is_device.h; "64 k" above
-         * reads IS_QB k.  Only the OBJECT type keeps the per-block array s_lb; the ground / sky types
-         * close when their own block's bound holds and the separable summaries (lemma L7) leave no
-         * surviving block below.) */
-        const unsigned long long dead = ~__builtin_amdgcn_ballot_w64(live);
-        const unsigned long long gdead = dead | __builtin_amdgcn_ballot_w64(my.G == IS_INF);
-        /* Separable block bounds of the ground / sky candidates (lemma L7, see l7_row_bounds): bit k
-         * of mask_g / mask_s = block k may hold the winning ground / sky candidate of some lane of
-         * this tile; the walk below never enters the other blocks.  Off (all ones) when the column's
-         * pruning is off or the column has more blocks than the masks have bits (then the ground /
-         * sky types only close in block 0: slower, never wrong). */
+         * Pre-pass: the waves evaluate the semantic terms at the tops of all lower blocks (at most tile values of vB,
+         * no LUT access, no update) and leave, per type and block k, the smallest bound of the blocks BELOW k in LDS
+         * (s_lb); the walk closes a type for good when the bound of its own block and that entry both exceed the lane's
+         * best cost. */
+        /* (round 4: the BOUND blocks are IS_QB = 32 rows, half a tile -- see is_device.h; "64 k" above reads IS_QB k.
+         * Only the OBJECT type keeps the per-block array s_lb; the ground / sky types close when their own block's
+         * bound holds and the separable summaries (lemma L7) leave no surviving block below.) */
+        /* the prune record, once for the pre-pass and the walk: 3 E2 (seg_o_lower_bound), the lanes without a bound */
+        const PruneVals pv = load_prune_vals(prec, 3.0f, live);
+        const unsigned long long dead = pv.dead, gdead = dead | __builtin_amdgcn_ballot_w64(my.G == IS_INF);
+        const float E1o = pv.E1o, E2 = pv.E2, E1gs = __builtin_fmaxf(pv.E1g, pv.E1s);
+        const bool nog = tile_lo >= vhor;
+        /* Separable block bounds of the ground / sky candidates (lemma L7, see l7_row_bounds): bit k of mask_g / mask_s
+         * = block k may hold the winning ground / sky candidate of some lane of this tile; the walk below never enters
+         * the other blocks.  Off (all ones) when the column's pruning is off or the column has more blocks than the
+         * masks have bits (then the ground / sky types only close in block 0: slower, never wrong). */
         unsigned long long mask_g = ~0ull, mask_s = ~0ull;
         L7B bl7;
         bool l7 = false;
         {
-            cprune_t pq0 = (cprune_t)prec;
-            const float pE1o = pq0->E1o;
-            const float pE1gs = __builtin_fmaxf(pq0->E1g, pq0->E1s);
-            const bool pnog = tile_lo >= vhor;
-            l7 = (pE1gs < IS_INF) && NLB <= 63;
+            l7 = (E1gs < IS_INF) && NLB <= 63;
             if (l7) {
                 bl7 = l7_lane_bounds(P, my);
                 float thr_g = IS_INF, thr_s = IS_INF;
@@ -818,7 +1030,7 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
                     thr_g = __builtin_fminf(thr_g, ubg);
                     thr_s = __builtin_fminf(thr_s, ubs);
                 }
-                if (!pnog && thr_g == thr_g) atomicMin(&s_thr[lane], l7_key(thr_g));
+                if (!nog && thr_g == thr_g) atomicMin(&s_thr[lane], l7_key(thr_g));
                 if (thr_s == thr_s) atomicMin(&s_thr[64 + lane], l7_key(thr_s));
             }
             /* lemma L8: the lower bound of every OBJECT candidate of the lower block k, per lane */
@@ -828,7 +1040,7 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
 #pragma unroll
                 for (int c = 0; c < 16; c++) {
                     const float ft = P.sw * (c < IS_N_ON ? my.Fon[c] + n1 : my.Foi[c - IS_N_ON]);
-                    bo[c] = (ft - pE1o) - ((ft + pE1o) * IS_L7_REL + IS_L7_ABS);
+                    bo[c] = (ft - E1o) - ((ft + E1o) * IS_L7_REL + IS_L7_ABS);
                 }
             }
             /* the instance classes also keep lemma L4's term of the block's TOP row: the computed
@@ -836,7 +1048,6 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
              * with the segment), so oi' >= fl(fl(ic_top - 3 E2) + f_oi') like in seg_o_lower_bound; it is
              * what makes a candidate that starts inside an instance object and ends in the sky above it
              * expensive.  ic_top: the expression of eval_segment on the staged prefixes of the top row. */
-            const float E2x3 = 3.0f * pq0->E2;
             const float t0 = P.pw * __builtin_fminf(P.first_o_below, P.first_o_above); /* block 0: the first segment, :189-199 */
             for (int k = wl; k < NLB - 1; k += nwl) {
                 float lb_n, lb_i; /* non-instance / instance classes */
@@ -872,11 +1083,10 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
                     const float meany2 = (my.MY2h - t1i.x) + (my.MY2l - t1i.y);
                     const float ic = P.iw * (meanx2 - fast_div(meanx * meanx, (float)h, rh) + meany2 -
                                              fast_div(meany * meany, (float)h, rh));
-                    lb_i = lb_i + P.sw * (ic - E2x3);
+                    lb_i = lb_i + P.sw * (ic - E2);
                 }
                 float lb_o = l7_dn(__builtin_fminf(lb_n, lb_i));
-                /* a NaN bound (inf - inf with the pruning switched off, NaN inputs) must never
-                 * close anything: -inf */
+                /* a NaN bound (inf - inf with the pruning switched off, NaN inputs) must never close anything: -inf */
                 lb_o = (lb_o == lb_o) ? lb_o : -IS_INF;
                 s_lb[k * 64 + lane] = lb_o;
             }
@@ -898,7 +1108,7 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
                     const L7Row m = l7_block_summary(P, s_sum + (size_t)k * IS_P1_SUM_F, k);
                     float lbg, ubg, lbs, ubs;
                     l7_combine(m, bl7, &lbg, &ubg, &lbs, &ubs);
-                    const bool has_g = !pnog && (m.lo_g0 < IS_INF || m.lo_g1 < IS_INF);
+                    const bool has_g = !nog && (m.lo_g0 < IS_INF || m.lo_g1 < IS_INF);
                     const bool has_s = m.lo_s < IS_INF;
                     if (has_g && (__builtin_amdgcn_ballot_w64(lbg > thr_g) | gdead) != ~0ull) mg |= 1ull << k;
                     if (has_s && (__builtin_amdgcn_ballot_w64(lbs > thr_s) | dead) != ~0ull) ms |= 1ull << k;
@@ -919,32 +1129,18 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
             }
         }
         if (w <= vB_last) {
-            cprune_t pq = (cprune_t)prec;
-            const float E1o = pq->E1o, E2 = 3.0f * pq->E2; /* see seg_o_lower_bound */
-            const float E1gs = __builtin_fmaxf(pq->E1g, pq->E1s);
-            const bool nog = tile_lo >= vhor;
             int vB = vB_last - (vB_last - w) % nw; /* the wave's largest vB */
             LutRow<NRW> next_row;
             load_lut_row<NRW>(next_row, lrsrc, lcol, vB, D, lane4r);
-            /* The bounds are sticky per type (a bound that holds at vB holds at every smaller vB:
-             * the class minima only grow, the running minima q only grow, the best cost cannot
-             * change any more).  The OBJECT bound -- minimum over the object classes only --
-             * explodes as soon as the segment leaves an object, long before the ground / sky bound
-             * of a homogeneous road or sky region does (there every split is a near-optimal
-             * candidate, nothing can be pruned).  Once the object type is closed the remaining
-             * candidates are ground / sky ones: two class differences, no instance term, no mean,
-             * no LUT access -- a fifth of the instructions of a full step; they are evaluated FOUR
-             * vB at a time so that one scalar-load latency covers four steps. */
+            /* The bounds are sticky per type (a bound that holds at vB holds at every smaller vB: the class minima only
+             * grow, the running minima q only grow, the best cost cannot change any more).  The OBJECT bound -- minimum
+             * over the object classes only -- explodes as soon as the segment leaves an object, long before the ground
+             * / sky bound of a homogeneous road or sky region does (there every split is a near-optimal candidate,
+             * nothing can be pruned).  Once the object type is closed the remaining candidates are ground / sky ones:
+             * two class differences, no instance term, no mean, no LUT access -- a fifth of the instructions of a full
+             * step; they are evaluated FOUR vB at a time so that one scalar-load latency covers four steps. */
             bool done = false, o_closed = false;
             int n_full = 0, n_gs = 0; /* evaluation counters (wave-uniform) */
-            /* lower bound of seg_o(vB', vT) for every vB' below the last fully evaluated step; before
-             * the first one: on >= 0, and X = fl(fl(ic - 3 E2) + f_oi) >= -4 E2 (1 + u) since the computed
-             * ic >= -E2 and f_oi >= 0 (`E2` here is 3 E2 of PruneRec: -2 * that = -6 E2) */
-            float lbseg = -2.0f * E2;
-#define IS_P1_NEXT_ROW() load_lut_row<NRW>(next_row, lrsrc, lcol, max(vB - nw, 0), D, lane4r)
-            /* (an invalid-disparity value takes the same step: valid-count operands and an IEEE division per step
-             * took it to 90+ VGPRs; the mean of a FAST column goes through mean_valid_fast -- a table read and the
-             * exact-division shortcut -- since round 5) */
             /* record of vB (c_*), of vB - nw (n_*): vector loads, two steps ahead; StepRec one step
              * ahead in a second set of SGPRs */
             const int l15 = lane & 15;
@@ -960,192 +1156,55 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
                 st_next = sload_step(scol + vB);
                 if (IS_P1_SREC) srec_request(S, rcol + vB);
             }
-#define IS_P1_DRAIN() if (IS_P1_SREC) srec_arrived(S) /* a request is in flight after every step */
-            /* IS_P1_SREC: the StepRec and the scalar half of the record of the next step are requested
-             * when the step has read its own for the last time (the bounds): one set of registers
-             * each instead of two, and the loads have the first half of the next step to arrive */
-#define IS_P1_REQUEST_NEXT(last_use)                                                               \
-            if (IS_P1_SREC) {                                                                      \
-                const int vn = max(vB - nw, 0);                                                    \
-                const StepRec* sn = scol + vn;                                                     \
-                asm volatile("" : "+s"(sn) : "s"(__builtin_amdgcn_readfirstlane((int)(last_use))));    \
-                st_next = sload_step_raw(sn); /* pinned (= waited for) at its use */               \
-                srec_request_next(S, rcol + vn);                                                   \
-            }
-#define IS_P1_STEP(SKY, NOG)                                                                       \
-            const LutRow<NRW> row = next_row;                                                       \
-            if (IS_P1_TOUCH_AHEAD > 0)                                                             \
-                touch_step(rcol, scol, max(vB - IS_P1_TOUCH_AHEAD * nw, 0), lane, scr);            \
-            IS_P1_NEXT_ROW();                                                                      \
-            const int h = vTc + 1 - vB;                                                            \
-            const int kb = (vB + IS_QB - 1) >> IS_QB_LOG; /* the bound block of vB (>= 1) */        \
-            const float* lbp = s_lb + kb * 64 + lane;                                              \
-            bool ok_o = false, ok_x = (NOG);                                                       \
-            {                                                                                      \
-                n_full++;                                                                          \
-                const float r0 = c_r0, r1 = c_r1;                                                  \
-                StepVals st = st_next;                                                             \
-                c_r0 = n_r0; c_r1 = n_r1;                                                          \
-                {                                                                                  \
-                    const float* q2 = (const float*)(rcol + max(vB - 2 * nw, 0));                  \
-                    if (!IS_P1_SREC) n_r0 = q2[l15];                                               \
-                    n_r1 = q2[16 + l15];                                                           \
-                }                                                                                  \
-                constexpr int WANT = (SKY) ? IS_WANT_SKY : ((NOG) ? 0 : IS_WANT_GROUND);           \
-                SegTerms t;                                                                        \
-                if (IS_P1_SREC) {                                                                  \
-                    pin_step(st);                                                                  \
-                    srec_arrived(S);                                                               \
-                    t = eval_segment_mix<HAS_INVALID, WANT>(my, S, r1, (float)h, s_rcp[h], D, P.iw, s_rcp); \
-                } else {                                                                           \
-                    t = eval_segment_dpp<HAS_INVALID, WANT>(my, r0, r1, (float)h, s_rcp[h], D, P.iw, s_rcp); \
-                }                                                                                  \
-                const float od = od_value(row, t.fni, vB);                                         \
-                if (!IS_P1_SREC) {                                                                 \
-                    /* the next StepRec: requested only now -- every LDS wait is an lgkmcnt(0)     \
-                     * wait and would wait for this scalar load too (SMEM returns out of order) */ \
-                    const StepRec* sn = scol + max(vB - nw, 0);                                    \
-                    asm volatile("" : "+s"(sn) : "v"(od));                                         \
-                    st_next = sload_step(sn);                                                      \
-                }                                                                                  \
-                pairwise_step<SKY, true, NOG, true>(P, st, vB, live, od, t, b);                    \
-                const float lb_o = min_raw((st.q_o - E1o) + P.sw * seg_o_lower_bound(t, E2), lbp[0]); \
-                ok_o = (__builtin_amdgcn_ballot_w64(lb_o > b.o) | dead) == ~0ull;                  \
-                if (SKY) {                                                                         \
-                    const float lb_s = (st.q_gs - E1gs) + P.sw * t.seg_s;                          \
-                    ok_x = (__builtin_amdgcn_ballot_w64(lb_s > b.s) | dead) == ~0ull &&            \
-                           IS_L7_NONE_BELOW(mask_s, kb);                                           \
-                } else if (!(NOG)) {                                                               \
-                    const float lb_g = (st.q_gs - E1gs) + P.sw * t.seg_g;                          \
-                    ok_x = (__builtin_amdgcn_ballot_w64(lb_g > b.g) | gdead) == ~0ull &&           \
-                           IS_L7_NONE_BELOW(mask_g, kb);                                           \
-                }                                                                                  \
-            }                                                                                      \
-            if (!(NOG)) ok_x = ok_x || IS_L7_NONE_LE((SKY) ? mask_s : mask_g, kb)
-            /* ground / sky candidates of up to four vB (vB, vB - nw, ...) >= lo; closes `x_closed`
-             * when the bound of the last one holds; leaves vB at the next unvisited value */
-#define IS_P1_GS4(SKY, lo, x_dead, x_closed)                                                       \
-            {                                                                                      \
-                const int n_here = min(4, (vB - (lo)) / nw + 1);                                   \
-                n_gs += n_here;                                                                    \
-                if (IS_P1_TOUCH_AHEAD > 0) touch_round(rcol, scol, vB - 4 * nw, nw, (lo), lane, scr); \
-                float c_f[4], c_cost[4];                                                           \
-                int c_idx[4];                                                                      \
-                float c_q[4];                                                                      \
-                _Pragma("unroll") for (int j = 0; j < 4; j++) {                                    \
-                    const int vj = max(vB - j * nw, (lo)); /* clamped: the loads are unconditional */ \
-                    crec_t rq = (crec_t)(rcol + vj);                                               \
-                    cstep_t sq = (cstep_t)(scol + vj);                                             \
-                    const float nic = P.iw * (float)(my.Fnic - rq->Fnic);                          \
-                    c_f[j] = (SKY) ? (my.Fsky - rq->Fsky)                                          \
-                                   : __builtin_fminf(my.Fg0 - rq->Fg0, my.Fg1 - rq->Fg1);         \
-                    const float data = (SKY) ? (my.K - rq->K) : (my.G - rq->G);                    \
-                    c_f[j] += nic; /* f + nic: also monotone (lemma L2), and part of the cost */   \
-                    c_cost[j] = P.dw * data + sq->pwmp + P.sw * c_f[j];                            \
-                    c_idx[j] = sq->idx_gs;                                                         \
-                    c_q[j] = sq->q_gs;                                                             \
-                }                                                                                  \
-                float f_last = c_f[0], q_last = c_q[0];                                            \
-                _Pragma("unroll") for (int j = 0; j < 4; j++) {                                    \
-                    if (j < n_here) {                                                              \
-                        if (SKY) take_if_le(b.s, b.is, c_cost[j], c_idx[j]);                       \
-                        else take_if_le(b.g, b.ig, c_cost[j], c_idx[j]);                           \
-                        f_last = c_f[j]; q_last = c_q[j];                                          \
-                    }                                                                              \
-                }                                                                                  \
-                const int vb_l = vB - (n_here - 1) * nw; /* the lowest vB just evaluated */      \
-                const float lb_x = (q_last - E1gs) + P.sw * f_last;                                \
-                if ((__builtin_amdgcn_ballot_w64(lb_x > ((SKY) ? b.s : b.g)) | (x_dead)) == ~0ull && \
-                    IS_L7_NONE_BELOW((SKY) ? mask_s : mask_g, (vb_l + IS_QB - 1) >> IS_QB_LOG))    \
-                    x_closed = true;                                                               \
-                vB -= n_here * nw;                                                                 \
-            }
-            /* lemma L7: no block at or below block k holds a possible winner */
-#define IS_L7_NONE_LE(mask, k) (((mask) & ((2ull << min((k), 62)) - 1ull)) == 0ull)
-            /* ... strictly below block k */
-#define IS_L7_NONE_BELOW(mask, k) (((mask) & ((1ull << min((k), 63)) - 1ull)) == 0ull)
-            /* in front of a ground / sky round: close the type when no surviving block is left at or
-             * below the block of vB; jump over the blocks that cannot hold the winner to this wave's
-             * largest vB in the next surviving block (block 0 = the first segment, vB = 0) */
-#define IS_P1_L7_SKIP(mask, x_closed)                                                              \
-            {                                                                                      \
-                const int kb = min((vB + IS_QB - 1) >> IS_QB_LOG, 62);                             \
-                const unsigned long long at_or_below = (mask) & ((2ull << kb) - 1ull);             \
-                if (at_or_below == 0ull) { x_closed = true; break; }                               \
-                if (!(((mask) >> kb) & 1ull)) {                                                    \
-                    const int top = (63 - __builtin_clzll(at_or_below)) << IS_QB_LOG;              \
-                    int dd = (top - w) % nw;                                                       \
-                    dd = dd < 0 ? dd + nw : dd;                                                    \
-                    vB = top - dd;                                                                 \
-                    continue;                                                                      \
-                }                                                                                  \
-            }
             const int sky_lo = max(vhor + 1, 1);
             for (; vB >= sky_lo; vB -= nw) { /* sky range: vB - 1 >= vhor */
-                IS_P1_STEP(true, false);
-                IS_P1_REQUEST_NEXT(ok_x);
+                IS_P1_STEP(true, false, HAS_INVALID, NRW, P, my, b, vB, nw, lane, l15, vTc, live, D, rcol, scol, lcol,
+                           lrsrc, lane4r, scr, s_rcp, s_lb, od_value, next_row, c_r0, c_r1, n_r0, n_r1, st_next, S, n_full,
+                           E1o, E2, E1gs, dead, gdead, mask_g, mask_s, ok_o, ok_x);
                 if (ok_o && ok_x) { done = true; break; }
                 if (ok_o) { o_closed = true; vB -= nw; break; }
             }
-            IS_P1_DRAIN();
+            if (IS_P1_SREC) srec_arrived(S); /* (a request is in flight after every step) */
             if (!done && o_closed) {
                 /* a tile with a sky range lies above the horizon: no ground candidates, and the
                  * first segment's object candidate is closed too -- only sky candidates are left */
                 bool s_closed = false;
                 while (vB >= sky_lo && !s_closed) {
-                    IS_P1_L7_SKIP(mask_s, s_closed)
-                    IS_P1_GS4(true, sky_lo, dead, s_closed)
+                    IS_P1_L7_SKIP(mask_s, s_closed, vB, w, nw)
+                    IS_P1_GS4(true, sky_lo, dead, s_closed, P, my, b, vB, nw, lane, rcol, scol, scr, n_gs, E1gs, mask_g, mask_s)
                 }
                 done = true;
             }
             if (!done && nog) {
                 for (; vB >= 1; vB -= nw) { /* ground range, ground candidates are +inf */
-                    IS_P1_STEP(false, true);
-                    IS_P1_REQUEST_NEXT(ok_o);
+                    IS_P1_STEP(false, true, HAS_INVALID, NRW, P, my, b, vB, nw, lane, l15, vTc, live, D, rcol, scol, lcol,
+                           lrsrc, lane4r, scr, s_rcp, s_lb, od_value, next_row, c_r0, c_r1, n_r0, n_r1, st_next, S, n_full,
+                           E1o, E2, E1gs, dead, gdead, mask_g, mask_s, ok_o, ok_x);
                     if (ok_o) { done = true; break; }
                 }
-                IS_P1_DRAIN();
+                if (IS_P1_SREC) srec_arrived(S);
             } else if (!done) {
                 for (; vB >= 1; vB -= nw) { /* ground range: vB - 1 < vhor */
-                    IS_P1_STEP(false, false);
-                    IS_P1_REQUEST_NEXT(ok_x);
+                    IS_P1_STEP(false, false, HAS_INVALID, NRW, P, my, b, vB, nw, lane, l15, vTc, live, D, rcol, scol, lcol,
+                           lrsrc, lane4r, scr, s_rcp, s_lb, od_value, next_row, c_r0, c_r1, n_r0, n_r1, st_next, S, n_full,
+                           E1o, E2, E1gs, dead, gdead, mask_g, mask_s, ok_o, ok_x);
                     if (ok_o && ok_x) { done = true; break; }
                     if (ok_o) { o_closed = true; vB -= nw; break; }
                 }
-                IS_P1_DRAIN();
+                if (IS_P1_SREC) srec_arrived(S);
                 if (!done && o_closed) {
                     bool g_closed = false;
                     while (vB >= 1 && !g_closed) {
-                        IS_P1_L7_SKIP(mask_g, g_closed)
-                        IS_P1_GS4(false, 1, gdead, g_closed)
+                        IS_P1_L7_SKIP(mask_g, g_closed, vB, w, nw)
+                        IS_P1_GS4(false, 1, gdead, g_closed, P, my, b, vB, nw, lane, rcol, scol, scr, n_gs, E1gs, mask_g, mask_s)
                     }
                     if (g_closed) done = true; /* else vB <= 0: the first segment is still to come */
                 }
             }
-#undef IS_P1_STEP
-#undef IS_P1_NEXT_ROW
-#undef IS_P1_GS4
-#undef IS_P1_L7_SKIP
-#undef IS_L7_NONE_LE
-#undef IS_L7_NONE_BELOW
-#undef IS_P1_DRAIN
-#undef IS_P1_REQUEST_NEXT
-            if (!done && vB == 0) { /* first segment, :481-594 */
+            if (!done && vB == 0) {
                 n_full++;
-                const RowRec rb = sload_rec(rcol);
-                const int h = vTc + 1;
-                const SegTerms t = eval_segment<true, HAS_INVALID>(my, rb, (float)h, s_rcp[h], D, P.iw, s_rcp);
-                const float od = vt_value(t.fni) - lcol[(unsigned)t.fni];
-                const bool below = vT <= vhor;
-                const float cost_g = P.dw * t.gd + P.pw * P.first_g + P.sw * t.seg_g;
-                const bool ug = live && below && (cost_g <= b.g);
-                b.g = ug ? cost_g : b.g;
-                b.ig = ug ? IS_GROUND : b.ig;
-                const float prior = below ? P.first_o_below : P.first_o_above;
-                const float cost = P.dw * od + P.pw * prior + P.sw * t.seg_o;
-                const bool uo = live && (cost <= b.o);
-                b.o = uo ? cost : b.o;
-                b.io = uo ? IS_OBJECT : b.io;
+                IS_P1_FIRST_SEGMENT(true, HAS_INVALID, <=, P, my, rcol, lcol, vT, vTc, live, vhor, D, s_rcp[vTc + 1], s_rcp,
+                                    vt_value, b.g, b.ig, b.o, b.io)
             }
             if (counters != nullptr && lane == 0) {
                 atomicAdd(counters + IS_CNT_P1_FULL, (unsigned long long)n_full);
@@ -1158,64 +1217,16 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
             }
         }
     } else {
-        int vB = w;
-        LutRow<NRW> next_row;
-        if (vB <= vB_last) load_lut_row<NRW>(next_row, lrsrc, lcol, vB == 0 ? min(nw, H) : vB, D, lane4r);
-        if (vB == 0) { /* first segment, :481-594 */
-            const RowRec rb = sload_rec(rcol);
-            const int h = vTc + 1;
-            const SegTerms t = eval_segment<FAST, HAS_INVALID>(my, rb, (float)h, s_rcp[h], D, P.iw, s_rcp);
-            const float od = vt_value(t.fni) - lcol[(unsigned)t.fni];
-            const bool below = vT <= vhor;
-            const float cost_g = P.dw * t.gd + P.pw * P.first_g + P.sw * t.seg_g;
-            const bool ug = live && below && (cost_g < b.g);
-            b.g = ug ? cost_g : b.g;
-            b.ig = ug ? IS_GROUND : b.ig;
-            const float prior = below ? P.first_o_below : P.first_o_above;
-            const float cost = P.dw * od + P.pw * prior + P.sw * t.seg_o;
-            b.o = (live && cost < b.o) ? cost : b.o;
-            vB += nw;
-        }
-        if (tile_lo >= vhor) {
-            for (; vB <= min(vhor, vB_last); vB += nw) { /* ground range, ground candidate = +inf */
-                const RowRec rb = sload_rec(rcol + vB);
-                const StepVals st = sload_step(scol + vB);
-                const LutRow<NRW> row = next_row;
-                load_lut_row<NRW>(next_row, lrsrc, lcol, min(vB + nw, H), D, lane4r);
-                const int h = vTc + 1 - vB;
-                const SegTerms t = eval_segment<FAST, HAS_INVALID>(my, rb, (float)h, s_rcp[h], D, P.iw, s_rcp);
-                const float od = od_value(row, t.fni, vB);
-                pairwise_step<false, true, true>(P, st, vB, live, od, t, b);
-            }
-        }
-        for (; vB <= min(vhor, vB_last); vB += nw) { /* ground range: vB-1 < vhor */
-            const RowRec rb = sload_rec(rcol + vB);
-            const StepVals st = sload_step(scol + vB);
-            const LutRow<NRW> row = next_row;
-            load_lut_row<NRW>(next_row, lrsrc, lcol, min(vB + nw, H), D, lane4r);
-            const int h = vTc + 1 - vB;
-            const SegTerms t = eval_segment<FAST, HAS_INVALID>(my, rb, (float)h, s_rcp[h], D, P.iw, s_rcp);
-            const float od = od_value(row, t.fni, vB);
-            pairwise_step<false, true>(P, st, vB, live, od, t, b);
-        }
-        for (; vB <= vB_last; vB += nw) { /* sky range */
-            const RowRec rb = sload_rec(rcol + vB);
-            const StepVals st = sload_step(scol + vB);
-            const LutRow<NRW> row = next_row;
-            load_lut_row<NRW>(next_row, lrsrc, lcol, min(vB + nw, H), D, lane4r);
-            const int h = vTc + 1 - vB;
-            const SegTerms t = eval_segment<FAST, HAS_INVALID>(my, rb, (float)h, s_rcp[h], D, P.iw, s_rcp);
-            const float od = od_value(row, t.fni, vB);
-            pairwise_step<true, true>(P, st, vB, live, od, t, b);
-        }
+        p1_generic_walk<HAS_INVALID, NRW>(P, my, b, w, nw, vT, vTc, live, vhor, tile_lo, vB_last, H, D, rcol, scol, lcol, lrsrc,
+                                          lane4r, s_rcp, od_value, vt_value);
     }
     /* merge the waves: min cost, ties -> smallest vB (a finite cost always has a real index).
      * Every L2-warming DMA must have landed before this wave can end: its LDS target would
      * otherwise be written after the workgroup's LDS has been handed to another one. */
     wait_vmcnt<0>();
     __syncthreads();
-    float* m_cost = (float*)smem;               /* [nwl][3][64] (aliases the tile) */
-    int* m_idx = (int*)(m_cost + nwl * 3 * 64); /* [nwl][3][64] */
+    float* m_cost = lds;                    /* [nwl][3][64] (aliases the tile) */
+    int* m_idx = (int*)(lds + L.merge / 2); /* [nwl][3][64] */
     m_cost[(wl * 3 + 0) * 64 + lane] = b.g; m_idx[(wl * 3 + 0) * 64 + lane] = b.ig;
     m_cost[(wl * 3 + 1) * 64 + lane] = b.o; m_idx[(wl * 3 + 1) * 64 + lane] = b.io;
     m_cost[(wl * 3 + 2) * 64 + lane] = b.s; m_idx[(wl * 3 + 2) * 64 + lane] = b.is;
@@ -1250,26 +1261,22 @@ __device__ __forceinline__ void pw_phase1_body(const DevParams& P, char* smem, i
 #endif
 template <bool HAS_INVALID, int NR, bool WIN = false>
 __global__ __launch_bounds__(IS_UNARY_WAVES * 64, HAS_INVALID ? ISP1_OCC_INV : (WIN ? ISP1_OCC_WIN : ISP1_OCC)) void k_pw_phase1(
-    const DevParams P, int col_base, int ncols, int tile, int nsplit,
-    const RowRec* __restrict__ recs, const float* __restrict__ lutT,
-    const StepRec* __restrict__ steps, const float* __restrict__ rcp,
-    const int* __restrict__ vhor_arr, const int* __restrict__ col_flags,
-    const PruneRec* __restrict__ prune, float* __restrict__ part_cost, int* __restrict__ part_idx,
-    unsigned long long* __restrict__ counters, const float* __restrict__ joined,
-    const float* __restrict__ cost_T, const float* __restrict__ blksum) {
+    const DevParams P, int col_base, int ncols, int tile, int nsplit, const RowRec* __restrict__ recs,
+    const float* __restrict__ lutT, const StepRec* __restrict__ steps, const float* __restrict__ rcp,
+    const int* __restrict__ vhor_arr, const int* __restrict__ col_flags, const PruneRec* __restrict__ prune,
+    float* __restrict__ part_cost, int* __restrict__ part_idx, unsigned long long* __restrict__ counters,
+    const float* __restrict__ blksum) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int colg = col_base + (int)(blockIdx.x / (unsigned)nsplit);
     const int split = __builtin_amdgcn_readfirstlane((int)(blockIdx.x % (unsigned)nsplit));
     if (colg >= ncols) return;
     const int vhor = __builtin_amdgcn_readfirstlane(vhor_arr[colg / P.C]);
     if (__builtin_amdgcn_readfirstlane(col_flags[colg]) == 0)
-        pw_phase1_body<true, HAS_INVALID, NR, WIN>(P, smem, colg, tile, recs, lutT, steps, rcp, vhor, split,
-                                              nsplit, prune + colg, part_cost, part_idx, counters, joined, cost_T,
-                                              blksum);
+        pw_phase1_body<true, HAS_INVALID, NR, WIN>(P, smem, colg, tile, recs, lutT, steps, rcp, vhor, split, nsplit,
+                                                   prune + colg, part_cost, part_idx, counters, blksum);
     else
-        pw_phase1_body<false, HAS_INVALID, NR, WIN>(P, smem, colg, tile, recs, lutT, steps, rcp, vhor, split,
-                                               nsplit, prune + colg, part_cost, part_idx, counters, joined, cost_T,
-                                               blksum);
+        pw_phase1_body<false, HAS_INVALID, NR, WIN>(P, smem, colg, tile, recs, lutT, steps, rcp, vhor, split, nsplit,
+                                                    prune + colg, part_cost, part_idx, counters, blksum);
 }
 
 /* ---- phase 2: the fn window --------------------------------------------------------------
@@ -2169,16 +2176,8 @@ __global__ __launch_bounds__(ISP2S_WAVES * 64, 5) void k_pw_phase2s(
 
 extern "C" {
 
-static size_t p1_lds_bytes(const DevParams* P, int nwaves, bool windowed) {
-    const size_t rcp = sizeof(float) * (((size_t)P->H + 1 + 3) & ~(size_t)3);
-    const size_t tile = sizeof(float) * (size_t)IS_TILE * ((windowed ? IS_P1_WIN : P->D) + 1);
-    const size_t merge = (size_t)nwaves * 3 * 64 * 8; /* aliases the tile after the loop */
-    /* + the object block bounds of the pre-pass: [ntiles * IS_QPT + 1][64] (a launch of tile t uses
-     * t * IS_QPT + 1 entries) */
-    return (tile > merge ? tile : merge) + rcp + sizeof(float) * 8 * (size_t)nwaves +
-           sizeof(float) * IS_P1_L7_WORDS + sizeof(float) * IS_P1_BLK_WORDS * ((size_t)P->ntiles * IS_QPT + 1) + 32;
-}
-size_t isk_pairwise_lds_bytes(const DevParams* P, int nwaves) { return p1_lds_bytes(P, nwaves, false); }
+/* (the last tile: the most bound blocks; the windowed instantiations need less) */
+size_t isk_pairwise_lds_bytes(const DevParams* P, int nwaves) { return p1_lds_bytes(P, nwaves, P->ntiles, false); }
 size_t isk_phase2_lds_bytes(const DevParams* P) {
     return sizeof(double) * 2 * IS_LOG_TABLE_SIZE +
            sizeof(float) * (P->D + (IS_TILE + 1) + (size_t)ISP2_ROWS * ISP2_WS) + 16;
@@ -2222,7 +2221,7 @@ hipError_t isk_launch_dp_pairwise(const DevParams* P, const CallPlan* plan, cons
 #define IS_LAUNCH_P1(KERNEL)                                                                                        \
     hipLaunchKernelGGL(KERNEL, dim3((c1 - c0) * nsplit), dim3(nw_t * 64), lds1_t, st, *P, c0, c1, tile, nsplit,     \
                        b->recs, b->lutT, b->steps, b->rcp, b->vhor, b->col_flags, b->prune, b->part_cost,           \
-                       b->part_idx, b->counters, b->joined, b->cost_T, b->blksum)
+                       b->part_idx, b->counters, b->blksum)
 #define IS_LAUNCH_TILE(INV)                                                                                         \
     do {                                                                                                            \
         if (win_t)                                                                                                  \
@@ -2250,11 +2249,9 @@ hipError_t isk_launch_dp_pairwise(const DevParams* P, const CallPlan* plan, cons
             if ((e = hipStreamWaitEvent(aux[g - 1], ev_fork, 0)) != hipSuccess) return e;
     }
     for (int tile = 0; tile < P->ntiles; tile++) {
-        /* (the block bounds of tile t need t + 1 of the ntiles + 1 entries lds1 has room for) */
         const bool win_t = tile < plan->win_tiles;
         const int nw_t = win_t ? nwaves_win : nwaves;
-        const size_t lds1_t = p1_lds_bytes(P, nw_t, win_t) -
-                              sizeof(float) * IS_P1_BLK_WORDS * (size_t)IS_QPT * (size_t)(P->ntiles - tile);
+        const size_t lds1_t = p1_lds_bytes(P, nw_t, tile, win_t);
         for (int g = 0; g < groups; g++) {
             const int c0 = (int)((long long)ncols * g / groups) & ~1; /* (even: column pairs) */
             const int c1 = g + 1 == groups ? ncols : ((int)((long long)ncols * (g + 1) / groups) & ~1);
