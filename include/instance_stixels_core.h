@@ -1231,6 +1231,81 @@ int is_conv3x3_pack_weights(const float* d_weight, int channels_out, int channel
  * overlap and a non-zero reserved field. */
 int is_conv3x3_bn_relu(const is_conv3x3_args* args, void* stream);
 
+/* ---- f18: the backbone's residual blocks, convolution + BatchNorm (+ residual) (+ ReLU) of a batch (is_k_conv3x3.hip) -
+ * layer5 and layer6 of the DRN behind every shipped config (drn_d_22; tools/CNN_training/models/drn.py:168-172): each
+ * two BasicBlocks (drn.py:54-87) built by _make_layer(..., new_level = False) (drn.py:199-221), 128 -> 256 -> 512
+ * channels, dilations (2, 2) and (4, 4), stride 1, at 1/8 resolution in the NCHW half layout f17 reads.  A block is
+ *     out = relu(bn1(conv1(x)));  out = bn2(conv2(out));  out += downsample(x) or x;  out = relu(out)
+ * with downsample = Conv2d(1x1, bias = False) + BatchNorm2d in the first block of a layer.  f17's entry point cannot
+ * express the residual operand between the BatchNorm and the ReLU, nor the 1x1 convolution; is_conv3x3_args cannot grow.
+ * This entry point is f17's with both, so that layer5 -> layer6 -> layer7 -> layer8 -> head is thirteen launches of this
+ * library with nothing in between; is_conv3x3_bn_relu is this call with kernel = 3 and no residual, the same launch
+ * and the same bytes, and is_conv_pack_weights(kernel = 3) writes the bytes of is_conv3x3_pack_weights.
+ *
+ *   Operands.    The half values: the features and the residual as given, the weights as is_conv_pack_weights rounded
+ *                them (round to nearest even).  A product of two of them is exact in fp32, and so is a widened residual.
+ *   Summation.   kernel = 3: f17's, over the 9 taps and all channels_in.  kernel = 1: a[n][co][y][x] = sum over all
+ *                channels_in of w[co][ci] * x[n][ci][y][x].  Accumulated in fp32 MFMA accumulators by
+ *                v_mfma_f32_32x32x16_f16 / _bf16, one accumulator chain per output element: no split over workgroups,
+ *                no atomics, no partial sums combined afterwards.
+ *   Order.       The MFMA instructions of an element follow each other in increasing 16-channel chunk and, inside a
+ *                chunk, in increasing tap 3 ky + kx: fixed by the shape alone.  The summation INSIDE one instruction
+ *                (16 products) is the hardware's and is not specified: as f17, this entry point is pinned by a derived
+ *                error bound plus inputs whose arithmetic is exact in every order, not by a C loop.
+ *   Epilogue.    In fp32, three steps:
+ *                    v = fmaf(scale[co], a, shift[co])
+ *                    v = v + (float)residual[n][co][y][x]      when d_residual is given (the widening is exact)
+ *                    v = max(v, 0)                             when relu is set
+ *                then the store: that value with out_dtype = IS_HEAD_F32, its round-to-nearest-even conversion with a
+ *                half out_dtype.  With a residual these are two fp32 roundings (the fmaf, the addition) before the
+ *                single final rounding to the half dtype.  The reference adds the residual on HALF tensors under amp
+ *                (bn2's half output, `out += residual`, drn.py:84: one more rounding to half in between); this
+ *                contract adds it in fp32 before the single final rounding, and says so on purpose.
+ *   Determinism. The same bytes on every run; a frame's result does not depend on its position in the batch or on
+ *                n_images.
+ *   Non-finite values give unspecified values, never an access outside the buffers; no address depends on a value.
+ *
+ * Weights: d_weight is conv.weight, [channels_out][channels_in][kernel][kernel] fp32; is_conv_pack_weights rounds each
+ * to the half dtype (round to nearest even) into is_conv_packed_bytes(...) bytes at a 16-byte aligned d_packed, in an
+ * opaque layout that holds exactly those values.
+ *
+ * Zero-initialise, then set the fields.  All arrays on the current device.  Fields as in is_conv3x3_args, and
+ *   kernel              3 or 1 (the convolution is kernel x kernel, padding = dilation * (kernel - 1) / 2, stride 1)
+ *   dilation            kernel 3: in [1, 8];  kernel 1: must be 1
+ *   d_packed            from is_conv_pack_weights with the same channels, kernel and dtype, 16-byte aligned
+ *   d_residual          NULL, or [n_images][channels_out][rows8][cols8] of `dtype` (the OUTPUT's shape), aligned to its
+ *                       element.  Exactly its n_images * channels_out * rows8 * cols8 elements are read.  It may be
+ *                       the features themselves (channels_in = channels_out: a block without downsample); its bytes
+ *                       must not overlap the output's
+ *   d_out               its bytes must overlap neither the features' nor the residual's */
+typedef struct is_conv_bn_args {
+    const void* d_features;
+    int dtype; /* IS_HEAD_F16 | IS_HEAD_BF16 */
+    int n_images, channels_in, channels_out, rows8, cols8;
+    int kernel;   /* 3 or 1 */
+    int dilation; /* kernel 3: [1, 8];  kernel 1: must be 1 */
+    const void* d_packed;
+    const float* d_scale;
+    const float* d_shift;
+    const void* d_residual; /* NULL, or [n][channels_out][rows8][cols8] of `dtype` */
+    int relu;
+    void* d_out;
+    int out_dtype;
+    int reserved[4]; /* 0 */
+} is_conv_bn_args;
+
+/* Bytes of d_packed: channels_out * channels_in * kernel * kernel * 2 (0 for arguments outside the ranges). */
+size_t is_conv_packed_bytes(int channels_out, int channels_in, int kernel, int dtype);
+/* One launch on `stream`, asynchronous.  IS_EINVAL before the device is touched for null pointers, channels, a kernel
+ * or a dtype outside the ranges above and misaligned pointers. */
+int is_conv_pack_weights(const float* d_weight, int channels_out, int channels_in, int kernel, int dtype,
+                         void* d_packed, void* stream);
+/* One launch on `stream`, asynchronous and stream-ordered; no allocation, copy or synchronisation.  IS_EINVAL, with
+ * the reason in is_last_error() and before the device is touched, for everything is_conv3x3_bn_relu refuses, a kernel
+ * outside {1, 3}, dilation != 1 with kernel 1, a residual off its element alignment and residual bytes that overlap
+ * the output's. */
+int is_conv_bn(const is_conv_bn_args* args, void* stream);
+
 /* ---- f9: per-instance objects and their contours (is_k_objects.hip) ------------------------------------------------
  * What the reference's consumers reduce on the host from the per-stixel output: the top-down view
  * (tools/visualization/clustering_visualization.py:563-792: per instance and column the closest stixel, connected

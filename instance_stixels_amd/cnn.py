@@ -3,7 +3,11 @@ models/drn.py:181-185, each an nn.Sequential(Conv2d 3x3 dilated without bias, Ba
 _make_conv_layers, drn.py:223-233) and the head `seg` behind them, as three launches of the C ABI with nothing in
 between: core.conv3x3_bn_relu twice, core.segmentation_head once.  Inference only: BatchNorm is folded from its running
 statistics, nothing here is differentiable.  torch owns the memory and the stream; every value comes from the library's
-kernels (there is no fall-back to torch's convolution)."""
+kernels (there is no fall-back to torch's convolution).
+
+f18 puts the residual blocks of layer5 and layer6 in front of it (BasicBlock, drn.py:54-87, built by _make_layer,
+drn.py:199-221, as drn.py:168-172): ResidualBlock is two launches of core.conv_bn, three with a downsample, and
+DrnDilated is layer5 -> layer6 -> DrnTail, the output of layer4 in and the DP's input out."""
 import torch
 
 from . import core
@@ -58,6 +62,87 @@ def _conv_bn_relu_of(layer, name):
             or not isinstance(mods[2], torch.nn.ReLU):
         raise core.CoreError(f"{name} must be nn.Sequential(Conv2d, BatchNorm2d, ReLU), as _make_conv_layers builds it")
     return mods[0], mods[1]
+
+
+def _dilated3x3(conv, name):
+    d = conv.dilation[0]
+    if not isinstance(conv, torch.nn.Conv2d) or tuple(conv.kernel_size) != (3, 3) or tuple(conv.dilation) != (d, d) or \
+            tuple(conv.padding) != (d, d) or conv.groups != 1 or conv.bias is not None or \
+            getattr(conv, "padding_mode", "zeros") != "zeros":
+        raise core.CoreError(f"{name} must be Conv2d(kernel_size=3, padding=dilation, groups=1, bias=False)")
+    if tuple(conv.stride) != (1, 1):
+        raise core.CoreError(f"{name} has stride {tuple(conv.stride)}: only the stride-1 blocks (layer5 on) are covered")
+    return int(d)
+
+
+class ResidualBlock:
+    """One BasicBlock of the reference (drn.py:54-87) in eval mode: relu(bn1(conv1(x))), then bn2(conv2(.)) with the
+    residual -- downsample(x) or x itself -- added in fp32 between the BatchNorm and the ReLU (is_conv_bn's epilogue),
+    as 2 launches, or 3 with a downsample.  `block` is any object with the attributes conv1, bn1, conv2, bn2,
+    downsample and residual; residual=False (arch C's layer7 / layer8) gives two plain conv + BN + ReLU launches.
+    Everything is checked and folded before the weights are packed on `device`."""
+
+    def __init__(self, block, dtype=torch.bfloat16, device=0):
+        if hasattr(block, "conv3"):
+            raise core.CoreError("a block with conv3 is a Bottleneck: only BasicBlock is covered")
+        self.dilations = (_dilated3x3(block.conv1, "conv1"), _dilated3x3(block.conv2, "conv2"))
+        c_in, c_mid, c_out = block.conv1.in_channels, block.conv1.out_channels, block.conv2.out_channels
+        if block.conv2.in_channels != c_mid or block.bn1.num_features != c_mid or block.bn2.num_features != c_out:
+            raise core.CoreError("conv1, bn1, conv2 and bn2 disagree on their channels")
+        self.residual = bool(block.residual)
+        down = block.downsample if self.residual else None      # (the reference computes and drops it otherwise)
+        folds = [fold_batchnorm(block.bn1), fold_batchnorm(block.bn2)]
+        convs = [block.conv1, block.conv2]
+        if down is not None:
+            mods = list(down) if isinstance(down, torch.nn.Sequential) else []
+            if len(mods) != 2 or not isinstance(mods[0], torch.nn.Conv2d) or not isinstance(mods[1], torch.nn.BatchNorm2d) \
+                    or tuple(mods[0].kernel_size) != (1, 1) or mods[0].bias is not None or mods[0].groups != 1 \
+                    or tuple(mods[0].padding) != (0, 0) or mods[0].in_channels != c_in or mods[0].out_channels != c_out \
+                    or mods[1].num_features != c_out:
+                raise core.CoreError("downsample must be nn.Sequential(Conv2d(kernel_size=1, bias=False), BatchNorm2d) "
+                                     "from the block's input to its output channels")
+            if tuple(mods[0].stride) != (1, 1):
+                raise core.CoreError(f"downsample has stride {tuple(mods[0].stride)}: only the stride-1 blocks are covered")
+            folds.append(fold_batchnorm(mods[1]))
+            convs.append(mods[0])
+        elif self.residual and c_in != c_out:
+            raise core.CoreError(f"residual=True without a downsample needs equal channels, not {c_in} -> {c_out}")
+        dev = torch.device("cuda", device) if not isinstance(device, torch.device) else device
+        self.dtype, self.has_downsample = dtype, down is not None
+        self.packed = [core.conv_pack_weights(c.weight.detach().to(dev), dtype) for c in convs]
+        self.folds = [(sc.to(dev), sh.to(dev)) for sc, sh in folds]
+
+    def __call__(self, x, out_dtype=None):
+        """x: [n][channels_in][rows8][cols8] of the block's dtype on its device."""
+        y = core.conv_bn(x, self.packed[0], *self.folds[0], 3, self.dilations[0])
+        res = None
+        if self.residual:
+            res = core.conv_bn(x, self.packed[2], *self.folds[2], 1, relu=False) if self.has_downsample else x
+        return core.conv_bn(y, self.packed[1], *self.folds[1], 3, self.dilations[1], residual=res, out_dtype=out_dtype)
+
+
+class DrnDilated:
+    """layer5 -> layer6 -> layer7 -> layer8 -> seg -> (-log_softmax, FlipAndPad): the output of the reference's layer4
+    in, the DP's input out.  layer5, layer6: sequences of BasicBlocks in eval mode (ResidualBlock); the rest is
+    DrnTail's.  The features between the launches stay in `dtype`."""
+
+    def __init__(self, layer5, layer6, layer7, layer8, seg, n_classes, rows_power2_segmentation, clamp=None,
+                 dtype=torch.bfloat16, device=0):
+        self.blocks = [ResidualBlock(b, dtype=dtype, device=device) for layer in (layer5, layer6) for b in layer]
+        self.tail = DrnTail(layer7, layer8, seg, n_classes, rows_power2_segmentation, clamp=clamp, dtype=dtype,
+                            device=device)
+        self.dtype = dtype
+
+    @torch.no_grad()
+    def forward(self, features, want_cnn_out=False):
+        """features: layer4's output [n][C][rows8][cols8] on the device; any other floating dtype than `dtype` is
+        converted first.  Returns what DrnTail.forward returns."""
+        x = features if features.dtype == self.dtype else features.to(self.dtype)
+        for block in self.blocks:
+            x = block(x)
+        return self.tail.forward(x, want_cnn_out=want_cnn_out)
+
+    __call__ = forward
 
 
 class DrnTail:

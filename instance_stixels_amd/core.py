@@ -47,6 +47,7 @@ EXPORTS = [
     "is_cnn_label_maps",
     "is_semantic_nll_up_scratch_bytes", "is_semantic_nll_up",
     "is_conv3x3_packed_bytes", "is_conv3x3_pack_weights", "is_conv3x3_bn_relu",
+    "is_conv_packed_bytes", "is_conv_pack_weights", "is_conv_bn",
 ]
 RENDER_MAX_LABELS = 64    # IS_RENDER_MAX_LABELS
 RENDER_MAX_CLASSES = 256  # IS_RENDER_MAX_CLASSES
@@ -249,6 +250,15 @@ class Conv3x3Args(ctypes.Structure):
                 ("relu", ci), ("d_out", vp), ("out_dtype", ci), ("reserved", ci * 4)]
 
 
+class ConvBnArgs(ctypes.Structure):
+    """is_conv_bn_args: zero-initialised by ctypes; device pointers as ints."""
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    _fields_ = [("d_features", vp), ("dtype", ci), ("n_images", ci), ("channels_in", ci), ("channels_out", ci),
+                ("rows8", ci), ("cols8", ci), ("kernel", ci), ("dilation", ci), ("d_packed", vp), ("d_scale", vp),
+                ("d_shift", vp), ("d_residual", vp), ("relu", ci), ("d_out", vp), ("out_dtype", ci),
+                ("reserved", ci * 4)]
+
+
 class RoadParams(ctypes.Structure):
     """is_road_params: one frame's road, the layout of Stixels::RoadParameters (16 bytes)"""
     _fields_ = [("vhor", ctypes.c_int), ("tilt", ctypes.c_float), ("height", ctypes.c_float),
@@ -352,6 +362,10 @@ def lib():
         L.is_conv3x3_packed_bytes.restype = ctypes.c_size_t
         L.is_conv3x3_pack_weights.argtypes = [vp, ci, ci, ci, vp, vp]
         L.is_conv3x3_bn_relu.argtypes = [ctypes.POINTER(Conv3x3Args), vp]
+        L.is_conv_packed_bytes.argtypes = [ci, ci, ci, ci]
+        L.is_conv_packed_bytes.restype = ctypes.c_size_t
+        L.is_conv_pack_weights.argtypes = [vp, ci, ci, ci, ci, vp, vp]
+        L.is_conv_bn.argtypes = [ctypes.POINTER(ConvBnArgs), vp]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
         L.is_get_device.argtypes = [ctypes.POINTER(ci)]
@@ -1240,6 +1254,110 @@ def conv3x3_bn_relu(features, packed, scale, shift, dilation, relu=True, out_dty
                         d_shift=sh.data_ptr(), relu=int(bool(relu)), d_out=out.data_ptr(),
                         out_dtype=HEAD_F32 if odt == torch.float32 else codes[x.dtype])
         _check(lib().is_conv3x3_bn_relu(ctypes.byref(a), _current_stream(dev)), "is_conv3x3_bn_relu")
+        if g:
+            return out, _guards({"out": (full, pattern)}, g, g)
+    return out
+
+
+def conv_packed_bytes(channels_out, channels_in, kernel, dtype):
+    """is_conv_packed_bytes: the bytes of the packed weights (0: channels, a kernel size or a dtype code outside the
+    ranges)."""
+    return int(lib().is_conv_packed_bytes(int(channels_out), int(channels_in), int(kernel), int(dtype)))
+
+
+def conv_pack_weights(weight, dtype, device=0):
+    """is_conv_pack_weights (instance_stixels_core.h f18): conv.weight [channels_out][channels_in][k][k] with k = 3 or
+    1, a tensor or an array, rounded to torch.float16 or torch.bfloat16 and laid out for is_conv_bn.  Returns a uint8
+    device tensor of conv_packed_bytes(...) bytes (on the weight's device if it is a device tensor, else on
+    cuda:`device`); enqueued on the current torch stream, once per model."""
+    import torch
+    if dtype not in _half_codes():
+        raise CoreError(f"dtype {dtype} is neither torch.float16 nor torch.bfloat16")
+    w = weight if torch.is_tensor(weight) else torch.from_numpy(np.ascontiguousarray(weight, np.float32))
+    if w.dim() != 4 or w.shape[2] != w.shape[3]:
+        raise CoreError("weight must be [channels_out][channels_in][k][k]")
+    dev = w.device if w.is_cuda else torch.device("cuda", device)
+    w = w.detach().to(device=dev, dtype=torch.float32).contiguous()
+    cout, cin, k = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+    nbytes = conv_packed_bytes(cout, cin, k, _half_codes()[dtype])
+    if nbytes == 0:
+        raise CoreError(f"is_conv_packed_bytes refuses channels_out {cout}, channels_in {cin}, kernel {k}")
+    with torch.cuda.device(dev):
+        packed = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        _check(lib().is_conv_pack_weights(w.data_ptr(), cout, cin, k, _half_codes()[dtype], packed.data_ptr(),
+                                          _current_stream(dev)), "is_conv_pack_weights")
+    return packed
+
+
+def conv_bn_ptr(stream=0, **fields):
+    """is_conv_bn on raw device pointers (ints): fields are those of ConvBnArgs.  Asynchronous on `stream`; returns
+    the return code and raises nothing (the tests check IS_EINVAL)."""
+    a = _with_reserved(ConvBnArgs, fields)
+    return lib().is_conv_bn(ctypes.byref(a), ctypes.c_void_p(int(stream)))
+
+
+def conv_bn(features, packed, scale, shift, kernel, dilation=1, residual=None, relu=True, out_dtype=None, canary=0):
+    """A 3x3 (dilated, padding = dilation) or 1x1 convolution without bias, stride 1, with folded BatchNorm, an
+    optional residual added in fp32 between the BatchNorm and the ReLU, and an optional ReLU, of a batch in one launch
+    (is_conv_bn, instance_stixels_core.h f18), with the numerics the header fixes.
+
+    features    device tensor [n][channels_in][rows8][cols8], float16 or bfloat16; made contiguous NCHW
+    packed      conv_pack_weights(conv.weight, features.dtype) on the same device, of the same `kernel`
+    scale, shift   [channels_out] float32, tensors or arrays: the folded BatchNorm (cnn.fold_batchnorm)
+    residual    None, or a device tensor [n][channels_out][rows8][cols8] of the features' dtype (it may be `features`)
+    out_dtype   None (the features' dtype) or torch.float32
+
+    Returns the output [n][channels_out][rows8][cols8] on the features' device, enqueued on the current torch stream.
+    canary > 0: as conv3x3_bn_relu, {"out": (front, back, pattern)} is returned second (one synchronisation)."""
+    import torch
+    x = features
+    if not torch.is_tensor(x) or not x.is_cuda or x.dim() != 4:
+        raise CoreError("features must be a device tensor [n][channels_in][rows8][cols8]")
+    codes = _half_codes()
+    if x.dtype not in codes:
+        raise CoreError(f"features dtype {x.dtype} is neither float16 nor bfloat16 (convert fp32 features first)")
+    odt = x.dtype if out_dtype is None else out_dtype
+    if odt != x.dtype and odt != torch.float32:
+        raise CoreError(f"out_dtype {odt} is neither the features' dtype nor float32")
+    same = residual is features
+    x = x.contiguous()
+    dev = x.device
+    n, cin, Hs, Ws = (int(v) for v in x.shape)
+
+    def f32(v):
+        t = v if torch.is_tensor(v) else torch.tensor(np.asarray(v, np.float32))
+        return t.detach().to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+    sc, sh = f32(scale), f32(shift)
+    cout = int(sc.numel())
+    if int(sh.numel()) != cout:
+        raise CoreError(f"scale holds {cout} channels, shift {int(sh.numel())}")
+    res = None
+    if residual is not None:
+        res = x if same else residual
+        if not torch.is_tensor(res) or res.device != dev or res.dtype != x.dtype or \
+                tuple(int(v) for v in res.shape) != (n, cout, Hs, Ws):
+            raise CoreError(f"residual must be a {x.dtype} tensor [{n}][{cout}][{Hs}][{Ws}] on the features' device")
+        res = res.contiguous()
+    need = conv_packed_bytes(cout, cin, int(kernel), codes[x.dtype])
+    if not torch.is_tensor(packed) or packed.device != dev or packed.dtype != torch.uint8 or \
+            not packed.is_contiguous() or need == 0 or int(packed.numel()) != need:
+        raise CoreError(f"packed must be conv_pack_weights' uint8 tensor for channels_out {cout}, channels_in {cin}, "
+                        f"kernel {kernel} and {x.dtype} on the features' device")
+    g = int(canary)
+    pattern = np.float32(-12345.0) if odt == torch.float32 else np.uint16(0x5A5A)
+    with torch.cuda.device(dev):
+        if odt == torch.float32:
+            full, flat = _guarded(n * cout * Hs * Ws, torch.float32, dev, g, float(pattern))
+        else:   # (the pattern as bits: 0x5A5A is a finite value in both half formats)
+            full, flat = _guarded(n * cout * Hs * Ws, torch.int16, dev, g, int(pattern))
+            flat = flat.view(odt)
+        out = flat.view(n, cout, Hs, Ws)
+        a = ConvBnArgs(d_features=x.data_ptr(), dtype=codes[x.dtype], n_images=n, channels_in=cin, channels_out=cout,
+                       rows8=Hs, cols8=Ws, kernel=int(kernel), dilation=int(dilation), d_packed=packed.data_ptr(),
+                       d_scale=sc.data_ptr(), d_shift=sh.data_ptr(),
+                       d_residual=res.data_ptr() if res is not None else None, relu=int(bool(relu)),
+                       d_out=out.data_ptr(), out_dtype=HEAD_F32 if odt == torch.float32 else codes[x.dtype])
+        _check(lib().is_conv_bn(ctypes.byref(a), _current_stream(dev)), "is_conv_bn")
         if g:
             return out, _guards({"out": (full, pattern)}, g, g)
     return out

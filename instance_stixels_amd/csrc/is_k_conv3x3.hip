@@ -1,6 +1,8 @@
 /*
  * is_k_conv3x3.hip -- f17: the backbone's tail, a dilated 3x3 convolution with folded BatchNorm and ReLU of a batch in
  * one launch (is_conv3x3_bn_relu), and the packing of its weights (is_conv3x3_pack_weights).
+ * f18: the same kernel with a residual operand in its epilogue and with one tap instead of nine (is_conv_bn,
+ * is_conv_pack_weights): the 3x3 convolutions and the 1x1 downsample of the residual blocks of layer5 and layer6.
  *
  * What it replaces: layer7 and layer8 of the reference's DRN (tools/CNN_training/models/drn.py:181-185, built by
  *   _make_conv_layers, :223-233: Conv2d(C, C, 3, padding = dilation, dilation, bias = False) + BatchNorm2d + ReLU),
@@ -22,6 +24,20 @@
  *             half dtype round to nearest even.
  *   The same bytes on every run; a frame's result does not depend on its position in the batch or on n_images.
  *   Non-finite values give unspecified values; no address depends on a value.
+ *
+ * f18 (BasicBlock, drn.py:54-87, built by _make_layer, drn.py:199-221, as layer5 and layer6,
+ * drn.py:168-172) adds two template parameters.  The four instantiations <TAPS = 9, RESIDUAL = false> are f17's.
+ *   RESIDUAL  the epilogue is v = fmaf(scale[co], a, shift[co]); v = v + (float)residual[n][co][y][x]; then max(v, 0)
+ *             with relu; then the store as above.  All in fp32: two roundings, then the one of the conversion.  The
+ *             residual has the features' half dtype (the widening is exact) and the OUTPUT's shape, and an element is
+ *             read under exactly the predicate of its store (y < H, x < W, channel tile <= last_tile): a ragged tile
+ *             and the phantom channel tile of channels_out = 32 mod 64 read nothing.
+ *   TAPS = 1  the 1x1 convolution (downsample: Conv2d(1x1, bias = False) + BatchNorm2d, no ReLU).  No halo: d = 0 in
+ *             every formula below, the B tile is 8 x 32 pixels, the packed layout is the same with one tap,
+ *             [channel tile][chunk][k half][channel][8 k].  A wave has only 4 MFMAs per chunk, so C1_STAGE = 4
+ *             16-channel chunks (fewer at the end of channels_in) are staged per barrier pair: 8 KB of weights and
+ *             32 KB of pixels.  The MFMAs of an element still follow each other in increasing chunk, fixed by the
+ *             shape alone.
  *
  * Tile mapping.  A workgroup of four waves owns C3_MT = 2 tiles of 32 output channels and C3_ROWS = 8 rows of
  * C3_COLS = 32 pixels of one frame; a wave takes two of the rows and holds 2 x 2 accumulators of 32x32x16: output
@@ -45,10 +61,13 @@
 #define C3_ROWS (4 * C3_NT)              /* rows of a workgroup */
 #define C3_MT 2                          /* 32-channel tiles of a workgroup */
 #define C3_KC 16                         /* input channels per chunk: the k of one MFMA */
-#define C3_ABLOCK (9 * 2 * 32)           /* 16-byte units of one (channel tile, chunk) block of the packed weights */
+#define C3_ABLOCK(TAPS) ((TAPS) * 2 * 32) /* 16-byte units of one (channel tile, chunk) block of the packed weights */
 #define C3_MAX_DILATION 8
-static_assert((C3_MT * C3_ABLOCK + 2 * (C3_ROWS + 2 * C3_MAX_DILATION) * (C3_COLS + 2 * C3_MAX_DILATION)) * 16 <= 65536,
+#define C1_STAGE 4                       /* TAPS = 1: chunks staged per barrier pair */
+#define C3_STAGE(TAPS) ((TAPS) == 1 ? C1_STAGE : 1)
+static_assert((C3_MT * C3_ABLOCK(9) + 2 * (C3_ROWS + 2 * C3_MAX_DILATION) * (C3_COLS + 2 * C3_MAX_DILATION)) * 16 <= 65536,
               "the weights and the halo tile of the largest dilation fit the LDS a launch may ask for");
+static_assert(C1_STAGE * (C3_MT * C3_ABLOCK(1) + 2 * C3_ROWS * C3_COLS) * 16 <= 65536, "and so does a stage of the 1x1 form");
 
 typedef float c3_acc __attribute__((ext_vector_type(16)));
 typedef _Float16 c3_f16x8 __attribute__((ext_vector_type(8)));
@@ -72,26 +91,35 @@ template <> __device__ __forceinline__ c3_acc c3_mfma<IS_HEAD_BF16>(uint4 a, uin
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(c3_bf16x8, a), __builtin_bit_cast(c3_bf16x8, b), c, 0, 0, 0);
 }
 
+/* half -> fp32, exact */
+template <int DT> __device__ __forceinline__ float c3_widen(uint16_t u);
+template <> __device__ __forceinline__ float c3_widen<IS_HEAD_F16>(uint16_t u) { return (float)__builtin_bit_cast(_Float16, u); }
+template <> __device__ __forceinline__ float c3_widen<IS_HEAD_BF16>(uint16_t u) { return __uint_as_float((uint32_t)u << 16); }
+
 /* the 16-byte slot of k half `h` of halo pixel `p` */
 __device__ __forceinline__ int c3_slot(int p, int h) { return 2 * p + (h ^ ((p >> 3) & 1)); }
 
-/* packed[((tile * chunks + chunk) * 9 + tap) * 512 + h * 256 + r * 8 + j] = round(w[32 tile + r][16 chunk + 8 h + j][tap]) */
+/* packed[((tile * chunks + chunk) * taps + tap) * 512 + h * 256 + r * 8 + j] = round(w[32 tile + r][16 chunk + 8 h + j][tap]) */
 template <int DT>
 __global__ __launch_bounds__(256) void k_conv3x3_pack(const float* __restrict__ weight, uint16_t* __restrict__ packed,
-                                                      int Cin, int total) {
+                                                      int Cin, int taps, int total) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= total) return;
-    const int j = e & 7, r = (e >> 3) & 31, h = (e >> 8) & 1, tap = (e >> 9) % 9, blk = (e >> 9) / 9;
+    const int j = e & 7, r = (e >> 3) & 31, h = (e >> 8) & 1, tap = (e >> 9) % taps, blk = (e >> 9) / taps;
     const int chunks = Cin / C3_KC, chunk = blk % chunks, tile = blk / chunks;
     const int co = 32 * tile + r, ci = C3_KC * chunk + 8 * h + j;
-    packed[e] = c3_round<DT>(weight[((size_t)co * Cin + ci) * 9 + tap]);
+    packed[e] = c3_round<DT>(weight[((size_t)co * Cin + ci) * taps + tap]);
 }
 
-template <int DT, bool F32OUT>
+template <int DT, bool F32OUT, int TAPS, bool RESIDUAL>
 __global__ __launch_bounds__(256) void k_conv3x3(const uint16_t* __restrict__ features, const uint4* __restrict__ packed,
                                                  const float* __restrict__ scale, const float* __restrict__ shift,
-                                                 void* __restrict__ out_, int Cin, int Cout, int H, int W, int d,
-                                                 int relu, int tiles_x, int tiles, int groups) {
+                                                 const uint16_t* __restrict__ residual, void* __restrict__ out_, int Cin,
+                                                 int Cout, int H, int W, int d_, int relu, int tiles_x, int tiles,
+                                                 int groups) {
+    static_assert(TAPS == 9 || TAPS == 1, "a 3x3 or a 1x1 convolution");
+    constexpr int ABLOCK = C3_ABLOCK(TAPS), STAGE = C3_STAGE(TAPS);
+    const int d = TAPS == 1 ? 0 : d_;
     extern __shared__ uint4 c3_lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, half = lane >> 5;
@@ -100,8 +128,8 @@ __global__ __launch_bounds__(256) void k_conv3x3(const uint16_t* __restrict__ fe
     if (tile >= tiles) return; /* (the whole workgroup, before any barrier) */
     const int n = blockIdx.y, y0 = (tile / tiles_x) * C3_ROWS, x0 = (tile % tiles_x) * C3_COLS;
     const int HW = C3_COLS + 2 * d, pixels = (C3_ROWS + 2 * d) * HW, chunks = Cin / C3_KC;
-    uint4* const ldsA = c3_lds;                    /* [C3_MT][tap][k half][channel] */
-    uint4* const ldsB = c3_lds + C3_MT * C3_ABLOCK; /* c3_slot(pixel, k half) */
+    uint4* const ldsA = c3_lds;                          /* [C3_MT][chunk of the stage][tap][k half][channel] */
+    uint4* const ldsB = c3_lds + C3_MT * STAGE * ABLOCK; /* [chunk of the stage] c3_slot(pixel, k half) */
     const size_t plane = (size_t)H * W;
     const uint16_t* const xn = features + (size_t)n * Cin * plane;
     const int last_tile = Cout / 32 - 1;
@@ -114,43 +142,47 @@ __global__ __launch_bounds__(256) void k_conv3x3(const uint16_t* __restrict__ fe
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[m][t][i] = 0.0f;
 
-    for (int chunk = 0; chunk < chunks; ++chunk) {
-        __syncthreads(); /* the previous chunk's operands are no longer read */
+    for (int chunk = 0; chunk < chunks; chunk += STAGE) {
+        const int nc = STAGE == 1 ? 1 : min(STAGE, chunks - chunk); /* chunks of this stage */
+        __syncthreads(); /* the previous stage's operands are no longer read */
         /* A: a channel tile past the last one (channels_out = 32 mod 64) copies the last one and is never stored */
 #pragma unroll
         for (int m = 0; m < C3_MT; ++m) {
-            const uint4* src = packed + ((size_t)min(C3_MT * group + m, last_tile) * chunks + chunk) * C3_ABLOCK;
-            for (int i = tid; i < C3_ABLOCK; i += 256) ldsA[m * C3_ABLOCK + i] = src[i];
+            const uint4* src = packed + ((size_t)min(C3_MT * group + m, last_tile) * chunks + chunk) * ABLOCK;
+            for (int i = tid; i < nc * ABLOCK; i += 256) ldsA[m * STAGE * ABLOCK + i] = src[i];
         }
         /* B: an item is 8 channels of one halo pixel; consecutive threads take consecutive pixels of a plane.  A pixel
          * outside the image loads the nearest pixel inside it and stores zeros. */
-        for (int it = tid; it < 2 * pixels; it += 256) {
+        for (int it_ = tid; it_ < nc * 2 * pixels; it_ += 256) {
+            const int cc = STAGE == 1 ? 0 : it_ / (2 * pixels), it = it_ - cc * 2 * pixels;
             const int h = it >= pixels, p = it - h * pixels, py = p / HW, px = p - py * HW;
             const int gy = y0 - d + py, gx = x0 - d + px;
             const bool inside = gy >= 0 && gy < H && gx >= 0 && gx < W;
-            const uint16_t* src = xn + (size_t)(C3_KC * chunk + 8 * h) * plane +
+            const uint16_t* src = xn + (size_t)(C3_KC * (chunk + cc) + 8 * h) * plane +
                                   (size_t)min(max(gy, 0), H - 1) * W + min(max(gx, 0), W - 1);
             uint32_t v[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = src[j * plane];
             uint4 q;
             q.x = v[0] | (v[1] << 16), q.y = v[2] | (v[3] << 16), q.z = v[4] | (v[5] << 16), q.w = v[6] | (v[7] << 16);
-            ldsB[c3_slot(p, h)] = inside ? q : make_uint4(0, 0, 0, 0);
+            ldsB[cc * 2 * pixels + c3_slot(p, h)] = inside ? q : make_uint4(0, 0, 0, 0);
         }
         __syncthreads();
+        for (int cc = 0; cc < nc; ++cc) {
 #pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            const int ky = tap / 3, kx = tap % 3;
-            uint4 a[C3_MT], b[C3_NT];
+            for (int tap = 0; tap < TAPS; ++tap) {
+                const int ky = tap / 3, kx = tap % 3;
+                uint4 a[C3_MT], b[C3_NT];
 #pragma unroll
-            for (int m = 0; m < C3_MT; ++m) a[m] = ldsA[m * C3_ABLOCK + (2 * tap + half) * 32 + r];
+                for (int m = 0; m < C3_MT; ++m) a[m] = ldsA[(m * STAGE + cc) * ABLOCK + (2 * tap + half) * 32 + r];
 #pragma unroll
-            for (int t = 0; t < C3_NT; ++t)
-                b[t] = ldsB[c3_slot((C3_NT * wave + t + ky * d) * HW + r + kx * d, half)];
+                for (int t = 0; t < C3_NT; ++t)
+                    b[t] = ldsB[cc * 2 * pixels + c3_slot((C3_NT * wave + t + ky * d) * HW + r + kx * d, half)];
 #pragma unroll
-            for (int m = 0; m < C3_MT; ++m)
+                for (int m = 0; m < C3_MT; ++m)
 #pragma unroll
-                for (int t = 0; t < C3_NT; ++t) acc[m][t] = c3_mfma<DT>(a[m], b[t], acc[m][t]);
+                    for (int t = 0; t < C3_NT; ++t) acc[m][t] = c3_mfma<DT>(a[m], b[t], acc[m][t]);
+            }
         }
     }
 
@@ -169,6 +201,9 @@ __global__ __launch_bounds__(256) void k_conv3x3(const uint16_t* __restrict__ fe
             for (int t = 0; t < C3_NT; ++t) {
                 const int y = y0 + C3_NT * wave + t;
                 float v = fmaf(sc, acc[m][t][i], sh);
+                if (RESIDUAL) { /* (read under the predicate of the store below, at the store's index) */
+                    if (y < H && x < W) v = v + c3_widen<DT>(residual[(((size_t)n * Cout + co) * H + y) * W + x]);
+                }
                 if (relu) v = fmaxf(v, 0.0f);
                 if (y < H && x < W) {
                     const size_t at = (((size_t)n * Cout + co) * H + y) * W + x;
@@ -180,39 +215,52 @@ __global__ __launch_bounds__(256) void k_conv3x3(const uint16_t* __restrict__ fe
     }
 }
 
-/* The arguments are checked by is_conv3x3_pack_weights. */
-extern "C" hipError_t isk_launch_conv3x3_pack(const float* d_weight, int channels_out, int channels_in, int dtype,
-                                              void* d_packed, hipStream_t stream) {
-    const int total = channels_out * channels_in * 9; /* at most 2048 * 2048 * 9 */
+/* The arguments are checked by is_conv_pack_weights. */
+extern "C" hipError_t isk_launch_conv_pack(const float* d_weight, int channels_out, int channels_in, int kernel, int dtype,
+                                           void* d_packed, hipStream_t stream) {
+    const int taps = kernel * kernel, total = channels_out * channels_in * taps; /* at most 2048 * 2048 * 9 */
     const dim3 grid((total + 255) / 256);
     if (dtype == IS_HEAD_F16)
-        hipLaunchKernelGGL(k_conv3x3_pack<IS_HEAD_F16>, grid, dim3(256), 0, stream, d_weight, (uint16_t*)d_packed, channels_in, total);
+        hipLaunchKernelGGL(k_conv3x3_pack<IS_HEAD_F16>, grid, dim3(256), 0, stream, d_weight, (uint16_t*)d_packed, channels_in, taps, total);
     else if (dtype == IS_HEAD_BF16)
-        hipLaunchKernelGGL(k_conv3x3_pack<IS_HEAD_BF16>, grid, dim3(256), 0, stream, d_weight, (uint16_t*)d_packed, channels_in, total);
+        hipLaunchKernelGGL(k_conv3x3_pack<IS_HEAD_BF16>, grid, dim3(256), 0, stream, d_weight, (uint16_t*)d_packed, channels_in, taps, total);
     else
         return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
-/* The arguments are checked by is_conv3x3_bn_relu. */
-extern "C" hipError_t isk_launch_conv3x3(const is_conv3x3_args* a, hipStream_t stream) {
-    const int d = a->dilation;
+template <int DT, bool F32OUT, int TAPS, bool RESIDUAL>
+static void c3_launch(const is_conv_bn_args* a, hipStream_t stream) {
+    const int d = TAPS == 1 ? 0 : a->dilation;
     const int tiles_x = (a->cols8 + C3_COLS - 1) / C3_COLS, tiles = tiles_x * ((a->rows8 + C3_ROWS - 1) / C3_ROWS);
     const int groups = (a->channels_out / 32 + C3_MT - 1) / C3_MT;
     const dim3 grid((unsigned)groups * (unsigned)((tiles + 7) / 8 * 8), a->n_images); /* at most 32 * 2^22 */
-    const size_t lds = (size_t)(C3_MT * C3_ABLOCK + 2 * (C3_ROWS + 2 * d) * (C3_COLS + 2 * d)) * 16;
+    const size_t lds = (size_t)C3_STAGE(TAPS) * (C3_MT * C3_ABLOCK(TAPS) + 2 * (C3_ROWS + 2 * d) * (C3_COLS + 2 * d)) * 16;
+    hipLaunchKernelGGL((k_conv3x3<DT, F32OUT, TAPS, RESIDUAL>), grid, dim3(256), lds, stream,
+                       (const uint16_t*)a->d_features, (const uint4*)a->d_packed, a->d_scale, a->d_shift,
+                       (const uint16_t*)a->d_residual, a->d_out, a->channels_in, a->channels_out, a->rows8, a->cols8, d,
+                       a->relu, tiles_x, tiles, groups);
+}
+
+template <int DT, bool F32OUT>
+static void c3_launch_form(const is_conv_bn_args* a, hipStream_t stream) {
+    if (a->kernel == 3) {
+        if (a->d_residual) c3_launch<DT, F32OUT, 9, true>(a, stream); else c3_launch<DT, F32OUT, 9, false>(a, stream);
+    } else {
+        if (a->d_residual) c3_launch<DT, F32OUT, 1, true>(a, stream); else c3_launch<DT, F32OUT, 1, false>(a, stream);
+    }
+}
+
+/* The arguments are checked by is_conv_bn (and, through it, by is_conv3x3_bn_relu). */
+extern "C" hipError_t isk_launch_conv_bn(const is_conv_bn_args* a, hipStream_t stream) {
     const bool f32out = a->out_dtype == IS_HEAD_F32;
-#define C3_LAUNCH(DT, F32)                                                                                           \
-    hipLaunchKernelGGL((k_conv3x3<DT, F32>), grid, dim3(256), lds, stream, (const uint16_t*)a->d_features,            \
-                       (const uint4*)a->d_packed, a->d_scale, a->d_shift, a->d_out, a->channels_in, a->channels_out, \
-                       a->rows8, a->cols8, d, a->relu, tiles_x, tiles, groups)
+    if (a->kernel != 3 && a->kernel != 1) return hipErrorInvalidValue;
     if (a->dtype == IS_HEAD_F16) {
-        if (f32out) C3_LAUNCH(IS_HEAD_F16, true); else C3_LAUNCH(IS_HEAD_F16, false);
+        if (f32out) c3_launch_form<IS_HEAD_F16, true>(a, stream); else c3_launch_form<IS_HEAD_F16, false>(a, stream);
     } else if (a->dtype == IS_HEAD_BF16) {
-        if (f32out) C3_LAUNCH(IS_HEAD_BF16, true); else C3_LAUNCH(IS_HEAD_BF16, false);
+        if (f32out) c3_launch_form<IS_HEAD_BF16, true>(a, stream); else c3_launch_form<IS_HEAD_BF16, false>(a, stream);
     } else {
         return hipErrorInvalidValue;
     }
-#undef C3_LAUNCH
     return hipGetLastError();
 }

@@ -1,0 +1,211 @@
+"""The residual blocks of the backbone (f18: is_conv_bn, core.conv_bn, cnn.ResidualBlock) against what they replace
+and against themselves, on the same device tensors (GPU box).
+
+Prints one JSON line (progress on stderr).  Every timing is ms per batch by device events around the enqueued work,
+median of --iters (at least 10) with min and max, every arm of a comparison warmed up first and the arms then
+ALTERNATING inside one loop.  Parts (--parts, comma-separated):
+- residual: core.conv_bn (3x3, dilation 2, --C channels) with a residual operand against the same call without one;
+  `residual_gb` is the extra operand's bytes.
+- 1x1: the downsample launch (core.conv_bn, kernel 1, no ReLU) at 128 -> 256 and 256 -> 512 channels against torch
+  F.conv2d + F.batch_norm (eval) in the same dtype, contiguous and channels_last; the faster of the two is the
+  comparison (`faster` is false where torch is as fast or faster: "not faster").
+- layers: layer5 + layer6 of drn_d_22 (two BasicBlocks each, 128 -> 256 -> 512, dilations 2 and 4, the first block of
+  each with a downsample) through cnn.ResidualBlock (10 launches) against the torch modules in the same dtype,
+  contiguous and channels_last.  `tflop` is computed from the shape; `mfma_floor_ms` is that over the dense half MFMA
+  rate of --cus compute units x 4 SIMDs x 1024 FLOP per clock at --mhz.
+--no-torch leaves the torch arms out.  torch's first convolution of a shape takes 30 - 160 s: run the dtypes, and if
+need be the parts, in separate commands.
+
+    python tools/time_resblock.py [--n 64 --rows8 128 --cols8 256 --iters 20 --dtypes bf16 --parts residual,1x1,layers]
+"""
+import argparse
+import copy
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT]
+
+
+def mmm(ts, digits=3):
+    import numpy as np
+    return [round(float(np.median(ts)), digits), round(min(ts), digits), round(max(ts), digits)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=64)
+    ap.add_argument("--C", type=int, default=512, help="channels of the `residual` part")
+    ap.add_argument("--rows8", type=int, default=128)
+    ap.add_argument("--cols8", type=int, default=256)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--mhz", type=float, default=2400.0)
+    ap.add_argument("--cus", type=int, default=256)
+    ap.add_argument("--dtypes", default="fp16,bf16", help="comma-separated subset of fp16,bf16")
+    ap.add_argument("--parts", default="residual,1x1,layers", help="comma-separated subset of residual,1x1,layers")
+    ap.add_argument("--no-torch", action="store_true", help="time the library's launches alone")
+    a = ap.parse_args()
+    if a.iters < 10:
+        sys.exit("time_resblock.py: --iters must be at least 10")
+    import numpy as np
+    import torch
+    import torch.nn.functional as F
+    from instance_stixels_amd import cnn, core
+    if not torch.cuda.is_available():
+        sys.exit("time_resblock.py needs a GPU")
+    dev = torch.device("cuda", 0)
+    n, Hs, Ws = a.n, a.rows8, a.cols8
+    parts = a.parts.split(",")
+    torch.manual_seed(1)
+    eps = 1e-5
+    t_start = time.time()
+
+    def note(*what):
+        print("[%6.1f s]" % (time.time() - t_start), *what, file=sys.stderr, flush=True)
+
+    def floor_ms(tflop):
+        return tflop * 1e12 / (a.cus * 4 * 1024 * a.mhz * 1e6) * 1e3
+
+    def bn_stats(c):
+        return (torch.randn(c, device=dev) * 0.2, torch.rand(c, device=dev) + 0.5, torch.rand(c, device=dev) + 0.5,
+                torch.randn(c, device=dev) * 0.1)                              # mean, var, gamma, beta
+
+    def fold(mean, var, gamma, beta):
+        scale = gamma.double() / torch.sqrt(var.double() + eps)
+        return scale.float(), (beta.double() - mean.double() * scale).float()
+
+    def weight(cout, cin, k):
+        return torch.randn((cout, cin, k, k), device=dev) * (2.0 / (k * k * cout)) ** 0.5
+
+    def measure(label, arms):
+        for arm, fn in arms.items():                # warm-up of every arm (a library's first call may tune itself)
+            note(label, "warm-up", arm)
+            for _ in range(2):
+                fn()
+            torch.cuda.synchronize()
+        ts = {arm: [] for arm in arms}
+        for _ in range(a.iters):
+            for arm, fn in arms.items():
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                fn()
+                t1.record()
+                t1.synchronize()
+                ts[arm].append(t0.elapsed_time(t1))
+        row = {arm + "_ms_med_min_max": mmm(t) for arm, t in ts.items()}
+        return row, {arm: float(np.median(t)) for arm, t in ts.items()}
+
+    def against_torch(row, med, new="new"):
+        if not a.no_torch:
+            best = min(med["torch_contiguous"], med["torch_channels_last"])
+            row["torch_best_ms"] = round(best, 3)
+            row["new_over_torch_best"] = round(med[new] / best, 3)
+            row["faster"] = bool(med[new] < best)
+
+    class TorchBlock(torch.nn.Module):
+        """conv1, bn1, relu, conv2, bn2, (+ downsample(x) or x), relu: a BasicBlock in eval mode."""
+
+        def __init__(self, cin, cout, d, dtype):
+            super().__init__()
+            self.conv1 = torch.nn.Conv2d(cin, cout, 3, padding=d, dilation=d, bias=False)
+            self.bn1 = torch.nn.BatchNorm2d(cout)
+            self.conv2 = torch.nn.Conv2d(cout, cout, 3, padding=d, dilation=d, bias=False)
+            self.bn2 = torch.nn.BatchNorm2d(cout)
+            self.downsample = None
+            if cin != cout:
+                self.downsample = torch.nn.Sequential(torch.nn.Conv2d(cin, cout, 1, bias=False), torch.nn.BatchNorm2d(cout))
+            self.residual = True
+            with torch.no_grad():
+                for m in self.modules():
+                    if isinstance(m, torch.nn.Conv2d):
+                        m.weight.copy_(weight(m.out_channels, m.in_channels, m.kernel_size[0]))
+                    elif isinstance(m, torch.nn.BatchNorm2d):
+                        mean, var, gamma, beta = bn_stats(m.num_features)
+                        m.running_mean.copy_(mean), m.running_var.copy_(var), m.weight.copy_(gamma), m.bias.copy_(beta)
+            self.eval()
+
+        def forward(self, x):
+            out = self.bn2(self.conv2(F.relu(self.bn1(self.conv1(x)))))
+            out = out + (x if self.downsample is None else self.downsample(x))
+            return F.relu(out)
+
+    out = {"frames": n, "plane": [Hs, Ws], "iters": a.iters, "mhz": a.mhz, "cus": a.cus}
+    for name, dtype in (("fp16", torch.float16), ("bf16", torch.bfloat16)):
+        if name not in a.dtypes.split(","):
+            continue
+        if "residual" in parts:
+            C = a.C
+            x = torch.randn((n, C, Hs, Ws), device=dev).abs_().to(dtype)
+            res = torch.randn((n, C, Hs, Ws), device=dev).to(dtype)
+            packed, (scale, shift) = core.conv_pack_weights(weight(C, C, 3), dtype), fold(*bn_stats(C))
+            tflop = 2.0 * 9 * C * C * n * Hs * Ws / 1e12
+            row, med = measure(name + " residual", {
+                "plain": lambda: core.conv_bn(x, packed, scale, shift, 3, 2),
+                "residual": lambda: core.conv_bn(x, packed, scale, shift, 3, 2, residual=res),
+                "residual_is_features": lambda: core.conv_bn(x, packed, scale, shift, 3, 2, residual=x)})
+            row.update(shape=[n, C, Hs, Ws], residual_gb=round(res.numel() * 2 / 1e9, 3),
+                       residual_minus_plain_ms=round(med["residual"] - med["plain"], 3),
+                       residual_tflops=round(tflop / (med["residual"] * 1e-3), 1))
+            out[name + "_residual"] = row
+            note(name, "residual", json.dumps(row))
+            del x, res, packed
+            torch.cuda.empty_cache()
+        if "1x1" in parts:
+            for cin, cout in ((128, 256), (256, 512)):
+                x = torch.randn((n, cin, Hs, Ws), device=dev).abs_().to(dtype)
+                w32, stats = weight(cout, cin, 1), bn_stats(cout)
+                packed, (scale, shift) = core.conv_pack_weights(w32, dtype), fold(*stats)
+                arms = {"new": lambda: core.conv_bn(x, packed, scale, shift, 1, relu=False)}
+                if not a.no_torch:
+                    wd, bn = w32.to(dtype), [t.to(dtype) for t in stats]
+                    x_cl, w_cl = x.contiguous(memory_format=torch.channels_last), wd.contiguous(memory_format=torch.channels_last)
+                    arms["torch_contiguous"] = lambda: F.batch_norm(F.conv2d(x, wd), *bn, False, 0.0, eps)
+                    arms["torch_channels_last"] = lambda: F.batch_norm(F.conv2d(x_cl, w_cl), *bn, False, 0.0, eps)
+                row, med = measure("%s 1x1 %d->%d" % (name, cin, cout), arms)
+                gb = n * Hs * Ws * (cin + cout) * 2 / 1e9
+                row.update(compulsory_gb=round(gb, 3), new_gb_per_s=round(gb / (med["new"] * 1e-3), 1),
+                           new_tflops=round(2.0 * cin * cout * n * Hs * Ws / 1e12 / (med["new"] * 1e-3), 1))
+                against_torch(row, med)
+                out["%s_1x1_%d_%d" % (name, cin, cout)] = row
+                note(name, "1x1", cin, cout, json.dumps(row))
+                del x, packed
+                if not a.no_torch:
+                    del x_cl
+                torch.cuda.empty_cache()
+        if "layers" in parts:
+            blocks = [TorchBlock(128, 256, 2, dtype), TorchBlock(256, 256, 2, dtype), TorchBlock(256, 512, 4, dtype),
+                      TorchBlock(512, 512, 4, dtype)]
+            ours = [cnn.ResidualBlock(b.to(dev), dtype=dtype) for b in blocks]      # (folded from the fp32 modules)
+            macs = sum(m.weight.numel() for b in blocks for m in b.modules() if isinstance(m, torch.nn.Conv2d))
+            tflop = 2.0 * macs * n * Hs * Ws / 1e12
+            x = torch.randn((n, 128, Hs, Ws), device=dev).abs_().to(dtype)
+
+            def new():
+                y = x
+                for blk in ours:
+                    y = blk(y)
+                return y
+            arms = {"new": new}
+            if not a.no_torch:
+                seq = torch.nn.Sequential(*blocks).to(device=dev, dtype=dtype).eval()
+                seq_cl = copy.deepcopy(seq).to(memory_format=torch.channels_last).eval()
+                x_cl = x.contiguous(memory_format=torch.channels_last)
+                arms["torch_contiguous"] = lambda: seq(x)
+                arms["torch_channels_last"] = lambda: seq_cl(x_cl)
+            with torch.no_grad():
+                row, med = measure(name + " layer5+layer6", arms)
+            row.update(shape_in=[n, 128, Hs, Ws], launches=10, tflop=round(tflop, 3),
+                       mfma_floor_ms=round(floor_ms(tflop), 3), new_tflops=round(tflop / (med["new"] * 1e-3), 1),
+                       new_share_of_mfma_floor=round(floor_ms(tflop) / med["new"], 3))
+            against_torch(row, med)
+            out[name + "_layers"] = row
+            note(name, "layers", json.dumps(row))
+            del x, ours
+            torch.cuda.empty_cache()
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
