@@ -1,13 +1,17 @@
 """The tail of the reference's backbone on the device (f17): layer7 and layer8 of the DRN (tools/CNN_training/
 models/drn.py:181-185, each an nn.Sequential(Conv2d 3x3 dilated without bias, BatchNorm2d, ReLU) built by
 _make_conv_layers, drn.py:223-233) and the head `seg` behind them, as three launches of the C ABI with nothing in
-between: core.conv3x3_bn_relu twice, core.segmentation_head once.  Inference only: BatchNorm is folded from its running
-statistics, nothing here is differentiable.  torch owns the memory and the stream; every value comes from the library's
-kernels (there is no fall-back to torch's convolution).
+between: core.conv_bn twice (with kernel 3 and no residual, the bytes of f17's core.conv3x3_bn_relu), then
+core.segmentation_head once.  Inference only: BatchNorm is folded from its running statistics, nothing here is
+differentiable.  torch owns the memory and the stream; every value comes from the library's kernels (there is no
+fall-back to torch's convolution).
 
 f18 puts the residual blocks of layer5 and layer6 in front of it (BasicBlock, drn.py:54-87, built by _make_layer,
 drn.py:199-221, as drn.py:168-172): ResidualBlock is two launches of core.conv_bn, three with a downsample, and
-DrnDilated is layer5 -> layer6 -> DrnTail, the output of layer4 in and the DP's input out."""
+DrnDilated is layer5 -> layer6 -> DrnTail, the output of layer4 in and the DP's input out.
+
+Every convolution here is one ConvBn: the packed weights, the folded BatchNorm and the launch's kernel, dilation and
+relu.  The tail's ConvBnRelu is a ConvBn built from (Conv2d, BatchNorm2d); a ResidualBlock holds two or three."""
 import torch
 
 from . import core
@@ -33,27 +37,46 @@ def fold_batchnorm(bn):
         return scale.float(), shift.float()
 
 
-class ConvBnRelu:
+def _device(device):
+    return device if isinstance(device, torch.device) else torch.device("cuda", device)
+
+
+def _dilated3x3(conv, name):
+    """The dilation of `conv` if it is the reference's 3x3: stride 1, padding = dilation (the same in both directions),
+    one group, no bias."""
+    if not isinstance(conv, torch.nn.Conv2d) or tuple(conv.kernel_size) != (3, 3) or \
+            tuple(conv.dilation) != (conv.dilation[0],) * 2 or tuple(conv.padding) != tuple(conv.dilation) or \
+            conv.groups != 1 or conv.bias is not None or getattr(conv, "padding_mode", "zeros") != "zeros":
+        raise core.CoreError(f"{name} must be Conv2d(kernel_size=3, padding=dilation, groups=1, bias=False)")
+    if tuple(conv.stride) != (1, 1):
+        raise core.CoreError(f"{name} has stride {tuple(conv.stride)}: only the stride-1 layers (layer5 on) are covered")
+    return int(conv.dilation[0])
+
+
+class ConvBn:
+    """A packed convolution and its folded BatchNorm on a device, one launch of core.conv_bn per call: `weight` is
+    conv.weight [channels_out][channels_in][kernel][kernel], `fold` the (scale, shift) of fold_batchnorm.  Nothing is
+    checked here beyond what core.conv_pack_weights checks: the callers check and fold first, then build this."""
+
+    def __init__(self, weight, fold, kernel, dilation, relu, dtype, dev):
+        self.kernel, self.dilation, self.relu, self.dtype = int(kernel), int(dilation), bool(relu), dtype
+        self.packed = core.conv_pack_weights(weight.detach().to(dev), dtype)
+        self.scale, self.shift = fold[0].to(dev), fold[1].to(dev)
+
+    def __call__(self, features, out_dtype=None, residual=None):
+        return core.conv_bn(features, self.packed, self.scale, self.shift, self.kernel, self.dilation,
+                            residual=residual, relu=self.relu, out_dtype=out_dtype)
+
+
+class ConvBnRelu(ConvBn):
     """One layer of the tail: the packed weights of `conv` in `dtype` and the fold of `bn`, on `device`.  conv must be
     the reference's: 3x3, stride 1, padding = dilation (the same in both directions), one group, no bias."""
 
     def __init__(self, conv, bn, dtype=torch.bfloat16, relu=True, device=0):
-        d = conv.dilation[0]
-        if tuple(conv.kernel_size) != (3, 3) or tuple(conv.stride) != (1, 1) or tuple(conv.dilation) != (d, d) or \
-                tuple(conv.padding) != (d, d) or conv.groups != 1 or conv.bias is not None or \
-                getattr(conv, "padding_mode", "zeros") != "zeros":
-            raise core.CoreError("conv must be Conv2d(kernel_size=3, stride=1, padding=dilation, groups=1, bias=False)")
+        d = _dilated3x3(conv, "conv")
         if bn.num_features != conv.out_channels:
             raise core.CoreError(f"bn has {bn.num_features} channels, conv {conv.out_channels}")
-        dev = torch.device("cuda", device) if not isinstance(device, torch.device) else device
-        self.dilation, self.relu, self.dtype = int(d), bool(relu), dtype
-        self.packed = core.conv3x3_pack_weights(conv.weight.detach().to(dev), dtype)
-        scale, shift = fold_batchnorm(bn)
-        self.scale, self.shift = scale.to(dev), shift.to(dev)
-
-    def __call__(self, features, out_dtype=None):
-        return core.conv3x3_bn_relu(features, self.packed, self.scale, self.shift, self.dilation, relu=self.relu,
-                                    out_dtype=out_dtype)
+        super().__init__(conv.weight, fold_batchnorm(bn), 3, d, relu, dtype, _device(device))
 
 
 def _conv_bn_relu_of(layer, name):
@@ -62,17 +85,6 @@ def _conv_bn_relu_of(layer, name):
             or not isinstance(mods[2], torch.nn.ReLU):
         raise core.CoreError(f"{name} must be nn.Sequential(Conv2d, BatchNorm2d, ReLU), as _make_conv_layers builds it")
     return mods[0], mods[1]
-
-
-def _dilated3x3(conv, name):
-    d = conv.dilation[0]
-    if not isinstance(conv, torch.nn.Conv2d) or tuple(conv.kernel_size) != (3, 3) or tuple(conv.dilation) != (d, d) or \
-            tuple(conv.padding) != (d, d) or conv.groups != 1 or conv.bias is not None or \
-            getattr(conv, "padding_mode", "zeros") != "zeros":
-        raise core.CoreError(f"{name} must be Conv2d(kernel_size=3, padding=dilation, groups=1, bias=False)")
-    if tuple(conv.stride) != (1, 1):
-        raise core.CoreError(f"{name} has stride {tuple(conv.stride)}: only the stride-1 blocks (layer5 on) are covered")
-    return int(d)
 
 
 class ResidualBlock:
@@ -85,14 +97,13 @@ class ResidualBlock:
     def __init__(self, block, dtype=torch.bfloat16, device=0):
         if hasattr(block, "conv3"):
             raise core.CoreError("a block with conv3 is a Bottleneck: only BasicBlock is covered")
-        self.dilations = (_dilated3x3(block.conv1, "conv1"), _dilated3x3(block.conv2, "conv2"))
+        d1, d2 = _dilated3x3(block.conv1, "conv1"), _dilated3x3(block.conv2, "conv2")
         c_in, c_mid, c_out = block.conv1.in_channels, block.conv1.out_channels, block.conv2.out_channels
         if block.conv2.in_channels != c_mid or block.bn1.num_features != c_mid or block.bn2.num_features != c_out:
             raise core.CoreError("conv1, bn1, conv2 and bn2 disagree on their channels")
         self.residual = bool(block.residual)
         down = block.downsample if self.residual else None      # (the reference computes and drops it otherwise)
-        folds = [fold_batchnorm(block.bn1), fold_batchnorm(block.bn2)]
-        convs = [block.conv1, block.conv2]
+        fold1, fold2, fold_down = fold_batchnorm(block.bn1), fold_batchnorm(block.bn2), None
         if down is not None:
             mods = list(down) if isinstance(down, torch.nn.Sequential) else []
             if len(mods) != 2 or not isinstance(mods[0], torch.nn.Conv2d) or not isinstance(mods[1], torch.nn.BatchNorm2d) \
@@ -103,22 +114,27 @@ class ResidualBlock:
                                      "from the block's input to its output channels")
             if tuple(mods[0].stride) != (1, 1):
                 raise core.CoreError(f"downsample has stride {tuple(mods[0].stride)}: only the stride-1 blocks are covered")
-            folds.append(fold_batchnorm(mods[1]))
-            convs.append(mods[0])
+            fold_down = fold_batchnorm(mods[1])
         elif self.residual and c_in != c_out:
             raise core.CoreError(f"residual=True without a downsample needs equal channels, not {c_in} -> {c_out}")
-        dev = torch.device("cuda", device) if not isinstance(device, torch.device) else device
-        self.dtype, self.has_downsample = dtype, down is not None
-        self.packed = [core.conv_pack_weights(c.weight.detach().to(dev), dtype) for c in convs]
-        self.folds = [(sc.to(dev), sh.to(dev)) for sc, sh in folds]
+        dev = _device(device)
+        self.dtype = dtype
+        self.conv1 = ConvBn(block.conv1.weight, fold1, 3, d1, True, dtype, dev)
+        self.conv2 = ConvBn(block.conv2.weight, fold2, 3, d2, True, dtype, dev)
+        self.downsample = ConvBn(mods[0].weight, fold_down, 1, 1, False, dtype, dev) if down is not None else None
+
+    @property
+    def packed(self):
+        """The packed weights of the block's launches: conv1's, conv2's and, if there is one, the downsample's."""
+        return [layer.packed for layer in (self.conv1, self.conv2, self.downsample) if layer is not None]
 
     def __call__(self, x, out_dtype=None):
         """x: [n][channels_in][rows8][cols8] of the block's dtype on its device."""
-        y = core.conv_bn(x, self.packed[0], *self.folds[0], 3, self.dilations[0])
+        y = self.conv1(x)
         res = None
         if self.residual:
-            res = core.conv_bn(x, self.packed[2], *self.folds[2], 1, relu=False) if self.has_downsample else x
-        return core.conv_bn(y, self.packed[1], *self.folds[1], 3, self.dilations[1], residual=res, out_dtype=out_dtype)
+            res = self.downsample(x) if self.downsample is not None else x
+        return self.conv2(y, out_dtype=out_dtype, residual=res)
 
 
 class DrnDilated:

@@ -894,6 +894,22 @@ def _torch_dtype_code(t):
     return codes[t.dtype]
 
 
+def _head_codes(halves_only=False):
+    """{torch dtype: IS_HEAD_* code} of the feature dtypes: float32, float16 and bfloat16, or the two halves alone."""
+    import torch
+    codes = {torch.float32: HEAD_F32, torch.float16: HEAD_F16, torch.bfloat16: HEAD_BF16}
+    if halves_only:
+        del codes[torch.float32]
+    return codes
+
+
+def _f32_on(v, dev):
+    """v, a tensor or an array, as a contiguous float32 tensor on `dev`."""
+    import torch
+    t = v if torch.is_tensor(v) else torch.tensor(np.asarray(v, np.float32))
+    return t.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+
 def _current_stream(dev):
     """The current torch stream of device `dev`, as the C ABI takes it."""
     import torch
@@ -1119,33 +1135,29 @@ def segmentation_head(features, weight, bias, n_classes, rows_power2_segmentatio
         x = torch.from_numpy(np.ascontiguousarray(x)).to(torch.device("cuda", device))
     if not x.is_cuda or x.dim() != 4:
         raise CoreError("features must be a device tensor [n][K][rows8][cols8]")
-    codes = {torch.float32: HEAD_F32, torch.float16: HEAD_F16, torch.bfloat16: HEAD_BF16}
+    codes = _head_codes()
     if x.dtype not in codes:
         raise CoreError(f"features dtype {x.dtype} is none of float32, float16, bfloat16")
     x = x.contiguous()
     dev = x.device
     n, K, Hs, Ws = x.shape
-
-    def f32(v, what):
-        t = v if torch.is_tensor(v) else torch.tensor(np.asarray(v, np.float32))
-        return t.detach().to(device=dev, dtype=torch.float32).contiguous()
-    b = f32(bias, "bias").reshape(-1)
+    b = _f32_on(bias, dev).reshape(-1)
     CH = int(b.numel())
-    w = f32(weight, "weight").reshape(CH, -1)
+    w = _f32_on(weight, dev).reshape(CH, -1)
     if w.shape[1] != K:
         raise CoreError(f"weight holds {w.shape[1]} values per channel, the features have K = {K}")
     P2S = int(rows_power2_segmentation)
     if not want_segmentation:
         want_cnn_out = True
     g = int(canary)
-    pat_i, pat_f = np.int32(0x5A5A5A5A), np.float32(-12345.0)
+    pat_i = np.int32(0x5A5A5A5A)
     with torch.cuda.device(dev):
         named, seg, cnn = {}, None, None
         if want_segmentation:
             full, flat = _guarded(n * Ws * CH * P2S, torch.int32, dev, g, int(pat_i))
             named["segmentation"], seg = (full, pat_i), flat.view(n, Ws, CH, P2S)
         if want_cnn_out:
-            full, flat = _guarded(n * CH * Hs * Ws, torch.float32, dev, g, float(pat_f))
+            full, flat, pat_f = _guarded_float(n * CH * Hs * Ws, torch.float32, dev, g)
             named["cnn_out"], cnn = (full, pat_f), flat.view(n, CH, Hs, Ws)
         a = SegmentationHeadArgs(d_features=x.data_ptr(), dtype=codes[x.dtype], n_images=n, K=K, rows8=Hs, cols8=Ws,
                                  d_weight=w.data_ptr(), d_bias=b.data_ptr(), n_classes=int(n_classes),
@@ -1161,9 +1173,82 @@ def segmentation_head(features, weight, bias, n_classes, rows_power2_segmentatio
     return out[0] if len(out) == 1 else tuple(out)
 
 
-def _half_codes():
+def _conv_pack(prefix, with_kernel, weight, dtype, device):
+    """The body of conv3x3_pack_weights and conv_pack_weights: the entry points `prefix`_packed_bytes and
+    `prefix`_pack_weights of the C ABI, which take the kernel size k of a weight [..][k][k] (with_kernel: f18) or are
+    3x3 alone (f17).  Every refusal is made before the weight goes to a device."""
     import torch
-    return {torch.float16: HEAD_F16, torch.bfloat16: HEAD_BF16}
+    codes = _head_codes(halves_only=True)
+    if dtype not in codes:
+        raise CoreError(f"dtype {dtype} is neither torch.float16 nor torch.bfloat16")
+    w = weight if torch.is_tensor(weight) else torch.from_numpy(np.ascontiguousarray(weight, np.float32))
+    if w.dim() != 4 or (w.shape[2] != w.shape[3] if with_kernel else tuple(w.shape[2:]) != (3, 3)):
+        raise CoreError(f"weight must be [channels_out][channels_in]{'[k][k]' if with_kernel else '[3][3]'}")
+    cout, cin = int(w.shape[0]), int(w.shape[1])
+    k = (int(w.shape[2]),) if with_kernel else ()
+    nbytes = int(getattr(lib(), prefix + "_packed_bytes")(cout, cin, *k, codes[dtype]))
+    if nbytes == 0:
+        raise CoreError(f"{prefix}_packed_bytes refuses channels_out {cout}, channels_in {cin}" +
+                        (f", kernel {k[0]}" if with_kernel else ""))
+    dev = w.device if w.is_cuda else torch.device("cuda", device)
+    w = w.detach().to(device=dev, dtype=torch.float32).contiguous()
+    with torch.cuda.device(dev):
+        packed = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        _check(getattr(lib(), prefix + "_pack_weights")(w.data_ptr(), cout, cin, *k, codes[dtype], packed.data_ptr(),
+                                                        _current_stream(dev)), prefix + "_pack_weights")
+    return packed
+
+
+def _conv_launch(prefix, entry, args_cls, with_kernel, features, packed, scale, shift, kernel, dilation, residual, relu,
+                 out_dtype, canary):
+    """The call sequence of conv3x3_bn_relu and conv_bn: the entry point `entry` of the C ABI with its args class, and
+    `prefix`_packed_bytes for the size of its packed weights.  with_kernel: the entry point has the fields `kernel`
+    and `d_residual` (f18); without it the caller passes kernel 3 and no residual (f17)."""
+    import torch
+    x = features
+    if not torch.is_tensor(x) or not x.is_cuda or x.dim() != 4:
+        raise CoreError("features must be a device tensor [n][channels_in][rows8][cols8]")
+    codes = _head_codes(halves_only=True)
+    if x.dtype not in codes:
+        raise CoreError(f"features dtype {x.dtype} is neither float16 nor bfloat16 (convert fp32 features first)")
+    odt = x.dtype if out_dtype is None else out_dtype
+    if odt != x.dtype and odt != torch.float32:
+        raise CoreError(f"out_dtype {odt} is neither the features' dtype nor float32")
+    same = residual is features
+    x = x.contiguous()
+    dev = x.device
+    n, cin, Hs, Ws = (int(v) for v in x.shape)
+    sc, sh = _f32_on(scale, dev).reshape(-1), _f32_on(shift, dev).reshape(-1)
+    cout = int(sc.numel())
+    if int(sh.numel()) != cout:
+        raise CoreError(f"scale holds {cout} channels, shift {int(sh.numel())}")
+    res = None
+    if residual is not None:
+        res = x if same else residual
+        if not torch.is_tensor(res) or res.device != dev or res.dtype != x.dtype or \
+                tuple(int(v) for v in res.shape) != (n, cout, Hs, Ws):
+            raise CoreError(f"residual must be a {x.dtype} tensor [{n}][{cout}][{Hs}][{Ws}] on the features' device")
+        res = res.contiguous()
+    k = (int(kernel),) if with_kernel else ()
+    own = dict(kernel=k[0], d_residual=res.data_ptr() if res is not None else None) if with_kernel else {}
+    need = int(getattr(lib(), prefix + "_packed_bytes")(cout, cin, *k, codes[x.dtype]))
+    if not torch.is_tensor(packed) or packed.device != dev or packed.dtype != torch.uint8 or \
+            not packed.is_contiguous() or need == 0 or int(packed.numel()) != need:
+        # (the Python packer has the C one's name without "is_")
+        raise CoreError(f"packed must be {prefix[3:]}_pack_weights' uint8 tensor for channels_out {cout}, channels_in "
+                        f"{cin}{f', kernel {kernel}' if with_kernel else ''} and {x.dtype} on the features' device")
+    g = int(canary)
+    with torch.cuda.device(dev):
+        full, flat, pattern = _guarded_float(n * cout * Hs * Ws, odt, dev, g)
+        out = flat.view(n, cout, Hs, Ws)
+        a = args_cls(d_features=x.data_ptr(), dtype=codes[x.dtype], n_images=n, channels_in=cin, channels_out=cout,
+                     rows8=Hs, cols8=Ws, dilation=int(dilation), d_packed=packed.data_ptr(), d_scale=sc.data_ptr(),
+                     d_shift=sh.data_ptr(), relu=int(bool(relu)), d_out=out.data_ptr(),
+                     out_dtype=HEAD_F32 if odt == torch.float32 else codes[x.dtype], **own)
+        _check(getattr(lib(), entry)(ctypes.byref(a), _current_stream(dev)), entry)
+        if g:
+            return out, _guards({"out": (full, pattern)}, g, g)
+    return out
 
 
 def conv3x3_packed_bytes(channels_out, channels_in, dtype):
@@ -1176,23 +1261,7 @@ def conv3x3_pack_weights(weight, dtype, device=0):
     or an array, rounded to torch.float16 or torch.bfloat16 and laid out for is_conv3x3_bn_relu.  Returns a uint8
     device tensor of conv3x3_packed_bytes(...) bytes (on the weight's device if it is a device tensor, else on
     cuda:`device`); enqueued on the current torch stream, once per model."""
-    import torch
-    if dtype not in _half_codes():
-        raise CoreError(f"dtype {dtype} is neither torch.float16 nor torch.bfloat16")
-    w = weight if torch.is_tensor(weight) else torch.from_numpy(np.ascontiguousarray(weight, np.float32))
-    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
-        raise CoreError("weight must be [channels_out][channels_in][3][3]")
-    dev = w.device if w.is_cuda else torch.device("cuda", device)
-    w = w.detach().to(device=dev, dtype=torch.float32).contiguous()
-    cout, cin = int(w.shape[0]), int(w.shape[1])
-    nbytes = conv3x3_packed_bytes(cout, cin, _half_codes()[dtype])
-    if nbytes == 0:
-        raise CoreError(f"is_conv3x3_packed_bytes refuses channels_out {cout}, channels_in {cin}")
-    with torch.cuda.device(dev):
-        packed = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        _check(lib().is_conv3x3_pack_weights(w.data_ptr(), cout, cin, _half_codes()[dtype], packed.data_ptr(),
-                                             _current_stream(dev)), "is_conv3x3_pack_weights")
-    return packed
+    return _conv_pack("is_conv3x3", False, weight, dtype, device)
 
 
 def conv3x3_bn_relu_ptr(stream=0, **fields):
@@ -1214,49 +1283,8 @@ def conv3x3_bn_relu(features, packed, scale, shift, dilation, relu=True, out_dty
     Returns the output [n][channels_out][rows8][cols8] on the features' device, enqueued on the current torch stream.
     canary > 0: the output is allocated with that many guard elements in front and behind, filled with a pattern, and
     {"out": (front, back, pattern)} of numpy copies of the guards is returned second (one synchronisation)."""
-    import torch
-    x = features
-    if not torch.is_tensor(x) or not x.is_cuda or x.dim() != 4:
-        raise CoreError("features must be a device tensor [n][channels_in][rows8][cols8]")
-    codes = _half_codes()
-    if x.dtype not in codes:
-        raise CoreError(f"features dtype {x.dtype} is neither float16 nor bfloat16 (convert fp32 features first)")
-    odt = x.dtype if out_dtype is None else out_dtype
-    if odt != x.dtype and odt != torch.float32:
-        raise CoreError(f"out_dtype {odt} is neither the features' dtype nor float32")
-    x = x.contiguous()
-    dev = x.device
-    n, cin, Hs, Ws = (int(v) for v in x.shape)
-
-    def f32(v):
-        t = v if torch.is_tensor(v) else torch.tensor(np.asarray(v, np.float32))
-        return t.detach().to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
-    sc, sh = f32(scale), f32(shift)
-    cout = int(sc.numel())
-    if int(sh.numel()) != cout:
-        raise CoreError(f"scale holds {cout} channels, shift {int(sh.numel())}")
-    need = conv3x3_packed_bytes(cout, cin, codes[x.dtype])
-    if not torch.is_tensor(packed) or packed.device != dev or packed.dtype != torch.uint8 or \
-            not packed.is_contiguous() or need == 0 or int(packed.numel()) != need:
-        raise CoreError(f"packed must be conv3x3_pack_weights' uint8 tensor for channels_out {cout}, channels_in {cin} "
-                        f"and {x.dtype} on the features' device")
-    g = int(canary)
-    pattern = np.float32(-12345.0) if odt == torch.float32 else np.uint16(0x5A5A)
-    with torch.cuda.device(dev):
-        if odt == torch.float32:
-            full, flat = _guarded(n * cout * Hs * Ws, torch.float32, dev, g, float(pattern))
-        else:   # (the pattern as bits: 0x5A5A is a finite value in both half formats)
-            full, flat = _guarded(n * cout * Hs * Ws, torch.int16, dev, g, int(pattern))
-            flat = flat.view(odt)
-        out = flat.view(n, cout, Hs, Ws)
-        a = Conv3x3Args(d_features=x.data_ptr(), dtype=codes[x.dtype], n_images=n, channels_in=cin, channels_out=cout,
-                        rows8=Hs, cols8=Ws, dilation=int(dilation), d_packed=packed.data_ptr(), d_scale=sc.data_ptr(),
-                        d_shift=sh.data_ptr(), relu=int(bool(relu)), d_out=out.data_ptr(),
-                        out_dtype=HEAD_F32 if odt == torch.float32 else codes[x.dtype])
-        _check(lib().is_conv3x3_bn_relu(ctypes.byref(a), _current_stream(dev)), "is_conv3x3_bn_relu")
-        if g:
-            return out, _guards({"out": (full, pattern)}, g, g)
-    return out
+    return _conv_launch("is_conv3x3", "is_conv3x3_bn_relu", Conv3x3Args, False, features, packed, scale, shift, 3,
+                        dilation, None, relu, out_dtype, canary)
 
 
 def conv_packed_bytes(channels_out, channels_in, kernel, dtype):
@@ -1270,23 +1298,7 @@ def conv_pack_weights(weight, dtype, device=0):
     1, a tensor or an array, rounded to torch.float16 or torch.bfloat16 and laid out for is_conv_bn.  Returns a uint8
     device tensor of conv_packed_bytes(...) bytes (on the weight's device if it is a device tensor, else on
     cuda:`device`); enqueued on the current torch stream, once per model."""
-    import torch
-    if dtype not in _half_codes():
-        raise CoreError(f"dtype {dtype} is neither torch.float16 nor torch.bfloat16")
-    w = weight if torch.is_tensor(weight) else torch.from_numpy(np.ascontiguousarray(weight, np.float32))
-    if w.dim() != 4 or w.shape[2] != w.shape[3]:
-        raise CoreError("weight must be [channels_out][channels_in][k][k]")
-    dev = w.device if w.is_cuda else torch.device("cuda", device)
-    w = w.detach().to(device=dev, dtype=torch.float32).contiguous()
-    cout, cin, k = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
-    nbytes = conv_packed_bytes(cout, cin, k, _half_codes()[dtype])
-    if nbytes == 0:
-        raise CoreError(f"is_conv_packed_bytes refuses channels_out {cout}, channels_in {cin}, kernel {k}")
-    with torch.cuda.device(dev):
-        packed = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        _check(lib().is_conv_pack_weights(w.data_ptr(), cout, cin, k, _half_codes()[dtype], packed.data_ptr(),
-                                          _current_stream(dev)), "is_conv_pack_weights")
-    return packed
+    return _conv_pack("is_conv", True, weight, dtype, device)
 
 
 def conv_bn_ptr(stream=0, **fields):
@@ -1309,58 +1321,8 @@ def conv_bn(features, packed, scale, shift, kernel, dilation=1, residual=None, r
 
     Returns the output [n][channels_out][rows8][cols8] on the features' device, enqueued on the current torch stream.
     canary > 0: as conv3x3_bn_relu, {"out": (front, back, pattern)} is returned second (one synchronisation)."""
-    import torch
-    x = features
-    if not torch.is_tensor(x) or not x.is_cuda or x.dim() != 4:
-        raise CoreError("features must be a device tensor [n][channels_in][rows8][cols8]")
-    codes = _half_codes()
-    if x.dtype not in codes:
-        raise CoreError(f"features dtype {x.dtype} is neither float16 nor bfloat16 (convert fp32 features first)")
-    odt = x.dtype if out_dtype is None else out_dtype
-    if odt != x.dtype and odt != torch.float32:
-        raise CoreError(f"out_dtype {odt} is neither the features' dtype nor float32")
-    same = residual is features
-    x = x.contiguous()
-    dev = x.device
-    n, cin, Hs, Ws = (int(v) for v in x.shape)
-
-    def f32(v):
-        t = v if torch.is_tensor(v) else torch.tensor(np.asarray(v, np.float32))
-        return t.detach().to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
-    sc, sh = f32(scale), f32(shift)
-    cout = int(sc.numel())
-    if int(sh.numel()) != cout:
-        raise CoreError(f"scale holds {cout} channels, shift {int(sh.numel())}")
-    res = None
-    if residual is not None:
-        res = x if same else residual
-        if not torch.is_tensor(res) or res.device != dev or res.dtype != x.dtype or \
-                tuple(int(v) for v in res.shape) != (n, cout, Hs, Ws):
-            raise CoreError(f"residual must be a {x.dtype} tensor [{n}][{cout}][{Hs}][{Ws}] on the features' device")
-        res = res.contiguous()
-    need = conv_packed_bytes(cout, cin, int(kernel), codes[x.dtype])
-    if not torch.is_tensor(packed) or packed.device != dev or packed.dtype != torch.uint8 or \
-            not packed.is_contiguous() or need == 0 or int(packed.numel()) != need:
-        raise CoreError(f"packed must be conv_pack_weights' uint8 tensor for channels_out {cout}, channels_in {cin}, "
-                        f"kernel {kernel} and {x.dtype} on the features' device")
-    g = int(canary)
-    pattern = np.float32(-12345.0) if odt == torch.float32 else np.uint16(0x5A5A)
-    with torch.cuda.device(dev):
-        if odt == torch.float32:
-            full, flat = _guarded(n * cout * Hs * Ws, torch.float32, dev, g, float(pattern))
-        else:   # (the pattern as bits: 0x5A5A is a finite value in both half formats)
-            full, flat = _guarded(n * cout * Hs * Ws, torch.int16, dev, g, int(pattern))
-            flat = flat.view(odt)
-        out = flat.view(n, cout, Hs, Ws)
-        a = ConvBnArgs(d_features=x.data_ptr(), dtype=codes[x.dtype], n_images=n, channels_in=cin, channels_out=cout,
-                       rows8=Hs, cols8=Ws, kernel=int(kernel), dilation=int(dilation), d_packed=packed.data_ptr(),
-                       d_scale=sc.data_ptr(), d_shift=sh.data_ptr(),
-                       d_residual=res.data_ptr() if res is not None else None, relu=int(bool(relu)),
-                       d_out=out.data_ptr(), out_dtype=HEAD_F32 if odt == torch.float32 else codes[x.dtype])
-        _check(lib().is_conv_bn(ctypes.byref(a), _current_stream(dev)), "is_conv_bn")
-        if g:
-            return out, _guards({"out": (full, pattern)}, g, g)
-    return out
+    return _conv_launch("is_conv", "is_conv_bn", ConvBnArgs, True, features, packed, scale, shift, kernel, dilation,
+                        residual, relu, out_dtype, canary)
 
 
 def _with_reserved(cls, fields):
@@ -1380,6 +1342,19 @@ def _guarded(numel, dtype, dev, g, pattern):
         return None, torch.empty((numel,), dtype=dtype, device=dev)
     full = torch.full((numel + 2 * g,), pattern, dtype=dtype, device=dev)
     return full, full[g: g + numel]
+
+
+def _guarded_float(numel, dtype, dev, g):
+    """_guarded for an output of float32 or of a half dtype, with the pattern of each: (the whole allocation or None,
+    the view of the numel elements in `dtype`, the pattern as _guards takes it).  A half's pattern is given as its 16
+    bits, 0x5A5A, a finite value in both half formats, so the allocation is int16 and the view reinterprets it."""
+    import torch
+    if dtype == torch.float32:
+        pattern = np.float32(-12345.0)
+        return _guarded(numel, dtype, dev, g, float(pattern)) + (pattern,)
+    pattern = np.uint16(0x5A5A)
+    full, flat = _guarded(numel, torch.int16, dev, g, int(pattern))
+    return full, flat.view(dtype), pattern
 
 
 def _guards(named, g, g_scratch):
@@ -1424,7 +1399,7 @@ def segmentation_head_backward(features, weight, cnn_out, grad_out, n_classes, w
     x = features
     if not torch.is_tensor(x) or not x.is_cuda or x.dim() != 4:
         raise CoreError("features must be a device tensor [n][K][rows8][cols8]")
-    codes = {torch.float32: HEAD_F32, torch.float16: HEAD_F16, torch.bfloat16: HEAD_BF16}
+    codes = _head_codes()
     if x.dtype not in codes:
         raise CoreError(f"features dtype {x.dtype} is none of float32, float16, bfloat16")
     x = x.detach().contiguous()
@@ -1451,22 +1426,16 @@ def segmentation_head_backward(features, weight, cnn_out, grad_out, n_classes, w
     with torch.cuda.device(dev):
         nbytes = _scratch_or_raise(segmentation_head_backward_scratch_bytes,
                                    dict(n_images=n, K=K, rows8=Hs, cols8=Ws, channels=CH))
-        pat_f = np.float32(-12345.0)
-        pat_x = {torch.float32: pat_f, torch.float16: np.uint16(0x5A5A), torch.bfloat16: np.uint16(0x5A5A)}[x.dtype]
         named, out = {}, {}
         ptr = {"features": None, "weight": None, "bias": None, "logits": None}
-        for name, want, numel, view, dtype, pat in (
-                ("features", want_features, n * K * Hs * Ws, (n, K, Hs, Ws), x.dtype, pat_x),
-                ("weight", want_weight, CH * K, (CH, K), torch.float32, pat_f),
-                ("bias", want_bias, CH, (CH,), torch.float32, pat_f),
-                ("logits", want_logits, n * frame, shape, torch.float32, pat_f)):
+        for name, want, numel, view, dtype in (
+                ("features", want_features, n * K * Hs * Ws, (n, K, Hs, Ws), x.dtype),
+                ("weight", want_weight, CH * K, (CH, K), torch.float32),
+                ("bias", want_bias, CH, (CH,), torch.float32),
+                ("logits", want_logits, n * frame, shape, torch.float32)):
             if not want:
                 continue
-            if g and dtype != torch.float32:   # (the guard pattern of a half as its 16 bits)
-                full = torch.full((numel + 2 * g,), int(pat), dtype=torch.int16, device=dev).view(dtype)
-                t = full[g: g + numel]
-            else:
-                full, t = _guarded(numel, dtype, dev, g, float(pat))
+            full, t, pat = _guarded_float(numel, dtype, dev, g)
             named[name] = (full, pat)
             out[name] = t.view(view)
             ptr[name] = t.data_ptr()
@@ -1514,11 +1483,11 @@ def _semantic_nll(entry, args_cls, scratch_fn, scratch_more, count, target_field
     y, y_stride = _frame_planes(y.detach(), n_classes)
     t, own = target_fields(n, Hs, Ws, dev)
     g = int(canary)
-    pat_f, (count_dtype, pat_i) = np.float32(-12345.0), count
+    count_dtype, pat_i = count
     with torch.cuda.device(dev):
         nbytes = _scratch_or_raise(scratch_fn, dict(n_images=n, rows8=Hs, cols8=Ws, **scratch_more))
         named = {}
-        lfull, loss = _guarded(1, torch.float32, dev, g, float(pat_f))
+        lfull, loss, pat_f = _guarded_float(1, torch.float32, dev, g)
         vfull, valid = _guarded(1, count_dtype, dev, g, int(pat_i))
         bfull, bad = _guarded(1, count_dtype, dev, g, int(pat_i))
         named.update(loss=(lfull, pat_f), valid_count=(vfull, pat_i), bad_count=(bfull, pat_i))
@@ -1531,7 +1500,7 @@ def _semantic_nll(entry, args_cls, scratch_fn, scratch_more, count, target_field
                                 "planes are contiguous")
             g_stride = gr.stride(0) if n > 1 else n_classes * Hs * Ws
         elif grad:
-            gfull, flat = _guarded(n * n_classes * Hs * Ws, torch.float32, dev, g, float(pat_f))
+            gfull, flat, _ = _guarded_float(n * n_classes * Hs * Ws, torch.float32, dev, g)
             named["grad"] = (gfull, pat_f)
             gr, g_stride = flat.view(n, n_classes, Hs, Ws), n_classes * Hs * Ws
         gs = (g + 15) // 16 * 16

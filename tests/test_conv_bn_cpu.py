@@ -2,8 +2,10 @@
 is_conv_packed_bytes, the refusals of is_conv_bn and is_conv_pack_weights (all made before the device is touched), the
 refusals of cnn.ResidualBlock (made before anything is packed), and the reference of tests/conv_bn_reference.py pinned
 against BasicBlock-shaped torch modules, against the claim that its exact inputs are exact, and against three wrong
-epilogues that its bound has to catch."""
+epilogues that its bound has to catch; the signatures of the Python surface of f17 and f18, and the packers' refusals
+(made before a device is touched)."""
 import ctypes
+import inspect
 import os
 import re
 import subprocess
@@ -341,6 +343,52 @@ def _with_downsample(down):
     block = Block(32, 64, downsample=True).eval()
     block.downsample = down.eval()
     return block
+
+
+# ---- the Python surface of f17 and f18: the signatures, and the packers' refusals ahead of the device ----
+
+SIGNATURES = [
+    (core.conv3x3_packed_bytes, "(channels_out, channels_in, dtype)"),
+    (core.conv3x3_pack_weights, "(weight, dtype, device=0)"),
+    (core.conv3x3_bn_relu_ptr, "(stream=0, **fields)"),
+    (core.conv3x3_bn_relu, "(features, packed, scale, shift, dilation, relu=True, out_dtype=None, canary=0)"),
+    (core.conv_packed_bytes, "(channels_out, channels_in, kernel, dtype)"),
+    (core.conv_pack_weights, "(weight, dtype, device=0)"),
+    (core.conv_bn_ptr, "(stream=0, **fields)"),
+    (core.conv_bn, "(features, packed, scale, shift, kernel, dilation=1, residual=None, relu=True, out_dtype=None, "
+                   "canary=0)"),
+    (cnn.ConvBnRelu.__init__, "(self, conv, bn, dtype=torch.bfloat16, relu=True, device=0)"),
+    (cnn.ResidualBlock.__init__, "(self, block, dtype=torch.bfloat16, device=0)"),
+    (cnn.DrnTail.__init__, "(self, layer7, layer8, seg, n_classes, rows_power2_segmentation, clamp=None, "
+                           "dtype=torch.bfloat16, device=0)"),
+    (cnn.DrnDilated.__init__, "(self, layer5, layer6, layer7, layer8, seg, n_classes, rows_power2_segmentation, "
+                              "clamp=None, dtype=torch.bfloat16, device=0)"),
+]
+
+
+@pytest.mark.parametrize("fn, signature", SIGNATURES, ids=[fn.__qualname__ for fn, _ in SIGNATURES])
+def test_public_signatures_are_pinned(fn, signature):
+    """Parameter names, order and defaults of the eight conv functions and of the four layer classes."""
+    assert str(inspect.signature(fn)) == signature
+
+
+@pytest.mark.parametrize("pack, weight, dtype, message", [
+    (core.conv3x3_pack_weights, (32, 16, 5, 5), torch.bfloat16, r"\[channels_out\]\[channels_in\]\[3\]\[3\]"),
+    (core.conv3x3_pack_weights, (32, 16, 3, 3), torch.float32, "neither torch.float16 nor torch.bfloat16"),
+    # (a 5x5 weight is [k][k]: is_conv_packed_bytes, a host function, refuses its k)
+    (core.conv_pack_weights, (32, 16, 5, 5), torch.bfloat16, "is_conv_packed_bytes refuses .* kernel 5"),
+    (core.conv_pack_weights, (32, 16, 3, 5), torch.bfloat16, r"\[channels_out\]\[channels_in\]\[k\]\[k\]"),
+    (core.conv_pack_weights, (32, 16, 3, 3), torch.float32, "neither torch.float16 nor torch.bfloat16"),
+], ids=["f17-5x5", "f17-float32", "f18-5x5", "f18-3x5", "f18-float32"])
+def test_pack_refusals_come_before_the_device(pack, weight, dtype, message, monkeypatch):
+    """A CPU weight that a packer refuses is refused before it is copied to a device or a stream is asked for."""
+    def touched(*args, **kwargs):
+        raise AssertionError("the device was touched before the refusal")
+    w = torch.zeros(weight)
+    monkeypatch.setattr(torch.Tensor, "to", touched)
+    monkeypatch.setattr(core, "_current_stream", touched)
+    with pytest.raises(core.CoreError, match=message):
+        pack(w, dtype)
 
 
 def _strided_downsample():

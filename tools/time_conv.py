@@ -1,22 +1,29 @@
-"""The residual blocks of the backbone (f18: is_conv_bn, core.conv_bn, cnn.ResidualBlock) against what they replace
-and against themselves, on the same device tensors (GPU box).
+"""The backbone's convolutions on the device (f17: is_conv3x3_bn_relu, core.conv3x3_bn_relu; f18: is_conv_bn,
+core.conv_bn, cnn.ResidualBlock) against what they replace and against themselves, on the same device tensors (GPU
+box).
 
 Prints one JSON line (progress on stderr).  Every timing is ms per batch by device events around the enqueued work,
 median of --iters (at least 10) with min and max, every arm of a comparison warmed up first and the arms then
-ALTERNATING inside one loop.  Parts (--parts, comma-separated):
+ALTERNATING inside one loop.  The torch arms are the same work in the same dtype on contiguous (NCHW) and on
+channels_last tensors; the faster of the two is the comparison (`faster` is false where torch is as fast or faster:
+"not faster").  `mfma_floor_ms` is a part's FLOP over the dense half MFMA rate of --cus compute units x 4 SIMDs x 1024
+FLOP per clock at --mhz (take the clock from a counter run; the default is the nominal 2400).  Parts (--parts,
+comma-separated), for fp16 and bf16 features [n][.][rows8][cols8] with half output:
+- tail: core.conv3x3_bn_relu (one launch, --C channels) for dilation 2 (layer7) and 1 (layer8) against F.conv2d +
+  F.batch_norm (eval) + F.relu.  `dp_ints_differing` counts, on a batch of --dp-n frames, the DP input ints
+  (core.segmentation_head of the layer8 output of layer7) that differ between this path and the torch sequences in
+  front of the same head.
 - residual: core.conv_bn (3x3, dilation 2, --C channels) with a residual operand against the same call without one;
   `residual_gb` is the extra operand's bytes.
-- 1x1: the downsample launch (core.conv_bn, kernel 1, no ReLU) at 128 -> 256 and 256 -> 512 channels against torch
-  F.conv2d + F.batch_norm (eval) in the same dtype, contiguous and channels_last; the faster of the two is the
-  comparison (`faster` is false where torch is as fast or faster: "not faster").
+- 1x1: the downsample launch (core.conv_bn, kernel 1, no ReLU) at 128 -> 256 and 256 -> 512 channels against F.conv2d +
+  F.batch_norm (eval).
 - layers: layer5 + layer6 of drn_d_22 (two BasicBlocks each, 128 -> 256 -> 512, dilations 2 and 4, the first block of
-  each with a downsample) through cnn.ResidualBlock (10 launches) against the torch modules in the same dtype,
-  contiguous and channels_last.  `tflop` is computed from the shape; `mfma_floor_ms` is that over the dense half MFMA
-  rate of --cus compute units x 4 SIMDs x 1024 FLOP per clock at --mhz.
---no-torch leaves the torch arms out.  torch's first convolution of a shape takes 30 - 160 s: run the dtypes, and if
-need be the parts, in separate commands.
+  each with a downsample) through cnn.ResidualBlock (10 launches) against the torch modules.
+--no-torch leaves the torch arms out (and alone allows fewer than 10 iterations, for a counter run).  torch's first
+convolution of a shape takes 30 - 160 s: run the dtypes, and if need be the parts, in separate commands.
 
-    python tools/time_resblock.py [--n 64 --rows8 128 --cols8 256 --iters 20 --dtypes bf16 --parts residual,1x1,layers]
+    python tools/time_conv.py [--n 64 --C 512 --rows8 128 --cols8 256 --iters 20 --mhz 2400 --cus 256 --dtypes fp16,bf16
+                               --parts tail,residual,1x1,layers --no-torch]
 """
 import argparse
 import copy
@@ -37,24 +44,26 @@ def mmm(ts, digits=3):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=64)
-    ap.add_argument("--C", type=int, default=512, help="channels of the `residual` part")
+    ap.add_argument("--C", type=int, default=512, help="channels of the `tail` and `residual` parts")
     ap.add_argument("--rows8", type=int, default=128)
     ap.add_argument("--cols8", type=int, default=256)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--mhz", type=float, default=2400.0)
     ap.add_argument("--cus", type=int, default=256)
+    ap.add_argument("--dp-n", type=int, default=0, help="0: the whole batch (a shape the library is already tuned for)")
     ap.add_argument("--dtypes", default="fp16,bf16", help="comma-separated subset of fp16,bf16")
-    ap.add_argument("--parts", default="residual,1x1,layers", help="comma-separated subset of residual,1x1,layers")
+    ap.add_argument("--parts", default="tail,residual,1x1,layers",
+                    help="comma-separated subset of tail,residual,1x1,layers")
     ap.add_argument("--no-torch", action="store_true", help="time the library's launches alone")
     a = ap.parse_args()
-    if a.iters < 10:
-        sys.exit("time_resblock.py: --iters must be at least 10")
+    if a.iters < 10 and not a.no_torch:
+        sys.exit("time_conv.py: --iters must be at least 10")
     import numpy as np
     import torch
     import torch.nn.functional as F
     from instance_stixels_amd import cnn, core
     if not torch.cuda.is_available():
-        sys.exit("time_resblock.py needs a GPU")
+        sys.exit("time_conv.py needs a GPU")
     dev = torch.device("cuda", 0)
     n, Hs, Ws = a.n, a.rows8, a.cols8
     parts = a.parts.split(",")
@@ -78,6 +87,13 @@ def main():
 
     def weight(cout, cin, k):
         return torch.randn((cout, cin, k, k), device=dev) * (2.0 / (k * k * cout)) ** 0.5
+
+    def torch_conv_bn(x, w, d, bn, relu):
+        y = F.batch_norm(F.conv2d(x, w, padding=d * (w.shape[2] // 2), dilation=d), *bn, False, 0.0, eps)
+        return F.relu(y) if relu else y
+
+    def channels_last(*ts):
+        return [t.contiguous(memory_format=torch.channels_last) for t in ts]
 
     def measure(label, arms):
         for arm, fn in arms.items():                # warm-up of every arm (a library's first call may tune itself)
@@ -135,6 +151,43 @@ def main():
     for name, dtype in (("fp16", torch.float16), ("bf16", torch.bfloat16)):
         if name not in a.dtypes.split(","):
             continue
+        if "tail" in parts:
+            C = a.C
+            tflop = 2.0 * 9 * C * C * n * Hs * Ws / 1e12
+            out.update(shape=[n, C, Hs, Ws], tflop_per_layer=round(tflop, 3), mfma_floor_ms=round(floor_ms(tflop), 3))
+            x = torch.randn((n, C, Hs, Ws), device=dev).abs_().to(dtype).contiguous()
+            w32, stats = weight(C, C, 3), bn_stats(C)
+            packed, (scale, shift) = core.conv3x3_pack_weights(w32, dtype), fold(*stats)
+            if not a.no_torch:
+                wd, bn = w32.to(dtype), [t.to(dtype) for t in stats]
+                x_cl, w_cl = channels_last(x, wd)
+            for d in (2, 1):
+                arms = {"new": lambda: core.conv3x3_bn_relu(x, packed, scale, shift, d)}
+                if not a.no_torch:
+                    arms["torch_contiguous"] = lambda: torch_conv_bn(x, wd, d, bn, True)
+                    arms["torch_channels_last"] = lambda: torch_conv_bn(x_cl, w_cl, d, bn, True)
+                row, med = measure("%s dilation %d" % (name, d), arms)
+                row.update(new_tflops=round(tflop / (med["new"] * 1e-3), 1),
+                           new_share_of_mfma_floor=round(floor_ms(tflop) / med["new"], 3))
+                against_torch(row, med)
+                out["%s_d%d" % (name, d)] = row
+                note(name, "dilation", d, json.dumps(row))
+            if not a.no_torch:
+                # the DP input of a small batch through both paths: layer7 (d = 2), layer8 (d = 1), the same head
+                m = min(a.dp_n, n) if a.dp_n > 0 else n
+                P2S = 1 << Hs.bit_length()
+                head_w, head_b = torch.randn((21, C), device=dev) * (2.0 / 21) ** 0.5, torch.zeros(21, device=dev)
+                xs, xs_cl = x[:m].contiguous(), x_cl[:m]
+                seg_new = core.segmentation_head(core.conv3x3_bn_relu(core.conv3x3_bn_relu(xs, packed, scale, shift, 2),
+                                                                      packed, scale, shift, 1), head_w, head_b, 19, P2S)
+                diff = {}
+                for arm, (xx, ww) in (("torch_contiguous", (xs, wd)), ("torch_channels_last", (xs_cl, w_cl))):
+                    y = torch_conv_bn(torch_conv_bn(xx, ww, 2, bn, True), ww, 1, bn, True).contiguous()
+                    diff[arm] = int((core.segmentation_head(y, head_w, head_b, 19, P2S) != seg_new).sum().item())
+                out[name + "_dp_ints_differing"] = dict(diff, ints=seg_new.numel(), frames=m)
+                del x_cl
+            del x, packed
+            torch.cuda.empty_cache()
         if "residual" in parts:
             C = a.C
             x = torch.randn((n, C, Hs, Ws), device=dev).abs_().to(dtype)
@@ -160,9 +213,9 @@ def main():
                 arms = {"new": lambda: core.conv_bn(x, packed, scale, shift, 1, relu=False)}
                 if not a.no_torch:
                     wd, bn = w32.to(dtype), [t.to(dtype) for t in stats]
-                    x_cl, w_cl = x.contiguous(memory_format=torch.channels_last), wd.contiguous(memory_format=torch.channels_last)
-                    arms["torch_contiguous"] = lambda: F.batch_norm(F.conv2d(x, wd), *bn, False, 0.0, eps)
-                    arms["torch_channels_last"] = lambda: F.batch_norm(F.conv2d(x_cl, w_cl), *bn, False, 0.0, eps)
+                    x_cl, w_cl = channels_last(x, wd)
+                    arms["torch_contiguous"] = lambda: torch_conv_bn(x, wd, 1, bn, False)
+                    arms["torch_channels_last"] = lambda: torch_conv_bn(x_cl, w_cl, 1, bn, False)
                 row, med = measure("%s 1x1 %d->%d" % (name, cin, cout), arms)
                 gb = n * Hs * Ws * (cin + cout) * 2 / 1e9
                 row.update(compulsory_gb=round(gb, 3), new_gb_per_s=round(gb / (med["new"] * 1e-3), 1),
@@ -191,7 +244,7 @@ def main():
             if not a.no_torch:
                 seq = torch.nn.Sequential(*blocks).to(device=dev, dtype=dtype).eval()
                 seq_cl = copy.deepcopy(seq).to(memory_format=torch.channels_last).eval()
-                x_cl = x.contiguous(memory_format=torch.channels_last)
+                x_cl, = channels_last(x)
                 arms["torch_contiguous"] = lambda: seq(x)
                 arms["torch_channels_last"] = lambda: seq_cl(x_cl)
             with torch.no_grad():
