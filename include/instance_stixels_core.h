@@ -1306,6 +1306,63 @@ int is_conv_pack_weights(const float* d_weight, int channels_out, int channels_i
  * the output's. */
 int is_conv_bn(const is_conv_bn_args* args, void* stream);
 
+/* ---- f19: the backbone's downsampling layers, the same launch with stride 1 or 2 (is_k_conv3x3.hip) -------------------
+ * layer2, layer3 and layer4 of drn_d_22 (tools/CNN_training/models/drn.py:161-167; layers [1, 1, 2, 2, 2, 2, 1, 1],
+ * channels (16, 32, 64, 128, 256, 512, 512, 512)): layer2 is Conv2d(16, 32, 3, stride = 2, padding = 1, bias = False) +
+ * BatchNorm2d + ReLU (_make_conv_layers, drn.py:223-233), layer3 and layer4 are two BasicBlocks each (_make_layer(...,
+ * new_level = True), drn.py:199-221, dilation (1, 1)), 32 -> 64 -> 128 channels, whose first block has stride 2 in its
+ * conv1 (3x3) and in its downsample (1x1).  Every other convolution of the three layers is a stride-1, dilation-1 3x3
+ * that is_conv_bn runs.  is_conv_bn_args cannot grow and its reserved fields stay refused, so this entry point stands
+ * beside it as f18's stands beside f17's: is_conv_bn is this call with stride = 1, the same launch and the same bytes,
+ * and layer2 -> ... -> layer8 -> head is 24 launches of this library with nothing in between, from layer1's output at
+ * full resolution to the DP's input.  These layers are not at 1/8 resolution: the extents are rows_in, cols_in.
+ *
+ *   Output.      stride 1: rows_in x cols_in.  stride 2: rows_out = (rows_in + 1) / 2 by cols_out = (cols_in + 1) / 2 in
+ *                integer division -- torch's floor((H + 2 p - d (k - 1) - 1) / 2) + 1, which is ceil(H / 2) both for
+ *                (k = 3, p = 1, d = 1) and for (k = 1, p = 0).  The output extents are derived, not fields.
+ *   Summation.   stride 2, kernel 3: a[n][co][y][x] = sum over the 9 taps and all channels_in of
+ *                w[co][ci][ky][kx] * x[n][ci][2 y + ky - 1][2 x + kx - 1];  kernel 1: of w[co][ci] * x[n][ci][2 y][2 x].
+ *                A tap outside the image contributes nothing: with an even extent the bottom / right padding is never
+ *                read, with an odd extent it is.  stride 2 means dilation 1 (the reference has no other).
+ *   Operands, order, epilogue, determinism and non-finite values: is_conv_bn's, unchanged.  One accumulator chain per
+ *                output element in increasing 16-channel chunk, then increasing tap 3 ky + kx; no atomics; the three
+ *                fp32 steps v = fmaf(scale[co], a, shift[co]), v + (float)residual[n][co][y][x], max(v, 0), then the
+ *                store.  Every output index, every predicate and the residual use the OUTPUT's extents.
+ *   Loads.       No address outside the features' n_images * channels_in * rows_in * cols_in elements is loaded from.
+ *
+ * Weights: the packed layout does not depend on the stride; is_conv_pack_weights and is_conv_packed_bytes serve.
+ *
+ * Zero-initialise, then set the fields.  Fields as in is_conv_bn_args, and
+ *   d_features          [n_images][channels_in][rows_in][cols_in];  rows_in, cols_in in [1, 32767]
+ *   stride              1 or 2;  2 needs dilation 1
+ *   d_residual          NULL, or [n_images][channels_out][rows_out][cols_out] of `dtype` (the OUTPUT's shape).  With
+ *                       stride 2 it cannot be the features (the shapes differ)
+ *   d_out               [n_images][channels_out][rows_out][cols_out]; its bytes must overlap neither the features' nor
+ *                       the residual's, each taken at its own size
+ *   reserved            0 */
+typedef struct is_conv_bn_stride_args {
+    const void* d_features;
+    int dtype; /* IS_HEAD_F16 | IS_HEAD_BF16 */
+    int n_images, channels_in, channels_out, rows_in, cols_in;
+    int kernel;   /* 3 or 1 */
+    int stride;   /* 1 or 2 */
+    int dilation; /* kernel 3: [1, 8], 1 with stride 2;  kernel 1: must be 1 */
+    const void* d_packed;
+    const float* d_scale;
+    const float* d_shift;
+    const void* d_residual; /* NULL, or [n][channels_out][rows_out][cols_out] of `dtype` */
+    int relu;
+    void* d_out;
+    int out_dtype;
+    int reserved[4]; /* 0 */
+} is_conv_bn_stride_args;
+
+/* One launch on `stream`, asynchronous and stream-ordered; no allocation, copy or synchronisation.  IS_EINVAL, with
+ * the reason in is_last_error() and before the device is touched, for everything is_conv_bn refuses (the extents are
+ * named rows_in and cols_in), a stride outside {1, 2}, stride 2 with dilation != 1, stride 2 with d_residual ==
+ * d_features, and, last, a non-zero reserved field. */
+int is_conv_bn_stride(const is_conv_bn_stride_args* args, void* stream);
+
 /* ---- f9: per-instance objects and their contours (is_k_objects.hip) ------------------------------------------------
  * What the reference's consumers reduce on the host from the per-stixel output: the top-down view
  * (tools/visualization/clustering_visualization.py:563-792: per instance and column the closest stixel, connected

@@ -11,7 +11,14 @@ drn.py:199-221, as drn.py:168-172): ResidualBlock is two launches of core.conv_b
 DrnDilated is layer5 -> layer6 -> DrnTail, the output of layer4 in and the DP's input out.
 
 Every convolution here is one ConvBn: the packed weights, the folded BatchNorm and the launch's kernel, dilation and
-relu.  The tail's ConvBnRelu is a ConvBn built from (Conv2d, BatchNorm2d); a ResidualBlock holds two or three."""
+relu.  The tail's ConvBnRelu is a ConvBn built from (Conv2d, BatchNorm2d); a ResidualBlock holds two or three.
+
+f19 puts the downsampling layers in front of that: layer2 (one stride-2 conv + BN + ReLU, drn.py:161-163) and the
+BasicBlocks of layer3 and layer4 (drn.py:164-167), whose first block has stride 2 in conv1 and in the downsample.  A
+ConvBn carries its stride and launches core.conv_bn_stride (at stride 1 the bytes of core.conv_bn); the classes that
+accept stride 2 are StridedConvBnRelu and StridedResidualBlock, which differ from ConvBnRelu and ResidualBlock in the
+strides they allow and in nothing else.  DrnDownsampling is layer2 -> layer3 -> layer4 -> DrnDilated: the output of
+layer1 at full resolution in, the DP's input out, 24 launches."""
 import torch
 
 from . import core
@@ -41,42 +48,56 @@ def _device(device):
     return device if isinstance(device, torch.device) else torch.device("cuda", device)
 
 
-def _dilated3x3(conv, name):
-    """The dilation of `conv` if it is the reference's 3x3: stride 1, padding = dilation (the same in both directions),
-    one group, no bias."""
+def _dilated3x3(conv, name, strides=(1,)):
+    """The dilation of `conv` if it is the reference's 3x3: padding = dilation (the same in both directions), one
+    group, no bias, and a stride (the same in both directions) out of `strides`; stride 2 needs dilation 1."""
     if not isinstance(conv, torch.nn.Conv2d) or tuple(conv.kernel_size) != (3, 3) or \
             tuple(conv.dilation) != (conv.dilation[0],) * 2 or tuple(conv.padding) != tuple(conv.dilation) or \
             conv.groups != 1 or conv.bias is not None or getattr(conv, "padding_mode", "zeros") != "zeros":
         raise core.CoreError(f"{name} must be Conv2d(kernel_size=3, padding=dilation, groups=1, bias=False)")
-    if tuple(conv.stride) != (1, 1):
-        raise core.CoreError(f"{name} has stride {tuple(conv.stride)}: only the stride-1 layers (layer5 on) are covered")
+    if tuple(conv.stride) not in [(s, s) for s in strides]:
+        raise core.CoreError(f"{name} has stride {tuple(conv.stride)}: " +
+                             ("only the stride-1 layers (layer5 on) are covered" if tuple(strides) == (1,) else
+                              f"only the strides {tuple(strides)} are covered"))
+    if conv.stride[0] == 2 and conv.dilation[0] != 1:
+        raise core.CoreError(f"{name} has stride 2 with dilation {conv.dilation[0]}: stride 2 needs dilation 1")
     return int(conv.dilation[0])
 
 
 class ConvBn:
-    """A packed convolution and its folded BatchNorm on a device, one launch of core.conv_bn per call: `weight` is
-    conv.weight [channels_out][channels_in][kernel][kernel], `fold` the (scale, shift) of fold_batchnorm.  Nothing is
-    checked here beyond what core.conv_pack_weights checks: the callers check and fold first, then build this."""
+    """A packed convolution and its folded BatchNorm on a device, one launch of core.conv_bn_stride per call (at stride
+    1 core.conv_bn's launch and bytes): `weight` is conv.weight [channels_out][channels_in][kernel][kernel], `fold` the
+    (scale, shift) of fold_batchnorm.  Nothing is checked here beyond what core.conv_pack_weights checks: the callers
+    check and fold first, then build this."""
 
-    def __init__(self, weight, fold, kernel, dilation, relu, dtype, dev):
+    def __init__(self, weight, fold, kernel, dilation, relu, dtype, dev, stride=1):
         self.kernel, self.dilation, self.relu, self.dtype = int(kernel), int(dilation), bool(relu), dtype
+        self.stride = int(stride)
         self.packed = core.conv_pack_weights(weight.detach().to(dev), dtype)
         self.scale, self.shift = fold[0].to(dev), fold[1].to(dev)
 
     def __call__(self, features, out_dtype=None, residual=None):
-        return core.conv_bn(features, self.packed, self.scale, self.shift, self.kernel, self.dilation,
-                            residual=residual, relu=self.relu, out_dtype=out_dtype)
+        return core.conv_bn_stride(features, self.packed, self.scale, self.shift, self.kernel, self.stride,
+                                   self.dilation, residual=residual, relu=self.relu, out_dtype=out_dtype)
 
 
 class ConvBnRelu(ConvBn):
     """One layer of the tail: the packed weights of `conv` in `dtype` and the fold of `bn`, on `device`.  conv must be
     the reference's: 3x3, stride 1, padding = dilation (the same in both directions), one group, no bias."""
 
+    strides = (1,)     # the strides of conv that the class accepts
+
     def __init__(self, conv, bn, dtype=torch.bfloat16, relu=True, device=0):
-        d = _dilated3x3(conv, "conv")
+        d = _dilated3x3(conv, "conv", self.strides)
         if bn.num_features != conv.out_channels:
             raise core.CoreError(f"bn has {bn.num_features} channels, conv {conv.out_channels}")
-        super().__init__(conv.weight, fold_batchnorm(bn), 3, d, relu, dtype, _device(device))
+        super().__init__(conv.weight, fold_batchnorm(bn), 3, d, relu, dtype, _device(device), stride=conv.stride[0])
+
+
+class StridedConvBnRelu(ConvBnRelu):
+    """ConvBnRelu for a conv of stride 1 or 2 (layer2 of the reference: stride 2, padding 1, dilation 1)."""
+
+    strides = (1, 2)
 
 
 def _conv_bn_relu_of(layer, name):
@@ -94,10 +115,13 @@ class ResidualBlock:
     downsample and residual; residual=False (arch C's layer7 / layer8) gives two plain conv + BN + ReLU launches.
     Everything is checked and folded before the weights are packed on `device`."""
 
+    strides = (1,)     # the strides of conv1 (and with it of the downsample) that the class accepts; conv2 has 1
+
     def __init__(self, block, dtype=torch.bfloat16, device=0):
         if hasattr(block, "conv3"):
             raise core.CoreError("a block with conv3 is a Bottleneck: only BasicBlock is covered")
-        d1, d2 = _dilated3x3(block.conv1, "conv1"), _dilated3x3(block.conv2, "conv2")
+        d1, d2 = _dilated3x3(block.conv1, "conv1", self.strides), _dilated3x3(block.conv2, "conv2")
+        stride = int(block.conv1.stride[0])
         c_in, c_mid, c_out = block.conv1.in_channels, block.conv1.out_channels, block.conv2.out_channels
         if block.conv2.in_channels != c_mid or block.bn1.num_features != c_mid or block.bn2.num_features != c_out:
             raise core.CoreError("conv1, bn1, conv2 and bn2 disagree on their channels")
@@ -112,16 +136,20 @@ class ResidualBlock:
                     or mods[1].num_features != c_out:
                 raise core.CoreError("downsample must be nn.Sequential(Conv2d(kernel_size=1, bias=False), BatchNorm2d) "
                                      "from the block's input to its output channels")
-            if tuple(mods[0].stride) != (1, 1):
-                raise core.CoreError(f"downsample has stride {tuple(mods[0].stride)}: only the stride-1 blocks are covered")
+            if tuple(mods[0].stride) != (stride, stride):
+                raise core.CoreError(f"downsample has stride {tuple(mods[0].stride)}, conv1 {(stride, stride)}: the "
+                                     "residual must have the shape of conv2's output")
             fold_down = fold_batchnorm(mods[1])
+        elif self.residual and stride != 1:
+            raise core.CoreError(f"conv1 has stride {stride} and the block no downsample: the input cannot be the residual")
         elif self.residual and c_in != c_out:
             raise core.CoreError(f"residual=True without a downsample needs equal channels, not {c_in} -> {c_out}")
         dev = _device(device)
         self.dtype = dtype
-        self.conv1 = ConvBn(block.conv1.weight, fold1, 3, d1, True, dtype, dev)
+        self.conv1 = ConvBn(block.conv1.weight, fold1, 3, d1, True, dtype, dev, stride=stride)
         self.conv2 = ConvBn(block.conv2.weight, fold2, 3, d2, True, dtype, dev)
-        self.downsample = ConvBn(mods[0].weight, fold_down, 1, 1, False, dtype, dev) if down is not None else None
+        self.downsample = ConvBn(mods[0].weight, fold_down, 1, 1, False, dtype, dev, stride=stride) \
+            if down is not None else None
 
     @property
     def packed(self):
@@ -135,6 +163,48 @@ class ResidualBlock:
         if self.residual:
             res = self.downsample(x) if self.downsample is not None else x
         return self.conv2(y, out_dtype=out_dtype, residual=res)
+
+
+class StridedResidualBlock(ResidualBlock):
+    """ResidualBlock for a BasicBlock whose conv1 has stride 1 or 2 (the first blocks of layer3 and layer4: stride 2,
+    dilation 1).  With stride 2 the block needs a downsample of the same stride -- the residual has the shape of
+    conv2's output, ceil(rows / 2) x ceil(cols / 2) -- and conv1 dilation 1; conv2 has stride 1."""
+
+    strides = (1, 2)
+
+
+class DrnDownsampling:
+    """layer2 -> layer3 -> layer4 -> layer5 -> ... -> layer8 -> seg -> (-log_softmax, FlipAndPad): the output of the
+    reference's layer1 [n][16][rows][cols] at full resolution in, the DP's input out, in 24 launches for drn_d_22.
+    layer2: nn.Sequential(Conv2d(3x3, stride 2, padding 1, bias=False), BatchNorm2d, ReLU); layer3, layer4: sequences
+    of BasicBlocks in eval mode (StridedResidualBlock); the rest is DrnDilated's.  rows and cols need not be multiples
+    of 8: the extents follow ceil(. / 2) three times, as the reference's do."""
+
+    def __init__(self, layer2, layer3, layer4, layer5, layer6, layer7, layer8, seg, n_classes,
+                 rows_power2_segmentation, clamp=None, dtype=torch.bfloat16, device=0):
+        self.layer2 = StridedConvBnRelu(*_conv_bn_relu_of(layer2, "layer2"), dtype=dtype, device=device)
+        self.blocks = [StridedResidualBlock(b, dtype=dtype, device=device) for layer in (layer3, layer4) for b in layer]
+        self.dilated = DrnDilated(layer5, layer6, layer7, layer8, seg, n_classes, rows_power2_segmentation, clamp=clamp,
+                                  dtype=dtype, device=device)
+        self.dtype = dtype
+
+    @property
+    def launches(self):
+        """The launches of one forward: one per packed convolution, and the head."""
+        blocks = self.blocks + self.dilated.blocks
+        return 1 + sum(len(b.packed) for b in blocks) + len(self.dilated.tail.layers) + 1
+
+    @torch.no_grad()
+    def forward(self, features, want_cnn_out=False):
+        """features: layer1's output [n][16][rows][cols] on the device; any other floating dtype than `dtype` is
+        converted first.  Returns what DrnTail.forward returns."""
+        x = features if features.dtype == self.dtype else features.to(self.dtype)
+        x = self.layer2(x)
+        for block in self.blocks:
+            x = block(x)
+        return self.dilated.forward(x, want_cnn_out=want_cnn_out)
+
+    __call__ = forward
 
 
 class DrnDilated:

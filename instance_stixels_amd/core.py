@@ -48,6 +48,7 @@ EXPORTS = [
     "is_semantic_nll_up_scratch_bytes", "is_semantic_nll_up",
     "is_conv3x3_packed_bytes", "is_conv3x3_pack_weights", "is_conv3x3_bn_relu",
     "is_conv_packed_bytes", "is_conv_pack_weights", "is_conv_bn",
+    "is_conv_bn_stride",
 ]
 RENDER_MAX_LABELS = 64    # IS_RENDER_MAX_LABELS
 RENDER_MAX_CLASSES = 256  # IS_RENDER_MAX_CLASSES
@@ -259,6 +260,15 @@ class ConvBnArgs(ctypes.Structure):
                 ("reserved", ci * 4)]
 
 
+class ConvBnStrideArgs(ctypes.Structure):
+    """is_conv_bn_stride_args: zero-initialised by ctypes; device pointers as ints."""
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    _fields_ = [("d_features", vp), ("dtype", ci), ("n_images", ci), ("channels_in", ci), ("channels_out", ci),
+                ("rows_in", ci), ("cols_in", ci), ("kernel", ci), ("stride", ci), ("dilation", ci), ("d_packed", vp),
+                ("d_scale", vp), ("d_shift", vp), ("d_residual", vp), ("relu", ci), ("d_out", vp), ("out_dtype", ci),
+                ("reserved", ci * 4)]
+
+
 class RoadParams(ctypes.Structure):
     """is_road_params: one frame's road, the layout of Stixels::RoadParameters (16 bytes)"""
     _fields_ = [("vhor", ctypes.c_int), ("tilt", ctypes.c_float), ("height", ctypes.c_float),
@@ -366,6 +376,7 @@ def lib():
         L.is_conv_packed_bytes.restype = ctypes.c_size_t
         L.is_conv_pack_weights.argtypes = [vp, ci, ci, ci, ci, vp, vp]
         L.is_conv_bn.argtypes = [ctypes.POINTER(ConvBnArgs), vp]
+        L.is_conv_bn_stride.argtypes = [ctypes.POINTER(ConvBnStrideArgs), vp]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
         L.is_get_device.argtypes = [ctypes.POINTER(ci)]
@@ -1200,10 +1211,12 @@ def _conv_pack(prefix, with_kernel, weight, dtype, device):
 
 
 def _conv_launch(prefix, entry, args_cls, with_kernel, features, packed, scale, shift, kernel, dilation, residual, relu,
-                 out_dtype, canary):
-    """The call sequence of conv3x3_bn_relu and conv_bn: the entry point `entry` of the C ABI with its args class, and
-    `prefix`_packed_bytes for the size of its packed weights.  with_kernel: the entry point has the fields `kernel`
-    and `d_residual` (f18); without it the caller passes kernel 3 and no residual (f17)."""
+                 out_dtype, canary, stride=None):
+    """The call sequence of conv3x3_bn_relu, conv_bn and conv_bn_stride: the entry point `entry` of the C ABI with its
+    args class, and `prefix`_packed_bytes for the size of its packed weights.  with_kernel: the entry point has the
+    fields `kernel` and `d_residual` (f18); without it the caller passes kernel 3 and no residual (f17).  stride: the
+    entry point has the field `stride` and names the extents rows_in, cols_in (f19); the output and the residual then
+    have ceil(. / stride) of the features' extents."""
     import torch
     x = features
     if not torch.is_tensor(x) or not x.is_cuda or x.dim() != 4:
@@ -1218,6 +1231,13 @@ def _conv_launch(prefix, entry, args_cls, with_kernel, features, packed, scale, 
     x = x.contiguous()
     dev = x.device
     n, cin, Hs, Ws = (int(v) for v in x.shape)
+    extents = dict(rows8=Hs, cols8=Ws)
+    Ho, Wo = Hs, Ws
+    if stride is not None:
+        if stride not in (1, 2):
+            raise CoreError(f"stride {stride} is neither 1 nor 2")
+        extents = dict(rows_in=Hs, cols_in=Ws, stride=int(stride))
+        Ho, Wo = (Hs + stride - 1) // stride, (Ws + stride - 1) // stride
     sc, sh = _f32_on(scale, dev).reshape(-1), _f32_on(shift, dev).reshape(-1)
     cout = int(sc.numel())
     if int(sh.numel()) != cout:
@@ -1226,8 +1246,8 @@ def _conv_launch(prefix, entry, args_cls, with_kernel, features, packed, scale, 
     if residual is not None:
         res = x if same else residual
         if not torch.is_tensor(res) or res.device != dev or res.dtype != x.dtype or \
-                tuple(int(v) for v in res.shape) != (n, cout, Hs, Ws):
-            raise CoreError(f"residual must be a {x.dtype} tensor [{n}][{cout}][{Hs}][{Ws}] on the features' device")
+                tuple(int(v) for v in res.shape) != (n, cout, Ho, Wo):
+            raise CoreError(f"residual must be a {x.dtype} tensor [{n}][{cout}][{Ho}][{Wo}] on the features' device")
         res = res.contiguous()
     k = (int(kernel),) if with_kernel else ()
     own = dict(kernel=k[0], d_residual=res.data_ptr() if res is not None else None) if with_kernel else {}
@@ -1239,12 +1259,12 @@ def _conv_launch(prefix, entry, args_cls, with_kernel, features, packed, scale, 
                         f"{cin}{f', kernel {kernel}' if with_kernel else ''} and {x.dtype} on the features' device")
     g = int(canary)
     with torch.cuda.device(dev):
-        full, flat, pattern = _guarded_float(n * cout * Hs * Ws, odt, dev, g)
-        out = flat.view(n, cout, Hs, Ws)
+        full, flat, pattern = _guarded_float(n * cout * Ho * Wo, odt, dev, g)
+        out = flat.view(n, cout, Ho, Wo)
         a = args_cls(d_features=x.data_ptr(), dtype=codes[x.dtype], n_images=n, channels_in=cin, channels_out=cout,
-                     rows8=Hs, cols8=Ws, dilation=int(dilation), d_packed=packed.data_ptr(), d_scale=sc.data_ptr(),
+                     dilation=int(dilation), d_packed=packed.data_ptr(), d_scale=sc.data_ptr(),
                      d_shift=sh.data_ptr(), relu=int(bool(relu)), d_out=out.data_ptr(),
-                     out_dtype=HEAD_F32 if odt == torch.float32 else codes[x.dtype], **own)
+                     out_dtype=HEAD_F32 if odt == torch.float32 else codes[x.dtype], **extents, **own)
         _check(getattr(lib(), entry)(ctypes.byref(a), _current_stream(dev)), entry)
         if g:
             return out, _guards({"out": (full, pattern)}, g, g)
@@ -1323,6 +1343,29 @@ def conv_bn(features, packed, scale, shift, kernel, dilation=1, residual=None, r
     canary > 0: as conv3x3_bn_relu, {"out": (front, back, pattern)} is returned second (one synchronisation)."""
     return _conv_launch("is_conv", "is_conv_bn", ConvBnArgs, True, features, packed, scale, shift, kernel, dilation,
                         residual, relu, out_dtype, canary)
+
+
+def conv_bn_stride_ptr(stream=0, **fields):
+    """is_conv_bn_stride on raw device pointers (ints): fields are those of ConvBnStrideArgs.  Asynchronous on
+    `stream`; returns the return code and raises nothing (the tests check IS_EINVAL)."""
+    a = _with_reserved(ConvBnStrideArgs, fields)
+    return lib().is_conv_bn_stride(ctypes.byref(a), ctypes.c_void_p(int(stream)))
+
+
+def conv_bn_stride(features, packed, scale, shift, kernel, stride, dilation=1, residual=None, relu=True, out_dtype=None,
+                   canary=0):
+    """conv_bn with a stride of 1 or 2 (is_conv_bn_stride, instance_stixels_core.h f19): the 3x3 (padding = dilation)
+    or 1x1 (no padding) convolution without bias, folded BatchNorm, optional residual and optional ReLU of a batch in
+    one launch.  stride 2 needs dilation 1; stride 1 is conv_bn's launch and bytes.
+
+    features    device tensor [n][channels_in][rows_in][cols_in], float16 or bfloat16; made contiguous NCHW
+    packed      conv_pack_weights(conv.weight, features.dtype) on the same device, of the same `kernel`
+    residual    None, or a device tensor of the features' dtype and the OUTPUT's shape (at stride 1 it may be `features`)
+
+    Returns the output [n][channels_out][ceil(rows_in / stride)][ceil(cols_in / stride)] on the features' device,
+    enqueued on the current torch stream.  canary > 0: as conv3x3_bn_relu."""
+    return _conv_launch("is_conv", "is_conv_bn_stride", ConvBnStrideArgs, True, features, packed, scale, shift, kernel,
+                        dilation, residual, relu, out_dtype, canary, stride=stride)
 
 
 def _with_reserved(cls, fields):

@@ -1193,8 +1193,8 @@ int is_semantic_nll_up(const is_semantic_nll_up_args* a, void* stream) {
     return IS_OK;
 }
 
-/* ---- f17, f18: convolution + BatchNorm (+ residual) (+ ReLU) (is_k_conv3x3.hip).  One checker and one launcher:
- * is_conv3x3_* are is_conv_* with kernel = 3 and no residual. ---- */
+/* ---- f17, f18, f19: convolution + BatchNorm (+ residual) (+ ReLU) (is_k_conv3x3.hip).  One checker and one launcher:
+ * is_conv3x3_* are is_conv_* with kernel = 3 and no residual, is_conv_bn is is_conv_bn_stride with stride = 1. ---- */
 static const char* conv_weights_fault(int channels_out, int channels_in, int kernel, int dtype) {
     if (dtype != IS_HEAD_F16 && dtype != IS_HEAD_BF16) return "dtype is neither IS_HEAD_F16 nor IS_HEAD_BF16";
     if (channels_in < 16 || channels_in > 2048 || channels_in % 16) return "channels_in must be a multiple of 16 in [16, 2048]";
@@ -1218,39 +1218,61 @@ int is_conv_pack_weights(const float* d_weight, int channels_out, int channels_i
     return IS_OK;
 }
 
-int is_conv_bn(const is_conv_bn_args* a, void* stream) {
-    if (!a) return fail_arg("null args");
+/* The one checker and launcher of f17, f18 and f19.  `extents_fault`: the refusal of the caller's own names for the
+ * extents (rows8 / cols8 in f17 and f18, rows_in / cols_in in f19). */
+static int conv_bn_run(const is_conv_bn_stride_args* a, void* stream, const char* extents_fault) {
     if (!a->d_features || !a->d_packed || !a->d_scale || !a->d_shift || !a->d_out)
         return fail_arg("null d_features, d_packed, d_scale, d_shift or d_out");
     if (const char* fault = conv_weights_fault(a->channels_out, a->channels_in, a->kernel, a->dtype)) return fail_arg(fault);
     if (a->out_dtype != a->dtype && a->out_dtype != IS_HEAD_F32)
         return fail_arg("out_dtype is neither the input's dtype nor IS_HEAD_F32");
     if (a->n_images < 1 || a->n_images > 65535) return fail_arg("n_images outside [1, 65535]");
-    if (a->rows8 < 1 || a->rows8 > 32767 || a->cols8 < 1 || a->cols8 > 32767)
-        return fail_arg("rows8 and cols8 must be in [1, 32767]");
+    if (a->rows_in < 1 || a->rows_in > 32767 || a->cols_in < 1 || a->cols_in > 32767) return fail_arg(extents_fault);
+    if (a->stride != 1 && a->stride != 2) return fail_arg("stride is neither 1 nor 2");
     if (a->kernel == 1 && a->dilation != 1) return fail_arg("dilation must be 1 with kernel 1");
     if (a->dilation < 1 || a->dilation > 8) return fail_arg("dilation outside [1, 8]");
+    if (a->stride == 2 && a->dilation != 1) return fail_arg("dilation must be 1 with stride 2");
     if (a->relu != 0 && a->relu != 1) return fail_arg("relu must be 0 or 1");
     if (misaligned(16, a->d_packed)) return fail_arg("d_packed must be 16-byte aligned");
     if (misaligned(2, a->d_features)) return fail_arg("d_features must be aligned to its element");
     if (misaligned(2, a->d_residual)) return fail_arg("d_residual must be aligned to its element");
     if (misaligned(a->out_dtype == IS_HEAD_F32 ? 4 : 2, a->d_out)) return fail_arg("d_out must be aligned to its element");
     if (misaligned(4, a->d_scale, a->d_shift)) return fail_arg("d_scale and d_shift must be 4-byte aligned");
-    /* (at most 2^16 * 2^11 * 2^30 elements of 4 bytes: no overflow) */
-    const uint64_t cells = (uint64_t)a->n_images * a->rows8 * a->cols8;
-    const uint64_t in_bytes = cells * a->channels_in * 2, out_bytes = cells * a->channels_out * (a->out_dtype == IS_HEAD_F32 ? 4 : 2);
+    if (a->stride == 2 && a->d_residual == a->d_features)
+        return fail_arg("d_residual is d_features with stride 2: the residual has the output's shape, not the features'");
+    /* each buffer at its own size (at most 2^16 * 2^11 * 2^30 elements of 4 bytes: no overflow) */
+    const uint64_t in_cells = (uint64_t)a->n_images * a->rows_in * a->cols_in;
+    const uint64_t out_cells = (uint64_t)a->n_images * ((a->rows_in + a->stride - 1) / a->stride) *
+                               ((a->cols_in + a->stride - 1) / a->stride);
+    const uint64_t in_bytes = in_cells * a->channels_in * 2, out_bytes = out_cells * a->channels_out * (a->out_dtype == IS_HEAD_F32 ? 4 : 2);
     const uint64_t in0 = (uint64_t)(uintptr_t)a->d_features, out0 = (uint64_t)(uintptr_t)a->d_out;
     if (in0 < out0 + out_bytes && out0 < in0 + in_bytes)
         return fail_arg(a->kernel == 3 ? "d_out overlaps d_features: the halo makes an in-place call wrong"
                                        : "d_out overlaps d_features: other channel groups still read them");
-    /* (the residual may be the features themselves: both are only read) */
-    const uint64_t res0 = (uint64_t)(uintptr_t)a->d_residual, res_bytes = cells * a->channels_out * 2;
+    /* (at stride 1 the residual may be the features themselves: both are only read) */
+    const uint64_t res0 = (uint64_t)(uintptr_t)a->d_residual, res_bytes = out_cells * a->channels_out * 2;
     if (a->d_residual && res0 < out0 + out_bytes && out0 < res0 + res_bytes)
         return fail_arg("d_out overlaps d_residual: the kernel reads the residual as memory that the launch does not write");
     /* (last: a call that is refused for this alone has passed every check above) */
     if (const char* fault = reserved_fault(a->reserved)) return fail_arg(fault);
     HIP_TRY(isk_launch_conv_bn(a, (hipStream_t)stream));
     return IS_OK;
+}
+
+int is_conv_bn_stride(const is_conv_bn_stride_args* a, void* stream) {
+    if (!a) return fail_arg("null args");
+    return conv_bn_run(a, stream, "rows_in and cols_in must be in [1, 32767]");
+}
+
+int is_conv_bn(const is_conv_bn_args* a, void* stream) {
+    if (!a) return fail_arg("null args");
+    is_conv_bn_stride_args b = {};
+    b.d_features = a->d_features, b.dtype = a->dtype, b.n_images = a->n_images, b.channels_in = a->channels_in;
+    b.channels_out = a->channels_out, b.rows_in = a->rows8, b.cols_in = a->cols8, b.kernel = a->kernel, b.stride = 1;
+    b.dilation = a->dilation, b.d_packed = a->d_packed, b.d_scale = a->d_scale, b.d_shift = a->d_shift;
+    b.d_residual = a->d_residual, b.relu = a->relu, b.d_out = a->d_out, b.out_dtype = a->out_dtype;
+    for (int i = 0; i < 4; ++i) b.reserved[i] = a->reserved[i];
+    return conv_bn_run(&b, stream, "rows8 and cols8 must be in [1, 32767]");
 }
 
 size_t is_conv3x3_packed_bytes(int channels_out, int channels_in, int dtype) {

@@ -39,6 +39,22 @@
  *             32 KB of pixels.  The MFMAs of an element still follow each other in increasing chunk, fixed by the
  *             shape alone.
  *
+ * f19 (layer2, layer3 and layer4 of drn_d_22, drn.py:161-167 and :199-233: a stride-2 3x3 convolution,
+ * and BasicBlocks whose conv1 3x3 and downsample 1x1 have stride 2) adds the template parameter STRIDE in {1, 2}.  The
+ * twelve instantiations <STRIDE = 1> are f17's and f18's.
+ *   STRIDE = 2  dilation 1 only.  H, W stay the INPUT's extents; the output is Ho = (H + 1) / 2 by Wo = (W + 1) / 2
+ *             (torch's floor((H + 2p - d(k - 1) - 1) / 2) + 1 for k = 3, p = 1 and for k = 1, p = 0).  Output pixel
+ *             (y, x) sums w[co][ci][ky][kx] * in[n][ci][2y + ky - 1][2x + kx - 1], the 1x1 form in[n][ci][2y][2x]; a
+ *             tap outside the image contributes nothing.  The tile mapping, every predicate, the stores and the
+ *             residual use the OUTPUT's extents; the order of the MFMAs and the epilogue are unchanged.
+ *             TAPS = 9: the input tile behind 8 x 32 outputs is 17 x 65 pixels at (2 y0 - 1, 2 x0 - 1), 35.4 KB beside
+ *             the 18 KB of weights.  It is stored as two column-parity planes per row, [row][33 even columns | 32 odd
+ *             columns]: tap kx = 0 reads the even plane at r, kx = 1 the odd plane at r, kx = 2 the even plane at
+ *             r + 1, so that the 32 lanes of every tap still read 32 CONSECUTIVE entries and c3_slot's swizzle spreads
+ *             a ds_read_b128 group over all 16 slots of a bank row exactly as at stride 1.
+ *             TAPS = 1: only the sampled pixels are staged, the 8 x 32 tile of in[2y][2x]; C1_STAGE as at stride 1.
+ *             No address outside the features is formed for a load: a pixel outside the image loads the clamped one.
+ *
  * Tile mapping.  A workgroup of four waves owns C3_MT = 2 tiles of 32 output channels and C3_ROWS = 8 rows of
  * C3_COLS = 32 pixels of one frame; a wave takes two of the rows and holds 2 x 2 accumulators of 32x32x16: output
  * channels on M, the 32 pixels of a row on N, so that an accumulator register is 32 consecutive pixels of one NCHW
@@ -67,6 +83,13 @@
 #define C3_STAGE(TAPS) ((TAPS) == 1 ? C1_STAGE : 1)
 static_assert((C3_MT * C3_ABLOCK(9) + 2 * (C3_ROWS + 2 * C3_MAX_DILATION) * (C3_COLS + 2 * C3_MAX_DILATION)) * 16 <= 65536,
               "the weights and the halo tile of the largest dilation fit the LDS a launch may ask for");
+#define C3S2_ROWS (2 * C3_ROWS + 1)       /* STRIDE = 2, TAPS = 9: the input tile behind C3_ROWS x C3_COLS outputs */
+#define C3S2_COLS (2 * C3_COLS + 1)
+#define C3S2_EVEN (C3_COLS + 1)          /* entries of the even-column plane of a row; the odd plane has C3_COLS */
+static_assert((C3_MT * C3_ABLOCK(9) + 2 * C3S2_ROWS * C3S2_COLS) * 16 <= 65536 &&
+                  3 * (C3_MT * C3_ABLOCK(9) + 2 * C3S2_ROWS * C3S2_COLS) * 16 <= 160 * 1024,
+              "the weights and the 17 x 65 input tile of stride 2 fit a launch's LDS, three workgroups a CU's");
+static_assert(C3S2_EVEN + C3_COLS == C3S2_COLS, "the two column-parity planes of a row are the row");
 static_assert(C1_STAGE * (C3_MT * C3_ABLOCK(1) + 2 * C3_ROWS * C3_COLS) * 16 <= 65536, "and so does a stage of the 1x1 form");
 
 typedef float c3_acc __attribute__((ext_vector_type(16)));
@@ -111,15 +134,19 @@ __global__ __launch_bounds__(256) void k_conv3x3_pack(const float* __restrict__ 
     packed[e] = c3_round<DT>(weight[((size_t)co * Cin + ci) * taps + tap]);
 }
 
-template <int DT, bool F32OUT, int TAPS, bool RESIDUAL>
+/* H, W: the INPUT's extents (STRIDE = 1: the output's as well). */
+template <int DT, bool F32OUT, int TAPS, bool RESIDUAL, int STRIDE>
 __global__ __launch_bounds__(256) void k_conv3x3(const uint16_t* __restrict__ features, const uint4* __restrict__ packed,
                                                  const float* __restrict__ scale, const float* __restrict__ shift,
                                                  const uint16_t* __restrict__ residual, void* __restrict__ out_, int Cin,
                                                  int Cout, int H, int W, int d_, int relu, int tiles_x, int tiles,
                                                  int groups) {
     static_assert(TAPS == 9 || TAPS == 1, "a 3x3 or a 1x1 convolution");
+    static_assert(STRIDE == 1 || STRIDE == 2, "stride 1, or stride 2 at dilation 1");
     constexpr int ABLOCK = C3_ABLOCK(TAPS), STAGE = C3_STAGE(TAPS);
-    const int d = TAPS == 1 ? 0 : d_;
+    constexpr bool PARITY = STRIDE == 2 && TAPS == 9; /* the B tile is the 17 x 65 input tile in column-parity planes */
+    const int d = TAPS == 1 ? 0 : STRIDE == 2 ? 1 : d_;
+    const int Ho = STRIDE == 2 ? (H + 1) / 2 : H, Wo = STRIDE == 2 ? (W + 1) / 2 : W; /* the output's extents */
     extern __shared__ uint4 c3_lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, half = lane >> 5;
@@ -127,7 +154,8 @@ __global__ __launch_bounds__(256) void k_conv3x3(const uint16_t* __restrict__ fe
     const int seq = blockIdx.x >> 3, group = seq % groups, tile = (seq / groups) * 8 + (blockIdx.x & 7);
     if (tile >= tiles) return; /* (the whole workgroup, before any barrier) */
     const int n = blockIdx.y, y0 = (tile / tiles_x) * C3_ROWS, x0 = (tile % tiles_x) * C3_COLS;
-    const int HW = C3_COLS + 2 * d, pixels = (C3_ROWS + 2 * d) * HW, chunks = Cin / C3_KC;
+    const int HW = PARITY ? C3S2_COLS : C3_COLS + 2 * d, pixels = (PARITY ? C3S2_ROWS : C3_ROWS + 2 * d) * HW;
+    const int chunks = Cin / C3_KC;
     uint4* const ldsA = c3_lds;                          /* [C3_MT][chunk of the stage][tap][k half][channel] */
     uint4* const ldsB = c3_lds + C3_MT * STAGE * ABLOCK; /* [chunk of the stage] c3_slot(pixel, k half) */
     const size_t plane = (size_t)H * W;
@@ -152,11 +180,15 @@ __global__ __launch_bounds__(256) void k_conv3x3(const uint16_t* __restrict__ fe
             for (int i = tid; i < nc * ABLOCK; i += 256) ldsA[m * STAGE * ABLOCK + i] = src[i];
         }
         /* B: an item is 8 channels of one halo pixel; consecutive threads take consecutive pixels of a plane.  A pixel
-         * outside the image loads the nearest pixel inside it and stores zeros. */
+         * outside the image loads the nearest pixel inside it and stores zeros.  STRIDE = 2: tile pixel (py, px) is
+         * input pixel (2 y0 - 1 + py, 2 x0 - 1 + px), stored at its column parity's plane; the 1x1 form takes the
+         * sampled pixels (2 (y0 + py), 2 (x0 + px)) alone. */
         for (int it_ = tid; it_ < nc * 2 * pixels; it_ += 256) {
             const int cc = STAGE == 1 ? 0 : it_ / (2 * pixels), it = it_ - cc * 2 * pixels;
             const int h = it >= pixels, p = it - h * pixels, py = p / HW, px = p - py * HW;
-            const int gy = y0 - d + py, gx = x0 - d + px;
+            const int gy = STRIDE == 1 ? y0 - d + py : TAPS == 9 ? 2 * y0 - 1 + py : 2 * (y0 + py);
+            const int gx = STRIDE == 1 ? x0 - d + px : TAPS == 9 ? 2 * x0 - 1 + px : 2 * (x0 + px);
+            const int lp = PARITY ? py * C3S2_COLS + (px & 1) * C3S2_EVEN + (px >> 1) : p;
             const bool inside = gy >= 0 && gy < H && gx >= 0 && gx < W;
             const uint16_t* src = xn + (size_t)(C3_KC * (chunk + cc) + 8 * h) * plane +
                                   (size_t)min(max(gy, 0), H - 1) * W + min(max(gx, 0), W - 1);
@@ -165,7 +197,7 @@ __global__ __launch_bounds__(256) void k_conv3x3(const uint16_t* __restrict__ fe
             for (int j = 0; j < 8; ++j) v[j] = src[j * plane];
             uint4 q;
             q.x = v[0] | (v[1] << 16), q.y = v[2] | (v[3] << 16), q.z = v[4] | (v[5] << 16), q.w = v[6] | (v[7] << 16);
-            ldsB[cc * 2 * pixels + c3_slot(p, h)] = inside ? q : make_uint4(0, 0, 0, 0);
+            ldsB[cc * 2 * pixels + c3_slot(lp, h)] = inside ? q : make_uint4(0, 0, 0, 0);
         }
         __syncthreads();
         for (int cc = 0; cc < nc; ++cc) {
@@ -176,8 +208,12 @@ __global__ __launch_bounds__(256) void k_conv3x3(const uint16_t* __restrict__ fe
 #pragma unroll
                 for (int m = 0; m < C3_MT; ++m) a[m] = ldsA[(m * STAGE + cc) * ABLOCK + (2 * tap + half) * 32 + r];
 #pragma unroll
-                for (int t = 0; t < C3_NT; ++t)
-                    b[t] = ldsB[cc * 2 * pixels + c3_slot((C3_NT * wave + t + ky * d) * HW + r + kx * d, half)];
+                for (int t = 0; t < C3_NT; ++t) {
+                    /* PARITY: input row 2 (row of the tile) + ky; column 2 r + kx is entry r + kx / 2 of plane kx & 1 */
+                    const int bp = PARITY ? (2 * (C3_NT * wave + t) + ky) * C3S2_COLS + (kx & 1) * C3S2_EVEN + (kx >> 1) + r
+                                          : (C3_NT * wave + t + ky * d) * HW + r + kx * d;
+                    b[t] = ldsB[cc * 2 * pixels + c3_slot(bp, half)];
+                }
 #pragma unroll
                 for (int m = 0; m < C3_MT; ++m)
 #pragma unroll
@@ -202,11 +238,11 @@ __global__ __launch_bounds__(256) void k_conv3x3(const uint16_t* __restrict__ fe
                 const int y = y0 + C3_NT * wave + t;
                 float v = fmaf(sc, acc[m][t][i], sh);
                 if (RESIDUAL) { /* (read under the predicate of the store below, at the store's index) */
-                    if (y < H && x < W) v = v + c3_widen<DT>(residual[(((size_t)n * Cout + co) * H + y) * W + x]);
+                    if (y < Ho && x < Wo) v = v + c3_widen<DT>(residual[(((size_t)n * Cout + co) * Ho + y) * Wo + x]);
                 }
                 if (relu) v = fmaxf(v, 0.0f);
-                if (y < H && x < W) {
-                    const size_t at = (((size_t)n * Cout + co) * H + y) * W + x;
+                if (y < Ho && x < Wo) {
+                    const size_t at = (((size_t)n * Cout + co) * Ho + y) * Wo + x;
                     if (F32OUT) ((float*)out_)[at] = v;
                     else ((uint16_t*)out_)[at] = c3_round<DT>(v);
                 }
@@ -229,32 +265,39 @@ extern "C" hipError_t isk_launch_conv_pack(const float* d_weight, int channels_o
     return hipGetLastError();
 }
 
-template <int DT, bool F32OUT, int TAPS, bool RESIDUAL>
-static void c3_launch(const is_conv_bn_args* a, hipStream_t stream) {
+template <int DT, bool F32OUT, int TAPS, bool RESIDUAL, int STRIDE>
+static void c3_launch(const is_conv_bn_stride_args* a, hipStream_t stream) {
     const int d = TAPS == 1 ? 0 : a->dilation;
-    const int tiles_x = (a->cols8 + C3_COLS - 1) / C3_COLS, tiles = tiles_x * ((a->rows8 + C3_ROWS - 1) / C3_ROWS);
+    const int rows_out = (a->rows_in + STRIDE - 1) / STRIDE, cols_out = (a->cols_in + STRIDE - 1) / STRIDE;
+    const int tiles_x = (cols_out + C3_COLS - 1) / C3_COLS, tiles = tiles_x * ((rows_out + C3_ROWS - 1) / C3_ROWS);
     const int groups = (a->channels_out / 32 + C3_MT - 1) / C3_MT;
     const dim3 grid((unsigned)groups * (unsigned)((tiles + 7) / 8 * 8), a->n_images); /* at most 32 * 2^22 */
-    const size_t lds = (size_t)C3_STAGE(TAPS) * (C3_MT * C3_ABLOCK(TAPS) + 2 * (C3_ROWS + 2 * d) * (C3_COLS + 2 * d)) * 16;
-    hipLaunchKernelGGL((k_conv3x3<DT, F32OUT, TAPS, RESIDUAL>), grid, dim3(256), lds, stream,
+    const size_t b_pixels = STRIDE == 2 && TAPS == 9 ? C3S2_ROWS * C3S2_COLS : (C3_ROWS + 2 * d) * (C3_COLS + 2 * d);
+    const size_t lds = (size_t)C3_STAGE(TAPS) * (C3_MT * C3_ABLOCK(TAPS) + 2 * b_pixels) * 16;
+    hipLaunchKernelGGL((k_conv3x3<DT, F32OUT, TAPS, RESIDUAL, STRIDE>), grid, dim3(256), lds, stream,
                        (const uint16_t*)a->d_features, (const uint4*)a->d_packed, a->d_scale, a->d_shift,
-                       (const uint16_t*)a->d_residual, a->d_out, a->channels_in, a->channels_out, a->rows8, a->cols8, d,
+                       (const uint16_t*)a->d_residual, a->d_out, a->channels_in, a->channels_out, a->rows_in, a->cols_in, d,
                        a->relu, tiles_x, tiles, groups);
 }
 
-template <int DT, bool F32OUT>
-static void c3_launch_form(const is_conv_bn_args* a, hipStream_t stream) {
-    if (a->kernel == 3) {
-        if (a->d_residual) c3_launch<DT, F32OUT, 9, true>(a, stream); else c3_launch<DT, F32OUT, 9, false>(a, stream);
+template <int DT, bool F32OUT, int TAPS>
+static void c3_launch_taps(const is_conv_bn_stride_args* a, hipStream_t stream) {
+    if (a->stride == 2) {
+        if (a->d_residual) c3_launch<DT, F32OUT, TAPS, true, 2>(a, stream); else c3_launch<DT, F32OUT, TAPS, false, 2>(a, stream);
     } else {
-        if (a->d_residual) c3_launch<DT, F32OUT, 1, true>(a, stream); else c3_launch<DT, F32OUT, 1, false>(a, stream);
+        if (a->d_residual) c3_launch<DT, F32OUT, TAPS, true, 1>(a, stream); else c3_launch<DT, F32OUT, TAPS, false, 1>(a, stream);
     }
 }
 
-/* The arguments are checked by is_conv_bn (and, through it, by is_conv3x3_bn_relu). */
-extern "C" hipError_t isk_launch_conv_bn(const is_conv_bn_args* a, hipStream_t stream) {
+template <int DT, bool F32OUT>
+static void c3_launch_form(const is_conv_bn_stride_args* a, hipStream_t stream) {
+    if (a->kernel == 3) c3_launch_taps<DT, F32OUT, 9>(a, stream); else c3_launch_taps<DT, F32OUT, 1>(a, stream);
+}
+
+/* The arguments are checked by is_core.hip's conv_bn_run, for is_conv_bn_stride, is_conv_bn and is_conv3x3_bn_relu alike. */
+extern "C" hipError_t isk_launch_conv_bn(const is_conv_bn_stride_args* a, hipStream_t stream) {
     const bool f32out = a->out_dtype == IS_HEAD_F32;
-    if (a->kernel != 3 && a->kernel != 1) return hipErrorInvalidValue;
+    if ((a->kernel != 3 && a->kernel != 1) || (a->stride != 1 && a->stride != 2)) return hipErrorInvalidValue;
     if (a->dtype == IS_HEAD_F16) {
         if (f32out) c3_launch_form<IS_HEAD_F16, true>(a, stream); else c3_launch_form<IS_HEAD_F16, false>(a, stream);
     } else if (a->dtype == IS_HEAD_BF16) {

@@ -252,7 +252,7 @@ hipError_t isk_launch_segmentation_head(const is_segmentation_head_args* a, hipS
 /* is_k_conv3x3.hip */
 hipError_t isk_launch_conv_pack(const float* d_weight, int channels_out, int channels_in, int kernel, int dtype,
                                 void* d_packed, hipStream_t stream);
-hipError_t isk_launch_conv_bn(const is_conv_bn_args* a, hipStream_t stream);
+hipError_t isk_launch_conv_bn(const is_conv_bn_stride_args* a, hipStream_t stream);
 
 /* is_k_head_backward.hip */
 size_t isk_head_backward_scratch_bytes(int n_images, int K, int Hs, int Ws, int channels);

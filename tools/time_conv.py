@@ -1,5 +1,6 @@
 """The backbone's convolutions on the device (f17: is_conv3x3_bn_relu, core.conv3x3_bn_relu; f18: is_conv_bn,
-core.conv_bn, cnn.ResidualBlock) against what they replace and against themselves, on the same device tensors (GPU
+core.conv_bn, cnn.ResidualBlock; f19: is_conv_bn_stride, core.conv_bn_stride, cnn.StridedResidualBlock) against what
+they replace and against themselves, on the same device tensors (GPU
 box).
 
 Prints one JSON line (progress on stderr).  Every timing is ms per batch by device events around the enqueued work,
@@ -19,11 +20,18 @@ comma-separated), for fp16 and bf16 features [n][.][rows8][cols8] with half outp
   F.batch_norm (eval).
 - layers: layer5 + layer6 of drn_d_22 (two BasicBlocks each, 128 -> 256 -> 512, dilations 2 and 4, the first block of
   each with a downsample) through cnn.ResidualBlock (10 launches) against the torch modules.
+- strided (not in the default --parts): the downsampling layers of drn_d_22 on layer1's output [n][16][--rows][--cols]
+  in half: each distinct new launch shape -- 3x3 stride 2 at 16 -> 32, 32 -> 64 and 64 -> 128, 1x1 stride 2 at 32 -> 64
+  and 64 -> 128, 3x3 stride 1 with a residual at 64 and 128 channels, each at its layer's resolution -- against
+  F.conv2d(stride) + F.batch_norm (+ residual) (+ F.relu), and layer2 + layer3 + layer4 whole (11 launches) against the
+  torch modules.  --strided-n frames per call (default --n): a slice of the batch where torch's intermediates or its
+  warm-up are too large; the row says how many.
 --no-torch leaves the torch arms out (and alone allows fewer than 10 iterations, for a counter run).  torch's first
 convolution of a shape takes 30 - 160 s: run the dtypes, and if need be the parts, in separate commands.
 
     python tools/time_conv.py [--n 64 --C 512 --rows8 128 --cols8 256 --iters 20 --mhz 2400 --cus 256 --dtypes fp16,bf16
-                               --parts tail,residual,1x1,layers --no-torch]
+                               --parts tail,residual,1x1,layers[,strided] --rows 1024 --cols 2048 --strided-n 64
+                               --no-torch]
 """
 import argparse
 import copy
@@ -53,7 +61,10 @@ def main():
     ap.add_argument("--dp-n", type=int, default=0, help="0: the whole batch (a shape the library is already tuned for)")
     ap.add_argument("--dtypes", default="fp16,bf16", help="comma-separated subset of fp16,bf16")
     ap.add_argument("--parts", default="tail,residual,1x1,layers",
-                    help="comma-separated subset of tail,residual,1x1,layers")
+                    help="comma-separated subset of tail,residual,1x1,layers,strided")
+    ap.add_argument("--rows", type=int, default=1024, help="rows of layer1's output (the `strided` part)")
+    ap.add_argument("--cols", type=int, default=2048)
+    ap.add_argument("--strided-n", type=int, default=0, help="frames per call of the `strided` part; 0: --n")
     ap.add_argument("--no-torch", action="store_true", help="time the library's launches alone")
     a = ap.parse_args()
     if a.iters < 10 and not a.no_torch:
@@ -88,8 +99,10 @@ def main():
     def weight(cout, cin, k):
         return torch.randn((cout, cin, k, k), device=dev) * (2.0 / (k * k * cout)) ** 0.5
 
-    def torch_conv_bn(x, w, d, bn, relu):
-        y = F.batch_norm(F.conv2d(x, w, padding=d * (w.shape[2] // 2), dilation=d), *bn, False, 0.0, eps)
+    def torch_conv_bn(x, w, d, bn, relu, stride=1, residual=None):
+        y = F.batch_norm(F.conv2d(x, w, stride=stride, padding=d * (w.shape[2] // 2), dilation=d), *bn, False, 0.0, eps)
+        if residual is not None:
+            y = y + residual
         return F.relu(y) if relu else y
 
     def channels_last(*ts):
@@ -123,15 +136,16 @@ def main():
     class TorchBlock(torch.nn.Module):
         """conv1, bn1, relu, conv2, bn2, (+ downsample(x) or x), relu: a BasicBlock in eval mode."""
 
-        def __init__(self, cin, cout, d, dtype):
+        def __init__(self, cin, cout, d, dtype, stride=1):
             super().__init__()
-            self.conv1 = torch.nn.Conv2d(cin, cout, 3, padding=d, dilation=d, bias=False)
+            self.conv1 = torch.nn.Conv2d(cin, cout, 3, stride=stride, padding=d, dilation=d, bias=False)
             self.bn1 = torch.nn.BatchNorm2d(cout)
             self.conv2 = torch.nn.Conv2d(cout, cout, 3, padding=d, dilation=d, bias=False)
             self.bn2 = torch.nn.BatchNorm2d(cout)
             self.downsample = None
             if cin != cout:
-                self.downsample = torch.nn.Sequential(torch.nn.Conv2d(cin, cout, 1, bias=False), torch.nn.BatchNorm2d(cout))
+                self.downsample = torch.nn.Sequential(torch.nn.Conv2d(cin, cout, 1, stride=stride, bias=False),
+                                                      torch.nn.BatchNorm2d(cout))
             self.residual = True
             with torch.no_grad():
                 for m in self.modules():
@@ -256,6 +270,79 @@ def main():
             out[name + "_layers"] = row
             note(name, "layers", json.dumps(row))
             del x, ours
+            torch.cuda.empty_cache()
+        if "strided" in parts:
+            m, H1, W1 = a.strided_n or n, a.rows, a.cols
+            half = lambda v, times: -(-v // 2 ** times)                      # ceil(v / 2^times)
+            # (label, channels_in, channels_out, kernel, stride, input rows and cols, residual, relu)
+            launches = [("3x3s2_16_32", 16, 32, 3, 2, 0, False, True), ("3x3s2_32_64", 32, 64, 3, 2, 1, False, True),
+                        ("3x3s2_64_128", 64, 128, 3, 2, 2, False, True), ("1x1s2_32_64", 32, 64, 1, 2, 1, False, False),
+                        ("1x1s2_64_128", 64, 128, 1, 2, 2, False, False), ("3x3s1_res_64", 64, 64, 3, 1, 2, True, True),
+                        ("3x3s1_res_128", 128, 128, 3, 1, 3, True, True)]
+            for label, cin, cout, k, stride, level, with_res, relu in launches:
+                Hi, Wi = half(H1, level), half(W1, level)
+                Ho, Wo = -(-Hi // stride), -(-Wi // stride)
+                x = torch.randn((m, cin, Hi, Wi), device=dev).abs_().to(dtype)
+                res = torch.randn((m, cout, Ho, Wo), device=dev).to(dtype) if with_res else None
+                w32, stats = weight(cout, cin, k), bn_stats(cout)
+                packed, (scale, shift) = core.conv_pack_weights(w32, dtype), fold(*stats)
+                arms = {"new": lambda: core.conv_bn_stride(x, packed, scale, shift, k, stride, residual=res, relu=relu)}
+                if not a.no_torch:
+                    wd, bn = w32.to(dtype), [t.to(dtype) for t in stats]
+                    x_cl, w_cl = channels_last(x, wd)
+                    res_cl = channels_last(res)[0] if with_res else None
+                    arms["torch_contiguous"] = lambda: torch_conv_bn(x, wd, 1, bn, relu, stride, res)
+                    arms["torch_channels_last"] = lambda: torch_conv_bn(x_cl, w_cl, 1, bn, relu, stride, res_cl)
+                row, med = measure("%s %s" % (name, label), arms)
+                gb = m * 2 * (cin * Hi * Wi + (2 if with_res else 1) * cout * Ho * Wo) / 1e9
+                tflop = 2.0 * k * k * cin * cout * m * Ho * Wo / 1e12
+                row.update(frames=m, shape_in=[m, cin, Hi, Wi], shape_out=[m, cout, Ho, Wo], compulsory_gb=round(gb, 3),
+                           tflop=round(tflop, 4), new_gb_per_s=round(gb / (med["new"] * 1e-3), 1),
+                           new_tflops=round(tflop / (med["new"] * 1e-3), 1))
+                against_torch(row, med)
+                out["%s_%s" % (name, label)] = row
+                note(name, label, json.dumps(row))
+                del x, res, packed, arms
+                if not a.no_torch:
+                    del x_cl, res_cl
+                torch.cuda.empty_cache()
+            layer2 = torch.nn.Sequential(torch.nn.Conv2d(16, 32, 3, stride=2, padding=1, bias=False),
+                                         torch.nn.BatchNorm2d(32), torch.nn.ReLU())
+            with torch.no_grad():
+                mean, var, gamma, beta = (t.cpu() for t in bn_stats(32))
+                layer2[0].weight.copy_(weight(32, 16, 3))
+                layer2[1].running_mean.copy_(mean), layer2[1].running_var.copy_(var)
+                layer2[1].weight.copy_(gamma), layer2[1].bias.copy_(beta)
+            layer2.eval()
+            blocks = [TorchBlock(32, 64, 1, dtype, stride=2), TorchBlock(64, 64, 1, dtype),
+                      TorchBlock(64, 128, 1, dtype, stride=2), TorchBlock(128, 128, 1, dtype)]
+            ours = [cnn.StridedConvBnRelu(layer2[0], layer2[1], dtype=dtype)] + \
+                   [cnn.StridedResidualBlock(b.to(dev), dtype=dtype) for b in blocks]
+            x = torch.randn((m, 16, H1, W1), device=dev).abs_().to(dtype)
+
+            def new():
+                y = x
+                for layer in ours:
+                    y = layer(y)
+                return y
+            arms = {"new": new}
+            if not a.no_torch:
+                seq = torch.nn.Sequential(layer2, *blocks).to(device=dev, dtype=dtype).eval()
+                seq_cl = copy.deepcopy(seq).to(memory_format=torch.channels_last).eval()
+                x_cl, = channels_last(x)
+                arms["torch_contiguous"] = lambda: seq(x)
+                arms["torch_channels_last"] = lambda: seq_cl(x_cl)
+            with torch.no_grad():
+                row, med = measure(name + " layer2+layer3+layer4", arms)
+            convs = [(layer2[0], 1)] + [(c, lv) for b, lv in zip(blocks, (2, 2, 3, 3)) for c in
+                                        [b.conv1, b.conv2] + ([b.downsample[0]] if b.downsample is not None else [])]
+            tflop = sum(2.0 * c.weight.numel() * m * half(H1, lv) * half(W1, lv) for c, lv in convs) / 1e12
+            row.update(frames=m, shape_in=[m, 16, H1, W1], launches=len(convs), tflop=round(tflop, 3),
+                       mfma_floor_ms=round(floor_ms(tflop), 3), new_tflops=round(tflop / (med["new"] * 1e-3), 1))
+            against_torch(row, med)
+            out[name + "_strided_layers"] = row
+            note(name, "strided layers", json.dumps(row))
+            del x, ours, arms
             torch.cuda.empty_cache()
     print(json.dumps(out), flush=True)
 
