@@ -1363,6 +1363,88 @@ typedef struct is_conv_bn_stride_args {
  * d_features, and, last, a non-zero reserved field. */
 int is_conv_bn_stride(const is_conv_bn_stride_args* args, void* stream);
 
+/* ---- f20: the backbone's stem, image bytes to layer1's output of a batch in one launch (is_k_stem.hip) -------------
+ * layer0 and layer1 of drn_d_22 (tools/CNN_training/models/drn.py:154-159: Conv2d(3, 16, 7, stride 1, padding 3, bias =
+ * False) + BatchNorm2d + ReLU;  drn.py:161-162, _make_conv_layers with layers[0] == 1: Conv2d(16, 16, 3, padding 1,
+ * bias = False) + BatchNorm2d + ReLU) and, in front of them, what the reference does to the camera image: ToTensor,
+ * Normalize and the cast to half (inference.py:109-110, :278).  is_conv_bn_stride cannot take these layers (3 and 16
+ * channels are below its tiles and it has no 7x7), and the two belong in one launch: layer0's output stays in LDS, so
+ * the compulsory traffic is 3 + 32 bytes per pixel instead of (3 + 32) + (32 + 32).  is_stem -> 23 x is_conv_bn_stride ->
+ * is_segmentation_head is 25 launches of this library with nothing in between: image bytes in, the DP's input out.
+ *
+ *     x[n][c][y][x]  = lut[c][ image[n][y][x][c] ]                       c in 0..2
+ *     mid            = half( relu( bn0( conv7x7(x), pad 3 ) ) )          3 -> 16 channels
+ *     out            = half( relu( bn1( conv3x3(mid), pad 1 ) ) )        16 -> 16 channels
+ *
+ *   Input.       d_image is uint8 [n_images][rows][cols][3]: interleaved, contiguous, as a decoder delivers it.  d_lut
+ *                is [3][256] of the half `dtype`.  The operand of layer0 at channel c is lut[c][byte], and that is the
+ *                whole definition of the normalisation: the launch gives the table's bits.  Byte position c pairs with
+ *                input channel c of layer0's weight; a BGR caller permutes the table's rows and the weight's input
+ *                channels.
+ *   Padding 0.   A tap of layer0 outside the image contributes nothing: zero padding of the NORMALISED value.  It is
+ *                not lut[c][0], and it cannot be folded into weights or shift.
+ *   mid.         a0 = sum over 3 x 7 x 7 of w0[co][ci][ky][kx] * x[n][ci][y + ky - 3][x + kx - 3], accumulated in fp32
+ *                by v_mfma_f32_16x16x32_{f16,bf16} on ONE accumulator chain per element, in an order fixed by the shape
+ *                alone (one instruction per ky, in increasing ky); zero-filled k slots are exact zeros; the order inside
+ *                one instruction is the hardware's, as in f17.  Then v = fmaf(scale0[co], a0, shift0[co]), max(v, 0),
+ *                rounded to `dtype` to nearest even.  layer1's operands are exactly these half values.
+ *   Padding 1.   A mid pixel outside the image is ZERO: not relu(shift0) and not a convolution evaluated past the edge.
+ *   out.         a1 = sum over 16 x 3 x 3 of w1[co][ci][ky][kx] * mid[n][ci][y + ky - 1][x + kx - 1] with the same
+ *                rules (increasing tap 3 ky + kx, 16 channels a tap); then fmaf(scale1[co], a1, shift1[co]), max(., 0),
+ *                rounded to nearest even to `dtype`.  d_out is [n][16][rows][cols] NCHW contiguous, what
+ *                is_conv_bn_stride reads for layer2.  Every element is written.
+ *   d_mid.       NULL, or [n][16][rows][cols] of `dtype`: every element of mid is also stored.  d_out has the same bytes
+ *                whether or not d_mid is given; with d_mid == NULL mid never reaches global memory.  A mid halo pixel
+ *                computed by two workgroups has the same bits in both, because the order is the same.
+ *   Determinism. The same bytes on every run; a frame's result does not depend on its position in the batch or on
+ *                n_images; no atomics.
+ *   Safety.      No address outside the image's n_images * rows * cols * 3 bytes is loaded from.  Non-finite table
+ *                entries give unspecified values and never a wild access: no address depends on a value other than the
+ *                table index, which is a byte.
+ *   Ranges.      n_images in [1, 65535]; rows, cols in [1, 32767] with no multiple-of-anything requirement.  The
+ *                channels are 3 -> 16 -> 16, kernel 7 / pad 3 and kernel 3 / pad 1, stride 1, dilation 1: not fields.
+ *
+ * Weights: d_w0 is layer0's conv.weight [16][3][7][7], d_w1 layer1's [16][16][3][3], fp32.  is_stem_pack_weights
+ * rounds each to the half dtype (round to nearest even) into one opaque blob that holds exactly those values (and
+ * zeros), is_stem_packed_bytes(dtype) bytes at a 16-byte aligned d_packed: one small launch, once per model.
+ *
+ * Zero-initialise, then set the fields.  All arrays on the current device.
+ *   d_image             [n_images][rows][cols][3] uint8
+ *   d_lut               [3][256] of `dtype`, aligned to its element
+ *   d_packed            from is_stem_pack_weights with the same dtype, 16-byte aligned
+ *   d_scale0 .. d_shift1   [16] fp32 each: the folded BatchNorms of layer0 and layer1
+ *   d_mid               NULL, or [n_images][16][rows][cols] of `dtype`
+ *   d_out               [n_images][16][rows][cols] of `dtype`; its bytes must overlap neither d_mid's nor the image's,
+ *                       and d_mid's not the image's, each taken at its own size
+ *   reserved            0 */
+typedef struct is_stem_args {
+    const void* d_image;
+    int n_images, rows, cols;
+    const void* d_lut;
+    int dtype; /* IS_HEAD_F16 | IS_HEAD_BF16 */
+    const void* d_packed;
+    const float* d_scale0;
+    const float* d_shift0;
+    const float* d_scale1;
+    const float* d_shift1;
+    void* d_mid; /* NULL, or [n][16][rows][cols] of `dtype` */
+    void* d_out;
+    int reserved[4]; /* 0 */
+} is_stem_args;
+
+/* The bytes of the packed weights; 0 for a dtype that is neither IS_HEAD_F16 nor IS_HEAD_BF16. */
+size_t is_stem_packed_bytes(int dtype);
+/* One small launch on `stream`.  IS_EINVAL for null pointers, a dtype as above, d_w0 / d_w1 off 4-byte alignment or
+ * d_packed off 16-byte alignment. */
+int is_stem_pack_weights(const float* d_w0 /*[16][3][7][7]*/, const float* d_w1 /*[16][16][3][3]*/, int dtype,
+                         void* d_packed, void* stream);
+/* One launch on `stream`, asynchronous and stream-ordered; no allocation, copy or synchronisation.  IS_EINVAL, with
+ * the reason in is_last_error() and before the device is touched, for null args or required pointers (all but d_mid);
+ * a dtype that is IS_HEAD_F32 or unknown; n_images, rows or cols out of range; d_packed off 16-byte alignment, d_lut,
+ * d_mid or d_out off their element, a fold off 4 bytes; d_out overlapping d_mid, or either of them overlapping the
+ * image, each taken at its own byte size; and, last, a non-zero reserved field. */
+int is_stem(const is_stem_args* args, void* stream);
+
 /* ---- f9: per-instance objects and their contours (is_k_objects.hip) ------------------------------------------------
  * What the reference's consumers reduce on the host from the per-stixel output: the top-down view
  * (tools/visualization/clustering_visualization.py:563-792: per instance and column the closest stixel, connected

@@ -18,7 +18,11 @@ BasicBlocks of layer3 and layer4 (drn.py:164-167), whose first block has stride 
 ConvBn carries its stride and launches core.conv_bn_stride (at stride 1 the bytes of core.conv_bn); the classes that
 accept stride 2 are StridedConvBnRelu and StridedResidualBlock, which differ from ConvBnRelu and ResidualBlock in the
 strides they allow and in nothing else.  DrnDownsampling is layer2 -> layer3 -> layer4 -> DrnDilated: the output of
-layer1 at full resolution in, the DP's input out, 24 launches."""
+layer1 at full resolution in, the DP's input out, 24 launches.
+
+f20 puts the stem in front of that: DrnStem is the table look-up of the image's bytes (input_table: ToTensor +
+Normalize + the cast to half), layer0 (7x7, 3 -> 16) and layer1 (3x3, 16 -> 16) in ONE launch of core.stem, and Drn is
+DrnStem -> DrnDownsampling: the camera's uint8 image in, the DP's input out, 25 launches for drn_d_22."""
 import torch
 
 from . import core
@@ -171,6 +175,110 @@ class StridedResidualBlock(ResidualBlock):
     conv2's output, ceil(rows / 2) x ceil(cols / 2) -- and conv1 dilation 1; conv2 has stride 1."""
 
     strides = (1, 2)
+
+
+def input_table(mean, std, dtype):
+    """The [3][256] table of ToTensor + Normalize(mean, std) + the cast to `dtype` (inference.py:109-110, :278):
+    ((arange(256, fp32) / 255) - mean[c]) / std[c] in fp32 on the CPU, then .to(dtype).  mean, std: three values each,
+    in the order of the image's bytes."""
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise core.CoreError(f"dtype {dtype} is neither torch.float16 nor torch.bfloat16")
+    mean = torch.as_tensor(mean, dtype=torch.float32).reshape(-1).cpu()
+    std = torch.as_tensor(std, dtype=torch.float32).reshape(-1).cpu()
+    if mean.numel() != 3 or std.numel() != 3:
+        raise core.CoreError("mean and std must hold three values each")
+    unit = torch.arange(256, dtype=torch.float32) / 255
+    return ((unit.view(1, 256) - mean.view(3, 1)) / std.view(3, 1)).to(dtype)
+
+
+def _stem_conv(layer, name, channels_in, kernel, padding, why_not_three):
+    """(conv, bn) of a stem layer: nn.Sequential(Conv2d(channels_in, 16, kernel, stride 1, padding, dilation 1,
+    bias=False), BatchNorm2d, ReLU) with exactly three modules."""
+    mods = list(layer) if isinstance(layer, torch.nn.Sequential) else None
+    if mods is None:
+        raise core.CoreError(f"{name} must be an nn.Sequential, not {type(layer).__name__}")
+    if any(hasattr(m, "conv1") and hasattr(m, "conv2") for m in mods):
+        raise core.CoreError(f"{name} holds a BasicBlock (arch C builds its {name} from blocks): only arch D's "
+                             "Conv2d + BatchNorm2d + ReLU stem is covered")
+    if len(mods) != 3:
+        raise core.CoreError(f"{name} has {len(mods)} modules, not the three of Conv2d + BatchNorm2d + ReLU" + why_not_three)
+    conv, bn, relu = mods
+    if not isinstance(conv, torch.nn.Conv2d) or not isinstance(bn, torch.nn.BatchNorm2d) or not isinstance(relu, torch.nn.ReLU):
+        raise core.CoreError(f"{name} must be nn.Sequential(Conv2d, BatchNorm2d, ReLU)")
+    if conv.in_channels != channels_in or conv.out_channels != 16 or tuple(conv.kernel_size) != (kernel, kernel) or \
+            tuple(conv.stride) != (1, 1) or tuple(conv.padding) != (padding, padding) or tuple(conv.dilation) != (1, 1) or \
+            conv.groups != 1 or getattr(conv, "padding_mode", "zeros") != "zeros":
+        raise core.CoreError(f"{name}'s conv must be Conv2d({channels_in}, 16, kernel_size={kernel}, stride=1, "
+                             f"padding={padding}, dilation=1, groups=1)")
+    if conv.bias is not None:
+        raise core.CoreError(f"{name}'s conv has a bias: the reference's has none (bias=False)")
+    if bn.num_features != 16:
+        raise core.CoreError(f"{name}'s bn has {bn.num_features} channels, its conv 16")
+    return conv, bn
+
+
+class DrnStem:
+    """ToTensor + Normalize + half -> layer0 -> layer1 of the reference's drn_d_22 in one launch (core.stem): the uint8
+    image [n][rows][cols][3] in, layer1's output [n][16][rows][cols] out.
+    layer0: nn.Sequential(Conv2d(3, 16, 7, stride 1, padding 3, bias=False), BatchNorm2d, ReLU) (drn.py:154-159);
+    layer1: nn.Sequential(Conv2d(16, 16, 3, stride 1, padding 1, dilation 1, bias=False), BatchNorm2d, ReLU) with
+    exactly three modules (drn.py:161-162 with layers[0] == 1), both in eval mode; mean, std: Normalize's, in the order
+    of the image's bytes (a BGR caller permutes them and layer0's input channels).  Everything is
+    checked and folded before anything is packed on `device`."""
+
+    def __init__(self, layer0, layer1, mean, std, dtype=torch.bfloat16, device=0):
+        conv0, bn0 = _stem_conv(layer0, "layer0", 3, 7, 3, "")
+        conv1, bn1 = _stem_conv(layer1, "layer1", 16, 3, 1, " (layers[0] > 1 repeats the three: only layers[0] == 1 is covered)")
+        fold0, fold1 = fold_batchnorm(bn0), fold_batchnorm(bn1)
+        table = input_table(mean, std, dtype)
+        dev = _device(device)
+        self.dtype = dtype
+        self.packed = core.stem_pack_weights(conv0.weight, conv1.weight, dtype, device=dev)
+        self.lut = table.to(dev)
+        self.fold0 = (fold0[0].to(dev), fold0[1].to(dev))
+        self.fold1 = (fold1[0].to(dev), fold1[1].to(dev))
+
+    launches = 1
+
+    @torch.no_grad()
+    def forward(self, image, want_mid=False):
+        """image: uint8 [n][rows][cols][3] on the device.  Returns layer1's output, with want_mid (out, mid)."""
+        return core.stem(image, self.lut, self.packed, *self.fold0, *self.fold1, want_mid=want_mid)
+
+    __call__ = forward
+
+
+class Drn:
+    """DrnStem -> DrnDownsampling: the camera's uint8 image [n][rows][cols][3] in, the DP's input out, in 25 launches
+    for drn_d_22 with nothing of torch in between."""
+
+    def __init__(self, layer0, layer1, layer2, layer3, layer4, layer5, layer6, layer7, layer8, seg, n_classes,
+                 rows_power2_segmentation, mean, std, clamp=None, dtype=torch.bfloat16, device=0):
+        self.stem = DrnStem(layer0, layer1, mean, std, dtype=dtype, device=device)
+        self.downsampling = DrnDownsampling(layer2, layer3, layer4, layer5, layer6, layer7, layer8, seg, n_classes,
+                                            rows_power2_segmentation, clamp=clamp, dtype=dtype, device=device)
+        self.dtype = dtype
+
+    @classmethod
+    def from_base(cls, base, seg, n_classes, rows_power2_segmentation, mean, std, clamp=None, dtype=torch.bfloat16,
+                  device=0):
+        """base: the reference's model.base, the nn.Sequential of the nine children layer0 .. layer8
+        (DRNDownsampled.py:77)."""
+        layers = list(base)
+        if len(layers) != 9:
+            raise core.CoreError(f"base has {len(layers)} children, not the nine layer0 .. layer8")
+        return cls(*layers, seg, n_classes, rows_power2_segmentation, mean, std, clamp=clamp, dtype=dtype, device=device)
+
+    @property
+    def launches(self):
+        return self.stem.launches + self.downsampling.launches
+
+    @torch.no_grad()
+    def forward(self, image, want_cnn_out=False):
+        """image: uint8 [n][rows][cols][3] on the device.  Returns what DrnTail.forward returns."""
+        return self.downsampling.forward(self.stem.forward(image), want_cnn_out=want_cnn_out)
+
+    __call__ = forward
 
 
 class DrnDownsampling:

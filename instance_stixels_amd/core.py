@@ -49,6 +49,7 @@ EXPORTS = [
     "is_conv3x3_packed_bytes", "is_conv3x3_pack_weights", "is_conv3x3_bn_relu",
     "is_conv_packed_bytes", "is_conv_pack_weights", "is_conv_bn",
     "is_conv_bn_stride",
+    "is_stem_packed_bytes", "is_stem_pack_weights", "is_stem",
 ]
 RENDER_MAX_LABELS = 64    # IS_RENDER_MAX_LABELS
 RENDER_MAX_CLASSES = 256  # IS_RENDER_MAX_CLASSES
@@ -269,6 +270,14 @@ class ConvBnStrideArgs(ctypes.Structure):
                 ("reserved", ci * 4)]
 
 
+class StemArgs(ctypes.Structure):
+    """is_stem_args: zero-initialised by ctypes; device pointers as ints."""
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    _fields_ = [("d_image", vp), ("n_images", ci), ("rows", ci), ("cols", ci), ("d_lut", vp), ("dtype", ci),
+                ("d_packed", vp), ("d_scale0", vp), ("d_shift0", vp), ("d_scale1", vp), ("d_shift1", vp), ("d_mid", vp),
+                ("d_out", vp), ("reserved", ci * 4)]
+
+
 class RoadParams(ctypes.Structure):
     """is_road_params: one frame's road, the layout of Stixels::RoadParameters (16 bytes)"""
     _fields_ = [("vhor", ctypes.c_int), ("tilt", ctypes.c_float), ("height", ctypes.c_float),
@@ -377,6 +386,10 @@ def lib():
         L.is_conv_pack_weights.argtypes = [vp, ci, ci, ci, ci, vp, vp]
         L.is_conv_bn.argtypes = [ctypes.POINTER(ConvBnArgs), vp]
         L.is_conv_bn_stride.argtypes = [ctypes.POINTER(ConvBnStrideArgs), vp]
+        L.is_stem_packed_bytes.argtypes = [ci]
+        L.is_stem_packed_bytes.restype = ctypes.c_size_t
+        L.is_stem_pack_weights.argtypes = [vp, vp, ci, vp, vp]
+        L.is_stem.argtypes = [ctypes.POINTER(StemArgs), vp]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
         L.is_get_device.argtypes = [ctypes.POINTER(ci)]
@@ -1366,6 +1379,90 @@ def conv_bn_stride(features, packed, scale, shift, kernel, stride, dilation=1, r
     enqueued on the current torch stream.  canary > 0: as conv3x3_bn_relu."""
     return _conv_launch("is_conv", "is_conv_bn_stride", ConvBnStrideArgs, True, features, packed, scale, shift, kernel,
                         dilation, residual, relu, out_dtype, canary, stride=stride)
+
+
+def stem_packed_bytes(dtype):
+    """is_stem_packed_bytes: the bytes of the stem's packed weights (0: a dtype code that is no half)."""
+    return int(lib().is_stem_packed_bytes(int(dtype)))
+
+
+def stem_pack_weights(w0, w1, dtype, device=0):
+    """is_stem_pack_weights (instance_stixels_core.h f20): layer0's conv.weight [16][3][7][7] and layer1's
+    [16][16][3][3], tensors or arrays, rounded to torch.float16 or torch.bfloat16 and laid out for is_stem.  Returns a
+    uint8 device tensor of stem_packed_bytes(...) bytes (on w0's device if it is a device tensor, else on
+    cuda:`device`); enqueued on the current torch stream, once per model.  Every refusal is made before a weight goes
+    to a device."""
+    import torch
+    codes = _head_codes(halves_only=True)
+    if dtype not in codes:
+        raise CoreError(f"dtype {dtype} is neither torch.float16 nor torch.bfloat16")
+    ws = [w if torch.is_tensor(w) else torch.from_numpy(np.ascontiguousarray(w, np.float32)) for w in (w0, w1)]
+    if tuple(ws[0].shape) != (16, 3, 7, 7) or tuple(ws[1].shape) != (16, 16, 3, 3):
+        raise CoreError("w0 must be [16][3][7][7] and w1 [16][16][3][3]")
+    dev = ws[0].device if ws[0].is_cuda else device if isinstance(device, torch.device) else torch.device("cuda", device)
+    ws = [w.detach().to(device=dev, dtype=torch.float32).contiguous() for w in ws]
+    with torch.cuda.device(dev):
+        packed = torch.empty((stem_packed_bytes(codes[dtype]),), dtype=torch.uint8, device=dev)
+        _check(lib().is_stem_pack_weights(ws[0].data_ptr(), ws[1].data_ptr(), codes[dtype], packed.data_ptr(),
+                                          _current_stream(dev)), "is_stem_pack_weights")
+    return packed
+
+
+def stem_ptr(stream=0, **fields):
+    """is_stem on raw device pointers (ints): fields are those of StemArgs.  Asynchronous on `stream`; returns the
+    return code and raises nothing (the tests check IS_EINVAL)."""
+    a = _with_reserved(StemArgs, fields)
+    return lib().is_stem(ctypes.byref(a), ctypes.c_void_p(int(stream)))
+
+
+def stem(image, lut, packed, scale0, shift0, scale1, shift1, want_mid=False, canary=0):
+    """The backbone's stem of a batch in one launch (is_stem, instance_stixels_core.h f20): the table look-up of the
+    image's bytes, layer0 (7x7, 3 -> 16, folded BatchNorm, ReLU) and layer1 (3x3, 16 -> 16, folded BatchNorm, ReLU),
+    with the numerics the header fixes.
+
+    image       device tensor [n][rows][cols][3] uint8; made contiguous
+    lut         [3][256] float16 or bfloat16 on the image's device (cnn.input_table): its dtype is the launch's
+    packed      stem_pack_weights(w0, w1, lut.dtype) on the same device
+    scale0 .. shift1   [16] float32 each, tensors or arrays: the folded BatchNorms (cnn.fold_batchnorm)
+
+    Returns layer1's output [n][16][rows][cols] of the table's dtype on the image's device, enqueued on the current
+    torch stream; with want_mid (out, mid), layer0's output in the same shape.  canary > 0: the outputs are allocated
+    with that many guard elements in front and behind, filled with a pattern, and {"out": (front, back, pattern)[,
+    "mid": ...]} of numpy copies of the guards is returned last (one synchronisation)."""
+    import torch
+    if not torch.is_tensor(image) or not image.is_cuda or image.dtype != torch.uint8 or image.dim() != 4 or \
+            int(image.shape[3]) != 3:
+        raise CoreError("image must be a uint8 device tensor [n][rows][cols][3]")
+    dev = image.device
+    codes = _head_codes(halves_only=True)
+    if not torch.is_tensor(lut) or lut.device != dev or lut.dtype not in codes or tuple(lut.shape) != (3, 256):
+        raise CoreError("lut must be a float16 or bfloat16 tensor [3][256] on the image's device")
+    dtype = lut.dtype
+    if not torch.is_tensor(packed) or packed.device != dev or packed.dtype != torch.uint8 or \
+            not packed.is_contiguous() or int(packed.numel()) != stem_packed_bytes(codes[dtype]):
+        raise CoreError(f"packed must be stem_pack_weights' uint8 tensor for {dtype} on the image's device")
+    folds = [_f32_on(v, dev).reshape(-1) for v in (scale0, shift0, scale1, shift1)]
+    if any(int(f.numel()) != 16 for f in folds):
+        raise CoreError("scale0, shift0, scale1 and shift1 must hold 16 channels each")
+    x, table = image.contiguous(), lut.contiguous()
+    n, H, W = (int(v) for v in x.shape[:3])
+    g = int(canary)
+    with torch.cuda.device(dev):
+        full, flat, pattern = _guarded_float(n * 16 * H * W, dtype, dev, g)
+        out, named = flat.view(n, 16, H, W), {"out": (full, pattern)}
+        mid = None
+        if want_mid:
+            full_mid, flat_mid, _ = _guarded_float(n * 16 * H * W, dtype, dev, g)
+            mid, named["mid"] = flat_mid.view(n, 16, H, W), (full_mid, pattern)
+        a = StemArgs(d_image=x.data_ptr(), n_images=n, rows=H, cols=W, d_lut=table.data_ptr(), dtype=codes[dtype],
+                     d_packed=packed.data_ptr(), d_scale0=folds[0].data_ptr(), d_shift0=folds[1].data_ptr(),
+                     d_scale1=folds[2].data_ptr(), d_shift1=folds[3].data_ptr(),
+                     d_mid=mid.data_ptr() if want_mid else None, d_out=out.data_ptr())
+        _check(lib().is_stem(ctypes.byref(a), _current_stream(dev)), "is_stem")
+        ret = (out, mid) if want_mid else (out,)
+        if g:
+            ret = ret + (_guards(named, g, g),)
+    return ret if len(ret) > 1 else ret[0]
 
 
 def _with_reserved(cls, fields):

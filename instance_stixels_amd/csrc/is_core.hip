@@ -1295,6 +1295,49 @@ int is_conv3x3_bn_relu(const is_conv3x3_args* a, void* stream) {
     return is_conv_bn(&b, stream);
 }
 
+/* ---- f20: the backbone's stem, image bytes to layer1's output (is_k_stem.hip).  One checker, one launcher. ---- */
+static const char* stem_dtype_fault(int dtype) {
+    return dtype != IS_HEAD_F16 && dtype != IS_HEAD_BF16 ? "dtype is neither IS_HEAD_F16 nor IS_HEAD_BF16" : nullptr;
+}
+
+size_t is_stem_packed_bytes(int dtype) { return stem_dtype_fault(dtype) ? 0 : isk_stem_packed_bytes(); }
+
+int is_stem_pack_weights(const float* d_w0, const float* d_w1, int dtype, void* d_packed, void* stream) {
+    if (!d_w0 || !d_w1 || !d_packed) return fail_arg("null d_w0, d_w1 or d_packed");
+    if (const char* fault = stem_dtype_fault(dtype)) return fail_arg(fault);
+    if (misaligned(4, d_w0, d_w1)) return fail_arg("d_w0 and d_w1 must be 4-byte aligned");
+    if (misaligned(16, d_packed)) return fail_arg("d_packed must be 16-byte aligned");
+    HIP_TRY(isk_launch_stem_pack(d_w0, d_w1, dtype, d_packed, (hipStream_t)stream));
+    return IS_OK;
+}
+
+int is_stem(const is_stem_args* a, void* stream) {
+    if (!a) return fail_arg("null args");
+    if (!a->d_image || !a->d_lut || !a->d_packed || !a->d_scale0 || !a->d_shift0 || !a->d_scale1 || !a->d_shift1 || !a->d_out)
+        return fail_arg("null d_image, d_lut, d_packed, d_scale0, d_shift0, d_scale1, d_shift1 or d_out");
+    if (const char* fault = stem_dtype_fault(a->dtype)) return fail_arg(fault);
+    if (a->n_images < 1 || a->n_images > 65535) return fail_arg("n_images outside [1, 65535]");
+    if (a->rows < 1 || a->rows > 32767 || a->cols < 1 || a->cols > 32767) return fail_arg("rows and cols must be in [1, 32767]");
+    if (misaligned(16, a->d_packed)) return fail_arg("d_packed must be 16-byte aligned");
+    if (misaligned(2, a->d_lut)) return fail_arg("d_lut must be aligned to its element");
+    if (misaligned(2, a->d_mid)) return fail_arg("d_mid must be aligned to its element");
+    if (misaligned(2, a->d_out)) return fail_arg("d_out must be aligned to its element");
+    if (misaligned(4, a->d_scale0, a->d_shift0, a->d_scale1, a->d_shift1))
+        return fail_arg("d_scale0, d_shift0, d_scale1 and d_shift1 must be 4-byte aligned");
+    /* each buffer at its own size (at most 2^16 * 2^30 pixels of 32 bytes: no overflow) */
+    const uint64_t pixels = (uint64_t)a->n_images * a->rows * a->cols, image_bytes = pixels * 3, plane_bytes = pixels * 16 * 2;
+    const uint64_t image0 = (uint64_t)(uintptr_t)a->d_image, out0 = (uint64_t)(uintptr_t)a->d_out, mid0 = (uint64_t)(uintptr_t)a->d_mid;
+    if (a->d_mid && mid0 < out0 + plane_bytes && out0 < mid0 + plane_bytes) return fail_arg("d_out overlaps d_mid");
+    if (image0 < out0 + plane_bytes && out0 < image0 + image_bytes)
+        return fail_arg("d_out overlaps d_image: other workgroups still read the image");
+    if (a->d_mid && image0 < mid0 + plane_bytes && mid0 < image0 + image_bytes)
+        return fail_arg("d_mid overlaps d_image: other workgroups still read the image");
+    /* (last: a call that is refused for this alone has passed every check above) */
+    if (const char* fault = reserved_fault(a->reserved)) return fail_arg(fault);
+    HIP_TRY(isk_launch_stem(a, (hipStream_t)stream));
+    return IS_OK;
+}
+
 /* ---- f9: per-instance objects and contours (is_k_objects.hip) ---- */
 int is_instance_objects(const is_instance_objects_args* a, void* stream) {
     if (!a) return fail_arg("null args");

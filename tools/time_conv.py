@@ -1,5 +1,5 @@
 """The backbone's convolutions on the device (f17: is_conv3x3_bn_relu, core.conv3x3_bn_relu; f18: is_conv_bn,
-core.conv_bn, cnn.ResidualBlock; f19: is_conv_bn_stride, core.conv_bn_stride, cnn.StridedResidualBlock) against what
+core.conv_bn, cnn.ResidualBlock; f19: is_conv_bn_stride, core.conv_bn_stride, cnn.StridedResidualBlock; f20: is_stem, core.stem) against what
 they replace and against themselves, on the same device tensors (GPU
 box).
 
@@ -26,11 +26,16 @@ comma-separated), for fp16 and bf16 features [n][.][rows8][cols8] with half outp
   F.conv2d(stride) + F.batch_norm (+ residual) (+ F.relu), and layer2 + layer3 + layer4 whole (11 launches) against the
   torch modules.  --strided-n frames per call (default --n): a slice of the batch where torch's intermediates or its
   warm-up are too large; the row says how many.
+- stem (not in the default --parts): core.stem on the camera's bytes [n][--rows][--cols][3], with and without d_mid,
+  against torch's sequence on the same bytes: byte -> float / 255 -> normalise -> half -> conv2d 7x7 -> batch_norm ->
+  relu -> conv2d 3x3 -> batch_norm -> relu.  `compulsory_gb` is 3 + 32 bytes per pixel.  --stem-n frames per call
+  (default --n) where torch's intermediates or its warm-up are too large; the row says how many.
 --no-torch leaves the torch arms out (and alone allows fewer than 10 iterations, for a counter run).  torch's first
 convolution of a shape takes 30 - 160 s: run the dtypes, and if need be the parts, in separate commands.
 
     python tools/time_conv.py [--n 64 --C 512 --rows8 128 --cols8 256 --iters 20 --mhz 2400 --cus 256 --dtypes fp16,bf16
-                               --parts tail,residual,1x1,layers[,strided] --rows 1024 --cols 2048 --strided-n 64
+                               --parts tail,residual,1x1,layers[,strided][,stem] --rows 1024 --cols 2048 --strided-n 64
+                               --stem-n 64
                                --no-torch]
 """
 import argparse
@@ -61,10 +66,11 @@ def main():
     ap.add_argument("--dp-n", type=int, default=0, help="0: the whole batch (a shape the library is already tuned for)")
     ap.add_argument("--dtypes", default="fp16,bf16", help="comma-separated subset of fp16,bf16")
     ap.add_argument("--parts", default="tail,residual,1x1,layers",
-                    help="comma-separated subset of tail,residual,1x1,layers,strided")
+                    help="comma-separated subset of tail,residual,1x1,layers,strided,stem")
     ap.add_argument("--rows", type=int, default=1024, help="rows of layer1's output (the `strided` part)")
     ap.add_argument("--cols", type=int, default=2048)
     ap.add_argument("--strided-n", type=int, default=0, help="frames per call of the `strided` part; 0: --n")
+    ap.add_argument("--stem-n", type=int, default=0, help="frames per call of the `stem` part; 0: --n")
     ap.add_argument("--no-torch", action="store_true", help="time the library's launches alone")
     a = ap.parse_args()
     if a.iters < 10 and not a.no_torch:
@@ -343,6 +349,39 @@ def main():
             out[name + "_strided_layers"] = row
             note(name, "strided layers", json.dumps(row))
             del x, ours, arms
+            torch.cuda.empty_cache()
+        if "stem" in parts:
+            m, H1, W1 = a.stem_n or n, a.rows, a.cols
+            mean, std = (0.290101, 0.328081, 0.286964), (0.182954, 0.186566, 0.184475)
+            image = torch.randint(0, 256, (m, H1, W1, 3), device=dev, dtype=torch.uint8)
+            w0, w1, stats0, stats1 = weight(16, 3, 7), weight(16, 16, 3), bn_stats(16), bn_stats(16)
+            lut = cnn.input_table(mean, std, dtype).to(dev)
+            packed, folds = core.stem_pack_weights(w0, w1, dtype), fold(*stats0) + fold(*stats1)
+            arms = {"new": lambda: core.stem(image, lut, packed, *folds),
+                    "new_with_mid": lambda: core.stem(image, lut, packed, *folds, want_mid=True)}
+            if not a.no_torch:
+                w0d, w1d, bn0, bn1 = w0.to(dtype), w1.to(dtype), [t.to(dtype) for t in stats0], [t.to(dtype) for t in stats1]
+                w0_cl, w1_cl = channels_last(w0d, w1d)
+                mean_t, std_t = (torch.tensor(v, device=dev).view(1, 3, 1, 1) for v in (mean, std))
+
+                def torch_stem(cl):
+                    x = ((image.permute(0, 3, 1, 2).float() / 255 - mean_t) / std_t).to(dtype)
+                    x = x.contiguous(memory_format=torch.channels_last) if cl else x.contiguous()
+                    y = torch_conv_bn(x, w0_cl if cl else w0d, 1, bn0, True)
+                    return torch_conv_bn(y, w1_cl if cl else w1d, 1, bn1, True)
+                arms["torch_contiguous"] = lambda: torch_stem(False)
+                arms["torch_channels_last"] = lambda: torch_stem(True)
+            row, med = measure(name + " stem", arms)
+            pixels = m * H1 * W1
+            gb, tflop = pixels * 35 / 1e9, 2.0 * 16 * (147 + 144) * pixels / 1e12
+            row.update(frames=m, shape_in=[m, H1, W1, 3], shape_out=[m, 16, H1, W1], compulsory_gb=round(gb, 3),
+                       tflop=round(tflop, 4), new_gb_per_s=round(gb / (med["new"] * 1e-3), 1),
+                       new_tflops=round(tflop / (med["new"] * 1e-3), 1),
+                       with_mid_gb_per_s=round(pixels * 67 / 1e9 / (med["new_with_mid"] * 1e-3), 1))
+            against_torch(row, med)
+            out[name + "_stem"] = row
+            note(name, "stem", json.dumps(row))
+            del image, arms
             torch.cuda.empty_cache()
     print(json.dumps(out), flush=True)
 
