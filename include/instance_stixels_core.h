@@ -1445,6 +1445,106 @@ int is_stem_pack_weights(const float* d_w0 /*[16][3][7][7]*/, const float* d_w1 
  * image, each taken at its own byte size; and, last, a non-zero reserved field. */
 int is_stem(const is_stem_args* args, void* stream);
 
+/* ---- f21: the backward pass of convolution + BatchNorm (+ residual) (+ ReLU), stride 1 (is_k_conv_backward.hip) ------
+ * What fine-tuning more than the head needs (the reference trains the whole base, optim_parameters yields
+ * base.parameters() in all but one configuration of tools/CNN_training/train.py): the gradients of is_conv_bn's output
+ * with respect to the features, the fp32 master weight, the folded scale and shift and the residual operand, by f14's
+ * rules: every summation order fixed by the shape alone, no floating-point atomics, the same bytes on every run.
+ *
+ * BatchNorm is FROZEN at its running statistics: (scale, shift) are the folded pair the forward takes, and this is
+ * the backward of exactly that forward.  The reference's train.py:947 runs NN.train() with batch statistics; that is a
+ * different forward and is not built.  Stride 1 only (layer5 .. layer8; stride 2 and the stem are not built).
+ *
+ * Forward (f18), a = conv(x, w):  v = fmaf(scale[co], a, shift[co]);  v += residual;  v = max(v, 0) with relu.
+ * P = rows8 * cols8, taps = kernel * kernel, d = dilation, w_half = the half rounding of w that is_conv_pack_weights makes.
+ *
+ *   gh [n][co][P], half dtype.  gh = round_half(dY) where relu is 0 or the STORED out is > 0, else +0 (round to nearest
+ *             even; a dY of the half dtype passes through).  An output that rounded to 0 is inactive, as torch's ReLU
+ *             backward.  gh is the gradient with respect to the residual operand (d_grad_pre), and the one operand
+ *             every other gradient is computed from.  fp16 under- and overflow of gh is the caller's loss scaling.
+ *   dshift[co] = (float) sum (double)gh[n][co][p], in binary64: a block of 256 threads takes 2048 consecutive p of one
+ *             plane, a thread 8 of them in increasing p, then an LDS tree (t += t + s, s = 128 .. 1); one block per co
+ *             adds the blocks' sums, n outer and block inner, as contiguous thread ranges and the same tree.
+ *   dX [n][ci][P], half dtype or fp32: the stride-1 convolution of gh, same kernel, dilation and padding, with
+ *             wT[ci][co][taps - 1 - tap] = round_half(scale[co] * w_half[co][ci][tap]) (the product in fp32, rounded
+ *             once), run by is_conv_bn's own launch with the channels swapped, scale 1, shift 0, relu 0: f18's
+ *             operands, order, bound and determinism word for word.  d_grad_features_add, dX's shape in the half
+ *             dtype, is that launch's residual operand: added in fp32 before the single final rounding.  Needs
+ *             channels_in % 32 == 0.  A frame's gh and dX do not depend on n_images or its position in the batch.
+ *   G[co][ci][tap] = sum over n, y, x of gh[n][co][y][x] * x[n][ci][y + (ky - 1) d][x + (kx - 1) d]; a tap outside
+ *             the image contributes nothing.  The contraction is split and the split is part of the contract: chunk
+ *             (i, j) is image i, rows [j B, min((j + 1) B, rows8)), B = IS_CONV_BACKWARD_BAND for every shape.  Inside a
+ *             chunk ONE fp32 MFMA accumulator per (co, ci, tap), fed by v_mfma_f32_32x32x16_{f16,bf16} in an order
+ *             the shape fixes: 32-pixel segments of the rows in increasing column; in a segment the chunk's rows by
+ *             residue class mod d (kernel 1: d = 1) and increasing inside a class; in a row the two 16-pixel steps in
+ *             increasing column (the lanes past the row's end are zero); the operands are
+ *             half values, their products exact in fp32; the summation of the 16 products inside one instruction is
+ *             the hardware's.  As f17, pinned by a derived bound plus exact-arithmetic inputs, not by a C loop.
+ *             Gsum = sum (double)part[i][j], i outer, j inner, both increasing.
+ *   dW[co][ci][tap] = (float)((double)scale[co] * Gsum[co][ci][tap]), rounded once; conv.weight's layout; the gradient
+ *             with respect to the fp32 master weight, straight through the half rounding.
+ *   dscale[co] = (float) sum (double)w_half[co][ci][tap] * Gsum[co][ci][tap] in binary64, in increasing (ci, tap):
+ *             contiguous ranges of 256 threads, then the LDS tree above.
+ *   Every output is optional, at least one is asked for; leaving one out changes no byte of the others and skips the
+ *   launches it alone needs.  Non-finite values give unspecified values, never an access outside the buffers; no
+ *   address depends on a value.
+ *
+ * Zero-initialise, then set the fields.  All arrays on the current device.
+ *   d_features, dtype, n_images, channels_in, channels_out, rows8, cols8, kernel, dilation   as in is_conv_bn_args
+ *   d_weight            conv.weight [channels_out][channels_in][kernel][kernel] fp32 (NOT the packed weights)
+ *   d_scale             [channels_out] fp32
+ *   d_out, out_dtype    the forward's saved output [n][channels_out][rows8][cols8], `dtype` or IS_HEAD_F32; read with
+ *                       relu = 1 only (it may be NULL with relu = 0)
+ *   d_grad_out, grad_out_dtype, grad_image_stride   dY, `dtype` or IS_HEAD_F32: frame f starts at d_grad_out + f *
+ *                       stride (elements), its planes contiguous [channels_out][rows8][cols8]; stride >= channels_out P
+ *   d_grad_features, grad_features_dtype   dX, `dtype` or IS_HEAD_F32;  d_grad_features_add: NULL or `dtype`, with dX only
+ *   d_grad_weight, d_grad_scale, d_grad_shift   fp32;  d_grad_pre: gh, `dtype`
+ *   d_scratch           16-byte aligned, scratch_bytes >= is_conv_bn_backward_scratch_bytes(...); its contents mean
+ *                       nothing between calls
+ *   reserved            0 */
+#ifndef IS_CONV_BACKWARD_BAND /* (an experiment build may define another; the product's value is this one) */
+#define IS_CONV_BACKWARD_BAND 32
+#endif
+typedef struct is_conv_bn_backward_args {
+    const void* d_features;
+    int dtype; /* IS_HEAD_F16 | IS_HEAD_BF16 */
+    int n_images, channels_in, channels_out, rows8, cols8;
+    int kernel;   /* 3 or 1 */
+    int dilation; /* kernel 3: [1, 8];  kernel 1: must be 1 */
+    const float* d_weight;
+    const float* d_scale;
+    const void* d_out;
+    int out_dtype;
+    int relu;
+    const void* d_grad_out;
+    int grad_out_dtype;
+    long long grad_image_stride;
+    void* d_grad_features;
+    int grad_features_dtype;
+    const void* d_grad_features_add;
+    float* d_grad_weight;
+    float* d_grad_scale;
+    float* d_grad_shift;
+    void* d_grad_pre;
+    void* d_scratch;
+    size_t scratch_bytes;
+    int reserved[4]; /* 0 */
+} is_conv_bn_backward_args;
+
+/* Bytes of d_scratch for a call of that shape (0 for a shape the call refuses): gh, the transposed pack, the dshift
+ * block sums, Gsum in binary64 and n_images * ceil(rows8 / B) partials of channels_out * channels_in * taps fp32. */
+size_t is_conv_bn_backward_scratch_bytes(int n_images, int channels_in, int channels_out, int rows8, int cols8, int kernel,
+                                         int dtype);
+/* Up to six launches on `stream` (gh and the dshift block sums; the transposed pack; dX by is_conv_bn's launch; the
+ * chunk partials; their reduction; dscale and dshift per channel), fewer with outputs left out; asynchronous and
+ * stream-ordered; no allocation, copy or synchronisation.  IS_EINVAL, with the reason in is_last_error() and before
+ * the device is touched, for everything is_conv_bn refuses, no output asked for, d_grad_features with channels_in %
+ * 32 != 0, d_grad_features_add without d_grad_features, a dtype of out, dY or dX that is neither `dtype` nor
+ * IS_HEAD_F32, a stride below channels_out * P, misaligned pointers, output bytes that overlap an input's or another
+ * output's, scratch that is too small or misaligned and, last, a non-zero reserved field.  There is no stride field:
+ * a stride-2 layer cannot be expressed, and the Python layer refuses it with a message. */
+int is_conv_bn_backward(const is_conv_bn_backward_args* args, void* stream);
+
 /* ---- f9: per-instance objects and their contours (is_k_objects.hip) ------------------------------------------------
  * What the reference's consumers reduce on the host from the per-stixel output: the top-down view
  * (tools/visualization/clustering_visualization.py:563-792: per instance and column the closest stixel, connected

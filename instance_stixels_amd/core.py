@@ -50,6 +50,7 @@ EXPORTS = [
     "is_conv_packed_bytes", "is_conv_pack_weights", "is_conv_bn",
     "is_conv_bn_stride",
     "is_stem_packed_bytes", "is_stem_pack_weights", "is_stem",
+    "is_conv_bn_backward_scratch_bytes", "is_conv_bn_backward",
 ]
 RENDER_MAX_LABELS = 64    # IS_RENDER_MAX_LABELS
 RENDER_MAX_CLASSES = 256  # IS_RENDER_MAX_CLASSES
@@ -278,6 +279,20 @@ class StemArgs(ctypes.Structure):
                 ("d_out", vp), ("reserved", ci * 4)]
 
 
+CONV_BACKWARD_BAND = 32  # IS_CONV_BACKWARD_BAND
+
+
+class ConvBnBackwardArgs(ctypes.Structure):
+    """is_conv_bn_backward_args: zero-initialised by ctypes; device pointers as ints."""
+    vp, ci, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    _fields_ = [("d_features", vp), ("dtype", ci), ("n_images", ci), ("channels_in", ci), ("channels_out", ci),
+                ("rows8", ci), ("cols8", ci), ("kernel", ci), ("dilation", ci), ("d_weight", vp), ("d_scale", vp),
+                ("d_out", vp), ("out_dtype", ci), ("relu", ci), ("d_grad_out", vp), ("grad_out_dtype", ci),
+                ("grad_image_stride", ll), ("d_grad_features", vp), ("grad_features_dtype", ci),
+                ("d_grad_features_add", vp), ("d_grad_weight", vp), ("d_grad_scale", vp), ("d_grad_shift", vp),
+                ("d_grad_pre", vp), ("d_scratch", vp), ("scratch_bytes", ctypes.c_size_t), ("reserved", ci * 4)]
+
+
 class RoadParams(ctypes.Structure):
     """is_road_params: one frame's road, the layout of Stixels::RoadParameters (16 bytes)"""
     _fields_ = [("vhor", ctypes.c_int), ("tilt", ctypes.c_float), ("height", ctypes.c_float),
@@ -390,6 +405,9 @@ def lib():
         L.is_stem_packed_bytes.restype = ctypes.c_size_t
         L.is_stem_pack_weights.argtypes = [vp, vp, ci, vp, vp]
         L.is_stem.argtypes = [ctypes.POINTER(StemArgs), vp]
+        L.is_conv_bn_backward_scratch_bytes.argtypes = [ci, ci, ci, ci, ci, ci, ci]
+        L.is_conv_bn_backward_scratch_bytes.restype = ctypes.c_size_t
+        L.is_conv_bn_backward.argtypes = [ctypes.POINTER(ConvBnBackwardArgs), vp]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
         L.is_get_device.argtypes = [ctypes.POINTER(ci)]
@@ -1594,6 +1612,124 @@ def segmentation_head_backward(features, weight, cnn_out, grad_out, n_classes, w
         if g:
             out["guards"] = _guards(named, g, gs)
     return out
+
+
+def conv_bn_backward_scratch_bytes(n_images, channels_in, channels_out, rows8, cols8, kernel, dtype):
+    """is_conv_bn_backward_scratch_bytes: the scratch a call of that shape needs (0: a refused shape)."""
+    return int(lib().is_conv_bn_backward_scratch_bytes(int(n_images), int(channels_in), int(channels_out), int(rows8),
+                                                       int(cols8), int(kernel), int(dtype)))
+
+
+def conv_bn_backward_ptr(stream=0, **fields):
+    """is_conv_bn_backward on raw device pointers (ints): fields are those of ConvBnBackwardArgs.  Asynchronous on
+    `stream`; returns the return code and raises nothing (the tests check IS_EINVAL)."""
+    a = _with_reserved(ConvBnBackwardArgs, fields)
+    return lib().is_conv_bn_backward(ctypes.byref(a), ctypes.c_void_p(int(stream)))
+
+
+def conv_bn_backward(features, weight, scale, out, grad_out, kernel, dilation=1, relu=True, want_features=True,
+                     want_weight=True, want_scale=True, want_shift=True, want_pre=False, features_add=None,
+                     grad_features_dtype=None, canary=0):
+    """The backward pass of conv_bn at stride 1 with BatchNorm frozen at its running statistics (is_conv_bn_backward,
+    instance_stixels_core.h f21), with the numerics the header fixes.
+
+    features    device tensor [n][channels_in][rows8][cols8], float16 or bfloat16 (made contiguous)
+    weight      conv.weight [channels_out][channels_in][kernel][kernel] float32 (the master weight, not the pack)
+    scale       [channels_out] float32: the folded BatchNorm scale the forward ran with
+    out         the forward's saved output [n][channels_out][rows8][cols8], the features' dtype or float32; read with
+                relu only (it may be None without)
+    grad_out    the gradient with respect to `out`, the features' dtype or float32; read in place when each frame's
+                planes are contiguous (a batch stride above channels_out * rows8 * cols8 is allowed)
+    features_add   None, or a tensor of the features' shape and dtype that is added to "features" in fp32 before its
+                single rounding (the other gradient path into a block's input)
+    grad_features_dtype   None (the features' dtype) or torch.float32
+
+    Returns a dict with the requested ones of "features", "weight" (conv.weight's shape), "scale", "shift"
+    [channels_out] (float32) and "pre" [n][channels_out][rows8][cols8] (the features' dtype: the masked gradient, which
+    is the gradient with respect to the forward's residual operand), on the features' device, enqueued on the current
+    torch stream; the scratch is allocated here.  canary > 0: every output and the scratch get that many guard
+    elements in front and behind, and the dict has "guards": {name: (front, back, pattern)} (one synchronisation)."""
+    import torch
+    x = features
+    if not torch.is_tensor(x) or not x.is_cuda or x.dim() != 4:
+        raise CoreError("features must be a device tensor [n][channels_in][rows8][cols8]")
+    codes = _head_codes(halves_only=True)
+    if x.dtype not in codes:
+        raise CoreError(f"features dtype {x.dtype} is neither float16 nor bfloat16 (fp32 features are not built)")
+    x = x.detach().contiguous()
+    dev = x.device
+    n, cin, Hs, Ws = (int(v) for v in x.shape)
+    k = int(kernel)
+    w = weight.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if w.dim() != 4 or int(w.shape[1]) != cin or tuple(int(v) for v in w.shape[2:]) != (k, k):
+        raise CoreError(f"weight must be [channels_out][{cin}][{k}][{k}]")
+    cout = int(w.shape[0])
+    sc = _f32_on(scale, dev).reshape(-1)
+    if int(sc.numel()) != cout:
+        raise CoreError(f"scale holds {int(sc.numel())} channels, the weight {cout}")
+    shape = (n, cout, Hs, Ws)
+
+    def half_or_f32(t, name):
+        if not torch.is_tensor(t) or t.device != dev or t.dtype not in (x.dtype, torch.float32) or \
+                tuple(int(v) for v in t.shape) != shape:
+            raise CoreError(f"{name} must be a {x.dtype} or float32 tensor {shape} on the features' device")
+        return HEAD_F32 if t.dtype == torch.float32 else codes[x.dtype]
+
+    y, y_code = None, codes[x.dtype]
+    if relu:
+        y_code = half_or_f32(out, "out")
+        y = out.detach().contiguous()
+    gy_code = half_or_f32(grad_out, "grad_out")
+    gy, gy_stride = _frame_planes(grad_out.detach(), cout)
+    xdt = x.dtype if grad_features_dtype is None else grad_features_dtype
+    if xdt != x.dtype and xdt != torch.float32:
+        raise CoreError(f"grad_features_dtype {xdt} is neither the features' dtype nor float32")
+    add = None
+    if features_add is not None:
+        if not want_features:
+            raise CoreError("features_add without want_features")
+        add = features_add
+        if not torch.is_tensor(add) or add.device != dev or add.dtype != x.dtype or tuple(add.shape) != tuple(x.shape):
+            raise CoreError(f"features_add must be a {x.dtype} tensor of the features' shape on their device")
+        add = add.detach().contiguous()
+    if not (want_features or want_weight or want_scale or want_shift or want_pre):
+        raise CoreError("no gradient is asked for")
+    g = int(canary)
+    with torch.cuda.device(dev):
+        nbytes = _scratch_or_raise(conv_bn_backward_scratch_bytes,
+                                   dict(n_images=n, channels_in=cin, channels_out=cout, rows8=Hs, cols8=Ws, kernel=k),
+                                   dtype=codes[x.dtype])
+        named, ret = {}, {}
+        ptr = {"features": None, "weight": None, "scale": None, "shift": None, "pre": None}
+        for name, want, view, dtype in (
+                ("features", want_features, (n, cin, Hs, Ws), xdt),
+                ("weight", want_weight, (cout, cin, k, k), torch.float32),
+                ("scale", want_scale, (cout,), torch.float32),
+                ("shift", want_shift, (cout,), torch.float32),
+                ("pre", want_pre, shape, x.dtype)):
+            if not want:
+                continue
+            full, t, pat = _guarded_float(int(np.prod(view)), dtype, dev, g)
+            named[name] = (full, pat)
+            ret[name] = t.view(view)
+            ptr[name] = t.data_ptr()
+        # (16 guard bytes keep the scratch 16-byte aligned; torch's allocations are)
+        gs = (g + 15) // 16 * 16
+        sfull, scratch = _guarded(nbytes, torch.uint8, dev, gs, 0xA5)
+        named["scratch"] = (sfull, np.uint8(0xA5))
+        a = ConvBnBackwardArgs(
+            d_features=x.data_ptr(), dtype=codes[x.dtype], n_images=n, channels_in=cin, channels_out=cout, rows8=Hs,
+            cols8=Ws, kernel=k, dilation=int(dilation), d_weight=w.data_ptr(), d_scale=sc.data_ptr(),
+            d_out=y.data_ptr() if y is not None else None, out_dtype=y_code, relu=int(bool(relu)),
+            d_grad_out=gy.data_ptr(), grad_out_dtype=gy_code, grad_image_stride=gy_stride,
+            d_grad_features=ptr["features"], grad_features_dtype=HEAD_F32 if xdt == torch.float32 else codes[x.dtype],
+            d_grad_features_add=add.data_ptr() if add is not None else None, d_grad_weight=ptr["weight"],
+            d_grad_scale=ptr["scale"], d_grad_shift=ptr["shift"], d_grad_pre=ptr["pre"],
+            d_scratch=scratch.data_ptr(), scratch_bytes=nbytes)
+        _check(lib().is_conv_bn_backward(ctypes.byref(a), _current_stream(dev)), "is_conv_bn_backward")
+        if g:
+            ret["guards"] = _guards(named, g, gs)
+    return ret
 
 
 def semantic_nll_scratch_bytes(n_images, rows8, cols8):

@@ -1295,6 +1295,96 @@ int is_conv3x3_bn_relu(const is_conv3x3_args* a, void* stream) {
     return is_conv_bn(&b, stream);
 }
 
+/* ---- f21: the backward pass of is_conv_bn (is_k_conv_backward.hip).  One checker, one launcher. ---- */
+static const char* conv_backward_shape_fault(int n_images, int channels_in, int channels_out, int rows8, int cols8, int kernel,
+                                             int dtype) {
+    if (const char* fault = conv_weights_fault(channels_out, channels_in, kernel, dtype)) return fault;
+    if (n_images < 1 || n_images > 65535) return "n_images outside [1, 65535]";
+    if (rows8 < 1 || rows8 > 32767 || cols8 < 1 || cols8 > 32767) return "rows8 and cols8 must be in [1, 32767]";
+    if (!isk_conv_backward_scratch_bytes(n_images, channels_in, channels_out, rows8, cols8, kernel))
+        return "the grid of the weight gradient does not fit 31 bits";
+    return nullptr;
+}
+
+size_t is_conv_bn_backward_scratch_bytes(int n_images, int channels_in, int channels_out, int rows8, int cols8, int kernel,
+                                         int dtype) {
+    if (conv_backward_shape_fault(n_images, channels_in, channels_out, rows8, cols8, kernel, dtype)) return 0;
+    return isk_conv_backward_scratch_bytes(n_images, channels_in, channels_out, rows8, cols8, kernel);
+}
+
+int is_conv_bn_backward(const is_conv_bn_backward_args* a, void* stream) {
+    if (!a) return fail_arg("null args");
+    if (!a->d_features || !a->d_weight || !a->d_scale || !a->d_grad_out)
+        return fail_arg("null d_features, d_weight, d_scale or d_grad_out");
+    if (!a->d_grad_features && !a->d_grad_weight && !a->d_grad_scale && !a->d_grad_shift && !a->d_grad_pre)
+        return fail_arg("d_grad_features, d_grad_weight, d_grad_scale, d_grad_shift and d_grad_pre are all null");
+    if (const char* fault = conv_backward_shape_fault(a->n_images, a->channels_in, a->channels_out, a->rows8, a->cols8,
+                                                      a->kernel, a->dtype))
+        return fail_arg(fault);
+    if (a->kernel == 1 && a->dilation != 1) return fail_arg("dilation must be 1 with kernel 1");
+    if (a->dilation < 1 || a->dilation > 8) return fail_arg("dilation outside [1, 8]");
+    if (a->relu != 0 && a->relu != 1) return fail_arg("relu must be 0 or 1");
+    if (a->relu && !a->d_out) return fail_arg("null d_out with relu: the mask reads the saved output");
+    if (a->relu && a->out_dtype != a->dtype && a->out_dtype != IS_HEAD_F32)
+        return fail_arg("out_dtype is neither the input's dtype nor IS_HEAD_F32");
+    if (a->grad_out_dtype != a->dtype && a->grad_out_dtype != IS_HEAD_F32)
+        return fail_arg("grad_out_dtype is neither the input's dtype nor IS_HEAD_F32");
+    if (a->d_grad_features && a->grad_features_dtype != a->dtype && a->grad_features_dtype != IS_HEAD_F32)
+        return fail_arg("grad_features_dtype is neither the input's dtype nor IS_HEAD_F32");
+    if (a->d_grad_features && a->channels_in % 32)
+        return fail_arg("d_grad_features needs channels_in % 32 == 0: it is the transposed call's channels_out");
+    if (a->d_grad_features_add && !a->d_grad_features) return fail_arg("d_grad_features_add without d_grad_features");
+    const uint64_t P = (uint64_t)a->rows8 * a->cols8, planes = P * a->channels_out;
+    if (a->grad_image_stride < (long long)planes) return fail_arg("grad_image_stride below the planes of a frame");
+    const uintptr_t out_el = a->out_dtype == IS_HEAD_F32 ? 4 : 2, gy_el = a->grad_out_dtype == IS_HEAD_F32 ? 4 : 2;
+    const uintptr_t dx_el = a->grad_features_dtype == IS_HEAD_F32 ? 4 : 2;
+    if (misaligned(2, a->d_features, a->d_grad_features_add, a->d_grad_pre))
+        return fail_arg("d_features, d_grad_features_add and d_grad_pre must be aligned to their element");
+    if (a->relu && misaligned(out_el, a->d_out)) return fail_arg("d_out must be aligned to its element");
+    if (misaligned(gy_el, a->d_grad_out)) return fail_arg("d_grad_out must be aligned to its element");
+    if (misaligned(dx_el, a->d_grad_features)) return fail_arg("d_grad_features must be aligned to its element");
+    if (misaligned(4, a->d_weight, a->d_scale, a->d_grad_weight, a->d_grad_scale, a->d_grad_shift))
+        return fail_arg("d_weight, d_scale, d_grad_weight, d_grad_scale and d_grad_shift must be 4-byte aligned");
+    const size_t need = isk_conv_backward_scratch_bytes(a->n_images, a->channels_in, a->channels_out, a->rows8, a->cols8,
+                                                        a->kernel);
+    if (const char* fault = scratch_fault(a->d_scratch, a->scratch_bytes, need)) return fail_arg(fault);
+    /* every output's bytes against every input's and every other output's, each at its own size (at most 2^16 * 2^11 *
+     * 2^30 elements of 4 bytes: no overflow) */
+    struct span { const void* p; uint64_t bytes; const char* name; };
+    const uint64_t n = a->n_images, wn = (uint64_t)a->channels_out * a->channels_in * a->kernel * a->kernel;
+    const uint64_t in_el = n * a->channels_in * P;
+    const span inputs[] = {
+        {a->d_features, in_el * 2, "d_features"},
+        {a->d_weight, wn * 4, "d_weight"},
+        {a->d_scale, (uint64_t)a->channels_out * 4, "d_scale"},
+        {a->relu ? a->d_out : nullptr, n * planes * out_el, "d_out"},
+        {a->d_grad_out, ((n - 1) * (uint64_t)a->grad_image_stride + planes) * gy_el, "d_grad_out"},
+        {a->d_grad_features_add, in_el * 2, "d_grad_features_add"},
+    };
+    const span outputs[] = {
+        {a->d_grad_features, in_el * dx_el, "d_grad_features"},
+        {a->d_grad_weight, wn * 4, "d_grad_weight"},
+        {a->d_grad_scale, (uint64_t)a->channels_out * 4, "d_grad_scale"},
+        {a->d_grad_shift, (uint64_t)a->channels_out * 4, "d_grad_shift"},
+        {a->d_grad_pre, n * planes * 2, "d_grad_pre"},
+        {a->d_scratch, need, "d_scratch"},
+    };
+    auto overlap = [](const span& u, const span& v) {
+        const uint64_t u0 = (uint64_t)(uintptr_t)u.p, v0 = (uint64_t)(uintptr_t)v.p;
+        return u.p && v.p && u0 < v0 + v.bytes && v0 < u0 + u.bytes;
+    };
+    for (size_t o = 0; o < sizeof(outputs) / sizeof(outputs[0]); ++o) {
+        for (const span& in : inputs)
+            if (overlap(outputs[o], in)) return fail_arg("an output's bytes (or the scratch's) overlap an input's");
+        for (size_t q = o + 1; q < sizeof(outputs) / sizeof(outputs[0]); ++q)
+            if (overlap(outputs[o], outputs[q])) return fail_arg("two outputs' bytes (or an output's and the scratch's) overlap");
+    }
+    /* (last: a call that is refused for this alone has passed every check above) */
+    if (const char* fault = reserved_fault(a->reserved)) return fail_arg(fault);
+    HIP_TRY(isk_launch_conv_bn_backward(a, (hipStream_t)stream));
+    return IS_OK;
+}
+
 /* ---- f20: the backbone's stem, image bytes to layer1's output (is_k_stem.hip).  One checker, one launcher. ---- */
 static const char* stem_dtype_fault(int dtype) {
     return dtype != IS_HEAD_F16 && dtype != IS_HEAD_BF16 ? "dtype is neither IS_HEAD_F16 nor IS_HEAD_BF16" : nullptr;

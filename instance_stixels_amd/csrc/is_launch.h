@@ -254,6 +254,10 @@ hipError_t isk_launch_conv_pack(const float* d_weight, int channels_out, int cha
                                 void* d_packed, hipStream_t stream);
 hipError_t isk_launch_conv_bn(const is_conv_bn_stride_args* a, hipStream_t stream);
 
+/* is_k_conv_backward.hip */
+size_t isk_conv_backward_scratch_bytes(int n_images, int channels_in, int channels_out, int rows8, int cols8, int kernel);
+hipError_t isk_launch_conv_bn_backward(const is_conv_bn_backward_args* a, hipStream_t stream);
+
 /* is_k_stem.hip */
 size_t isk_stem_packed_bytes(void);
 hipError_t isk_launch_stem_pack(const float* d_w0, const float* d_w1, int dtype, void* d_packed, hipStream_t stream);

@@ -228,3 +228,199 @@ class SemanticNLLLossUp:
             t = t.to(torch.uint8)
         out = _class_planes(output, self.n_classes)
         return _SemanticNLLFunction.apply(out, t, self.ignore_index, self.check, "semantic_nll_up")[0]
+
+
+# ---- f21: conv + frozen BatchNorm (+ residual) (+ ReLU) with a backward pass on the device ----
+
+def _frozen_bn(bn, name):
+    """The checks of a BatchNorm2d whose running statistics the modules below freeze."""
+    if not isinstance(bn, torch.nn.BatchNorm2d):
+        raise core.CoreError(f"{name} must be a BatchNorm2d, not {type(bn).__name__}")
+    if bn.training:
+        raise core.CoreError(f"{name} is in training mode: batch statistics are another forward and are not built; "
+                             "put it into eval() to freeze it at its running statistics")
+    if bn.running_mean is None or bn.running_var is None:
+        raise core.CoreError(f"{name} tracks no running statistics")
+
+
+class _FrozenBatchNorm(torch.nn.Module):
+    """The affine pair of a BatchNorm2d as Parameters, its running statistics as buffers that are never updated.
+    fold() is cnn.fold_batchnorm's (scale, shift), value for value -- float64, rounded once each -- made of
+    differentiable torch ops on the parameters' device, so autograd reaches weight and bias by itself."""
+
+    def __init__(self, bn):
+        super().__init__()
+        n = bn.num_features
+        self.weight = torch.nn.Parameter(bn.weight.detach().clone().float() if bn.weight is not None else torch.ones(n))
+        self.bias = torch.nn.Parameter(bn.bias.detach().clone().float() if bn.bias is not None else torch.zeros(n))
+        self.register_buffer("running_mean", bn.running_mean.detach().clone().float())
+        self.register_buffer("running_var", bn.running_var.detach().clone().float())
+        self.eps = float(bn.eps)
+
+    def fold(self):
+        scale = self.weight.double() / torch.sqrt(self.running_var.double() + self.eps)
+        shift = self.bias.double() - self.running_mean.double() * scale
+        return scale.float(), shift.float()
+
+
+def _half_features(x):
+    if not torch.is_tensor(x) or not x.is_cuda or x.dim() != 4 or x.dtype not in (torch.float16, torch.bfloat16):
+        raise core.CoreError("the features must be a float16 or bfloat16 device tensor [n][channels][rows8][cols8] "
+                             "(fp32 features are not built: convert them first)")
+
+
+class _ConvBnFunction(torch.autograd.Function):
+    """Forward: the pack of the current weight and one launch of core.conv_bn.  Backward: one call of
+    core.conv_bn_backward that asks for the gradients autograd needs and no others."""
+
+    @staticmethod
+    def forward(ctx, x, weight, scale, shift, kernel, dilation, relu):
+        packed = core.conv_pack_weights(weight.detach(), x.dtype)
+        out = core.conv_bn(x.detach(), packed, scale.detach(), shift.detach(), kernel, dilation, relu=relu)
+        ctx.save_for_backward(x, weight, scale, out)
+        ctx.conv = (kernel, dilation, relu)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, weight, scale, out = ctx.saved_tensors
+        kernel, dilation, relu = ctx.conv
+        need = ctx.needs_input_grad[:4]
+        if not any(need):
+            return (None,) * 7
+        g = core.conv_bn_backward(x, weight, scale, out, grad_out, kernel, dilation, relu=relu, want_features=need[0],
+                                  want_weight=need[1], want_scale=need[2], want_shift=need[3])
+        return g.get("features"), g.get("weight"), g.get("scale"), g.get("shift"), None, None, None
+
+
+class ConvBnReLU(torch.nn.Module):
+    """Conv2d(3x3, padding = dilation, stride 1, bias=False) + BatchNorm2d frozen at its running statistics + ReLU, as
+    cnn.ConvBnRelu checks the pair, trainable: `weight` is the fp32 master weight, bn.weight and bn.bias the affine
+    pair; the running statistics are buffers that no forward updates, whatever train() says.  forward(features) runs
+    is_conv_bn on features of float16 or bfloat16 and returns their dtype; its backward is one call of
+    is_conv_bn_backward (instance_stixels_core.h f21).  Batch-statistics BatchNorm, stride 2 and fp32 features raise
+    CoreError before anything is packed."""
+
+    def __init__(self, conv, bn, relu=True):
+        super().__init__()
+        from . import cnn
+        self.dilation = cnn._dilated3x3(conv, "conv", (1,))
+        _frozen_bn(bn, "bn")
+        if bn.num_features != conv.out_channels:
+            raise core.CoreError(f"bn has {bn.num_features} channels, conv {conv.out_channels}")
+        self.kernel, self.relu = 3, bool(relu)
+        self.weight = torch.nn.Parameter(conv.weight.detach().clone().float())
+        self.bn = _FrozenBatchNorm(bn)
+
+    def forward(self, features):
+        _half_features(features)
+        scale, shift = self.bn.fold()
+        return _ConvBnFunction.apply(features, self.weight, scale, shift, self.kernel, self.dilation, self.relu)
+
+
+def _basic_block_layout(block):
+    """The checks of a BasicBlock-shaped `block` (conv1, bn1, conv2, bn2, downsample, residual), cnn.ResidualBlock's at
+    stride 1, made before anything is folded or packed: (conv1's dilation, conv2's dilation, whether the block adds a
+    residual, the downsample's (Conv2d, BatchNorm2d) or None)."""
+    from . import cnn
+    if hasattr(block, "conv3"):
+        raise core.CoreError("a block with conv3 is a Bottleneck: only BasicBlock is covered")
+    d1, d2 = cnn._dilated3x3(block.conv1, "conv1", (1,)), cnn._dilated3x3(block.conv2, "conv2")
+    c_in, c_mid, c_out = block.conv1.in_channels, block.conv1.out_channels, block.conv2.out_channels
+    if block.conv2.in_channels != c_mid or block.bn1.num_features != c_mid or block.bn2.num_features != c_out:
+        raise core.CoreError("conv1, bn1, conv2 and bn2 disagree on their channels")
+    residual = bool(block.residual)
+    down = block.downsample if residual else None      # (the reference computes and drops it otherwise)
+    if down is None:
+        if residual and c_in != c_out:
+            raise core.CoreError(f"residual=True without a downsample needs equal channels, not {c_in} -> {c_out}")
+        return d1, d2, residual, None
+    mods = list(down) if isinstance(down, torch.nn.Sequential) else []
+    if len(mods) != 2 or not isinstance(mods[0], torch.nn.Conv2d) or not isinstance(mods[1], torch.nn.BatchNorm2d) \
+            or tuple(mods[0].kernel_size) != (1, 1) or mods[0].bias is not None or mods[0].groups != 1 \
+            or tuple(mods[0].padding) != (0, 0) or mods[0].in_channels != c_in or mods[0].out_channels != c_out \
+            or mods[1].num_features != c_out:
+        raise core.CoreError("downsample must be nn.Sequential(Conv2d(kernel_size=1, bias=False), BatchNorm2d) "
+                             "from the block's input to its output channels")
+    if tuple(mods[0].stride) != (1, 1):
+        raise core.CoreError(f"downsample has stride {tuple(mods[0].stride)}: only stride 1 is covered")
+    return d1, d2, residual, (mods[0], mods[1])
+
+
+class _BasicBlockFunction(torch.autograd.Function):
+    """The whole block as one node.  inputs: x, then (weight, scale, shift) of conv1, conv2 and, with a downsample, of
+    it.  The backward is conv2's call, the downsample's and conv1's, with nothing of torch's in between: conv2's call
+    hands out the masked gradient (want_pre), which is the gradient with respect to the residual operand, and the
+    second path into x joins conv1's dX inside its launch (features_add)."""
+
+    @staticmethod
+    def forward(ctx, x, d1, d2, residual, *params):
+        w1, s1, b1, w2, s2, b2 = params[:6]
+        down = params[6:] if len(params) == 9 else None
+        xd = x.detach()
+        pack = lambda w: core.conv_pack_weights(w.detach(), x.dtype)
+        y1 = core.conv_bn(xd, pack(w1), s1.detach(), b1.detach(), 3, d1, relu=True)
+        res = None
+        if residual:
+            res = core.conv_bn(xd, pack(down[0]), down[1].detach(), down[2].detach(), 1, 1, relu=False) if down else xd
+        out = core.conv_bn(y1, pack(w2), s2.detach(), b2.detach(), 3, d2, residual=res, relu=True)
+        ctx.save_for_backward(x, y1, out, w1, s1, w2, s2, *((down[0], down[1]) if down else ()))
+        ctx.block = (d1, d2, residual, down is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, y1, out, w1, s1, w2, s2 = ctx.saved_tensors[:7]
+        d1, d2, residual, has_down = ctx.block
+        need = ctx.needs_input_grad
+        need_x, n1, n2, nd = need[0], need[4:7], need[7:10], need[10:13] if has_down else (False,) * 3
+        through1 = need_x or any(n1)                       # anything behind conv1's output
+        side = residual and (need_x or any(nd))            # the residual operand's gradient is used
+        grads = [None] * (4 + (9 if has_down else 6))
+        if not (through1 or side or any(n2)):
+            return tuple(grads)
+        g2 = core.conv_bn_backward(y1, w2, s2, out, grad_out, 3, d2, relu=True, want_features=through1,
+                                   want_weight=n2[0], want_scale=n2[1], want_shift=n2[2], want_pre=side)
+        grads[7:10] = g2.get("weight"), g2.get("scale"), g2.get("shift")
+        add = None
+        if side and has_down:
+            wd, sd = ctx.saved_tensors[7:9]
+            gd = core.conv_bn_backward(x, wd, sd, None, g2["pre"], 1, 1, relu=False, want_features=need_x,
+                                       want_weight=nd[0], want_scale=nd[1], want_shift=nd[2])
+            grads[10:13] = gd.get("weight"), gd.get("scale"), gd.get("shift")
+            add = gd.get("features")
+        elif side:
+            add = g2["pre"]                                # x itself was the residual
+        if through1:
+            g1 = core.conv_bn_backward(x, w1, s1, y1, g2["features"], 3, d1, relu=True, want_features=need_x,
+                                       want_weight=n1[0], want_scale=n1[1], want_shift=n1[2],
+                                       features_add=add if need_x else None)
+            grads[0] = g1.get("features")
+            grads[4:7] = g1.get("weight"), g1.get("scale"), g1.get("shift")
+        return tuple(grads)
+
+
+class BasicBlock(torch.nn.Module):
+    """One BasicBlock of the reference (drn.py:54-87) with its BatchNorms frozen at their running statistics, as
+    cnn.ResidualBlock checks it, trainable: conv1.weight, conv2.weight (and downsample's) are fp32 master weights, the
+    BatchNorm affine pairs Parameters.  The forward is cnn.ResidualBlock's launches; the whole block is ONE autograd
+    node whose backward is 2 calls of is_conv_bn_backward, 3 with a downsample, and no torch kernel between them.
+    Stride 2, batch statistics and fp32 features raise CoreError before anything is packed."""
+
+    def __init__(self, block):
+        super().__init__()
+        self.d1, self.d2, self.residual, down = _basic_block_layout(block)
+        for name, bn in (("bn1", block.bn1), ("bn2", block.bn2)) + ((("downsample's bn", down[1]),) if down else ()):
+            _frozen_bn(bn, name)
+        self.weight1 = torch.nn.Parameter(block.conv1.weight.detach().clone().float())
+        self.weight2 = torch.nn.Parameter(block.conv2.weight.detach().clone().float())
+        self.bn1, self.bn2 = _FrozenBatchNorm(block.bn1), _FrozenBatchNorm(block.bn2)
+        self.weight_down = torch.nn.Parameter(down[0].weight.detach().clone().float()) if down else None
+        self.bn_down = _FrozenBatchNorm(down[1]) if down else None
+
+    def forward(self, features):
+        _half_features(features)
+        params = [self.weight1, *self.bn1.fold(), self.weight2, *self.bn2.fold()]
+        if self.weight_down is not None:
+            params += [self.weight_down, *self.bn_down.fold()]
+        return _BasicBlockFunction.apply(features, self.d1, self.d2, self.residual, *params)

@@ -30,6 +30,13 @@ comma-separated), for fp16 and bf16 features [n][.][rows8][cols8] with half outp
   against torch's sequence on the same bytes: byte -> float / 255 -> normalise -> half -> conv2d 7x7 -> batch_norm ->
   relu -> conv2d 3x3 -> batch_norm -> relu.  `compulsory_gb` is 3 + 32 bytes per pixel.  --stem-n frames per call
   (default --n) where torch's intermediates or its warm-up are too large; the row says how many.
+- backward (not in the default --parts): core.conv_bn_backward (f21) with every gradient (dX, dW, dscale, dshift) and
+  without dX, at --backward-n frames (default 4, the size training uses): 3x3 at --C channels with dilation 2 and 1
+  (layer7, layer8), and layer5's and layer6's pairs 128 -> 256 (dilation 2) and 256 -> 512 (dilation 4) as 3x3 and as
+  1x1, against torch.autograd.grad of relu(batch_norm_eval(conv2d(x))) in the same half dtype with respect to x, the
+  weight and the BatchNorm affine pair, the forward graph built outside the timing.  `scratch_mb` is the call's scratch.
+  The MFMA floor counts dX and dW: 2 x the forward's FLOP.  Both arms allocate their outputs inside the timing (torch's
+  caching allocator; the library's arm also its scratch), as a training step does.  --backward-cases picks shapes.
 --no-torch leaves the torch arms out (and alone allows fewer than 10 iterations, for a counter run).  torch's first
 convolution of a shape takes 30 - 160 s: run the dtypes, and if need be the parts, in separate commands.
 
@@ -66,7 +73,9 @@ def main():
     ap.add_argument("--dp-n", type=int, default=0, help="0: the whole batch (a shape the library is already tuned for)")
     ap.add_argument("--dtypes", default="fp16,bf16", help="comma-separated subset of fp16,bf16")
     ap.add_argument("--parts", default="tail,residual,1x1,layers",
-                    help="comma-separated subset of tail,residual,1x1,layers,strided,stem")
+                    help="comma-separated subset of tail,residual,1x1,layers,strided,stem,backward")
+    ap.add_argument("--backward-n", type=int, default=4, help="frames per call of the `backward` part")
+    ap.add_argument("--backward-cases", default="0,1,2,3,4,5", help="which of the six shapes of the `backward` part")
     ap.add_argument("--rows", type=int, default=1024, help="rows of layer1's output (the `strided` part)")
     ap.add_argument("--cols", type=int, default=2048)
     ap.add_argument("--strided-n", type=int, default=0, help="frames per call of the `strided` part; 0: --n")
@@ -277,6 +286,47 @@ def main():
             note(name, "layers", json.dumps(row))
             del x, ours
             torch.cuda.empty_cache()
+        if "backward" in parts:
+            m = a.backward_n
+            cases = ((a.C, a.C, 3, 2), (a.C, a.C, 3, 1), (128, 256, 3, 2), (128, 256, 1, 1), (256, 512, 3, 4), (256, 512, 1, 1))
+            for cin, cout, k, d in [cases[int(i)] for i in a.backward_cases.split(",")]:
+                relu = k == 3                                                  # (the 1x1 is the downsample: no ReLU)
+                x = torch.randn((m, cin, Hs, Ws), device=dev).abs_().to(dtype)
+                w32, stats = weight(cout, cin, k), bn_stats(cout)
+                scale, shift = fold(*stats)
+                y = core.conv_bn(x, core.conv_pack_weights(w32, dtype), scale, shift, k, d, relu=relu)
+                gy = torch.randn((m, cout, Hs, Ws), device=dev).to(dtype)
+                arms = {"new": lambda: core.conv_bn_backward(x, w32, scale, y, gy, k, d, relu=relu),
+                        "new_no_dx": lambda: core.conv_bn_backward(x, w32, scale, y, gy, k, d, relu=relu,
+                                                                   want_features=False)}
+                if not a.no_torch:
+                    graphs = {}
+                    for arm, cl in (("torch_contiguous", False), ("torch_channels_last", True)):
+                        xt, wt = x.clone(), w32.to(dtype)
+                        if cl:
+                            xt, wt = channels_last(xt, wt)
+                        xt, wt = xt.requires_grad_(True), wt.requires_grad_(True)
+                        mean, var, gamma, beta = [t.to(dtype) for t in stats]
+                        gamma, beta = gamma.requires_grad_(True), beta.requires_grad_(True)
+                        yt = F.batch_norm(F.conv2d(xt, wt, padding=d * (k // 2), dilation=d), mean, var, gamma, beta, False,
+                                          0.0, eps)
+                        yt = F.relu(yt) if relu else yt
+                        graphs[arm] = (yt, (xt, wt, gamma, beta), channels_last(gy)[0] if cl else gy)
+                        arms[arm] = lambda arm=arm: torch.autograd.grad(graphs[arm][0], graphs[arm][1], graphs[arm][2],
+                                                                        retain_graph=True)
+                row, med = measure("%s backward %d->%d k%d d%d" % (name, cin, cout, k, d), arms)
+                tflop = 2 * 2.0 * k * k * cin * cout * m * Hs * Ws / 1e12
+                row.update(shape=[m, cin, cout, Hs, Ws, k, d], tflop=round(tflop, 3), mfma_floor_ms=round(floor_ms(tflop), 3),
+                           new_share_of_mfma_floor=round(floor_ms(tflop) / med["new"], 3),
+                           scratch_mb=round(core.conv_bn_backward_scratch_bytes(
+                               m, cin, cout, Hs, Ws, k, core.HEAD_F16 if dtype == torch.float16 else core.HEAD_BF16) / 2 ** 20, 1))
+                against_torch(row, med)
+                out["%s_backward_%d_%d_k%d_d%d" % (name, cin, cout, k, d)] = row
+                note(name, "backward", json.dumps(row))
+                del x, y, gy, arms
+                if not a.no_torch:
+                    del graphs
+                torch.cuda.empty_cache()
         if "strided" in parts:
             m, H1, W1 = a.strided_n or n, a.rows, a.cols
             half = lambda v, times: -(-v // 2 ** times)                      # ceil(v / 2^times)
