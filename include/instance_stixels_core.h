@@ -1545,6 +1545,83 @@ size_t is_conv_bn_backward_scratch_bytes(int n_images, int channels_in, int chan
  * a stride-2 layer cannot be expressed, and the Python layer refuses it with a message. */
 int is_conv_bn_backward(const is_conv_bn_backward_args* args, void* stream);
 
+/* ---- f22: the backward pass of is_conv_bn_stride, stride 1 or 2 (is_k_conv_backward.hip, is_k_conv_backward_stride.hip) --
+ * The five stride-2 launches of drn_d_22 (layer2; conv1 and downsample of layer3[0] and layer4[0]) get their backward.
+ * is_conv_bn_backward_args cannot grow and its reserved fields stay refused, so this entry point stands beside it as
+ * is_conv_bn_stride stands beside is_conv_bn: with stride = 1 the call IS is_conv_bn_backward -- one checker, one
+ * launcher, the same launches, bytes, scratch size and messages, the extents named rows_in / cols_in.
+ *
+ * At stride 2 (dilation 1; kernel 3 with padding 1 or kernel 1) rows_out = (rows_in + 1) / 2, cols_out = (cols_in + 1) / 2
+ * are derived, P = rows_out * cols_out, and f21's rules hold word for word except:
+ *
+ *   gh, dshift  f21's, over the OUTPUT's P (the same launches).
+ *   G[co][ci][tap] = sum over n, y, x of gh[n][co][y][x] * x[n][ci][2 y + ky - 1][2 x + kx - 1] (kernel 1: x[n][ci][2 y]
+ *             [2 x]); a tap outside the image contributes nothing (with an even extent the bottom / right padding is
+ *             never touched, with an odd one it is).  Chunk (i, j) is image i and OUTPUT rows [j B, min((j + 1) B,
+ *             rows_out)), B = IS_CONV_BACKWARD_STRIDE_BAND for every shape; no column split.  Inside a chunk ONE fp32
+ *             MFMA accumulator per (co, ci, tap), fed by v_mfma_f32_32x32x16_{f16,bf16}: 32-pixel segments of the
+ *             OUTPUT rows in increasing column; in a segment the chunk's rows in increasing y; in a row the two
+ *             16-pixel steps in increasing column (the lanes past the row's end are zero).  Gsum, dW and dscale: f21's
+ *             binary64 reductions (the same launches).
+ *   dX[n][ci][r][c] = sum over co and over the taps (ky, kx) with r + 1 - ky and c + 1 - kx both even and y = (r + 1 -
+ *             ky) / 2 in [0, rows_out), x = (c + 1 - kx) / 2 in [0, cols_out), of wT[ci][co][tap] * gh[n][co][y][x], wT =
+ *             round_half(scale[co] * w_half[co][ci][tap]) as in f21.  The four (row, column) parity classes of an
+ *             element use 1, 2, 2 and 4 taps at kernel 3; at kernel 1 only (even, even) elements get a sum and every
+ *             other element is exactly +0 (or the features_add value).  ONE fp32 MFMA accumulator chain per element,
+ *             not split and not combined: increasing 16-channel chunk of channels_out and, inside a chunk, increasing
+ *             tap 3 ky + kx among the element's class (v_mfma_f32_32x32x16, the 16 products of one instruction in the
+ *             hardware's order).  d_grad_features_add is added in fp32 before the single final rounding.  Every
+ *             element of dX is written.  Needs channels_in % 32 == 0: layer2 (16 channels in) gets dW, dscale and
+ *             dshift only, its dX has no consumer until the stem has a backward.
+ *
+ * Fields as in is_conv_bn_backward_args, and
+ *   rows_in, cols_in    the INPUT's extents: d_features, d_grad_features, d_grad_features_add are [n][channels_in][rows_in]
+ *                       [cols_in]
+ *   stride              1 or 2;  2 needs dilation 1
+ *   d_out, d_grad_out, d_grad_pre   the OUTPUT's extents [n][channels_out][rows_out][cols_out]; grad_image_stride >=
+ *                       channels_out * rows_out * cols_out
+ *   reserved            0 */
+#ifndef IS_CONV_BACKWARD_STRIDE_BAND /* (an experiment build may define another; the product's value is this one) */
+#define IS_CONV_BACKWARD_STRIDE_BAND 8
+#endif
+typedef struct is_conv_bn_stride_backward_args {
+    const void* d_features;
+    int dtype; /* IS_HEAD_F16 | IS_HEAD_BF16 */
+    int n_images, channels_in, channels_out, rows_in, cols_in;
+    int kernel;   /* 3 or 1 */
+    int stride;   /* 1 or 2 */
+    int dilation; /* kernel 3: [1, 8], 1 with stride 2;  kernel 1: must be 1 */
+    const float* d_weight;
+    const float* d_scale;
+    const void* d_out;
+    int out_dtype;
+    int relu;
+    const void* d_grad_out;
+    int grad_out_dtype;
+    long long grad_image_stride;
+    void* d_grad_features;
+    int grad_features_dtype;
+    const void* d_grad_features_add;
+    float* d_grad_weight;
+    float* d_grad_scale;
+    float* d_grad_shift;
+    void* d_grad_pre;
+    void* d_scratch;
+    size_t scratch_bytes;
+    int reserved[4]; /* 0 */
+} is_conv_bn_stride_backward_args;
+
+/* Bytes of d_scratch for a call of that shape (0 for a shape the call refuses); with stride 1,
+ * is_conv_bn_backward_scratch_bytes' value.  At stride 2 the sections have the OUTPUT's extents and n_images *
+ * ceil(rows_out / IS_CONV_BACKWARD_STRIDE_BAND) partials. */
+size_t is_conv_bn_stride_backward_scratch_bytes(int n_images, int channels_in, int channels_out, int rows_in, int cols_in,
+                                                int kernel, int stride, int dtype);
+/* is_conv_bn_backward's launches, with dX by k_conv_bwd_data_s2 and the partials by k_conv_bwd_weight_s2 at stride 2.
+ * IS_EINVAL, with the reason in is_last_error() and before the device is touched, for everything is_conv_bn_backward
+ * refuses (the extents are named rows_in and cols_in), a stride outside {1, 2}, stride 2 with dilation != 1 and, last, a
+ * non-zero reserved field. */
+int is_conv_bn_stride_backward(const is_conv_bn_stride_backward_args* args, void* stream);
+
 /* ---- f9: per-instance objects and their contours (is_k_objects.hip) ------------------------------------------------
  * What the reference's consumers reduce on the host from the per-stixel output: the top-down view
  * (tools/visualization/clustering_visualization.py:563-792: per instance and column the closest stixel, connected

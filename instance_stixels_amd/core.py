@@ -51,6 +51,7 @@ EXPORTS = [
     "is_conv_bn_stride",
     "is_stem_packed_bytes", "is_stem_pack_weights", "is_stem",
     "is_conv_bn_backward_scratch_bytes", "is_conv_bn_backward",
+    "is_conv_bn_stride_backward_scratch_bytes", "is_conv_bn_stride_backward",
 ]
 RENDER_MAX_LABELS = 64    # IS_RENDER_MAX_LABELS
 RENDER_MAX_CLASSES = 256  # IS_RENDER_MAX_CLASSES
@@ -293,6 +294,21 @@ class ConvBnBackwardArgs(ctypes.Structure):
                 ("d_grad_pre", vp), ("d_scratch", vp), ("scratch_bytes", ctypes.c_size_t), ("reserved", ci * 4)]
 
 
+CONV_BACKWARD_STRIDE_BAND = 8  # IS_CONV_BACKWARD_STRIDE_BAND
+
+
+class ConvBnStrideBackwardArgs(ctypes.Structure):
+    """is_conv_bn_stride_backward_args: zero-initialised by ctypes; device pointers as ints."""
+    vp, ci, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    _fields_ = [("d_features", vp), ("dtype", ci), ("n_images", ci), ("channels_in", ci), ("channels_out", ci),
+                ("rows_in", ci), ("cols_in", ci), ("kernel", ci), ("stride", ci), ("dilation", ci), ("d_weight", vp),
+                ("d_scale", vp), ("d_out", vp), ("out_dtype", ci), ("relu", ci), ("d_grad_out", vp),
+                ("grad_out_dtype", ci), ("grad_image_stride", ll), ("d_grad_features", vp),
+                ("grad_features_dtype", ci), ("d_grad_features_add", vp), ("d_grad_weight", vp), ("d_grad_scale", vp),
+                ("d_grad_shift", vp), ("d_grad_pre", vp), ("d_scratch", vp), ("scratch_bytes", ctypes.c_size_t),
+                ("reserved", ci * 4)]
+
+
 class RoadParams(ctypes.Structure):
     """is_road_params: one frame's road, the layout of Stixels::RoadParameters (16 bytes)"""
     _fields_ = [("vhor", ctypes.c_int), ("tilt", ctypes.c_float), ("height", ctypes.c_float),
@@ -408,6 +424,9 @@ def lib():
         L.is_conv_bn_backward_scratch_bytes.argtypes = [ci, ci, ci, ci, ci, ci, ci]
         L.is_conv_bn_backward_scratch_bytes.restype = ctypes.c_size_t
         L.is_conv_bn_backward.argtypes = [ctypes.POINTER(ConvBnBackwardArgs), vp]
+        L.is_conv_bn_stride_backward_scratch_bytes.argtypes = [ci, ci, ci, ci, ci, ci, ci, ci]
+        L.is_conv_bn_stride_backward_scratch_bytes.restype = ctypes.c_size_t
+        L.is_conv_bn_stride_backward.argtypes = [ctypes.POINTER(ConvBnStrideBackwardArgs), vp]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
         L.is_get_device.argtypes = [ctypes.POINTER(ci)]
@@ -1649,10 +1668,46 @@ def conv_bn_backward(features, weight, scale, out, grad_out, kernel, dilation=1,
     is the gradient with respect to the forward's residual operand), on the features' device, enqueued on the current
     torch stream; the scratch is allocated here.  canary > 0: every output and the scratch get that many guard
     elements in front and behind, and the dict has "guards": {name: (front, back, pattern)} (one synchronisation)."""
+    return _conv_backward(None, features, weight, scale, out, grad_out, kernel, dilation, relu, want_features, want_weight,
+                          want_scale, want_shift, want_pre, features_add, grad_features_dtype, canary)
+
+
+def conv_bn_stride_backward_scratch_bytes(n_images, channels_in, channels_out, rows_in, cols_in, kernel, stride, dtype):
+    """is_conv_bn_stride_backward_scratch_bytes: the scratch a call of that shape needs (0: a refused shape)."""
+    return int(lib().is_conv_bn_stride_backward_scratch_bytes(int(n_images), int(channels_in), int(channels_out),
+                                                              int(rows_in), int(cols_in), int(kernel), int(stride),
+                                                              int(dtype)))
+
+
+def conv_bn_stride_backward_ptr(stream=0, **fields):
+    """is_conv_bn_stride_backward on raw device pointers (ints): fields are those of ConvBnStrideBackwardArgs.
+    Asynchronous on `stream`; returns the return code and raises nothing (the tests check IS_EINVAL)."""
+    a = _with_reserved(ConvBnStrideBackwardArgs, fields)
+    return lib().is_conv_bn_stride_backward(ctypes.byref(a), ctypes.c_void_p(int(stream)))
+
+
+def conv_bn_stride_backward(features, weight, scale, out, grad_out, kernel, stride, dilation=1, relu=True,
+                            want_features=True, want_weight=True, want_scale=True, want_shift=True, want_pre=False,
+                            features_add=None, grad_features_dtype=None, canary=0):
+    """conv_bn_backward with a stride of 1 or 2 (is_conv_bn_stride_backward, instance_stixels_core.h f22): the backward
+    pass of conv_bn_stride.  Arguments and result as conv_bn_backward, except that `features`, "features" and
+    `features_add` have the INPUT's extents [n][channels_in][rows_in][cols_in] and `out`, `grad_out` and "pre" the
+    OUTPUT's, ceil(rows_in / stride) x ceil(cols_in / stride).  At stride 1 the bytes are conv_bn_backward's; stride 2
+    needs dilation 1, and "features" needs channels_in % 32 == 0 (layer2's 16 channels get weight, scale and shift
+    only)."""
+    return _conv_backward(stride, features, weight, scale, out, grad_out, kernel, dilation, relu, want_features,
+                          want_weight, want_scale, want_shift, want_pre, features_add, grad_features_dtype, canary)
+
+
+def _conv_backward(stride, features, weight, scale, out, grad_out, kernel, dilation, relu, want_features, want_weight,
+                   want_scale, want_shift, want_pre, features_add, grad_features_dtype, canary):
+    """The call sequence of conv_bn_backward (stride None: is_conv_bn_backward, extents rows8 / cols8) and
+    conv_bn_stride_backward (is_conv_bn_stride_backward, extents rows_in / cols_in)."""
+    ext = ("rows8", "cols8") if stride is None else ("rows_in", "cols_in")
     import torch
     x = features
     if not torch.is_tensor(x) or not x.is_cuda or x.dim() != 4:
-        raise CoreError("features must be a device tensor [n][channels_in][rows8][cols8]")
+        raise CoreError(f"features must be a device tensor [n][channels_in][{ext[0]}][{ext[1]}]")
     codes = _head_codes(halves_only=True)
     if x.dtype not in codes:
         raise CoreError(f"features dtype {x.dtype} is neither float16 nor bfloat16 (fp32 features are not built)")
@@ -1667,7 +1722,10 @@ def conv_bn_backward(features, weight, scale, out, grad_out, kernel, dilation=1,
     sc = _f32_on(scale, dev).reshape(-1)
     if int(sc.numel()) != cout:
         raise CoreError(f"scale holds {int(sc.numel())} channels, the weight {cout}")
-    shape = (n, cout, Hs, Ws)
+    st = 1 if stride is None else int(stride)
+    if st not in (1, 2):
+        raise CoreError(f"stride {stride} is neither 1 nor 2")
+    shape = (n, cout, (Hs + st - 1) // st, (Ws + st - 1) // st)      # the OUTPUT's: out, grad_out, "pre"
 
     def half_or_f32(t, name):
         if not torch.is_tensor(t) or t.device != dev or t.dtype not in (x.dtype, torch.float32) or \
@@ -1696,8 +1754,11 @@ def conv_bn_backward(features, weight, scale, out, grad_out, kernel, dilation=1,
         raise CoreError("no gradient is asked for")
     g = int(canary)
     with torch.cuda.device(dev):
-        nbytes = _scratch_or_raise(conv_bn_backward_scratch_bytes,
-                                   dict(n_images=n, channels_in=cin, channels_out=cout, rows8=Hs, cols8=Ws, kernel=k),
+        extents = {ext[0]: Hs, ext[1]: Ws}
+        nbytes = _scratch_or_raise(conv_bn_backward_scratch_bytes if stride is None else
+                                   conv_bn_stride_backward_scratch_bytes,
+                                   dict(n_images=n, channels_in=cin, channels_out=cout, **extents, kernel=k,
+                                        **({} if stride is None else dict(stride=st))),
                                    dtype=codes[x.dtype])
         named, ret = {}, {}
         ptr = {"features": None, "weight": None, "scale": None, "shift": None, "pre": None}
@@ -1717,16 +1778,18 @@ def conv_bn_backward(features, weight, scale, out, grad_out, kernel, dilation=1,
         gs = (g + 15) // 16 * 16
         sfull, scratch = _guarded(nbytes, torch.uint8, dev, gs, 0xA5)
         named["scratch"] = (sfull, np.uint8(0xA5))
-        a = ConvBnBackwardArgs(
-            d_features=x.data_ptr(), dtype=codes[x.dtype], n_images=n, channels_in=cin, channels_out=cout, rows8=Hs,
-            cols8=Ws, kernel=k, dilation=int(dilation), d_weight=w.data_ptr(), d_scale=sc.data_ptr(),
+        a = (ConvBnBackwardArgs if stride is None else ConvBnStrideBackwardArgs)(
+            d_features=x.data_ptr(), dtype=codes[x.dtype], n_images=n, channels_in=cin, channels_out=cout, **extents,
+            kernel=k, dilation=int(dilation), **({} if stride is None else dict(stride=st)), d_weight=w.data_ptr(),
+            d_scale=sc.data_ptr(),
             d_out=y.data_ptr() if y is not None else None, out_dtype=y_code, relu=int(bool(relu)),
             d_grad_out=gy.data_ptr(), grad_out_dtype=gy_code, grad_image_stride=gy_stride,
             d_grad_features=ptr["features"], grad_features_dtype=HEAD_F32 if xdt == torch.float32 else codes[x.dtype],
             d_grad_features_add=add.data_ptr() if add is not None else None, d_grad_weight=ptr["weight"],
             d_grad_scale=ptr["scale"], d_grad_shift=ptr["shift"], d_grad_pre=ptr["pre"],
             d_scratch=scratch.data_ptr(), scratch_bytes=nbytes)
-        _check(lib().is_conv_bn_backward(ctypes.byref(a), _current_stream(dev)), "is_conv_bn_backward")
+        entry = "is_conv_bn_backward" if stride is None else "is_conv_bn_stride_backward"
+        _check(getattr(lib(), entry)(ctypes.byref(a), _current_stream(dev)), entry)
         if g:
             ret["guards"] = _guards(named, g, gs)
     return ret

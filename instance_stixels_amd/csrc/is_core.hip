@@ -1295,34 +1295,47 @@ int is_conv3x3_bn_relu(const is_conv3x3_args* a, void* stream) {
     return is_conv_bn(&b, stream);
 }
 
-/* ---- f21: the backward pass of is_conv_bn (is_k_conv_backward.hip).  One checker, one launcher. ---- */
-static const char* conv_backward_shape_fault(int n_images, int channels_in, int channels_out, int rows8, int cols8, int kernel,
-                                             int dtype) {
+/* ---- f21, f22: the backward pass of is_conv_bn_stride (is_k_conv_backward.hip, is_k_conv_backward_stride.hip).  One
+ * checker and one launcher: is_conv_bn_backward is is_conv_bn_stride_backward with stride = 1.  `extents_fault`: the
+ * refusal in the caller's own names for the extents (rows8 / cols8 in f21, rows_in / cols_in in f22). ---- */
+static const char* conv_backward_shape_fault(int n_images, int channels_in, int channels_out, int rows_in, int cols_in,
+                                             int kernel, int stride, int dtype, const char* extents_fault) {
     if (const char* fault = conv_weights_fault(channels_out, channels_in, kernel, dtype)) return fault;
     if (n_images < 1 || n_images > 65535) return "n_images outside [1, 65535]";
-    if (rows8 < 1 || rows8 > 32767 || cols8 < 1 || cols8 > 32767) return "rows8 and cols8 must be in [1, 32767]";
-    if (!isk_conv_backward_scratch_bytes(n_images, channels_in, channels_out, rows8, cols8, kernel))
+    if (rows_in < 1 || rows_in > 32767 || cols_in < 1 || cols_in > 32767) return extents_fault;
+    if (stride != 1 && stride != 2) return "stride is neither 1 nor 2";
+    if (!isk_conv_backward_scratch_bytes(n_images, channels_in, channels_out, rows_in, cols_in, kernel, stride))
         return "the grid of the weight gradient does not fit 31 bits";
     return nullptr;
 }
 
+static const char* const kExtents8 = "rows8 and cols8 must be in [1, 32767]";
+static const char* const kExtentsIn = "rows_in and cols_in must be in [1, 32767]";
+
 size_t is_conv_bn_backward_scratch_bytes(int n_images, int channels_in, int channels_out, int rows8, int cols8, int kernel,
                                          int dtype) {
-    if (conv_backward_shape_fault(n_images, channels_in, channels_out, rows8, cols8, kernel, dtype)) return 0;
-    return isk_conv_backward_scratch_bytes(n_images, channels_in, channels_out, rows8, cols8, kernel);
+    if (conv_backward_shape_fault(n_images, channels_in, channels_out, rows8, cols8, kernel, 1, dtype, kExtents8)) return 0;
+    return isk_conv_backward_scratch_bytes(n_images, channels_in, channels_out, rows8, cols8, kernel, 1);
 }
 
-int is_conv_bn_backward(const is_conv_bn_backward_args* a, void* stream) {
-    if (!a) return fail_arg("null args");
+size_t is_conv_bn_stride_backward_scratch_bytes(int n_images, int channels_in, int channels_out, int rows_in, int cols_in,
+                                                int kernel, int stride, int dtype) {
+    if (conv_backward_shape_fault(n_images, channels_in, channels_out, rows_in, cols_in, kernel, stride, dtype, kExtentsIn))
+        return 0;
+    return isk_conv_backward_scratch_bytes(n_images, channels_in, channels_out, rows_in, cols_in, kernel, stride);
+}
+
+static int conv_bn_backward_run(const is_conv_bn_stride_backward_args* a, void* stream, const char* extents_fault) {
     if (!a->d_features || !a->d_weight || !a->d_scale || !a->d_grad_out)
         return fail_arg("null d_features, d_weight, d_scale or d_grad_out");
     if (!a->d_grad_features && !a->d_grad_weight && !a->d_grad_scale && !a->d_grad_shift && !a->d_grad_pre)
         return fail_arg("d_grad_features, d_grad_weight, d_grad_scale, d_grad_shift and d_grad_pre are all null");
-    if (const char* fault = conv_backward_shape_fault(a->n_images, a->channels_in, a->channels_out, a->rows8, a->cols8,
-                                                      a->kernel, a->dtype))
+    if (const char* fault = conv_backward_shape_fault(a->n_images, a->channels_in, a->channels_out, a->rows_in, a->cols_in,
+                                                      a->kernel, a->stride, a->dtype, extents_fault))
         return fail_arg(fault);
     if (a->kernel == 1 && a->dilation != 1) return fail_arg("dilation must be 1 with kernel 1");
     if (a->dilation < 1 || a->dilation > 8) return fail_arg("dilation outside [1, 8]");
+    if (a->stride == 2 && a->dilation != 1) return fail_arg("dilation must be 1 with stride 2");
     if (a->relu != 0 && a->relu != 1) return fail_arg("relu must be 0 or 1");
     if (a->relu && !a->d_out) return fail_arg("null d_out with relu: the mask reads the saved output");
     if (a->relu && a->out_dtype != a->dtype && a->out_dtype != IS_HEAD_F32)
@@ -1334,7 +1347,9 @@ int is_conv_bn_backward(const is_conv_bn_backward_args* a, void* stream) {
     if (a->d_grad_features && a->channels_in % 32)
         return fail_arg("d_grad_features needs channels_in % 32 == 0: it is the transposed call's channels_out");
     if (a->d_grad_features_add && !a->d_grad_features) return fail_arg("d_grad_features_add without d_grad_features");
-    const uint64_t P = (uint64_t)a->rows8 * a->cols8, planes = P * a->channels_out;
+    /* P: the pixels of an OUTPUT plane; P_in: of an input plane */
+    const uint64_t P = (uint64_t)((a->rows_in + a->stride - 1) / a->stride) * ((a->cols_in + a->stride - 1) / a->stride);
+    const uint64_t P_in = (uint64_t)a->rows_in * a->cols_in, planes = P * a->channels_out;
     if (a->grad_image_stride < (long long)planes) return fail_arg("grad_image_stride below the planes of a frame");
     const uintptr_t out_el = a->out_dtype == IS_HEAD_F32 ? 4 : 2, gy_el = a->grad_out_dtype == IS_HEAD_F32 ? 4 : 2;
     const uintptr_t dx_el = a->grad_features_dtype == IS_HEAD_F32 ? 4 : 2;
@@ -1345,14 +1360,14 @@ int is_conv_bn_backward(const is_conv_bn_backward_args* a, void* stream) {
     if (misaligned(dx_el, a->d_grad_features)) return fail_arg("d_grad_features must be aligned to its element");
     if (misaligned(4, a->d_weight, a->d_scale, a->d_grad_weight, a->d_grad_scale, a->d_grad_shift))
         return fail_arg("d_weight, d_scale, d_grad_weight, d_grad_scale and d_grad_shift must be 4-byte aligned");
-    const size_t need = isk_conv_backward_scratch_bytes(a->n_images, a->channels_in, a->channels_out, a->rows8, a->cols8,
-                                                        a->kernel);
+    const size_t need = isk_conv_backward_scratch_bytes(a->n_images, a->channels_in, a->channels_out, a->rows_in, a->cols_in,
+                                                        a->kernel, a->stride);
     if (const char* fault = scratch_fault(a->d_scratch, a->scratch_bytes, need)) return fail_arg(fault);
     /* every output's bytes against every input's and every other output's, each at its own size (at most 2^16 * 2^11 *
      * 2^30 elements of 4 bytes: no overflow) */
     struct span { const void* p; uint64_t bytes; const char* name; };
     const uint64_t n = a->n_images, wn = (uint64_t)a->channels_out * a->channels_in * a->kernel * a->kernel;
-    const uint64_t in_el = n * a->channels_in * P;
+    const uint64_t in_el = n * a->channels_in * P_in;
     const span inputs[] = {
         {a->d_features, in_el * 2, "d_features"},
         {a->d_weight, wn * 4, "d_weight"},
@@ -1383,6 +1398,26 @@ int is_conv_bn_backward(const is_conv_bn_backward_args* a, void* stream) {
     if (const char* fault = reserved_fault(a->reserved)) return fail_arg(fault);
     HIP_TRY(isk_launch_conv_bn_backward(a, (hipStream_t)stream));
     return IS_OK;
+}
+
+int is_conv_bn_stride_backward(const is_conv_bn_stride_backward_args* a, void* stream) {
+    if (!a) return fail_arg("null args");
+    return conv_bn_backward_run(a, stream, kExtentsIn);
+}
+
+int is_conv_bn_backward(const is_conv_bn_backward_args* a, void* stream) {
+    if (!a) return fail_arg("null args");
+    is_conv_bn_stride_backward_args b = {};
+    b.d_features = a->d_features, b.dtype = a->dtype, b.n_images = a->n_images, b.channels_in = a->channels_in;
+    b.channels_out = a->channels_out, b.rows_in = a->rows8, b.cols_in = a->cols8, b.kernel = a->kernel, b.stride = 1;
+    b.dilation = a->dilation, b.d_weight = a->d_weight, b.d_scale = a->d_scale, b.d_out = a->d_out;
+    b.out_dtype = a->out_dtype, b.relu = a->relu, b.d_grad_out = a->d_grad_out, b.grad_out_dtype = a->grad_out_dtype;
+    b.grad_image_stride = a->grad_image_stride, b.d_grad_features = a->d_grad_features;
+    b.grad_features_dtype = a->grad_features_dtype, b.d_grad_features_add = a->d_grad_features_add;
+    b.d_grad_weight = a->d_grad_weight, b.d_grad_scale = a->d_grad_scale, b.d_grad_shift = a->d_grad_shift;
+    b.d_grad_pre = a->d_grad_pre, b.d_scratch = a->d_scratch, b.scratch_bytes = a->scratch_bytes;
+    for (int i = 0; i < 4; ++i) b.reserved[i] = a->reserved[i];
+    return conv_bn_backward_run(&b, stream, kExtents8);
 }
 
 /* ---- f20: the backbone's stem, image bytes to layer1's output (is_k_stem.hip).  One checker, one launcher. ---- */

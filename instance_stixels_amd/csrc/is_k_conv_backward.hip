@@ -1,5 +1,5 @@
 /*
- * is_k_conv_backward.hip -- f21: the backward pass of is_conv_bn at stride 1 (a 3x3 dilated or 1x1 convolution, folded
+ * is_k_conv_backward.hip -- f21, and f22's launcher: the backward pass of is_conv_bn at stride 1 (a 3x3 dilated or 1x1 convolution, folded
  * BatchNorm frozen at its running statistics, optional residual, optional ReLU): the masked gradient gh, dshift, the
  * transposed pack for dX, the weight-gradient partials G, their reduction to dW, and dscale.  dX itself is
  * is_k_conv3x3.hip's launch (isk_launch_conv_bn) on gh and the transposed pack; that file is not touched.
@@ -47,38 +47,10 @@
  * consecutive pixels.  The loads of a step are issued one step ahead into 32 registers and go to LDS between the two
  * barriers of their step, so they are in flight while the step before multiplies; a deeper pipeline is not built.
  */
-#include "is_launch.h"
+#include "is_conv_backward.h"
 
-#define CB_SEG 32                  /* pixels of a staged segment: two K steps */
-#define CB_TILE_ENTRIES 256        /* 16-byte entries of a 64-row x 32-pixel tile */
 #define CB_PREP_ITEMS 8            /* elements of a thread of k_conv_bwd_prepare */
 #define CB_PREP_BLOCK (256 * CB_PREP_ITEMS)
-
-typedef float cb_acc __attribute__((ext_vector_type(16)));
-typedef _Float16 cb_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 cb_bf16x8 __attribute__((ext_vector_type(8)));
-
-/* fp32 -> half, round to nearest even, as 16 bits (the rounding of is_conv_pack_weights) */
-template <int DT> __device__ __forceinline__ uint16_t cb_round(float v);
-template <> __device__ __forceinline__ uint16_t cb_round<IS_HEAD_F16>(float v) {
-    return __builtin_bit_cast(uint16_t, (_Float16)v);
-}
-template <> __device__ __forceinline__ uint16_t cb_round<IS_HEAD_BF16>(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-/* half -> fp32, exact */
-template <int DT> __device__ __forceinline__ float cb_widen(uint16_t u);
-template <> __device__ __forceinline__ float cb_widen<IS_HEAD_F16>(uint16_t u) { return (float)__builtin_bit_cast(_Float16, u); }
-template <> __device__ __forceinline__ float cb_widen<IS_HEAD_BF16>(uint16_t u) { return __uint_as_float((uint32_t)u << 16); }
-
-template <int DT> __device__ __forceinline__ cb_acc cb_mfma(uint4 a, uint4 b, cb_acc c);
-template <> __device__ __forceinline__ cb_acc cb_mfma<IS_HEAD_F16>(uint4 a, uint4 b, cb_acc c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(cb_f16x8, a), __builtin_bit_cast(cb_f16x8, b), c, 0, 0, 0);
-}
-template <> __device__ __forceinline__ cb_acc cb_mfma<IS_HEAD_BF16>(uint4 a, uint4 b, cb_acc c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cb_bf16x8, a), __builtin_bit_cast(cb_bf16x8, b), c, 0, 0, 0);
-}
 
 /* The sum of the 256 threads' values in binary64: t += t + s for s = 128 .. 1.  `lds` holds 256 doubles; every thread
  * of the block calls, and gets the sum. */
@@ -190,9 +162,6 @@ __global__ __launch_bounds__(256) void k_conv_bwd_pack_t(const float* __restrict
     asm volatile("" : "+v"(product));
     packed[e] = cb_round<DT>(product);
 }
-
-/* entry of (slot s of 8 pixels, row) in a tile */
-__device__ __forceinline__ int cb_entry(int s, int row) { return 64 * s + (row ^ (2 * s)); }
 
 /* part[((chunk * TAPS + tap) * Cout + co) * Cin + ci], chunk = image * bands + band */
 template <int DT, int TAPS>
@@ -372,14 +341,19 @@ __global__ __launch_bounds__(256) void k_conv_bwd_channel(const double* __restri
 }
 
 static size_t cb_align(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-static int cb_bands(int H) { return (H + IS_CONV_BACKWARD_BAND - 1) / IS_CONV_BACKWARD_BAND; }
+/* the bands of H OUTPUT rows: IS_CONV_BACKWARD_BAND rows at stride 1, IS_CONV_BACKWARD_STRIDE_BAND at stride 2 */
+static int cb_bands(int H, int stride) {
+    const int band = stride == 2 ? IS_CONV_BACKWARD_STRIDE_BAND : IS_CONV_BACKWARD_BAND;
+    return (H + band - 1) / band;
+}
 static int cb_pblocks(int H, int W) { return (int)(((long long)H * W + CB_PREP_BLOCK - 1) / CB_PREP_BLOCK); }
 
 /* the sections of the scratch, in this order, each 16-byte aligned */
 struct cb_scratch {
     size_t gh, packed, ones, zeros, shift_part, gsum, part, end;
 };
-static cb_scratch cb_layout(int n, int Cin, int Cout, int H, int W, int kernel) {
+/* H, W: the OUTPUT's extents (the input's at stride 1) */
+static cb_scratch cb_layout(int n, int Cin, int Cout, int H, int W, int kernel, int stride) {
     const size_t taps = (size_t)kernel * kernel, P = (size_t)H * W;
     cb_scratch s;
     s.gh = 0;
@@ -389,28 +363,33 @@ static cb_scratch cb_layout(int n, int Cin, int Cout, int H, int W, int kernel) 
     s.shift_part = s.zeros + cb_align((size_t)Cin * 4);
     s.gsum = s.shift_part + cb_align((size_t)n * Cout * cb_pblocks(H, W) * 8);
     s.part = s.gsum + cb_align((size_t)Cout * Cin * taps * 8);
-    s.end = s.part + cb_align((size_t)n * cb_bands(H) * taps * Cout * Cin * 4);
+    s.end = s.part + cb_align((size_t)n * cb_bands(H, stride) * taps * Cout * Cin * 4);
     return s;
 }
 
 /* The grid of k_conv_bwd_weight (0: it does not fit 31 bits). */
 static long long cb_weight_grid(int n, int Cin, int Cout, int H) {
-    const long long tiles = (long long)((Cout + 63) / 64) * ((Cin + 63) / 64), chunks = (long long)n * cb_bands(H);
+    const long long tiles = (long long)((Cout + 63) / 64) * ((Cin + 63) / 64), chunks = (long long)n * cb_bands(H, 1);
     const long long grid = tiles * ((chunks + 7) / 8 * 8);
     return grid > 0x7fffffffLL ? 0 : grid;
 }
 
-extern "C" size_t isk_conv_backward_scratch_bytes(int n_images, int channels_in, int channels_out, int rows8, int cols8,
-                                                  int kernel) {
-    if (!cb_weight_grid(n_images, channels_in, channels_out, rows8)) return 0;
-    return cb_layout(n_images, channels_in, channels_out, rows8, cols8, kernel).end;
+extern "C" size_t isk_conv_backward_scratch_bytes(int n_images, int channels_in, int channels_out, int rows_in, int cols_in,
+                                                  int kernel, int stride) {
+    const int H = (rows_in + stride - 1) / stride, W = (cols_in + stride - 1) / stride;
+    if (!(stride == 2 ? isk_conv_bwd_weight_s2_grid(n_images, channels_in, channels_out, H)
+                      : cb_weight_grid(n_images, channels_in, channels_out, H)))
+        return 0;
+    return cb_layout(n_images, channels_in, channels_out, H, W, kernel, stride).end;
 }
 
-/* The arguments are checked by is_conv_bn_backward. */
-extern "C" hipError_t isk_launch_conv_bn_backward(const is_conv_bn_backward_args* a, hipStream_t stream) {
-    const int n = a->n_images, Cin = a->channels_in, Cout = a->channels_out, H = a->rows8, W = a->cols8;
-    const int taps = a->kernel * a->kernel, P = H * W, pblocks = cb_pblocks(H, W), bands = cb_bands(H), chunks = n * bands;
-    const cb_scratch lay = cb_layout(n, Cin, Cout, H, W, a->kernel);
+/* The arguments are checked by is_core.hip's conv_bn_backward_run, for is_conv_bn_backward and
+ * is_conv_bn_stride_backward alike.  H, W: the OUTPUT's extents, which gh, dshift and the chunks go by. */
+extern "C" hipError_t isk_launch_conv_bn_backward(const is_conv_bn_stride_backward_args* a, hipStream_t stream) {
+    const int n = a->n_images, Cin = a->channels_in, Cout = a->channels_out, s2 = a->stride == 2;
+    const int H = (a->rows_in + a->stride - 1) / a->stride, W = (a->cols_in + a->stride - 1) / a->stride;
+    const int taps = a->kernel * a->kernel, P = H * W, pblocks = cb_pblocks(H, W), bands = cb_bands(H, a->stride), chunks = n * bands;
+    const cb_scratch lay = cb_layout(n, Cin, Cout, H, W, a->kernel, a->stride);
     char* const scratch = (char*)a->d_scratch;
     uint16_t* const gh = a->d_grad_pre ? (uint16_t*)a->d_grad_pre : (uint16_t*)(scratch + lay.gh);
     uint16_t* const packed = (uint16_t*)(scratch + lay.packed);
@@ -439,7 +418,7 @@ extern "C" hipError_t isk_launch_conv_bn_backward(const is_conv_bn_backward_args
             hipLaunchKernelGGL(k_conv_bwd_prepare<IS_HEAD_BF16>, grid, dim3(256), 0, stream, a->d_out, out_f32, a->relu,
                                a->d_grad_out, dy_f32, a->grad_image_stride, gh, sp, Cout, P, vec);
     }
-    if (a->d_grad_features) { /* the transposed pack, then f18's launch with the channels swapped */
+    if (a->d_grad_features) { /* the transposed pack, then (stride 1) f18's launch with the channels swapped */
         const int total = Cin * Cout * taps;
         const dim3 grid((total + 255) / 256);
         if (f16)
@@ -448,15 +427,20 @@ extern "C" hipError_t isk_launch_conv_bn_backward(const is_conv_bn_backward_args
         else
             hipLaunchKernelGGL(k_conv_bwd_pack_t<IS_HEAD_BF16>, grid, dim3(256), 0, stream, a->d_weight, a->d_scale, packed,
                                ones, zeros, Cin, Cout, taps, total);
-        is_conv_bn_stride_args c = {};
-        c.d_features = gh, c.dtype = a->dtype, c.n_images = n, c.channels_in = Cout, c.channels_out = Cin;
-        c.rows_in = H, c.cols_in = W, c.kernel = a->kernel, c.stride = 1, c.dilation = a->dilation;
-        c.d_packed = packed, c.d_scale = ones, c.d_shift = zeros, c.d_residual = a->d_grad_features_add, c.relu = 0;
-        c.d_out = a->d_grad_features, c.out_dtype = a->grad_features_dtype;
-        const hipError_t e = isk_launch_conv_bn(&c, stream);
-        if (e != hipSuccess) return e;
+        if (s2) { /* the gather form of the transposed convolution (is_k_conv_backward_stride.hip) */
+            isk_launch_conv_bwd_data_s2(a, gh, packed, stream);
+        } else {
+            is_conv_bn_stride_args c = {};
+            c.d_features = gh, c.dtype = a->dtype, c.n_images = n, c.channels_in = Cout, c.channels_out = Cin;
+            c.rows_in = H, c.cols_in = W, c.kernel = a->kernel, c.stride = 1, c.dilation = a->dilation;
+            c.d_packed = packed, c.d_scale = ones, c.d_shift = zeros, c.d_residual = a->d_grad_features_add, c.relu = 0;
+            c.d_out = a->d_grad_features, c.out_dtype = a->grad_features_dtype;
+            const hipError_t e = isk_launch_conv_bn(&c, stream);
+            if (e != hipSuccess) return e;
+        }
     }
-    if (contract) {
+    if (contract && s2) isk_launch_conv_bwd_weight_s2(a, gh, part, stream);
+    if (contract && !s2) {
         const int tiles_ci = (Cin + 63) / 64, tiles = tiles_ci * ((Cout + 63) / 64);
         const dim3 grid((unsigned)cb_weight_grid(n, Cin, Cout, H));
         const size_t lds = (size_t)(1 + taps) * CB_TILE_ENTRIES * 16;
@@ -469,6 +453,8 @@ extern "C" hipError_t isk_launch_conv_bn_backward(const is_conv_bn_backward_args
             if (taps == 9) CB_WEIGHT(IS_HEAD_BF16, 9); else CB_WEIGHT(IS_HEAD_BF16, 1);
         }
 #undef CB_WEIGHT
+    }
+    if (contract) {
         const int total = taps * Cout * Cin; /* at most 9 * 2^22 */
         hipLaunchKernelGGL(k_conv_bwd_reduce, dim3((total + 255) / 256), dim3(256), 0, stream, (const float*)part, chunks,
                            Cin, Cout, taps, a->d_scale, a->d_grad_weight, a->d_grad_scale ? gsum : nullptr);

@@ -255,8 +255,15 @@ hipError_t isk_launch_conv_pack(const float* d_weight, int channels_out, int cha
 hipError_t isk_launch_conv_bn(const is_conv_bn_stride_args* a, hipStream_t stream);
 
 /* is_k_conv_backward.hip */
-size_t isk_conv_backward_scratch_bytes(int n_images, int channels_in, int channels_out, int rows8, int cols8, int kernel);
-hipError_t isk_launch_conv_bn_backward(const is_conv_bn_backward_args* a, hipStream_t stream);
+size_t isk_conv_backward_scratch_bytes(int n_images, int channels_in, int channels_out, int rows_in, int cols_in, int kernel,
+                                       int stride);
+hipError_t isk_launch_conv_bn_backward(const is_conv_bn_stride_backward_args* a, hipStream_t stream);
+
+/* is_k_conv_backward_stride.hip: the two stride-2 kernels of the launcher above.  gh, part: the launcher's sections. */
+void isk_launch_conv_bwd_data_s2(const is_conv_bn_stride_backward_args* a, const void* gh, const void* packed,
+                                 hipStream_t stream);
+void isk_launch_conv_bwd_weight_s2(const is_conv_bn_stride_backward_args* a, const void* gh, float* part, hipStream_t stream);
+long long isk_conv_bwd_weight_s2_grid(int n_images, int channels_in, int channels_out, int rows_out);
 
 /* is_k_stem.hip */
 size_t isk_stem_packed_bytes(void);

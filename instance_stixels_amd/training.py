@@ -269,28 +269,43 @@ def _half_features(x):
                              "(fp32 features are not built: convert them first)")
 
 
+def _conv(x, packed, scale, shift, kernel, stride, dilation, **more):
+    """core.conv_bn at stride 1 (f21's modules keep their call), core.conv_bn_stride at stride 2."""
+    if stride == 1:
+        return core.conv_bn(x, packed, scale, shift, kernel, dilation, **more)
+    return core.conv_bn_stride(x, packed, scale, shift, kernel, stride, dilation, **more)
+
+
+def _conv_backward(x, weight, scale, out, grad_out, kernel, stride, dilation, **more):
+    """core.conv_bn_backward at stride 1, core.conv_bn_stride_backward at stride 2."""
+    if stride == 1:
+        return core.conv_bn_backward(x, weight, scale, out, grad_out, kernel, dilation, **more)
+    return core.conv_bn_stride_backward(x, weight, scale, out, grad_out, kernel, stride, dilation, **more)
+
+
 class _ConvBnFunction(torch.autograd.Function):
-    """Forward: the pack of the current weight and one launch of core.conv_bn.  Backward: one call of
-    core.conv_bn_backward that asks for the gradients autograd needs and no others."""
+    """Forward: the pack of the current weight and one launch of core.conv_bn (stride 2: core.conv_bn_stride).
+    Backward: one call of core.conv_bn_backward (core.conv_bn_stride_backward) that asks for the gradients autograd
+    needs and no others."""
 
     @staticmethod
-    def forward(ctx, x, weight, scale, shift, kernel, dilation, relu):
+    def forward(ctx, x, weight, scale, shift, kernel, dilation, relu, stride=1):
         packed = core.conv_pack_weights(weight.detach(), x.dtype)
-        out = core.conv_bn(x.detach(), packed, scale.detach(), shift.detach(), kernel, dilation, relu=relu)
+        out = _conv(x.detach(), packed, scale.detach(), shift.detach(), kernel, stride, dilation, relu=relu)
         ctx.save_for_backward(x, weight, scale, out)
-        ctx.conv = (kernel, dilation, relu)
+        ctx.conv = (kernel, dilation, relu, stride)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         x, weight, scale, out = ctx.saved_tensors
-        kernel, dilation, relu = ctx.conv
+        kernel, dilation, relu, stride = ctx.conv
         need = ctx.needs_input_grad[:4]
         if not any(need):
-            return (None,) * 7
-        g = core.conv_bn_backward(x, weight, scale, out, grad_out, kernel, dilation, relu=relu, want_features=need[0],
-                                  want_weight=need[1], want_scale=need[2], want_shift=need[3])
-        return g.get("features"), g.get("weight"), g.get("scale"), g.get("shift"), None, None, None
+            return (None,) * 8
+        g = _conv_backward(x, weight, scale, out, grad_out, kernel, stride, dilation, relu=relu, want_features=need[0],
+                           want_weight=need[1], want_scale=need[2], want_shift=need[3])
+        return g.get("features"), g.get("weight"), g.get("scale"), g.get("shift"), None, None, None, None
 
 
 class ConvBnReLU(torch.nn.Module):
@@ -301,10 +316,13 @@ class ConvBnReLU(torch.nn.Module):
     is_conv_bn_backward (instance_stixels_core.h f21).  Batch-statistics BatchNorm, stride 2 and fp32 features raise
     CoreError before anything is packed."""
 
+    strides = (1,)     # the strides of conv that the class accepts
+
     def __init__(self, conv, bn, relu=True):
         super().__init__()
         from . import cnn
-        self.dilation = cnn._dilated3x3(conv, "conv", (1,))
+        self.dilation = cnn._dilated3x3(conv, "conv", self.strides)
+        self.stride = int(conv.stride[0])
         _frozen_bn(bn, "bn")
         if bn.num_features != conv.out_channels:
             raise core.CoreError(f"bn has {bn.num_features} channels, conv {conv.out_channels}")
@@ -315,23 +333,37 @@ class ConvBnReLU(torch.nn.Module):
     def forward(self, features):
         _half_features(features)
         scale, shift = self.bn.fold()
-        return _ConvBnFunction.apply(features, self.weight, scale, shift, self.kernel, self.dilation, self.relu)
+        return _ConvBnFunction.apply(features, self.weight, scale, shift, self.kernel, self.dilation, self.relu,
+                                     self.stride)
 
 
-def _basic_block_layout(block):
-    """The checks of a BasicBlock-shaped `block` (conv1, bn1, conv2, bn2, downsample, residual), cnn.ResidualBlock's at
-    stride 1, made before anything is folded or packed: (conv1's dilation, conv2's dilation, whether the block adds a
-    residual, the downsample's (Conv2d, BatchNorm2d) or None)."""
+class StridedConvBnReLU(ConvBnReLU):
+    """ConvBnReLU for a conv of stride 1 or 2, as cnn.StridedConvBnRelu checks the pair (layer2 of the reference: stride
+    2, padding 1, dilation 1).  Its forward is cnn.StridedConvBnRelu's launch and bytes; its backward at stride 2 is
+    one call of is_conv_bn_stride_backward (instance_stixels_core.h f22).  The gradient of the features needs
+    channels_in % 32 == 0: layer2 itself (16 channels in) trains its weight and BatchNorm pair behind a frozen stem."""
+
+    strides = (1, 2)
+
+
+def _basic_block_layout(block, strides=(1,)):
+    """The checks of a BasicBlock-shaped `block` (conv1, bn1, conv2, bn2, downsample, residual), cnn.ResidualBlock's
+    (strides (1, 2): cnn.StridedResidualBlock's), made before anything is folded or packed: (conv1's dilation, conv2's
+    dilation, whether the block adds a residual, the downsample's (Conv2d, BatchNorm2d) or None).  conv1's stride, and
+    with it the downsample's, is out of `strides`."""
     from . import cnn
     if hasattr(block, "conv3"):
         raise core.CoreError("a block with conv3 is a Bottleneck: only BasicBlock is covered")
-    d1, d2 = cnn._dilated3x3(block.conv1, "conv1", (1,)), cnn._dilated3x3(block.conv2, "conv2")
+    d1, d2 = cnn._dilated3x3(block.conv1, "conv1", strides), cnn._dilated3x3(block.conv2, "conv2")
+    stride = int(block.conv1.stride[0])
     c_in, c_mid, c_out = block.conv1.in_channels, block.conv1.out_channels, block.conv2.out_channels
     if block.conv2.in_channels != c_mid or block.bn1.num_features != c_mid or block.bn2.num_features != c_out:
         raise core.CoreError("conv1, bn1, conv2 and bn2 disagree on their channels")
     residual = bool(block.residual)
     down = block.downsample if residual else None      # (the reference computes and drops it otherwise)
     if down is None:
+        if residual and stride != 1:
+            raise core.CoreError(f"conv1 has stride {stride} and the block no downsample: the input cannot be the residual")
         if residual and c_in != c_out:
             raise core.CoreError(f"residual=True without a downsample needs equal channels, not {c_in} -> {c_out}")
         return d1, d2, residual, None
@@ -342,8 +374,11 @@ def _basic_block_layout(block):
             or mods[1].num_features != c_out:
         raise core.CoreError("downsample must be nn.Sequential(Conv2d(kernel_size=1, bias=False), BatchNorm2d) "
                              "from the block's input to its output channels")
-    if tuple(mods[0].stride) != (1, 1):
+    if tuple(strides) == (1,) and tuple(mods[0].stride) != (1, 1):
         raise core.CoreError(f"downsample has stride {tuple(mods[0].stride)}: only stride 1 is covered")
+    if tuple(mods[0].stride) != (stride, stride):
+        raise core.CoreError(f"downsample has stride {tuple(mods[0].stride)}, conv1 {(stride, stride)}: the "
+                             "residual must have the shape of conv2's output")
     return d1, d2, residual, (mods[0], mods[1])
 
 
@@ -355,28 +390,31 @@ class _BasicBlockFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, d1, d2, residual, *params):
+        stride = 1
+        if isinstance(params[-1], int):                    # (StridedBasicBlock's: conv1's and the downsample's stride)
+            params, stride = params[:-1], params[-1]
         w1, s1, b1, w2, s2, b2 = params[:6]
         down = params[6:] if len(params) == 9 else None
         xd = x.detach()
         pack = lambda w: core.conv_pack_weights(w.detach(), x.dtype)
-        y1 = core.conv_bn(xd, pack(w1), s1.detach(), b1.detach(), 3, d1, relu=True)
+        y1 = _conv(xd, pack(w1), s1.detach(), b1.detach(), 3, stride, d1, relu=True)
         res = None
         if residual:
-            res = core.conv_bn(xd, pack(down[0]), down[1].detach(), down[2].detach(), 1, 1, relu=False) if down else xd
+            res = _conv(xd, pack(down[0]), down[1].detach(), down[2].detach(), 1, stride, 1, relu=False) if down else xd
         out = core.conv_bn(y1, pack(w2), s2.detach(), b2.detach(), 3, d2, residual=res, relu=True)
         ctx.save_for_backward(x, y1, out, w1, s1, w2, s2, *((down[0], down[1]) if down else ()))
-        ctx.block = (d1, d2, residual, down is not None)
+        ctx.block = (d1, d2, residual, down is not None, stride)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         x, y1, out, w1, s1, w2, s2 = ctx.saved_tensors[:7]
-        d1, d2, residual, has_down = ctx.block
+        d1, d2, residual, has_down, stride = ctx.block
         need = ctx.needs_input_grad
         need_x, n1, n2, nd = need[0], need[4:7], need[7:10], need[10:13] if has_down else (False,) * 3
         through1 = need_x or any(n1)                       # anything behind conv1's output
         side = residual and (need_x or any(nd))            # the residual operand's gradient is used
-        grads = [None] * (4 + (9 if has_down else 6))
+        grads = [None] * (4 + (9 if has_down else 6) + (stride != 1))
         if not (through1 or side or any(n2)):
             return tuple(grads)
         g2 = core.conv_bn_backward(y1, w2, s2, out, grad_out, 3, d2, relu=True, want_features=through1,
@@ -385,16 +423,16 @@ class _BasicBlockFunction(torch.autograd.Function):
         add = None
         if side and has_down:
             wd, sd = ctx.saved_tensors[7:9]
-            gd = core.conv_bn_backward(x, wd, sd, None, g2["pre"], 1, 1, relu=False, want_features=need_x,
-                                       want_weight=nd[0], want_scale=nd[1], want_shift=nd[2])
+            gd = _conv_backward(x, wd, sd, None, g2["pre"], 1, stride, 1, relu=False, want_features=need_x,
+                                want_weight=nd[0], want_scale=nd[1], want_shift=nd[2])
             grads[10:13] = gd.get("weight"), gd.get("scale"), gd.get("shift")
             add = gd.get("features")
         elif side:
             add = g2["pre"]                                # x itself was the residual
         if through1:
-            g1 = core.conv_bn_backward(x, w1, s1, y1, g2["features"], 3, d1, relu=True, want_features=need_x,
-                                       want_weight=n1[0], want_scale=n1[1], want_shift=n1[2],
-                                       features_add=add if need_x else None)
+            g1 = _conv_backward(x, w1, s1, y1, g2["features"], 3, stride, d1, relu=True, want_features=need_x,
+                                want_weight=n1[0], want_scale=n1[1], want_shift=n1[2],
+                                features_add=add if need_x else None)
             grads[0] = g1.get("features")
             grads[4:7] = g1.get("weight"), g1.get("scale"), g1.get("shift")
         return tuple(grads)
@@ -407,9 +445,12 @@ class BasicBlock(torch.nn.Module):
     node whose backward is 2 calls of is_conv_bn_backward, 3 with a downsample, and no torch kernel between them.
     Stride 2, batch statistics and fp32 features raise CoreError before anything is packed."""
 
+    strides = (1,)     # the strides of conv1 (and with it of the downsample) that the class accepts; conv2 has 1
+
     def __init__(self, block):
         super().__init__()
-        self.d1, self.d2, self.residual, down = _basic_block_layout(block)
+        self.d1, self.d2, self.residual, down = _basic_block_layout(block, self.strides)
+        self.stride = int(block.conv1.stride[0])
         for name, bn in (("bn1", block.bn1), ("bn2", block.bn2)) + ((("downsample's bn", down[1]),) if down else ()):
             _frozen_bn(bn, name)
         self.weight1 = torch.nn.Parameter(block.conv1.weight.detach().clone().float())
@@ -423,4 +464,48 @@ class BasicBlock(torch.nn.Module):
         params = [self.weight1, *self.bn1.fold(), self.weight2, *self.bn2.fold()]
         if self.weight_down is not None:
             params += [self.weight_down, *self.bn_down.fold()]
+        if self.stride != 1:
+            params.append(self.stride)
         return _BasicBlockFunction.apply(features, self.d1, self.d2, self.residual, *params)
+
+
+class StridedBasicBlock(BasicBlock):
+    """BasicBlock for a block whose conv1 has stride 1 or 2, as cnn.StridedResidualBlock checks it (the first blocks of
+    layer3 and layer4: conv1 3x3 stride 2, downsample 1x1 stride 2 + BatchNorm, conv2 3x3 stride 1).  The forward is
+    cnn.StridedResidualBlock's launches and bytes; the block is ONE autograd node whose backward is conv2's call of
+    is_conv_bn_backward with the masked gradient handed out, the downsample's call of is_conv_bn_stride_backward and
+    conv1's, which takes the downsample's dX as features_add: no torch kernel in between."""
+
+    strides = (1, 2)
+
+
+class DrnLayers(torch.nn.Module):
+    """layer2 -> layer3 -> ... -> layer8 of the reference's base as one trainable chain: layer1's output [n][16][rows]
+    [cols] in float16 or bfloat16 in, layer8's output at 1/8 resolution out, which feeds SegmentationHead.  A layer
+    that is nn.Sequential(Conv2d, BatchNorm2d, ReLU) (layer2, layer7, layer8) becomes a StridedConvBnReLU, every other
+    layer a sequence of StridedBasicBlocks; every BatchNorm is frozen at its running statistics.  The stem is frozen:
+    an input that requires grad raises CoreError, because dX at layer2's 16 channels is not built."""
+
+    def __init__(self, layer2, layer3, layer4, layer5, layer6, layer7, layer8):
+        super().__init__()
+        from . import cnn
+        mods = []
+        for i, layer in enumerate((layer2, layer3, layer4, layer5, layer6, layer7, layer8)):
+            name = f"layer{i + 2}"
+            if not isinstance(layer, torch.nn.Sequential):
+                raise core.CoreError(f"{name} must be an nn.Sequential, not {type(layer).__name__}")
+            if len(layer) and isinstance(layer[0], torch.nn.Conv2d):
+                mods.append(StridedConvBnReLU(*cnn._conv_bn_relu_of(layer, name)))
+            else:
+                mods.extend(StridedBasicBlock(b) for b in layer)
+        self.layers = torch.nn.ModuleList(mods)
+
+    def forward(self, features):
+        if torch.is_tensor(features) and features.requires_grad:
+            raise core.CoreError("the input of DrnLayers requires grad: the stem is frozen, and the gradient of layer2's "
+                                 "16-channel input is not built")
+        _half_features(features)
+        x = features
+        for layer in self.layers:
+            x = layer(x)
+        return x

@@ -37,11 +37,17 @@ comma-separated), for fp16 and bf16 features [n][.][rows8][cols8] with half outp
   weight and the BatchNorm affine pair, the forward graph built outside the timing.  `scratch_mb` is the call's scratch.
   The MFMA floor counts dX and dW: 2 x the forward's FLOP.  Both arms allocate their outputs inside the timing (torch's
   caching allocator; the library's arm also its scratch), as a training step does.  --backward-cases picks shapes.
+- backward_stride (not in the default --parts): core.conv_bn_stride_backward (f22) at the five stride-2 launches of
+  drn_d_22 on layer1's output [--backward-n][16][--rows][--cols] -- 3x3 at 16 -> 32 (layer2, no dX: it is refused at 16
+  channels), 32 -> 64 and 64 -> 128, 1x1 at 32 -> 64 and 64 -> 128, each at its layer's resolution -- with every gradient
+  and without dX, against torch.autograd.grad as in `backward` (with respect to x too, except at layer2).
+  `compulsory_gb` is x, the saved output (3x3), dY and dX once each; `new_share_of_hbm_floor` is its time at --hbm-gbs
+  over the call's.  --backward-stride-cases picks launches.
 --no-torch leaves the torch arms out (and alone allows fewer than 10 iterations, for a counter run).  torch's first
 convolution of a shape takes 30 - 160 s: run the dtypes, and if need be the parts, in separate commands.
 
     python tools/time_conv.py [--n 64 --C 512 --rows8 128 --cols8 256 --iters 20 --mhz 2400 --cus 256 --dtypes fp16,bf16
-                               --parts tail,residual,1x1,layers[,strided][,stem] --rows 1024 --cols 2048 --strided-n 64
+                               --parts tail,residual,1x1,layers[,strided][,stem][,backward][,backward_stride] --rows 1024 --cols 2048 --strided-n 64
                                --stem-n 64
                                --no-torch]
 """
@@ -73,7 +79,9 @@ def main():
     ap.add_argument("--dp-n", type=int, default=0, help="0: the whole batch (a shape the library is already tuned for)")
     ap.add_argument("--dtypes", default="fp16,bf16", help="comma-separated subset of fp16,bf16")
     ap.add_argument("--parts", default="tail,residual,1x1,layers",
-                    help="comma-separated subset of tail,residual,1x1,layers,strided,stem,backward")
+                    help="comma-separated subset of tail,residual,1x1,layers,strided,stem,backward,backward_stride")
+    ap.add_argument("--backward-stride-cases", default="0,1,2,3,4", help="which of the five launches of `backward_stride`")
+    ap.add_argument("--hbm-gbs", type=float, default=6300.0, help="the memory rate of the compulsory-traffic floor")
     ap.add_argument("--backward-n", type=int, default=4, help="frames per call of the `backward` part")
     ap.add_argument("--backward-cases", default="0,1,2,3,4,5", help="which of the six shapes of the `backward` part")
     ap.add_argument("--rows", type=int, default=1024, help="rows of layer1's output (the `strided` part)")
@@ -323,6 +331,56 @@ def main():
                 against_torch(row, med)
                 out["%s_backward_%d_%d_k%d_d%d" % (name, cin, cout, k, d)] = row
                 note(name, "backward", json.dumps(row))
+                del x, y, gy, arms
+                if not a.no_torch:
+                    del graphs
+                torch.cuda.empty_cache()
+        if "backward_stride" in parts:
+            m, H1, W1 = a.backward_n, a.rows, a.cols
+            half = lambda v, times: -(-v // 2 ** times)                      # ceil(v / 2^times)
+            # (label, channels_in, channels_out, kernel, level of the input's resolution)
+            cases = (("3x3s2_16_32", 16, 32, 3, 0), ("3x3s2_32_64", 32, 64, 3, 1), ("1x1s2_32_64", 32, 64, 1, 1),
+                     ("3x3s2_64_128", 64, 128, 3, 2), ("1x1s2_64_128", 64, 128, 1, 2))
+            for label, cin, cout, k, level in [cases[int(i)] for i in a.backward_stride_cases.split(",")]:
+                relu, dx = k == 3, cin % 32 == 0                               # (the 1x1 is the downsample: no ReLU)
+                Hi, Wi = half(H1, level), half(W1, level)
+                Ho, Wo = half(Hi, 1), half(Wi, 1)
+                x = torch.randn((m, cin, Hi, Wi), device=dev).abs_().to(dtype)
+                w32, stats = weight(cout, cin, k), bn_stats(cout)
+                scale, shift = fold(*stats)
+                y = core.conv_bn_stride(x, core.conv_pack_weights(w32, dtype), scale, shift, k, 2, relu=relu)
+                gy = torch.randn((m, cout, Ho, Wo), device=dev).to(dtype)
+                arms = {"new_no_dx": lambda: core.conv_bn_stride_backward(x, w32, scale, y, gy, k, 2, relu=relu,
+                                                                          want_features=False)}
+                if dx:
+                    arms["new"] = lambda: core.conv_bn_stride_backward(x, w32, scale, y, gy, k, 2, relu=relu)
+                whole = "new" if dx else "new_no_dx"
+                if not a.no_torch:
+                    graphs = {}
+                    for arm, cl in (("torch_contiguous", False), ("torch_channels_last", True)):
+                        xt, wt = x.clone(), w32.to(dtype)
+                        if cl:
+                            xt, wt = channels_last(xt, wt)
+                        xt, wt = xt.requires_grad_(dx), wt.requires_grad_(True)
+                        mean, var, gamma, beta = [t.to(dtype) for t in stats]
+                        gamma, beta = gamma.requires_grad_(True), beta.requires_grad_(True)
+                        yt = F.batch_norm(F.conv2d(xt, wt, stride=2, padding=k // 2), mean, var, gamma, beta, False, 0.0, eps)
+                        yt = F.relu(yt) if relu else yt
+                        wrt = ((xt,) if dx else ()) + (wt, gamma, beta)
+                        graphs[arm] = (yt, wrt, channels_last(gy)[0] if cl else gy)
+                        arms[arm] = lambda arm=arm: torch.autograd.grad(graphs[arm][0], graphs[arm][1], graphs[arm][2],
+                                                                        retain_graph=True)
+                row, med = measure("%s backward_stride %s" % (name, label), arms)
+                gb = m * 2 * (cin * Hi * Wi * (2 if dx else 1) + (2 if relu else 1) * cout * Ho * Wo) / 1e9
+                tflop = (2 if dx else 1) * 2.0 * k * k * cin * cout * m * Ho * Wo / 1e12
+                row.update(shape=[m, cin, cout, Hi, Wi, k, 2], band=core.CONV_BACKWARD_STRIDE_BAND, tflop=round(tflop, 4),
+                           compulsory_gb=round(gb, 3), hbm_floor_ms=round(gb / a.hbm_gbs * 1e3, 3),
+                           new_share_of_hbm_floor=round(gb / a.hbm_gbs * 1e3 / med[whole], 3),
+                           scratch_mb=round(core.conv_bn_stride_backward_scratch_bytes(
+                               m, cin, cout, Hi, Wi, k, 2, core.HEAD_F16 if dtype == torch.float16 else core.HEAD_BF16) / 2 ** 20, 1))
+                against_torch(row, med, new=whole)
+                out["%s_backward_stride_%s" % (name, label)] = row
+                note(name, "backward_stride", json.dumps(row))
                 del x, y, gy, arms
                 if not a.no_torch:
                     del graphs
