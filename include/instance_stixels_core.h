@@ -1622,6 +1622,121 @@ size_t is_conv_bn_stride_backward_scratch_bytes(int n_images, int channels_in, i
  * non-zero reserved field. */
 int is_conv_bn_stride_backward(const is_conv_bn_stride_backward_args* args, void* stream);
 
+/* ---- f23: the backward pass of the stem, layer0 and layer1 (is_k_stem_backward.hip) ----------------------------------
+ * The backward of exactly is_stem's forward: BatchNorm folded and frozen, the operands the half values the forward
+ * used, f21's rules (every summation order fixed by the shape alone, no floating-point atomics, the same bytes on every
+ * run and for every choice of outputs, a frame's gh planes independent of n_images and of its position in the batch, no
+ * address that depends on a value other than the table index, no load outside the image's bytes or the tensors'
+ * extents; non-finite values give unspecified values, never a wild access).  With it every parameter of drn_d_22 has a
+ * gradient on the device.  There is no gradient for the table or the image.
+ *
+ * w*_half = the half rounding is_stem_pack_weights makes; P = rows * cols.
+ *
+ *   g_out [n][16][rows][cols]   the gradient with respect to `out`, from exactly one of two sources:
+ *             (a) d_grad_out (dY), `dtype` or IS_HEAD_F32, frame f at d_grad_out + f * grad_image_stride elements, as
+ *             f21's;
+ *             (b) d_grad_next, the masked gradient gh of the stride-2 3x3 layer that reads `out` (layer2's d_grad_pre of
+ *             f22, [n][channels_next][(rows + 1) / 2][(cols + 1) / 2] of `dtype`), with that layer's master weight
+ *             d_weight_next [channels_next][16][3][3] and folded scale d_scale_next: f22's stride-2 dX formula at kernel
+ *             3 with 16 input channels, g_out[n][ci][r][c] = sum over co and over the taps (ky, kx) with r + 1 - ky and
+ *             c + 1 - kx both even and y = (r + 1 - ky) / 2, x = (c + 1 - kx) / 2 inside gh, of wT[ci][co][tap] *
+ *             gh[n][co][y][x], wT = round_half(scale_next[co] * w_next_half[co][ci][tap]); the parity classes use 1, 2,
+ *             2 and 4 taps.  ONE fp32 MFMA accumulator chain per element (v_mfma_f32_16x16x32), in increasing 32-channel
+ *             chunk of channels_next and, inside a chunk, increasing tap 3 ky + kx among the element's class; rounded
+ *             once to `dtype`.  g_out is computed by a launch of its own into the scratch (the fusion
+ *             into the next launch is not built; the bytes are the same).
+ *   gh1 = round_half(g_out) where the STORED out > 0, else +0.
+ *   dshift1[co] = (float) sum (double)gh1, in binary64: a workgroup of k_stem_bwd_data owns a tile of IS_STEM_BACKWARD_TILE_ROWS
+ *             x IS_STEM_BACKWARD_TILE_COLS pixels of one frame; thread (row r, channel co) adds its row of the tile in
+ *             increasing column, then the 16 rows in increasing r; one block per co adds the tiles' sums, image outer
+ *             and tile inner (row-major), as contiguous thread ranges and f21's LDS tree (k_conv_bwd_channel).
+ *   dMid [n][16][rows][cols] = the 3x3, padding-1 convolution of gh1 with wT1[ci][co][8 - tap] = round_half(scale1[co] *
+ *             w1_half[co][ci][tap]) (the product in fp32, rounded once); a tap outside the image contributes nothing.
+ *             ONE fp32 accumulator chain per element by v_mfma_f32_16x16x32_{f16,bf16}: five instructions in increasing
+ *             k = 16 tap' + co, tap' = 8 - tap, the slots k >= 144 exact zeros on both operands; rounded once to `dtype`.
+ *   gh0 = dMid where the STORED mid > 0, else +0.
+ *   dshift0[co] = (float) sum (double)gh0: a lane of k_stem_bwd_data adds its four pixels of a 16-pixel group in increasing
+ *             column and its groups in increasing order (row-major in the tile, every fourth group to a wave); the 16
+ *             lanes of a channel are added in increasing (wave, lane >> 4); then as dshift1.
+ *   G1[co][ci][tap] = sum gh1[n][co][y][x] * mid[n][ci][y + ky - 1][x + kx - 1]
+ *   G0[co][c][ky][kx] = sum gh0[n][co][y][x] * lut[c][image[n][y + ky - 3][x + kx - 3][c]]; a tap outside the image
+ *             contributes nothing (zero padding of the normalised value, not lut[c][0]).
+ *             The contraction over pixels is split and the split is part of the contract: chunk (i, j, k) is image i,
+ *             rows [j B, (j + 1) B), columns [k S, (k + 1) S), B = IS_STEM_BACKWARD_BAND and S =
+ *             IS_STEM_BACKWARD_SEGMENT for every shape.  Inside a chunk ONE fp32 MFMA accumulator per (co, ci, tap), fed
+ *             by v_mfma_f32_16x16x32_{f16,bf16} with pixels on K: the chunk's rows in increasing y, in a row the S / 32
+ *             steps of 32 pixels in increasing column (the slots past the row's end or outside the image are exact
+ *             zeros).  Gsum = the binary64 sum of the partials, i outer, then j, then k, increasing.
+ *   dW = (float)((double)scale[co] * Gsum), conv.weight's layout;  dscale[co] = (float) sum (double)w_half * Gsum in
+ *             increasing (ci, tap): f21's reductions (k_conv_bwd_reduce, k_conv_bwd_channel), their instantiations.
+ *   Every output is optional, at least one is asked for; leaving one out changes no byte of the others.  The launch
+ *   of the partials and the reductions run only when an output needs them.
+ *
+ * Zero-initialise, then set the fields.  All arrays on the current device.
+ *   d_image, n_images, rows, cols, d_lut, dtype   as in is_stem_args
+ *   d_w0, d_w1          the fp32 master weights [16][3][7][7] and [16][16][3][3] (NOT the pack)
+ *   d_scale0, d_scale1  [16] fp32
+ *   d_mid, d_out        the forward's saved tensors [n][16][rows][cols] of `dtype` (is_stem with d_mid given)
+ *   d_grad_out, grad_out_dtype, grad_image_stride   dY; stride >= 16 P
+ *   d_grad_next, channels_next, d_weight_next, d_scale_next   source (b); channels_next % 32 == 0, in [32, 128]
+ *   d_grad_weight0 .. d_grad_shift1   fp32: [16][3][7][7], [16], [16], [16][16][3][3], [16], [16]
+ *   d_grad_pre1, d_grad_pre0   gh1 and gh0, [n][16][rows][cols] of `dtype`; without them they live in the scratch
+ *   d_scratch           16-byte aligned, scratch_bytes >= is_stem_backward_scratch_bytes(...)
+ *   reserved            0 */
+#ifndef IS_STEM_BACKWARD_BAND /* (an experiment build may define another; the product's value is this one) */
+#define IS_STEM_BACKWARD_BAND 64
+#endif
+#define IS_STEM_BACKWARD_SEGMENT 64
+#define IS_STEM_BACKWARD_TILE_ROWS 16
+#define IS_STEM_BACKWARD_TILE_COLS 64
+typedef struct is_stem_backward_args {
+    const void* d_image;
+    int n_images, rows, cols;
+    const void* d_lut;
+    int dtype; /* IS_HEAD_F16 | IS_HEAD_BF16 */
+    const float* d_w0;
+    const float* d_w1;
+    const float* d_scale0;
+    const float* d_scale1;
+    const void* d_mid;
+    const void* d_out;
+    const void* d_grad_out;
+    int grad_out_dtype;
+    long long grad_image_stride;
+    const void* d_grad_next; /* source (b), or NULL */
+    int channels_next;       /* 0 with source (a) */
+    const float* d_weight_next;
+    const float* d_scale_next;
+    float* d_grad_weight0;
+    float* d_grad_scale0;
+    float* d_grad_shift0;
+    float* d_grad_weight1;
+    float* d_grad_scale1;
+    float* d_grad_shift1;
+    void* d_grad_pre1;
+    void* d_grad_pre0;
+    void* d_scratch;
+    size_t scratch_bytes;
+    int reserved[4]; /* 0 */
+} is_stem_backward_args;
+
+/* Bytes of d_scratch for a call of that shape (0 for a shape the call refuses): gh1 and gh0, the transposed pack, the
+ * dshift tile sums, Gsum in binary64 and the chunks' partials; with channels_next != 0 (source (b)) also g_out and that
+ * layer's pack.  channels_next = 0 is source (a). */
+size_t is_stem_backward_scratch_bytes(int n_images, int rows, int cols, int channels_next, int dtype);
+/* Up to nine launches on `stream` (with source (b) the next layer's pack and g_out; the transposed pack; gh1, dMid, gh0
+ * and the dshift tile sums; the chunk partials of G1 and G0; their two reductions; dscale and dshift per channel,
+ * twice), fewer with outputs left out; asynchronous and stream-ordered; no allocation, copy or synchronisation.
+ * IS_EINVAL, with the reason in is_last_error() and before the device is touched, for null args or required pointers;
+ * everything is_stem refuses for the fields they share; both or neither gradient source; channels_next out of range; a
+ * grad_out_dtype that is neither `dtype` nor IS_HEAD_F32; a stride below 16 * rows * cols; misaligned pointers; output bytes that overlap
+ * an input's or another output's; a scratch that is too small or misaligned; no output asked for; and, last, a non-zero
+ * reserved field. */
+int is_stem_backward(const is_stem_backward_args* args, void* stream);
+/* IS_STEM_BACKWARD_BAND, IS_STEM_BACKWARD_SEGMENT, IS_STEM_BACKWARD_TILE_ROWS and IS_STEM_BACKWARD_TILE_COLS of the
+ * library as it was built (which = 0 .. 3; -1 for another). */
+int is_stem_backward_constant(int which);
+
 /* ---- f9: per-instance objects and their contours (is_k_objects.hip) ------------------------------------------------
  * What the reference's consumers reduce on the host from the per-stixel output: the top-down view
  * (tools/visualization/clustering_visualization.py:563-792: per instance and column the closest stixel, connected

@@ -52,6 +52,7 @@ EXPORTS = [
     "is_stem_packed_bytes", "is_stem_pack_weights", "is_stem",
     "is_conv_bn_backward_scratch_bytes", "is_conv_bn_backward",
     "is_conv_bn_stride_backward_scratch_bytes", "is_conv_bn_stride_backward",
+    "is_stem_backward_scratch_bytes", "is_stem_backward", "is_stem_backward_constant",
 ]
 RENDER_MAX_LABELS = 64    # IS_RENDER_MAX_LABELS
 RENDER_MAX_CLASSES = 256  # IS_RENDER_MAX_CLASSES
@@ -309,6 +310,29 @@ class ConvBnStrideBackwardArgs(ctypes.Structure):
                 ("reserved", ci * 4)]
 
 
+class StemBackwardArgs(ctypes.Structure):
+    """is_stem_backward_args: zero-initialised by ctypes; device pointers as ints."""
+    vp, ci, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    _fields_ = [("d_image", vp), ("n_images", ci), ("rows", ci), ("cols", ci), ("d_lut", vp), ("dtype", ci),
+                ("d_w0", vp), ("d_w1", vp), ("d_scale0", vp), ("d_scale1", vp), ("d_mid", vp), ("d_out", vp),
+                ("d_grad_out", vp), ("grad_out_dtype", ci), ("grad_image_stride", ll), ("d_grad_next", vp),
+                ("channels_next", ci), ("d_weight_next", vp), ("d_scale_next", vp), ("d_grad_weight0", vp),
+                ("d_grad_scale0", vp), ("d_grad_shift0", vp), ("d_grad_weight1", vp), ("d_grad_scale1", vp),
+                ("d_grad_shift1", vp), ("d_grad_pre1", vp), ("d_grad_pre0", vp), ("d_scratch", vp),
+                ("scratch_bytes", ctypes.c_size_t), ("reserved", ci * 4)]
+
+
+# IS_STEM_BACKWARD_BAND, _SEGMENT, _TILE_ROWS and _TILE_COLS, read from the library on first use (__getattr__ below)
+_STEM_BACKWARD_CONSTANTS = {"STEM_BACKWARD_BAND": 0, "STEM_BACKWARD_SEGMENT": 1, "STEM_BACKWARD_TILE_ROWS": 2,
+                            "STEM_BACKWARD_TILE_COLS": 3}
+
+
+def __getattr__(name):
+    if name in _STEM_BACKWARD_CONSTANTS:
+        return int(lib().is_stem_backward_constant(_STEM_BACKWARD_CONSTANTS[name]))
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 class RoadParams(ctypes.Structure):
     """is_road_params: one frame's road, the layout of Stixels::RoadParameters (16 bytes)"""
     _fields_ = [("vhor", ctypes.c_int), ("tilt", ctypes.c_float), ("height", ctypes.c_float),
@@ -427,6 +451,10 @@ def lib():
         L.is_conv_bn_stride_backward_scratch_bytes.argtypes = [ci, ci, ci, ci, ci, ci, ci, ci]
         L.is_conv_bn_stride_backward_scratch_bytes.restype = ctypes.c_size_t
         L.is_conv_bn_stride_backward.argtypes = [ctypes.POINTER(ConvBnStrideBackwardArgs), vp]
+        L.is_stem_backward_scratch_bytes.argtypes = [ci, ci, ci, ci, ci]
+        L.is_stem_backward_scratch_bytes.restype = ctypes.c_size_t
+        L.is_stem_backward.argtypes = [ctypes.POINTER(StemBackwardArgs), vp]
+        L.is_stem_backward_constant.argtypes = [ci]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
         L.is_get_device.argtypes = [ctypes.POINTER(ci)]
@@ -1790,6 +1818,137 @@ def _conv_backward(stride, features, weight, scale, out, grad_out, kernel, dilat
             d_scratch=scratch.data_ptr(), scratch_bytes=nbytes)
         entry = "is_conv_bn_backward" if stride is None else "is_conv_bn_stride_backward"
         _check(getattr(lib(), entry)(ctypes.byref(a), _current_stream(dev)), entry)
+        if g:
+            ret["guards"] = _guards(named, g, gs)
+    return ret
+
+
+def stem_backward_scratch_bytes(n_images, rows, cols, channels_next, dtype):
+    """is_stem_backward_scratch_bytes: the scratch a call of that shape needs (0: a refused shape)."""
+    return int(lib().is_stem_backward_scratch_bytes(int(n_images), int(rows), int(cols), int(channels_next), int(dtype)))
+
+
+def stem_backward_ptr(stream=0, **fields):
+    """is_stem_backward on raw device pointers (ints): fields are those of StemBackwardArgs.  Asynchronous on `stream`;
+    returns the return code and raises nothing (the tests check IS_EINVAL)."""
+    a = _with_reserved(StemBackwardArgs, fields)
+    return lib().is_stem_backward(ctypes.byref(a), ctypes.c_void_p(int(stream)))
+
+
+_STEM_BACKWARD_OUTPUTS = ("weight0", "scale0", "shift0", "weight1", "scale1", "shift1")
+
+
+def stem_backward(image, lut, w0, w1, scale0, scale1, mid, out, grad_out=None, grad_next=None, weight_next=None,
+                  scale_next=None, want_weight0=True, want_scale0=True, want_shift0=True, want_weight1=True,
+                  want_scale1=True, want_shift1=True, want_pre=False, canary=0):
+    """The backward pass of `stem` with BatchNorm frozen (is_stem_backward, instance_stixels_core.h f23), with the
+    numerics the header fixes.
+
+    image, lut  as `stem` takes them; the table's dtype is the launch's
+    w0, w1      layer0's conv.weight [16][3][7][7] and layer1's [16][16][3][3], float32: the master weights, not the pack
+    scale0, scale1   [16] float32 each: the folded BatchNorm scales the forward ran with
+    mid, out    the forward's saved tensors (stem(..., want_mid=True)), [n][16][rows][cols] of the table's dtype
+    grad_out    the gradient with respect to `out`, the table's dtype or float32; read in place when each frame's planes
+                are contiguous
+    grad_next, weight_next, scale_next   the other gradient source, in place of grad_out: the masked gradient of the
+                stride-2 3x3 layer that reads `out` (conv_bn_stride_backward's "pre" of layer2), [n][channels_next]
+                [(rows + 1) / 2][(cols + 1) / 2] of the table's dtype, with that layer's conv.weight [channels_next][16]
+                [3][3] float32 and folded scale [channels_next]
+
+    Returns a dict with the requested ones of "weight0", "scale0", "shift0", "weight1", "scale1", "shift1" (float32,
+    the parameters' shapes) and, with want_pre, "pre0" and "pre1" [n][16][rows][cols] of the table's dtype (the masked
+    gradients behind layer0's and layer1's ReLU), on the image's device, enqueued on the current torch stream; the
+    scratch is allocated here.  canary > 0: every output and the scratch get that many guard elements in front and
+    behind, and the dict has "guards": {name: (front, back, pattern)} (one synchronisation).  Every refusal is made
+    before anything is allocated on the device."""
+    import torch
+    source_b = grad_next is not None or weight_next is not None or scale_next is not None
+    if grad_out is not None and source_b:
+        raise CoreError("both gradient sources: grad_out and grad_next's arguments")
+    if grad_out is None and not source_b:
+        raise CoreError("no gradient source: grad_out and grad_next are None")
+    if source_b and (grad_next is None or weight_next is None or scale_next is None):
+        raise CoreError("grad_next, weight_next and scale_next come together")
+    if not torch.is_tensor(image) or not image.is_cuda or image.dtype != torch.uint8 or image.dim() != 4 or \
+            int(image.shape[3]) != 3:
+        raise CoreError("image must be a uint8 device tensor [n][rows][cols][3]")
+    dev = image.device
+    codes = _head_codes(halves_only=True)
+    if not torch.is_tensor(lut) or lut.device != dev or lut.dtype not in codes or tuple(lut.shape) != (3, 256):
+        raise CoreError("lut must be a float16 or bfloat16 tensor [3][256] on the image's device")
+    dtype = lut.dtype
+    n, H, W = (int(v) for v in image.shape[:3])
+    shape = (n, 16, H, W)
+    for name, t in (("mid", mid), ("out", out)):
+        if not torch.is_tensor(t) or t.device != dev or t.dtype != dtype or tuple(int(v) for v in t.shape) != shape:
+            raise CoreError(f"{name} must be a {dtype} tensor {shape} on the image's device")
+    cn = 0
+    if source_b:
+        if not torch.is_tensor(grad_next) or grad_next.device != dev or grad_next.dtype != dtype or grad_next.dim() != 4 or \
+                (int(grad_next.shape[0]), int(grad_next.shape[2]), int(grad_next.shape[3])) != (n, (H + 1) // 2, (W + 1) // 2):
+            raise CoreError(f"grad_next must be a {dtype} tensor [{n}][channels_next][{(H + 1) // 2}][{(W + 1) // 2}] on "
+                            "the image's device")
+        cn = int(grad_next.shape[1])
+        if cn % 32 or not 32 <= cn <= 128:
+            raise CoreError(f"channels_next {cn} is no multiple of 32 in [32, 128]")
+        wn = weight_next if torch.is_tensor(weight_next) else torch.from_numpy(np.ascontiguousarray(weight_next, np.float32))
+        sn = scale_next if torch.is_tensor(scale_next) else torch.tensor(np.asarray(scale_next, np.float32))
+        if tuple(wn.shape) != (cn, 16, 3, 3) or int(sn.numel()) != cn:
+            raise CoreError(f"weight_next must be [{cn}][16][3][3] and scale_next hold {cn} channels")
+    elif not torch.is_tensor(grad_out) or grad_out.device != dev or grad_out.dtype not in (dtype, torch.float32) or \
+            tuple(int(v) for v in grad_out.shape) != shape:
+        raise CoreError(f"grad_out must be a {dtype} or float32 tensor {shape} on the image's device")
+    ws = [w if torch.is_tensor(w) else torch.from_numpy(np.ascontiguousarray(w, np.float32)) for w in (w0, w1)]
+    if tuple(ws[0].shape) != (16, 3, 7, 7) or tuple(ws[1].shape) != (16, 16, 3, 3):
+        raise CoreError("w0 must be [16][3][7][7] and w1 [16][16][3][3]")
+    scales = [v if torch.is_tensor(v) else torch.tensor(np.asarray(v, np.float32)) for v in (scale0, scale1)]
+    if any(int(s.numel()) != 16 for s in scales):
+        raise CoreError("scale0 and scale1 must hold 16 channels each")
+    wants = dict(zip(_STEM_BACKWARD_OUTPUTS, (want_weight0, want_scale0, want_shift0, want_weight1, want_scale1,
+                                              want_shift1)))
+    if not (any(wants.values()) or want_pre):
+        raise CoreError("no gradient is asked for")
+    ws = [w.detach().to(device=dev, dtype=torch.float32).contiguous() for w in ws]
+    scales = [_f32_on(s, dev).reshape(-1) for s in scales]
+    x, table, m, y = image.contiguous(), lut.contiguous(), mid.detach().contiguous(), out.detach().contiguous()
+    source = {}
+    if source_b:
+        gn = grad_next.detach().contiguous()
+        wn = wn.detach().to(device=dev, dtype=torch.float32).contiguous()
+        sn = _f32_on(sn, dev).reshape(-1)
+        source = dict(d_grad_next=gn.data_ptr(), channels_next=cn, d_weight_next=wn.data_ptr(), d_scale_next=sn.data_ptr())
+    else:
+        gy, gy_stride = _frame_planes(grad_out.detach(), 16)
+        source = dict(d_grad_out=gy.data_ptr(), grad_image_stride=gy_stride,
+                      grad_out_dtype=HEAD_F32 if grad_out.dtype == torch.float32 else codes[dtype])
+    g = int(canary)
+    with torch.cuda.device(dev):
+        nbytes = _scratch_or_raise(stem_backward_scratch_bytes, dict(n_images=n, rows=H, cols=W, channels_next=cn),
+                                   dtype=codes[dtype])
+        views = {"weight0": (16, 3, 7, 7), "scale0": (16,), "shift0": (16,), "weight1": (16, 16, 3, 3), "scale1": (16,),
+                 "shift1": (16,), "pre0": shape, "pre1": shape}
+        wants["pre0"] = wants["pre1"] = bool(want_pre)
+        named, ret, ptr = {}, {}, {}
+        for name, view in views.items():
+            ptr[name] = None
+            if not wants[name]:
+                continue
+            full, t, pat = _guarded_float(int(np.prod(view)), dtype if name.startswith("pre") else torch.float32, dev, g)
+            named[name] = (full, pat)
+            ret[name] = t.view(view)
+            ptr[name] = t.data_ptr()
+        # (16 guard bytes keep the scratch 16-byte aligned; torch's allocations are)
+        gs = (g + 15) // 16 * 16
+        sfull, scratch = _guarded(nbytes, torch.uint8, dev, gs, 0xA5)
+        named["scratch"] = (sfull, np.uint8(0xA5))
+        a = StemBackwardArgs(
+            d_image=x.data_ptr(), n_images=n, rows=H, cols=W, d_lut=table.data_ptr(), dtype=codes[dtype],
+            d_w0=ws[0].data_ptr(), d_w1=ws[1].data_ptr(), d_scale0=scales[0].data_ptr(), d_scale1=scales[1].data_ptr(),
+            d_mid=m.data_ptr(), d_out=y.data_ptr(), **source, d_grad_weight0=ptr["weight0"], d_grad_scale0=ptr["scale0"],
+            d_grad_shift0=ptr["shift0"], d_grad_weight1=ptr["weight1"], d_grad_scale1=ptr["scale1"],
+            d_grad_shift1=ptr["shift1"], d_grad_pre1=ptr["pre1"], d_grad_pre0=ptr["pre0"], d_scratch=scratch.data_ptr(),
+            scratch_bytes=nbytes)
+        _check(lib().is_stem_backward(ctypes.byref(a), _current_stream(dev)), "is_stem_backward")
         if g:
             ret["guards"] = _guards(named, g, gs)
     return ret

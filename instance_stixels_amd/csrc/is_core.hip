@@ -1463,6 +1463,90 @@ int is_stem(const is_stem_args* a, void* stream) {
     return IS_OK;
 }
 
+/* ---- f23: the backward pass of the stem (is_k_stem_backward.hip).  One checker, one launcher. ---- */
+static const char* stem_backward_shape_fault(int n_images, int rows, int cols, int channels_next, int dtype) {
+    if (const char* fault = stem_dtype_fault(dtype)) return fault;
+    if (n_images < 1 || n_images > 65535) return "n_images outside [1, 65535]";
+    if (rows < 1 || rows > 32767 || cols < 1 || cols > 32767) return "rows and cols must be in [1, 32767]";
+    if (channels_next != 0 && (channels_next < 32 || channels_next > 128 || channels_next % 32))
+        return "channels_next must be a multiple of 32 in [32, 128]";
+    return nullptr;
+}
+
+size_t is_stem_backward_scratch_bytes(int n_images, int rows, int cols, int channels_next, int dtype) {
+    if (stem_backward_shape_fault(n_images, rows, cols, channels_next, dtype)) return 0;
+    return isk_stem_backward_scratch_bytes(n_images, rows, cols, channels_next);
+}
+
+int is_stem_backward_constant(int which) {
+    static const int values[4] = {IS_STEM_BACKWARD_BAND, IS_STEM_BACKWARD_SEGMENT, IS_STEM_BACKWARD_TILE_ROWS,
+                                  IS_STEM_BACKWARD_TILE_COLS};
+    return which >= 0 && which < 4 ? values[which] : -1;
+}
+
+int is_stem_backward(const is_stem_backward_args* a, void* stream) {
+    if (!a) return fail_arg("null args");
+    if (!a->d_image || !a->d_lut || !a->d_w0 || !a->d_w1 || !a->d_scale0 || !a->d_scale1 || !a->d_mid || !a->d_out)
+        return fail_arg("null d_image, d_lut, d_w0, d_w1, d_scale0, d_scale1, d_mid or d_out");
+    const bool source_b = a->d_grad_next || a->channels_next || a->d_weight_next || a->d_scale_next;
+    if (a->d_grad_out && source_b) return fail_arg("both gradient sources: d_grad_out and d_grad_next's fields");
+    if (!a->d_grad_out && !source_b) return fail_arg("no gradient source: d_grad_out is null");
+    if (source_b && (!a->d_grad_next || !a->d_weight_next || !a->d_scale_next))
+        return fail_arg("null d_grad_next, d_weight_next or d_scale_next");
+    if (source_b && !a->channels_next) return fail_arg("channels_next must be a multiple of 32 in [32, 128]");
+    if (const char* fault = stem_backward_shape_fault(a->n_images, a->rows, a->cols, a->channels_next, a->dtype))
+        return fail_arg(fault);
+    if (!source_b && a->grad_out_dtype != a->dtype && a->grad_out_dtype != IS_HEAD_F32)
+        return fail_arg("grad_out_dtype is neither the stem's dtype nor IS_HEAD_F32");
+    const uint64_t P = (uint64_t)a->rows * a->cols, planes = 16 * P;
+    const uint64_t P_next = (uint64_t)((a->rows + 1) / 2) * ((a->cols + 1) / 2);
+    if (!source_b && a->grad_image_stride < (long long)planes) return fail_arg("grad_image_stride below the planes of a frame");
+    const uintptr_t gy_el = a->grad_out_dtype == IS_HEAD_F32 ? 4 : 2;
+    if (misaligned(2, a->d_lut, a->d_mid, a->d_out, a->d_grad_pre1, a->d_grad_pre0, a->d_grad_next))
+        return fail_arg("d_lut, d_mid, d_out, d_grad_pre1, d_grad_pre0 and d_grad_next must be aligned to their element");
+    if (!source_b && misaligned(gy_el, a->d_grad_out)) return fail_arg("d_grad_out must be aligned to its element");
+    if (misaligned(4, a->d_w0, a->d_w1, a->d_scale0, a->d_scale1, a->d_weight_next, a->d_scale_next))
+        return fail_arg("d_w0, d_w1, d_scale0, d_scale1, d_weight_next and d_scale_next must be 4-byte aligned");
+    if (misaligned(4, a->d_grad_weight0, a->d_grad_scale0, a->d_grad_shift0, a->d_grad_weight1, a->d_grad_scale1, a->d_grad_shift1))
+        return fail_arg("the fp32 gradients must be 4-byte aligned");
+    const size_t need = isk_stem_backward_scratch_bytes(a->n_images, a->rows, a->cols, a->channels_next);
+    if (const char* fault = scratch_fault(a->d_scratch, a->scratch_bytes, need)) return fail_arg(fault);
+    /* every output's bytes against every input's and every other output's, each at its own size (at most 2^16 * 2^30
+     * pixels of 64 bytes: no overflow) */
+    struct span { const void* p; uint64_t bytes; };
+    const uint64_t n = a->n_images;
+    const span inputs[] = {
+        {a->d_image, n * P * 3},      {a->d_lut, 3 * 256 * 2},  {a->d_w0, 16 * 3 * 49 * 4}, {a->d_w1, 16 * 16 * 9 * 4},
+        {a->d_scale0, 16 * 4},        {a->d_scale1, 16 * 4},    {a->d_mid, n * planes * 2}, {a->d_out, n * planes * 2},
+        {a->d_grad_out, source_b ? 0 : ((n - 1) * (uint64_t)a->grad_image_stride + planes) * gy_el},
+        {a->d_grad_next, n * a->channels_next * P_next * 2},
+        {a->d_weight_next, (uint64_t)a->channels_next * 16 * 9 * 4},
+        {a->d_scale_next, (uint64_t)a->channels_next * 4},
+    };
+    const span outputs[] = {
+        {a->d_grad_weight0, 16 * 3 * 49 * 4}, {a->d_grad_scale0, 16 * 4}, {a->d_grad_shift0, 16 * 4},
+        {a->d_grad_weight1, 16 * 16 * 9 * 4}, {a->d_grad_scale1, 16 * 4}, {a->d_grad_shift1, 16 * 4},
+        {a->d_grad_pre1, n * planes * 2},     {a->d_grad_pre0, n * planes * 2}, {a->d_scratch, need},
+    };
+    auto overlap = [](const span& u, const span& v) {
+        const uint64_t u0 = (uint64_t)(uintptr_t)u.p, v0 = (uint64_t)(uintptr_t)v.p;
+        return u.p && v.p && u0 < v0 + v.bytes && v0 < u0 + u.bytes;
+    };
+    for (size_t o = 0; o < sizeof(outputs) / sizeof(outputs[0]); ++o) {
+        for (const span& in : inputs)
+            if (overlap(outputs[o], in)) return fail_arg("an output's bytes (or the scratch's) overlap an input's");
+        for (size_t q = o + 1; q < sizeof(outputs) / sizeof(outputs[0]); ++q)
+            if (overlap(outputs[o], outputs[q])) return fail_arg("two outputs' bytes (or an output's and the scratch's) overlap");
+    }
+    if (!a->d_grad_weight0 && !a->d_grad_scale0 && !a->d_grad_shift0 && !a->d_grad_weight1 && !a->d_grad_scale1 &&
+        !a->d_grad_shift1 && !a->d_grad_pre1 && !a->d_grad_pre0)
+        return fail_arg("no output is asked for");
+    /* (last: a call that is refused for this alone has passed every check above) */
+    if (const char* fault = reserved_fault(a->reserved)) return fail_arg(fault);
+    HIP_TRY(isk_launch_stem_backward(a, (hipStream_t)stream));
+    return IS_OK;
+}
+
 /* ---- f9: per-instance objects and contours (is_k_objects.hip) ---- */
 int is_instance_objects(const is_instance_objects_args* a, void* stream) {
     if (!a) return fail_arg("null args");

@@ -471,3 +471,23 @@ extern "C" hipError_t isk_launch_conv_bn_backward(const is_conv_bn_stride_backwa
     }
     return hipGetLastError();
 }
+
+/* f23 (is_k_stem_backward.hip) runs the two reductions above on the stem's partials: the same kernels, the same
+ * instantiations. */
+extern "C" void isk_launch_conv_bwd_reduce(const float* part, int chunks, int Cin, int Cout, int taps, const float* scale,
+                                           float* dw, double* gsum, hipStream_t stream) {
+    const int total = taps * Cout * Cin;
+    hipLaunchKernelGGL(k_conv_bwd_reduce, dim3((total + 255) / 256), dim3(256), 0, stream, part, chunks, Cin, Cout, taps,
+                       scale, dw, gsum);
+}
+
+extern "C" void isk_launch_conv_bwd_channel(int dtype, const double* gsum, const float* weight, const double* shift_part,
+                                            int n_images, int pblocks, int Cin, int Cout, int taps, float* dscale,
+                                            float* dshift, hipStream_t stream) {
+    if (dtype == IS_HEAD_F16)
+        hipLaunchKernelGGL(k_conv_bwd_channel<IS_HEAD_F16>, dim3(Cout), dim3(256), 0, stream, gsum, weight, shift_part,
+                           n_images, pblocks, Cin, Cout, taps, dscale, dshift);
+    else
+        hipLaunchKernelGGL(k_conv_bwd_channel<IS_HEAD_BF16>, dim3(Cout), dim3(256), 0, stream, gsum, weight, shift_part,
+                           n_images, pblocks, Cin, Cout, taps, dscale, dshift);
+}

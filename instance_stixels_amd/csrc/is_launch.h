@@ -259,6 +259,13 @@ size_t isk_conv_backward_scratch_bytes(int n_images, int channels_in, int channe
                                        int stride);
 hipError_t isk_launch_conv_bn_backward(const is_conv_bn_stride_backward_args* a, hipStream_t stream);
 
+/* ... and its two reductions on another launcher's partials (f23): part[(chunk * taps + tap) * Cout * Cin + co * Cin + ci],
+ * shift_part[(image * Cout + co) * pblocks + block] */
+void isk_launch_conv_bwd_reduce(const float* part, int chunks, int Cin, int Cout, int taps, const float* scale, float* dw,
+                                double* gsum, hipStream_t stream);
+void isk_launch_conv_bwd_channel(int dtype, const double* gsum, const float* weight, const double* shift_part, int n_images,
+                                 int pblocks, int Cin, int Cout, int taps, float* dscale, float* dshift, hipStream_t stream);
+
 /* is_k_conv_backward_stride.hip: the two stride-2 kernels of the launcher above.  gh, part: the launcher's sections. */
 void isk_launch_conv_bwd_data_s2(const is_conv_bn_stride_backward_args* a, const void* gh, const void* packed,
                                  hipStream_t stream);
@@ -269,6 +276,10 @@ long long isk_conv_bwd_weight_s2_grid(int n_images, int channels_in, int channel
 size_t isk_stem_packed_bytes(void);
 hipError_t isk_launch_stem_pack(const float* d_w0, const float* d_w1, int dtype, void* d_packed, hipStream_t stream);
 hipError_t isk_launch_stem(const is_stem_args* a, hipStream_t stream);
+
+/* is_k_stem_backward.hip */
+size_t isk_stem_backward_scratch_bytes(int n_images, int rows, int cols, int channels_next);
+hipError_t isk_launch_stem_backward(const is_stem_backward_args* a, hipStream_t stream);
 
 /* is_k_head_backward.hip */
 size_t isk_head_backward_scratch_bytes(int n_images, int K, int Hs, int Ws, int channels);

@@ -509,3 +509,137 @@ class DrnLayers(torch.nn.Module):
         for layer in self.layers:
             x = layer(x)
         return x
+
+
+# ---- f23: the stem with a backward pass on the device ----
+
+class _StemFunction(torch.autograd.Function):
+    """Forward: the pack of the current weights and one launch of core.stem with mid kept.  Backward: one call of
+    core.stem_backward that asks for the gradients autograd needs and no others."""
+
+    @staticmethod
+    def forward(ctx, image, lut, w0, scale0, shift0, w1, scale1, shift1):
+        packed = core.stem_pack_weights(w0.detach(), w1.detach(), lut.dtype, device=image.device)
+        out, mid = core.stem(image, lut, packed, scale0.detach(), shift0.detach(), scale1.detach(), shift1.detach(),
+                             want_mid=True)
+        ctx.save_for_backward(image, lut, w0, scale0, w1, scale1, mid, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        image, lut, w0, scale0, w1, scale1, mid, out = ctx.saved_tensors
+        need = ctx.needs_input_grad[2:]
+        if not any(need):
+            return (None,) * 8
+        g = core.stem_backward(image, lut, w0, w1, scale0, scale1, mid, out, grad_out=grad_out, want_weight0=need[0],
+                               want_scale0=need[1], want_shift0=need[2], want_weight1=need[3], want_scale1=need[4],
+                               want_shift1=need[5])
+        return (None, None, g.get("weight0"), g.get("scale0"), g.get("shift0"), g.get("weight1"), g.get("scale1"),
+                g.get("shift1"))
+
+
+class Stem(torch.nn.Module):
+    """layer0 and layer1 of the reference's drn_d_22 behind the image's table, as cnn.DrnStem checks them, trainable:
+    `weight0` and `weight1` are the fp32 master weights, bn0 and bn1 the affine pairs of the two BatchNorms, frozen at
+    their running statistics.  forward(image) takes the uint8 image [n][rows][cols][3] on the device and returns
+    layer1's output [n][16][rows][cols] in `dtype`, the bytes of cnn.DrnStem; it is ONE autograd node whose backward is
+    one call of is_stem_backward (instance_stixels_core.h f23) on the gradient its consumer gives.  There is no
+    gradient for the image or the table.  Everything is checked before anything is packed."""
+
+    def __init__(self, layer0, layer1, mean, std, dtype=torch.bfloat16):
+        super().__init__()
+        from . import cnn
+        conv0, bn0 = cnn._stem_conv(layer0, "layer0", 3, 7, 3, "")
+        conv1, bn1 = cnn._stem_conv(layer1, "layer1", 16, 3, 1,
+                                    " (layers[0] > 1 repeats the three: only layers[0] == 1 is covered)")
+        _frozen_bn(bn0, "layer0's bn")
+        _frozen_bn(bn1, "layer1's bn")
+        self.dtype = dtype
+        self.register_buffer("lut", cnn.input_table(mean, std, dtype))
+        self.weight0 = torch.nn.Parameter(conv0.weight.detach().clone().float())
+        self.weight1 = torch.nn.Parameter(conv1.weight.detach().clone().float())
+        self.bn0, self.bn1 = _FrozenBatchNorm(bn0), _FrozenBatchNorm(bn1)
+
+    def forward(self, image):
+        if not torch.is_tensor(image) or not image.is_cuda or image.dtype != torch.uint8 or image.dim() != 4 or \
+                int(image.shape[3]) != 3:
+            raise core.CoreError("image must be a uint8 device tensor [n][rows][cols][3]")
+        scale0, shift0 = self.bn0.fold()
+        scale1, shift1 = self.bn1.fold()
+        return _StemFunction.apply(image, self.lut, self.weight0, scale0, shift0, self.weight1, scale1, shift1)
+
+
+class _StemLayer2Function(torch.autograd.Function):
+    """The stem and layer2 as ONE autograd node.  Forward: core.stem with mid kept, then layer2's launch of
+    core.conv_bn_stride.  Backward: core.conv_bn_stride_backward for layer2's parameters and its masked gradient, then
+    one core.stem_backward that takes that masked gradient as its source: the gradient with respect to layer1's output
+    is formed inside the library, and no torch kernel runs between the two calls."""
+
+    @staticmethod
+    def forward(ctx, image, lut, w0, scale0, shift0, w1, scale1, shift1, w2, scale2, shift2):
+        packed = core.stem_pack_weights(w0.detach(), w1.detach(), lut.dtype, device=image.device)
+        out1, mid = core.stem(image, lut, packed, scale0.detach(), shift0.detach(), scale1.detach(), shift1.detach(),
+                              want_mid=True)
+        packed2 = core.conv_pack_weights(w2.detach(), lut.dtype)
+        out2 = core.conv_bn_stride(out1, packed2, scale2.detach(), shift2.detach(), 3, 2, 1, relu=True)
+        ctx.save_for_backward(image, lut, w0, scale0, w1, scale1, mid, out1, w2, scale2, out2)
+        return out2
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        image, lut, w0, scale0, w1, scale1, mid, out1, w2, scale2, out2 = ctx.saved_tensors
+        need = ctx.needs_input_grad[2:]
+        if not any(need):
+            return (None,) * 11
+        stem_needs = any(need[:6])
+        g2 = core.conv_bn_stride_backward(out1, w2, scale2, out2, grad_out, 3, 2, want_features=False, want_weight=need[6],
+                                          want_scale=need[7], want_shift=need[8], want_pre=stem_needs)
+        g = {}
+        if stem_needs:
+            g = core.stem_backward(image, lut, w0, w1, scale0, scale1, mid, out1, grad_next=g2["pre"], weight_next=w2,
+                                   scale_next=scale2, want_weight0=need[0], want_scale0=need[1], want_shift0=need[2],
+                                   want_weight1=need[3], want_scale1=need[4], want_shift1=need[5])
+        return (None, None, g.get("weight0"), g.get("scale0"), g.get("shift0"), g.get("weight1"), g.get("scale1"),
+                g.get("shift1"), g2.get("weight"), g2.get("scale"), g2.get("shift"))
+
+
+class Drn(torch.nn.Module):
+    """The whole base of the reference's drn_d_22, trainable: the uint8 image [n][rows][cols][3] on the device in,
+    layer8's output at 1/8 resolution in `dtype` out, which feeds SegmentationHead.  `stem` is a Stem (layer0, layer1)
+    and `layers` a DrnLayers (layer2 .. layer8), whose checks and parameters they are; the stem and layer2 run as one
+    autograd node (_StemLayer2Function), layer3 .. layer8 are DrnLayers' modules as they are.  Every BatchNorm is
+    frozen at its running statistics.  layer2 must be the reference's Conv2d(16, channels, 3, stride 2, padding 1) with
+    channels a multiple of 32 in [32, 128]."""
+
+    def __init__(self, layer0, layer1, layer2, layer3, layer4, layer5, layer6, layer7, layer8, mean, std,
+                 dtype=torch.bfloat16):
+        super().__init__()
+        self.stem = Stem(layer0, layer1, mean, std, dtype)
+        self.layers = DrnLayers(layer2, layer3, layer4, layer5, layer6, layer7, layer8)
+        first = self.layers.layers[0]
+        cn = int(first.weight.shape[0]) if isinstance(first, StridedConvBnReLU) else 0
+        if cn == 0 or int(first.weight.shape[1]) != 16 or first.stride != 2 or first.dilation != 1 or not first.relu:
+            raise core.CoreError("layer2 must be nn.Sequential(Conv2d(16, channels, 3, stride=2, padding=1, bias=False), "
+                                 "BatchNorm2d, ReLU)")
+        if cn % 32 or not 32 <= cn <= 128:
+            raise core.CoreError(f"layer2 has {cn} channels: the stem's backward takes a multiple of 32 in [32, 128]")
+        self.dtype = dtype
+
+    @classmethod
+    def from_base(cls, base, mean, std, dtype=torch.bfloat16):
+        """base: the reference's model.base, the nn.Sequential of the nine children layer0 .. layer8."""
+        layers = list(base)
+        if len(layers) != 9:
+            raise core.CoreError(f"base has {len(layers)} children, not the nine layer0 .. layer8")
+        return cls(*layers, mean, std, dtype=dtype)
+
+    def forward(self, image):
+        if not torch.is_tensor(image) or not image.is_cuda or image.dtype != torch.uint8 or image.dim() != 4 or \
+                int(image.shape[3]) != 3:
+            raise core.CoreError("image must be a uint8 device tensor [n][rows][cols][3]")
+        stem, first = self.stem, self.layers.layers[0]
+        x = _StemLayer2Function.apply(image, stem.lut, stem.weight0, *stem.bn0.fold(), stem.weight1, *stem.bn1.fold(),
+                                      first.weight, *first.bn.fold())
+        for layer in self.layers.layers[1:]:
+            x = layer(x)
+        return x

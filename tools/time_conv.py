@@ -37,6 +37,10 @@ comma-separated), for fp16 and bf16 features [n][.][rows8][cols8] with half outp
   weight and the BatchNorm affine pair, the forward graph built outside the timing.  `scratch_mb` is the call's scratch.
   The MFMA floor counts dX and dW: 2 x the forward's FLOP.  Both arms allocate their outputs inside the timing (torch's
   caching allocator; the library's arm also its scratch), as a training step does.  --backward-cases picks shapes.
+- stem_backward (not in the default --parts): core.stem_backward (f23) on --stem-n frames of [--rows][--cols][3] bytes
+  with every gradient, from dY (`new`) and from layer2's masked gradient at 32 channels (`new_next`), against
+  torch.autograd.grad of the same three layers (and, for `_next`, of layer2's convolution on top) in the same half
+  dtype.  `compulsory_gb` is 3 + 32 + 32 + 32 bytes per pixel: the image, dY, out and mid once each.
 - backward_stride (not in the default --parts): core.conv_bn_stride_backward (f22) at the five stride-2 launches of
   drn_d_22 on layer1's output [--backward-n][16][--rows][--cols] -- 3x3 at 16 -> 32 (layer2, no dX: it is refused at 16
   channels), 32 -> 64 and 64 -> 128, 1x1 at 32 -> 64 and 64 -> 128, each at its layer's resolution -- with every gradient
@@ -47,7 +51,7 @@ comma-separated), for fp16 and bf16 features [n][.][rows8][cols8] with half outp
 convolution of a shape takes 30 - 160 s: run the dtypes, and if need be the parts, in separate commands.
 
     python tools/time_conv.py [--n 64 --C 512 --rows8 128 --cols8 256 --iters 20 --mhz 2400 --cus 256 --dtypes fp16,bf16
-                               --parts tail,residual,1x1,layers[,strided][,stem][,backward][,backward_stride] --rows 1024 --cols 2048 --strided-n 64
+                               --parts tail,residual,1x1,layers[,strided][,stem][,backward][,backward_stride][,stem_backward] --rows 1024 --cols 2048 --strided-n 64
                                --stem-n 64
                                --no-torch]
 """
@@ -79,7 +83,7 @@ def main():
     ap.add_argument("--dp-n", type=int, default=0, help="0: the whole batch (a shape the library is already tuned for)")
     ap.add_argument("--dtypes", default="fp16,bf16", help="comma-separated subset of fp16,bf16")
     ap.add_argument("--parts", default="tail,residual,1x1,layers",
-                    help="comma-separated subset of tail,residual,1x1,layers,strided,stem,backward,backward_stride")
+                    help="comma-separated subset of tail,residual,1x1,layers,strided,stem,backward,backward_stride,stem_backward")
     ap.add_argument("--backward-stride-cases", default="0,1,2,3,4", help="which of the five launches of `backward_stride`")
     ap.add_argument("--hbm-gbs", type=float, default=6300.0, help="the memory rate of the compulsory-traffic floor")
     ap.add_argument("--backward-n", type=int, default=4, help="frames per call of the `backward` part")
@@ -490,6 +494,64 @@ def main():
             out[name + "_stem"] = row
             note(name, "stem", json.dumps(row))
             del image, arms
+            torch.cuda.empty_cache()
+        if "stem_backward" in parts:
+            m, H1, W1, cn = a.stem_n or n, a.rows, a.cols, 32
+            mean, std = (0.290101, 0.328081, 0.286964), (0.182954, 0.186566, 0.184475)
+            image = torch.randint(0, 256, (m, H1, W1, 3), device=dev, dtype=torch.uint8)
+            w0, w1, w2 = weight(16, 3, 7), weight(16, 16, 3), weight(cn, 16, 3)
+            stats0, stats1, stats2 = bn_stats(16), bn_stats(16), bn_stats(cn)
+            lut = cnn.input_table(mean, std, dtype).to(dev)
+            folds = fold(*stats0) + fold(*stats1)
+            scale2 = fold(*stats2)[0]
+            y, mid = core.stem(image, lut, core.stem_pack_weights(w0, w1, dtype), *folds, want_mid=True)
+            gy = torch.randn((m, 16, H1, W1), device=dev).to(dtype)
+            Ho, Wo = (H1 + 1) // 2, (W1 + 1) // 2
+            gnext = (torch.randn((m, cn, Ho, Wo), device=dev) * (torch.rand((m, cn, Ho, Wo), device=dev) > 0.5)).to(dtype)
+            call = lambda **src: core.stem_backward(image, lut, w0, w1, folds[0], folds[2], mid, y, **src)
+            arms = {"new": lambda: call(grad_out=gy),
+                    "new_next": lambda: call(grad_next=gnext, weight_next=w2, scale_next=scale2)}
+            if not a.no_torch:
+                graphs = {}
+                mean_t, std_t = (torch.tensor(v, device=dev).view(1, 3, 1, 1) for v in (mean, std))
+                x = ((image.permute(0, 3, 1, 2).float() / 255 - mean_t) / std_t).to(dtype)
+                for arm, cl in (("torch_contiguous", False), ("torch_channels_last", True)):
+                    xt, ws = x.clone(), [w0.to(dtype), w1.to(dtype), w2.to(dtype)]
+                    if cl:
+                        xt, ws = channels_last(xt)[0], channels_last(*ws)
+                    ws = [w.requires_grad_(True) for w in ws]
+                    bns = [[t.to(dtype) for t in st] for st in (stats0, stats1, stats2)]
+                    for bn in bns[:2]:
+                        bn[2].requires_grad_(True), bn[3].requires_grad_(True)
+                    y1 = torch_conv_bn(torch_conv_bn(xt, ws[0], 1, bns[0], True), ws[1], 1, bns[1], True)
+                    y2 = torch_conv_bn(y1, ws[2], 1, bns[2], False, stride=2)         # gnext is already masked
+                    wrt = (ws[0], bns[0][2], bns[0][3], ws[1], bns[1][2], bns[1][3])
+                    graphs[arm] = (y1, y2, wrt, channels_last(gy)[0] if cl else gy, channels_last(gnext)[0] if cl else gnext)
+                    arms[arm] = lambda arm=arm: torch.autograd.grad(graphs[arm][0], graphs[arm][2], graphs[arm][3],
+                                                                    retain_graph=True)
+                    arms[arm + "_next"] = lambda arm=arm: torch.autograd.grad(graphs[arm][1], graphs[arm][2], graphs[arm][4],
+                                                                              retain_graph=True)
+            row, med = measure(name + " stem_backward", arms)
+            pixels = m * H1 * W1
+            # the compulsory bytes once each: the image, dY (or layer2's masked gradient), out and mid
+            gb, gb_next = pixels * (3 + 32 + 32 + 32) / 1e9, (pixels * (3 + 32 + 32) + m * cn * Ho * Wo * 2) / 1e9
+            row.update(frames=m, shape_in=[m, H1, W1, 3], band=core.STEM_BACKWARD_BAND, segment=core.STEM_BACKWARD_SEGMENT,
+                       compulsory_gb=round(gb, 3), hbm_floor_ms=round(gb / a.hbm_gbs * 1e3, 3),
+                       new_share_of_hbm_floor=round(gb / a.hbm_gbs * 1e3 / med["new"], 3),
+                       next_compulsory_gb=round(gb_next, 3), next_hbm_floor_ms=round(gb_next / a.hbm_gbs * 1e3, 3),
+                       next_share_of_hbm_floor=round(gb_next / a.hbm_gbs * 1e3 / med["new_next"], 3),
+                       scratch_mb=round(core.stem_backward_scratch_bytes(
+                           m, H1, W1, 0, core.HEAD_F16 if dtype == torch.float16 else core.HEAD_BF16) / 2 ** 20, 1))
+            against_torch(row, med)
+            if not a.no_torch:
+                best = min(med["torch_contiguous_next"], med["torch_channels_last_next"])
+                row.update(next_torch_best_ms=round(best, 3), next_over_torch_best=round(med["new_next"] / best, 3),
+                           next_faster=bool(med["new_next"] < best))
+            out[name + "_stem_backward"] = row
+            note(name, "stem_backward", json.dumps(row))
+            del image, arms, y, mid, gy, gnext
+            if not a.no_torch:
+                del graphs
             torch.cuda.empty_cache()
     print(json.dumps(out), flush=True)
 
