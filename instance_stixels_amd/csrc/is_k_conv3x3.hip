@@ -50,7 +50,7 @@
  *             TAPS = 9: the input tile behind 8 x 32 outputs is 17 x 65 pixels at (2 y0 - 1, 2 x0 - 1), 35.4 KB beside
  *             the 18 KB of weights.  It is stored as two column-parity planes per row, [row][33 even columns | 32 odd
  *             columns]: tap kx = 0 reads the even plane at r, kx = 1 the odd plane at r, kx = 2 the even plane at
- *             r + 1, so that the 32 lanes of every tap still read 32 CONSECUTIVE entries and c3_slot's swizzle spreads
+ *             r + 1, so that the 32 lanes of every tap still read 32 CONSECUTIVE entries and hm_slot's swizzle spreads
  *             a ds_read_b128 group over all 16 slots of a bank row exactly as at stride 1.
  *             TAPS = 1: only the sampled pixels are staged, the 8 x 32 tile of in[2y][2x]; C1_STAGE as at stride 1.
  *             No address outside the features is formed for a load: a pixel outside the image loads the clamped one.
@@ -70,7 +70,7 @@
  * Then 9 taps x 4 MFMAs per wave.  Consecutive workgroups of one XCD (every eighth of the grid) take the channel groups
  * of ONE pixel tile, so the tile's features come from memory once and from L2 for the other channel groups.
  */
-#include "is_launch.h"
+#include "is_half_mfma.h"
 
 #define C3_COLS 32
 #define C3_NT 2                          /* rows of a wave */
@@ -92,36 +92,6 @@ static_assert((C3_MT * C3_ABLOCK(9) + 2 * C3S2_ROWS * C3S2_COLS) * 16 <= 65536 &
 static_assert(C3S2_EVEN + C3_COLS == C3S2_COLS, "the two column-parity planes of a row are the row");
 static_assert(C1_STAGE * (C3_MT * C3_ABLOCK(1) + 2 * C3_ROWS * C3_COLS) * 16 <= 65536, "and so does a stage of the 1x1 form");
 
-typedef float c3_acc __attribute__((ext_vector_type(16)));
-typedef _Float16 c3_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 c3_bf16x8 __attribute__((ext_vector_type(8)));
-
-/* fp32 -> half, round to nearest even, as 16 bits */
-template <int DT> __device__ __forceinline__ uint16_t c3_round(float v);
-template <> __device__ __forceinline__ uint16_t c3_round<IS_HEAD_F16>(float v) {
-    return __builtin_bit_cast(uint16_t, (_Float16)v);
-}
-template <> __device__ __forceinline__ uint16_t c3_round<IS_HEAD_BF16>(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
-template <int DT> __device__ __forceinline__ c3_acc c3_mfma(uint4 a, uint4 b, c3_acc c);
-template <> __device__ __forceinline__ c3_acc c3_mfma<IS_HEAD_F16>(uint4 a, uint4 b, c3_acc c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(c3_f16x8, a), __builtin_bit_cast(c3_f16x8, b), c, 0, 0, 0);
-}
-template <> __device__ __forceinline__ c3_acc c3_mfma<IS_HEAD_BF16>(uint4 a, uint4 b, c3_acc c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(c3_bf16x8, a), __builtin_bit_cast(c3_bf16x8, b), c, 0, 0, 0);
-}
-
-/* half -> fp32, exact */
-template <int DT> __device__ __forceinline__ float c3_widen(uint16_t u);
-template <> __device__ __forceinline__ float c3_widen<IS_HEAD_F16>(uint16_t u) { return (float)__builtin_bit_cast(_Float16, u); }
-template <> __device__ __forceinline__ float c3_widen<IS_HEAD_BF16>(uint16_t u) { return __uint_as_float((uint32_t)u << 16); }
-
-/* the 16-byte slot of k half `h` of halo pixel `p` */
-__device__ __forceinline__ int c3_slot(int p, int h) { return 2 * p + (h ^ ((p >> 3) & 1)); }
-
 /* packed[((tile * chunks + chunk) * taps + tap) * 512 + h * 256 + r * 8 + j] = round(w[32 tile + r][16 chunk + 8 h + j][tap]) */
 template <int DT>
 __global__ __launch_bounds__(256) void k_conv3x3_pack(const float* __restrict__ weight, uint16_t* __restrict__ packed,
@@ -131,7 +101,7 @@ __global__ __launch_bounds__(256) void k_conv3x3_pack(const float* __restrict__ 
     const int j = e & 7, r = (e >> 3) & 31, h = (e >> 8) & 1, tap = (e >> 9) % taps, blk = (e >> 9) / taps;
     const int chunks = Cin / C3_KC, chunk = blk % chunks, tile = blk / chunks;
     const int co = 32 * tile + r, ci = C3_KC * chunk + 8 * h + j;
-    packed[e] = c3_round<DT>(weight[((size_t)co * Cin + ci) * taps + tap]);
+    packed[e] = hm_round<DT>(weight[((size_t)co * Cin + ci) * taps + tap]);
 }
 
 /* H, W: the INPUT's extents (STRIDE = 1: the output's as well). */
@@ -157,12 +127,12 @@ __global__ __launch_bounds__(256) void k_conv3x3(const uint16_t* __restrict__ fe
     const int HW = PARITY ? C3S2_COLS : C3_COLS + 2 * d, pixels = (PARITY ? C3S2_ROWS : C3_ROWS + 2 * d) * HW;
     const int chunks = Cin / C3_KC;
     uint4* const ldsA = c3_lds;                          /* [C3_MT][chunk of the stage][tap][k half][channel] */
-    uint4* const ldsB = c3_lds + C3_MT * STAGE * ABLOCK; /* [chunk of the stage] c3_slot(pixel, k half) */
+    uint4* const ldsB = c3_lds + C3_MT * STAGE * ABLOCK; /* [chunk of the stage] hm_slot(pixel, k half) */
     const size_t plane = (size_t)H * W;
     const uint16_t* const xn = features + (size_t)n * Cin * plane;
     const int last_tile = Cout / 32 - 1;
 
-    c3_acc acc[C3_MT][C3_NT];
+    hm_acc16 acc[C3_MT][C3_NT];
 #pragma unroll
     for (int m = 0; m < C3_MT; ++m)
 #pragma unroll
@@ -197,7 +167,7 @@ __global__ __launch_bounds__(256) void k_conv3x3(const uint16_t* __restrict__ fe
             for (int j = 0; j < 8; ++j) v[j] = src[j * plane];
             uint4 q;
             q.x = v[0] | (v[1] << 16), q.y = v[2] | (v[3] << 16), q.z = v[4] | (v[5] << 16), q.w = v[6] | (v[7] << 16);
-            ldsB[cc * 2 * pixels + c3_slot(lp, h)] = inside ? q : make_uint4(0, 0, 0, 0);
+            ldsB[cc * 2 * pixels + hm_slot(lp, h)] = inside ? q : make_uint4(0, 0, 0, 0);
         }
         __syncthreads();
         for (int cc = 0; cc < nc; ++cc) {
@@ -212,18 +182,18 @@ __global__ __launch_bounds__(256) void k_conv3x3(const uint16_t* __restrict__ fe
                     /* PARITY: input row 2 (row of the tile) + ky; column 2 r + kx is entry r + kx / 2 of plane kx & 1 */
                     const int bp = PARITY ? (2 * (C3_NT * wave + t) + ky) * C3S2_COLS + (kx & 1) * C3S2_EVEN + (kx >> 1) + r
                                           : (C3_NT * wave + t + ky * d) * HW + r + kx * d;
-                    b[t] = ldsB[cc * 2 * pixels + c3_slot(bp, half)];
+                    b[t] = ldsB[cc * 2 * pixels + hm_slot(bp, half)];
                 }
 #pragma unroll
                 for (int m = 0; m < C3_MT; ++m)
 #pragma unroll
-                    for (int t = 0; t < C3_NT; ++t) acc[m][t] = c3_mfma<DT>(a[m], b[t], acc[m][t]);
+                    for (int t = 0; t < C3_NT; ++t) acc[m][t] = hm_mfma<DT>(a[m], b[t], acc[m][t]);
             }
         }
     }
 
-    /* epilogue: register i of a lane is channel (i & 3) + 8 (i >> 2) + 4 half of its tile (the C/D map of the 32x32
-     * shapes) at the lane's pixel: 32 lanes store 32 consecutive elements of a plane */
+    /* epilogue: register i of a lane is channel hm_cd_row(i, half) of its tile at the lane's pixel: 32 lanes store 32
+     * consecutive elements of a plane */
     const int x = x0 + r;
 #pragma unroll
     for (int m = 0; m < C3_MT; ++m) {
@@ -231,20 +201,20 @@ __global__ __launch_bounds__(256) void k_conv3x3(const uint16_t* __restrict__ fe
         if (tile_m > last_tile) break;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int co = 32 * tile_m + (i & 3) + 8 * (i >> 2) + 4 * half;
+            const int co = 32 * tile_m + hm_cd_row(i, half);
             const float sc = scale[co], sh = shift[co];
 #pragma unroll
             for (int t = 0; t < C3_NT; ++t) {
                 const int y = y0 + C3_NT * wave + t;
                 float v = fmaf(sc, acc[m][t][i], sh);
                 if (RESIDUAL) { /* (read under the predicate of the store below, at the store's index) */
-                    if (y < Ho && x < Wo) v = v + c3_widen<DT>(residual[(((size_t)n * Cout + co) * Ho + y) * Wo + x]);
+                    if (y < Ho && x < Wo) v = v + hm_widen<DT>(residual[(((size_t)n * Cout + co) * Ho + y) * Wo + x]);
                 }
                 if (relu) v = fmaxf(v, 0.0f);
                 if (y < Ho && x < Wo) {
                     const size_t at = (((size_t)n * Cout + co) * Ho + y) * Wo + x;
                     if (F32OUT) ((float*)out_)[at] = v;
-                    else ((uint16_t*)out_)[at] = c3_round<DT>(v);
+                    else ((uint16_t*)out_)[at] = hm_round<DT>(v);
                 }
             }
         }
@@ -256,12 +226,10 @@ extern "C" hipError_t isk_launch_conv_pack(const float* d_weight, int channels_o
                                            void* d_packed, hipStream_t stream) {
     const int taps = kernel * kernel, total = channels_out * channels_in * taps; /* at most 2048 * 2048 * 9 */
     const dim3 grid((total + 255) / 256);
-    if (dtype == IS_HEAD_F16)
-        hipLaunchKernelGGL(k_conv3x3_pack<IS_HEAD_F16>, grid, dim3(256), 0, stream, d_weight, (uint16_t*)d_packed, channels_in, taps, total);
-    else if (dtype == IS_HEAD_BF16)
-        hipLaunchKernelGGL(k_conv3x3_pack<IS_HEAD_BF16>, grid, dim3(256), 0, stream, d_weight, (uint16_t*)d_packed, channels_in, taps, total);
-    else
-        return hipErrorInvalidValue;
+    const bool half = hm_dispatch(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(k_conv3x3_pack<dt()>, grid, dim3(256), 0, stream, d_weight, (uint16_t*)d_packed, channels_in, taps, total);
+    });
+    if (!half) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
@@ -280,30 +248,21 @@ static void c3_launch(const is_conv_bn_stride_args* a, hipStream_t stream) {
                        a->relu, tiles_x, tiles, groups);
 }
 
-template <int DT, bool F32OUT, int TAPS>
-static void c3_launch_taps(const is_conv_bn_stride_args* a, hipStream_t stream) {
-    if (a->stride == 2) {
-        if (a->d_residual) c3_launch<DT, F32OUT, TAPS, true, 2>(a, stream); else c3_launch<DT, F32OUT, TAPS, false, 2>(a, stream);
-    } else {
-        if (a->d_residual) c3_launch<DT, F32OUT, TAPS, true, 1>(a, stream); else c3_launch<DT, F32OUT, TAPS, false, 1>(a, stream);
-    }
-}
-
-template <int DT, bool F32OUT>
-static void c3_launch_form(const is_conv_bn_stride_args* a, hipStream_t stream) {
-    if (a->kernel == 3) c3_launch_taps<DT, F32OUT, 9>(a, stream); else c3_launch_taps<DT, F32OUT, 1>(a, stream);
-}
-
 /* The arguments are checked by is_core.hip's conv_bn_run, for is_conv_bn_stride, is_conv_bn and is_conv3x3_bn_relu alike. */
 extern "C" hipError_t isk_launch_conv_bn(const is_conv_bn_stride_args* a, hipStream_t stream) {
     const bool f32out = a->out_dtype == IS_HEAD_F32;
     if ((a->kernel != 3 && a->kernel != 1) || (a->stride != 1 && a->stride != 2)) return hipErrorInvalidValue;
-    if (a->dtype == IS_HEAD_F16) {
-        if (f32out) c3_launch_form<IS_HEAD_F16, true>(a, stream); else c3_launch_form<IS_HEAD_F16, false>(a, stream);
-    } else if (a->dtype == IS_HEAD_BF16) {
-        if (f32out) c3_launch_form<IS_HEAD_BF16, true>(a, stream); else c3_launch_form<IS_HEAD_BF16, false>(a, stream);
-    } else {
-        return hipErrorInvalidValue;
-    }
+    const bool half = hm_dispatch(a->dtype, [&](auto dt) {
+        hm_either<true, false>(f32out, [&](auto f32) {
+            hm_either<9, 1>(a->kernel == 3, [&](auto taps) {
+                hm_either<2, 1>(a->stride == 2, [&](auto stride) {
+                    hm_either<true, false>(a->d_residual != nullptr, [&](auto residual) {
+                        c3_launch<dt(), f32(), taps(), residual(), stride()>(a, stream);
+                    });
+                });
+            });
+        });
+    });
+    if (!half) return hipErrorInvalidValue;
     return hipGetLastError();
 }

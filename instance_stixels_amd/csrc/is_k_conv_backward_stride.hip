@@ -7,14 +7,9 @@
  *
  * Extents: Hi x Wi is the input (x, dX), Ho x Wo = ceil(Hi / 2) x ceil(Wi / 2) the output (gh).
  *
- * k_conv_bwd_data_s2<DT, KERNEL>.  dX[ci][r][c] sums wT[ci][co][tap] gh[co][y][x] over the taps with 2 y + ky - 1 = r and
- * 2 x + kx - 1 = c.  A CELL (Y, X) is the input pixels (2 Y + {0, 1}, 2 X + {0, 1}), one of each parity class; its taps
- * read gh at (Y .. Y + 1, X .. X + 1) only:
- *     (even, even)  tap 4 gh[Y][X]
- *     (even, odd)   tap 3 gh[Y][X + 1],  tap 5 gh[Y][X]
- *     (odd, even)   tap 1 gh[Y + 1][X],  tap 7 gh[Y][X]
- *     (odd, odd)    tap 0 gh[Y + 1][X + 1],  tap 2 gh[Y + 1][X],  tap 6 gh[Y][X + 1],  tap 8 gh[Y][X]
- * (kernel 1: (even, even) is w gh[Y][X] and the other three classes have no tap).  A workgroup of four waves owns 32
+ * k_conv_bwd_data_s2<DT, KERNEL>.  The cells, parity classes and tap table of the transposed convolution are
+ * is_conv_backward.h's, at cb_parity_taps (kernel 1: the class (even, even) is w gh[Y][X] and the other three have no
+ * tap).  A workgroup of four waves owns 32
  * ci x (4 x 32) cells, wave w the 32 cells of cell row Y0 + w.  Each class is its own chain of 32x32x16 MFMAs, M = ci, N =
  * the 32 cells, K = 16 co, in increasing 16-co chunk and, inside a chunk, increasing tap: one accumulator per dX
  * element, never split or combined.  Per 16-co chunk the workgroup stages the gh tile it reads, (4 + 1) rows x (32 + 1)
@@ -35,16 +30,17 @@
  *           half wave fall on 8 of the banks, a 4-way conflict.  Accepted: a thread writes 6 dwords per chunk against
  *           4 reads of 16 bytes and 9 MFMAs of 8 passes; coalesced global reads of whole rows were put first.
  *
- * k_conv_bwd_weight_s2<DT, TAPS> is k_conv_bwd_weight's implicit GEMM (same tile, same LDS tile and bank account, same
- * fragment reads) with the x operand of tap (ky, kx) at x[ci][2 y + ky - 1][2 p + kx - 1] for output pixel (y, p).  The
- * staging deinterleaves: per kx the workgroup holds a copy of the input row whose pixel p is column 2 p + kx - 1, so
- * every fragment of every tap stays one aligned ds_read_b128 (kx = 1 is the even columns, kx = 0 and 2 the odd ones
- * at p - 1 and p).  Output rows y and y + 1 share input row 2 y + 1: input row g lives in ring slot (g + 1) % 3, a
- * step stages gh and the two new rows 2 y and 2 y + 1 in their kx copies (7 tiles for 18 MFMAs per wave; stride 1
- * stages 4) and keeps row 2 y - 1 from the step before.  The 2-byte global loads of a copy are 4 bytes apart; the three
- * copies of a row read it 1.5 times, from the same cache lines.  A wave whose 32 x 32 block lies wholly past
- * channels_out or channels_in (layer2's 16 channels in, a 1x1 with 32) skips its MFMAs and stores and only helps
- * staging; a narrower tile is not built.
+ * k_conv_bwd_weight_s2<DT, TAPS> is the implicit GEMM that is_conv_backward.h describes (same tile, same LDS tile and bank
+ * account, same fragment reads) at STEP = 2: the x operand of tap (ky, kx) is x[ci][2 y + ky - 1][2 p + kx - 1] for output
+ * pixel (y, p), so the kx copies deinterleave the input row (kx = 1 is the even columns, kx = 0 and 2 the odd ones at p - 1
+ * and p).  Output rows y and y + 1 share input row 2 y + 1: input row g lives in ring slot (g + 1) % 3, a step stages gh
+ * and the two new rows 2 y and 2 y + 1 in their kx copies (7 tiles for 18 MFMAs per wave; stride 1 stages 4) and keeps
+ * row 2 y - 1 from the step before.  A wave whose 32 x 32 block lies wholly past channels_out or channels_in (layer2's 16
+ * channels in, a 1x1 with 32) skips its MFMAs and stores and only helps staging; a narrower tile is not built.
+ * It shares cb_decode and cb_clear with k_conv_bwd_weight and KEEPS ITS OWN COPY of the staging, the MFMA step and the
+ * epilogue (is_conv_backward.h's cb_load_* / cb_store_* at STEP = 2, CB_MULTIPLY, cb_store_part say the same): at 3x3 it
+ * sits at the register limit (356 VGPRs, 12 SGPRs spilled to lanes), and through the shared functions the same work was
+ * allocated differently (19 spills) and ran 1 % slower on layer2's shape.  Whoever changes one changes both.
  */
 #include "is_conv_backward.h"
 
@@ -69,11 +65,8 @@ __global__ __launch_bounds__(256) void k_conv_bwd_data_s2(const uint16_t* __rest
     for (int z = blockIdx.z; z < n_images * tiles_ci; z += gridDim.z) { /* (the same trip count for the whole workgroup) */
         const int n = z / tiles_ci, tile_ci = z % tiles_ci;
         const uint16_t* const ghn = gh + (size_t)n * Cout * plane_o;
-        cb_acc acc[4]; /* (even, even), (even, odd), (odd, even), (odd, odd) */
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[c][i] = 0.0f;
+        hm_acc16 acc[4]; /* (even, even), (even, odd), (odd, even), (odd, odd) */
+        cb_clear(acc);
 
         /* A thread's items (co pair q, row, col) of the tile, consecutive threads consecutive columns. */
         uint32_t v[ITERS][2];
@@ -108,32 +101,22 @@ __global__ __launch_bounds__(256) void k_conv_bwd_data_s2(const uint16_t* __rest
             const uint4* const wfrag = packed + ((size_t)(tile_ci * chunks + chunk) * TAPS) * 64 + lane;
             const uint4* const b = tile + ENTRIES * (chunk & 1) + (half * ROWS + wave) * COLS + r;
             /* the pack holds tap t at index TAPS - 1 - t (it is f18's flipped operand) */
-#define CS_W(t) wfrag[(TAPS - 1 - (t)) * 64]
             if (KERNEL == 3) {
-                const uint4 b00 = b[0], b01 = b[1], b10 = b[COLS], b11 = b[COLS + 1];
-                acc[3] = cb_mfma<DT>(CS_W(0), b11, acc[3]);
-                acc[2] = cb_mfma<DT>(CS_W(1), b10, acc[2]);
-                acc[3] = cb_mfma<DT>(CS_W(2), b10, acc[3]);
-                acc[1] = cb_mfma<DT>(CS_W(3), b01, acc[1]);
-                acc[0] = cb_mfma<DT>(CS_W(4), b00, acc[0]);
-                acc[1] = cb_mfma<DT>(CS_W(5), b00, acc[1]);
-                acc[3] = cb_mfma<DT>(CS_W(6), b01, acc[3]);
-                acc[2] = cb_mfma<DT>(CS_W(7), b00, acc[2]);
-                acc[3] = cb_mfma<DT>(CS_W(8), b00, acc[3]);
+                const uint4 bq[4] = {b[0], b[1], b[COLS], b[COLS + 1]};
+                cb_parity_taps<DT>(acc, bq, [&](int t) { return wfrag[(TAPS - 1 - t) * 64]; });
             } else {
-                acc[0] = cb_mfma<DT>(CS_W(0), b[0], acc[0]);
+                acc[0] = hm_mfma<DT>(wfrag[0], b[0], acc[0]);
             }
-#undef CS_W
             if (chunk + 1 < chunks) store_tile((chunk + 1) & 1);
             __syncthreads();
         }
 
-        /* register i of a lane is ci row (i & 3) + 8 (i >> 2) + 4 half of the tile at cell X0 + r */
+        /* register i of a lane is ci row hm_cd_row(i, half) of the tile at cell X0 + r */
         const int Y = Y0 + wave, X = X0 + r, c0 = 2 * X;
         if (Y < Ho && X < Wo) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int ci = 32 * tile_ci + (i & 3) + 8 * (i >> 2) + 4 * half;
+                const int ci = 32 * tile_ci + hm_cd_row(i, half);
 #pragma unroll
                 for (int pr = 0; pr < 2; ++pr) {
                     const int row = 2 * Y + pr;
@@ -144,21 +127,21 @@ __global__ __launch_bounds__(256) void k_conv_bwd_data_s2(const uint16_t* __rest
                     if (pairs) { /* Wi is even and every base 4-byte (fp32: 8-byte) aligned: the cell's two columns at once */
                         if (add) {
                             const uint32_t a2 = *(const uint32_t*)(add + at);
-                            v0 = v0 + cb_widen<DT>((uint16_t)a2), v1 = v1 + cb_widen<DT>((uint16_t)(a2 >> 16));
+                            v0 = v0 + hm_widen<DT>((uint16_t)a2), v1 = v1 + hm_widen<DT>((uint16_t)(a2 >> 16));
                         }
                         if (dx_f32) *(float2*)((float*)dx_ + at) = make_float2(v0, v1);
-                        else *(uint32_t*)((uint16_t*)dx_ + at) = cb_round<DT>(v0) | ((uint32_t)cb_round<DT>(v1) << 16);
+                        else *(uint32_t*)((uint16_t*)dx_ + at) = hm_round<DT>(v0) | ((uint32_t)hm_round<DT>(v1) << 16);
                     } else {
                         if (add) {
-                            v0 = v0 + cb_widen<DT>(add[at]);
-                            if (second) v1 = v1 + cb_widen<DT>(add[at + 1]);
+                            v0 = v0 + hm_widen<DT>(add[at]);
+                            if (second) v1 = v1 + hm_widen<DT>(add[at + 1]);
                         }
                         if (dx_f32) {
                             ((float*)dx_)[at] = v0;
                             if (second) ((float*)dx_)[at + 1] = v1;
                         } else {
-                            ((uint16_t*)dx_)[at] = cb_round<DT>(v0);
-                            if (second) ((uint16_t*)dx_)[at + 1] = cb_round<DT>(v1);
+                            ((uint16_t*)dx_)[at] = hm_round<DT>(v0);
+                            if (second) ((uint16_t*)dx_)[at + 1] = hm_round<DT>(v1);
                         }
                     }
                 }
@@ -177,25 +160,17 @@ __global__ __launch_bounds__(256) void k_conv_bwd_weight_s2(const uint16_t* __re
     constexpr int KX = TAPS == 9 ? 3 : 1, NEW = TAPS == 9 ? 2 : 1; /* kx copies of a row; new input rows of a step */
     extern __shared__ uint4 cs_lds[]; /* [1 + TAPS] tiles: gh, then x [ring slot][kx] */
     uint32_t* const ldsw = (uint32_t*)cs_lds;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, half = lane >> 5;
-    /* workgroup b of the grid is taken to run on XCD b & 7: the weight tiles of a chunk follow each other there */
-    const int seq = blockIdx.x >> 3, tile = seq % tiles, chunk = (seq / tiles) * 8 + (blockIdx.x & 7);
-    if (chunk >= chunks) return; /* (the whole workgroup, before any barrier) */
-    const int n = chunk / bands, ya = (chunk % bands) * IS_CONV_BACKWARD_STRIDE_BAND;
-    const int yb = min(ya + IS_CONV_BACKWARD_STRIDE_BAND, Ho);
-    const int co0 = (tile / tiles_ci) * 64, ci0 = (tile % tiles_ci) * 64;
-    const int mrow = 32 * (wave & 1), nrow = 32 * (wave >> 1);
+    const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, half = lane >> 5;
+    const cb_group g = cb_decode<IS_CONV_BACKWARD_STRIDE_BAND>(Ho, bands, tiles_ci, tiles);
+    if (g.chunk >= chunks) return; /* (the whole workgroup, before any barrier) */
+    const int chunk = g.chunk, n = g.n, ya = g.ya, yb = g.yb, co0 = g.co0, ci0 = g.ci0, mrow = g.mrow, nrow = g.nrow;
     const bool live = co0 + mrow < Cout && ci0 + nrow < Cin; /* (per wave) a block wholly past the channels multiplies nothing */
     const size_t plane_o = (size_t)Ho * Wo, plane_i = (size_t)Hi * Wi;
     const uint16_t* const ghn = gh + (size_t)n * Cout * plane_o;
     const uint16_t* const xn = x + (size_t)n * Cin * plane_i;
 
-    cb_acc acc[TAPS];
-#pragma unroll
-    for (int t = 0; t < TAPS; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+    hm_acc16 acc[TAPS];
+    cb_clear(acc);
 
     /* column of the input that output pixel p reads in copy kx */
     auto col_of = [](int p, int kx) { return TAPS == 9 ? 2 * p + kx - 1 : 2 * p; };
@@ -279,7 +254,7 @@ __global__ __launch_bounds__(256) void k_conv_bwd_weight_s2(const uint16_t* __re
 #pragma unroll
                     for (int tap = 0; tap < TAPS; ++tap) {
                         const int tile_b = TAPS == 1 ? 1 : 1 + KX * ((s0 + tap / 3) % 3) + tap % 3;
-                        acc[tap] = cb_mfma<DT>(a, cs_lds[CB_TILE_ENTRIES * tile_b + eb], acc[tap]);
+                        acc[tap] = hm_mfma<DT>(a, cs_lds[CB_TILE_ENTRIES * tile_b + eb], acc[tap]);
                     }
                 }
             }
@@ -300,16 +275,6 @@ __global__ __launch_bounds__(256) void k_conv_bwd_weight_s2(const uint16_t* __re
     }
 }
 
-static int cs_bands(int Ho) { return (Ho + IS_CONV_BACKWARD_STRIDE_BAND - 1) / IS_CONV_BACKWARD_STRIDE_BAND; }
-
-/* The grid of k_conv_bwd_weight_s2 (0: it does not fit 31 bits). */
-extern "C" long long isk_conv_bwd_weight_s2_grid(int n_images, int channels_in, int channels_out, int rows_out) {
-    const long long tiles = (long long)((channels_out + 63) / 64) * ((channels_in + 63) / 64);
-    const long long chunks = (long long)n_images * cs_bands(rows_out);
-    const long long grid = tiles * ((chunks + 7) / 8 * 8);
-    return grid > 0x7fffffffLL ? 0 : grid;
-}
-
 /* dX of a stride-2 call: every element of d_grad_features is written.  gh: [n][Cout][Ho][Wo]; packed: the transposed
  * pack of k_conv_bwd_pack_t, 16-byte aligned. */
 extern "C" void isk_launch_conv_bwd_data_s2(const is_conv_bn_stride_backward_args* a, const void* gh, const void* packed,
@@ -322,16 +287,13 @@ extern "C" void isk_launch_conv_bwd_data_s2(const is_conv_bn_stride_backward_arg
     const long long zs = (long long)a->n_images * tiles_ci;
     const dim3 grid((Wo + CS_CELL_COLS - 1) / CS_CELL_COLS, (Ho + CS_CELL_ROWS - 1) / CS_CELL_ROWS,
                     (unsigned)(zs < 65535 ? zs : 65535));
-#define CS_DATA(DT, K)                                                                                                   \
-    hipLaunchKernelGGL((k_conv_bwd_data_s2<DT, K>), grid, dim3(256), 0, stream, (const uint16_t*)gh, (const uint4*)packed, \
-                       (const uint16_t*)a->d_grad_features_add, a->d_grad_features, dx_f32, pairs, a->n_images,            \
-                       a->channels_in, a->channels_out, Hi, Wi, Ho, Wo)
-    if (a->dtype == IS_HEAD_F16) {
-        if (a->kernel == 3) CS_DATA(IS_HEAD_F16, 3); else CS_DATA(IS_HEAD_F16, 1);
-    } else {
-        if (a->kernel == 3) CS_DATA(IS_HEAD_BF16, 3); else CS_DATA(IS_HEAD_BF16, 1);
-    }
-#undef CS_DATA
+    hm_dispatch(a->dtype, [&](auto dt) {
+        hm_either<3, 1>(a->kernel == 3, [&](auto k) {
+            hipLaunchKernelGGL((k_conv_bwd_data_s2<dt(), k()>), grid, dim3(256), 0, stream, (const uint16_t*)gh,
+                               (const uint4*)packed, (const uint16_t*)a->d_grad_features_add, a->d_grad_features, dx_f32, pairs,
+                               a->n_images, a->channels_in, a->channels_out, Hi, Wi, Ho, Wo);
+        });
+    });
 }
 
 /* The chunk partials of a stride-2 call into `part`. */
@@ -339,17 +301,14 @@ extern "C" void isk_launch_conv_bwd_weight_s2(const is_conv_bn_stride_backward_a
                                               hipStream_t stream) {
     const int Cin = a->channels_in, Cout = a->channels_out, Hi = a->rows_in, Wi = a->cols_in;
     const int Ho = (Hi + 1) / 2, Wo = (Wi + 1) / 2;
-    const int taps = a->kernel * a->kernel, bands = cs_bands(Ho), chunks = a->n_images * bands;
+    const int taps = a->kernel * a->kernel, bands = cb_bands(Ho, 2), chunks = a->n_images * bands;
     const int tiles_ci = (Cin + 63) / 64, tiles = tiles_ci * ((Cout + 63) / 64);
-    const dim3 grid((unsigned)isk_conv_bwd_weight_s2_grid(a->n_images, Cin, Cout, Ho));
-    const size_t lds = (size_t)(1 + taps) * CB_TILE_ENTRIES * 16;
-#define CS_WEIGHT(DT, TAPS)                                                                                              \
-    hipLaunchKernelGGL((k_conv_bwd_weight_s2<DT, TAPS>), grid, dim3(256), lds, stream, (const uint16_t*)gh,               \
-                       (const uint16_t*)a->d_features, part, Cin, Cout, Hi, Wi, Ho, Wo, bands, tiles_ci, tiles, chunks)
-    if (a->dtype == IS_HEAD_F16) {
-        if (taps == 9) CS_WEIGHT(IS_HEAD_F16, 9); else CS_WEIGHT(IS_HEAD_F16, 1);
-    } else {
-        if (taps == 9) CS_WEIGHT(IS_HEAD_BF16, 9); else CS_WEIGHT(IS_HEAD_BF16, 1);
-    }
-#undef CS_WEIGHT
+    const dim3 grid((unsigned)cb_weight_grid(a->n_images, Cin, Cout, bands));
+    hm_dispatch(a->dtype, [&](auto dt) {
+        hm_either<9, 1>(taps == 9, [&](auto t) {
+            hipLaunchKernelGGL((k_conv_bwd_weight_s2<dt(), t()>), grid, dim3(256), cb_weight_lds(taps), stream,
+                               (const uint16_t*)gh, (const uint16_t*)a->d_features, part, Cin, Cout, Hi, Wi, Ho, Wo, bands,
+                               tiles_ci, tiles, chunks);
+        });
+    });
 }

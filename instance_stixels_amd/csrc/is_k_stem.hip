@@ -53,7 +53,7 @@
  *      consecutive pixels of ONE channel plane, one 8-byte store.
  *   The weights never touch LDS: the packed blob is the 7 + 5 fragments lane by lane, 48 registers for the launch.
  */
-#include "is_launch.h"
+#include "is_half_mfma.h"
 
 #define ST_ROWS 16
 #define ST_COLS 64
@@ -73,32 +73,6 @@ static_assert(ST_LDS_BYTES <= 65536 && 3 * ST_LDS_BYTES <= 160 * 1024,
 static_assert(ST_COLS % 16 == 0 && ST_OGROUPS % 4 == 0, "an output group is 16 pixels of one row; four waves share them");
 static_assert((ST_XROWS - 1) * ST_XCOLS + (ST_MCOLS - 1) + 2 * 3 + 1 < ST_XPIX, "the last read of layer0 is inside the tile");
 
-typedef float st_acc __attribute__((ext_vector_type(4)));
-typedef _Float16 st_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 st_bf16x8 __attribute__((ext_vector_type(8)));
-
-/* fp32 -> half, round to nearest even, as 16 bits */
-template <int DT> __device__ __forceinline__ uint32_t st_round(float v);
-template <> __device__ __forceinline__ uint32_t st_round<IS_HEAD_F16>(float v) {
-    return __builtin_bit_cast(uint16_t, (_Float16)v);
-}
-template <> __device__ __forceinline__ uint32_t st_round<IS_HEAD_BF16>(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-
-template <int DT> __device__ __forceinline__ st_acc st_mfma(uint4 a, uint4 b, st_acc c);
-template <> __device__ __forceinline__ st_acc st_mfma<IS_HEAD_F16>(uint4 a, uint4 b, st_acc c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(st_f16x8, a), __builtin_bit_cast(st_f16x8, b), c, 0, 0, 0);
-}
-template <> __device__ __forceinline__ st_acc st_mfma<IS_HEAD_BF16>(uint4 a, uint4 b, st_acc c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(st_bf16x8, a), __builtin_bit_cast(st_bf16x8, b), c, 0, 0, 0);
-}
-
-/* the 16-byte slot of channel half `h` of mid pixel `p` (is_k_conv3x3.hip's c3_slot: the 16 lanes of a ds_read_b128
- * group read 16 consecutive pixels, whose slots then cover all 16 slots of a bank row) */
-__device__ __forceinline__ int st_slot(int p, int h) { return 2 * p + (h ^ ((p >> 3) & 1)); }
-
 /* The blob, in 16-bit elements e = (step * 64 + lane) * 8 + j, the fragment of `lane` in `step`:
  *   step < 7   layer0, ky = step: round(w0[lane & 15][j & 3][ky][2 (lane >> 4) + (j >> 2)]), 0 where ci = 3 or kx = 7
  *   step >= 7  layer1, s = step - 7, k = 32 s + 8 (lane >> 4) + j = 16 tap + ci: round(w1[lane & 15][ci][tap / 3][tap % 3]),
@@ -117,7 +91,7 @@ __global__ __launch_bounds__(256) void k_stem_pack(const float* __restrict__ w0,
         const int k = 32 * (step - ST_K0) + 8 * g + j, tap = k >> 4, ci = k & 15;
         if (tap < 9) v = w1[(co * 16 + ci) * 9 + tap];
     }
-    packed[e] = (uint16_t)st_round<DT>(v);
+    packed[e] = hm_round<DT>(v);
 }
 
 template <int DT>
@@ -128,7 +102,7 @@ __global__ __launch_bounds__(256) void k_stem(const uint8_t* __restrict__ image,
                                               uint16_t* __restrict__ out, int H, int W, int tiles_x) {
     __shared__ uint16_t s_lut[3 * 256];
     __shared__ uint2 s_x[ST_XPIX];         /* [pixel of the looked-up tile] (ci 0, ci 1), (ci 2, 0) */
-    __shared__ uint4 s_mid[2 * ST_MPIX];   /* st_slot(pixel of the mid tile, channel half) */
+    __shared__ uint4 s_mid[2 * ST_MPIX];   /* hm_slot(pixel of the mid tile, channel half) */
     static_assert(sizeof(s_lut) + sizeof(s_x) + sizeof(s_mid) == ST_LDS_BYTES, "the LDS account of the header");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, p = lane & 15, g = lane >> 4;
     const int n = blockIdx.y, y0 = (blockIdx.x / tiles_x) * ST_ROWS, x0 = (blockIdx.x % tiles_x) * ST_COLS;
@@ -169,20 +143,20 @@ __global__ __launch_bounds__(256) void k_stem(const uint8_t* __restrict__ image,
         /* mid pixel (my, mx) is image pixel (y0 - 1 + my, x0 - 1 + mx); tap (ky, kx) of it is pixel (my + ky, mx + kx)
          * of the looked-up tile */
         const uint2* const b = s_x + my * ST_XCOLS + mx + 2 * g;
-        st_acc acc = {0.0f, 0.0f, 0.0f, 0.0f};
+        hm_acc4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int ky = 0; ky < ST_K0; ++ky) {
             const uint2 lo = b[ky * ST_XCOLS], hi = b[ky * ST_XCOLS + 1];
             /* kx = 7 is no tap: an exact zero, whatever pixel stands there */
-            acc = st_mfma<DT>(w0[ky], make_uint4(lo.x, lo.y, g == 3 ? 0u : hi.x, g == 3 ? 0u : hi.y), acc);
+            acc = hm_mfma<DT>(w0[ky], make_uint4(lo.x, lo.y, g == 3 ? 0u : hi.x, g == 3 ? 0u : hi.y), acc);
         }
         const int gy = y0 - 1 + my, gx = x0 - 1 + mx;
         const bool inside = gy >= 0 && gy < H && gx >= 0 && gx < W;
         uint32_t r[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = inside ? st_round<DT>(fmaxf(fmaf(sc0[i], acc[i], sh0[i]), 0.0f)) : 0u;
+        for (int i = 0; i < 4; ++i) r[i] = inside ? hm_round<DT>(fmaxf(fmaf(sc0[i], acc[i], sh0[i]), 0.0f)) : 0u;
         if (16 * grp + p < ST_MPIX) {
-            ((uint2*)s_mid)[2 * st_slot(q, g >> 1) + (g & 1)] = make_uint2(r[0] | (r[1] << 16), r[2] | (r[3] << 16));
+            ((uint2*)s_mid)[2 * hm_slot(q, g >> 1) + (g & 1)] = make_uint2(r[0] | (r[1] << 16), r[2] | (r[3] << 16));
             /* the workgroup that owns the pixel stores it */
             if (mid_out && inside && my >= 1 && my <= ST_ROWS && mx >= 1 && mx <= ST_COLS) {
 #pragma unroll
@@ -203,18 +177,18 @@ __global__ __launch_bounds__(256) void k_stem(const uint8_t* __restrict__ image,
     for (int grp = wave; grp < ST_OGROUPS; grp += 4) {
         const int row = grp / (ST_COLS / 16), col = (grp % (ST_COLS / 16)) * 16;
         const int at = row * ST_MCOLS + col + p;   /* tap (0, 0) of output pixel (row, col + p) in the mid tile */
-        st_acc acc = {0.0f, 0.0f, 0.0f, 0.0f};
+        hm_acc4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int s = 0; s < ST_K1; ++s) {
-            uint4 a = s_mid[st_slot(at + tap_at[s], g & 1)];
+            uint4 a = s_mid[hm_slot(at + tap_at[s], g & 1)];
             if (s == ST_K1 - 1 && g >= 2) a = make_uint4(0, 0, 0, 0);
-            acc = st_mfma<DT>(a, w1[s], acc);
+            acc = hm_mfma<DT>(a, w1[s], acc);
         }
         /* register i is pixel col + 4g + i of the row, channel p */
         const int y = y0 + row, x = x0 + col + 4 * g;
         uint32_t r[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = st_round<DT>(fmaxf(fmaf(sc1, acc[i], sh1), 0.0f));
+        for (int i = 0; i < 4; ++i) r[i] = hm_round<DT>(fmaxf(fmaf(sc1, acc[i], sh1), 0.0f));
         if (y < H && x < W) {
             uint16_t* const dst = out + ((size_t)n * 16 + p) * plane + (size_t)y * W + x;
             if (x + 3 < W) {
@@ -233,12 +207,10 @@ __global__ __launch_bounds__(256) void k_stem(const uint8_t* __restrict__ image,
 /* The arguments are checked by is_stem_pack_weights. */
 extern "C" hipError_t isk_launch_stem_pack(const float* d_w0, const float* d_w1, int dtype, void* d_packed, hipStream_t stream) {
     const dim3 grid(((ST_K0 + ST_K1) * 64 * 8 + 255) / 256);
-    if (dtype == IS_HEAD_F16)
-        hipLaunchKernelGGL(k_stem_pack<IS_HEAD_F16>, grid, dim3(256), 0, stream, d_w0, d_w1, (uint16_t*)d_packed);
-    else if (dtype == IS_HEAD_BF16)
-        hipLaunchKernelGGL(k_stem_pack<IS_HEAD_BF16>, grid, dim3(256), 0, stream, d_w0, d_w1, (uint16_t*)d_packed);
-    else
-        return hipErrorInvalidValue;
+    const bool half = hm_dispatch(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(k_stem_pack<dt()>, grid, dim3(256), 0, stream, d_w0, d_w1, (uint16_t*)d_packed);
+    });
+    if (!half) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
@@ -248,15 +220,11 @@ extern "C" size_t isk_stem_packed_bytes(void) { return (size_t)(ST_K0 + ST_K1) *
 extern "C" hipError_t isk_launch_stem(const is_stem_args* a, hipStream_t stream) {
     const int tiles_x = (a->cols + ST_COLS - 1) / ST_COLS, tiles_y = (a->rows + ST_ROWS - 1) / ST_ROWS;
     const dim3 grid((unsigned)tiles_x * (unsigned)tiles_y, a->n_images); /* at most 512 * 2048 by 65535 */
-    if (a->dtype == IS_HEAD_F16)
-        hipLaunchKernelGGL(k_stem<IS_HEAD_F16>, grid, dim3(256), 0, stream, (const uint8_t*)a->d_image, (const uint16_t*)a->d_lut,
+    const bool half = hm_dispatch(a->dtype, [&](auto dt) {
+        hipLaunchKernelGGL(k_stem<dt()>, grid, dim3(256), 0, stream, (const uint8_t*)a->d_image, (const uint16_t*)a->d_lut,
                            (const uint4*)a->d_packed, a->d_scale0, a->d_shift0, a->d_scale1, a->d_shift1,
                            (uint16_t*)a->d_mid, (uint16_t*)a->d_out, a->rows, a->cols, tiles_x);
-    else if (a->dtype == IS_HEAD_BF16)
-        hipLaunchKernelGGL(k_stem<IS_HEAD_BF16>, grid, dim3(256), 0, stream, (const uint8_t*)a->d_image, (const uint16_t*)a->d_lut,
-                           (const uint4*)a->d_packed, a->d_scale0, a->d_shift0, a->d_scale1, a->d_shift1,
-                           (uint16_t*)a->d_mid, (uint16_t*)a->d_out, a->rows, a->cols, tiles_x);
-    else
-        return hipErrorInvalidValue;
+    });
+    if (!half) return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -14,7 +14,7 @@
  *
  * k_stem_bwd_data<DT>     is_k_stem.hip's tile: a workgroup of four waves owns SB_ROWS = 16 rows of SB_COLS = 64 pixels
  *   of one frame.
- *   1  gh1 on the tile plus a halo of 1, 18 x 66 pixels, into LDS as [pixel][16 channels] in k_stem's st_slot layout
+ *   1  gh1 on the tile plus a halo of 1, 18 x 66 pixels, into LDS as [pixel][16 channels] in k_stem's hm_slot layout
  *      (38 KB): a thread takes a pixel and eight channels, 8 + 8 two-byte loads of dY and out that consecutive lanes make
  *      at consecutive pixels, one 16-byte LDS write; a pixel outside the image is zero (the address is clamped into the
  *      image).  The owner of a pixel stores its gh1.
@@ -62,19 +62,6 @@ static_assert(SB_COLS % 16 == 0 && SB_OGROUPS % 4 == 0 && SB_ROWS == 16, "a grou
 static_assert(SW_SEG % 32 == 0 && (SW_RS * 2) % 16 == 0, "whole K steps; 16-byte aligned fragments");
 static_assert(3 * SW_LDS_BYTES <= 160 * 1024 && SW_LDS_BYTES <= 65536, "three workgroups a CU");
 
-typedef float sb_acc __attribute__((ext_vector_type(4)));
-
-template <int DT> __device__ __forceinline__ sb_acc sb_mfma(uint4 a, uint4 b, sb_acc c);
-template <> __device__ __forceinline__ sb_acc sb_mfma<IS_HEAD_F16>(uint4 a, uint4 b, sb_acc c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(cb_f16x8, a), __builtin_bit_cast(cb_f16x8, b), c, 0, 0, 0);
-}
-template <> __device__ __forceinline__ sb_acc sb_mfma<IS_HEAD_BF16>(uint4 a, uint4 b, sb_acc c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(cb_bf16x8, a), __builtin_bit_cast(cb_bf16x8, b), c, 0, 0, 0);
-}
-
-/* is_k_stem.hip's st_slot: the 16-byte slot of channel half `h` of pixel `p` */
-__device__ __forceinline__ int sb_slot(int p, int h) { return 2 * p + (h ^ ((p >> 3) & 1)); }
-
 template <int DT>
 __global__ __launch_bounds__(256) void k_stem_bwd_pack_t(const float* __restrict__ w1, const float* __restrict__ scale1,
                                                          uint16_t* __restrict__ packed) {
@@ -82,15 +69,7 @@ __global__ __launch_bounds__(256) void k_stem_bwd_pack_t(const float* __restrict
     if (e >= SB_K1 * 64 * 8) return;
     const int j = e & 7, lane = (e >> 3) & 63, s = e >> 9, ci = lane & 15, g = lane >> 4;
     const int k = 32 * s + 8 * g + j, tap = k >> 4, co = k & 15;
-    uint16_t r = 0;
-    if (tap < 9) {
-        const float wh = cb_widen<DT>(cb_round<DT>(w1[(co * 16 + ci) * 9 + (8 - tap)]));
-        float product = scale1[co] * wh;
-        /* the fp32 product as a value (k_conv_bwd_pack_t: no fused mixed-precision multiply) */
-        asm volatile("" : "+v"(product));
-        r = cb_round<DT>(product);
-    }
-    packed[e] = r;
+    packed[e] = tap < 9 ? hm_scaled_weight<DT>(scale1[co], w1[(co * 16 + ci) * 9 + (8 - tap)]) : (uint16_t)0;
 }
 
 /* The A fragments of g_out, lane by lane: element ((chunk * 9 + tap) * 64 + lane) * 8 + j is
@@ -102,15 +81,12 @@ __global__ __launch_bounds__(256) void k_stem_bwd_pack_next(const float* __restr
     if (e >= total) return;
     const int j = e & 7, lane = (e >> 3) & 63, tap = (e >> 9) % 9, chunk = (e >> 9) / 9;
     const int ci = lane & 15, co = 32 * chunk + 8 * (lane >> 4) + j;
-    const float wh = cb_widen<DT>(cb_round<DT>(w[((size_t)co * 16 + ci) * 9 + tap]));
-    float product = scale[co] * wh;
-    asm volatile("" : "+v"(product)); /* (as above) */
-    packed[e] = cb_round<DT>(product);
+    packed[e] = hm_scaled_weight<DT>(scale[co], w[((size_t)co * 16 + ci) * 9 + tap]);
 }
 
 /* g_out from the masked gradient of the stride-2 3x3 layer that reads `out` (f22's dX at 16 input channels).  A wave
  * owns 16 CELLS of one cell row: cell (Y, X) is the pixels (2 Y + {0, 1}, 2 X + {0, 1}), one of each parity class, and
- * its taps read gh at (Y .. Y + 1, X .. X + 1) only (is_k_conv_backward_stride.hip's table).  Each class is its own
+ * its taps read gh at (Y .. Y + 1, X .. X + 1) only (is_conv_backward.h's cb_parity_taps).  Each class is its own
  * chain of 16x16x32 MFMAs, M = ci, N = the 16 cells, K = 32 co, in increasing 32-co chunk and, inside a chunk,
  * increasing tap: one accumulator per element.  The B fragment of a lane is 8 co of its cell's pixel: eight 2-byte
  * loads a pixel, which the 16 lanes of a group make at consecutive pixels of a plane; no LDS.  A gh pixel outside the
@@ -126,9 +102,9 @@ __global__ __launch_bounds__(256) void k_stem_bwd_gout(const uint16_t* __restric
                           (size_t)min(Y + 1, Ho - 1) * Wo + min(X, Wo - 1), (size_t)min(Y + 1, Ho - 1) * Wo + min(X + 1, Wo - 1)};
     const uint32_t keep[4] = {Y < Ho && X < Wo ? 0xffffu : 0u, Y < Ho && X + 1 < Wo ? 0xffffu : 0u,
                               Y + 1 < Ho && X < Wo ? 0xffffu : 0u, Y + 1 < Ho && X + 1 < Wo ? 0xffffu : 0u};
-    sb_acc acc[4]; /* (even, even), (even, odd), (odd, even), (odd, odd) */
+    hm_acc4 acc[4]; /* (even, even), (even, odd), (odd, even), (odd, odd) */
 #pragma unroll
-    for (int c = 0; c < 4; ++c) acc[c] = sb_acc{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int c = 0; c < 4; ++c) acc[c] = hm_acc4{0.0f, 0.0f, 0.0f, 0.0f};
     for (int chunk = 0; chunk < Cn / 32; ++chunk) {
         const uint16_t* const base = ghn + (size_t)(32 * chunk + 8 * g) * plane_o;
         uint4 b[4]; /* gh[Y][X], gh[Y][X + 1], gh[Y + 1][X], gh[Y + 1][X + 1] */
@@ -140,17 +116,7 @@ __global__ __launch_bounds__(256) void k_stem_bwd_gout(const uint16_t* __restric
             b[q] = make_uint4(v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16));
         }
         const uint4* const wfrag = packed + (size_t)chunk * 9 * 64 + lane;
-#define SB_W(t) wfrag[(t) * 64]
-        acc[3] = sb_mfma<DT>(SB_W(0), b[3], acc[3]);
-        acc[2] = sb_mfma<DT>(SB_W(1), b[2], acc[2]);
-        acc[3] = sb_mfma<DT>(SB_W(2), b[2], acc[3]);
-        acc[1] = sb_mfma<DT>(SB_W(3), b[1], acc[1]);
-        acc[0] = sb_mfma<DT>(SB_W(4), b[0], acc[0]);
-        acc[1] = sb_mfma<DT>(SB_W(5), b[0], acc[1]);
-        acc[3] = sb_mfma<DT>(SB_W(6), b[1], acc[3]);
-        acc[2] = sb_mfma<DT>(SB_W(7), b[0], acc[2]);
-        acc[3] = sb_mfma<DT>(SB_W(8), b[0], acc[3]);
-#undef SB_W
+        cb_parity_taps<DT>(acc, b, [&](int t) { return wfrag[t * 64]; });
     }
     /* register i of a lane is ci = 4 g + i of cell X */
 #pragma unroll
@@ -158,7 +124,7 @@ __global__ __launch_bounds__(256) void k_stem_bwd_gout(const uint16_t* __restric
         const int row = 2 * Y + (c >> 1), col = 2 * X + (c & 1);
         if (row >= H || col >= W) continue;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) gout[((size_t)n * 16 + 4 * g + i) * plane + (size_t)row * W + col] = cb_round<DT>(acc[c][i]);
+        for (int i = 0; i < 4; ++i) gout[((size_t)n * 16 + 4 * g + i) * plane + (size_t)row * W + col] = hm_round<DT>(acc[c][i]);
     }
 }
 
@@ -182,7 +148,7 @@ __global__ __launch_bounds__(256) void k_stem_bwd_data(const void* __restrict__ 
                                                        const uint4* __restrict__ packed, uint16_t* __restrict__ gh1_out,
                                                        uint16_t* __restrict__ gh0_out, double* __restrict__ shift1_part,
                                                        double* __restrict__ shift0_part, int H, int W, int tiles_x) {
-    __shared__ uint4 s_gh[2 * SB_GPIX];   /* sb_slot(pixel of the gh1 tile, channel half) */
+    __shared__ uint4 s_gh[2 * SB_GPIX];   /* hm_slot(pixel of the gh1 tile, channel half) */
     __shared__ double s_sum[256];
     static_assert(sizeof(s_gh) + sizeof(s_sum) == SB_LDS_BYTES, "the LDS account of the header");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, p = lane & 15, g = lane >> 4;
@@ -206,11 +172,11 @@ __global__ __launch_bounds__(256) void k_stem_bwd_data(const void* __restrict__ 
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const size_t e = (size_t)(8 * h + j) * plane + at;
-            const float o = cb_widen<DT>(outn[e]);
-            const float gv = dy_f32 ? ((const float*)dy_)[dyn + e] : cb_widen<DT>(((const uint16_t*)dy_)[dyn + e]);
-            r[j] = inside && o > 0.0f ? cb_round<DT>(gv) : 0u;
+            const float o = hm_widen<DT>(outn[e]);
+            const float gv = dy_f32 ? ((const float*)dy_)[dyn + e] : hm_widen<DT>(((const uint16_t*)dy_)[dyn + e]);
+            r[j] = inside && o > 0.0f ? hm_round<DT>(gv) : 0u;
         }
-        s_gh[sb_slot(q, h)] = make_uint4(r[0] | (r[1] << 16), r[2] | (r[3] << 16), r[4] | (r[5] << 16), r[6] | (r[7] << 16));
+        s_gh[hm_slot(q, h)] = make_uint4(r[0] | (r[1] << 16), r[2] | (r[3] << 16), r[4] | (r[5] << 16), r[6] | (r[7] << 16));
         /* the workgroup that owns the pixel stores it */
         if (inside && qy >= 1 && qy <= SB_ROWS && qx >= 1 && qx <= SB_COLS) {
 #pragma unroll
@@ -227,7 +193,7 @@ __global__ __launch_bounds__(256) void k_stem_bwd_data(const void* __restrict__ 
         if (shift1_part) {
             for (int x = 0; x < SB_COLS; ++x) {
                 const int q = (row + 1) * SB_GCOLS + x + 1;
-                s = s + (double)cb_widen<DT>(((const uint16_t*)s_gh)[8 * sb_slot(q, c >> 3) + (c & 7)]);
+                s = s + (double)hm_widen<DT>(((const uint16_t*)s_gh)[8 * hm_slot(q, c >> 3) + (c & 7)]);
             }
         }
         sb_tile_sum(s, s_sum, shift1_part + ((size_t)n * 16) * tiles + blockIdx.x, tiles, shift1_part != nullptr);
@@ -244,12 +210,12 @@ __global__ __launch_bounds__(256) void k_stem_bwd_data(const void* __restrict__ 
     for (int grp = wave; grp < SB_OGROUPS; grp += 4) {
         const int row = grp / (SB_COLS / 16), col = (grp % (SB_COLS / 16)) * 16;
         const int at = row * SB_GCOLS + col + p;   /* tap' (0, 0) of pixel (row, col + p) in the gh1 tile */
-        sb_acc acc = {0.0f, 0.0f, 0.0f, 0.0f};
+        hm_acc4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int s = 0; s < SB_K1; ++s) {
-            uint4 a = s_gh[sb_slot(at + tap_at[s], g & 1)];
+            uint4 a = s_gh[hm_slot(at + tap_at[s], g & 1)];
             if (s == SB_K1 - 1 && g >= 2) a = make_uint4(0, 0, 0, 0);
-            acc = sb_mfma<DT>(a, wt[s], acc);
+            acc = hm_mfma<DT>(a, wt[s], acc);
         }
         /* register i is pixel col + 4g + i of the row, channel p */
         const int y = y0 + row, x = x0 + col + 4 * g;
@@ -265,7 +231,7 @@ __global__ __launch_bounds__(256) void k_stem_bwd_data(const void* __restrict__ 
                     if (x + i < W) m[i] = midn[(size_t)p * plane + (size_t)y * W + x + i];
             }
 #pragma unroll
-            for (int i = 0; i < 4; ++i) r[i] = x + i < W && cb_widen<DT>(m[i]) > 0.0f ? cb_round<DT>(acc[i]) : 0u;
+            for (int i = 0; i < 4; ++i) r[i] = x + i < W && hm_widen<DT>(m[i]) > 0.0f ? hm_round<DT>(acc[i]) : 0u;
             if (x + 3 < W) {
                 const uint2 v = make_uint2(r[0] | (r[1] << 16), r[2] | (r[3] << 16));
                 __builtin_memcpy(gh0_out + e, &v, 8);
@@ -276,7 +242,7 @@ __global__ __launch_bounds__(256) void k_stem_bwd_data(const void* __restrict__ 
             }
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) sum0 = sum0 + (double)cb_widen<DT>((uint16_t)r[i]);
+        for (int i = 0; i < 4; ++i) sum0 = sum0 + (double)hm_widen<DT>((uint16_t)r[i]);
     }
     /* thread tid holds channel tid & 15: the same sum over tid >> 4 = 4 wave + g */
     sb_tile_sum(sum0, s_sum, shift0_part + ((size_t)n * 16) * tiles + blockIdx.x, tiles, shift0_part != nullptr);
@@ -320,9 +286,9 @@ __global__ __launch_bounds__(256) void k_stem_bwd_weight(const uint8_t* __restri
             live[i] = t < SW_TILES && 16 * (t - 9) + p < 147;
         }
     }
-    sb_acc acc[5];
+    hm_acc4 acc[5];
 #pragma unroll
-    for (int i = 0; i < 5; ++i) acc[i] = sb_acc{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int i = 0; i < 5; ++i) acc[i] = hm_acc4{0.0f, 0.0f, 0.0f, 0.0f};
 
     /* A pixel pair of a row, from `src` (a row of a plane, or null for a row outside the image) shifted by `shift`
      * pixels: the address is clamped into the row and the bits are masked. */
@@ -384,7 +350,7 @@ __global__ __launch_bounds__(256) void k_stem_bwd_weight(const uint8_t* __restri
                 const int row = (is_g1[i] ? SW_ROW_MID + ((y + b_ky[i]) % 3) * 48 : SW_ROW_X + ((y + b_ky[i]) % 7) * 21) + b_inner[i];
                 uint4 b = *(const uint4*)(s_rows + row * SW_RS + at);
                 if (!live[i]) b = make_uint4(0, 0, 0, 0);
-                acc[i] = sb_mfma<DT>(a, b, acc[i]);
+                acc[i] = hm_mfma<DT>(a, b, acc[i]);
             }
         }
     }
@@ -408,7 +374,6 @@ __global__ __launch_bounds__(256) void k_stem_bwd_weight(const uint8_t* __restri
     }
 }
 
-static size_t sb_align(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
 static int sb_tiles(int H, int W) { return ((H + SB_ROWS - 1) / SB_ROWS) * ((W + SB_COLS - 1) / SB_COLS); }
 static int sb_chunks(int H, int W) { return ((H + SW_BAND - 1) / SW_BAND) * ((W + SW_SEG - 1) / SW_SEG); }
 
@@ -420,17 +385,17 @@ static sb_scratch sb_layout(int n, int H, int W, int Cn) {
     const size_t P = (size_t)H * W, tiles = sb_tiles(H, W), chunks = (size_t)n * sb_chunks(H, W);
     sb_scratch s;
     s.gh1 = 0;
-    s.gh0 = s.gh1 + sb_align((size_t)n * 16 * P * 2);
-    s.packed = s.gh0 + sb_align((size_t)n * 16 * P * 2);
-    s.shift1 = s.packed + sb_align((size_t)SB_K1 * 64 * 16);
-    s.shift0 = s.shift1 + sb_align((size_t)n * 16 * tiles * 8);
-    s.gsum1 = s.shift0 + sb_align((size_t)n * 16 * tiles * 8);
-    s.gsum0 = s.gsum1 + sb_align((size_t)16 * 16 * 9 * 8);
-    s.part1 = s.gsum0 + sb_align((size_t)16 * 3 * 49 * 8);
-    s.part0 = s.part1 + sb_align(chunks * 16 * 16 * 9 * 4);
-    s.gout = s.part0 + sb_align(chunks * 16 * 3 * 49 * 4);
-    s.packed_next = s.gout + (Cn ? sb_align((size_t)n * 16 * P * 2) : 0);
-    s.end = s.packed_next + sb_align((size_t)(Cn / 32) * 9 * 64 * 16);
+    s.gh0 = s.gh1 + cb_align16((size_t)n * 16 * P * 2);
+    s.packed = s.gh0 + cb_align16((size_t)n * 16 * P * 2);
+    s.shift1 = s.packed + cb_align16((size_t)SB_K1 * 64 * 16);
+    s.shift0 = s.shift1 + cb_align16((size_t)n * 16 * tiles * 8);
+    s.gsum1 = s.shift0 + cb_align16((size_t)n * 16 * tiles * 8);
+    s.gsum0 = s.gsum1 + cb_align16((size_t)16 * 16 * 9 * 8);
+    s.part1 = s.gsum0 + cb_align16((size_t)16 * 3 * 49 * 8);
+    s.part0 = s.part1 + cb_align16(chunks * 16 * 16 * 9 * 4);
+    s.gout = s.part0 + cb_align16(chunks * 16 * 3 * 49 * 4);
+    s.packed_next = s.gout + (Cn ? cb_align16((size_t)n * 16 * P * 2) : 0);
+    s.end = s.packed_next + cb_align16((size_t)(Cn / 32) * 9 * 64 * 16);
     return s;
 }
 
@@ -457,55 +422,45 @@ extern "C" hipError_t isk_launch_stem_backward(const is_stem_backward_args* a, h
     double* const gsum0 = (double*)(scratch + lay.gsum0);
     float* const part1 = (float*)(scratch + lay.part1);
     float* const part0 = (float*)(scratch + lay.part0);
-    const bool f16 = a->dtype == IS_HEAD_F16;
-    if (!f16 && a->dtype != IS_HEAD_BF16) return hipErrorInvalidValue;
+    if (a->dtype != IS_HEAD_F16 && a->dtype != IS_HEAD_BF16) return hipErrorInvalidValue;
     const bool contract = a->d_grad_weight0 || a->d_grad_scale0 || a->d_grad_weight1 || a->d_grad_scale1;
     /* the gradient with respect to out: dY, or g_out computed into the scratch in the half dtype */
     const void* dy = a->d_grad_out;
     int dy_f32 = a->grad_out_dtype == IS_HEAD_F32;
     long long dy_stride = a->grad_image_stride;
 
-#define SB_BOTH(CALL_F16, CALL_BF16) do { if (f16) { CALL_F16; } else { CALL_BF16; } } while (0)
-    SB_BOTH(hipLaunchKernelGGL(k_stem_bwd_pack_t<IS_HEAD_F16>, dim3((SB_K1 * 64 * 8 + 255) / 256), dim3(256), 0, stream,
-                               a->d_w1, a->d_scale1, packed),
-            hipLaunchKernelGGL(k_stem_bwd_pack_t<IS_HEAD_BF16>, dim3((SB_K1 * 64 * 8 + 255) / 256), dim3(256), 0, stream,
-                               a->d_w1, a->d_scale1, packed));
+    hm_dispatch(a->dtype, [&](auto dt) {
+        hipLaunchKernelGGL(k_stem_bwd_pack_t<dt()>, dim3((SB_K1 * 64 * 8 + 255) / 256), dim3(256), 0, stream, a->d_w1,
+                           a->d_scale1, packed);
+    });
     if (Cn) {
         uint16_t* const gout = (uint16_t*)(scratch + lay.gout);
         uint16_t* const packed_next = (uint16_t*)(scratch + lay.packed_next);
         const int total = (Cn / 32) * 9 * 512, Ho = (H + 1) / 2, Wo = (W + 1) / 2;
         const dim3 grid((Wo + 15) / 16, (Ho + 3) / 4, n);
-        SB_BOTH(hipLaunchKernelGGL(k_stem_bwd_pack_next<IS_HEAD_F16>, dim3((total + 255) / 256), dim3(256), 0, stream,
-                                   a->d_weight_next, a->d_scale_next, packed_next, total),
-                hipLaunchKernelGGL(k_stem_bwd_pack_next<IS_HEAD_BF16>, dim3((total + 255) / 256), dim3(256), 0, stream,
-                                   a->d_weight_next, a->d_scale_next, packed_next, total));
-        SB_BOTH(hipLaunchKernelGGL(k_stem_bwd_gout<IS_HEAD_F16>, grid, dim3(256), 0, stream, (const uint16_t*)a->d_grad_next,
-                                   (const uint4*)packed_next, gout, Cn, H, W, Ho, Wo),
-                hipLaunchKernelGGL(k_stem_bwd_gout<IS_HEAD_BF16>, grid, dim3(256), 0, stream, (const uint16_t*)a->d_grad_next,
-                                   (const uint4*)packed_next, gout, Cn, H, W, Ho, Wo));
+        hm_dispatch(a->dtype, [&](auto dt) {
+            hipLaunchKernelGGL(k_stem_bwd_pack_next<dt()>, dim3((total + 255) / 256), dim3(256), 0, stream,
+                               a->d_weight_next, a->d_scale_next, packed_next, total);
+        });
+        hm_dispatch(a->dtype, [&](auto dt) {
+            hipLaunchKernelGGL(k_stem_bwd_gout<dt()>, grid, dim3(256), 0, stream, (const uint16_t*)a->d_grad_next,
+                               (const uint4*)packed_next, gout, Cn, H, W, Ho, Wo);
+        });
         dy = gout, dy_f32 = 0, dy_stride = 16LL * H * W;
     }
-    {
+    hm_dispatch(a->dtype, [&](auto dt) {
         const dim3 grid((unsigned)tiles, n); /* at most 512 * 2048 by 65535 */
         double* const sp1 = a->d_grad_shift1 ? shift1 : nullptr;
         double* const sp0 = a->d_grad_shift0 ? shift0 : nullptr;
-        SB_BOTH(hipLaunchKernelGGL(k_stem_bwd_data<IS_HEAD_F16>, grid, dim3(256), 0, stream, dy, dy_f32,
-                                   dy_stride, (const uint16_t*)a->d_out, (const uint16_t*)a->d_mid,
-                                   (const uint4*)packed, gh1, gh0, sp1, sp0, H, W, tiles_x),
-                hipLaunchKernelGGL(k_stem_bwd_data<IS_HEAD_BF16>, grid, dim3(256), 0, stream, dy, dy_f32,
-                                   dy_stride, (const uint16_t*)a->d_out, (const uint16_t*)a->d_mid,
-                                   (const uint4*)packed, gh1, gh0, sp1, sp0, H, W, tiles_x));
-    }
-    if (contract) {
+        hipLaunchKernelGGL(k_stem_bwd_data<dt()>, grid, dim3(256), 0, stream, dy, dy_f32, dy_stride, (const uint16_t*)a->d_out,
+                           (const uint16_t*)a->d_mid, (const uint4*)packed, gh1, gh0, sp1, sp0, H, W, tiles_x);
+    });
+    if (contract) hm_dispatch(a->dtype, [&](auto dt) {
         const dim3 grid((unsigned)chunks_image, n); /* at most 1024 * 512 by 65535 */
-        SB_BOTH(hipLaunchKernelGGL(k_stem_bwd_weight<IS_HEAD_F16>, grid, dim3(256), 0, stream, (const uint8_t*)a->d_image,
-                                   (const uint16_t*)a->d_lut, (const uint16_t*)a->d_mid, (const uint16_t*)gh1,
-                                   (const uint16_t*)gh0, part1, part0, H, W, segs),
-                hipLaunchKernelGGL(k_stem_bwd_weight<IS_HEAD_BF16>, grid, dim3(256), 0, stream, (const uint8_t*)a->d_image,
-                                   (const uint16_t*)a->d_lut, (const uint16_t*)a->d_mid, (const uint16_t*)gh1,
-                                   (const uint16_t*)gh0, part1, part0, H, W, segs));
-    }
-#undef SB_BOTH
+        hipLaunchKernelGGL(k_stem_bwd_weight<dt()>, grid, dim3(256), 0, stream, (const uint8_t*)a->d_image,
+                           (const uint16_t*)a->d_lut, (const uint16_t*)a->d_mid, (const uint16_t*)gh1, (const uint16_t*)gh0,
+                           part1, part0, H, W, segs);
+    });
     if (a->d_grad_weight1 || a->d_grad_scale1)
         isk_launch_conv_bwd_reduce(part1, chunks, 16, 16, 9, a->d_scale1, a->d_grad_weight1, a->d_grad_scale1 ? gsum1 : nullptr, stream);
     if (a->d_grad_weight0 || a->d_grad_scale0)

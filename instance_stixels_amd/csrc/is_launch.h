@@ -270,7 +270,6 @@ void isk_launch_conv_bwd_channel(int dtype, const double* gsum, const float* wei
 void isk_launch_conv_bwd_data_s2(const is_conv_bn_stride_backward_args* a, const void* gh, const void* packed,
                                  hipStream_t stream);
 void isk_launch_conv_bwd_weight_s2(const is_conv_bn_stride_backward_args* a, const void* gh, float* part, hipStream_t stream);
-long long isk_conv_bwd_weight_s2_grid(int n_images, int channels_in, int channels_out, int rows_out);
 
 /* is_k_stem.hip */
 size_t isk_stem_packed_bytes(void);
