@@ -9,10 +9,21 @@
 #define PREP_MAXR 9 /* rows per thread whose fp32 prefixes are held in registers: H + 1 <= 9 * 256 */
 
 /* LDS stride of a segmentation channel: H/8 + 1 prefix entries, rounded up to 16 bytes */
-__host__ __device__ static inline int prep_seg_stride(int H) { return (((H >> 3) + 1) + 3) & ~3; }
+__host__ __device__ static constexpr int prep_seg_stride(int H) { return (((H >> 3) + 1) + 3) & ~3; }
 /* leaves of the fp32 scan trees: H when H is a power of two (then P2 = 2H), else P2 */
-__host__ __device__ static inline int prep_scan_leaves(int H, int P2) {
+__host__ __device__ static constexpr int prep_scan_leaves(int H, int P2) {
     return ((H & (H - 1)) == 0 && P2 == 2 * H && H >= 16) ? H : P2;
+}
+/* DevParams::P2 of a context of H rows: the smallest power of two >= H + 1 (is_ctx_create), and the log2 of one */
+__host__ __device__ static constexpr int prep_rows_pow2(int H) {
+    int p = 1;
+    while (p < H + 1) p <<= 1;
+    return p;
+}
+__host__ __device__ static constexpr int prep_log2(int pow2) {
+    int l = 0;
+    while ((1 << l) < pow2) l++;
+    return l;
 }
 
 /* Exclusive prefix of index i (0 <= i < n) with the association of the reference's
@@ -128,14 +139,36 @@ __device__ __forceinline__ PrepLds prep_lds(char* smem, int NP, int CH, int SS) 
     int64_t* wave = (int64_t*)(seg + CH * SS);
     return {d, d + NP, seg, wave, (float*)(wave + 4), (float*)(wave + 4) + 8};
 }
+/* bytes of that carve-up */
+__host__ __device__ static constexpr size_t prep_lds_carve_bytes(int NP, int CH, int SS) {
+    return sizeof(float) * (size_t)NP * 3 + sizeof(int32_t) * (size_t)CH * SS + PREP_LDS_TAIL;
+}
 extern "C" size_t isk_prepare_lds_bytes(const DevParams* P) {
-    return sizeof(float) * (size_t)prep_scan_leaves(P->H, P->P2) * 3 +
-           sizeof(int32_t) * (size_t)P->CH * prep_seg_stride(P->H) + PREP_LDS_TAIL;
+    return prep_lds_carve_bytes(prep_scan_leaves(P->H, P->P2), P->CH, prep_seg_stride(P->H));
 }
 
-/* What the stages of one column share: its shape, which column it is, who owns which rows, where its data lie. */
-struct PrepCol {
-    int H, K, CH;
+/* What the stages of one column share: its shape, which column it is, who owns which rows, where its data lie.
+ * PrepCol<HC>, HC > 0: a kernel compiled for HC rows -- everything that follows from the row count alone is a constant
+ * of the type (the same names, so the stages read c.H, c.NP, .. either way); PrepCol<0>: the rows at run time. */
+struct PrepColWhere {
+    int K, CH;
+    int colg, img, col, tid;
+    int r_lo;            /* instance sums: thread t owns rows [t * R, t * R + R) */
+    const int32_t* scol; /* [CH][P2S]  its segmentation channels */
+    RowRec* rcol;        /* [H + 1]    its records               */
+};
+template <int HC>
+struct PrepCol : PrepColWhere {
+    static constexpr int H = HC, SS = prep_seg_stride(HC);
+    static constexpr int P2 = prep_rows_pow2(HC), NP = prep_scan_leaves(HC, P2), LNP = prep_log2(NP);
+    static constexpr int R = (HC + PREP_THREADS - 1) / PREP_THREADS;
+    static constexpr bool regs = (HC + 1) <= PREP_MAXR * PREP_THREADS;
+    /* live slots of PrepPlanes and blocks of the epilogue: rows 0 .. H */
+    static constexpr int slots = regs ? (HC + 1 + PREP_THREADS - 1) / PREP_THREADS : 0;
+};
+template <>
+struct PrepCol<0> : PrepColWhere {
+    int H;
     /* LDS stride of a segmentation channel: only its first H/8 + 1 entries matter (an exclusive prefix at index <= H/8
      * never sees the zero padding up to P2S), and 21 channels of P2S = 256 entries were 21.5 of the kernel's 46 KB of
      * LDS: with 132 the CU holds four workgroups, not three */
@@ -145,24 +178,30 @@ struct PrepCol {
      * as in a tree over H leaves, and index H is the left child of the root = the root of the H-leaf tree.  The tree is
      * then built over NP = H leaves: identical sums, half the LDS (12 instead of 24 KB at H = 1024). */
     int NP, LNP;
-    int colg, img, col, tid;
-    int R, r_lo; /* instance sums: thread t owns rows [t * R, t * R + R) */
+    int R; /* rows per thread of the instance sums (r_lo) */
     /* fp32 prefixes: thread t owns rows t + k * PREP_THREADS.  regs: it keeps them in registers (PrepPlanes) and the
      * records get {G, K, S, V} as ONE 16-byte store per row at the end, block by block (prep_store_records); else each
      * prefix goes to its record field at once */
     bool regs;
-    const int32_t* scol; /* [CH][P2S]  its segmentation channels */
-    RowRec* rcol;        /* [H + 1]    its records               */
+    static constexpr int slots = PREP_MAXR; /* each guarded by the row count */
 };
-__device__ __forceinline__ PrepCol prep_col(const DevParams& P, int colg, const int32_t* seg, RowRec* recs) {
-    PrepCol c;
-    c.H = P.H, c.K = P.K, c.CH = P.CH;
-    c.SS = prep_seg_stride(c.H);
-    c.NP = prep_scan_leaves(c.H, P.P2);
-    c.LNP = (c.NP == P.P2) ? P.log2P2 : P.log2P2 - 1;
+/* the shapes a kernel is compiled for: the benchmarked row counts (the headline shape, ref_shape_784x1792) */
+static_assert(PrepCol<1024>::NP == 1024 && PrepCol<1024>::LNP == 10 && PrepCol<1024>::slots == 5, "1024 rows");
+static_assert(PrepCol<784>::NP == 1024 && PrepCol<784>::LNP == 10 && PrepCol<784>::slots == 4, "784 rows");
+template <int HC>
+__device__ __forceinline__ PrepCol<HC> prep_col(const DevParams& P, int colg, const int32_t* seg, RowRec* recs) {
+    PrepCol<HC> c;
+    if constexpr (HC == 0) {
+        c.H = P.H;
+        c.SS = prep_seg_stride(c.H);
+        c.NP = prep_scan_leaves(c.H, P.P2);
+        c.LNP = (c.NP == P.P2) ? P.log2P2 : P.log2P2 - 1;
+        c.R = (c.H + PREP_THREADS - 1) / PREP_THREADS;
+        c.regs = (c.H + 1) <= PREP_MAXR * PREP_THREADS;
+    }
+    c.K = P.K, c.CH = P.CH;
     c.colg = colg, c.img = colg / P.C, c.col = colg % P.C, c.tid = threadIdx.x;
-    c.R = (c.H + PREP_THREADS - 1) / PREP_THREADS, c.r_lo = c.tid * c.R;
-    c.regs = (c.H + 1) <= PREP_MAXR * PREP_THREADS;
+    c.r_lo = c.tid * c.R;
     c.scol = seg + (size_t)colg * c.CH * P.P2S;
     c.rcol = recs + (size_t)colg * (c.H + 1);
     return c;
@@ -170,7 +209,8 @@ __device__ __forceinline__ PrepCol prep_col(const DevParams& P, int colg, const 
 
 /* ---- the column inputs into LDS with 16-byte loads (H is a multiple of 8; the segmentation column is
  * 16-byte aligned when P2S is a multiple of 4) */
-__device__ __forceinline__ void prep_stage_column(const DevParams& P, const PrepLds& L, const PrepCol& c,
+template <int HC>
+__device__ __forceinline__ void prep_stage_column(const DevParams& P, const PrepLds& L, const PrepCol<HC>& c,
                                                   const float* __restrict__ joined) {
     const int H = c.H, SS = c.SS, CH = c.CH, P2S = P.P2S, tid = c.tid;
     const float4* d4 = reinterpret_cast<const float4*>(joined + (size_t)c.colg * H);
@@ -197,7 +237,8 @@ __device__ __forceinline__ void prep_stage_column(const DevParams& P, const Prep
 /* ---- fn windows of the pairwise phase 1 (is_device.h, IS_P1_WIN): per 64-row tile the smallest valid
  * disparity, rounded down to a multiple of 4 columns (16-byte loads), one below for the rounding of
  * the prefix sums a mean is computed from.  Reads L.d. */
-__device__ __forceinline__ void prep_fn_windows(const DevParams& P, const PrepLds& L, const PrepCol& c) {
+template <int HC>
+__device__ __forceinline__ void prep_fn_windows(const DevParams& P, const PrepLds& L, const PrepCol<HC>& c) {
     if (!(IS_P1_WINDOWED(P.D) && P.win_lo != nullptr)) return;
     const int lane = c.tid & 63, wv = c.tid >> 6;
     for (int t = wv; t < P.ntiles; t += PREP_THREADS / 64) {
@@ -261,7 +302,8 @@ __device__ __forceinline__ void instance_centre_add(const DevParams& P, int col,
 /* ---- instance sums of this thread's rows and the three checks of the FAST encodings (RowRec).  Returns `slow`, the
  * same in every thread: the column needs the generic (int64 / IEEE-division) DP path; `base`: the exclusive prefixes of
  * the four sums at row r_lo; L.tot[0]: the column totals of the squares.  L.wave: block_sum_u64, then the four scans. */
-__device__ __forceinline__ int prep_instance_sums(const DevParams& P, const PrepLds& L, const PrepCol& c,
+template <int HC>
+__device__ __forceinline__ int prep_instance_sums(const DevParams& P, const PrepLds& L, const PrepCol<HC>& c,
                                                   int* __restrict__ col_flags, int* __restrict__ n_generic,
                                                   InstSums& base) {
     const int H = c.H, K = c.K, SS = c.SS, tid = c.tid;
@@ -324,7 +366,8 @@ __device__ __forceinline__ int prep_instance_sums(const DevParams& P, const Prep
  * thread: the branch-and-bound precondition fails.  The non-instance offset term is >= 0 and monotone when no
  * squared entry is negative as int32 (the reference squares in wrapping int32) and the full-resolution total stays
  * below 2^31.  L.wave: block_sum_u64. */
-__device__ __forceinline__ int prep_square_offsets(const PrepLds& L, const PrepCol& c) {
+template <int HC>
+__device__ __forceinline__ int prep_square_offsets(const PrepLds& L, const PrepCol<HC>& c) {
     int32_t* off = L.seg + c.K * c.SS; /* offy, then offx */
     for (int i = c.tid; i < 2 * c.SS; i += PREP_THREADS) {
         const uint32_t x = (uint32_t)off[i];
@@ -345,7 +388,8 @@ __device__ __forceinline__ int prep_square_offsets(const PrepLds& L, const PrepC
 
 /* ---- every channel of L.seg becomes its exclusive prefix at 1/8 resolution, in place (:462-469); integer, so any
  * order is exact.  One wave per channel (round robin): lane l owns `per` consecutive entries of the SS */
-__device__ __forceinline__ void prep_class_prefixes(const PrepLds& L, const PrepCol& c) {
+template <int HC>
+__device__ __forceinline__ void prep_class_prefixes(const PrepLds& L, const PrepCol<HC>& c) {
     const int SS = c.SS, lane = c.tid & 63, wv = c.tid >> 6, per = (SS + 63) >> 6;
     for (int chn = wv; chn < c.CH; chn += PREP_THREADS / 64) {
         int32_t* ch = L.seg + chn * SS;
@@ -378,7 +422,8 @@ __device__ __forceinline__ void prep_class_prefixes(const PrepLds& L, const Prep
  * copy[v] where a compact copy is wanted (the S / V copies of the pairwise phase 2).  The caller puts a barrier in
  * front of the next fill. */
 struct PrepPlanes { float G[PREP_MAXR], K[PREP_MAXR], S[PREP_MAXR], V[PREP_MAXR]; }; /* this thread's prefixes */
-__device__ __forceinline__ void prep_scan_plane(const PrepLds& L, const PrepCol& c, float (&p)[PREP_MAXR],
+template <int HC>
+__device__ __forceinline__ void prep_scan_plane(const PrepLds& L, const PrepCol<HC>& c, float (&p)[PREP_MAXR],
                                                 float RowRec::*field, float* __restrict__ copy) {
     const int NP = c.NP, LNP = c.LNP, H = c.H;
     __syncthreads();
@@ -388,7 +433,7 @@ __device__ __forceinline__ void prep_scan_plane(const PrepLds& L, const PrepCol&
     };
     if (c.regs) {
 #pragma unroll
-        for (int k = 0; k < PREP_MAXR; k++) {
+        for (int k = 0; k < c.slots; k++) {
             const int v = c.tid + k * PREP_THREADS;
             if (v <= H) { p[k] = prefix_at(v); if (copy) copy[v] = p[k]; }
         }
@@ -402,7 +447,8 @@ __device__ __forceinline__ void prep_scan_plane(const PrepLds& L, const PrepCol&
 }
 
 /* S: disparity (valid-masked when invalid >= 0, :382-389) */
-__device__ __forceinline__ void prep_fill_S(const DevParams& P, const PrepLds& L, const PrepCol& c) {
+template <int HC>
+__device__ __forceinline__ void prep_fill_S(const DevParams& P, const PrepLds& L, const PrepCol<HC>& c) {
     for (int i = c.tid; i < c.NP; i += PREP_THREADS) {
         float x = 0.0f;
         if (i < c.H) {
@@ -418,12 +464,14 @@ __device__ __forceinline__ void prep_fill_S(const DevParams& P, const PrepLds& L
     }
 }
 /* V: valid count (only with an invalid-disparity value) */
-__device__ __forceinline__ void prep_fill_V(const DevParams& P, const PrepLds& L, const PrepCol& c) {
+template <int HC>
+__device__ __forceinline__ void prep_fill_V(const DevParams& P, const PrepLds& L, const PrepCol<HC>& c) {
     for (int i = c.tid; i < c.NP; i += PREP_THREADS) L.pyr[i] = (i < c.H) ? (float)(L.d[i] != P.invalid) : 0.0f;
 }
 /* G: ground data cost, +inf at / above the horizon (:435-446).  Returns (sum |x|, min x) over the finite rows: the
  * slack of the ground data term */
-__device__ __forceinline__ float2 prep_fill_G(const DevParams& P, const PrepLds& L, const PrepCol& c,
+template <int HC>
+__device__ __forceinline__ float2 prep_fill_G(const DevParams& P, const PrepLds& L, const PrepCol<HC>& c,
                                               const float* __restrict__ ground /*[img][3][H]*/, int vhor) {
     const float* gfun = ground + (size_t)c.img * 3 * c.H;
     const float* gnorm = gfun + c.H;
@@ -440,7 +488,8 @@ __device__ __forceinline__ float2 prep_fill_G(const DevParams& P, const PrepLds&
     return block_sum_min(g_abs, g_min, L.red);
 }
 /* K: sky data cost, 0 below the horizon (:424-433).  Returns (sum |x|, min x) */
-__device__ __forceinline__ float2 prep_fill_K(const DevParams& P, const PrepLds& L, const PrepCol& c, int vhor) {
+template <int HC>
+__device__ __forceinline__ float2 prep_fill_K(const DevParams& P, const PrepLds& L, const PrepCol<HC>& c, int vhor) {
     float k_abs = 0.0f, k_min = 0.0f;
     for (int i = c.tid; i < c.NP; i += PREP_THREADS) {
         float x = 0.0f;
@@ -455,7 +504,8 @@ __device__ __forceinline__ float2 prep_fill_K(const DevParams& P, const PrepLds&
 /* ---- PruneRec of the column (thread 0): see is_device.h.  A prefix difference P[a] - P[b] of per-row values x >= -nu
  * with sum|x| = T is >= -(nu * H + gamma2 * T); NaN anywhere makes the slack NaN, and a NaN slack makes every bound
  * NaN, which never passes the `>` test: no pruning.  Reads L.tot[0]. */
-__device__ __forceinline__ void prep_prune_rec(const DevParams& P, const PrepLds& L, const PrepCol& c, float2 g_red,
+template <int HC>
+__device__ __forceinline__ void prep_prune_rec(const DevParams& P, const PrepLds& L, const PrepCol<HC>& c, float2 g_red,
                                                float2 k_red, int slow, int nic_bad, PruneRec* __restrict__ prune) {
     if (c.tid != 0) return;
     const float safe = 1.0f + 0x1p-10f;
@@ -501,7 +551,8 @@ __device__ __forceinline__ void store_instance_prefix(RowRec* o, int slow, const
 /* The instance prefixes of this thread's rows [r_lo, r_lo + R): the exclusive prefix at those indices; the owner of
  * row H - 1 also writes index H (the total).  (The raw offsets from the input tensor: the LDS copies have been squared
  * in place.) */
-__device__ __forceinline__ void prep_store_instance_rows(const DevParams& P, const PrepCol& c, int slow,
+template <int HC>
+__device__ __forceinline__ void prep_store_instance_rows(const DevParams& P, const PrepCol<HC>& c, int slow,
                                                          const InstSums& base) {
     const int H = c.H;
     const int32_t* offy = c.scol + c.K * P.P2S;
@@ -518,7 +569,8 @@ __device__ __forceinline__ void prep_store_instance_rows(const DevParams& P, con
  * block kb: the full-resolution prefix at row 8 kb + m is ps[kb] * 8 + (ps[kb + 1] - ps[kb]) * m in wrapping uint32
  * arithmetic, so the two table entries are read once per block and the rows follow by repeated addition -- an eighth of
  * the LDS reads and a fifth of the instructions of one (row, chunk) item per thread. */
-__device__ __forceinline__ void prep_store_class_item(const PrepLds& L, const PrepCol& c, int slow, int kb, int q) {
+template <int HC>
+__device__ __forceinline__ void prep_store_class_item(const PrepLds& L, const PrepCol<HC>& c, int slow, int kb, int q) {
     const int SS = c.SS, K = c.K;
     const int kn = min(kb + 1, SS - 1); /* (the last block has one row: its increment is never used) */
     uint32_t cur[4], dif[4];
@@ -562,7 +614,8 @@ __device__ __forceinline__ void prep_store_class_item(const PrepLds& L, const Pr
  * removed: the records staged 64 rows at a time in LDS and stored as whole 128-byte lines, eight lanes per record -- 1.53
  * instead of 1.21 ms for the column blocks of a batch of 64: the 34 extra barriers cost more than the partial lines do;
  * the kernel is bound by its LDS / VALU work, not by its 2.15 GB of stores) */
-__device__ __forceinline__ void prep_store_records(const DevParams& P, const PrepLds& L, const PrepCol& c, int slow,
+template <int HC>
+__device__ __forceinline__ void prep_store_records(const DevParams& P, const PrepLds& L, const PrepCol<HC>& c, int slow,
                                                    const InstSums& base, const PrepPlanes& pl) {
     const int H = c.H, tid = c.tid;
     if (c.regs) {
@@ -573,7 +626,7 @@ __device__ __forceinline__ void prep_store_records(const DevParams& P, const Pre
          * against 4 MB of L2 -- lines left the L2 before their last piece arrived). */
         static_assert(PREP_THREADS % 64 == 0, "a block of the epilogue: one row per thread, whole waves");
 #pragma unroll
-        for (int k = 0; k < PREP_MAXR; k++) {
+        for (int k = 0; k < c.slots; k++) {
             const int row0 = k * PREP_THREADS;
             if (row0 <= H) {
                 const int v = row0 + tid;
@@ -605,7 +658,9 @@ __device__ __forceinline__ void prep_store_records(const DevParams& P, const Pre
 }
 
 /* One column of a call: its records (RowRec), PruneRec, col_flags entry and fn windows.  The stages in order, with the
- * barriers between them and the LDS each one takes over (PrepLds). */
+ * barriers between them and the LDS each one takes over (PrepLds).  HC > 0: compiled for a context of HC rows (PrepCol);
+ * 0: the rows at run time. */
+template <int HC>
 __device__ __forceinline__ void prepare_columns_body(
     const DevParams& P, const int colg, char* smem, const float* __restrict__ joined,
     const int32_t* __restrict__ seg, const float* __restrict__ ground /*[img][3][H]*/,
@@ -619,7 +674,7 @@ __device__ __forceinline__ void prepare_columns_body(
         P.lut_ready[colg] = 0; /* (the fused LUT units of the DP launch count up) */
         if (colg == 0 && P.lutf_bad != nullptr) *P.lutf_bad = 0;
     }
-    const PrepCol c = prep_col(P, colg, seg, recs);
+    const PrepCol<HC> c = prep_col<HC>(P, colg, seg, recs);
     const PrepLds L = prep_lds(smem, c.NP, c.CH, c.SS);
     const int vhor = vhor_arr[c.img];
     const int H = c.H, tid = c.tid;
@@ -661,14 +716,15 @@ __device__ __forceinline__ void prepare_columns_body(
     prep_store_records(P, L, c, slow, base, pl); /* no barrier: reads L.seg and registers only */
 }
 
+template <int HC>
 __global__ __launch_bounds__(PREP_THREADS) void k_prepare_columns(
     const DevParams P, const float* __restrict__ joined, const int32_t* __restrict__ seg,
     const float* __restrict__ ground, const int* __restrict__ vhor_arr, RowRec* __restrict__ recs,
     int* __restrict__ col_flags, float* __restrict__ sv_arr, PruneRec* __restrict__ prune,
     int* __restrict__ n_generic, int* __restrict__ path_bad) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    prepare_columns_body(P, (int)blockIdx.x, smem, joined, seg, ground, vhor_arr, recs, col_flags, sv_arr,
-                         prune, n_generic, path_bad);
+    prepare_columns_body<HC>(P, (int)blockIdx.x, smem, joined, seg, ground, vhor_arr, recs, col_flags, sv_arr,
+                             prune, n_generic, path_bad);
 }
 
 /* ====================================================================================== */
@@ -814,8 +870,8 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prepare_fused(
         if (unit < ncols * fn_blocks)
             object_lut_body<CARRY>(P, unit / fn_blocks, unit % fn_blocks, (int)(threadIdx.x & 63), joined, cost_T, lut);
     } else {
-        prepare_columns_body(P, col_b, smem, joined, seg, ground, vhor_arr, recs,
-                             col_flags, sv_arr, prune, n_generic, path_bad);
+        prepare_columns_body<0>(P, col_b, smem, joined, seg, ground, vhor_arr, recs,
+                                col_flags, sv_arr, prune, n_generic, path_bad);
     }
 }
 
@@ -946,6 +1002,23 @@ __global__ void k_prior_tables(const DevParams P, const float* __restrict__ grou
     priors[idx] = r;
 }
 
+/* k_prepare_columns of a context.  A kernel compiled for HC rows serves the contexts of HC rows: the host
+ * checks that what it holds as constants -- the rows, the tree over them, the LDS carve-up -- is what DevParams and
+ * isk_prepare_lds_bytes say (is_ctx_create derives P2 from the rows, so it is); any other shape takes the run-time
+ * body. */
+typedef void (*prep_columns_kernel_t)(const DevParams, const float*, const int32_t*, const float*, const int*, RowRec*,
+                                      int*, float*, PruneRec*, int*, int*);
+template <int HC>
+static bool prep_compiled_for(const DevParams* P) {
+    return P->H == HC && P->P2 == PrepCol<HC>::P2 && P->log2P2 == prep_log2(PrepCol<HC>::P2) &&
+           prep_lds_carve_bytes(PrepCol<HC>::NP, P->CH, PrepCol<HC>::SS) == isk_prepare_lds_bytes(P);
+}
+static prep_columns_kernel_t prep_columns_kernel(const DevParams* P) {
+    if (prep_compiled_for<1024>(P)) return k_prepare_columns<1024>;
+    if (prep_compiled_for<784>(P)) return k_prepare_columns<784>;
+    return k_prepare_columns<0>;
+}
+
 extern "C" {
 
 hipError_t isk_launch_lut_repair(const DevParams* P, int ncols, const float* joined, const float* cost_T, float* lutT,
@@ -993,7 +1066,7 @@ hipError_t isk_launch_prepare(const DevParams* P, const CallPlan* plan, const Ca
      * k_lut_carry's -- both kernels only read `joined`, kernel boundaries order them in front of the DP (measured in
      * both orders: 952 + 145 and 958 + 141 us per 64 frames) */
     if (!plan->prepare_lut || carry_lds) {
-        hipLaunchKernelGGL(k_prepare_columns, dim3(ncols), dim3(PREP_THREADS), isk_prepare_lds_bytes(P), stream, *P,
+        hipLaunchKernelGGL(prep_columns_kernel(P), dim3(ncols), dim3(PREP_THREADS), isk_prepare_lds_bytes(P), stream, *P,
                            b->joined, b->seg, b->ground, b->vhor, b->recs, b->col_flags, sv, b->prune, b->n_generic,
                            b->path_bad);
         const hipError_t e = hipGetLastError();
@@ -1021,7 +1094,7 @@ hipError_t isk_launch_priors(const DevParams* P, const float* ground, PriorRec* 
 }
 
 hipError_t isk_set_lds_prepare(const DevParams* P) {
-    const void* kernels[3] = {(const void*)k_prepare_columns, (const void*)k_prepare_fused<false>,
+    const void* kernels[3] = {(const void*)prep_columns_kernel(P), (const void*)k_prepare_fused<false>,
                               (const void*)k_prepare_fused<true>};
     for (const void* k : kernels) {
         const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
