@@ -1837,6 +1837,27 @@ static CallBuffers call_buffers(const is_ctx* c, const float* d_joined, const in
     return b;
 }
 
+/* The tail of a DP call behind its prepare launches: the pairwise or unary DP, the back-trace into b.sections and, with
+ * instance outputs (b.inst_cnt), the instance candidates (StixelsKernels.cu:926-942) and their clustering
+ * (Stixels::ClusterInstances, Stixels.cu:613) of the WHOLE batch into d_tbl: two launches.  ev_dp (timing, or null) is
+ * recorded between the DP and the back-trace. */
+static int dp_tail_enqueue(is_ctx* c, const DevParams& P, const CallPlan& plan, const CallBuffers& b, int n_images,
+                           const is_instance_buffers* d_tbl, bool want_labels, float eps, int min_pts,
+                           hipStream_t stream, hipEvent_t ev_dp) {
+    if (plan.pairwise)
+        HIP_TRY(isk_launch_dp_pairwise(&P, &plan, &b, stream, c->aux_streams, c->ev_fork, c->ev_joins));
+    else
+        HIP_TRY(isk_launch_dp_unary(&P, &plan, &b, stream));
+    if (ev_dp) HIP_TRY(hipEventRecord(ev_dp, stream));
+    HIP_TRY(isk_launch_backtrace(&P, &plan, &b, stream));
+    if (b.inst_cnt) {
+        HIP_TRY(isk_launch_compact(&P, n_images, b.sections, b.inst_cnt, d_tbl, stream));
+        if (want_labels)
+            HIP_TRY(isk_launch_cluster(P.C * P.S, eps, min_pts, n_images, d_tbl, nullptr, c->d_cluster_scratch, stream));
+    }
+    return IS_OK;
+}
+
 /* Everything is_compute and is_compute_road queue on `stream` behind the host-side staging of slot `slot`.  d_road
  * null (is_compute): the slot's ground model is uploaded.  Else k_ground_model builds it from d_road in place, and
  * the plan takes vhor_min_hint (< 0: unknown, planned as 0) for the smallest horizon. */
@@ -1871,20 +1892,9 @@ static int compute_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_se
     HIP_TRY(isk_launch_prepare(&P, &plan, &b, stream));
     if (pairwise) HIP_TRY(isk_launch_priors(&P, c->d_ground, c->d_priors, n_images, stream));
     if (timing) HIP_TRY(hipEventRecord(c->ev[1], stream));
-    if (pairwise)
-        HIP_TRY(isk_launch_dp_pairwise(&P, &plan, &b, stream, c->aux_streams, c->ev_fork, c->ev_joins));
-    else
-        HIP_TRY(isk_launch_dp_unary(&P, &plan, &b, stream));
-    if (timing) HIP_TRY(hipEventRecord(c->ev[2], stream));
-    HIP_TRY(isk_launch_backtrace(&P, &plan, &b, stream));
-    if (want_inst) {
-        /* the instance candidates (StixelsKernels.cu:926-942) and their clustering
-         * (Stixels::ClusterInstances, Stixels.cu:613) of the WHOLE batch: two launches */
-        HIP_TRY(isk_launch_compact(&P, n_images, d_sections, c->d_inst_cnt, c->d_inst_tbl, stream));
-        if (want_labels)
-            HIP_TRY(isk_launch_cluster(P.C * P.S, c->params.clustering_eps, c->params.clustering_min_pts,
-                                       n_images, c->d_inst_tbl, nullptr, c->d_cluster_scratch, stream));
-    }
+    const int rc = dp_tail_enqueue(c, P, plan, b, n_images, c->d_inst_tbl, want_labels, c->params.clustering_eps,
+                                   c->params.clustering_min_pts, stream, timing ? c->ev[2] : nullptr);
+    if (rc != IS_OK) return rc;
     if (timing) {
         HIP_TRY(hipEventRecord(c->ev[3], stream));
         c->ev_valid = true;
@@ -2130,17 +2140,9 @@ static int sweep_enqueue(is_ctx* c, const float* d_joined, const int32_t* d_seg,
         b.prune = c->d_sweep_prune + (size_t)k * ncols;
         b.sections = sections;
         b.inst_cnt = want_inst ? c->d_inst_cnt : nullptr;
-        if (pairwise)
-            HIP_TRY(isk_launch_dp_pairwise(&P, &plan, &b, stream, c->aux_streams, c->ev_fork, c->ev_joins));
-        else
-            HIP_TRY(isk_launch_dp_unary(&P, &plan, &b, stream));
-        HIP_TRY(isk_launch_backtrace(&P, &plan, &b, stream));
-        if (want_inst) {
-            HIP_TRY(isk_launch_compact(&P, n_images, sections, c->d_inst_cnt, d_tbl, stream));
-            if (want_labels)
-                HIP_TRY(isk_launch_cluster(P.C * P.S, sets[k].clustering_eps, sets[k].clustering_min_pts, n_images,
-                                           d_tbl, nullptr, c->d_cluster_scratch, stream));
-        }
+        const int rc = dp_tail_enqueue(c, P, plan, b, n_images, d_tbl, want_labels, sets[k].clustering_eps,
+                                       sets[k].clustering_min_pts, stream, nullptr);
+        if (rc != IS_OK) return rc;
         if (!pairwise) c->last_unary_path = plan.unary_walk;
     }
     return IS_OK;

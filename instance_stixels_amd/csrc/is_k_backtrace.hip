@@ -232,6 +232,13 @@ __global__ __launch_bounds__(ISC_THREADS) void k_compact_instances(
     }
 }
 
+/* The instantiation of a form (IS_BT_*, plan_call) */
+using BacktraceKernel = decltype(&k_backtrace<false>);
+static BacktraceKernel backtrace_kernel(int form) {
+    const BacktraceKernel k[3] = {k_backtrace<false>, k_backtrace<true>, k_backtrace<false, true>}; /* [IS_BT_*] */
+    return form >= 0 && form < 3 ? k[form] : nullptr;
+}
+
 extern "C" {
 
 /* dynamic LDS of each form (IS_BT_*, plan_call): the launch and its attribute */
@@ -243,16 +250,11 @@ size_t isk_backtrace_lds_bytes(const DevParams* P, int form) {
 hipError_t isk_launch_backtrace(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream) {
     const int ncols = plan->ncols;
     const size_t lds = isk_backtrace_lds_bytes(P, plan->backtrace);
-#define IS_BT_ARGS                                                                                                 \
-    *P, ncols, plan->pairwise, b->recs, b->cost_table, b->index_table, b->col_flags, b->sections, b->inst_cnt,     \
-        b->n_generic, b->path_bad, plan->walk_sections
-    if (plan->backtrace == IS_BT_STAGED)
-        hipLaunchKernelGGL(k_backtrace<true>, dim3(ncols), dim3(64), lds, stream, IS_BT_ARGS);
-    else if (plan->backtrace == IS_BT_TWO)
-        hipLaunchKernelGGL((k_backtrace<false, true>), dim3((ncols + 1) / 2), dim3(64), lds, stream, IS_BT_ARGS);
-    else
-        hipLaunchKernelGGL(k_backtrace<false>, dim3(ncols), dim3(64), lds, stream, IS_BT_ARGS);
-#undef IS_BT_ARGS
+    const BacktraceKernel k = backtrace_kernel(plan->backtrace);
+    if (k == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k, dim3(plan->backtrace == IS_BT_TWO ? (ncols + 1) / 2 : ncols), dim3(64), lds, stream, *P, ncols,
+                       plan->pairwise, b->recs, b->cost_table, b->index_table, b->col_flags, b->sections, b->inst_cnt,
+                       b->n_generic, b->path_bad, plan->walk_sections);
     return hipGetLastError();
 }
 
@@ -271,12 +273,10 @@ hipError_t isk_launch_compact(const DevParams* P, int n_images, const is_section
 
 /* every form plan_call can select: the plain one, the staged one up to 64 KiB, the two-column one up to 160 KiB */
 hipError_t isk_set_lds_backtrace(const DevParams* P) {
-    const void* kernel[3] = {(const void*)k_backtrace<false>, (const void*)k_backtrace<true>,
-                             (const void*)k_backtrace<false, true>}; /* [IS_BT_*] */
-    const size_t cap[3] = {160 * 1024, 64 * 1024, 160 * 1024};
+    const size_t cap[3] = {160 * 1024, 64 * 1024, 160 * 1024}; /* [IS_BT_*] */
     for (int form = 0; form < 3; form++) {
         const size_t bytes = isk_backtrace_lds_bytes(P, form);
-        const hipError_t e = bytes <= cap[form] ? hipFuncSetAttribute(kernel[form], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipSuccess;
+        const hipError_t e = bytes <= cap[form] ? hipFuncSetAttribute((const void*)backtrace_kernel(form), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipSuccess;
         if (e != hipSuccess) return e;
     }
     /* more than ~2000 stixel columns: the per-column offsets exceed the 64 KiB default */

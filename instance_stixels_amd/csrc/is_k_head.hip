@@ -229,20 +229,24 @@ __global__ __launch_bounds__(256) void k_head(const void* __restrict__ features_
     }
 }
 
+/* The instantiation for a feature type (IS_HEAD_*); nullptr for any other value */
+static decltype(&k_head<IS_HEAD_F32>) head_kernel(int dtype) {
+    switch (dtype) {
+    case IS_HEAD_F32: return k_head<IS_HEAD_F32>;
+    case IS_HEAD_F16: return k_head<IS_HEAD_F16>;
+    case IS_HEAD_BF16: return k_head<IS_HEAD_BF16>;
+    }
+    return nullptr;
+}
+
 extern "C" hipError_t isk_launch_segmentation_head(const is_segmentation_head_args* a, hipStream_t stream) {
     const int CH = a->n_classes + a->n_regression;
     const dim3 grid((a->cols8 + HEAD_COLS - 1) / HEAD_COLS,
                     (a->rows_power2_segmentation + HEAD_ROWS - 1) / HEAD_ROWS, a->n_images);
-#define HEAD_LAUNCH(DT)                                                                                              \
-    hipLaunchKernelGGL(k_head<DT>, grid, dim3(256), 0, stream, a->d_features, a->d_weight, a->d_bias, a->d_cnn_out,  \
-                       a->d_segmentation, a->K, a->rows8, a->cols8, a->n_classes, CH, a->rows_power2_segmentation,   \
-                       a->clamp_channel, a->clamp_lo, a->clamp_hi)
-    switch (a->dtype) {
-    case IS_HEAD_F32: HEAD_LAUNCH(IS_HEAD_F32); break;
-    case IS_HEAD_F16: HEAD_LAUNCH(IS_HEAD_F16); break;
-    case IS_HEAD_BF16: HEAD_LAUNCH(IS_HEAD_BF16); break;
-    default: return hipErrorInvalidValue;
-    }
-#undef HEAD_LAUNCH
+    const auto kernel = head_kernel(a->dtype);
+    if (kernel == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, a->d_features, a->d_weight, a->d_bias, a->d_cnn_out,
+                       a->d_segmentation, a->K, a->rows8, a->cols8, a->n_classes, CH, a->rows_power2_segmentation,
+                       a->clamp_channel, a->clamp_lo, a->clamp_hi);
     return hipGetLastError();
 }

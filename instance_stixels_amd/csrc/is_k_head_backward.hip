@@ -256,6 +256,22 @@ extern "C" size_t isk_head_backward_scratch_bytes(int n_images, int K, int Hs, i
            (size_t)n_images * hb_chunks(Hs, Ws) * channels * (size_t)(K + 1) * sizeof(float);
 }
 
+/* The two instantiations for a feature type (IS_HEAD_*); null for any other value */
+struct HeadBackwardKernels {
+    decltype(&k_head_backward_dx<IS_HEAD_F32>) dx;
+    decltype(&k_head_backward_partials<IS_HEAD_F32>) partials;
+};
+template <int DT>
+static HeadBackwardKernels head_backward_kernels_of() { return {k_head_backward_dx<DT>, k_head_backward_partials<DT>}; }
+static HeadBackwardKernels head_backward_kernels(int dtype) {
+    switch (dtype) {
+    case IS_HEAD_F32: return head_backward_kernels_of<IS_HEAD_F32>();
+    case IS_HEAD_F16: return head_backward_kernels_of<IS_HEAD_F16>();
+    case IS_HEAD_BF16: return head_backward_kernels_of<IS_HEAD_BF16>();
+    }
+    return {nullptr, nullptr};
+}
+
 /* The arguments are checked by is_segmentation_head_backward. */
 extern "C" hipError_t isk_launch_segmentation_head_backward(const is_segmentation_head_backward_args* a, hipStream_t stream) {
     const int CH = a->n_classes + a->n_regression, P = a->rows8 * a->cols8, chunks = hb_chunks(a->rows8, a->cols8);
@@ -265,21 +281,12 @@ extern "C" hipError_t isk_launch_segmentation_head_backward(const is_segmentatio
     /* the contraction reads dz from d_grad_logits where that is given, from the scratch otherwise */
     float* dz_a = a->d_grad_logits ? a->d_grad_logits : contract ? scratch_dz : nullptr;
     const dim3 grid_a((P + 127) / 128, a->n_images), grid_b(chunks, a->n_images);
-#define HB_LAUNCH(DT)                                                                                                \
-    do {                                                                                                             \
-        hipLaunchKernelGGL(k_head_backward_dx<DT>, grid_a, dim3(256), 0, stream, a->d_cnn_out, a->d_grad_out,        \
-                           a->grad_image_stride, a->d_weight, dz_a, a->d_grad_features, a->K, P, a->n_classes, CH);  \
-        if (contract)                                                                                                \
-            hipLaunchKernelGGL(k_head_backward_partials<DT>, grid_b, dim3(256), 0, stream, a->d_features,            \
-                               (const float*)dz_a, part, a->K, P, CH);                                               \
-    } while (0)
-    switch (a->dtype) {
-    case IS_HEAD_F32: HB_LAUNCH(IS_HEAD_F32); break;
-    case IS_HEAD_F16: HB_LAUNCH(IS_HEAD_F16); break;
-    case IS_HEAD_BF16: HB_LAUNCH(IS_HEAD_BF16); break;
-    default: return hipErrorInvalidValue;
-    }
-#undef HB_LAUNCH
+    const HeadBackwardKernels k = head_backward_kernels(a->dtype);
+    if (k.dx == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k.dx, grid_a, dim3(256), 0, stream, a->d_cnn_out, a->d_grad_out, a->grad_image_stride, a->d_weight, dz_a,
+                       a->d_grad_features, a->K, P, a->n_classes, CH);
+    if (contract)
+        hipLaunchKernelGGL(k.partials, grid_b, dim3(256), 0, stream, a->d_features, (const float*)dz_a, part, a->K, P, CH);
     if (contract)
         hipLaunchKernelGGL(k_head_backward_reduce, dim3((CH * (a->K + 1) + 255) / 256), dim3(256), 0, stream,
                            (const float*)part, a->n_images * chunks, a->K, CH, a->d_grad_weight, a->d_grad_bias);

@@ -2174,6 +2174,32 @@ __global__ __launch_bounds__(ISP2S_WAVES * 64, 5) void k_pw_phase2s(
                                             vhor, nsplit, part_cost, part_idx, steps, cost_table, index_table, blksum, t8row);
 }
 
+/* The phase-1 instantiation for (invalid-disparity value or none, D <= 128, windowed): the only ones the library holds.
+ * The vB-side lutT row in registers (LutRow<2>, D <= 128): slower than the per-lane gather while
+ * phase 1 was issue-bound (41.4 vs 38.0 ms per 64 frames, round 1), faster now that the pruned
+ * phase 1 is latency-bound (30.4 vs 31.2 ms): no memory access on the chain mean -> fn -> value.
+ * (any D: the windowed instantiation keeps 64 columns of a vB row in one register per lane) */
+using Phase1Kernel = decltype(&k_pw_phase1<false, 2>);
+static Phase1Kernel phase1_kernel(bool invalid, bool d128, bool windowed) {
+    if (windowed) return invalid ? k_pw_phase1<true, 2, true> : k_pw_phase1<false, 2, true>;
+    if (d128) return invalid ? k_pw_phase1<true, 2> : k_pw_phase1<false, 2>;
+    return invalid ? k_pw_phase1<true, 0> : k_pw_phase1<false, 0>;
+}
+
+/* The phase-2 kernel of a form (IS_P2_*; IS_P2_TWO: k_pw_phase2x, followed by k_pw_phase2_generic) */
+using Phase2Kernel = decltype(&k_pw_phase2<false>);
+static Phase2Kernel phase2_kernel(bool invalid, int form) {
+    switch (form) {
+    case IS_P2_ONE: return invalid ? k_pw_phase2<true> : k_pw_phase2<false>;
+    case IS_P2_SPLIT: return invalid ? k_pw_phase2s<true> : k_pw_phase2s<false>;
+    case IS_P2_TWO: return invalid ? k_pw_phase2x<true> : k_pw_phase2x<false>;
+    }
+    return nullptr;
+}
+static decltype(&k_pw_phase2_generic<false>) phase2_generic_kernel(bool invalid) {
+    return invalid ? k_pw_phase2_generic<true> : k_pw_phase2_generic<false>;
+}
+
 extern "C" {
 
 /* (the last tile: the most bound blocks; the windowed instantiations need less) */
@@ -2210,39 +2236,8 @@ hipError_t isk_launch_dp_pairwise(const DevParams* P, const CallPlan* plan, cons
     const size_t lds2 = isk_phase2_lds_bytes(P);
     const size_t lds2s = isk_phase2s_lds_bytes(P);
     const size_t lds2x = isk_phase2x_lds_bytes(P);
+    const bool inv = P->invalid >= 0;
     hipError_t e;
-#define IS_P2_ARGS                                                                                                  \
-    c0, c1, tile, nsplit, b->recs, b->lutT, b->joined, b->priors, b->odr, b->rcp, b->sv, b->vhor, b->col_flags,     \
-        b->part_cost, b->part_idx, b->steps, b->cost_table, b->index_table
-/* the vB-side lutT row in registers (LutRow<2>, D <= 128): slower than the per-lane gather while
- * phase 1 was issue-bound (41.4 vs 38.0 ms per 64 frames, round 1), faster now that the pruned
- * phase 1 is latency-bound (30.4 vs 31.2 ms): no memory access on the chain mean -> fn -> value.
- * (any D: the windowed instantiation keeps 64 columns of a vB row in one register per lane) */
-#define IS_LAUNCH_P1(KERNEL)                                                                                        \
-    hipLaunchKernelGGL(KERNEL, dim3((c1 - c0) * nsplit), dim3(nw_t * 64), lds1_t, st, *P, c0, c1, tile, nsplit,     \
-                       b->recs, b->lutT, b->steps, b->rcp, b->vhor, b->col_flags, b->prune, b->part_cost,           \
-                       b->part_idx, b->counters, b->blksum)
-#define IS_LAUNCH_TILE(INV)                                                                                         \
-    do {                                                                                                            \
-        if (win_t)                                                                                                  \
-            IS_LAUNCH_P1((k_pw_phase1<INV, 2, true>));                                                              \
-        else if (P->D <= 128)                                                                                       \
-            IS_LAUNCH_P1((k_pw_phase1<INV, 2>));                                                                    \
-        else                                                                                                        \
-            IS_LAUNCH_P1((k_pw_phase1<INV, 0>));                                                                    \
-        if (plan->phase2 == IS_P2_SPLIT) {                                                                          \
-            hipLaunchKernelGGL(k_pw_phase2s<INV>, dim3(c1 - c0), dim3(ISP2S_WAVES * 64), lds2s, st, *P, IS_P2_ARGS, \
-                               b->blksum, b->t8row);                                                                \
-        } else if (plan->phase2 == IS_P2_TWO) {                                                                     \
-            hipLaunchKernelGGL(k_pw_phase2x<INV>, dim3((c1 - c0 + 1) / 2), dim3(64), lds2x, st, *P, IS_P2_ARGS,     \
-                               b->blksum, b->t8row);                                                                \
-            hipLaunchKernelGGL(k_pw_phase2_generic<INV>, dim3(min(c1 - c0, 512)), dim3(64), lds2, st, *P,           \
-                               IS_P2_ARGS, b->n_generic, b->blksum, b->t8row);                                      \
-        } else {                                                                                                    \
-            hipLaunchKernelGGL(k_pw_phase2<INV>, dim3(c1 - c0), dim3(64), lds2, st, *P, IS_P2_ARGS, b->blksum,      \
-                               b->t8row);                                                                           \
-        }                                                                                                           \
-    } while (0)
     if (groups > 1) {
         if ((e = hipEventRecord(ev_fork, stream)) != hipSuccess) return e;
         for (int g = 1; g < groups; g++)
@@ -2256,12 +2251,25 @@ hipError_t isk_launch_dp_pairwise(const DevParams* P, const CallPlan* plan, cons
             const int c0 = (int)((long long)ncols * g / groups) & ~1; /* (even: column pairs) */
             const int c1 = g + 1 == groups ? ncols : ((int)((long long)ncols * (g + 1) / groups) & ~1);
             hipStream_t st = g == 0 ? stream : aux[g - 1];
-            if (P->invalid >= 0) IS_LAUNCH_TILE(true); else IS_LAUNCH_TILE(false);
+            hipLaunchKernelGGL(phase1_kernel(inv, P->D <= 128, win_t), dim3((c1 - c0) * nsplit), dim3(nw_t * 64), lds1_t, st,
+                               *P, c0, c1, tile, nsplit, b->recs, b->lutT, b->steps, b->rcp, b->vhor, b->col_flags,
+                               b->prune, b->part_cost, b->part_idx, b->counters, b->blksum);
+            auto launch2 = [&](auto kernel, int grid, int block, size_t lds, auto... tail) {
+                hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, st, *P, c0, c1, tile, nsplit, b->recs, b->lutT,
+                                   b->joined, b->priors, b->odr, b->rcp, b->sv, b->vhor, b->col_flags, b->part_cost,
+                                   b->part_idx, b->steps, b->cost_table, b->index_table, tail...);
+            };
+            const Phase2Kernel k2 = phase2_kernel(inv, plan->phase2);
+            if (k2 == nullptr) return hipErrorInvalidValue;
+            if (plan->phase2 == IS_P2_SPLIT) {
+                launch2(k2, c1 - c0, ISP2S_WAVES * 64, lds2s, b->blksum, b->t8row);
+            } else if (plan->phase2 == IS_P2_TWO) {
+                launch2(k2, (c1 - c0 + 1) / 2, 64, lds2x, b->blksum, b->t8row);
+                launch2(phase2_generic_kernel(inv), min(c1 - c0, 512), 64, lds2, b->n_generic, b->blksum, b->t8row);
+            } else
+                launch2(k2, c1 - c0, 64, lds2, b->blksum, b->t8row);
         }
     }
-#undef IS_LAUNCH_TILE
-#undef IS_LAUNCH_P1
-#undef IS_P2_ARGS
     for (int g = 1; g < groups; g++) {
         if ((e = hipEventRecord(ev_join[g - 1], aux[g - 1])) != hipSuccess) return e;
         if ((e = hipStreamWaitEvent(stream, ev_join[g - 1], 0)) != hipSuccess) return e;
@@ -2269,14 +2277,14 @@ hipError_t isk_launch_dp_pairwise(const DevParams* P, const CallPlan* plan, cons
     return hipGetLastError();
 }
 
+/* (the instantiations this context's D and invalid value can launch; phase 2 stays below 64 KiB by
+ * ctx_init's check and needs none) */
 hipError_t isk_set_lds_pairwise(const DevParams* P, int nwaves) {
     const int c = (int)isk_pairwise_lds_bytes(P, nwaves); /* (the windowed instantiations need less) */
     hipError_t e = hipSuccess;
-#define IS_SET_P1_LDS(...) \
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_pw_phase1<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, c)
-    IS_SET_P1_LDS(true, 2); IS_SET_P1_LDS(false, 2); IS_SET_P1_LDS(true, 2, true); IS_SET_P1_LDS(false, 2, true);
-    IS_SET_P1_LDS(true, 0); IS_SET_P1_LDS(false, 0);
-#undef IS_SET_P1_LDS
+    for (int windowed = 0; windowed < 2 && e == hipSuccess; windowed++)
+        e = hipFuncSetAttribute((const void*)phase1_kernel(P->invalid >= 0, P->D <= 128, windowed != 0),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, c);
     return e;
 }
 

@@ -1018,6 +1018,11 @@ static prep_columns_kernel_t prep_columns_kernel(const DevParams* P) {
     if (prep_compiled_for<784>(P)) return k_prepare_columns<784>;
     return k_prepare_columns<0>;
 }
+/* k_prepare_fused for (carry rows or the whole lutT); k_lut_carry for (D <= 64): one or two fn per lane */
+static decltype(&k_prepare_fused<false>) prepare_fused_kernel(bool carry) {
+    return carry ? k_prepare_fused<true> : k_prepare_fused<false>;
+}
+static decltype(&k_lut_carry<1>) lut_carry_kernel(bool d64) { return d64 ? k_lut_carry<1> : k_lut_carry<2>; }
 
 extern "C" {
 
@@ -1046,12 +1051,8 @@ size_t isk_lut_carry_lds_bytes(const DevParams* P) {
 hipError_t isk_launch_lut_carry(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream) {
     const int per_wg = LUTC_THREADS / 64, wgs = (plan->ncols + per_wg - 1) / per_wg;
     const dim3 grid(wgs < LUTC_MAX_WGS ? wgs : LUTC_MAX_WGS);
-    if (P->D <= 64)
-        hipLaunchKernelGGL(k_lut_carry<1>, grid, dim3(LUTC_THREADS), isk_lut_carry_lds_bytes(P), stream, *P, plan->ncols,
-                           b->joined, b->cost_T, b->lutC);
-    else
-        hipLaunchKernelGGL(k_lut_carry<2>, grid, dim3(LUTC_THREADS), isk_lut_carry_lds_bytes(P), stream, *P, plan->ncols,
-                           b->joined, b->cost_T, b->lutC);
+    hipLaunchKernelGGL(lut_carry_kernel(P->D <= 64), grid, dim3(LUTC_THREADS), isk_lut_carry_lds_bytes(P), stream, *P,
+                       plan->ncols, b->joined, b->cost_T, b->lutC);
     return hipGetLastError();
 }
 
@@ -1076,12 +1077,9 @@ hipError_t isk_launch_prepare(const DevParams* P, const CallPlan* plan, const Ca
     /* the two prepare kernels are independent: one launch with workgroups of both kinds (k_prepare_fused) */
     const int units = ncols * ((P->D + 63) / 64);
     const int n_lut = (units + PREP_THREADS / 64 - 1) / (PREP_THREADS / 64);
-#define IS_LAUNCH_PREPARE(CARRY, LUT)                                                                                 \
-    hipLaunchKernelGGL(k_prepare_fused<CARRY>, dim3(ncols + n_lut), dim3(PREP_THREADS), isk_prepare_lds_bytes(P), stream, \
-                       *P, ncols, b->joined, b->seg, b->ground, b->vhor, b->cost_T, b->recs, LUT, b->col_flags,  \
-                       sv, b->prune, b->n_generic, b->path_bad)
-    if (plan->lut_carry) IS_LAUNCH_PREPARE(true, b->lutC); else IS_LAUNCH_PREPARE(false, b->lutT);
-#undef IS_LAUNCH_PREPARE
+    hipLaunchKernelGGL(prepare_fused_kernel(plan->lut_carry != 0), dim3(ncols + n_lut), dim3(PREP_THREADS),
+                       isk_prepare_lds_bytes(P), stream, *P, ncols, b->joined, b->seg, b->ground, b->vhor, b->cost_T, b->recs,
+                       plan->lut_carry ? b->lutC : b->lutT, b->col_flags, sv, b->prune, b->n_generic, b->path_bad);
     return hipGetLastError();
 }
 
@@ -1094,8 +1092,8 @@ hipError_t isk_launch_priors(const DevParams* P, const float* ground, PriorRec* 
 }
 
 hipError_t isk_set_lds_prepare(const DevParams* P) {
-    const void* kernels[3] = {(const void*)prep_columns_kernel(P), (const void*)k_prepare_fused<false>,
-                              (const void*)k_prepare_fused<true>};
+    const void* kernels[3] = {(const void*)prep_columns_kernel(P), (const void*)prepare_fused_kernel(false),
+                              (const void*)prepare_fused_kernel(true)};
     for (const void* k : kernels) {
         const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)isk_prepare_lds_bytes(P));
@@ -1107,9 +1105,7 @@ hipError_t isk_set_lds_prepare(const DevParams* P) {
 hipError_t isk_set_lds_lut_carry(const DevParams* P) {
     const int bytes = (int)isk_lut_carry_lds_bytes(P);
     if (bytes == 0) return hipSuccess; /* the shape keeps k_prepare_fused<true> */
-    if (P->D <= 64)
-        return hipFuncSetAttribute((const void*)k_lut_carry<1>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    return hipFuncSetAttribute((const void*)k_lut_carry<2>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    return hipFuncSetAttribute((const void*)lut_carry_kernel(P->D <= 64), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
 } /* extern "C" */

@@ -278,6 +278,21 @@ __global__ __launch_bounds__(IS_UNARY_WAVES * 64, IS_UNARY_OCC) void k_dp_unary(
     } /* item */
 }
 
+/* The instantiation for (invalid-disparity value or none, D <= 128, form): the only ones the library holds.
+ * D <= 128: the vB-side lutT row travels in two registers per lane (LutRow<2>); wider tables gather per lane. */
+enum { IS_UNARY_FASTCOLS = 0, IS_UNARY_GENERIC = 1, IS_UNARY_REPAIR = 2, IS_UNARY_FORMS = 3 };
+using UnaryKernel = decltype(&k_dp_unary<false, 2, true>);
+template <bool INV, int NR>
+static UnaryKernel unary_kernel_form(int form) {
+    const UnaryKernel k[IS_UNARY_FORMS] = {k_dp_unary<INV, NR, true>, k_dp_unary<INV, NR, false>,
+                                           k_dp_unary<INV, NR, true, true>}; /* [IS_UNARY_*] */
+    return form >= 0 && form < IS_UNARY_FORMS ? k[form] : nullptr;
+}
+static UnaryKernel unary_kernel(bool invalid, bool d128, int form) {
+    if (d128) return invalid ? unary_kernel_form<true, 2>(form) : unary_kernel_form<false, 2>(form);
+    return invalid ? unary_kernel_form<true, 0>(form) : unary_kernel_form<false, 0>(form);
+}
+
 extern "C" {
 
 size_t isk_unary_lds_bytes(const DevParams* P) {
@@ -304,7 +319,6 @@ hipError_t isk_launch_dp_unary(const DevParams* P, const CallPlan* plan, const C
     else if (plan->unary_nvr)
         e = isk_launch_dp_unary_fast(P, plan, b, stream);
     if (e != hipSuccess) return e;
-    const bool tiles = !plan->unary_walk && !plan->unary_nvr;
     /* one tile pair (big, small) per workgroup: equal-length workgroups pack best; measured on
      * MI355X at batch 32: 1 pair 9.98 ms, 2 pairs 10.10 ms, 4 pairs 10.55 ms, single tiles 11.1 ms */
     const int npairs = (P->ntiles + 1) / 2;
@@ -312,56 +326,37 @@ hipError_t isk_launch_dp_unary(const DevParams* P, const CallPlan* plan, const C
     const unsigned items = (unsigned)((ncols + 7) / 8) * 8u * (unsigned)npairs;
     const dim3 grid_generic(items < 16384u ? items : 16384u); /* walks the items, see the kernel */
     const dim3 grid_repair(items < 2048u ? items : 2048u);    /* (walks the items: a safety net, not a fast path) */
-    const dim3 block(plan->nwaves * 64);
-    const size_t lds = isk_unary_lds_bytes(P);
-    /* D <= 128: the vB-side lutT row travels in two registers per lane (LutRow<2>); wider
-     * tables gather per lane */
-#define IS_LAUNCH_UNARY(INV, NR)                                                                           \
-    do {                                                                                                   \
-        if (tiles)                                                                                         \
-            hipLaunchKernelGGL((k_dp_unary<INV, NR, true>), dim3(items), block, lds, stream, *P, ncols, b->recs,  \
-                               b->lutT, b->rcp, b->vhor, b->col_flags, b->prune, b->cost_table,            \
-                               b->index_table, b->n_generic, pairs_per_wg);                                \
-        if (plan->lut_carry && (e = isk_launch_lut_generic(P, plan, b, stream)) != hipSuccess) return e;  \
-        hipLaunchKernelGGL((k_dp_unary<INV, NR, false>), grid_generic, block, lds, stream, *P, ncols,      \
-                           b->recs, b->lutT, b->rcp, b->vhor, b->col_flags, b->prune, b->cost_table,       \
-                           b->index_table, b->n_generic, pairs_per_wg);                                    \
-        if (plan->unary_walk) {                                                                            \
-            if (plan->lut_carry &&                                                                         \
-                (e = isk_launch_lut_repair(P, ncols, b->joined, b->cost_T, b->lutT, b->path_bad, stream)) != \
-                    hipSuccess)                                                                            \
-                return e;                                                                                  \
-            hipLaunchKernelGGL((k_dp_unary<INV, NR, true, true>), grid_repair, block, lds, stream, *P,     \
-                               ncols, b->recs, b->lutT, b->rcp, b->vhor, b->col_flags, b->prune,           \
-                               b->cost_table, b->index_table, b->path_bad, pairs_per_wg);                  \
-        }                                                                                                  \
-    } while (0)
-    if (P->D <= 128) {
-        if (P->invalid >= 0) IS_LAUNCH_UNARY(true, 2); else IS_LAUNCH_UNARY(false, 2);
-    } else {
-        if (P->invalid >= 0) IS_LAUNCH_UNARY(true, 0); else IS_LAUNCH_UNARY(false, 0);
+    const bool inv = P->invalid >= 0, d128 = P->D <= 128;
+    auto launch = [&](int form, dim3 grid, const int* gate) {
+        const UnaryKernel k = unary_kernel(inv, d128, form);
+        if (k == nullptr) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k, grid, dim3(plan->nwaves * 64), isk_unary_lds_bytes(P), stream, *P, ncols, b->recs, b->lutT,
+                           b->rcp, b->vhor, b->col_flags, b->prune, b->cost_table, b->index_table, gate, pairs_per_wg);
+        return hipSuccess;
+    };
+    if (!plan->unary_walk && !plan->unary_nvr) e = launch(IS_UNARY_FASTCOLS, dim3(items), b->n_generic);
+    if (e == hipSuccess && plan->lut_carry) e = isk_launch_lut_generic(P, plan, b, stream);
+    if (e == hipSuccess) e = launch(IS_UNARY_GENERIC, grid_generic, b->n_generic);
+    if (e == hipSuccess && plan->unary_walk) {
+        if (plan->lut_carry) e = isk_launch_lut_repair(P, ncols, b->joined, b->cost_T, b->lutT, b->path_bad, stream);
+        if (e == hipSuccess) e = launch(IS_UNARY_REPAIR, grid_repair, b->path_bad);
     }
-#undef IS_LAUNCH_UNARY
-    return hipGetLastError();
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 int isk_debug_occupancy(const DevParams* P, int nwaves) {
     int nb = -1;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_dp_unary<false, 2, true>,
-                                                 nwaves * 64, isk_unary_lds_bytes(P));
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)unary_kernel(false, true, IS_UNARY_FASTCOLS),
+                                                       nwaves * 64, isk_unary_lds_bytes(P));
     return nb;
 }
 
+/* (the instantiations this context's D and invalid value can launch) */
 hipError_t isk_set_lds_unary(const DevParams* P) {
-    const int b = (int)isk_unary_lds_bytes(P);
     hipError_t e = hipSuccess;
-#define IS_SET_UNARY_LDS(...) \
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_dp_unary<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, b)
-    IS_SET_UNARY_LDS(true, 2, true); IS_SET_UNARY_LDS(true, 2, false); IS_SET_UNARY_LDS(true, 2, true, true);
-    IS_SET_UNARY_LDS(false, 2, true); IS_SET_UNARY_LDS(false, 2, false); IS_SET_UNARY_LDS(false, 2, true, true);
-    IS_SET_UNARY_LDS(true, 0, true); IS_SET_UNARY_LDS(true, 0, false); IS_SET_UNARY_LDS(true, 0, true, true);
-    IS_SET_UNARY_LDS(false, 0, true); IS_SET_UNARY_LDS(false, 0, false); IS_SET_UNARY_LDS(false, 0, true, true);
-#undef IS_SET_UNARY_LDS
+    for (int form = 0; form < IS_UNARY_FORMS && e == hipSuccess; form++)
+        e = hipFuncSetAttribute((const void*)unary_kernel(P->invalid >= 0, P->D <= 128, form),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)isk_unary_lds_bytes(P));
     return e != hipSuccess ? e : isk_set_lds_unary_fast(P);
 }
 

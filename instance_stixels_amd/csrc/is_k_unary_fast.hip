@@ -733,6 +733,22 @@ item_done:
     }
 }
 
+/* The instantiation for (invalid-disparity value or none, nvr 2 or 4, form): the only ones the library holds */
+enum { ISF_CLASSIC = 0, ISF_WINDOWED = 1, ISF_FUSED = 2, ISF_REPAIR = 3, ISF_FORMS = 4 };
+using UnaryFastKernel = decltype(&k_dp_unary_fast<false, 2>);
+template <bool INV, int NVR>
+static UnaryFastKernel unary_fast_kernel_form(int form) {
+    const UnaryFastKernel k[ISF_FORMS] = {k_dp_unary_fast<INV, NVR>, k_dp_unary_fast<INV, NVR, true>,
+                                          k_dp_unary_fast<INV, NVR, true, true>,
+                                          k_dp_unary_fast<INV, NVR, true, false, true>}; /* [ISF_CLASSIC ..] */
+    return form >= 0 && form < ISF_FORMS ? k[form] : nullptr;
+}
+static UnaryFastKernel unary_fast_kernel(bool invalid, int nvr, int form) {
+    if (nvr == 2) return invalid ? unary_fast_kernel_form<true, 2>(form) : unary_fast_kernel_form<false, 2>(form);
+    if (nvr == 4) return invalid ? unary_fast_kernel_form<true, 4>(form) : unary_fast_kernel_form<false, 4>(form);
+    return nullptr;
+}
+
 extern "C" {
 
 /* NVR = 64-lane loads per lutT row; 0 = the shape cannot use this kernel */
@@ -762,21 +778,18 @@ int isk_unary_fast_chunk_rows(const DevParams* P) {
     return isk_unary_fast_lds_bytes(P, nvr) <= 160 * 1024 ? nvr : 0;
 }
 
+/* (the instantiations this context's nvr and invalid value can launch) */
 hipError_t isk_set_lds_unary_fast(const DevParams* P) {
     const int nvr = isk_unary_fast_chunk_rows(P);
     if (nvr == 0) return hipSuccess;
     size_t bb = isk_unary_fast_lds_bytes(P, nvr);
     const size_t w = isf_lds_bytes(P, nvr, ISF_WIN_WAVES, true); /* (smaller at every shape in use; not relied upon) */
     if (w > bb) bb = w;
-    const int b = (int)bb;
     hipError_t e = hipSuccess;
-    /* (the LUTF and REPAIR forms of the windowed launch: same LDS layout, bounded by b) */
-#define ISF_SET(...) \
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_dp_unary_fast<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, b)
-#define ISF_SET_ALL(INV, NVR) ISF_SET(INV, NVR); ISF_SET(INV, NVR, true); ISF_SET(INV, NVR, true, true); ISF_SET(INV, NVR, true, false, true)
-    if (nvr == 2) { ISF_SET_ALL(true, 2); ISF_SET_ALL(false, 2); } else { ISF_SET_ALL(true, 4); ISF_SET_ALL(false, 4); }
-#undef ISF_SET_ALL
-#undef ISF_SET
+    /* (the LUTF and REPAIR forms of the windowed launch: same LDS layout, bounded by bb) */
+    for (int form = 0; form < ISF_FORMS && e == hipSuccess; form++)
+        e = hipFuncSetAttribute((const void*)unary_fast_kernel(P->invalid >= 0, nvr, form),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bb);
     return e;
 }
 
@@ -799,35 +812,26 @@ hipError_t isk_launch_dp_unary_fast(const DevParams* P, const CallPlan* plan, co
         fused_grid = (unsigned)nSG * (8u + (unsigned)(cpb * 8 * P->ntiles));
     }
     const size_t lds_win = isf_lds_bytes(P, nvr, nw_win, true);
-#define ISF_ARGS(COUNTERS) \
-    ncols, b->recs, b->lutT, b->rcp, b->vhor, b->col_flags, b->prune, b->cost_table, b->index_table, COUNTERS, b->joined, \
-        b->cost_T
-#define ISF_LAUNCH(INV, NVR)                                                                                         \
-    do {                                                                                                             \
-        if (wt < P->ntiles)                                                                                          \
-            hipLaunchKernelGGL((k_dp_unary_fast<INV, NVR>), dim3(groups * 8 * (P->ntiles - wt)), dim3(ISF_THREADS),  \
-                               lds, stream, *P, ISF_ARGS(b->counters), wt, P->ntiles - wt, nullptr);                 \
-        if (wt > 0 && plan->lut_fused) {                                                                             \
-            hipLaunchKernelGGL((k_dp_unary_fast<INV, NVR, true, true>), dim3(fused_grid), dim3(nw_win * 64),         \
-                               lds_win, stream, *P, ISF_ARGS(b->counters), 0, wt, nullptr);                          \
-            /* the repair launches: they leave at once unless a workgroup above set lutf_bad */                      \
-            const hipError_t er = isk_launch_lut_repair(P, ncols, b->joined, b->cost_T, b->lutT, P->lutf_bad, stream); \
-            if (er != hipSuccess) return er;                                                                         \
-            hipLaunchKernelGGL((k_dp_unary_fast<INV, NVR, true, false, true>),                                       \
-                               dim3(groups * 8 * wt < 1536 ? groups * 8 * wt : 1536), dim3(nw_win * 64), lds_win,    \
-                               stream, *P, ISF_ARGS(nullptr), 0, wt, P->lutf_bad);                                   \
-        } else if (wt > 0)                                                                                           \
-            hipLaunchKernelGGL((k_dp_unary_fast<INV, NVR, true>), dim3(groups * 8 * wt), dim3(nw_win * 64), lds_win, \
-                               stream, *P, ISF_ARGS(b->counters), 0, wt, nullptr);                                   \
-    } while (0)
-    if (P->invalid >= 0) {
-        if (nvr == 2) ISF_LAUNCH(true, 2); else ISF_LAUNCH(true, 4);
-    } else {
-        if (nvr == 2) ISF_LAUNCH(false, 2); else ISF_LAUNCH(false, 4);
-    }
-#undef ISF_LAUNCH
-#undef ISF_ARGS
-    return hipGetLastError();
+    /* the classic launch; the others are windowed: ISF_WIN_WAVES waves, the tiles 0 .. wt - 1 */
+    auto launch = [&](int form, unsigned grid, unsigned long long* counters, const int* run_if) {
+        const UnaryFastKernel k = unary_fast_kernel(P->invalid >= 0, nvr, form);
+        if (k == nullptr) return hipErrorInvalidValue;
+        const bool classic = form == ISF_CLASSIC;
+        hipLaunchKernelGGL(k, dim3(grid), dim3(classic ? ISF_THREADS : nw_win * 64), classic ? lds : lds_win, stream, *P,
+                           ncols, b->recs, b->lutT, b->rcp, b->vhor, b->col_flags, b->prune, b->cost_table, b->index_table,
+                           counters, b->joined, b->cost_T, classic ? wt : 0, classic ? P->ntiles - wt : wt, run_if);
+        return hipSuccess;
+    };
+    hipError_t e = hipSuccess;
+    if (wt < P->ntiles) e = launch(ISF_CLASSIC, groups * 8 * (P->ntiles - wt), b->counters, nullptr);
+    if (e == hipSuccess && wt > 0 && plan->lut_fused) {
+        e = launch(ISF_FUSED, fused_grid, b->counters, nullptr);
+        /* the repair launches: they leave at once unless a workgroup above set lutf_bad */
+        if (e == hipSuccess) e = isk_launch_lut_repair(P, ncols, b->joined, b->cost_T, b->lutT, P->lutf_bad, stream);
+        if (e == hipSuccess) e = launch(ISF_REPAIR, groups * 8 * wt < 1536 ? groups * 8 * wt : 1536, nullptr, P->lutf_bad);
+    } else if (e == hipSuccess && wt > 0)
+        e = launch(ISF_WINDOWED, groups * 8 * wt, b->counters, nullptr);
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 } /* extern "C" */

@@ -439,6 +439,11 @@ void k_unary_path(const DevParams P, int ncols, const RowRec* __restrict__ recs,
     }
 }
 
+/* The instantiation for (invalid-disparity value or none) */
+static decltype(&k_unary_path<false>) unary_path_kernel(bool invalid) {
+    return invalid ? k_unary_path<true> : k_unary_path<false>;
+}
+
 extern "C" {
 
 /* one record, the row cache [2][D] and the hops [S][4] */
@@ -447,20 +452,15 @@ size_t isk_unary_path_lds_bytes(const DevParams* P) {
 }
 
 hipError_t isk_set_lds_unary_path(const DevParams* P) {
-    const int b = (int)isk_unary_path_lds_bytes(P);
-    hipError_t e = hipFuncSetAttribute((const void*)k_unary_path<false>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute((const void*)k_unary_path<true>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
+    return hipFuncSetAttribute((const void*)unary_path_kernel(P->invalid >= 0), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)isk_unary_path_lds_bytes(P));
 }
 
 hipError_t isk_launch_unary_path(const DevParams* P, const CallPlan* plan, const CallBuffers* b, hipStream_t stream) {
-#define IS_LAUNCH_PATH(INV)                                                                                        \
-    hipLaunchKernelGGL(k_unary_path<INV>, dim3(plan->ncols), dim3(64), isk_unary_path_lds_bytes(P), stream, *P,    \
-                       plan->ncols, b->recs, b->joined, b->lutC, b->cost_F, b->rcp, b->vhor, b->col_flags, b->prune, \
-                       b->cost_table, b->index_table, plan->walk_sections ? b->sections : nullptr, b->path_bad,    \
-                       plan->unary_force_bad)
-    if (P->invalid >= 0) IS_LAUNCH_PATH(true); else IS_LAUNCH_PATH(false);
-#undef IS_LAUNCH_PATH
+    hipLaunchKernelGGL(unary_path_kernel(P->invalid >= 0), dim3(plan->ncols), dim3(64), isk_unary_path_lds_bytes(P), stream,
+                       *P, plan->ncols, b->recs, b->joined, b->lutC, b->cost_F, b->rcp, b->vhor, b->col_flags, b->prune,
+                       b->cost_table, b->index_table, plan->walk_sections ? b->sections : nullptr, b->path_bad,
+                       plan->unary_force_bad);
     return hipGetLastError();
 }
 

@@ -13,8 +13,10 @@ Shapes, the smallest at which the shared pieces meet their edges: 160 rows (tile
 != 0, a last tile of 8 rows), 8 stixel columns, 64 disparities (windowed); one image, and two with different horizons
 (87 or 74: the middle tile holds it and the last lies wholly above it, NOGROUND; 39 in the second image: the first tile
 holds it); with and without an invalid-disparity value; one hostile case, whose generic columns go through the
-ascending `<` form; and one call of 320 disparities: above 256 there is no ring kernel and k_dp_unary<.., true> is the
-primary route of the FAST columns."""
+ascending `<` form; one call of 320 disparities: above 256 there is no ring kernel and k_dp_unary<.., true> is the
+primary route of the FAST columns; and one of 196 disparities with an invalid-disparity value through the three tile
+routes: the smallest count with four fn blocks that is windowed, where k_dp_unary_fast<true, 4> runs classic, windowed
+and with the LUT units fused (and its repair launch behind them) -- instantiations no other test launches."""
 import itertools
 
 import numpy as np
@@ -38,6 +40,7 @@ CASES = [(rows, 64, n, inv, False, ROUTES)
          for rows, n, inv in itertools.product((160, 136), (1, 2), (False, True))]
 CASES.append((160, 64, 2, False, True, ROUTES))       # generic columns beside FAST ones
 CASES.append((136, 320, 1, False, False, ROUTES[:1]))   # D > 256: k_dp_unary<.., true> takes the FAST columns
+CASES.append((136, 196, 1, True, False, ROUTES[:3]))    # k_dp_unary_fast<true, 4, ...>: windowed, fused + repair, classic
 
 
 def _case_id(c):
