@@ -110,10 +110,14 @@ private:
     void ComputeCameraProperties(int vdisp_rows, const float rho, const float theta,
                                  float& horizonPoint, float& pitch, float& cameraHeight,
                                  float& slope) const;
-    bool ComputeHough(float& rho, float& theta, float& horizonPoint, float& pitch,
-                      float& cameraHeight, float& slope);
-    /* the line choice of ComputeHough over lines[0 .. n): the index of the accepted line, or -1 */
+    /* the line choice of Compute over lines[0 .. n): the index of the accepted line (out = its record), or -1 */
     int ChooseLine(const std::pair<float, float>* lines, size_t n, Stixels::RoadParameters& out) const;
+    /* HoughLines of a binary v-disparity image on the device, fetched into `image` (one synchronisation) */
+    std::vector<std::pair<float, float>> FetchHoughLines(const uint8_t* d_binary, std::vector<uint8_t>& image,
+                                                         void* stream);
+    /* v-disparity + Hough transform of a batch, queued: where in d_batch_out its lines land, and the stream */
+    struct BatchLines { int* d_total; int* d_overflow; float* d_lines; void* stream; };
+    BatchLines EnqueueBatch(const char* who, const pixel_t* d_disparity, int n_images, bool outputs, void* stream);
     void FreeBatch();
 
     bool m_is_initialized = false;

@@ -20,6 +20,28 @@
 #include "instance_stixels_core.h"
 #include "is_numerics.h"
 
+/* ---- host only: the geometry of the standard Hough transform (OpenCV's HoughLinesStandard) of a width x height image,
+ * stated once for RoadEstimation::HoughLines, the device transform's tables (is_road_ctx_create) and the angle index
+ * of the line choice: host and device transforms agree bit for bit only while all three read it here ---- */
+#define IS_ROAD_HOUGH_RHO 1.0f                                         /* the road estimation's rho ... */
+#define IS_ROAD_HOUGH_THETA (3.1415926535897932384626433832795f / 180) /* ... and theta: (float)CV_PI / 180 */
+static inline int is_hough_numangle(float theta) {
+    const double min_theta = 0, max_theta = 3.1415926535897932384626433832795;
+    return (int)lrint((max_theta - min_theta) / theta);
+}
+static inline int is_hough_numrho(int width, int height, float rho) {
+    return (int)lrint(((width + height) * 2 + 1) / rho);
+}
+/* tabSin, tabCos [numangle]: the angle accumulated in fp32, its sin / cos taken in double */
+static inline void is_hough_tables(int numangle, float rho, float theta, float* tabSin, float* tabCos) {
+    const float irho = 1 / rho;
+    float ang = 0.0f; /* (float)min_theta */
+    for (int n = 0; n < numangle; ang += theta, n++) {
+        tabSin[n] = (float)(sin((double)ang) * irho);
+        tabCos[n] = (float)(cos((double)ang) * irho);
+    }
+}
+
 /* The angle index n of a Hough line: theta == 0.0f + n * step bitwise, 0 <= n < numangle; -1 for any other theta
  * (NaN, negative, not a table angle). */
 IS_HD int is_road_angle_index(float theta, float step, int numangle) {

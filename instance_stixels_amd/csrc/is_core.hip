@@ -15,6 +15,7 @@
 
 #include "instance_stixels_core.h"
 #include "is_device.h"
+#include "is_ground_model.h"
 #include "is_launch.h"
 #include "is_numerics.h"
 
@@ -545,16 +546,23 @@ int is_flip_and_pad(const float* d_cnn_out, int32_t* d_segmentation, int n_image
     return IS_OK;
 }
 
+/* ---- road estimation (is_k_road.hip) ---- */
+/* the frame shape of both entries (max_dis ints of LDS per histogram row); the batched one adds its own row limit */
+static bool road_shape_ok(int rows, int cols, int max_dis) {
+    return rows >= 1 && cols >= 1 && max_dis >= 1 && max_dis <= 16384;
+}
+
 int is_road_vdisparity(const float* d_disparity, int rows, int cols, int max_dis, float threshold,
                        int* d_vdisp, int* d_maximum, uint8_t* d_binary, void* stream) {
     if (!d_disparity || !d_vdisp || !d_maximum || !d_binary) return fail_arg("null pointer");
-    if (rows < 1 || cols < 1 || max_dis < 1 || max_dis > 16384) return fail_arg("bad shape");
-    HIP_TRY(isk_launch_vdisparity(d_disparity, d_vdisp, d_maximum, d_binary, rows, cols, max_dis,
-                                  threshold, (hipStream_t)stream));
+    if (!road_shape_ok(rows, cols, max_dis)) return fail_arg("bad shape");
+    const hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(d_maximum, 0, sizeof(int), s));
+    HIP_TRY(isk_launch_road_vdisparity_single(d_disparity, d_vdisp, d_binary, d_maximum, rows, cols, max_dis,
+                                              threshold, s));
     return IS_OK;
 }
 
-/* ---- batched road estimation (is_k_road.hip) ---- */
 struct is_road_ctx {
     OwnedBlocks owned;          /* every device block below */
     int device, rows, cols, max_dis, max_batch;
@@ -579,28 +587,19 @@ static void road_ctx_free(is_road_ctx* c) {
 int is_road_ctx_create(is_road_ctx** out, int rows, int cols, int max_dis, int max_batch, int device) {
     if (!out) return fail_arg("null pointer");
     *out = nullptr;
-    if (rows < 1 || rows > 32767 || cols < 1 || max_dis < 1 || max_dis > 16384)
+    if (!road_shape_ok(rows, cols, max_dis) || rows > 32767) /* (the point list packs (row << 16) | column) */
         return fail_arg("bad shape (rows in [1, 32767], cols >= 1, max_dis in [1, 16384])");
     if (max_batch < 1 || max_batch > 65535) return fail_arg("max_batch outside [1, 65535]");
     if (isk_road_sort_max() != IS_ROAD_MAX_CANDIDATES) return fail_arg("is_k_road.hip and the header disagree");
     if (device < 0) HIP_TRY(hipGetDevice(&device));
     DeviceScope dev_scope(device);
     if (dev_scope.err != hipSuccess) return fail_hip(dev_scope.err, "hipSetDevice(device)", __FILE__, __LINE__);
-    /* RoadEstimation::HoughLines(image, rows, max_dis, 1.0f, kPi / 180, threshold), expression for expression */
-    const float kPi = 3.1415926535897932384626433832795f;
-    const float rho = 1.0f, theta = kPi / 180;
-    const int width = max_dis, height = rows;
-    const float irho = 1 / rho;
-    const double min_theta = 0, max_theta = 3.1415926535897932384626433832795;
-    const int numangle = (int)lrint((max_theta - min_theta) / theta);
-    const int numrho = (int)lrint(((width + height) * 2 + 1) / rho);
+    /* the geometry and tables of RoadEstimation::HoughLines(image, rows, max_dis, rho, theta, threshold) */
+    const float rho = IS_ROAD_HOUGH_RHO, theta = IS_ROAD_HOUGH_THETA;
+    const int numangle = is_hough_numangle(theta), numrho = is_hough_numrho(max_dis, rows, rho);
     float* tab = (float*)malloc(sizeof(float) * 4 * numangle); /* [tabSin | tabCos | sinf | cosf of a line's theta] */
     if (!tab) return IS_ENOMEM;
-    float ang = (float)min_theta;
-    for (int n = 0; n < numangle; ang += theta, n++) {
-        tab[n] = (float)(sin((double)ang) * irho);
-        tab[numangle + n] = (float)(cos((double)ang) * irho);
-    }
+    is_hough_tables(numangle, rho, theta, tab, tab + numangle);
     /* what RoadEstimation::ComputeCameraProperties evaluates for a line of angle index n (k_road_sort writes theta as
      * exactly this expression): the device has no sinf / cosf with libm's bits, so the host's travel */
     for (int n = 0; n < numangle; n++) {

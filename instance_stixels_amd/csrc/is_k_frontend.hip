@@ -1,5 +1,4 @@
-/* is_k_frontend.hip -- kernels around the DP: JoinColumns, the CNN output wrapper, the
- * v-disparity histogram of the road estimation.  See is_kernels.h. */
+/* is_k_frontend.hip -- kernels around the DP: JoinColumns, the CNN output wrapper.  See is_kernels.h. */
 #include "is_kernels.h"
 
 /* ====================================================================================== */
@@ -120,58 +119,6 @@ __global__ __launch_bounds__(256) void k_flip_and_pad(const float* __restrict__ 
     }
 }
 
-/* ====================================================================================== */
-/* f3  road estimation: v-disparity histogram, maximum, binarisation                       */
-/*     (RoadEstimationKernels.cu:25-60)                                                     */
-/* ====================================================================================== */
-/* The reference does one global atomicAdd per pixel and a second kernel of global atomicMax.
- * Here one workgroup owns one image row: the row is read coalesced, binned with LDS atomics,
- * written once, and its maximum goes to a single global atomicMax.  Integer counts and maxima
- * do not depend on the order, so the result is identical. */
-__global__ __launch_bounds__(256) void k_vdisp_histogram(const float* __restrict__ disparity,
-                                                         int* __restrict__ vdisp,
-                                                         int* __restrict__ maximum, int cols,
-                                                         int max_dis) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    int* bins = (int*)smem; /* [max_dis] */
-    const int row = blockIdx.x;
-    for (int i = threadIdx.x; i < max_dis; i += blockDim.x) bins[i] = 0;
-    __syncthreads();
-    const float* src = disparity + (size_t)row * cols;
-    for (int j = threadIdx.x; j < cols; j += blockDim.x) {
-        const float d = src[j];
-        if (d != 0) {
-            /* RoadEstimationKernels.cu:33-37: the bin is (int)d, truncation toward zero.  NaN goes to bin 0,
-             * stated here and not left to the conversion: the reference's float -> int of NaN gives 0 on its
-             * GPU, in C++ (int)NaN is undefined.  The bin guard (the reference is unchecked) is the float
-             * range (-1, max_dis), so +-inf and |d| >= 2^31 are never converted and fall in no bin. */
-            if (d != d) atomicAdd(&bins[0], 1);
-            else if (d > -1.0f && d < (float)max_dis) atomicAdd(&bins[(int)d], 1);
-        }
-    }
-    __syncthreads();
-    int m = 0;
-    for (int i = threadIdx.x; i < max_dis; i += blockDim.x) {
-        const int v = bins[i];
-        vdisp[(size_t)row * max_dis + i] = v;
-        m = max(m, v);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o, 64));
-    if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(maximum, m);
-}
-
-__global__ __launch_bounds__(256) void k_vdisp_binarize(const int* __restrict__ vdisp,
-                                                        uint8_t* __restrict__ out,
-                                                        const int* __restrict__ maximum,
-                                                        float threshold, int n) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx < n) {
-        const float p = (float)vdisp[idx]; /* RoadEstimationKernels.cu:55-58 */
-        out[idx] = (p > (*maximum) * threshold) ? 255 : 0;
-    }
-}
-
 extern "C" {
 
 hipError_t isk_launch_join(const float* big, float* joined, int H, int W, int C, int step,
@@ -187,19 +134,6 @@ hipError_t isk_launch_flip_and_pad(const float* in, int32_t* out, int n, int CH,
                                    int P2S, hipStream_t stream) {
     dim3 grid((Ws + 63) / 64, (P2S + 63) / 64, n * CH);
     hipLaunchKernelGGL(k_flip_and_pad, grid, dim3(256), 0, stream, in, out, CH, Hs, Ws, P2S);
-    return hipGetLastError();
-}
-
-hipError_t isk_launch_vdisparity(const float* disparity, int* vdisp, int* maximum, uint8_t* binary,
-                                 int rows, int cols, int max_dis, float threshold,
-                                 hipStream_t stream) {
-    hipError_t e = hipMemsetAsync(maximum, 0, sizeof(int), stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_vdisp_histogram, dim3(rows), dim3(256), sizeof(int) * max_dis, stream,
-                       disparity, vdisp, maximum, cols, max_dis);
-    const int n = rows * max_dis;
-    hipLaunchKernelGGL(k_vdisp_binarize, dim3((n + 255) / 256), dim3(256), 0, stream, vdisp, binary,
-                       maximum, threshold, n);
     return hipGetLastError();
 }
 

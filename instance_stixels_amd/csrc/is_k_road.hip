@@ -1,9 +1,8 @@
 /*
- * is_k_road.hip -- batched road estimation (f3 for n frames): v-disparity histogram, binarisation +
- * compaction, the standard Hough transform and its per-frame sort, every launch covering the whole batch.
- * Results are those of RoadEstimation::Compute frame by frame (is_k_frontend.hip k_vdisp_* for the
- * histogram, RoadEstimation::HoughLines for the transform), bit for bit.  See is_road_* in
- * instance_stixels_core.h.
+ * is_k_road.hip -- road estimation (f3), for one frame and for n: v-disparity histogram, binarisation (+
+ * compaction), the standard Hough transform and its per-frame sort, every launch covering the whole batch.
+ * Results are those of RoadEstimation::Compute frame by frame (the same histogram kernels, and
+ * RoadEstimation::HoughLines for the transform), bit for bit.  See is_road_* in instance_stixels_core.h.
  */
 #include <hip/hip_runtime.h>
 
@@ -18,7 +17,11 @@
 #define IS_ROAD_CNT_POINTS 1 /* non-zero pixels of the binary image (entries of the point list) */
 #define IS_ROAD_SORT_MAX 8192 /* largest candidate capacity the one-workgroup sort handles (64 KiB of keys) */
 
-/* Histogram of one (row, frame): the scheme of k_vdisp_histogram with a frame index. */
+/* f3: v-disparity histogram, maximum, binarisation (RoadEstimationKernels.cu:25-60), of the single-frame entry
+ * (is_road_vdisparity: a batch of one whose counters are the caller's maximum) and of the batched one.
+ * The reference does one global atomicAdd per pixel and a second kernel of global atomicMax.  Here one workgroup
+ * owns one (row, frame): the row is read coalesced, binned with LDS atomics, written once, and its maximum goes
+ * to a single global atomicMax.  Integer counts and maxima do not depend on the order, so the result is identical. */
 __global__ __launch_bounds__(256) void k_road_histogram(const float* __restrict__ disparity,
                                                         int* __restrict__ vdisp, int* __restrict__ counters,
                                                         int rows, int cols, int max_dis) {
@@ -30,7 +33,11 @@ __global__ __launch_bounds__(256) void k_road_histogram(const float* __restrict_
     const float* src = disparity + ((size_t)f * rows + row) * cols;
     for (int j = threadIdx.x; j < cols; j += blockDim.x) {
         const float d = src[j];
-        if (d != 0) { /* RoadEstimationKernels.cu:33-37; NaN -> bin 0 explicitly, as k_vdisp_histogram */
+        if (d != 0) {
+            /* RoadEstimationKernels.cu:33-37: the bin is (int)d, truncation toward zero.  NaN goes to bin 0,
+             * stated here and not left to the conversion: the reference's float -> int of NaN gives 0 on its
+             * GPU, in C++ (int)NaN is undefined.  The bin guard (the reference is unchecked) is the float
+             * range (-1, max_dis), so +-inf and |d| >= 2^31 are never converted and fall in no bin. */
             if (d != d) atomicAdd(&bins[0], 1);
             else if (d > -1.0f && d < (float)max_dis) atomicAdd(&bins[(int)d], 1);
         }
@@ -48,8 +55,10 @@ __global__ __launch_bounds__(256) void k_road_histogram(const float* __restrict_
     if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(&counters[f * IS_ROAD_CNT + IS_ROAD_CNT_MAX], m);
 }
 
-/* Binarisation (the comparison of k_vdisp_binarize) and compaction of the non-zero pixels of each frame
- * into points[f][k] = (i << 16) | j.  One atomic per wave: the ballot's popcount reserves the wave's slots. */
+/* Binarisation (RoadEstimationKernels.cu:55-58) and, WITH_POINTS, compaction of the non-zero pixels of each
+ * frame into points[f][k] = (i << 16) | j (rows <= 32767).  One atomic per wave: the ballot's popcount reserves
+ * the wave's slots.  Without it neither the point counter nor `points` is read or written. */
+template <bool WITH_POINTS>
 __global__ __launch_bounds__(256) void k_road_binarize(const int* __restrict__ vdisp, uint8_t* __restrict__ binary,
                                                        int* __restrict__ counters, int* __restrict__ points,
                                                        float threshold, int rows, int max_dis) {
@@ -63,6 +72,7 @@ __global__ __launch_bounds__(256) void k_road_binarize(const int* __restrict__ v
         on = p > counters[f * IS_ROAD_CNT + IS_ROAD_CNT_MAX] * threshold;
         binary[off + idx] = on ? 255 : 0;
     }
+    if (!WITH_POINTS) return;
     const uint64_t mask = __ballot(on);
     if (mask == 0) return;
     const int lane = threadIdx.x & 63;
@@ -241,8 +251,20 @@ hipError_t isk_launch_road_vdisparity(const float* disparity, int* vdisp, uint8_
     hipLaunchKernelGGL(k_road_histogram, dim3(rows, n_images), dim3(256), sizeof(int) * max_dis, stream,
                        disparity, vdisp, counters, rows, cols, max_dis);
     const int n = rows * max_dis;
-    hipLaunchKernelGGL(k_road_binarize, dim3((n + 255) / 256, n_images), dim3(256), 0, stream, vdisp, binary,
+    hipLaunchKernelGGL(k_road_binarize<true>, dim3((n + 255) / 256, n_images), dim3(256), 0, stream, vdisp, binary,
                        counters, points, threshold, rows, max_dis);
+    return hipGetLastError();
+}
+
+/* One frame without a point list (any rows): *maximum, zero on entry, is frame 0's IS_ROAD_CNT_MAX. */
+hipError_t isk_launch_road_vdisparity_single(const float* disparity, int* vdisp, uint8_t* binary, int* maximum,
+                                             int rows, int cols, int max_dis, float threshold, hipStream_t stream) {
+    static_assert(IS_ROAD_CNT_MAX == 0, "the caller's int is entry 0 of frame 0's counters");
+    hipLaunchKernelGGL(k_road_histogram, dim3(rows, 1), dim3(256), sizeof(int) * max_dis, stream, disparity, vdisp,
+                       maximum, rows, cols, max_dis);
+    const int n = rows * max_dis;
+    hipLaunchKernelGGL(k_road_binarize<false>, dim3((n + 255) / 256, 1), dim3(256), 0, stream, vdisp, binary,
+                       maximum, nullptr, threshold, rows, max_dis);
     return hipGetLastError();
 }
 

@@ -6,7 +6,7 @@
  * kernels restructure the same arithmetic (bit-exactly, see DESIGN.md "Exact rewrites") as
  *
  *   is_k_frontend.hip   k_join_columns      A3   StixelsKernels.cu:980-1095   LDS-transposed
- *                       k_flip_and_pad, k_vdisp_*  
+ *                       k_flip_and_pad      (f3, the road estimation, is is_k_road.hip)
  *   is_k_prepare.hip    k_prepare_columns   A4-A6 StixelsKernels.cu:371-469 and
  *                                           StixelsKernels.h:73-103: per-row boundary records
  *                       k_prepare_fused     A4   StixelsKernels.cu:236-296, 959-978: the records + the

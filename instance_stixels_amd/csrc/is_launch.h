@@ -180,8 +180,6 @@ hipError_t isk_launch_join(const float* big, float* joined, int H, int W, int C,
                            float invalid, int n_images, hipStream_t stream);
 hipError_t isk_launch_flip_and_pad(const float* in, int32_t* out, int n, int CH, int Hs, int Ws, int P2S,
                                    hipStream_t stream);
-hipError_t isk_launch_vdisparity(const float* disparity, int* vdisp, int* maximum, uint8_t* binary, int rows,
-                                 int cols, int max_dis, float threshold, hipStream_t stream);
 
 /* is_k_pack.hip */
 hipError_t isk_launch_count_sections(const is_section* sections, int n_columns, int S, int32_t* counts,
@@ -198,6 +196,8 @@ hipError_t isk_set_lds_road_hough(int bytes);
 hipError_t isk_launch_road_vdisparity(const float* disparity, int* vdisp, uint8_t* binary, int* counters, int* points,
                                       int n_images, int rows, int cols, int max_dis, float threshold,
                                       hipStream_t stream);
+hipError_t isk_launch_road_vdisparity_single(const float* disparity, int* vdisp, uint8_t* binary, int* maximum,
+                                             int rows, int cols, int max_dis, float threshold, hipStream_t stream);
 hipError_t isk_launch_road_hough(const int* points, const int* counters, int* ncand, const float* tab, int2* cand,
                                  float* lines, int* votes, int* total, int* overflow, int n_images, int n_cells,
                                  int numangle, int numrho, int band, int threshold, int cap, int max_lines, float rho,

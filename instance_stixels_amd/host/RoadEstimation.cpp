@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <stdexcept>
+#include <string>
 
 static const float kPi = 3.1415926535897932384626433832795f; /* CV_PI as float */
 
@@ -103,26 +104,33 @@ void RoadEstimation::ReserveBatch(int n_images) { /* (under the caller's device 
     }
 }
 
+/* What ComputeBatch and ComputeBatchDevice share (under the caller's device guard): their refusals, the stream choice,
+ * the scratch, and v-disparity + Hough transform of the batch queued on that stream. */
+RoadEstimation::BatchLines RoadEstimation::EnqueueBatch(const char* who, const pixel_t* d_im, int n_images,
+                                                        bool outputs, void* stream) {
+    if (!m_is_initialized) throw std::invalid_argument(std::string("RoadEstimation::") + who + " before Initialize()");
+    if (n_images < 1 || !d_im || !outputs) throw std::invalid_argument(std::string(who) + ": empty batch or null pointer");
+    ReserveBatch(n_images);
+    BatchLines q;
+    q.stream = stream ? stream : m_stream;
+    q.d_total = (int*)d_batch_out.get();
+    q.d_overflow = q.d_total + m_batch_cap;
+    q.d_lines = (float*)(q.d_overflow + m_batch_cap);
+    IS_CHECK_RETURN(is_road_vdisparity_batch(m_batch_ctx, d_im, n_images, m_binThr, nullptr, nullptr, nullptr, q.stream));
+    IS_CHECK_RETURN(is_road_hough_batch(m_batch_ctx, n_images, m_HoughAccumThr, m_batch_lines, m_batch_candidates,
+                                        q.d_lines, nullptr, q.d_total, q.d_overflow, q.stream));
+    return q;
+}
+
 void RoadEstimation::ComputeBatchDevice(const pixel_t* d_im, int n_images, Stixels::RoadParameters* d_road,
                                         uint8_t* d_status, const Stixels::RoadParameters& fallback, void* stream) {
-    if (!m_is_initialized) throw std::invalid_argument("RoadEstimation::ComputeBatchDevice before Initialize()");
-    if (n_images < 1 || !d_im || !d_road || !d_status)
-        throw std::invalid_argument("ComputeBatchDevice: empty batch or null pointer");
     const DeviceGuard guard(m_ctx_device);
-    void* s = stream ? stream : m_stream;
-    const int L = m_batch_lines;
-    ReserveBatch(n_images);
-    const int cap = m_batch_cap;
-    int* d_total = (int*)d_batch_out.get();
-    int* d_overflow = d_total + cap;
-    float* d_lines = (float*)(d_overflow + cap);
-    IS_CHECK_RETURN(is_road_vdisparity_batch(m_batch_ctx, d_im, n_images, m_binThr, nullptr, nullptr, nullptr, s));
-    IS_CHECK_RETURN(is_road_hough_batch(m_batch_ctx, n_images, m_HoughAccumThr, L, m_batch_candidates, d_lines,
-                                        nullptr, d_total, d_overflow, s));
+    const BatchLines q = EnqueueBatch("ComputeBatchDevice", d_im, n_images, d_road && d_status, stream);
     static_assert(sizeof(Stixels::RoadParameters) == sizeof(is_road_params), "d_road holds is_road_params records");
     const is_road_params fb = {fallback.vhor, fallback.camera_tilt, fallback.camera_height, fallback.alpha_ground};
-    IS_CHECK_RETURN(is_road_choose_batch(m_batch_ctx, n_images, d_lines, d_total, d_overflow, L, m_cy, m_b, m_focal,
-                                         m_minPitch, m_maxPitch, fb, (is_road_params*)d_road, d_status, s));
+    IS_CHECK_RETURN(is_road_choose_batch(m_batch_ctx, n_images, q.d_lines, q.d_total, q.d_overflow, m_batch_lines, m_cy,
+                                         m_b, m_focal, m_minPitch, m_maxPitch, fb, (is_road_params*)d_road, d_status,
+                                         q.stream));
 }
 
 void RoadEstimation::PitchGate(float& min_pitch, float& max_pitch) {
@@ -134,8 +142,8 @@ int RoadEstimation::ChooseLineShared(float camera_center_y, float baseline, floa
                                      float max_pitch, const float* lines, int total, int overflow, int max_lines,
                                      const Stixels::RoadParameters& fallback, Stixels::RoadParameters& out,
                                      int* index) { /* k_road_choose, line by line */
-    const float step = kPi / 180;
-    const int numangle = (int)lrint((3.1415926535897932384626433832795 - 0.0) / step); /* as HoughLines */
+    const float step = IS_ROAD_HOUGH_THETA;
+    const int numangle = is_hough_numangle(step);
     out = fallback;
     if (index) *index = -1;
     const int nl = overflow ? 0 : std::min(total, max_lines);
@@ -160,19 +168,9 @@ int RoadEstimation::ChooseLineShared(float camera_center_y, float baseline, floa
 
 void RoadEstimation::ComputeBatch(const pixel_t* d_im, int n_images, Stixels::RoadParameters* out, uint8_t* ok,
                                   void* stream) {
-    if (!m_is_initialized) throw std::invalid_argument("RoadEstimation::ComputeBatch before Initialize()");
-    if (n_images < 1 || !d_im || !out || !ok) throw std::invalid_argument("ComputeBatch: empty batch or null pointer");
     const DeviceGuard guard(m_ctx_device);
-    void* s = stream ? stream : m_stream;
-    const int L = m_batch_lines;
-    ReserveBatch(n_images);
-    const int cap = m_batch_cap;
-    int* d_total = (int*)d_batch_out.get();
-    int* d_overflow = d_total + cap;
-    float* d_lines = (float*)(d_overflow + cap);
-    IS_CHECK_RETURN(is_road_vdisparity_batch(m_batch_ctx, d_im, n_images, m_binThr, nullptr, nullptr, nullptr, s));
-    IS_CHECK_RETURN(is_road_hough_batch(m_batch_ctx, n_images, m_HoughAccumThr, L, m_batch_candidates, d_lines,
-                                        nullptr, d_total, d_overflow, s));
+    void* s = EnqueueBatch("ComputeBatch", d_im, n_images, out && ok, stream).stream;
+    const int L = m_batch_lines, cap = m_batch_cap;
     const size_t bytes = sizeof(int) * 2 * (size_t)cap + sizeof(float) * 2 * (size_t)n_images * L;
     IS_CHECK_RETURN(is_memcpy_d2h(h_batch_out.get(), d_batch_out.get(), bytes, s));
     IS_CHECK_RETURN(is_stream_synchronize(s));
@@ -190,11 +188,7 @@ void RoadEstimation::ComputeBatch(const pixel_t* d_im, int n_images, Stixels::Ro
             lines[k] = std::make_pair(h_lines[((size_t)i * L + k) * 2], h_lines[((size_t)i * L + k) * 2 + 1]);
         bool found = !overflow[i] && ChooseLine(lines.data(), lines.size(), out[i]) >= 0;
         if (!found && (overflow[i] || total[i] > L)) { /* the lines the device kept do not decide it */
-            m_batch_binary.resize(cells);
-            IS_CHECK_RETURN(is_memcpy_d2h(m_batch_binary.data(), is_road_ctx_binary(m_batch_ctx) + i * cells,
-                                          cells, s));
-            IS_CHECK_RETURN(is_stream_synchronize(s));
-            lines = HoughLines(m_batch_binary.data(), m_rows, m_max_dis, 1.0f, kPi / 180, m_HoughAccumThr);
+            lines = FetchHoughLines(is_road_ctx_binary(m_batch_ctx) + i * cells, m_batch_binary, s);
             found = ChooseLine(lines.data(), lines.size(), out[i]) >= 0;
             m_batch_fallbacks++;
         }
@@ -211,7 +205,7 @@ int RoadEstimation::ChooseLine(float camera_center_y, float baseline, float foca
 }
 
 int RoadEstimation::ChooseLine(const std::pair<float, float>* lines, size_t n,
-                               Stixels::RoadParameters& out) const { /* ComputeHough's loop */
+                               Stixels::RoadParameters& out) const { /* RE.cu:155-176 */
     float rho, theta, horizonPoint, pitch, cameraHeight, slope;
     for (size_t k = 0; k < n; k++) {
         rho = std::abs(lines[k].first);
@@ -238,18 +232,25 @@ bool RoadEstimation::Compute(pixel_t* d_im) { /* RE.cu:104-138 */
     const DeviceGuard guard(m_ctx_device); /* (d_im lives on the object's device: Stixels::SetDevice(d) + SetDevice(d)) */
     IS_CHECK_RETURN(is_road_vdisparity(d_im, m_rows, m_cols, m_max_dis, m_binThr, d_vDisp.get(), d_maximum.get(),
                                        d_vDispBinary.get(), m_stream));
-    float rho, theta, horizonPoint, pitch, cameraHeight, slope;
-    bool ok = false;
-    if (ComputeHough(rho, theta, horizonPoint, pitch, cameraHeight, slope)) {
-        m_rho = rho;
-        m_theta = theta;
-        m_horizonPoint = (int)ceil(horizonPoint);
-        m_pitch = pitch;
-        m_cameraHeight = cameraHeight;
-        m_slope = slope;
-        ok = true;
-    }
-    return ok;
+    const auto lines = FetchHoughLines(d_vDispBinary.get(), m_vDisp, m_stream); /* RE.cu:140-153 */
+    Stixels::RoadParameters r;
+    const int k = ChooseLine(lines.data(), lines.size(), r);
+    if (k < 0) return false;
+    m_rho = std::abs(lines[k].first);
+    m_theta = lines[k].second;
+    m_horizonPoint = r.vhor;
+    m_pitch = r.camera_tilt;
+    m_cameraHeight = r.camera_height;
+    m_slope = r.alpha_ground;
+    return true;
+}
+
+std::vector<std::pair<float, float>> RoadEstimation::FetchHoughLines(const uint8_t* d_binary,
+                                                                     std::vector<uint8_t>& image, void* stream) {
+    image.resize((size_t)m_max_dis * m_rows);
+    IS_CHECK_RETURN(is_memcpy_d2h(image.data(), d_binary, image.size(), stream));
+    IS_CHECK_RETURN(is_stream_synchronize(stream));
+    return HoughLines(image.data(), m_rows, m_max_dis, IS_ROAD_HOUGH_RHO, IS_ROAD_HOUGH_THETA, m_HoughAccumThr);
 }
 
 /* OpenCV's HoughLinesStandard (the algorithm behind cv::HoughLines(image, lines, rho, theta,
@@ -259,17 +260,11 @@ std::vector<std::pair<float, float>> RoadEstimation::HoughLines(const uint8_t* i
                                                                 int cols, float rho, float theta,
                                                                 int threshold) {
     const int width = cols, height = rows;
-    const float irho = 1 / rho;
-    const double min_theta = 0, max_theta = 3.1415926535897932384626433832795;
-    const int numangle = (int)lrint((max_theta - min_theta) / theta);
-    const int numrho = (int)lrint(((width + height) * 2 + 1) / rho);
+    const float min_theta = 0;
+    const int numangle = is_hough_numangle(theta), numrho = is_hough_numrho(width, height, rho);
     std::vector<int> accum((size_t)(numangle + 2) * (numrho + 2), 0);
     std::vector<float> tabSin(numangle), tabCos(numangle);
-    float ang = (float)min_theta;
-    for (int n = 0; n < numangle; ang += theta, n++) {
-        tabSin[n] = (float)(sin((double)ang) * irho);
-        tabCos[n] = (float)(cos((double)ang) * irho);
-    }
+    is_hough_tables(numangle, rho, theta, tabSin.data(), tabCos.data());
     for (int i = 0; i < height; i++)
         for (int j = 0; j < width; j++)
             if (image[(size_t)i * width + j] != 0)
@@ -295,24 +290,9 @@ std::vector<std::pair<float, float>> RoadEstimation::HoughLines(const uint8_t* i
     for (int idx : sort_buf) {
         const int n = (int)floor(idx * scale) - 1;
         const int r = idx - (n + 1) * (numrho + 2) - 1;
-        lines.emplace_back((r - (numrho - 1) * 0.5f) * rho, (float)min_theta + n * theta);
+        lines.emplace_back((r - (numrho - 1) * 0.5f) * rho, min_theta + n * theta);
     }
     return lines;
-}
-
-bool RoadEstimation::ComputeHough(float& rho, float& theta, float& horizonPoint, float& pitch,
-                                  float& cameraHeight, float& slope) { /* RE.cu:140-176 */
-    /* (called from Compute, under its device guard) */
-    IS_CHECK_RETURN(is_memcpy_d2h(m_vDisp.data(), d_vDispBinary.get(), (size_t)m_max_dis * m_rows, m_stream));
-    IS_CHECK_RETURN(is_stream_synchronize(m_stream));
-    const auto lines = HoughLines(m_vDisp.data(), m_rows, m_max_dis, 1.0f, kPi / 180, m_HoughAccumThr);
-    for (const auto& l : lines) {
-        rho = std::abs(l.first);
-        theta = l.second;
-        ComputeCameraProperties(m_rows, rho, theta, horizonPoint, pitch, cameraHeight, slope);
-        if (pitch >= m_minPitch && pitch <= m_maxPitch) return true;
-    }
-    return false;
 }
 
 void RoadEstimation::ComputeCameraProperties(int vdisp_rows, const float rho, const float theta,

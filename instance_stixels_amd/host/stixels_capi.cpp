@@ -54,10 +54,10 @@ thread_local Pending<Stixels::InstanceObjectsView> g_objects;
 thread_local Pending<std::vector<int32_t>> g_gt_quads;
 
 /* road [n][4] = (vhor_image, camera_tilt, camera_height, alpha_ground) */
+Stixels::RoadParameters road_record(const float* r) { return Stixels::RoadParameters{(int)r[0], r[1], r[2], r[3]}; }
 std::vector<Stixels::RoadParameters> to_road(const float* road, int n) {
     std::vector<Stixels::RoadParameters> rp(n);
-    for (int i = 0; i < n; i++)
-        rp[i] = Stixels::RoadParameters{(int)road[4 * i], road[4 * i + 1], road[4 * i + 2], road[4 * i + 3]};
+    for (int i = 0; i < n; i++) rp[i] = road_record(road + 4 * i);
     return rp;
 }
 }  // namespace
@@ -752,7 +752,7 @@ int ish_compute_batch_road(void* h, int pairwise, int n_images, const float* d_b
 int ire_compute_batch_device(void* h, const float* d_disparity, int n, void* d_road, uint8_t* d_status,
                              const float* fallback4, void* stream) {
     return guard([&] {
-        const Stixels::RoadParameters fb = {(int)fallback4[0], fallback4[1], fallback4[2], fallback4[3]};
+        const Stixels::RoadParameters fb = road_record(fallback4);
         ((RoadEstimation*)h)->ComputeBatchDevice(d_disparity, n, (Stixels::RoadParameters*)d_road, d_status, fb,
                                                  stream);
     });
@@ -763,7 +763,7 @@ int ire_choose_line_shared(float cy, float baseline, float focal, int rows, cons
                            int overflow, int max_lines, const float* fallback4, void* out, int* index) {
     float lo, hi;
     RoadEstimation::PitchGate(lo, hi);
-    const Stixels::RoadParameters fb = {(int)fallback4[0], fallback4[1], fallback4[2], fallback4[3]};
+    const Stixels::RoadParameters fb = road_record(fallback4);
     return RoadEstimation::ChooseLineShared(cy, baseline, focal, rows, lo, hi, lines, total, overflow, max_lines, fb,
                                             *(Stixels::RoadParameters*)out, index);
 }
@@ -780,7 +780,7 @@ int ish_time_road_chain(void* h, void* hre, int device_chain, int pairwise, int 
     return guard([&] {
         Stixels* s = (Stixels*)h;
         RoadEstimation* r = (RoadEstimation*)hre;
-        const Stixels::RoadParameters fb = {(int)fallback4[0], fallback4[1], fallback4[2], fallback4[3]};
+        const Stixels::RoadParameters fb = road_record(fallback4);
         std::vector<Stixels::RoadParameters> rp(n_images);
         std::vector<uint8_t> ok(n_images);
         std::vector<StixelsData> out;

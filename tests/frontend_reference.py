@@ -1,5 +1,5 @@
 """Plain restatements of the small kernels in front of and behind the DP: JoinColumns (k_join_columns), the
-v-disparity histogram of the road estimation (k_vdisp_* / k_road_histogram / k_road_binarize) and the
+v-disparity histogram of the road estimation (k_road_histogram / k_road_binarize) and the
 compaction of the Section arrays (is_k_pack.hip).  numpy and Python only, fp32 in the kernels' operation
 order, no import from the product: the tests compare the device with these, bit for bit."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""k_vdisp_histogram / k_vdisp_binarize (is_k_frontend.hip) and k_road_histogram / k_road_binarize (is_k_road.hip)
+"""k_road_histogram / k_road_binarize (is_k_road.hip; the binarise without and with its point list)
 at their edges: NaN (bin 0, stated in the kernels), +-inf, values in (-1, 0), values <= -1, |d| >= 2^31, exact
 zeros, row lengths that are no multiple of the 256 threads and max_dis that is no multiple of 64, against
 frontend_reference.vdisparity -- exactly, through the single-frame entry and the batched one.  The CPU half
@@ -158,3 +158,29 @@ def test_both_entries_equal_the_restatement(shape):
                 assert np.array_equal(bn[k], want[i][1]) and np.array_equal(bn[k], single[i][1]), i
     finally:
         assert L.is_road_ctx_destroy(ctx) == 0
+
+
+TALL = (32768 + 8, 1, 2)    # more rows than the 15 bits the batched point list's (row << 16) | column holds
+
+
+@pytest.mark.gpu
+def test_single_frame_entry_takes_more_rows_than_the_point_list_packs():
+    """is_road_vdisparity builds no point list, so the row limit of is_road_ctx_create is not its own: a mixed
+    frame of _frames at TALL, with counted pixels in the rows past 32767, exactly against the restatement."""
+    import torch
+    from instance_stixels_amd import core
+    rows, cols, D = TALL
+    frame, want = _frames(TALL)[0], _want(TALL)[0]
+    assert np.isnan(frame).any() and np.isinf(frame).any() and (frame == 0).any()
+    assert want[0][32768:].any() and want[1][32768:].any() and not want[1][32768:].all()
+    L = core.lib()
+    ctx = ctypes.c_void_p()
+    assert L.is_road_ctx_create(ctypes.byref(ctx), rows, cols, D, 1, -1) != 0 and not ctx.value
+    d = _device(frame)
+    vd, mx, bn = Out((rows, D), np.int32), Out((1,), np.int32), Out((rows, D), np.uint8)
+    assert L.is_road_vdisparity(d.data_ptr(), rows, cols, D, ctypes.c_float(THR), vd.ptr, mx.ptr, bn.ptr,
+                                None) == 0, L.is_last_error()
+    torch.cuda.synchronize()
+    assert np.array_equal(vd.get(), want[0])
+    assert int(mx.get()[0]) == want[2]
+    assert np.array_equal(bn.get(), want[1])

@@ -5,7 +5,7 @@ Kernels are matched by name (instantiation order may move them within a file); l
 function's ordinal.  Prints per file the kernels that are missing, new or different and a digest of each; exit 1 on any."""
 import re, sys, hashlib
 FILES = ["is_k_unary", "is_k_unary_fast", "is_k_unary_path", "is_k_pairwise", "is_k_prepare", "is_k_backtrace",
-         "is_k_head", "is_k_head_backward"]
+         "is_k_head", "is_k_head_backward", "is_k_road", "is_k_frontend"]
 SUF = "-hip-amdgcn-amd-amdhsa-gfx950.s"
 
 def kernels(path):
