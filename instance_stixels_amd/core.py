@@ -5,6 +5,8 @@ library is missing -- there is no CPU fallback.  PyTorch is used only as the own
 memory / streams (plumbing); every compute call goes through the C ABI.
 """
 import ctypes
+import functools
+import math
 import os
 
 import numpy as np
@@ -349,6 +351,21 @@ ROAD_DTYPE = np.dtype([("vhor", np.int32), ("tilt", np.float32), ("height", np.f
 ROAD_NONE, ROAD_OK, ROAD_UNDECIDED, ROAD_HORIZON = 0, 1, 2, 3   # d_status of is_road_choose_batch
 
 
+# The entry points of the C ABI with the signature (const X_args*, void* stream) and the class of X here: lib() sets
+# their argtypes from this table, and _args_ptr makes the `_ptr` functions that only fill the struct.
+_ARGS_ENTRY = {
+    "is_render_sections": RenderArgs, "is_instance_overlap": InstanceOverlapArgs, "is_stixel_world": WorldArgs,
+    "is_assign_instances_gt": AssignGtArgs, "is_instance_objects": InstanceObjectsArgs,
+    "is_cluster_instance_disparity": InstanceDisparityArgs, "is_gt_instance_targets": GtTargetsArgs,
+    "is_offset_loss": OffsetLossArgs, "is_segmentation_head": SegmentationHeadArgs,
+    "is_segmentation_head_backward": SegmentationHeadBackwardArgs, "is_semantic_nll": SemanticNllArgs,
+    "is_cnn_label_maps": CnnLabelArgs, "is_semantic_nll_up": SemanticNllUpArgs, "is_conv3x3_bn_relu": Conv3x3Args,
+    "is_conv_bn": ConvBnArgs, "is_conv_bn_stride": ConvBnStrideArgs, "is_stem": StemArgs,
+    "is_conv_bn_backward": ConvBnBackwardArgs, "is_conv_bn_stride_backward": ConvBnStrideBackwardArgs,
+    "is_stem_backward": StemBackwardArgs,
+}
+
+
 class CoreError(RuntimeError):
     pass
 
@@ -400,60 +417,42 @@ def lib():
         L.is_ctx_set_ground_model.argtypes = [vp, ctypes.POINTER(GroundParams), vp, ci]
         L.is_compute_road.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, ci, vp]
         L.is_debug_read_ground.argtypes = [vp, ci, vp, ctypes.POINTER(ci)]
+        for entry, args_cls in _ARGS_ENTRY.items():
+            getattr(L, entry).argtypes = [ctypes.POINTER(args_cls), vp]
         L.is_cluster_instances.argtypes = [vp, ctypes.POINTER(InstanceBuffers), vp]
         L.is_section_instance_labels.argtypes = [ctypes.POINTER(InstanceBuffers), ci, ci, ci, vp, vp]
-        L.is_render_sections.argtypes = [ctypes.POINTER(RenderArgs), vp]
-        L.is_instance_overlap.argtypes = [ctypes.POINTER(InstanceOverlapArgs), vp]
         L.is_pack_overlap_records.argtypes = [vp, vp, ci, ci, vp, vp]
-        L.is_stixel_world.argtypes = [ctypes.POINTER(WorldArgs), vp]
-        L.is_assign_instances_gt.argtypes = [ctypes.POINTER(AssignGtArgs), vp]
         L.is_pack_section_labels.argtypes = [vp, ci, ci, ci, ci, vp, vp]
-        L.is_instance_objects.argtypes = [ctypes.POINTER(InstanceObjectsArgs), vp]
         L.is_compute_sweep.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, ci, vp, vp, vp]
         L.is_recluster.argtypes = [vp, vp, ci, cf, ci, ci, vp, vp]
-        L.is_cluster_instance_disparity.argtypes = [ctypes.POINTER(InstanceDisparityArgs), vp]
         L.is_instance_disparity_scratch_bytes.argtypes = [ci, ci, ci, ci]
         L.is_instance_disparity_scratch_bytes.restype = ctypes.c_size_t
         L.is_mode_downsample.argtypes = [vp, ci, ci, ci, ci, vp, vp]
         L.is_gt_targets_scratch_bytes.argtypes = [ci, ci, ci, ci, ci]
         L.is_gt_targets_scratch_bytes.restype = ctypes.c_size_t
-        L.is_gt_instance_targets.argtypes = [ctypes.POINTER(GtTargetsArgs), vp]
         L.is_offset_loss_scratch_bytes.argtypes = [ci, ci, ci, ci, ci]
         L.is_offset_loss_scratch_bytes.restype = ctypes.c_size_t
-        L.is_offset_loss.argtypes = [ctypes.POINTER(OffsetLossArgs), vp]
-        L.is_segmentation_head.argtypes = [ctypes.POINTER(SegmentationHeadArgs), vp]
         L.is_segmentation_head_backward_scratch_bytes.argtypes = [ci, ci, ci, ci, ci]
         L.is_segmentation_head_backward_scratch_bytes.restype = ctypes.c_size_t
-        L.is_segmentation_head_backward.argtypes = [ctypes.POINTER(SegmentationHeadBackwardArgs), vp]
         L.is_semantic_nll_scratch_bytes.argtypes = [ci, ci, ci]
         L.is_semantic_nll_scratch_bytes.restype = ctypes.c_size_t
-        L.is_semantic_nll.argtypes = [ctypes.POINTER(SemanticNllArgs), vp]
-        L.is_cnn_label_maps.argtypes = [ctypes.POINTER(CnnLabelArgs), vp]
         L.is_semantic_nll_up_scratch_bytes.argtypes = [ci, ci, ci, ci]
         L.is_semantic_nll_up_scratch_bytes.restype = ctypes.c_size_t
-        L.is_semantic_nll_up.argtypes = [ctypes.POINTER(SemanticNllUpArgs), vp]
         L.is_conv3x3_packed_bytes.argtypes = [ci, ci, ci]
         L.is_conv3x3_packed_bytes.restype = ctypes.c_size_t
         L.is_conv3x3_pack_weights.argtypes = [vp, ci, ci, ci, vp, vp]
-        L.is_conv3x3_bn_relu.argtypes = [ctypes.POINTER(Conv3x3Args), vp]
         L.is_conv_packed_bytes.argtypes = [ci, ci, ci, ci]
         L.is_conv_packed_bytes.restype = ctypes.c_size_t
         L.is_conv_pack_weights.argtypes = [vp, ci, ci, ci, ci, vp, vp]
-        L.is_conv_bn.argtypes = [ctypes.POINTER(ConvBnArgs), vp]
-        L.is_conv_bn_stride.argtypes = [ctypes.POINTER(ConvBnStrideArgs), vp]
         L.is_stem_packed_bytes.argtypes = [ci]
         L.is_stem_packed_bytes.restype = ctypes.c_size_t
         L.is_stem_pack_weights.argtypes = [vp, vp, ci, vp, vp]
-        L.is_stem.argtypes = [ctypes.POINTER(StemArgs), vp]
         L.is_conv_bn_backward_scratch_bytes.argtypes = [ci, ci, ci, ci, ci, ci, ci]
         L.is_conv_bn_backward_scratch_bytes.restype = ctypes.c_size_t
-        L.is_conv_bn_backward.argtypes = [ctypes.POINTER(ConvBnBackwardArgs), vp]
         L.is_conv_bn_stride_backward_scratch_bytes.argtypes = [ci, ci, ci, ci, ci, ci, ci, ci]
         L.is_conv_bn_stride_backward_scratch_bytes.restype = ctypes.c_size_t
-        L.is_conv_bn_stride_backward.argtypes = [ctypes.POINTER(ConvBnStrideBackwardArgs), vp]
         L.is_stem_backward_scratch_bytes.argtypes = [ci, ci, ci, ci, ci]
         L.is_stem_backward_scratch_bytes.restype = ctypes.c_size_t
-        L.is_stem_backward.argtypes = [ctypes.POINTER(StemBackwardArgs), vp]
         L.is_stem_backward_constant.argtypes = [ci]
         L.is_host_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
         L.is_host_free.argtypes = [vp]
@@ -941,6 +940,106 @@ def road_choose_batch_ptr(road_ctx, n_images, d_lines, d_total, d_overflow, max_
                                       baseline, focal, min_pitch, max_pitch, fb, d_road, d_status, stream)
 
 
+def _with_reserved(cls, fields):
+    reserved = fields.pop("reserved", None)
+    a = cls(**fields)
+    if reserved is not None:
+        for i, v in enumerate(reserved):
+            a.reserved[i] = int(v)
+    return a
+
+
+def _args_ptr(entry, **defaults):
+    """The function `entry`_ptr (without "is_") of an entry point of _ARGS_ENTRY that takes nothing but the struct:
+    (stream=0, **fields) -> the return code.  defaults: field values other than the zeros of ctypes."""
+    cls = _ARGS_ENTRY[entry]
+    fill = _with_reserved if hasattr(cls, "reserved") else lambda cls, fields: cls(**fields)
+
+    def ptr(stream=0, **fields):
+        a = fill(cls, {**defaults, **fields})
+        return getattr(lib(), entry)(ctypes.byref(a), ctypes.c_void_p(int(stream)))
+    ptr.__name__ = ptr.__qualname__ = entry[3:] + "_ptr"
+    ptr.__doc__ = (f"{entry} on raw device pointers (ints): fields are those of {cls.__name__}" +
+                   "".join(f" ({k} defaults to {v} here)" for k, v in defaults.items()) +
+                   ".  Asynchronous on `stream`; returns the return code and raises nothing (the tests check IS_EINVAL).")
+    return ptr
+
+
+gt_instance_targets_ptr = _args_ptr("is_gt_instance_targets")
+offset_loss_ptr = _args_ptr("is_offset_loss")
+segmentation_head_ptr = _args_ptr("is_segmentation_head", clamp_channel=-1)
+segmentation_head_backward_ptr = _args_ptr("is_segmentation_head_backward")
+semantic_nll_ptr = _args_ptr("is_semantic_nll")
+semantic_nll_up_ptr = _args_ptr("is_semantic_nll_up")
+conv3x3_bn_relu_ptr = _args_ptr("is_conv3x3_bn_relu")
+conv_bn_ptr = _args_ptr("is_conv_bn")
+conv_bn_stride_ptr = _args_ptr("is_conv_bn_stride")
+stem_ptr = _args_ptr("is_stem")
+conv_bn_backward_ptr = _args_ptr("is_conv_bn_backward")
+conv_bn_stride_backward_ptr = _args_ptr("is_conv_bn_stride_backward")
+stem_backward_ptr = _args_ptr("is_stem_backward")
+
+
+@functools.lru_cache(maxsize=None)
+def _guard_patterns():
+    """{torch dtype: (the allocation's dtype, the fill value, the pattern as _Fresh.guards() gives it)}; made on first
+    use, as torch is imported late."""
+    import torch
+    half = (torch.int16, 0x5A5A, np.uint16(0x5A5A))
+    return {torch.float32: (torch.float32, -12345.0, np.float32(-12345.0)), torch.float16: half, torch.bfloat16: half,
+            torch.int32: (torch.int32, 0x5A5A5A5A, np.int32(0x5A5A5A5A)),
+            torch.int64: (torch.int64, 0x5A5A5A5A5A5A5A5A, np.int64(0x5A5A5A5A5A5A5A5A)),
+            torch.uint8: (torch.uint8, 0xA5, np.uint8(0xA5))}
+
+
+class _Fresh:
+    """The tensors one call of an entry point allocates on `dev`.  canary = 0: plain torch.empty, nothing is recorded.
+    canary > 0: every tensor is the middle of one torch.full allocation with that many guard elements of the dtype's
+    pattern in front and behind, and guards() reads them back.  A half's pattern is given as its 16 bits, 0x5A5A, a
+    finite value in both half formats, so its allocation is int16 and the tensor reinterprets it."""
+    def __init__(self, dev, canary):
+        self.dev, self.g, self._named = dev, int(canary), {}
+
+    def new(self, name, shape, dtype, g=None):
+        """A tensor of `shape`, recorded as `name`; g: a guard length other than the canary."""
+        import torch
+        g = self.g if g is None else g
+        if not g:
+            return torch.empty(shape, dtype=dtype, device=self.dev)
+        whole, fill, pattern = _guard_patterns()[dtype]
+        numel = math.prod(shape)
+        full = torch.full((numel + 2 * g,), fill, dtype=whole, device=self.dev)
+        self._named[name] = (full, g, pattern)
+        flat = full[g: g + numel]
+        return (flat if whole is dtype else flat.view(dtype)).view(shape)
+
+    def rows(self, rows):
+        """new() for the wanted ones of the rows (name, want, shape, dtype): ({name: tensor}, {name: data pointer,
+        None where not wanted})."""
+        out, ptr = {}, {}
+        for name, want, shape, dtype in rows:
+            ptr[name] = None
+            if want:
+                out[name] = self.new(name, shape, dtype)
+                ptr[name] = out[name].data_ptr()
+        return out, ptr
+
+    def scratch(self, nbytes):
+        """The uint8 scratch of a call, recorded as "scratch".  Its guard is whole 16 bytes, which keeps it 16-byte
+        aligned (torch's allocations are)."""
+        import torch
+        return self.new("scratch", (nbytes,), torch.uint8, (self.g + 15) // 16 * 16)
+
+    def guards(self):
+        """{name: (front, back, pattern)} as numpy copies of the guard elements (one synchronisation)."""
+        import torch
+        out = {}
+        for name, (full, g, pattern) in self._named.items():
+            h = full.view(torch.uint8).cpu().numpy().view(pattern.dtype)
+            out[name] = (h[:g].copy(), h[h.size - g:].copy(), pattern)
+        return out
+
+
 def flip_and_pad(cnn_out, rows_power2_segmentation, device=0):
     """CNN output [n][CH][Hs][Ws] float32 (numpy) -> DP input [n][Ws][CH][P2S] int32 (numpy)."""
     import torch
@@ -966,13 +1065,6 @@ def gt_targets_scratch_bytes(n_images, rows, cols, with_disparity=False, capacit
     """is_gt_targets_scratch_bytes: the scratch a call of that shape needs (0: a shape the call refuses)."""
     return int(lib().is_gt_targets_scratch_bytes(int(n_images), int(rows), int(cols), int(bool(with_disparity)),
                                                  int(capacity)))
-
-
-def gt_instance_targets_ptr(stream=0, **fields):
-    """is_gt_instance_targets on raw device pointers (ints): fields are those of GtTargetsArgs.  Asynchronous on
-    `stream`; returns the return code and raises nothing (the tests check IS_EINVAL)."""
-    a = GtTargetsArgs(**fields)
-    return lib().is_gt_instance_targets(ctypes.byref(a), ctypes.c_void_p(int(stream)))
 
 
 def _torch_dtype_code(t):
@@ -1129,13 +1221,6 @@ def offset_loss_scratch_bytes(n_images, planes, rows8, cols8, capacity=0):
     return int(lib().is_offset_loss_scratch_bytes(int(n_images), int(planes), int(rows8), int(cols8), int(capacity)))
 
 
-def offset_loss_ptr(stream=0, **fields):
-    """is_offset_loss on raw device pointers (ints): fields are those of OffsetLossArgs.  Asynchronous on `stream`;
-    returns the return code and raises nothing (the tests check IS_EINVAL)."""
-    a = OffsetLossArgs(**fields)
-    return lib().is_offset_loss(ctypes.byref(a), ctypes.c_void_p(int(stream)))
-
-
 def offset_loss(prediction, ids8, disparity8_u16=None, weights=OFFSET_LOSS_WEIGHTS, abs_variance=False, capacity=0,
                 check=True, return_key_count=False):
     """The reference's OffsetLossSL / DisparityOffsetLossSL of a batch with the gradient (is_offset_loss,
@@ -1192,15 +1277,6 @@ def offset_loss(prediction, ids8, disparity8_u16=None, weights=OFFSET_LOSS_WEIGH
     return (loss5, terms, grad, count) if return_key_count else (loss5, terms, grad)
 
 
-def segmentation_head_ptr(stream=0, **fields):
-    """is_segmentation_head on raw device pointers (ints): fields are those of SegmentationHeadArgs (clamp_channel
-    defaults to -1 here).  Asynchronous on `stream`; returns the return code and raises nothing (the tests check
-    IS_EINVAL)."""
-    fields.setdefault("clamp_channel", -1)
-    a = _with_reserved(SegmentationHeadArgs, fields)
-    return lib().is_segmentation_head(ctypes.byref(a), ctypes.c_void_p(int(stream)))
-
-
 def segmentation_head(features, weight, bias, n_classes, rows_power2_segmentation, want_cnn_out=False, clamp=None,
                       device=0, want_segmentation=True, canary=0):
     """The CNN's segmentation head of a batch in one launch (is_segmentation_head, instance_stixels_core.h f13): the
@@ -1238,27 +1314,20 @@ def segmentation_head(features, weight, bias, n_classes, rows_power2_segmentatio
     P2S = int(rows_power2_segmentation)
     if not want_segmentation:
         want_cnn_out = True
-    g = int(canary)
-    pat_i = np.int32(0x5A5A5A5A)
     with torch.cuda.device(dev):
-        named, seg, cnn = {}, None, None
-        if want_segmentation:
-            full, flat = _guarded(n * Ws * CH * P2S, torch.int32, dev, g, int(pat_i))
-            named["segmentation"], seg = (full, pat_i), flat.view(n, Ws, CH, P2S)
-        if want_cnn_out:
-            full, flat, pat_f = _guarded_float(n * CH * Hs * Ws, torch.float32, dev, g)
-            named["cnn_out"], cnn = (full, pat_f), flat.view(n, CH, Hs, Ws)
+        fresh = _Fresh(dev, canary)
+        out, ptr = fresh.rows((("segmentation", want_segmentation, (n, Ws, CH, P2S), torch.int32),
+                               ("cnn_out", want_cnn_out, (n, CH, Hs, Ws), torch.float32)))
         a = SegmentationHeadArgs(d_features=x.data_ptr(), dtype=codes[x.dtype], n_images=n, K=K, rows8=Hs, cols8=Ws,
                                  d_weight=w.data_ptr(), d_bias=b.data_ptr(), n_classes=int(n_classes),
                                  n_regression=CH - int(n_classes), rows_power2_segmentation=P2S, clamp_channel=-1,
-                                 d_cnn_out=cnn.data_ptr() if cnn is not None else None,
-                                 d_segmentation=seg.data_ptr() if seg is not None else None)
+                                 d_cnn_out=ptr["cnn_out"], d_segmentation=ptr["segmentation"])
         if clamp is not None:
             a.clamp_channel, a.clamp_lo, a.clamp_hi = int(clamp[0]), float(clamp[1]), float(clamp[2])
         _check(lib().is_segmentation_head(ctypes.byref(a), _current_stream(dev)), "is_segmentation_head")
-        out = [t for t in (seg, cnn) if t is not None]
-        if g:
-            out.append(_guards(named, g, g))
+        out = list(out.values())
+        if fresh.g:
+            out.append(fresh.guards())
     return out[0] if len(out) == 1 else tuple(out)
 
 
@@ -1335,17 +1404,16 @@ def _conv_launch(prefix, entry, args_cls, with_kernel, features, packed, scale, 
         # (the Python packer has the C one's name without "is_")
         raise CoreError(f"packed must be {prefix[3:]}_pack_weights' uint8 tensor for channels_out {cout}, channels_in "
                         f"{cin}{f', kernel {kernel}' if with_kernel else ''} and {x.dtype} on the features' device")
-    g = int(canary)
     with torch.cuda.device(dev):
-        full, flat, pattern = _guarded_float(n * cout * Ho * Wo, odt, dev, g)
-        out = flat.view(n, cout, Ho, Wo)
+        fresh = _Fresh(dev, canary)
+        out = fresh.new("out", (n, cout, Ho, Wo), odt)
         a = args_cls(d_features=x.data_ptr(), dtype=codes[x.dtype], n_images=n, channels_in=cin, channels_out=cout,
                      dilation=int(dilation), d_packed=packed.data_ptr(), d_scale=sc.data_ptr(),
                      d_shift=sh.data_ptr(), relu=int(bool(relu)), d_out=out.data_ptr(),
                      out_dtype=HEAD_F32 if odt == torch.float32 else codes[x.dtype], **extents, **own)
         _check(getattr(lib(), entry)(ctypes.byref(a), _current_stream(dev)), entry)
-        if g:
-            return out, _guards({"out": (full, pattern)}, g, g)
+        if fresh.g:
+            return out, fresh.guards()
     return out
 
 
@@ -1360,13 +1428,6 @@ def conv3x3_pack_weights(weight, dtype, device=0):
     device tensor of conv3x3_packed_bytes(...) bytes (on the weight's device if it is a device tensor, else on
     cuda:`device`); enqueued on the current torch stream, once per model."""
     return _conv_pack("is_conv3x3", False, weight, dtype, device)
-
-
-def conv3x3_bn_relu_ptr(stream=0, **fields):
-    """is_conv3x3_bn_relu on raw device pointers (ints): fields are those of Conv3x3Args.  Asynchronous on `stream`;
-    returns the return code and raises nothing (the tests check IS_EINVAL)."""
-    a = _with_reserved(Conv3x3Args, fields)
-    return lib().is_conv3x3_bn_relu(ctypes.byref(a), ctypes.c_void_p(int(stream)))
 
 
 def conv3x3_bn_relu(features, packed, scale, shift, dilation, relu=True, out_dtype=None, canary=0):
@@ -1399,13 +1460,6 @@ def conv_pack_weights(weight, dtype, device=0):
     return _conv_pack("is_conv", True, weight, dtype, device)
 
 
-def conv_bn_ptr(stream=0, **fields):
-    """is_conv_bn on raw device pointers (ints): fields are those of ConvBnArgs.  Asynchronous on `stream`; returns
-    the return code and raises nothing (the tests check IS_EINVAL)."""
-    a = _with_reserved(ConvBnArgs, fields)
-    return lib().is_conv_bn(ctypes.byref(a), ctypes.c_void_p(int(stream)))
-
-
 def conv_bn(features, packed, scale, shift, kernel, dilation=1, residual=None, relu=True, out_dtype=None, canary=0):
     """A 3x3 (dilated, padding = dilation) or 1x1 convolution without bias, stride 1, with folded BatchNorm, an
     optional residual added in fp32 between the BatchNorm and the ReLU, and an optional ReLU, of a batch in one launch
@@ -1421,13 +1475,6 @@ def conv_bn(features, packed, scale, shift, kernel, dilation=1, residual=None, r
     canary > 0: as conv3x3_bn_relu, {"out": (front, back, pattern)} is returned second (one synchronisation)."""
     return _conv_launch("is_conv", "is_conv_bn", ConvBnArgs, True, features, packed, scale, shift, kernel, dilation,
                         residual, relu, out_dtype, canary)
-
-
-def conv_bn_stride_ptr(stream=0, **fields):
-    """is_conv_bn_stride on raw device pointers (ints): fields are those of ConvBnStrideArgs.  Asynchronous on
-    `stream`; returns the return code and raises nothing (the tests check IS_EINVAL)."""
-    a = _with_reserved(ConvBnStrideArgs, fields)
-    return lib().is_conv_bn_stride(ctypes.byref(a), ctypes.c_void_p(int(stream)))
 
 
 def conv_bn_stride(features, packed, scale, shift, kernel, stride, dilation=1, residual=None, relu=True, out_dtype=None,
@@ -1473,13 +1520,6 @@ def stem_pack_weights(w0, w1, dtype, device=0):
     return packed
 
 
-def stem_ptr(stream=0, **fields):
-    """is_stem on raw device pointers (ints): fields are those of StemArgs.  Asynchronous on `stream`; returns the
-    return code and raises nothing (the tests check IS_EINVAL)."""
-    a = _with_reserved(StemArgs, fields)
-    return lib().is_stem(ctypes.byref(a), ctypes.c_void_p(int(stream)))
-
-
 def stem(image, lut, packed, scale0, shift0, scale1, shift1, want_mid=False, canary=0):
     """The backbone's stem of a batch in one launch (is_stem, instance_stixels_core.h f20): the table look-up of the
     image's bytes, layer0 (7x7, 3 -> 16, folded BatchNorm, ReLU) and layer1 (3x3, 16 -> 16, folded BatchNorm, ReLU),
@@ -1511,79 +1551,23 @@ def stem(image, lut, packed, scale0, shift0, scale1, shift1, want_mid=False, can
         raise CoreError("scale0, shift0, scale1 and shift1 must hold 16 channels each")
     x, table = image.contiguous(), lut.contiguous()
     n, H, W = (int(v) for v in x.shape[:3])
-    g = int(canary)
     with torch.cuda.device(dev):
-        full, flat, pattern = _guarded_float(n * 16 * H * W, dtype, dev, g)
-        out, named = flat.view(n, 16, H, W), {"out": (full, pattern)}
-        mid = None
-        if want_mid:
-            full_mid, flat_mid, _ = _guarded_float(n * 16 * H * W, dtype, dev, g)
-            mid, named["mid"] = flat_mid.view(n, 16, H, W), (full_mid, pattern)
+        fresh = _Fresh(dev, canary)
+        ret, ptr = fresh.rows((("out", True, (n, 16, H, W), dtype), ("mid", want_mid, (n, 16, H, W), dtype)))
         a = StemArgs(d_image=x.data_ptr(), n_images=n, rows=H, cols=W, d_lut=table.data_ptr(), dtype=codes[dtype],
                      d_packed=packed.data_ptr(), d_scale0=folds[0].data_ptr(), d_shift0=folds[1].data_ptr(),
-                     d_scale1=folds[2].data_ptr(), d_shift1=folds[3].data_ptr(),
-                     d_mid=mid.data_ptr() if want_mid else None, d_out=out.data_ptr())
+                     d_scale1=folds[2].data_ptr(), d_shift1=folds[3].data_ptr(), d_mid=ptr["mid"], d_out=ptr["out"])
         _check(lib().is_stem(ctypes.byref(a), _current_stream(dev)), "is_stem")
-        ret = (out, mid) if want_mid else (out,)
-        if g:
-            ret = ret + (_guards(named, g, g),)
+        ret = tuple(ret.values())
+        if fresh.g:
+            ret = ret + (fresh.guards(),)
     return ret if len(ret) > 1 else ret[0]
-
-
-def _with_reserved(cls, fields):
-    reserved = fields.pop("reserved", None)
-    a = cls(**fields)
-    if reserved is not None:
-        for i, v in enumerate(reserved):
-            a.reserved[i] = int(v)
-    return a
-
-
-def _guarded(numel, dtype, dev, g, pattern):
-    """A flat device tensor of numel elements, with g guard elements of `pattern` in front and behind when g > 0:
-    (the whole allocation or None, the view of the numel elements)."""
-    import torch
-    if not g:
-        return None, torch.empty((numel,), dtype=dtype, device=dev)
-    full = torch.full((numel + 2 * g,), pattern, dtype=dtype, device=dev)
-    return full, full[g: g + numel]
-
-
-def _guarded_float(numel, dtype, dev, g):
-    """_guarded for an output of float32 or of a half dtype, with the pattern of each: (the whole allocation or None,
-    the view of the numel elements in `dtype`, the pattern as _guards takes it).  A half's pattern is given as its 16
-    bits, 0x5A5A, a finite value in both half formats, so the allocation is int16 and the view reinterprets it."""
-    import torch
-    if dtype == torch.float32:
-        pattern = np.float32(-12345.0)
-        return _guarded(numel, dtype, dev, g, float(pattern)) + (pattern,)
-    pattern = np.uint16(0x5A5A)
-    full, flat = _guarded(numel, torch.int16, dev, g, int(pattern))
-    return full, flat.view(dtype), pattern
-
-
-def _guards(named, g, g_scratch):
-    """{name: (front, back, pattern)} as numpy copies of the guard elements (one synchronisation)."""
-    import torch
-    out = {}
-    for name, (full, pattern) in named.items():
-        h = full.view(torch.uint8).cpu().numpy().view(np.asarray(pattern).dtype)
-        k = g_scratch if name == "scratch" else g
-        out[name] = (h[:k].copy(), h[h.size - k:].copy(), pattern)
-    return out
 
 
 def segmentation_head_backward_scratch_bytes(n_images, K, rows8, cols8, channels):
     """is_segmentation_head_backward_scratch_bytes: the scratch a call of that shape needs (0: a refused shape)."""
     return int(lib().is_segmentation_head_backward_scratch_bytes(int(n_images), int(K), int(rows8), int(cols8),
                                                                  int(channels)))
-
-
-def segmentation_head_backward_ptr(stream=0, **fields):
-    """is_segmentation_head_backward on raw device pointers (ints): fields are those of SegmentationHeadBackwardArgs.
-    Asynchronous on `stream`; returns the return code and raises nothing (the tests check IS_EINVAL)."""
-    a = _with_reserved(SegmentationHeadBackwardArgs, fields)
-    return lib().is_segmentation_head_backward(ctypes.byref(a), ctypes.c_void_p(int(stream)))
 
 
 def segmentation_head_backward(features, weight, cnn_out, grad_out, n_classes, want_features=True, want_weight=True,
@@ -1624,30 +1608,17 @@ def segmentation_head_backward(features, weight, cnn_out, grad_out, n_classes, w
     if gy.device != dev or gy.dtype != torch.float32 or tuple(gy.shape) != shape:
         raise CoreError(f"grad_out must be a float32 tensor {shape} on the features' device")
     gy, gy_stride = _frame_planes(gy.detach(), CH)
-    frame = CH * Hs * Ws
     if not (want_features or want_weight or want_bias or want_logits):
         raise CoreError("no gradient is asked for")
-    g = int(canary)
     with torch.cuda.device(dev):
         nbytes = _scratch_or_raise(segmentation_head_backward_scratch_bytes,
                                    dict(n_images=n, K=K, rows8=Hs, cols8=Ws, channels=CH))
-        named, out = {}, {}
-        ptr = {"features": None, "weight": None, "bias": None, "logits": None}
-        for name, want, numel, view, dtype in (
-                ("features", want_features, n * K * Hs * Ws, (n, K, Hs, Ws), x.dtype),
-                ("weight", want_weight, CH * K, (CH, K), torch.float32),
-                ("bias", want_bias, CH, (CH,), torch.float32),
-                ("logits", want_logits, n * frame, shape, torch.float32)):
-            if not want:
-                continue
-            full, t, pat = _guarded_float(numel, dtype, dev, g)
-            named[name] = (full, pat)
-            out[name] = t.view(view)
-            ptr[name] = t.data_ptr()
-        # (16 guard bytes keep the scratch 16-byte aligned; torch's allocations are)
-        gs = (g + 15) // 16 * 16
-        sfull, scratch = _guarded(nbytes, torch.uint8, dev, gs, 0xA5)
-        named["scratch"] = (sfull, np.uint8(0xA5))
+        fresh = _Fresh(dev, canary)
+        out, ptr = fresh.rows((("features", want_features, (n, K, Hs, Ws), x.dtype),
+                               ("weight", want_weight, (CH, K), torch.float32),
+                               ("bias", want_bias, (CH,), torch.float32),
+                               ("logits", want_logits, shape, torch.float32)))
+        scratch = fresh.scratch(nbytes)
         a = SegmentationHeadBackwardArgs(
             d_features=x.data_ptr(), dtype=codes[x.dtype], n_images=n, K=K, rows8=Hs, cols8=Ws, d_weight=w.data_ptr(),
             n_classes=int(n_classes), n_regression=CH - int(n_classes), d_cnn_out=y.data_ptr(),
@@ -1656,8 +1627,8 @@ def segmentation_head_backward(features, weight, cnn_out, grad_out, n_classes, w
             d_scratch=scratch.data_ptr(), scratch_bytes=nbytes)
         _check(lib().is_segmentation_head_backward(ctypes.byref(a), _current_stream(dev)),
                "is_segmentation_head_backward")
-        if g:
-            out["guards"] = _guards(named, g, gs)
+        if fresh.g:
+            out["guards"] = fresh.guards()
     return out
 
 
@@ -1665,13 +1636,6 @@ def conv_bn_backward_scratch_bytes(n_images, channels_in, channels_out, rows8, c
     """is_conv_bn_backward_scratch_bytes: the scratch a call of that shape needs (0: a refused shape)."""
     return int(lib().is_conv_bn_backward_scratch_bytes(int(n_images), int(channels_in), int(channels_out), int(rows8),
                                                        int(cols8), int(kernel), int(dtype)))
-
-
-def conv_bn_backward_ptr(stream=0, **fields):
-    """is_conv_bn_backward on raw device pointers (ints): fields are those of ConvBnBackwardArgs.  Asynchronous on
-    `stream`; returns the return code and raises nothing (the tests check IS_EINVAL)."""
-    a = _with_reserved(ConvBnBackwardArgs, fields)
-    return lib().is_conv_bn_backward(ctypes.byref(a), ctypes.c_void_p(int(stream)))
 
 
 def conv_bn_backward(features, weight, scale, out, grad_out, kernel, dilation=1, relu=True, want_features=True,
@@ -1705,13 +1669,6 @@ def conv_bn_stride_backward_scratch_bytes(n_images, channels_in, channels_out, r
     return int(lib().is_conv_bn_stride_backward_scratch_bytes(int(n_images), int(channels_in), int(channels_out),
                                                               int(rows_in), int(cols_in), int(kernel), int(stride),
                                                               int(dtype)))
-
-
-def conv_bn_stride_backward_ptr(stream=0, **fields):
-    """is_conv_bn_stride_backward on raw device pointers (ints): fields are those of ConvBnStrideBackwardArgs.
-    Asynchronous on `stream`; returns the return code and raises nothing (the tests check IS_EINVAL)."""
-    a = _with_reserved(ConvBnStrideBackwardArgs, fields)
-    return lib().is_conv_bn_stride_backward(ctypes.byref(a), ctypes.c_void_p(int(stream)))
 
 
 def conv_bn_stride_backward(features, weight, scale, out, grad_out, kernel, stride, dilation=1, relu=True,
@@ -1780,7 +1737,6 @@ def _conv_backward(stride, features, weight, scale, out, grad_out, kernel, dilat
         add = add.detach().contiguous()
     if not (want_features or want_weight or want_scale or want_shift or want_pre):
         raise CoreError("no gradient is asked for")
-    g = int(canary)
     with torch.cuda.device(dev):
         extents = {ext[0]: Hs, ext[1]: Ws}
         nbytes = _scratch_or_raise(conv_bn_backward_scratch_bytes if stride is None else
@@ -1788,24 +1744,13 @@ def _conv_backward(stride, features, weight, scale, out, grad_out, kernel, dilat
                                    dict(n_images=n, channels_in=cin, channels_out=cout, **extents, kernel=k,
                                         **({} if stride is None else dict(stride=st))),
                                    dtype=codes[x.dtype])
-        named, ret = {}, {}
-        ptr = {"features": None, "weight": None, "scale": None, "shift": None, "pre": None}
-        for name, want, view, dtype in (
-                ("features", want_features, (n, cin, Hs, Ws), xdt),
-                ("weight", want_weight, (cout, cin, k, k), torch.float32),
-                ("scale", want_scale, (cout,), torch.float32),
-                ("shift", want_shift, (cout,), torch.float32),
-                ("pre", want_pre, shape, x.dtype)):
-            if not want:
-                continue
-            full, t, pat = _guarded_float(int(np.prod(view)), dtype, dev, g)
-            named[name] = (full, pat)
-            ret[name] = t.view(view)
-            ptr[name] = t.data_ptr()
-        # (16 guard bytes keep the scratch 16-byte aligned; torch's allocations are)
-        gs = (g + 15) // 16 * 16
-        sfull, scratch = _guarded(nbytes, torch.uint8, dev, gs, 0xA5)
-        named["scratch"] = (sfull, np.uint8(0xA5))
+        fresh = _Fresh(dev, canary)
+        ret, ptr = fresh.rows((("features", want_features, (n, cin, Hs, Ws), xdt),
+                               ("weight", want_weight, (cout, cin, k, k), torch.float32),
+                               ("scale", want_scale, (cout,), torch.float32),
+                               ("shift", want_shift, (cout,), torch.float32),
+                               ("pre", want_pre, shape, x.dtype)))
+        scratch = fresh.scratch(nbytes)
         a = (ConvBnBackwardArgs if stride is None else ConvBnStrideBackwardArgs)(
             d_features=x.data_ptr(), dtype=codes[x.dtype], n_images=n, channels_in=cin, channels_out=cout, **extents,
             kernel=k, dilation=int(dilation), **({} if stride is None else dict(stride=st)), d_weight=w.data_ptr(),
@@ -1818,21 +1763,14 @@ def _conv_backward(stride, features, weight, scale, out, grad_out, kernel, dilat
             d_scratch=scratch.data_ptr(), scratch_bytes=nbytes)
         entry = "is_conv_bn_backward" if stride is None else "is_conv_bn_stride_backward"
         _check(getattr(lib(), entry)(ctypes.byref(a), _current_stream(dev)), entry)
-        if g:
-            ret["guards"] = _guards(named, g, gs)
+        if fresh.g:
+            ret["guards"] = fresh.guards()
     return ret
 
 
 def stem_backward_scratch_bytes(n_images, rows, cols, channels_next, dtype):
     """is_stem_backward_scratch_bytes: the scratch a call of that shape needs (0: a refused shape)."""
     return int(lib().is_stem_backward_scratch_bytes(int(n_images), int(rows), int(cols), int(channels_next), int(dtype)))
-
-
-def stem_backward_ptr(stream=0, **fields):
-    """is_stem_backward on raw device pointers (ints): fields are those of StemBackwardArgs.  Asynchronous on `stream`;
-    returns the return code and raises nothing (the tests check IS_EINVAL)."""
-    a = _with_reserved(StemBackwardArgs, fields)
-    return lib().is_stem_backward(ctypes.byref(a), ctypes.c_void_p(int(stream)))
 
 
 _STEM_BACKWARD_OUTPUTS = ("weight0", "scale0", "shift0", "weight1", "scale1", "shift1")
@@ -1921,26 +1859,15 @@ def stem_backward(image, lut, w0, w1, scale0, scale1, mid, out, grad_out=None, g
         gy, gy_stride = _frame_planes(grad_out.detach(), 16)
         source = dict(d_grad_out=gy.data_ptr(), grad_image_stride=gy_stride,
                       grad_out_dtype=HEAD_F32 if grad_out.dtype == torch.float32 else codes[dtype])
-    g = int(canary)
     with torch.cuda.device(dev):
         nbytes = _scratch_or_raise(stem_backward_scratch_bytes, dict(n_images=n, rows=H, cols=W, channels_next=cn),
                                    dtype=codes[dtype])
         views = {"weight0": (16, 3, 7, 7), "scale0": (16,), "shift0": (16,), "weight1": (16, 16, 3, 3), "scale1": (16,),
-                 "shift1": (16,), "pre0": shape, "pre1": shape}
-        wants["pre0"] = wants["pre1"] = bool(want_pre)
-        named, ret, ptr = {}, {}, {}
-        for name, view in views.items():
-            ptr[name] = None
-            if not wants[name]:
-                continue
-            full, t, pat = _guarded_float(int(np.prod(view)), dtype if name.startswith("pre") else torch.float32, dev, g)
-            named[name] = (full, pat)
-            ret[name] = t.view(view)
-            ptr[name] = t.data_ptr()
-        # (16 guard bytes keep the scratch 16-byte aligned; torch's allocations are)
-        gs = (g + 15) // 16 * 16
-        sfull, scratch = _guarded(nbytes, torch.uint8, dev, gs, 0xA5)
-        named["scratch"] = (sfull, np.uint8(0xA5))
+                 "shift1": (16,)}
+        fresh = _Fresh(dev, canary)
+        ret, ptr = fresh.rows([(name, wants[name], view, torch.float32) for name, view in views.items()] +
+                              [(name, want_pre, shape, dtype) for name in ("pre0", "pre1")])
+        scratch = fresh.scratch(nbytes)
         a = StemBackwardArgs(
             d_image=x.data_ptr(), n_images=n, rows=H, cols=W, d_lut=table.data_ptr(), dtype=codes[dtype],
             d_w0=ws[0].data_ptr(), d_w1=ws[1].data_ptr(), d_scale0=scales[0].data_ptr(), d_scale1=scales[1].data_ptr(),
@@ -1949,8 +1876,8 @@ def stem_backward(image, lut, w0, w1, scale0, scale1, mid, out, grad_out=None, g
             d_grad_shift1=ptr["shift1"], d_grad_pre1=ptr["pre1"], d_grad_pre0=ptr["pre0"], d_scratch=scratch.data_ptr(),
             scratch_bytes=nbytes)
         _check(lib().is_stem_backward(ctypes.byref(a), _current_stream(dev)), "is_stem_backward")
-        if g:
-            ret["guards"] = _guards(named, g, gs)
+        if fresh.g:
+            ret["guards"] = fresh.guards()
     return ret
 
 
@@ -1959,19 +1886,12 @@ def semantic_nll_scratch_bytes(n_images, rows8, cols8):
     return int(lib().is_semantic_nll_scratch_bytes(int(n_images), int(rows8), int(cols8)))
 
 
-def semantic_nll_ptr(stream=0, **fields):
-    """is_semantic_nll on raw device pointers (ints): fields are those of SemanticNllArgs.  Asynchronous on `stream`;
-    returns the return code and raises nothing (the tests check IS_EINVAL)."""
-    a = _with_reserved(SemanticNllArgs, fields)
-    return lib().is_semantic_nll(ctypes.byref(a), ctypes.c_void_p(int(stream)))
-
-
 def _semantic_nll(entry, args_cls, scratch_fn, scratch_more, count, target_fields, cnn_out, n_classes, ignore_index,
                   grad, check, canary):
     """The call sequence of semantic_nll and semantic_nll_up: the entry point `entry` of the C ABI with its args class
-    and the scratch of scratch_fn(n_images, rows8, cols8, **scratch_more).  count: the torch dtype and the guard
-    pattern of valid_count and bad_count.  target_fields(n, rows8, cols8, dev) checks the caller's target and returns
-    the tensor to pass and the args fields that are the entry point's own."""
+    and the scratch of scratch_fn(n_images, rows8, cols8, **scratch_more).  count: the torch dtype of valid_count
+    and bad_count.  target_fields(n, rows8, cols8, dev) checks the caller's target and returns the tensor to pass and
+    the args fields that are the entry point's own."""
     import torch
     y = cnn_out
     if not torch.is_tensor(y) or not y.is_cuda or y.dtype != torch.float32 or y.dim() != 4 or y.shape[1] < n_classes:
@@ -1980,15 +1900,11 @@ def _semantic_nll(entry, args_cls, scratch_fn, scratch_more, count, target_field
     n, _, Hs, Ws = y.shape
     y, y_stride = _frame_planes(y.detach(), n_classes)
     t, own = target_fields(n, Hs, Ws, dev)
-    g = int(canary)
-    count_dtype, pat_i = count
     with torch.cuda.device(dev):
         nbytes = _scratch_or_raise(scratch_fn, dict(n_images=n, rows8=Hs, cols8=Ws, **scratch_more))
-        named = {}
-        lfull, loss, pat_f = _guarded_float(1, torch.float32, dev, g)
-        vfull, valid = _guarded(1, count_dtype, dev, g, int(pat_i))
-        bfull, bad = _guarded(1, count_dtype, dev, g, int(pat_i))
-        named.update(loss=(lfull, pat_f), valid_count=(vfull, pat_i), bad_count=(bfull, pat_i))
+        fresh = _Fresh(dev, canary)
+        loss = fresh.new("loss", (1,), torch.float32)
+        valid, bad = fresh.new("valid_count", (1,), count), fresh.new("bad_count", (1,), count)
         gr, g_stride = None, 0
         if torch.is_tensor(grad):
             gr = grad
@@ -1998,12 +1914,8 @@ def _semantic_nll(entry, args_cls, scratch_fn, scratch_more, count, target_field
                                 "planes are contiguous")
             g_stride = gr.stride(0) if n > 1 else n_classes * Hs * Ws
         elif grad:
-            gfull, flat, _ = _guarded_float(n * n_classes * Hs * Ws, torch.float32, dev, g)
-            named["grad"] = (gfull, pat_f)
-            gr, g_stride = flat.view(n, n_classes, Hs, Ws), n_classes * Hs * Ws
-        gs = (g + 15) // 16 * 16
-        sfull, scratch = _guarded(nbytes, torch.uint8, dev, gs, 0xA5)
-        named["scratch"] = (sfull, np.uint8(0xA5))
+            gr, g_stride = fresh.new("grad", (n, n_classes, Hs, Ws), torch.float32), n_classes * Hs * Ws
+        scratch = fresh.scratch(nbytes)
         a = args_cls(d_cnn_out=y.data_ptr(), cnn_image_stride=y_stride, d_target=t.data_ptr(),
                      ignore_index=int(ignore_index), n_images=n, rows8=Hs, cols8=Ws, n_classes=int(n_classes),
                      d_loss=loss.data_ptr(), d_valid_count=valid.data_ptr(), d_bad_count=bad.data_ptr(),
@@ -2016,8 +1928,8 @@ def _semantic_nll(entry, args_cls, scratch_fn, scratch_more, count, target_field
                 raise CoreError(f"{nb} targets are neither a class in [0, {int(n_classes)}) nor ignore_index "
                                 f"{int(ignore_index)}")
         out = (loss, valid, bad, gr)
-        if g:
-            out = out + (_guards(named, g, gs),)
+        if fresh.g:
+            out = out + (fresh.guards(),)
     return out
 
 
@@ -2042,21 +1954,13 @@ def semantic_nll(cnn_out, target, n_classes, ignore_index=255, grad=True, check=
         if target.device != dev or target.dtype not in dtypes or tuple(target.shape) != (n, Hs, Ws):
             raise CoreError(f"target must be a uint8 or int32 tensor {(n, Hs, Ws)} on cnn_out's device")
         return target.contiguous(), dict(target_dtype=dtypes[target.dtype])
-    return _semantic_nll("is_semantic_nll", SemanticNllArgs, semantic_nll_scratch_bytes, {},
-                         (torch.int32, np.int32(0x5A5A5A5A)), target_fields, cnn_out, n_classes, ignore_index, grad,
-                         check, canary)
+    return _semantic_nll("is_semantic_nll", SemanticNllArgs, semantic_nll_scratch_bytes, {}, torch.int32, target_fields,
+                         cnn_out, n_classes, ignore_index, grad, check, canary)
 
 
 def semantic_nll_up_scratch_bytes(n_images, rows8, cols8, n_classes):
     """is_semantic_nll_up_scratch_bytes: the scratch a call of that shape needs (0: a refused shape)."""
     return int(lib().is_semantic_nll_up_scratch_bytes(int(n_images), int(rows8), int(cols8), int(n_classes)))
-
-
-def semantic_nll_up_ptr(stream=0, **fields):
-    """is_semantic_nll_up on raw device pointers (ints): fields are those of SemanticNllUpArgs.  Asynchronous on
-    `stream`; returns the return code and raises nothing (the tests check IS_EINVAL)."""
-    a = _with_reserved(SemanticNllUpArgs, fields)
-    return lib().is_semantic_nll_up(ctypes.byref(a), ctypes.c_void_p(int(stream)))
 
 
 def semantic_nll_up(cnn_out, target_full, n_classes, ignore_index=255, grad=True, check=True, canary=0):
@@ -2084,8 +1988,8 @@ def semantic_nll_up(cnn_out, target_full, n_classes, ignore_index=255, grad=True
             raise CoreError(f"target_full must be a uint8 tensor {(n, 8 * Hs)} x (cols >= {8 * Ws}) on cnn_out's device")
         return t.contiguous(), dict(mode=CNN_UP_DECONV, rows=8 * Hs, cols=int(t.shape[2]))
     return _semantic_nll("is_semantic_nll_up", SemanticNllUpArgs, semantic_nll_up_scratch_bytes,
-                         dict(n_classes=int(n_classes)), (torch.int64, np.int64(0x5A5A5A5A5A5A5A5A)), target_fields,
-                         cnn_out, n_classes, ignore_index, grad, check, canary)
+                         dict(n_classes=int(n_classes)), torch.int64, target_fields, cnn_out, n_classes, ignore_index,
+                         grad, check, canary)
 
 
 def cnn_label_maps_ptr(stream=0, class_to_label=None, **fields):
@@ -2139,17 +2043,10 @@ def cnn_label_maps(cnn_out, n_classes, mode="nearest", cols=None, gt_label=None,
     table = None if class_to_label is None else np.ascontiguousarray(class_to_label, np.uint8)
     if table is not None and table.size != int(n_classes):
         raise CoreError(f"class_to_label holds {table.size} values, n_classes is {int(n_classes)}")
-    g = int(canary)
-    pat8, pat64 = np.uint8(0xA5), np.int64(0x5A5A5A5A5A5A5A5A)
     with torch.cuda.device(dev):
-        named, out = {}, {}
-        ptr = {"label": None, "class8": None}
-        for name, want, shape in (("label", want_label, (n, rows, cols)), ("class8", want_class8, (n, Hs, Ws))):
-            if want:
-                full, t = _guarded(n * shape[1] * shape[2], torch.uint8, dev, g, int(pat8))
-                named[name] = (full, pat8)
-                out[name] = t.view(shape)
-                ptr[name] = t.data_ptr()
+        fresh = _Fresh(dev, canary)
+        out, ptr = fresh.rows((("label", want_label, (n, rows, cols), torch.uint8),
+                               ("class8", want_class8, (n, Hs, Ws), torch.uint8)))
         gt = conf = None
         if gt_label is not None:
             gt, nl = gt_label, int(n_labels)
@@ -2158,11 +2055,7 @@ def cnn_label_maps(cnn_out, n_classes, mode="nearest", cols=None, gt_label=None,
                 raise CoreError(f"gt_label must be a uint8 tensor {(n, rows, cols)} on cnn_out's device")
             gt = gt.contiguous()
             if confusion is None:
-                full, flat = _guarded(nl * nl, torch.int64, dev, g, int(pat64))
-                flat.zero_()   # (the table is added to)
-                conf = flat.view(nl, nl)
-                if g:
-                    named["confusion"] = (full, pat64)
+                conf = fresh.new("confusion", (nl, nl), torch.int64).zero_()   # (the table is added to)
             else:
                 conf = confusion
                 if not torch.is_tensor(conf) or conf.device != dev or conf.dtype != torch.int64 or \
@@ -2178,6 +2071,6 @@ def cnn_label_maps(cnn_out, n_classes, mode="nearest", cols=None, gt_label=None,
                          d_confusion=conf.data_ptr() if conf is not None else None)
         s = ctypes.c_void_p(int(stream)) if stream else _current_stream(dev)
         _check(lib().is_cnn_label_maps(ctypes.byref(a), s), "is_cnn_label_maps")
-        if g:
-            out["guards"] = _guards(named, g, g)
+        if fresh.g:
+            out["guards"] = fresh.guards()
     return out

@@ -10,6 +10,7 @@ import pytest
 import cnn_labels_reference as cr
 import head_reference as hr
 import helpers
+from guards import check_guards
 from instance_stixels_amd import core, evaluation, host
 
 pytestmark = pytest.mark.gpu
@@ -50,13 +51,6 @@ def _guarded_table(start):
     return full, full[GUARD: GUARD + nl * nl].view(nl, nl)
 
 
-def _check_guards(guards, names):
-    assert set(guards) == set(names)
-    for name, (front, back, pattern) in guards.items():
-        assert front.size == GUARD and back.size == GUARD
-        assert (front == pattern).all() and (back == pattern).all(), name
-
-
 def _call(x, n_classes, mode, gt=None, start=None, n_labels=NL, **kw):
     """One guarded call with every output; the table is added to `start`.  Returns numpy copies."""
     torch, dev = _torch()
@@ -66,7 +60,7 @@ def _call(x, n_classes, mode, gt=None, start=None, n_labels=NL, **kw):
     out = core.cnn_label_maps(torch.tensor(x, device=dev), n_classes, mode=mode,
                               gt_label=None if gt is None else torch.tensor(gt, device=dev), n_labels=n_labels,
                               confusion=conf, want_class8=True, canary=GUARD, **kw)
-    _check_guards(out["guards"], ("label", "class8"))
+    check_guards(out["guards"], GUARD, ("label", "class8"))
     got = dict(label=out["label"].cpu().numpy(), class8=out["class8"].cpu().numpy())
     if gt is not None:
         h = full.cpu().numpy()
@@ -173,7 +167,7 @@ def test_every_choice_of_outputs_gives_the_same_bytes(mode):
                 out = core.cnn_label_maps(d_x, 19, mode=mode, gt_label=d_gt if conf else None, confusion=table,
                                           want_label=label, want_class8=class8, canary=GUARD)
                 names = [k for k, v in (("label", label), ("class8", class8)) if v]
-                _check_guards(out["guards"], names)
+                check_guards(out["guards"], GUARD, names)
                 assert set(out) == set(names) | {"guards"} | ({"confusion"} if conf else set())
                 for k in names:
                     assert np.array_equal(out[k].cpu().numpy(), want[k]), (k, label, class8, conf)

@@ -8,6 +8,7 @@ import pytest
 
 import head_backward_reference as hbr
 import head_reference as hr
+from guards import check_guards
 from instance_stixels_amd import core, training
 
 pytestmark = pytest.mark.gpu
@@ -106,10 +107,7 @@ def test_contractions_are_the_chains_on_the_devices_dz_bitwise(s, k):
 
 @pytest.mark.parametrize("s, k", CASES, ids=IDS)
 def test_guards_are_intact(s, k):
-    guards = _run(s, k)["guards"]
-    assert set(guards) == {"features", "weight", "bias", "logits", "scratch"}
-    for name, (front, back, pattern) in guards.items():
-        assert front.size >= GUARD and (front == pattern).all() and (back == pattern).all(), name
+    check_guards(_run(s, k)["guards"], GUARD, {"features", "weight", "bias", "logits", "scratch"})
 
 
 @pytest.mark.parametrize("s, k", CASES, ids=IDS)
@@ -123,8 +121,7 @@ def test_optional_outputs_do_not_change_the_others(s, k):
         assert set(got) == names | {"guards"}, kw
         for name in names:
             assert np.array_equal(_bits(got[name]), _bits(full[name])), (kw, name)
-        for name, (front, back, pattern) in got["guards"].items():
-            assert (front == pattern).all() and (back == pattern).all(), (kw, name)
+        check_guards(got["guards"], GUARD, names | {"scratch"}, where=kw)
 
 
 @pytest.mark.parametrize("s, k", CASES, ids=IDS)
@@ -158,8 +155,7 @@ def test_half_features(s, k, dtype):
         assert np.array_equal(_bits(half[name]), _bits(wide[name])), name
     rounded = _np(torch.tensor(wide["features"]).to(getattr(torch, dtype)))
     assert np.array_equal(_bits(half["features"]), _bits(rounded))
-    for name, (front, back, pattern) in half["guards"].items():
-        assert (front == pattern).all() and (back == pattern).all(), name
+    check_guards(half["guards"], GUARD)
 
 
 # ---- is_semantic_nll ----
@@ -186,9 +182,7 @@ def test_semantic_nll(s, k, dtype):
     assert got in (w32, np.nextafter(w32, np.float32(np.inf)), np.nextafter(w32, np.float32(-np.inf))), (got, want)
     assert int(valid.item()) == V and int(nbad.item()) == 0 == bad
     assert np.array_equal(_bits(g.cpu().numpy()), _bits(grad))
-    assert set(guards) == {"loss", "valid_count", "bad_count", "grad", "scratch"}
-    for name, (front, back, pattern) in guards.items():
-        assert (front == pattern).all() and (back == pattern).all(), name
+    check_guards(guards, GUARD, {"loss", "valid_count", "bad_count", "grad", "scratch"})
     # twice the same bytes
     again = core.semantic_nll(torch.tensor(y, device=dev), tt, ncls)
     assert np.array_equal(_bits(again[0].cpu().numpy()), _bits(loss.cpu().numpy()))

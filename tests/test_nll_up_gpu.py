@@ -20,6 +20,7 @@ import pytest
 
 import cnn_labels_reference as cr
 import nll_up_reference as nr
+from guards import check_guards
 from instance_stixels_amd import core, training
 
 pytestmark = pytest.mark.gpu
@@ -76,11 +77,6 @@ def _call(y, t, ncls, **kw):
     return [o.cpu().numpy() if torch.is_tensor(o) else o for o in out]
 
 
-def _guards_intact(guards):
-    for name, (front, back, pattern) in guards.items():
-        assert (front == pattern).all() and (back == pattern).all(), name
-
-
 def _within_bounds(out, ref, what=""):
     loss, valid, bad, grad = out[:4]
     assert int(valid[0]) == ref["valid"] and int(bad[0]) == ref["bad"]
@@ -97,7 +93,7 @@ def test_loss_counts_and_gradient_within_the_bound(name):
     y, t, ncls = _inputs(name)
     ref = _reference(name)
     out = _call(y, t, ncls, canary=GUARD)
-    _guards_intact(out[4])
+    check_guards(out[4], GUARD)
     assert set(out[4]) == {"loss", "valid_count", "bad_count", "grad", "scratch"}
     _within_bounds(out, ref, name)
     assert out[3].shape == ref["grad"].shape and np.isfinite(out[3]).all()
@@ -110,7 +106,7 @@ def test_two_runs_and_the_loss_only_call_agree_bit_for_bit(name):
     for u, v in zip(a, b):
         assert np.array_equal(_bits(u), _bits(v))
     only = _call(y, t, ncls, grad=False, canary=GUARD)
-    _guards_intact(only[4])
+    check_guards(only[4], GUARD)
     assert only[3] is None and set(only[4]) == {"loss", "valid_count", "bad_count", "scratch"}
     for u, v in zip(a[:3], only[:3]):
         assert np.array_equal(_bits(u), _bits(v))
@@ -147,7 +143,7 @@ def test_ignored_pixels_at_tile_borders_in_whole_tiles_and_a_whole_frame():
     t[1] = 255
     ref = nr.evaluate(y, t, ncls)
     out = _call(y, t, ncls, canary=GUARD)
-    _guards_intact(out[4])
+    check_guards(out[4], GUARD)
     _within_bounds(out, ref, "ignored")
     assert not _bits(out[3][1]).any()                                        # +0.0f everywhere
     assert not out[3][2, :, 8:13, 32:61].any() and out[3][2, :, 7, 31].any()  # cells no valid pixel reaches
@@ -157,7 +153,7 @@ def test_no_valid_pixel_gives_nan_and_zeros_and_bad_targets_are_counted():
     torch, dev = _torch()
     y, t, ncls = _inputs("partial")
     out = _call(y, np.full_like(t, 255), ncls, canary=GUARD)
-    _guards_intact(out[4])
+    check_guards(out[4], GUARD)
     assert np.isnan(out[0][0]) and int(out[1][0]) == 0 and int(out[2][0]) == 0 and not _bits(out[3]).any()
     k = int(t[0, 0, 0])
     t2 = np.where(t == k, 19, t)                                             # 19: a channel, but no class
